@@ -21,6 +21,14 @@ tests/test.py:88), `c5` (hybrid dense + BM25 + RRF over 1M documents), `c3` (10M
 walk with the quaternary distance).  `--configs` selects them (default: all at N = 1, none at N > 1); other c4shard variants
 (`c4shard_ref` = default hyper-parameters, `c4shard_exact`, other M0 / M) on request.
 
+A plain run (`--gpus N --steps K --warmup W`) does only what `value` needs: corpus, graph build, ground truth, ef selection and the
+hold-out recall, the W + K steps, the line.  Everything else above — the extra configs, the CPU baseline and oracle parity, the
+roofline / per-dispatch figures, the single-batch, launch-size, host-API, HBM-probe and append legs, the complete record file — runs
+with `--full`.  `--dump-outputs DIR` writes what the last timed step returned (ids, scores, counts, status) as DIR/<name>.npy.
+On a machine with a GPU, build() stores the main workload's graph (`--prepare-graph-cache`, under ~/.cache/cosdata_amd); a plain run
+loads it instead of building it, after checking that it answers 256 check queries bit for bit as the built graph did (`graph` in
+the line says which; `--no-graph-cache` builds), `--full` always builds.
+
 N > 1: one process per GPU.  `--gpus N` without WORLD_SIZE in the environment starts the N ranks itself
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`); under an external
 torchrun the flag must agree with WORLD_SIZE.  Every rank owns an independent shard (ID-range partition, weak scaling:
@@ -184,6 +192,96 @@ def committed_kernel_traffic(key):
     except (OSError, ValueError, KeyError):
         pass
     return None
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """`--dump-outputs`: the last timed step's per-query arrays as out_dir/<name>.npy — integers as float64 (ids up to 2^32 stay
+    exact, the empty-slot id 0xFFFFFFFF included), floats as float32.  Above `limit` bytes in all, the same seeded sample of
+    queries is taken from every array and its row numbers go to rows.npy.  Returns {name: path}."""
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.dtype == np.int32:
+            a = a.view(np.uint32)
+        conv[name] = a.astype(np.float32 if a.dtype.kind == "f" else np.float64)
+    rows = next(iter(conv.values())).shape[0]
+    per_row = sum(a.nbytes for a in conv.values()) / max(1, rows)
+    if rows * per_row > limit:
+        keep = int((limit - 4096) // (per_row + 8))           # + 8 bytes per row of rows.npy, 4 KB for the .npy headers
+        sel = np.sort(np.random.default_rng(0).choice(rows, size=keep, replace=False))
+        conv = {name: a[sel] for name, a in conv.items()}
+        conv["rows"] = sel.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    paths = {}
+    for name, a in conv.items():
+        paths[name] = os.path.join(out_dir, name + ".npy")
+        np.save(paths[name], a)
+    return paths
+
+
+def graph_cache_dir():
+    """where build() stores the benchmark's graph for plain runs to load (one graph: storing a new one removes the old)"""
+    base = os.environ.get("XDG_CACHE_HOME") or os.path.join(os.path.expanduser("~"), ".cache")
+    return os.path.join(base, "cosdata_amd", "bench_graphs")
+
+
+GRAPH_NOT_STORED = 75   # exit status of `--prepare-graph-cache` when the graph was built but could not be written (space, permissions)
+
+
+class GraphNotStored(Exception):
+    pass
+
+
+def store_graph(ix, path, check):
+    """the index's graph as path/{root,ids_<level>,nbr_<level>,check}.npy + a `complete` marker, written under a temporary name
+    first; `check` = what the graph answers to the check queries (DenseWorkload._graph_check).  File-system failures raise
+    GraphNotStored."""
+    import shutil
+    base = os.path.dirname(path)
+    tmp = path + ".partial"
+    try:
+        os.makedirs(base, exist_ok=True)
+        for old in os.listdir(base):
+            shutil.rmtree(os.path.join(base, old), ignore_errors=True)
+        levels = ix.download_graph()
+        need = sum(ids.nbytes + nbr.nbytes for ids, nbr in levels)
+        if shutil.disk_usage(base).free < need + (4 << 30):
+            raise GraphNotStored(f"not enough free space under {base} for a {need >> 20} MB graph")
+        os.makedirs(tmp)
+        np.save(os.path.join(tmp, "root.npy"), ix.download_root())
+        np.save(os.path.join(tmp, "check.npy"), check)
+        for l, (ids, nbr) in enumerate(levels):
+            np.save(os.path.join(tmp, f"ids_{l}.npy"), ids)
+            np.save(os.path.join(tmp, f"nbr_{l}.npy"), nbr)
+        open(os.path.join(tmp, "complete"), "w").close()
+        os.rename(tmp, path)
+    except OSError as exc:
+        shutil.rmtree(tmp, ignore_errors=True)
+        raise GraphNotStored(f"{type(exc).__name__}: {exc}") from exc
+    except BaseException:
+        shutil.rmtree(tmp, ignore_errors=True)
+        raise
+
+
+def prepare_graph_cache(timeout_s=1500):
+    """build(): store the graph a plain `bench.py --gpus 1` run measures on, so that the run loads it instead of building it (about
+    50 s on one MI355X).  A child process does it; without a GPU it does nothing.  Only a graph that was built but could not be
+    written (exit status GRAPH_NOT_STORED) is tolerated — the plain run then builds it itself; any other failure of the child (an
+    error, a signal, the time limit) is raised: the device may be in no state for what runs next."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--prepare-graph-cache"]
+    try:
+        rc = subprocess.run(cmd, cwd=ROOT, timeout=timeout_s).returncode
+    except subprocess.TimeoutExpired as exc:
+        raise RuntimeError(f"bench.py --prepare-graph-cache did not finish within {timeout_s} s and was stopped") from exc
+    if rc == GRAPH_NOT_STORED:
+        print("bench.py: the benchmark graph was not stored (see above); a plain run will build it", file=sys.stderr)
+        return False
+    if rc != 0:
+        raise RuntimeError(f"bench.py --prepare-graph-cache failed with exit status {rc}")
+    return True
 
 
 def ca_mod():
@@ -466,9 +564,9 @@ class DenseWorkload:
         sims = torch.einsum("qd,qkd->qk", Qset, rows) / (Qset.norm(dim=1, keepdim=True) * rows.norm(dim=2))
         return global_topk_by_score(local_ids_global, sims, self.k)
 
-    def _ground_truth(self, ix):
+    def _ground_truth(self, ix, cross_check=True):
         """the engine's own exhaustive scan (f32-MFMA GEMM -> top-64 -> reference-order re-score), cross-checked against an
-        independent torch matmul + topk on a slice"""
+        independent torch matmul + topk on a slice (`cross_check`; it also fills self.flat)"""
         env, torch, n, d, k, rank = self.env, self.env.torch, self.n, self.d, self.k, self.env.rank
 
         def gt(Qset):
@@ -479,18 +577,23 @@ class DenseWorkload:
             return torch.from_numpy(ids.astype(np.int64) - rank * n).to(env.dev), time.perf_counter() - t
         gt_sel_local, bf_seconds = gt(self.Q_sel)
         gt_rep_local, _ = gt(self.Q_rep)
-        nx = min(self.nrq, 1024)
-        gt_torch = bruteforce_top10(torch, self.X, self.Q_sel[:nx], k)
-        agree = float((gt_sel_local[:nx].unsqueeze(2) == gt_torch.unsqueeze(1)).any(dim=2).float().mean().item())
-        self.flat = {"queries": self.nrq, "seconds": bf_seconds, "tflops_end_to_end": 2.0 * self.nrq * n * d / bf_seconds / 1e12,
-                     "agreement_with_torch_topk": agree, "torch_checked_queries": nx,
-                     "note": "cos_bruteforce_topk incl. H2D/D2H, selection and exact re-score; kernel-level MFMA rate: profiles/"}
+        if cross_check:
+            nx = min(self.nrq, 1024)
+            gt_torch = bruteforce_top10(torch, self.X, self.Q_sel[:nx], k)
+            agree = float((gt_sel_local[:nx].unsqueeze(2) == gt_torch.unsqueeze(1)).any(dim=2).float().mean().item())
+            self.flat = {"queries": self.nrq, "seconds": bf_seconds, "tflops_end_to_end": 2.0 * self.nrq * n * d / bf_seconds / 1e12,
+                         "agreement_with_torch_topk": agree, "torch_checked_queries": nx,
+                         "note": "cos_bruteforce_topk incl. H2D/D2H, selection and exact re-score; kernel-level MFMA rate: profiles/"}
         self.gt_sel = self._merge_global(self.Q_sel, gt_sel_local + rank * n) if env.dist_on else gt_sel_local
         self.gt_rep = self._merge_global(self.Q_rep, gt_rep_local + rank * n) if env.dist_on else gt_rep_local
 
     # ---- one (build filter, search filter) mode -------------------------------------------------------------------
     def run_mode(self, build_visited, visited, ef_arg="auto", ef_sweep="", cpu_seconds=12.0, single_batch=False, host_api=False,
-                 hbm_probe=False, exchange="auto", m0=64, m_upper=32, append_probe=False):
+                 hbm_probe=False, exchange="auto", m0=64, m_upper=32, append_probe=False, extras=True, keep_outputs=False, graph_cache="off"):
+        """extras=False: only what `value` needs (graph, ground truth, ef selection, hold-out recall, the timed steps); the named legs
+        above are off by their own arguments.  keep_outputs: rec["outputs"] = host copies of what the last timed step returned.
+        graph_cache: off = build the graph; use = load it from the graph cache when it holds this graph, else build; make = build,
+        store it in the cache and return None (no search)."""
         env, ca, torch = self.env, self.ca, self.env.torch
         args = env.args
         dev, rank, world, local_rank, dist, dist_on = env.dev, env.rank, env.world, env.local_rank, env.dist, env.dist_on
@@ -510,11 +613,13 @@ class DenseWorkload:
                           device=local_rank, id_base=rank * n, seed=42 + rank, visited_mode=mode_of(build_visited))
         ix.upload_vectors_device(X.data_ptr(), n, keepalive=X)
         t0 = time.time()
-        ix.build(self.build_batch)
+        graph_source = self._graph(ix, graph_cache, (build_visited, m0, m_upper, ef))
         build_s = time.time() - t0
+        if graph_source == "prepared":
+            return None
         ix.set_visited_mode(mode_of(visited))
         if self.gt_sel is None:
-            self._ground_truth(ix)
+            self._ground_truth(ix, cross_check=extras)
         gt_sel, gt_rep = self.gt_sel, self.gt_rep
 
         exchange_kind = None
@@ -574,27 +679,29 @@ class DenseWorkload:
 
         # ---- size-independent properties of the returned lists, checked at the full workload size (no oracle needed): ids in
         # this shard's range and unique per query, scores non-increasing, every score = the exact f32 cosine of the row it names
-        m = min(B, nrq, 2048)
-        ix.batch_search_device(self.Q_rep[:m].data_ptr(), m, k, o_ids[0].data_ptr(), o_sc[0].data_ptr(), o_cnt[0].data_ptr(), o_st[0].data_ptr(),
-                               streams[0].cuda_stream)
-        streams[0].synchronize()
-        cnt = o_cnt[0][:m].to(torch.int64)
-        valid = torch.arange(k, device=dev)[None, :] < cnt[:, None]
-        gid = o_ids[0][:m].to(torch.int64) & 0xFFFFFFFF
-        loc = gid - rank * n
-        in_range = bool(((loc >= 0) & (loc < n))[valid].all().item())
-        srt = torch.where(valid, gid, -1 - torch.arange(k, device=dev)[None, :].expand(m, k)).sort(dim=1).values
-        unique = bool((srt[:, 1:] != srt[:, :-1]).all().item())
-        sc = o_sc[0][:m]
-        both = valid[:, 1:] & valid[:, :-1]
-        sorted_desc = bool((sc[:, :-1] >= sc[:, 1:])[both].all().item())
-        rows = X[loc.clamp(0, n - 1)].double()
-        qd = self.Q_rep[:m].double()
-        exact = torch.einsum("qd,qkd->qk", qd, rows) / (qd.norm(dim=1, keepdim=True) * rows.norm(dim=2))
-        max_err = float((sc.double() - exact).abs()[valid].max().item())
-        props = {"queries": m, "ids_in_shard_range": in_range, "ids_unique": unique, "scores_sorted_desc": sorted_desc,
-                 "max_abs_err_vs_f64_cosine": max_err, "full_lists": bool((cnt == k).all().item())}
-        del rows, qd, exact
+        props = None
+        if extras:
+            m = min(B, nrq, 2048)
+            ix.batch_search_device(self.Q_rep[:m].data_ptr(), m, k, o_ids[0].data_ptr(), o_sc[0].data_ptr(), o_cnt[0].data_ptr(), o_st[0].data_ptr(),
+                                   streams[0].cuda_stream)
+            streams[0].synchronize()
+            cnt = o_cnt[0][:m].to(torch.int64)
+            valid = torch.arange(k, device=dev)[None, :] < cnt[:, None]
+            gid = o_ids[0][:m].to(torch.int64) & 0xFFFFFFFF
+            loc = gid - rank * n
+            in_range = bool(((loc >= 0) & (loc < n))[valid].all().item())
+            srt = torch.where(valid, gid, -1 - torch.arange(k, device=dev)[None, :].expand(m, k)).sort(dim=1).values
+            unique = bool((srt[:, 1:] != srt[:, :-1]).all().item())
+            sc = o_sc[0][:m]
+            both = valid[:, 1:] & valid[:, :-1]
+            sorted_desc = bool((sc[:, :-1] >= sc[:, 1:])[both].all().item())
+            rows = X[loc.clamp(0, n - 1)].double()
+            qd = self.Q_rep[:m].double()
+            exact = torch.einsum("qd,qkd->qk", qd, rows) / (qd.norm(dim=1, keepdim=True) * rows.norm(dim=2))
+            max_err = float((sc.double() - exact).abs()[valid].max().item())
+            props = {"queries": m, "ids_in_shard_range": in_range, "ids_unique": unique, "scores_sorted_desc": sorted_desc,
+                     "max_abs_err_vs_f64_cosine": max_err, "full_lists": bool((cnt == k).all().item())}
+            del rows, qd, exact
 
         # ---- warmup + timed region: EXACTLY n_launch steps (launches) ---------------------------------------
         def timed_run():
@@ -639,6 +746,24 @@ class DenseWorkload:
                     "rounds": float(np.mean([c[3] for c in cnts])), "split": sp}
 
         tr = timed_run()
+        outputs = None
+        if keep_outputs:   # what the caller of the last timed step received, before any later leg reuses its stream's buffers
+            s_last = (n_warm + n_launch - 1) % S
+            got = {"ids": m_ids[s_last], "scores": m_sc[s_last], "counts": m_cnt[s_last]} if dist_on else \
+                  {"ids": o_ids[s_last], "scores": o_sc[s_last], "counts": o_cnt[s_last], "status": o_st[s_last]}
+            outputs = {name: t.cpu().numpy() for name, t in got.items()}
+        elapsed = tr["elapsed"]
+        merged_qps = n_launch * B / elapsed        # answers over the global (world x n) corpus per second
+        if not extras:
+            if shardset is not None:
+                shardset.close()
+            rec = {"value": merged_qps, "elapsed": elapsed, "steps": n_launch, "warmup": n_warm, "ef": ef, "ef_table": ef_table,
+                   "recall": (recall, recall_se, recall_lo), "status_bad": status_bad, "props": props, "sweep": [], "size_sweep": [], "serial": None,
+                   "host_api": None, "cpu": None, "parity": None, "append": None, "build_s": build_s, "graph_source": graph_source,
+                   "seconds": time.time() - t_setup, "exchange_kind": exchange_kind, "config": self._config(ef, ef_arg, m0, m_upper, build_visited, visited, exchange_kind),
+                   "roofline": None, "outputs": outputs}
+            del ix
+            return rec
         # the same step three more times, ONE launch at a time: the durations of its dispatches without a neighbouring launch's
         # kernels on the chip (what a serialized rocprofv3 trace shows); the timed region's own events stretch a short kernel that
         # shares the chip with another stream's walk (the level-table GEMM: 0.4 ms alone, ~3 ms under a walk)
@@ -652,8 +777,6 @@ class DenseWorkload:
         sp_alone = {k_: float(np.mean([getattr(x, k_) for x in alone])) for k_ in ("table_ms", "upper_ms", "sort_ms", "lower_ms")}
         # the locality order of big launches (cos_index_set_walk_order: from WALK_ORDER_DEFAULT_MIN_B queries, ef <= 256)
         cuts = ix.walk_order_cuts() if B >= ca.HNSWIndex.WALK_ORDER_DEFAULT_MIN_B and ef <= 256 else []
-        elapsed = tr["elapsed"]
-        merged_qps = n_launch * B / elapsed        # answers over the global (world x n) corpus per second
         # Algorithmic bytes of one step's walk AS THIS DESIGN EVALUATES IT (SURVEY.md 8d's per-unit figures): an evaluation that gathers
         # and dots a code row reads bytes_vec + 4; an evaluation served by the level table (cos_index_set_walk_table) reads the 4-byte
         # similarity the table GEMM left — that GEMM is a dispatch of its own with its own (MFMA) roofline below; an expansion reads
@@ -947,19 +1070,9 @@ class DenseWorkload:
         rec = {
             "value": merged_qps, "elapsed": elapsed, "steps": n_launch, "warmup": n_warm, "ef": ef, "ef_table": ef_table,
             "recall": (recall, recall_se, recall_lo), "status_bad": status_bad, "props": props, "sweep": sweep, "size_sweep": size_sweep, "serial": serial,
-            "host_api": host, "cpu": cpu, "parity": parity, "append": append, "build_s": build_s, "seconds": time.time() - t_setup, "exchange_kind": exchange_kind,
-            "config": {"workload": (value_workload(world) if (self.name, m0, m_upper, visited) == (MAIN_WORKLOAD, MAIN_M0, MAIN_M, "ref")
-                                    else self.name + ": " + self.desc),
-                       "n_gpus": world, "standard_size": self.standard_size, "vectors_per_gpu": n, "dim": d,
-                       "step": f"one coalesced launch = {self.C} client batches x {Bc} queries = {B} queries through quantize -> walk -> rerank -> top-k",
-                       "query_batch": Bc, "batches_per_launch": self.C, "queries_per_step": B, "launches_in_flight": S, "top_k": k, "ef_search": ef,
-                       "ef_policy": ("smallest ef whose recall@10 on the selection query set is >= %.2f with 95%% confidence; recall_at_10 is "
-                                     "measured on a disjoint hold-out set" % args.recall_target) if ef_arg == "auto" else "fixed",
-                       "M": m_upper, "M0": m0, "num_layers": 9, "ef_construction": self.ef_construction, "build_visited": build_visited,
-                       "storage": f"u8 (quantization {self.quantization}, values_range {self.values_range})",
-                       "visited": "reference PerformantFixedSet (ID parity mode)" if visited == "ref" else "exact visited set (recall mode)",
-                       "parallelism": f"id-range shards x{world}" + (" + RCCL all-gather top-k merge" if world > 1 else ""),
-                       "exchange": exchange_kind, "corpus": self.corpus_desc},
+            "host_api": host, "cpu": cpu, "parity": parity, "append": append, "build_s": build_s, "graph_source": graph_source, "seconds": time.time() - t_setup,
+            "exchange_kind": exchange_kind,
+            "config": self._config(ef, ef_arg, m0, m_upper, build_visited, visited, exchange_kind), "outputs": outputs,
             "roofline": {"bound": "hbm", "achieved": kernel_gbps, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": kernel_gbps / HBM_PEAK_GBPS,
                          "step_frac": avg_bytes / (elapsed / n_launch) / 1e9 / HBM_PEAK_GBPS,   # the same bytes over the whole step (GEMM, sort, rerank and what does not overlap included)
                          "traffic": traffic, "traffic_GBps": (traffic / (kern_ms * 1e-3) / 1e9) if traffic else None,
@@ -987,6 +1100,66 @@ class DenseWorkload:
         }
         del ix
         return rec
+
+    def _graph_key(self, params):
+        """what the graph depends on: the library binary (its builder), the index and build parameters, the corpus (sampled)"""
+        import hashlib
+        import torch
+        h = hashlib.sha256()
+        with open(self.ca._lib.SO_PATH, "rb") as fh:
+            h.update(fh.read())
+        h.update(self.X_all[::max(1, self.X_all.shape[0] // 4096)].cpu().numpy().tobytes())
+        h.update(repr((self.name, self.n, self.d, self.env.rank, self.env.world, self.ef_construction, self.build_batch, self.quantization,
+                       self.values_range, self.append_rows, params, torch.__version__)).encode())
+        return h.hexdigest()[:32]
+
+    def _graph(self, ix, mode, params):
+        """the index's graph: built (mode off), loaded from the graph cache when it holds this graph (use), or built and stored
+        there (make: what build() prepares on a machine with a GPU, so that a plain run loads the graph instead of building it)"""
+        path = os.path.join(graph_cache_dir(), self._graph_key(params)) if mode != "off" else None
+        if mode == "use" and path and os.path.exists(os.path.join(path, "complete")):
+            root = np.load(os.path.join(path, "root.npy"))
+            levels = [(np.load(os.path.join(path, f"ids_{l}.npy")), np.load(os.path.join(path, f"nbr_{l}.npy"), mmap_mode="r"))
+                      for l in range(ix.hnsw_params.num_layers + 1)]
+            ix.upload_graph(levels, root)
+            del levels
+            if np.array_equal(self._graph_check(ix), np.load(os.path.join(path, "check.npy"))):
+                return "loaded"
+            print(f"bench.py: the graph stored under {path} does not answer its check queries as the built one did: building it",
+                  file=sys.stderr)
+            ix.build(self.build_batch)
+            return "built (the stored graph failed its check)"
+        ix.build(self.build_batch)
+        if mode != "make":
+            return "built"
+        store_graph(ix, path, self._graph_check(ix))
+        return "prepared"
+
+    def _graph_check(self, ix):
+        """ids, score bits and counts of 256 corpus rows searched on the graph (the device path the recall sets take, the index's
+        ef): a loaded graph must reproduce them bit for bit"""
+        q = self.X[::max(1, self.n // 256)][:256].contiguous()
+        m, st = q.shape[0], self.streams[0]
+        ix.batch_search_device(q.data_ptr(), m, self.k, self.o_ids[0].data_ptr(), self.o_sc[0].data_ptr(), self.o_cnt[0].data_ptr(),
+                               self.o_st[0].data_ptr(), st.cuda_stream)
+        st.synchronize()
+        return np.concatenate([t[:m].cpu().numpy().view(np.uint32).ravel() for t in (self.o_ids[0], self.o_sc[0], self.o_cnt[0])])
+
+    def _config(self, ef, ef_arg, m0, m_upper, build_visited, visited, exchange_kind):
+        """the `config` block of a mode's record"""
+        world, n, d, k, B, Bc, S = self.env.world, self.n, self.d, self.k, self.B, self.Bc, self.S
+        return {"workload": (value_workload(world) if (self.name, m0, m_upper, visited) == (MAIN_WORKLOAD, MAIN_M0, MAIN_M, "ref")
+                             else self.name + ": " + self.desc),
+                "n_gpus": world, "standard_size": self.standard_size, "vectors_per_gpu": n, "dim": d,
+                "step": f"one coalesced launch = {self.C} client batches x {Bc} queries = {B} queries through quantize -> walk -> rerank -> top-k",
+                "query_batch": Bc, "batches_per_launch": self.C, "queries_per_step": B, "launches_in_flight": S, "top_k": k, "ef_search": ef,
+                "ef_policy": ("smallest ef whose recall@10 on the selection query set is >= %.2f with 95%% confidence; recall_at_10 is "
+                              "measured on a disjoint hold-out set" % self.env.args.recall_target) if ef_arg == "auto" else "fixed",
+                "M": m_upper, "M0": m0, "num_layers": 9, "ef_construction": self.ef_construction, "build_visited": build_visited,
+                "storage": f"u8 (quantization {self.quantization}, values_range {self.values_range})",
+                "visited": "reference PerformantFixedSet (ID parity mode)" if visited == "ref" else "exact visited set (recall mode)",
+                "parallelism": f"id-range shards x{world}" + (" + RCCL all-gather top-k merge" if world > 1 else ""),
+                "exchange": exchange_kind, "corpus": self.corpus_desc}
 
     def _cpu_baseline_and_parity(self, ix, ef, visited, cpu_seconds, m0=64, m=32):
         """the oracle on all usable host cores over a bounded sample of the SAME queries on the SAME graph; the same sample is the
@@ -1174,8 +1347,9 @@ class Emitter:
     """owns the saved stdout descriptor; prints the ONE JSON line exactly once — at the normal end, or from the deadline timer with
     what has been measured so far (then the process exits hard: a hung HIP / RCCL call cannot be interrupted from Python)"""
 
-    def __init__(self, json_fd, rank, deadline_s):
+    def __init__(self, json_fd, rank, deadline_s, full_record=True):
         self.fd, self.rank, self.lock, self.done, self.out = json_fd, rank, threading.Lock(), False, None
+        self.full_record = full_record       # False (a plain run): the line only, no record file
         self.timer = None
         if deadline_s > 0:
             self.timer = threading.Timer(deadline_s, self._deadline)
@@ -1185,6 +1359,9 @@ class Emitter:
     def _write(self):
         if self.rank == 0 and self.out is not None:
             full = rounded(self.out)
+            if not self.full_record:
+                os.write(self.fd, (json.dumps(slim_line(full)) + "\n").encode())
+                return
             # the complete record (every per-launch figure, ef tables, notes) goes to a file next to the other run artefacts; the ONE
             # line on stdout carries the same results without the prose, so that it stays a few KB whatever reads it
             path = None
@@ -1279,6 +1456,15 @@ def main():
     ap.add_argument("--allow-shared-devices", action="store_true", help="--single-process: place several shards on one device if fewer "
                     "than --gpus are visible (code-path check on a 1-GPU box; NOT a scaling number)")
     ap.add_argument("--launcher-selftest", action="store_true", help="CPU/gloo check of the launch + rank plumbing, no search")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond `value`: the extra configs (--configs), CPU "
+                    "baseline + oracle parity, roofline and per-dispatch figures, single-batch / launch-size / host-API / HBM-probe / append legs, "
+                    "ef sweep, torch cross-check of the ground truth; writes the complete record file.  Off: a plain run times `value` only")
+    ap.add_argument("--no-graph-cache", action="store_true", help="build the graph even when build() stored it (a plain run loads a stored graph; "
+                    "--full always builds)")
+    ap.add_argument("--prepare-graph-cache", action="store_true", help="build the main workload's graph and store it for plain runs (build() runs "
+                    "this on a machine with a GPU); no search")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write what the last timed step returned (ids, scores, counts, status; "
+                    "merged answers at N > 1) as DIR/<name>.npy in float64 / float32")
     args = ap.parse_args()
 
     if args.gpus < 1:
@@ -1288,13 +1474,20 @@ def main():
         sys.exit(launch_ranks(args, sys.argv[1:]))
     if env_world is not None and int(env_world) != args.gpus and not args.single_process:
         raise SystemExit(f"bench.py: --gpus {args.gpus} disagrees with WORLD_SIZE={env_world} set by the launcher; refusing to report either")
+    if not args.full and (args.configs not in ("auto", "none", "") or args.ef_sweep not in ("auto", "")):
+        raise SystemExit("bench.py: --configs / --ef-sweep select measurements of a --full run; add --full")
     if args.launcher_selftest:
         return launcher_selftest(args)
     if args.single_process:
+        if args.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs is not supported with --single-process")
         from scripts import bench_single_process
         return bench_single_process.run(args, METRIC)
 
     import torch  # noqa: F401  (imported before the HIP library: one runtime)
+    if args.prepare_graph_cache and not torch.cuda.is_available():
+        print("bench.py: no GPU, no graph to prepare", file=sys.stderr)
+        return
     env = Env(args)
     rank, world = env.rank, env.world
     # stdout carries exactly ONE JSON line: libraries that print banners through C stdio (RCCL prints its version block on
@@ -1302,8 +1495,9 @@ def main():
     sys.stdout.flush()
     json_fd = os.dup(1)
     os.dup2(2, 1)
-    emitter = Emitter(json_fd, rank, args.deadline_seconds)
+    emitter = Emitter(json_fd, rank, args.deadline_seconds, full_record=args.full)
     t_setup = time.time()
+    full = args.full
 
     # ---- the main workload: `value` -------------------------------------------------------------------------------
     C2_SWEEP = "256,exact:32,exact:64"
@@ -1311,13 +1505,29 @@ def main():
     m0 = args.m0 or (MAIN_M0 if is_shard else 64)
     mm = args.m or (MAIN_M if is_shard else 32)
     main_sweep = ("" if is_shard else C2_SWEEP) if args.ef_sweep == "auto" else args.ef_sweep
+    if not full:
+        main_sweep = ""
+    # (the append probe's rows are drawn in a plain run too: they come from the corpus' own generator stream, and the shard's last
+    # chunk of rows depends on how many rows that stream draws in all)
     wl = DenseWorkload(env, args.workload, n_override=args.n, ef_construction=args.ef_construction, quantization=args.quantization,
                        build_batch=args.build_batch, append_rows=0 if (args.no_append_probe or env.world > 1) else args.append_rows)
+    if args.prepare_graph_cache:
+        try:
+            wl.run_mode(args.build_visited, args.visited, ef_arg=args.ef, m0=m0, m_upper=mm, extras=False, graph_cache="make")
+        except GraphNotStored as exc:
+            print(f"bench.py: graph not stored: {exc}", file=sys.stderr)
+            sys.exit(GRAPH_NOT_STORED)
+        print(f"bench.py: graph stored under {graph_cache_dir()}", file=sys.stderr)
+        return
     # the host-buffer legs (cos_search_batch from 1-256 host threads: BASELINE configs[1]'s "query-batch=256") belong to c2, as a main
     # workload or as the record under `configs`
-    rec = wl.run_mode(args.build_visited, args.visited, ef_arg=args.ef, ef_sweep=main_sweep, cpu_seconds=args.cpu_seconds,
-                      single_batch=True, host_api=(not args.no_host_api) and not is_shard, hbm_probe=not args.no_hbm_probe, exchange=args.exchange,
-                      m0=m0, m_upper=mm, append_probe=not args.no_append_probe)
+    rec = wl.run_mode(args.build_visited, args.visited, ef_arg=args.ef, ef_sweep=main_sweep, cpu_seconds=args.cpu_seconds if full else 0.0,
+                      single_batch=full, host_api=full and (not args.no_host_api) and not is_shard, hbm_probe=full and not args.no_hbm_probe,
+                      exchange=args.exchange, m0=m0, m_upper=mm, append_probe=full and not args.no_append_probe, extras=full,
+                      keep_outputs=bool(args.dump_outputs), graph_cache="off" if (full or args.no_graph_cache) else "use")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, rec["outputs"])
+    rec.pop("outputs", None)
     flat = wl.flat
     n = wl.n
     c4 = wl if is_shard else None      # the 51 GB shard, its ground truth and the oracle's quantized copy serve the 8-shard record too
@@ -1345,8 +1555,10 @@ def main():
         "value_note": ("n_gpus == 1: value = queries/s over the whole corpus" if world == 1 else
                        "value = merged answers/s over the GLOBAL corpus (n_gpus x vectors_per_gpu; every query is searched on every "
                        "shard, then all-gathered and merged); shard_searches_per_s = value x n_gpus is the shard-level work"),
-        **serial_block(rec),
-        "ef_selection": rec["ef_table"], "ef_sweep": rec["sweep"], "launch_size_sweep": rec["size_sweep"], "build_seconds": rec["build_s"],
+        **(serial_block(rec) if rec["serial"] else {}),
+        "full": full,
+        "ef_selection": rec["ef_table"], "ef_sweep": rec["sweep"], "launch_size_sweep": rec["size_sweep"],
+        "build_seconds": rec["build_s"] if rec["graph_source"].startswith("built") else None, "graph": rec["graph_source"], "graph_seconds": rec["build_s"],
         "setup_seconds": time.time() - t_setup,
         "roofline": rec["roofline"],
         "flat_scan_ground_truth": flat, "result_properties": rec["props"], "cpu_baseline": rec["cpu"], "parity_vs_oracle": rec["parity"],
@@ -1363,7 +1575,7 @@ def main():
     emitter.out = out
 
     # ---- the remaining BASELINE configs, each to the same parity + roofline + cpu_baseline bar ------------------------
-    todo = resolve_configs(args.configs, world, args.workload)
+    todo = resolve_configs(args.configs, world, args.workload) if full else []
     scale = args.config_scale
     for name in todo:
         t_c = time.time()

@@ -14,6 +14,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "engine_internal.h"
@@ -401,6 +402,71 @@ static int32_t push_level_to_device(cos_index *ix, u32 level) {
     return COS_OK;
 }
 
+// Level 0 holds every vector row in ascending order, root last (cos_index_upload_graph_level checks it), so a neighbour's node index
+// IS its vector row: no search.  At 10M+ vectors the level is billions of slots, so host threads convert the caller's ids straight
+// into two pinned staging chunks that are copied while the next chunk converts; the host id copy is left to materialize_host_level,
+// as after a device build.
+static int32_t push_level0_to_device(cos_index *ix, const u32 *nbr) {
+    LevelHost &L = ix->lv[0];
+    const u32 n = (u32)L.node_ids.size(), M = L.M;
+    const size_t slots = (size_t)n * M, chunk = (size_t)32 << 20;
+    struct Staging {
+        u32 *buf[2] = {nullptr, nullptr};
+        hipEvent_t done[2] = {nullptr, nullptr};
+        ~Staging() {
+            for (int b = 0; b < 2; b++) {
+                if (done[b]) (void)hipEventSynchronize(done[b]), (void)hipEventDestroy(done[b]);
+                if (buf[b]) (void)hipHostFree(buf[b]);
+            }
+        }
+    } stg;
+    if (L.d_adj_vec) (void)hipFree(L.d_adj_vec);
+    L.d_adj_vec = nullptr;
+    HIP_TRY(hipMalloc(&L.d_adj_vec, slots * 4));
+    for (int b = 0; b < 2; b++) {
+        HIP_TRY(hipHostMalloc((void **)&stg.buf[b], std::min(chunk, slots) * 4, hipHostMallocDefault));
+        HIP_TRY(hipEventCreateWithFlags(&stg.done[b], hipEventDisableTiming));
+    }
+    const u32 nt = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+    for (size_t c0 = 0, k = 0; c0 < slots; c0 += chunk, k++) {
+        const size_t m = std::min(chunk, slots - c0);
+        u32 *out = stg.buf[k & 1];
+        if (k >= 2) HIP_TRY(hipEventSynchronize(stg.done[k & 1])); // the copy that last read this buffer has finished
+        std::vector<int> bad(nt, 0);
+        auto convert = [&](u32 t) {
+            for (size_t s = m * t / nt, e = m * (t + 1) / nt; s < e; s++) {
+                const u32 id = nbr[c0 + s];
+                if (id == COS_SLOT_EMPTY) { out[s] = ROW_EMPTY; continue; }
+                if (id != COS_ROOT_ID && (id % ix->id_stride != 0 || id / ix->id_stride >= ix->n)) { bad[t] = 1; return; }
+                out[s] = row_of(ix, id);
+            }
+        };
+        std::vector<std::thread> th;
+        u32 started = 0;
+        try {
+            th.reserve(nt);
+            for (; started < nt; started++) th.emplace_back(convert, started);
+        } catch (...) { // no thread to be had (no exception leaves the C ABI): this thread converts the shares nobody took
+        }
+        for (u32 t = started; t < nt; t++) convert(t);
+        for (auto &x : th) x.join();
+        for (int b : bad)
+            if (b) return cos_fail(COS_ERR_INVALID, "level 0: a neighbour id is not a node of this level");
+        HIP_TRY(hipMemcpyAsync(L.d_adj_vec + c0, out, m * 4, hipMemcpyHostToDevice, ix->own_stream));
+        HIP_TRY(hipEventRecord(stg.done[k & 1], ix->own_stream));
+    }
+    HIP_TRY(hipStreamSynchronize(ix->own_stream));
+    L.nbr_ids.clear();
+    L.nbr_ids.shrink_to_fit();
+    L.n = n;
+    L.host_valid = false;
+    ix->order_rank_valid = false;
+    ix->level_table_valid = false;
+    ix->adj_mag_valid = false;
+    ix->link.release();
+    return COS_OK;
+}
+
 // child links: same id one level down (vector_store.rs:897-903)
 static int32_t resolve_children(cos_index *ix, u32 level) {
     if (level == 0 || level > ix->p.num_layers) return COS_OK;
@@ -435,8 +501,12 @@ extern "C" int32_t cos_index_upload_graph_level(cos_index *ix, uint32_t level, u
     if (level == 0 && n_nodes != ix->n + 1) return cos_fail(COS_ERR_INVALID, "level 0 must hold every vector plus the root (%u nodes, expected %u)", n_nodes, ix->n + 1);
     LevelHost &L = ix->lv[level];
     L.node_ids.assign(node_ids, node_ids + n_nodes);
-    L.nbr_ids.assign(nbr_ids, nbr_ids + (size_t)n_nodes * L.M);
-    rc = push_level_to_device(ix, level);
+    if (level == 0) {
+        rc = push_level0_to_device(ix, nbr_ids);
+    } else {
+        L.nbr_ids.assign(nbr_ids, nbr_ids + (size_t)n_nodes * L.M);
+        rc = push_level_to_device(ix, level);
+    }
     if (rc) { free_level(L); return rc; }
     rc = resolve_children(ix, level);
     if (rc == COS_OK) rc = resolve_children(ix, level + 1);

@@ -119,3 +119,65 @@ def test_value_at_query_batch_256_takes_the_best_setting_per_caller_count_and_sk
     assert v["by_callers"]["64"] == {"qps": 3.2e6, "coalescing_max_queries": 8192} and v["by_callers"]["128"]["qps"] == 3.9e6
     assert v["min_over_caller_counts"] == 3.2e6
     assert bench.value_at_batch_256(None) is None and bench.value_at_batch_256({"concurrent_256_query_callers": []}) is None
+
+
+def test_dump_outputs_writes_exact_float_arrays(tmp_path):
+    """--dump-outputs: integer outputs as float64 (the empty-slot id 0xFFFFFFFF stays exact), scores as float32, one file per array"""
+    import bench
+    ids = np.array([[7, 12_499_999, -1], [0, 3, 5]], dtype=np.int32)
+    sc = np.array([[0.9, 0.5, -np.inf], [1.0, 0.25, 0.125]], dtype=np.float32)
+    cnt = np.array([2, 3], dtype=np.int32)
+    paths = bench.dump_outputs(str(tmp_path / "out"), {"ids": ids, "scores": sc, "counts": cnt})
+    assert sorted(os.path.basename(p) for p in paths.values()) == ["counts.npy", "ids.npy", "scores.npy"]
+    i, s, c = (np.load(paths[n]) for n in ("ids", "scores", "counts"))
+    assert i.dtype == np.float64 and s.dtype == np.float32 and c.dtype == np.float64
+    assert i[0, 2] == 0xFFFFFFFF and i[0, 1] == 12_499_999 and np.array_equal(i[1], [0, 3, 5])
+    assert np.array_equal(s.view(np.uint32), sc.view(np.uint32)) and np.array_equal(c, [2, 3])
+
+
+def test_dump_outputs_samples_the_same_rows_of_every_array_under_the_size_limit(tmp_path):
+    import bench
+    rows = 5000
+    arrays = {"ids": np.arange(rows * 10, dtype=np.int32).reshape(rows, 10), "scores": np.random.default_rng(1).random((rows, 10), dtype=np.float32),
+              "counts": np.full(rows, 10, np.int32)}
+    limit = 200_000
+    a = bench.dump_outputs(str(tmp_path / "a"), arrays, limit=limit)
+    b = bench.dump_outputs(str(tmp_path / "b"), arrays, limit=limit)
+    assert sum(os.path.getsize(p) for p in a.values()) <= limit
+    sel = np.load(a["rows"])
+    assert 0 < sel.size < rows and np.array_equal(sel, np.load(b["rows"])) and np.all(np.diff(sel) > 0)   # seeded: the same sample every run
+    k = sel.astype(np.int64)
+    assert np.array_equal(np.load(a["ids"]), arrays["ids"][k].astype(np.float64))
+    assert np.array_equal(np.load(a["scores"]), arrays["scores"][k]) and np.load(a["counts"]).shape == (sel.size,)
+
+
+def test_extra_measurements_need_full():
+    """a plain run times `value` only: asking it for an extra config or an ef sweep is refused before any device work"""
+    import subprocess
+    for extra in (["--configs", "c2"], ["--ef-sweep", "256"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + extra, capture_output=True, text=True, timeout=120, cwd=ROOT)
+        assert r.returncode != 0 and "--full" in r.stderr, (extra, r.stderr[-400:])
+
+
+def test_prepare_graph_cache_tolerates_only_a_graph_that_was_not_stored(monkeypatch):
+    """build() runs the graph-preparing child: a graph it could not write is tolerated (the plain run builds it); an error, a
+    signal or the time limit is raised, so that nothing else is started on a device that may have faulted"""
+    import subprocess
+    import pytest
+    import bench
+    outcome = {}
+
+    def fake_run(cmd, **kw):
+        assert cmd[-1] == "--prepare-graph-cache" and kw["timeout"] > 0
+        if outcome["rc"] == "timeout":
+            raise subprocess.TimeoutExpired(cmd, kw["timeout"])
+        return subprocess.CompletedProcess(cmd, outcome["rc"])
+    monkeypatch.setattr(bench.subprocess, "run", fake_run)
+    outcome["rc"] = 0
+    assert bench.prepare_graph_cache() is True
+    outcome["rc"] = bench.GRAPH_NOT_STORED
+    assert bench.prepare_graph_cache() is False
+    for rc in (1, 3, -6, -11, -9, "timeout"):
+        outcome["rc"] = rc
+        with pytest.raises(RuntimeError):
+            bench.prepare_graph_cache()
