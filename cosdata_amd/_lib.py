@@ -78,6 +78,13 @@ class CosFlatStats(C.Structure):
     _fields_ = [("gemm_ms", C.c_float), ("gemm_launches", C.c_uint32), ("int8_ops", C.c_double), ("code_bytes", C.c_double)]
 
 
+class CosBM25Stats(C.Structure):
+    """cos_bm25_index_stats: what a BM25 handle holds (postings count tombstones too)"""
+    _fields_ = [("struct_size", C.c_uint32), ("documents_count", C.c_uint32), ("n_terms", C.c_uint32), ("largest_doc_id", C.c_uint32),
+                ("dir_rows", C.c_uint32), ("dir_tiles", C.c_uint32), ("reserved", C.c_uint32),
+                ("postings", C.c_uint64), ("tombstones", C.c_uint64), ("device_bytes", C.c_uint64)]
+
+
 def build(force: bool = False, verbose: bool = False) -> str:
     """Compile every HIP source for gfx950 into cosdata_amd/libcosdata_hip.so (in-tree)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
@@ -104,6 +111,7 @@ ABI_SYMBOLS = [
     "cos_search_batch", "cos_search_batch_device", "cos_ann_search_batch", "cos_index_set_coalescing", "cos_index_coalescing_stats", "cos_index_set_ef_search",
     "cos_index_set_visited_mode", "cos_index_set_latency_mode", "cos_index_set_latency_waves", "cos_index_set_walk_order", "cos_index_walk_order_cuts", "cos_index_set_walk_table", "cos_index_walk_table_info", "cos_index_last_walk_split", "cos_index_enable_timing", "cos_index_last_stats", "cos_index_timing_summary", "cos_quantize_batch",
     "cos_code_bytes", "cos_sample_values_range", "cos_distance_batch", "cos_bruteforce_topk", "cos_flat_search_batch", "cos_bm25_create", "cos_bm25_destroy",
+    "cos_bm25_insert", "cos_bm25_delete", "cos_bm25_stats", "cos_bm25_download",
     "cos_bm25_search_batch", "cos_bm25_search_batch_device", "cos_rrf_fuse_batch", "cos_hybrid_search_batch", "cos_text_process", "cos_text_count_tokens", "cos_bm25_term_frequency", "cos_xxhash32", "cos_stem_english", "cos_sparse_create", "cos_sparse_build_csr", "cos_sparse_create_from_vectors", "cos_sparse_destroy", "cos_sparse_search_batch", "cos_sparse_last_stats", "cos_sparse_layout", "cos_merge_topk_device", "cos_merge_topk_packed_device", "cos_hbm_probe",
     "cos_shardset_unique_id", "cos_shardset_create", "cos_shardset_destroy", "cos_shardset_search_batch", "cos_shardset_exchange_device",
     "cos_tuning_set", "cos_tuning_clear", "cos_tuning_get",
@@ -177,6 +185,10 @@ def lib():
         "cos_flat_search_batch": [vp, vp, u32, u32, vp, vp, vp, C.POINTER(CosFlatStats)],
         "cos_bm25_create": [i32, vp, vp, u32, vp, vp, u32, C.POINTER(vp)],
         "cos_bm25_destroy": [vp],
+        "cos_bm25_insert": [vp, vp, vp, u32, vp, vp],
+        "cos_bm25_delete": [vp, vp, vp, u32, vp],
+        "cos_bm25_stats": [vp, C.POINTER(CosBM25Stats)],
+        "cos_bm25_download": [vp, C.POINTER(u32), C.POINTER(C.c_uint64), vp, vp, vp, vp, vp],
         "cos_bm25_search_batch": [vp, vp, vp, u32, u32, vp, vp, vp],
         "cos_bm25_search_batch_device": [vp, vp, vp, u32, u32, vp, vp, vp, vp],
         "cos_rrf_fuse_batch": [vp, vp, u32, vp, vp, u32, u32, f32, u32, vp, vp, vp],

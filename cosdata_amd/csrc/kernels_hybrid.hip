@@ -12,12 +12,14 @@
 // The 512 result buckets (doc_id % 512, strictly-greater score wins, first seen = smallest id on ties) are
 // an order-independent max over the key (score, ~doc_id): one 64-bit LDS/global atomic max.
 #include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <numeric>
 #include <vector>
 
 #include "engine_internal.h"
@@ -58,9 +60,17 @@ __device__ __forceinline__ u64 lower_bound_doc(const u32 *__restrict__ docs, u64
 // against 0.66 ms for this one: dropped).
 constexpr u32 UNTOUCHED = 0xFFFFFFFFu;
 
+// TOMBSTONE_TF is the stored term frequency of a deleted posting (cos_bm25_delete; the reference overwrites the entry with u64::MAX,
+// versioned_vec.rs:141-150, and its iterator skips it, :251-275): another NaN pattern, so no stored tf can take it (create and insert
+// reject non-finite values) and it is distinct from UNTOUCHED.  The document id stays in place — the lists stay ascending for the
+// tile directory and for the delete's own search — and the posting still counts in the list's length, which is what get_idf sees.
+constexpr u32 TOMBSTONE_TF = 0x7FC0DEADu;
+
 // apply one chunk (PU postings per lane, all of ONE term: distinct documents, so the PU read-modify-writes of a lane and those of
 // the other lanes never touch the same slot and the reads can all be issued before the first write)
-template <u32 N>
+// TOMBS: the index holds tombstones (cos_bm25_delete marked at least one posting).  An index without any runs the instantiation
+// without the test, the inner loop it had before deletes existed.
+template <u32 N, bool TOMBS>
 __device__ __forceinline__ void bm25_apply_chunk(float *acc, u32 d0, float idf, const u32 (&dv)[PU], const float (&tv)[PU], u32 mask) {
     float old[PU];
     bool ok[PU];
@@ -72,7 +82,7 @@ __device__ __forceinline__ void bm25_apply_chunk(float *acc, u32 d0, float idf, 
     }
 #pragma unroll
     for (int u = 0; u < PU; u++) {
-        if (ok[u]) {
+        if (ok[u] && (!TOMBS || __float_as_uint(tv[u]) != TOMBSTONE_TF)) { // a deleted posting adds nothing: one compare per posting
             const float p = __fmul_rn(tv[u], idf); // tf * head.idf
             acc[(dv[u] - d0) & (N - 1)] = __float_as_uint(old[u]) != UNTOUCHED ? __fadd_rn(old[u], p) : p;
         }
@@ -96,6 +106,7 @@ struct Bm25Cursor { // block-uniform
     bool valid;
 };
 
+template <bool TOMBS>
 __global__ __launch_bounds__(256) void bm25_score_kernel(const u32 *__restrict__ docs, const float *__restrict__ tfs,
                                                          const QueryTerms *__restrict__ qts, u32 n_docs, const u32 *__restrict__ tile_dir,
                                                          u64 *__restrict__ buckets /*[B][512]*/, const u32 *__restrict__ order, u32 splits) {
@@ -153,7 +164,7 @@ __global__ __launch_bounds__(256) void bm25_score_kernel(const u32 *__restrict__
     auto apply = [&](const Bm25Cursor &c, const Bm25Cursor &nx, const u32 (&dv)[PU], const float (&tv)[PU], const u32 mask) {
         const u32 d0 = c.tile * TILE;
         const float idf = qt->idf[c.t];
-        bm25_apply_chunk<TILE>(acc, d0, idf, dv, tv, mask);
+        bm25_apply_chunk<TILE, TOMBS>(acc, d0, idf, dv, tv, mask);
         const bool term_done = !nx.valid || nx.tile != c.tile || nx.t != c.t;
         const bool tile_done = !nx.valid || nx.tile != c.tile;
         if (term_done) __syncthreads(); // a document's score is p0, then + p1, then + p2 ... in term order
@@ -282,6 +293,9 @@ __global__ __launch_bounds__(64) void rrf_kernel(const u32 *__restrict__ dense_i
 struct cos_bm25 {
     int32_t device = 0;
     u32 n_terms = 0, documents_count = 0, max_doc = 0;
+    long long max_id_ever = -1; // the largest document id the index has ever held (cos_bm25_insert's id rule); -1 = none
+    u64 n_tombstones = 0;
+    u32 dir_rows = 0, dir_tiles = 0; // shape of d_tile_dir: [dir_rows][dir_tiles + 1]
     std::vector<u32> term_hashes;
     std::vector<u64> offsets;
     u32 *d_docs = nullptr;
@@ -356,6 +370,9 @@ extern "C" int32_t cos_bm25_create(int32_t device, const uint32_t *term_hashes, 
     if (e == hipSuccess) e = hipMemcpy(b->d_tfs, tfs, nnz * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess && !dir.empty()) e = hipMemcpy(b->d_tile_dir, dir.data(), dir.size() * 4, hipMemcpyHostToDevice);
     if (e != hipSuccess) { cos_bm25_destroy(b); HIP_TRY(e); }
+    if (nnz) b->max_id_ever = b->max_doc;
+    b->dir_rows = rows;
+    b->dir_tiles = n_tiles;
     *out = b;
     return COS_OK;
 }
@@ -443,8 +460,13 @@ static int32_t bm25_launch(cos_bm25 *b, u32 B, u32 top_k, u32 *d_out_ids, float 
     const u32 target_blocks = (u32)std::max<long long>(1, tune_or(TUNE_BM25_BLOCKS, 8192));
     const u32 n_tiles = (span + TILE - 1) / TILE;
     const u32 splits = std::max(1u, std::min(n_tiles, std::max(1u, target_blocks / B)));
-    hipLaunchKernelGGL(bm25_score_kernel, dim3(B * splits), dim3(256), 0, st, b->d_docs, b->d_tfs, b->d_qt, span, b->d_tile_dir, b->d_buckets,
-                       (const u32 *)(b->d_qt + b->capB), splits);
+    // an index that holds no tombstone (never the target of a delete that found something) keeps the kernel without the tombstone test
+    if (b->n_tombstones)
+        hipLaunchKernelGGL(bm25_score_kernel<true>, dim3(B * splits), dim3(256), 0, st, b->d_docs, b->d_tfs, b->d_qt, span, b->d_tile_dir, b->d_buckets,
+                           (const u32 *)(b->d_qt + b->capB), splits);
+    else
+        hipLaunchKernelGGL(bm25_score_kernel<false>, dim3(B * splits), dim3(256), 0, st, b->d_docs, b->d_tfs, b->d_qt, span, b->d_tile_dir, b->d_buckets,
+                           (const u32 *)(b->d_qt + b->capB), splits);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(bm25_topk_kernel, dim3(B), dim3(64), 0, st, b->d_buckets, B, top_k, d_out_ids, d_out_scores, d_out_counts);
     HIP_TRY(hipGetLastError());
@@ -620,5 +642,429 @@ extern "C" int32_t cos_hybrid_search_batch(cos_index *ix, cos_bm25 *b, const flo
     const int32_t *status = (const int32_t *)(hr + 2 * nk + B);
     for (u32 q = 0; q < B; q++)
         if (status[q] != COS_OK) return cos_fail(status[q], "dense half: query %u failed with status %d (zero-norm vector -> DistanceError::CalculationError)", q, status[q]);
+    return COS_OK;
+}
+
+
+// ------------------------------------------------------------------------------------------------
+// Updates of the resident postings: cos_bm25_insert / cos_bm25_delete / cos_bm25_stats / cos_bm25_download.
+//   TFIDFIndex::insert                     indexes/tf_idf/mod.rs:85-110   (documents_count += 1; (doc id, tf) to the END of every term's list)
+//   TFIDFIndex::mark_embedding_as_deleted  indexes/tf_idf/mod.rs:112-141  (documents_count -= 1; the first entry with the id becomes a tombstone)
+//   TFIDFIndexNode::insert / delete        models/tf_idf_index.rs:212-266
+//   VersionedVec::push_sorted / delete     models/versioned_vec.rs:131-150, :205-222; the iterator that skips tombstones :251-275
+//
+// The postings never go back through the host.  The host owns the term table (term_hashes, offsets: O(n_terms)) and sees the
+// update itself (O(size of the update)); the device turns the document-major update into term-major order (stable radix sort by
+// term hash: ids arrive ascending, so every term's new postings come out ascending), streams old list + new postings of every term
+// into NEW arrays (bm25_merge_kernel: 8 B read + 8 B written per posting of the new array), and searches the tile directory of the
+// new arrays (bm25_tile_dir_kernel).  Only then are the handle's pointers swapped and the old arrays freed: a call that fails
+// before that point leaves the handle exactly as it was.
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr u32 MERGE_PIECE = 4096; // postings of the OUTPUT per workgroup: 256 threads x 4 rounds x 4 postings (16 B of ids + 16 B of tfs)
+
+// the term that owns posting j of the new array: the LAST t in [lo, hi] whose list starts at or before j (new_off(t) = old_off[t] +
+// del_off[t]; an empty list shares its start with the list behind it and is passed over).  Needs new_off(lo) <= j.
+__device__ __forceinline__ u32 merge_term_of(const u64 *__restrict__ old_off, const u64 *__restrict__ del_off, u32 lo, u32 hi, u64 j) {
+    while (lo < hi) {
+        const u32 mid = lo + (hi - lo + 1) / 2;
+        if (old_off[mid] + del_off[mid] <= j) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// delta in term-major order: perm = the stable sort's permutation of the update's postings
+__global__ __launch_bounds__(256) void bm25_delta_gather_kernel(const u32 *__restrict__ perm, const u32 *__restrict__ pdocs, const float *__restrict__ ptfs,
+                                                                u32 n, u32 *__restrict__ out_docs, float *__restrict__ out_tfs) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const u32 s = perm[i];
+    out_docs[i] = pdocs[s];
+    out_tfs[i] = ptfs[s];
+}
+
+// new list of term t = old list of t, then the delta's postings of t (ids above every id the index ever held: still ascending).
+// old_off / del_off [T + 1]: where term t's old postings / delta postings start, both indexed by the NEW term table (a term that
+// exists only in the update has an empty old part, an untouched term an empty delta part).  One workgroup per MERGE_PIECE postings
+// of the OUTPUT, whatever the list lengths: a 400 000-posting list is 98 workgroups, 4096 one-posting lists are one.  A thread
+// moves 4 consecutive output postings; when they come from one list and one source they are 4 consecutive source words
+// (global_load_dwordx4, the source only 4-byte aligned) and always one 16-byte store per array (the piece and the arrays are
+// 16-byte aligned).
+__global__ __launch_bounds__(256) void bm25_merge_kernel(const u32 *__restrict__ old_docs, const float *__restrict__ old_tfs,
+                                                         const u32 *__restrict__ del_docs, const float *__restrict__ del_tfs,
+                                                         const u64 *__restrict__ old_off, const u64 *__restrict__ del_off, u32 T, u64 nnz,
+                                                         u32 *__restrict__ new_docs, float *__restrict__ new_tfs) {
+    const u64 p0 = (u64)blockIdx.x * MERGE_PIECE;
+    if (p0 >= nnz) return;
+    const u64 p1 = p0 + MERGE_PIECE < nnz ? p0 + MERGE_PIECE : nnz;
+    const u32 t_lo = merge_term_of(old_off, del_off, 0, T - 1, p0); // block-uniform: the piece's first and last term bound every thread's search
+    const u32 t_hi = merge_term_of(old_off, del_off, t_lo, T - 1, p1 - 1);
+    for (u64 j0 = p0 + (u64)threadIdx.x * 4; j0 < p1; j0 += 1024) {
+        u32 t = merge_term_of(old_off, del_off, t_lo, t_hi, j0);
+        u64 ob = old_off[t], db = del_off[t];
+        u64 ol = old_off[t + 1] - ob;
+        const u64 ne = old_off[t + 1] + del_off[t + 1];
+        u64 k = j0 - ob - db;
+        u32 d[4];
+        float f[4];
+        if (j0 + 4 <= ne && (k + 4 <= ol || k >= ol)) { // one list, one source: 4 consecutive words of it
+            const bool from_old = k + 4 <= ol;
+            const u32 *sd = from_old ? old_docs + ob + k : del_docs + db + (k - ol);
+            const float *sf = from_old ? old_tfs + ob + k : del_tfs + db + (k - ol);
+#pragma unroll
+            for (int u = 0; u < 4; u++) { d[u] = sd[u]; f[u] = sf[u]; }
+        } else { // a list boundary or the old/delta seam inside the 4: posting by posting
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const u64 j = j0 + u;
+                d[u] = 0;
+                f[u] = 0.0f;
+                if (j < nnz) {
+                    while (j >= old_off[t + 1] + del_off[t + 1]) t++; // j < nnz = new_off(T): stops at t <= T - 1
+                    ob = old_off[t];
+                    db = del_off[t];
+                    ol = old_off[t + 1] - ob;
+                    k = j - ob - db;
+                    if (k < ol) { d[u] = old_docs[ob + k]; f[u] = old_tfs[ob + k]; }
+                    else { d[u] = del_docs[db + (k - ol)]; f[u] = del_tfs[db + (k - ol)]; }
+                }
+            }
+        }
+        if (j0 + 4 <= nnz) {
+            *reinterpret_cast<uint4 *>(new_docs + j0) = make_uint4(d[0], d[1], d[2], d[3]);
+            *reinterpret_cast<float4 *>(new_tfs + j0) = make_float4(f[0], f[1], f[2], f[3]);
+        } else {
+#pragma unroll
+            for (int u = 0; u < 4; u++)
+                if (j0 + u < nnz) { new_docs[j0 + u] = d[u]; new_tfs[j0 + u] = f[u]; }
+        }
+    }
+}
+
+// tile_dir[row][t] = offset (from the list's begin) of the first posting with doc id >= t * TILE, t = 0 .. n_tiles; the last column
+// is the list's length.  One lower-bound search per entry; the same values cos_bm25_create's host pass writes.
+__global__ __launch_bounds__(256) void bm25_tile_dir_kernel(const u32 *__restrict__ docs, const u64 *__restrict__ row_begin, const u32 *__restrict__ row_len,
+                                                            u32 rows, u32 n_tiles, u32 *__restrict__ tile_dir) {
+    const u64 idx = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    const u64 width = (u64)n_tiles + 1;
+    if (idx >= (u64)rows * width) return;
+    const u32 row = (u32)(idx / width), t = (u32)(idx % width);
+    const u64 lo = row_begin[row];
+    const u32 len = row_len[row];
+    tile_dir[idx] = t == n_tiles ? len : (u32)(lower_bound_doc(docs, lo, lo + len, t * TILE) - lo); // t < n_tiles: t * TILE <= the largest id
+}
+
+// one thread per (document, term) pair of a delete call whose term has a list: lower-bound search for the id, mark the posting if it
+// is there and not yet marked (the exchange makes two pairs naming the same posting count it once), count what was marked
+__global__ __launch_bounds__(256) void bm25_tombstone_kernel(const u32 *__restrict__ docs, float *__restrict__ tfs, const u32 *__restrict__ pair_doc,
+                                                             const u64 *__restrict__ pair_begin, const u32 *__restrict__ pair_len, u32 n_pairs,
+                                                             u32 *__restrict__ marked) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pairs) return;
+    const u64 lo = pair_begin[i], hi = lo + pair_len[i];
+    const u32 doc = pair_doc[i];
+    const u64 pos = lower_bound_doc(docs, lo, hi, doc);
+    if (pos < hi && docs[pos] == doc) {
+        const u32 old = atomicExch(reinterpret_cast<unsigned int *>(tfs + pos), TOMBSTONE_TF);
+        if (old != TOMBSTONE_TF) atomicAdd(marked, 1u);
+    }
+}
+
+// device allocations of one update call: whatever is still listed when the call leaves (by any path) is freed
+struct UpdateAllocs {
+    std::vector<void *> ptrs;
+    ~UpdateAllocs() { for (void *p : ptrs) if (p) (void)hipFree(p); }
+    template <typename T>
+    hipError_t alloc(T *&out, size_t n) {
+        void *p = nullptr;
+        const hipError_t e = hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T));
+        if (e == hipSuccess) ptrs.push_back(p);
+        out = (T *)p;
+        return e;
+    }
+    void keep(void *p) { ptrs.erase(std::remove(ptrs.begin(), ptrs.end(), p), ptrs.end()); } // now owned by the handle
+};
+
+// updates wait for everything the handle has in flight (the caller holds b->mu): a search sees the index before or after, never between
+int32_t bm25_quiesce(cos_bm25 *b) {
+    HIP_TRY(hipSetDevice(b->device));
+    if (!b->stream) HIP_TRY(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    if (b->stream_dense) HIP_TRY(hipStreamSynchronize(b->stream_dense));
+    return COS_OK;
+}
+
+int32_t bm25_check_doc_offsets(const uint64_t *doc_offsets, u32 m) {
+    if (doc_offsets[0] != 0) return cos_fail(COS_ERR_INVALID, "doc_offsets[0] must be 0");
+    for (u32 i = 0; i < m; i++)
+        if (doc_offsets[i + 1] < doc_offsets[i]) return cos_fail(COS_ERR_INVALID, "doc_offsets must not decrease (document %u)", i);
+    return COS_OK;
+}
+
+} // namespace
+
+extern "C" int32_t cos_bm25_insert(cos_bm25 *b, const uint32_t *doc_ids, const uint64_t *doc_offsets, uint32_t m, const uint32_t *term_hashes,
+                                   const float *tfs) {
+    if (!b) return cos_fail(COS_ERR_INVALID, "bad argument");
+    if (m == 0) return COS_OK;
+    if (!doc_ids || !doc_offsets) return cos_fail(COS_ERR_INVALID, "bad argument");
+    int32_t rc = bm25_check_doc_offsets(doc_offsets, m);
+    if (rc) return rc;
+    const u64 nd = doc_offsets[m];
+    if (nd && (!term_hashes || !tfs)) return cos_fail(COS_ERR_INVALID, "bad argument");
+    if (nd > 0x7FFFFFFFull) return cos_fail(COS_ERR_UNIMPLEMENTED, "more than 2^31 - 1 postings in one insert");
+    for (u32 i = 1; i < m; i++)
+        if (doc_ids[i] <= doc_ids[i - 1]) return cos_fail(COS_ERR_INVALID, "document ids must be strictly ascending (document %u)", i);
+    for (u64 i = 0; i < nd; i++) // same rule and status as cos_bm25_create; it also keeps TOMBSTONE_TF out of the caller's hands
+        if (!std::isfinite(tfs[i])) return cos_fail(COS_ERR_INVALID, "stored term frequency %llu is not finite", (unsigned long long)i);
+    std::vector<u32> tmp;
+    for (u32 i = 0; i < m; i++) { // term hashes distinct inside a document (process_text counts per hash: indexes/tf_idf/mod.rs:310-360)
+        const u32 *h = term_hashes + doc_offsets[i];
+        const size_t n = (size_t)(doc_offsets[i + 1] - doc_offsets[i]);
+        bool ascending = true;
+        for (size_t j = 1; j < n && ascending; j++) ascending = h[j] > h[j - 1];
+        if (ascending) continue; // what cos_text_process hands out
+        tmp.assign(h, h + n);
+        std::sort(tmp.begin(), tmp.end());
+        if (std::adjacent_find(tmp.begin(), tmp.end()) != tmp.end()) return cos_fail(COS_ERR_INVALID, "term hash repeated inside document %u", doc_ids[i]);
+    }
+    std::lock_guard<std::mutex> g(b->mu);
+    if ((long long)doc_ids[0] <= b->max_id_ever)
+        return cos_fail(COS_ERR_INVALID, "document id %u is not above the largest id the index has held (%lld)", doc_ids[0], b->max_id_ever);
+    if ((u64)b->documents_count + m > 0xFFFFFFFFull) return cos_fail(COS_ERR_INVALID, "documents_count would pass 2^32 - 1");
+    rc = bm25_quiesce(b);
+    if (rc) return rc;
+    if (nd == 0) { // documents without terms: counted, nothing to post
+        b->documents_count += m;
+        b->max_id_ever = doc_ids[m - 1];
+        return COS_OK;
+    }
+    hipStream_t st = b->stream;
+    UpdateAllocs A;
+    const u32 n = (u32)nd;
+
+    // 1. the delta in term-major order (uploads from host arrays are synchronous copies: an early return never leaves one in flight)
+    std::vector<u32> h_pdocs(n), h_iota(n);
+    u32 delta_max_doc = 0;
+    for (u32 i = 0; i < m; i++) {
+        for (u64 j = doc_offsets[i]; j < doc_offsets[i + 1]; j++) h_pdocs[j] = doc_ids[i];
+        if (doc_offsets[i + 1] > doc_offsets[i]) delta_max_doc = doc_ids[i];
+    }
+    std::iota(h_iota.begin(), h_iota.end(), 0u);
+    u32 *d_keys = nullptr, *d_keys_sorted = nullptr, *d_iota = nullptr, *d_perm = nullptr, *d_pdocs = nullptr, *d_del_docs = nullptr;
+    u32 *d_uniq = nullptr, *d_counts = nullptr, *d_nruns = nullptr;
+    float *d_ptfs = nullptr, *d_del_tfs = nullptr;
+    void *d_tmp = nullptr;
+    HIP_TRY(A.alloc(d_keys, n)); HIP_TRY(A.alloc(d_keys_sorted, n)); HIP_TRY(A.alloc(d_iota, n)); HIP_TRY(A.alloc(d_perm, n));
+    HIP_TRY(A.alloc(d_pdocs, n)); HIP_TRY(A.alloc(d_ptfs, n)); HIP_TRY(A.alloc(d_del_docs, n)); HIP_TRY(A.alloc(d_del_tfs, n));
+    HIP_TRY(A.alloc(d_uniq, n)); HIP_TRY(A.alloc(d_counts, n)); HIP_TRY(A.alloc(d_nruns, 1));
+    size_t sort_bytes = 0, rle_bytes = 0;
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, d_keys, d_keys_sorted, d_iota, d_perm, (int)n, 0, 32, st));
+    HIP_TRY(hipcub::DeviceRunLengthEncode::Encode(nullptr, rle_bytes, d_keys_sorted, d_uniq, d_counts, d_nruns, (int)n, st));
+    size_t tmp_bytes = std::max(sort_bytes, rle_bytes);
+    {
+        unsigned char *t = nullptr;
+        HIP_TRY(A.alloc(t, tmp_bytes));
+        d_tmp = t;
+    }
+    HIP_TRY(hipMemcpy(d_keys, term_hashes, (size_t)n * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_iota, h_iota.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_pdocs, h_pdocs.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_ptfs, tfs, (size_t)n * 4, hipMemcpyHostToDevice));
+    size_t bytes = tmp_bytes;
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, bytes, d_keys, d_keys_sorted, d_iota, d_perm, (int)n, 0, 32, st)); // LSD radix sort: stable
+    hipLaunchKernelGGL(bm25_delta_gather_kernel, dim3((n + 255) / 256), dim3(256), 0, st, d_perm, d_pdocs, d_ptfs, n, d_del_docs, d_del_tfs);
+    HIP_TRY(hipGetLastError());
+    bytes = tmp_bytes;
+    HIP_TRY(hipcub::DeviceRunLengthEncode::Encode(d_tmp, bytes, d_keys_sorted, d_uniq, d_counts, d_nruns, (int)n, st));
+    u32 U = 0;
+    HIP_TRY(hipMemcpyAsync(&U, d_nruns, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (U == 0 || U > n) return cos_fail(COS_ERR_HIP, "run-length encoding of the update returned %u runs for %u postings", U, n);
+    std::vector<u32> uniq(U), counts(U); // only the delta's distinct hashes and their counts come to the host
+    HIP_TRY(hipMemcpyAsync(uniq.data(), d_uniq, (size_t)U * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(counts.data(), d_counts, (size_t)U * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+
+    // 2. merge the two sorted term tables on the host: new hashes, and per new term where its old part and its delta part start
+    const u32 T0 = b->n_terms;
+    std::vector<u32> new_hashes;
+    std::vector<u64> old_off, del_off, new_off;
+    new_hashes.reserve((size_t)T0 + U);
+    old_off.reserve((size_t)T0 + U + 1); del_off.reserve((size_t)T0 + U + 1); new_off.reserve((size_t)T0 + U + 1);
+    {
+        u32 i = 0, j = 0;
+        u64 dpos = 0;
+        while (i < T0 || j < U) {
+            const bool take_old = j == U || (i < T0 && b->term_hashes[i] <= uniq[j]);
+            const bool take_del = i == T0 || (j < U && uniq[j] <= b->term_hashes[i]);
+            new_hashes.push_back(take_old ? b->term_hashes[i] : uniq[j]);
+            old_off.push_back(b->offsets[i]); // i <= T0; a term that only the update has: an empty old part where it would stand
+            del_off.push_back(dpos);
+            new_off.push_back(old_off.back() + dpos);
+            if (take_old) i++;
+            if (take_del) dpos += counts[j++];
+        }
+        old_off.push_back(b->offsets[T0]);
+        del_off.push_back(dpos);
+        new_off.push_back(old_off.back() + dpos);
+        if (dpos != n) return cos_fail(COS_ERR_HIP, "the update's run lengths add up to %llu, not %u", (unsigned long long)dpos, n);
+    }
+    if (new_hashes.size() > 0xFFFFFFFFull) return cos_fail(COS_ERR_UNIMPLEMENTED, "more than 2^32 - 1 terms");
+    const u32 T = (u32)new_hashes.size();
+    const u64 nnz = new_off[T];
+
+    // 3. the new directory's shape: a list crossing DIR_MIN gets a row, a larger largest id widens every row
+    const u32 new_max_doc = std::max(b->max_doc, delta_max_doc);
+    const u32 n_tiles = (u32)(((u64)new_max_doc + 1 + TILE - 1) / TILE);
+    std::vector<u32> new_dir_row(T, NO_DIR), row_len;
+    std::vector<u64> row_begin;
+    for (u32 t = 0; t < T; t++) {
+        const u64 len = new_off[t + 1] - new_off[t];
+        if (len <= DIR_MIN) continue;
+        if (len > 0xFFFFFFFFull) return cos_fail(COS_ERR_UNIMPLEMENTED, "posting list of term %u too long", new_hashes[t]);
+        new_dir_row[t] = (u32)row_begin.size();
+        row_begin.push_back(new_off[t]);
+        row_len.push_back((u32)len);
+    }
+    const u32 rows = (u32)row_begin.size();
+    const u64 dir_words = (u64)rows * (n_tiles + 1);
+
+    // 4. new arrays, merge, directory — all on the device; the old arrays are only read
+    u32 *d_new_docs = nullptr, *d_new_dir = nullptr, *d_row_len = nullptr;
+    float *d_new_tfs = nullptr;
+    u64 *d_old_off = nullptr, *d_del_off = nullptr, *d_row_begin = nullptr;
+    HIP_TRY(A.alloc(d_new_docs, nnz)); HIP_TRY(A.alloc(d_new_tfs, nnz)); HIP_TRY(A.alloc(d_new_dir, dir_words));
+    HIP_TRY(A.alloc(d_old_off, (size_t)T + 1)); HIP_TRY(A.alloc(d_del_off, (size_t)T + 1));
+    HIP_TRY(A.alloc(d_row_begin, rows)); HIP_TRY(A.alloc(d_row_len, rows));
+    HIP_TRY(hipMemcpy(d_old_off, old_off.data(), ((size_t)T + 1) * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_del_off, del_off.data(), ((size_t)T + 1) * 8, hipMemcpyHostToDevice));
+    const u64 pieces = (nnz + MERGE_PIECE - 1) / MERGE_PIECE;
+    if (pieces > 0x7FFFFFFFull) return cos_fail(COS_ERR_UNIMPLEMENTED, "too many postings for one merge launch");
+    hipLaunchKernelGGL(bm25_merge_kernel, dim3((u32)pieces), dim3(256), 0, st, b->d_docs, b->d_tfs, d_del_docs, d_del_tfs, d_old_off, d_del_off, T, nnz,
+                       d_new_docs, d_new_tfs);
+    HIP_TRY(hipGetLastError());
+    if (rows) {
+        if ((dir_words + 255) / 256 > 0x7FFFFFFFull) return cos_fail(COS_ERR_UNIMPLEMENTED, "tile directory too large for one launch");
+        HIP_TRY(hipMemcpy(d_row_begin, row_begin.data(), (size_t)rows * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_row_len, row_len.data(), (size_t)rows * 4, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(bm25_tile_dir_kernel, dim3((u32)((dir_words + 255) / 256)), dim3(256), 0, st, d_new_docs, d_row_begin, d_row_len, rows, n_tiles,
+                           d_new_dir);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+
+    // 5. everything is complete: swap, then free the old arrays.  The search workspace is reused as is.
+    A.keep(d_new_docs); A.keep(d_new_tfs); A.keep(d_new_dir);
+    (void)hipFree(b->d_docs); (void)hipFree(b->d_tfs); (void)hipFree(b->d_tile_dir);
+    b->d_docs = d_new_docs; b->d_tfs = d_new_tfs; b->d_tile_dir = d_new_dir;
+    b->term_hashes.swap(new_hashes);
+    b->offsets.swap(new_off);
+    b->dir_row.swap(new_dir_row);
+    b->n_terms = T;
+    b->max_doc = new_max_doc;
+    b->max_id_ever = doc_ids[m - 1];
+    b->documents_count += m;
+    b->dir_rows = rows;
+    b->dir_tiles = n_tiles;
+    return COS_OK;
+}
+
+extern "C" int32_t cos_bm25_delete(cos_bm25 *b, const uint32_t *doc_ids, const uint64_t *doc_offsets, uint32_t m, const uint32_t *term_hashes) {
+    if (!b) return cos_fail(COS_ERR_INVALID, "bad argument");
+    if (m == 0) return COS_OK;
+    if (!doc_ids || !doc_offsets) return cos_fail(COS_ERR_INVALID, "bad argument");
+    int32_t rc = bm25_check_doc_offsets(doc_offsets, m);
+    if (rc) return rc;
+    const u64 nd = doc_offsets[m];
+    if (nd && !term_hashes) return cos_fail(COS_ERR_INVALID, "bad argument");
+    std::lock_guard<std::mutex> g(b->mu);
+    if (b->documents_count < m) return cos_fail(COS_ERR_INVALID, "delete of %u documents from an index that counts %u", m, b->documents_count);
+    // term -> list on the host's term table (like bm25_prepare for queries); a term without a list is left alone (mod.rs:124-133)
+    std::vector<u32> pair_doc, pair_len;
+    std::vector<u64> pair_begin;
+    for (u32 i = 0; i < m; i++)
+        for (u64 j = doc_offsets[i]; j < doc_offsets[i + 1]; j++) {
+            auto it = std::lower_bound(b->term_hashes.begin(), b->term_hashes.end(), term_hashes[j]);
+            if (it == b->term_hashes.end() || *it != term_hashes[j]) continue;
+            const size_t ti = (size_t)(it - b->term_hashes.begin());
+            const u64 len = b->offsets[ti + 1] - b->offsets[ti];
+            if (len == 0) continue;
+            pair_doc.push_back(doc_ids[i]);
+            pair_begin.push_back(b->offsets[ti]);
+            pair_len.push_back((u32)len); // lists longer than 2^32 - 1 are refused by create and insert
+        }
+    if (pair_doc.size() > 0x7FFFFFFFull) return cos_fail(COS_ERR_UNIMPLEMENTED, "more than 2^31 - 1 (document, term) pairs in one delete");
+    const u32 np = (u32)pair_doc.size();
+    rc = bm25_quiesce(b);
+    if (rc) return rc;
+    u32 marked = 0;
+    if (np) {
+        hipStream_t st = b->stream;
+        UpdateAllocs A;
+        u32 *d_pd = nullptr, *d_pl = nullptr, *d_marked = nullptr;
+        u64 *d_pb = nullptr;
+        HIP_TRY(A.alloc(d_pd, np)); HIP_TRY(A.alloc(d_pl, np)); HIP_TRY(A.alloc(d_pb, np)); HIP_TRY(A.alloc(d_marked, 1));
+        HIP_TRY(hipMemcpy(d_pd, pair_doc.data(), (size_t)np * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_pl, pair_len.data(), (size_t)np * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_pb, pair_begin.data(), (size_t)np * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemsetAsync(d_marked, 0, 4, st));
+        // nothing of the handle has been written up to here; from the launch on the call can only fail with the device itself
+        hipLaunchKernelGGL(bm25_tombstone_kernel, dim3((np + 255) / 256), dim3(256), 0, st, b->d_docs, b->d_tfs, d_pd, d_pb, d_pl, np, d_marked);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&marked, d_marked, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    b->documents_count -= m; // once per document, found or not (mod.rs:117-119)
+    b->n_tombstones += marked;
+    return COS_OK;
+}
+
+extern "C" int32_t cos_bm25_stats(cos_bm25 *b, cos_bm25_index_stats *out) {
+    if (!b || !out || out->struct_size != sizeof(cos_bm25_index_stats)) return cos_fail(COS_ERR_INVALID, "bad argument (struct_size must be sizeof(cos_bm25_index_stats))");
+    std::lock_guard<std::mutex> g(b->mu);
+    const u64 nnz = b->offsets[b->n_terms];
+    out->documents_count = b->documents_count;
+    out->n_terms = b->n_terms;
+    out->largest_doc_id = b->max_id_ever < 0 ? 0u : (u32)b->max_id_ever;
+    out->dir_rows = b->dir_rows;
+    out->dir_tiles = b->dir_tiles;
+    out->reserved = 0;
+    out->postings = nnz;
+    out->tombstones = b->n_tombstones;
+    u64 bytes = 2 * std::max<u64>(nnz, 1) * 4 + std::max<u64>((u64)b->dir_rows * (b->dir_tiles + 1), 1) * 4; // postings + directory
+    bytes += (u64)b->capB * (sizeof(QueryTerms) + 4 + BUCKETS * 8 + 4) + 2 * (u64)b->capB * b->cap_k * 4;     // search workspace
+    bytes += ((u64)b->cap_hq + b->cap_did + b->cap_dsc + b->cap_dcnt + b->cap_ret) * 4;                       // hybrid search buffers
+    out->device_bytes = bytes;
+    return COS_OK;
+}
+
+extern "C" int32_t cos_bm25_download(cos_bm25 *b, uint32_t *n_terms, uint64_t *n_postings, uint32_t *term_hashes, uint64_t *offsets, uint32_t *doc_ids,
+                                     float *tfs, uint8_t *tombstones) {
+    if (!b || !n_terms || !n_postings) return cos_fail(COS_ERR_INVALID, "bad argument");
+    std::lock_guard<std::mutex> g(b->mu);
+    const u32 T = b->n_terms;
+    const u64 nnz = b->offsets[T];
+    const u32 cap_t = *n_terms;
+    const u64 cap_p = *n_postings;
+    *n_terms = T;
+    *n_postings = nnz;
+    if (!term_hashes && !offsets && !doc_ids && !tfs && !tombstones) return COS_OK; // first call: the sizes
+    if (!term_hashes || !offsets || !doc_ids || !tfs || !tombstones) return cos_fail(COS_ERR_INVALID, "bad argument: all five arrays or none");
+    if (cap_t < T || cap_p < nnz)
+        return cos_fail(COS_ERR_INVALID, "arrays for %u terms / %llu postings, the index holds %u / %llu", cap_t, (unsigned long long)cap_p, T, (unsigned long long)nnz);
+    int32_t rc = bm25_quiesce(b);
+    if (rc) return rc;
+    memcpy(term_hashes, b->term_hashes.data(), (size_t)T * 4);
+    memcpy(offsets, b->offsets.data(), ((size_t)T + 1) * 8);
+    HIP_TRY(hipMemcpy(doc_ids, b->d_docs, nnz * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(tfs, b->d_tfs, nnz * 4, hipMemcpyDeviceToHost));
+    for (u64 i = 0; i < nnz; i++) { // a tombstone leaves as a flag and a finite 0: the arrays are again what cos_bm25_create takes
+        u32 bits;
+        memcpy(&bits, &tfs[i], 4);
+        tombstones[i] = bits == TOMBSTONE_TF;
+        if (bits == TOMBSTONE_TF) tfs[i] = 0.0f;
+    }
     return COS_OK;
 }

@@ -71,6 +71,52 @@ def _bm25_search_batch_device(self, q_terms, q_offsets, top_k: int, out_ids_ptr:
 BM25Index.search_batch_device = _bm25_search_batch_device
 
 
+def _bm25_insert(self, doc_ids, doc_offsets, term_hashes, tfs):
+    """TFIDFIndex::insert for m documents (cos_bm25_insert): document-major (doc_ids[m] strictly ascending and above every id the
+    index has held, doc_offsets[m+1] into term_hashes / tfs); the resident postings are merged on the device"""
+    di, do = _c(doc_ids, np.uint32), _c(doc_offsets, np.uint64)
+    th, tf = _c(term_hashes, np.uint32), _c(tfs, np.float32)
+    if do.size != di.size + 1 or th.size != tf.size or (do.size and int(do[-1]) != th.size):
+        raise ValueError("doc_offsets must have len(doc_ids) + 1 entries and end at len(term_hashes) == len(tfs)")
+    check(_lib.lib().cos_bm25_insert(self._h, _p(di), _p(do), di.size, _p(th), _p(tf)))
+    return self
+
+
+def _bm25_delete(self, doc_ids, doc_offsets, term_hashes):
+    """TFIDFIndex::mark_embedding_as_deleted for m documents (cos_bm25_delete): tombstones in place, documents_count -= m"""
+    di, do, th = _c(doc_ids, np.uint32), _c(doc_offsets, np.uint64), _c(term_hashes, np.uint32)
+    if do.size != di.size + 1 or (do.size and int(do[-1]) != th.size):
+        raise ValueError("doc_offsets must have len(doc_ids) + 1 entries and end at len(term_hashes)")
+    check(_lib.lib().cos_bm25_delete(self._h, _p(di), _p(do), di.size, _p(th)))
+    return self
+
+
+def _bm25_stats(self) -> dict:
+    """cos_bm25_stats as a dict: documents_count, n_terms, largest_doc_id, dir_rows, dir_tiles, postings, tombstones, device_bytes"""
+    st = _lib.CosBM25Stats()
+    st.struct_size = C.sizeof(_lib.CosBM25Stats)
+    check(_lib.lib().cos_bm25_stats(self._h, C.byref(st)))
+    return {name: int(getattr(st, name)) for name, _ in st._fields_ if name not in ("struct_size", "reserved")}
+
+
+def _bm25_download(self):
+    """cos_bm25_download -> (term_hashes, offsets, doc_ids, tfs, tombstones): the CSR cos_bm25_create takes + one flag per posting"""
+    L = _lib.lib()
+    nt, nnz = C.c_uint32(0), C.c_uint64(0)
+    check(L.cos_bm25_download(self._h, C.byref(nt), C.byref(nnz), None, None, None, None, None))
+    th, off = np.zeros(nt.value, np.uint32), np.zeros(nt.value + 1, np.uint64)
+    n = int(nnz.value)
+    di, tf, tomb = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.uint8)
+    check(L.cos_bm25_download(self._h, C.byref(nt), C.byref(nnz), _p(th), _p(off), _p(di), _p(tf), _p(tomb)))
+    return th, off, di[:n], tf[:n], tomb[:n].astype(bool)
+
+
+BM25Index.insert = _bm25_insert
+BM25Index.delete = _bm25_delete
+BM25Index.stats = _bm25_stats
+BM25Index.download = _bm25_download
+
+
 def rrf_fuse_batch(dense_ids, dense_counts, sparse_ids, sparse_counts, fusion_constant_k: float, top_k: int):
     d, s = _c(dense_ids, np.uint32), _c(sparse_ids, np.uint32)
     dc, sc_ = _c(dense_counts, np.uint32), _c(sparse_counts, np.uint32)

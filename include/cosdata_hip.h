@@ -398,6 +398,48 @@ typedef struct cos_bm25 cos_bm25;
 int32_t cos_bm25_create(int32_t device, const uint32_t *term_hashes, const uint64_t *offsets, uint32_t n_terms,
                         const uint32_t *doc_ids, const float *tfs, uint32_t documents_count, cos_bm25 **out);
 int32_t cos_bm25_destroy(cos_bm25 *b);
+/* ---- updates of the resident postings ---------------------------------------------------------
+ * The postings stay on the device: the host passes the update, the library keeps the term table.  Every call below takes the
+ * handle's lock and waits for the handle's streams, so a search on another thread sees the index before or after an update, never
+ * between.  Strong guarantee: a call that fails (bad argument, or hipErrorOutOfMemory while the new arrays are allocated) leaves
+ * the handle exactly as it was, and usable.
+ *
+ * TFIDFIndex::insert (indexes/tf_idf/mod.rs:85-110; TFIDFIndexNode::insert models/tf_idf_index.rs:212-240, VersionedVec::push_sorted
+ * models/versioned_vec.rs:205-222) for m documents in document-major form — what cos_text_process gives per document:
+ * term_hashes / tfs [doc_offsets[i], doc_offsets[i+1]) belong to doc_ids[i].  (doc id, tf) goes to the END of each term's list, a new
+ * term gets a list, documents_count += m.  doc_ids strictly ascending and all above every id the index has ever held, term hashes
+ * distinct within a document, tfs finite (else COS_ERR_INVALID); m == 0 succeeds and does nothing.
+ * Peak device memory during the call: old arrays + new arrays (8 B per posting each, plus the two tile directories) + the update
+ * itself (about 40 B per posting of the update, the sort's workspace included) + 16 B per term. */
+int32_t cos_bm25_insert(cos_bm25 *b, const uint32_t *doc_ids, const uint64_t *doc_offsets, uint32_t m, const uint32_t *term_hashes,
+                        const float *tfs);
+/* TFIDFIndex::mark_embedding_as_deleted (indexes/tf_idf/mod.rs:112-141; TFIDFIndexNode::delete models/tf_idf_index.rs:242-266,
+ * VersionedVec::delete models/versioned_vec.rs:131-150) for m documents given with the term hashes of their text:
+ * documents_count -= m (once per document, found or not; documents_count < m is COS_ERR_INVALID with nothing changed), and for
+ * every (document, term) the entry of that term's list with this id becomes a tombstone: skipped by every search
+ * (versioned_vec.rs:251-275), still counted in the list's length that get_idf sees, never compacted.  A term without a list, or a
+ * list without the id (second delete), is left alone. */
+int32_t cos_bm25_delete(cos_bm25 *b, const uint32_t *doc_ids, const uint64_t *doc_offsets, uint32_t m, const uint32_t *term_hashes);
+typedef struct {
+    uint32_t struct_size;     /* in: sizeof(cos_bm25_index_stats) */
+    uint32_t documents_count; /* TFIDFIndexRoot::total_documents_count: what the idf uses */
+    uint32_t n_terms;
+    uint32_t largest_doc_id;  /* the largest document id the index has ever held (0 when it has held none) */
+    uint32_t dir_rows;        /* lists long enough for a row of the tile directory */
+    uint32_t dir_tiles;       /* tiles of 8192 document ids the directory spans */
+    uint32_t reserved;
+    uint64_t postings;        /* tombstones included */
+    uint64_t tombstones;
+    uint64_t device_bytes;    /* postings, tile directory and the search workspace */
+} cos_bm25_index_stats;
+int32_t cos_bm25_stats(cos_bm25 *b, cos_bm25_index_stats *out);
+/* The index as the CSR cos_bm25_create takes, plus one flag per posting (1 = tombstone; its tf comes back as 0).  Two calls: with the
+ * five arrays NULL, *n_terms / *n_postings receive the sizes; with the arrays (term_hashes[T], offsets[T+1], doc_ids / tfs /
+ * tombstones [postings]) they carry the capacities in and the sizes out (too small: COS_ERR_INVALID, nothing written).  An index
+ * that holds tombstones is restored by cos_bm25_create from these arrays followed by ONE cos_bm25_delete of the flagged (document,
+ * term) pairs, with documents_count passed to create so that it ends right. */
+int32_t cos_bm25_download(cos_bm25 *b, uint32_t *n_terms, uint64_t *n_postings, uint32_t *term_hashes, uint64_t *offsets,
+                          uint32_t *doc_ids, float *tfs, uint8_t *tombstones);
 /* SparseAnnQueryBasic::search_bm25 (models/sparse_ann_query.rs:149) for B queries given as
  * pre-hashed terms (CSR q_offsets[B+1] into q_terms); outputs [B][top_k]. */
 int32_t cos_bm25_search_batch(cos_bm25 *b, const uint32_t *q_terms, const uint32_t *q_offsets, uint32_t B,
