@@ -45,14 +45,6 @@ inline int32_t order_key(u32 metric, float v) {
     return (metric == COS_METRIC_EUCLIDEAN || metric == COS_METRIC_HAMMING) ? ~k : k;
 }
 
-// pinned host staging
-struct HostBuf {
-    void *p = nullptr;
-    ~HostBuf() { if (p) (void)hipHostFree(p); }
-    hipError_t alloc(size_t bytes) { return hipHostMalloc(&p, bytes ? bytes : 1); }
-    template <typename T> T *as() const { return (T *)p; }
-};
-
 } // namespace
 
 namespace {
@@ -82,16 +74,7 @@ struct GraphGuard {
     ~GraphGuard() {
         if (!armed) return;
         (void)hipStreamSynchronize(ix->own_stream);
-        for (auto &l : ix->lv) {
-            void *ptrs[] = {l.d_adj_vec, l.d_adj_node, l.d_node_vec, l.d_child, l.d_adj_mag};
-            for (void *p : ptrs) if (p) (void)hipFree(p);
-            l.d_adj_vec = l.d_adj_node = l.d_node_vec = l.d_child = nullptr;
-            l.d_adj_mag = nullptr;
-            l.n = 0;
-            l.node_ids.clear();
-            l.nbr_ids.clear();
-            l.host_valid = false;
-        }
+        for (auto &l : ix->lv) l.release();
         ix->link.release();
         ix->adj_mag_valid = false;
         ix->have_root = false;
@@ -131,7 +114,7 @@ int32_t run_batches(cos_index *ix, u32 first, const uint8_t *max_level, std::vec
     // ---- batch workspace (device) + pinned staging -----------------------------------------------------------
     const u32 KEEP = (u32)KEEP_INDEX;
     DevBuf d_rows, d_out_ids, d_out_nodes, d_out_sims, d_out_counts, d_status, d_me, d_pend[2], d_cnt, d_evq;
-    HostBuf h_rows, h_me, h_pend, h_status, h_cnt;
+    PinArr<unsigned char> h_rows, h_me, h_pend, h_status, h_cnt;
     const size_t pend_cap = (size_t)Bmax * L1;              // (level, batch position) entries
     const size_t evq_cap = pend_cap * 2 * KEEP;             // a node queues at most 2 evictions per candidate
     HIP_TRY(d_rows.alloc((size_t)Bmax * 4));
@@ -151,7 +134,6 @@ int32_t run_batches(cos_index *ix, u32 first, const uint8_t *max_level, std::vec
     HIP_TRY(h_status.alloc((size_t)Bmax * 4));
     HIP_TRY(h_cnt.alloc(4 * 4));
     VisTab vtab; // EXACT build mode: visited filters of the batch walks
-    struct VisFree { VisTab &v; ~VisFree() { if (v.bits) (void)hipFree(v.bits); if (v.log) (void)hipFree(v.log); } } visfree{vtab};
 
     la.L1 = L1;
     la.z_nodes = d_out_nodes.as<u32>();
@@ -274,19 +256,13 @@ extern "C" int32_t cos_index_build(cos_index *ix, uint32_t batch_size) {
     // ---- level skeletons: nodes of a level in ascending id, root last; every slot empty ------------------------
     for (u32 l = 0; l <= Ltop; l++) {
         LevelHost &H = ix->lv[l];
-        void *old[] = {H.d_adj_vec, H.d_adj_node, H.d_node_vec, H.d_child, H.d_adj_mag};
-        for (void *p : old) if (p) (void)hipFree(p);
-        H.d_adj_vec = H.d_adj_node = H.d_node_vec = H.d_child = nullptr;
-        H.d_adj_mag = nullptr;
-        H.host_valid = false;
-        H.nbr_ids.clear();
-        H.node_ids.clear();
+        H.release();
         for (u32 id = 0; id < n; id++)
             if (max_level[id] >= l) H.node_ids.push_back(id * ix->id_stride); // internal id of vector row `id`
         H.node_ids.push_back(COS_ROOT_ID);
         const u32 nl = (u32)H.node_ids.size(), M = H.M;
         if (M > 256) return cos_fail(COS_ERR_UNIMPLEMENTED, "more than 256 neighbour slots per node");
-        HIP_TRY(hipMalloc((void **)&H.d_adj_vec, (size_t)nl * M * 4));
+        HIP_TRY(H.d_adj_vec.alloc((size_t)nl * M));
         HIP_TRY(hipMemsetAsync(H.d_adj_vec, 0xFF, (size_t)nl * M * 4, st));
         if (l > 0) {
             std::vector<u32> node_vec(nl), child(nl);
@@ -295,11 +271,11 @@ extern "C" int32_t cos_index_build(cos_index *ix, uint32_t batch_size) {
                 node_vec[i] = H.node_ids[i] == COS_ROOT_ID ? n : H.node_ids[i] / ix->id_stride;
                 child[i] = (u32)(std::lower_bound(D.begin(), D.end(), H.node_ids[i]) - D.begin()); // same id one level down (vector_store.rs:897-903)
             }
-            HIP_TRY(hipMalloc((void **)&H.d_adj_node, (size_t)nl * M * 4));
+            HIP_TRY(H.d_adj_node.alloc((size_t)nl * M));
             HIP_TRY(hipMemsetAsync(H.d_adj_node, 0xFF, (size_t)nl * M * 4, st));
-            HIP_TRY(hipMalloc((void **)&H.d_node_vec, (size_t)nl * 4));
+            HIP_TRY(H.d_node_vec.alloc(nl));
             HIP_TRY(hipMemcpy(H.d_node_vec, node_vec.data(), (size_t)nl * 4, hipMemcpyHostToDevice));
-            HIP_TRY(hipMalloc((void **)&H.d_child, (size_t)nl * 4));
+            HIP_TRY(H.d_child.alloc(nl));
             HIP_TRY(hipMemcpy(H.d_child, child.data(), (size_t)nl * 4, hipMemcpyHostToDevice));
         }
         H.n = nl;
@@ -410,7 +386,7 @@ extern "C" int32_t cos_index_append(cos_index *ix, const float *raw, uint32_t m,
     if (ix->id_stride != 1u || ix->meta.mdim != 0u) return cos_fail(COS_ERR_UNIMPLEMENTED, "append on a collection with a metadata schema");
     if ((u64)ix->n + m >= 0xFFFFFFF0ull) return cos_fail(COS_ERR_INVALID, "too many vectors");
     const bool borrow = (flags & COS_UPLOAD_BORROW_DEVICE) != 0;
-    if (borrow != ix->raw_borrowed)
+    if (borrow != !ix->raw_own) // (an empty owner = the table is the caller's)
         return cos_fail(COS_ERR_INVALID, borrow ? "the index owns its raw rows: append host rows" : "the index borrows its raw rows: append with COS_UPLOAD_BORROW_DEVICE and the whole grown table");
     int32_t rc = cos_set_device(ix);
     if (rc) return rc;
@@ -428,12 +404,11 @@ extern "C" int32_t cos_index_append(cos_index *ix, const float *raw, uint32_t m,
 
     // ---- 1. the vector tables grow: rows [0, n0) stay, rows [n0, n1) are the new vectors, the root and the pseudo nodes' vector move behind them
     {
-        uint8_t *codes = nullptr;
-        float *mags = nullptr, *raw_mags = nullptr, *new_raw = nullptr;
-        struct Tmp { void **p[4]; ~Tmp() { for (auto q : p) if (q && *q) (void)hipFree(*q); } } tmp{{(void **)&codes, (void **)&mags, (void **)&raw_mags, (void **)&new_raw}};
-        HIP_TRY(hipMalloc((void **)&codes, ((size_t)n1 + 2) * rs));
-        HIP_TRY(hipMalloc((void **)&mags, ((size_t)n1 + 2) * 4));
-        HIP_TRY(hipMalloc((void **)&raw_mags, ((size_t)n1 + 2) * 4));
+        DevArr<uint8_t> codes;
+        DevArr<float> mags, raw_mags, new_raw;
+        HIP_TRY(codes.alloc(((size_t)n1 + 2) * rs));
+        HIP_TRY(mags.alloc((size_t)n1 + 2));
+        HIP_TRY(raw_mags.alloc((size_t)n1 + 2));
         HIP_TRY(hipMemcpyAsync(codes, ix->d_codes, (size_t)n0 * rs, hipMemcpyDeviceToDevice, st));
         HIP_TRY(hipMemcpyAsync(codes + (size_t)n1 * rs, ix->d_codes + (size_t)n0 * rs, 2 * rs, hipMemcpyDeviceToDevice, st));
         HIP_TRY(hipMemcpyAsync(mags, ix->d_mags, (size_t)n0 * 4, hipMemcpyDeviceToDevice, st));
@@ -444,19 +419,19 @@ extern "C" int32_t cos_index_append(cos_index *ix, const float *raw, uint32_t m,
         if (borrow) {
             new_rows = raw + (size_t)n0 * dim; // raw = the caller's whole grown table (device)
         } else {
-            HIP_TRY(hipMalloc((void **)&new_raw, (size_t)n1 * dim * 4));
+            HIP_TRY(new_raw.alloc((size_t)n1 * dim));
             HIP_TRY(hipMemcpyAsync(new_raw, ix->d_raw, (size_t)n0 * dim * 4, hipMemcpyDeviceToDevice, st));
             HIP_TRY(hipMemcpyAsync(new_raw + (size_t)n0 * dim, raw, (size_t)m * dim * 4, hipMemcpyHostToDevice, st));
             new_rows = new_raw + (size_t)n0 * dim;
         }
         HIP_TRY(launch_quantize_rows(ix->eng, new_rows, dim, m, ix->p.dim, ix->p.range_lo, ix->p.range_hi, codes + (size_t)n0 * rs, rs, mags + n0, raw_mags + n0, st));
         HIP_TRY(hipStreamSynchronize(st));
-        std::swap(codes, ix->d_codes);
-        std::swap(mags, ix->d_mags);
-        std::swap(raw_mags, ix->d_raw_mags);
-        if (borrow) ix->d_raw = const_cast<float *>(raw);
-        else std::swap(new_raw, ix->d_raw);
-        ix->n = n1; // (tmp frees the old arrays)
+        codes.swap(ix->d_codes);
+        mags.swap(ix->d_mags);
+        raw_mags.swap(ix->d_raw_mags);
+        new_raw.swap(ix->raw_own); // (borrowed: both empty)
+        ix->d_raw = borrow ? raw : ix->raw_own.p;
+        ix->n = n1; // (the locals free the old arrays)
     }
 
     // ---- 2. level draws of the new ids: the draws a full build would have given them
@@ -480,14 +455,13 @@ extern "C" int32_t cos_index_append(cos_index *ix, const float *raw, uint32_t m,
         H.node_ids.push_back(COS_ROOT_ID);
         H.host_valid = false;
         H.nbr_ids.clear();
-        if (H.d_adj_mag) { (void)hipFree(H.d_adj_mag); H.d_adj_mag = nullptr; }
-        u32 *adj_vec = nullptr, *adj_node = nullptr, *node_vec = nullptr, *child = nullptr;
+        H.d_adj_mag.reset();
+        DevArr<u32> adj_vec, adj_node, node_vec, child;
         DevBuf key, low_idx, low_key;
-        struct Tmp { void **p[4]; ~Tmp() { for (auto q : p) if (q && *q) (void)hipFree(*q); } } tmp{{(void **)&adj_vec, (void **)&adj_node, (void **)&node_vec, (void **)&child}};
-        HIP_TRY(hipMalloc((void **)&adj_vec, (size_t)nl1 * M * 4));
+        HIP_TRY(adj_vec.alloc((size_t)nl1 * M));
         HIP_TRY(launch_grow_rows(H.d_adj_vec, adj_vec, nl0, nl1, M, n0, n1, ROW_EMPTY, st)); // vector rows: the root is row n
         if (l > 0) {
-            HIP_TRY(hipMalloc((void **)&adj_node, (size_t)nl1 * M * 4));
+            HIP_TRY(adj_node.alloc((size_t)nl1 * M));
             HIP_TRY(launch_grow_rows(H.d_adj_node, adj_node, nl0, nl1, M, nl0 - 1, nl1 - 1, ROW_EMPTY, st)); // node indices: the root is the last node
             // node -> vector row and node -> node one level down: old nodes keep theirs, the root's follow it, the new nodes' are known
             std::vector<u32> nv(add[l] + 1), ch(add[l] + 1);
@@ -499,8 +473,8 @@ extern "C" int32_t cos_index_append(cos_index *ix, const float *raw, uint32_t m,
             }
             nv[k] = n1;                       // the root's vector row
             ch[k] = ix->lv[l - 1].n - 1;      // ... and its node one level down
-            HIP_TRY(hipMalloc((void **)&node_vec, (size_t)nl1 * 4));
-            HIP_TRY(hipMalloc((void **)&child, (size_t)nl1 * 4));
+            HIP_TRY(node_vec.alloc(nl1));
+            HIP_TRY(child.alloc(nl1));
             HIP_TRY(hipMemcpyAsync(node_vec, H.d_node_vec, (size_t)(nl0 - 1) * 4, hipMemcpyDeviceToDevice, st));
             HIP_TRY(hipMemcpyAsync(child, H.d_child, (size_t)(nl0 - 1) * 4, hipMemcpyDeviceToDevice, st));
             HIP_TRY(hipMemcpy(node_vec + (nl0 - 1), nv.data(), nv.size() * 4, hipMemcpyHostToDevice));
@@ -515,14 +489,14 @@ extern "C" int32_t cos_index_append(cos_index *ix, const float *raw, uint32_t m,
         HIP_TRY(ix->link.owner[l].alloc((size_t)nl1 * 4));
         HIP_TRY(hipMemsetAsync(ix->link.owner[l].p, 0, (size_t)nl1 * 4, st)); // a new tag epoch (run_batches starts at round 1)
         HIP_TRY(hipStreamSynchronize(st));
-        std::swap(adj_vec, H.d_adj_vec);
-        std::swap(adj_node, H.d_adj_node);
-        std::swap(node_vec, H.d_node_vec);
-        std::swap(child, H.d_child);
-        std::swap(key.p, ix->link.key[l].p);
-        std::swap(low_idx.p, ix->link.low_idx[l].p);
-        std::swap(low_key.p, ix->link.low_key[l].p);
-        H.n = nl1; // (tmp / the DevBufs free the old arrays)
+        adj_vec.swap(H.d_adj_vec);
+        adj_node.swap(H.d_adj_node);
+        node_vec.swap(H.d_node_vec);
+        child.swap(H.d_child);
+        key.swap(ix->link.key[l]);
+        low_idx.swap(ix->link.low_idx[l]);
+        low_key.swap(ix->link.low_key[l]);
+        H.n = nl1; // (the locals free the old arrays)
     }
     // child links INTO a level that grew: level l's root entry was written above; the old nodes' children are old nodes (unchanged)
 
@@ -649,7 +623,6 @@ extern "C" int32_t cos_index_delete(cos_index *ix, const uint32_t *ids, uint32_t
     HIP_TRY(d_ds.alloc((size_t)KEEP * 4));
     HIP_TRY(d_dst.alloc((size_t)KEEP * 4));
     VisTab vtab;
-    struct VisFree { VisTab &v; ~VisFree() { if (v.bits) (void)hipFree(v.bits); if (v.log) (void)hipFree(v.log); } } visfree{vtab};
     std::vector<u32> h_ids((size_t)L1 * KEEP), h_nodes((size_t)L1 * KEEP), h_counts(L1), h_dn(L1), h_ust(L1);
     std::vector<std::vector<u32>> node_vec(L1); // slow path only: node -> vector row, fetched once per level
     // (the locality order stays a permutation of the level's nodes and the level table's operand holds code rows: both still valid)
@@ -855,12 +828,12 @@ extern "C" int32_t cos_index_build_meta(cos_index *ix, uint32_t n_nodes, const u
             }
         }
         tab_of[l] = std::move(rows);
-        auto up = [&](u32 *&dst, const std::vector<u32> &src) -> hipError_t {
-            hipError_t e = hipMalloc((void **)&dst, std::max<size_t>(src.size(), 1) * 4);
+        auto up = [&](DevArr<u32> &dst, const std::vector<u32> &src) -> hipError_t {
+            hipError_t e = dst.alloc(src.size());
             return e == hipSuccess ? hipMemcpy(dst, src.data(), src.size() * 4, hipMemcpyHostToDevice) : e;
         };
-        HIP_TRY(hipMalloc((void **)&H.d_adj_vec, (size_t)nl * M * 4));
-        HIP_TRY(hipMalloc((void **)&H.d_adj_node, (size_t)nl * M * 4));
+        HIP_TRY(H.d_adj_vec.alloc((size_t)nl * M));
+        HIP_TRY(H.d_adj_node.alloc((size_t)nl * M));
         HIP_TRY(hipMemsetAsync(H.d_adj_vec, 0xFF, (size_t)nl * M * 4, st));
         HIP_TRY(hipMemsetAsync(H.d_adj_node, 0xFF, (size_t)nl * M * 4, st));
         HIP_TRY(up(H.d_node_vec, node_vec));

@@ -189,85 +189,33 @@ IndexDev cos_make_meta_dev(const cos_index *ix) {
     return d;
 }
 
-static void free_level(LevelHost &l) {
-    if (l.d_adj_vec) (void)hipFree(l.d_adj_vec);
-    if (l.d_adj_node) (void)hipFree(l.d_adj_node);
-    if (l.d_node_vec) (void)hipFree(l.d_node_vec);
-    if (l.d_child) (void)hipFree(l.d_child);
-    if (l.d_node_id) (void)hipFree(l.d_node_id);
-    if (l.d_node_meta) (void)hipFree(l.d_node_meta);
-    if (l.d_adj_mag) (void)hipFree(l.d_adj_mag);
-    l.d_adj_mag = nullptr;
-    l.d_node_id = l.d_node_meta = nullptr;
-    l.d_adj_vec = l.d_adj_node = l.d_node_vec = l.d_child = nullptr;
-    l.n = 0;
-    l.node_ids.clear();
-    l.nbr_ids.clear();
-    l.host_valid = false;
-}
-static void free_ws(Workspace *w) {
-    void *ptrs[] = {w->fin_flags, w->stats2, w->tab, w->qsums, w->qdig, w->q_codes, w->q_mags, w->q_raw_mags, w->walk_ids, w->walk_counts, w->walk_sims, w->walk_status, w->stats,
-                    w->rerank_rows, w->vis.bits, w->vis.log, w->d_queries, w->d_out_ids, w->d_out_counts, w->d_out_scores, w->d_out_status, w->f_buf};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    cosdev::walk_order_free(w->order);
-    for (auto &e : w->ev) if (e) (void)hipEventDestroy(e);
-    if (w->walk_done) (void)hipEventDestroy(w->walk_done);
-    if (w->walk_fin) (void)hipEventDestroy(w->walk_fin);
-    if (w->last_range) (void)hipEventDestroy(w->last_range);
-    if (w->prep_done) (void)hipEventDestroy(w->prep_done);
-    if (w->walk_stream) (void)hipStreamDestroy(w->walk_stream);
-    delete w;
-}
-
 void cos_meta_free_levels(cos_index *ix) {
-    for (auto &l : ix->meta.lv) free_level(l);
+    for (auto &l : ix->meta.lv) l.release();
 }
 
 // the whole pseudo-root component: levels, node table, metadata dimensions, and the id stride it imposed on the base graph.
 // After this the handle is a collection without a metadata schema again (cos_index_enable_metadata re-creates row n + 1).
 static void reset_meta(cos_index *ix) {
-    for (auto &l : ix->meta.lv) free_level(l);
-    if (ix->meta.d_mbits) (void)hipFree(ix->meta.d_mbits);
-    if (ix->meta.d_mmags) (void)hipFree(ix->meta.d_mmags);
-    ix->meta.d_mbits = nullptr;
-    ix->meta.d_mmags = nullptr;
+    for (auto &l : ix->meta.lv) l.release();
+    ix->meta.d_mbits.reset();
+    ix->meta.d_mmags.reset();
     ix->meta.node_ids.clear();
     ix->meta.mdim = 0;
     ix->id_stride = 1;
-}
-
-static void free_pipe(HostPipe *hp) {
-    void *ptrs[] = {hp->d_q, hp->d_ids, hp->d_counts, hp->d_scores, hp->d_status};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    for (hipEvent_t e : hp->ev_in) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : hp->ev_walk) if (e) (void)hipEventDestroy(e);
-    hipStream_t sts[] = {hp->s[0], hp->s[1], hp->sc, hp->sf};
-    for (hipStream_t st : sts) if (st) (void)hipStreamDestroy(st);
-    delete hp;
 }
 
 extern "C" int32_t cos_index_destroy(cos_index *ix) {
     if (!ix) return COS_OK;
     (void)hipSetDevice(ix->p.device);
     (void)hipDeviceSynchronize();
-    for (auto &kv : ix->ws) free_ws(kv.second);
+    // on the handle's device, after the drain above, in this order; what is left (vectors, order ranks, level-table operands,
+    // link state) goes with the members of the handle
+    ix->ws.clear();
     cos_flat_ws_release(ix);
-    for (HostPipe *hp : ix->pipes_all) free_pipe(hp);
+    ix->pipes_all.clear();
     cos_coalesce_release(ix);
-    for (auto &l : ix->lv) free_level(l);
-    for (auto &l : ix->meta.lv) free_level(l);
-    if (ix->meta.d_mbits) (void)hipFree(ix->meta.d_mbits);
-    if (ix->meta.d_mmags) (void)hipFree(ix->meta.d_mmags);
-    if (ix->d_raw && !ix->raw_borrowed) (void)hipFree(ix->d_raw);
-    if (ix->d_raw_mags) (void)hipFree(ix->d_raw_mags);
-    if (ix->d_codes) (void)hipFree(ix->d_codes);
-    if (ix->d_mags) (void)hipFree(ix->d_mags);
-    for (u32 *p : ix->d_order_rank) if (p) (void)hipFree(p);
-    for (auto &t : ix->table_sets) { // level-table operands (the current one is among them)
-        if (t.tcodes) (void)hipFree(t.tcodes);
-        if (t.tmags) (void)hipFree(t.tmags);
-        if (t.tcsums) (void)hipFree(t.tcsums);
-    }
+    for (auto &l : ix->lv) l.release();
+    reset_meta(ix);
     if (ix->own_stream) (void)hipStreamDestroy(ix->own_stream);
     delete ix;
     return COS_OK;
@@ -281,55 +229,44 @@ extern "C" int32_t cos_index_upload_vectors(cos_index *ix, const float *raw, uin
     if (n >= 0xFFFFFFF0u) return cos_fail(COS_ERR_INVALID, "too many vectors");
     int32_t rc = cos_set_device(ix);
     if (rc) return rc;
-    if (ix->d_raw && !ix->raw_borrowed) (void)hipFree(ix->d_raw);
-    if (ix->d_raw_mags) (void)hipFree(ix->d_raw_mags);
-    if (ix->d_codes) (void)hipFree(ix->d_codes);
-    if (ix->d_mags) (void)hipFree(ix->d_mags);
-    ix->d_raw = nullptr; ix->d_raw_mags = nullptr; ix->d_codes = nullptr; ix->d_mags = nullptr;
+    ix->d_raw = nullptr;
+    ix->raw_own.reset(); ix->d_raw_mags.reset(); ix->d_codes.reset(); ix->d_mags.reset();
     ix->have_vectors = false;
     cos_flat_ws_release(ix); // cached sums of the stored codes, scan buffers sized for the old corpus
     ix->have_root = false;
-    for (auto &l : ix->lv) free_level(l); // a graph refers to vector rows: new vectors invalidate it
+    for (auto &l : ix->lv) l.release(); // a graph refers to vector rows: new vectors invalidate it
     ix->order_rank_valid = false;
     ix->level_table_valid = false;
     ix->adj_mag_valid = false;
     ix->link.release();
     reset_meta(ix);                       // ... and so do the pseudo-root component, its node table and the id stride
     const u64 dim = ix->p.dim;
-    struct Rollback { // a failed upload leaves the handle empty instead of half-populated
-        cos_index *ix;
-        bool armed = true;
-        ~Rollback() {
-            if (!armed) return;
-            if (ix->d_raw && !ix->raw_borrowed) (void)hipFree(ix->d_raw);
-            if (ix->d_raw_mags) (void)hipFree(ix->d_raw_mags);
-            if (ix->d_codes) (void)hipFree(ix->d_codes);
-            if (ix->d_mags) (void)hipFree(ix->d_mags);
-            ix->d_raw = nullptr; ix->d_raw_mags = nullptr; ix->d_codes = nullptr; ix->d_mags = nullptr;
-            ix->raw_borrowed = false;
-        }
-    } rollback{ix};
+    // a failed upload leaves the handle empty instead of half-populated: the tables are built in locals and move in at the end
+    const float *d_raw = raw;
+    DevArr<float> raw_own, raw_mags, mags;
+    DevArr<uint8_t> codes;
     if (flags & COS_UPLOAD_BORROW_DEVICE) {
         // the caller's producer (e.g. a torch kernel on another stream) may still be writing the buffer: our streams
         // are non-blocking, so drain the device once before the quantize kernel reads it
         HIP_TRY(hipDeviceSynchronize());
-        ix->d_raw = const_cast<float *>(raw);
-        ix->raw_borrowed = true;
     } else {
-        HIP_TRY(hipMalloc(&ix->d_raw, (size_t)n * dim * 4));
-        HIP_TRY(hipMemcpy(ix->d_raw, raw, (size_t)n * dim * 4, hipMemcpyHostToDevice));
-        ix->raw_borrowed = false;
+        HIP_TRY(raw_own.alloc((size_t)n * dim));
+        HIP_TRY(hipMemcpy(raw_own, raw, (size_t)n * dim * 4, hipMemcpyHostToDevice));
+        d_raw = raw_own;
     }
     // rows [0, n) = vectors, row n = the root, row n + 1 = the vector shared by the pseudo nodes of a metadata collection
-    HIP_TRY(hipMalloc(&ix->d_raw_mags, ((size_t)n + 2) * 4));
-    HIP_TRY(hipMalloc(&ix->d_codes, ((size_t)n + 2) * ix->row_stride));
-    HIP_TRY(hipMalloc(&ix->d_mags, ((size_t)n + 2) * 4));
-    HIP_TRY(hipMemsetAsync(ix->d_codes + (size_t)n * ix->row_stride, 0, 2 * ix->row_stride, ix->own_stream));
-    HIP_TRY(hipMemsetAsync(ix->d_mags + n, 0, 8, ix->own_stream));
-    HIP_TRY(launch_quantize_rows(ix->eng, ix->d_raw, dim, n, ix->p.dim, ix->p.range_lo, ix->p.range_hi, ix->d_codes, ix->row_stride,
-                                 ix->d_mags, ix->d_raw_mags, ix->own_stream));
+    HIP_TRY(raw_mags.alloc((size_t)n + 2));
+    HIP_TRY(codes.alloc(((size_t)n + 2) * ix->row_stride));
+    HIP_TRY(mags.alloc((size_t)n + 2));
+    HIP_TRY(hipMemsetAsync(codes + (size_t)n * ix->row_stride, 0, 2 * ix->row_stride, ix->own_stream));
+    HIP_TRY(hipMemsetAsync(mags + n, 0, 8, ix->own_stream));
+    HIP_TRY(launch_quantize_rows(ix->eng, d_raw, dim, n, ix->p.dim, ix->p.range_lo, ix->p.range_hi, codes, ix->row_stride, mags, raw_mags, ix->own_stream));
     HIP_TRY(hipStreamSynchronize(ix->own_stream));
-    rollback.armed = false;
+    ix->d_raw = d_raw;
+    ix->raw_own = std::move(raw_own);
+    ix->d_raw_mags = std::move(raw_mags);
+    ix->d_codes = std::move(codes);
+    ix->d_mags = std::move(mags);
     ix->n = n;
     ix->have_vectors = true;
     ix->have_root = false;
@@ -381,16 +318,14 @@ static int32_t push_level_to_device(cos_index *ix, u32 level) {
             if (level > 0) adj_node[(size_t)i * M + j] = (u32)(it - L.node_ids.begin());
         }
     }
-    if (L.d_adj_vec) (void)hipFree(L.d_adj_vec);
-    if (L.d_adj_node) (void)hipFree(L.d_adj_node);
-    if (L.d_node_vec) (void)hipFree(L.d_node_vec);
-    L.d_adj_vec = L.d_adj_node = L.d_node_vec = nullptr;
-    HIP_TRY(hipMalloc(&L.d_adj_vec, adj_vec.size() * 4));
+    L.d_adj_node.reset();
+    L.d_node_vec.reset();
+    HIP_TRY(L.d_adj_vec.alloc(adj_vec.size()));
     HIP_TRY(hipMemcpy(L.d_adj_vec, adj_vec.data(), adj_vec.size() * 4, hipMemcpyHostToDevice));
     if (level > 0) {
-        HIP_TRY(hipMalloc(&L.d_adj_node, adj_node.size() * 4));
+        HIP_TRY(L.d_adj_node.alloc(adj_node.size()));
         HIP_TRY(hipMemcpy(L.d_adj_node, adj_node.data(), adj_node.size() * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMalloc(&L.d_node_vec, node_vec.size() * 4));
+        HIP_TRY(L.d_node_vec.alloc(node_vec.size()));
         HIP_TRY(hipMemcpy(L.d_node_vec, node_vec.data(), node_vec.size() * 4, hipMemcpyHostToDevice));
     }
     L.n = n;
@@ -410,27 +345,24 @@ static int32_t push_level0_to_device(cos_index *ix, const u32 *nbr) {
     LevelHost &L = ix->lv[0];
     const u32 n = (u32)L.node_ids.size(), M = L.M;
     const size_t slots = (size_t)n * M, chunk = (size_t)32 << 20;
-    struct Staging {
-        u32 *buf[2] = {nullptr, nullptr};
+    struct Staging { // (declared after the buffers it guards: the copies are waited for before the buffers go)
         hipEvent_t done[2] = {nullptr, nullptr};
         ~Staging() {
-            for (int b = 0; b < 2; b++) {
+            for (int b = 0; b < 2; b++)
                 if (done[b]) (void)hipEventSynchronize(done[b]), (void)hipEventDestroy(done[b]);
-                if (buf[b]) (void)hipHostFree(buf[b]);
-            }
         }
-    } stg;
-    if (L.d_adj_vec) (void)hipFree(L.d_adj_vec);
-    L.d_adj_vec = nullptr;
-    HIP_TRY(hipMalloc(&L.d_adj_vec, slots * 4));
+    };
+    PinArr<u32> buf[2];
+    Staging stg;
+    HIP_TRY(L.d_adj_vec.alloc(slots));
     for (int b = 0; b < 2; b++) {
-        HIP_TRY(hipHostMalloc((void **)&stg.buf[b], std::min(chunk, slots) * 4, hipHostMallocDefault));
+        HIP_TRY(buf[b].alloc(std::min(chunk, slots)));
         HIP_TRY(hipEventCreateWithFlags(&stg.done[b], hipEventDisableTiming));
     }
     const u32 nt = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
     for (size_t c0 = 0, k = 0; c0 < slots; c0 += chunk, k++) {
         const size_t m = std::min(chunk, slots - c0);
-        u32 *out = stg.buf[k & 1];
+        u32 *out = buf[k & 1];
         if (k >= 2) HIP_TRY(hipEventSynchronize(stg.done[k & 1])); // the copy that last read this buffer has finished
         std::vector<int> bad(nt, 0);
         auto convert = [&](u32 t) {
@@ -478,9 +410,7 @@ static int32_t resolve_children(cos_index *ix, u32 level) {
         if (it == D.node_ids.end() || *it != L.node_ids[i]) return cos_fail(COS_ERR_INVALID, "node %u of level %u is missing on level %u", L.node_ids[i], level, level - 1);
         child[i] = (u32)(it - D.node_ids.begin());
     }
-    if (L.d_child) (void)hipFree(L.d_child);
-    L.d_child = nullptr;
-    HIP_TRY(hipMalloc(&L.d_child, child.size() * 4));
+    HIP_TRY(L.d_child.alloc(child.size()));
     HIP_TRY(hipMemcpy(L.d_child, child.data(), child.size() * 4, hipMemcpyHostToDevice));
     return COS_OK;
 }
@@ -507,7 +437,7 @@ extern "C" int32_t cos_index_upload_graph_level(cos_index *ix, uint32_t level, u
         L.nbr_ids.assign(nbr_ids, nbr_ids + (size_t)n_nodes * L.M);
         rc = push_level_to_device(ix, level);
     }
-    if (rc) { free_level(L); return rc; }
+    if (rc) { L.release(); return rc; }
     rc = resolve_children(ix, level);
     if (rc == COS_OK) rc = resolve_children(ix, level + 1);
     if (rc == COS_OK && graph_ready(ix)) rc = cos_prepare_walk_plans(ix); // the last level of a graph: its order / level tables now, not under a search
@@ -703,13 +633,6 @@ extern "C" int32_t cos_index_enable_timing(cos_index *ix, int32_t on) {
 // ------------------------------------------------------------------------------------------------
 // workspaces (one per stream; same-stream work is ordered, so reuse is safe)
 // ------------------------------------------------------------------------------------------------
-template <typename T>
-static hipError_t regrow(T *&p, size_t count) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    return hipMalloc((void **)&p, count * sizeof(T));
-}
-
 int32_t vis_tab_prepare(VisTab &vt, const cos_index *ix, u32 B, u32 ef, hipStream_t st, WalkArgs &wa) {
     const u32 M = std::max(ix->p.level0_neighbors_count, ix->p.neighbors_count);
     // a level inserts its entry node plus at most M neighbours per pop, and pops at most ef times
@@ -719,28 +642,16 @@ int32_t vis_tab_prepare(VisTab &vt, const cos_index *ix, u32 B, u32 ef, hipStrea
     const u32 words = (max_nodes + 31) / 32 + 1;
     if (log_cap > 0xFFFFFFFFull) return cos_fail(COS_ERR_INVALID, "ef too large");
     const size_t need_bits = (size_t)B * words, need_log = (size_t)B * log_cap;
-    if (need_bits > vt.bits_cap || need_log > vt.log_cap) {
+    if (need_bits > vt.bits.cap || need_log > vt.log.cap) {
         HIP_TRY(hipStreamSynchronize(st));
-        if (need_bits > vt.bits_cap) {
-            if (vt.bits) HIP_TRY(hipFree(vt.bits));
-            vt.bits = nullptr;
-            vt.bits_cap = 0;
-            HIP_TRY(hipMalloc((void **)&vt.bits, need_bits * 4));
-            vt.bits_cap = need_bits;
-        }
-        if (need_log > vt.log_cap) {
-            if (vt.log) HIP_TRY(hipFree(vt.log));
-            vt.log = nullptr;
-            vt.log_cap = 0;
-            HIP_TRY(hipMalloc((void **)&vt.log, need_log * 4));
-            vt.log_cap = need_log;
-        }
+        if (need_bits > vt.bits.cap) vt.zeroed = false; // (before the attempt: a bitset regrown after a failure is a new allocation too)
+        HIP_TRY(vt.bits.grow(need_bits));
+        HIP_TRY(vt.log.grow(need_log));
     }
     // the per-query stride may change (other B / graph), which is harmless: the whole allocation is all-zero between launches
-    if (!vt.zeroed || vt.zeroed_cap != vt.bits_cap) {
-        HIP_TRY(hipMemsetAsync(vt.bits, 0, vt.bits_cap * 4, st));
+    if (!vt.zeroed) {
+        HIP_TRY(hipMemsetAsync(vt.bits, 0, vt.bits.cap * 4, st));
         vt.zeroed = true;
-        vt.zeroed_cap = vt.bits_cap;
     }
     wa.vis_bits = vt.bits;
     wa.vis_log = vt.log;
@@ -765,8 +676,7 @@ int32_t vis_tab_prepare(VisTab &vt, const cos_index *ix, u32 B, u32 ef, hipStrea
 static int32_t ensure_order_rank(cos_index *ix) {
     if (ix->order_rank_valid) return COS_OK;
     for (u32 l = 0; l < cosdev::MAX_LEVELS; l++) {
-        if (ix->d_order_rank[l]) (void)hipFree(ix->d_order_rank[l]);
-        ix->d_order_rank[l] = nullptr;
+        ix->d_order_rank[l].reset();
         ix->order_rank_n[l] = 0;
     }
     ix->order_levels.clear();
@@ -811,7 +721,7 @@ static int32_t ensure_order_rank(cos_index *ix) {
         };
         dfs_from(n - 1); // the root (last node of every level): where every walk of the level starts
         for (u32 v = 0; v < n; v++) if (!seen[v]) dfs_from(v);
-        HIP_TRY(hipMalloc((void **)&ix->d_order_rank[kl], (size_t)n * 4));
+        HIP_TRY(ix->d_order_rank[kl].alloc(n));
         HIP_TRY(hipMemcpy(ix->d_order_rank[kl], rank.data(), (size_t)n * 4, hipMemcpyHostToDevice));
         ix->order_rank_n[kl] = n;
     }
@@ -828,16 +738,6 @@ static void clear_current_table(cos_index *ix) {
     ix->table_cols = 0;
     ix->table_level_min = 0;
     ix->table_stride = 0;
-}
-// every operand of the handle (the graph changed, or the handle dies): exclusive entry points only
-static void free_level_tables(cos_index *ix) {
-    for (auto &t : ix->table_sets) {
-        if (t.tcodes) (void)hipFree(t.tcodes);
-        if (t.tmags) (void)hipFree(t.tmags);
-        if (t.tcsums) (void)hipFree(t.tcsums);
-    }
-    ix->table_sets.clear();
-    clear_current_table(ix);
 }
 static u32 walk_table_max_cols(const cos_index *ix) { // COS_WALK_TABLE_AUTO = sized from ef_search and neighbors_count (ensure_level_table)
     const long long env = cosdev::tune_or(cosdev::TUNE_WALK_TABLE_COLS, -1);
@@ -872,7 +772,7 @@ static int32_t ensure_level_table(cos_index *ix) {
     if (ix->level_table_valid && ix->table_built_for_key == key) return COS_OK;
     if (!ix->level_table_valid) { // a new graph: the old graph's operands go (graph changes are exclusive: no search is in flight)
         HIP_TRY(hipDeviceSynchronize());
-        free_level_tables(ix);
+        ix->table_sets.clear();
     }
     // (from here on every path leaves a definite state for this (graph, key): a table, or "none" — which is also what an operand
     // that could not be allocated leaves, see below)
@@ -900,28 +800,23 @@ static int32_t ensure_level_table(cos_index *ix) {
     }
     if (lmin == 0) return COS_OK;
     HIP_TRY(hipDeviceSynchronize()); // a build or an upload on another stream may still be writing the levels
-    uint8_t *tcodes = nullptr;
-    float *tmags = nullptr;
-    u32 *tcsums = nullptr;
-    auto build = [&]() -> hipError_t { // (a failure leaves the handle without a table for this key — same results — and frees what it had allocated)
-        hipError_t e = hipMalloc((void **)&tcodes, (size_t)cols * ix->row_stride);
-        if (e == hipSuccess) e = hipMalloc((void **)&tmags, (size_t)cols * 4);
-        if (e == hipSuccess) e = hipMalloc((void **)&tcsums, (size_t)cols * 4);
+    cos_index::TableSet t;
+    auto build = [&]() -> hipError_t { // (a failure leaves the handle without a table for this key — same results — and `t` frees what it had allocated)
+        hipError_t e = t.tcodes.alloc((size_t)cols * ix->row_stride);
+        if (e == hipSuccess) e = t.tmags.alloc(cols);
+        if (e == hipSuccess) e = t.tcsums.alloc(cols);
         u32 c0 = 0;
         for (u32 l = Ltop; l >= lmin && e == hipSuccess; l--) {
             ix->table_col0[l] = c0;
-            e = cosdev::launch_level_table_gather(ix->d_codes, ix->d_mags, ix->row_stride, ix->lv[l].d_node_vec, ix->lv[l].n, c0, tcodes, tmags, nullptr);
+            e = cosdev::launch_level_table_gather(ix->d_codes, ix->d_mags, ix->row_stride, ix->lv[l].d_node_vec, ix->lv[l].n, c0, t.tcodes, t.tmags, nullptr);
             c0 += ix->lv[l].n;
         }
-        if (e == hipSuccess) e = cosdev::launch_code_sums(tcodes, ix->row_stride, cols, tcsums, nullptr);
+        if (e == hipSuccess) e = cosdev::launch_code_sums(t.tcodes, ix->row_stride, cols, t.tcsums, nullptr);
         if (e == hipSuccess) e = hipDeviceSynchronize();
         return e;
     };
     if (const hipError_t e = build(); e != hipSuccess) {
         (void)hipDeviceSynchronize();
-        if (tcodes) (void)hipFree(tcodes);
-        if (tmags) (void)hipFree(tmags);
-        if (tcsums) (void)hipFree(tcsums);
         if (e == hipErrorOutOfMemory) { // the table is an optimisation: short of HBM the walk reads rows (same results)
             (void)hipGetLastError();
             return COS_OK;
@@ -929,22 +824,18 @@ static int32_t ensure_level_table(cos_index *ix) {
         ix->level_table_valid = false; // anything else is a real failure: reported, and retried by the next search
         HIP_TRY(e);
     }
-    ix->d_tcodes = tcodes;
-    ix->d_tmags = tmags;
-    ix->d_tcsums = tcsums;
+    ix->d_tcodes = t.tcodes;
+    ix->d_tmags = t.tmags;
+    ix->d_tcsums = t.tcsums;
     ix->table_cols = cols;
     ix->table_level_min = lmin;
     ix->table_stride = ((u64)cols + 31) / 32 * 32;
-    cos_index::TableSet t;
     t.key = key;
     t.level_min = lmin;
     t.cols = cols;
     t.stride = ix->table_stride;
     memcpy(t.col0, ix->table_col0, sizeof(t.col0));
-    t.tcodes = ix->d_tcodes;
-    t.tmags = ix->d_tmags;
-    t.tcsums = ix->d_tcsums;
-    ix->table_sets.push_back(t);
+    ix->table_sets.push_back(std::move(t));
     return COS_OK;
 }
 
@@ -984,17 +875,15 @@ static int32_t ensure_adj_mags(cos_index *ix) {
         return COS_OK; // (walk_general_kernel's indexes: it gathers the norms)
     HIP_TRY(hipDeviceSynchronize()); // a build or an upload on another stream may still be writing the adjacency
     for (u32 l = 0; l <= ix->p.num_layers; l++) {
-        LevelHost &H = ix->lv[l];
-        if (H.d_adj_mag) (void)hipFree(H.d_adj_mag);
-        H.d_adj_mag = nullptr;
+        ix->lv[l].d_adj_mag.reset();
     }
     for (u32 l = 0; l <= ix->p.num_layers; l++) {
         LevelHost &H = ix->lv[l];
         const u32 slots = std::min(H.M, ix->p.shortlist_size);
-        const hipError_t e = hipMalloc((void **)&H.d_adj_mag, (size_t)H.n * slots * 4);
+        const hipError_t e = H.d_adj_mag.alloc((size_t)H.n * slots);
         if (e == hipErrorOutOfMemory) {
             (void)hipGetLastError();
-            for (u32 k = 0; k <= l; k++) { if (ix->lv[k].d_adj_mag) (void)hipFree(ix->lv[k].d_adj_mag); ix->lv[k].d_adj_mag = nullptr; }
+            for (u32 k = 0; k < l; k++) ix->lv[k].d_adj_mag.reset();
             return COS_OK; // adj_mag_valid stays false: the next graph change tries again
         }
         HIP_TRY(e);
@@ -1030,34 +919,41 @@ extern "C" int32_t cos_index_walk_order_cuts(cos_index *ix, uint32_t *out_levels
     return COS_OK;
 }
 
+// The norms beside the adjacency (LevelDev::adj_mag), invalidated by a root replaced on a live graph, are refilled by the first launch
+// of ADJ_MAG_REFILL_MIN_B queries (get_workspace) but only read by launches of ADJ_MAG_USE_MIN_B (run_search): the two disagree
+// (ADVICE.md), so a launch in between pays for a refill it does not use.
+static constexpr u32 ADJ_MAG_REFILL_MIN_B = 1024u, ADJ_MAG_USE_MIN_B = 4096u;
+
 static int32_t get_workspace(cos_index *ix, void *key, hipStream_t st, u32 B, u32 top_k, bool host_api, Workspace **out) {
     std::lock_guard<std::mutex> g(ix->mu);
-    Workspace *&w = ix->ws[key];
-    if (!w) w = new Workspace();
+    std::unique_ptr<Workspace> &slot = ix->ws[key];
+    if (!slot) slot.reset(new Workspace());
+    Workspace *w = slot.get();
     const u32 L1 = ix->p.num_layers + 1;
     if (B > w->capB) {
         u32 cap = std::max(B, 64u);
         HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(regrow(w->q_codes, (size_t)cap * ix->row_stride));
-        HIP_TRY(regrow(w->q_mags, cap));
-        HIP_TRY(regrow(w->q_raw_mags, cap));
-        HIP_TRY(regrow(w->walk_ids, (size_t)cap * L1 * KEEP_SEARCH));
-        HIP_TRY(regrow(w->walk_sims, (size_t)cap * L1 * KEEP_SEARCH));
-        HIP_TRY(regrow(w->walk_counts, (size_t)cap * L1));
-        HIP_TRY(regrow(w->walk_status, cap));
-        HIP_TRY(regrow(w->stats, (size_t)cap * 4));
-        HIP_TRY(regrow(w->stats2, (size_t)cap * 4));
-        HIP_TRY(regrow(w->qsums, cap));
-        if (ix->eng == ENG_Q2) HIP_TRY(regrow(w->qdig, (size_t)cap * (ix->row_stride / 16) * 64)); // the table GEMM's digit rows of the queries
-        HIP_TRY(regrow(w->fin_flags, (size_t)cap + 1));
-        HIP_TRY(regrow(w->rerank_rows, cap));
-        HIP_TRY(regrow(w->d_queries, (size_t)cap * ix->p.dim));
-        HIP_TRY(regrow(w->d_out_counts, cap));
-        HIP_TRY(regrow(w->d_out_status, cap));
-        w->capB = cap;
+        w->capB = 0; // (a growth that fails half way leaves a workspace for no query: the next call grows all of it again)
         w->cap_topk = 0;
+        HIP_TRY(w->q_codes.alloc((size_t)cap * ix->row_stride));
+        HIP_TRY(w->q_mags.alloc(cap));
+        HIP_TRY(w->q_raw_mags.alloc(cap));
+        HIP_TRY(w->walk_ids.alloc((size_t)cap * L1 * KEEP_SEARCH));
+        HIP_TRY(w->walk_sims.alloc((size_t)cap * L1 * KEEP_SEARCH));
+        HIP_TRY(w->walk_counts.alloc((size_t)cap * L1));
+        HIP_TRY(w->walk_status.alloc(cap));
+        HIP_TRY(w->stats.alloc((size_t)cap * 4));
+        HIP_TRY(w->stats2.alloc((size_t)cap * 4));
+        HIP_TRY(w->qsums.alloc(cap));
+        if (ix->eng == ENG_Q2) HIP_TRY(w->qdig.alloc((size_t)cap * (ix->row_stride / 16) * 64)); // the table GEMM's digit rows of the queries
+        HIP_TRY(w->fin_flags.alloc((size_t)cap + 1));
+        HIP_TRY(w->rerank_rows.alloc(cap));
+        HIP_TRY(w->d_queries.alloc((size_t)cap * ix->p.dim));
+        HIP_TRY(w->d_out_counts.alloc(cap));
+        HIP_TRY(w->d_out_status.alloc(cap));
+        w->capB = cap;
     }
-    if (!ix->adj_mag_valid && B >= 1024u) // (a root replaced on a live graph; small launches keep their gathers until a big one pays for the refill)
+    if (!ix->adj_mag_valid && B >= ADJ_MAG_REFILL_MIN_B) // (a root replaced on a live graph; small launches keep their gathers until a big one pays for the refill)
         if (int32_t rc = ensure_adj_mags(ix)) return rc;
     if (ix->walk_order_min_B && B >= ix->walk_order_min_B && ix->p.ef_search <= 256u) { // wider beams keep the single launch (run_search)
         if (w->order.cap < w->capB) {
@@ -1069,31 +965,28 @@ static int32_t get_workspace(cos_index *ix, void *key, hipStream_t st, u32 B, u3
     if (const u32 tmin = walk_table_min_B(ix); tmin && (B >= tmin || B <= ix->lat4_max_B)) { // from min_queries on, and the four-wave latency kernel's launches
         if (int32_t rc = ensure_level_table(ix)) return rc;
         const size_t need = (size_t)w->capB * ix->table_stride;
-        if (need > w->tab_cap) {
+        if (need > w->tab.cap) {
             // every workspace (one per caller stream, up to five per leased host pipe) holds the table of its own launch in flight:
             // a handle's tables together stay under a budget (tuning knob walk_table_max_bytes, default 48 GiB) — a workspace that would
             // exceed it simply walks without a table (same results)
             const size_t budget = (size_t)cosdev::tune_or(cosdev::TUNE_WALK_TABLE_MAX_BYTES, (long long)48 << 30);
             HIP_TRY(hipStreamSynchronize(st));
-            if (w->tab) HIP_TRY(hipFree(w->tab));
-            ix->table_bytes_total -= w->tab_cap * 4;
-            w->tab = nullptr;
-            w->tab_cap = 0;
+            ix->table_bytes_total -= w->tab.cap * 4;
+            w->tab.reset();
             if (ix->table_bytes_total + need * 4 <= budget) {
-                if (const hipError_t e = hipMalloc((void **)&w->tab, need * 4); e == hipSuccess) {
-                    w->tab_cap = need;
+                if (const hipError_t e = w->tab.alloc(need); e == hipSuccess)
                     ix->table_bytes_total += need * 4;
-                } else if (e == hipErrorOutOfMemory) { // HBM is short: this workspace walks without a table (same results)
+                else if (e == hipErrorOutOfMemory) // HBM is short: this workspace walks without a table (same results)
                     (void)hipGetLastError();
-                    w->tab = nullptr;
-                } else
+                else
                     HIP_TRY(e);
             }
         }
     }
     if (host_api && (size_t)top_k * w->capB > (size_t)w->cap_topk * w->capB) {
-        HIP_TRY(regrow(w->d_out_ids, (size_t)w->capB * top_k));
-        HIP_TRY(regrow(w->d_out_scores, (size_t)w->capB * top_k));
+        w->cap_topk = 0;
+        HIP_TRY(w->d_out_ids.alloc((size_t)w->capB * top_k));
+        HIP_TRY(w->d_out_scores.alloc((size_t)w->capB * top_k));
         w->cap_topk = top_k;
     }
     if (w->ev.empty()) {
@@ -1131,7 +1024,7 @@ static int32_t run_search(cos_index *ix, Workspace *w, const float *d_queries, u
             order_rank[n_keys++] = ix->d_order_rank[l];
         }
         tab_min_B = walk_table_min_B(ix);
-        if (tab_min_B && ix->level_table_valid && ix->table_level_min && w->tab && (size_t)B * ix->table_stride <= w->tab_cap) {
+        if (tab_min_B && ix->level_table_valid && ix->table_level_min && w->tab && (size_t)B * ix->table_stride <= w->tab.cap) {
             tab_level_min = ix->table_level_min;
             tab_cols = ix->table_cols;
             tab_stride = ix->table_stride;
@@ -1154,7 +1047,7 @@ static int32_t run_search(cos_index *ix, Workspace *w, const float *d_queries, u
     // loads and an LDS round trip per window entry only add latency (single batch of c2: 407 k QPS without, 396 k with).
     if (cosdev::tune_or(cosdev::TUNE_WALK_ADJ_MAG, 1) != 2) // (2 = at every ef and launch size: experiments)
         for (u32 l = 0; l <= dev.num_layers; l++)
-            if (ef > 2u * dev.lv[l].M || B < 4096u) dev.lv[l].adj_mag = nullptr;
+            if (ef > 2u * dev.lv[l].M || B < ADJ_MAG_USE_MIN_B) dev.lv[l].adj_mag = nullptr;
     WalkArgs wa;
     memset(&wa, 0, sizeof(wa));
     if (dev.visited_mode == COS_VISITED_EXACT) {
@@ -1338,11 +1231,11 @@ struct PipeLease {
         for (;;) {
             if (!ix->pipes_free.empty()) { hp = ix->pipes_free.back(); ix->pipes_free.pop_back(); break; }
             if (ix->pipes_all.size() < COS_MAX_HOST_PIPES) {
-                HostPipe *n = new HostPipe();
+                std::unique_ptr<HostPipe> n(new HostPipe());
                 hipError_t e = hipStreamCreateWithFlags(&n->s[0], hipStreamNonBlocking);
-                if (e != hipSuccess) { delete n; return cos_fail(COS_ERR_HIP, "hipStreamCreateWithFlags: %s", hipGetErrorString(e)); }
-                ix->pipes_all.push_back(n);
-                hp = n;
+                if (e != hipSuccess) return cos_fail(COS_ERR_HIP, "hipStreamCreateWithFlags: %s", hipGetErrorString(e));
+                hp = n.get();
+                ix->pipes_all.push_back(std::move(n));
                 break;
             }
             ix->pipe_cv.wait(lk); // COS_MAX_HOST_PIPES calls are in flight: wait for one to finish
@@ -1357,17 +1250,6 @@ struct PipeLease {
         ix->pipe_cv.notify_one();
     }
 };
-
-template <typename T>
-static hipError_t grow_elems(T *&p, size_t &cap, size_t need) { // one capacity per buffer; a failed allocation leaves (null, 0)
-    if (need <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    hipError_t e = hipMalloc((void **)&p, need * sizeof(T));
-    if (e == hipSuccess) cap = need;
-    return e;
-}
 
 static int32_t report_status(const int32_t *status, u32 B) {
     for (u32 b = 0; b < B; b++)
@@ -1421,11 +1303,11 @@ static int32_t search_host_pipelined(cos_index *ix, HostPipe *hp, const float *q
         if (!hp->ev_in[i]) HIP_TRY(hipEventCreateWithFlags(&hp->ev_in[i], hipEventDisableTiming));
         if (!hp->ev_walk[i]) HIP_TRY(hipEventCreateWithFlags(&hp->ev_walk[i], hipEventDisableTiming));
     }
-    HIP_TRY(grow_elems(hp->d_q, hp->cap_q, (size_t)B * dim));
-    HIP_TRY(grow_elems(hp->d_ids, hp->cap_ids, (size_t)B * top_k));
-    HIP_TRY(grow_elems(hp->d_scores, hp->cap_scores, (size_t)B * top_k));
-    HIP_TRY(grow_elems(hp->d_counts, hp->cap_counts, (size_t)B));
-    HIP_TRY(grow_elems(hp->d_status, hp->cap_status, (size_t)B));
+    HIP_TRY(hp->d_q.grow((size_t)B * dim));
+    HIP_TRY(hp->d_ids.grow((size_t)B * top_k));
+    HIP_TRY(hp->d_scores.grow((size_t)B * top_k));
+    HIP_TRY(hp->d_counts.grow((size_t)B));
+    HIP_TRY(hp->d_status.grow((size_t)B));
     struct Drain { // whatever happens, nothing of this call is still running when its buffers are handed back
         HostPipe *hp;
         bool ok = false;
@@ -1511,8 +1393,8 @@ static int32_t search_host_once(cos_index *ix, const float *queries, uint32_t B,
 // "inside" swings with every return, slots closed early, 128 / 256 callers fell to 3.3 / 3.1 M; (ii) running a launch that has the
 // device to itself as the chunk pipeline of a lone big host call — 64 callers 2.47 M against 2.77 M, 32 callers 2.0 against 2.5 M.
 struct CoSlot {
-    float *pin_q = nullptr;     // [cap][dim]
-    unsigned char *pin_out = nullptr; // ids [cap][k] | scores [cap][k] | counts [cap] | status [cap]
+    PinArr<float> pin_q;        // [cap][dim]
+    PinArr<unsigned char> pin_out; // ids [cap][k] | scores [cap][k] | counts [cap] | status [cap]
     u32 cap = 0, cap_k = 0;
     u32 top_k = 0;
     u32 reserved = 0, n_req = 0;           // queries reserved, requests in the slot (co_mu)
@@ -1527,13 +1409,8 @@ struct CoSlot {
     std::condition_variable cv_done;       // with mu: `done`
 };
 
-static void co_slot_free(CoSlot *sl) {
-    if (sl->pin_q) (void)hipHostFree(sl->pin_q);
-    if (sl->pin_out) (void)hipHostFree(sl->pin_out);
-    delete sl;
-}
 void cos_coalesce_release(cos_index *ix) { // cos_index_destroy
-    for (CoSlot *sl : ix->co_slots) co_slot_free(sl);
+    for (CoSlot *sl : ix->co_slots) delete sl;
     ix->co_slots.clear();
     ix->co_open = nullptr;
 }
@@ -1549,18 +1426,13 @@ static CoSlot *co_slot_get(cos_index *ix, u32 max_q, u32 top_k) {
         ix->co_slots.push_back(sl);
     }
     if (sl->cap < max_q) {
-        if (sl->pin_q) (void)hipHostFree(sl->pin_q);
-        sl->pin_q = nullptr;
-        sl->cap = 0;
-        if (hipHostMalloc((void **)&sl->pin_q, (size_t)max_q * ix->p.dim * 4, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        sl->cap = sl->cap_k = 0;
+        if (sl->pin_q.alloc((size_t)max_q * ix->p.dim) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
         sl->cap = max_q;
-        sl->cap_k = 0;
     }
     if (sl->cap_k < top_k) {
-        if (sl->pin_out) (void)hipHostFree(sl->pin_out);
-        sl->pin_out = nullptr;
         sl->cap_k = 0;
-        if (hipHostMalloc((void **)&sl->pin_out, (size_t)sl->cap * top_k * 8 + (size_t)sl->cap * 8, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        if (sl->pin_out.alloc((size_t)sl->cap * top_k * 8 + (size_t)sl->cap * 8) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
         sl->cap_k = top_k;
     }
     sl->top_k = top_k;
@@ -1580,7 +1452,7 @@ static int32_t co_slot_run(cos_index *ix, CoSlot *sl) {
     int32_t rc = lease.acquire();
     if (rc) return rc;
     hipStream_t st = lease.hp->s[0];
-    u32 *p_ids = (u32 *)sl->pin_out;
+    u32 *p_ids = sl->pin_out.as<u32>();
     float *p_sc = (float *)(p_ids + (size_t)sl->cap * top_k);
     u32 *p_cnt = (u32 *)(p_sc + (size_t)sl->cap * top_k);
     int32_t *p_st = (int32_t *)(p_cnt + sl->cap);
@@ -1714,7 +1586,7 @@ extern "C" int32_t cos_search_batch(cos_index *ix, const float *queries, uint32_
     int32_t my_rc = COS_OK;
     u32 bad_q = 0;
     if (slot_rc == COS_OK) {
-        const u32 *p_ids = (const u32 *)sl->pin_out;
+        const u32 *p_ids = sl->pin_out.as<const u32>();
         const float *p_sc = (const float *)(p_ids + (size_t)sl->cap * top_k);
         const u32 *p_cnt = (const u32 *)(p_sc + (size_t)sl->cap * top_k);
         const int32_t *p_st = (const int32_t *)(p_cnt + sl->cap);
@@ -1773,7 +1645,7 @@ extern "C" int32_t cos_index_last_stats(cos_index *ix, void *stream, cos_search_
         std::lock_guard<std::mutex> g(ix->mu);
         if (stream) {
             auto it = ix->ws.find(stream);
-            if (it != ix->ws.end()) w = it->second;
+            if (it != ix->ws.end()) w = it->second.get();
         } else
             w = ix->last_ws;
         if (!w) return cos_fail(COS_ERR_NOT_READY, "no batch has run on this stream");
@@ -1813,7 +1685,7 @@ extern "C" int32_t cos_index_last_walk_split(cos_index *ix, void *stream, cos_wa
         std::lock_guard<std::mutex> g(ix->mu);
         if (stream) {
             auto it = ix->ws.find(stream);
-            if (it != ix->ws.end()) w = it->second;
+            if (it != ix->ws.end()) w = it->second.get();
         } else
             w = ix->last_ws;
     }
@@ -1865,7 +1737,7 @@ extern "C" int32_t cos_index_timing_summary(cos_index *ix, void *stream, cos_tim
     {
         std::lock_guard<std::mutex> g(ix->mu);
         auto it = ix->ws.find(stream);
-        if (it != ix->ws.end()) w = it->second;
+        if (it != ix->ws.end()) w = it->second.get();
     }
     if (!w || w->ev_count == 0) return cos_fail(COS_ERR_NOT_READY, "no timed batch has run on this stream");
     const u32 n = std::min(w->ev_count, Workspace::EV_RING);
@@ -1941,12 +1813,11 @@ extern "C" int32_t cos_index_upload_meta_nodes(cos_index *ix, uint32_t n_nodes, 
         for (u32 j = 0; j < md; j++) { const float x = (float)mbits[(size_t)i * md + j]; acc = acc + x * x; }
         mags[i] = sqrtf(acc);
     }
-    if (ix->meta.d_mbits) (void)hipFree(ix->meta.d_mbits);
-    if (ix->meta.d_mmags) (void)hipFree(ix->meta.d_mmags);
-    ix->meta.d_mbits = nullptr; ix->meta.d_mmags = nullptr;
-    for (auto &l : ix->meta.lv) free_level(l);
-    HIP_TRY(hipMalloc((void **)&ix->meta.d_mbits, (size_t)n_nodes * md * 4));
-    HIP_TRY(hipMalloc((void **)&ix->meta.d_mmags, (size_t)n_nodes * 4));
+    ix->meta.d_mbits.reset();
+    ix->meta.d_mmags.reset();
+    for (auto &l : ix->meta.lv) l.release();
+    HIP_TRY(ix->meta.d_mbits.alloc((size_t)n_nodes * md));
+    HIP_TRY(ix->meta.d_mmags.alloc(n_nodes));
     HIP_TRY(hipMemcpy(ix->meta.d_mbits, mbits, (size_t)n_nodes * md * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(ix->meta.d_mmags, mags.data(), (size_t)n_nodes * 4, hipMemcpyHostToDevice));
     ix->meta.node_ids.assign(node_ids, node_ids + n_nodes);
@@ -1984,10 +1855,9 @@ extern "C" int32_t cos_index_upload_meta_graph_level(cos_index *ix, uint32_t lev
             adj_node[(size_t)i * M + j] = (u32)(it - node_ids);
             adj_vec[(size_t)i * M + j] = node_vec[it - node_ids];
         }
-    free_level(L);
-    L.M = M;
-    auto up = [&](u32 *&dst, const std::vector<u32> &src) -> hipError_t {
-        hipError_t e = hipMalloc((void **)&dst, std::max<size_t>(src.size(), 1) * 4);
+    L.release();
+    auto up = [&](DevArr<u32> &dst, const std::vector<u32> &src) -> hipError_t {
+        hipError_t e = dst.alloc(src.size());
         return e == hipSuccess ? hipMemcpy(dst, src.data(), src.size() * 4, hipMemcpyHostToDevice) : e;
     };
     std::vector<u32> ids(node_ids, node_ids + n_nodes);
@@ -2010,8 +1880,6 @@ extern "C" int32_t cos_index_upload_meta_graph_level(cos_index *ix, uint32_t lev
             if (it == D.node_ids.end() || *it != U.node_ids[i]) return cos_fail(COS_ERR_INVALID, "node %u of level %u is missing on level %u", U.node_ids[i], lv, lv - 1);
             child[i] = (u32)(it - D.node_ids.begin());
         }
-        if (U.d_child) (void)hipFree(U.d_child);
-        U.d_child = nullptr;
         HIP_TRY(up(U.d_child, child));
     }
     return COS_OK;
@@ -2055,13 +1923,9 @@ static int32_t search_filtered_host(cos_index *ix, const float *queries, u32 B, 
     if (rc) return rc;
     // the batch's filters in the workspace's own buffer, ONE copy: [dims nf x md | norms nf | offsets B + 1]
     const size_t f_words = fd.size() + fm.size() + (size_t)B + 1;
-    if (f_words * 4 > w->f_cap) {
+    if (f_words > w->f_buf.cap) {
         HIP_TRY(hipStreamSynchronize(st));
-        if (w->f_buf) (void)hipFree(w->f_buf);
-        w->f_buf = nullptr;
-        w->f_cap = 0;
-        HIP_TRY(hipMalloc((void **)&w->f_buf, f_words * 4 * 2));
-        w->f_cap = f_words * 4 * 2;
+        HIP_TRY(w->f_buf.alloc(f_words * 2));
     }
     std::vector<u32> fpack(f_words);
     memcpy(fpack.data(), fd.data(), fd.size() * 4);
@@ -2084,9 +1948,9 @@ static int32_t search_filtered_host(cos_index *ix, const float *queries, u32 B, 
     wa.out_sims = w->walk_sims;
     wa.out_counts = w->walk_counts;
     wa.out_status = w->walk_status;
-    wa.f_dims = (const int32_t *)w->f_buf;
-    wa.f_mags = (const float *)(w->f_buf + fd.size() * 4);
-    wa.f_off = (const u32 *)(w->f_buf + (fd.size() + fm.size()) * 4);
+    wa.f_dims = w->f_buf.as<const int32_t>();
+    wa.f_mags = (const float *)(w->f_buf + fd.size());
+    wa.f_off = w->f_buf + (fd.size() + fm.size());
     HIP_TRY(launch_walk_meta(ix->eng, dev, wa, st));
     std::vector<int32_t> status(B);
     if (lvl_ids) {

@@ -5,6 +5,7 @@
 #include <atomic>
 #include <condition_variable>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -14,6 +15,7 @@
 #include "engine_types.h"
 #include "tuning.h"
 #include "link_types.h"
+#include "dev_mem.h"
 
 namespace cosdev {
 hipError_t launch_fill_i32(int32_t *p, u64 n, int32_t v, hipStream_t st);
@@ -41,16 +43,14 @@ hipError_t launch_finalize(const IndexDev &ix, const float *queries, u64 q_strid
                            hipStream_t st, const u32 *q_order = nullptr, u32 *slow_list = nullptr);
 // buffers of the locality order of one workspace's big launches (kernels_order.hip)
 struct WalkOrder {
-    u32 cap = 0;
-    u32 *entry0 = nullptr;      // [cap] level-0 entry node per query
-    u32 *order_key = nullptr;   // [cap]
-    u32 *keys_sorted = nullptr; // [cap]
-    u32 *iota = nullptr, *vals_sorted = nullptr, *q_order = nullptr; // [cap]
-    void *tmp = nullptr;        // radix sort scratch
-    size_t tmp_bytes = 0;
+    u32 cap = 0;                // queries every array below holds (0 after a failed reservation)
+    DevArr<u32> entry0;         // [cap] level-0 entry node per query
+    DevArr<u32> order_key;      // [cap]
+    DevArr<u32> keys_sorted;    // [cap]
+    DevArr<u32> iota, vals_sorted, q_order; // [cap]
+    DevBuf tmp;                 // radix sort scratch
 };
 hipError_t walk_order_reserve(WalkOrder &o, u32 B); // synchronous (re)allocation
-void walk_order_free(WalkOrder &o);
 hipError_t launch_walk_order(WalkOrder &o, u32 B, u32 key_max, u32 num_xcd, hipStream_t st);
 // level table of the walk (kernels_flat.hip; WalkArgs::tab)
 hipError_t launch_level_table_gather(const uint8_t *codes, const float *mags, u64 row_stride, const u32 *node_vec, u32 n, u32 col0,
@@ -75,30 +75,26 @@ int32_t cos_fail(int32_t code, const char *fmt, ...);
         if (_e != hipSuccess) return cos_fail(COS_ERR_HIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
     } while (0)
 
-// scoped device allocation: temporaries of an entry point are released on every return path
-struct DevBuf {
-    void *p = nullptr;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { release(); return hipMalloc(&p, bytes ? bytes : 1); }
-    void release() { if (p) (void)hipFree(p); p = nullptr; }
-    template <typename T> T *as() const { return (T *)p; }
-};
-
 // ------------------------------------------------------------------------------------------------
 // handle
 // ------------------------------------------------------------------------------------------------
 struct LevelHost {
     std::vector<u32> node_ids; // ascending, root last
     std::vector<u32> nbr_ids;  // [n][M] internal ids / COS_SLOT_EMPTY
-    u32 *d_adj_vec = nullptr, *d_adj_node = nullptr, *d_node_vec = nullptr, *d_child = nullptr;
-    u32 *d_node_id = nullptr, *d_node_meta = nullptr; // pseudo-root component only (metadata-filtered search)
-    float *d_adj_mag = nullptr; // [n][min(M, shortlist)] norms of the scanned neighbour slots (LevelDev::adj_mag), valid while cos_index::adj_mag_valid
+    DevArr<u32> d_adj_vec, d_adj_node, d_node_vec, d_child;
+    DevArr<u32> d_node_id, d_node_meta; // pseudo-root component only (metadata-filtered search)
+    DevArr<float> d_adj_mag; // [n][min(M, shortlist)] norms of the scanned neighbour slots (LevelDev::adj_mag), valid while cos_index::adj_mag_valid
     u32 n = 0, M = 0;
     u32 root_idx = 0;        // pseudo-root component: node index of the pseudo root (base graph: the root is the last node)
     bool host_valid = false; // node_ids/nbr_ids mirror the device arrays
+    void release() { // the level's device arrays and host mirrors (M stays)
+        d_adj_vec.reset(); d_adj_node.reset(); d_node_vec.reset(); d_child.reset();
+        d_node_id.reset(); d_node_meta.reset(); d_adj_mag.reset();
+        n = 0;
+        node_ids.clear();
+        nbr_ids.clear();
+        host_valid = false;
+    }
 };
 
 // What cos_index_build leaves behind so that cos_index_append can CONTINUE it (builder.hip): the link state of every level — the
@@ -111,7 +107,7 @@ struct LinkState {
     u32 n_built = 0;
     bool valid = false;
     void release() {
-        for (int l = 0; l < cosdev::MAX_LEVELS; l++) { key[l].release(); low_idx[l].release(); low_key[l].release(); owner[l].release(); }
+        for (int l = 0; l < cosdev::MAX_LEVELS; l++) { key[l].reset(); low_idx[l].reset(); low_key[l].reset(); owner[l].reset(); }
         valid = false;
     }
 };
@@ -119,40 +115,36 @@ struct LinkState {
 // EXACT-mode visited filters of one stream (WalkArgs::vis_bits / vis_log).  The bitset is zeroed once, when it is
 // (re)allocated; afterwards every walk level undoes its own bits.
 struct VisTab {
-    u32 *bits = nullptr, *log = nullptr;
-    size_t bits_cap = 0, log_cap = 0; // allocated u32 words
-    bool zeroed = false;
-    size_t zeroed_cap = 0;
+    DevArr<u32> bits, log;
+    bool zeroed = false; // cleared whenever `bits` is reallocated
 };
 // sizes/allocates the filter for B queries at beam width ef and fills wa.vis_*
 int32_t vis_tab_prepare(VisTab &vt, const cos_index *ix, u32 B, u32 ef, hipStream_t st, cosdev::WalkArgs &wa);
 
 struct Workspace {
     u32 capB = 0, cap_topk = 0;
-    uint8_t *q_codes = nullptr;
-    float *q_mags = nullptr, *q_raw_mags = nullptr;
-    u32 *walk_ids = nullptr, *walk_counts = nullptr;
-    float *walk_sims = nullptr;
-    int32_t *walk_status = nullptr;
-    u64 *stats = nullptr;       // [B][4]
-    u64 *stats2 = nullptr;      // [B][4] WalkArgs::out_stats2
-    float *tab = nullptr;       // level table of this workspace's big launches [capB][tab_stride] (WalkArgs::tab), grown on demand
-    size_t tab_cap = 0;         // floats
-    u32 *qsums = nullptr;       // [capB] code sums of the queries (the table GEMM's recentring term)
-    uint8_t *qdig = nullptr;    // [capB][dims] quaternary codes: the queries' i8 digit rows (the table GEMM's resident operand)
-    u32 *fin_flags = nullptr;   // [capB + 1] finalize_fast_kernel -> finalize_list_kernel hand-over: count, then the queries (kernels_walk.hip)
-    u64 *rerank_rows = nullptr; // [B]
+    DevArr<uint8_t> q_codes;
+    DevArr<float> q_mags, q_raw_mags;
+    DevArr<u32> walk_ids, walk_counts;
+    DevArr<float> walk_sims;
+    DevArr<int32_t> walk_status;
+    DevArr<u64> stats;          // [B][4]
+    DevArr<u64> stats2;         // [B][4] WalkArgs::out_stats2
+    DevArr<float> tab;          // level table of this workspace's big launches [capB][tab_stride] (WalkArgs::tab), grown on demand
+    DevArr<u32> qsums;          // [capB] code sums of the queries (the table GEMM's recentring term)
+    DevArr<uint8_t> qdig;       // [capB][dims] quaternary codes: the queries' i8 digit rows (the table GEMM's resident operand)
+    DevArr<u32> fin_flags;      // [capB + 1] finalize_fast_kernel -> finalize_list_kernel hand-over: count, then the queries (kernels_walk.hip)
+    DevArr<u64> rerank_rows;    // [B]
     VisTab vis; // EXACT mode visited filters
     cosdev::WalkOrder order; // locality order of big launches (cos_index::walk_order_min_B)
     // host-API staging (device)
-    float *d_queries = nullptr;
-    u32 *d_out_ids = nullptr, *d_out_counts = nullptr;
-    float *d_out_scores = nullptr;
-    int32_t *d_out_status = nullptr;
-    // filtered search (cos_search_filtered_batch): the batch's filters [f_cap words: dims | norms | offsets], grown on demand — until
+    DevArr<float> d_queries;
+    DevArr<u32> d_out_ids, d_out_counts;
+    DevArr<float> d_out_scores;
+    DevArr<int32_t> d_out_status;
+    // filtered search (cos_search_filtered_batch): the batch's filters [dims | norms | offsets], grown on demand — until
     // round 6 three hipMalloc / hipFree pairs per call (a hipFree drains the device)
-    unsigned char *f_buf = nullptr;
-    size_t f_cap = 0;
+    DevArr<u32> f_buf;
     // timing: a ring of event quadruples (before prep | after prep | after walk | after finalize), one per launch, so a
     // run of launches can be summarised afterwards without synchronising between them (cos_index_timing_summary)
     // + the inner marks of a big launch's walk: [4] before / [5] after the level-table GEMM (caller's stream), [6] after the upper
@@ -169,6 +161,13 @@ struct Workspace {
     bool timed = false;
     bool last_tab = false, last_split = false; // the last launch used the level table / was cut into two level ranges
     u32 last_tab_cols = 0, last_tab_level_min = 0, last_cut_level = 0;
+    Workspace() = default;
+    Workspace(const Workspace &) = delete;
+    ~Workspace() { // (the caller has drained the device: cos_index_destroy)
+        for (hipEvent_t e : {walk_done, walk_fin, last_range, prep_done}) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        if (walk_stream) (void)hipStreamDestroy(walk_stream);
+    }
 };
 
 // The pseudo-root component of a collection with a metadata schema: pseudo nodes + Metadata replicas, a graph of
@@ -176,8 +175,8 @@ struct Workspace {
 struct MetaGraph {
     u32 mdim = 0;                 // metadata dimensions per node (0 = the index has no metadata schema)
     std::vector<u32> node_ids;    // [n_meta] ascending
-    int32_t *d_mbits = nullptr;   // [n_meta][mdim]
-    float *d_mmags = nullptr;     // [n_meta]
+    DevArr<int32_t> d_mbits;      // [n_meta][mdim]
+    DevArr<float> d_mmags;        // [n_meta]
     std::vector<LevelHost> lv;    // [num_layers + 1]
 };
 
@@ -189,11 +188,17 @@ struct HostPipe {
     hipStream_t s[2] = {nullptr, nullptr}, sc = nullptr, sf = nullptr;
     hipEvent_t ev_in[MAX_CHUNKS] = {}, ev_walk[MAX_CHUNKS] = {};
     char wkey[MAX_CHUNKS] = {}; // &wkey[i] = key of chunk i's Workspace in cos_index::ws
-    float *d_q = nullptr;       // [B][dim] the call's queries
-    u32 *d_ids = nullptr, *d_counts = nullptr;
-    float *d_scores = nullptr;
-    int32_t *d_status = nullptr;
-    size_t cap_q = 0, cap_ids = 0, cap_scores = 0, cap_counts = 0, cap_status = 0; // elements, one capacity per buffer
+    DevArr<float> d_q;          // [B][dim] the call's queries
+    DevArr<u32> d_ids, d_counts;
+    DevArr<float> d_scores;
+    DevArr<int32_t> d_status;
+    HostPipe() = default;
+    HostPipe(const HostPipe &) = delete;
+    ~HostPipe() {
+        for (hipEvent_t e : ev_in) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : ev_walk) if (e) (void)hipEventDestroy(e);
+        for (hipStream_t st : {s[0], s[1], sc, sf}) if (st) (void)hipStreamDestroy(st);
+    }
 };
 static constexpr u32 COS_MAX_HOST_PIPES = 32; // concurrent host-API calls served at once; further callers wait for a pipe
 
@@ -201,11 +206,12 @@ struct cos_index {
     cos_params p;
     int eng = -1;
     u32 n = 0;
-    bool have_vectors = false, have_root = false, raw_borrowed = false;
-    float *d_raw = nullptr;
-    float *d_raw_mags = nullptr;
-    uint8_t *d_codes = nullptr;
-    float *d_mags = nullptr;
+    bool have_vectors = false, have_root = false;
+    const float *d_raw = nullptr; // the f32 table the kernels read: raw_own, or the caller's (COS_UPLOAD_BORROW_DEVICE)
+    DevArr<float> raw_own;        // empty while the table is borrowed
+    DevArr<float> d_raw_mags;
+    DevArr<uint8_t> d_codes;
+    DevArr<float> d_mags;
     u64 row_stride = 0;
     u32 nchunks = 0, G = 1;
     std::vector<float> root_raw;
@@ -214,12 +220,13 @@ struct cos_index {
     MetaGraph meta;
     hipStream_t own_stream = nullptr; // uploads / builder stream (exclusive entry points)
     std::mutex mu;                    // guards the workspace + thread-stream maps, the timing flag, ef_search and visited_mode
-    std::map<void *, Workspace *> ws;
+    std::map<void *, std::unique_ptr<Workspace>> ws;
     // host-API searches: a call leases one HostPipe (private streams + staging) for its duration from a bounded pool, so
     // concurrent callers neither serialise nor share buffers and a host that churns threads cannot grow device memory
     std::mutex pipe_mu;
     std::condition_variable pipe_cv;
-    std::vector<struct HostPipe *> pipes_all, pipes_free;
+    std::vector<std::unique_ptr<HostPipe>> pipes_all;
+    std::vector<HostPipe *> pipes_free;
     std::atomic<int> host_calls_active{0};
     Workspace *last_ws = nullptr; // most recent batch (cos_index_last_stats with stream == NULL)
     // host-API request coalescing (cos_index_set_coalescing)
@@ -254,7 +261,7 @@ struct cos_index {
     u32 num_xcd = 8; // hipDeviceAttributeNumberOfXccs of the handle's device (workgroup b of a grid runs on XCD b % num_xcd)
     // the order keys' tables: position of every node of a key level in a depth-first order of that level's graph, and the key
     // levels themselves, descending (ensure_order_rank, engine.hip); rebuilt after the graph changes
-    u32 *d_order_rank[cosdev::MAX_LEVELS] = {};
+    DevArr<u32> d_order_rank[cosdev::MAX_LEVELS];
     u32 order_rank_n[cosdev::MAX_LEVELS] = {};
     std::vector<u32> order_levels; // empty = the graph has no level the order could use
     bool order_rank_valid = false;
@@ -270,12 +277,12 @@ struct cos_index {
     u64 table_built_for_key = 0;    // max_cols, or the automatic rule's per-level bound: a change rebuilds the operand
     u64 table_stride = 0;            // floats per query row (cols padded to 32)
     u32 table_col0[cosdev::MAX_LEVELS] = {};
-    uint8_t *d_tcodes = nullptr;     // [table_cols][row_stride] code rows of the table's nodes, level by level from the top
-    float *d_tmags = nullptr;        // [table_cols]
-    u32 *d_tcsums = nullptr;         // [table_cols]
+    const uint8_t *d_tcodes = nullptr; // (these three: views into the set of table_sets that is current) [table_cols][row_stride] code rows of the table's nodes, level by level from the top
+    const float *d_tmags = nullptr;  // [table_cols]
+    const u32 *d_tcsums = nullptr;   // [table_cols]
     // operands built for other keys of the SAME graph (ef_search changes re-select the table's levels while searches of the previous
     // ef may still be in flight: nothing a launch may be reading is freed before the graph itself is replaced)
-    struct TableSet { u64 key; u32 level_min, cols; u64 stride; u32 col0[cosdev::MAX_LEVELS]; uint8_t *tcodes; float *tmags; u32 *tcsums; };
+    struct TableSet { u64 key; u32 level_min, cols; u64 stride; u32 col0[cosdev::MAX_LEVELS]; DevArr<uint8_t> tcodes; DevArr<float> tmags; DevArr<u32> tcsums; };
     std::vector<TableSet> table_sets;
     u32 walk_side_min_B = 4096; // launches of at least this many queries walk on the workspace's low-priority stream; 0 = never
     // launches of at most this many queries run the latency variant of the walk (kernels_walk_lat.hip) where it applies; 0 = never

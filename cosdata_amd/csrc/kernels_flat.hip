@@ -633,26 +633,27 @@ extern "C" int32_t cos_bruteforce_topk(cos_index *ix, const float *queries, uint
     constexpr u32 SEED = 16384, APP_CAP = 4096;
     const bool allow_fused = tune_or(TUNE_FLAT_UNFUSED, 0) == 0 && n > SEED;
     const u64 s_stride = ((u64)chunk + 63) & ~63ull;
-    float *d_q = nullptr, *d_qm = nullptr, *d_scores = nullptr, *d_os = nullptr, *d_dummy = nullptr;
-    u64 *d_pool = nullptr, *d_part = nullptr, *d_thr = nullptr, *d_app = nullptr;
-    u32 *d_oi = nullptr, *d_appcnt = nullptr, *d_over = nullptr;
-    uint8_t *d_codes = nullptr;
+    DevArr<float> d_q, d_qm, d_scores, d_os, d_dummy;
+    DevArr<u64> d_pool, d_part, d_thr, d_app;
+    DevArr<u32> d_oi, d_appcnt, d_over;
+    DevArr<uint8_t> d_codes;
     hipStream_t st = ix->own_stream;
     const u32 S = select_segments(B, chunk);
-    hipError_t e = hipMalloc(&d_q, (size_t)B * dim * 4);
-    if (e == hipSuccess) e = hipMalloc(&d_part, (size_t)B * S * SEL * 8);
-    if (e == hipSuccess) e = hipMalloc(&d_qm, (size_t)B * 4);
-    if (e == hipSuccess) e = hipMalloc(&d_dummy, (size_t)B * 4);
-    if (e == hipSuccess) e = hipMalloc(&d_codes, (size_t)B * (((size_t)dim * 4 + 15) & ~(size_t)15));
-    if (e == hipSuccess) e = hipMalloc(&d_scores, (size_t)B * s_stride * 4);
-    if (e == hipSuccess) e = hipMalloc(&d_pool, (size_t)B * SEL * 8);
-    if (e == hipSuccess) e = hipMalloc(&d_thr, (size_t)B * 8);
-    if (e == hipSuccess && allow_fused) e = hipMalloc(&d_app, (size_t)B * APP_CAP * 8);
-    if (e == hipSuccess) e = hipMalloc(&d_appcnt, (size_t)B * 4);
-    if (e == hipSuccess) e = hipMalloc(&d_over, 4);
-    if (e == hipSuccess) e = hipMalloc(&d_oi, (size_t)B * k * 4);
-    if (e == hipSuccess) e = hipMalloc(&d_os, (size_t)B * k * 4);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_q, queries, (size_t)B * dim * 4, hipMemcpyHostToDevice, st);
+    HIP_TRY(d_q.alloc((size_t)B * dim));
+    HIP_TRY(d_part.alloc((size_t)B * S * SEL));
+    HIP_TRY(d_qm.alloc(B));
+    HIP_TRY(d_dummy.alloc(B));
+    HIP_TRY(d_codes.alloc((size_t)B * (((size_t)dim * 4 + 15) & ~(size_t)15)));
+    HIP_TRY(d_scores.alloc((size_t)B * s_stride));
+    HIP_TRY(d_pool.alloc((size_t)B * SEL));
+    HIP_TRY(d_thr.alloc(B));
+    if (allow_fused) HIP_TRY(d_app.alloc((size_t)B * APP_CAP));
+    HIP_TRY(d_appcnt.alloc(B));
+    HIP_TRY(d_over.alloc(1));
+    HIP_TRY(d_oi.alloc((size_t)B * k));
+    HIP_TRY(d_os.alloc((size_t)B * k));
+    // (from here on a ladder: the stream is drained below on every path before the buffers and `hover` go out of scope)
+    hipError_t e = hipMemcpyAsync(d_q, queries, (size_t)B * dim * 4, hipMemcpyHostToDevice, st);
     // |q| in the reference's sequential order (vector_store.rs:414): reuse the F32 quantize kernel's raw_mags output
     if (e == hipSuccess) e = launch_quantize_rows(ENG_F32, d_q, dim, B, dim, 0.f, 0.f, d_codes, ((u64)dim * 4 + 15) & ~15ull, d_dummy, d_qm, st);
     for (const void *f : {(const void *)flat_gemm_f32<true, false>, (const void *)flat_gemm_f32<false, false>, (const void *)flat_gemm_f32<true, true>,
@@ -704,8 +705,6 @@ extern "C" int32_t cos_bruteforce_topk(cos_index *ix, const float *queries, uint
     if (e == hipSuccess) e = hipMemcpyAsync(out_ids, d_oi, (size_t)B * k * 4, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipMemcpyAsync(out_scores, d_os, (size_t)B * k * 4, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    void *ptrs[] = {d_q, d_qm, d_dummy, d_codes, d_scores, d_pool, d_part, d_thr, d_app, d_appcnt, d_over, d_oi, d_os};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
     HIP_TRY(e);
     return COS_OK;
 }
@@ -715,32 +714,17 @@ extern "C" int32_t cos_bruteforce_topk(cos_index *ix, const float *queries, uint
 // and a dozen event create / destroy calls used to cost about as much wall time as the scan kernel itself.
 struct FlatWs {
     std::mutex mu; // the scan runs on the index's own stream: one call at a time
-    struct Buf { void *p = nullptr; size_t cap = 0; };
-    Buf q, zero, qm, qrm, qc, qd, qdp, qs, cs, pool, thr, app, appcnt, oi, os, oc, scores, part;
+    DevArr<float> q, qm, qrm, os, scores;
+    DevArr<uint8_t> qc, qd, qdp;
+    DevArr<u32> zero, qs, cs, appcnt, oi, oc;
+    DevArr<u64> pool, thr, app, part;
     bool cs_valid = false; // code sums of the stored vectors (u8 engine) computed for the current upload
     u32 cs_n = 0;
     bool zn_valid = false, zn_zero = false; // "a stored vector has a zero norm" for the current upload (cosine's CalculationError screen)
     u32 zn_n = 0;
-    Buf out;                  // [ids B x k | scores B x k | counts B | zero-norm flag, overflow flag]: ONE copy back per call
-    void *h_out = nullptr;    // its pinned landing area
-    size_t h_out_cap = 0;
-    hipError_t need_host(size_t bytes) {
-        if (bytes <= h_out_cap && h_out) return hipSuccess;
-        if (h_out) (void)hipHostFree(h_out);
-        h_out = nullptr; h_out_cap = 0;
-        hipError_t e = hipHostMalloc(&h_out, bytes);
-        if (e == hipSuccess) h_out_cap = bytes;
-        return e;
-    }
+    DevArr<u32> out;          // [ids B x k | scores B x k | counts B | zero-norm flag, overflow flag]: ONE copy back per call
+    PinArr<u32> h_out;        // its pinned landing area
     std::vector<hipEvent_t> evs;
-    hipError_t need(Buf &b, size_t bytes) {
-        if (bytes <= b.cap && b.p) return hipSuccess;
-        if (b.p) (void)hipFree(b.p);
-        b.p = nullptr; b.cap = 0;
-        hipError_t e = hipMalloc(&b.p, bytes ? bytes : 1);
-        if (e == hipSuccess) b.cap = bytes ? bytes : 1;
-        return e;
-    }
     hipError_t event(size_t i, hipEvent_t *out) {
         while (evs.size() <= i) {
             hipEvent_t ev = nullptr;
@@ -752,9 +736,6 @@ struct FlatWs {
         return hipSuccess;
     }
     ~FlatWs() {
-        for (Buf *b : {&q, &zero, &qm, &qrm, &qc, &qd, &qdp, &qs, &cs, &pool, &thr, &app, &appcnt, &oi, &os, &oc, &scores, &part, &out})
-            if (b->p) (void)hipFree(b->p);
-        if (h_out) (void)hipHostFree(h_out);
         for (hipEvent_t ev : evs) (void)hipEventDestroy(ev);
     }
 };
@@ -811,30 +792,32 @@ extern "C" int32_t cos_flat_search_batch(cos_index *ix, const float *queries, ui
     double streamed = 0.0;
     bool zero = false;
     hipError_t e = hipSuccess;
+    auto need = [&e](auto &buf, auto *&ptr, size_t count) { // the workspace's buffer grown to `count` elements
+        if (e == hipSuccess) { e = buf.grow(count); ptr = buf; }
+    };
     for (int attempt = 0; attempt < 2 && e == hipSuccess; attempt++) {
         const bool fused = allow_fused && attempt == 0 && n > SEED;
         const u32 first = fused ? SEED : chunk;                              // size of the (unfused) first chunk
         const u64 s_stride = ((u64)std::min(first, n) + 63) & ~63ull;
         const u32 S = select_segments(B, std::min(first, n));
         if (attempt == 0) {
-#define WS_NEED(buf, ptr, bytes) if (e == hipSuccess) { e = W->need(W->buf, (bytes)); ptr = (decltype(ptr))W->buf.p; }
-            WS_NEED(q, d_q, (size_t)B * dim * 4)
-            WS_NEED(zero, d_zero, 8)
+            need(W->q, d_q, (size_t)B * dim);
+            need(W->zero, d_zero, 2);
             if (e == hipSuccess) e = hipMemsetAsync(d_zero, 0, 8, st);
-            WS_NEED(qm, d_qm, (size_t)B * 4)
-            WS_NEED(qrm, d_qrm, (size_t)B * 4)
-            WS_NEED(qc, d_qc, (size_t)B * ix->row_stride)
-            WS_NEED(qd, d_qd, (size_t)B * kdims)
-            if (use_areg) WS_NEED(qdp, d_qdp, (size_t)B * kdims)
-            WS_NEED(qs, d_qs, (size_t)B * 4)
-            WS_NEED(cs, d_cs, ((size_t)n + 1) * 4)
-            WS_NEED(pool, d_pool, (size_t)B * SEL * 8)
-            WS_NEED(thr, d_thr, (size_t)B * 8)
-            WS_NEED(app, d_app, (size_t)B * APP_CAP * 8)
-            WS_NEED(appcnt, d_appcnt, (size_t)B * 4)
-            WS_NEED(oi, d_oi, (size_t)B * top_k * 4)
-            WS_NEED(os, d_os, (size_t)B * top_k * 4)
-            WS_NEED(oc, d_oc, (size_t)B * 4)
+            need(W->qm, d_qm, B);
+            need(W->qrm, d_qrm, B);
+            need(W->qc, d_qc, (size_t)B * ix->row_stride);
+            need(W->qd, d_qd, (size_t)B * kdims);
+            if (use_areg) need(W->qdp, d_qdp, (size_t)B * kdims);
+            need(W->qs, d_qs, B);
+            need(W->cs, d_cs, (size_t)n + 1);
+            need(W->pool, d_pool, (size_t)B * SEL);
+            need(W->thr, d_thr, B);
+            need(W->app, d_app, (size_t)B * APP_CAP);
+            need(W->appcnt, d_appcnt, B);
+            need(W->oi, d_oi, (size_t)B * top_k);
+            need(W->os, d_os, (size_t)B * top_k);
+            need(W->oc, d_oc, B);
             if (e == hipSuccess) e = hipMemcpyAsync(d_q, queries, (size_t)B * dim * 4, hipMemcpyHostToDevice, st);
             if (e == hipSuccess) e = launch_quantize_rows(ix->eng, d_q, dim, B, dim, ix->p.range_lo, ix->p.range_hi, d_qc, ix->row_stride, d_qm, d_qrm, st);
             if (e == hipSuccess && ix->eng == ENG_U8) {
@@ -874,9 +857,8 @@ extern "C" int32_t cos_flat_search_batch(cos_index *ix, const float *queries, ui
                 }
             }
         }
-        WS_NEED(scores, d_scores, (size_t)B * s_stride * 4)
-        WS_NEED(part, d_part, (size_t)B * S * SEL * 8)
-#undef WS_NEED
+        need(W->scores, d_scores, (size_t)B * s_stride);
+        need(W->part, d_part, (size_t)B * S * SEL);
         if (e == hipSuccess) {
             hipLaunchKernelGGL(flat_reset_kernel, dim3(64), dim3(256), 0, st, d_pool, (u64)B * SEL, d_thr, d_appcnt, B, d_zero + 1); // (d_zero + 1: overflow flag of the fused path)
             e = hipGetLastError();
@@ -929,17 +911,17 @@ extern "C" int32_t cos_flat_search_batch(cos_index *ix, const float *queries, ui
         // rerank, then ONE copy back: results, the zero-norm flag of the queries and the overflow flag of the fused path.  (Until round 6: a
         // device round trip for the overflow flag, then the rerank, then three pageable copies.)  An overflow repeats the scan unfused.
         const size_t nk = (size_t)B * top_k, out_words = 2 * nk + B + 2;
-        if (e == hipSuccess) e = W->need(W->out, out_words * 4);
-        if (e == hipSuccess) e = W->need_host(out_words * 4);
+        if (e == hipSuccess) e = W->out.grow(out_words);
+        if (e == hipSuccess) e = W->h_out.grow(out_words);
         if (e != hipSuccess) break;
         hipLaunchKernelGGL(flat_rerank_top5k, dim3(B), dim3(64), (((size_t)dim * 4 + 15) & ~(size_t)15), st, d_q, (u64)dim, d_qrm, B, ix->d_raw, (u64)dim,
                            ix->d_raw_mags, dim, d_pool, 5 * top_k, top_k, ix->p.id_base, d_oi, d_os, d_oc);
-        hipLaunchKernelGGL(flat_pack_out_kernel, dim3((u32)((std::max<size_t>(nk, B) + 255) / 256)), dim3(256), 0, st, d_oi, d_os, d_oc, d_zero, B, top_k, (u32 *)W->out.p);
+        hipLaunchKernelGGL(flat_pack_out_kernel, dim3((u32)((std::max<size_t>(nk, B) + 255) / 256)), dim3(256), 0, st, d_oi, d_os, d_oc, d_zero, B, top_k, W->out.p);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(W->h_out, W->out.p, out_words * 4, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e != hipSuccess) break;
-        const u32 *ho = (const u32 *)W->h_out;
+        const u32 *ho = W->h_out;
         zero = ho[2 * nk + B] != 0;
         const u32 hover = ho[2 * nk + B + 1];
         if (zero) break;

@@ -298,29 +298,32 @@ struct cos_bm25 {
     u32 dir_rows = 0, dir_tiles = 0; // shape of d_tile_dir: [dir_rows][dir_tiles + 1]
     std::vector<u32> term_hashes;
     std::vector<u64> offsets;
-    u32 *d_docs = nullptr;
-    float *d_tfs = nullptr;
+    DevArr<u32> d_docs;
+    DevArr<float> d_tfs;
     std::vector<u32> dir_row; // [n_terms] row in the tile directory or NO_DIR
-    u32 *d_tile_dir = nullptr; // [rows][n_tiles + 1]
+    DevArr<u32> d_tile_dir; // [rows][n_tiles + 1]
     // per-handle workspace of the search (grown on demand, reused across calls: no allocation on the query path)
     std::mutex mu;
-    QueryTerms *d_qt = nullptr, *h_qt = nullptr; // device / pinned host; followed by the launch order u32[capB] in the same allocation
-    u64 *d_buckets = nullptr;
-    u32 *d_ids = nullptr, *d_cnt = nullptr;
-    float *d_sc = nullptr;
+    DevBuf d_qt;                  // QueryTerms[capB], followed by the launch order u32[capB] in the same allocation
+    PinArr<unsigned char> h_qt;   // ... and its pinned host image
+    DevArr<u64> d_buckets;
+    DevArr<u32> d_ids, d_cnt;
+    DevArr<float> d_sc;
     u32 capB = 0, cap_k = 0;
     hipStream_t stream = nullptr;
     // cos_hybrid_search_batch: dense half + fusion (second stream, buffers grown on demand)
     hipStream_t stream_dense = nullptr;
     hipEvent_t ev_sparse = nullptr;
-    float *d_hq = nullptr, *d_dsc = nullptr;
-    u32 *d_did = nullptr, *d_dcnt = nullptr;
+    DevArr<float> d_hq, d_dsc;
+    DevArr<u32> d_did, d_dcnt;
     // what goes back to the caller, side by side for ONE copy: [fused ids B x k | fused scores B x k | counts B | dense status B]
-    u32 *d_ret = nullptr;
-    void *h_ret = nullptr; // its pinned landing area
-    // one capacity per buffer, written back by grow_buf itself: a failed hipMalloc leaves that buffer null WITH capacity 0,
-    // so a later, smaller batch grows it again instead of launching on a null pointer
-    size_t cap_hq = 0, cap_did = 0, cap_dsc = 0, cap_dcnt = 0, cap_ret = 0, cap_hret = 0;
+    DevArr<u32> d_ret;
+    PinArr<u32> h_ret; // its pinned landing area
+    ~cos_bm25() { // (cos_bm25_destroy has drained both streams)
+        if (stream) (void)hipStreamDestroy(stream);
+        if (stream_dense) (void)hipStreamDestroy(stream_dense);
+        if (ev_sparse) (void)hipEventDestroy(ev_sparse);
+    }
 };
 
 extern "C" int32_t cos_bm25_create(int32_t device, const uint32_t *term_hashes, const uint64_t *offsets, uint32_t n_terms, const uint32_t *doc_ids,
@@ -363,9 +366,9 @@ extern "C" int32_t cos_bm25_create(int32_t device, const uint32_t *term_hashes, 
         }
         dir[base + n_tiles] = (u32)(hi - lo);
     }
-    hipError_t e = hipMalloc(&b->d_docs, std::max<u64>(nnz, 1) * 4);
-    if (e == hipSuccess) e = hipMalloc(&b->d_tfs, std::max<u64>(nnz, 1) * 4);
-    if (e == hipSuccess) e = hipMalloc(&b->d_tile_dir, std::max<size_t>(dir.size(), 1) * 4);
+    hipError_t e = b->d_docs.alloc(nnz);
+    if (e == hipSuccess) e = b->d_tfs.alloc(nnz);
+    if (e == hipSuccess) e = b->d_tile_dir.alloc(dir.size());
     if (e == hipSuccess) e = hipMemcpy(b->d_docs, doc_ids, nnz * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(b->d_tfs, tfs, nnz * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess && !dir.empty()) e = hipMemcpy(b->d_tile_dir, dir.data(), dir.size() * 4, hipMemcpyHostToDevice);
@@ -380,14 +383,8 @@ extern "C" int32_t cos_bm25_create(int32_t device, const uint32_t *term_hashes, 
 extern "C" int32_t cos_bm25_destroy(cos_bm25 *b) {
     if (!b) return COS_OK;
     (void)hipSetDevice(b->device);
-    if (b->stream) { (void)hipStreamSynchronize(b->stream); (void)hipStreamDestroy(b->stream); }
-    if (b->stream_dense) { (void)hipStreamSynchronize(b->stream_dense); (void)hipStreamDestroy(b->stream_dense); }
-    if (b->ev_sparse) (void)hipEventDestroy(b->ev_sparse);
-    void *ptrs[] = {b->d_docs, b->d_tfs, b->d_qt, b->d_buckets, b->d_ids, b->d_cnt, b->d_sc, b->d_tile_dir,
-                    b->d_hq, b->d_dsc, b->d_did, b->d_dcnt, b->d_ret};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    if (b->h_qt) (void)hipHostFree(b->h_qt);
-    if (b->h_ret) (void)hipHostFree(b->h_ret);
+    if (b->stream) (void)hipStreamSynchronize(b->stream);
+    if (b->stream_dense) (void)hipStreamSynchronize(b->stream_dense);
     delete b;
     return COS_OK;
 }
@@ -395,10 +392,11 @@ extern "C" int32_t cos_bm25_destroy(cos_bm25 *b) {
 // host side of a batch: sort each query's terms by hash, look the posting lists up, idf via libm log1pf
 // (sparse_ann_query.rs:298-302) -> QueryTerms in pinned memory
 static int32_t bm25_prepare(cos_bm25 *b, const uint32_t *q_terms, const uint32_t *q_offsets, u32 B) {
+    QueryTerms *h_qt = b->h_qt.as<QueryTerms>();
     for (u32 q = 0; q < B; q++) {
         std::vector<u32> t(q_terms + q_offsets[q], q_terms + q_offsets[q + 1]);
         std::sort(t.begin(), t.end());
-        QueryTerms &qt = b->h_qt[q];
+        QueryTerms &qt = h_qt[q];
         qt.n = 0;
         for (u32 h : t) {
             auto it = std::lower_bound(b->term_hashes.begin(), b->term_hashes.end(), h);
@@ -417,11 +415,11 @@ static int32_t bm25_prepare(cos_bm25 *b, const uint32_t *q_terms, const uint32_t
     std::vector<std::pair<u64, u32>> w(B);
     for (u32 q = 0; q < B; q++) {
         u64 tot = 0;
-        for (u32 t = 0; t < b->h_qt[q].n; t++) tot += b->h_qt[q].end[t] - b->h_qt[q].begin[t];
+        for (u32 t = 0; t < h_qt[q].n; t++) tot += h_qt[q].end[t] - h_qt[q].begin[t];
         w[q] = {~tot, q};
     }
     std::sort(w.begin(), w.end());
-    u32 *order = (u32 *)(b->h_qt + b->capB);
+    u32 *order = (u32 *)(h_qt + b->capB);
     for (u32 q = 0; q < B; q++) order[q] = w[q].second;
     return COS_OK;
 }
@@ -431,17 +429,13 @@ static int32_t bm25_workspace(cos_bm25 *b, u32 B, u32 top_k) {
     if (B > b->capB || top_k > b->cap_k) {
         HIP_TRY(hipStreamSynchronize(b->stream));
         const u32 nb = std::max(B, b->capB), nk = std::max(top_k, b->cap_k);
-        void *ptrs[] = {b->d_qt, b->d_buckets, b->d_ids, b->d_cnt, b->d_sc};
-        for (void *p : ptrs) if (p) (void)hipFree(p);
-        if (b->h_qt) (void)hipHostFree(b->h_qt);
-        b->d_qt = nullptr; b->h_qt = nullptr; b->d_buckets = nullptr; b->d_ids = nullptr; b->d_cnt = nullptr; b->d_sc = nullptr;
-        b->capB = b->cap_k = 0;
-        HIP_TRY(hipMalloc((void **)&b->d_qt, (size_t)nb * (sizeof(QueryTerms) + 4)));
-        HIP_TRY(hipHostMalloc((void **)&b->h_qt, (size_t)nb * (sizeof(QueryTerms) + 4)));
-        HIP_TRY(hipMalloc((void **)&b->d_buckets, (size_t)nb * BUCKETS * 8));
-        HIP_TRY(hipMalloc((void **)&b->d_ids, (size_t)nb * nk * 4));
-        HIP_TRY(hipMalloc((void **)&b->d_sc, (size_t)nb * nk * 4));
-        HIP_TRY(hipMalloc((void **)&b->d_cnt, (size_t)nb * 4));
+        b->capB = b->cap_k = 0; // (a failure below leaves a workspace for no query: the next call allocates all of it again)
+        HIP_TRY(b->d_qt.alloc((size_t)nb * (sizeof(QueryTerms) + 4)));
+        HIP_TRY(b->h_qt.alloc((size_t)nb * (sizeof(QueryTerms) + 4)));
+        HIP_TRY(b->d_buckets.alloc((size_t)nb * BUCKETS));
+        HIP_TRY(b->d_ids.alloc((size_t)nb * nk));
+        HIP_TRY(b->d_sc.alloc((size_t)nb * nk));
+        HIP_TRY(b->d_cnt.alloc(nb));
         b->capB = nb;
         b->cap_k = nk;
     }
@@ -450,8 +444,9 @@ static int32_t bm25_workspace(cos_bm25 *b, u32 B, u32 top_k) {
 
 // scoring + bucket top-k enqueued on `st`; outputs are device pointers
 static int32_t bm25_launch(cos_bm25 *b, u32 B, u32 top_k, u32 *d_out_ids, float *d_out_scores, u32 *d_out_counts, hipStream_t st) {
-    HIP_TRY(hipMemcpyAsync(b->d_qt, b->h_qt, (size_t)B * sizeof(QueryTerms), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(b->d_qt + b->capB, b->h_qt + b->capB, (size_t)B * 4, hipMemcpyHostToDevice, st));
+    const QueryTerms *d_qt = b->d_qt.as<QueryTerms>(), *h_qt = b->h_qt.as<QueryTerms>();
+    HIP_TRY(hipMemcpyAsync(b->d_qt, h_qt, (size_t)B * sizeof(QueryTerms), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b->d_qt.as<QueryTerms>() + b->capB, h_qt + b->capB, (size_t)B * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(b->d_buckets, 0, (size_t)B * BUCKETS * 8, st));
     const u32 span = b->max_doc + 1; // doc ids are internal ids; the largest one bounds the tile count
     // launch shape: enough blocks that the heaviest query's share is small against the whole launch, few enough that a block's fixed
@@ -462,11 +457,11 @@ static int32_t bm25_launch(cos_bm25 *b, u32 B, u32 top_k, u32 *d_out_ids, float 
     const u32 splits = std::max(1u, std::min(n_tiles, std::max(1u, target_blocks / B)));
     // an index that holds no tombstone (never the target of a delete that found something) keeps the kernel without the tombstone test
     if (b->n_tombstones)
-        hipLaunchKernelGGL(bm25_score_kernel<true>, dim3(B * splits), dim3(256), 0, st, b->d_docs, b->d_tfs, b->d_qt, span, b->d_tile_dir, b->d_buckets,
-                           (const u32 *)(b->d_qt + b->capB), splits);
+        hipLaunchKernelGGL(bm25_score_kernel<true>, dim3(B * splits), dim3(256), 0, st, b->d_docs, b->d_tfs, d_qt, span, b->d_tile_dir, b->d_buckets,
+                           (const u32 *)(d_qt + b->capB), splits);
     else
-        hipLaunchKernelGGL(bm25_score_kernel<false>, dim3(B * splits), dim3(256), 0, st, b->d_docs, b->d_tfs, b->d_qt, span, b->d_tile_dir, b->d_buckets,
-                           (const u32 *)(b->d_qt + b->capB), splits);
+        hipLaunchKernelGGL(bm25_score_kernel<false>, dim3(B * splits), dim3(256), 0, st, b->d_docs, b->d_tfs, d_qt, span, b->d_tile_dir, b->d_buckets,
+                           (const u32 *)(d_qt + b->capB), splits);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(bm25_topk_kernel, dim3(B), dim3(64), 0, st, b->d_buckets, B, top_k, d_out_ids, d_out_scores, d_out_counts);
     HIP_TRY(hipGetLastError());
@@ -522,36 +517,31 @@ extern "C" int32_t cos_rrf_fuse_batch(const uint32_t *dense_ids, const uint32_t 
         maxn = std::max(maxn, dense_counts[q] + sparse_counts[q]);
     }
     if (maxn > 1024) return cos_fail(COS_ERR_UNIMPLEMENTED, "RRF lists longer than 1024 entries");
-    u32 *d_d = nullptr, *d_dc = nullptr, *d_s = nullptr, *d_sc = nullptr, *d_oi = nullptr, *d_oc = nullptr;
-    float *d_os = nullptr;
-    hipError_t e = hipMalloc(&d_d, (size_t)B * dense_stride * 4);
-    if (e == hipSuccess) e = hipMalloc(&d_s, (size_t)B * sparse_stride * 4);
-    if (e == hipSuccess) e = hipMalloc(&d_dc, (size_t)B * 4);
-    if (e == hipSuccess) e = hipMalloc(&d_sc, (size_t)B * 4);
-    if (e == hipSuccess) e = hipMalloc(&d_oi, (size_t)B * top_k * 4);
-    if (e == hipSuccess) e = hipMalloc(&d_os, (size_t)B * top_k * 4);
-    if (e == hipSuccess) e = hipMalloc(&d_oc, (size_t)B * 4);
-    if (e == hipSuccess) e = hipMemcpy(d_d, dense_ids, (size_t)B * dense_stride * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_s, sparse_ids, (size_t)B * sparse_stride * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_dc, dense_counts, (size_t)B * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_sc, sparse_counts, (size_t)B * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        const size_t smem = (size_t)std::max(maxn, 1u) * 4;
+    DevArr<u32> d_d, d_dc, d_s, d_sc, d_oi, d_oc;
+    DevArr<float> d_os;
+    HIP_TRY(d_d.alloc((size_t)B * dense_stride));
+    HIP_TRY(d_s.alloc((size_t)B * sparse_stride));
+    HIP_TRY(d_dc.alloc(B));
+    HIP_TRY(d_sc.alloc(B));
+    HIP_TRY(d_oi.alloc((size_t)B * top_k));
+    HIP_TRY(d_os.alloc((size_t)B * top_k));
+    HIP_TRY(d_oc.alloc(B));
+    HIP_TRY(hipMemcpy(d_d, dense_ids, (size_t)B * dense_stride * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_s, sparse_ids, (size_t)B * sparse_stride * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_dc, dense_counts, (size_t)B * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_sc, sparse_counts, (size_t)B * 4, hipMemcpyHostToDevice));
+    const size_t smem = (size_t)std::max(maxn, 1u) * 4;
 #define LAUNCH(R) hipLaunchKernelGGL(rrf_kernel<R>, dim3(B), dim3(64), smem, 0, d_d, d_dc, dense_stride, d_s, d_sc, sparse_stride, B, fusion_constant_k, top_k, d_oi, d_os, d_oc)
-        if (maxn <= 64) LAUNCH(1);
-        else if (maxn <= 128) LAUNCH(2);
-        else if (maxn <= 256) LAUNCH(4);
-        else if (maxn <= 512) LAUNCH(8);
-        else LAUNCH(16);
+    if (maxn <= 64) LAUNCH(1);
+    else if (maxn <= 128) LAUNCH(2);
+    else if (maxn <= 256) LAUNCH(4);
+    else if (maxn <= 512) LAUNCH(8);
+    else LAUNCH(16);
 #undef LAUNCH
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(out_ids, d_oi, (size_t)B * top_k * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(out_scores, d_os, (size_t)B * top_k * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(out_counts, d_oc, (size_t)B * 4, hipMemcpyDeviceToHost);
-    void *ptrs[] = {d_d, d_s, d_dc, d_sc, d_oi, d_os, d_oc};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    HIP_TRY(e);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out_ids, d_oi, (size_t)B * top_k * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_scores, d_os, (size_t)B * top_k * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_counts, d_oc, (size_t)B * 4, hipMemcpyDeviceToHost));
     return COS_OK;
 }
 
@@ -561,17 +551,6 @@ extern "C" int32_t cos_rrf_fuse_batch(const uint32_t *dense_ids, const uint32_t 
 // for top_k * 3 (:200, :240, :251) — here concurrently, on two streams of the same device — and the two lists are fused with
 // RRF on the device; only the fused top_k crosses PCIe.
 // ------------------------------------------------------------------------------------------------
-template <typename T>
-static hipError_t grow_buf(T *&p, size_t &cap, size_t need) {
-    if (need <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    hipError_t e = hipMalloc((void **)&p, need * sizeof(T));
-    if (e == hipSuccess) cap = need;
-    return e;
-}
-
 extern "C" int32_t cos_hybrid_search_batch(cos_index *ix, cos_bm25 *b, const float *queries, const uint32_t *q_terms, const uint32_t *q_offsets, uint32_t B,
                                            uint32_t top_k, float fusion_constant_k, uint32_t *out_ids, float *out_scores, uint32_t *out_counts) {
     if (!ix || !b || !queries || !q_terms || !q_offsets || !out_ids || !out_scores || !out_counts || B == 0 || top_k == 0) return cos_fail(COS_ERR_INVALID, "bad argument");
@@ -591,19 +570,13 @@ extern "C" int32_t cos_hybrid_search_batch(cos_index *ix, cos_bm25 *b, const flo
     HIP_TRY(hipStreamSynchronize(b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream_dense));
     const size_t dim = ix->p.dim;
-    HIP_TRY(grow_buf(b->d_hq, b->cap_hq, (size_t)B * dim));
-    HIP_TRY(grow_buf(b->d_did, b->cap_did, (size_t)B * k3));
-    HIP_TRY(grow_buf(b->d_dsc, b->cap_dsc, (size_t)B * k3));
-    HIP_TRY(grow_buf(b->d_dcnt, b->cap_dcnt, (size_t)B));
+    HIP_TRY(b->d_hq.grow((size_t)B * dim));
+    HIP_TRY(b->d_did.grow((size_t)B * k3));
+    HIP_TRY(b->d_dsc.grow((size_t)B * k3));
+    HIP_TRY(b->d_dcnt.grow((size_t)B));
     const size_t nk = (size_t)B * top_k, ret_words = 2 * nk + 2 * (size_t)B;
-    HIP_TRY(grow_buf(b->d_ret, b->cap_ret, ret_words));
-    if (ret_words * 4 > b->cap_hret) {
-        if (b->h_ret) (void)hipHostFree(b->h_ret);
-        b->h_ret = nullptr;
-        b->cap_hret = 0;
-        HIP_TRY(hipHostMalloc(&b->h_ret, ret_words * 4));
-        b->cap_hret = ret_words * 4;
-    }
+    HIP_TRY(b->d_ret.grow(ret_words));
+    HIP_TRY(b->h_ret.grow(ret_words));
     u32 *d_fid = b->d_ret, *d_fcnt = b->d_ret + 2 * nk;
     float *d_fsc = (float *)(b->d_ret + nk);
     int32_t *d_dst = (int32_t *)(b->d_ret + 2 * nk + B);
@@ -635,7 +608,7 @@ extern "C" int32_t cos_hybrid_search_batch(cos_index *ix, cos_bm25 *b, const flo
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(b->h_ret, b->d_ret, ret_words * 4, hipMemcpyDeviceToHost, sd)); // (until round 6: four pageable copies)
     HIP_TRY(hipStreamSynchronize(sd));
-    const u32 *hr = (const u32 *)b->h_ret;
+    const u32 *hr = b->h_ret;
     memcpy(out_ids, hr, nk * 4);
     memcpy(out_scores, hr + nk, nk * 4);
     memcpy(out_counts, hr + 2 * nk, (size_t)B * 4);
@@ -771,21 +744,6 @@ __global__ __launch_bounds__(256) void bm25_tombstone_kernel(const u32 *__restri
     }
 }
 
-// device allocations of one update call: whatever is still listed when the call leaves (by any path) is freed
-struct UpdateAllocs {
-    std::vector<void *> ptrs;
-    ~UpdateAllocs() { for (void *p : ptrs) if (p) (void)hipFree(p); }
-    template <typename T>
-    hipError_t alloc(T *&out, size_t n) {
-        void *p = nullptr;
-        const hipError_t e = hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T));
-        if (e == hipSuccess) ptrs.push_back(p);
-        out = (T *)p;
-        return e;
-    }
-    void keep(void *p) { ptrs.erase(std::remove(ptrs.begin(), ptrs.end(), p), ptrs.end()); } // now owned by the handle
-};
-
 // updates wait for everything the handle has in flight (the caller holds b->mu): a search sees the index before or after, never between
 int32_t bm25_quiesce(cos_bm25 *b) {
     HIP_TRY(hipSetDevice(b->device));
@@ -841,7 +799,6 @@ extern "C" int32_t cos_bm25_insert(cos_bm25 *b, const uint32_t *doc_ids, const u
         return COS_OK;
     }
     hipStream_t st = b->stream;
-    UpdateAllocs A;
     const u32 n = (u32)nd;
 
     // 1. the delta in term-major order (uploads from host arrays are synchronous copies: an early return never leaves one in flight)
@@ -852,32 +809,28 @@ extern "C" int32_t cos_bm25_insert(cos_bm25 *b, const uint32_t *doc_ids, const u
         if (doc_offsets[i + 1] > doc_offsets[i]) delta_max_doc = doc_ids[i];
     }
     std::iota(h_iota.begin(), h_iota.end(), 0u);
-    u32 *d_keys = nullptr, *d_keys_sorted = nullptr, *d_iota = nullptr, *d_perm = nullptr, *d_pdocs = nullptr, *d_del_docs = nullptr;
-    u32 *d_uniq = nullptr, *d_counts = nullptr, *d_nruns = nullptr;
-    float *d_ptfs = nullptr, *d_del_tfs = nullptr;
-    void *d_tmp = nullptr;
-    HIP_TRY(A.alloc(d_keys, n)); HIP_TRY(A.alloc(d_keys_sorted, n)); HIP_TRY(A.alloc(d_iota, n)); HIP_TRY(A.alloc(d_perm, n));
-    HIP_TRY(A.alloc(d_pdocs, n)); HIP_TRY(A.alloc(d_ptfs, n)); HIP_TRY(A.alloc(d_del_docs, n)); HIP_TRY(A.alloc(d_del_tfs, n));
-    HIP_TRY(A.alloc(d_uniq, n)); HIP_TRY(A.alloc(d_counts, n)); HIP_TRY(A.alloc(d_nruns, 1));
+    // (device allocations of the call are locals: whatever has not moved into the handle when the call leaves, by any path, is freed)
+    DevArr<u32> d_keys, d_keys_sorted, d_iota, d_perm, d_pdocs, d_del_docs, d_uniq, d_counts, d_nruns;
+    DevArr<float> d_ptfs, d_del_tfs;
+    DevBuf d_tmp;
+    HIP_TRY(d_keys.alloc(n)); HIP_TRY(d_keys_sorted.alloc(n)); HIP_TRY(d_iota.alloc(n)); HIP_TRY(d_perm.alloc(n));
+    HIP_TRY(d_pdocs.alloc(n)); HIP_TRY(d_ptfs.alloc(n)); HIP_TRY(d_del_docs.alloc(n)); HIP_TRY(d_del_tfs.alloc(n));
+    HIP_TRY(d_uniq.alloc(n)); HIP_TRY(d_counts.alloc(n)); HIP_TRY(d_nruns.alloc(1));
     size_t sort_bytes = 0, rle_bytes = 0;
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, d_keys, d_keys_sorted, d_iota, d_perm, (int)n, 0, 32, st));
-    HIP_TRY(hipcub::DeviceRunLengthEncode::Encode(nullptr, rle_bytes, d_keys_sorted, d_uniq, d_counts, d_nruns, (int)n, st));
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, d_keys.p, d_keys_sorted.p, d_iota.p, d_perm.p, (int)n, 0, 32, st));
+    HIP_TRY(hipcub::DeviceRunLengthEncode::Encode(nullptr, rle_bytes, d_keys_sorted.p, d_uniq.p, d_counts.p, d_nruns.p, (int)n, st));
     size_t tmp_bytes = std::max(sort_bytes, rle_bytes);
-    {
-        unsigned char *t = nullptr;
-        HIP_TRY(A.alloc(t, tmp_bytes));
-        d_tmp = t;
-    }
+    HIP_TRY(d_tmp.alloc(tmp_bytes));
     HIP_TRY(hipMemcpy(d_keys, term_hashes, (size_t)n * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_iota, h_iota.data(), (size_t)n * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_pdocs, h_pdocs.data(), (size_t)n * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_ptfs, tfs, (size_t)n * 4, hipMemcpyHostToDevice));
     size_t bytes = tmp_bytes;
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, bytes, d_keys, d_keys_sorted, d_iota, d_perm, (int)n, 0, 32, st)); // LSD radix sort: stable
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, bytes, d_keys.p, d_keys_sorted.p, d_iota.p, d_perm.p, (int)n, 0, 32, st)); // LSD radix sort: stable
     hipLaunchKernelGGL(bm25_delta_gather_kernel, dim3((n + 255) / 256), dim3(256), 0, st, d_perm, d_pdocs, d_ptfs, n, d_del_docs, d_del_tfs);
     HIP_TRY(hipGetLastError());
     bytes = tmp_bytes;
-    HIP_TRY(hipcub::DeviceRunLengthEncode::Encode(d_tmp, bytes, d_keys_sorted, d_uniq, d_counts, d_nruns, (int)n, st));
+    HIP_TRY(hipcub::DeviceRunLengthEncode::Encode(d_tmp.p, bytes, d_keys_sorted.p, d_uniq.p, d_counts.p, d_nruns.p, (int)n, st));
     u32 U = 0;
     HIP_TRY(hipMemcpyAsync(&U, d_nruns, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -932,12 +885,12 @@ extern "C" int32_t cos_bm25_insert(cos_bm25 *b, const uint32_t *doc_ids, const u
     const u64 dir_words = (u64)rows * (n_tiles + 1);
 
     // 4. new arrays, merge, directory — all on the device; the old arrays are only read
-    u32 *d_new_docs = nullptr, *d_new_dir = nullptr, *d_row_len = nullptr;
-    float *d_new_tfs = nullptr;
-    u64 *d_old_off = nullptr, *d_del_off = nullptr, *d_row_begin = nullptr;
-    HIP_TRY(A.alloc(d_new_docs, nnz)); HIP_TRY(A.alloc(d_new_tfs, nnz)); HIP_TRY(A.alloc(d_new_dir, dir_words));
-    HIP_TRY(A.alloc(d_old_off, (size_t)T + 1)); HIP_TRY(A.alloc(d_del_off, (size_t)T + 1));
-    HIP_TRY(A.alloc(d_row_begin, rows)); HIP_TRY(A.alloc(d_row_len, rows));
+    DevArr<u32> d_new_docs, d_new_dir, d_row_len;
+    DevArr<float> d_new_tfs;
+    DevArr<u64> d_old_off, d_del_off, d_row_begin;
+    HIP_TRY(d_new_docs.alloc(nnz)); HIP_TRY(d_new_tfs.alloc(nnz)); HIP_TRY(d_new_dir.alloc(dir_words));
+    HIP_TRY(d_old_off.alloc((size_t)T + 1)); HIP_TRY(d_del_off.alloc((size_t)T + 1));
+    HIP_TRY(d_row_begin.alloc(rows)); HIP_TRY(d_row_len.alloc(rows));
     HIP_TRY(hipMemcpy(d_old_off, old_off.data(), ((size_t)T + 1) * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_del_off, del_off.data(), ((size_t)T + 1) * 8, hipMemcpyHostToDevice));
     const u64 pieces = (nnz + MERGE_PIECE - 1) / MERGE_PIECE;
@@ -956,9 +909,7 @@ extern "C" int32_t cos_bm25_insert(cos_bm25 *b, const uint32_t *doc_ids, const u
     HIP_TRY(hipStreamSynchronize(st));
 
     // 5. everything is complete: swap, then free the old arrays.  The search workspace is reused as is.
-    A.keep(d_new_docs); A.keep(d_new_tfs); A.keep(d_new_dir);
-    (void)hipFree(b->d_docs); (void)hipFree(b->d_tfs); (void)hipFree(b->d_tile_dir);
-    b->d_docs = d_new_docs; b->d_tfs = d_new_tfs; b->d_tile_dir = d_new_dir;
+    b->d_docs = std::move(d_new_docs); b->d_tfs = std::move(d_new_tfs); b->d_tile_dir = std::move(d_new_dir);
     b->term_hashes.swap(new_hashes);
     b->offsets.swap(new_off);
     b->dir_row.swap(new_dir_row);
@@ -1002,10 +953,9 @@ extern "C" int32_t cos_bm25_delete(cos_bm25 *b, const uint32_t *doc_ids, const u
     u32 marked = 0;
     if (np) {
         hipStream_t st = b->stream;
-        UpdateAllocs A;
-        u32 *d_pd = nullptr, *d_pl = nullptr, *d_marked = nullptr;
-        u64 *d_pb = nullptr;
-        HIP_TRY(A.alloc(d_pd, np)); HIP_TRY(A.alloc(d_pl, np)); HIP_TRY(A.alloc(d_pb, np)); HIP_TRY(A.alloc(d_marked, 1));
+        DevArr<u32> d_pd, d_pl, d_marked;
+        DevArr<u64> d_pb;
+        HIP_TRY(d_pd.alloc(np)); HIP_TRY(d_pl.alloc(np)); HIP_TRY(d_pb.alloc(np)); HIP_TRY(d_marked.alloc(1));
         HIP_TRY(hipMemcpy(d_pd, pair_doc.data(), (size_t)np * 4, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(d_pl, pair_len.data(), (size_t)np * 4, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(d_pb, pair_begin.data(), (size_t)np * 8, hipMemcpyHostToDevice));
@@ -1035,7 +985,7 @@ extern "C" int32_t cos_bm25_stats(cos_bm25 *b, cos_bm25_index_stats *out) {
     out->tombstones = b->n_tombstones;
     u64 bytes = 2 * std::max<u64>(nnz, 1) * 4 + std::max<u64>((u64)b->dir_rows * (b->dir_tiles + 1), 1) * 4; // postings + directory
     bytes += (u64)b->capB * (sizeof(QueryTerms) + 4 + BUCKETS * 8 + 4) + 2 * (u64)b->capB * b->cap_k * 4;     // search workspace
-    bytes += ((u64)b->cap_hq + b->cap_did + b->cap_dsc + b->cap_dcnt + b->cap_ret) * 4;                       // hybrid search buffers
+    bytes += ((u64)b->d_hq.cap + b->d_did.cap + b->d_dsc.cap + b->d_dcnt.cap + b->d_ret.cap) * 4;                       // hybrid search buffers
     out->device_bytes = bytes;
     return COS_OK;
 }

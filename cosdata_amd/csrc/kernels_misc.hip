@@ -233,37 +233,32 @@ extern "C" int32_t cos_distance_batch(uint32_t metric, uint32_t storage, uint32_
     std::vector<uint8_t> hx, hy;
     rows_to_device_layout(eng, dim, (const uint8_t *)x_codes, cb, nx, row_stride, hx);
     rows_to_device_layout(eng, dim, (const uint8_t *)y_codes, cb, ny, row_stride, hy);
-    uint8_t *dx = nullptr, *dy = nullptr;
-    float *dxm = nullptr, *dym = nullptr, *dout = nullptr;
-    u32 *dpx = nullptr, *dpy = nullptr;
-    int32_t *dst = nullptr;
-    hipError_t e = hipMalloc(&dx, hx.size());
-    if (e == hipSuccess) e = hipMalloc(&dy, hy.size());
-    if (e == hipSuccess) e = hipMalloc(&dxm, (size_t)nx * 4);
-    if (e == hipSuccess) e = hipMalloc(&dym, (size_t)ny * 4);
-    if (e == hipSuccess) e = hipMalloc(&dpx, (size_t)n_pairs * 4);
-    if (e == hipSuccess) e = hipMalloc(&dpy, (size_t)n_pairs * 4);
-    if (e == hipSuccess) e = hipMalloc(&dout, (size_t)n_pairs * 4);
-    if (e == hipSuccess) e = hipMalloc(&dst, (size_t)n_pairs * 4);
-    if (e == hipSuccess) e = hipMemcpy(dx, hx.data(), hx.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dy, hy.data(), hy.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dxm, x_mags, (size_t)nx * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dym, y_mags, (size_t)ny * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dpx, pair_x, (size_t)n_pairs * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dpy, pair_y, (size_t)n_pairs * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        DistArgs a{dx, dy, dxm, dym, dpx, dpy, row_stride, n_pairs, dim, metric, nchunks, dout, dst};
-        dim3 grid(n_pairs), block(64);
-        if (eng == ENG_U8) hipLaunchKernelGGL(distance_pairs_kernel<ENG_U8>, grid, block, 0, 0, a);
-        else if (eng == ENG_Q2) hipLaunchKernelGGL(distance_pairs_kernel<ENG_Q2>, grid, block, 0, 0, a);
-        else hipLaunchKernelGGL(distance_pairs_kernel<ENG_F32>, grid, block, (size_t)row_stride, 0, a);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(out, dout, (size_t)n_pairs * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(status, dst, (size_t)n_pairs * 4, hipMemcpyDeviceToHost);
-    void *ptrs[] = {dx, dy, dxm, dym, dpx, dpy, dout, dst};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    HIP_TRY(e);
+    DevArr<uint8_t> dx, dy;
+    DevArr<float> dxm, dym, dout;
+    DevArr<u32> dpx, dpy;
+    DevArr<int32_t> dst;
+    HIP_TRY(dx.alloc(hx.size()));
+    HIP_TRY(dy.alloc(hy.size()));
+    HIP_TRY(dxm.alloc(nx));
+    HIP_TRY(dym.alloc(ny));
+    HIP_TRY(dpx.alloc(n_pairs));
+    HIP_TRY(dpy.alloc(n_pairs));
+    HIP_TRY(dout.alloc(n_pairs));
+    HIP_TRY(dst.alloc(n_pairs));
+    HIP_TRY(hipMemcpy(dx, hx.data(), hx.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dy, hy.data(), hy.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dxm, x_mags, (size_t)nx * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dym, y_mags, (size_t)ny * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dpx, pair_x, (size_t)n_pairs * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dpy, pair_y, (size_t)n_pairs * 4, hipMemcpyHostToDevice));
+    DistArgs a{dx, dy, dxm, dym, dpx, dpy, row_stride, n_pairs, dim, metric, nchunks, dout, dst};
+    dim3 grid(n_pairs), block(64);
+    if (eng == ENG_U8) hipLaunchKernelGGL(distance_pairs_kernel<ENG_U8>, grid, block, 0, 0, a);
+    else if (eng == ENG_Q2) hipLaunchKernelGGL(distance_pairs_kernel<ENG_Q2>, grid, block, 0, 0, a);
+    else hipLaunchKernelGGL(distance_pairs_kernel<ENG_F32>, grid, block, (size_t)row_stride, 0, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out, dout, (size_t)n_pairs * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(status, dst, (size_t)n_pairs * 4, hipMemcpyDeviceToHost));
     return COS_OK;
 }
 
@@ -297,21 +292,17 @@ extern "C" int32_t cos_sample_values_range(const float *x, uint32_t n, uint32_t 
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return cos_fail(COS_ERR_NO_DEVICE, "no HIP device visible; the GPU path has no CPU fallback");
     const u64 total = (u64)n * dim;
-    float *d_x = nullptr;
-    unsigned long long *d_c = nullptr, h_c[14];
-    hipError_t e = hipMalloc(&d_x, total * 4);
-    if (e == hipSuccess) e = hipMalloc(&d_c, 14 * 8);
-    if (e == hipSuccess) e = hipMemcpy(d_x, x, total * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(d_c, 0, 14 * 8);
-    if (e == hipSuccess) {
-        const u32 blocks = (u32)std::min<u64>(2048, (total + 255) / 256);
-        hipLaunchKernelGGL(sample_counts_kernel, dim3(blocks), dim3(256), 0, 0, d_x, total, d_c);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(h_c, d_c, 14 * 8, hipMemcpyDeviceToHost);
-    if (d_x) (void)hipFree(d_x);
-    if (d_c) (void)hipFree(d_c);
-    HIP_TRY(e);
+    DevArr<float> d_x;
+    DevArr<unsigned long long> d_c;
+    unsigned long long h_c[14];
+    HIP_TRY(d_x.alloc(total));
+    HIP_TRY(d_c.alloc(14));
+    HIP_TRY(hipMemcpy(d_x, x, total * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(d_c, 0, 14 * 8));
+    const u32 blocks = (u32)std::min<u64>(2048, (total + 255) / 256);
+    hipLaunchKernelGGL(sample_counts_kernel, dim3(blocks), dim3(256), 0, 0, d_x.p, total, d_c.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(h_c, d_c, 14 * 8, hipMemcpyDeviceToHost));
     // finalize_sampling: first threshold whose tail holds <= clamp_margin_percent of all values, else +-1.0
     const float values_count = (float)total; // (dimension * embeddings.len()) as f32
     const float T[7] = {0.025f, 0.05f, 0.1f, 0.2f, 0.3f, 0.4f, 0.5f};
@@ -455,21 +446,17 @@ namespace cosdev {
 // reference-layout operators for the kinds that have no device index layout
 int32_t quantize_ref_layout(uint32_t storage, uint32_t res, uint32_t dim, const float *x, uint32_t n, void *codes, float *mags) {
     const size_t cb = cos_code_bytes(storage, res, dim);
-    float *d_x = nullptr, *d_m = nullptr;
-    uint8_t *d_c = nullptr;
-    hipError_t e = hipMalloc(&d_x, (size_t)n * dim * 4);
-    if (e == hipSuccess) e = hipMalloc(&d_m, (size_t)n * 4);
-    if (e == hipSuccess) e = hipMalloc(&d_c, (size_t)n * cb);
-    if (e == hipSuccess) e = hipMemcpy(d_x, x, (size_t)n * dim * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(d_c, 0, (size_t)n * cb);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(quantize_ref_kernel, dim3((n + 3) / 4), dim3(256), 0, 0, d_x, n, dim, storage, res, d_c, (u64)cb, d_m);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(codes, d_c, (size_t)n * cb, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(mags, d_m, (size_t)n * 4, hipMemcpyDeviceToHost);
-    (void)hipFree(d_x); (void)hipFree(d_m); (void)hipFree(d_c);
-    HIP_TRY(e);
+    DevArr<float> d_x, d_m;
+    DevArr<uint8_t> d_c;
+    HIP_TRY(d_x.alloc((size_t)n * dim));
+    HIP_TRY(d_m.alloc(n));
+    HIP_TRY(d_c.alloc((size_t)n * cb));
+    HIP_TRY(hipMemcpy(d_x, x, (size_t)n * dim * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(d_c, 0, (size_t)n * cb));
+    hipLaunchKernelGGL(quantize_ref_kernel, dim3((n + 3) / 4), dim3(256), 0, 0, d_x.p, n, dim, storage, res, d_c.p, (u64)cb, d_m.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(codes, d_c, (size_t)n * cb, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(mags, d_m, (size_t)n * 4, hipMemcpyDeviceToHost));
     return COS_OK;
 }
 
@@ -477,34 +464,29 @@ int32_t distance_ref_layout(uint32_t metric, uint32_t storage, uint32_t res, uin
                             const void *y_codes, const float *y_mags, uint32_t ny, const uint32_t *pair_x, const uint32_t *pair_y, uint32_t n_pairs,
                             float *out, int32_t *status) {
     const size_t cb = cos_code_bytes(storage, res, dim);
-    uint8_t *dx = nullptr, *dy = nullptr;
-    float *dxm = nullptr, *dym = nullptr, *dout = nullptr;
-    u32 *dpx = nullptr, *dpy = nullptr;
-    int32_t *dst = nullptr;
-    hipError_t e = hipMalloc(&dx, std::max<size_t>((size_t)nx * cb, 16));
-    if (e == hipSuccess) e = hipMalloc(&dy, std::max<size_t>((size_t)ny * cb, 16));
-    if (e == hipSuccess) e = hipMalloc(&dxm, (size_t)nx * 4);
-    if (e == hipSuccess) e = hipMalloc(&dym, (size_t)ny * 4);
-    if (e == hipSuccess) e = hipMalloc(&dpx, (size_t)n_pairs * 4);
-    if (e == hipSuccess) e = hipMalloc(&dpy, (size_t)n_pairs * 4);
-    if (e == hipSuccess) e = hipMalloc(&dout, (size_t)n_pairs * 4);
-    if (e == hipSuccess) e = hipMalloc(&dst, (size_t)n_pairs * 4);
-    if (e == hipSuccess) e = hipMemcpy(dx, x_codes, (size_t)nx * cb, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dy, y_codes, (size_t)ny * cb, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dxm, x_mags, (size_t)nx * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dym, y_mags, (size_t)ny * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dpx, pair_x, (size_t)n_pairs * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dpy, pair_y, (size_t)n_pairs * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        DistRefArgs a{dx, dy, dxm, dym, dpx, dpy, (u64)cb, n_pairs, dim, metric, storage, res, dout, dst};
-        hipLaunchKernelGGL(distance_ref_kernel, dim3(n_pairs), dim3(64), 0, 0, a);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(out, dout, (size_t)n_pairs * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(status, dst, (size_t)n_pairs * 4, hipMemcpyDeviceToHost);
-    void *ptrs[] = {dx, dy, dxm, dym, dpx, dpy, dout, dst};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    HIP_TRY(e);
+    DevArr<uint8_t> dx, dy;
+    DevArr<float> dxm, dym, dout;
+    DevArr<u32> dpx, dpy;
+    DevArr<int32_t> dst;
+    HIP_TRY(dx.alloc(std::max<size_t>((size_t)nx * cb, 16)));
+    HIP_TRY(dy.alloc(std::max<size_t>((size_t)ny * cb, 16)));
+    HIP_TRY(dxm.alloc(nx));
+    HIP_TRY(dym.alloc(ny));
+    HIP_TRY(dpx.alloc(n_pairs));
+    HIP_TRY(dpy.alloc(n_pairs));
+    HIP_TRY(dout.alloc(n_pairs));
+    HIP_TRY(dst.alloc(n_pairs));
+    HIP_TRY(hipMemcpy(dx, x_codes, (size_t)nx * cb, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dy, y_codes, (size_t)ny * cb, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dxm, x_mags, (size_t)nx * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dym, y_mags, (size_t)ny * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dpx, pair_x, (size_t)n_pairs * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dpy, pair_y, (size_t)n_pairs * 4, hipMemcpyHostToDevice));
+    DistRefArgs a{dx, dy, dxm, dym, dpx, dpy, (u64)cb, n_pairs, dim, metric, storage, res, dout, dst};
+    hipLaunchKernelGGL(distance_ref_kernel, dim3(n_pairs), dim3(64), 0, 0, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out, dout, (size_t)n_pairs * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(status, dst, (size_t)n_pairs * 4, hipMemcpyDeviceToHost));
     return COS_OK;
 }
 } // namespace cosdev

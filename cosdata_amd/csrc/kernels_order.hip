@@ -26,27 +26,16 @@ __global__ void deal_to_xcds_kernel(const u32 *__restrict__ sorted, u32 B, u32 n
 
 hipError_t walk_order_reserve(WalkOrder &o, u32 B) {
     if (B <= o.cap) return hipSuccess;
-    walk_order_free(o);
+    o.cap = 0; // (a failure at any array leaves an order for no query: launch_walk_order refuses, the next reservation starts over)
     hipError_t e;
-    if ((e = hipMalloc((void **)&o.entry0, (size_t)B * 4)) != hipSuccess) return e;
-    if ((e = hipMalloc((void **)&o.order_key, (size_t)B * 4)) != hipSuccess) return e;
-    if ((e = hipMalloc((void **)&o.keys_sorted, (size_t)B * 4)) != hipSuccess) return e;
-    if ((e = hipMalloc((void **)&o.iota, (size_t)B * 4)) != hipSuccess) return e;
-    if ((e = hipMalloc((void **)&o.vals_sorted, (size_t)B * 4)) != hipSuccess) return e;
-    if ((e = hipMalloc((void **)&o.q_order, (size_t)B * 4)) != hipSuccess) return e;
+    for (DevArr<u32> *a : {&o.entry0, &o.order_key, &o.keys_sorted, &o.iota, &o.vals_sorted, &o.q_order})
+        if ((e = a->alloc(B)) != hipSuccess) return e;
     size_t bytes = 0;
-    if ((e = hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, o.order_key, o.keys_sorted, o.iota, o.vals_sorted, (int)B, 0, 32, (hipStream_t)0)) != hipSuccess)
+    if ((e = hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, o.order_key.p, o.keys_sorted.p, o.iota.p, o.vals_sorted.p, (int)B, 0, 32, (hipStream_t)0)) != hipSuccess)
         return e;
-    if ((e = hipMalloc(&o.tmp, bytes ? bytes : 16)) != hipSuccess) return e;
-    o.tmp_bytes = bytes;
+    if ((e = o.tmp.alloc(bytes)) != hipSuccess) return e;
     o.cap = B;
     return hipSuccess;
-}
-
-void walk_order_free(WalkOrder &o) {
-    void *ptrs[] = {o.entry0, o.order_key, o.keys_sorted, o.iota, o.vals_sorted, o.q_order, o.tmp};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    o = WalkOrder();
 }
 
 // order_key[0..B) / iota[0..B) (both written by the upper-level phase; keys <= key_max) -> q_order[0..B), all on `st`
@@ -55,13 +44,13 @@ hipError_t launch_walk_order(WalkOrder &o, u32 B, u32 key_max, u32 num_xcd, hipS
     int end_bit = 1;
     while (end_bit < 32 && (key_max >> end_bit)) end_bit++; // radix passes over the bits the keys have
     size_t bytes = 0;
-    hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, o.order_key, o.keys_sorted, o.iota, o.vals_sorted, (int)B, 0, end_bit, st);
+    hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, o.order_key.p, o.keys_sorted.p, o.iota.p, o.vals_sorted.p, (int)B, 0, end_bit, st);
     if (e != hipSuccess) return e;
-    if (bytes > o.tmp_bytes) return hipErrorOutOfMemory; // sized for cap >= B items: cannot happen unless the library's sizing is not monotonic
-    bytes = o.tmp_bytes;
-    e = hipcub::DeviceRadixSort::SortPairs(o.tmp, bytes, o.order_key, o.keys_sorted, o.iota, o.vals_sorted, (int)B, 0, end_bit, st);
+    if (bytes > o.tmp.cap) return hipErrorOutOfMemory; // sized for cap >= B items: cannot happen unless the library's sizing is not monotonic
+    bytes = o.tmp.cap;
+    e = hipcub::DeviceRadixSort::SortPairs(o.tmp.p, bytes, o.order_key.p, o.keys_sorted.p, o.iota.p, o.vals_sorted.p, (int)B, 0, end_bit, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(deal_to_xcds_kernel, dim3((B + 255) / 256), dim3(256), 0, st, o.vals_sorted, B, num_xcd ? num_xcd : 1u, o.q_order);
+    hipLaunchKernelGGL(deal_to_xcds_kernel, dim3((B + 255) / 256), dim3(256), 0, st, o.vals_sorted.p, B, num_xcd ? num_xcd : 1u, o.q_order.p);
     return hipGetLastError();
 }
 

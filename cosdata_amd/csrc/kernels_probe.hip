@@ -79,38 +79,29 @@ extern "C" int32_t cos_hbm_probe(int32_t device, uint32_t kind, uint64_t buffer_
     if (!out_gbps || kind > 2 || buffer_bytes < (1ull << 20) || iters == 0) return cos_fail(COS_ERR_INVALID, "bad argument");
     if (kind == 2 && (row_bytes == 0 || row_bytes > 1024 || row_bytes % 16 != 0)) return cos_fail(COS_ERR_INVALID, "row_bytes must be a multiple of 16, <= 1024");
     HIP_TRY(hipSetDevice(device));
-    uint8_t *buf = nullptr, *dst = nullptr;
-    u32 *sink = nullptr;
-    hipStream_t st = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int32_t rc = COS_OK;
-    auto cleanup = [&]() {
-        if (buf) (void)hipFree(buf);
-        if (dst) (void)hipFree(dst);
-        if (sink) (void)hipFree(sink);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        if (st) (void)hipStreamDestroy(st);
-    };
-#define TRY(x)                                                                                                             \
-    do {                                                                                                                   \
-        hipError_t _e = (x);                                                                                               \
-        if (_e != hipSuccess) {                                                                                            \
-            rc = cos_fail(COS_ERR_HIP, "%s: %s", #x, hipGetErrorString(_e));                                               \
-            cleanup();                                                                                                     \
-            return rc;                                                                                                     \
-        }                                                                                                                  \
-    } while (0)
+    struct Run { // stream and events of one probe; declared before the buffers, so they outlive them
+        hipStream_t st = nullptr;
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ~Run() {
+            if (e0) (void)hipEventDestroy(e0);
+            if (e1) (void)hipEventDestroy(e1);
+            if (st) (void)hipStreamDestroy(st);
+        }
+    } run;
+    hipStream_t &st = run.st;
+    hipEvent_t &e0 = run.e0, &e1 = run.e1;
+    DevArr<uint8_t> buf, dst;
+    DevArr<u32> sink;
     buffer_bytes &= ~0xFFFull;
-    TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    TRY(hipEventCreate(&e0));
-    TRY(hipEventCreate(&e1));
-    TRY(hipMalloc((void **)&buf, buffer_bytes));
-    TRY(hipMalloc((void **)&sink, 64));
-    TRY(hipMemsetAsync(buf, 0x5A, buffer_bytes, st));
+    HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreate(&e0));
+    HIP_TRY(hipEventCreate(&e1));
+    HIP_TRY(buf.alloc(buffer_bytes));
+    HIP_TRY(sink.alloc(16));
+    HIP_TRY(hipMemsetAsync(buf, 0x5A, buffer_bytes, st));
     if (kind == 1) {
-        TRY(hipMalloc((void **)&dst, buffer_bytes));
-        TRY(hipMemsetAsync(dst, 0, buffer_bytes, st));
+        HIP_TRY(dst.alloc(buffer_bytes));
+        HIP_TRY(hipMemsetAsync(dst, 0, buffer_bytes, st));
     }
     const u64 n16 = buffer_bytes / 16;
     const u32 n_rows = kind == 2 ? (u32)std::min<u64>(buffer_bytes / row_bytes, 0xFFFFFFFFull) : 0;
@@ -118,26 +109,24 @@ extern "C" int32_t cos_hbm_probe(int32_t device, uint32_t kind, uint64_t buffer_
     double bytes_per_launch = 0;
     auto launch = [&]() {
         if (kind == 0) {
-            hipLaunchKernelGGL(stream_read_kernel, dim3(256 * 32), dim3(256), 0, st, (const uint4 *)buf, n16, sink);
+            hipLaunchKernelGGL(stream_read_kernel, dim3(256 * 32), dim3(256), 0, st, (const uint4 *)buf.p, n16, sink.p);
             bytes_per_launch = (double)buffer_bytes;
         } else if (kind == 1) {
-            hipLaunchKernelGGL(stream_copy_kernel, dim3(256 * 32), dim3(256), 0, st, (const uint4 *)buf, (uint4 *)dst, n16);
+            hipLaunchKernelGGL(stream_copy_kernel, dim3(256 * 32), dim3(256), 0, st, (const uint4 *)buf.p, (uint4 *)dst.p, n16);
             bytes_per_launch = 2.0 * (double)buffer_bytes;
         } else {
-            hipLaunchKernelGGL(row_gather_kernel, dim3(gather_waves / 4), dim3(256), 0, st, buf, n_rows, row_bytes, rows_per_wave, sink);
+            hipLaunchKernelGGL(row_gather_kernel, dim3(gather_waves / 4), dim3(256), 0, st, buf.p, n_rows, row_bytes, rows_per_wave, sink.p);
             bytes_per_launch = (double)gather_waves * rows_per_wave * row_bytes;
         }
     };
     launch(); // warm-up (TLB, clocks)
-    TRY(hipGetLastError());
-    TRY(hipEventRecord(e0, st));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(e0, st));
     for (u32 i = 0; i < iters; i++) launch();
-    TRY(hipEventRecord(e1, st));
-    TRY(hipEventSynchronize(e1));
+    HIP_TRY(hipEventRecord(e1, st));
+    HIP_TRY(hipEventSynchronize(e1));
     float ms = 0.f;
-    TRY(hipEventElapsedTime(&ms, e0, e1));
-#undef TRY
+    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
     *out_gbps = bytes_per_launch * iters / ((double)ms * 1e-3) / 1e9;
-    cleanup();
     return COS_OK;
 }

@@ -705,40 +705,27 @@ struct cos_sparse {
     std::vector<u32> h_mult;    // [T] how often one vector id occurs in the dimension's list at most (1 unless the caller's CSR repeats ids)
     bool packed = false;        // device layout: one u32 per posting (d_pk) instead of d_ids + d_keys
     // device: one id-sorted list per dimension (same offsets as the caller's CSR: list t = [key_off[t][0], key_off[t][Q]))
-    u32 *d_ids = nullptr;
-    uint8_t *d_keys = nullptr;
-    u32 *d_pk = nullptr; // packed layout: key << 24 | (vector id + 1)
-    u32 *d_tile_dir = nullptr; // [rows][n_tiles + 1], offsets relative to the list's begin
-    u32 *d_raw_dims = nullptr;
-    u64 *d_row_off = nullptr;
-    float *d_raw_vals = nullptr;
+    DevArr<u32> d_ids;
+    DevArr<uint8_t> d_keys;
+    DevArr<u32> d_pk; // packed layout: key << 24 | (vector id + 1)
+    DevArr<u32> d_tile_dir; // [rows][n_tiles + 1], offsets relative to the list's begin
+    DevArr<u32> d_raw_dims;
+    DevArr<u64> d_row_off;
+    DevArr<float> d_raw_vals;
     // grow-only workspace of cos_sparse_search_batch (no allocation on the query path once warm); `mu` serialises callers
     std::mutex mu;
-    struct Buf { void *p = nullptr; size_t cap = 0; } w_qd, w_qv, w_qo, w_terms, w_qt_off, w_order, w_part, w_oi, w_os, w_oc;
+    DevBuf w_qd, w_qv, w_qo, w_terms, w_qt_off, w_order, w_part, w_oi, w_os, w_oc; // (bytes)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     cos_sparse_stats last{};
+    ~cos_sparse() {
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+    }
 };
-
-struct SparseView { void *p; template <typename T> T *as() const { return (T *)p; } };
-
-static hipError_t sparse_grow(cos_sparse::Buf &b, size_t need) {
-    if (need <= b.cap) return hipSuccess;
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-    hipError_t e = hipMalloc(&b.p, need);
-    if (e == hipSuccess) b.cap = need;
-    return e;
-}
 
 extern "C" int32_t cos_sparse_destroy(cos_sparse *s) {
     if (!s) return COS_OK;
     (void)hipSetDevice(s->device);
-    void *ptrs[] = {s->d_ids, s->d_keys, s->d_pk, s->d_tile_dir, s->d_raw_dims, s->d_row_off, s->d_raw_vals, s->w_qd.p, s->w_qv.p, s->w_qo.p,
-                    s->w_terms.p, s->w_qt_off.p, s->w_order.p, s->w_part.p, s->w_oi.p, s->w_os.p, s->w_oc.p};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    if (s->ev0) (void)hipEventDestroy(s->ev0);
-    if (s->ev1) (void)hipEventDestroy(s->ev1);
     delete s;
     return COS_OK;
 }
@@ -811,25 +798,25 @@ extern "C" int32_t cos_sparse_create(int32_t device, uint32_t quantization_bits,
             }
         }
     }
-    auto up = [&](void **dst, const void *src, size_t bytes) -> hipError_t {
-        hipError_t e = hipMalloc(dst, bytes ? bytes : 1);
-        return e == hipSuccess && bytes ? hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) : e;
+    auto up = [&](auto &dst, const void *src, size_t count) -> hipError_t {
+        hipError_t e = dst.alloc(count);
+        return e == hipSuccess && count ? hipMemcpy(dst, src, count * sizeof(*dst.p), hipMemcpyHostToDevice) : e;
     };
     hipError_t e = hipSuccess;
     if (s->packed) {
         std::vector<u32> m_pk((size_t)nnz + 1, 0u);
         for (u64 p = 0; p < nnz; p++) m_pk[p] = (u32)m_keys[p] << 24 | (m_ids[p] + 1u);
-        e = up((void **)&s->d_pk, m_pk.data(), m_pk.size() * 4);
+        e = up(s->d_pk, m_pk.data(), m_pk.size());
     } else {
-        e = up((void **)&s->d_ids, m_ids.data(), m_ids.size() * 4);
-        if (e == hipSuccess) e = up((void **)&s->d_keys, m_keys.data(), m_keys.size());
+        e = up(s->d_ids, m_ids.data(), m_ids.size());
+        if (e == hipSuccess) e = up(s->d_keys, m_keys.data(), m_keys.size());
     }
-    if (e == hipSuccess) e = up((void **)&s->d_tile_dir, tile_dir.data(), tile_dir.size() * 4);
+    if (e == hipSuccess) e = up(s->d_tile_dir, tile_dir.data(), tile_dir.size());
     if (e == hipSuccess && row_offsets) {
         const u64 rnnz = row_offsets[n_vectors];
-        e = up((void **)&s->d_row_off, row_offsets, ((size_t)n_vectors + 1) * 8);
-        if (e == hipSuccess) e = up((void **)&s->d_raw_dims, raw_dims, (size_t)rnnz * 4);
-        if (e == hipSuccess) e = up((void **)&s->d_raw_vals, raw_vals, (size_t)rnnz * 4);
+        e = up(s->d_row_off, row_offsets, (size_t)n_vectors + 1);
+        if (e == hipSuccess) e = up(s->d_raw_dims, raw_dims, (size_t)rnnz);
+        if (e == hipSuccess) e = up(s->d_raw_vals, raw_vals, (size_t)rnnz);
         s->have_raw = true;
     }
     if (e == hipSuccess) e = hipEventCreate(&s->ev0);
@@ -969,18 +956,18 @@ extern "C" int32_t cos_sparse_search_batch(cos_sparse *s, const uint32_t *q_dims
     // blocks: enough to fill the chip several times over, at most one per tile
     const u32 splits = std::max<u32>(1u, std::min<u32>(s->n_tiles, (4096u + B - 1) / B));
     std::lock_guard<std::mutex> guard(s->mu);
-    HIP_TRY(sparse_grow(s->w_qd, (size_t)std::max(nq, 1u) * 4));
-    HIP_TRY(sparse_grow(s->w_qv, (size_t)std::max(nq, 1u) * 4));
-    HIP_TRY(sparse_grow(s->w_qo, ((size_t)B + 1) * 4));
-    HIP_TRY(sparse_grow(s->w_terms, std::max<size_t>(terms.size(), 1) * sizeof(STerm)));
-    HIP_TRY(sparse_grow(s->w_qt_off, ((size_t)B + 1) * 4));
-    HIP_TRY(sparse_grow(s->w_order, (size_t)B * 4));
-    HIP_TRY(sparse_grow(s->w_part, (size_t)B * splits * SEL * 8));
-    HIP_TRY(sparse_grow(s->w_oi, (size_t)B * top_k * 4));
-    HIP_TRY(sparse_grow(s->w_os, (size_t)B * top_k * 4));
-    HIP_TRY(sparse_grow(s->w_oc, (size_t)B * 4));
-    const SparseView d_qd{s->w_qd.p}, d_qv{s->w_qv.p}, d_qo{s->w_qo.p}, d_terms{s->w_terms.p}, d_qt_off{s->w_qt_off.p}, d_order{s->w_order.p},
-        d_part{s->w_part.p}, d_oi{s->w_oi.p}, d_os{s->w_os.p}, d_oc{s->w_oc.p};
+    HIP_TRY(s->w_qd.grow((size_t)std::max(nq, 1u) * 4));
+    HIP_TRY(s->w_qv.grow((size_t)std::max(nq, 1u) * 4));
+    HIP_TRY(s->w_qo.grow(((size_t)B + 1) * 4));
+    HIP_TRY(s->w_terms.grow(std::max<size_t>(terms.size(), 1) * sizeof(STerm)));
+    HIP_TRY(s->w_qt_off.grow(((size_t)B + 1) * 4));
+    HIP_TRY(s->w_order.grow((size_t)B * 4));
+    HIP_TRY(s->w_part.grow((size_t)B * splits * SEL * 8));
+    HIP_TRY(s->w_oi.grow((size_t)B * top_k * 4));
+    HIP_TRY(s->w_os.grow((size_t)B * top_k * 4));
+    HIP_TRY(s->w_oc.grow((size_t)B * 4));
+    const DevBuf &d_qd = s->w_qd, &d_qv = s->w_qv, &d_qo = s->w_qo, &d_terms = s->w_terms, &d_qt_off = s->w_qt_off, &d_order = s->w_order, &d_part = s->w_part,
+                 &d_oi = s->w_oi, &d_os = s->w_os, &d_oc = s->w_oc;
     HIP_TRY(hipMemcpy(d_qd.p, q_dims, (size_t)nq * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_qv.p, q_vals, (size_t)nq * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_qo.p, q_offsets, ((size_t)B + 1) * 4, hipMemcpyHostToDevice));
@@ -991,10 +978,10 @@ extern "C" int32_t cos_sparse_search_batch(cos_sparse *s, const uint32_t *q_dims
     HIP_TRY(hipEventRecord(s->ev0, 0));
     // eight postings per lane and step; sixteen measured the same (0.447 against 0.453 ms) and was dropped
     if (s->packed)
-        hipLaunchKernelGGL(sparse_packed_kernel<8>, dim3(B * splits), dim3(256), 0, 0, s->d_pk, d_terms.as<STerm>(), d_qt_off.as<u32>(), s->n, s->d_tile_dir,
+        hipLaunchKernelGGL(sparse_packed_kernel<8>, dim3(B * splits), dim3(256), 0, 0, s->d_pk.p, d_terms.as<STerm>(), d_qt_off.as<u32>(), s->n, s->d_tile_dir.p,
                            d_order.as<u32>(), splits, d_part.as<u64>());
     else
-        hipLaunchKernelGGL(sparse_tile_kernel, dim3(B * splits), dim3(256), 0, 0, s->d_ids, s->d_keys, d_terms.as<STerm>(), d_qt_off.as<u32>(), s->n, s->d_tile_dir,
+        hipLaunchKernelGGL(sparse_tile_kernel, dim3(B * splits), dim3(256), 0, 0, s->d_ids.p, s->d_keys.p, d_terms.as<STerm>(), d_qt_off.as<u32>(), s->n, s->d_tile_dir.p,
                            d_order.as<u32>(), splits, d_part.as<u64>());
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(sparse_finish_kernel, dim3(B), dim3(64), 0, 0, dev, d_part.as<u64>(), splits, d_qd.as<u32>(), d_qv.as<float>(), d_qo.as<u32>(), top_k, kwr,

@@ -81,11 +81,20 @@ struct LocalShard {
     hipEvent_t done = nullptr;
     ncclComm_t comm = nullptr;
     // per-shard device buffers, grown on demand
-    float *d_queries = nullptr;
-    u32 *d_packed = nullptr;   // this shard's record [ids B*k | scores B*k | counts B]
-    u32 *d_gathered = nullptr; // [world][words]
-    int32_t *d_status = nullptr;
-    size_t cap_q = 0, cap_words = 0, cap_gath = 0, cap_B = 0;
+    DevArr<float> d_queries;
+    DevArr<u32> d_packed;   // this shard's record [ids B*k | scores B*k | counts B]
+    DevArr<u32> d_gathered; // [world][words]
+    DevArr<int32_t> d_status;
+    LocalShard() = default;
+    LocalShard(const LocalShard &) = delete;
+    ~LocalShard() { // on the shard's device, its stream drained before anything is released
+        (void)hipSetDevice(device);
+        if (stream) (void)hipStreamSynchronize(stream);
+        if (comm) (void)rccl()->CommDestroy(comm);
+        d_queries.reset(); d_packed.reset(); d_gathered.reset(); d_status.reset();
+        if (done) (void)hipEventDestroy(done);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
 };
 
 } // namespace
@@ -96,9 +105,8 @@ struct cos_shardset {
     bool use_rccl = false;
     std::mutex mu; // one search at a time per shard set (the collectives of two batches must not interleave)
     // merge output on shard 0's device
-    u32 *d_out_ids = nullptr, *d_out_counts = nullptr;
-    float *d_out_scores = nullptr;
-    size_t cap_out = 0, cap_outB = 0;
+    DevArr<u32> d_out_ids, d_out_counts;
+    DevArr<float> d_out_scores;
 };
 
 extern "C" int32_t cos_shardset_unique_id(uint8_t *out) {
@@ -114,18 +122,12 @@ extern "C" int32_t cos_shardset_unique_id(uint8_t *out) {
 
 extern "C" int32_t cos_shardset_destroy(cos_shardset *ss) {
     if (!ss) return COS_OK;
-    for (LocalShard &s : ss->sh) {
-        (void)hipSetDevice(s.device);
-        if (s.stream) (void)hipStreamSynchronize(s.stream);
-        if (s.comm) (void)rccl()->CommDestroy(s.comm);
-        void *ptrs[] = {s.d_queries, s.d_packed, s.d_gathered, s.d_status};
-        for (void *p : ptrs) if (p) (void)hipFree(p);
-        if (s.done) (void)hipEventDestroy(s.done);
-        if (s.stream) (void)hipStreamDestroy(s.stream);
-    }
-    if (!ss->sh.empty()) (void)hipSetDevice(ss->sh[0].device);
-    void *ptrs[] = {ss->d_out_ids, ss->d_out_counts, ss->d_out_scores};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
+    // the shards first, each on its own device (~LocalShard), then the merge output on shard 0's
+    const bool any = !ss->sh.empty();
+    const int dev0 = any ? ss->sh[0].device : 0;
+    ss->sh.clear();
+    if (any) (void)hipSetDevice(dev0);
+    ss->d_out_ids.reset(); ss->d_out_counts.reset(); ss->d_out_scores.reset();
     delete ss;
     return COS_OK;
 }
@@ -145,7 +147,7 @@ extern "C" int32_t cos_shardset_create(cos_index *const *shards, uint32_t n_loca
     cos_shardset *ss = new cos_shardset();
     ss->first_rank = first_rank;
     ss->world = world_size;
-    ss->sh.resize(n_local);
+    ss->sh = std::vector<LocalShard>(n_local);
     bool distinct = true;
     for (u32 s = 0; s < n_local; s++) {
         ss->sh[s].ix = shards[s];
@@ -211,17 +213,6 @@ static int32_t exchange_local(cos_shardset *ss, size_t words) {
     return COS_OK;
 }
 
-template <typename T>
-static hipError_t grow(T *&p, size_t &cap, size_t need) {
-    if (need <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    hipError_t e = hipMalloc((void **)&p, need * sizeof(T));
-    if (e == hipSuccess) cap = need;
-    return e;
-}
-
 extern "C" int32_t cos_shardset_search_batch(cos_shardset *ss, const float *queries, uint32_t B, uint32_t top_k, uint32_t *out_ids, float *out_scores,
                                              uint32_t *out_counts) {
     if (!ss || !queries || !out_ids || !out_scores || !out_counts || B == 0 || top_k == 0) return cos_fail(COS_ERR_INVALID, "bad argument");
@@ -239,10 +230,10 @@ extern "C" int32_t cos_shardset_search_batch(cos_shardset *ss, const float *quer
     // 1. every shard: queries up, walk + exact rerank into its packed record (all shards run concurrently on their devices)
     for (LocalShard &s : ss->sh) {
         HIP_TRY(hipSetDevice(s.device));
-        HIP_TRY(grow(s.d_queries, s.cap_q, (size_t)B * dim));
-        HIP_TRY(grow(s.d_packed, s.cap_words, words));
-        HIP_TRY(grow(s.d_gathered, s.cap_gath, words * S));
-        HIP_TRY(grow(s.d_status, s.cap_B, (size_t)B));
+        HIP_TRY(s.d_queries.grow((size_t)B * dim));
+        HIP_TRY(s.d_packed.grow(words));
+        HIP_TRY(s.d_gathered.grow(words * S));
+        HIP_TRY(s.d_status.grow((size_t)B));
         HIP_TRY(hipMemcpyAsync(s.d_queries, queries, (size_t)B * dim * 4, hipMemcpyHostToDevice, s.stream));
         int32_t rc = cos_search_batch_device(s.ix, s.d_queries, B, top_k, s.d_packed, reinterpret_cast<float *>(s.d_packed + (size_t)B * top_k),
                                              s.d_packed + 2 * (size_t)B * top_k, s.d_status, s.stream);
@@ -254,15 +245,9 @@ extern "C" int32_t cos_shardset_search_batch(cos_shardset *ss, const float *quer
     if (rc) return rc;
     LocalShard &root = ss->sh[0];
     HIP_TRY(hipSetDevice(root.device));
-    HIP_TRY(grow(ss->d_out_ids, ss->cap_out, (size_t)B * top_k));
-    if (ss->cap_outB < (size_t)B * top_k) {
-        if (ss->d_out_scores) (void)hipFree(ss->d_out_scores);
-        if (ss->d_out_counts) (void)hipFree(ss->d_out_counts);
-        ss->d_out_scores = nullptr; ss->d_out_counts = nullptr; ss->cap_outB = 0;
-        HIP_TRY(hipMalloc((void **)&ss->d_out_scores, (size_t)B * top_k * 4));
-        HIP_TRY(hipMalloc((void **)&ss->d_out_counts, (size_t)B * top_k * 4));
-        ss->cap_outB = (size_t)B * top_k;
-    }
+    HIP_TRY(ss->d_out_ids.grow((size_t)B * top_k));
+    HIP_TRY(ss->d_out_scores.grow((size_t)B * top_k));
+    HIP_TRY(ss->d_out_counts.grow((size_t)B * top_k));
     rc = cos_merge_topk_packed_device(root.d_gathered, S, B, top_k, ss->d_out_ids, ss->d_out_scores, ss->d_out_counts, root.device, root.stream);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(out_ids, ss->d_out_ids, (size_t)B * top_k * 4, hipMemcpyDeviceToHost, root.stream));
