@@ -85,6 +85,13 @@ class CosBM25Stats(C.Structure):
                 ("postings", C.c_uint64), ("tombstones", C.c_uint64), ("device_bytes", C.c_uint64)]
 
 
+class CosSparseIndexStats(C.Structure):
+    """cos_sparse_index_stats: what a learned-sparse handle holds"""
+    _fields_ = [("struct_size", C.c_uint32), ("n_vectors", C.c_uint32), ("n_dims", C.c_uint32), ("dir_rows", C.c_uint32),
+                ("dir_tiles", C.c_uint32), ("packed", C.c_uint32), ("have_raw", C.c_uint32), ("reserved", C.c_uint32),
+                ("postings", C.c_uint64), ("removed", C.c_uint64), ("raw_pairs", C.c_uint64), ("device_bytes", C.c_uint64)]
+
+
 def build(force: bool = False, verbose: bool = False) -> str:
     """Compile every HIP source for gfx950 into cosdata_amd/libcosdata_hip.so (in-tree)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
@@ -112,7 +119,8 @@ ABI_SYMBOLS = [
     "cos_index_set_visited_mode", "cos_index_set_latency_mode", "cos_index_set_latency_waves", "cos_index_set_walk_order", "cos_index_walk_order_cuts", "cos_index_set_walk_table", "cos_index_walk_table_info", "cos_index_last_walk_split", "cos_index_enable_timing", "cos_index_last_stats", "cos_index_timing_summary", "cos_quantize_batch",
     "cos_code_bytes", "cos_sample_values_range", "cos_distance_batch", "cos_bruteforce_topk", "cos_flat_search_batch", "cos_bm25_create", "cos_bm25_destroy",
     "cos_bm25_insert", "cos_bm25_delete", "cos_bm25_stats", "cos_bm25_download",
-    "cos_bm25_search_batch", "cos_bm25_search_batch_device", "cos_rrf_fuse_batch", "cos_hybrid_search_batch", "cos_text_process", "cos_text_count_tokens", "cos_bm25_term_frequency", "cos_xxhash32", "cos_stem_english", "cos_sparse_create", "cos_sparse_build_csr", "cos_sparse_create_from_vectors", "cos_sparse_destroy", "cos_sparse_search_batch", "cos_sparse_last_stats", "cos_sparse_layout", "cos_merge_topk_device", "cos_merge_topk_packed_device", "cos_hbm_probe",
+    "cos_bm25_search_batch", "cos_bm25_search_batch_device", "cos_rrf_fuse_batch", "cos_hybrid_search_batch", "cos_text_process", "cos_text_count_tokens", "cos_bm25_term_frequency", "cos_xxhash32", "cos_stem_english", "cos_sparse_create", "cos_sparse_build_csr", "cos_sparse_create_from_vectors", "cos_sparse_destroy", "cos_sparse_search_batch", "cos_sparse_last_stats", "cos_sparse_layout",
+    "cos_sparse_insert", "cos_sparse_delete", "cos_sparse_stats", "cos_sparse_download", "cos_merge_topk_device", "cos_merge_topk_packed_device", "cos_hbm_probe",
     "cos_shardset_unique_id", "cos_shardset_create", "cos_shardset_destroy", "cos_shardset_search_batch", "cos_shardset_exchange_device",
     "cos_tuning_set", "cos_tuning_clear", "cos_tuning_get",
 ]
@@ -200,6 +208,10 @@ def lib():
         "cos_sparse_search_batch": [vp, vp, vp, vp, u32, u32, f32, u32, vp, vp, vp],
         "cos_sparse_last_stats": [vp, vp],
         "cos_sparse_layout": [vp, C.POINTER(u32)],
+        "cos_sparse_insert": [vp, u32, vp, vp, vp, C.POINTER(u32)],
+        "cos_sparse_delete": [vp, vp, vp, u32, vp, vp, C.POINTER(C.c_uint64)],
+        "cos_sparse_stats": [vp, C.POINTER(CosSparseIndexStats)],
+        "cos_sparse_download": [vp, C.POINTER(u32), C.POINTER(C.c_uint64), vp, vp, vp],
         "cos_merge_topk_device": [vp, vp, vp, u32, u32, u32, vp, vp, vp, i32, vp],
         "cos_merge_topk_packed_device": [vp, u32, u32, u32, vp, vp, vp, i32, vp],
         "cos_hbm_probe": [i32, u32, C.c_uint64, u32, u32, C.POINTER(C.c_double)],

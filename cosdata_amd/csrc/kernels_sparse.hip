@@ -9,6 +9,7 @@
 // of the postings, no MFMA (integer adds).  Sums are exact u32 -> atomic adds in any order give the reference's value.  The reference returns the survivors of
 // select_nth_unstable in hash-map order; here (as in the oracle) they are ordered by similarity descending, larger id first.
 #include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cstdlib>
@@ -696,6 +697,8 @@ __global__ __launch_bounds__(64) void sparse_finish_kernel(const SparseDev ix, c
 struct cos_sparse {
     int32_t device = 0;
     u32 bits = 0, T = 0, n = 0, n_tiles = 0;
+    u32 dir_rows = 0;            // rows of d_tile_dir
+    u64 raw_nnz = 0, removed = 0; // pairs of the raw CSR; postings removed by cos_sparse_delete since create
     float upper = 1.0f;
     bool have_raw = false;
     // host side of a query's preparation: find_node, the early-termination rule, posting counts
@@ -716,7 +719,7 @@ struct cos_sparse {
     std::mutex mu;
     DevBuf w_qd, w_qv, w_qo, w_terms, w_qt_off, w_order, w_part, w_oi, w_os, w_oc; // (bytes)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    cos_sparse_stats last{};
+    cos_sparse_search_stats last{};
     ~cos_sparse() {
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
@@ -788,6 +791,7 @@ extern "C" int32_t cos_sparse_create(int32_t device, uint32_t quantization_bits,
         if (e - b > SDIR_MIN) {
             if (e - b > 0xFFFFFFFFull) { cos_sparse_destroy(s); return cos_fail(COS_ERR_UNIMPLEMENTED, "dimension %u holds more than 2^32 postings", dims[t]); }
             s->h_dir[t] = rows++;
+            s->dir_rows = rows;
             tile_dir.resize((size_t)rows * nt1);
             u32 *row = tile_dir.data() + (size_t)(rows - 1) * nt1;
             u64 p = b;
@@ -818,6 +822,7 @@ extern "C" int32_t cos_sparse_create(int32_t device, uint32_t quantization_bits,
         if (e == hipSuccess) e = up(s->d_raw_dims, raw_dims, (size_t)rnnz);
         if (e == hipSuccess) e = up(s->d_raw_vals, raw_vals, (size_t)rnnz);
         s->have_raw = true;
+        s->raw_nnz = rnnz;
     }
     if (e == hipSuccess) e = hipEventCreate(&s->ev0);
     if (e == hipSuccess) e = hipEventCreate(&s->ev1);
@@ -917,6 +922,9 @@ extern "C" int32_t cos_sparse_search_batch(cos_sparse *s, const uint32_t *q_dims
     for (u32 b = 0; b < B; b++)
         if (q_offsets[b + 1] < q_offsets[b]) return cos_fail(COS_ERR_INVALID, "query offsets decrease");
     const u32 nq = q_offsets[B], Q = 1u << s->bits;
+    // cos_sparse_insert / cos_sparse_delete replace the host tables the resolution reads (absolute list offsets included) together
+    // with the device arrays: one lock over both
+    std::lock_guard<std::mutex> guard(s->mu);
     // ---- resolve the query terms on the host (sparse_ann_query.rs:80-125): find_node, quantize, which keys the term visits ----
     const float qf = (float)Q;
     float etv = qf * early_terminate_threshold;
@@ -955,7 +963,6 @@ extern "C" int32_t cos_sparse_search_batch(cos_sparse *s, const uint32_t *q_dims
             if (counted[order[b]]) order[b] |= SPK_COUNTED;
     // blocks: enough to fill the chip several times over, at most one per tile
     const u32 splits = std::max<u32>(1u, std::min<u32>(s->n_tiles, (4096u + B - 1) / B));
-    std::lock_guard<std::mutex> guard(s->mu);
     HIP_TRY(s->w_qd.grow((size_t)std::max(nq, 1u) * 4));
     HIP_TRY(s->w_qv.grow((size_t)std::max(nq, 1u) * 4));
     HIP_TRY(s->w_qo.grow(((size_t)B + 1) * 4));
@@ -1006,9 +1013,616 @@ extern "C" int32_t cos_sparse_layout(cos_sparse *s, uint32_t *packed) {
     return COS_OK;
 }
 
-extern "C" int32_t cos_sparse_last_stats(cos_sparse *s, cos_sparse_stats *out) {
+extern "C" int32_t cos_sparse_last_stats(cos_sparse *s, cos_sparse_search_stats *out) {
     if (!s || !out) return cos_fail(COS_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> guard(s->mu);
     *out = s->last;
+    return COS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Updates of the resident postings: cos_sparse_insert / cos_sparse_delete / cos_sparse_stats / cos_sparse_download.
+//   InvertedIndex::insert / InvertedIndexRoot::insert / InvertedIndexNode::insert    indexes/inverted/mod.rs:72-89, models/inverted_index.rs:273-289, :176-201
+//   InvertedIndex::mark_embedding_as_deleted / InvertedIndexRoot::delete / Node::delete   mod.rs:91-108, inverted_index.rs:291-306, :205-222
+//   VersionedVec::delete (first entry that equals the id) and the iterator that skips tombstones   models/versioned_vec.rs:131-154, :251-275
+//
+// The postings never go back through the host.  The host owns the dimension table and the per-(dimension, key) counts (h_dims,
+// h_key_off: O(T * Q)) and sees the update itself; the device turns the vector-major update into dimension-major order (stable
+// radix sort by dimension slot: ids arrive ascending), streams old list + new postings of every dimension into NEW arrays
+// (sparse_merge_kernel), or the surviving postings of every list (sparse_compact_kernel), and searches the tile directory of the
+// new arrays (sparse_tile_dir_kernel).  A delete REMOVES the posting: the packed word has no spare bit at 8-bit keys, and a
+// search cannot tell a tombstone from an absent posting (nothing of a list but its live entries enters a score).  Only when all
+// of it is complete are the handle's pointers and host tables swapped: a call that fails before leaves the handle as it was.
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr u32 SMERGE_PIECE = 4096; // postings of the OUTPUT per workgroup: 256 threads x 4 rounds x 4 postings
+constexpr size_t SPAD_UNPACKED = 64 * SPU, SPAD_PACKED = 1; // padding behind the last posting (cos_sparse_create)
+
+__device__ __forceinline__ u32 spk_word(u32 id, u32 key) { return key << 24 | (id + 1u); }
+
+// vector id of posting p in either layout
+template <bool PACKED>
+__device__ __forceinline__ u32 sparse_id_at(const u32 *__restrict__ a, u64 p) { return PACKED ? (a[p] & 0xFFFFFFu) - 1u : a[p]; }
+
+// first position in [lo, hi) whose vector id is >= id (the lists are id-sorted)
+template <bool PACKED>
+__device__ __forceinline__ u64 sparse_lower_bound(const u32 *__restrict__ a, u64 lo, u64 hi, u64 id) {
+    while (lo < hi) {
+        const u64 mid = lo + (hi - lo) / 2;
+        if ((u64)sparse_id_at<PACKED>(a, mid) < id) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// the update's pairs as (vector id << 8 | key): InvertedIndexNode::quantize on the device
+__global__ __launch_bounds__(256) void sparse_delta_kernel(const u32 *__restrict__ pair_id, const float *__restrict__ vals, u32 np, float upper, u32 bits,
+                                                           u64 *__restrict__ out) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= np) return;
+    out[i] = (u64)pair_id[i] << 8 | sparse_quantize(vals[i], upper, bits);
+}
+
+// the dimension that owns posting j of the new array: the LAST t in [lo, hi] whose list starts at or before j (an empty list
+// shares its start with the list behind it and is passed over).  Needs old_off[lo] + del_off[lo] <= j.
+__device__ __forceinline__ u32 sparse_dim_of(const u64 *__restrict__ old_off, const u64 *__restrict__ del_off, u32 lo, u32 hi, u64 j) {
+    while (lo < hi) {
+        const u32 mid = lo + (hi - lo + 1) / 2;
+        if (old_off[mid] + del_off[mid] <= j) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// new list of dimension t = old list of t, then the delta's postings of t (every new id is above every old one: still id-sorted).
+// old_off / del_off [T + 1] are indexed by the NEW dimension table (a dimension only the update has: an empty old part).  One
+// workgroup per SMERGE_PIECE postings of the OUTPUT whatever the list lengths; a thread moves 4 consecutive output postings — 4
+// consecutive source words when they come from one list and one source — and stores them as one 16-byte word of ids (or packed
+// words) and, in the unpacked layout, one 4-byte word of keys.
+template <bool PACKED>
+__global__ __launch_bounds__(256) void sparse_merge_kernel(const u32 *__restrict__ old_a /* ids or packed words */, const uint8_t *__restrict__ old_keys,
+                                                           const u64 *__restrict__ delta, const u64 *__restrict__ old_off, const u64 *__restrict__ del_off,
+                                                           u32 T, u64 nnz, u32 *__restrict__ new_a, uint8_t *__restrict__ new_keys) {
+    const u64 p0 = (u64)blockIdx.x * SMERGE_PIECE;
+    if (p0 >= nnz) return;
+    const u64 p1 = p0 + SMERGE_PIECE < nnz ? p0 + SMERGE_PIECE : nnz;
+    const u32 t_lo = sparse_dim_of(old_off, del_off, 0, T - 1, p0); // block-uniform: they bound every thread's search
+    const u32 t_hi = sparse_dim_of(old_off, del_off, t_lo, T - 1, p1 - 1);
+    for (u64 j0 = p0 + (u64)threadIdx.x * 4; j0 < p1; j0 += 1024) {
+        u32 t = sparse_dim_of(old_off, del_off, t_lo, t_hi, j0);
+        u64 ob = old_off[t], db = del_off[t];
+        u64 ol = old_off[t + 1] - ob;
+        const u64 ne = old_off[t + 1] + del_off[t + 1];
+        u64 k = j0 - ob - db;
+        u32 a[4], ky[4];
+        if (j0 + 4 <= ne && k + 4 <= ol) { // one list, the old part: 4 consecutive words of it
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                a[u] = old_a[ob + k + u];
+                ky[u] = PACKED ? 0u : old_keys[ob + k + u];
+            }
+        } else if (j0 + 4 <= ne && k >= ol) { // one list, the delta part
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const u64 v = delta[db + (k - ol) + u];
+                a[u] = PACKED ? spk_word((u32)(v >> 8), (u32)v & 255u) : (u32)(v >> 8);
+                ky[u] = (u32)v & 255u;
+            }
+        } else { // a list boundary or the old/delta seam inside the 4: posting by posting
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const u64 j = j0 + u;
+                a[u] = 0u;
+                ky[u] = 0u;
+                if (j < nnz) {
+                    while (j >= old_off[t + 1] + del_off[t + 1]) t++; // j < nnz = the end of list T - 1: stops at t <= T - 1
+                    ob = old_off[t];
+                    db = del_off[t];
+                    ol = old_off[t + 1] - ob;
+                    k = j - ob - db;
+                    if (k < ol) {
+                        a[u] = old_a[ob + k];
+                        ky[u] = PACKED ? 0u : old_keys[ob + k];
+                    } else {
+                        const u64 v = delta[db + (k - ol)];
+                        a[u] = PACKED ? spk_word((u32)(v >> 8), (u32)v & 255u) : (u32)(v >> 8);
+                        ky[u] = (u32)v & 255u;
+                    }
+                }
+            }
+        }
+        if (j0 + 4 <= nnz) { // (the piece and the arrays are 16-byte aligned)
+            *reinterpret_cast<uint4 *>(new_a + j0) = make_uint4(a[0], a[1], a[2], a[3]);
+            if (!PACKED) *reinterpret_cast<u32 *>(new_keys + j0) = ky[0] | ky[1] << 8 | ky[2] << 16 | ky[3] << 24;
+        } else {
+#pragma unroll
+            for (int u = 0; u < 4; u++)
+                if (j0 + u < nnz) {
+                    new_a[j0 + u] = a[u];
+                    if (!PACKED) new_keys[j0 + u] = (uint8_t)ky[u];
+                }
+        }
+    }
+}
+
+// tile_dir[row][t] = offset (from the list's begin) of the first posting with vector id >= t * STILE, t = 0 .. n_tiles; the last
+// column is the list's length.  One lower-bound search per entry; the same values cos_sparse_create's host pass writes.
+template <bool PACKED>
+__global__ __launch_bounds__(256) void sparse_tile_dir_kernel(const u32 *__restrict__ a, const u64 *__restrict__ row_begin, const u32 *__restrict__ row_len,
+                                                              u32 rows, u32 n_tiles, u32 *__restrict__ tile_dir) {
+    const u64 idx = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    const u64 width = (u64)n_tiles + 1;
+    if (idx >= (u64)rows * width) return;
+    const u32 row = (u32)(idx / width), t = (u32)(idx % width);
+    const u64 lo = row_begin[row];
+    const u32 len = row_len[row];
+    tile_dir[idx] = t == n_tiles ? len : (u32)(sparse_lower_bound<PACKED>(a, lo, lo + len, (u64)t * STILE) - lo);
+}
+
+// one thread per (id, dimension, key) pair of a delete call whose key list holds something: lower bound on the id in the
+// dimension's list, then the postings of that id in turn — the first one with the pair's key that nobody has claimed yet is
+// claimed (the atomic OR on the flag word makes k pairs naming the same (id, dimension, key) claim k different postings)
+template <bool PACKED>
+__global__ __launch_bounds__(256) void sparse_claim_kernel(const u32 *__restrict__ a, const uint8_t *__restrict__ keys, const u32 *__restrict__ pair_id_key /* id, key */,
+                                                           const u64 *__restrict__ pair_begin, const u32 *__restrict__ pair_len, u32 np,
+                                                           u32 *__restrict__ flags, uint8_t *__restrict__ found) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= np) return;
+    const u32 id = pair_id_key[2 * i], key = pair_id_key[2 * i + 1];
+    const u64 lo = pair_begin[i], hi = lo + pair_len[i];
+    uint8_t hit = 0;
+    for (u64 p = sparse_lower_bound<PACKED>(a, lo, hi, id); p < hi && sparse_id_at<PACKED>(a, p) == id; p++) {
+        const u32 k = PACKED ? a[p] >> 24 : (u32)keys[p];
+        if (k != key) continue;
+        const u32 bit = 1u << (p & 31u);
+        if (!(atomicOr(&flags[p >> 5], bit) & bit)) { hit = 1; break; }
+    }
+    found[i] = hit;
+}
+
+__global__ __launch_bounds__(256) void sparse_flag_count_kernel(const u32 *__restrict__ flags, u64 n_words, u32 *__restrict__ counts) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_words) counts[i] = (u32)__popc(flags[i]);
+}
+
+// stream compaction: posting p of the old arrays moves to p - (claimed postings before p); `before` = exclusive sum of the flag
+// words' popcounts.  A thread reads 4 consecutive postings (one 16-byte load) and, when none of them goes and their destination
+// is 16-byte aligned, stores them as one word; otherwise posting by posting (a wave's stores stay contiguous either way).
+template <bool PACKED>
+__global__ __launch_bounds__(256) void sparse_compact_kernel(const u32 *__restrict__ old_a, const uint8_t *__restrict__ old_keys, const u32 *__restrict__ flags,
+                                                             const u32 *__restrict__ before, u64 nnz, u32 *__restrict__ new_a, uint8_t *__restrict__ new_keys) {
+    const u64 p0 = ((u64)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (p0 >= nnz) return;
+    const u32 w = flags[p0 >> 5], sh = (u32)(p0 & 31u);
+    const u32 f = (w >> sh) & 15u;
+    u64 o = p0 - ((u64)before[p0 >> 5] + (u64)__popc(w & ((1u << sh) - 1u)));
+    if (p0 + 4 <= nnz) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(old_a + p0);
+        const u32 kw = PACKED ? 0u : *reinterpret_cast<const u32 *>(old_keys + p0);
+        if (f == 0u && (o & 3u) == 0u) {
+            *reinterpret_cast<uint4 *>(new_a + o) = v;
+            if (!PACKED) *reinterpret_cast<u32 *>(new_keys + o) = kw;
+            return;
+        }
+        const u32 a[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int u = 0; u < 4; u++)
+            if (!((f >> u) & 1u)) {
+                new_a[o] = a[u];
+                if (!PACKED) new_keys[o] = (uint8_t)(kw >> (8 * u));
+                o++;
+            }
+        return;
+    }
+    for (u32 u = 0; p0 + u < nnz; u++)
+        if (!((f >> u) & 1u)) {
+            new_a[o] = old_a[p0 + u];
+            if (!PACKED) new_keys[o] = old_keys[p0 + u];
+            o++;
+        }
+}
+
+int32_t sparse_check_row_offsets(const uint64_t *row_offsets, u32 m) {
+    if (row_offsets[0] != 0) return cos_fail(COS_ERR_INVALID, "row_offsets[0] must be 0");
+    for (u32 i = 0; i < m; i++)
+        if (row_offsets[i + 1] < row_offsets[i]) return cos_fail(COS_ERR_INVALID, "row_offsets must not decrease (vector %u)", i);
+    return COS_OK;
+}
+
+// the posting arrays of a handle in the making: allocated with the padding the search kernels rely on, the padding zeroed
+struct SparseArrays {
+    DevArr<u32> a; // d_ids or d_pk
+    DevArr<uint8_t> keys;
+    hipError_t alloc(bool packed, u64 nnz) {
+        const size_t pad = packed ? SPAD_PACKED : SPAD_UNPACKED;
+        hipError_t e = a.alloc((size_t)nnz + pad);
+        if (e == hipSuccess) e = hipMemsetAsync(a.p + nnz, 0, pad * 4, 0);
+        if (e == hipSuccess && !packed) {
+            e = keys.alloc((size_t)nnz + pad);
+            if (e == hipSuccess) e = hipMemsetAsync(keys.p + nnz, 0, pad, 0);
+        }
+        return e;
+    }
+};
+
+// rows of the tile directory for the lists of `key_off` ([T][Q + 1]) that are longer than SDIR_MIN, searched on the device
+int32_t sparse_build_dir(bool packed, const u32 *d_a, const std::vector<u64> &key_off, u32 T, u32 Q, u32 n_tiles, std::vector<u32> &h_dir, u32 &rows_out,
+                         DevArr<u32> &d_dir) {
+    std::vector<u64> row_begin;
+    std::vector<u32> row_len;
+    h_dir.assign(T, SNO_DIR);
+    for (u32 t = 0; t < T; t++) {
+        const u64 b = key_off[(size_t)t * (Q + 1)], e = key_off[(size_t)t * (Q + 1) + Q];
+        if (e - b <= SDIR_MIN) continue;
+        if (e - b > 0xFFFFFFFFull) return cos_fail(COS_ERR_UNIMPLEMENTED, "a dimension would hold more than 2^32 postings");
+        h_dir[t] = (u32)row_begin.size();
+        row_begin.push_back(b);
+        row_len.push_back((u32)(e - b));
+    }
+    const u32 rows = (u32)row_begin.size();
+    const u64 dir_words = (u64)rows * (n_tiles + 1);
+    rows_out = rows;
+    HIP_TRY(d_dir.alloc(dir_words));
+    if (!rows) return COS_OK;
+    if ((dir_words + 255) / 256 > 0x7FFFFFFFull) return cos_fail(COS_ERR_UNIMPLEMENTED, "tile directory too large for one launch");
+    DevArr<u64> d_row_begin;
+    DevArr<u32> d_row_len;
+    HIP_TRY(d_row_begin.alloc(rows));
+    HIP_TRY(d_row_len.alloc(rows));
+    HIP_TRY(hipMemcpy(d_row_begin, row_begin.data(), (size_t)rows * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_row_len, row_len.data(), (size_t)rows * 4, hipMemcpyHostToDevice));
+    const dim3 grid((u32)((dir_words + 255) / 256));
+    if (packed) hipLaunchKernelGGL(sparse_tile_dir_kernel<true>, grid, dim3(256), 0, 0, d_a, d_row_begin.p, d_row_len.p, rows, n_tiles, d_dir.p);
+    else hipLaunchKernelGGL(sparse_tile_dir_kernel<false>, grid, dim3(256), 0, 0, d_a, d_row_begin.p, d_row_len.p, rows, n_tiles, d_dir.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(0)); // the two row tables are locals
+    return COS_OK;
+}
+
+} // namespace
+
+extern "C" int32_t cos_sparse_insert(cos_sparse *s, uint32_t m, const uint64_t *row_offsets, const uint32_t *raw_dims, const float *raw_vals,
+                                     uint32_t *out_first_id) {
+    if (!s) return cos_fail(COS_ERR_INVALID, "bad argument");
+    if (m == 0) {
+        if (out_first_id) { std::lock_guard<std::mutex> g(s->mu); *out_first_id = s->n; }
+        return COS_OK;
+    }
+    if (!row_offsets) return cos_fail(COS_ERR_INVALID, "bad argument");
+    int32_t rc = sparse_check_row_offsets(row_offsets, m);
+    if (rc) return rc;
+    const u64 nd = row_offsets[m];
+    if (nd && (!raw_dims || !raw_vals)) return cos_fail(COS_ERR_INVALID, "bad argument");
+    if (nd > 0x7FFFFFFFull) return cos_fail(COS_ERR_UNIMPLEMENTED, "more than 2^31 - 1 pairs in one insert");
+    const u32 np = (u32)nd;
+    std::lock_guard<std::mutex> g(s->mu);
+    const u32 Q = 1u << s->bits, n0 = s->n, T0 = s->T;
+    if ((u64)n0 + m > 0xFFFFFFFFull) return cos_fail(COS_ERR_INVALID, "%u + %u vectors do not fit 32-bit ids", n0, m);
+    const u32 n1 = n0 + m;
+    if (s->packed && n1 > SPK_MAX_N)
+        return cos_fail(COS_ERR_UNIMPLEMENTED, "%u vectors pass the packed layout's limit of %u (create the index with sparse_layout = 0)", n1, SPK_MAX_N);
+    // ---- host: O(update + T * Q) ------------------------------------------------------------------------------------------------
+    // the update's dimensions, the merged dimension table, per pair its slot in it
+    std::vector<u32> ud(raw_dims, raw_dims + np);
+    std::sort(ud.begin(), ud.end());
+    ud.erase(std::unique(ud.begin(), ud.end()), ud.end());
+    const u32 U = (u32)ud.size();
+    std::vector<u32> new_dims, old_of, ud_slot(U); // old_of[t] = index in the old table or SNO_DIR
+    new_dims.reserve((size_t)T0 + U);
+    old_of.reserve((size_t)T0 + U);
+    {
+        u32 i = 0, j = 0;
+        while (i < T0 || j < U) {
+            const bool take_old = j == U || (i < T0 && s->h_dims[i] <= ud[j]);
+            const bool take_del = i == T0 || (j < U && ud[j] <= s->h_dims[i]);
+            if (take_del) ud_slot[j] = (u32)new_dims.size();
+            new_dims.push_back(take_old ? s->h_dims[i] : ud[j]);
+            old_of.push_back(take_old ? i : SNO_DIR);
+            if (take_old) i++;
+            if (take_del) j++;
+        }
+    }
+    if (new_dims.size() > 0xFFFFFFFFull) return cos_fail(COS_ERR_UNIMPLEMENTED, "more than 2^32 - 1 dimensions");
+    const u32 T1 = (u32)new_dims.size();
+    std::vector<u32> h_slot(np), h_pid(np), cnt((size_t)T1 * Q, 0u), new_mult(T1, 1u), tmp;
+    for (u32 t = 0; t < T1; t++)
+        if (old_of[t] != SNO_DIR) new_mult[t] = s->h_mult[old_of[t]];
+    for (u32 i = 0; i < m; i++) {
+        const u64 b = row_offsets[i], e = row_offsets[i + 1];
+        bool ascending = true;
+        for (u64 p = b; p < e; p++) {
+            const u32 sl = ud_slot[std::lower_bound(ud.begin(), ud.end(), raw_dims[p]) - ud.begin()];
+            h_slot[p] = sl;
+            h_pid[p] = n0 + i;
+            cnt[(size_t)sl * Q + host_sparse_quantize(raw_vals[p], s->upper, s->bits)]++;
+            if (p > b && raw_dims[p] <= raw_dims[p - 1]) ascending = false;
+        }
+        if (ascending) continue;
+        if (s->have_raw) return cos_fail(COS_ERR_INVALID, "the dimensions of vector %u do not ascend (the raw-value rerank searches them)", i);
+        tmp.assign(h_slot.begin() + b, h_slot.begin() + e); // a dimension named twice: its id is pushed twice (h_mult feeds the COUNTED bound)
+        std::sort(tmp.begin(), tmp.end());
+        for (size_t a = 0, z; a < tmp.size(); a = z) {
+            for (z = a + 1; z < tmp.size() && tmp[z] == tmp[a]; z++) {}
+            new_mult[tmp[a]] = std::max(new_mult[tmp[a]], (u32)(z - a));
+        }
+    }
+    // new per-key offsets; per new dimension where its old part and its delta part start
+    std::vector<u64> new_ko((size_t)T1 * (Q + 1)), old_off((size_t)T1 + 1), del_off((size_t)T1 + 1);
+    const u64 nnz0 = s->h_key_off[(size_t)(T0 - 1) * (Q + 1) + Q];
+    {
+        u64 run = 0, dpos = 0;
+        u32 next_old = 0; // the old dimension at or behind new slot t
+        for (u32 t = 0; t < T1; t++) {
+            const u64 *oko = old_of[t] != SNO_DIR ? s->h_key_off.data() + (size_t)old_of[t] * (Q + 1) : nullptr;
+            old_off[t] = next_old < T0 ? s->h_key_off[(size_t)next_old * (Q + 1)] : nnz0;
+            del_off[t] = dpos;
+            const u64 begin = run;
+            for (u32 k = 0; k < Q; k++) {
+                new_ko[(size_t)t * (Q + 1) + k] = run;
+                run += (oko ? oko[k + 1] - oko[k] : 0ull) + cnt[(size_t)t * Q + k];
+                dpos += cnt[(size_t)t * Q + k];
+            }
+            new_ko[(size_t)t * (Q + 1) + Q] = run;
+            if (run - begin > 0xFFFFFFFFull) return cos_fail(COS_ERR_UNIMPLEMENTED, "dimension %u would hold more than 2^32 postings", new_dims[t]);
+            if (oko) next_old++;
+        }
+        old_off[T1] = nnz0;
+        del_off[T1] = dpos;
+    }
+    const u64 nnz1 = nnz0 + np;
+    const u32 n_tiles1 = (u32)(((u64)n1 + STILE - 1) / STILE);
+    const u64 pieces = (nnz1 + SMERGE_PIECE - 1) / SMERGE_PIECE;
+    if (pieces > 0x7FFFFFFFull) return cos_fail(COS_ERR_UNIMPLEMENTED, "too many postings for one merge launch");
+    std::vector<u64> raw_off_tail;
+    if (s->have_raw) {
+        raw_off_tail.resize(m);
+        for (u32 i = 0; i < m; i++) raw_off_tail[i] = s->raw_nnz + row_offsets[i + 1];
+    }
+    // ---- device: everything into locals; the handle's arrays are only read ------------------------------------------------------
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(0));
+    DevArr<u64> d_delta;
+    if (np) { // the delta in dimension-major order (uploads from host arrays are synchronous copies)
+        DevArr<u32> d_slot, d_slot_sorted, d_pid;
+        DevArr<float> d_vals;
+        DevArr<u64> d_pairs;
+        DevBuf d_tmp;
+        HIP_TRY(d_slot.alloc(np)); HIP_TRY(d_slot_sorted.alloc(np)); HIP_TRY(d_pid.alloc(np)); HIP_TRY(d_vals.alloc(np));
+        HIP_TRY(d_pairs.alloc(np)); HIP_TRY(d_delta.alloc(np));
+        int end_bit = 1;
+        while (end_bit < 32 && (1ull << end_bit) < T1) end_bit++;
+        size_t sort_bytes = 0;
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, d_slot.p, d_slot_sorted.p, d_pairs.p, d_delta.p, (int)np, 0, end_bit, 0));
+        HIP_TRY(d_tmp.alloc(sort_bytes));
+        HIP_TRY(hipMemcpy(d_slot, h_slot.data(), (size_t)np * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_pid, h_pid.data(), (size_t)np * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_vals, raw_vals, (size_t)np * 4, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(sparse_delta_kernel, dim3((np + 255) / 256), dim3(256), 0, 0, d_pid.p, d_vals.p, np, s->upper, s->bits, d_pairs.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, sort_bytes, d_slot.p, d_slot_sorted.p, d_pairs.p, d_delta.p, (int)np, 0, end_bit, 0)); // LSD radix sort: stable
+        HIP_TRY(hipStreamSynchronize(0)); // the sort's inputs and workspace are locals of this block
+    } else
+        HIP_TRY(d_delta.alloc(1));
+    SparseArrays na;
+    DevArr<u64> d_old_off, d_del_off;
+    HIP_TRY(na.alloc(s->packed, nnz1));
+    HIP_TRY(d_old_off.alloc((size_t)T1 + 1)); HIP_TRY(d_del_off.alloc((size_t)T1 + 1));
+    HIP_TRY(hipMemcpy(d_old_off, old_off.data(), ((size_t)T1 + 1) * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_del_off, del_off.data(), ((size_t)T1 + 1) * 8, hipMemcpyHostToDevice));
+    if (pieces) {
+        if (s->packed)
+            hipLaunchKernelGGL(sparse_merge_kernel<true>, dim3((u32)pieces), dim3(256), 0, 0, s->d_pk.p, (const uint8_t *)nullptr, d_delta.p, d_old_off.p, d_del_off.p,
+                               T1, nnz1, na.a.p, (uint8_t *)nullptr);
+        else
+            hipLaunchKernelGGL(sparse_merge_kernel<false>, dim3((u32)pieces), dim3(256), 0, 0, s->d_ids.p, s->d_keys.p, d_delta.p, d_old_off.p, d_del_off.p, T1, nnz1,
+                               na.a.p, na.keys.p);
+        HIP_TRY(hipGetLastError());
+    }
+    std::vector<u32> new_dir;
+    DevArr<u32> d_new_dir;
+    u32 rows1 = 0;
+    rc = sparse_build_dir(s->packed, na.a.p, new_ko, T1, Q, n_tiles1, new_dir, rows1, d_new_dir);
+    if (rc) { (void)hipStreamSynchronize(0); return rc; }
+    DevArr<u64> d_row_off;
+    DevArr<u32> d_raw_dims;
+    DevArr<float> d_raw_vals;
+    if (s->have_raw) { // the raw CSR grows by the same rows: device-side copy of the old arrays + upload of the new rows
+        const u64 r0 = s->raw_nnz;
+        HIP_TRY(d_row_off.alloc((size_t)n1 + 1)); HIP_TRY(d_raw_dims.alloc((size_t)(r0 + np))); HIP_TRY(d_raw_vals.alloc((size_t)(r0 + np)));
+        HIP_TRY(hipMemcpy(d_row_off, s->d_row_off, ((size_t)n0 + 1) * 8, hipMemcpyDeviceToDevice));
+        HIP_TRY(hipMemcpy(d_row_off.p + n0 + 1, raw_off_tail.data(), (size_t)m * 8, hipMemcpyHostToDevice));
+        if (r0) {
+            HIP_TRY(hipMemcpy(d_raw_dims, s->d_raw_dims, (size_t)r0 * 4, hipMemcpyDeviceToDevice));
+            HIP_TRY(hipMemcpy(d_raw_vals, s->d_raw_vals, (size_t)r0 * 4, hipMemcpyDeviceToDevice));
+        }
+        if (np) {
+            HIP_TRY(hipMemcpy(d_raw_dims.p + r0, raw_dims, (size_t)np * 4, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(d_raw_vals.p + r0, raw_vals, (size_t)np * 4, hipMemcpyHostToDevice));
+        }
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    // ---- everything is complete: swap, the old arrays are freed by the moves ----------------------------------------------------
+    if (s->packed) s->d_pk = std::move(na.a);
+    else { s->d_ids = std::move(na.a); s->d_keys = std::move(na.keys); }
+    s->d_tile_dir = std::move(d_new_dir);
+    if (s->have_raw) {
+        s->d_row_off = std::move(d_row_off); s->d_raw_dims = std::move(d_raw_dims); s->d_raw_vals = std::move(d_raw_vals);
+        s->raw_nnz += np;
+    }
+    s->h_dims.swap(new_dims);
+    s->h_key_off.swap(new_ko);
+    s->h_dir.swap(new_dir);
+    s->h_mult.swap(new_mult);
+    s->T = T1;
+    s->n = n1;
+    s->n_tiles = n_tiles1;
+    s->dir_rows = rows1;
+    if (out_first_id) *out_first_id = n0;
+    return COS_OK;
+}
+
+extern "C" int32_t cos_sparse_delete(cos_sparse *s, const uint32_t *ids, const uint64_t *row_offsets, uint32_t m, const uint32_t *raw_dims,
+                                     const float *raw_vals, uint64_t *out_removed) {
+    if (!s) return cos_fail(COS_ERR_INVALID, "bad argument");
+    if (out_removed) *out_removed = 0;
+    if (m == 0) return COS_OK;
+    if (!ids || !row_offsets) return cos_fail(COS_ERR_INVALID, "bad argument");
+    int32_t rc = sparse_check_row_offsets(row_offsets, m);
+    if (rc) return rc;
+    const u64 nd = row_offsets[m];
+    if (nd && (!raw_dims || !raw_vals)) return cos_fail(COS_ERR_INVALID, "bad argument");
+    if (nd > 0x7FFFFFFFull) return cos_fail(COS_ERR_UNIMPLEMENTED, "more than 2^31 - 1 pairs in one delete");
+    std::lock_guard<std::mutex> g(s->mu);
+    const u32 Q = 1u << s->bits, T = s->T;
+    // (id, dimension, value) -> the key list on the host's tables; no node, no list for the key: left alone (inverted_index.rs:205-222)
+    std::vector<u32> pair_ik, pair_len, pair_slot; // (id, key) interleaved; pair_slot = t * Q + key for the host's counts
+    std::vector<u64> pair_begin;
+    for (u32 i = 0; i < m; i++) {
+        if (ids[i] >= s->n) continue;
+        for (u64 p = row_offsets[i]; p < row_offsets[i + 1]; p++) {
+            auto it = std::lower_bound(s->h_dims.begin(), s->h_dims.end(), raw_dims[p]);
+            if (it == s->h_dims.end() || *it != raw_dims[p]) continue;
+            const u32 t = (u32)(it - s->h_dims.begin());
+            const u32 key = host_sparse_quantize(raw_vals[p], s->upper, s->bits);
+            const u64 *ko = s->h_key_off.data() + (size_t)t * (Q + 1);
+            if (ko[key + 1] == ko[key]) continue;
+            pair_ik.push_back(ids[i]);
+            pair_ik.push_back(key);
+            pair_begin.push_back(ko[0]);
+            pair_len.push_back((u32)(ko[Q] - ko[0])); // lists longer than 2^32 - 1 are refused by create and insert
+            pair_slot.push_back(t * Q + key);
+        }
+    }
+    const u32 np = (u32)pair_len.size();
+    if (!np) return COS_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(0));
+    const u64 nnz0 = s->h_key_off[(size_t)(T - 1) * (Q + 1) + Q];
+    const u64 n_words = (nnz0 + 31) / 32;
+    if ((n_words + 255) / 256 > 0x7FFFFFFFull || (nnz0 + 1023) / 1024 > 0x7FFFFFFFull) return cos_fail(COS_ERR_UNIMPLEMENTED, "too many postings for one launch");
+    const u32 *old_a = s->packed ? s->d_pk.p : s->d_ids.p;
+    DevArr<u32> d_ik, d_len, d_flags, d_before;
+    DevArr<u64> d_begin;
+    DevArr<uint8_t> d_found;
+    HIP_TRY(d_ik.alloc((size_t)np * 2)); HIP_TRY(d_len.alloc(np)); HIP_TRY(d_begin.alloc(np)); HIP_TRY(d_found.alloc(np)); HIP_TRY(d_flags.alloc(n_words));
+    HIP_TRY(hipMemcpy(d_ik, pair_ik.data(), (size_t)np * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_len, pair_len.data(), (size_t)np * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_begin, pair_begin.data(), (size_t)np * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemsetAsync(d_flags, 0, n_words * 4, 0));
+    // (the flags are the call's own: nothing of the handle is written before the swap)
+    if (s->packed) hipLaunchKernelGGL(sparse_claim_kernel<true>, dim3((np + 255) / 256), dim3(256), 0, 0, old_a, (const uint8_t *)nullptr, d_ik.p, d_begin.p, d_len.p, np, d_flags.p, d_found.p);
+    else hipLaunchKernelGGL(sparse_claim_kernel<false>, dim3((np + 255) / 256), dim3(256), 0, 0, old_a, s->d_keys.p, d_ik.p, d_begin.p, d_len.p, np, d_flags.p, d_found.p);
+    HIP_TRY(hipGetLastError());
+    std::vector<uint8_t> found(np);
+    HIP_TRY(hipMemcpy(found.data(), d_found, np, hipMemcpyDeviceToHost));
+    // the per-key counts of the pairs the device found: postings_visited stays exact
+    std::vector<u64> dec((size_t)T * Q, 0ull);
+    u64 removed = 0;
+    for (u32 i = 0; i < np; i++)
+        if (found[i]) { dec[pair_slot[i]]++; removed++; }
+    if (!removed) return COS_OK; // nothing found: nothing swapped
+    std::vector<u64> new_ko((size_t)T * (Q + 1));
+    {
+        u64 run = 0;
+        for (u32 t = 0; t < T; t++) {
+            const u64 *ko = s->h_key_off.data() + (size_t)t * (Q + 1);
+            for (u32 k = 0; k < Q; k++) {
+                new_ko[(size_t)t * (Q + 1) + k] = run;
+                const u64 have = ko[k + 1] - ko[k], d = dec[(size_t)t * Q + k];
+                if (d > have) return cos_fail(COS_ERR_HIP, "delete found %llu postings in a key list of %llu", (unsigned long long)d, (unsigned long long)have);
+                run += have - d;
+            }
+            new_ko[(size_t)t * (Q + 1) + Q] = run;
+        }
+    }
+    const u64 nnz1 = nnz0 - removed;
+    // exclusive sum of the flag words' popcounts, compaction into new arrays, their tile directory
+    DevBuf d_tmp;
+    SparseArrays na;
+    HIP_TRY(d_before.alloc(n_words));
+    size_t scan_bytes = 0;
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, d_before.p, d_before.p, (int)n_words, 0));
+    HIP_TRY(d_tmp.alloc(scan_bytes));
+    HIP_TRY(na.alloc(s->packed, nnz1));
+    hipLaunchKernelGGL(sparse_flag_count_kernel, dim3((u32)((n_words + 255) / 256)), dim3(256), 0, 0, d_flags.p, n_words, d_before.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, scan_bytes, d_before.p, d_before.p, (int)n_words, 0));
+    const dim3 grid((u32)((nnz0 + 1023) / 1024));
+    if (s->packed) hipLaunchKernelGGL(sparse_compact_kernel<true>, grid, dim3(256), 0, 0, old_a, (const uint8_t *)nullptr, d_flags.p, d_before.p, nnz0, na.a.p, (uint8_t *)nullptr);
+    else hipLaunchKernelGGL(sparse_compact_kernel<false>, grid, dim3(256), 0, 0, old_a, s->d_keys.p, d_flags.p, d_before.p, nnz0, na.a.p, na.keys.p);
+    HIP_TRY(hipGetLastError());
+    std::vector<u32> new_dir;
+    DevArr<u32> d_new_dir;
+    u32 rows1 = 0;
+    rc = sparse_build_dir(s->packed, na.a.p, new_ko, T, Q, s->n_tiles, new_dir, rows1, d_new_dir);
+    if (rc) { (void)hipStreamSynchronize(0); return rc; }
+    HIP_TRY(hipDeviceSynchronize());
+    if (s->packed) s->d_pk = std::move(na.a);
+    else { s->d_ids = std::move(na.a); s->d_keys = std::move(na.keys); }
+    s->d_tile_dir = std::move(d_new_dir);
+    s->h_key_off.swap(new_ko);
+    s->h_dir.swap(new_dir);
+    s->dir_rows = rows1;
+    s->removed += removed; // (h_mult stays: an upper bound is all the COUNTED proof needs)
+    if (out_removed) *out_removed = removed;
+    return COS_OK;
+}
+
+extern "C" int32_t cos_sparse_stats(cos_sparse *s, cos_sparse_index_stats *out) {
+    if (!s || !out || out->struct_size != sizeof(cos_sparse_index_stats))
+        return cos_fail(COS_ERR_INVALID, "bad argument (struct_size must be sizeof(cos_sparse_index_stats))");
+    std::lock_guard<std::mutex> g(s->mu);
+    const u32 Q = 1u << s->bits;
+    out->n_vectors = s->n;
+    out->n_dims = s->T;
+    out->dir_rows = s->dir_rows;
+    out->dir_tiles = s->n_tiles;
+    out->packed = s->packed ? 1u : 0u;
+    out->have_raw = s->have_raw ? 1u : 0u;
+    out->reserved = 0;
+    out->postings = s->h_key_off[(size_t)(s->T - 1) * (Q + 1) + Q];
+    out->removed = s->removed;
+    out->raw_pairs = s->raw_nnz;
+    u64 bytes = (u64)s->d_ids.cap * 4 + s->d_keys.cap + (u64)s->d_pk.cap * 4 + (u64)std::max<size_t>(s->d_tile_dir.cap, 1) * 4; // postings + directory
+    bytes += (u64)s->d_row_off.cap * 8 + (u64)s->d_raw_dims.cap * 4 + (u64)s->d_raw_vals.cap * 4;                                 // raw vectors
+    for (const DevBuf *w : {&s->w_qd, &s->w_qv, &s->w_qo, &s->w_terms, &s->w_qt_off, &s->w_order, &s->w_part, &s->w_oi, &s->w_os, &s->w_oc}) bytes += w->cap; // search workspace
+    out->device_bytes = bytes;
+    return COS_OK;
+}
+
+extern "C" int32_t cos_sparse_download(cos_sparse *s, uint32_t *n_dims, uint64_t *n_postings, uint32_t *dims, uint64_t *key_offsets, uint32_t *vec_ids) {
+    if (!s || !n_dims || !n_postings) return cos_fail(COS_ERR_INVALID, "bad argument");
+    std::lock_guard<std::mutex> g(s->mu);
+    const u32 Q = 1u << s->bits, T = s->T;
+    const u64 nnz = s->h_key_off[(size_t)(T - 1) * (Q + 1) + Q];
+    const u32 cap_t = *n_dims;
+    const u64 cap_p = *n_postings;
+    *n_dims = T;
+    *n_postings = nnz;
+    if (!dims && !key_offsets && !vec_ids) return COS_OK; // first call: the sizes
+    if (!dims || !key_offsets || !vec_ids) return cos_fail(COS_ERR_INVALID, "bad argument: all three arrays or none");
+    if (cap_t < T || cap_p < nnz)
+        return cos_fail(COS_ERR_INVALID, "arrays for %u dimensions / %llu postings, the index holds %u / %llu", cap_t, (unsigned long long)cap_p, T, (unsigned long long)nnz);
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(0));
+    // a persistence / test path: the id-sorted lists come back whole and are split by key on the host
+    std::vector<u32> a((size_t)std::max<u64>(nnz, 1));
+    std::vector<uint8_t> kb;
+    HIP_TRY(hipMemcpy(a.data(), s->packed ? s->d_pk.p : s->d_ids.p, (size_t)nnz * 4, hipMemcpyDeviceToHost));
+    if (!s->packed) {
+        kb.resize((size_t)std::max<u64>(nnz, 1));
+        HIP_TRY(hipMemcpy(kb.data(), s->d_keys.p, (size_t)nnz, hipMemcpyDeviceToHost));
+    }
+    memcpy(dims, s->h_dims.data(), (size_t)T * 4);
+    memcpy(key_offsets, s->h_key_off.data(), (size_t)T * (Q + 1) * 8);
+    std::vector<u64> cursor(Q);
+    for (u32 t = 0; t < T; t++) {
+        const u64 *ko = s->h_key_off.data() + (size_t)t * (Q + 1);
+        for (u32 k = 0; k < Q; k++) cursor[k] = ko[k];
+        for (u64 p = ko[0]; p < ko[Q]; p++) {
+            const u32 key = s->packed ? a[p] >> 24 : kb[p], id = s->packed ? (a[p] & 0xFFFFFFu) - 1u : a[p];
+            if (key >= Q || cursor[key] >= ko[key + 1]) return cos_fail(COS_ERR_HIP, "the postings of dimension %u do not match the host's key counts", s->h_dims[t]);
+            vec_ids[cursor[key]++] = id;
+        }
+    }
     return COS_OK;
 }

@@ -152,6 +152,7 @@ class InvertedIndex:
         if raw_row_offsets is not None:
             raw = (_c(raw_row_offsets, np.uint64), _c(raw_dims, np.uint32), _c(raw_vals, np.float32))
         self._h = C.c_void_p()
+        self._bits = int(quantization_bits)
         check(_lib.lib().cos_sparse_create(device, quantization_bits, values_upper_bound, _p(d), d.size, _p(ko), _p(vi), n_vectors,
                                            _p(raw[0]) if raw else None, _p(raw[1]) if raw else None, _p(raw[2]) if raw else None,
                                            C.byref(self._h)))
@@ -163,6 +164,7 @@ class InvertedIndex:
         ro, rd, rv = _c(row_offsets, np.uint64), _c(raw_dims, np.uint32), _c(raw_vals, np.float32)
         self = cls.__new__(cls)
         self._h = C.c_void_p()
+        self._bits = int(quantization_bits)
         check(_lib.lib().cos_sparse_create_from_vectors(device, quantization_bits, values_upper_bound, ro.size - 1, _p(ro), _p(rd), _p(rv),
                                                         1 if keep_raw else 0, C.byref(self._h)))
         return self
@@ -208,6 +210,54 @@ def _sparse_packed(self) -> bool:
 
 
 InvertedIndex.packed = property(_sparse_packed)
+
+
+def _sparse_insert(self, row_offsets, raw_dims, raw_vals) -> int:
+    """InvertedIndex::insert for m more vectors (cos_sparse_insert): they take the ids [n, n + m); pairs of vector i are
+    raw_dims / raw_vals [row_offsets[i], row_offsets[i+1]).  The resident postings are merged on the device.  -> the first new id"""
+    ro, rd, rv = _c(row_offsets, np.uint64), _c(raw_dims, np.uint32), _c(raw_vals, np.float32)
+    if ro.size < 1 or rd.size != rv.size or int(ro[-1]) != rd.size:
+        raise ValueError("row_offsets must have m + 1 entries and end at len(raw_dims) == len(raw_vals)")
+    first = C.c_uint32(0)
+    check(_lib.lib().cos_sparse_insert(self._h, ro.size - 1, _p(ro), _p(rd), _p(rv), C.byref(first)))
+    return int(first.value)
+
+
+def _sparse_delete(self, ids, row_offsets, raw_dims, raw_vals) -> int:
+    """InvertedIndex::mark_embedding_as_deleted for m vectors given with the pairs of their raw embeddings (cos_sparse_delete): the
+    first posting of the id in the list of (dimension, quantize(value)) goes.  -> postings actually removed"""
+    vi, ro, rd, rv = _c(ids, np.uint32), _c(row_offsets, np.uint64), _c(raw_dims, np.uint32), _c(raw_vals, np.float32)
+    if ro.size != vi.size + 1 or rd.size != rv.size or int(ro[-1]) != rd.size:
+        raise ValueError("row_offsets must have len(ids) + 1 entries and end at len(raw_dims) == len(raw_vals)")
+    removed = C.c_uint64(0)
+    check(_lib.lib().cos_sparse_delete(self._h, _p(vi), _p(ro), vi.size, _p(rd), _p(rv), C.byref(removed)))
+    return int(removed.value)
+
+
+def _sparse_stats(self) -> dict:
+    """cos_sparse_stats as a dict: n_vectors, n_dims, dir_rows, dir_tiles, packed, have_raw, postings, removed, raw_pairs, device_bytes"""
+    st = _lib.CosSparseIndexStats()
+    st.struct_size = C.sizeof(_lib.CosSparseIndexStats)
+    check(_lib.lib().cos_sparse_stats(self._h, C.byref(st)))
+    return {name: int(getattr(st, name)) for name, _ in st._fields_ if name not in ("struct_size", "reserved")}
+
+
+def _sparse_download(self):
+    """cos_sparse_download -> (dims, key_offsets, vec_ids): the CSR cos_sparse_create takes, ids ascending inside a (dimension, key) list"""
+    L = _lib.lib()
+    nt, nnz = C.c_uint32(0), C.c_uint64(0)
+    check(L.cos_sparse_download(self._h, C.byref(nt), C.byref(nnz), None, None, None))
+    T, n = int(nt.value), int(nnz.value)
+    w = (1 << self._bits) + 1
+    dims, ko, vi = np.zeros(max(T, 1), np.uint32), np.zeros(max(T, 1) * w, np.uint64), np.zeros(max(n, 1), np.uint32)
+    check(L.cos_sparse_download(self._h, C.byref(nt), C.byref(nnz), _p(dims), _p(ko), _p(vi)))
+    return dims[:T], ko[:T * w], vi[:n]
+
+
+InvertedIndex.insert = _sparse_insert
+InvertedIndex.delete = _sparse_delete
+InvertedIndex.stats = _sparse_stats
+InvertedIndex.download = _sparse_download
 
 
 def sparse_build_csr(quantization_bits: int, values_upper_bound: float, row_offsets, raw_dims, raw_vals):

@@ -521,13 +521,73 @@ typedef struct cos_sparse_stats {
     uint32_t blocks;
     uint64_t postings_visited;
     uint64_t posting_bytes;
-} cos_sparse_stats;
-int32_t cos_sparse_last_stats(cos_sparse *s, cos_sparse_stats *out);
+} cos_sparse_search_stats; /* (the plain name cos_sparse_stats is the function further down: in C say `struct cos_sparse_stats`) */
+int32_t cos_sparse_last_stats(cos_sparse *s, cos_sparse_search_stats *out);
 /* Device layout of the handle's postings: 0 = a u32 id + a u8 key per posting (5 B), 1 = one packed u32 per posting
  * (key << 24 | id + 1; what cos_sparse_create builds whenever the collection holds fewer than 2^24 - 16384 vectors: measured in
  * round 5 at 0.453 ms against 0.540 ms per 256-query batch; tuning knob sparse_layout = 0 keeps the 5-byte layout).  Same results
  * either way; a tuning choice, not a reference interface. */
 int32_t cos_sparse_layout(cos_sparse *s, uint32_t *packed);
+/* ---- updates of the resident postings ---------------------------------------------------------
+ * The postings stay on the device: the host passes the update, the library keeps the dimension table and the per-(dimension, key)
+ * counts.  Every call below takes the handle's lock (the one cos_sparse_search_batch holds from the resolution of its terms to its
+ * results) and waits for the device, so a search on another thread sees the index before or after an update, never between.
+ * Strong guarantee: every allocation and kernel of a call completes before the handle's pointers and host tables are swapped; a
+ * call that fails (bad argument, hipErrorOutOfMemory) leaves the handle exactly as it was, and usable.  Host work per call is
+ * O(update + n_dims * 2^bits), never O(postings).
+ *
+ * InvertedIndex::insert (indexes/inverted/mod.rs:72-89; InvertedIndexRoot::insert models/inverted_index.rs:273-289,
+ * InvertedIndexNode::insert :176-201) for m more vectors, which take the ids [n, n + m) (sequential, like cos_index_append);
+ * *out_first_id (optional) = n before the call.  The pairs of vector i are raw_dims / raw_vals [row_offsets[i], row_offsets[i+1]):
+ * every pair, zero values included, pushes the id to the END of the list of (dimension, quantize(value)); a dimension never seen
+ * gets a list; a vector without pairs still takes an id.  row_offsets[0] == 0 and non-decreasing, n + m must fit 32 bits (else
+ * COS_ERR_INVALID), at most 2^31 - 1 pairs per call; any f32 value is accepted (quantized as cos_sparse_build_csr quantizes it);
+ * m == 0 succeeds and does nothing.  On a handle created with raw vectors the raw CSR grows by the same rows, and the dimensions of
+ * a row must strictly ascend (the rerank's lookup is a binary search), else COS_ERR_INVALID.  On the packed layout
+ * (cos_sparse_layout) n + m > 2^24 - 16384 is COS_ERR_UNIMPLEMENTED with the handle unchanged: a packed handle is not converted to
+ * the unpacked layout; create the index with the tuning knob sparse_layout = 0 when it is meant to grow past that.
+ * Peak device memory during the call: old + new posting arrays (4 B per posting packed, 5 B unpacked, each) + the two tile
+ * directories + about 44 B per pair of the update (the sort's workspace included) + 16 B per dimension; with raw vectors also the
+ * old and the new raw CSR (8 B per pair + 8 B per vector each). */
+int32_t cos_sparse_insert(cos_sparse *s, uint32_t m, const uint64_t *row_offsets, const uint32_t *raw_dims, const float *raw_vals,
+                          uint32_t *out_first_id);
+/* InvertedIndex::mark_embedding_as_deleted (indexes/inverted/mod.rs:91-108; InvertedIndexRoot::delete models/inverted_index.rs:291-306,
+ * InvertedIndexNode::delete :205-222, VersionedVec::delete models/versioned_vec.rs:131-154).  The pairs of ids[i] are raw_dims /
+ * raw_vals [row_offsets[i], row_offsets[i+1]): what the host's raw embedding holds (delete_embedding passes raw_emb.sparse_values).
+ * For every pair the FIRST posting of the id in the list of (dimension, quantize(value)) is removed; *out_removed (optional) =
+ * postings actually removed.  Ids in any order; ids >= n, unknown dimensions, a key without a list and a list without the id
+ * (second delete) are not errors: nothing is removed.  k pairs of one call that name the same (id, dimension, key) remove k such
+ * postings.  A pair whose value quantizes to another key than the stored one removes nothing (the reference's rule).  Dimensions
+ * are never dropped from the table, even when every list of one is empty; the raw rows of a deleted vector stay (only candidates
+ * are ever reranked).  The reference marks a tombstone that every reader skips and nothing else of a list enters a score; here the
+ * posting is removed (stream compaction into new arrays), which no search can tell apart — so a call streams the index once:
+ * pass the ids of a transaction together.  A call that finds nothing swaps nothing.
+ * Peak device memory during the call: old + new posting arrays + 1 B per 4 postings (claim flags and their prefix sums) + 21 B
+ * per pair + the two tile directories. */
+int32_t cos_sparse_delete(cos_sparse *s, const uint32_t *ids, const uint64_t *row_offsets, uint32_t m, const uint32_t *raw_dims,
+                          const float *raw_vals, uint64_t *out_removed);
+typedef struct {
+    uint32_t struct_size; /* in: sizeof(cos_sparse_index_stats) */
+    uint32_t n_vectors;   /* ids handed out so far: the next insert starts here */
+    uint32_t n_dims;      /* dimensions in the table (those whose lists are all empty included) */
+    uint32_t dir_rows;    /* lists long enough (> 256 postings) for a row of the tile directory */
+    uint32_t dir_tiles;   /* tiles of 8192 vector ids the directory spans */
+    uint32_t packed;      /* cos_sparse_layout */
+    uint32_t have_raw;    /* raw vectors kept for the raw-value rerank */
+    uint32_t reserved;
+    uint64_t postings;    /* live postings (removed ones are gone) */
+    uint64_t removed;     /* postings removed by cos_sparse_delete since create */
+    uint64_t raw_pairs;   /* pairs of the raw CSR */
+    uint64_t device_bytes; /* postings, tile directory, raw vectors and the search workspace */
+} cos_sparse_index_stats;
+int32_t cos_sparse_stats(cos_sparse *s, cos_sparse_index_stats *out);
+/* The index as the CSR cos_sparse_create takes.  Two calls: with the three arrays NULL, *n_dims / *n_postings receive the sizes; with
+ * the arrays (dims[T], key_offsets[T * (2^bits + 1)], vec_ids[postings]) they carry the capacities in and the sizes out (too small:
+ * COS_ERR_INVALID, nothing written).  Ids ascend inside every (dimension, key) list — push order whenever the index was built by
+ * inserts; a caller-chosen order inside a key list at create is not preserved (no score depends on it).  A persistence / test path:
+ * the posting arrays are copied back and split by key on the host. */
+int32_t cos_sparse_download(cos_sparse *s, uint32_t *n_dims, uint64_t *n_postings, uint32_t *dims, uint64_t *key_offsets,
+                            uint32_t *vec_ids);
 
 /* ---- multi-GPU helper ----------------------------------------------------------------------- */
 /* S-way merge of per-shard top-k lists gathered by the caller's RCCL all-gather
