@@ -113,6 +113,9 @@ __device__ __forceinline__ u32 chunk_dot<ENG_Q3>(uint4 q, uint4 y, u32 acc) { //
 
 // reference-order f32 dot (dot_product_f32_simd, x86_64.rs:418-444) by a PAIR of lanes:
 // even lane owns accumulators 0..3, odd lane 4..7; returns the full dot in both lanes.
+// `row` need only be 4-byte aligned (raw rows have stride dim: any dim % 4 != 0, or a borrowed table off a 16-byte boundary): the
+// 16-byte loads below are global_load_dwordx4, which gfx950 under amdhsa serves at dword alignment (the compiler emits the same
+// instruction for a load declared align 4); q_lds is a 16-byte aligned LDS base.
 __device__ __forceinline__ float f32_pair_dot(const float *__restrict__ row, const float *__restrict__ q_lds, u32 dim, int half) {
     float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
     const u32 chunks = dim >> 3;

@@ -60,19 +60,26 @@ def _py_ann_search(levels, codes, mags, qcode, qmag, p, exact=False):
     return np.array(out_ids, np.uint32), np.array(out_sims, np.float32), np.array(counts, np.uint32)
 
 
-@pytest.mark.parametrize("storage,res", [(O.STORAGE_U8, 0), (O.STORAGE_SUBBYTE, 2), (O.STORAGE_F32, 0)])
-@pytest.mark.parametrize("M,M0,ef,shortlist,exact", [(8, 16, 12, 64, False), (4, 8, 40, 6, False), (16, 32, 7, 20, False),
-                                                     (8, 16, 25, 64, True), (2, 4, 100, 64, False)])
-def test_python_walk_equals_c_oracle(storage, res, M, M0, ef, shortlist, exact):
+WALK_STORAGES = [(O.STORAGE_U8, 0), (O.STORAGE_SUBBYTE, 2), (O.STORAGE_F32, 0)]
+WALK_SHAPES = [(8, 16, 12, 64, False), (4, 8, 40, 6, False), (16, 32, 7, 20, False), (8, 16, 25, 64, True), (2, 4, 100, 64, False)]
+# dim 24 is the aligned case and keeps its test ids; 7, 13 and 33 leave a partial last byte in every SubByte plane, a u8 row that
+# is no whole 16-byte chunk and an f32 dot that ends in the scalar tail (dim % 8 = 7, 5, 1)
+WALK_DIMS = [24, 7, 13, 33]
+WALK_CASES = [pytest.param(st, res, *shape, dim, id="-".join(map(str, shape + (st, res))) + ("" if dim == 24 else f"-dim{dim}"))
+              for dim in WALK_DIMS for st, res in WALK_STORAGES for shape in WALK_SHAPES]
+
+
+@pytest.mark.parametrize("storage,res,M,M0,ef,shortlist,exact,dim", WALK_CASES)
+def test_python_walk_equals_c_oracle(storage, res, M, M0, ef, shortlist, exact, dim):
     rng = np.random.default_rng(M * 131 + ef)
-    X = H.clustered_corpus(500, 24, n_centers=7, seed=M0 + ef)
-    p = O.HNSWParams(dim=24, storage=storage, resolution=res, num_layers=3, neighbors_count=M, level0_neighbors_count=M0,
+    X = H.clustered_corpus(500, dim, n_centers=7, seed=M0 + ef)
+    p = O.HNSWParams(dim=dim, storage=storage, resolution=res, num_layers=3, neighbors_count=M, level0_neighbors_count=M0,
                      ef_construction=24, ef_search=ef, shortlist_size=shortlist,
                      visited_mode=O.VISITED_EXACT if exact else O.VISITED_REF, seed=5)
     ix = O.OracleIndex(p).set_vectors(X).build()
     levels = ix.export_graph()
     codes, mags = O.quantize_batch(np.vstack([X, ix.root_raw()[None, :]]), storage, res, -1.0, 1.0)
-    Q = np.concatenate([H.queries_from(X, 6, seed=ef), rng.uniform(-1, 1, (2, 24)).astype(np.float32)])
+    Q = np.concatenate([H.queries_from(X, 6, seed=ef), rng.uniform(-1, 1, (2, dim)).astype(np.float32)])
     for q in Q:
         qcode, qmag = O.quantize(q, storage, res, -1.0, 1.0)
         pi, ps, pc = _py_ann_search(levels, codes, mags, qcode, qmag, p, exact)

@@ -23,15 +23,21 @@ def _free_port():
     return p
 
 
+def _total_key(x):
+    """f32::total_cmp as an integer key: -NaN < -inf < ... < -0.0 < +0.0 < ... < +inf < +NaN"""
+    b = int(np.float32(x).view(np.int32))
+    return b ^ (0x7FFFFFFF if b < 0 else 0)
+
+
 def _merge_numpy(g_ids, g_sc, g_cnt, k):
-    """checker for the merge rule: total_cmp desc, larger id first."""
+    """checker for the merge rule: total_cmp desc (so +0.0 ranks before -0.0), larger id first."""
     S, B, _ = g_ids.shape
     out_ids = np.full((B, k), 0xFFFFFFFF, np.uint32)
     out_sc = np.zeros((B, k), np.float32)
     out_cnt = np.zeros(B, np.uint32)
     for b in range(B):
-        ent = [(float(g_sc[s, b, j]), int(g_ids[s, b, j])) for s in range(S) for j in range(int(g_cnt[s, b]))]
-        ent.sort(key=lambda t: (t[0], t[1]), reverse=True)
+        ent = [(g_sc[s, b, j], int(g_ids[s, b, j])) for s in range(S) for j in range(int(g_cnt[s, b]))]
+        ent.sort(key=lambda t: (_total_key(t[0]), t[1]), reverse=True)
         ent = ent[:k]
         out_cnt[b] = len(ent)
         for j, (sc, i) in enumerate(ent):
@@ -120,35 +126,89 @@ def test_shard_range_partition():
         assert r[0][0] == 0 and r[-1][1] == n and all(r[i][1] == r[i + 1][0] for i in range(w - 1))
 
 
+def test_merge_checker_orders_by_total_cmp():
+    """the checker itself: -0.0 sorts below +0.0 whatever the ids, negatives below both, equal bits by the larger id"""
+    sc = np.array([[[0.5, 0.0, -0.0, -0.25]], [[0.0, -0.0, -0.0, -0.5]]], np.float32)
+    ids = np.array([[[1, 2, 90, 4]], [[5, 6, 7, 8]]], np.uint32)
+    m_ids, m_sc, m_cnt = _merge_numpy(ids, sc, np.full((2, 1), 4, np.uint32), 8)
+    assert m_ids[0].tolist() == [1, 5, 2, 90, 7, 6, 4, 8] and m_cnt[0] == 8
+    assert m_sc[0].view(np.uint32).tolist() == np.array([0.5, 0.0, 0.0, -0.0, -0.0, -0.0, -0.25, -0.5], np.float32).view(np.uint32).tolist()
+
+
+# S, B, k, counts ("random" | "zero" | "full"), scores ("ties": a few positive values | "signed": negatives, -0.0 and +0.0 among them).
+# S*k picks the instantiation of merge_topk_kernel<R>: <= 64 R=1, <= 128 R=2, <= 256 R=4, <= 512 R=8, <= 1024 R=16.
+MERGE_CASES = [(2, 33, 10, "random", "ties"), (8, 256, 10, "random", "ties"), (4, 7, 50, "random", "ties"), (8, 5, 100, "random", "ties"),
+               (8, 9, 40, "random", "ties"),          # 320: R = 8
+               (8, 9, 40, "full", "signed"),          # 320 live entries
+               (8, 5, 8, "full", "signed"),           # 64: last size of R = 1
+               (2, 3, 64, "full", "ties"),            # 128: last size of R = 2
+               (8, 4, 128, "full", "signed"),         # 1024: last size of R = 16
+               (4, 3, 64, "random", "signed"),        # 256: last size of R = 4
+               (8, 3, 64, "full", "signed"),          # 512: last size of R = 8
+               (1, 6, 10, "random", "signed"), (1, 2, 300, "full", "ties"),   # S = 1
+               (8, 11, 1, "random", "signed"), (1, 4, 1, "full", "ties"),     # k = 1
+               (4, 5, 20, "zero", "ties"),            # every count 0
+               (3, 70, 33, "random", "signed")]
+PAT_I, PAT_S = 0x5A5A5A5A, -123.25                    # what the outputs hold before the call
+
+
+def _merge_inputs(rng, S, B, k, counts, scores):
+    if scores == "ties":
+        pool = np.linspace(0.1, 0.9, 23).astype(np.float32)
+    else:
+        pool = np.concatenate([np.linspace(-0.9, 0.9, 19), [0.0, -0.0, 0.0, -0.0, -1e-30, 1e-30]]).astype(np.float32)
+    sc = rng.choice(pool, (S, B, k))
+    keys = np.vectorize(_total_key)(sc)                               # a shard emits its list in total_cmp order: +0.0 ahead of -0.0
+    sc = np.take_along_axis(sc, np.argsort(-keys, axis=2, kind="stable"), axis=2)
+    ids = rng.permutation(S * B * k).astype(np.uint32).reshape(S, B, k)
+    cnt = {"random": rng.integers(0, k + 1, (S, B)), "zero": np.zeros((S, B)), "full": np.full((S, B), k)}[counts].astype(np.uint32)
+    return ids, sc, cnt
+
+
 @pytest.mark.gpu
 def test_merge_kernel_matches_rule():
     import cosdata_amd  # noqa: F401
+    from cosdata_amd import _lib
     from cosdata_amd.sharding import merge_topk_device, merge_topk_packed_device
     rng = np.random.default_rng(5)
-    for S, B, k in [(2, 33, 10), (8, 256, 10), (4, 7, 50), (8, 5, 100)]:
-        sc = rng.choice(np.linspace(0.1, 0.9, 23).astype(np.float32), (S, B, k))  # many ties
-        sc = -np.sort(-sc, axis=2)
-        ids = rng.permutation(S * B * k).astype(np.uint32).reshape(S, B, k)
-        cnt = rng.integers(0, k + 1, (S, B)).astype(np.uint32)
+    dev = torch.device("cuda:0")
+    t = lambda a, dt: torch.from_numpy(a.view(dt) if a.dtype != np.float32 else a).to(dev)
+    outs = lambda B, k: (torch.full((B, k), PAT_I, dtype=torch.int32, device=dev), torch.full((B, k), PAT_S, dtype=torch.float32, device=dev),
+                         torch.full((B,), PAT_I, dtype=torch.int32, device=dev))
+    for S, B, k, counts, scores in MERGE_CASES:
+        ids, sc, cnt = _merge_inputs(rng, S, B, k, counts, scores)
         exp = _merge_numpy(ids, sc, cnt, k)
-        dev = torch.device("cuda:0")
-        t = lambda a, dt: torch.from_numpy(a.view(dt) if a.dtype != np.float32 else a).to(dev)
-        o_i = torch.zeros(B, k, dtype=torch.int32, device=dev); o_s = torch.zeros(B, k, dtype=torch.float32, device=dev)
-        o_c = torch.zeros(B, dtype=torch.int32, device=dev)
+        o_i, o_s, o_c = outs(B, k)
         merge_topk_device(t(ids, np.int32), t(sc, np.float32), t(cnt, np.int32), o_i, o_s, o_c, 0, 0)
         torch.cuda.synchronize()
         # packed per-shard records [ids | scores | counts] through cos_merge_topk_packed_device
         packed = np.concatenate([ids.reshape(S, -1).view(np.int32), sc.reshape(S, -1).view(np.int32), cnt.view(np.int32)], axis=1)
-        p_i = torch.zeros_like(o_i); p_s = torch.zeros_like(o_s); p_c = torch.zeros_like(o_c)
+        p_i, p_s, p_c = outs(B, k)
         merge_topk_packed_device(torch.from_numpy(np.ascontiguousarray(packed)).to(dev), B, k, p_i, p_s, p_c, 0, 0)
         torch.cuda.synchronize()
         for (r_i, r_s, r_c) in [(o_i, o_s, o_c), (p_i, p_s, p_c)]:
             gc = r_c.cpu().numpy().view(np.uint32)
-            assert np.array_equal(gc, exp[2])
+            gi, gs = r_i.cpu().numpy().view(np.uint32), r_s.cpu().numpy()
+            assert np.array_equal(gc, exp[2]), (S, B, k)
+            assert np.array_equal(gc, np.minimum(cnt.sum(axis=0), k))
             for b in range(B):
                 c = int(gc[b])
-                assert np.array_equal(r_i.cpu().numpy().view(np.uint32)[b, :c], exp[0][b, :c])
-                assert np.array_equal(r_s.cpu().numpy()[b, :c], exp[1][b, :c])
+                assert np.array_equal(gi[b, :c], exp[0][b, :c]), (S, B, k, b)
+                assert np.array_equal(gs[b, :c].view(np.uint32), exp[1][b, :c].view(np.uint32)), (S, B, k, b)   # bits: -0.0 is not +0.0
+                assert (gi[b, c:] == PAT_I).all() and (gs[b, c:] == np.float32(PAT_S)).all(), (S, B, k, b, "slots past count were written")
+    # S*k = 1025: one past the widest instantiation — refused, nothing written
+    for S, B, k in [(5, 3, 205), (1, 2, 1025)]:
+        ids, sc, cnt = _merge_inputs(rng, S, B, k, "full", "ties")
+        packed = np.concatenate([ids.reshape(S, -1).view(np.int32), sc.reshape(S, -1).view(np.int32), cnt.view(np.int32)], axis=1)
+        o_i, o_s, o_c = outs(B, k)
+        with pytest.raises(_lib.CosdataError) as ei:
+            merge_topk_device(t(ids, np.int32), t(sc, np.float32), t(cnt, np.int32), o_i, o_s, o_c, 0, 0)
+        assert ei.value.status == 4                      # COS_ERR_UNIMPLEMENTED
+        with pytest.raises(_lib.CosdataError) as ei:
+            merge_topk_packed_device(torch.from_numpy(np.ascontiguousarray(packed)).to(dev), B, k, o_i, o_s, o_c, 0, 0)
+        assert ei.value.status == 4
+        torch.cuda.synchronize()
+        assert (o_i == PAT_I).all() and (o_s == PAT_S).all() and (o_c == PAT_I).all()
 
 
 def _recall_worker(rank, world, port, tmp):
