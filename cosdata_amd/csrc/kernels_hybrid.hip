@@ -23,16 +23,17 @@
 #include <vector>
 
 #include "engine_internal.h"
+#include "postings_update.h"
 
 using namespace cosdev;
 
 namespace {
 
 constexpr u32 BUCKETS = 512;  // sparse_ann_query.rs:154
-constexpr u32 TILE = 8192;    // doc ids per LDS accumulator tile (32 KB of f32)
+constexpr u32 TILE = POSTINGS_TILE; // doc ids per LDS accumulator tile (32 KB of f32)
 constexpr u32 MAX_QTERMS = 64;
 constexpr u32 DIR_MIN = 256;  // posting lists longer than this get a tile directory; shorter ones are scanned whole per tile
-constexpr u32 NO_DIR = 0xFFFFFFFFu;
+constexpr u32 NO_DIR = POSTINGS_NONE;
 constexpr int PU = 8;       // postings per thread per chunk
 
 struct QueryTerms { // per query, terms ascending by hash, only those that have a posting list
@@ -42,14 +43,6 @@ struct QueryTerms { // per query, terms ascending by hash, only those that have 
     u32 dir[MAX_QTERMS]; // row of the term in the tile directory, NO_DIR for short lists
     u32 n;
 };
-
-__device__ __forceinline__ u64 lower_bound_doc(const u32 *__restrict__ docs, u64 lo, u64 hi, u32 key) {
-    while (lo < hi) {
-        u64 mid = lo + (hi - lo) / 2;
-        if (docs[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
 
 // UNTOUCHED marks a document no term has reached yet: a NaN bit pattern that tf * idf and the sums of such products cannot take
 // (cos_bm25_create rejects non-finite stored term frequencies; idf is finite), so the accumulator itself says whether the first
@@ -629,23 +622,11 @@ extern "C" int32_t cos_hybrid_search_batch(cos_index *ix, cos_bm25 *b, const flo
 // The postings never go back through the host.  The host owns the term table (term_hashes, offsets: O(n_terms)) and sees the
 // update itself (O(size of the update)); the device turns the document-major update into term-major order (stable radix sort by
 // term hash: ids arrive ascending, so every term's new postings come out ascending), streams old list + new postings of every term
-// into NEW arrays (bm25_merge_kernel: 8 B read + 8 B written per posting of the new array), and searches the tile directory of the
-// new arrays (bm25_tile_dir_kernel).  Only then are the handle's pointers swapped and the old arrays freed: a call that fails
-// before that point leaves the handle exactly as it was.
+// into NEW arrays (postings_merge_kernel<Bm25Merge>, postings_update.h: 8 B read + 8 B written per posting of the new array), and
+// searches the tile directory of the new arrays (postings_tile_dir_kernel<Bm25Ids>).  Only then are the handle's pointers swapped
+// and the old arrays freed: a call that fails before that point leaves the handle exactly as it was.
 // ------------------------------------------------------------------------------------------------
 namespace {
-
-constexpr u32 MERGE_PIECE = 4096; // postings of the OUTPUT per workgroup: 256 threads x 4 rounds x 4 postings (16 B of ids + 16 B of tfs)
-
-// the term that owns posting j of the new array: the LAST t in [lo, hi] whose list starts at or before j (new_off(t) = old_off[t] +
-// del_off[t]; an empty list shares its start with the list behind it and is passed over).  Needs new_off(lo) <= j.
-__device__ __forceinline__ u32 merge_term_of(const u64 *__restrict__ old_off, const u64 *__restrict__ del_off, u32 lo, u32 hi, u64 j) {
-    while (lo < hi) {
-        const u32 mid = lo + (hi - lo + 1) / 2;
-        if (old_off[mid] + del_off[mid] <= j) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
 
 // delta in term-major order: perm = the stable sort's permutation of the update's postings
 __global__ __launch_bounds__(256) void bm25_delta_gather_kernel(const u32 *__restrict__ perm, const u32 *__restrict__ pdocs, const float *__restrict__ ptfs,
@@ -657,76 +638,28 @@ __global__ __launch_bounds__(256) void bm25_delta_gather_kernel(const u32 *__res
     out_tfs[i] = ptfs[s];
 }
 
-// new list of term t = old list of t, then the delta's postings of t (ids above every id the index ever held: still ascending).
-// old_off / del_off [T + 1]: where term t's old postings / delta postings start, both indexed by the NEW term table (a term that
-// exists only in the update has an empty old part, an untouched term an empty delta part).  One workgroup per MERGE_PIECE postings
-// of the OUTPUT, whatever the list lengths: a 400 000-posting list is 98 workgroups, 4096 one-posting lists are one.  A thread
-// moves 4 consecutive output postings; when they come from one list and one source they are 4 consecutive source words
-// (global_load_dwordx4, the source only 4-byte aligned) and always one 16-byte store per array (the piece and the arrays are
-// 16-byte aligned).
-__global__ __launch_bounds__(256) void bm25_merge_kernel(const u32 *__restrict__ old_docs, const float *__restrict__ old_tfs,
-                                                         const u32 *__restrict__ del_docs, const float *__restrict__ del_tfs,
-                                                         const u64 *__restrict__ old_off, const u64 *__restrict__ del_off, u32 T, u64 nnz,
-                                                         u32 *__restrict__ new_docs, float *__restrict__ new_tfs) {
-    const u64 p0 = (u64)blockIdx.x * MERGE_PIECE;
-    if (p0 >= nnz) return;
-    const u64 p1 = p0 + MERGE_PIECE < nnz ? p0 + MERGE_PIECE : nnz;
-    const u32 t_lo = merge_term_of(old_off, del_off, 0, T - 1, p0); // block-uniform: the piece's first and last term bound every thread's search
-    const u32 t_hi = merge_term_of(old_off, del_off, t_lo, T - 1, p1 - 1);
-    for (u64 j0 = p0 + (u64)threadIdx.x * 4; j0 < p1; j0 += 1024) {
-        u32 t = merge_term_of(old_off, del_off, t_lo, t_hi, j0);
-        u64 ob = old_off[t], db = del_off[t];
-        u64 ol = old_off[t + 1] - ob;
-        const u64 ne = old_off[t + 1] + del_off[t + 1];
-        u64 k = j0 - ob - db;
-        u32 d[4];
-        float f[4];
-        if (j0 + 4 <= ne && (k + 4 <= ol || k >= ol)) { // one list, one source: 4 consecutive words of it
-            const bool from_old = k + 4 <= ol;
-            const u32 *sd = from_old ? old_docs + ob + k : del_docs + db + (k - ol);
-            const float *sf = from_old ? old_tfs + ob + k : del_tfs + db + (k - ol);
-#pragma unroll
-            for (int u = 0; u < 4; u++) { d[u] = sd[u]; f[u] = sf[u]; }
-        } else { // a list boundary or the old/delta seam inside the 4: posting by posting
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const u64 j = j0 + u;
-                d[u] = 0;
-                f[u] = 0.0f;
-                if (j < nnz) {
-                    while (j >= old_off[t + 1] + del_off[t + 1]) t++; // j < nnz = new_off(T): stops at t <= T - 1
-                    ob = old_off[t];
-                    db = del_off[t];
-                    ol = old_off[t + 1] - ob;
-                    k = j - ob - db;
-                    if (k < ol) { d[u] = old_docs[ob + k]; f[u] = old_tfs[ob + k]; }
-                    else { d[u] = del_docs[db + (k - ol)]; f[u] = del_tfs[db + (k - ol)]; }
-                }
-            }
-        }
-        if (j0 + 4 <= nnz) {
-            *reinterpret_cast<uint4 *>(new_docs + j0) = make_uint4(d[0], d[1], d[2], d[3]);
-            *reinterpret_cast<float4 *>(new_tfs + j0) = make_float4(f[0], f[1], f[2], f[3]);
-        } else {
-#pragma unroll
-            for (int u = 0; u < 4; u++)
-                if (j0 + u < nnz) { new_docs[j0 + u] = d[u]; new_tfs[j0 + u] = f[u]; }
-        }
+// the posting format of postings_update.h: a document id and a stored term frequency, in two arrays; the delta has the same shape
+struct Bm25Ids {
+    const u32 *__restrict__ docs;
+    __device__ __forceinline__ u32 operator()(u64 p) const { return docs[p]; }
+};
+struct Bm25Merge {
+    const u32 *__restrict__ old_docs;
+    const float *__restrict__ old_tfs;
+    const u32 *__restrict__ del_docs;
+    const float *__restrict__ del_tfs;
+    u32 *__restrict__ new_docs;
+    float *__restrict__ new_tfs;
+    struct P { u32 d; float f; };
+    __device__ __forceinline__ P zero() const { return {0u, 0.0f}; }
+    __device__ __forceinline__ P from_old(u64 p) const { return {old_docs[p], old_tfs[p]}; }
+    __device__ __forceinline__ P from_delta(u64 p) const { return {del_docs[p], del_tfs[p]}; }
+    __device__ __forceinline__ void store4(u64 j, const P (&v)[4]) const {
+        *reinterpret_cast<uint4 *>(new_docs + j) = make_uint4(v[0].d, v[1].d, v[2].d, v[3].d);
+        *reinterpret_cast<float4 *>(new_tfs + j) = make_float4(v[0].f, v[1].f, v[2].f, v[3].f);
     }
-}
-
-// tile_dir[row][t] = offset (from the list's begin) of the first posting with doc id >= t * TILE, t = 0 .. n_tiles; the last column
-// is the list's length.  One lower-bound search per entry; the same values cos_bm25_create's host pass writes.
-__global__ __launch_bounds__(256) void bm25_tile_dir_kernel(const u32 *__restrict__ docs, const u64 *__restrict__ row_begin, const u32 *__restrict__ row_len,
-                                                            u32 rows, u32 n_tiles, u32 *__restrict__ tile_dir) {
-    const u64 idx = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    const u64 width = (u64)n_tiles + 1;
-    if (idx >= (u64)rows * width) return;
-    const u32 row = (u32)(idx / width), t = (u32)(idx % width);
-    const u64 lo = row_begin[row];
-    const u32 len = row_len[row];
-    tile_dir[idx] = t == n_tiles ? len : (u32)(lower_bound_doc(docs, lo, lo + len, t * TILE) - lo); // t < n_tiles: t * TILE <= the largest id
-}
+    __device__ __forceinline__ void store1(u64 j, const P &v) const { new_docs[j] = v.d; new_tfs[j] = v.f; }
+};
 
 // one thread per (document, term) pair of a delete call whose term has a list: lower-bound search for the id, mark the posting if it
 // is there and not yet marked (the exchange makes two pairs naming the same posting count it once), count what was marked
@@ -737,7 +670,7 @@ __global__ __launch_bounds__(256) void bm25_tombstone_kernel(const u32 *__restri
     if (i >= n_pairs) return;
     const u64 lo = pair_begin[i], hi = lo + pair_len[i];
     const u32 doc = pair_doc[i];
-    const u64 pos = lower_bound_doc(docs, lo, hi, doc);
+    const u64 pos = postings_lower_bound(Bm25Ids{docs}, lo, hi, doc);
     if (pos < hi && docs[pos] == doc) {
         const u32 old = atomicExch(reinterpret_cast<unsigned int *>(tfs + pos), TOMBSTONE_TF);
         if (old != TOMBSTONE_TF) atomicAdd(marked, 1u);
@@ -753,13 +686,6 @@ int32_t bm25_quiesce(cos_bm25 *b) {
     return COS_OK;
 }
 
-int32_t bm25_check_doc_offsets(const uint64_t *doc_offsets, u32 m) {
-    if (doc_offsets[0] != 0) return cos_fail(COS_ERR_INVALID, "doc_offsets[0] must be 0");
-    for (u32 i = 0; i < m; i++)
-        if (doc_offsets[i + 1] < doc_offsets[i]) return cos_fail(COS_ERR_INVALID, "doc_offsets must not decrease (document %u)", i);
-    return COS_OK;
-}
-
 } // namespace
 
 extern "C" int32_t cos_bm25_insert(cos_bm25 *b, const uint32_t *doc_ids, const uint64_t *doc_offsets, uint32_t m, const uint32_t *term_hashes,
@@ -767,7 +693,7 @@ extern "C" int32_t cos_bm25_insert(cos_bm25 *b, const uint32_t *doc_ids, const u
     if (!b) return cos_fail(COS_ERR_INVALID, "bad argument");
     if (m == 0) return COS_OK;
     if (!doc_ids || !doc_offsets) return cos_fail(COS_ERR_INVALID, "bad argument");
-    int32_t rc = bm25_check_doc_offsets(doc_offsets, m);
+    int32_t rc = postings_check_offsets(doc_offsets, m, "doc_offsets", "document");
     if (rc) return rc;
     const u64 nd = doc_offsets[m];
     if (nd && (!term_hashes || !tfs)) return cos_fail(COS_ERR_INVALID, "bad argument");
@@ -842,75 +768,54 @@ extern "C" int32_t cos_bm25_insert(cos_bm25 *b, const uint32_t *doc_ids, const u
 
     // 2. merge the two sorted term tables on the host: new hashes, and per new term where its old part and its delta part start
     const u32 T0 = b->n_terms;
-    std::vector<u32> new_hashes;
-    std::vector<u64> old_off, del_off, new_off;
-    new_hashes.reserve((size_t)T0 + U);
-    old_off.reserve((size_t)T0 + U + 1); del_off.reserve((size_t)T0 + U + 1); new_off.reserve((size_t)T0 + U + 1);
+    MergedKeys mk = postings_merge_keys(b->term_hashes, uniq);
+    if (mk.keys.size() > 0xFFFFFFFFull) return cos_fail(COS_ERR_UNIMPLEMENTED, "more than 2^32 - 1 terms");
+    const u32 T = (u32)mk.keys.size();
+    std::vector<u64> old_off((size_t)T + 1), del_off((size_t)T + 1), new_off((size_t)T + 1);
     {
-        u32 i = 0, j = 0;
+        u32 i = 0; // the old term at or behind new slot t; a term that only the update has: an empty old part where it would stand
         u64 dpos = 0;
-        while (i < T0 || j < U) {
-            const bool take_old = j == U || (i < T0 && b->term_hashes[i] <= uniq[j]);
-            const bool take_del = i == T0 || (j < U && uniq[j] <= b->term_hashes[i]);
-            new_hashes.push_back(take_old ? b->term_hashes[i] : uniq[j]);
-            old_off.push_back(b->offsets[i]); // i <= T0; a term that only the update has: an empty old part where it would stand
-            del_off.push_back(dpos);
-            new_off.push_back(old_off.back() + dpos);
-            if (take_old) i++;
-            if (take_del) dpos += counts[j++];
+        for (u32 t = 0; t < T; t++) {
+            old_off[t] = b->offsets[i];
+            del_off[t] = dpos;
+            new_off[t] = old_off[t] + dpos;
+            if (mk.old_of[t] != POSTINGS_NONE) i++;
+            if (mk.del_of[t] != POSTINGS_NONE) dpos += counts[mk.del_of[t]];
         }
-        old_off.push_back(b->offsets[T0]);
-        del_off.push_back(dpos);
-        new_off.push_back(old_off.back() + dpos);
+        old_off[T] = b->offsets[T0];
+        del_off[T] = dpos;
+        new_off[T] = old_off[T] + dpos;
         if (dpos != n) return cos_fail(COS_ERR_HIP, "the update's run lengths add up to %llu, not %u", (unsigned long long)dpos, n);
     }
-    if (new_hashes.size() > 0xFFFFFFFFull) return cos_fail(COS_ERR_UNIMPLEMENTED, "more than 2^32 - 1 terms");
-    const u32 T = (u32)new_hashes.size();
     const u64 nnz = new_off[T];
 
-    // 3. the new directory's shape: a list crossing DIR_MIN gets a row, a larger largest id widens every row
-    const u32 new_max_doc = std::max(b->max_doc, delta_max_doc);
-    const u32 n_tiles = (u32)(((u64)new_max_doc + 1 + TILE - 1) / TILE);
-    std::vector<u32> new_dir_row(T, NO_DIR), row_len;
-    std::vector<u64> row_begin;
-    for (u32 t = 0; t < T; t++) {
-        const u64 len = new_off[t + 1] - new_off[t];
-        if (len <= DIR_MIN) continue;
-        if (len > 0xFFFFFFFFull) return cos_fail(COS_ERR_UNIMPLEMENTED, "posting list of term %u too long", new_hashes[t]);
-        new_dir_row[t] = (u32)row_begin.size();
-        row_begin.push_back(new_off[t]);
-        row_len.push_back((u32)len);
-    }
-    const u32 rows = (u32)row_begin.size();
-    const u64 dir_words = (u64)rows * (n_tiles + 1);
-
-    // 4. new arrays, merge, directory — all on the device; the old arrays are only read
-    DevArr<u32> d_new_docs, d_new_dir, d_row_len;
+    // 3. new arrays and merge on the device; the old arrays are only read
+    DevArr<u32> d_new_docs, d_new_dir;
     DevArr<float> d_new_tfs;
-    DevArr<u64> d_old_off, d_del_off, d_row_begin;
-    HIP_TRY(d_new_docs.alloc(nnz)); HIP_TRY(d_new_tfs.alloc(nnz)); HIP_TRY(d_new_dir.alloc(dir_words));
+    DevArr<u64> d_old_off, d_del_off;
+    HIP_TRY(d_new_docs.alloc(nnz)); HIP_TRY(d_new_tfs.alloc(nnz));
     HIP_TRY(d_old_off.alloc((size_t)T + 1)); HIP_TRY(d_del_off.alloc((size_t)T + 1));
-    HIP_TRY(d_row_begin.alloc(rows)); HIP_TRY(d_row_len.alloc(rows));
     HIP_TRY(hipMemcpy(d_old_off, old_off.data(), ((size_t)T + 1) * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_del_off, del_off.data(), ((size_t)T + 1) * 8, hipMemcpyHostToDevice));
     const u64 pieces = (nnz + MERGE_PIECE - 1) / MERGE_PIECE;
     if (pieces > 0x7FFFFFFFull) return cos_fail(COS_ERR_UNIMPLEMENTED, "too many postings for one merge launch");
-    hipLaunchKernelGGL(bm25_merge_kernel, dim3((u32)pieces), dim3(256), 0, st, b->d_docs, b->d_tfs, d_del_docs, d_del_tfs, d_old_off, d_del_off, T, nnz,
-                       d_new_docs, d_new_tfs);
+    hipLaunchKernelGGL(postings_merge_kernel<Bm25Merge>, dim3((u32)pieces), dim3(256), 0, st,
+                       Bm25Merge{b->d_docs, b->d_tfs, d_del_docs, d_del_tfs, d_new_docs, d_new_tfs}, d_old_off.p, d_del_off.p, T, nnz);
     HIP_TRY(hipGetLastError());
-    if (rows) {
-        if ((dir_words + 255) / 256 > 0x7FFFFFFFull) return cos_fail(COS_ERR_UNIMPLEMENTED, "tile directory too large for one launch");
-        HIP_TRY(hipMemcpy(d_row_begin, row_begin.data(), (size_t)rows * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_row_len, row_len.data(), (size_t)rows * 4, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(bm25_tile_dir_kernel, dim3((u32)((dir_words + 255) / 256)), dim3(256), 0, st, d_new_docs, d_row_begin, d_row_len, rows, n_tiles,
-                           d_new_dir);
-        HIP_TRY(hipGetLastError());
-    }
+
+    // 4. the new directory: a list crossing DIR_MIN gets a row, a larger largest id widens every row
+    const u32 new_max_doc = std::max(b->max_doc, delta_max_doc);
+    const u32 n_tiles = (u32)(((u64)new_max_doc + 1 + TILE - 1) / TILE);
+    std::vector<u32> new_dir_row;
+    u32 rows = 0;
+    rc = postings_build_dir(Bm25Ids{d_new_docs}, new_off.data(), 1, 1, T, DIR_MIN, n_tiles, st,
+                            [&](u32 t) { return cos_fail(COS_ERR_UNIMPLEMENTED, "posting list of term %u too long", mk.keys[t]); }, new_dir_row, rows, d_new_dir);
+    if (rc) { (void)hipStreamSynchronize(st); return rc; } // (the merge may still be reading the handle's arrays)
     HIP_TRY(hipStreamSynchronize(st));
 
     // 5. everything is complete: swap, then free the old arrays.  The search workspace is reused as is.
     b->d_docs = std::move(d_new_docs); b->d_tfs = std::move(d_new_tfs); b->d_tile_dir = std::move(d_new_dir);
-    b->term_hashes.swap(new_hashes);
+    b->term_hashes.swap(mk.keys);
     b->offsets.swap(new_off);
     b->dir_row.swap(new_dir_row);
     b->n_terms = T;
@@ -926,7 +831,7 @@ extern "C" int32_t cos_bm25_delete(cos_bm25 *b, const uint32_t *doc_ids, const u
     if (!b) return cos_fail(COS_ERR_INVALID, "bad argument");
     if (m == 0) return COS_OK;
     if (!doc_ids || !doc_offsets) return cos_fail(COS_ERR_INVALID, "bad argument");
-    int32_t rc = bm25_check_doc_offsets(doc_offsets, m);
+    int32_t rc = postings_check_offsets(doc_offsets, m, "doc_offsets", "document");
     if (rc) return rc;
     const u64 nd = doc_offsets[m];
     if (nd && !term_hashes) return cos_fail(COS_ERR_INVALID, "bad argument");

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "engine_internal.h"
+#include "postings_update.h"
 
 using namespace cosdev;
 
@@ -58,9 +59,9 @@ __device__ __forceinline__ u32 sparse_quantize(float value, float upper, u32 bit
 // Sums are exact u32 adds (qq * key), so the order in which a tile's terms and postings arrive is irrelevant: LDS atomic adds,
 // no barrier between terms.  A vector is a result as soon as any visited list holds it, also with similarity 0 (key 0, or a query
 // value that quantizes to 0): those rare postings set a bit in a per-tile flag word instead.
-constexpr u32 STILE = 8192;      // vector ids per LDS accumulator tile (32 KB of u32)
+constexpr u32 STILE = POSTINGS_TILE; // vector ids per LDS accumulator tile (32 KB of u32)
 constexpr u32 SDIR_MIN = 256;    // dimensions with more postings get a tile directory; shorter lists are scanned whole per tile
-constexpr u32 SNO_DIR = 0xFFFFFFFFu;
+constexpr u32 SNO_DIR = POSTINGS_NONE;
 constexpr int SPU = 8;           // postings per thread per chunk
 constexpr u32 SLICES = 256;      // (tile, term) slices a block resolves up front (LDS table); beyond that they are looked up on the way
 
@@ -1029,31 +1030,24 @@ extern "C" int32_t cos_sparse_last_stats(cos_sparse *s, cos_sparse_search_stats 
 // The postings never go back through the host.  The host owns the dimension table and the per-(dimension, key) counts (h_dims,
 // h_key_off: O(T * Q)) and sees the update itself; the device turns the vector-major update into dimension-major order (stable
 // radix sort by dimension slot: ids arrive ascending), streams old list + new postings of every dimension into NEW arrays
-// (sparse_merge_kernel), or the surviving postings of every list (sparse_compact_kernel), and searches the tile directory of the
-// new arrays (sparse_tile_dir_kernel).  A delete REMOVES the posting: the packed word has no spare bit at 8-bit keys, and a
-// search cannot tell a tombstone from an absent posting (nothing of a list but its live entries enters a score).  Only when all
-// of it is complete are the handle's pointers and host tables swapped: a call that fails before leaves the handle as it was.
+// (postings_merge_kernel<SparseMerge<PACKED>>, postings_update.h), or the surviving postings of every list (sparse_compact_kernel),
+// and searches the tile directory of the new arrays (postings_tile_dir_kernel<SparseIds<PACKED>>).  A delete REMOVES the posting:
+// the packed word has no spare bit at 8-bit keys, and a search cannot tell a tombstone from an absent posting (nothing of a list
+// but its live entries enters a score).  Only when all of it is complete are the handle's pointers and host tables swapped: a
+// call that fails before leaves the handle as it was.
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-constexpr u32 SMERGE_PIECE = 4096; // postings of the OUTPUT per workgroup: 256 threads x 4 rounds x 4 postings
 constexpr size_t SPAD_UNPACKED = 64 * SPU, SPAD_PACKED = 1; // padding behind the last posting (cos_sparse_create)
 
 __device__ __forceinline__ u32 spk_word(u32 id, u32 key) { return key << 24 | (id + 1u); }
 
 // vector id of posting p in either layout
 template <bool PACKED>
-__device__ __forceinline__ u32 sparse_id_at(const u32 *__restrict__ a, u64 p) { return PACKED ? (a[p] & 0xFFFFFFu) - 1u : a[p]; }
-
-// first position in [lo, hi) whose vector id is >= id (the lists are id-sorted)
-template <bool PACKED>
-__device__ __forceinline__ u64 sparse_lower_bound(const u32 *__restrict__ a, u64 lo, u64 hi, u64 id) {
-    while (lo < hi) {
-        const u64 mid = lo + (hi - lo) / 2;
-        if ((u64)sparse_id_at<PACKED>(a, mid) < id) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
+struct SparseIds {
+    const u32 *__restrict__ a; // ids or packed words
+    __device__ __forceinline__ u32 operator()(u64 p) const { return PACKED ? (a[p] & 0xFFFFFFu) - 1u : a[p]; }
+};
 
 // the update's pairs as (vector id << 8 | key): InvertedIndexNode::quantize on the device
 __global__ __launch_bounds__(256) void sparse_delta_kernel(const u32 *__restrict__ pair_id, const float *__restrict__ vals, u32 np, float upper, u32 bits,
@@ -1063,100 +1057,31 @@ __global__ __launch_bounds__(256) void sparse_delta_kernel(const u32 *__restrict
     out[i] = (u64)pair_id[i] << 8 | sparse_quantize(vals[i], upper, bits);
 }
 
-// the dimension that owns posting j of the new array: the LAST t in [lo, hi] whose list starts at or before j (an empty list
-// shares its start with the list behind it and is passed over).  Needs old_off[lo] + del_off[lo] <= j.
-__device__ __forceinline__ u32 sparse_dim_of(const u64 *__restrict__ old_off, const u64 *__restrict__ del_off, u32 lo, u32 hi, u64 j) {
-    while (lo < hi) {
-        const u32 mid = lo + (hi - lo + 1) / 2;
-        if (old_off[mid] + del_off[mid] <= j) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
-// new list of dimension t = old list of t, then the delta's postings of t (every new id is above every old one: still id-sorted).
-// old_off / del_off [T + 1] are indexed by the NEW dimension table (a dimension only the update has: an empty old part).  One
-// workgroup per SMERGE_PIECE postings of the OUTPUT whatever the list lengths; a thread moves 4 consecutive output postings — 4
-// consecutive source words when they come from one list and one source — and stores them as one 16-byte word of ids (or packed
-// words) and, in the unpacked layout, one 4-byte word of keys.
+// the posting formats of postings_update.h: a vector id and a key byte in two arrays (unpacked) or one word (packed); the delta is
+// `id << 8 | key` either way.  The registers hold the key on its own in both layouts; the packed stores leave it out.
 template <bool PACKED>
-__global__ __launch_bounds__(256) void sparse_merge_kernel(const u32 *__restrict__ old_a /* ids or packed words */, const uint8_t *__restrict__ old_keys,
-                                                           const u64 *__restrict__ delta, const u64 *__restrict__ old_off, const u64 *__restrict__ del_off,
-                                                           u32 T, u64 nnz, u32 *__restrict__ new_a, uint8_t *__restrict__ new_keys) {
-    const u64 p0 = (u64)blockIdx.x * SMERGE_PIECE;
-    if (p0 >= nnz) return;
-    const u64 p1 = p0 + SMERGE_PIECE < nnz ? p0 + SMERGE_PIECE : nnz;
-    const u32 t_lo = sparse_dim_of(old_off, del_off, 0, T - 1, p0); // block-uniform: they bound every thread's search
-    const u32 t_hi = sparse_dim_of(old_off, del_off, t_lo, T - 1, p1 - 1);
-    for (u64 j0 = p0 + (u64)threadIdx.x * 4; j0 < p1; j0 += 1024) {
-        u32 t = sparse_dim_of(old_off, del_off, t_lo, t_hi, j0);
-        u64 ob = old_off[t], db = del_off[t];
-        u64 ol = old_off[t + 1] - ob;
-        const u64 ne = old_off[t + 1] + del_off[t + 1];
-        u64 k = j0 - ob - db;
-        u32 a[4], ky[4];
-        if (j0 + 4 <= ne && k + 4 <= ol) { // one list, the old part: 4 consecutive words of it
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                a[u] = old_a[ob + k + u];
-                ky[u] = PACKED ? 0u : old_keys[ob + k + u];
-            }
-        } else if (j0 + 4 <= ne && k >= ol) { // one list, the delta part
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const u64 v = delta[db + (k - ol) + u];
-                a[u] = PACKED ? spk_word((u32)(v >> 8), (u32)v & 255u) : (u32)(v >> 8);
-                ky[u] = (u32)v & 255u;
-            }
-        } else { // a list boundary or the old/delta seam inside the 4: posting by posting
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const u64 j = j0 + u;
-                a[u] = 0u;
-                ky[u] = 0u;
-                if (j < nnz) {
-                    while (j >= old_off[t + 1] + del_off[t + 1]) t++; // j < nnz = the end of list T - 1: stops at t <= T - 1
-                    ob = old_off[t];
-                    db = del_off[t];
-                    ol = old_off[t + 1] - ob;
-                    k = j - ob - db;
-                    if (k < ol) {
-                        a[u] = old_a[ob + k];
-                        ky[u] = PACKED ? 0u : old_keys[ob + k];
-                    } else {
-                        const u64 v = delta[db + (k - ol)];
-                        a[u] = PACKED ? spk_word((u32)(v >> 8), (u32)v & 255u) : (u32)(v >> 8);
-                        ky[u] = (u32)v & 255u;
-                    }
-                }
-            }
-        }
-        if (j0 + 4 <= nnz) { // (the piece and the arrays are 16-byte aligned)
-            *reinterpret_cast<uint4 *>(new_a + j0) = make_uint4(a[0], a[1], a[2], a[3]);
-            if (!PACKED) *reinterpret_cast<u32 *>(new_keys + j0) = ky[0] | ky[1] << 8 | ky[2] << 16 | ky[3] << 24;
-        } else {
-#pragma unroll
-            for (int u = 0; u < 4; u++)
-                if (j0 + u < nnz) {
-                    new_a[j0 + u] = a[u];
-                    if (!PACKED) new_keys[j0 + u] = (uint8_t)ky[u];
-                }
-        }
+struct SparseMerge {
+    const u32 *__restrict__ old_a; // ids or packed words
+    const uint8_t *__restrict__ old_keys;
+    const u64 *__restrict__ delta;
+    u32 *__restrict__ new_a;
+    uint8_t *__restrict__ new_keys;
+    struct P { u32 a, ky; };
+    __device__ __forceinline__ P zero() const { return {0u, 0u}; }
+    __device__ __forceinline__ P from_old(u64 p) const { return {old_a[p], PACKED ? 0u : (u32)old_keys[p]}; }
+    __device__ __forceinline__ P from_delta(u64 p) const {
+        const u64 v = delta[p];
+        return {PACKED ? spk_word((u32)(v >> 8), (u32)v & 255u) : (u32)(v >> 8), (u32)v & 255u};
     }
-}
-
-// tile_dir[row][t] = offset (from the list's begin) of the first posting with vector id >= t * STILE, t = 0 .. n_tiles; the last
-// column is the list's length.  One lower-bound search per entry; the same values cos_sparse_create's host pass writes.
-template <bool PACKED>
-__global__ __launch_bounds__(256) void sparse_tile_dir_kernel(const u32 *__restrict__ a, const u64 *__restrict__ row_begin, const u32 *__restrict__ row_len,
-                                                              u32 rows, u32 n_tiles, u32 *__restrict__ tile_dir) {
-    const u64 idx = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    const u64 width = (u64)n_tiles + 1;
-    if (idx >= (u64)rows * width) return;
-    const u32 row = (u32)(idx / width), t = (u32)(idx % width);
-    const u64 lo = row_begin[row];
-    const u32 len = row_len[row];
-    tile_dir[idx] = t == n_tiles ? len : (u32)(sparse_lower_bound<PACKED>(a, lo, lo + len, (u64)t * STILE) - lo);
-}
+    __device__ __forceinline__ void store4(u64 j, const P (&v)[4]) const {
+        *reinterpret_cast<uint4 *>(new_a + j) = make_uint4(v[0].a, v[1].a, v[2].a, v[3].a);
+        if (!PACKED) *reinterpret_cast<u32 *>(new_keys + j) = v[0].ky | v[1].ky << 8 | v[2].ky << 16 | v[3].ky << 24;
+    }
+    __device__ __forceinline__ void store1(u64 j, const P &v) const {
+        new_a[j] = v.a;
+        if (!PACKED) new_keys[j] = (uint8_t)v.ky;
+    }
+};
 
 // one thread per (id, dimension, key) pair of a delete call whose key list holds something: lower bound on the id in the
 // dimension's list, then the postings of that id in turn — the first one with the pair's key that nobody has claimed yet is
@@ -1170,7 +1095,8 @@ __global__ __launch_bounds__(256) void sparse_claim_kernel(const u32 *__restrict
     const u32 id = pair_id_key[2 * i], key = pair_id_key[2 * i + 1];
     const u64 lo = pair_begin[i], hi = lo + pair_len[i];
     uint8_t hit = 0;
-    for (u64 p = sparse_lower_bound<PACKED>(a, lo, hi, id); p < hi && sparse_id_at<PACKED>(a, p) == id; p++) {
+    const SparseIds<PACKED> ids{a};
+    for (u64 p = postings_lower_bound(ids, lo, hi, id); p < hi && ids(p) == id; p++) {
         const u32 k = PACKED ? a[p] >> 24 : (u32)keys[p];
         if (k != key) continue;
         const u32 bit = 1u << (p & 31u);
@@ -1221,13 +1147,6 @@ __global__ __launch_bounds__(256) void sparse_compact_kernel(const u32 *__restri
         }
 }
 
-int32_t sparse_check_row_offsets(const uint64_t *row_offsets, u32 m) {
-    if (row_offsets[0] != 0) return cos_fail(COS_ERR_INVALID, "row_offsets[0] must be 0");
-    for (u32 i = 0; i < m; i++)
-        if (row_offsets[i + 1] < row_offsets[i]) return cos_fail(COS_ERR_INVALID, "row_offsets must not decrease (vector %u)", i);
-    return COS_OK;
-}
-
 // the posting arrays of a handle in the making: allocated with the padding the search kernels rely on, the padding zeroed
 struct SparseArrays {
     DevArr<u32> a; // d_ids or d_pk
@@ -1244,38 +1163,12 @@ struct SparseArrays {
     }
 };
 
-// rows of the tile directory for the lists of `key_off` ([T][Q + 1]) that are longer than SDIR_MIN, searched on the device
-int32_t sparse_build_dir(bool packed, const u32 *d_a, const std::vector<u64> &key_off, u32 T, u32 Q, u32 n_tiles, std::vector<u32> &h_dir, u32 &rows_out,
-                         DevArr<u32> &d_dir) {
-    std::vector<u64> row_begin;
-    std::vector<u32> row_len;
-    h_dir.assign(T, SNO_DIR);
-    for (u32 t = 0; t < T; t++) {
-        const u64 b = key_off[(size_t)t * (Q + 1)], e = key_off[(size_t)t * (Q + 1) + Q];
-        if (e - b <= SDIR_MIN) continue;
-        if (e - b > 0xFFFFFFFFull) return cos_fail(COS_ERR_UNIMPLEMENTED, "a dimension would hold more than 2^32 postings");
-        h_dir[t] = (u32)row_begin.size();
-        row_begin.push_back(b);
-        row_len.push_back((u32)(e - b));
-    }
-    const u32 rows = (u32)row_begin.size();
-    const u64 dir_words = (u64)rows * (n_tiles + 1);
-    rows_out = rows;
-    HIP_TRY(d_dir.alloc(dir_words));
-    if (!rows) return COS_OK;
-    if ((dir_words + 255) / 256 > 0x7FFFFFFFull) return cos_fail(COS_ERR_UNIMPLEMENTED, "tile directory too large for one launch");
-    DevArr<u64> d_row_begin;
-    DevArr<u32> d_row_len;
-    HIP_TRY(d_row_begin.alloc(rows));
-    HIP_TRY(d_row_len.alloc(rows));
-    HIP_TRY(hipMemcpy(d_row_begin, row_begin.data(), (size_t)rows * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_row_len, row_len.data(), (size_t)rows * 4, hipMemcpyHostToDevice));
-    const dim3 grid((u32)((dir_words + 255) / 256));
-    if (packed) hipLaunchKernelGGL(sparse_tile_dir_kernel<true>, grid, dim3(256), 0, 0, d_a, d_row_begin.p, d_row_len.p, rows, n_tiles, d_dir.p);
-    else hipLaunchKernelGGL(sparse_tile_dir_kernel<false>, grid, dim3(256), 0, 0, d_a, d_row_begin.p, d_row_len.p, rows, n_tiles, d_dir.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(0)); // the two row tables are locals
-    return COS_OK;
+// tile directory of new arrays `d_a` whose lists are the rows of `key_off` ([T][Q + 1]): rows for those longer than SDIR_MIN
+int32_t sparse_new_dir(bool packed, const u32 *d_a, const std::vector<u64> &key_off, u32 T, u32 Q, u32 n_tiles, std::vector<u32> &h_dir, u32 &rows_out,
+                       DevArr<u32> &d_dir) {
+    auto too_long = [](u32) { return cos_fail(COS_ERR_UNIMPLEMENTED, "a dimension would hold more than 2^32 postings"); };
+    if (packed) return postings_build_dir(SparseIds<true>{d_a}, key_off.data(), Q + 1, Q, T, SDIR_MIN, n_tiles, 0, too_long, h_dir, rows_out, d_dir);
+    return postings_build_dir(SparseIds<false>{d_a}, key_off.data(), Q + 1, Q, T, SDIR_MIN, n_tiles, 0, too_long, h_dir, rows_out, d_dir);
 }
 
 } // namespace
@@ -1288,7 +1181,7 @@ extern "C" int32_t cos_sparse_insert(cos_sparse *s, uint32_t m, const uint64_t *
         return COS_OK;
     }
     if (!row_offsets) return cos_fail(COS_ERR_INVALID, "bad argument");
-    int32_t rc = sparse_check_row_offsets(row_offsets, m);
+    int32_t rc = postings_check_offsets(row_offsets, m, "row_offsets", "vector");
     if (rc) return rc;
     const u64 nd = row_offsets[m];
     if (nd && (!raw_dims || !raw_vals)) return cos_fail(COS_ERR_INVALID, "bad argument");
@@ -1306,26 +1199,16 @@ extern "C" int32_t cos_sparse_insert(cos_sparse *s, uint32_t m, const uint64_t *
     std::sort(ud.begin(), ud.end());
     ud.erase(std::unique(ud.begin(), ud.end()), ud.end());
     const u32 U = (u32)ud.size();
-    std::vector<u32> new_dims, old_of, ud_slot(U); // old_of[t] = index in the old table or SNO_DIR
-    new_dims.reserve((size_t)T0 + U);
-    old_of.reserve((size_t)T0 + U);
-    {
-        u32 i = 0, j = 0;
-        while (i < T0 || j < U) {
-            const bool take_old = j == U || (i < T0 && s->h_dims[i] <= ud[j]);
-            const bool take_del = i == T0 || (j < U && ud[j] <= s->h_dims[i]);
-            if (take_del) ud_slot[j] = (u32)new_dims.size();
-            new_dims.push_back(take_old ? s->h_dims[i] : ud[j]);
-            old_of.push_back(take_old ? i : SNO_DIR);
-            if (take_old) i++;
-            if (take_del) j++;
-        }
-    }
+    MergedKeys mk = postings_merge_keys(s->h_dims, ud);
+    std::vector<u32> &new_dims = mk.keys, &old_of = mk.old_of; // old_of[t] = index in the old table or POSTINGS_NONE
+    std::vector<u32> ud_slot(U);
     if (new_dims.size() > 0xFFFFFFFFull) return cos_fail(COS_ERR_UNIMPLEMENTED, "more than 2^32 - 1 dimensions");
     const u32 T1 = (u32)new_dims.size();
+    for (u32 t = 0; t < T1; t++)
+        if (mk.del_of[t] != POSTINGS_NONE) ud_slot[mk.del_of[t]] = t;
     std::vector<u32> h_slot(np), h_pid(np), cnt((size_t)T1 * Q, 0u), new_mult(T1, 1u), tmp;
     for (u32 t = 0; t < T1; t++)
-        if (old_of[t] != SNO_DIR) new_mult[t] = s->h_mult[old_of[t]];
+        if (old_of[t] != POSTINGS_NONE) new_mult[t] = s->h_mult[old_of[t]];
     for (u32 i = 0; i < m; i++) {
         const u64 b = row_offsets[i], e = row_offsets[i + 1];
         bool ascending = true;
@@ -1352,7 +1235,7 @@ extern "C" int32_t cos_sparse_insert(cos_sparse *s, uint32_t m, const uint64_t *
         u64 run = 0, dpos = 0;
         u32 next_old = 0; // the old dimension at or behind new slot t
         for (u32 t = 0; t < T1; t++) {
-            const u64 *oko = old_of[t] != SNO_DIR ? s->h_key_off.data() + (size_t)old_of[t] * (Q + 1) : nullptr;
+            const u64 *oko = old_of[t] != POSTINGS_NONE ? s->h_key_off.data() + (size_t)old_of[t] * (Q + 1) : nullptr;
             old_off[t] = next_old < T0 ? s->h_key_off[(size_t)next_old * (Q + 1)] : nnz0;
             del_off[t] = dpos;
             const u64 begin = run;
@@ -1370,7 +1253,7 @@ extern "C" int32_t cos_sparse_insert(cos_sparse *s, uint32_t m, const uint64_t *
     }
     const u64 nnz1 = nnz0 + np;
     const u32 n_tiles1 = (u32)(((u64)n1 + STILE - 1) / STILE);
-    const u64 pieces = (nnz1 + SMERGE_PIECE - 1) / SMERGE_PIECE;
+    const u64 pieces = (nnz1 + MERGE_PIECE - 1) / MERGE_PIECE;
     if (pieces > 0x7FFFFFFFull) return cos_fail(COS_ERR_UNIMPLEMENTED, "too many postings for one merge launch");
     std::vector<u64> raw_off_tail;
     if (s->have_raw) {
@@ -1410,17 +1293,17 @@ extern "C" int32_t cos_sparse_insert(cos_sparse *s, uint32_t m, const uint64_t *
     HIP_TRY(hipMemcpy(d_del_off, del_off.data(), ((size_t)T1 + 1) * 8, hipMemcpyHostToDevice));
     if (pieces) {
         if (s->packed)
-            hipLaunchKernelGGL(sparse_merge_kernel<true>, dim3((u32)pieces), dim3(256), 0, 0, s->d_pk.p, (const uint8_t *)nullptr, d_delta.p, d_old_off.p, d_del_off.p,
-                               T1, nnz1, na.a.p, (uint8_t *)nullptr);
+            hipLaunchKernelGGL(postings_merge_kernel<SparseMerge<true>>, dim3((u32)pieces), dim3(256), 0, 0,
+                               SparseMerge<true>{s->d_pk.p, nullptr, d_delta.p, na.a.p, nullptr}, d_old_off.p, d_del_off.p, T1, nnz1);
         else
-            hipLaunchKernelGGL(sparse_merge_kernel<false>, dim3((u32)pieces), dim3(256), 0, 0, s->d_ids.p, s->d_keys.p, d_delta.p, d_old_off.p, d_del_off.p, T1, nnz1,
-                               na.a.p, na.keys.p);
+            hipLaunchKernelGGL(postings_merge_kernel<SparseMerge<false>>, dim3((u32)pieces), dim3(256), 0, 0,
+                               SparseMerge<false>{s->d_ids.p, s->d_keys.p, d_delta.p, na.a.p, na.keys.p}, d_old_off.p, d_del_off.p, T1, nnz1);
         HIP_TRY(hipGetLastError());
     }
     std::vector<u32> new_dir;
     DevArr<u32> d_new_dir;
     u32 rows1 = 0;
-    rc = sparse_build_dir(s->packed, na.a.p, new_ko, T1, Q, n_tiles1, new_dir, rows1, d_new_dir);
+    rc = sparse_new_dir(s->packed, na.a.p, new_ko, T1, Q, n_tiles1, new_dir, rows1, d_new_dir);
     if (rc) { (void)hipStreamSynchronize(0); return rc; }
     DevArr<u64> d_row_off;
     DevArr<u32> d_raw_dims;
@@ -1466,7 +1349,7 @@ extern "C" int32_t cos_sparse_delete(cos_sparse *s, const uint32_t *ids, const u
     if (out_removed) *out_removed = 0;
     if (m == 0) return COS_OK;
     if (!ids || !row_offsets) return cos_fail(COS_ERR_INVALID, "bad argument");
-    int32_t rc = sparse_check_row_offsets(row_offsets, m);
+    int32_t rc = postings_check_offsets(row_offsets, m, "row_offsets", "vector");
     if (rc) return rc;
     const u64 nd = row_offsets[m];
     if (nd && (!raw_dims || !raw_vals)) return cos_fail(COS_ERR_INVALID, "bad argument");
@@ -1553,7 +1436,7 @@ extern "C" int32_t cos_sparse_delete(cos_sparse *s, const uint32_t *ids, const u
     std::vector<u32> new_dir;
     DevArr<u32> d_new_dir;
     u32 rows1 = 0;
-    rc = sparse_build_dir(s->packed, na.a.p, new_ko, T, Q, s->n_tiles, new_dir, rows1, d_new_dir);
+    rc = sparse_new_dir(s->packed, na.a.p, new_ko, T, Q, s->n_tiles, new_dir, rows1, d_new_dir);
     if (rc) { (void)hipStreamSynchronize(0); return rc; }
     HIP_TRY(hipDeviceSynchronize());
     if (s->packed) s->d_pk = std::move(na.a);

@@ -12,7 +12,7 @@
            build on the never-updated index, alternated with (b) round by round so that the spread of each against itself is known.
 
 --profile-insert: one create + one insert + one delete and nothing else — the run to put under `rocprofv3 --kernel-trace --stats`
-for sparse_merge_kernel's and sparse_compact_kernel's own time (bytes read + written per posting of the new array over that
+for postings_merge_kernel<SparseMerge<true>>'s (SparseMerge<false> in the unpacked layout) and sparse_compact_kernel's own time (bytes read + written per posting of the new array over that
 time, against the streaming-copy ceiling cos_hbm_probe(kind = 1) reports on the same machine)."""
 import argparse, ctypes as C, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
