@@ -16,15 +16,9 @@
 
 #include <algorithm>
 
-#include "dot_engines.h"
-#include "engine_types.h"
+#include "walk_common.h"
 
 using namespace cosdev;
-
-#define COS_OK 0
-#define COS_ERR_CALCULATION 2
-#define COS_ERR_UNIMPLEMENTED 4
-#define COS_QUERY_ID 0xFFFFFFFEu
 
 namespace {
 
@@ -71,7 +65,7 @@ __global__ __launch_bounds__(64) void walk_meta_kernel(const IndexDev ix, const 
     const u32 qi = blockIdx.x;
     if (qi >= wa.B) return;
     const u32 L = ix.num_layers, metric = ix.metric, md = ix.mdim;
-    const u32 Mmax = ix.lv[0].M > ix.lv[L].M ? ix.lv[0].M : ix.lv[L].M;
+    const u32 Mmax = walk_mmax(ix);
     MetaSmem sm;
     {
         unsigned char *p = smem_raw;
@@ -124,28 +118,15 @@ __global__ __launch_bounds__(64) void walk_meta_kernel(const IndexDev ix, const 
     auto vec_distance_single = [&](u32 row, float &sim_out) -> bool {
         float dotf;
         if constexpr (!FLOAT_ENG) {
-            u32 a = 0;
-            if (grp == 0) {
-#pragma unroll
-                for (int c = 0; c < CH; c++) {
-                    const u32 chunk = (u32)lig + (u32)c * (u32)G;
-                    if (chunk < ix.nchunks) a = chunk_dot<ENG>(qreg[c], *(const uint4 *)(ix.codes + (u64)row * ix.row_stride + (u64)chunk * 16), a);
-                }
-            }
-            a = group_reduce_add_u32(a, G);
-            dotf = (float)readlane_u32(a, 0);
+            dotf = (float)int_row_dot_group0<ENG, CH>(qreg, ix.codes + (u64)row * ix.row_stride, ix.nchunks, lig, grp, G);
         } else if constexpr (ENG == ENG_F16) {
             dotf = __uint_as_float(readlane_u32(__float_as_uint(f16_lane_dot(ix.codes + (u64)row * ix.row_stride, sm.qf, ix.dim)), 0));
         } else {
             dotf = __uint_as_float(readlane_u32(__float_as_uint(f32_oct_dot((const float *)(ix.codes + (u64)row * ix.row_stride), sm.qf, ix.dim, lane & 7)), 0));
         }
-        if (metric == 0u) {
-            const float den = __fmul_rn(qmag, ix.mags[row]);
-            if (den == 0.0f) return false;
-            sim_out = __fdiv_rn(dotf, den);
-        } else
-            sim_out = dotf;
-        return true;
+        bool bad;
+        sim_out = cosine_or_dot(metric, dotf, qmag, ix.mags[row], bad);
+        return !bad;
     };
 
     // CosineSimilarity::calculate's dispatch for (stored node, query with the filter in sm.fq / sm.fqi):
@@ -188,8 +169,8 @@ __global__ __launch_bounds__(64) void walk_meta_kernel(const IndexDev ix, const 
         const u32 slots = M < ix.shortlist ? M : ix.shortlist;
         const u32 bitmask = 64u * M - 1u;
         const u32 out_slot = L - (u32)level;
-        for (u32 w = lane; w < 2 * M; w += 64) sm.vis[w] = 0;
-        if (lane == 0) { const u32 b = self_id & bitmask; sm.vis[b >> 5] |= 1u << (b & 31); }
+        vis_clear<64>(sm.vis, M, lane);
+        if (lane == 0) vis_set_bit(sm.vis, self_id & bitmask);
         u32 nacc = 0; // merged candidates so far (sm.acc)
 
         for (u32 f = f0; f < f1 && status == COS_OK; f++) {
@@ -218,7 +199,7 @@ __global__ __launch_bounds__(64) void walk_meta_kernel(const IndexDev ix, const 
                 s0 = __uint_as_float(readlane_u32(__float_as_uint(s0), 0));
                 if (dec < 0) { status = -dec; break; }
                 if (dec == 1 && !vec_distance_single(lv.node_vec[entry], s0)) { status = COS_ERR_CALCULATION; break; }
-                if (lane == 0) { const u32 b = eid & bitmask; sm.vis[b >> 5] |= 1u << (b & 31); }
+                if (lane == 0) vis_set_bit(sm.vis, eid & bitmask);
                 pool.insert_at(pack_key(metric_key(metric, s0), entry), 0, lane);
                 npool = 1;
             }
@@ -281,17 +262,7 @@ __global__ __launch_bounds__(64) void walk_meta_kernel(const IndexDev ix, const 
                 if (!__any(cand)) continue;
                 u32 old = 0;
                 if (cand) old = atomicOr(&sm.vis[word], msk);
-                const bool lost = cand && (old & msk);
-                bool win = cand && !lost;
-                u64 lostmask = __ballot(lost);
-                while (lostmask) { // two slots of this expansion alias the same residue: the LOWER slot wins (sequential scan order)
-                    const int l = __ffsll((long long)lostmask) - 1;
-                    const u32 b = readlane_u32(bit, l);
-                    const u64 g = __ballot(cand && bit == b);
-                    const int w = __ffsll((long long)g) - 1;
-                    if (cand && bit == b) win = (lane == w);
-                    lostmask &= ~g;
-                }
+                const bool win = __builtin_amdgcn_inverse_ballot_w64(vis_alias_winners(__ballot(cand), bit, __ballot(cand && (old & msk))));
                 // node-kind dispatch per winner
                 float csim = 0.0f;
                 int dec = 0;
@@ -356,14 +327,9 @@ __global__ __launch_bounds__(64) void walk_meta_kernel(const IndexDev ix, const 
                             dotf = (float)a;
                         } else
                             dotf = fdot[p];
-                        float sim = dotf;
-                        bool bad = false;
-                        if (metric == 0u) {
-                            const float den = __fmul_rn(qmag, pmag[p]);
-                            bad = (base + p * RP + grp < W) && den == 0.0f;
-                            sim = __fdiv_rn(dotf, den);
-                        }
-                        if (__any(bad)) { status = COS_ERR_CALCULATION; failed = true; break; }
+                        bool bad;
+                        const float sim = cosine_or_dot(metric, dotf, qmag, pmag[p], bad);
+                        if (__any(bad && base + p * RP + grp < W)) { status = COS_ERR_CALCULATION; failed = true; break; }
                         const u32 key = metric_key(metric, sim);
                         for (int g = 0; g < RP; g++) {
                             const int my = base + p * RP + g;
@@ -483,7 +449,7 @@ __global__ __launch_bounds__(64) void walk_meta_kernel(const IndexDev ix, const 
 namespace cosdev {
 
 size_t walk_meta_smem_bytes(const IndexDev &ix, u32 ef, int eng) {
-    const u32 Mmax = ix.lv[0].M > ix.lv[ix.num_layers].M ? ix.lv[0].M : ix.lv[ix.num_layers].M;
+    const u32 Mmax = walk_mmax(ix);
     const u32 res = ef < 128u ? 128u : ef; // the popped list doubles as the 128-entry staging list of the merge
     size_t b = (size_t)Mmax * 8 + (size_t)res * 8 + 128 * 8 + 64 * 4 * 4 + (size_t)5 * LA_M * 64 * 4;
     b = (b + 15) & ~(size_t)15;

@@ -17,14 +17,9 @@
 
 #include "engine_types.h"
 #include "tuning.h"
-#include "dot_engines.h"
+#include "walk_common.h"
 
 using namespace cosdev;
-
-#define COS_OK 0
-#define COS_ERR_CALCULATION 2
-#define COS_QUERY_ID 0xFFFFFFFEu
-#define COS_ROOT_ID 0xFFFFFFFFu
 
 namespace {
 
@@ -112,7 +107,6 @@ __global__ __launch_bounds__(256) void quantize_rows_kernel(const float *__restr
     }
 }
 
-#define COS_WALK_KERNEL_NAME walk_kernel
 #include "walk_kernel.inc"
 
 // ------------------------------------------------------------------------------------------------

@@ -24,15 +24,9 @@
 
 #include <algorithm>
 
-#include "engine_types.h"
-#include "dot_engines.h"
+#include "walk_common.h"
 
 using namespace cosdev;
-
-#define COS_OK 0
-#define COS_ERR_CALCULATION 2
-#define COS_QUERY_ID 0xFFFFFFFEu
-#define COS_ROOT_ID 0xFFFFFFFFu
 
 namespace {
 
@@ -96,14 +90,9 @@ __global__ __launch_bounds__(64) void walk_general_kernel(const IndexDev ix, con
             const float d = f32_oct_dot((const float *)rp, qf, ix.dim, lane & 7);
             dotf = __uint_as_float(readlane_u32(__float_as_uint(d), 0));
         }
-        if (metric == 0u) { // cosine_similarity_from_dot_product (cosine.rs:223-235)
-            const float den = uniform_f32(__fmul_rn(qmag, ix.mags[row]));
-            if (den == 0.0f) return false;
-            sim_out = __fdiv_rn(dotf, den);
-        } else {
-            sim_out = dotf; // DotProductDistance (dotproduct.rs:14-64)
-        }
-        return true;
+        bool bad;
+        sim_out = cosine_or_dot(metric, dotf, qmag, uniform_f32(ix.mags[row]), bad);
+        return !bad;
     };
 
     u64 n_evals = 0, n_exp = 0, adj_bytes = 0;
@@ -120,12 +109,9 @@ __global__ __launch_bounds__(64) void walk_general_kernel(const IndexDev ix, con
 
         // fresh visited filter, pre-seeded with the query / new-node id (vector_store.rs:266-271, :807)
         if (!EXACT) {
-            for (u32 w = lane; w < 2 * M; w += 64) vis_lds[w] = 0;
+            vis_clear<64>(vis_lds, M, lane);
             wave_lds_sync();
-            if (lane == 0 && wa.no_self_seed == 0u) {
-                const u32 b = self_id & bitmask;
-                vis_lds[b >> 5] |= 1u << (b & 31);
-            }
+            if (lane == 0 && wa.no_self_seed == 0u) vis_set_bit(vis_lds, self_id & bitmask);
         }
         u32 npool = 0, npop = 0, failed = 0;
         u32 lev_evals = 1;
@@ -133,9 +119,8 @@ __global__ __launch_bounds__(64) void walk_general_kernel(const IndexDev ix, con
             const u32 erow = uniform_u32(lv.node_vec ? lv.node_vec[entry] : entry);
             float s0;
             if (!row_similarity(erow, s0)) { status = COS_ERR_CALCULATION; break; }
-            const u32 eid = erow == N ? COS_ROOT_ID : erow * ix.id_stride;
             if (lane == 0) {
-                if (!EXACT) { const u32 b = eid & bitmask; vis_lds[b >> 5] |= 1u << (b & 31); }
+                if (!EXACT) vis_set_bit(vis_lds, vis_bit_of(erow, N, ix.id_stride, bitmask));
                 else {
                     atomicOr(&vis[entry >> 5], 1u << (entry & 31));
                     vlog[0] = entry >> 5;
@@ -163,23 +148,13 @@ __global__ __launch_bounds__(64) void walk_general_kernel(const IndexDev ix, con
                 const u64 vmask = ballot64(nb_vec != ROW_EMPTY);
                 u64 wmask;
                 if (!EXACT) {
-                    // PerformantFixedSet: bucket=(id>>6)&(M-1), bit=id&63  <=> linear bit id & (64M-1)
-                    const u32 id = nb_vec == N ? COS_ROOT_ID : nb_vec * ix.id_stride;
-                    const u32 bit = id & bitmask;
+                    const u32 bit = vis_bit_of(nb_vec, N, ix.id_stride, bitmask);
                     const u32 word = bit >> 5, msk = 1u << (bit & 31);
                     const u32 seen = vis_lds[word];
                     const u64 cmask = vmask & ballot64((seen & msk) == 0u);
                     u32 old = 0;
                     if (__builtin_amdgcn_inverse_ballot_w64(cmask)) old = atomicOr(&vis_lds[word], msk);
-                    u64 lostmask = cmask & ballot64((old & msk) != 0u);
-                    wmask = cmask & ~lostmask;
-                    // two slots of this pass alias the same residue: the LOWER slot wins (sequential scan order)
-                    while (lostmask) {
-                        const int l = __ffsll((long long)lostmask) - 1;
-                        const u64 g = cmask & ballot64(bit == readlane_u32(bit, l));
-                        wmask = (wmask & ~g) | (g & (0ull - g));
-                        lostmask &= ~g;
-                    }
+                    wmask = vis_alias_winners(cmask, bit, cmask & ballot64((old & msk) != 0u));
                     wave_lds_sync();
                 } else {
                     u32 w = 0;
@@ -245,17 +220,13 @@ __global__ __launch_bounds__(64) void walk_general_kernel(const IndexDev ix, con
         // keep the best `keep` of the popped entries, sorted descending (vector_store.rs:1194-1201): repeated selection of the largest
         // key still in the list (keys are distinct: a node enters a level's candidates once)
         u32 cnt = npop < wa.keep ? npop : wa.keep;
-        const u64 obase = ((u64)qi * (L + 1) + out_slot) * wa.keep;
+        const u64 obase = level_list_base(ix, wa, qi, out_slot);
         u32 best_node = 0;
         if (npop == 0) { // only if ef == 0: the entry node's own distance (vector_store.rs:329-380)
             const u32 erow = uniform_u32(lv.node_vec ? lv.node_vec[entry] : entry);
             float s0;
             if (!row_similarity(erow, s0)) { status = COS_ERR_CALCULATION; break; }
-            if (lane == 0) {
-                wa.out_ids[obase] = erow == N ? COS_ROOT_ID : erow * ix.id_stride;
-                wa.out_sims[obase] = metric_key_inv(metric, metric_key(metric, s0));
-                if (wa.out_nodes) wa.out_nodes[obase] = entry;
-            }
+            if (lane == 0) write_level_entry(pack_key(metric_key(metric, s0), entry), obase, ix, lv, wa);
             best_node = entry;
             cnt = 1;
         }
@@ -276,12 +247,7 @@ __global__ __launch_bounds__(64) void walk_general_kernel(const IndexDev ix, con
             wave_lds_sync();
             const u32 nd = (u32)wm;
             if (k == 0) best_node = nd;
-            if (lane == 0) {
-                const u32 vrow = lv.node_vec ? lv.node_vec[nd] : nd;
-                wa.out_ids[obase + k] = vrow == N ? COS_ROOT_ID : vrow * ix.id_stride;
-                wa.out_sims[obase + k] = metric_key_inv(metric, (u32)(wm >> 32));
-                if (wa.out_nodes) wa.out_nodes[obase + k] = nd;
-            }
+            if (lane == 0) write_level_entry(wm, obase + k, ix, lv, wa);
         }
         if (lane == 0) wa.out_counts[(u64)qi * (L + 1) + out_slot] = cnt;
         // descend through the best hit's child link (vector_store.rs:382-385)
@@ -290,18 +256,8 @@ __global__ __launch_bounds__(64) void walk_general_kernel(const IndexDev ix, con
 
     if (lane == 0) {
         wa.out_status[qi] = status;
-        if (wa.out_stats) {
-            wa.out_stats[(u64)qi * 4 + 0] = n_evals;
-            wa.out_stats[(u64)qi * 4 + 1] = n_exp;
-            wa.out_stats[(u64)qi * 4 + 2] = adj_bytes;
-            wa.out_stats[(u64)qi * 4 + 3] = n_exp;
-        }
-        if (wa.out_stats2) {
-            wa.out_stats2[(u64)qi * 4 + 0] = n_evals;
-            wa.out_stats2[(u64)qi * 4 + 1] = n_exp;
-            wa.out_stats2[(u64)qi * 4 + 2] = adj_bytes;
-            wa.out_stats2[(u64)qi * 4 + 3] = 0ull;
-        }
+        write_walk_stats(wa.out_stats, qi, n_evals, n_exp, adj_bytes, n_exp); // one expansion per round
+        write_walk_stats(wa.out_stats2, qi, n_evals, n_exp, adj_bytes, 0ull); // no level table here
     }
 }
 

@@ -26,20 +26,14 @@
 
 #include "engine_types.h"
 #include "tuning.h"
-#include "dot_engines.h"
+#include "walk_common.h"
 
 using namespace cosdev;
-
-#define COS_OK 0
-#define COS_ERR_CALCULATION 2
-#define COS_QUERY_ID 0xFFFFFFFEu
-#define COS_ROOT_ID 0xFFFFFFFFu
 
 namespace {
 
 constexpr int LAL = 4;  // window capacity (adjacency rows prefetched per round); the launch picks la <= LAL.  8 measured slower (see launch_walk_lat)
-constexpr int GL = 16;  // lanes per code row
-constexpr int RPL = 64 / GL; // rows per wave pass
+constexpr int GL = LAT_ROW_LANES; // lanes per code row (4 rows per wave pass)
 constexpr int PBL = 8;  // passes in flight before the dots are consumed (32 rows)
 
 template <int ENG, int CH, int R, bool PREFETCH_ADJ>
@@ -49,7 +43,6 @@ __global__ __launch_bounds__(64) void walk_lat_kernel(const IndexDev ix, const W
     const u32 qi = blockIdx.x;
     if (qi >= wa.B) return;
 
-    const u32 Mmax = ix.lv[0].M > ix.lv[ix.num_layers].M ? ix.lv[0].M : ix.lv[ix.num_layers].M;
     u64 *s_spec, *s_cl, *s_res;
     u32 *s_vis;
     {
@@ -85,25 +78,10 @@ __global__ __launch_bounds__(64) void walk_lat_kernel(const IndexDev ix, const W
 
     // similarity of ONE row, computed by lane group 0; result in every lane
     auto single_distance = [&](u32 row, float &sim_out) -> bool {
-        u32 acc = 0;
-        if (grp == 0) {
-#pragma unroll
-            for (int c = 0; c < CH; c++) {
-                const u32 chunk = (u32)lig + (u32)c * (u32)GL;
-                if (chunk < ix.nchunks) acc = chunk_dot<ENG>(qreg[c], *(const uint4 *)(ix.codes + (u64)row * ix.row_stride + (u64)chunk * 16), acc);
-            }
-        }
-        acc = group_reduce_add_u32(acc, GL);
-        acc = readlane_u32(acc, 0);
-        const float dotf = (float)acc; // integer dot `as f32` (RNE)
-        if (metric == 0u) {            // cosine_similarity_from_dot_product (cosine.rs:223-235)
-            const float den = __fmul_rn(qmag, ix.mags[row]);
-            if (den == 0.0f) return false;
-            sim_out = __fdiv_rn(dotf, den);
-        } else {
-            sim_out = dotf; // DotProductDistance (dotproduct.rs:14-64)
-        }
-        return true;
+        const u32 acc = int_row_dot_group0<ENG, CH>(qreg, ix.codes + (u64)row * ix.row_stride, ix.nchunks, lig, grp, GL);
+        bool bad;
+        sim_out = cosine_or_dot(metric, (float)acc, qmag, ix.mags[row], bad); // integer dot `as f32` (RNE)
+        return !bad;
     };
 
     for (int level = (int)L; level >= 0; level--) {
@@ -114,12 +92,9 @@ __global__ __launch_bounds__(64) void walk_lat_kernel(const IndexDev ix, const W
         const u32 out_slot = L - (u32)level;
 
         // fresh visited filter, pre-seeded with the query / new-node id (vector_store.rs:266-271, :807)
-        for (u32 w = lane; w < 2 * M; w += 64) s_vis[w] = 0;
+        vis_clear<64>(s_vis, M, lane);
         __builtin_amdgcn_wave_barrier();
-        if (lane == 0) {
-            const u32 b = self_id & bitmask;
-            s_vis[b >> 5] |= 1u << (b & 31);
-        }
+        if (lane == 0) vis_set_bit(s_vis, self_id & bitmask);
 
         Pool<R> pool;
         pool.clear();
@@ -130,11 +105,7 @@ __global__ __launch_bounds__(64) void walk_lat_kernel(const IndexDev ix, const W
             float s0;
             n_evals++;
             if (!single_distance(erow, s0)) { status = COS_ERR_CALCULATION; break; }
-            const u32 eid = erow == N ? COS_ROOT_ID : erow * ix.id_stride;
-            if (lane == 0) {
-                const u32 b = eid & bitmask;
-                s_vis[b >> 5] |= 1u << (b & 31);
-            }
+            if (lane == 0) vis_set_bit(s_vis, vis_bit_of(erow, N, ix.id_stride, bitmask));
             pool.insert_at(pack_key(metric_key(metric, s0), entry), 0, lane);
             npool = 1;
         }
@@ -180,13 +151,11 @@ __global__ __launch_bounds__(64) void walk_lat_kernel(const IndexDev ix, const W
             u32 vword[LAL]; // the filter words first (one LDS round trip for the window), then the ballots
             static_for<0, LAL>([&](auto ic) {
                 constexpr int i = decltype(ic)::value;
-                const u32 id = av[i] == N ? COS_ROOT_ID : av[i] * ix.id_stride; // an empty slot maps somewhere inside the filter too
-                vword[i] = s_vis[(id & bitmask) >> 5];
+                vword[i] = s_vis[vis_bit_of(av[i], N, ix.id_stride, bitmask) >> 5]; // an empty slot maps somewhere inside the filter too
             });
             static_for<0, LAL>([&](auto ic) {
                 constexpr int i = decltype(ic)::value;
-                const u32 id = av[i] == N ? COS_ROOT_ID : av[i] * ix.id_stride;
-                const bool c = av[i] != ROW_EMPTY && !(vword[i] & (1u << (id & bitmask & 31u))); // entries past kwin hold only empty slots
+                const bool c = av[i] != ROW_EMPTY && !(vword[i] & (1u << (vis_bit_of(av[i], N, ix.id_stride, bitmask) & 31u))); // entries past kwin hold only empty slots
                 const u64 cm = __ballot(c);
                 if (c) s_cl[T + (u32)__popcll(cm & lt_mask)] = (u64)av[i] | ((u64)(u32)(i * 64 + lane) << 32);
                 T += (u32)__popcll(cm);
@@ -204,57 +173,8 @@ __global__ __launch_bounds__(64) void walk_lat_kernel(const IndexDev ix, const W
             });
             __builtin_amdgcn_wave_barrier();
 
-            // ---- 3. similarities of every candidate: 4 rows per pass, PBL passes in flight ---------------------------------
-            // No lane is ever masked off: a lane group without a candidate re-reads the block's first row and a lane past the
-            // row's last chunk re-reads that chunk against a zero query chunk (both dropped / worth 0) — every predicated load
-            // was three scalar instructions of exec bookkeeping, 40 % of this kernel's instructions were scalar
-            // (profiles/archive/r02_single_batch_latency_walk_sq_counters.txt).
-            for (u32 b0 = 0; b0 < T; b0 += RPL * PBL) {
-                uint4 buf[PBL][CH];
-                float pmag[PBL];
-                u32 ppos[PBL], prow[PBL];
-#pragma unroll
-                for (int p = 0; p < PBL; p++) { // the candidates' rows first: one LDS round trip for the whole block
-                    if (b0 + (u32)(p * RPL) >= T) break; // wave-uniform
-                    const u32 my = b0 + (u32)(p * RPL + grp);
-                    const bool v = my < T;
-                    const u64 e = s_cl[v ? my : b0];
-                    prow[p] = (u32)e;
-                    ppos[p] = v ? (u32)(e >> 32) : 0xFFFFFFFFu;
-                }
-#pragma unroll
-                for (int p = 0; p < PBL; p++) {
-                    if (b0 + (u32)(p * RPL) >= T) break; // wave-uniform
-                    pmag[p] = ix.mags[prow[p]];
-                    const uint8_t *rp = ix.codes + (u64)prow[p] * ix.row_stride;
-#pragma unroll
-                    for (int c = 0; c < CH; c++) {
-                        u32 chunk = (u32)lig + (u32)c * (u32)GL;
-                        if (c == CH - 1) chunk = chunk < ix.nchunks ? chunk : ix.nchunks - 1u; // only the last round of chunks can overshoot
-                        buf[p][c] = *(const uint4 *)(rp + (u64)chunk * 16);
-                    }
-                }
-#pragma unroll
-                for (int p = 0; p < PBL; p++) {
-                    if (b0 + (u32)(p * RPL) >= T) break; // wave-uniform
-                    u32 part[CH]; // one chain per chunk: independent dot4 chains interleave instead of waiting on each other
-#pragma unroll
-                    for (int c = 0; c < CH; c++) part[c] = chunk_dot<ENG>(qreg[c], buf[p][c], 0u);
-                    u32 acc = part[0];
-#pragma unroll
-                    for (int c = 1; c < CH; c++) acc += part[c];
-                    acc = group_reduce_add_u32(acc, GL);
-                    const float dotf = (float)acc; // integer dot `as f32` (RNE)
-                    float sim = dotf;
-                    bool bad = false;
-                    if (metric == 0u) { // cosine_similarity_from_dot_product (cosine.rs:223-235)
-                        const float den = __fmul_rn(qmag, pmag[p]);
-                        bad = den == 0.0f;
-                        sim = __fdiv_rn(dotf, den);
-                    }
-                    if (lig == 0 && ppos[p] != 0xFFFFFFFFu) s_spec[ppos[p]] = (u64)metric_key(metric, sim) | (bad ? (1ull << 32) : 0ull);
-                }
-            }
+            // ---- 3. similarities of every candidate: 4 rows per pass, PBL passes in flight, no lane ever masked off ----------
+            spec_row_dots<ENG, CH, GL, PBL>(s_cl, s_spec, T, qreg, ix, qmag, lig, grp);
             if (PREFETCH_ADJ) {
 #pragma unroll
                 for (int i = 0; i < 2 * LAL; i++) warm ^= wv[i];
@@ -280,28 +200,15 @@ __global__ __launch_bounds__(64) void walk_lat_kernel(const IndexDev ix, const W
 
                     const u32 nb_vec = av[wi], nb_node = an[wi];
                     const bool valid = nb_vec != ROW_EMPTY;
-                    // PerformantFixedSet: bucket=(id>>6)&(M-1), bit=id&63  <=> linear bit id & (64M-1)
-                    const u32 id = nb_vec == N ? COS_ROOT_ID : nb_vec * ix.id_stride;
-                    const u32 bit = id & bitmask;
+                    const u32 bit = vis_bit_of(nb_vec, N, ix.id_stride, bitmask);
                     const u32 word = bit >> 5, msk = 1u << (bit & 31);
                     const bool pre = valid && (s_vis[word] & msk);
                     const bool cand = valid && !pre;
                     if (__any(cand)) { // else nothing new: the next window entry is certainly the next pop
                         u32 old = 0;
                         if (cand) old = atomicOr(&s_vis[word], msk);
-                        const bool lost = cand && (old & msk);
-                        bool win = cand && !lost;
-                        u64 lostmask = __ballot(lost);
-                        // two slots of this expansion alias the same residue: the LOWER slot wins (sequential scan order)
-                        while (lostmask) {
-                            const int l = __ffsll((long long)lostmask) - 1;
-                            const u32 b = readlane_u32(bit, l);
-                            const u64 g = __ballot(cand && bit == b);
-                            const int w = __ffsll((long long)g) - 1;
-                            if (cand && bit == b) win = (lane == w);
-                            lostmask &= ~g;
-                        }
-                        u64 m = __ballot(win);
+                        u64 m = vis_alias_winners(__ballot(cand), bit, __ballot(cand && (old & msk)));
+                        const bool win = __builtin_amdgcn_inverse_ballot_w64(m);
                         n_evals += (u64)__popcll(m);
                         if (__any(win && (sp_all >> 32) != 0ull)) failed = true; // zero denominator -> CalculationError
                         else {
@@ -334,33 +241,9 @@ __global__ __launch_bounds__(64) void walk_lat_kernel(const IndexDev ix, const W
         // keep the best `keep`, sorted descending (vector_store.rs:1194-1201)
         __builtin_amdgcn_wave_barrier();
         u64 rk[R];
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            const u32 e = (u32)lane * R + r;
-            rk[r] = e < npop ? s_res[e] : 0ull;
-        }
-        bitonic_sort_desc<R>(rk, lane);
-        u32 cnt = npop < wa.keep ? npop : wa.keep;
-        if (npop == 0) { // only if ef == 0: the entry node's own distance (vector_store.rs:329-380)
-            const u32 erow = lv.node_vec ? lv.node_vec[entry] : entry;
-            float s0;
-            if (!single_distance(erow, s0)) { status = COS_ERR_CALCULATION; break; }
-            rk[0] = lane == 0 ? pack_key(metric_key(metric, s0), entry) : 0ull;
-            cnt = 1;
-        }
-        const u64 obase = ((u64)qi * (L + 1) + out_slot) * wa.keep;
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            const u32 e = (u32)lane * R + r;
-            if (e < cnt) {
-                const u32 nd = (u32)rk[r];
-                const u32 vrow = lv.node_vec ? lv.node_vec[nd] : nd;
-                wa.out_ids[obase + e] = vrow == N ? COS_ROOT_ID : vrow * ix.id_stride;
-                wa.out_sims[obase + e] = metric_key_inv(metric, (u32)(rk[r] >> 32));
-                if (wa.out_nodes) wa.out_nodes[obase + e] = nd;
-            }
-        }
-        if (lane == 0) wa.out_counts[(u64)qi * (L + 1) + out_slot] = cnt;
+        sort_popped_list<R>(rk, s_res, npop, lane);
+        // npop >= 1: walk_lat_applicable refuses ef == 0, and with ef >= 1 the first round pops the start node
+        write_level_list<R>(rk, npop < wa.keep ? npop : wa.keep, ix, lv, wa, qi, out_slot, lane);
         if (level > 0) { // descend through the best hit's child link (vector_store.rs:382-385)
             const u32 best = (u32)readlane_u64(rk[0], 0);
             entry = lv.child[best];
@@ -370,18 +253,12 @@ __global__ __launch_bounds__(64) void walk_lat_kernel(const IndexDev ix, const W
     if (warm == 0x9E3779B9u && wa.keep == 0xFFFFFFFFu) wa.out_status[qi] = (int32_t)warm; // keep is 100 / 64: never true, but not provably — keeps the warm-up loads alive
     if (lane == 0) {
         wa.out_status[qi] = status;
-        if (wa.out_stats) {
-            wa.out_stats[(u64)qi * 4 + 0] = n_evals;
-            wa.out_stats[(u64)qi * 4 + 1] = n_exp;
-            wa.out_stats[(u64)qi * 4 + 2] = adj_bytes;
-            wa.out_stats[(u64)qi * 4 + 3] = n_rounds;
-        }
+        write_walk_stats(wa.out_stats, qi, n_evals, n_exp, adj_bytes, n_rounds);
     }
 }
 
 size_t walk_lat_smem_bytes(const IndexDev &ix, u32 ef) {
-    const u32 Mmax = ix.lv[0].M > ix.lv[ix.num_layers].M ? ix.lv[0].M : ix.lv[ix.num_layers].M;
-    return (size_t)LAL * 64 * 8 * 2 + (size_t)ef * 8 + (size_t)Mmax * 8 + 16;
+    return (size_t)LAL * 64 * 8 * 2 + (size_t)ef * 8 + (size_t)walk_mmax(ix) * 8 + 16;
 }
 
 template <int ENG, int CH>
@@ -415,14 +292,7 @@ hipError_t launch_lat_ch(const IndexDev &ix, const WalkArgs &wa, u32 ch, u32 la,
 namespace cosdev {
 
 // which launches take the latency kernel: reference filter, u8 / quaternary codes of <= 64 chunks, ef <= 256, at most max_B queries
-bool walk_lat_applicable(int eng, const IndexDev &ix, const WalkArgs &wa, u32 max_B) {
-    if (max_B == 0 || wa.B > max_B) return false;
-    if (ix.visited_mode != 0) return false;
-    if (eng != ENG_U8 && eng != ENG_Q2) return false;
-    if (ix.nchunks == 0 || ix.nchunks > (u32)(4 * GL)) return false;
-    if (wa.ef == 0 || wa.ef > 256) return false;
-    return true;
-}
+bool walk_lat_applicable(int eng, const IndexDev &ix, const WalkArgs &wa, u32 max_B) { return walk_latency_domain(eng, ix, wa, max_B); }
 
 hipError_t launch_walk_lat(int eng, const IndexDev &ix, const WalkArgs &wa, hipStream_t st) {
     // window size: 4 (profiles/archive/r02_latency_walk_sweep_first_version_window4_vs_8.jsonl: an 8-entry window needs 24 % fewer rounds but only 3.9

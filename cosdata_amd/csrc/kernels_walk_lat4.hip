@@ -27,20 +27,14 @@
 
 #include "engine_types.h"
 #include "tuning.h"
-#include "dot_engines.h"
+#include "walk_common.h"
 
 using namespace cosdev;
-
-#define COS_OK 0
-#define COS_ERR_CALCULATION 2
-#define COS_QUERY_ID 0xFFFFFFFEu
-#define COS_ROOT_ID 0xFFFFFFFFu
 
 namespace {
 
 constexpr int NW = 4;   // waves per query
-constexpr int GL4 = 16; // lanes per code row
-constexpr int RPL4 = 64 / GL4;
+constexpr int GL4 = LAT_ROW_LANES; // lanes per code row (4 rows per wave pass)
 constexpr int PBL4 = 8; // passes in flight before the dots are consumed (32 rows per wave)
 constexpr u32 FREE = 0xFFFFFFFFu;
 
@@ -53,7 +47,7 @@ __global__ __launch_bounds__(256) void walk_lat4_kernel(const IndexDev ix, const
     const u32 qi = blockIdx.x;
     if (qi >= wa.B) return;
 
-    const u32 Mmax = ix.lv[0].M > ix.lv[ix.num_layers].M ? ix.lv[0].M : ix.lv[ix.num_layers].M;
+    const u32 Mmax = walk_mmax(ix);
     u64 *s_pool, *s_res, *s_win, *s_cl, *s_spec;
     u32 *s_vis, *s_first, *s_flag, *s_misc;
     {
@@ -96,25 +90,10 @@ __global__ __launch_bounds__(256) void walk_lat4_kernel(const IndexDev ix, const
 
     // similarity of ONE row, computed by lane group 0 of the calling wave; result in every lane of that wave
     auto single_distance = [&](u32 row, float &sim_out) -> bool {
-        u32 acc = 0;
-        if (grp == 0) {
-#pragma unroll
-            for (int c = 0; c < CH; c++) {
-                const u32 chunk = (u32)lig + (u32)c * (u32)GL4;
-                if (chunk < ix.nchunks) acc = chunk_dot<ENG>(qreg[c], *(const uint4 *)(ix.codes + (u64)row * ix.row_stride + (u64)chunk * 16), acc);
-            }
-        }
-        acc = group_reduce_add_u32(acc, GL4);
-        acc = readlane_u32(acc, 0);
-        const float dotf = (float)acc; // integer dot `as f32` (RNE)
-        if (metric == 0u) {            // cosine_similarity_from_dot_product (cosine.rs:223-235)
-            const float den = uniform_f32(__fmul_rn(qmag, ix.mags[row]));
-            if (den == 0.0f) return false;
-            sim_out = __fdiv_rn(dotf, den);
-        } else {
-            sim_out = dotf; // DotProductDistance (dotproduct.rs:14-64)
-        }
-        return true;
+        const u32 acc = int_row_dot_group0<ENG, CH>(qreg, ix.codes + (u64)row * ix.row_stride, ix.nchunks, lig, grp, GL4);
+        bool bad;
+        sim_out = cosine_or_dot(metric, (float)acc, qmag, uniform_f32(ix.mags[row]), bad); // integer dot `as f32` (RNE)
+        return !bad;
     };
 
     for (int level = (int)L; level >= 0; level--) {
@@ -131,7 +110,7 @@ __global__ __launch_bounds__(256) void walk_lat4_kernel(const IndexDev ix, const
         const float *tabm = wa.tab_mags + wa.tab_col0[level];
 
         // fresh visited filter, pre-seeded with the query / new-node id (vector_store.rs:266-271, :807)
-        for (u32 w = tid; w < 2 * M; w += 256) s_vis[w] = 0;
+        vis_clear<256>(s_vis, M, tid);
         __syncthreads();
         u32 npool = 0, npop = 0;
         if (wave == 0) { // start node (vector_store.rs:1144-1148)
@@ -139,21 +118,14 @@ __global__ __launch_bounds__(256) void walk_lat4_kernel(const IndexDev ix, const
             float s0 = 0.0f;
             bool ok;
             if (tab_level) {
-                s0 = uniform_f32(tabq[entry]);
-                ok = true;
-                if (metric == 0u) {
-                    const float den = uniform_f32(__fmul_rn(qmag, tabm[entry]));
-                    ok = den != 0.0f;
-                    s0 = __fdiv_rn(s0, den); // (0 / 0 when !ok: never used)
-                }
+                bool bad;
+                s0 = cosine_or_dot(metric, uniform_f32(tabq[entry]), qmag, uniform_f32(tabm[entry]), bad);
+                ok = !bad;
             } else
                 ok = single_distance(erow, s0);
             if (lane == 0) {
-                const u32 b = self_id & bitmask;
-                s_vis[b >> 5] |= 1u << (b & 31);
-                const u32 eid = erow == N ? COS_ROOT_ID : erow * ix.id_stride;
-                const u32 b2 = eid & bitmask;
-                s_vis[b2 >> 5] |= 1u << (b2 & 31);
+                vis_set_bit(s_vis, self_id & bitmask);
+                vis_set_bit(s_vis, vis_bit_of(erow, N, ix.id_stride, bitmask));
                 s_pool[0] = pack_key(metric_key(metric, s0), entry);
                 s_misc[1] = ok ? 0u : 1u;
             }
@@ -196,9 +168,7 @@ __global__ __launch_bounds__(256) void walk_lat4_kernel(const IndexDev ix, const
                 const bool live = e < kwin && (u32)lane < slots;
                 av[i] = live ? av[i] : ROW_EMPTY;
                 an[i] = live ? (level == 0 ? av[i] : an[i]) : ROW_EMPTY;
-                // PerformantFixedSet: bucket=(id>>6)&(M-1), bit=id&63  <=> linear bit id & (64M-1)
-                const u32 id = av[i] == N ? COS_ROOT_ID : av[i] * ix.id_stride;
-                bitv[i] = id & bitmask;
+                bitv[i] = vis_bit_of(av[i], N, ix.id_stride, bitmask);
                 const u32 vword = s_vis[bitv[i] >> 5];
                 cnd[i] = av[i] != ROW_EMPTY && !(vword & (1u << (bitv[i] & 31u)));
                 if (cnd[i]) atomicMin(&s_first[bitv[i]], e * 64u + (u32)lane);
@@ -213,65 +183,14 @@ __global__ __launch_bounds__(256) void walk_lat4_kernel(const IndexDev ix, const
                 for (int i = 0; i < E; i++) {
                     float sim = 0.0f, magv = 1.0f;
                     if (cnd[i]) { sim = tabq[an[i]]; magv = tabm[an[i]]; }
-                    bool bad = false;
-                    if (metric == 0u) {
-                        const float den = __fmul_rn(qmag, magv);
-                        bad = den == 0.0f;
-                        sim = __fdiv_rn(sim, den);
-                    }
+                    bool bad;
+                    sim = cosine_or_dot(metric, sim, qmag, magv, bad);
                     if (cnd[i]) my_spec[i * 64 + lane] = (u64)metric_key(metric, sim) | (bad ? (1ull << 32) : 0ull);
                 }
                 T = 0; // nothing left for the row loop below
             }
-            // similarities of this wave's candidates: 4 rows per pass, PBL4 passes in flight; no lane is ever masked off (see
-            // kernels_walk_lat.hip: a lane group without a candidate re-reads the block's first row, a lane past the row's last
-            // chunk re-reads that chunk against a zero query chunk)
-            for (u32 b0 = 0; b0 < T; b0 += RPL4 * PBL4) {
-                uint4 buf[PBL4][CH];
-                float pmag[PBL4];
-                u32 ppos[PBL4], prow[PBL4];
-#pragma unroll
-                for (int p = 0; p < PBL4; p++) {
-                    if (b0 + (u32)(p * RPL4) >= T) break; // wave-uniform
-                    const u32 my = b0 + (u32)(p * RPL4 + grp);
-                    const bool v = my < T;
-                    const u64 ce = my_cl[v ? my : b0];
-                    prow[p] = (u32)ce;
-                    ppos[p] = v ? (u32)(ce >> 32) : 0xFFFFFFFFu;
-                }
-#pragma unroll
-                for (int p = 0; p < PBL4; p++) {
-                    if (b0 + (u32)(p * RPL4) >= T) break; // wave-uniform
-                    pmag[p] = ix.mags[prow[p]];
-                    const uint8_t *rp = ix.codes + (u64)prow[p] * ix.row_stride;
-#pragma unroll
-                    for (int c = 0; c < CH; c++) {
-                        u32 chunk = (u32)lig + (u32)c * (u32)GL4;
-                        if (c == CH - 1) chunk = chunk < ix.nchunks ? chunk : ix.nchunks - 1u;
-                        buf[p][c] = *(const uint4 *)(rp + (u64)chunk * 16);
-                    }
-                }
-#pragma unroll
-                for (int p = 0; p < PBL4; p++) {
-                    if (b0 + (u32)(p * RPL4) >= T) break; // wave-uniform
-                    u32 part[CH];
-#pragma unroll
-                    for (int c = 0; c < CH; c++) part[c] = chunk_dot<ENG>(qreg[c], buf[p][c], 0u);
-                    u32 acc = part[0];
-#pragma unroll
-                    for (int c = 1; c < CH; c++) acc += part[c];
-                    acc = group_reduce_add_u32(acc, GL4);
-                    const float dotf = (float)acc; // integer dot `as f32` (RNE)
-                    float sim = dotf;
-                    bool bad = false;
-                    if (metric == 0u) { // cosine_similarity_from_dot_product (cosine.rs:223-235)
-                        const float den = __fmul_rn(qmag, pmag[p]);
-                        bad = den == 0.0f;
-                        sim = __fdiv_rn(dotf, den);
-                    }
-                    if (lig == 0 && ppos[p] != 0xFFFFFFFFu) my_spec[ppos[p]] = (u64)metric_key(metric, sim) | (bad ? (1ull << 32) : 0ull);
-                }
-            }
+            // similarities of this wave's candidates: 4 rows per pass, PBL4 passes in flight, no lane ever masked off
+            spec_row_dots<ENG, CH, GL4, PBL4>(my_cl, my_spec, T, qreg, ix, qmag, lig, grp);
             __syncthreads(); // B1: every claim of the round is in s_first (and this wave's similarities are in my_spec)
 
             // ---- B. winners: first occurrence per filter bit in (entry, slot) order; stale / fail flags per entry ----------------------
@@ -415,59 +334,25 @@ __global__ __launch_bounds__(256) void walk_lat4_kernel(const IndexDev ix, const
         __syncthreads();
         if (wave == 0) {
             u64 rk[R];
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                const u32 e = (u32)lane * R + r;
-                rk[r] = e < npop ? s_res[e] : 0ull;
-            }
-            bitonic_sort_desc<R>(rk, lane);
-            u32 cnt = npop < wa.keep ? npop : wa.keep;
-            bool ok = true;
-            if (npop == 0) { // only if ef == 0: the entry node's own distance (vector_store.rs:329-380)
-                const u32 erow = lv.node_vec ? lv.node_vec[entry] : entry;
-                float s0 = 0.0f;
-                ok = single_distance(erow, s0);
-                rk[0] = lane == 0 ? pack_key(metric_key(metric, s0), entry) : 0ull;
-                cnt = 1;
-            }
-            const u64 obase = ((u64)qi * (L + 1) + out_slot) * wa.keep;
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                const u32 e = (u32)lane * R + r;
-                if (ok && e < cnt) {
-                    const u32 nd = (u32)rk[r];
-                    const u32 vrow = lv.node_vec ? lv.node_vec[nd] : nd;
-                    wa.out_ids[obase + e] = vrow == N ? COS_ROOT_ID : vrow * ix.id_stride;
-                    wa.out_sims[obase + e] = metric_key_inv(metric, (u32)(rk[r] >> 32));
-                    if (wa.out_nodes) wa.out_nodes[obase + e] = nd;
-                }
-            }
-            if (lane == 0) {
-                wa.out_counts[(u64)qi * (L + 1) + out_slot] = ok ? cnt : 0u;
-                s_misc[1] = ok ? 0u : 1u;
-                if (level > 0 && ok) s_misc[0] = lv.child[(u32)readlane_u64(rk[0], 0)]; // descend through the best hit's child link (vector_store.rs:382-385)
-            }
+            sort_popped_list<R>(rk, s_res, npop, lane);
+            // npop >= 1: walk_lat4_applicable refuses ef == 0, and with ef >= 1 the first round pops the start node
+            write_level_list<R>(rk, npop < wa.keep ? npop : wa.keep, ix, lv, wa, qi, out_slot, lane);
+            if (lane == 0 && level > 0) s_misc[0] = lv.child[(u32)readlane_u64(rk[0], 0)]; // descend through the best hit's child link (vector_store.rs:382-385)
         }
         __syncthreads();
-        if (uniform_u32(s_misc[1])) { status = COS_ERR_CALCULATION; break; }
         if (level > 0) entry = uniform_u32(s_misc[0]);
         __syncthreads(); // s_misc is rewritten by the next level's start node
     }
 
     if (tid == 0) {
         wa.out_status[qi] = status;
-        if (wa.out_stats) {
-            wa.out_stats[(u64)qi * 4 + 0] = n_evals;
-            wa.out_stats[(u64)qi * 4 + 1] = n_exp;
-            wa.out_stats[(u64)qi * 4 + 2] = adj_bytes;
-            wa.out_stats[(u64)qi * 4 + 3] = n_rounds;
-        }
+        write_walk_stats(wa.out_stats, qi, n_evals, n_exp, adj_bytes, n_rounds);
     }
 }
 
 template <int E>
 size_t walk_lat4_smem_bytes(const IndexDev &ix, u32 ef, u32 cap) {
-    const u32 Mmax = ix.lv[0].M > ix.lv[ix.num_layers].M ? ix.lv[0].M : ix.lv[ix.num_layers].M;
+    const u32 Mmax = walk_mmax(ix);
     const size_t la = (size_t)NW * E;
     return (size_t)2 * cap * 8 + (size_t)ef * 8 + la * 64 * 8 + (size_t)NW * E * 64 * 8 * 2 + (size_t)64 * Mmax * 4 + (size_t)2 * Mmax * 4 + la * 4 + 16;
 }
@@ -497,14 +382,8 @@ namespace cosdev {
 
 // same launches as the one-wave latency kernel (walk_lat_applicable), up to max_B queries
 bool walk_lat4_applicable(int eng, const IndexDev &ix, const WalkArgs &wa, u32 max_B) {
-    if (max_B == 0 || wa.B > max_B) return false;
-    if (ix.visited_mode != 0) return false;
-    if (eng != ENG_U8 && eng != ENG_Q2) return false;
-    if (ix.nchunks == 0 || ix.nchunks > (u32)(4 * GL4)) return false;
-    if (wa.ef == 0 || wa.ef > 256) return false;
-    const u32 Mmax = ix.lv[0].M > ix.lv[ix.num_layers].M ? ix.lv[0].M : ix.lv[ix.num_layers].M;
-    if (Mmax > 64) return false; // s_first is sized 64 * Mmax words: keep the workgroup's LDS small
-    return true;
+    if (!walk_latency_domain(eng, ix, wa, max_B)) return false;
+    return walk_mmax(ix) <= 64; // s_first is sized 64 * Mmax words: keep the workgroup's LDS small
 }
 
 hipError_t launch_walk_lat4(int eng, const IndexDev &ix, const WalkArgs &wa, hipStream_t st) {

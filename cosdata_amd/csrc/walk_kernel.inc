@@ -1,9 +1,5 @@
 // walk_kernel.inc — the HNSW walk kernel (ann_search / traverse_find_nearest, vector_store.rs:256-402, 1112-1204), textually included
-// by kernels_walk.hip (COS_WALK_KERNEL_NAME = walk_kernel: every shipped instantiation).  Round 4 included it a second time with
-// COS_WALK_SPEC defined — a variant that gathered the table values of 2 / 4 / 8 window entries ahead of their consumption; round 5
-// measured it (parity green; upper range of c2 2.87-3.67 ms against 2.80 ms for this kernel, one client batch 0.79-0.82 ms against
-// 0.765: profiles/r05_candidates_walk_spec.txt) and removed it: the table levels are bound by instruction issue and LDS round
-// trips inside an expansion, not by the dependent table gather.
+// by kernels_walk.hip; the rules it shares with the other walk kernels are in walk_common.h.
 constexpr int PB = 4; // code rows in flight per lane group before the dots are consumed
 constexpr int LA = 4; // lookahead window: adjacency rows prefetched per round
 // G = 64 path: code rows in flight per wave = template parameter PB64.  An expansion discovers ~7 new neighbours on average:
@@ -29,7 +25,7 @@ struct WalkSmem {
 };
 
 template <int ENG, int CH, int R, bool G64, bool EXACT, int PB64 = 4>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH >= 3 ? (R <= 4 ? (CH == 3 ? 4 : 3) : (CH == 3 ? 3 : 2)) : (R == 1 ? ((ENG == ENG_U8 && CH == 1 && G64 && !EXACT) ? 7 : 6) : (R <= 4 ? 5 : 4)), 8))) void COS_WALK_KERNEL_NAME(const IndexDev ix, const WalkArgs wa) {
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH >= 3 ? (R <= 4 ? (CH == 3 ? 4 : 3) : (CH == 3 ? 3 : 2)) : (R == 1 ? ((ENG == ENG_U8 && CH == 1 && G64 && !EXACT) ? 7 : 6) : (R <= 4 ? 5 : 4)), 8))) void walk_kernel(const IndexDev ix, const WalkArgs wa) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int lane = threadIdx.x;
     if (blockIdx.x >= wa.B) return;
@@ -114,17 +110,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH >= 3 ? (R
     auto single_distance = [&](u32 row, float &sim_out) -> bool {
         float dotf;
         if constexpr (!FLOAT_ENG) {
-            u32 acc = 0;
-            if (grp == 0) {
-#pragma unroll
-                for (int c = 0; c < CH; c++) {
-                    u32 chunk = (u32)lig + (u32)c * (u32)G;
-                    if (chunk < ix.nchunks) acc = chunk_dot<ENG>(qreg[c], *(const uint4 *)(ix.codes + (u64)row * ix.row_stride + (u64)chunk * 16), acc);
-                }
-            }
-            acc = group_reduce_add_u32(acc, G);
-            acc = readlane_u32(acc, 0);
-            dotf = (float)acc; // integer dot `as f32` (RNE)
+            dotf = (float)int_row_dot_group0<ENG, CH>(qreg, ix.codes + (u64)row * ix.row_stride, ix.nchunks, lig, grp, G); // integer dot `as f32` (RNE)
         } else if constexpr (ENG == ENG_F16) {
             float d = f16_lane_dot(ix.codes + (u64)row * ix.row_stride, sm.qf, ix.dim);
             dotf = __uint_as_float(readlane_u32(__float_as_uint(d), 0));
@@ -132,14 +118,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH >= 3 ? (R
             float d = f32_oct_dot((const float *)(ix.codes + (u64)row * ix.row_stride), sm.qf, ix.dim, lane & 7);
             dotf = __uint_as_float(readlane_u32(__float_as_uint(d), 0));
         }
-        if (metric == 0u) { // cosine_similarity_from_dot_product (cosine.rs:223-235)
-            const float den = uniform_f32(__fmul_rn(qmag, ix.mags[row]));
-            if (den == 0.0f) return false;
-            sim_out = __fdiv_rn(dotf, den);
-        } else {
-            sim_out = dotf; // DotProductDistance (dotproduct.rs:14-64)
-        }
-        return true;
+        bool bad;
+        sim_out = cosine_or_dot(metric, dotf, qmag, uniform_f32(ix.mags[row]), bad);
+        return !bad;
     };
 
     for (int level = level_first; level >= level_last; level--) {
@@ -156,11 +137,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH >= 3 ? (R
 
         // fresh visited filter, pre-seeded with the query / new-node id (vector_store.rs:266-271, :807)
         if (!exact) {
-            for (u32 w = lane; w < 2 * M; w += 64) sm.vis[w] = 0;
-            if (lane == 0 && wa.no_self_seed == 0u) {
-                u32 b = self_id & bitmask;
-                sm.vis[b >> 5] |= 1u << (b & 31);
-            }
+            vis_clear<64>(sm.vis, M, lane);
+            if (lane == 0 && wa.no_self_seed == 0u) vis_set_bit(sm.vis, self_id & bitmask);
         }
 
         Pool<R> pool;
@@ -173,16 +151,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH >= 3 ? (R
             const u32 erow = uniform_u32(lv.node_vec ? lv.node_vec[entry] : entry);
             float s0;
             if (tab_level) { // the table holds the integer dot `as f32`: the same product and quotient as single_distance
-                s0 = uniform_f32(tabq[entry]);
-                if (metric == 0u) {
-                    const float den = uniform_f32(__fmul_rn(qmag, tabm[entry]));
-                    if (den == 0.0f) { status = COS_ERR_CALCULATION; break; }
-                    s0 = __fdiv_rn(s0, den);
-                }
+                bool bad;
+                s0 = cosine_or_dot(metric, uniform_f32(tabq[entry]), qmag, uniform_f32(tabm[entry]), bad);
+                if (bad) { status = COS_ERR_CALCULATION; break; }
             } else if (!single_distance(erow, s0)) { status = COS_ERR_CALCULATION; break; }
-            const u32 eid = erow == N ? COS_ROOT_ID : erow * ix.id_stride;
             if (lane == 0) {
-                if (!exact) { u32 b = eid & bitmask; sm.vis[b >> 5] |= 1u << (b & 31); }
+                if (!exact) vis_set_bit(sm.vis, vis_bit_of(erow, N, ix.id_stride, bitmask));
                 else {
                     atomicOr(&vis[entry >> 5], 1u << (entry & 31));
                     vlog[0] = entry >> 5;
@@ -270,14 +244,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH >= 3 ? (R
                 const u64 vmask = ballot64(nb_vec != ROW_EMPTY) & slotmask;
                 u64 wmask; // the expansion's winners: unvisited neighbours, as a lane set
                 if (!exact) {
-                    // PerformantFixedSet: bucket=(id>>6)&(M-1), bit=id&63  <=> linear bit id & (64M-1)
-                    u32 id = nb_vec;
+                    u32 bit = vis_bit_of(nb_vec, N, 1u, bitmask);
                     if (ix.id_stride != 1u) { // wave-uniform branch (the empty asm keeps it one): v_mul_lo_u32 is a quarter-rate instruction
                         asm volatile("");
-                        id = nb_vec * ix.id_stride;
+                        bit = vis_bit_of(nb_vec, N, ix.id_stride, bitmask);
                     }
-                    id = nb_vec == N ? COS_ROOT_ID : id;
-                    const u32 bit = id & bitmask;
                     const u32 word = bit >> 5, msk = 1u << (bit & 31);
                     u32 seen = sm.vis[word]; // unpredicated (an empty slot's word is in range too); the asm keeps the load out of an `if (valid)`
                     asm volatile("" : "+v"(seen));
@@ -286,15 +257,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH >= 3 ? (R
                     if (cmask) {
                     u32 old = 0;
                     if (__builtin_amdgcn_inverse_ballot_w64(cmask)) old = atomicOr(&sm.vis[word], msk);
-                    u64 lostmask = cmask & ballot64((old & msk) != 0u);
-                    wmask = cmask & ~lostmask;
-                    // two slots of this expansion alias the same residue: the LOWER slot wins (sequential scan order)
-                    while (lostmask) {
-                        const int l = __ffsll((long long)lostmask) - 1;
-                        const u64 g = cmask & ballot64(bit == readlane_u32(bit, l));
-                        wmask = (wmask & ~g) | (g & (0ull - g)); // of the slots that share the residue only the lowest stays
-                        lostmask &= ~g;
-                    }
+                    wmask = vis_alias_winners(cmask, bit, cmask & ballot64((old & msk) != 0u));
                     }
                 } else {
                     u32 w = 0;
@@ -399,14 +362,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH >= 3 ? (R
                     // fetched or dotted.
                     float simv = 0.0f, magv = 1.0f;
                     if (win) { simv = tabq[nb_node]; magv = tabm[nb_node]; }
-                    u32 bad = 0;
-                    if (metric_t == 0u) {
-                        const float den = __fmul_rn(qmag, magv);
-                        bad = (wmask & ballot64(den == 0.0f)) != 0ull;
-                        // u8 codes: both norms are roots of integer sums (>= 1 when not 0): the quotient needs no scaling
-                        simv = ENG == ENG_U8 ? div_rn_unscaled(simv, den) : __fdiv_rn(simv, den);
-                    }
-                    if (bad) failed = 1;
+                    bool badl;
+                    // u8 codes: both norms are roots of integer sums (>= 1 when not 0): the quotient needs no scaling
+                    simv = cosine_or_dot<ENG == ENG_U8>(metric_t, simv, qmag, magv, badl);
+                    if (wmask & ballot64(badl)) failed = 1;
                     else if constexpr (R <= 4) {
                         if (merge_min != 0u) commit_merge(wmask, metric_key(metric_t, simv), nb_node);
                         else commit(wmask, metric_key(metric_t, simv), nb_node);
@@ -477,13 +436,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH >= 3 ? (R
                         const float magv = __uint_as_float((u32)__builtin_amdgcn_ds_bpermute((int)lsel, (int)__float_as_uint(magw)));
                         const u32 nodev = (u32)__builtin_amdgcn_ds_bpermute((int)lsel, (int)nb_node);
                         const float dotv = (float)tot; // integer dot `as f32` (RNE)
-                        // one vector epilogue for the whole block: cosine_similarity_from_dot_product (cosine.rs:223-235)
-                        float sim = dotv;
-                        if (metric == 0u) {
-                            const float den = __fmul_rn(qmag, magv);
-                            if (leadmask & ballot64(den == 0.0f)) { failed = 1; break; }
-                            sim = ENG == ENG_U8 ? div_rn_unscaled(dotv, den) : __fdiv_rn(dotv, den);
-                        }
+                        // one vector epilogue for the whole block
+                        bool badl;
+                        const float sim = cosine_or_dot<ENG == ENG_U8>(metric, dotv, qmag, magv, badl);
+                        if (leadmask & ballot64(badl)) { failed = 1; break; }
                         commit(leadmask, metric_key(metric, sim), nodev);
                     }
                 } else {
@@ -544,12 +500,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH >= 3 ? (R
                         // this pass's rows in winner order: the first lane of every group holds its row's key
                         const int mine = base + p * RP + grp;
                         const bool leadg = lig == 0 && mine < W;
-                        float sim = dotf;
-                        if (metric == 0u) {
-                            const float den = __fmul_rn(qmag, pmag[p]);
-                            if (ballot64(mine < W && den == 0.0f)) { failed = 1; break; }
-                            sim = __fdiv_rn(dotf, den);
-                        }
+                        bool badl;
+                        const float sim = cosine_or_dot(metric, dotf, qmag, pmag[p], badl);
+                        if (ballot64(mine < W && badl)) { failed = 1; break; }
                         const u32 mynode = leadg ? sm.wl_node[mine] : 0u;
                         commit(ballot64(leadg), metric_key(metric, sim), mynode);
                     }
@@ -621,7 +574,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH >= 3 ? (R
             rk[0] = lane == 0 ? pack_key(metric_key(metric, s0), entry) : 0ull;
             cnt = 1;
         }
-        const u64 obase = ((u64)qi * (L + 1) + out_slot) * wa.keep;
+        // write_level_list (walk_common.h), written out: through the helper walk_kernel<ENG_U8, 1, 4, false, false> takes 74 VGPRs
+        // instead of 71 and loses its seventh wave per SIMD
+        const u64 obase = level_list_base(ix, wa, qi, out_slot);
 #pragma unroll
         for (int r = 0; r < R; r++) {
             const u32 e = (u32)lane * R + r;

@@ -127,6 +127,38 @@ def test_search_clustered_default_params():
     _assert_same_search(oix, dix, Q, 10)
 
 
+def test_rows_wider_than_64_go_to_the_one_wave_latency_kernel():
+    """neighbour rows of 128 slots: walk_lat4_applicable must decline (its claim table is sized for rows of <= 64) and
+    walk_lat_applicable accept.  Which kernel ran is read off the round count: the knob walk_lat_la = 1 narrows the window of the
+    one-wave kernel alone to one entry, so that kernel, and no other, then issues exactly one round per expansion."""
+    from cosdata_amd import _lib
+    X = H.uniform_corpus(600, 48, seed=7)
+    Q = np.concatenate([H.queries_from(X, 24, seed=3), H.uniform_corpus(8, 48, seed=99)])
+
+    def rounds_per_variant(oix):
+        dix = H.device_index_from_oracle(oix, X)
+        _assert_same_walk(oix, dix, Q)
+        out = {}
+        with _lib.tuning(walk_lat_la=1):
+            for vname, max_b, max_b4, order_min, table in WALK_VARIANTS[:3]:
+                _set_variant(dix, max_b, max_b4, order_min, table)
+                dix.batch_search(Q, 10)
+                st = dix.last_stats()
+                out[vname] = (int(st.reserved), int(st.expansions))
+        _reset_variant(dix)
+        return out
+
+    wide = rounds_per_variant(H.oracle_index(X, O.STORAGE_U8, 0, num_layers=5, ef_construction=64, ef_search=32,
+                                             neighbors_count=128, level0_neighbors_count=128))
+    narrow = rounds_per_variant(H.oracle_index(X, O.STORAGE_U8, 0, num_layers=5, ef_construction=64, ef_search=32))
+    tk, lat, lat4 = (v[0] for v in WALK_VARIANTS[:3])
+    for r in (wide, narrow):
+        assert r[tk][0] < r[tk][1], r          # the throughput kernel pops several window entries per round
+        assert r[lat][0] == r[lat][1], r       # the one-wave kernel under the knob: one
+    assert narrow[lat4][0] < narrow[lat4][1], narrow   # rows of <= 64: the four-wave kernel takes the launch
+    assert wide[lat4] == wide[lat], wide               # rows of 128: it declines, the one-wave kernel runs
+
+
 def test_zero_norm_query_is_calculation_error():
     import cosdata_amd as ca
     X = H.uniform_corpus(500, 96, seed=2)
