@@ -120,6 +120,7 @@ ABI_SYMBOLS = [
     "cos_code_bytes", "cos_sample_values_range", "cos_distance_batch", "cos_bruteforce_topk", "cos_flat_search_batch", "cos_bm25_create", "cos_bm25_destroy",
     "cos_bm25_insert", "cos_bm25_delete", "cos_bm25_stats", "cos_bm25_download",
     "cos_bm25_search_batch", "cos_bm25_search_batch_device", "cos_rrf_fuse_batch", "cos_hybrid_search_batch", "cos_text_process", "cos_text_count_tokens", "cos_bm25_term_frequency", "cos_xxhash32", "cos_stem_english", "cos_sparse_create", "cos_sparse_build_csr", "cos_sparse_create_from_vectors", "cos_sparse_destroy", "cos_sparse_search_batch", "cos_sparse_last_stats", "cos_sparse_layout",
+    "cos_sparse_set_max_candidates", "cos_sparse_max_candidates",
     "cos_sparse_insert", "cos_sparse_delete", "cos_sparse_stats", "cos_sparse_download", "cos_merge_topk_device", "cos_merge_topk_packed_device", "cos_hbm_probe",
     "cos_shardset_unique_id", "cos_shardset_create", "cos_shardset_destroy", "cos_shardset_search_batch", "cos_shardset_exchange_device",
     "cos_tuning_set", "cos_tuning_clear", "cos_tuning_get",
@@ -208,6 +209,8 @@ def lib():
         "cos_sparse_search_batch": [vp, vp, vp, vp, u32, u32, f32, u32, vp, vp, vp],
         "cos_sparse_last_stats": [vp, vp],
         "cos_sparse_layout": [vp, C.POINTER(u32)],
+        "cos_sparse_set_max_candidates": [vp, u32],
+        "cos_sparse_max_candidates": [vp, C.POINTER(u32)],
         "cos_sparse_insert": [vp, u32, vp, vp, vp, C.POINTER(u32)],
         "cos_sparse_delete": [vp, vp, vp, u32, vp, vp, C.POINTER(C.c_uint64)],
         "cos_sparse_stats": [vp, C.POINTER(CosSparseIndexStats)],

@@ -24,7 +24,10 @@ using namespace cosdev;
 
 namespace {
 
-constexpr u32 SEL = 64; // candidates kept per query: top_k * reranking_factor <= 64
+constexpr u32 SEL = 64; // candidates a call keeps per query on the narrow path: top_k * reranking_factor <= 64
+// A call that keeps more runs the wide instantiation R = 2, 4, 8 or 16 (cos_sparse_set_max_candidates): pools, partial results and
+// the finish kernel hold 64 * R keys.  R = 1 is the narrow path; its kernels are not touched by the wide ones.
+constexpr u32 SEL_MAX = 1024;
 
 struct SparseDev {
     const u32 *dims;      // [T]
@@ -77,28 +80,99 @@ struct SCursor { // block-uniform
     bool valid;
 };
 
+// ---- the wide path's merges (R > 1): block-wide bitonic networks over u64 keys in LDS --------------------------------------------
+// Three wave pools of 1024 keys folded into the fourth by single inserts would be 3072 inserts of ~150 wave instructions each, on
+// one wave, per block; a bitonic merge is log2(N) rounds of one compare-exchange per thread and pair.
+// `nseq` bitonic sequences of N keys, sequence j at buf + j * pitch -> each sorted descending.  Ends with a barrier.
+template <u32 N>
+__device__ __forceinline__ void lds_bitonic_merge_desc(u64 *buf, u32 nseq, u32 pitch) {
+    for (u32 stride = N / 2; stride > 0; stride >>= 1) {
+        __syncthreads();
+        for (u32 p = threadIdx.x; p < nseq * (N / 2); p += blockDim.x) {
+            u64 *b = buf + (p / (N / 2)) * pitch;
+            const u32 j = p % (N / 2);
+            const u32 i = ((j & ~(stride - 1u)) << 1) | (j & (stride - 1u)); // the pair (i, i + stride)
+            const u64 x = b[i], y = b[i + stride];
+            if (x < y) { b[i] = y; b[i + stride] = x; }
+        }
+    }
+    __syncthreads();
+}
+// any N keys -> sorted descending (0 = empty sinks to the end).  Ends with a barrier.
+template <u32 N>
+__device__ __forceinline__ void lds_bitonic_sort_desc(u64 *buf) {
+    for (u32 size = 2; size <= N; size <<= 1)
+        for (u32 stride = size >> 1; stride > 0; stride >>= 1) {
+            __syncthreads();
+            for (u32 j = threadIdx.x; j < N / 2; j += blockDim.x) {
+                const u32 i = ((j & ~(stride - 1u)) << 1) | (j & (stride - 1u));
+                const bool desc = (i & size) == 0u;
+                const u64 x = buf[i], y = buf[i + stride];
+                if ((x < y) == desc) { buf[i] = y; buf[i + stride] = x; }
+            }
+        }
+    __syncthreads();
+}
+// best[i] = max(best[i], other[N - 1 - i]) for two descending sequences is a bitonic sequence of the best N keys of both (the
+// first half-cleaner of the merge network); lds_bitonic_merge_desc sorts it.  `other` may be LDS or global memory.
+template <u32 N>
+__device__ __forceinline__ void fold_reversed(u64 *best, const u64 *other) {
+    for (u32 i = threadIdx.x; i < N; i += blockDim.x) {
+        const u64 x = best[i], y = other[N - 1u - i];
+        best[i] = x > y ? x : y;
+    }
+}
+// A block's four wave pools (each sorted descending, blocked layout) -> ONE sorted segment of the block's best 64 * R keys in out[]:
+// the finish kernel then folds `splits` segments per query, not 4 * splits, and part[] stays a quarter of the size.  buf = the
+// accumulator tile, dead after the block's last flush and exactly 4 * 1024 u64: the merge costs no LDS, so no occupancy.
+template <int R>
+__device__ __forceinline__ void block_merge_pools(const Pool<R> &pool, u64 *buf, u64 *__restrict__ out, int wave, int lane) {
+    constexpr u32 N = 64u * R;
+    static_assert(4u * N * 8u <= STILE * 4u, "the four pools are staged in the accumulator tile");
+    __syncthreads(); // every wave is done with the tile
+#pragma unroll
+    for (int r = 0; r < R; r++) buf[(u32)wave * N + (u32)lane * R + r] = pool.e[r];
+    __syncthreads();
+    for (u32 p = threadIdx.x; p < 2u * N; p += blockDim.x) { // pools (0, 1) and (2, 3), as fold_reversed
+        u64 *a = buf + (p / N) * 2u * N;
+        const u32 i = p % N;
+        const u64 x = a[i], y = a[2u * N - 1u - i];
+        a[i] = x > y ? x : y;
+    }
+    lds_bitonic_merge_desc<N>(buf, 2, 2 * N);
+    fold_reversed<N>(buf, buf + 2 * N);
+    lds_bitonic_merge_desc<N>(buf, 1, 0);
+    for (u32 i = threadIdx.x; i < N; i += blockDim.x) out[i] = buf[i];
+}
+
 // grid = B * splits blocks, heaviest query first: block (q, s) owns the tiles s, s + splits, ...; every wave keeps a private pool
-// of the best SEL keys ((similarity + 1) << 32 | id) it has flushed, the block's four pools are merged into part[q][s][64].
+// of the best SEL * R keys ((similarity + 1) << 32 | id) it has flushed, the block's four pools are merged into part[q][s][64 * R].
+// R = 1 is the narrow kernel; R = 2, 4, 8, 16 are the wide instantiations of the unpacked layout.
+template <int R>
 __global__ __launch_bounds__(256) void sparse_tile_kernel(const u32 *__restrict__ m_ids, const uint8_t *__restrict__ m_keys, const STerm *__restrict__ terms,
                                                           const u32 *__restrict__ qt_off, u32 n, const u32 *__restrict__ tile_dir,
-                                                          const u32 *__restrict__ order, u32 splits, u64 *__restrict__ part /*[B][splits][64]*/) {
-    __shared__ u32 acc[STILE + 64]; // [STILE + lane] = the lane's dummy slot for postings that do not count (one per lane: same-address LDS atomics serialise)
+                                                          const u32 *__restrict__ order, u32 splits, u64 *__restrict__ part /*[B][splits][64 * R]*/) {
+    static_assert(R == 1 || R == 2 || R == 4 || R == 8 || R == 16, "narrow or a wide instantiation");
+    __shared__ alignas(R == 1 ? 4 : 16) u32 acc[STILE + 64]; // [STILE + lane] = the lane's dummy slot for postings that do not count (one per lane: same-address LDS atomics serialise)
     __shared__ u32 zflag[STILE / 32];
-    __shared__ u64 wpool[4][SEL];
+    __shared__ u64 wpool[4][SEL]; // (R == 1 only: the wide merge is staged in acc)
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const u32 q = order[blockIdx.x / splits];
     const u32 split = blockIdx.x % splits;
     const u32 t0 = qt_off[q], nt = qt_off[q + 1] - t0;
     const u32 n_tiles = (n + STILE - 1) / STILE;
-    u64 *out = part + ((u64)q * splits + split) * SEL;
+    u64 *out = part + ((u64)q * splits + split) * (SEL * R);
     if (nt == 0 || split >= n_tiles) { // nothing to visit: an empty pool (the finish kernel reads every split)
-        if (threadIdx.x < SEL) out[threadIdx.x] = 0ull;
+        if constexpr (R == 1) {
+            if (threadIdx.x < SEL) out[threadIdx.x] = 0ull;
+        } else
+            for (u32 i = threadIdx.x; i < SEL * R; i += blockDim.x) out[i] = 0ull;
         return;
     }
     for (u32 i = threadIdx.x; i < STILE; i += blockDim.x) acc[i] = 0u;
     for (u32 i = threadIdx.x; i < STILE / 32; i += blockDim.x) zflag[i] = 0u;
     const STerm *qt = terms + t0;
-    Pool<1> pool;
+    Pool<R> pool;
     pool.clear();
     u64 thr = 0ull;
 
@@ -128,12 +202,25 @@ __global__ __launch_bounds__(256) void sparse_tile_kernel(const u32 *__restrict_
             if (p < nt) sl_w[p] = qt[p].qq_k0;
         }
     auto slice = [&](u32 tile, u32 t, u64 &b, u64 &e) {
-        if (tabled) {
-            const u32 p = ((tile - split) / splits) * nt + t;
-            b = sl_b[p];
-            e = b + sl_n[p];
-        } else
-            slice_global(tile, t, b, e);
+        if constexpr (R == 1) {
+            if (tabled) {
+                const u32 p = ((tile - split) / splits) * nt + t;
+                b = sl_b[p];
+                e = b + sl_n[p];
+            } else
+                slice_global(tile, t, b, e);
+        } else { // through locals: written straight into a cursor's fields, the two branches end as one store to a selected
+                 // address and the cursors move to scratch memory (the narrow kernel carries 40 B of it)
+            u64 bb, ee;
+            if (tabled) {
+                const u32 p = ((tile - split) / splits) * nt + t;
+                bb = sl_b[p];
+                ee = bb + sl_n[p];
+            } else
+                slice_global(tile, t, bb, ee);
+            b = bb;
+            e = ee;
+        }
     };
     auto advance = [&](const SCursor &c) -> SCursor {
         SCursor nx = c;
@@ -190,7 +277,7 @@ __global__ __launch_bounds__(256) void sparse_tile_kernel(const u32 *__restrict_
                     const u64 kk = readlane_u64(key, l);
                     if (kk > thr) {
                         pool.insert_at(kk, pool.rank_of(kk), lane);
-                        thr = readlane_u64(pool.e[0], SEL - 1);
+                        thr = readlane_u64(pool.e[R - 1], 63); // the pool's last key
                     }
                 }
             }
@@ -314,13 +401,17 @@ __global__ __launch_bounds__(256) void sparse_tile_kernel(const u32 *__restrict_
                     const u64 kk = readlane_u64(key, l);
                     if (kk > thr) {
                         pool.insert_at(kk, pool.rank_of(kk), lane);
-                        thr = readlane_u64(pool.e[0], SEL - 1);
+                        thr = readlane_u64(pool.e[R - 1], 63); // the pool's last key
                     }
                 }
             }
             __syncthreads(); // everybody has read the flag words of its slots
             for (u32 i = threadIdx.x; i < STILE / 32; i += blockDim.x) zflag[i] = 0u;
             // (the next tile's prefix barrier orders these stores before its first atomic)
+        }
+        if constexpr (R > 1) {
+            block_merge_pools<R>(pool, reinterpret_cast<u64 *>(acc), out, wave, lane);
+            return;
         }
         wpool[wave][lane] = pool.e[0];
         __syncthreads();
@@ -334,7 +425,7 @@ __global__ __launch_bounds__(256) void sparse_tile_kernel(const u32 *__restrict_
                     const u64 kk = readlane_u64(key, l);
                     if (kk > thr) {
                         pool.insert_at(kk, pool.rank_of(kk), lane);
-                        thr = readlane_u64(pool.e[0], SEL - 1);
+                        thr = readlane_u64(pool.e[R - 1], 63); // the pool's last key
                     }
                 }
             }
@@ -361,6 +452,10 @@ __global__ __launch_bounds__(256) void sparse_tile_kernel(const u32 *__restrict_
         cur = n2;
     }
     // merge the four wave pools
+    if constexpr (R > 1) {
+        block_merge_pools<R>(pool, reinterpret_cast<u64 *>(acc), out, wave, lane);
+        return;
+    }
     wpool[wave][lane] = pool.e[0];
     __syncthreads();
     if (wave == 0) {
@@ -373,7 +468,7 @@ __global__ __launch_bounds__(256) void sparse_tile_kernel(const u32 *__restrict_
                 const u64 kk = readlane_u64(key, l);
                 if (kk > thr) {
                     pool.insert_at(kk, pool.rank_of(kk), lane);
-                    thr = readlane_u64(pool.e[0], SEL - 1);
+                    thr = readlane_u64(pool.e[R - 1], 63); // the pool's last key
                 }
             }
         }
@@ -400,7 +495,7 @@ constexpr u32 SPK_SUM = SPK_CNT - 1u;
 constexpr u32 SPK_MAX_N = (1u << 24) - 2u * STILE;
 constexpr u32 SPK_COUNTED = 0x80000000u; // bit of order[]: this query's blocks may count touches in the accumulator
 
-template <bool COUNTED, int PU /* postings per lane per step */>
+template <bool COUNTED, int PU /* postings per lane per step */, int R = 1 /* pool of 64 * R keys per wave */>
 __device__ __forceinline__ void sparse_packed_body(const u32 *__restrict__ m_pk, const STerm *__restrict__ qt, const u32 nt, const u32 n_tiles,
                                                    const u32 *__restrict__ tile_dir, const u32 split, const u32 splits, u64 *__restrict__ out, u32 *acc,
                                                    u32 *zflag, u64 (*wpool)[SEL], u64 *sl_b, u32 *sl_n, u32 *sl_w, u32 *st_pre, u32 *st_ctr) {
@@ -409,7 +504,7 @@ __device__ __forceinline__ void sparse_packed_body(const u32 *__restrict__ m_pk,
     for (u32 i = threadIdx.x; i < STILE / 4; i += blockDim.x) reinterpret_cast<uint4 *>(acc)[i] = make_uint4(0u, 0u, 0u, 0u);
     if (!COUNTED)
         for (u32 i = threadIdx.x; i < STILE / 32; i += blockDim.x) zflag[i] = 0u;
-    Pool<1> pool;
+    Pool<R> pool;
     pool.clear();
     u64 thr = 0ull;
     auto insert_keys = [&](u64 key) { // the keys of a wave's lanes that beat the pool's last entry
@@ -420,7 +515,7 @@ __device__ __forceinline__ void sparse_packed_body(const u32 *__restrict__ m_pk,
             const u64 kk = readlane_u64(key, l);
             if (kk > thr) {
                 pool.insert_at(kk, pool.rank_of(kk), lane);
-                thr = readlane_u64(pool.e[0], SEL - 1);
+                thr = readlane_u64(pool.e[R - 1], 63); // the pool's last key
             }
         }
     };
@@ -602,6 +697,10 @@ __device__ __forceinline__ void sparse_packed_body(const u32 *__restrict__ m_pk,
             }
         }
     }
+    if constexpr (R > 1) {
+        block_merge_pools<R>(pool, reinterpret_cast<u64 *>(acc), out, wave, lane); // (wpool is a null pointer here)
+        return;
+    }
     wpool[wave][lane] = pool.e[0];
     __syncthreads();
     if (wave == 0) {
@@ -634,6 +733,32 @@ __global__ __launch_bounds__(256) void sparse_packed_kernel(const u32 *__restric
     }
     if (oq & SPK_COUNTED) sparse_packed_body<true, PU>(m_pk, terms + t0, nt, n_tiles, tile_dir, split, splits, out, acc, zflag, wpool, sl_b, sl_n, sl_w, st_pre, &st_ctr);
     else sparse_packed_body<false, PU>(m_pk, terms + t0, nt, n_tiles, tile_dir, split, splits, out, acc, zflag, wpool, sl_b, sl_n, sl_w, st_pre, &st_ctr);
+}
+
+// the same scan with pools of 64 * R keys per wave (R = 2, 4, 8, 16), eight postings per lane and step
+template <int R>
+__global__ __launch_bounds__(256) void sparse_wide_packed_kernel(const u32 *__restrict__ m_pk, const STerm *__restrict__ terms, const u32 *__restrict__ qt_off, u32 n,
+                                                                 const u32 *__restrict__ tile_dir, const u32 *__restrict__ order, u32 splits,
+                                                                 u64 *__restrict__ part /*[B][splits][64 * R]*/) {
+    static_assert(R == 2 || R == 4 || R == 8 || R == 16, "wide instantiations");
+    __shared__ __attribute__((aligned(16))) u32 acc[STILE + 64];
+    __shared__ u32 zflag[STILE / 32];
+    __shared__ u64 sl_b[SLICES];
+    __shared__ u32 sl_n[SLICES], sl_w[SLICES];
+    __shared__ u32 st_pre[65];
+    __shared__ u32 st_ctr;
+    const u32 oq = order[blockIdx.x / splits];
+    const u32 q = oq & ~SPK_COUNTED;
+    const u32 split = blockIdx.x % splits;
+    const u32 t0 = qt_off[q], nt = qt_off[q + 1] - t0;
+    const u32 n_tiles = (n + STILE - 1) / STILE;
+    u64 *out = part + ((u64)q * splits + split) * (SEL * R);
+    if (nt == 0 || split >= n_tiles) { // nothing to visit: an empty segment (the finish kernel reads every split)
+        for (u32 i = threadIdx.x; i < SEL * R; i += blockDim.x) out[i] = 0ull;
+        return;
+    }
+    if (oq & SPK_COUNTED) sparse_packed_body<true, 8, R>(m_pk, terms + t0, nt, n_tiles, tile_dir, split, splits, out, acc, zflag, nullptr, sl_b, sl_n, sl_w, st_pre, &st_ctr);
+    else sparse_packed_body<false, 8, R>(m_pk, terms + t0, nt, n_tiles, tile_dir, split, splits, out, acc, zflag, nullptr, sl_b, sl_n, sl_w, st_pre, &st_ctr);
 }
 
 // one wave per query: merge the segment pools, optional raw-value rerank, write the top k
@@ -693,6 +818,69 @@ __global__ __launch_bounds__(64) void sparse_finish_kernel(const SparseDev ix, c
     if (lane == 0) out_counts[q] = nout;
 }
 
+// The wide finish, one block of 256 threads per query: the S sorted segments of 64 * R keys are folded into the best 64 * R one
+// after the other (fold_reversed + a bitonic merge of log2(64 R) rounds in 8 KB of LDS at R = 16), cut to k * reranking_factor,
+// re-scored four candidates per thread at R = 16 and sorted again in LDS.  Same arithmetic and order as sparse_finish_kernel.
+template <int R>
+__global__ __launch_bounds__(256) void sparse_wide_finish_kernel(const SparseDev ix, const u64 *__restrict__ part, u32 S, const u32 *__restrict__ q_dims,
+                                                                 const float *__restrict__ q_vals, const u32 *__restrict__ q_off, u32 top_k, u32 k_with_reranking,
+                                                                 int rerank, u32 *__restrict__ out_ids, float *__restrict__ out_scores, u32 *__restrict__ out_counts) {
+    static_assert(R == 2 || R == 4 || R == 8 || R == 16, "wide instantiations");
+    constexpr u32 N = 64u * R;
+    __shared__ u64 best[N];
+    __shared__ u32 s_ncand;
+    const u32 q = blockIdx.x;
+    const u64 *seg = part + (u64)q * S * N;
+    for (u32 i = threadIdx.x; i < N; i += blockDim.x) best[i] = seg[i];
+    __syncthreads();
+    for (u32 sgm = 1; sgm < S; sgm++) {
+        const u64 *other = seg + (u64)sgm * N;
+        if (other[0] <= best[N - 1]) continue; // block-uniform: the segment's best key does not make the cut (an empty segment never does)
+        __syncthreads();                       // everybody has read best[N - 1]
+        fold_reversed<N>(best, other);
+        lds_bitonic_merge_desc<N>(best, 1, 0);
+    }
+    // select_nth + truncate(k * reranking_factor): the filled entries come first
+    if (threadIdx.x == 0) s_ncand = k_with_reranking < N ? k_with_reranking : N;
+    __syncthreads();
+    for (u32 i = threadIdx.x; i < k_with_reranking && i < N; i += blockDim.x)
+        if (best[i] == 0ull && (i == 0u || best[i - 1] != 0ull)) s_ncand = i;
+    __syncthreads();
+    const u32 ncand = s_ncand, nout = ncand < top_k ? ncand : top_k;
+    if (!rerank) {
+        for (u32 i = threadIdx.x; i < nout; i += blockDim.x) {
+            const u64 mine = best[i];
+            out_ids[(u64)q * top_k + i] = (u32)mine;
+            out_scores[(u64)q * top_k + i] = (float)((u32)(mine >> 32) - 1u); // `similarity as f32`
+        }
+        if (threadIdx.x == 0) out_counts[q] = nout;
+        return;
+    }
+    // finalize_sparse_ann_results: dp over the QUERY pairs in order, f32 multiply then add; sort by total_cmp descending
+    for (u32 c = threadIdx.x; c < N; c += blockDim.x) { // (every thread rewrites the entries it read)
+        u64 res = 0ull;
+        if (c < ncand) {
+            const u32 v = (u32)best[c];
+            const u64 b = ix.row_off[v], e = ix.row_off[v + 1];
+            float dp = 0.0f;
+            for (u32 i = q_off[q]; i < q_off[q + 1]; i++) {
+                const u32 d = q_dims[i];
+                u64 lo = b, hi = e;
+                while (lo < hi) { const u64 mid = lo + (hi - lo) / 2; if (ix.raw_dims[mid] < d) lo = mid + 1; else hi = mid; }
+                if (lo < e && ix.raw_dims[lo] == d) dp = __fadd_rn(dp, __fmul_rn(ix.raw_vals[lo], q_vals[i]));
+            }
+            res = pack_key(simkey(dp), v);
+        }
+        best[c] = res;
+    }
+    lds_bitonic_sort_desc<N>(best);
+    for (u32 i = threadIdx.x; i < nout; i += blockDim.x) {
+        out_ids[(u64)q * top_k + i] = (u32)best[i];
+        out_scores[(u64)q * top_k + i] = simkey_inv((u32)(best[i] >> 32));
+    }
+    if (threadIdx.x == 0) out_counts[q] = nout;
+}
+
 } // namespace
 
 struct cos_sparse {
@@ -708,6 +896,7 @@ struct cos_sparse {
     std::vector<u32> h_dir;     // [T] row in the tile directory or SNO_DIR
     std::vector<u32> h_mult;    // [T] how often one vector id occurs in the dimension's list at most (1 unless the caller's CSR repeats ids)
     bool packed = false;        // device layout: one u32 per posting (d_pk) instead of d_ids + d_keys
+    u32 max_cand = SEL;         // widest top_k * max(reranking_factor, 1) a search keeps: 64, 128, 256, 512 or 1024 (cos_sparse_set_max_candidates)
     // device: one id-sorted list per dimension (same offsets as the caller's CSR: list t = [key_off[t][0], key_off[t][Q]))
     DevArr<u32> d_ids;
     DevArr<uint8_t> d_keys;
@@ -726,6 +915,20 @@ struct cos_sparse {
         if (ev1) (void)hipEventDestroy(ev1);
     }
 };
+
+// scan + finish of a call that keeps more than 64 candidates per query: the instantiation R, pools and segments of 64 * R keys
+template <int R>
+static hipError_t sparse_launch_wide(const cos_sparse *s, const SparseDev &dev, u32 B, u32 splits, const STerm *terms, const u32 *qt_off, const u32 *order,
+                                     u64 *part, const u32 *qd, const float *qv, const u32 *qo, u32 top_k, u32 kwr, int rerank, u32 *oi, float *os, u32 *oc) {
+    if (s->packed)
+        hipLaunchKernelGGL(sparse_wide_packed_kernel<R>, dim3(B * splits), dim3(256), 0, 0, s->d_pk.p, terms, qt_off, s->n, s->d_tile_dir.p, order, splits, part);
+    else
+        hipLaunchKernelGGL(sparse_tile_kernel<R>, dim3(B * splits), dim3(256), 0, 0, s->d_ids.p, s->d_keys.p, terms, qt_off, s->n, s->d_tile_dir.p, order, splits, part);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(sparse_wide_finish_kernel<R>, dim3(B), dim3(256), 0, 0, dev, part, splits, qd, qv, qo, top_k, kwr, rerank, oi, os, oc);
+    return hipGetLastError();
+}
 
 extern "C" int32_t cos_sparse_destroy(cos_sparse *s) {
     if (!s) return COS_OK;
@@ -917,15 +1120,19 @@ extern "C" int32_t cos_sparse_search_batch(cos_sparse *s, const uint32_t *q_dims
     if (B >= SPK_COUNTED) return cos_fail(COS_ERR_INVALID, "batch of %u queries", B);
     const bool rerank = reranking_factor != 0;
     if (rerank && !s->have_raw) return cos_fail(COS_ERR_NOT_READY, "raw-value rerank needs the raw sparse vectors (cos_sparse_create row_offsets / raw_dims / raw_vals)");
-    const u32 kwr = top_k * (rerank ? reranking_factor : 1u);
-    if (kwr > SEL) return cos_fail(COS_ERR_UNIMPLEMENTED, "top_k x reranking_factor must be <= %u", SEL);
+    // cos_sparse_insert / cos_sparse_delete replace the host tables the resolution reads (absolute list offsets included) together
+    // with the device arrays, cos_sparse_set_max_candidates the width this call is held to: one lock over all of it
+    std::lock_guard<std::mutex> guard(s->mu);
+    const u64 kwr64 = (u64)top_k * (rerank ? reranking_factor : 1u);
+    if (kwr64 > s->max_cand) return cos_fail(COS_ERR_UNIMPLEMENTED, "top_k x reranking_factor must be <= %u", s->max_cand);
+    const u32 kwr = (u32)kwr64;
+    // the variant is the call's, not the handle's: up to 64 candidates run the narrow kernels whatever the handle allows
+    u32 R = 1;
+    while (SEL * R < kwr) R *= 2;
     HIP_TRY(hipSetDevice(s->device));
     for (u32 b = 0; b < B; b++)
         if (q_offsets[b + 1] < q_offsets[b]) return cos_fail(COS_ERR_INVALID, "query offsets decrease");
     const u32 nq = q_offsets[B], Q = 1u << s->bits;
-    // cos_sparse_insert / cos_sparse_delete replace the host tables the resolution reads (absolute list offsets included) together
-    // with the device arrays: one lock over both
-    std::lock_guard<std::mutex> guard(s->mu);
     // ---- resolve the query terms on the host (sparse_ann_query.rs:80-125): find_node, quantize, which keys the term visits ----
     const float qf = (float)Q;
     float etv = qf * early_terminate_threshold;
@@ -970,7 +1177,7 @@ extern "C" int32_t cos_sparse_search_batch(cos_sparse *s, const uint32_t *q_dims
     HIP_TRY(s->w_terms.grow(std::max<size_t>(terms.size(), 1) * sizeof(STerm)));
     HIP_TRY(s->w_qt_off.grow(((size_t)B + 1) * 4));
     HIP_TRY(s->w_order.grow((size_t)B * 4));
-    HIP_TRY(s->w_part.grow((size_t)B * splits * SEL * 8));
+    HIP_TRY(s->w_part.grow((size_t)B * splits * SEL * R * 8));
     HIP_TRY(s->w_oi.grow((size_t)B * top_k * 4));
     HIP_TRY(s->w_os.grow((size_t)B * top_k * 4));
     HIP_TRY(s->w_oc.grow((size_t)B * 4));
@@ -984,17 +1191,23 @@ extern "C" int32_t cos_sparse_search_batch(cos_sparse *s, const uint32_t *q_dims
     HIP_TRY(hipMemcpy(d_order.p, order.data(), (size_t)B * 4, hipMemcpyHostToDevice));
     SparseDev dev{nullptr, nullptr, nullptr, s->d_row_off, s->d_raw_dims, s->d_raw_vals, s->T, Q, s->n, s->bits, s->upper};
     HIP_TRY(hipEventRecord(s->ev0, 0));
-    // eight postings per lane and step; sixteen measured the same (0.447 against 0.453 ms) and was dropped
-    if (s->packed)
-        hipLaunchKernelGGL(sparse_packed_kernel<8>, dim3(B * splits), dim3(256), 0, 0, s->d_pk.p, d_terms.as<STerm>(), d_qt_off.as<u32>(), s->n, s->d_tile_dir.p,
-                           d_order.as<u32>(), splits, d_part.as<u64>());
-    else
-        hipLaunchKernelGGL(sparse_tile_kernel, dim3(B * splits), dim3(256), 0, 0, s->d_ids.p, s->d_keys.p, d_terms.as<STerm>(), d_qt_off.as<u32>(), s->n, s->d_tile_dir.p,
-                           d_order.as<u32>(), splits, d_part.as<u64>());
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(sparse_finish_kernel, dim3(B), dim3(64), 0, 0, dev, d_part.as<u64>(), splits, d_qd.as<u32>(), d_qv.as<float>(), d_qo.as<u32>(), top_k, kwr,
-                       rerank ? 1 : 0, d_oi.as<u32>(), d_os.as<float>(), d_oc.as<u32>());
-    HIP_TRY(hipGetLastError());
+    if (R > 1) {
+        auto wide = R == 2 ? sparse_launch_wide<2> : R == 4 ? sparse_launch_wide<4> : R == 8 ? sparse_launch_wide<8> : sparse_launch_wide<16>;
+        HIP_TRY(wide(s, dev, B, splits, d_terms.as<STerm>(), d_qt_off.as<u32>(), d_order.as<u32>(), d_part.as<u64>(), d_qd.as<u32>(), d_qv.as<float>(),
+                     d_qo.as<u32>(), top_k, kwr, rerank ? 1 : 0, d_oi.as<u32>(), d_os.as<float>(), d_oc.as<u32>()));
+    } else {
+        // eight postings per lane and step; sixteen measured the same (0.447 against 0.453 ms) and was dropped
+        if (s->packed)
+            hipLaunchKernelGGL(sparse_packed_kernel<8>, dim3(B * splits), dim3(256), 0, 0, s->d_pk.p, d_terms.as<STerm>(), d_qt_off.as<u32>(), s->n, s->d_tile_dir.p,
+                               d_order.as<u32>(), splits, d_part.as<u64>());
+        else
+            hipLaunchKernelGGL(sparse_tile_kernel<1>, dim3(B * splits), dim3(256), 0, 0, s->d_ids.p, s->d_keys.p, d_terms.as<STerm>(), d_qt_off.as<u32>(), s->n, s->d_tile_dir.p,
+                               d_order.as<u32>(), splits, d_part.as<u64>());
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(sparse_finish_kernel, dim3(B), dim3(64), 0, 0, dev, d_part.as<u64>(), splits, d_qd.as<u32>(), d_qv.as<float>(), d_qo.as<u32>(), top_k, kwr,
+                           rerank ? 1 : 0, d_oi.as<u32>(), d_os.as<float>(), d_oc.as<u32>());
+        HIP_TRY(hipGetLastError());
+    }
     HIP_TRY(hipEventRecord(s->ev1, 0));
     HIP_TRY(hipMemcpy(out_ids, d_oi.p, (size_t)B * top_k * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(out_scores, d_os.p, (size_t)B * top_k * 4, hipMemcpyDeviceToHost));
@@ -1011,6 +1224,23 @@ extern "C" int32_t cos_sparse_search_batch(cos_sparse *s, const uint32_t *q_dims
 extern "C" int32_t cos_sparse_layout(cos_sparse *s, uint32_t *packed) {
     if (!s || !packed) return cos_fail(COS_ERR_INVALID, "null argument");
     *packed = s->packed ? 1u : 0u;
+    return COS_OK;
+}
+
+extern "C" int32_t cos_sparse_set_max_candidates(cos_sparse *s, uint32_t max_candidates) {
+    if (!s) return cos_fail(COS_ERR_INVALID, "null argument");
+    if (max_candidates == 0 || max_candidates > SEL_MAX) return cos_fail(COS_ERR_INVALID, "max_candidates must be in [1, %u]", SEL_MAX);
+    u32 w = SEL;
+    while (w < max_candidates) w *= 2;
+    std::lock_guard<std::mutex> guard(s->mu);
+    s->max_cand = w; // the workspace follows the calls (grow-only): narrowing the setting frees nothing
+    return COS_OK;
+}
+
+extern "C" int32_t cos_sparse_max_candidates(cos_sparse *s, uint32_t *out) {
+    if (!s || !out) return cos_fail(COS_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> guard(s->mu);
+    *out = s->max_cand;
     return COS_OK;
 }
 

@@ -212,6 +212,26 @@ def _sparse_packed(self) -> bool:
 InvertedIndex.packed = property(_sparse_packed)
 
 
+def _sparse_set_max_candidates(self, n: int):
+    """cos_sparse_set_max_candidates: the widest top_k * max(reranking_factor, 1) a search_batch on this handle may keep, 1..1024
+    (rounded up to 64, 128, 256, 512 or 1024; 64 unless set).  Narrower calls run what they ran before."""
+    if not 0 <= int(n) <= 0xFFFFFFFF:
+        raise ValueError("max_candidates must fit an unsigned 32-bit integer")
+    check(_lib.lib().cos_sparse_set_max_candidates(self._h, int(n)))
+    return self
+
+
+def _sparse_max_candidates(self) -> int:
+    """the rounded setting of set_max_candidates (cos_sparse_max_candidates)"""
+    v = C.c_uint32(0)
+    check(_lib.lib().cos_sparse_max_candidates(self._h, C.byref(v)))
+    return int(v.value)
+
+
+InvertedIndex.set_max_candidates = _sparse_set_max_candidates
+InvertedIndex.max_candidates = property(_sparse_max_candidates)
+
+
 def _sparse_insert(self, row_offsets, raw_dims, raw_vals) -> int:
     """InvertedIndex::insert for m more vectors (cos_sparse_insert): they take the ids [n, n + m); pairs of vector i are
     raw_dims / raw_vals [row_offsets[i], row_offsets[i+1]).  The resident postings are merged on the device.  -> the first new id"""

@@ -507,11 +507,24 @@ int32_t cos_sparse_destroy(cos_sparse *s);
 /* InvertedIndex::search_internal (indexes/inverted/mod.rs:278-331) -> SparseAnnQueryBasic::sequential_search
  * (models/sparse_ann_query.rs:68-147) for B queries given as CSR pairs (q_offsets[B+1] into q_dims / q_vals).
  * reranking_factor = 0: config.rerank_sparse_with_raw_values = false -> scores are the quantized similarities as f32;
- * otherwise the best top_k * reranking_factor candidates are re-scored with the raw values and sorted (<= 64 candidates).
+ * otherwise the best top_k * reranking_factor candidates are re-scored with the raw values and sorted.
+ * top_k * max(reranking_factor, 1) above the handle's cos_sparse_set_max_candidates (64 unless set) is COS_ERR_UNIMPLEMENTED and
+ * leaves the handle usable.
  * Order: score descending, larger id first (the reference leaves the order of equal / unranked entries to its hash map). */
 int32_t cos_sparse_search_batch(cos_sparse *s, const uint32_t *q_dims, const float *q_vals, const uint32_t *q_offsets, uint32_t B,
                                 uint32_t top_k, float early_terminate_threshold, uint32_t reranking_factor, uint32_t *out_ids,
                                 float *out_scores, uint32_t *out_counts);
+
+/* Widest candidate set, top_k * max(reranking_factor, 1), a search on this handle may keep.  Default 64.
+ * Accepted 1..1024, rounded up to 64, 128, 256, 512 or 1024; 0 or > 1024 -> COS_ERR_INVALID, handle unchanged.
+ * Takes the handle's lock (a search on another thread runs before or after).  Kept across
+ * cos_sparse_insert / cos_sparse_delete.
+ * The setting only admits wider calls; every call picks its kernels by its own width: up to 64 candidates run exactly what a
+ * default handle runs, (32 R, 64 R] candidates run the instantiation R = 2, 4, 8, 16 with pools of 64 R keys.  What a wide call
+ * costs beside time is the grow-only workspace: B * splits * 64 R * 8 bytes of partial results (B * splits is about 4096 for
+ * B <= 4096: 34 MB at R = 16), kept until the handle is destroyed. */
+int32_t cos_sparse_set_max_candidates(cos_sparse *s, uint32_t max_candidates);
+int32_t cos_sparse_max_candidates(cos_sparse *s, uint32_t *out);   /* the rounded value */
 
 /* Figures of the most recent cos_sparse_search_batch on this handle: HIP-event time of its kernels, and the postings the
  * reference's traversal visits for that batch (sparse_ann_query.rs:92-125: every list of a term from its first visited key on;
