@@ -32,6 +32,33 @@ hipError_t launch_flat_scan(u32 kdims, u32 n_cus, hipStream_t st, const uint8_t 
 hipError_t launch_flat_scan_u8(u32 kdims, u32 n_cus, hipStream_t st, const uint8_t *qcodes, const u32 *qsums, const float *qmags, u32 B, const uint8_t *codes,
                                const u32 *csums, const float *mags, u64 row_stride, u32 n0, u32 nc, u32 metric, const FusedOut &fo);
 
+// Survivor pools wider than 64 keys (kernels_flat_wide.hip): P = 64 * R keys per query, R = 2, 4, 8, 16, kept sorted (descending) as
+// pool[B][P].  The scan kernels are the same at every width: they read thr[q] (the P-th best key, 0 while the pool is not full) and
+// append to app[B][cap].  R = 1 stays on the kernels of kernels_flat.hip.
+constexpr u32 FLAT_SEED = 16384;  // candidates that go through the score matrix first and seed every query's threshold (every width)
+// Fused schedule of a pool of P keys: a chunk `growth` times the size of everything seen lets ~growth * P keys per query through (a key
+// passes with probability P / seen while the threshold stands), and the append buffer holds eight times that:
+//   P = 64        growth 8, cap 64 P = 4096 keys (32 KB per query)
+//   P = 128..1024 growth 4, cap 32 P        keys (256 P bytes per query: 32 KB .. 256 KB)
+__host__ __device__ constexpr u32 flat_growth(u32 P) { return P == 64 ? 8u : 4u; }
+__host__ __device__ constexpr u32 flat_app_cap(u32 P) { return P == 64 ? 4096u : 32u * P; }
+// smallest pool width (64, 128, ..., 1024) that holds `need` keys; 0 when none does
+inline u32 flat_pool_width(u32 need) {
+    for (u32 P = 64; P <= 1024; P *= 2)
+        if (need <= P) return P;
+    return 0;
+}
+// score chunk [B][nc] -> per-segment top P (part[B][S][P]) -> merged into pool[B][P]; thr[q] = the pool's P-th best
+hipError_t launch_flat_select_wide(u32 R, const float *d_scores, u64 s_stride, u32 B, u32 n0, u32 nc, u64 *d_part, u32 S, u64 *d_pool, u64 *d_thr,
+                                   hipStream_t st);
+// fold of the fused scan's append buffer (entries past `cap` were dropped: *d_overflow |= 1), new thresholds, counters cleared
+hipError_t launch_flat_append_wide(u32 R, const u64 *d_app, u32 *d_appcnt, u32 cap, u32 B, u64 *d_pool, u64 *d_thr, u32 *d_overflow, hipStream_t st);
+// exact re-score against the raw rows, sort, top k.  brute = false: the best min(have, ncand_max) of the pool, out_counts set (code scan);
+// brute = true: every survivor, ~0 / 0.0 where there is none, out_counts unused (brute force)
+hipError_t launch_flat_rerank_wide(u32 R, bool brute, const float *Q, u64 q_stride, const float *qmags, u32 B, const float *X, u64 x_stride,
+                                   const float *xmags, u32 dim, const u64 *d_pool, u32 ncand_max, u32 k, u32 id_base, u32 *out_ids, float *out_scores,
+                                   u32 *out_counts, hipStream_t st);
+
 // the walk's level table as a query-resident GEMM (kernels_scan.hip): tab[q][c] = (f32) exact integer dot; u8 or quaternary codes
 bool level_table_areg_supported(int eng, u64 row_stride);
 hipError_t launch_level_table_areg(int eng, u32 n_cus, hipStream_t st, const uint8_t *qcodes, const u32 *qsums, u32 B, const uint8_t *tcodes,

@@ -9,6 +9,8 @@
 // MFMA accumulation order differs from the reference's 8-lane tree in the last ulp, so the GEMM only
 // GENERATES candidates (64 >= 2k with margin); the returned ids/scores come from the reference-order kernel
 // and are bit-identical to the oracle's brute force.
+// Calls that need more than 64 survivors (k > 32 here, top_k > 12 in the code scan) keep pools of 128 .. 1024 keys: the kernels
+// behind the GEMMs are then those of kernels_flat_wide.hip, the GEMMs and the flow below are the same.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -620,7 +622,9 @@ __global__ __launch_bounds__(64) void flat_rerank_top5k(const float *__restrict_
 extern "C" int32_t cos_bruteforce_topk(cos_index *ix, const float *queries, uint32_t B, uint32_t k, uint32_t *out_ids, float *out_scores) {
     if (!ix || !queries || !out_ids || !out_scores || B == 0) return cos_fail(COS_ERR_INVALID, "bad argument");
     if (!ix->have_vectors) return cos_fail(COS_ERR_NOT_READY, "upload vectors first");
-    if (k == 0 || k > 32 || k > ix->n) return cos_fail(COS_ERR_INVALID, "k must be in [1, min(32, n)]");
+    if (k == 0 || k > 512 || k > ix->n) return cos_fail(COS_ERR_INVALID, "k must be in [1, min(512, n)]");
+    // survivors per query: the GEMM only generates candidates, so the pool holds at least 2k of them (64 for k <= 32, as ever)
+    const u32 P = flat_pool_width(2 * k), R = P / SEL;
     int32_t rc = cos_set_device(ix);
     if (rc) return rc;
     const u32 dim = ix->p.dim, n = ix->n;
@@ -629,8 +633,10 @@ extern "C" int32_t cos_bruteforce_topk(cos_index *ix, const float *queries, uint
     chunk = std::min(n, std::max<u32>(chunk, BN));
     // Same schedule as cos_flat_search_batch: the first SEED candidates go through the score matrix + segmented selection and
     // seed every query's threshold; later chunks grow 8x and the GEMM epilogue appends only what beats the threshold.  An
-    // append-buffer overflow repeats the call on the unfused path (tuning knob flat_unfused = 1 forces it).
-    constexpr u32 SEED = 16384, APP_CAP = 4096;
+    // append-buffer overflow repeats the call on the unfused path (tuning knob flat_unfused = 1 forces it).  Wider pools grow 4x into
+    // an append buffer of 32 P keys (flat_scan.h flat_growth / flat_app_cap).
+    constexpr u32 SEED = FLAT_SEED;
+    const u32 APP_CAP = flat_app_cap(P), growth = flat_growth(P);
     const bool allow_fused = tune_or(TUNE_FLAT_UNFUSED, 0) == 0 && n > SEED;
     const u64 s_stride = ((u64)chunk + 63) & ~63ull;
     DevArr<float> d_q, d_qm, d_scores, d_os, d_dummy;
@@ -640,12 +646,12 @@ extern "C" int32_t cos_bruteforce_topk(cos_index *ix, const float *queries, uint
     hipStream_t st = ix->own_stream;
     const u32 S = select_segments(B, chunk);
     HIP_TRY(d_q.alloc((size_t)B * dim));
-    HIP_TRY(d_part.alloc((size_t)B * S * SEL));
+    HIP_TRY(d_part.alloc((size_t)B * S * P));
     HIP_TRY(d_qm.alloc(B));
     HIP_TRY(d_dummy.alloc(B));
     HIP_TRY(d_codes.alloc((size_t)B * (((size_t)dim * 4 + 15) & ~(size_t)15)));
     HIP_TRY(d_scores.alloc((size_t)B * s_stride));
-    HIP_TRY(d_pool.alloc((size_t)B * SEL));
+    HIP_TRY(d_pool.alloc((size_t)B * P));
     HIP_TRY(d_thr.alloc(B));
     if (allow_fused) HIP_TRY(d_app.alloc((size_t)B * APP_CAP));
     HIP_TRY(d_appcnt.alloc(B));
@@ -663,7 +669,7 @@ extern "C" int32_t cos_bruteforce_topk(cos_index *ix, const float *queries, uint
     const bool vec = dim % 4 == 0 && ((uintptr_t)ix->d_raw & 15) == 0;
     for (int attempt = 0; attempt < 2 && e == hipSuccess; attempt++) {
         const bool fused = allow_fused && attempt == 0;
-        if (e == hipSuccess) e = hipMemsetAsync(d_pool, 0, (size_t)B * SEL * 8, st);
+        if (e == hipSuccess) e = hipMemsetAsync(d_pool, 0, (size_t)B * P * 8, st);
         if (e == hipSuccess) e = hipMemsetAsync(d_thr, 0, (size_t)B * 8, st);
         if (e == hipSuccess) e = hipMemsetAsync(d_appcnt, 0, (size_t)B * 4, st);
         if (e == hipSuccess) e = hipMemsetAsync(d_over, 0, 4, st);
@@ -671,7 +677,7 @@ extern "C" int32_t cos_bruteforce_topk(cos_index *ix, const float *queries, uint
         u32 n0 = 0;
         while (n0 < n && e == hipSuccess) {
             const bool use_fused = fused && n0 > 0;
-            u32 nc = use_fused ? (u32)std::min<u64>((u64)n0 * 8, 1ull << 22) : (fused ? std::min(SEED, chunk) : chunk);
+            u32 nc = use_fused ? (u32)std::min<u64>((u64)n0 * growth, 1ull << 22) : (fused ? std::min(SEED, chunk) : chunk);
             nc = std::min(nc, n - n0);
             dim3 grid((nc + BN - 1) / BN, (B + BM - 1) / BM);
 #define GEMM_ARGS d_q, (u64)dim, d_qm, B, ix->d_raw, (u64)dim, ix->d_raw_mags, n0, nc, dim, d_scores, s_stride, fo
@@ -679,15 +685,17 @@ extern "C" int32_t cos_bruteforce_topk(cos_index *ix, const float *queries, uint
                 if (vec) hipLaunchKernelGGL((flat_gemm_f32<true, true>), grid, dim3(256), GEMM_SMEM, st, GEMM_ARGS);
                 else hipLaunchKernelGGL((flat_gemm_f32<false, true>), grid, dim3(256), GEMM_SMEM, st, GEMM_ARGS);
                 e = hipGetLastError();
-                if (e == hipSuccess) {
+                if (e == hipSuccess && R == 1) {
                     hipLaunchKernelGGL(flat_select_append, dim3(B), dim3(64), 0, st, (const u64 *)d_app, d_appcnt, APP_CAP, B, d_pool, d_thr, d_over);
                     e = hipGetLastError();
-                }
+                } else if (e == hipSuccess)
+                    e = launch_flat_append_wide(R, d_app, d_appcnt, APP_CAP, B, d_pool, d_thr, d_over, st);
             } else {
                 if (vec) hipLaunchKernelGGL((flat_gemm_f32<true, false>), grid, dim3(256), GEMM_SMEM, st, GEMM_ARGS);
                 else hipLaunchKernelGGL((flat_gemm_f32<false, false>), grid, dim3(256), GEMM_SMEM, st, GEMM_ARGS);
                 e = hipGetLastError();
-                if (e == hipSuccess) e = launch_select(d_scores, s_stride, B, n0, nc, d_part, select_segments(B, nc), d_pool, st, d_thr);
+                if (e == hipSuccess && R == 1) e = launch_select(d_scores, s_stride, B, n0, nc, d_part, select_segments(B, nc), d_pool, st, d_thr);
+                else if (e == hipSuccess) e = launch_flat_select_wide(R, d_scores, s_stride, B, n0, nc, d_part, select_segments(B, nc), d_pool, d_thr, st);
             }
 #undef GEMM_ARGS
             n0 += nc;
@@ -697,11 +705,12 @@ extern "C" int32_t cos_bruteforce_topk(cos_index *ix, const float *queries, uint
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e != hipSuccess || !fused || hover == 0) break; // done; otherwise the append buffer overflowed: repeat unfused
     }
-    if (e == hipSuccess) {
+    if (e == hipSuccess && R == 1) {
         hipLaunchKernelGGL(flat_rescore, dim3(B), dim3(64), (((size_t)dim * 4 + 15) & ~(size_t)15), st, d_q, (u64)dim, d_qm, B, ix->d_raw, (u64)dim,
                            ix->d_raw_mags, dim, d_pool, k, ix->p.id_base, d_oi, d_os);
         e = hipGetLastError();
-    }
+    } else if (e == hipSuccess)
+        e = launch_flat_rerank_wide(R, true, d_q, (u64)dim, d_qm, B, ix->d_raw, (u64)dim, ix->d_raw_mags, dim, d_pool, P, k, ix->p.id_base, d_oi, d_os, nullptr, st);
     if (e == hipSuccess) e = hipMemcpyAsync(out_ids, d_oi, (size_t)B * k * 4, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipMemcpyAsync(out_scores, d_os, (size_t)B * k * 4, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -752,7 +761,10 @@ extern "C" int32_t cos_flat_search_batch(cos_index *ix, const float *queries, ui
                                          uint32_t *out_counts, cos_flat_stats *stats) {
     if (!ix || !queries || !out_ids || !out_scores || !out_counts || B == 0) return cos_fail(COS_ERR_INVALID, "bad argument");
     if (!ix->have_vectors) return cos_fail(COS_ERR_NOT_READY, "upload vectors first");
-    if (top_k == 0 || 5 * top_k > (u32)SEL) return cos_fail(COS_ERR_UNIMPLEMENTED, "flat search keeps 64 survivors: top_k must be in [1, 12]");
+    if (top_k == 0 || top_k > 204) return cos_fail(COS_ERR_UNIMPLEMENTED, "flat search keeps at most 1024 survivors (5 * top_k): top_k must be in [1, 204]");
+    // survivors per query: the smallest pool that holds the 5 * top_k rerank candidates (64 for top_k <= 12, as ever).  Every buffer
+    // below is sized and indexed by this call's P, not by the widest call the handle has served.
+    const u32 P = flat_pool_width(5 * top_k), R = P / SEL;
     if (ix->eng != ENG_U8 && ix->eng != ENG_Q2) return cos_fail(COS_ERR_UNIMPLEMENTED, "flat search over codes implements u8 and quaternary storage");
     int32_t rc = cos_set_device(ix);
     if (rc) return rc;
@@ -763,6 +775,9 @@ extern "C" int32_t cos_flat_search_batch(cos_index *ix, const float *queries, ui
     // beats the threshold: a chunk 8x the size of everything seen before lets ~64 * 8 entries per query through, an eighth of
     // the append capacity.  An adversarially ordered corpus can still overflow it; that is detected on the device and the
     // call is repeated on the unfused path, so the result never depends on the shortcut.  Tuning knob flat_unfused = 1 forces that path.
+    // Wider pools (P = 128 .. 1024) keep the seed — 16 candidates per pool slot at P = 1024: the pool is full and its threshold is the
+    // best 1/16 before the first fused chunk — and grow 4x into an append buffer of 32 P keys: ~4 P entries per query pass a chunk, an
+    // eighth of the capacity again (flat_scan.h flat_growth / flat_app_cap).
     const bool allow_fused = tune_or(TUNE_FLAT_UNFUSED, 0) == 0;
     const int pf = (int)tune_or(TUNE_FLAT_PF, 1); // k panels prefetched into registers (1..3); results do not depend on it
     // fused chunks of quaternary codes run on the query-resident kernel when K has an instantiation (tuning knob flat_tile_kernel = 1: never)
@@ -772,7 +787,8 @@ extern "C" int32_t cos_flat_search_batch(cos_index *ix, const float *queries, ui
     const bool use_u8q = ix->eng == ENG_U8 && ix->row_stride == (u64)kdims && flat_scan_supported(kdims) && tune_or(TUNE_FLAT_TILE_KERNEL, 0) == 0; // (1024 dims: 32 query rows per wave instead of 64)
     int n_cus = 0;
     if (hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, ix->p.device) != hipSuccess || n_cus <= 0) n_cus = 256;
-    constexpr u32 SEED = 16384, APP_CAP = 4096;
+    constexpr u32 SEED = FLAT_SEED;
+    const u32 APP_CAP = flat_app_cap(P), growth = flat_growth(P);
     u32 chunk = (u32)std::min<u64>(1u << 20, ((1ull << 31) / B / 4) / CN * CN); // unfused: the [B][chunk] score buffer stays <= 2 GiB
     chunk = std::min(n, std::max<u32>(chunk, CN));
     hipStream_t st = ix->own_stream;
@@ -811,7 +827,7 @@ extern "C" int32_t cos_flat_search_batch(cos_index *ix, const float *queries, ui
             if (use_areg) need(W->qdp, d_qdp, (size_t)B * kdims);
             need(W->qs, d_qs, B);
             need(W->cs, d_cs, (size_t)n + 1);
-            need(W->pool, d_pool, (size_t)B * SEL);
+            need(W->pool, d_pool, (size_t)B * P);
             need(W->thr, d_thr, B);
             need(W->app, d_app, (size_t)B * APP_CAP);
             need(W->appcnt, d_appcnt, B);
@@ -858,9 +874,9 @@ extern "C" int32_t cos_flat_search_batch(cos_index *ix, const float *queries, ui
             }
         }
         need(W->scores, d_scores, (size_t)B * s_stride);
-        need(W->part, d_part, (size_t)B * S * SEL);
+        need(W->part, d_part, (size_t)B * S * P);
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(flat_reset_kernel, dim3(64), dim3(256), 0, st, d_pool, (u64)B * SEL, d_thr, d_appcnt, B, d_zero + 1); // (d_zero + 1: overflow flag of the fused path)
+            hipLaunchKernelGGL(flat_reset_kernel, dim3(64), dim3(256), 0, st, d_pool, (u64)B * P, d_thr, d_appcnt, B, d_zero + 1); // (d_zero + 1: overflow flag of the fused path)
             e = hipGetLastError();
         }
         FusedOut fo{d_thr, d_app, d_appcnt, APP_CAP, d_qd};
@@ -869,7 +885,7 @@ extern "C" int32_t cos_flat_search_batch(cos_index *ix, const float *queries, ui
             const bool use_fused = fused && n0 > 0;
             // chunk cap: the tile kernel's grid (and its event granularity) like 4 M; the query-resident kernel is persistent and
             // pays ~35 us of prologue per launch, so it takes everything that is left once the 8x rule allows it
-            u32 nc = use_fused ? (u32)std::min<u64>((u64)seen * 8, use_areg || use_u8q ? (1ull << 31) : (1ull << 22)) : first;
+            u32 nc = use_fused ? (u32)std::min<u64>((u64)seen * growth, use_areg || use_u8q ? (1ull << 31) : (1ull << 22)) : first;
             nc = std::min(nc, n - n0);
             dim3 grid((nc + CN - 1) / CN, (B + CM - 1) / CM);
             hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -897,11 +913,15 @@ extern "C" int32_t cos_flat_search_batch(cos_index *ix, const float *queries, ui
             e = hipGetLastError();
             if (e == hipSuccess) e = hipEventRecord(ev1, st);
             if (e == hipSuccess) {
-                if (use_fused) {
+                if (use_fused && R == 1) {
                     hipLaunchKernelGGL(flat_select_append, dim3(B), dim3(64), 0, st, (const u64 *)d_app, d_appcnt, APP_CAP, B, d_pool, d_thr, d_zero + 1);
                     e = hipGetLastError();
-                } else
+                } else if (use_fused)
+                    e = launch_flat_append_wide(R, d_app, d_appcnt, APP_CAP, B, d_pool, d_thr, d_zero + 1, st);
+                else if (R == 1)
                     e = launch_select(d_scores, s_stride, B, n0, nc, d_part, S, d_pool, st, d_thr);
+                else
+                    e = launch_flat_select_wide(R, d_scores, s_stride, B, n0, nc, d_part, S, d_pool, d_thr, st);
             }
             launches++;
             streamed += (double)nc * (double)ix->row_stride * (double)((B + CM - 1) / CM);
@@ -914,8 +934,14 @@ extern "C" int32_t cos_flat_search_batch(cos_index *ix, const float *queries, ui
         if (e == hipSuccess) e = W->out.grow(out_words);
         if (e == hipSuccess) e = W->h_out.grow(out_words);
         if (e != hipSuccess) break;
-        hipLaunchKernelGGL(flat_rerank_top5k, dim3(B), dim3(64), (((size_t)dim * 4 + 15) & ~(size_t)15), st, d_q, (u64)dim, d_qrm, B, ix->d_raw, (u64)dim,
-                           ix->d_raw_mags, dim, d_pool, 5 * top_k, top_k, ix->p.id_base, d_oi, d_os, d_oc);
+        if (R == 1) {
+            hipLaunchKernelGGL(flat_rerank_top5k, dim3(B), dim3(64), (((size_t)dim * 4 + 15) & ~(size_t)15), st, d_q, (u64)dim, d_qrm, B, ix->d_raw, (u64)dim,
+                               ix->d_raw_mags, dim, d_pool, 5 * top_k, top_k, ix->p.id_base, d_oi, d_os, d_oc);
+        } else {
+            e = launch_flat_rerank_wide(R, false, d_q, (u64)dim, d_qrm, B, ix->d_raw, (u64)dim, ix->d_raw_mags, dim, d_pool, 5 * top_k, top_k, ix->p.id_base,
+                                        d_oi, d_os, d_oc, st);
+            if (e != hipSuccess) break;
+        }
         hipLaunchKernelGGL(flat_pack_out_kernel, dim3((u32)((std::max<size_t>(nk, B) + 255) / 256)), dim3(256), 0, st, d_oi, d_os, d_oc, d_zero, B, top_k, W->out.p);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(W->h_out, W->out.p, out_words * 4, hipMemcpyDeviceToHost, st);

@@ -1,0 +1,276 @@
+// kernels_flat_wide.hip — what stands behind the exhaustive scans' MFMA kernels when a query keeps more than 64 survivors
+// (cos_flat_search_batch with top_k > 12, cos_bruteforce_topk with k > 32): pools of P = 64 * R keys, R = 2, 4, 8, 16.  The scan
+// kernels (kernels_flat.hip, kernels_scan.hip) do not know the width: they read a threshold per query and append to app[B][cap].
+//   flat_select_segments_w<R>  one wave per (query, segment of the score chunk) -> the segment's sorted top P
+//   flat_select_merge_w<R>     one wave per query merges the S sorted partial lists into the query's pool
+//   flat_select_append_w<R>    one wave per query folds the fused scan's append buffer into the pool
+//   flat_rerank_w<R, BRUTE>    one workgroup (4 waves) per query: exact re-score of the survivors, sort, top k
+// A pool lives sorted (descending) in registers, R keys per lane, blocked layout e = lane * R + r, and in memory as pool[q][e].
+// Keys enter it BATCH-WISE: what beats the threshold is compacted into an LDS batch of up to P keys; a full batch is sorted with
+// bitonic_sort_desc<R> and merged with the pool in one bitonic merge (max(pool[e], batch[P - 1 - e]) is bitonic and holds the best P
+// of both).  A single key inserted into a 64 * R register pool costs ~6 R instructions; the seed chunk and an
+// append fold pass thousands of keys per query, so here the cost per key is that of the sort divided by the batch: ~R log^2(P) / P.
+// Keys are unique ((simkey, id) with distinct ids), so "larger id first among equal scores" is simply the order of the u64 keys.
+#include <hip/hip_runtime.h>
+
+#include "dot_engines.h"
+#include "engine_internal.h"
+#include "flat_scan.h"
+
+using namespace cosdev;
+
+namespace {
+
+// a bitonic sequence of 64 * R keys (blocked layout) -> sorted descending: the last stage of bitonic_sort_desc<R>
+template <int R, int STRIDE>
+__device__ __forceinline__ void bitonic_merge_step(u64 (&k)[R], int lane) {
+    if constexpr (STRIDE >= R) {
+        constexpr int lmask = STRIDE / R;
+        const bool lower = (lane & lmask) == 0;
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            const u64 other = shfl_xor_u64(k[r], lmask);
+            const u64 mx = k[r] > other ? k[r] : other, mn = k[r] > other ? other : k[r];
+            k[r] = lower ? mx : mn;
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            if ((r & STRIDE) == 0) {
+                const u64 a = k[r], b = k[r | STRIDE];
+                k[r] = a > b ? a : b;
+                k[r | STRIDE] = a > b ? b : a;
+            }
+        }
+    }
+    if constexpr (STRIDE > 1) bitonic_merge_step<R, STRIDE / 2>(k, lane);
+}
+template <int R>
+__device__ __forceinline__ void bitonic_merge_desc(u64 (&k)[R], int lane) {
+    bitonic_merge_step<R, WAVE * R / 2>(k, lane);
+}
+
+// pool, other: sorted descending -> pool = the best 64 * R of both, sorted descending
+template <int R>
+__device__ __forceinline__ void merge_sorted_desc(u64 (&pool)[R], const u64 (&other)[R], int lane) {
+#pragma unroll
+    for (int r = 0; r < R; r++) { // position e of the reversed list = position P - 1 - e = (lane 63 - lane, register R - 1 - r)
+        const u64 o = other[R - 1 - r];
+        const u32 lo = (u32)__shfl((int)(u32)o, 63 - lane, WAVE), hi = (u32)__shfl((int)(u32)(o >> 32), 63 - lane, WAVE);
+        const u64 rev = ((u64)hi << 32) | lo;
+        pool[r] = pool[r] > rev ? pool[r] : rev;
+    }
+    bitonic_merge_desc<R>(pool, lane);
+}
+
+// `count` keys, key i = load(i), folded into the sorted pool; thr = the pool's P-th best (0 while it is not full) on entry and exit.
+// batch: P keys of LDS, this wave's own (the workgroup is one wave: the barriers only order the LDS traffic).
+template <int R, typename Load>
+__device__ __forceinline__ void fold_stream(u64 (&pool)[R], u64 &thr, u64 *batch, u32 count, Load load, int lane) {
+    constexpr u32 P = WAVE * R;
+    u32 cnt = 0; // keys in the batch (wave-uniform)
+    auto flush = [&]() {
+        __syncthreads();
+        u64 b[R];
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            const u32 i = (u32)lane * R + r;
+            b[r] = i < cnt ? batch[i] : 0ull;
+        }
+        __syncthreads();
+        bitonic_sort_desc<R>(b, lane);
+        merge_sorted_desc<R>(pool, b, lane);
+        thr = readlane_u64(pool[R - 1], WAVE - 1);
+        cnt = 0;
+    };
+    const u64 below = (1ull << lane) - 1ull;
+    for (u32 c = 0; c < count; c += WAVE) {
+        if (cnt + WAVE > P) flush(); // the batch may not take 64 more: every write below stays inside batch[P]
+        const u64 key = c + lane < count ? load(c + (u32)lane) : 0ull;
+        const bool in = key > thr;
+        const u64 m = ballot64(in);
+        if (in) batch[cnt + (u32)__popcll(m & below)] = key;
+        cnt += (u32)__popcll(m);
+    }
+    if (cnt) flush();
+}
+
+template <int R>
+__global__ __launch_bounds__(64) void flat_select_segments_w(const float *__restrict__ scores, u64 s_stride, u32 B, u32 n0, u32 n_chunk, u32 seg_len,
+                                                             u64 *__restrict__ part /*[B][S][64 R]*/) {
+    __shared__ u64 batch[WAVE * R];
+    const int lane = threadIdx.x;
+    const u32 q = blockIdx.x, seg = blockIdx.y, S = gridDim.y;
+    if (q >= B) return;
+    u64 pool[R];
+#pragma unroll
+    for (int r = 0; r < R; r++) pool[r] = 0ull;
+    u64 thr = 0ull;
+    const float *sr = scores + (u64)q * s_stride;
+    const u32 c0 = seg * seg_len, c1 = (c0 + seg_len < n_chunk) ? c0 + seg_len : n_chunk;
+    const u32 count = c1 > c0 ? c1 - c0 : 0u;
+    fold_stream<R>(pool, thr, batch, count, [&](u32 i) { return pack_key(simkey(sr[c0 + i]), n0 + c0 + i); }, lane);
+    u64 *dst = part + ((u64)q * S + seg) * (WAVE * R) + (u32)lane * R;
+#pragma unroll
+    for (int r = 0; r < R; r++) dst[r] = pool[r];
+}
+
+template <int R>
+__global__ __launch_bounds__(64) void flat_select_merge_w(const u64 *__restrict__ part, u32 B, u32 S, u64 *__restrict__ pool_mem /*[B][64 R]*/,
+                                                          u64 *__restrict__ thr_out /*optional [B]*/) {
+    const int lane = threadIdx.x;
+    const u32 q = blockIdx.x;
+    if (q >= B) return;
+    u64 pool[R], b[R];
+    u64 *pm = pool_mem + (u64)q * (WAVE * R) + (u32)lane * R;
+#pragma unroll
+    for (int r = 0; r < R; r++) pool[r] = pm[r];
+    for (u32 sgm = 0; sgm < S; sgm++) {
+        const u64 *src = part + ((u64)q * S + sgm) * (WAVE * R) + (u32)lane * R;
+#pragma unroll
+        for (int r = 0; r < R; r++) b[r] = src[r];
+        merge_sorted_desc<R>(pool, b, lane);
+    }
+#pragma unroll
+    for (int r = 0; r < R; r++) pm[r] = pool[r];
+    const u64 thr = readlane_u64(pool[R - 1], WAVE - 1);
+    if (thr_out && lane == 0) thr_out[q] = thr;
+}
+
+// a counter above `cap` means the scan dropped entries: the flag makes the host repeat the search on the unfused path
+template <int R>
+__global__ __launch_bounds__(64) void flat_select_append_w(const u64 *__restrict__ app, u32 *__restrict__ app_cnt, u32 cap, u32 B, u64 *__restrict__ pool_mem,
+                                                           u64 *__restrict__ thr_out, u32 *__restrict__ overflow) {
+    __shared__ u64 batch[WAVE * R];
+    const int lane = threadIdx.x;
+    const u32 q = blockIdx.x;
+    if (q >= B) return;
+    u64 pool[R];
+    u64 *pm = pool_mem + (u64)q * (WAVE * R) + (u32)lane * R;
+#pragma unroll
+    for (int r = 0; r < R; r++) pool[r] = pm[r];
+    u64 thr = readlane_u64(pool[R - 1], WAVE - 1);
+    u32 cnt = uniform_u32(app_cnt[q]);
+    if (cnt > cap) { if (lane == 0) atomicOr(overflow, 1u); cnt = cap; }
+    const u64 *src = app + (u64)q * cap;
+    fold_stream<R>(pool, thr, batch, cnt, [&](u32 i) { return src[i]; }, lane);
+#pragma unroll
+    for (int r = 0; r < R; r++) pm[r] = pool[r];
+    if (lane == 0) { thr_out[q] = thr; app_cnt[q] = 0; }
+}
+
+// Exact re-score of a query's survivors against the raw f32 rows, sort, top k: the arithmetic of flat_rerank_top5k / flat_rescore
+// (f32_pair_dot, x86_div(dp, |q| * |x|), simkey, pack_key), one lane pair per survivor, 128 survivors per pass of the 4 waves.
+//   BRUTE = false (code scan): the best min(have, ncand_max) entries of the pool (sorted by quantized score) are re-scored;
+//                              min(that, k) results and out_counts
+//   BRUTE = true  (brute force): every survivor with a non-zero score key; k results, ~0 / 0.0 where there is none
+template <int R, bool BRUTE>
+__global__ __launch_bounds__(256) void flat_rerank_w(const float *__restrict__ Q, u64 q_stride, const float *__restrict__ qmags, u32 B,
+                                                     const float *__restrict__ X, u64 x_stride, const float *__restrict__ xmags, u32 dim,
+                                                     const u64 *__restrict__ pool_mem, u32 ncand_max, u32 k, u32 id_base, u32 *__restrict__ out_ids,
+                                                     float *__restrict__ out_scores, u32 *__restrict__ out_counts) {
+    constexpr u32 P = WAVE * R;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    float *qf = (float *)smem_raw;                                            // [dim], padded to 16 B
+    u64 *keys = (u64 *)(smem_raw + (((size_t)dim * 4 + 15) & ~(size_t)15));   // [P]
+    const int tid = threadIdx.x, lane = tid & 63;
+    const u32 q = blockIdx.x;
+    if (q >= B) return;
+    for (u32 i = tid; i < dim; i += 256) qf[i] = Q[(u64)q * q_stride + i];
+    __syncthreads();
+    const u64 *pm = pool_mem + (u64)q * P;
+    const float mq = qmags[q];
+    const u32 lim = BRUTE ? P : (ncand_max < P ? ncand_max : P);
+    for (u32 c0 = 0; c0 < P; c0 += 128) { // (P is a multiple of 128: every lane of a wave runs every pass)
+        const u32 c = c0 + ((u32)tid >> 1);
+        u64 key = 0ull;
+        if (c0 < lim) { // workgroup-uniform
+            const u64 pk = pm[c];
+            const bool valid = BRUTE ? (u32)(pk >> 32) != 0u : (pk != 0ull && c < lim);
+            const u32 sid = (u32)pk, row = valid ? sid : 0u;
+            const float dp = f32_pair_dot(X + (u64)row * x_stride, qf, dim, tid & 1);
+            const float cs = x86_div(dp, mq * xmags[row]); // dp / (mag_query * mag_raw), vector_store.rs:427
+            if (valid) key = pack_key(simkey(cs), sid);
+        }
+        if ((tid & 1) == 0) keys[c] = key;
+    }
+    __syncthreads();
+    if (tid >= 64) return;
+    u64 res[R];
+    u32 have = 0;
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        res[r] = keys[(u32)lane * R + r];
+        if constexpr (!BRUTE) have += (u32)__popcll(ballot64(pm[(u32)lane * R + r] != 0ull));
+    }
+    bitonic_sort_desc<R>(res, lane);
+    if constexpr (BRUTE) {
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            const u32 e = (u32)lane * R + r;
+            if (e < k) {
+                const bool ok = res[r] != 0ull;
+                out_ids[(u64)q * k + e] = ok ? (u32)res[r] + id_base : 0xFFFFFFFFu;
+                out_scores[(u64)q * k + e] = ok ? simkey_inv((u32)(res[r] >> 32)) : 0.0f;
+            }
+        }
+    } else {
+        const u32 ncand = have < lim ? have : lim;
+        const u32 nout = ncand < k ? ncand : k;
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            const u32 e = (u32)lane * R + r;
+            if (e < nout) {
+                out_ids[(u64)q * k + e] = (u32)res[r] + id_base;
+                out_scores[(u64)q * k + e] = simkey_inv((u32)(res[r] >> 32));
+            }
+        }
+        if (lane == 0) out_counts[q] = nout;
+    }
+}
+
+} // namespace
+
+namespace cosdev {
+
+#define WIDE_DISPATCH(R, CALL)                       \
+    switch (R) {                                     \
+    case 2: { constexpr int RR = 2; CALL; } break;   \
+    case 4: { constexpr int RR = 4; CALL; } break;   \
+    case 8: { constexpr int RR = 8; CALL; } break;   \
+    case 16: { constexpr int RR = 16; CALL; } break; \
+    default: return hipErrorInvalidValue;            \
+    }
+
+hipError_t launch_flat_select_wide(u32 R, const float *d_scores, u64 s_stride, u32 B, u32 n0, u32 nc, u64 *d_part, u32 S, u64 *d_pool, u64 *d_thr,
+                                   hipStream_t st) {
+    const u32 seg_len = ((nc + S - 1) / S + 63) / 64 * 64;
+    WIDE_DISPATCH(R, hipLaunchKernelGGL(flat_select_segments_w<RR>, dim3(B, S), dim3(64), 0, st, d_scores, s_stride, B, n0, nc, seg_len, d_part))
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    WIDE_DISPATCH(R, hipLaunchKernelGGL(flat_select_merge_w<RR>, dim3(B), dim3(64), 0, st, (const u64 *)d_part, B, S, d_pool, d_thr))
+    return hipGetLastError();
+}
+
+hipError_t launch_flat_append_wide(u32 R, const u64 *d_app, u32 *d_appcnt, u32 cap, u32 B, u64 *d_pool, u64 *d_thr, u32 *d_overflow, hipStream_t st) {
+    WIDE_DISPATCH(R, hipLaunchKernelGGL(flat_select_append_w<RR>, dim3(B), dim3(64), 0, st, d_app, d_appcnt, cap, B, d_pool, d_thr, d_overflow))
+    return hipGetLastError();
+}
+
+hipError_t launch_flat_rerank_wide(u32 R, bool brute, const float *Q, u64 q_stride, const float *qmags, u32 B, const float *X, u64 x_stride,
+                                   const float *xmags, u32 dim, const u64 *d_pool, u32 ncand_max, u32 k, u32 id_base, u32 *out_ids, float *out_scores,
+                                   u32 *out_counts, hipStream_t st) {
+    const size_t smem = (((size_t)dim * 4 + 15) & ~(size_t)15) + (size_t)R * 64 * 8;
+#define RERANK_ARGS Q, q_stride, qmags, B, X, x_stride, xmags, dim, d_pool, ncand_max, k, id_base, out_ids, out_scores, out_counts
+    if (brute) {
+        WIDE_DISPATCH(R, hipLaunchKernelGGL((flat_rerank_w<RR, true>), dim3(B), dim3(256), smem, st, RERANK_ARGS))
+    } else {
+        WIDE_DISPATCH(R, hipLaunchKernelGGL((flat_rerank_w<RR, false>), dim3(B), dim3(256), smem, st, RERANK_ARGS))
+    }
+#undef RERANK_ARGS
+    return hipGetLastError();
+}
+
+#undef WIDE_DISPATCH
+
+} // namespace cosdev

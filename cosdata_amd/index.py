@@ -450,7 +450,9 @@ class HNSWIndex:
         return st
 
     def flat_search(self, queries, top_k: int, with_stats: bool = False):
-        """Exhaustive search over the quantized codes (i8 MFMA GEMM) + exact rerank of the best 5k."""
+        """Exhaustive search over the quantized codes (i8 MFMA GEMM) + exact rerank of the best 5 * top_k.
+        top_k in [1, 204] (status 4, Unimplemented, above): a query keeps the smallest pool of 64 .. 1024 survivors that holds
+        5 * top_k; the append buffer of a wide call (top_k > 12) costs 256 bytes per pool slot and query (include/cosdata_hip.h)."""
         q = self._queries(queries)
         B = q.shape[0]
         ids = np.full((B, top_k), 0xFFFFFFFF, np.uint32)
@@ -461,6 +463,8 @@ class HNSWIndex:
         return (ids, scores, counts, st) if with_stats else (ids, scores, counts)
 
     def bruteforce_topk(self, queries, k: int):
+        """Exact cosine top-k over the raw vectors (f32 MFMA GEMM for candidates + reference-order re-score): the recall ground truth.
+        k in [1, min(512, n)] (status 3, Invalid, outside); a query keeps the smallest pool of 64 .. 1024 survivors that holds 2k."""
         q = self._queries(queries)
         ids = np.zeros((q.shape[0], k), np.uint32)
         scores = np.zeros((q.shape[0], k), np.float32)

@@ -373,15 +373,28 @@ int32_t cos_distance_batch(uint32_t metric, uint32_t storage, uint32_t resolutio
                            const uint32_t *pair_x, const uint32_t *pair_y, uint32_t n_pairs, float *out,
                            int32_t *status);
 /* exact brute-force cosine top-k on the resident raw vectors (ground truth for recall@k):
- * MFMA f32 GEMM for candidate generation + reference-order re-score of the survivors. */
+ * MFMA f32 GEMM for candidate generation + reference-order re-score of the survivors.
+ * k in [1, min(512, n)], anything else is COS_ERR_INVALID.  A query keeps a pool of P survivors, the smallest of
+ * 64, 128, 256, 512, 1024 with 2k <= P (the GEMM's summation order differs from the reference's in the last ulp:
+ * it only generates candidates).  Device memory of a call beyond the score chunk, per query: 8 P bytes of pool,
+ * up to 512 P bytes of per-segment partial pools (fewer for batches above 64 queries) and, above 16384 vectors, the
+ * append buffer of the threshold-filtered scan: 32 KB at P = 64, 256 P bytes (32 KB .. 256 KB) at P >= 128. */
 int32_t cos_bruteforce_topk(cos_index *ix, const float *queries, uint32_t B, uint32_t k, uint32_t *out_ids,
                             float *out_scores);
 
 /* Exhaustive search over the index's QUANTIZED codes (u8 / quaternary) as an exact-integer i8 MFMA GEMM,
  * then the reference's finalisation on the full candidate set: sort by quantized score (desc, larger id
- * first), keep 5k, exact f32 rerank (vector_store.rs:404-445), top-k (k <= 12).  The result is what
+ * first), keep 5k, exact f32 rerank (vector_store.rs:404-445), top-k.  The result is what
  * ann_search + finalize_ann_results would return if the walk visited every node: config c3's flat scan and
- * the exhaustive per-shard mode.  Host buffers. */
+ * the exhaustive per-shard mode.  Host buffers.
+ * top_k in [1, 204]; above that COS_ERR_UNIMPLEMENTED (the handle stays usable).  A query keeps a pool of P
+ * survivors, the smallest of 64, 128, 256, 512, 1024 with 5 * top_k <= P: top_k <= 12 runs the 64-key kernels,
+ * 13..25 P = 128, 26..51 P = 256, 52..102 P = 512, 103..204 P = 1024.  The index's workspace grows to the widest call
+ * it has served and stays until the index is destroyed or its vectors are replaced; per query it holds 8 P bytes of pool,
+ * up to 512 P bytes of per-segment partial pools (fewer for batches above 64 queries) and the append buffer of the
+ * threshold-filtered scan: 32 KB at P = 64, 256 P bytes at P >= 128 (32 KB at top_k 13..25 up to 256 KB at
+ * top_k 103..204: 64 MB for a 256-query call).  A call indexes the workspace by its own P: a narrow call after a wide
+ * one returns the bits it returned before. */
 typedef struct {
     float gemm_ms;          /* summed HIP-event time of the i8 MFMA GEMM launches */
     uint32_t gemm_launches;
