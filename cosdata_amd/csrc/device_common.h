@@ -1,4 +1,5 @@
-// device_common.h — wave64 helpers shared by the gfx950 kernels (CDNA4 only; no CUDA path).
+// device_common.h — wave64 helpers shared by the gfx950 kernels (CDNA4 only; no CUDA path): keys, lane primitives, reductions.
+// Pools, sorts and merges of keys are in topk_select.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -205,116 +206,5 @@ __device__ __forceinline__ void static_for(F &&f) {
         static_for<I + 1, N>(f);
     }
 }
-
-// Bitonic sort (descending) of 64*R u64 keys held R per lane, blocked layout e = lane*R + r.
-// Empty entries are 0 and sink to the end.  Fully unrolled: every register index is static.
-template <int R>
-__device__ __forceinline__ void bitonic_sort_desc(u64 (&k)[R], int lane) {
-    constexpr int N = WAVE * R;
-#pragma unroll
-    for (int size = 2; size <= N; size <<= 1) {
-#pragma unroll
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            if (stride >= R) {
-                const int lmask = stride / R;
-#pragma unroll
-                for (int r = 0; r < R; r++) {
-                    u64 other = shfl_xor_u64(k[r], lmask);
-                    int e = lane * R + r;
-                    bool desc = (e & size) == 0;
-                    bool lower = (e & stride) == 0;
-                    bool keepmax = (desc == lower);
-                    u64 mx = k[r] > other ? k[r] : other;
-                    u64 mn = k[r] > other ? other : k[r];
-                    k[r] = keepmax ? mx : mn;
-                }
-            } else {
-#pragma unroll
-                for (int r = 0; r < R; r++) {
-                    if ((r & stride) == 0) {
-                        int e = lane * R + r;
-                        bool desc = (e & size) == 0;
-                        u64 a = k[r], b = k[r | stride];
-                        u64 mx = a > b ? a : b, mn = a > b ? b : a;
-                        k[r] = desc ? mx : mn;
-                        k[r | stride] = desc ? mn : mx;
-                    }
-                }
-            }
-        }
-    }
-}
-
-// Sorted (descending) candidate pool of 64*R u64 keys, blocked layout e = lane*R + r; 0 = empty.
-// Replaces the reference's BinaryHeap (vector_store.rs:1125): only the best (ef - popped) entries
-// can ever be popped, so a bounded sorted pool reproduces the pop sequence exactly.
-template <int R>
-struct Pool {
-    u64 e[R];
-    __device__ __forceinline__ void clear() {
-#pragma unroll
-        for (int r = 0; r < R; r++) e[r] = 0;
-    }
-    __device__ __forceinline__ u64 head() const { return readlane_u64(e[0], 0); }
-    // entry at sorted position I (wave-uniform result); static register index
-    template <int I>
-    __device__ __forceinline__ u64 peek() const { return readlane_u64(e[I % R], I / R); }
-    // entry at sorted position pos, pos wave-uniform but only known at run time.  Every register's candidate is read with
-    // v_readlane and the choice is made among SCALARS: selecting the vector register first (x = e[pos % R]) made the compiler
-    // index the pool as an array and move it to scratch memory (40 B per lane, the ef 256 walk 35 % slower).
-    __device__ __forceinline__ u64 peek_dyn(u32 pos) const {
-        const int l = (int)(pos / (u32)R);
-        const u32 rr = pos % (u32)R;
-        u64 v = readlane_u64(e[0], l);
-#pragma unroll
-        for (int r = 1; r < R; r++) {
-            const u64 t = readlane_u64(e[r], l);
-            v = rr == (u32)r ? t : v;
-        }
-        return v;
-    }
-    // node index (low half) of the entry at sorted position I: one v_readlane
-    template <int I>
-    __device__ __forceinline__ u32 peek_node() const { return readlane_u32((u32)e[I % R], I / R); }
-    __device__ __forceinline__ void pop_head(int lane) {
-        // lane l <- lane l+1's first entry; lane 63 <- empty (bound_ctrl zero fill: two DPP moves, nothing else)
-        const u64 nxt = ((u64)dpp_mov_z<0x130>((u32)(e[0] >> 32)) << 32) | dpp_mov_z<0x130>((u32)e[0]);
-#pragma unroll
-        for (int r = 0; r + 1 < R; r++) e[r] = e[r + 1];
-        e[R - 1] = nxt;
-    }
-    // number of entries strictly greater than k (= insertion position); k is wave-uniform
-    __device__ __forceinline__ int rank_of(u64 k) const {
-        int p = 0;
-#pragma unroll
-        for (int r = 0; r < R; r++) p += __popcll(__ballot(e[r] > k));
-        return p;
-    }
-    // insert wave-uniform key k at position p (entries >= p shift up by one, the last one drops)
-    __device__ __forceinline__ void insert_at(u64 k, int p, int lane) {
-        if constexpr (R == 1) {
-            // one entry per lane: lanes above p take their lower neighbour's entry (two DPP moves + one compare + two selects),
-            // lane p takes k by v_writelane (no compare against p, no broadcast of k into a VGPR pair)
-            u32 lo = (u32)e[0], hi = (u32)(e[0] >> 32);
-            const u32 slo = dpp_mov_z<0x138>(lo), shi = dpp_mov_z<0x138>(hi); // lane 0 has no lower neighbour and never shifts
-            const bool up = lane > p;
-            lo = up ? slo : lo;
-            hi = up ? shi : hi;
-            lo = writelane_dyn(lo, (u32)k, p);
-            hi = writelane_dyn(hi, (u32)(k >> 32), p);
-            e[0] = ((u64)hi << 32) | lo;
-            return;
-        }
-        const int lp = p / R, rp = p % R;
-        const u64 prev_last = dpp_wave_shr1_u64(e[R - 1], 0ull); // lane l <- lane l-1's last entry
-#pragma unroll
-        for (int r = R - 1; r >= 0; r--) {
-            u64 src = (r == 0) ? prev_last : e[r > 0 ? r - 1 : 0];
-            bool shift = (lane > lp) || (lane == lp && r > rp);
-            bool ins = (lane == lp && r == rp);
-            e[r] = ins ? k : (shift ? src : e[r]);
-        }
-    }
-};
 
 } // namespace cosdev

@@ -22,6 +22,7 @@
 #include "dot_engines.h"
 #include "engine_internal.h"
 #include "flat_scan.h"
+#include "topk_select.h"
 
 using namespace cosdev;
 
@@ -208,16 +209,7 @@ __global__ __launch_bounds__(64) void flat_select_segments(const float *__restri
         const u32 col = c + lane;
         u64 key = 0ull;
         if (col < c1) key = pack_key(simkey(sr[col]), n0 + col);
-        u64 m = __ballot(key > thr);
-        while (m) {
-            const int l = __ffsll((long long)m) - 1;
-            m &= m - 1;
-            const u64 kk = readlane_u64(key, l);
-            if (kk > thr) {
-                pool.insert_at(kk, pool.rank_of(kk), lane);
-                thr = readlane_u64(pool.e[0], SEL - 1);
-            }
-        }
+        pool_fold_lanes<1>(pool, thr, key, lane);
     }
     part[((u64)q * S + seg) * SEL + lane] = pool.e[0];
 }
@@ -232,16 +224,7 @@ __global__ __launch_bounds__(64) void flat_select_merge(const u64 *__restrict__ 
     u64 thr = readlane_u64(pool.e[0], SEL - 1);
     for (u32 sgm = 0; sgm < S; sgm++) {
         const u64 key = part[((u64)q * S + sgm) * SEL + lane];
-        u64 m = __ballot(key > thr);
-        while (m) {
-            const int l = __ffsll((long long)m) - 1;
-            m &= m - 1;
-            const u64 kk = readlane_u64(key, l);
-            if (kk > thr) {
-                pool.insert_at(kk, pool.rank_of(kk), lane);
-                thr = readlane_u64(pool.e[0], SEL - 1);
-            }
-        }
+        pool_fold_lanes<1>(pool, thr, key, lane);
     }
     pool_mem[(u64)q * SEL + lane] = pool.e[0];
     if (thr_out && lane == 0) thr_out[q] = thr;
@@ -262,16 +245,7 @@ __global__ __launch_bounds__(64) void flat_select_append(const u64 *__restrict__
     if (cnt > cap) { if (lane == 0) atomicOr(overflow, 1u); cnt = cap; }
     for (u32 c = 0; c < cnt; c += 64) {
         const u64 key = c + lane < cnt ? app[(u64)q * cap + c + lane] : 0ull;
-        u64 m = __ballot(key > thr);
-        while (m) {
-            const int l = __ffsll((long long)m) - 1;
-            m &= m - 1;
-            const u64 kk = readlane_u64(key, l);
-            if (kk > thr) {
-                pool.insert_at(kk, pool.rank_of(kk), lane);
-                thr = readlane_u64(pool.e[0], SEL - 1);
-            }
-        }
+        pool_fold_lanes<1>(pool, thr, key, lane);
     }
     pool_mem[(u64)q * SEL + lane] = pool.e[0];
     if (lane == 0) { thr_out[q] = thr; app_cnt[q] = 0; }

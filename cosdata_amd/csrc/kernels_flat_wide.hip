@@ -5,95 +5,20 @@
 //   flat_select_merge_w<R>     one wave per query merges the S sorted partial lists into the query's pool
 //   flat_select_append_w<R>    one wave per query folds the fused scan's append buffer into the pool
 //   flat_rerank_w<R, BRUTE>    one workgroup (4 waves) per query: exact re-score of the survivors, sort, top k
-// A pool lives sorted (descending) in registers, R keys per lane, blocked layout e = lane * R + r, and in memory as pool[q][e].
-// Keys enter it BATCH-WISE: what beats the threshold is compacted into an LDS batch of up to P keys; a full batch is sorted with
-// bitonic_sort_desc<R> and merged with the pool in one bitonic merge (max(pool[e], batch[P - 1 - e]) is bitonic and holds the best P
-// of both).  A single key inserted into a 64 * R register pool costs ~6 R instructions; the seed chunk and an
-// append fold pass thousands of keys per query, so here the cost per key is that of the sort divided by the batch: ~R log^2(P) / P.
-// Keys are unique ((simkey, id) with distinct ids), so "larger id first among equal scores" is simply the order of the u64 keys.
+// A pool lives sorted in registers, R keys per lane, and in memory as pool[q][e] (the conventions of topk_select.h).  Keys enter it
+// BATCH-WISE through fold_stream<R> of that header (sort a batch of up to P keys, one bitonic merge with the pool): the seed chunk and
+// an append fold pass thousands of keys per query, and a single insert into a 64 * R register pool costs ~6 R instructions
+// (DESIGN.md §4.9).  This file holds the kernels and their launchers only.
 #include <hip/hip_runtime.h>
 
 #include "dot_engines.h"
 #include "engine_internal.h"
 #include "flat_scan.h"
+#include "topk_select.h"
 
 using namespace cosdev;
 
 namespace {
-
-// a bitonic sequence of 64 * R keys (blocked layout) -> sorted descending: the last stage of bitonic_sort_desc<R>
-template <int R, int STRIDE>
-__device__ __forceinline__ void bitonic_merge_step(u64 (&k)[R], int lane) {
-    if constexpr (STRIDE >= R) {
-        constexpr int lmask = STRIDE / R;
-        const bool lower = (lane & lmask) == 0;
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            const u64 other = shfl_xor_u64(k[r], lmask);
-            const u64 mx = k[r] > other ? k[r] : other, mn = k[r] > other ? other : k[r];
-            k[r] = lower ? mx : mn;
-        }
-    } else {
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            if ((r & STRIDE) == 0) {
-                const u64 a = k[r], b = k[r | STRIDE];
-                k[r] = a > b ? a : b;
-                k[r | STRIDE] = a > b ? b : a;
-            }
-        }
-    }
-    if constexpr (STRIDE > 1) bitonic_merge_step<R, STRIDE / 2>(k, lane);
-}
-template <int R>
-__device__ __forceinline__ void bitonic_merge_desc(u64 (&k)[R], int lane) {
-    bitonic_merge_step<R, WAVE * R / 2>(k, lane);
-}
-
-// pool, other: sorted descending -> pool = the best 64 * R of both, sorted descending
-template <int R>
-__device__ __forceinline__ void merge_sorted_desc(u64 (&pool)[R], const u64 (&other)[R], int lane) {
-#pragma unroll
-    for (int r = 0; r < R; r++) { // position e of the reversed list = position P - 1 - e = (lane 63 - lane, register R - 1 - r)
-        const u64 o = other[R - 1 - r];
-        const u32 lo = (u32)__shfl((int)(u32)o, 63 - lane, WAVE), hi = (u32)__shfl((int)(u32)(o >> 32), 63 - lane, WAVE);
-        const u64 rev = ((u64)hi << 32) | lo;
-        pool[r] = pool[r] > rev ? pool[r] : rev;
-    }
-    bitonic_merge_desc<R>(pool, lane);
-}
-
-// `count` keys, key i = load(i), folded into the sorted pool; thr = the pool's P-th best (0 while it is not full) on entry and exit.
-// batch: P keys of LDS, this wave's own (the workgroup is one wave: the barriers only order the LDS traffic).
-template <int R, typename Load>
-__device__ __forceinline__ void fold_stream(u64 (&pool)[R], u64 &thr, u64 *batch, u32 count, Load load, int lane) {
-    constexpr u32 P = WAVE * R;
-    u32 cnt = 0; // keys in the batch (wave-uniform)
-    auto flush = [&]() {
-        __syncthreads();
-        u64 b[R];
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            const u32 i = (u32)lane * R + r;
-            b[r] = i < cnt ? batch[i] : 0ull;
-        }
-        __syncthreads();
-        bitonic_sort_desc<R>(b, lane);
-        merge_sorted_desc<R>(pool, b, lane);
-        thr = readlane_u64(pool[R - 1], WAVE - 1);
-        cnt = 0;
-    };
-    const u64 below = (1ull << lane) - 1ull;
-    for (u32 c = 0; c < count; c += WAVE) {
-        if (cnt + WAVE > P) flush(); // the batch may not take 64 more: every write below stays inside batch[P]
-        const u64 key = c + lane < count ? load(c + (u32)lane) : 0ull;
-        const bool in = key > thr;
-        const u64 m = ballot64(in);
-        if (in) batch[cnt + (u32)__popcll(m & below)] = key;
-        cnt += (u32)__popcll(m);
-    }
-    if (cnt) flush();
-}
 
 template <int R>
 __global__ __launch_bounds__(64) void flat_select_segments_w(const float *__restrict__ scores, u64 s_stride, u32 B, u32 n0, u32 n_chunk, u32 seg_len,

@@ -24,6 +24,7 @@
 
 #include "engine_internal.h"
 #include "postings_update.h"
+#include "topk_select.h"
 
 using namespace cosdev;
 

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "engine_internal.h"
+#include "topk_select.h"
 
 using namespace cosdev;
 

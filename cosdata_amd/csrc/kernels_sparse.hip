@@ -19,6 +19,7 @@
 
 #include "engine_internal.h"
 #include "postings_update.h"
+#include "topk_select.h"
 
 using namespace cosdev;
 
@@ -40,13 +41,15 @@ struct SparseDev {
     float upper;
 };
 
-// Rust `as u8` / `as u32` on f32 (saturating, NaN -> 0) and f32::clamp
-__device__ __forceinline__ u32 f32_as_u8(float v) { return !(v == v) || v <= 0.0f ? 0u : (v >= 255.0f ? 255u : (u32)(int)v); }
-__device__ __forceinline__ u32 f32_as_u32(float v) { return !(v == v) || v <= 0.0f ? 0u : (v >= 4294967296.0f ? 0xFFFFFFFFu : (u32)v); }
-__device__ __forceinline__ u32 sparse_quantize(float value, float upper, u32 bits) { // inverted_index.rs:168-172
+// Rust `as u8` / `as u32` on f32 (saturating, NaN -> 0) and f32::clamp; host and device
+__host__ __device__ __forceinline__ u32 f32_as_u8(float v) { return !(v == v) || v <= 0.0f ? 0u : (v >= 255.0f ? 255u : (u32)(int)v); }
+__host__ __device__ __forceinline__ u32 f32_as_u32(float v) { return !(v == v) || v <= 0.0f ? 0u : (v >= 4294967296.0f ? 0xFFFFFFFFu : (u32)v); }
+// InvertedIndexNode::quantize, inverted_index.rs:168-172: one correctly rounded division, one multiplication (this file is built with
+// -ffp-contract=off and -fhip-fp32-correctly-rounded-divide-sqrt: the device runs the host's two f32 operations)
+__host__ __device__ __forceinline__ u32 sparse_quantize(float value, float upper, u32 bits) {
     const u32 quantization = (1u << bits) - 1u;
     const float max_val = (float)quantization;
-    float t = __fmul_rn(__fdiv_rn(value, upper), max_val);
+    float t = (value / upper) * max_val;
     t = t < 0.0f ? 0.0f : (t > max_val ? max_val : t); // clamp keeps NaN
     const u32 q = f32_as_u8(t);
     return q < quantization ? q : quantization;
@@ -80,69 +83,84 @@ struct SCursor { // block-uniform
     bool valid;
 };
 
-// ---- the wide path's merges (R > 1): block-wide bitonic networks over u64 keys in LDS --------------------------------------------
-// Three wave pools of 1024 keys folded into the fourth by single inserts would be 3072 inserts of ~150 wave instructions each, on
-// one wave, per block; a bitonic merge is log2(N) rounds of one compare-exchange per thread and pair.
-// `nseq` bitonic sequences of N keys, sequence j at buf + j * pitch -> each sorted descending.  Ends with a barrier.
-template <u32 N>
-__device__ __forceinline__ void lds_bitonic_merge_desc(u64 *buf, u32 nseq, u32 pitch) {
-    for (u32 stride = N / 2; stride > 0; stride >>= 1) {
-        __syncthreads();
-        for (u32 p = threadIdx.x; p < nseq * (N / 2); p += blockDim.x) {
-            u64 *b = buf + (p / (N / 2)) * pitch;
-            const u32 j = p % (N / 2);
-            const u32 i = ((j & ~(stride - 1u)) << 1) | (j & (stride - 1u)); // the pair (i, i + stride)
-            const u64 x = b[i], y = b[i + stride];
-            if (x < y) { b[i] = y; b[i + stride] = x; }
-        }
-    }
-    __syncthreads();
-}
-// any N keys -> sorted descending (0 = empty sinks to the end).  Ends with a barrier.
-template <u32 N>
-__device__ __forceinline__ void lds_bitonic_sort_desc(u64 *buf) {
-    for (u32 size = 2; size <= N; size <<= 1)
-        for (u32 stride = size >> 1; stride > 0; stride >>= 1) {
-            __syncthreads();
-            for (u32 j = threadIdx.x; j < N / 2; j += blockDim.x) {
-                const u32 i = ((j & ~(stride - 1u)) << 1) | (j & (stride - 1u));
-                const bool desc = (i & size) == 0u;
-                const u64 x = buf[i], y = buf[i + stride];
-                if ((x < y) == desc) { buf[i] = y; buf[i + stride] = x; }
-            }
-        }
-    __syncthreads();
-}
-// best[i] = max(best[i], other[N - 1 - i]) for two descending sequences is a bitonic sequence of the best N keys of both (the
-// first half-cleaner of the merge network); lds_bitonic_merge_desc sorts it.  `other` may be LDS or global memory.
-template <u32 N>
-__device__ __forceinline__ void fold_reversed(u64 *best, const u64 *other) {
-    for (u32 i = threadIdx.x; i < N; i += blockDim.x) {
-        const u64 x = best[i], y = other[N - 1u - i];
-        best[i] = x > y ? x : y;
+// ---- what the tile kernels share ---------------------------------------------------------------------------------------------
+// postings [b, e) of query term t that fall into `tile`: the directory's range for a long list, the whole list for a short one
+__device__ __forceinline__ void slice_lookup(const STerm *__restrict__ qt, u32 t, const u32 *__restrict__ tile_dir, u32 n_tiles, u32 tile, u64 &b, u64 &e) {
+    const u32 dr = qt[t].dir;
+    b = qt[t].begin;
+    e = qt[t].end;
+    if (dr != SNO_DIR) {
+        const u32 *row = tile_dir + (u64)dr * (n_tiles + 1);
+        e = b + row[tile + 1];
+        b = b + row[tile];
     }
 }
-// A block's four wave pools (each sorted descending, blocked layout) -> ONE sorted segment of the block's best 64 * R keys in out[]:
-// the finish kernel then folds `splits` segments per query, not 4 * splits, and part[] stays a quarter of the size.  buf = the
-// accumulator tile, dead after the block's last flush and exactly 4 * 1024 u64: the merge costs no LDS, so no occupancy.
-template <int R>
-__device__ __forceinline__ void block_merge_pools(const Pool<R> &pool, u64 *buf, u64 *__restrict__ out, int wave, int lane) {
-    constexpr u32 N = 64u * R;
-    static_assert(4u * N * 8u <= STILE * 4u, "the four pools are staged in the accumulator tile");
-    __syncthreads(); // every wave is done with the tile
+// wave 0, one lane per term (nt <= 64): the step counts of the slices of sl_n[0 .. nt) -> exclusive prefix st_pre[0 .. nt],
+// [nt] = total; the tile's step counter back to 0
+template <u32 STEP>
+__device__ __forceinline__ void step_prefix(const u32 *sl_n, u32 nt, u32 *st_pre, u32 *st_ctr, int lane) {
+    u32 ns = 0;
+    if ((u32)lane < nt) ns = (sl_n[lane] + STEP - 1u) / STEP;
+    u32 incl = ns;
 #pragma unroll
-    for (int r = 0; r < R; r++) buf[(u32)wave * N + (u32)lane * R + r] = pool.e[r];
-    __syncthreads();
-    for (u32 p = threadIdx.x; p < 2u * N; p += blockDim.x) { // pools (0, 1) and (2, 3), as fold_reversed
-        u64 *a = buf + (p / N) * 2u * N;
-        const u32 i = p % N;
-        const u64 x = a[i], y = a[2u * N - 1u - i];
-        a[i] = x > y ? x : y;
+    for (int dd = 1; dd < 64; dd <<= 1) {
+        const u32 o = (u32)__shfl_up((int)incl, dd, 64);
+        if (lane >= dd) incl += o;
     }
-    lds_bitonic_merge_desc<N>(buf, 2, 2 * N);
-    fold_reversed<N>(buf, buf + 2 * N);
-    lds_bitonic_merge_desc<N>(buf, 1, 0);
-    for (u32 i = threadIdx.x; i < N; i += blockDim.x) out[i] = buf[i];
+    if ((u32)lane < nt) st_pre[lane] = incl - ns;
+    if ((u32)lane == nt - 1u) st_pre[nt] = incl;
+    if (lane == 0) *st_ctr = 0u;
+}
+// Flush of a tile whose similarity-0 hits are flag bits: wave w scans slots [w * 2048, (w + 1) * 2048) of the tile, 64 at a time.
+// This takes one slot: its key ((similarity + 1) << 32 | id, 0 = not reached), the accumulator cleared.
+__device__ __forceinline__ u64 take_flagged_slot(u32 *acc, const u32 *zflag, u32 d0, u32 slot) {
+    const u32 a = acc[slot];
+    const u32 fw = zflag[slot >> 5];
+    acc[slot] = 0u;
+    const bool reached = a != 0u || ((fw >> (slot & 31u)) & 1u);
+    return reached ? (((u64)a + 1ull) << 32 | (u64)(d0 + slot)) : 0ull;
+}
+// a block that has nothing to visit writes an empty segment of 64 * R keys (the finish kernel reads every split)
+template <int R>
+__device__ __forceinline__ void write_empty_segment(u64 *out) {
+    if constexpr (R == 1) {
+        if (threadIdx.x < SEL) out[threadIdx.x] = 0ull;
+    } else
+        for (u32 i = threadIdx.x; i < SEL * R; i += blockDim.x) out[i] = 0ull;
+}
+// A block's four wave pools (each sorted, blocked layout) -> ONE sorted segment of the block's best 64 * R keys in out[]: the finish
+// kernel then folds `splits` segments per query, not 4 * splits, and part[] stays a quarter of the size.
+//   R > 1: the LDS networks of topk_select.h over the accumulator tile `acc`, dead after the block's last flush and exactly
+//          4 * 1024 u64: the merge costs no LDS, so no occupancy (wpool is not touched and may be null).
+//   R = 1: through wpool; wave 0 folds the three other pools into its own key by key, with the fold(key) of its flushes.
+template <int R, typename Fold>
+__device__ __forceinline__ void block_merge_pools(const Pool<R> &pool, u64 (*wpool)[SEL], u32 *acc, u64 *__restrict__ out, int wave, int lane, Fold fold) {
+    if constexpr (R == 1) {
+        wpool[wave][lane] = pool.e[0];
+        __syncthreads();
+        if (wave == 0) {
+            for (int w = 1; w < 4; w++) fold(wpool[w][lane]);
+            out[lane] = pool.e[0];
+        }
+    } else {
+        constexpr u32 N = 64u * R;
+        u64 *buf = reinterpret_cast<u64 *>(acc);
+        static_assert(4u * N * 8u <= STILE * 4u, "the four pools are staged in the accumulator tile");
+        __syncthreads(); // every wave is done with the tile
+#pragma unroll
+        for (int r = 0; r < R; r++) buf[(u32)wave * N + (u32)lane * R + r] = pool.e[r];
+        __syncthreads();
+        for (u32 p = threadIdx.x; p < 2u * N; p += blockDim.x) { // pools (0, 1) and (2, 3), as fold_reversed
+            u64 *a = buf + (p / N) * 2u * N;
+            const u32 i = p % N;
+            const u64 x = a[i], y = a[2u * N - 1u - i];
+            a[i] = x > y ? x : y;
+        }
+        lds_bitonic_merge_desc<N>(buf, 2, 2 * N);
+        fold_reversed<N>(buf, buf + 2 * N);
+        lds_bitonic_merge_desc<N>(buf, 1, 0);
+        for (u32 i = threadIdx.x; i < N; i += blockDim.x) out[i] = buf[i];
+    }
 }
 
 // grid = B * splits blocks, heaviest query first: block (q, s) owns the tiles s, s + splits, ...; every wave keeps a private pool
@@ -162,11 +180,8 @@ __global__ __launch_bounds__(256) void sparse_tile_kernel(const u32 *__restrict_
     const u32 t0 = qt_off[q], nt = qt_off[q + 1] - t0;
     const u32 n_tiles = (n + STILE - 1) / STILE;
     u64 *out = part + ((u64)q * splits + split) * (SEL * R);
-    if (nt == 0 || split >= n_tiles) { // nothing to visit: an empty pool (the finish kernel reads every split)
-        if constexpr (R == 1) {
-            if (threadIdx.x < SEL) out[threadIdx.x] = 0ull;
-        } else
-            for (u32 i = threadIdx.x; i < SEL * R; i += blockDim.x) out[i] = 0ull;
+    if (nt == 0 || split >= n_tiles) { // nothing to visit
+        write_empty_segment<R>(out);
         return;
     }
     for (u32 i = threadIdx.x; i < STILE; i += blockDim.x) acc[i] = 0u;
@@ -176,16 +191,9 @@ __global__ __launch_bounds__(256) void sparse_tile_kernel(const u32 *__restrict_
     pool.clear();
     u64 thr = 0ull;
 
-    auto slice_global = [&](u32 tile, u32 t, u64 &b, u64 &e) {
-        const u32 dr = qt[t].dir;
-        b = qt[t].begin;
-        e = qt[t].end;
-        if (dr != SNO_DIR) {
-            const u32 *row = tile_dir + (u64)dr * (n_tiles + 1);
-            e = b + row[tile + 1];
-            b = b + row[tile];
-        }
-    };
+    // __ballot, as this kernel always voted; pool_fold_lanes' ballot64 is the same vote in fewer instructions, but switching is a change to time
+    auto fold_keys = [&](u64 key) { pool_fold_mask<R>(pool, thr, key, __ballot(key > thr), lane); };
+    auto slice_global = [&](u32 tile, u32 t, u64 &b, u64 &e) { slice_lookup(qt, t, tile_dir, n_tiles, tile, b, e); };
     // The (tile, term) slices of this block, resolved once, all lookups in flight together: a chunk used to start with two
     // DEPENDENT global loads (the term's directory row, then its two entries) that nothing overlapped — with ~900 postings per slice
     // the kernel spent more time finding its slices than streaming them (0.95 ms per 256-query batch, 0.14 of the HBM roof).
@@ -262,25 +270,7 @@ __global__ __launch_bounds__(256) void sparse_tile_kernel(const u32 *__restrict_
         const bool tile_done = !nx.valid || nx.tile != c.tile;
         if (tile_done) {
             __syncthreads();
-            // flush: wave w scans slots [w * 2048, (w + 1) * 2048) of the tile, 64 at a time, into its pool
-            for (u32 s0 = (u32)wave * (STILE / 4); s0 < (u32)(wave + 1) * (STILE / 4); s0 += 64) {
-                const u32 slot = s0 + (u32)lane;
-                const u32 a = acc[slot];
-                const u32 fw = zflag[slot >> 5];
-                acc[slot] = 0u;
-                const bool reached = a != 0u || ((fw >> (slot & 31u)) & 1u);
-                const u64 key = reached ? (((u64)a + 1ull) << 32 | (u64)(d0 + slot)) : 0ull;
-                u64 m = __ballot(key > thr);
-                while (m) {
-                    const int l = __ffsll((long long)m) - 1;
-                    m &= m - 1;
-                    const u64 kk = readlane_u64(key, l);
-                    if (kk > thr) {
-                        pool.insert_at(kk, pool.rank_of(kk), lane);
-                        thr = readlane_u64(pool.e[R - 1], 63); // the pool's last key
-                    }
-                }
-            }
+            for (u32 s0 = (u32)wave * (STILE / 4); s0 < (u32)(wave + 1) * (STILE / 4); s0 += 64) fold_keys(take_flagged_slot(acc, zflag, d0, s0 + (u32)lane));
             __syncthreads(); // everybody has read the flag words of its slots
             for (u32 i = threadIdx.x; i < STILE / 32; i += blockDim.x) zflag[i] = 0u;
             __syncthreads();
@@ -300,19 +290,7 @@ __global__ __launch_bounds__(256) void sparse_tile_kernel(const u32 *__restrict_
         constexpr u32 STEP = 64u * SPU;
         for (u32 ti = 0; ti < my_tiles; ti++) {
             const u32 tile = split + ti * splits, d0 = tile * STILE;
-            if (wave == 0) { // step counts of this tile's slices -> exclusive prefix (one lane per term)
-                u32 ns = 0;
-                if ((u32)lane < nt) ns = (sl_n[ti * nt + lane] + STEP - 1u) / STEP;
-                u32 incl = ns;
-#pragma unroll
-                for (int dd = 1; dd < 64; dd <<= 1) {
-                    const u32 o = (u32)__shfl_up((int)incl, dd, 64);
-                    if (lane >= dd) incl += o;
-                }
-                if ((u32)lane < nt) st_pre[lane] = incl - ns;
-                if ((u32)lane == nt - 1u) st_pre[nt] = incl;
-                if (lane == 0) st_ctr = 0u;
-            }
+            if (wave == 0) step_prefix<STEP>(sl_n + ti * nt, nt, st_pre, &st_ctr, lane); // this tile's slices
             __syncthreads();
             const u32 total = st_pre[nt];
             // which slice does step k belong to: one lane per term tests its range, a ballot finds it (no dependent LDS chain)
@@ -386,51 +364,12 @@ __global__ __launch_bounds__(256) void sparse_tile_kernel(const u32 *__restrict_
                 apply_s(sb, ib, kb);
             }
             __syncthreads();
-            // flush: wave w scans slots [w * 2048, (w + 1) * 2048) of the tile, 64 at a time, into its pool
-            for (u32 s0 = (u32)wave * (STILE / 4); s0 < (u32)(wave + 1) * (STILE / 4); s0 += 64) {
-                const u32 slot = s0 + (u32)lane;
-                const u32 a = acc[slot];
-                const u32 fw = zflag[slot >> 5];
-                acc[slot] = 0u;
-                const bool reached = a != 0u || ((fw >> (slot & 31u)) & 1u);
-                const u64 key = reached ? (((u64)a + 1ull) << 32 | (u64)(d0 + slot)) : 0ull;
-                u64 m = __ballot(key > thr);
-                while (m) {
-                    const int l = __ffsll((long long)m) - 1;
-                    m &= m - 1;
-                    const u64 kk = readlane_u64(key, l);
-                    if (kk > thr) {
-                        pool.insert_at(kk, pool.rank_of(kk), lane);
-                        thr = readlane_u64(pool.e[R - 1], 63); // the pool's last key
-                    }
-                }
-            }
+            for (u32 s0 = (u32)wave * (STILE / 4); s0 < (u32)(wave + 1) * (STILE / 4); s0 += 64) fold_keys(take_flagged_slot(acc, zflag, d0, s0 + (u32)lane));
             __syncthreads(); // everybody has read the flag words of its slots
             for (u32 i = threadIdx.x; i < STILE / 32; i += blockDim.x) zflag[i] = 0u;
             // (the next tile's prefix barrier orders these stores before its first atomic)
         }
-        if constexpr (R > 1) {
-            block_merge_pools<R>(pool, reinterpret_cast<u64 *>(acc), out, wave, lane);
-            return;
-        }
-        wpool[wave][lane] = pool.e[0];
-        __syncthreads();
-        if (wave == 0) {
-            for (int w = 1; w < 4; w++) {
-                const u64 key = wpool[w][lane];
-                u64 m = __ballot(key > thr);
-                while (m) {
-                    const int l = __ffsll((long long)m) - 1;
-                    m &= m - 1;
-                    const u64 kk = readlane_u64(key, l);
-                    if (kk > thr) {
-                        pool.insert_at(kk, pool.rank_of(kk), lane);
-                        thr = readlane_u64(pool.e[R - 1], 63); // the pool's last key
-                    }
-                }
-            }
-            out[lane] = pool.e[0];
-        }
+        block_merge_pools<R>(pool, wpool, acc, out, wave, lane, fold_keys);
         return;
     }
     // ---- block-wide chunks: queries of more than 64 terms, or more (tile, term) slices than the table holds ----------------------
@@ -451,29 +390,7 @@ __global__ __launch_bounds__(256) void sparse_tile_kernel(const u32 *__restrict_
         if (!n2.valid) break;
         cur = n2;
     }
-    // merge the four wave pools
-    if constexpr (R > 1) {
-        block_merge_pools<R>(pool, reinterpret_cast<u64 *>(acc), out, wave, lane);
-        return;
-    }
-    wpool[wave][lane] = pool.e[0];
-    __syncthreads();
-    if (wave == 0) {
-        for (int w = 1; w < 4; w++) {
-            const u64 key = wpool[w][lane];
-            u64 m = __ballot(key > thr);
-            while (m) {
-                const int l = __ffsll((long long)m) - 1;
-                m &= m - 1;
-                const u64 kk = readlane_u64(key, l);
-                if (kk > thr) {
-                    pool.insert_at(kk, pool.rank_of(kk), lane);
-                    thr = readlane_u64(pool.e[R - 1], 63); // the pool's last key
-                }
-            }
-        }
-        out[lane] = pool.e[0];
-    }
+    block_merge_pools<R>(pool, wpool, acc, out, wave, lane, fold_keys);
 }
 
 // ---- packed layout (cos_sparse::packed: the default wherever vector ids fit 24 bits; tuning knob sparse_layout = 0 keeps the other) ----
@@ -507,18 +424,7 @@ __device__ __forceinline__ void sparse_packed_body(const u32 *__restrict__ m_pk,
     Pool<R> pool;
     pool.clear();
     u64 thr = 0ull;
-    auto insert_keys = [&](u64 key) { // the keys of a wave's lanes that beat the pool's last entry
-        u64 m = ballot64(key > thr);
-        while (m) {
-            const int l = __ffsll((long long)m) - 1;
-            m &= m - 1;
-            const u64 kk = readlane_u64(key, l);
-            if (kk > thr) {
-                pool.insert_at(kk, pool.rank_of(kk), lane);
-                thr = readlane_u64(pool.e[R - 1], 63); // the pool's last key
-            }
-        }
-    };
+    auto insert_keys = [&](u64 key) { pool_fold_lanes<R>(pool, thr, key, lane); };
     // The (tile, term) slices are resolved into the LDS table a WINDOW at a time, all lookups of a window in flight together: TB tiles
     // x all nt terms when nt <= SLICES (one window for the whole block in the usual case), one tile x SLICES terms otherwise.
     const u32 my_tiles = (n_tiles - split + splits - 1) / splits;
@@ -533,13 +439,8 @@ __device__ __forceinline__ void sparse_packed_body(const u32 *__restrict__ m_pk,
             __syncthreads(); // the previous window is done with the table
             for (u32 p = threadIdx.x; p < tbn * twn; p += blockDim.x) {
                 const u32 tile = split + (ti0 + p / twn) * splits, t = tw0 + p % twn;
-                const u32 dr = qt[t].dir;
-                u64 b = qt[t].begin, e = qt[t].end;
-                if (dr != SNO_DIR) {
-                    const u32 *row = tile_dir + (u64)dr * (n_tiles + 1);
-                    e = b + row[tile + 1];
-                    b = b + row[tile];
-                }
+                u64 b, e;
+                slice_lookup(qt, t, tile_dir, n_tiles, tile, b, e);
                 sl_b[p] = b;
                 sl_n[p] = (u32)(e - b);
                 if (p < twn) sl_w[p] = qt[t].qq_k0;
@@ -552,19 +453,7 @@ __device__ __forceinline__ void sparse_packed_body(const u32 *__restrict__ m_pk,
                     const u32 tb = g << 6, ng = twn - tb < 64u ? twn - tb : 64u;
                     const u32 row0 = tj * twn + tb; // table row of the group's first term
                     __syncthreads(); // the table; the previous group's directory is no longer read; the previous tile's flush
-                    if (wave == 0) { // step counts of this group's slices of the tile -> exclusive prefix (one lane per term)
-                        u32 ns = 0;
-                        if ((u32)lane < ng) ns = (sl_n[row0 + lane] + STEP - 1u) / STEP;
-                        u32 incl = ns;
-#pragma unroll
-                        for (int dd = 1; dd < 64; dd <<= 1) {
-                            const u32 o = (u32)__shfl_up((int)incl, dd, 64);
-                            if (lane >= dd) incl += o;
-                        }
-                        if ((u32)lane < ng) st_pre[lane] = incl - ns;
-                        if ((u32)lane == ng - 1u) st_pre[ng] = incl;
-                        if (lane == 0) *st_ctr = 0u;
-                    }
+                    if (wave == 0) step_prefix<STEP>(sl_n + row0, ng, st_pre, st_ctr, lane); // this group's slices of the tile
                     __syncthreads();
                     const u32 total = uniform_u32(st_pre[ng]);
                     const u32 my_lo = (u32)lane < ng ? st_pre[lane] : 0xFFFFFFFFu, my_hi = (u32)lane < ng ? st_pre[lane + 1] : 0u;
@@ -683,30 +572,14 @@ __device__ __forceinline__ void sparse_packed_body(const u32 *__restrict__ m_pk,
                         }
                     }
                 } else {
-                    for (u32 s0 = (u32)wave * (STILE / 4); s0 < (u32)(wave + 1) * (STILE / 4); s0 += 64) {
-                        const u32 slot = s0 + (u32)lane;
-                        const u32 a = acc[slot];
-                        const u32 fw = zflag[slot >> 5];
-                        acc[slot] = 0u;
-                        const bool reached = a != 0u || ((fw >> (slot & 31u)) & 1u);
-                        insert_keys(reached ? (((u64)a + 1ull) << 32 | (u64)(d0 + slot)) : 0ull);
-                    }
+                    for (u32 s0 = (u32)wave * (STILE / 4); s0 < (u32)(wave + 1) * (STILE / 4); s0 += 64) insert_keys(take_flagged_slot(acc, zflag, d0, s0 + (u32)lane));
                     zflag[(u32)wave * (STILE / 128) + (u32)lane] = 0u; // the flag words of this wave's own slots (nobody else reads them)
                 }
                 // (the next group's barrier orders the cleared slots before the next tile's first add)
             }
         }
     }
-    if constexpr (R > 1) {
-        block_merge_pools<R>(pool, reinterpret_cast<u64 *>(acc), out, wave, lane); // (wpool is a null pointer here)
-        return;
-    }
-    wpool[wave][lane] = pool.e[0];
-    __syncthreads();
-    if (wave == 0) {
-        for (int w = 1; w < 4; w++) insert_keys(wpool[w][lane]);
-        out[lane] = pool.e[0];
-    }
+    block_merge_pools<R>(pool, wpool, acc, out, wave, lane, insert_keys);
 }
 
 // grid / blocks / pools as sparse_tile_kernel; order[i] = query | SPK_COUNTED
@@ -727,8 +600,8 @@ __global__ __launch_bounds__(256) void sparse_packed_kernel(const u32 *__restric
     const u32 t0 = qt_off[q], nt = qt_off[q + 1] - t0;
     const u32 n_tiles = (n + STILE - 1) / STILE;
     u64 *out = part + ((u64)q * splits + split) * SEL;
-    if (nt == 0 || split >= n_tiles) { // nothing to visit: an empty pool (the finish kernel reads every split)
-        if (threadIdx.x < SEL) out[threadIdx.x] = 0ull;
+    if (nt == 0 || split >= n_tiles) { // nothing to visit
+        write_empty_segment<1>(out);
         return;
     }
     if (oq & SPK_COUNTED) sparse_packed_body<true, PU>(m_pk, terms + t0, nt, n_tiles, tile_dir, split, splits, out, acc, zflag, wpool, sl_b, sl_n, sl_w, st_pre, &st_ctr);
@@ -753,12 +626,27 @@ __global__ __launch_bounds__(256) void sparse_wide_packed_kernel(const u32 *__re
     const u32 t0 = qt_off[q], nt = qt_off[q + 1] - t0;
     const u32 n_tiles = (n + STILE - 1) / STILE;
     u64 *out = part + ((u64)q * splits + split) * (SEL * R);
-    if (nt == 0 || split >= n_tiles) { // nothing to visit: an empty segment (the finish kernel reads every split)
-        for (u32 i = threadIdx.x; i < SEL * R; i += blockDim.x) out[i] = 0ull;
+    if (nt == 0 || split >= n_tiles) { // nothing to visit
+        write_empty_segment<R>(out);
         return;
     }
     if (oq & SPK_COUNTED) sparse_packed_body<true, 8, R>(m_pk, terms + t0, nt, n_tiles, tile_dir, split, splits, out, acc, zflag, nullptr, sl_b, sl_n, sl_w, st_pre, &st_ctr);
     else sparse_packed_body<false, 8, R>(m_pk, terms + t0, nt, n_tiles, tile_dir, split, splits, out, acc, zflag, nullptr, sl_b, sl_n, sl_w, st_pre, &st_ctr);
+}
+
+// finalize_sparse_ann_results' key of candidate v: dp over the QUERY pairs in order, f32 multiply then add (the caller sorts by
+// total_cmp descending)
+__device__ __forceinline__ u64 raw_rerank_key(const SparseDev &ix, u32 v, const u32 *__restrict__ q_dims, const float *__restrict__ q_vals,
+                                              const u32 *__restrict__ q_off, u32 q) {
+    const u64 b = ix.row_off[v], e = ix.row_off[v + 1];
+    float dp = 0.0f;
+    for (u32 i = q_off[q]; i < q_off[q + 1]; i++) {
+        const u32 d = q_dims[i];
+        u64 lo = b, hi = e;
+        while (lo < hi) { const u64 mid = lo + (hi - lo) / 2; if (ix.raw_dims[mid] < d) lo = mid + 1; else hi = mid; }
+        if (lo < e && ix.raw_dims[lo] == d) dp = __fadd_rn(dp, __fmul_rn(ix.raw_vals[lo], q_vals[i]));
+    }
+    return pack_key(simkey(dp), v);
 }
 
 // one wave per query: merge the segment pools, optional raw-value rerank, write the top k
@@ -770,19 +658,7 @@ __global__ __launch_bounds__(64) void sparse_finish_kernel(const SparseDev ix, c
     Pool<1> pool;
     pool.clear();
     u64 thr = 0ull;
-    for (u32 sgm = 0; sgm < S; sgm++) {
-        const u64 key = part[((u64)q * S + sgm) * SEL + lane];
-        u64 m = __ballot(key > thr);
-        while (m) {
-            const int l = __ffsll((long long)m) - 1;
-            m &= m - 1;
-            const u64 kk = readlane_u64(key, l);
-            if (kk > thr) {
-                pool.insert_at(kk, pool.rank_of(kk), lane);
-                thr = readlane_u64(pool.e[0], SEL - 1);
-            }
-        }
-    }
+    for (u32 sgm = 0; sgm < S; sgm++) pool_fold_lanes<1>(pool, thr, part[((u64)q * S + sgm) * SEL + lane], lane);
     const u32 have = (u32)__popcll(__ballot(pool.e[0] != 0ull));
     const u32 ncand = have < k_with_reranking ? have : k_with_reranking; // select_nth + truncate(k * reranking_factor)
     const u64 mine = pool.e[0];
@@ -795,19 +671,9 @@ __global__ __launch_bounds__(64) void sparse_finish_kernel(const SparseDev ix, c
         if (lane == 0) out_counts[q] = nout;
         return;
     }
-    // finalize_sparse_ann_results: dp over the QUERY pairs in order, f32 multiply then add; sort by total_cmp descending
     u64 res[1] = {0ull};
     if ((u32)lane < ncand) {
-        const u32 v = (u32)mine;
-        const u64 b = ix.row_off[v], e = ix.row_off[v + 1];
-        float dp = 0.0f;
-        for (u32 i = q_off[q]; i < q_off[q + 1]; i++) {
-            const u32 d = q_dims[i];
-            u64 lo = b, hi = e;
-            while (lo < hi) { const u64 mid = lo + (hi - lo) / 2; if (ix.raw_dims[mid] < d) lo = mid + 1; else hi = mid; }
-            if (lo < e && ix.raw_dims[lo] == d) dp = __fadd_rn(dp, __fmul_rn(ix.raw_vals[lo], q_vals[i]));
-        }
-        res[0] = pack_key(simkey(dp), v);
+        res[0] = raw_rerank_key(ix, (u32)mine, q_dims, q_vals, q_off, q);
     }
     bitonic_sort_desc<1>(res, lane);
     const u32 nout = ncand < top_k ? ncand : top_k;
@@ -819,7 +685,7 @@ __global__ __launch_bounds__(64) void sparse_finish_kernel(const SparseDev ix, c
 }
 
 // The wide finish, one block of 256 threads per query: the S sorted segments of 64 * R keys are folded into the best 64 * R one
-// after the other (fold_reversed + a bitonic merge of log2(64 R) rounds in 8 KB of LDS at R = 16), cut to k * reranking_factor,
+// after the other (fold_reversed + lds_bitonic_merge_desc of topk_select.h: log2(64 R) rounds in 8 KB of LDS at R = 16), cut to k * reranking_factor,
 // re-scored four candidates per thread at R = 16 and sorted again in LDS.  Same arithmetic and order as sparse_finish_kernel.
 template <int R>
 __global__ __launch_bounds__(256) void sparse_wide_finish_kernel(const SparseDev ix, const u64 *__restrict__ part, u32 S, const u32 *__restrict__ q_dims,
@@ -856,20 +722,10 @@ __global__ __launch_bounds__(256) void sparse_wide_finish_kernel(const SparseDev
         if (threadIdx.x == 0) out_counts[q] = nout;
         return;
     }
-    // finalize_sparse_ann_results: dp over the QUERY pairs in order, f32 multiply then add; sort by total_cmp descending
     for (u32 c = threadIdx.x; c < N; c += blockDim.x) { // (every thread rewrites the entries it read)
         u64 res = 0ull;
         if (c < ncand) {
-            const u32 v = (u32)best[c];
-            const u64 b = ix.row_off[v], e = ix.row_off[v + 1];
-            float dp = 0.0f;
-            for (u32 i = q_off[q]; i < q_off[q + 1]; i++) {
-                const u32 d = q_dims[i];
-                u64 lo = b, hi = e;
-                while (lo < hi) { const u64 mid = lo + (hi - lo) / 2; if (ix.raw_dims[mid] < d) lo = mid + 1; else hi = mid; }
-                if (lo < e && ix.raw_dims[lo] == d) dp = __fadd_rn(dp, __fmul_rn(ix.raw_vals[lo], q_vals[i]));
-            }
-            res = pack_key(simkey(dp), v);
+            res = raw_rerank_key(ix, (u32)best[c], q_dims, q_vals, q_off, q);
         }
         best[c] = res;
     }
@@ -1035,16 +891,6 @@ extern "C" int32_t cos_sparse_create(int32_t device, uint32_t quantization_bits,
     return COS_OK;
 }
 
-// InvertedIndexNode::quantize on the host (the same f32 operations as sparse_quantize above; this file is built with -ffp-contract=off)
-static inline uint32_t host_sparse_quantize(float value, float upper, uint32_t bits) {
-    const uint32_t quantization = (1u << bits) - 1u;
-    const float max_val = (float)quantization;
-    float t = (value / upper) * max_val;
-    t = t < 0.0f ? 0.0f : (t > max_val ? max_val : t); // f32::clamp keeps NaN
-    const uint32_t q = !(t == t) || t <= 0.0f ? 0u : (t >= 255.0f ? 255u : (uint32_t)(int)t); // `as u8`
-    return q < quantization ? q : quantization;
-}
-
 // InvertedIndex::insert for a whole collection (indexes/inverted/mod.rs + models/inverted_index.rs:176-200): the vectors are taken in
 // id order and every (dimension, value) pair pushes the id to the END of the list of (dimension, quantize(value)) — so the CSR this
 // produces is what the host's tree holds after inserting ids 0 .. n-1.  Host code, no device.
@@ -1070,7 +916,7 @@ extern "C" int32_t cos_sparse_build_csr(uint32_t quantization_bits, float values
     std::vector<u32> slot(nnz);
     for (u64 p = 0; p < nnz; p++) {
         const u32 t = (u32)(std::lower_bound(dims.begin(), dims.end(), raw_dims[p]) - dims.begin());
-        slot[p] = t * Q + host_sparse_quantize(raw_vals[p], values_upper_bound, quantization_bits);
+        slot[p] = t * Q + sparse_quantize(raw_vals[p], values_upper_bound, quantization_bits);
         count[slot[p]]++;
     }
     std::vector<u64> cursor((size_t)T * Q);
@@ -1109,10 +955,6 @@ extern "C" int32_t cos_sparse_create_from_vectors(int32_t device, uint32_t quant
                              keep_raw ? row_offsets : nullptr, keep_raw ? raw_dims : nullptr, keep_raw ? raw_vals : nullptr, out);
 }
 
-// Rust `as u8` / `as u32` on f32 (saturating, NaN -> 0), host side
-static inline uint32_t host_f32_as_u8(float v) { return !(v == v) || v <= 0.0f ? 0u : (v >= 255.0f ? 255u : (uint32_t)(int)v); }
-static inline uint32_t host_f32_as_u32(float v) { return !(v == v) || v <= 0.0f ? 0u : (v >= 4294967296.0f ? 0xFFFFFFFFu : (uint32_t)v); }
-
 extern "C" int32_t cos_sparse_search_batch(cos_sparse *s, const uint32_t *q_dims, const float *q_vals, const uint32_t *q_offsets, uint32_t B, uint32_t top_k,
                                            float early_terminate_threshold, uint32_t reranking_factor, uint32_t *out_ids, float *out_scores,
                                            uint32_t *out_counts) {
@@ -1137,7 +979,7 @@ extern "C" int32_t cos_sparse_search_batch(cos_sparse *s, const uint32_t *q_dims
     const float qf = (float)Q;
     float etv = qf * early_terminate_threshold;
     etv = etv > 255.0f ? 255.0f : etv;
-    const u32 early_terminate_value = host_f32_as_u8(etv), low_threshold = host_f32_as_u32(early_terminate_threshold * qf);
+    const u32 early_terminate_value = f32_as_u8(etv), low_threshold = f32_as_u32(early_terminate_threshold * qf);
     std::vector<STerm> terms;
     terms.reserve(nq);
     std::vector<u32> qt_off(B + 1, 0), order(B);
@@ -1150,7 +992,7 @@ extern "C" int32_t cos_sparse_search_batch(cos_sparse *s, const uint32_t *q_dims
             auto it = std::lower_bound(s->h_dims.begin(), s->h_dims.end(), q_dims[i]);
             if (it == s->h_dims.end() || *it != q_dims[i]) continue;
             const u32 t = (u32)(it - s->h_dims.begin());
-            const u32 qq = host_sparse_quantize(q_vals[i], s->upper, s->bits);
+            const u32 qq = sparse_quantize(q_vals[i], s->upper, s->bits);
             const u32 k0 = qq > low_threshold ? 0u : early_terminate_value;
             if (k0 >= Q) continue;
             const u64 *ko = s->h_key_off.data() + (size_t)t * (Q + 1);
@@ -1446,7 +1288,7 @@ extern "C" int32_t cos_sparse_insert(cos_sparse *s, uint32_t m, const uint64_t *
             const u32 sl = ud_slot[std::lower_bound(ud.begin(), ud.end(), raw_dims[p]) - ud.begin()];
             h_slot[p] = sl;
             h_pid[p] = n0 + i;
-            cnt[(size_t)sl * Q + host_sparse_quantize(raw_vals[p], s->upper, s->bits)]++;
+            cnt[(size_t)sl * Q + sparse_quantize(raw_vals[p], s->upper, s->bits)]++;
             if (p > b && raw_dims[p] <= raw_dims[p - 1]) ascending = false;
         }
         if (ascending) continue;
@@ -1595,7 +1437,7 @@ extern "C" int32_t cos_sparse_delete(cos_sparse *s, const uint32_t *ids, const u
             auto it = std::lower_bound(s->h_dims.begin(), s->h_dims.end(), raw_dims[p]);
             if (it == s->h_dims.end() || *it != raw_dims[p]) continue;
             const u32 t = (u32)(it - s->h_dims.begin());
-            const u32 key = host_sparse_quantize(raw_vals[p], s->upper, s->bits);
+            const u32 key = sparse_quantize(raw_vals[p], s->upper, s->bits);
             const u64 *ko = s->h_key_off.data() + (size_t)t * (Q + 1);
             if (ko[key + 1] == ko[key]) continue;
             pair_ik.push_back(ids[i]);

@@ -8,7 +8,7 @@
 // Rounds 1-5 refused all three at cos_index_create (COS_ERR_UNIMPLEMENTED).  This kernel is the plain statement of the loop — one wave per
 // query, nothing speculative:
 //   * the candidates of a level live in ONE array of ef keys in LDS, sorted descending.  The reference's BinaryHeap only ever hands out
-//     its best ef - popped entries, so a sorted array truncated at `limit` = ef - popped reproduces the pop sequence (device_common.h
+//     its best ef - popped entries, so a sorted array truncated at `limit` = ef - popped reproduces the pop sequence (topk_select.h
 //     Pool); the popped entries simply stay where they are: positions [0, popped) ARE the popped list, [popped, popped + live) the
 //     candidates, and live <= limit keeps the two inside the ef slots;
 //   * an expansion scans its neighbour slots 64 at a time, in slot order (vector_store.rs:1161-1171); a pass tests and sets the

@@ -6,6 +6,7 @@
 #pragma once
 #include "engine_types.h"
 #include "dot_engines.h"
+#include "topk_select.h"
 
 namespace cosdev {
 

@@ -7,12 +7,15 @@ of every case.  One JSON line; exit status 1 when any query mismatches.
 
     timeout -k 10 900 python scripts/bench_sparse_wide.py
     timeout -k 10 300 rocprofv3 --kernel-trace --stats -d DIR -- python scripts/bench_sparse_wide.py --cases 1024,0 200,5 --no-parity
-"""
+    timeout -k 10 300 python scripts/bench_sparse_wide.py --no-parity --lib /path/to/another/libcosdata_hip.so
+
+The last form times another build of the library (the parent commit's, say) on the same corpus: run the two alternately."""
 import argparse, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 import cosdata_amd as ca
+from cosdata_amd import _lib
 from oracle import oracle as O
 
 CASES = [(10, 0), (64, 0), (65, 0), (128, 0), (256, 0), (512, 0), (1024, 0), (20, 5), (200, 5)]
@@ -20,7 +23,10 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--cases", nargs="*", default=None, help="top_k,factor pairs (default: all nine)")
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--no-parity", action="store_true", help="skip the oracle (profiler runs)")
+ap.add_argument("--lib", default=None, help="load this libcosdata_hip.so instead of the tree's")
 args = ap.parse_args()
+if args.lib:
+    _lib.SO_PATH = os.path.abspath(args.lib)
 cases = [tuple(int(x) for x in c.split(",")) for c in args.cases] if args.cases else CASES
 
 n = int(os.environ.get("SPARSE_N", 400_000)); vocab = 30_000; nnz = 48; bits = 6; upper = 3.0; B = 256
@@ -101,6 +107,7 @@ if not args.no_parity:
         total_bad += bad
 print(json.dumps({"config": {"workload": f"learned-sparse inverted index, {n} vectors, vocab {vocab}, {int(dim.numel())} postings, {bits}-bit keys, "
                                          f"batch {B} queries of 16-32 terms, handle at max_candidates {ix.max_candidates}",
-                             "layout": "packed u32" if ix.packed else "u32 id + u8 key", "timed_calls": args.reps},
+                             "layout": "packed u32" if ix.packed else "u32 id + u8 key", "timed_calls": args.reps,
+                             "library": _lib.SO_PATH},
                   "cases": results, "parity_vs_oracle": {"queries_per_case": B, "mismatching_queries": total_bad}}))
 sys.exit(1 if total_bad else 0)
