@@ -190,7 +190,9 @@ int32_t run_batches(cos_index *ix, u32 first, const uint8_t *max_level, std::vec
         wa.out_nodes = d_out_nodes.as<u32>();
         wa.out_counts = d_out_counts.as<u32>();
         wa.out_status = d_status.as<int32_t>();
-        HIP_TRY(launch_walk(ix->eng, dev, wa, ix->lat_max_B, ix->lat4_max_B, st));
+        cosdev::WalkPlanIn pin = cos_walk_plan_in(ix, bs, wa.ef); // the handle's latency knobs; an insertion walk has no table and no order
+        pin.table_min_B = pin.order_min_B = 0;
+        HIP_TRY(launch_walk(ix->eng, dev, wa, cosdev::walk_plan(pin).kernel, st));
         HIP_TRY(hipMemcpyAsync(h_status.p, d_status.p, (size_t)bs * 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st)); // a failed walk leaves its lower levels unwritten: never link from it
         for (u32 b = 0; b < bs; b++)
@@ -652,7 +654,10 @@ extern "C" int32_t cos_index_delete(cos_index *ix, const uint32_t *ids, uint32_t
         wa.out_nodes = d_out_nodes.as<u32>();
         wa.out_counts = d_out_counts.as<u32>();
         wa.out_status = d_status.as<int32_t>();
-        HIP_TRY(launch_walk(ix->eng, dev, wa, 0, 0, st)); // (the throughput kernel: the latency kernels have no unseeded filter)
+        cosdev::WalkPlanIn pin = cos_walk_plan_in(ix, 1, EF);
+        pin.table_min_B = pin.order_min_B = 0;
+        pin.no_self_seed = true; // (the throughput kernel: the latency kernels have no unseeded filter)
+        HIP_TRY(launch_walk(ix->eng, dev, wa, cosdev::walk_plan(pin).kernel, st));
         int32_t wst = COS_OK;
         HIP_TRY(hipMemcpyAsync(&wst, d_status.p, 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(h_ids.data(), d_out_ids.p, h_ids.size() * 4, hipMemcpyDeviceToHost, st));

@@ -583,7 +583,7 @@ static u32 walk_table_min_B(const cos_index *ix);
 extern "C" int32_t cos_index_set_ef_search(cos_index *ix, uint32_t ef) {
     if (!ix) return cos_fail(COS_ERR_INVALID, "null index");
     if (ef > cosdev::WALK_GENERAL_MAX_EF) return cos_fail(COS_ERR_UNIMPLEMENTED, "ef > %u not supported on the device", cosdev::WALK_GENERAL_MAX_EF);
-    std::lock_guard<std::mutex> g(ix->mu); // searches snapshot ef / visited mode under the same lock (run_search); the graph state is read under it too
+    std::lock_guard<std::mutex> g(ix->mu); // searches snapshot ef / visited mode under the same lock (get_workspace); the graph state is read under it too
     const bool live = graph_ready(ix);
     if (live)
         if (int32_t rc = cos_set_device(ix)) return rc; // (nothing changed yet)
@@ -747,6 +747,37 @@ static u32 walk_table_min_B(const cos_index *ix) {
     const long long env = cosdev::tune_or(cosdev::TUNE_WALK_TABLE_MIN_B, -1);
     return env >= 0 ? (u32)std::min<long long>(env, 0xFFFFFFFFll) : ix->walk_table_min_B;
 }
+// the handle as walk_plan (walk_plan.h) sees it: shape, every knob resolved (the tuning registry's overrides included), a launch of B
+// queries at beam width ef that takes part in the walk chain.  Caller holds ix->mu where the handle is shared.
+cosdev::WalkPlanIn cos_walk_plan_in(const cos_index *ix, u32 B, u32 ef) {
+    cosdev::WalkPlanIn in{};
+    in.eng = ix->eng;
+    in.storage = ix->p.storage;
+    in.nchunks = ix->nchunks;
+    in.G = ix->G;
+    in.num_layers = ix->p.num_layers;
+    for (u32 l = 0; l <= ix->p.num_layers; l++) in.M[l] = ix->lv[l].M;
+    in.shortlist = ix->p.shortlist_size;
+    in.visited_mode = ix->p.visited_mode;
+    in.mdim = ix->meta.mdim;
+    in.B = B;
+    in.ef = ef;
+    in.chain = true;
+    // tuning knobs walk_lat / walk_lat4 = <n> override the handle's values (experiments: 0 = off, 4294967295 = always)
+    const long long lat = cosdev::tune_or(cosdev::TUNE_WALK_LAT, -1), lat4 = cosdev::tune_or(cosdev::TUNE_WALK_LAT4, -1);
+    in.lat_max_B = lat >= 0 ? (u32)std::min(lat, 0xFFFFFFFFll) : ix->lat_max_B;
+    in.lat4_max_B = lat4 >= 0 ? (u32)std::min(lat4, 0xFFFFFFFFll) : ix->lat4_max_B;
+    in.small_table_tk = cosdev::tune_or(cosdev::TUNE_WALK_SMALL_TABLE_TK, 1) != 0;
+    in.adj_mag_mode = (u32)cosdev::tune_or(cosdev::TUNE_WALK_ADJ_MAG, 1);
+    in.table_min_B = walk_table_min_B(ix);
+    in.order_min_B = ix->walk_order_min_B;
+    in.chain_min_B = ix->chain_min_B;
+    in.side_min_B = ix->walk_side_min_B;
+    in.table_after_sort = cosdev::tune_or(cosdev::TUNE_WALK_TABLE_AFTER_SORT, 1);
+    in.table_supported = cosdev::level_table_eng_supported(ix->eng, ix->row_stride);
+    in.adj_mag_valid = ix->adj_mag_valid;
+    return in;
+}
 static int32_t ensure_level_table(cos_index *ix) {
     const u32 max_cols = walk_table_max_cols(ix);
     // Which levels pay.  A table column costs one GEMM column per launch (~2.6 ps per query and column at K = 1024), a level walked
@@ -871,8 +902,7 @@ extern "C" int32_t cos_index_walk_table_info(cos_index *ix, uint32_t *out_level_
 static int32_t ensure_adj_mags(cos_index *ix) {
     if (ix->adj_mag_valid) return COS_OK;
     if (!graph_ready(ix) || ix->meta.mdim != 0u) return COS_OK; // (collections with a metadata schema keep the gathers: their walks are walk_meta_kernel's)
-    if (std::min(ix->p.neighbors_count, ix->p.shortlist_size) > 64u || std::min(ix->p.level0_neighbors_count, ix->p.shortlist_size) > 64u)
-        return COS_OK; // (walk_general_kernel's indexes: it gathers the norms)
+    if (cosdev::walk_rows_over_64_slots(cos_walk_plan_in(ix, 0, 0))) return COS_OK; // (walk_general_kernel's indexes: it gathers the norms)
     HIP_TRY(hipDeviceSynchronize()); // a build or an upload on another stream may still be writing the adjacency
     for (u32 l = 0; l <= ix->p.num_layers; l++) {
         ix->lv[l].d_adj_mag.reset();
@@ -919,12 +949,28 @@ extern "C" int32_t cos_index_walk_order_cuts(cos_index *ix, uint32_t *out_levels
     return COS_OK;
 }
 
-// The norms beside the adjacency (LevelDev::adj_mag), invalidated by a root replaced on a live graph, are refilled by the first launch
-// of ADJ_MAG_REFILL_MIN_B queries (get_workspace) but only read by launches of ADJ_MAG_USE_MIN_B (run_search): the two disagree
-// (ADVICE.md), so a launch in between pays for a refill it does not use.
-static constexpr u32 ADJ_MAG_REFILL_MIN_B = 1024u, ADJ_MAG_USE_MIN_B = 4096u;
+// What one dense search launch runs from: its settled plan (walk_plan.h) and everything of the handle the plan refers to, taken in ONE
+// snapshot under one hold of ix->mu (cos_index_set_* may change the knobs from another thread) by get_workspace; run_search reads
+// nothing of it from the handle again.
+struct SearchLaunch {
+    cosdev::WalkPlan plan;
+    u32 ef = 0, visited_mode = 0;
+    bool timed = false;
+    // the level table's operand (plan.use_table)
+    u64 tab_stride = 0;
+    u32 tab_col0[cosdev::MAX_LEVELS] = {};
+    const uint8_t *tcodes = nullptr;
+    const float *tmags = nullptr;
+    const u32 *tcsums = nullptr;
+    // the order keys (plan.ordered)
+    u32 n_keys = 0, key_level[cosdev::MAX_LEVELS], key_n[cosdev::MAX_LEVELS];
+    const u32 *order_rank[cosdev::MAX_LEVELS];
+};
 
-static int32_t get_workspace(cos_index *ix, void *key, hipStream_t st, u32 B, u32 top_k, bool host_api, Workspace **out) {
+// `chain` = the launch may take part in the walk chain (big launches of different streams one after the other); the chunks of one
+// pipelined host call co-run instead.
+static int32_t get_workspace(cos_index *ix, void *key, hipStream_t st, u32 B, u32 top_k, bool host_api, Workspace **out, SearchLaunch *L,
+                             bool chain = true) {
     std::lock_guard<std::mutex> g(ix->mu);
     std::unique_ptr<Workspace> &slot = ix->ws[key];
     if (!slot) slot.reset(new Workspace());
@@ -953,16 +999,29 @@ static int32_t get_workspace(cos_index *ix, void *key, hipStream_t st, u32 B, u3
         HIP_TRY(w->d_out_status.alloc(cap));
         w->capB = cap;
     }
-    if (!ix->adj_mag_valid && B >= ADJ_MAG_REFILL_MIN_B) // (a root replaced on a live graph; small launches keep their gathers until a big one pays for the refill)
+    // what the launch wants, what could be prepared of it, and the plan settled on that
+    L->ef = ix->p.ef_search;
+    L->visited_mode = ix->p.visited_mode;
+    L->timed = ix->timing;
+    cosdev::WalkPlanIn in = cos_walk_plan_in(ix, B, L->ef);
+    in.chain = chain;
+    const cosdev::WalkPlan want = cosdev::walk_plan(in);
+    cosdev::WalkHave have{};
+    if (want.refill_adj_mag) {
         if (int32_t rc = ensure_adj_mags(ix)) return rc;
-    if (ix->walk_order_min_B && B >= ix->walk_order_min_B && ix->p.ef_search <= 256u) { // wider beams keep the single launch (run_search)
+        in.adj_mag_valid = ix->adj_mag_valid;
+    }
+    if (want.prepare_order) {
         if (w->order.cap < w->capB) {
             HIP_TRY(hipStreamSynchronize(st));
             HIP_TRY(cosdev::walk_order_reserve(w->order, w->capB));
         }
         if (int32_t rc = ensure_order_rank(ix)) return rc;
+        have.order_buffers = w->order.cap >= B;
+        have.n_order_keys = (u32)ix->order_levels.size();
+        have.order_level0 = have.n_order_keys ? ix->order_levels[0] : 0u;
     }
-    if (const u32 tmin = walk_table_min_B(ix); tmin && (B >= tmin || B <= ix->lat4_max_B)) { // from min_queries on, and the four-wave latency kernel's launches
+    if (want.prepare_table) {
         if (int32_t rc = ensure_level_table(ix)) return rc;
         const size_t need = (size_t)w->capB * ix->table_stride;
         if (need > w->tab.cap) {
@@ -982,7 +1041,24 @@ static int32_t get_workspace(cos_index *ix, void *key, hipStream_t st, u32 B, u3
                     HIP_TRY(e);
             }
         }
+        have.table_level_min = ix->level_table_valid ? ix->table_level_min : 0u;
+        have.table_cols = ix->table_cols;
+        have.table_buffer = w->tab && (size_t)B * ix->table_stride <= w->tab.cap;
     }
+    L->plan = cosdev::walk_plan(in, &have);
+    if (L->plan.use_table) {
+        L->tab_stride = ix->table_stride;
+        memcpy(L->tab_col0, ix->table_col0, sizeof(L->tab_col0));
+        L->tcodes = ix->d_tcodes;
+        L->tmags = ix->d_tmags;
+        L->tcsums = ix->d_tcsums;
+    }
+    if (L->plan.ordered)
+        for (u32 l : ix->order_levels) {
+            L->key_level[L->n_keys] = l;
+            L->key_n[L->n_keys] = ix->order_rank_n[l];
+            L->order_rank[L->n_keys++] = ix->d_order_rank[l];
+        }
     if (host_api && (size_t)top_k * w->capB > (size_t)w->cap_topk * w->capB) {
         w->cap_topk = 0;
         HIP_TRY(w->d_out_ids.alloc((size_t)w->capB * top_k));
@@ -1001,73 +1077,22 @@ static int32_t get_workspace(cos_index *ix, void *key, hipStream_t st, u32 B, u3
 }
 
 // quantize -> walk on `st`, then (finalize) on `st_fin` (the same stream unless the caller pipelines chunks: then `st_fin` waits
-// for the walk through an event); all buffers device memory.  `chain` = take part in the walk chain (big launches of
-// different streams one after the other); the chunks of one pipelined host call co-run instead.
-static int32_t run_search(cos_index *ix, Workspace *w, const float *d_queries, u32 B, u32 top_k, u32 *d_out_ids, float *d_out_scores,
-                          u32 *d_out_counts, int32_t *d_out_status, bool do_finalize, hipStream_t st, hipStream_t st_fin = nullptr,
-                          hipEvent_t walk_ev = nullptr, bool chain = true) {
+// for the walk through an event); all buffers device memory.  `L`: the launch get_workspace planned for these B queries.
+static int32_t run_search(cos_index *ix, Workspace *w, const SearchLaunch &L, const float *d_queries, u32 B, u32 top_k, u32 *d_out_ids,
+                          float *d_out_scores, u32 *d_out_counts, int32_t *d_out_status, bool do_finalize, hipStream_t st,
+                          hipStream_t st_fin = nullptr, hipEvent_t walk_ev = nullptr) {
+    const cosdev::WalkPlan &plan = L.plan;
+    const bool timed = L.timed, ordered = plan.ordered, chained = plan.chained;
+    const u32 ef = L.ef, n_keys = L.n_keys;
     IndexDev dev = cos_make_index_dev(ix);
-    bool timed;
-    u32 ef, lat_max_B, lat4_max_B, order_min_B, n_keys = 0, key_level[cosdev::MAX_LEVELS], key_n[cosdev::MAX_LEVELS];
-    const u32 *order_rank[cosdev::MAX_LEVELS];
-    u32 tab_level_min = 0, tab_cols = 0, tab_col0[cosdev::MAX_LEVELS] = {}, tab_min_B = 0;
-    u64 tab_stride = 0;
-    const uint8_t *tcodes = nullptr;
-    const float *tmags = nullptr;
-    const u32 *tcsums = nullptr;
-    { // one consistent snapshot of the knobs cos_index_set_* may change from another thread
-        std::lock_guard<std::mutex> g(ix->mu);
-        order_min_B = ix->order_rank_valid && !ix->order_levels.empty() ? ix->walk_order_min_B : 0u;
-        for (u32 l : ix->order_levels) {
-            key_level[n_keys] = l;
-            key_n[n_keys] = ix->order_rank_n[l];
-            order_rank[n_keys++] = ix->d_order_rank[l];
-        }
-        tab_min_B = walk_table_min_B(ix);
-        if (tab_min_B && ix->level_table_valid && ix->table_level_min && w->tab && (size_t)B * ix->table_stride <= w->tab.cap) {
-            tab_level_min = ix->table_level_min;
-            tab_cols = ix->table_cols;
-            tab_stride = ix->table_stride;
-            memcpy(tab_col0, ix->table_col0, sizeof(tab_col0));
-            tcodes = ix->d_tcodes;
-            tmags = ix->d_tmags;
-            tcsums = ix->d_tcsums;
-        }
-        timed = ix->timing;
-        ef = ix->p.ef_search;
-        lat_max_B = ix->lat_max_B;
-        lat4_max_B = ix->lat4_max_B;
-        dev.visited_mode = ix->p.visited_mode;
-    }
-    // Norms beside the adjacency (LevelDev::adj_mag) cost two more lines per window entry and save one line per winner: they pay while an
-    // expansion still finds several winners, i.e. while the level's filter (64 x M bits) is not saturated by the ef pops of the level.
-    // Measured (profiles/r06_adjmag_probe_*.jsonl): 1M x 768, M0 64 — ef 64: 7.8 evaluations per expansion, lower range 2.64 -> 2.42 ms;
-    // ef 256: 2.35 per expansion, 5.10 -> 5.31 ms; 12.5M x 1024, M0 256 / M 64, ef 128: 9.8 per expansion, 26.5 -> 24.3 ms.
-    // ... and while the launch is bound by bandwidth at all: one client batch is a chain of dependent round trips per query, where two more
-    // loads and an LDS round trip per window entry only add latency (single batch of c2: 407 k QPS without, 396 k with).
-    if (cosdev::tune_or(cosdev::TUNE_WALK_ADJ_MAG, 1) != 2) // (2 = at every ef and launch size: experiments)
-        for (u32 l = 0; l <= dev.num_layers; l++)
-            if (ef > 2u * dev.lv[l].M || B < ADJ_MAG_USE_MIN_B) dev.lv[l].adj_mag = nullptr;
+    dev.visited_mode = L.visited_mode;
+    for (u32 l = 0; l <= dev.num_layers; l++)
+        if (!((plan.use_adj_mag >> l) & 1u)) dev.lv[l].adj_mag = nullptr;
     WalkArgs wa;
     memset(&wa, 0, sizeof(wa));
     if (dev.visited_mode == COS_VISITED_EXACT) {
         int32_t rc = vis_tab_prepare(w->vis, ix, B, ef, st, wa);
         if (rc) return rc;
-    }
-    // which kernel walks this launch decides whether the level table is worth its GEMM: the throughput kernel (big launches, from
-    // walk_table_min_B queries) and the four-wave latency kernel (one client batch) read it, the one-wave latency kernel does not
-    // (a launch outside the fast kernels' domain — walk_general_kernel — walks every level from rows, in one launch, in arrival order)
-    const bool general = cosdev::walk_general_needed(dev, ef);
-    const bool ordered = !general && order_min_B && B >= order_min_B && n_keys > 0 && w->order.cap >= B && ef <= 256u;
-    if (general) tab_level_min = 0;
-    if (tab_level_min) {
-        WalkArgs probe;
-        memset(&probe, 0, sizeof(probe));
-        probe.B = B;
-        probe.ef = ef;
-        const int kind = ordered ? 0 : cosdev::walk_kernel_kind(ix->eng, dev, probe, lat_max_B, lat4_max_B, true);
-        // (the four-wave kernel reads the table of u8 codes only)
-        if (!((kind == 4 && ix->eng == ENG_U8) || (kind == 0 && (B >= tab_min_B || B <= lat4_max_B)))) tab_level_min = 0;
     }
     hipEvent_t *ev = &w->ev[(size_t)(w->ev_count % Workspace::EV_RING) * Workspace::EV_PER];
     if (timed) HIP_TRY(hipEventRecord(ev[0], st));
@@ -1076,19 +1101,14 @@ static int32_t run_search(cos_index *ix, Workspace *w, const float *d_queries, u
     // Level table: on the caller's stream, i.e. BEFORE the walk takes its place in the walk chain — the GEMM of this launch runs next
     // to the previous launch's walk.  (Round 5 also issued it inside the chain, right in front of its own walk, where it shares the
     // chip with nobody: 7.07-7.12 against 6.69 ms per step — the overlap hides 0.4 ms.  profiles/r05_table_gemm_in_chain_probe_not_kept.jsonl)
-    const bool chained = chain && B >= ix->chain_min_B;
-    if (tab_level_min) {
-        // (engine_internal.h, chain_last_range_ev.)  Only a GEMM long enough to outlast the previous walk's upper range blocks its sort: the
-        // shard's 65 161 columns x 32 768 queries (3.1 ms alone; gate: 33.3 -> 32.6 ms per step) do, c2's 20 903 (0.85 ms; 6.22 -> 6.29) do not
-        // (profiles/r06_inflight_probe.txt); knob: 0 = never, 2 = always
-        const long long gate = cosdev::tune_or(cosdev::TUNE_WALK_TABLE_AFTER_SORT, 1);
-        if (chained && (gate == 2 || (gate == 1 && (u64)tab_cols * B >= (1ull << 30)))) {
+    if (plan.use_table) {
+        if (plan.table_waits_for_sort) { // (engine_internal.h, chain_last_range_ev)
             std::lock_guard<std::mutex> g(ix->chain_mu);
             if (ix->chain_last_range_ev && ix->chain_last_range_ev != w->last_range) HIP_TRY(hipStreamWaitEvent(st, ix->chain_last_range_ev, 0));
         }
         if (timed) HIP_TRY(hipEventRecord(ev[4], st));
-        HIP_TRY(cosdev::launch_level_table(ix->eng, w->q_codes, w->q_mags, w->qsums, w->qdig, B, tcodes, tmags, tcsums, ix->row_stride, tab_cols, w->tab,
-                                           tab_stride, ix->n_cus, st));
+        HIP_TRY(cosdev::launch_level_table(ix->eng, w->q_codes, w->q_mags, w->qsums, w->qdig, B, L.tcodes, L.tmags, L.tcsums, ix->row_stride, plan.table_cols,
+                                           w->tab, L.tab_stride, ix->n_cus, st));
         if (timed) HIP_TRY(hipEventRecord(ev[5], st));
     }
     if (timed) HIP_TRY(hipEventRecord(ev[1], st));
@@ -1104,19 +1124,19 @@ static int32_t run_search(cos_index *ix, Workspace *w, const float *d_queries, u
     wa.out_stats = w->stats;
     wa.out_stats2 = w->stats2;
     HIP_TRY(hipMemsetAsync(w->stats2, 0, (size_t)B * 32, st)); // the latency kernels do not write it
-    if (tab_level_min) {
+    if (plan.use_table) {
         wa.tab = w->tab;
-        wa.tab_mags = tmags;
-        wa.tab_stride = tab_stride;
-        wa.tab_level_min = tab_level_min;
-        memcpy(wa.tab_col0, tab_col0, sizeof(tab_col0));
+        wa.tab_mags = L.tmags;
+        wa.tab_stride = L.tab_stride;
+        wa.tab_level_min = plan.table_level_min;
+        memcpy(wa.tab_col0, L.tab_col0, sizeof(L.tab_col0));
     }
     // Big walks run on the workspace's own LOW-PRIORITY stream (ordered after the quantize and before the finalize of `st` by
     // events): the short kernels around a walk — the neighbouring launch's quantize and, above all, its finalize, which used to
     // take 11-16 ms instead of 1.2 when its waves queued behind 32 768 walk waves of the next launch — are dispatched ahead of
     // the walk's pending workgroups.  The caller sees the same stream order.
     hipStream_t sw = st;
-    if (ix->walk_side_min_B && B >= ix->walk_side_min_B) {
+    if (plan.side_stream) {
         if (!w->walk_stream) {
             int lo = 0, hi = 0;
             HIP_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi)); // numerically largest = lowest priority
@@ -1130,14 +1150,10 @@ static int32_t run_search(cos_index *ix, Workspace *w, const float *d_queries, u
     // Big launches walk in locality order (kernels_order.hip): the levels down to the first key level in arrival order, then, after
     // every key level, a sort of the launch by the key that level left and the levels below with the sorted queries dealt to the
     // XCDs.  Same walks, same results.
-    // Beam widths above 256 keep the single launch: the cut costs the tail of one more launch, a fixed ~3 % of the walk whatever
-    // the ef, while what the order saves shrinks as the walk turns from memory-bound to bound by its own serial work (c2: +16 % at
-    // ef 64, +3.6 % at 128, +2.6 % at 256, +1 % at 512; nothing measurable at ef 512 on the uniform corpus or on a 12.5M shard:
-    // profiles/archive/r03_order_probe_*.jsonl and the two r03_final_bench_default_* lines, taken with and without this rule).
     auto walk = [&](hipStream_t s) -> int32_t {
         if (!ordered) {
             if (chained) HIP_TRY(hipEventRecord(w->last_range, s));
-            HIP_TRY(launch_walk(ix->eng, dev, wa, lat_max_B, lat4_max_B, s));
+            HIP_TRY(launch_walk(ix->eng, dev, wa, plan.kernel, s));
             return COS_OK;
         }
         wa.phase = 1;
@@ -1148,17 +1164,17 @@ static int32_t run_search(cos_index *ix, Workspace *w, const float *d_queries, u
         for (u32 i = 0; i <= n_keys; i++) {
             const bool last = i == n_keys;
             wa.level_first = first;
-            wa.level_last = last ? 0u : key_level[i];
-            wa.key_n = last ? 0u : key_n[i];
-            wa.order_rank = last ? nullptr : order_rank[i];
+            wa.level_last = last ? 0u : L.key_level[i];
+            wa.key_n = last ? 0u : L.key_n[i];
+            wa.order_rank = last ? nullptr : L.order_rank[i];
             if (last && chained) HIP_TRY(hipEventRecord(w->last_range, s));
-            HIP_TRY(launch_walk(ix->eng, dev, wa, 0, 0, s));
+            HIP_TRY(launch_walk(ix->eng, dev, wa, plan.kernel, s));
             if (last) break;
             if (timed && i == 0) HIP_TRY(hipEventRecord(ev[6], s));
-            HIP_TRY(cosdev::launch_walk_order(w->order, B, key_n[i], ix->num_xcd, s));
+            HIP_TRY(cosdev::launch_walk_order(w->order, B, L.key_n[i], ix->num_xcd, s));
             if (timed && i == 0) HIP_TRY(hipEventRecord(ev[7], s));
             wa.q_order = w->order.q_order;
-            first = key_level[i] - 1;
+            first = L.key_level[i] - 1;
         }
         return COS_OK;
     };
@@ -1188,11 +1204,7 @@ static int32_t run_search(cos_index *ix, Workspace *w, const float *d_queries, u
     if (timed) { HIP_TRY(hipEventRecord(ev[3], sf)); w->ev_count++; }
     w->lastB = B;
     w->timed = timed;
-    w->last_tab = tab_level_min != 0;
-    w->last_tab_cols = tab_cols;
-    w->last_tab_level_min = tab_level_min;
-    w->last_split = ordered;
-    w->last_cut_level = ordered ? key_level[0] : 0u;
+    w->last_plan = plan;
     { std::lock_guard<std::mutex> g(ix->mu); ix->last_ws = w; }
     return COS_OK;
 }
@@ -1211,9 +1223,10 @@ extern "C" int32_t cos_search_batch_device(cos_index *ix, const float *d_queries
     if (rc) return rc;
     if (!d_out_ids || !d_out_scores || !d_out_counts || !d_out_status) return cos_fail(COS_ERR_INVALID, "null output");
     Workspace *w;
-    rc = get_workspace(ix, stream, (hipStream_t)stream, B, top_k, false, &w);
+    SearchLaunch L;
+    rc = get_workspace(ix, stream, (hipStream_t)stream, B, top_k, false, &w, &L);
     if (rc) return rc;
-    return run_search(ix, w, d_queries, B, top_k, d_out_ids, d_out_scores, d_out_counts, d_out_status, true, (hipStream_t)stream);
+    return run_search(ix, w, L, d_queries, B, top_k, d_out_ids, d_out_scores, d_out_counts, d_out_status, true, (hipStream_t)stream);
 }
 
 // host API: every call leases a HostPipe (private streams, staging and, through it, private workspaces) from the handle's
@@ -1262,10 +1275,11 @@ static int32_t search_host_simple(cos_index *ix, HostPipe *hp, const float *quer
                                   uint32_t *out_counts, int32_t *out_status) {
     hipStream_t st = hp->s[0];
     Workspace *w;
-    int32_t rc = get_workspace(ix, (void *)st, st, B, top_k, true, &w);
+    SearchLaunch L;
+    int32_t rc = get_workspace(ix, (void *)st, st, B, top_k, true, &w, &L);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(w->d_queries, queries, (size_t)B * ix->p.dim * 4, hipMemcpyHostToDevice, st));
-    rc = run_search(ix, w, w->d_queries, B, top_k, w->d_out_ids, w->d_out_scores, w->d_out_counts, w->d_out_status, true, st);
+    rc = run_search(ix, w, L, w->d_queries, B, top_k, w->d_out_ids, w->d_out_scores, w->d_out_counts, w->d_out_status, true, st);
     if (rc) { (void)hipDeviceSynchronize(); return rc; } // the walk may be running on the workspace's side stream
     std::vector<int32_t> status(B);
     hipError_t e = hipMemcpyAsync(out_ids, w->d_out_ids, (size_t)B * top_k * 4, hipMemcpyDeviceToHost, st);
@@ -1323,15 +1337,16 @@ static int32_t search_host_pipelined(cos_index *ix, HostPipe *hp, const float *q
         const u32 c0 = i * chunk, cb = std::min(chunk, B - c0);
         hipStream_t st = hp->s[i & 1];
         Workspace *w;
-        int32_t rc = get_workspace(ix, (void *)&hp->wkey[i], st, cb, top_k, false, &w);
+        SearchLaunch L;
+        int32_t rc = get_workspace(ix, (void *)&hp->wkey[i], st, cb, top_k, false, &w, &L, false);
         if (rc) return rc;
         float *dq = hp->d_q + (size_t)c0 * dim;
         const float *src = queries + (size_t)c0 * dim;
         HIP_TRY(hipMemcpyAsync(dq, src, (size_t)cb * dim * 4, hipMemcpyHostToDevice, hp->sc));
         HIP_TRY(hipEventRecord(hp->ev_in[i], hp->sc));
         HIP_TRY(hipStreamWaitEvent(st, hp->ev_in[i], 0));
-        rc = run_search(ix, w, dq, cb, top_k, hp->d_ids + (size_t)c0 * top_k, hp->d_scores + (size_t)c0 * top_k, hp->d_counts + c0, hp->d_status + c0,
-                        true, st, hp->sf, hp->ev_walk[i], false);
+        rc = run_search(ix, w, L, dq, cb, top_k, hp->d_ids + (size_t)c0 * top_k, hp->d_scores + (size_t)c0 * top_k, hp->d_counts + c0, hp->d_status + c0,
+                        true, st, hp->sf, hp->ev_walk[i]);
         if (rc) return rc;
     }
     std::vector<int32_t> status(B);
@@ -1457,10 +1472,11 @@ static int32_t co_slot_run(cos_index *ix, CoSlot *sl) {
     u32 *p_cnt = (u32 *)(p_sc + (size_t)sl->cap * top_k);
     int32_t *p_st = (int32_t *)(p_cnt + sl->cap);
     Workspace *w;
-    rc = get_workspace(ix, (void *)st, st, total, top_k, true, &w);
+    SearchLaunch L;
+    rc = get_workspace(ix, (void *)st, st, total, top_k, true, &w, &L);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(w->d_queries, sl->pin_q, (size_t)total * ix->p.dim * 4, hipMemcpyHostToDevice, st));
-    rc = run_search(ix, w, w->d_queries, total, top_k, w->d_out_ids, w->d_out_scores, w->d_out_counts, w->d_out_status, true, st);
+    rc = run_search(ix, w, L, w->d_queries, total, top_k, w->d_out_ids, w->d_out_scores, w->d_out_counts, w->d_out_status, true, st);
     if (rc) { (void)hipDeviceSynchronize(); return rc; } // the walk may be running on the workspace's side stream
     hipError_t e = hipMemcpyAsync(p_ids, w->d_out_ids, (size_t)total * top_k * 4, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipMemcpyAsync(p_sc, w->d_out_scores, (size_t)total * top_k * 4, hipMemcpyDeviceToHost, st);
@@ -1617,11 +1633,12 @@ extern "C" int32_t cos_ann_search_batch(cos_index *ix, const float *queries, uin
     if (rc) return rc;
     hipStream_t st = lease.hp->s[0];
     Workspace *w;
-    rc = get_workspace(ix, (void *)st, st, B, 1, true, &w);
+    SearchLaunch L;
+    rc = get_workspace(ix, (void *)st, st, B, 1, true, &w, &L);
     if (rc) return rc;
     const u32 L1 = ix->p.num_layers + 1;
     HIP_TRY(hipMemcpyAsync(w->d_queries, queries, (size_t)B * ix->p.dim * 4, hipMemcpyHostToDevice, st));
-    rc = run_search(ix, w, w->d_queries, B, 1, nullptr, nullptr, nullptr, nullptr, false, st);
+    rc = run_search(ix, w, L, w->d_queries, B, 1, nullptr, nullptr, nullptr, nullptr, false, st);
     if (rc) return rc;
     std::vector<int32_t> status(B);
     HIP_TRY(hipMemcpyAsync(out_ids, w->walk_ids, (size_t)B * L1 * KEEP_SEARCH * 4, hipMemcpyDeviceToHost, st));
@@ -1635,22 +1652,30 @@ extern "C" int32_t cos_ann_search_batch(cos_index *ix, const float *queries, uin
     return COS_OK;
 }
 
+// the workspace of `stream`'s launches, or (stream == NULL and `null_is_last`) of the handle's most recent launch
+static Workspace *find_workspace(cos_index *ix, void *stream, bool null_is_last) {
+    std::lock_guard<std::mutex> g(ix->mu);
+    if (!stream && null_is_last) return ix->last_ws;
+    auto it = ix->ws.find(stream);
+    return it != ix->ws.end() ? it->second.get() : nullptr;
+}
+// the per-query counters [B][4] of a launch (WalkArgs::out_stats / out_stats2), summed over the launch
+static int32_t sum_launch_stats(const u64 *d_stats, u32 B, u64 sum[4]) {
+    std::vector<u64> st((size_t)B * 4);
+    HIP_TRY(hipMemcpy(st.data(), d_stats, st.size() * 8, hipMemcpyDeviceToHost));
+    sum[0] = sum[1] = sum[2] = sum[3] = 0;
+    for (u32 b = 0; b < B; b++)
+        for (int k = 0; k < 4; k++) sum[k] += st[(size_t)b * 4 + k];
+    return COS_OK;
+}
+
 extern "C" int32_t cos_index_last_stats(cos_index *ix, void *stream, cos_search_stats *out) {
     if (!ix || !out) return cos_fail(COS_ERR_INVALID, "null argument");
     memset(out, 0, sizeof(*out));
     int32_t rc = cos_set_device(ix);
     if (rc) return rc;
-    Workspace *w = nullptr;
-    {
-        std::lock_guard<std::mutex> g(ix->mu);
-        if (stream) {
-            auto it = ix->ws.find(stream);
-            if (it != ix->ws.end()) w = it->second.get();
-        } else
-            w = ix->last_ws;
-        if (!w) return cos_fail(COS_ERR_NOT_READY, "no batch has run on this stream");
-    }
-    if (w->lastB == 0) return cos_fail(COS_ERR_NOT_READY, "no batch has run on this stream");
+    Workspace *w = find_workspace(ix, stream, true);
+    if (!w || w->lastB == 0) return cos_fail(COS_ERR_NOT_READY, "no batch has run on this stream");
     if (w->timed && w->ev_count) {
         hipEvent_t *ev = &w->ev[(size_t)((w->ev_count - 1) % Workspace::EV_RING) * Workspace::EV_PER];
         HIP_TRY(hipEventSynchronize(ev[3]));
@@ -1660,16 +1685,15 @@ extern "C" int32_t cos_index_last_stats(cos_index *ix, void *stream, cos_search_
     } else {
         HIP_TRY(hipDeviceSynchronize());
     }
-    std::vector<u64> st((size_t)w->lastB * 4), rr(w->lastB);
-    HIP_TRY(hipMemcpy(st.data(), w->stats, st.size() * 8, hipMemcpyDeviceToHost));
+    u64 st[4];
+    if ((rc = sum_launch_stats(w->stats, w->lastB, st))) return rc;
+    out->evals = st[0];
+    out->expansions = st[1];
+    out->adj_bytes = st[2];
+    out->reserved = (uint32_t)st[3]; // walk rounds (lookahead windows issued)
+    std::vector<u64> rr(w->lastB);
     HIP_TRY(hipMemcpy(rr.data(), w->rerank_rows, rr.size() * 8, hipMemcpyDeviceToHost));
-    for (u32 b = 0; b < w->lastB; b++) {
-        out->evals += st[(size_t)b * 4 + 0];
-        out->expansions += st[(size_t)b * 4 + 1];
-        out->adj_bytes += st[(size_t)b * 4 + 2];
-        out->reserved += (uint32_t)st[(size_t)b * 4 + 3]; // walk rounds (lookahead windows issued)
-        out->rerank_rows += rr[b];
-    }
+    for (u32 b = 0; b < w->lastB; b++) out->rerank_rows += rr[b];
     return COS_OK;
 }
 
@@ -1680,25 +1704,18 @@ extern "C" int32_t cos_index_last_walk_split(cos_index *ix, void *stream, cos_wa
     out->struct_size = sizeof(cos_walk_split);
     int32_t rc = cos_set_device(ix);
     if (rc) return rc;
-    Workspace *w = nullptr;
-    {
-        std::lock_guard<std::mutex> g(ix->mu);
-        if (stream) {
-            auto it = ix->ws.find(stream);
-            if (it != ix->ws.end()) w = it->second.get();
-        } else
-            w = ix->last_ws;
-    }
+    Workspace *w = find_workspace(ix, stream, true);
     if (!w || w->lastB == 0) return cos_fail(COS_ERR_NOT_READY, "no batch has run on this stream");
+    const cosdev::WalkPlan &plan = w->last_plan;
     out->queries = w->lastB;
-    out->table_level_min = w->last_tab ? w->last_tab_level_min : 0u; // of THAT launch (the handle's may have moved on with ef_search)
-    out->table_cols = w->last_tab ? w->last_tab_cols : 0u;
-    out->cut_after_level = w->last_cut_level;
+    out->table_level_min = plan.table_level_min; // of THAT launch (the handle's may have moved on with ef_search)
+    out->table_cols = plan.table_cols;
+    out->cut_after_level = plan.cut_after_level;
     if (w->timed && w->ev_count) {
         hipEvent_t *ev = &w->ev[(size_t)((w->ev_count - 1) % Workspace::EV_RING) * Workspace::EV_PER];
         HIP_TRY(hipEventSynchronize(ev[3]));
-        if (w->last_tab) HIP_TRY(hipEventElapsedTime(&out->table_ms, ev[4], ev[5]));
-        if (w->last_split) {
+        if (plan.use_table) HIP_TRY(hipEventElapsedTime(&out->table_ms, ev[4], ev[5]));
+        if (plan.ordered) {
             HIP_TRY(hipEventElapsedTime(&out->upper_ms, ev[1], ev[6]));
             HIP_TRY(hipEventElapsedTime(&out->sort_ms, ev[6], ev[7]));
             HIP_TRY(hipEventElapsedTime(&out->lower_ms, ev[7], ev[2]));
@@ -1709,22 +1726,15 @@ extern "C" int32_t cos_index_last_walk_split(cos_index *ix, void *stream, cos_wa
     }
     const u32 kdims = (u32)((ix->row_stride + 63) / 64 * 64);
     out->table_int8_ops = 2.0 * (double)w->lastB * (double)out->table_cols * (double)kdims;
-    std::vector<u64> st((size_t)w->lastB * 4), s2((size_t)w->lastB * 4);
-    HIP_TRY(hipMemcpy(st.data(), w->stats, st.size() * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(s2.data(), w->stats2, s2.size() * 8, hipMemcpyDeviceToHost));
-    u64 te = 0, tx = 0, ta = 0;
-    for (u32 b = 0; b < w->lastB; b++) {
-        te += st[(size_t)b * 4 + 0];
-        tx += st[(size_t)b * 4 + 1];
-        ta += st[(size_t)b * 4 + 2];
-        out->lower_evals += s2[(size_t)b * 4 + 0];
-        out->lower_expansions += s2[(size_t)b * 4 + 1];
-        out->lower_adj_bytes += s2[(size_t)b * 4 + 2];
-        out->table_evals += s2[(size_t)b * 4 + 3];
-    }
-    out->upper_evals = te - out->lower_evals;
-    out->upper_expansions = tx - out->lower_expansions;
-    out->upper_adj_bytes = ta - out->lower_adj_bytes;
+    u64 st[4], s2[4];
+    if ((rc = sum_launch_stats(w->stats, w->lastB, st)) || (rc = sum_launch_stats(w->stats2, w->lastB, s2))) return rc;
+    out->lower_evals = s2[0];
+    out->lower_expansions = s2[1];
+    out->lower_adj_bytes = s2[2];
+    out->table_evals = s2[3];
+    out->upper_evals = st[0] - s2[0];
+    out->upper_expansions = st[1] - s2[1];
+    out->upper_adj_bytes = st[2] - s2[2];
     return COS_OK;
 }
 
@@ -1733,12 +1743,7 @@ extern "C" int32_t cos_index_timing_summary(cos_index *ix, void *stream, cos_tim
     memset(out, 0, sizeof(*out));
     int32_t rc = cos_set_device(ix);
     if (rc) return rc;
-    Workspace *w = nullptr;
-    {
-        std::lock_guard<std::mutex> g(ix->mu);
-        auto it = ix->ws.find(stream);
-        if (it != ix->ws.end()) w = it->second.get();
-    }
+    Workspace *w = find_workspace(ix, stream, false);
     if (!w || w->ev_count == 0) return cos_fail(COS_ERR_NOT_READY, "no timed batch has run on this stream");
     const u32 n = std::min(w->ev_count, Workspace::EV_RING);
     out->launches = n;
@@ -1919,7 +1924,8 @@ static int32_t search_filtered_host(cos_index *ix, const float *queries, u32 B, 
     hipStream_t st = lease.hp->s[0];
     struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{st};
     Workspace *w;
-    rc = get_workspace(ix, (void *)st, st, B, top_k ? top_k : 1, true, &w);
+    SearchLaunch unused; // (the metadata walk has its own launch; the workspace is shared)
+    rc = get_workspace(ix, (void *)st, st, B, top_k ? top_k : 1, true, &w, &unused);
     if (rc) return rc;
     // the batch's filters in the workspace's own buffer, ONE copy: [dims nf x md | norms nf | offsets B + 1]
     const size_t f_words = fd.size() + fm.size() + (size_t)B + 1;

@@ -16,6 +16,7 @@
 #include "tuning.h"
 #include "link_types.h"
 #include "dev_mem.h"
+#include "walk_plan.h"
 
 namespace cosdev {
 hipError_t launch_fill_i32(int32_t *p, u64 n, int32_t v, hipStream_t st);
@@ -32,9 +33,9 @@ hipError_t launch_link_round(const LinkArgs &a, u32 maxM, const u32 *pend, const
                              u32 count_ub, u32 round, hipStream_t st);
 hipError_t launch_quantize_rows(int eng, const float *x, u64 x_stride, u32 n, u32 dim, float lo, float hi, uint8_t *codes,
                                 u64 row_stride, float *mags, float *raw_mags, hipStream_t st);
-hipError_t launch_walk(int eng, const IndexDev &ix, const WalkArgs &wa, u32 lat_max_B, u32 lat4_max_B, hipStream_t st);
-bool walk_general_needed(const IndexDev &ix, u32 ef); // kernels_walk_general.hip: ef > 1024 or more than 64 scanned slots per node
-int walk_kernel_kind(int eng, const IndexDev &ix, const WalkArgs &wa, u32 lat_max_B, u32 lat4_max_B, bool table_available); // 0 throughput | 1 one-wave | 4 four-wave latency kernel
+hipError_t launch_walk(int eng, const IndexDev &ix, const WalkArgs &wa, WalkKernel kernel, hipStream_t st); // `kernel`: WalkPlan::kernel (walk_plan.h)
+static_assert(WALK_PLAN_MAX_LEVELS == MAX_LEVELS && WALK_PLAN_ENG_U8 == ENG_U8 && WALK_PLAN_ENG_Q2 == ENG_Q2 && WALK_PLAN_FAST_MAX_EF == WALK_FAST_MAX_EF &&
+              COS_STORAGE_U8 == 0u && COS_VISITED_REF == 0u, "walk_plan.h restates these");
 hipError_t launch_walk_meta(int eng, const IndexDev &ix, const WalkArgs &wa, hipStream_t st);
 hipError_t launch_walk_meta_index(int eng, const IndexDev &ix, const WalkArgs &wa, hipStream_t st);
 hipError_t launch_finalize(const IndexDev &ix, const float *queries, u64 q_stride, const float *q_raw_mags, const u32 *walk_ids,
@@ -148,7 +149,7 @@ struct Workspace {
     // timing: a ring of event quadruples (before prep | after prep | after walk | after finalize), one per launch, so a
     // run of launches can be summarised afterwards without synchronising between them (cos_index_timing_summary)
     // + the inner marks of a big launch's walk: [4] before / [5] after the level-table GEMM (caller's stream), [6] after the upper
-    // level range, [7] after the order sort (walk stream); lastSplit says which of them the last launch recorded
+    // level range, [7] after the order sort (walk stream); last_plan says which of them the last launch recorded
     static constexpr u32 EV_RING = 128;
     static constexpr u32 EV_PER = 8;
     std::vector<hipEvent_t> ev; // [EV_RING][EV_PER]
@@ -159,8 +160,7 @@ struct Workspace {
     hipEvent_t prep_done = nullptr, walk_fin = nullptr; // caller's stream -> walk stream -> finalize stream
     u32 lastB = 0;
     bool timed = false;
-    bool last_tab = false, last_split = false; // the last launch used the level table / was cut into two level ranges
-    u32 last_tab_cols = 0, last_tab_level_min = 0, last_cut_level = 0;
+    cosdev::WalkPlan last_plan{}; // of the last launch: whether it used the level table / was cut into level ranges, and where
     Workspace() = default;
     Workspace(const Workspace &) = delete;
     ~Workspace() { // (the caller has drained the device: cos_index_destroy)
@@ -299,5 +299,6 @@ void cos_coalesce_release(cos_index *ix);
 cosdev::IndexDev cos_make_index_dev(const cos_index *ix);
 cosdev::IndexDev cos_make_meta_dev(const cos_index *ix);
 int32_t cos_set_device(const cos_index *ix);
+cosdev::WalkPlanIn cos_walk_plan_in(const cos_index *ix, u32 B, u32 ef); // the handle's shape and resolved knobs as walk_plan's inputs (engine.hip)
 int32_t cos_prepare_walk_plans(cos_index *ix); // order ranks + level-table operand of a freshly committed graph (engine.hip)
 void cos_meta_free_levels(cos_index *ix); // device arrays + host lists of every level of the pseudo-root component

@@ -18,6 +18,7 @@
 #include "engine_types.h"
 #include "tuning.h"
 #include "walk_common.h"
+#include "walk_plan.h"
 
 using namespace cosdev;
 
@@ -614,54 +615,17 @@ static hipError_t launch_walk_r(const IndexDev &ix, const WalkArgs &wa_in, hipSt
     return hipGetLastError();
 }
 
-// kernels_walk_lat.hip
-bool walk_lat_applicable(int eng, const IndexDev &ix, const WalkArgs &wa, u32 max_B);
+// kernels_walk_lat.hip, kernels_walk_lat4.hip, kernels_walk_general.hip
 hipError_t launch_walk_lat(int eng, const IndexDev &ix, const WalkArgs &wa, hipStream_t st);
-
-// kernels_walk_lat4.hip
-bool walk_lat4_applicable(int eng, const IndexDev &ix, const WalkArgs &wa, u32 max_B);
 hipError_t launch_walk_lat4(int eng, const IndexDev &ix, const WalkArgs &wa, hipStream_t st);
-// kernels_walk_general.hip
-bool walk_general_needed(const IndexDev &ix, u32 ef);
 hipError_t launch_walk_general(int eng, const IndexDev &ix, const WalkArgs &wa, hipStream_t st);
 
-// lat_max_B: launches of at most this many queries take the latency kernel where it applies (cos_index_set_latency_mode; 0 = never);
-// lat4_max_B: the smallest of them give every query four waves (cos_index_set_latency_waves; 0 = never).
-// tuning knobs walk_lat / walk_lat4 = <n> override the handle's values (experiments: 0 = off, 4294967295 = always)
-// does the kernel launch_walk would pick for this launch read WalkArgs::tab?  (the throughput kernel and the four-wave latency
-// kernel do; the one-wave latency kernel does not: engine.hip then skips the table GEMM)
-static void walk_env_overrides(u32 &lat_max_B, u32 &lat4_max_B) {
-    const long long lat_env = tune_or(TUNE_WALK_LAT, -1), lat4_env = tune_or(TUNE_WALK_LAT4, -1);
-    if (lat_env >= 0) lat_max_B = lat_env > 0xFFFFFFFFll ? 0xFFFFFFFFu : (u32)lat_env;
-    if (lat4_env >= 0) lat4_max_B = lat4_env > 0xFFFFFFFFll ? 0xFFFFFFFFu : (u32)lat4_env;
-}
-// table_available: the launch can have a level table (u8 codes).  With the table the throughput kernel beats the one-wave latency
-// kernel at every launch size (1M x 768, ms per launch at ef 64 / 256: 256 queries 0.77 / 2.20 against 0.99 / 2.37; 1 024 queries
-// 0.84 / 2.33 against 1.13 / 2.57; 2 048 queries 0.95 / 2.58 against 1.50 / 2.91) and the four-wave kernel up to ef 64 (0.77
-// against 0.82 with the table, 0.88 without); above ef 64 the four-wave kernel with the table stays ahead on one client batch
-// (1.73 against 2.20 at ef 256).  profiles/r04_single_batch_probe.jsonl, r04_mid_size_probe.jsonl.  Round 6 (r06_single_batch_probe.jsonl): one
-// client batch with the automatic table — ef 64 0.642 / 0.643 ms (throughput / four waves), ef 128 1.017 / 1.148, ef 256 1.747 / 1.658.
-int walk_kernel_kind(int eng, const IndexDev &ix, const WalkArgs &wa, u32 lat_max_B, u32 lat4_max_B, bool table_available) { // 0 throughput, 1 one-wave latency, 4 four-wave latency
-    walk_env_overrides(lat_max_B, lat4_max_B);
-    const bool tk_small = tune_or(TUNE_WALK_SMALL_TABLE_TK, 1) != 0;
-    if (table_available && tk_small && eng == ENG_U8) {
-        if (wa.phase == 0u && wa.ef > 128u && walk_lat4_applicable(eng, ix, wa, lat4_max_B)) return 4; // (round 6: the 128-key pool + ranked merge moved the crossover from ef 64 to 128)
-        return 0;
-    }
-    if (wa.phase == 0u) {
-        if (walk_lat4_applicable(eng, ix, wa, lat4_max_B)) return 4;
-        if (walk_lat_applicable(eng, ix, wa, lat_max_B)) return 1;
-    }
-    return 0;
-}
-
-hipError_t launch_walk(int eng, const IndexDev &ix, const WalkArgs &wa, u32 lat_max_B, u32 lat4_max_B, hipStream_t st) {
+// `kernel` is the launch plan's choice (walk_plan.h): nothing is decided here
+hipError_t launch_walk(int eng, const IndexDev &ix, const WalkArgs &wa, WalkKernel kernel, hipStream_t st) {
     if (wa.B == 0) return hipSuccess;
-    if (walk_general_needed(ix, wa.ef)) return launch_walk_general(eng, ix, wa, st); // ef > 1024 or more than 64 scanned slots per node
-    // the split (locality-ordered) walk and the unseeded filter of delete_embedding's walks (WalkArgs::no_self_seed) exist in the throughput kernel only
-    const int kind = wa.no_self_seed ? 0 : walk_kernel_kind(eng, ix, wa, lat_max_B, lat4_max_B, wa.tab != nullptr);
-    if (kind == 4) return launch_walk_lat4(eng, ix, wa, st);
-    if (kind == 1) return launch_walk_lat(eng, ix, wa, st);
+    if (kernel == WalkKernel::General) return launch_walk_general(eng, ix, wa, st);
+    if (kernel == WalkKernel::Lat4) return launch_walk_lat4(eng, ix, wa, st);
+    if (kernel == WalkKernel::Lat1) return launch_walk_lat(eng, ix, wa, st);
     const u32 ch = (eng == ENG_F32 || eng == ENG_F16) ? 1 : (ix.nchunks + ix.G - 1) / ix.G;
     switch (eng) {
     case ENG_U8:

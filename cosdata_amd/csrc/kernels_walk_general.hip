@@ -281,16 +281,6 @@ hipError_t launch_general_eng(const IndexDev &ix, const WalkArgs &wa, size_t sme
 
 namespace cosdev {
 
-// the launches walk_kernel and the latency kernels cannot hold (engine.hip: cos_index_create's domain checks follow this)
-bool walk_general_needed(const IndexDev &ix, u32 ef) {
-    if (ef > WALK_FAST_MAX_EF) return true;
-    // code rows wider than walk_kernel's chunk passes: u8 above 4096 dims (four passes of 64 lanes x 16 B), SubByte above 64 chunks
-    if (ix.nchunks != 0u && ix.G != 0u && (ix.nchunks + ix.G - 1u) / ix.G > (ix.storage == 0u /* COS_STORAGE_U8 */ ? 4u : 1u)) return true;
-    for (u32 l = 0; l <= ix.num_layers; l++)
-        if (std::min(ix.lv[l].M, ix.shortlist) > 64u) return true;
-    return false;
-}
-
 hipError_t launch_walk_general(int eng, const IndexDev &ix, const WalkArgs &wa_in, hipStream_t st) {
     if (wa_in.phase != 0u || wa_in.ef > WALK_GENERAL_MAX_EF) return hipErrorInvalidValue;
     WalkArgs wa = wa_in;

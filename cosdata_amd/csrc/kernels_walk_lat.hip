@@ -291,9 +291,6 @@ hipError_t launch_lat_ch(const IndexDev &ix, const WalkArgs &wa, u32 ch, u32 la,
 
 namespace cosdev {
 
-// which launches take the latency kernel: reference filter, u8 / quaternary codes of <= 64 chunks, ef <= 256, at most max_B queries
-bool walk_lat_applicable(int eng, const IndexDev &ix, const WalkArgs &wa, u32 max_B) { return walk_latency_domain(eng, ix, wa, max_B); }
-
 hipError_t launch_walk_lat(int eng, const IndexDev &ix, const WalkArgs &wa, hipStream_t st) {
     // window size: 4 (profiles/archive/r02_latency_walk_sweep_first_version_window4_vs_8.jsonl: an 8-entry window needs 24 % fewer rounds but only 3.9
     // of its 8 entries are consumed before it goes stale, and the wasted evaluations cost more issue time than the rounds save; the

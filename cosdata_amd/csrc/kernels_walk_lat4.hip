@@ -380,12 +380,6 @@ hipError_t launch_lat4_ch(const IndexDev &ix, const WalkArgs &wa, u32 ch, hipStr
 
 namespace cosdev {
 
-// same launches as the one-wave latency kernel (walk_lat_applicable), up to max_B queries
-bool walk_lat4_applicable(int eng, const IndexDev &ix, const WalkArgs &wa, u32 max_B) {
-    if (!walk_latency_domain(eng, ix, wa, max_B)) return false;
-    return walk_mmax(ix) <= 64; // s_first is sized 64 * Mmax words: keep the workgroup's LDS small
-}
-
 hipError_t launch_walk_lat4(int eng, const IndexDev &ix, const WalkArgs &wa, hipStream_t st) {
     // window: 4 entries (one per wave).  8 (two per wave, COS_WALK_LAT4_E=2) needs 24 % fewer rounds but measured 2.6x slower per
     // round (profiles/archive/r03_latency_sweep_*): the wasted evaluations and the wider merge cost every wave more than the rounds save

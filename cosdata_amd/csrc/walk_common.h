@@ -22,16 +22,6 @@ __host__ __device__ __forceinline__ u32 walk_mmax(const IndexDev &ix) {
     return ix.lv[0].M > ix.lv[ix.num_layers].M ? ix.lv[0].M : ix.lv[ix.num_layers].M;
 }
 
-// the launches both latency kernels take: reference filter, u8 / quaternary codes of <= 64 chunks, 1 <= ef <= 256, at most max_B queries
-static inline bool walk_latency_domain(int eng, const IndexDev &ix, const WalkArgs &wa, u32 max_B) {
-    if (max_B == 0 || wa.B > max_B) return false;
-    if (ix.visited_mode != 0) return false;
-    if (eng != ENG_U8 && eng != ENG_Q2) return false;
-    if (ix.nchunks == 0 || ix.nchunks > (u32)(4 * LAT_ROW_LANES)) return false;
-    if (wa.ef == 0 || wa.ef > 256) return false;
-    return true;
-}
-
 // ---- visited filter: PerformantFixedSet, 2 * M words of LDS per level ---------------------------------------------------------
 // bucket = (id >> 6) & (M - 1), bit = id & 63  <=>  linear bit id & (64 * M - 1) (bitmask); the id of vector row `row`
 __device__ __forceinline__ u32 vis_bit_of(u32 row, u32 N, u32 id_stride, u32 bitmask) {
