@@ -44,6 +44,8 @@ __device__ __forceinline__ u64 pack_key(u32 hi, u32 lo) { return ((u64)hi << 32)
 // integer sums; the SubByte / float storages, whose norms come from the raw vectors, keep the full division), so the scale
 // factors are 1, div_fmas is a plain FMA and the fix-up is the identity: same bits, four instructions less per quotient.
 // (den == 0 never reaches it: the callers test for CalculationError first.)
+// Checked bit for bit against the host's quotient by tests/cxx/wave_prims_check.hip: 2^24 pairs the walk can form (rows of up to 4096
+// dimensions, so num up to 255^2 * 4096 < 2^28) and 2^24 pairs of the range above.
 __device__ __forceinline__ float div_rn_unscaled(float num, float den) {
     float r = __builtin_amdgcn_rcpf(den);
     const float e = __builtin_fmaf(-den, r, 1.0f);
@@ -94,7 +96,8 @@ __device__ __forceinline__ u64 dpp_wave_shl1_u64(u64 v, u64 fill) { // lane l <-
     return ((u64)hi << 32) | lo;
 }
 // sum over aligned groups of G lanes (G power of two, 2..64); every lane of a group (G <= 32) or of the
-// wave (G = 64) ends with the group total.  Integer adds: order-independent, exact.
+// wave (G = 64) ends with the group total.  Integer adds: order-independent, exact.  (G = 1 returns v.)
+// Checked at every G by tests/cxx/wave_prims_check.hip.
 __device__ __forceinline__ u32 group_reduce_add_u32(u32 v, int G) {
     if (G >= 2) v += dpp_mov<0xB1>(0u, v);     // quad_perm [1,0,3,2]: xor 1
     if (G >= 4) v += dpp_mov<0x4E>(0u, v);     // quad_perm [2,3,0,1]: xor 2

@@ -8,6 +8,7 @@
 //   * ties between equal scores are resolved by the key's low half (the larger id first): keys are unique, so the order of the
 //     u64 keys is the whole rule.
 // Register networks (one wave, cross-lane moves) come first, the LDS networks (one workgroup, any size) last.
+// Checked on the device primitive by primitive, at every width the kernels instantiate, by tests/cxx/topk_select_check.hip (host models: tests/cxx/topk_check_host.h).
 #pragma once
 #include "device_common.h"
 

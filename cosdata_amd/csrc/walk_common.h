@@ -37,7 +37,7 @@ __device__ __forceinline__ void vis_clear(u32 *vis, u32 M, int tid) {
 __device__ __forceinline__ void vis_set_bit(u32 *vis, u32 bit) { vis[bit >> 5] |= 1u << (bit & 31); }
 // Two slots of one expansion alias the same residue: the LOWER slot wins (sequential scan order).  cmask: the lanes that claimed
 // their bit with an atomic OR, lostmask: those that found it set by then (by another lane of this expansion: it was clear when the
-// expansion began).  Returns the expansion's winners.
+// expansion began).  Returns the expansion's winners.  Checked by tests/cxx/wave_prims_check.hip.
 __device__ __forceinline__ u64 vis_alias_winners(u64 cmask, u32 bit, u64 lostmask) {
     u64 wmask = cmask & ~lostmask;
     while (lostmask) {
