@@ -52,7 +52,7 @@ class CosWalkSplit(C.Structure):
     """cos_walk_split: the last batch of a stream split by dispatch (level-table GEMM | levels above the cut | levels below it)."""
     _fields_ = [
         ("struct_size", C.c_uint32), ("queries", C.c_uint32), ("table_level_min", C.c_uint32), ("table_cols", C.c_uint32),
-        ("cut_after_level", C.c_uint32), ("reserved", C.c_uint32),
+        ("cut_after_level", C.c_uint32), ("table_early_wgs", C.c_uint32),
         ("table_ms", C.c_float), ("upper_ms", C.c_float), ("sort_ms", C.c_float), ("lower_ms", C.c_float),
         ("table_int8_ops", C.c_double), ("table_evals", C.c_uint64),
         ("upper_evals", C.c_uint64), ("upper_expansions", C.c_uint64), ("upper_adj_bytes", C.c_uint64),

@@ -747,6 +747,9 @@ static u32 walk_table_min_B(const cos_index *ix) {
     const long long env = cosdev::tune_or(cosdev::TUNE_WALK_TABLE_MIN_B, -1);
     return env >= 0 ? (u32)std::min<long long>(env, 0xFFFFFFFFll) : ix->walk_table_min_B;
 }
+// Workgroups of the early part of a gated level-table GEMM (walk_plan.h; tuning knob walk_table_early_wgs).  Measured on the 12.5M x 1024
+// shard, 32 768 queries per step: DESIGN.md §8.1, profiles/r07_table_early_wgs_sweep.jsonl.
+static constexpr long long WALK_TABLE_EARLY_WGS_DEFAULT = 0;
 // the handle as walk_plan (walk_plan.h) sees it: shape, every knob resolved (the tuning registry's overrides included), a launch of B
 // queries at beam width ef that takes part in the walk chain.  Caller holds ix->mu where the handle is shared.
 cosdev::WalkPlanIn cos_walk_plan_in(const cos_index *ix, u32 B, u32 ef) {
@@ -776,6 +779,9 @@ cosdev::WalkPlanIn cos_walk_plan_in(const cos_index *ix, u32 B, u32 ef) {
     in.table_after_sort = cosdev::tune_or(cosdev::TUNE_WALK_TABLE_AFTER_SORT, 1);
     in.table_supported = cosdev::level_table_eng_supported(ix->eng, ix->row_stride);
     in.adj_mag_valid = ix->adj_mag_valid;
+    in.table_early_wgs = (u32)std::min<long long>(std::max<long long>(cosdev::tune_or(cosdev::TUNE_WALK_TABLE_EARLY_WGS, WALK_TABLE_EARLY_WGS_DEFAULT), 0), 0xFFFFFFFFll);
+    in.table_queue = cosdev::level_table_gemm_queue(ix->eng, ix->row_stride);
+    in.n_cus = ix->n_cus;
     return in;
 }
 static int32_t ensure_level_table(cos_index *ix) {
@@ -991,6 +997,7 @@ static int32_t get_workspace(cos_index *ix, void *key, hipStream_t st, u32 B, u3
         HIP_TRY(w->stats.alloc((size_t)cap * 4));
         HIP_TRY(w->stats2.alloc((size_t)cap * 4));
         HIP_TRY(w->qsums.alloc(cap));
+        HIP_TRY(w->tab_queue.alloc(16));
         if (ix->eng == ENG_Q2) HIP_TRY(w->qdig.alloc((size_t)cap * (ix->row_stride / 16) * 64)); // the table GEMM's digit rows of the queries
         HIP_TRY(w->fin_flags.alloc((size_t)cap + 1));
         HIP_TRY(w->rerank_rows.alloc(cap));
@@ -1072,6 +1079,7 @@ static int32_t get_workspace(cos_index *ix, void *key, hipStream_t st, u32 B, u3
     if (!w->walk_done) HIP_TRY(hipEventCreateWithFlags(&w->walk_done, hipEventDisableTiming));
     if (!w->walk_fin) HIP_TRY(hipEventCreateWithFlags(&w->walk_fin, hipEventDisableTiming));
     if (!w->last_range) HIP_TRY(hipEventCreateWithFlags(&w->last_range, hipEventDisableTiming));
+    if (!w->upper_done) HIP_TRY(hipEventCreateWithFlags(&w->upper_done, hipEventDisableTiming));
     *out = w;
     return COS_OK;
 }
@@ -1097,19 +1105,32 @@ static int32_t run_search(cos_index *ix, Workspace *w, const SearchLaunch &L, co
     hipEvent_t *ev = &w->ev[(size_t)(w->ev_count % Workspace::EV_RING) * Workspace::EV_PER];
     if (timed) HIP_TRY(hipEventRecord(ev[0], st));
     HIP_TRY(launch_quantize_rows(ix->eng, d_queries, ix->p.dim, B, ix->p.dim, ix->p.range_lo, ix->p.range_hi, w->q_codes, ix->row_stride,
-                                 w->q_mags, w->q_raw_mags, st));
+                                 w->q_mags, w->q_raw_mags, st, plan.use_table && ix->eng == ENG_U8 ? w->qsums.p : nullptr));
     // Level table: on the caller's stream, i.e. BEFORE the walk takes its place in the walk chain — the GEMM of this launch runs next
     // to the previous launch's walk.  (Round 5 also issued it inside the chain, right in front of its own walk, where it shares the
     // chip with nobody: 7.07-7.12 against 6.69 ms per step — the overlap hides 0.4 ms.  profiles/r05_table_gemm_in_chain_probe_not_kept.jsonl)
+    // A gated GEMM (plan.table_waits_for_sort) goes out as two launches over one queue of work items where the plan says so (walk_plan.h):
+    // plan.table_early_wgs workgroups behind the previous chained walk's upper range, then the full width behind that walk's end for what
+    // is left of the queue.  Both on the caller's stream, i.e. one after the other: the early part leaves when the queue is empty
+    // (measured, not a gain, the knob's default is 0).
     if (plan.use_table) {
-        if (plan.table_waits_for_sort) { // (engine_internal.h, chain_last_range_ev)
-            std::lock_guard<std::mutex> g(ix->chain_mu);
-            if (ix->chain_last_range_ev && ix->chain_last_range_ev != w->last_range) HIP_TRY(hipStreamWaitEvent(st, ix->chain_last_range_ev, 0));
-        }
-        if (timed) HIP_TRY(hipEventRecord(ev[4], st));
-        HIP_TRY(cosdev::launch_level_table(ix->eng, w->q_codes, w->q_mags, w->qsums, w->qdig, B, L.tcodes, L.tmags, L.tcsums, ix->row_stride, plan.table_cols,
-                                           w->tab, L.tab_stride, ix->n_cus, st));
-        if (timed) HIP_TRY(hipEventRecord(ev[5], st));
+        auto table_part = [&](hipEvent_t cos_index::*handle_ev, hipEvent_t own_ev, hipEvent_t *marks, u32 wgs, bool first) -> int32_t {
+            if (plan.table_waits_for_sort) { // (engine_internal.h, chain_last_range_ev / chain_upper_ev; this workspace's own walk: stream order)
+                std::lock_guard<std::mutex> g(ix->chain_mu);
+                if (ix->*handle_ev && ix->*handle_ev != own_ev) HIP_TRY(hipStreamWaitEvent(st, ix->*handle_ev, 0));
+            }
+            if (timed) HIP_TRY(hipEventRecord(marks[0], st));
+            HIP_TRY(cosdev::launch_level_table(ix->eng, w->q_codes, w->q_mags, w->qsums, w->qdig, B, L.tcodes, L.tmags, L.tcsums, ix->row_stride, plan.table_cols,
+                                               w->tab, L.tab_stride, ix->n_cus, st, w->tab_queue, wgs, first, plan.table_waits_for_sort));
+            if (timed) HIP_TRY(hipEventRecord(marks[1], st));
+            return COS_OK;
+        };
+        if (cosdev::level_table_gemm_queue(ix->eng, ix->row_stride)) HIP_TRY(hipMemsetAsync(w->tab_queue, 0, sizeof(u32), st)); // (the tile GEMM has no queue)
+        if (plan.table_early_wgs) {
+            if (int32_t rc = table_part(&cos_index::chain_upper_ev, w->upper_done, ev + 4, plan.table_early_wgs, true)) return rc;
+            if (int32_t rc = table_part(&cos_index::chain_ev, w->walk_done, ev + 8, 0u, false)) return rc;
+        } else if (int32_t rc = table_part(&cos_index::chain_last_range_ev, w->last_range, ev + 4, 0u, true))
+            return rc;
     }
     if (timed) HIP_TRY(hipEventRecord(ev[1], st));
     wa.qcodes = w->q_codes;
@@ -1152,6 +1173,7 @@ static int32_t run_search(cos_index *ix, Workspace *w, const SearchLaunch &L, co
     // XCDs.  Same walks, same results.
     auto walk = [&](hipStream_t s) -> int32_t {
         if (!ordered) {
+            if (chained) HIP_TRY(hipEventRecord(w->upper_done, s));
             if (chained) HIP_TRY(hipEventRecord(w->last_range, s));
             HIP_TRY(launch_walk(ix->eng, dev, wa, plan.kernel, s));
             return COS_OK;
@@ -1170,6 +1192,7 @@ static int32_t run_search(cos_index *ix, Workspace *w, const SearchLaunch &L, co
             if (last && chained) HIP_TRY(hipEventRecord(w->last_range, s));
             HIP_TRY(launch_walk(ix->eng, dev, wa, plan.kernel, s));
             if (last) break;
+            if (chained && i == 0) HIP_TRY(hipEventRecord(w->upper_done, s));
             if (timed && i == 0) HIP_TRY(hipEventRecord(ev[6], s));
             HIP_TRY(cosdev::launch_walk_order(w->order, B, L.key_n[i], ix->num_xcd, s));
             if (timed && i == 0) HIP_TRY(hipEventRecord(ev[7], s));
@@ -1186,6 +1209,7 @@ static int32_t run_search(cos_index *ix, Workspace *w, const SearchLaunch &L, co
         HIP_TRY(hipEventRecord(w->walk_done, sw));
         ix->chain_ev = w->walk_done;
         ix->chain_last_range_ev = w->last_range;
+        ix->chain_upper_ev = w->upper_done;
     } else {
         if (timed && sw != st) HIP_TRY(hipEventRecord(ev[1], sw));
         if (int32_t rc = walk(sw)) return rc;
@@ -1711,10 +1735,16 @@ extern "C" int32_t cos_index_last_walk_split(cos_index *ix, void *stream, cos_wa
     out->table_level_min = plan.table_level_min; // of THAT launch (the handle's may have moved on with ef_search)
     out->table_cols = plan.table_cols;
     out->cut_after_level = plan.cut_after_level;
+    out->table_early_wgs = plan.use_table ? plan.table_early_wgs : 0u;
     if (w->timed && w->ev_count) {
         hipEvent_t *ev = &w->ev[(size_t)((w->ev_count - 1) % Workspace::EV_RING) * Workspace::EV_PER];
         HIP_TRY(hipEventSynchronize(ev[3]));
         if (plan.use_table) HIP_TRY(hipEventElapsedTime(&out->table_ms, ev[4], ev[5]));
+        if (plan.use_table && plan.table_early_wgs) { // two parts, one after the other on one stream: the sum of their execution times, without the wait between them
+            float late_ms = 0.f;
+            HIP_TRY(hipEventElapsedTime(&late_ms, ev[8], ev[9]));
+            out->table_ms += late_ms;
+        }
         if (plan.ordered) {
             HIP_TRY(hipEventElapsedTime(&out->upper_ms, ev[1], ev[6]));
             HIP_TRY(hipEventElapsedTime(&out->sort_ms, ev[6], ev[7]));

@@ -32,7 +32,7 @@ hipError_t launch_fill_adj_mag(const u32 *adj_vec, const float *mags, float *adj
 hipError_t launch_link_round(const LinkArgs &a, u32 maxM, const u32 *pend, const u32 *pcount, u32 *next, u32 *next_count, u32 *evq, u32 *evq_count,
                              u32 count_ub, u32 round, hipStream_t st);
 hipError_t launch_quantize_rows(int eng, const float *x, u64 x_stride, u32 n, u32 dim, float lo, float hi, uint8_t *codes,
-                                u64 row_stride, float *mags, float *raw_mags, hipStream_t st);
+                                u64 row_stride, float *mags, float *raw_mags, hipStream_t st, u32 *code_sums = nullptr); // code_sums: [n] sums of the code bytes (u8 only)
 hipError_t launch_walk(int eng, const IndexDev &ix, const WalkArgs &wa, WalkKernel kernel, hipStream_t st); // `kernel`: WalkPlan::kernel (walk_plan.h)
 static_assert(WALK_PLAN_MAX_LEVELS == MAX_LEVELS && WALK_PLAN_ENG_U8 == ENG_U8 && WALK_PLAN_ENG_Q2 == ENG_Q2 && WALK_PLAN_FAST_MAX_EF == WALK_FAST_MAX_EF &&
               COS_STORAGE_U8 == 0u && COS_VISITED_REF == 0u, "walk_plan.h restates these");
@@ -57,8 +57,9 @@ hipError_t launch_walk_order(WalkOrder &o, u32 B, u32 key_max, u32 num_xcd, hipS
 hipError_t launch_level_table_gather(const uint8_t *codes, const float *mags, u64 row_stride, const u32 *node_vec, u32 n, u32 col0,
                                      uint8_t *tcodes, float *tmags, hipStream_t st);
 hipError_t launch_code_sums(const uint8_t *codes, u64 row_stride, u32 n, u32 *sums, hipStream_t st);
-hipError_t launch_level_table(int eng, const uint8_t *qcodes, const float *qmags, u32 *qsums, uint8_t *qdig, u32 B, const uint8_t *tcodes, const float *tmags,
-                              const u32 *tcsums, u64 row_stride, u32 ncols, float *tab, u64 tab_stride, u32 n_cus, hipStream_t st);
+hipError_t launch_level_table(int eng, const uint8_t *qcodes, const float *qmags, const u32 *qsums, uint8_t *qdig, u32 B, const uint8_t *tcodes, const float *tmags,
+                              const u32 *tcsums, u64 row_stride, u32 ncols, float *tab, u64 tab_stride, u32 n_cus, hipStream_t st, u32 *queue, u32 wgs, bool first, bool shared);
+bool level_table_gemm_queue(int eng, u64 row_stride);   // the table comes from the query-resident GEMM (work items claimed from a queue)
 bool level_table_eng_supported(int eng, u64 row_stride); // storages the level table exists for (kernels_flat.hip)
 int32_t quantize_ref_layout(uint32_t storage, uint32_t res, uint32_t dim, const float *x, uint32_t n, void *codes, float *mags);
 int32_t distance_ref_layout(uint32_t metric, uint32_t storage, uint32_t res, uint32_t dim, const void *x_codes, const float *x_mags, uint32_t nx,
@@ -132,7 +133,8 @@ struct Workspace {
     DevArr<u64> stats;          // [B][4]
     DevArr<u64> stats2;         // [B][4] WalkArgs::out_stats2
     DevArr<float> tab;          // level table of this workspace's big launches [capB][tab_stride] (WalkArgs::tab), grown on demand
-    DevArr<u32> qsums;          // [capB] code sums of the queries (the table GEMM's recentring term)
+    DevArr<u32> qsums;          // [capB] code sums of the queries (the table GEMM's recentring term; written by quantize_rows_kernel)
+    DevArr<u32> tab_queue;      // [1] next work item of the table GEMM in flight (level_table_areg), zeroed before its first part
     DevArr<uint8_t> qdig;       // [capB][dims] quaternary codes: the queries' i8 digit rows (the table GEMM's resident operand)
     DevArr<u32> fin_flags;      // [capB + 1] finalize_fast_kernel -> finalize_list_kernel hand-over: count, then the queries (kernels_walk.hip)
     DevArr<u64> rerank_rows;    // [B]
@@ -149,13 +151,16 @@ struct Workspace {
     // timing: a ring of event quadruples (before prep | after prep | after walk | after finalize), one per launch, so a
     // run of launches can be summarised afterwards without synchronising between them (cos_index_timing_summary)
     // + the inner marks of a big launch's walk: [4] before / [5] after the level-table GEMM (caller's stream), [6] after the upper
-    // level range, [7] after the order sort (walk stream); last_plan says which of them the last launch recorded
+    // level range, [7] after the order sort (walk stream), [8] before / [9] after the GEMM's late part (WalkPlan::table_early_wgs: then
+    // [4] / [5] bracket the early part; both on the caller's stream, the waits in front of either part outside the brackets); last_plan
+    // says which of them the last launch recorded
     static constexpr u32 EV_RING = 128;
-    static constexpr u32 EV_PER = 8;
+    static constexpr u32 EV_PER = 10;
     std::vector<hipEvent_t> ev; // [EV_RING][EV_PER]
     u32 ev_count = 0;           // timed launches since timing was switched on (ring position = ev_count % EV_RING)
     hipEvent_t walk_done = nullptr; // recorded after this workspace's walk kernel (walk chain, see cos_index::chain_*)
     hipEvent_t last_range = nullptr; // recorded when this workspace's walk reaches its LAST level range (after the order sort; an unsplit walk: its start)
+    hipEvent_t upper_done = nullptr; // recorded when this workspace's walk has finished its FIRST level range (before the order sort; an unsplit walk: its start)
     hipStream_t walk_stream = nullptr; // low-priority stream big walks run on (cos_index::walk_side_min_B), created on first use
     hipEvent_t prep_done = nullptr, walk_fin = nullptr; // caller's stream -> walk stream -> finalize stream
     u32 lastB = 0;
@@ -164,7 +169,7 @@ struct Workspace {
     Workspace() = default;
     Workspace(const Workspace &) = delete;
     ~Workspace() { // (the caller has drained the device: cos_index_destroy)
-        for (hipEvent_t e : {walk_done, walk_fin, last_range, prep_done}) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : {walk_done, walk_fin, last_range, upper_done, prep_done}) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
         if (walk_stream) (void)hipStreamDestroy(walk_stream);
     }
@@ -249,6 +254,9 @@ struct cos_index {
     // GEMM's 450-register waves hold every SIMD: the chip ran the GEMM alone for 3 ms per step and the lower range waited
     // (profiles/r06_step_timeline_before.txt).  Behind this event the GEMM shares the chip with the HBM-bound lower range instead.
     hipEvent_t chain_last_range_ev = nullptr;
+    // ... and its upper_done (round 7): between the upper range and the order sort the chip is empty for ~60 us.  The EARLY part of the
+    // next launch's GEMM (WalkPlan::table_early_wgs workgroups; 0 by default) waits for this event, the LATE part for chain_ev (walk_plan.h).
+    hipEvent_t chain_upper_ev = nullptr;
     // (Round 5 also chained the two level ranges of a split walk separately, so that the upper range of launch i+1 — table levels,
     // instruction issue — co-ran with the lower range of launch i — HBM.  Measured: 7.08 against 7.12 ms per step at ef 64, 17.34
     // against 17.27 at ef 256 (profiles/r05_phase_chain_probe.jsonl): both ranges are limited by the queries in flight, and two

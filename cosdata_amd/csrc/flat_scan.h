@@ -59,9 +59,10 @@ hipError_t launch_flat_rerank_wide(u32 R, bool brute, const float *Q, u64 q_stri
                                    const float *xmags, u32 dim, const u64 *d_pool, u32 ncand_max, u32 k, u32 id_base, u32 *out_ids, float *out_scores,
                                    u32 *out_counts, hipStream_t st);
 
-// the walk's level table as a query-resident GEMM (kernels_scan.hip): tab[q][c] = (f32) exact integer dot; u8 or quaternary codes
+// the walk's level table as a query-resident GEMM (kernels_scan.hip): tab[q][c] = (f32) exact integer dot; u8 or quaternary codes.
+// Its workgroups claim work items from *queue (zeroed before the first launch over it); wgs = workgroups of this launch, 0 = full width
 bool level_table_areg_supported(int eng, u64 row_stride);
 hipError_t launch_level_table_areg(int eng, u32 n_cus, hipStream_t st, const uint8_t *qcodes, const u32 *qsums, u32 B, const uint8_t *tcodes,
-                                   const u32 *tcsums, u64 row_stride, u32 ncols, float *tab, u64 tab_stride);
+                                   const u32 *tcsums, u64 row_stride, u32 ncols, float *tab, u64 tab_stride, u32 *queue, u32 wgs, bool shared);
 
 } // namespace cosdev

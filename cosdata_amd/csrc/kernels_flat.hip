@@ -997,33 +997,37 @@ bool level_table_eng_supported(int eng, u64 row_stride) {
 // for the entries it reads (walk_kernel.inc, table levels): the GEMM's epilogue is an add, a convert and a store.  The
 // query-resident kernel (kernels_scan.hip level_table_areg) wherever the code rows are whole 64-byte chunks with an
 // instantiation (768, 1024, ...), the 256 x 128 tile kernel otherwise (and with tuning knob walk_table_gemm = 0); same table.
-hipError_t launch_level_table(int eng, const uint8_t *qcodes, const float *qmags, u32 *qsums /*[B] scratch (u8)*/, uint8_t *qdig /*[B][dims] scratch (quaternary)*/,
+// qsums: the queries' code sums (u8; quantize_rows_kernel leaves them beside the codes).  The query-resident kernel's workgroups claim
+// their work from *queue, which the caller zeroes before the FIRST launch over a table; a table may be computed by several launches of
+// `wgs` workgroups each (0 = the full width), one after the other on `st`; `first` = this is the first of them (it prepares the
+// quaternary query operand).  shared: the size of the work items (walk_plan.h table_gemm_stripe_tiles).
+bool level_table_gemm_queue(int eng, u64 row_stride) { return level_table_areg_supported(eng, row_stride) && tune_or(TUNE_WALK_TABLE_GEMM, 1) != 0; }
+hipError_t launch_level_table(int eng, const uint8_t *qcodes, const float *qmags, const u32 *qsums /*[B] (u8)*/, uint8_t *qdig /*[B][dims] scratch (quaternary)*/,
                               u32 B, const uint8_t *tcodes, const float *tmags, const u32 *tcsums, u64 row_stride, u32 ncols, float *tab, u64 tab_stride,
-                              u32 n_cus, hipStream_t st) {
+                              u32 n_cus, hipStream_t st, u32 *queue, u32 wgs, bool first, bool shared) {
     if (B == 0 || ncols == 0) return hipSuccess;
     const bool q2 = eng == ENG_Q2;
     const u32 kdims = q2 ? (u32)(row_stride / 16) * 64 : (u32)((row_stride + 63) / 64 * 64);
     hipError_t e = hipSuccess;
-    if (!q2) e = launch_code_sums(qcodes, row_stride, B, qsums, st);
-    if (e != hipSuccess) return e;
-    if (level_table_areg_supported(eng, row_stride) && tune_or(TUNE_WALK_TABLE_GEMM, 1) != 0) {
-        if (q2) { // the queries' planes -> the permuted i8 digit rows the kernel keeps resident
+    if (level_table_gemm_queue(eng, row_stride)) {
+        if (q2 && first) { // the queries' planes -> the permuted i8 digit rows the kernel keeps resident
             e = launch_flat_scan_expand_queries(qcodes, row_stride, B, kdims, qdig, st, false);
             if (e != hipSuccess) return e;
         }
         // (one workgroup per CU; on half the CUs — so that the previous launch's walk keeps the other half — the GEMM takes 1.31 instead
         // of 0.85 ms and the step 6.57 instead of 6.49: profiles/r05_table_gemm_half_the_cus_probe_not_kept.jsonl)
-        return launch_level_table_areg(eng, n_cus ? n_cus : 256u, st, q2 ? qdig : qcodes, (const u32 *)qsums, B, tcodes, tcsums, row_stride, ncols, tab, tab_stride);
+        return launch_level_table_areg(eng, n_cus ? n_cus : 256u, st, q2 ? qdig : qcodes, qsums, B, tcodes, tcsums, row_stride, ncols, tab, tab_stride, queue, wgs, shared);
     }
+    if (!first) return hipSuccess; // (the tile kernel has no queue: one launch computes the table)
     const u32 metric = 1u; // the tile kernel's unfused epilogue with the dot-product metric: the converted integer dot, no quotient
     dim3 grid((ncols + CN - 1) / CN, (B + CM - 1) / CM);
     FusedOut fo{nullptr, nullptr, nullptr, 0u, nullptr};
     // two k panels in flight (one and three were measured slower in round 4)
     if (q2)
-        hipLaunchKernelGGL((flat_codes_gemm_i8<ENG_Q2, false, 2>), grid, dim3(512), 0, st, qcodes, qmags, (const u32 *)qsums, B, tcodes, tmags, tcsums, row_stride, 0u,
+        hipLaunchKernelGGL((flat_codes_gemm_i8<ENG_Q2, false, 2>), grid, dim3(512), 0, st, qcodes, qmags, qsums, B, tcodes, tmags, tcsums, row_stride, 0u,
                            ncols, kdims, metric, tab, tab_stride, fo);
     else
-        hipLaunchKernelGGL((flat_codes_gemm_i8<ENG_U8, false, 2>), grid, dim3(512), 0, st, qcodes, qmags, (const u32 *)qsums, B, tcodes, tmags, tcsums, row_stride, 0u,
+        hipLaunchKernelGGL((flat_codes_gemm_i8<ENG_U8, false, 2>), grid, dim3(512), 0, st, qcodes, qmags, qsums, B, tcodes, tmags, tcsums, row_stride, 0u,
                            ncols, kdims, metric, tab, tab_stride, fo);
     return hipGetLastError();
 }

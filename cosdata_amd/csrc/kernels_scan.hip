@@ -9,6 +9,7 @@
 #include "device_common.h"
 #include "flat_scan.h"
 #include "tuning.h"
+#include "walk_plan.h"
 
 using namespace cosdev;
 
@@ -750,7 +751,14 @@ __global__ __launch_bounds__(512) void flat_scan_q2_fp4_w8(const uint8_t *__rest
 //     128 (sum q + sum c) - 16384 K back (kernels_flat.hip: the same correction);
 //   * what bounds it is the table itself: B x cols x 4 bytes written once (2.7 GB per 32 768 queries at c2) against 1.05 TOP —
 //     13 TB/s of output at the i8 peak — so this is an HBM WRITE stream with the MFMA at ~40 % duty, and is reported as such.
-// One workgroup per CU, persistent over its column tiles; the grid is (column groups, query groups of 256).
+// One workgroup per CU, persistent.  Round 7: the workgroups claim WORK ITEMS — (row group of 256 queries, stripe of `stripe` column
+// tiles; walk_plan.h table_gemm_stripe_tiles) — from one counter with an atomicAdd (one lane claims, the value reaches the other waves
+// through LDS) and leave when the counter has passed the item count.  Nobody waits for anybody, so one table can be shared by several
+// launches over the same counter (engine.hip: a few early workgroups under the previous walk, the full width after it), and an item's
+// output does not depend on who computed it.  Item i = stripe i / row_groups of row group i % row_groups: workgroups that claim at
+// about the same time read the same stripes of the table operand (as the fixed grid did).  A workgroup keeps its row group from one
+// claim to the next only while the claims stay in step (and the row groups divide the grid); in general every item reloads the A
+// fragments and the recentring terms — 256 x K bytes from L2 against `stripe` tiles of MFMAs, which is what bounds the stripe from below.
 // ------------------------------------------------------------------------------------------------
 // Q2 = quaternary codes (round 5: the c3 walk's table): the operands are the i8 digits of the exhaustive scan above — queries
 // pre-expanded once per launch (expand_q2_digits_perm_kernel), table columns expanded planes -> digits while they are staged —
@@ -759,35 +767,36 @@ template <int KC, bool Q2>
 __global__ __launch_bounds__(256) void level_table_areg(const uint8_t *__restrict__ qcodes /* u8: [B][64 KC] codes; Q2: [B][64 KC] permuted digits */,
                                                         const u32 *__restrict__ qsums, u32 B, const uint8_t *__restrict__ tcodes,
                                                         const u32 *__restrict__ tcsums, u64 row_stride /* u8: 64 KC; Q2: 16 KC */, u32 ncols,
-                                                        float *__restrict__ tab, u64 tab_stride) {
+                                                        float *__restrict__ tab, u64 tab_stride, u32 *__restrict__ queue, u32 stripe) {
     constexpr int K = KC * 64, KS = KC * 2, LDB = K + 16;
     constexpr int PC = Q2 ? KC : K / 16;           // 16-byte RAW pieces per column (Q2: one per 64 dims, expanded to four in LDS)
     constexpr int NP = (64 * PC + 255) / 256;      // raw pieces a thread stages per tile
     extern __shared__ __attribute__((aligned(16))) unsigned char areg_lds[]; // [2][64][LDB]
+    __shared__ u32 s_item;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, half = lane >> 5, l31 = lane & 31;
-    const u32 row0 = blockIdx.y * 256 + w * 64;
-    const u32 n_tiles = (ncols + 63) / 64, G = gridDim.x;
-    u32 t = blockIdx.x;
-    if (t >= n_tiles) return; // uniform
-    // resident query fragments (u8: recentred); rows past B are zero (their outputs are never stored)
+    const u32 n_tiles = (ncols + 63) / 64, row_groups = (B + 255) / 256, n_items = (n_tiles + stripe - 1) / stripe * row_groups;
+    u32 row0 = 0, rg_now = 0xFFFFFFFFu, t = 0, t_end = 0;
+    // resident query fragments (u8: recentred) of the current row group; rows past B are zero (their outputs are never stored)
     i32x4 a[2][KS];
-    static_for<0, 2 * KS>([&](auto Ic) __attribute__((always_inline)) {
-        constexpr int i = decltype(Ic)::value / KS, s = decltype(Ic)::value % KS;
-        const u32 row = row0 + 32 * i + l31;
-        i32x4 v = *(const i32x4 *)(qcodes + (u64)(row < B ? row : B - 1) * K + 32 * s + 16 * half);
-        if constexpr (!Q2) v = v ^ (int)0x80808080;
-        a[i][s] = row < B ? v : i32x4{0, 0, 0, 0};
-        asm volatile("" : "+a"(a[i][s])); // the value now IS an AccVGPR tuple: its MFMA uses need no copies
-    });
     // u8: per-row share of the recentring, 128 * sum(q) - 16384 * K, for this lane's 32 accumulator rows
     int rqs[2][16];
+    auto load_rows = [&]() __attribute__((always_inline)) {
+        static_for<0, 2 * KS>([&](auto Ic) __attribute__((always_inline)) {
+            constexpr int i = decltype(Ic)::value / KS, s = decltype(Ic)::value % KS;
+            const u32 row = row0 + 32 * i + l31;
+            i32x4 v = *(const i32x4 *)(qcodes + (u64)(row < B ? row : B - 1) * K + 32 * s + 16 * half);
+            if constexpr (!Q2) v = v ^ (int)0x80808080;
+            a[i][s] = row < B ? v : i32x4{0, 0, 0, 0};
+            asm volatile("" : "+a"(a[i][s])); // the value now IS an AccVGPR tuple: its MFMA uses need no copies
+        });
 #pragma unroll
-    for (int i = 0; i < 2; i++)
+        for (int i = 0; i < 2; i++)
 #pragma unroll
-        for (int r = 0; r < 16; r++) {
-            const u32 row = row0 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * half;
-            rqs[i][r] = Q2 ? 0 : 128 * (int)qsums[row < B ? row : B - 1] - 16384 * K;
-        }
+            for (int r = 0; r < 16; r++) {
+                const u32 row = row0 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * half;
+                rqs[i][r] = Q2 ? 0 : 128 * (int)qsums[row < B ? row : B - 1] - 16384 * K;
+            }
+    };
     // staging: raw piece g = p * 256 + tid of the tile's 64 * PC pieces is bytes [16 (g % PC), +16) of column g / PC — consecutive
     // threads read consecutive 16 B of one code row (coalesced); columns past ncols re-read the last one (never stored)
     uint4 raw[NP];
@@ -815,65 +824,81 @@ __global__ __launch_bounds__(256) void level_table_areg(const uint8_t *__restric
             }
         }
     };
-    load_tile(t);
-    store_tile(0);
-    __syncthreads();
-    int P = 0;
     while (true) {
-        const bool more = t + G < n_tiles; // uniform
-        if (more) load_tile(t + G);       // in flight while this tile is multiplied
-        const unsigned char *bt = areg_lds + (size_t)P * 64 * LDB + l31 * LDB + 16 * half;
-        i32x16 acc[2][2];
-        i32x4 bf[3][2]; // column fragments, read two k steps ahead of their MFMAs
-#pragma unroll
-        for (int s = 0; s < 2 && s < KS; s++) {
-            bf[s][0] = *(const i32x4 *)(bt + 32 * s);
-            bf[s][1] = *(const i32x4 *)(bt + 32 * LDB + 32 * s);
+        // claim the next item (the first barrier: every wave is done with the previous item's tile buffers and has read s_item)
+        __syncthreads();
+        if (tid == 0) s_item = atomicAdd(queue, 1u);
+        __syncthreads();
+        const u32 item = s_item;
+        if (item >= n_items) break; // uniform
+        const u32 rg = item % row_groups;
+        t = item / row_groups * stripe;
+        t_end = min(n_tiles, t + stripe);
+        if (rg != rg_now) { // uniform
+            rg_now = rg;
+            row0 = rg * 256 + w * 64;
+            load_rows();
         }
-        static_for<0, KS>([&](auto Sc) __attribute__((always_inline)) {
-            constexpr int s = decltype(Sc)::value;
-            if (s + 2 < KS) { // (pinned: left alone the scheduler sinks each read to just before its MFMAs and exposes the LDS latency)
-                bf[(s + 2) % 3][0] = *(const i32x4 *)(bt + 32 * (s + 2));
-                bf[(s + 2) % 3][1] = *(const i32x4 *)(bt + 32 * LDB + 32 * (s + 2));
+        load_tile(t);
+        store_tile(0);
+        __syncthreads();
+        int P = 0;
+        while (true) {
+            const bool more = t + 1 < t_end; // uniform
+            if (more) load_tile(t + 1);       // in flight while this tile is multiplied
+            const unsigned char *bt = areg_lds + (size_t)P * 64 * LDB + l31 * LDB + 16 * half;
+            i32x16 acc[2][2];
+            i32x4 bf[3][2]; // column fragments, read two k steps ahead of their MFMAs
+#pragma unroll
+            for (int s = 0; s < 2 && s < KS; s++) {
+                bf[s][0] = *(const i32x4 *)(bt + 32 * s);
+                bf[s][1] = *(const i32x4 *)(bt + 32 * LDB + 32 * s);
             }
-            __builtin_amdgcn_sched_barrier(0);
-            const i32x4 b0 = bf[s % 3][0], b1 = bf[s % 3][1];
-            areg_mfma<s == 0>(acc[0][0], a[0][s], b0);
-            areg_mfma<s == 0>(acc[0][1], a[0][s], b1);
-            areg_mfma<s == 0>(acc[1][0], a[1][s], b0);
-            areg_mfma<s == 0>(acc[1][1], a[1][s], b1);
-            __builtin_amdgcn_sched_barrier(0);
-        });
-        // epilogue: exact u32 dot -> f32 (RNE), 2 rows x 32 columns (two full 128-byte lines) per store instruction; a tile inside
-        // the matrix (all but the last row group / column tile) stores without predication
-        auto epilogue = [&](auto fullc) __attribute__((always_inline)) {
-            constexpr bool FULL = decltype(fullc)::value;
+            static_for<0, KS>([&](auto Sc) __attribute__((always_inline)) {
+                constexpr int s = decltype(Sc)::value;
+                if (s + 2 < KS) { // (pinned: left alone the scheduler sinks each read to just before its MFMAs and exposes the LDS latency)
+                    bf[(s + 2) % 3][0] = *(const i32x4 *)(bt + 32 * (s + 2));
+                    bf[(s + 2) % 3][1] = *(const i32x4 *)(bt + 32 * LDB + 32 * (s + 2));
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                const i32x4 b0 = bf[s % 3][0], b1 = bf[s % 3][1];
+                areg_mfma<s == 0>(acc[0][0], a[0][s], b0);
+                areg_mfma<s == 0>(acc[0][1], a[0][s], b1);
+                areg_mfma<s == 0>(acc[1][0], a[1][s], b0);
+                areg_mfma<s == 0>(acc[1][1], a[1][s], b1);
+                __builtin_amdgcn_sched_barrier(0);
+            });
+            // epilogue: exact u32 dot -> f32 (RNE), 2 rows x 32 columns (two full 128-byte lines) per store instruction; a tile inside
+            // the matrix (all but the last row group / column tile) stores without predication
+            auto epilogue = [&](auto fullc) __attribute__((always_inline)) {
+                constexpr bool FULL = decltype(fullc)::value;
 #pragma unroll
-            for (int j = 0; j < 2; j++) {
-                const u32 col = t * 64 + 32 * j + l31;
-                const bool cv = FULL || col < ncols;
-                int cs = 0;
-                if constexpr (!Q2) cs = 128 * (int)tcsums[cv ? col : ncols - 1];
+                for (int j = 0; j < 2; j++) {
+                    const u32 col = t * 64 + 32 * j + l31;
+                    const bool cv = FULL || col < ncols;
+                    int cs = 0;
+                    if constexpr (!Q2) cs = 128 * (int)tcsums[cv ? col : ncols - 1];
 #pragma unroll
-                for (int i = 0; i < 2; i++) {
-                    const u32 rbase = row0 + 32 * i + 4 * half;
-                    float *out = tab + (u64)rbase * tab_stride + col;
+                    for (int i = 0; i < 2; i++) {
+                        const u32 rbase = row0 + 32 * i + 4 * half;
+                        float *out = tab + (u64)rbase * tab_stride + col;
 #pragma unroll
-                    for (int r = 0; r < 16; r++) {
-                        const u32 dr = (r & 3) + 8 * (r >> 2);
-                        const u32 dot = (u32)(acc[i][j][r] + rqs[i][r] + cs);
-                        if (FULL || (cv && rbase + dr < B)) out[(u64)dr * tab_stride] = (float)dot;
+                        for (int r = 0; r < 16; r++) {
+                            const u32 dr = (r & 3) + 8 * (r >> 2);
+                            const u32 dot = (u32)(acc[i][j][r] + rqs[i][r] + cs);
+                            if (FULL || (cv && rbase + dr < B)) out[(u64)dr * tab_stride] = (float)dot;
+                        }
                     }
                 }
-            }
-        };
-        if (row0 + 64 <= B && t * 64 + 64 <= ncols) epilogue(std::true_type{}); // wave-uniform
-        else epilogue(std::false_type{});
-        if (!more) break;
-        store_tile(P ^ 1); // the other buffer: every wave finished reading it before the last barrier
-        __syncthreads();
-        P ^= 1;
-        t += G;
+            };
+            if (row0 + 64 <= B && t * 64 + 64 <= ncols) epilogue(std::true_type{}); // wave-uniform
+            else epilogue(std::false_type{});
+            if (!more) break;
+            store_tile(P ^ 1); // the other buffer: every wave finished reading it before the last barrier
+            __syncthreads();
+            P ^= 1;
+            t += 1;
+        }
     }
 }
 
@@ -1122,27 +1147,28 @@ bool level_table_areg_supported(int eng, u64 row_stride) {
     return false;
 }
 template <int KC, bool Q2>
-static hipError_t launch_table_kc(dim3 grid, hipStream_t st, const uint8_t *qcodes, const u32 *qsums, u32 B, const uint8_t *tcodes, const u32 *tcsums,
-                                  u64 row_stride, u32 ncols, float *tab, u64 tab_stride) {
+static hipError_t launch_table_kc(u32 wgs, hipStream_t st, const uint8_t *qcodes, const u32 *qsums, u32 B, const uint8_t *tcodes, const u32 *tcsums,
+                                  u64 row_stride, u32 ncols, float *tab, u64 tab_stride, u32 *queue, u32 stripe) {
     const size_t lds = (size_t)2 * 64 * (KC * 64 + 16);
     hipError_t e = hipFuncSetAttribute((const void *)level_table_areg<KC, Q2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((level_table_areg<KC, Q2>), grid, dim3(256), lds, st, qcodes, qsums, B, tcodes, tcsums, row_stride, ncols, tab, tab_stride);
+    hipLaunchKernelGGL((level_table_areg<KC, Q2>), dim3(wgs), dim3(256), lds, st, qcodes, qsums, B, tcodes, tcsums, row_stride, ncols, tab, tab_stride, queue, stripe);
     return hipGetLastError();
 }
-// tab[q][c] = (f32) integer dot of query q with table column c; grid = (column groups, query groups of 256), about one workgroup per CU.
-// u8: qcodes = the queries' code rows, qsums / tcsums = code sums.  Q2: qcodes = the queries' permuted digit rows
+// tab[q][c] = (f32) integer dot of query q with table column c, as work items claimed from *queue (zeroed by the caller before the
+// first launch over it; walk_plan.h table_gemm_items: shared = fine items, for a queue that several launches may share or whose
+// workgroups are placed one by one; else one item per full-width workgroup).  wgs = workgroups of this launch, 0 = the full width:
+// one per CU, at most one per item.  u8: qcodes = the queries' code rows, qsums / tcsums = code sums.  Q2: qcodes = the queries' permuted digit rows
 // (launch_flat_scan_expand_queries, fp4 = false), qsums / tcsums unused.
 hipError_t launch_level_table_areg(int eng, u32 n_cus, hipStream_t st, const uint8_t *qcodes, const u32 *qsums, u32 B, const uint8_t *tcodes, const u32 *tcsums,
-                                   u64 row_stride, u32 ncols, float *tab, u64 tab_stride) {
-    const u32 n_tiles = (ncols + 63) / 64, row_groups = (B + 255) / 256;
-    const u32 G = std::max(1u, std::min(n_tiles, n_cus / std::max(1u, std::min(row_groups, n_cus))));
-    dim3 grid(G, row_groups);
+                                   u64 row_stride, u32 ncols, float *tab, u64 tab_stride, u32 *queue, u32 wgs, bool shared) {
+    const u32 stripe = table_gemm_stripe_tiles(B, ncols, n_cus, shared), n_items = table_gemm_items(B, ncols, n_cus, shared);
+    wgs = std::max(1u, std::min(n_items, wgs ? wgs : std::max(1u, n_cus)));
     const u32 kc = eng == ENG_Q2 ? (u32)(row_stride / 16) : (u32)(row_stride / 64);
-#define TAB_CASE(KC)                                                                                                                          \
-    case KC:                                                                                                                                  \
-        return eng == ENG_Q2 ? launch_table_kc<KC, true>(grid, st, qcodes, qsums, B, tcodes, tcsums, row_stride, ncols, tab, tab_stride)     \
-                             : launch_table_kc<KC, false>(grid, st, qcodes, qsums, B, tcodes, tcsums, row_stride, ncols, tab, tab_stride)
+#define TAB_CASE(KC)                                                                                                                                  \
+    case KC:                                                                                                                                          \
+        return eng == ENG_Q2 ? launch_table_kc<KC, true>(wgs, st, qcodes, qsums, B, tcodes, tcsums, row_stride, ncols, tab, tab_stride, queue, stripe) \
+                             : launch_table_kc<KC, false>(wgs, st, qcodes, qsums, B, tcodes, tcsums, row_stride, ncols, tab, tab_stride, queue, stripe)
     switch (kc) {
         TAB_CASE(2); TAB_CASE(4); TAB_CASE(6); TAB_CASE(8); TAB_CASE(12); TAB_CASE(16);
         default: return hipErrorInvalidValue;

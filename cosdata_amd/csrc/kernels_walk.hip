@@ -33,7 +33,7 @@ namespace {
 template <int ENG>
 __global__ __launch_bounds__(256) void quantize_rows_kernel(const float *__restrict__ x, u64 x_stride, u32 n, u32 dim, float lo,
                                                             float hi, uint8_t *__restrict__ codes, u64 row_stride,
-                                                            float *__restrict__ mags, float *__restrict__ raw_mags) {
+                                                            float *__restrict__ mags, float *__restrict__ raw_mags, u32 *__restrict__ code_sums) {
     const int lane = threadIdx.x & 63;
     const u32 row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (row >= n) return;
@@ -44,7 +44,7 @@ __global__ __launch_bounds__(256) void quantize_rows_kernel(const float *__restr
     if (need_seq) rn = seq_norm_wave(xr, dim, lane); // wave-uniform branch; every lane gets the value
     if (raw_mags && lane == 0) raw_mags[row] = rn;
     if constexpr (ENG == ENG_U8) {
-        u32 ss = 0;
+        u32 ss = 0, sum = 0; // (sum: the level-table GEMM's recentring term of a query, engine.hip run_search)
         for (u32 i = lane; i < (u32)row_stride; i += 64) {
             uint8_t q = 0;
             if (i < dim) {
@@ -54,10 +54,16 @@ __global__ __launch_bounds__(256) void quantize_rows_kernel(const float *__restr
             }
             cr[i] = q;
             ss += (u32)q * (u32)q;
+            sum += (u32)q;
         }
 #pragma unroll
         for (int m = 32; m > 0; m >>= 1) ss += (u32)__shfl_xor((int)ss, m, 64);
         if (lane == 0) mags[row] = sqrtf((float)ss); // (sum::<u32>() as f32).sqrt()
+        if (code_sums) { // wave-uniform
+#pragma unroll
+            for (int m = 32; m > 0; m >>= 1) sum += (u32)__shfl_xor((int)sum, m, 64);
+            if (lane == 0) code_sums[row] = sum;
+        }
     } else if constexpr (ENG == ENG_Q2) {
         const u32 nch = (u32)(row_stride / 16);
         for (u32 c = 0; c < nch; c++) {
@@ -519,16 +525,16 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(NWV ==
 namespace cosdev {
 
 hipError_t launch_quantize_rows(int eng, const float *x, u64 x_stride, u32 n, u32 dim, float lo, float hi, uint8_t *codes,
-                                u64 row_stride, float *mags, float *raw_mags, hipStream_t st) {
+                                u64 row_stride, float *mags, float *raw_mags, hipStream_t st, u32 *code_sums) {
     if (n == 0) return hipSuccess;
     dim3 block(256), grid((n + 3) / 4);
     switch (eng) {
-    case ENG_U8: hipLaunchKernelGGL(quantize_rows_kernel<ENG_U8>, grid, block, 0, st, x, x_stride, n, dim, lo, hi, codes, row_stride, mags, raw_mags); break;
-    case ENG_Q2: hipLaunchKernelGGL(quantize_rows_kernel<ENG_Q2>, grid, block, 0, st, x, x_stride, n, dim, lo, hi, codes, row_stride, mags, raw_mags); break;
-    case ENG_F32: hipLaunchKernelGGL(quantize_rows_kernel<ENG_F32>, grid, block, 0, st, x, x_stride, n, dim, lo, hi, codes, row_stride, mags, raw_mags); break;
-    case ENG_F16: hipLaunchKernelGGL(quantize_rows_kernel<ENG_F16>, grid, block, 0, st, x, x_stride, n, dim, lo, hi, codes, row_stride, mags, raw_mags); break;
-    case ENG_Q1: hipLaunchKernelGGL(quantize_rows_kernel<ENG_Q1>, grid, block, 0, st, x, x_stride, n, dim, lo, hi, codes, row_stride, mags, raw_mags); break;
-    case ENG_Q3: hipLaunchKernelGGL(quantize_rows_kernel<ENG_Q3>, grid, block, 0, st, x, x_stride, n, dim, lo, hi, codes, row_stride, mags, raw_mags); break;
+    case ENG_U8: hipLaunchKernelGGL(quantize_rows_kernel<ENG_U8>, grid, block, 0, st, x, x_stride, n, dim, lo, hi, codes, row_stride, mags, raw_mags, code_sums); break;
+    case ENG_Q2: hipLaunchKernelGGL(quantize_rows_kernel<ENG_Q2>, grid, block, 0, st, x, x_stride, n, dim, lo, hi, codes, row_stride, mags, raw_mags, code_sums); break;
+    case ENG_F32: hipLaunchKernelGGL(quantize_rows_kernel<ENG_F32>, grid, block, 0, st, x, x_stride, n, dim, lo, hi, codes, row_stride, mags, raw_mags, code_sums); break;
+    case ENG_F16: hipLaunchKernelGGL(quantize_rows_kernel<ENG_F16>, grid, block, 0, st, x, x_stride, n, dim, lo, hi, codes, row_stride, mags, raw_mags, code_sums); break;
+    case ENG_Q1: hipLaunchKernelGGL(quantize_rows_kernel<ENG_Q1>, grid, block, 0, st, x, x_stride, n, dim, lo, hi, codes, row_stride, mags, raw_mags, code_sums); break;
+    case ENG_Q3: hipLaunchKernelGGL(quantize_rows_kernel<ENG_Q3>, grid, block, 0, st, x, x_stride, n, dim, lo, hi, codes, row_stride, mags, raw_mags, code_sums); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -4,6 +4,20 @@
 // in WalkPlanIn, so the rules can be checked on a CPU (tests/cxx/walk_plan_check.cpp against tests/golden/walk_plan_cases.txt).
 // engine.hip plans in get_workspace (cos_walk_plan_in fills the inputs), prepares what the plan wants, settles it against what exists and
 // launches from it; builder.hip's walks take their kernel from the same function.
+//
+// The level-table GEMM of a chained big launch (round 7).  The query-resident GEMM (kernels_scan.hip level_table_areg) is a queue of
+// work items — (row group of 256 queries, stripe of column tiles), table_gemm_items() of them — that its workgroups claim from one
+// counter, so one table can be computed by several launches.  Where the GEMM is gated behind the previous chained walk
+// (table_waits_for_sort) and tuning knob walk_table_early_wgs is not 0, engine.hip issues it as TWO launches over one counter:
+//   * an EARLY part of WalkPlan::table_early_wgs workgroups that waits for the previous chained walk's END OF UPPER RANGE
+//     (cos_index::chain_upper_ev, recorded between the upper range and the order sort, when the chip is empty for ~60 us);
+//   * a LATE part, the full-width grid, that waits for the previous walk's completion (cos_index::chain_ev) and drains what is left of
+//     the queue — or reads one word per workgroup and leaves.
+// Both go out on the caller's stream, so the late part starts when the early one has left, and the early one leaves when the queue is
+// empty: the early part computes the whole table on its few CUs and the late part is an empty launch.  No setting of the knob beat the
+// single launch behind chain_last_range_ev on the 12.5M x 1024 shard, so table_early_wgs = 0 is the default; an arrangement in which
+// the late part works BESIDE the early one (the early part on a stream of its own) was measured too and is not in the tree
+// (profiles/r07_table_early_wgs_sweep.jsonl).
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -47,6 +61,10 @@ struct WalkPlanIn {
     // what exists before anything is prepared
     bool table_supported;           // the engine has a level table at all (level_table_eng_supported)
     bool adj_mag_valid;             // cos_index::adj_mag_valid (engine.hip sets it again after the refill, before it settles the plan)
+    // the two-part level-table GEMM (header comment)
+    uint32_t table_early_wgs;       // tuning knob walk_table_early_wgs, resolved (0 = one launch)
+    bool table_queue;               // the table comes from the query-resident GEMM, whose work items can be shared by two launches
+    uint32_t n_cus;                 // compute units of the device (0 = 256): sizes the GEMM's work items
 };
 
 // What preparation left, for the second step: no table operand for this graph and rule, no room for a workspace's table (out of
@@ -63,6 +81,7 @@ struct WalkPlan {
     bool ordered;              // the walk is cut after every order key level and the levels below run in locality order (throughput kernel)
     bool use_table;            // the level-table GEMM runs and the walk reads it
     bool table_waits_for_sort; // ... behind the previous chained launch's order sort (cos_index::chain_last_range_ev)
+    uint32_t table_early_wgs;  // ... as two launches over one queue: workgroups of the early part (0 = one launch; header comment)
     uint32_t use_adj_mag;      // bit l: level l reads its winners' norms beside the adjacency
     bool refill_adj_mag;       // the norms are refilled first
     bool chained;              // the walk takes its place in the walk chain
@@ -70,6 +89,30 @@ struct WalkPlan {
     bool prepare_order, prepare_table; // what the above needs: order buffers + ranks, table operand + buffer
     uint32_t table_level_min, table_cols, cut_after_level; // of this launch (0 without a table / unsplit): cos_index_last_walk_split
 };
+
+// Work items of the query-resident level-table GEMM: a row group of 256 queries x a stripe of table_gemm_stripe_tiles() column tiles of
+// 64 nodes.
+//   * shared = false, a GEMM that is ONE full-width launch (not gated: c2's 20 903 columns): one item per workgroup — the partition of
+//     the fixed grid it replaces, n_cus / row groups contiguous column groups per row group.  No workgroup restarts its staging
+//     pipeline or reloads its query rows (finer items cost c2 0.14 ms per step: DESIGN.md §0.1);
+//   * shared = true, a gated GEMM (table_waits_for_sort), whose queue two launches may share and whose workgroups are placed one by one
+//     into the previous walk's draining lower range: about 24 items per workgroup of a full-width launch, so that late workgroups
+//     find the rest of the work evenly spread; at least 2 and at most 64 tiles, so that the 256 query rows a workgroup reloads when
+//     its row group changes (256 x K bytes from L2) stay small against the item's MFMAs.  12.5M x 1024 shard (65 161 columns x 32 768
+//     queries): 21 tiles = 1 344 columns, 6 272 items.
+inline uint32_t table_gemm_stripe_tiles(uint32_t B, uint32_t cols, uint32_t n_cus, bool shared) {
+    const uint32_t n_tiles = (cols + 63u) / 64u, row_groups = (B + 255u) / 256u, cus = n_cus ? n_cus : 256u;
+    if (!shared) {
+        const uint32_t groups = std::max(1u, cus / std::max(1u, std::min(row_groups, cus)));
+        return std::max(1u, (n_tiles + groups - 1u) / groups);
+    }
+    const uint64_t units = (uint64_t)n_tiles * row_groups;
+    return (uint32_t)std::min<uint64_t>(64u, std::max<uint64_t>(2u, units / (24ull * cus)));
+}
+inline uint32_t table_gemm_items(uint32_t B, uint32_t cols, uint32_t n_cus, bool shared) {
+    const uint32_t n_tiles = (cols + 63u) / 64u, st = table_gemm_stripe_tiles(B, cols, n_cus, shared);
+    return (uint32_t)std::min<uint64_t>(0xFFFFFFFFull, (uint64_t)((n_tiles + st - 1u) / st) * ((B + 255u) / 256u));
+}
 
 // more than 64 scanned slots per node on some level: walk_general_kernel's graphs (it gathers the norms: no LevelDev::adj_mag)
 inline bool walk_rows_over_64_slots(const WalkPlanIn &in) {
@@ -149,6 +192,9 @@ inline WalkPlan walk_plan(const WalkPlanIn &in, const WalkHave *have = nullptr) 
         // shard's 65 161 columns x 32 768 queries (3.1 ms alone; gate: 33.3 -> 32.6 ms per step) do, c2's 20 903 (0.85 ms; 6.22 -> 6.29) do not
         // (profiles/r06_inflight_probe.txt)
         p.table_waits_for_sort = p.chained && (in.table_after_sort == 2 || (in.table_after_sort == 1 && (uint64_t)have->table_cols * in.B >= (1ull << 30)));
+        // ... and only such a GEMM is worth two launches: the early part runs under the previous walk's lower range (header comment)
+        if (p.table_waits_for_sort && in.table_queue)
+            p.table_early_wgs = std::min(in.table_early_wgs, table_gemm_items(in.B, have->table_cols, in.n_cus, true));
     }
     if (have && p.ordered) p.cut_after_level = have->order_level0;
     // Norms beside the adjacency cost two more lines per window entry and save one line per winner: they pay while an expansion still

@@ -291,8 +291,8 @@ typedef struct {
     uint32_t table_level_min;   /* 0 = the launch used no table */
     uint32_t table_cols;
     uint32_t cut_after_level;   /* 0 = the walk was one dispatch (everything is in `lower`) */
-    uint32_t reserved;
-    float table_ms;             /* level-table GEMM (+ the queries' code sums) */
+    uint32_t table_early_wgs;   /* workgroups of the GEMM's early part (tuning knob walk_table_early_wgs, clamped); 0 = the GEMM was one launch */
+    float table_ms;             /* level-table GEMM: execution time, summed over its launches (the waits in front of them excluded) */
     float upper_ms, sort_ms, lower_ms;
     double table_int8_ops;      /* 2 * queries * cols * padded dims */
     uint64_t table_evals;       /* evaluations the table served (all of them above the cut) */
