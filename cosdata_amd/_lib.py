@@ -92,6 +92,15 @@ class CosSparseIndexStats(C.Structure):
                 ("postings", C.c_uint64), ("removed", C.c_uint64), ("raw_pairs", C.c_uint64), ("device_bytes", C.c_uint64)]
 
 
+class CosHybridRequest(C.Structure):
+    """cos_hybrid_request: one mixed hybrid batch (every query names its arm; the three query sets are in query order)"""
+    _fields_ = [("struct_size", C.c_uint32), ("B", C.c_uint32), ("arm", C.c_void_p), ("dense_queries", C.c_void_p),
+                ("sparse_dims", C.c_void_p), ("sparse_vals", C.c_void_p), ("sparse_offsets", C.c_void_p),
+                ("bm25_terms", C.c_void_p), ("bm25_offsets", C.c_void_p),
+                ("sparse_early_terminate_threshold", C.c_float), ("sparse_reranking_factor", C.c_uint32),
+                ("top_k", C.c_uint32), ("fusion_constant_k", C.c_float)]
+
+
 def build(force: bool = False, verbose: bool = False) -> str:
     """Compile every HIP source for gfx950 into cosdata_amd/libcosdata_hip.so (in-tree)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
@@ -120,7 +129,8 @@ ABI_SYMBOLS = [
     "cos_code_bytes", "cos_sample_values_range", "cos_distance_batch", "cos_bruteforce_topk", "cos_flat_search_batch", "cos_bm25_create", "cos_bm25_destroy",
     "cos_bm25_insert", "cos_bm25_delete", "cos_bm25_stats", "cos_bm25_download",
     "cos_bm25_search_batch", "cos_bm25_search_batch_device", "cos_rrf_fuse_batch", "cos_hybrid_search_batch", "cos_text_process", "cos_text_count_tokens", "cos_bm25_term_frequency", "cos_xxhash32", "cos_stem_english", "cos_sparse_create", "cos_sparse_build_csr", "cos_sparse_create_from_vectors", "cos_sparse_destroy", "cos_sparse_search_batch", "cos_sparse_last_stats", "cos_sparse_layout",
-    "cos_sparse_set_max_candidates", "cos_sparse_max_candidates",
+    "cos_sparse_set_max_candidates", "cos_sparse_max_candidates", "cos_sparse_search_batch_device",
+    "cos_hybrid_create", "cos_hybrid_destroy", "cos_hybrid_search_mixed",
     "cos_sparse_insert", "cos_sparse_delete", "cos_sparse_stats", "cos_sparse_download", "cos_merge_topk_device", "cos_merge_topk_packed_device", "cos_hbm_probe",
     "cos_shardset_unique_id", "cos_shardset_create", "cos_shardset_destroy", "cos_shardset_search_batch", "cos_shardset_exchange_device",
     "cos_tuning_set", "cos_tuning_clear", "cos_tuning_get",
@@ -207,6 +217,10 @@ def lib():
         "cos_sparse_create_from_vectors": [i32, u32, f32, u32, vp, vp, vp, i32, C.POINTER(vp)],
         "cos_sparse_destroy": [vp],
         "cos_sparse_search_batch": [vp, vp, vp, vp, u32, u32, f32, u32, vp, vp, vp],
+        "cos_sparse_search_batch_device": [vp, vp, vp, vp, u32, u32, f32, u32, vp, vp, vp, vp],
+        "cos_hybrid_create": [i32, C.POINTER(vp)],
+        "cos_hybrid_destroy": [vp],
+        "cos_hybrid_search_mixed": [vp, vp, vp, vp, C.POINTER(CosHybridRequest), vp, vp, vp],
         "cos_sparse_last_stats": [vp, vp],
         "cos_sparse_layout": [vp, C.POINTER(u32)],
         "cos_sparse_set_max_candidates": [vp, u32],

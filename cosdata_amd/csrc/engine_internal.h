@@ -77,6 +77,16 @@ int32_t cos_fail(int32_t code, const char *fmt, ...);
         if (_e != hipSuccess) return cos_fail(COS_ERR_HIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
     } while (0)
 
+// The learned-sparse handle as the fused hybrid call sees it (kernels_sparse.hip defines it, kernels_hybrid.hip holds its lock from the
+// limit check to the call's one synchronisation).  sparse_limits and sparse_search_locked are for a caller that holds sparse_mutex.
+namespace cosdev {
+std::mutex &sparse_mutex(cos_sparse *s);
+int32_t sparse_device(const cos_sparse *s);
+void sparse_limits(const cos_sparse *s, u32 *max_candidates, bool *have_raw, u32 *batch_bound);
+int32_t sparse_search_locked(cos_sparse *s, const uint32_t *q_dims, const float *q_vals, const uint32_t *q_offsets, u32 B, u32 top_k,
+                             float early_terminate_threshold, u32 reranking_factor, u32 *d_out_ids, float *d_out_scores, u32 *d_out_counts, hipStream_t st);
+} // namespace cosdev
+
 // ------------------------------------------------------------------------------------------------
 // handle
 // ------------------------------------------------------------------------------------------------

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "engine_internal.h"
+#include "hybrid_plan.h"
 #include "postings_update.h"
 #include "topk_select.h"
 
@@ -232,19 +233,15 @@ __global__ __launch_bounds__(64) void bm25_topk_kernel(const u64 *__restrict__ b
     if (lane == 0) out_counts[q] = n;
 }
 
-// RRF: one wave per query.  score(id) = [last dense occurrence: 1/(rank+k+eps)] then += each sparse occurrence.
+// RRF: one wave per query.  score(id) = [last occurrence in the FIRST list: 1/(rank+k+eps)] then += each occurrence in the SECOND list.
+// The body both fusion kernels share, from the query's two rows on: gather into LDS, first-occurrence ownership, overwrite in the
+// first list (insert()), add in the second, pack, bitonic sort, write-out.  ids: LDS, [nd + ns].
 template <int R>
-__global__ __launch_bounds__(64) void rrf_kernel(const u32 *__restrict__ dense_ids, const u32 *__restrict__ dense_counts, u32 dense_stride,
-                                                 const u32 *__restrict__ sparse_ids, const u32 *__restrict__ sparse_counts, u32 sparse_stride, u32 B,
-                                                 float kc, u32 top_k, u32 *__restrict__ out_ids, float *__restrict__ out_scores,
-                                                 u32 *__restrict__ out_counts) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    u32 *ids = (u32 *)smem_raw; // [nd + ns]
+__device__ __forceinline__ void rrf_fuse_query(u32 *ids, const u32 *__restrict__ first_row, u32 nd, const u32 *__restrict__ second_row, u32 ns, u32 q, float kc,
+                                               u32 top_k, u32 *__restrict__ out_ids, float *__restrict__ out_scores, u32 *__restrict__ out_counts) {
     const int lane = threadIdx.x;
-    const u32 q = blockIdx.x;
-    if (q >= B) return;
-    const u32 nd = dense_counts[q], ns = sparse_counts[q], n = nd + ns;
-    for (u32 i = lane; i < n; i += 64) ids[i] = i < nd ? dense_ids[(u64)q * dense_stride + i] : sparse_ids[(u64)q * sparse_stride + (i - nd)];
+    const u32 n = nd + ns;
+    for (u32 i = lane; i < n; i += 64) ids[i] = i < nd ? first_row[i] : second_row[i - nd];
     __builtin_amdgcn_wave_barrier();
     u64 key[R];
     u32 cnt = 0;
@@ -280,6 +277,40 @@ __global__ __launch_bounds__(64) void rrf_kernel(const u32 *__restrict__ dense_i
         }
     }
     if (lane == 0) out_counts[q] = nout;
+}
+
+template <int R>
+__global__ __launch_bounds__(64) void rrf_kernel(const u32 *__restrict__ dense_ids, const u32 *__restrict__ dense_counts, u32 dense_stride,
+                                                 const u32 *__restrict__ sparse_ids, const u32 *__restrict__ sparse_counts, u32 sparse_stride, u32 B,
+                                                 float kc, u32 top_k, u32 *__restrict__ out_ids, float *__restrict__ out_scores,
+                                                 u32 *__restrict__ out_counts) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    u32 *ids = (u32 *)smem_raw; // [nd + ns]
+    const u32 q = blockIdx.x;
+    if (q >= B) return;
+    rrf_fuse_query<R>(ids, dense_ids + (u64)q * dense_stride, dense_counts[q], sparse_ids + (u64)q * sparse_stride, sparse_counts[q], q, kc, top_k, out_ids,
+                      out_scores, out_counts);
+}
+
+// The three list sets of a mixed hybrid batch, each ids [n_x][stride] + counts [n_x]; a set without queries is null and never chosen.
+struct RrfListSets {
+    const u32 *dense_ids, *dense_counts, *sparse_ids, *sparse_counts, *bm25_ids, *bm25_counts;
+};
+// One wave per query of the request: slots[q] = (arm, row of its first list, row of its second list) chooses the two lists — (dense,
+// sparse), (dense, BM25), (sparse, BM25) — and the rest is rrf_kernel's.  A count is held to the stride: the LDS holds 2 * stride ids.
+template <int R>
+__global__ __launch_bounds__(64) void rrf_mixed_kernel(const RrfListSets sets, const hybrid_plan::Slot *__restrict__ slots, u32 stride, u32 B, float kc, u32 top_k,
+                                                       u32 *__restrict__ out_ids, float *__restrict__ out_scores, u32 *__restrict__ out_counts) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    u32 *ids = (u32 *)smem_raw; // [2 * stride]
+    const u32 q = blockIdx.x;
+    if (q >= B) return;
+    const hybrid_plan::Slot sl = slots[q];
+    const bool first_sparse = sl.arm == hybrid_plan::SPARSE_BM25, second_sparse = sl.arm == hybrid_plan::DENSE_SPARSE;
+    const u32 *fi = first_sparse ? sets.sparse_ids : sets.dense_ids, *fc = first_sparse ? sets.sparse_counts : sets.dense_counts;
+    const u32 *si = second_sparse ? sets.sparse_ids : sets.bm25_ids, *sc = second_sparse ? sets.sparse_counts : sets.bm25_counts;
+    const u32 nd = min(fc[sl.pos_first], stride), ns = min(sc[sl.pos_second], stride);
+    rrf_fuse_query<R>(ids, fi + (u64)sl.pos_first * stride, nd, si + (u64)sl.pos_second * stride, ns, q, kc, top_k, out_ids, out_scores, out_counts);
 }
 
 } // namespace
@@ -609,6 +640,211 @@ extern "C" int32_t cos_hybrid_search_batch(cos_index *ix, cos_bm25 *b, const flo
     const int32_t *status = (const int32_t *)(hr + 2 * nk + B);
     for (u32 q = 0; q < B; q++)
         if (status[q] != COS_OK) return cos_fail(status[q], "dense half: query %u failed with status %d (zero-norm vector -> DistanceError::CalculationError)", q, status[q]);
+    return COS_OK;
+}
+
+
+// ------------------------------------------------------------------------------------------------
+// repo::batch_hybrid_search (api/vectordb/search/repo.rs:343-555) in one call: every query names its arm, the three batch searches
+// run side by side for top_k * 3, each over its own sub-batch only, and rrf_mixed_kernel fuses every query's two lists on the device.
+// The host-only part (the split of arm[], the limits) is hybrid_plan.h.
+// ------------------------------------------------------------------------------------------------
+static_assert(hybrid_plan::OK == COS_OK && hybrid_plan::INVALID == COS_ERR_INVALID && hybrid_plan::UNIMPLEMENTED == COS_ERR_UNIMPLEMENTED &&
+                  hybrid_plan::NOT_READY == COS_ERR_NOT_READY, "hybrid_plan.h restates cos_status");
+static_assert(hybrid_plan::DENSE_SPARSE == COS_HYBRID_DENSE_SPARSE && hybrid_plan::DENSE_BM25 == COS_HYBRID_DENSE_BM25 &&
+                  hybrid_plan::SPARSE_BM25 == COS_HYBRID_SPARSE_BM25, "hybrid_plan.h restates the arms");
+static_assert(sizeof(hybrid_plan::Slot) == 12, "three words per query");
+static_assert(hybrid_plan::MAX_LIST == BUCKETS, "a BM25 list is at most its buckets");
+
+struct cos_hybrid {
+    int32_t device = 0;
+    std::mutex mu; // one call at a time; taken before the sparse handle's lock, that before the BM25 handle's
+    // three non-blocking streams: the dense half (highest priority; the fusion and the copy back follow on it), the sparse half, the BM25 half
+    hipStream_t st_dense = nullptr, st_sparse = nullptr, st_bm25 = nullptr;
+    hipEvent_t ev_sparse = nullptr, ev_bm25 = nullptr;
+    std::vector<hybrid_plan::Slot> slots; // the request's query_mapping (host)
+    // what goes up in ONE copy: [dense queries n_dense x dim f32 | Slot x B] (the queries first: they keep the allocation's alignment), pinned image and device block
+    PinArr<unsigned char> h_in;
+    DevBuf d_in;
+    // the three list sets [n_x][3 * top_k] + counts [n_x] (grow-only)
+    DevArr<u32> d_did, d_dcnt, d_sid, d_scnt, d_bid, d_bcnt;
+    DevArr<float> d_dsc, d_ssc, d_bsc;
+    // what comes back in ONE copy: [fused ids B x k | fused scores B x k | counts B | dense status n_dense], device block and pinned landing area
+    DevArr<u32> d_ret;
+    PinArr<u32> h_ret;
+    ~cos_hybrid() { // (cos_hybrid_destroy has drained the streams)
+        if (st_dense) (void)hipStreamDestroy(st_dense);
+        if (st_sparse) (void)hipStreamDestroy(st_sparse);
+        if (st_bm25) (void)hipStreamDestroy(st_bm25);
+        if (ev_sparse) (void)hipEventDestroy(ev_sparse);
+        if (ev_bm25) (void)hipEventDestroy(ev_bm25);
+    }
+};
+
+static int32_t hybrid_drain(cos_hybrid *h) {
+    HIP_TRY(hipStreamSynchronize(h->st_sparse));
+    HIP_TRY(hipStreamSynchronize(h->st_bm25));
+    HIP_TRY(hipStreamSynchronize(h->st_dense));
+    return COS_OK;
+}
+
+extern "C" int32_t cos_hybrid_destroy(cos_hybrid *h) {
+    if (!h) return COS_OK;
+    (void)hipSetDevice(h->device);
+    if (h->st_dense && h->st_sparse && h->st_bm25) (void)hybrid_drain(h);
+    delete h;
+    return COS_OK;
+}
+
+extern "C" int32_t cos_hybrid_create(int32_t device, cos_hybrid **out) {
+    if (!out) return cos_fail(COS_ERR_INVALID, "bad argument");
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return cos_fail(COS_ERR_NO_DEVICE, "no HIP device visible; the GPU path has no CPU fallback");
+    if (device < 0 || device >= ndev) return cos_fail(COS_ERR_INVALID, "device %d of %d", device, ndev);
+    HIP_TRY(hipSetDevice(device));
+    cos_hybrid *h = new cos_hybrid();
+    h->device = device;
+    int prio_low = 0, prio_high = 0;
+    hipError_t e = hipDeviceGetStreamPriorityRange(&prio_low, &prio_high);
+    if (e == hipSuccess) e = hipStreamCreateWithPriority(&h->st_dense, hipStreamNonBlocking, prio_high);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->st_sparse, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->st_bm25, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_sparse, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_bm25, hipEventDisableTiming);
+    if (e != hipSuccess) { delete h; HIP_TRY(e); }
+    *out = h;
+    return COS_OK;
+}
+
+extern "C" int32_t cos_hybrid_search_mixed(cos_hybrid *h, cos_index *ix, cos_sparse *sp, cos_bm25 *bm, const cos_hybrid_request *rq, uint32_t *out_ids,
+                                           float *out_scores, uint32_t *out_counts) {
+    namespace hp = hybrid_plan;
+    if (!h || !rq || !out_ids || !out_scores || !out_counts) return cos_fail(COS_ERR_INVALID, "bad argument");
+    if (rq->struct_size < sizeof(cos_hybrid_request)) return cos_fail(COS_ERR_INVALID, "cos_hybrid_request.struct_size %u, expected %zu", rq->struct_size, sizeof(cos_hybrid_request));
+    const u32 B = rq->B, top_k = rq->top_k, rf = rq->sparse_reranking_factor;
+    int32_t rc = hp::check_request(rq->struct_size, (u32)sizeof(cos_hybrid_request), B, top_k);
+    if (rc == COS_ERR_UNIMPLEMENTED) return cos_fail(rc, "top_k above %u: every half is asked for 3 * top_k, BM25 keeps %u buckets and the fusion holds two such lists", hp::MAX_TOP_K, BUCKETS);
+    if (rc || !rq->arm) return cos_fail(COS_ERR_INVALID, "bad argument (B %u, top_k %u)", B, top_k);
+    const u32 k3 = hp::LIST_FACTOR * top_k;
+    std::lock_guard<std::mutex> gh(h->mu);
+    // ---- the request's query_mapping and everything that refuses it: nothing is enqueued before the last check ----
+    try {
+        h->slots.resize(B);
+    } catch (const std::bad_alloc &) {
+        return cos_fail(COS_ERR_INVALID, "batch of %u queries", B);
+    }
+    hp::Split n;
+    u32 bad = 0;
+    if (hp::split(rq->arm, B, h->slots.data(), n, &bad)) return cos_fail(COS_ERR_INVALID, "arm %u of query %u", (u32)rq->arm[bad], bad);
+    if (hp::check_handles(n, ix != nullptr, sp != nullptr, bm != nullptr))
+        return cos_fail(COS_ERR_INVALID, "a handle is NULL whose half has queries (dense %u, sparse %u, BM25 %u)", n.n_dense, n.n_sparse, n.n_bm25);
+    if ((n.n_dense && !rq->dense_queries) || (n.n_sparse && (!rq->sparse_dims || !rq->sparse_vals || !rq->sparse_offsets)) || (n.n_bm25 && (!rq->bm25_terms || !rq->bm25_offsets)))
+        return cos_fail(COS_ERR_INVALID, "the queries of a half that has some are NULL");
+    if ((n.n_dense && ix->p.device != h->device) || (n.n_sparse && sparse_device(sp) != h->device) || (n.n_bm25 && bm->device != h->device))
+        return cos_fail(COS_ERR_INVALID, "the indexes of a hybrid call live on the device of its cos_hybrid (%d)", h->device);
+    if (n.n_sparse && !hp::offsets_ascend(rq->sparse_offsets, n.n_sparse)) return cos_fail(COS_ERR_INVALID, "sparse query offsets decrease");
+    if (n.n_bm25 && !hp::offsets_ascend(rq->bm25_offsets, n.n_bm25)) return cos_fail(COS_ERR_INVALID, "BM25 query offsets decrease");
+    std::unique_lock<std::mutex> gs, gb; // cos_hybrid -> cos_sparse -> cos_bm25, each held until the synchronise below
+    if (n.n_sparse) {
+        gs = std::unique_lock<std::mutex>(sparse_mutex(sp));
+        hp::SparseLimits lim{};
+        sparse_limits(sp, &lim.max_candidates, &lim.have_raw, &lim.batch_bound);
+        rc = hp::check_sparse(n.n_sparse, top_k, rf, lim);
+        if (rc == COS_ERR_NOT_READY) return cos_fail(rc, "raw-value rerank needs the raw sparse vectors (cos_sparse_create row_offsets / raw_dims / raw_vals)");
+        if (rc == COS_ERR_UNIMPLEMENTED) return cos_fail(rc, "3 x top_k x reranking_factor must be <= %u (cos_sparse_set_max_candidates)", lim.max_candidates);
+        if (rc) return cos_fail(rc, "sparse sub-batch of %u queries", n.n_sparse);
+    }
+    if (n.n_bm25) gb = std::unique_lock<std::mutex>(bm->mu);
+    HIP_TRY(hipSetDevice(h->device));
+    rc = hybrid_drain(h); // a call that failed half-way may have left work behind: the staging is free only now
+    if (rc) return rc;
+    // ---- buffers (grow-only; no allocation once warm) ----
+    const size_t dim = n.n_dense ? ix->p.dim : 0;
+    const size_t in_bytes = (size_t)B * sizeof(hp::Slot) + (size_t)n.n_dense * dim * 4;
+    HIP_TRY(h->h_in.grow(in_bytes));
+    HIP_TRY(h->d_in.grow(in_bytes));
+    if (n.n_dense) { HIP_TRY(h->d_did.grow((size_t)n.n_dense * k3)); HIP_TRY(h->d_dsc.grow((size_t)n.n_dense * k3)); HIP_TRY(h->d_dcnt.grow(n.n_dense)); }
+    if (n.n_sparse) { HIP_TRY(h->d_sid.grow((size_t)n.n_sparse * k3)); HIP_TRY(h->d_ssc.grow((size_t)n.n_sparse * k3)); HIP_TRY(h->d_scnt.grow(n.n_sparse)); }
+    if (n.n_bm25) { HIP_TRY(h->d_bid.grow((size_t)n.n_bm25 * k3)); HIP_TRY(h->d_bsc.grow((size_t)n.n_bm25 * k3)); HIP_TRY(h->d_bcnt.grow(n.n_bm25)); }
+    const size_t nk = (size_t)B * top_k, ret_words = 2 * nk + (size_t)B + n.n_dense;
+    HIP_TRY(h->d_ret.grow(ret_words));
+    HIP_TRY(h->h_ret.grow(ret_words));
+    u32 *d_fid = h->d_ret, *d_fcnt = h->d_ret + 2 * nk;
+    float *d_fsc = (float *)(h->d_ret + nk);
+    int32_t *d_dst = (int32_t *)(h->d_ret + 2 * nk + B);
+    if (n.n_bm25) {
+        rc = bm25_workspace(bm, n.n_bm25, k3);
+        if (rc) return rc;
+        HIP_TRY(hipStreamSynchronize(bm->stream)); // the handle's own batches have consumed its pinned term table
+        if (bm->stream_dense) HIP_TRY(hipStreamSynchronize(bm->stream_dense));
+    }
+    // ---- enqueue.  From here a failure drains the three streams before the locks go. ----
+    auto fail = [&](int32_t code) { (void)hybrid_drain(h); return code; };
+#define HYB_TRY(expr)                                                                                                                                  \
+    do {                                                                                                                                               \
+        const hipError_t _e = (expr);                                                                                                                  \
+        if (_e != hipSuccess) return fail(cos_fail(COS_ERR_HIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__));                  \
+    } while (0)
+    // The dense half goes FIRST, on the stream of the highest priority, as in cos_hybrid_search_batch: its walk is a chain of
+    // dependent rounds on a part of the chip, the two postings scans are bandwidth kernels that fill what it leaves free.  The mapping rides
+    // in the same copy as the dense queries.
+    const size_t q_bytes = (size_t)n.n_dense * dim * 4;
+    if (n.n_dense) memcpy(h->h_in.p, rq->dense_queries, q_bytes);
+    memcpy(h->h_in.p + q_bytes, h->slots.data(), (size_t)B * sizeof(hp::Slot));
+    HYB_TRY(hipMemcpyAsync(h->d_in.p, h->h_in.p, in_bytes, hipMemcpyHostToDevice, h->st_dense));
+    if (n.n_dense) {
+        rc = cos_search_batch_device(ix, (const float *)h->d_in.p, n.n_dense, k3, h->d_did, h->d_dsc, h->d_dcnt, d_dst, h->st_dense);
+        if (rc) return fail(rc);
+    }
+    // the sparse half next, on its stream: host resolution while the device already walks.  Sparse before BM25 in the SPARSE_BM25 arm: not measured.
+    if (n.n_sparse) {
+        rc = sparse_search_locked(sp, rq->sparse_dims, rq->sparse_vals, rq->sparse_offsets, n.n_sparse, k3, rq->sparse_early_terminate_threshold, rf, h->d_sid,
+                                  h->d_ssc, h->d_scnt, h->st_sparse);
+        if (rc) return fail(rc);
+        HYB_TRY(hipEventRecord(h->ev_sparse, h->st_sparse));
+    }
+    if (n.n_bm25) {
+        rc = bm25_prepare(bm, rq->bm25_terms, rq->bm25_offsets, n.n_bm25);
+        if (rc) return fail(rc);
+        rc = bm25_launch(bm, n.n_bm25, k3, h->d_bid, h->d_bsc, h->d_bcnt, h->st_bm25);
+        if (rc) return fail(rc);
+        HYB_TRY(hipEventRecord(h->ev_bm25, h->st_bm25));
+    }
+    // fusion once the halves that ran are there
+    hipStream_t sf = h->st_dense;
+    if (n.n_sparse) HYB_TRY(hipStreamWaitEvent(sf, h->ev_sparse, 0));
+    if (n.n_bm25) HYB_TRY(hipStreamWaitEvent(sf, h->ev_bm25, 0));
+    const RrfListSets sets{n.n_dense ? h->d_did.p : nullptr, n.n_dense ? h->d_dcnt.p : nullptr, n.n_sparse ? h->d_sid.p : nullptr, n.n_sparse ? h->d_scnt.p : nullptr,
+                           n.n_bm25 ? h->d_bid.p : nullptr, n.n_bm25 ? h->d_bcnt.p : nullptr};
+    const hp::Slot *d_slots = (const hp::Slot *)(h->d_in.p + q_bytes);
+    const size_t smem = (size_t)2 * k3 * 4;
+#define LAUNCH(R) hipLaunchKernelGGL(rrf_mixed_kernel<R>, dim3(B), dim3(64), smem, sf, sets, d_slots, k3, B, rq->fusion_constant_k, top_k, d_fid, d_fsc, d_fcnt)
+    switch (hp::rrf_keys_per_lane(2 * k3)) {
+    case 1: LAUNCH(1); break;
+    case 2: LAUNCH(2); break;
+    case 4: LAUNCH(4); break;
+    case 8: LAUNCH(8); break;
+    default: LAUNCH(16); break; // (2 * k3 <= 1024: checked above)
+    }
+#undef LAUNCH
+    HYB_TRY(hipGetLastError());
+    HYB_TRY(hipMemcpyAsync(h->h_ret, h->d_ret, ret_words * 4, hipMemcpyDeviceToHost, sf));
+    HYB_TRY(hipStreamSynchronize(sf));
+#undef HYB_TRY
+    const u32 *hr = h->h_ret;
+    const int32_t *status = (const int32_t *)(hr + 2 * nk + B);
+    for (u32 q = 0; q < B; q++) { // the first failing query in request order
+        const hp::Slot &sl = h->slots[q];
+        if (hp::arm_has_dense(sl.arm) && status[sl.pos_first] != COS_OK)
+            return cos_fail(status[sl.pos_first], "dense half: query %u failed with status %d (zero-norm vector -> DistanceError::CalculationError)", q, status[sl.pos_first]);
+    }
+    for (u32 q = 0; q < B; q++) { // entries past a query's count are not written
+        const u32 c = std::min(hr[2 * nk + q], top_k);
+        memcpy(out_ids + (size_t)q * top_k, hr + (size_t)q * top_k, (size_t)c * 4);
+        memcpy(out_scores + (size_t)q * top_k, hr + nk + (size_t)q * top_k, (size_t)c * 4);
+        out_counts[q] = c;
+    }
     return COS_OK;
 }
 

@@ -763,8 +763,11 @@ struct cos_sparse {
     DevArr<float> d_raw_vals;
     // grow-only workspace of cos_sparse_search_batch (no allocation on the query path once warm); `mu` serialises callers
     std::mutex mu;
-    DevBuf w_qd, w_qv, w_qo, w_terms, w_qt_off, w_order, w_part, w_oi, w_os, w_oc; // (bytes)
+    DevBuf w_in, w_part, w_oi, w_os, w_oc; // (bytes) w_in: the batch's resolved tables, one image (SparseImage); w_o*: the host entry point's results
+    PinArr<unsigned char> h_in;            // pinned staging of w_in: written by the host resolution, read by the launch's one copy
+    // ev0 / ev1 bracket the kernels of the most recent batch on the stream they ran on; ev1 is what the next batch (and destroy) waits for
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    bool stats_pending = false; // last.kernel_ms is still to be read from the events
     cos_sparse_search_stats last{};
     ~cos_sparse() {
         if (ev0) (void)hipEventDestroy(ev0);
@@ -775,20 +778,22 @@ struct cos_sparse {
 // scan + finish of a call that keeps more than 64 candidates per query: the instantiation R, pools and segments of 64 * R keys
 template <int R>
 static hipError_t sparse_launch_wide(const cos_sparse *s, const SparseDev &dev, u32 B, u32 splits, const STerm *terms, const u32 *qt_off, const u32 *order,
-                                     u64 *part, const u32 *qd, const float *qv, const u32 *qo, u32 top_k, u32 kwr, int rerank, u32 *oi, float *os, u32 *oc) {
+                                     u64 *part, const u32 *qd, const float *qv, const u32 *qo, u32 top_k, u32 kwr, int rerank, u32 *oi, float *os, u32 *oc,
+                                     hipStream_t st) {
     if (s->packed)
-        hipLaunchKernelGGL(sparse_wide_packed_kernel<R>, dim3(B * splits), dim3(256), 0, 0, s->d_pk.p, terms, qt_off, s->n, s->d_tile_dir.p, order, splits, part);
+        hipLaunchKernelGGL(sparse_wide_packed_kernel<R>, dim3(B * splits), dim3(256), 0, st, s->d_pk.p, terms, qt_off, s->n, s->d_tile_dir.p, order, splits, part);
     else
-        hipLaunchKernelGGL(sparse_tile_kernel<R>, dim3(B * splits), dim3(256), 0, 0, s->d_ids.p, s->d_keys.p, terms, qt_off, s->n, s->d_tile_dir.p, order, splits, part);
+        hipLaunchKernelGGL(sparse_tile_kernel<R>, dim3(B * splits), dim3(256), 0, st, s->d_ids.p, s->d_keys.p, terms, qt_off, s->n, s->d_tile_dir.p, order, splits, part);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(sparse_wide_finish_kernel<R>, dim3(B), dim3(256), 0, 0, dev, part, splits, qd, qv, qo, top_k, kwr, rerank, oi, os, oc);
+    hipLaunchKernelGGL(sparse_wide_finish_kernel<R>, dim3(B), dim3(256), 0, st, dev, part, splits, qd, qv, qo, top_k, kwr, rerank, oi, os, oc);
     return hipGetLastError();
 }
 
 extern "C" int32_t cos_sparse_destroy(cos_sparse *s) {
     if (!s) return COS_OK;
     (void)hipSetDevice(s->device);
+    if (s->ev1) (void)hipEventSynchronize(s->ev1); // a batch of cos_sparse_search_batch_device may still be reading the workspace
     delete s;
     return COS_OK;
 }
@@ -955,37 +960,83 @@ extern "C" int32_t cos_sparse_create_from_vectors(int32_t device, uint32_t quant
                              keep_raw ? row_offsets : nullptr, keep_raw ? raw_dims : nullptr, keep_raw ? raw_vals : nullptr, out);
 }
 
-extern "C" int32_t cos_sparse_search_batch(cos_sparse *s, const uint32_t *q_dims, const float *q_vals, const uint32_t *q_offsets, uint32_t B, uint32_t top_k,
-                                           float early_terminate_threshold, uint32_t reranking_factor, uint32_t *out_ids, float *out_scores,
-                                           uint32_t *out_counts) {
-    if (!s || !q_dims || !q_vals || !q_offsets || !out_ids || !out_scores || !out_counts || B == 0 || top_k == 0) return cos_fail(COS_ERR_INVALID, "bad argument");
+// ---- the search in two parts: host resolution into pinned staging, then copy + kernels on a stream --------------------------------
+// what the resolution of one batch leaves for its launch (the tables themselves are in the handle's staging)
+struct SparseBatch {
+    u32 B = 0, nq = 0, top_k = 0, kwr = 0, R = 1, splits = 1;
+    int rerank = 0;
+    size_t bytes = 0; // of the staging image
+};
+// One image, one copy: [STerm x nq (a query pair resolves to at most one term) | q_dims nq | q_vals nq | q_offsets B + 1 | qt_off B + 1 | order B]
+struct SparseImage {
+    size_t qd, qv, qo, qt_off, order, bytes;
+    SparseImage(u32 B, u32 nq) {
+        qd = (size_t)nq * sizeof(STerm);
+        qv = qd + (size_t)nq * 4;
+        qo = qv + (size_t)nq * 4;
+        qt_off = qo + ((size_t)B + 1) * 4;
+        order = qt_off + ((size_t)B + 1) * 4;
+        bytes = order + (size_t)B * 4;
+    }
+};
+
+// the handle's previous batch has left the staging and the workspace (its end event; a never-recorded event is complete), and its
+// kernel time is settled while both events still belong to it
+static int32_t sparse_wait_previous(cos_sparse *s) {
+    HIP_TRY(hipEventSynchronize(s->ev1));
+    if (s->stats_pending) {
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+        s->last.kernel_ms = ms;
+        s->stats_pending = false;
+    }
+    return COS_OK;
+}
+
+// limits of a call, in the order cos_sparse_search_batch has always checked them (the caller holds s->mu for max_cand)
+static int32_t sparse_admit(const cos_sparse *s, u32 B, u32 top_k, u32 reranking_factor) {
     if (B >= SPK_COUNTED) return cos_fail(COS_ERR_INVALID, "batch of %u queries", B);
     const bool rerank = reranking_factor != 0;
     if (rerank && !s->have_raw) return cos_fail(COS_ERR_NOT_READY, "raw-value rerank needs the raw sparse vectors (cos_sparse_create row_offsets / raw_dims / raw_vals)");
-    // cos_sparse_insert / cos_sparse_delete replace the host tables the resolution reads (absolute list offsets included) together
-    // with the device arrays, cos_sparse_set_max_candidates the width this call is held to: one lock over all of it
-    std::lock_guard<std::mutex> guard(s->mu);
     const u64 kwr64 = (u64)top_k * (rerank ? reranking_factor : 1u);
     if (kwr64 > s->max_cand) return cos_fail(COS_ERR_UNIMPLEMENTED, "top_k x reranking_factor must be <= %u", s->max_cand);
-    const u32 kwr = (u32)kwr64;
+    return COS_OK;
+}
+
+// Host resolution (sparse_ann_query.rs:80-125): find_node, quantize, which keys a term visits, the launch order — written into the
+// handle's pinned staging.  The caller holds s->mu (cos_sparse_insert / cos_sparse_delete replace the host tables this reads, absolute
+// list offsets included, cos_sparse_set_max_candidates the width the call is held to) and the previous batch has been waited for.
+static int32_t sparse_resolve(cos_sparse *s, const uint32_t *q_dims, const float *q_vals, const uint32_t *q_offsets, u32 B, u32 top_k,
+                              float early_terminate_threshold, u32 reranking_factor, SparseBatch &sb) {
+    int32_t rc = sparse_admit(s, B, top_k, reranking_factor);
+    if (rc) return rc;
+    const bool rerank = reranking_factor != 0;
+    const u32 kwr = (u32)((u64)top_k * (rerank ? reranking_factor : 1u));
     // the variant is the call's, not the handle's: up to 64 candidates run the narrow kernels whatever the handle allows
     u32 R = 1;
     while (SEL * R < kwr) R *= 2;
-    HIP_TRY(hipSetDevice(s->device));
     for (u32 b = 0; b < B; b++)
         if (q_offsets[b + 1] < q_offsets[b]) return cos_fail(COS_ERR_INVALID, "query offsets decrease");
     const u32 nq = q_offsets[B], Q = 1u << s->bits;
-    // ---- resolve the query terms on the host (sparse_ann_query.rs:80-125): find_node, quantize, which keys the term visits ----
+    const SparseImage im(B, nq);
+    HIP_TRY(s->h_in.grow(im.bytes));
+    unsigned char *h = s->h_in;
+    STerm *terms = (STerm *)h;
+    u32 *qt_off = (u32 *)(h + im.qt_off), *order = (u32 *)(h + im.order);
+    if (nq) {
+        memcpy(h + im.qd, q_dims, (size_t)nq * 4);
+        memcpy(h + im.qv, q_vals, (size_t)nq * 4);
+    }
+    memcpy(h + im.qo, q_offsets, ((size_t)B + 1) * 4);
     const float qf = (float)Q;
     float etv = qf * early_terminate_threshold;
     etv = etv > 255.0f ? 255.0f : etv;
     const u32 early_terminate_value = f32_as_u8(etv), low_threshold = f32_as_u32(early_terminate_threshold * qf);
-    std::vector<STerm> terms;
-    terms.reserve(nq);
-    std::vector<u32> qt_off(B + 1, 0), order(B);
+    u32 n_terms = 0;
     std::vector<u64> weight(B, 0);
     std::vector<uint8_t> counted(B, 0);
     u64 visited = 0;
+    qt_off[0] = 0;
     for (u32 b = 0; b < B; b++) {
         u64 sum_bound = 0, touch_bound = 0; // packed layout: may this query's blocks count touches next to the sum (sparse_packed_body)?
         for (u32 i = q_offsets[b]; i < q_offsets[b + 1]; i++) {
@@ -997,70 +1048,123 @@ extern "C" int32_t cos_sparse_search_batch(cos_sparse *s, const uint32_t *q_dims
             if (k0 >= Q) continue;
             const u64 *ko = s->h_key_off.data() + (size_t)t * (Q + 1);
             if (ko[Q] == ko[0]) continue;
-            terms.push_back(STerm{ko[0], ko[Q], s->h_dir[t], qq | k0 << 8});
+            terms[n_terms++] = STerm{ko[0], ko[Q], s->h_dir[t], qq | k0 << 8};
             weight[b] += ko[Q] - ko[0];
             visited += ko[Q] - ko[k0];
             sum_bound += (u64)s->h_mult[t] * qq * (Q - 1u);
             touch_bound += s->h_mult[t];
         }
         counted[b] = sum_bound < SPK_CNT && touch_bound <= 1023u;
-        qt_off[b + 1] = (u32)terms.size();
+        qt_off[b + 1] = n_terms;
     }
     for (u32 b = 0; b < B; b++) order[b] = b;
-    std::stable_sort(order.begin(), order.end(), [&](u32 a, u32 c) { return weight[a] > weight[c]; }); // heaviest query first
+    std::stable_sort(order, order + B, [&](u32 a, u32 c) { return weight[a] > weight[c]; }); // heaviest query first
     if (s->packed)
         for (u32 b = 0; b < B; b++)
             if (counted[order[b]]) order[b] |= SPK_COUNTED;
+    sb.B = B;
+    sb.nq = nq;
+    sb.top_k = top_k;
+    sb.kwr = kwr;
+    sb.R = R;
+    sb.rerank = rerank ? 1 : 0;
     // blocks: enough to fill the chip several times over, at most one per tile
-    const u32 splits = std::max<u32>(1u, std::min<u32>(s->n_tiles, (4096u + B - 1) / B));
-    HIP_TRY(s->w_qd.grow((size_t)std::max(nq, 1u) * 4));
-    HIP_TRY(s->w_qv.grow((size_t)std::max(nq, 1u) * 4));
-    HIP_TRY(s->w_qo.grow(((size_t)B + 1) * 4));
-    HIP_TRY(s->w_terms.grow(std::max<size_t>(terms.size(), 1) * sizeof(STerm)));
-    HIP_TRY(s->w_qt_off.grow(((size_t)B + 1) * 4));
-    HIP_TRY(s->w_order.grow((size_t)B * 4));
+    sb.splits = std::max<u32>(1u, std::min<u32>(s->n_tiles, (4096u + B - 1) / B));
+    sb.bytes = im.bytes;
+    s->last.postings_visited = visited;
+    s->last.posting_bytes = visited * 4;
+    s->last.blocks = B * sb.splits;
+    return COS_OK;
+}
+
+// Launch: one copy of the staging image, then scan + finish, all on `st`; results to device pointers.  The two events bracket the
+// kernels on the stream they run on.  Nothing here synchronises.
+static int32_t sparse_launch(cos_sparse *s, const SparseBatch &sb, u32 *d_oi, float *d_os, u32 *d_oc, hipStream_t st) {
+    const u32 B = sb.B, R = sb.R, splits = sb.splits, Q = 1u << s->bits;
+    const SparseImage im(B, sb.nq);
+    HIP_TRY(s->w_in.grow(im.bytes));
     HIP_TRY(s->w_part.grow((size_t)B * splits * SEL * R * 8));
-    HIP_TRY(s->w_oi.grow((size_t)B * top_k * 4));
-    HIP_TRY(s->w_os.grow((size_t)B * top_k * 4));
-    HIP_TRY(s->w_oc.grow((size_t)B * 4));
-    const DevBuf &d_qd = s->w_qd, &d_qv = s->w_qv, &d_qo = s->w_qo, &d_terms = s->w_terms, &d_qt_off = s->w_qt_off, &d_order = s->w_order, &d_part = s->w_part,
-                 &d_oi = s->w_oi, &d_os = s->w_os, &d_oc = s->w_oc;
-    HIP_TRY(hipMemcpy(d_qd.p, q_dims, (size_t)nq * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_qv.p, q_vals, (size_t)nq * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_qo.p, q_offsets, ((size_t)B + 1) * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_terms.p, terms.data(), terms.size() * sizeof(STerm), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_qt_off.p, qt_off.data(), ((size_t)B + 1) * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_order.p, order.data(), (size_t)B * 4, hipMemcpyHostToDevice));
+    unsigned char *d = s->w_in.p;
+    const STerm *d_terms = (const STerm *)d;
+    const u32 *d_qd = (const u32 *)(d + im.qd), *d_qo = (const u32 *)(d + im.qo), *d_qt_off = (const u32 *)(d + im.qt_off), *d_order = (const u32 *)(d + im.order);
+    const float *d_qv = (const float *)(d + im.qv);
+    u64 *d_part = s->w_part.as<u64>();
+    HIP_TRY(hipMemcpyAsync(d, s->h_in.p, im.bytes, hipMemcpyHostToDevice, st));
     SparseDev dev{nullptr, nullptr, nullptr, s->d_row_off, s->d_raw_dims, s->d_raw_vals, s->T, Q, s->n, s->bits, s->upper};
-    HIP_TRY(hipEventRecord(s->ev0, 0));
+    HIP_TRY(hipEventRecord(s->ev0, st));
     if (R > 1) {
         auto wide = R == 2 ? sparse_launch_wide<2> : R == 4 ? sparse_launch_wide<4> : R == 8 ? sparse_launch_wide<8> : sparse_launch_wide<16>;
-        HIP_TRY(wide(s, dev, B, splits, d_terms.as<STerm>(), d_qt_off.as<u32>(), d_order.as<u32>(), d_part.as<u64>(), d_qd.as<u32>(), d_qv.as<float>(),
-                     d_qo.as<u32>(), top_k, kwr, rerank ? 1 : 0, d_oi.as<u32>(), d_os.as<float>(), d_oc.as<u32>()));
+        HIP_TRY(wide(s, dev, B, splits, d_terms, d_qt_off, d_order, d_part, d_qd, d_qv, d_qo, sb.top_k, sb.kwr, sb.rerank, d_oi, d_os, d_oc, st));
     } else {
         // eight postings per lane and step; sixteen measured the same (0.447 against 0.453 ms) and was dropped
         if (s->packed)
-            hipLaunchKernelGGL(sparse_packed_kernel<8>, dim3(B * splits), dim3(256), 0, 0, s->d_pk.p, d_terms.as<STerm>(), d_qt_off.as<u32>(), s->n, s->d_tile_dir.p,
-                               d_order.as<u32>(), splits, d_part.as<u64>());
+            hipLaunchKernelGGL(sparse_packed_kernel<8>, dim3(B * splits), dim3(256), 0, st, s->d_pk.p, d_terms, d_qt_off, s->n, s->d_tile_dir.p, d_order, splits, d_part);
         else
-            hipLaunchKernelGGL(sparse_tile_kernel<1>, dim3(B * splits), dim3(256), 0, 0, s->d_ids.p, s->d_keys.p, d_terms.as<STerm>(), d_qt_off.as<u32>(), s->n, s->d_tile_dir.p,
-                               d_order.as<u32>(), splits, d_part.as<u64>());
+            hipLaunchKernelGGL(sparse_tile_kernel<1>, dim3(B * splits), dim3(256), 0, st, s->d_ids.p, s->d_keys.p, d_terms, d_qt_off, s->n, s->d_tile_dir.p, d_order, splits,
+                               d_part);
         HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(sparse_finish_kernel, dim3(B), dim3(64), 0, 0, dev, d_part.as<u64>(), splits, d_qd.as<u32>(), d_qv.as<float>(), d_qo.as<u32>(), top_k, kwr,
-                           rerank ? 1 : 0, d_oi.as<u32>(), d_os.as<float>(), d_oc.as<u32>());
+        hipLaunchKernelGGL(sparse_finish_kernel, dim3(B), dim3(64), 0, st, dev, d_part, splits, d_qd, d_qv, d_qo, sb.top_k, sb.kwr, sb.rerank, d_oi, d_os, d_oc);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(s->ev1, 0));
-    HIP_TRY(hipMemcpy(out_ids, d_oi.p, (size_t)B * top_k * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_scores, d_os.p, (size_t)B * top_k * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_counts, d_oc.p, (size_t)B * 4, hipMemcpyDeviceToHost));
-    float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
-    s->last.kernel_ms = ms;
-    s->last.postings_visited = visited;
-    s->last.posting_bytes = visited * 4;
-    s->last.blocks = B * splits;
+    HIP_TRY(hipEventRecord(s->ev1, st));
+    s->stats_pending = true;
     return COS_OK;
+}
+
+// both parts, for a caller that holds s->mu (cos_sparse_search_batch_device, and the fused hybrid call through cosdev::sparse_search_locked)
+static int32_t sparse_search_on_stream(cos_sparse *s, const uint32_t *q_dims, const float *q_vals, const uint32_t *q_offsets, u32 B, u32 top_k,
+                                       float early_terminate_threshold, u32 reranking_factor, u32 *d_oi, float *d_os, u32 *d_oc, hipStream_t st) {
+    HIP_TRY(hipSetDevice(s->device));
+    int32_t rc = sparse_wait_previous(s);
+    if (rc) return rc;
+    SparseBatch sb;
+    rc = sparse_resolve(s, q_dims, q_vals, q_offsets, B, top_k, early_terminate_threshold, reranking_factor, sb);
+    if (rc) return rc;
+    return sparse_launch(s, sb, d_oi, d_os, d_oc, st);
+}
+
+namespace cosdev {
+std::mutex &sparse_mutex(cos_sparse *s) { return s->mu; }
+int32_t sparse_device(const cos_sparse *s) { return s->device; }
+void sparse_limits(const cos_sparse *s, u32 *max_candidates, bool *have_raw, u32 *batch_bound) {
+    *max_candidates = s->max_cand;
+    *have_raw = s->have_raw;
+    *batch_bound = SPK_COUNTED;
+}
+int32_t sparse_search_locked(cos_sparse *s, const uint32_t *q_dims, const float *q_vals, const uint32_t *q_offsets, u32 B, u32 top_k,
+                             float early_terminate_threshold, u32 reranking_factor, u32 *d_out_ids, float *d_out_scores, u32 *d_out_counts, hipStream_t st) {
+    return sparse_search_on_stream(s, q_dims, q_vals, q_offsets, B, top_k, early_terminate_threshold, reranking_factor, d_out_ids, d_out_scores, d_out_counts, st);
+}
+} // namespace cosdev
+
+extern "C" int32_t cos_sparse_search_batch_device(cos_sparse *s, const uint32_t *q_dims, const float *q_vals, const uint32_t *q_offsets, uint32_t B,
+                                                  uint32_t top_k, float early_terminate_threshold, uint32_t reranking_factor, uint32_t *d_out_ids,
+                                                  float *d_out_scores, uint32_t *d_out_counts, void *stream) {
+    if (!s || !q_dims || !q_vals || !q_offsets || !d_out_ids || !d_out_scores || !d_out_counts || B == 0 || top_k == 0) return cos_fail(COS_ERR_INVALID, "bad argument");
+    std::lock_guard<std::mutex> guard(s->mu);
+    return sparse_search_on_stream(s, q_dims, q_vals, q_offsets, B, top_k, early_terminate_threshold, reranking_factor, d_out_ids, d_out_scores, d_out_counts,
+                                   (hipStream_t)stream);
+}
+
+extern "C" int32_t cos_sparse_search_batch(cos_sparse *s, const uint32_t *q_dims, const float *q_vals, const uint32_t *q_offsets, uint32_t B, uint32_t top_k,
+                                           float early_terminate_threshold, uint32_t reranking_factor, uint32_t *out_ids, float *out_scores,
+                                           uint32_t *out_counts) {
+    if (!s || !q_dims || !q_vals || !q_offsets || !out_ids || !out_scores || !out_counts || B == 0 || top_k == 0) return cos_fail(COS_ERR_INVALID, "bad argument");
+    std::lock_guard<std::mutex> guard(s->mu);
+    int32_t rc = sparse_admit(s, B, top_k, reranking_factor); // (before the device is touched, as ever)
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(s->w_oi.grow((size_t)B * top_k * 4));
+    HIP_TRY(s->w_os.grow((size_t)B * top_k * 4));
+    HIP_TRY(s->w_oc.grow((size_t)B * 4));
+    // the host entry point launches where it always has: the default stream; its copies back wait for the kernels
+    rc = sparse_search_on_stream(s, q_dims, q_vals, q_offsets, B, top_k, early_terminate_threshold, reranking_factor, s->w_oi.as<u32>(), s->w_os.as<float>(),
+                                 s->w_oc.as<u32>(), 0);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(out_ids, s->w_oi.p, (size_t)B * top_k * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_scores, s->w_os.p, (size_t)B * top_k * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_counts, s->w_oc.p, (size_t)B * 4, hipMemcpyDeviceToHost));
+    return sparse_wait_previous(s); // (complete already: settles kernel_ms)
 }
 
 extern "C" int32_t cos_sparse_layout(cos_sparse *s, uint32_t *packed) {
@@ -1089,6 +1193,9 @@ extern "C" int32_t cos_sparse_max_candidates(cos_sparse *s, uint32_t *out) {
 extern "C" int32_t cos_sparse_last_stats(cos_sparse *s, cos_sparse_search_stats *out) {
     if (!s || !out) return cos_fail(COS_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> guard(s->mu);
+    HIP_TRY(hipSetDevice(s->device));
+    const int32_t rc = sparse_wait_previous(s); // a batch left on a stream by cos_sparse_search_batch_device: its time exists once it has run
+    if (rc) return rc;
     *out = s->last;
     return COS_OK;
 }
@@ -1539,7 +1646,7 @@ extern "C" int32_t cos_sparse_stats(cos_sparse *s, cos_sparse_index_stats *out) 
     out->raw_pairs = s->raw_nnz;
     u64 bytes = (u64)s->d_ids.cap * 4 + s->d_keys.cap + (u64)s->d_pk.cap * 4 + (u64)std::max<size_t>(s->d_tile_dir.cap, 1) * 4; // postings + directory
     bytes += (u64)s->d_row_off.cap * 8 + (u64)s->d_raw_dims.cap * 4 + (u64)s->d_raw_vals.cap * 4;                                 // raw vectors
-    for (const DevBuf *w : {&s->w_qd, &s->w_qv, &s->w_qo, &s->w_terms, &s->w_qt_off, &s->w_order, &s->w_part, &s->w_oi, &s->w_os, &s->w_oc}) bytes += w->cap; // search workspace
+    for (const DevBuf *w : {&s->w_in, &s->w_part, &s->w_oi, &s->w_os, &s->w_oc}) bytes += w->cap; // search workspace
     out->device_bytes = bytes;
     return COS_OK;
 }

@@ -3,6 +3,7 @@
     distance_batch      DistanceMetric::calculate            src/models/types.rs:469
     BM25Index           TFIDFIndex / search_bm25             src/indexes/tf_idf/mod.rs:243, src/models/sparse_ann_query.rs:149
     rrf_fuse_batch      RRF fusion of hybrid_search          src/api/vectordb/search/repo.rs:311-340
+    hybrid_search_mixed batch_hybrid_search, one arm per query   src/api/vectordb/search/repo.rs:343-555
 
 All numeric work runs in libcosdata_hip.so (gfx950 kernels); no CPU fallback.
 """
@@ -141,6 +142,87 @@ def hybrid_search_batch(index, bm25: "BM25Index", queries, q_terms, q_offsets, t
     return ids, sc, cnt
 
 
+ARM_DENSE_SPARSE, ARM_DENSE_BM25, ARM_SPARSE_BM25 = 0, 1, 2   # COS_HYBRID_*
+
+
+class HybridContext:
+    """What one mixed hybrid call keeps between calls (cos_hybrid): three streams, events, pinned staging, device buffers of the
+    three list sets.  One call at a time per context; threads that search concurrently hold one each."""
+
+    def __init__(self, device: int = 0):
+        self._h = C.c_void_p()
+        check(_lib.lib().cos_hybrid_create(device, C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            _lib.lib().cos_hybrid_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def hybrid_search_mixed(ctx: "HybridContext", index, sparse, bm25, arms, dense_queries, sparse_queries, bm25_queries, top_k: int,
+                        fusion_constant_k: float = 60.0, early_terminate_threshold: float = 0.0, reranking_factor: int = 0):
+    """repo::batch_hybrid_search in one call (cos_hybrid_search_mixed): arms[B] names every query's arm (ARM_DENSE_SPARSE,
+    ARM_DENSE_BM25, ARM_SPARSE_BM25); dense_queries [n_dense][dim], sparse_queries = (q_dims, q_vals, q_offsets) and
+    bm25_queries = (q_terms, q_offsets) hold the queries of the arms that have such a half, in query order.  A half without queries
+    takes None for its queries and may take None for its index.  Every half searches top_k * 3 on its own stream, RRF fuses each
+    query's two lists on the device.  -> ids [B][k], scores [B][k], counts [B]; entries past counts[q] keep 0xFFFFFFFF / 0."""
+    a = _c(arms, np.uint8).ravel()
+    B = a.size
+    rq = _lib.CosHybridRequest()
+    rq.struct_size = C.sizeof(_lib.CosHybridRequest)
+    rq.B = B
+    keep = [a]
+    rq.arm = a.ctypes.data
+    known = B == 0 or int(a.max()) <= ARM_SPARSE_BM25   # (an arm the library does not know is the library's to refuse)
+
+    def ptr(x, dt):
+        x = _c(x, dt)
+        keep.append(x)
+        return x.ctypes.data
+
+    if dense_queries is not None:
+        q = index._queries(dense_queries) if index is not None else _c(np.atleast_2d(dense_queries), np.float32)
+        n_dense = int(np.count_nonzero(a != ARM_SPARSE_BM25))
+        if known and q.shape[0] != n_dense:
+            raise ValueError(f"arms name {n_dense} queries with a dense half, dense_queries holds {q.shape[0]}")
+        rq.dense_queries = ptr(q, np.float32)
+    if sparse_queries is not None:
+        qd, qv, qo = sparse_queries
+        rq.sparse_dims, rq.sparse_vals, rq.sparse_offsets = ptr(qd, np.uint32), ptr(qv, np.float32), ptr(qo, np.uint32)
+        n_sparse = int(np.count_nonzero(a != ARM_DENSE_BM25))
+        if known and (keep[-1].size != n_sparse + 1 or keep[-3].size != keep[-2].size or keep[-3].size < int(keep[-1].max(initial=0))):
+            raise ValueError(f"arms name {n_sparse} queries with a sparse half: q_offsets must hold {n_sparse + 1} entries inside q_dims / q_vals")
+    if bm25_queries is not None:
+        qt, qo = bm25_queries
+        rq.bm25_terms, rq.bm25_offsets = ptr(qt, np.uint32), ptr(qo, np.uint32)
+        n_bm25 = int(np.count_nonzero(a != ARM_DENSE_SPARSE))
+        if known and (keep[-1].size != n_bm25 + 1 or keep[-2].size < int(keep[-1].max(initial=0))):
+            raise ValueError(f"arms name {n_bm25} queries with a BM25 half: q_offsets must hold {n_bm25 + 1} entries inside q_terms")
+    rq.sparse_early_terminate_threshold = early_terminate_threshold
+    rq.sparse_reranking_factor = reranking_factor
+    rq.top_k = top_k
+    rq.fusion_constant_k = fusion_constant_k
+    ids = np.full((B, max(top_k, 1)), 0xFFFFFFFF, np.uint32)
+    sc = np.zeros((B, max(top_k, 1)), np.float32)
+    cnt = np.zeros(max(B, 1), np.uint32)
+    check(_lib.lib().cos_hybrid_search_mixed(ctx._h, index._h if index is not None else None, sparse._h if sparse is not None else None,
+                                             bm25._h if bm25 is not None else None, C.byref(rq), _p(ids), _p(sc), _p(cnt)))
+    return ids, sc, cnt[:B]
+
+
 class InvertedIndex:
     """Device-resident learned-sparse inverted index (src/indexes/inverted/mod.rs, src/models/inverted_index.rs) as CSR:
     dims ascending, key_offsets [T][2^bits + 1], vec_ids; optional raw sparse vectors (CSR) for the raw-value rerank."""
@@ -192,8 +274,19 @@ class InvertedIndex:
         return ids, scores, counts
 
 
+def _sparse_search_batch_device(self, q_dims, q_vals, q_offsets, top_k: int, out_ids_ptr: int, out_scores_ptr: int, out_counts_ptr: int,
+                                early_terminate_threshold: float = 0.0, reranking_factor: int = 0, stream: int = 0):
+    """same search, results left in device memory ([B][k] ids, [B][k] scores, [B] counts); enqueued on `stream`, not synchronised"""
+    qd, qv, qo = _c(q_dims, np.uint32), _c(q_vals, np.float32), _c(q_offsets, np.uint32)
+    check(_lib.lib().cos_sparse_search_batch_device(self._h, _p(qd), _p(qv), _p(qo), qo.size - 1, top_k, early_terminate_threshold, reranking_factor,
+                                                    C.c_void_p(out_ids_ptr), C.c_void_p(out_scores_ptr), C.c_void_p(out_counts_ptr), C.c_void_p(stream)))
+
+
+InvertedIndex.search_batch_device = _sparse_search_batch_device
+
+
 def _sparse_last_stats(self):
-    """kernel time + visited postings of the most recent search_batch on this handle"""
+    """kernel time + visited postings of the most recent search_batch / search_batch_device on this handle"""
     st = _lib.CosSparseStats()
     check(_lib.lib().cos_sparse_last_stats(self._h, C.byref(st)))
     return st

@@ -615,6 +615,76 @@ int32_t cos_sparse_stats(cos_sparse *s, cos_sparse_index_stats *out);
 int32_t cos_sparse_download(cos_sparse *s, uint32_t *n_dims, uint64_t *n_postings, uint32_t *dims, uint64_t *key_offsets,
                             uint32_t *vec_ids);
 
+/* ---- hybrid search, all three arms, mixed per query --------------------------------------------
+ * repo::batch_hybrid_search (api/vectordb/search/repo.rs:343-555) in one call: every query of the request names its own arm,
+ * the queries are split into a dense, a learned-sparse and a BM25 sub-batch, the three batch searches run side by side on three
+ * streams of one device, each for top_k * 3 and only for its own sub-batch (a DENSE_BM25 query costs no sparse work), and every
+ * query's two lists are fused with RRF on the device; only the fused top_k crosses PCIe.  The library builds the reference's
+ * query_mapping itself (:366-419): a query's lists are the next free rows of the sub-batches it joins, in request order.
+ *
+ * Lists: the FIRST and SECOND list of an arm are (dense, sparse), (dense, BM25) and (sparse, BM25).  The order matters: an id's
+ * score from the first list is overwritten by a later occurrence of the id in the first list (`insert`), second-list scores
+ * are added (:524-537).  score = 1 / (rank as f32 + fusion_constant_k + f32::EPSILON) in f32.  Output: fused score descending
+ * (total_cmp), larger id first on ties, truncated to top_k; entries past out_counts[q] are NOT written.
+ *
+ * Shared id space: fusion is on the u32 ids the three searches return (dense ids include id_base).  The three indexes of a
+ * collection share ONE internal id space — document id = vector id = id_base + dense internal id — as cos_hybrid_search_batch
+ * already assumes; the library cannot check it.
+ *
+ * Sparse threshold: one per call.  batch_hybrid_search drops the per-query threshold and passes None, which becomes the
+ * config default (:447, indexes/inverted/mod.rs:296-297).  The single-query hybrid_search (:168-341), which does take a
+ * threshold, is this call with B = 1.
+ *
+ * Handles: a handle whose sub-batch is empty may be NULL; one that is needed and NULL, handles on different devices or on a
+ * device other than h's are COS_ERR_INVALID.  Locks are taken in the order cos_hybrid -> cos_sparse -> cos_bm25 and each is held
+ * until the call's one synchronisation, so searches and updates on the same handles from other threads run before or after.
+ *
+ * Refused before anything is enqueued, every handle staying usable: top_k > 170 (3 * top_k > 512: BM25 keeps 512 buckets per
+ * query, the fusion holds two lists of at most 1024 ids together) -> COS_ERR_UNIMPLEMENTED; 3 * top_k * max(reranking_factor, 1)
+ * above the sparse handle's cos_sparse_set_max_candidates -> COS_ERR_UNIMPLEMENTED; a rerank on a sparse handle without raw
+ * vectors -> COS_ERR_NOT_READY; B == 0, top_k == 0, an arm above 2, decreasing offsets, a small struct_size -> COS_ERR_INVALID;
+ * a sparse sub-batch at or above cos_sparse_search_batch's own bound on B is refused as that call refuses it.
+ * A failing dense query (zero norm -> COS_ERR_CALCULATION) fails the call like cos_hybrid_search_batch: the status of the first
+ * failing query in request order is returned, and the next call on the same handles answers. */
+typedef struct cos_hybrid cos_hybrid;   /* streams, events, pinned staging and device buffers of the fused call; one call at a time */
+int32_t cos_hybrid_create(int32_t device, cos_hybrid **out);
+int32_t cos_hybrid_destroy(cos_hybrid *h);
+
+enum { COS_HYBRID_DENSE_SPARSE = 0, COS_HYBRID_DENSE_BM25 = 1, COS_HYBRID_SPARSE_BM25 = 2 };
+
+typedef struct cos_hybrid_request {
+    uint32_t struct_size;               /* sizeof(cos_hybrid_request) */
+    uint32_t B;                         /* queries of the request */
+    const uint8_t *arm;                 /* [B] COS_HYBRID_* */
+    const float *dense_queries;         /* [n_dense][dim]: vectors of the queries whose arm has a dense half, in query order */
+    const uint32_t *sparse_dims;        /* CSR over the n_sparse queries whose arm has a sparse half, in query order: */
+    const float *sparse_vals;           /*   pairs [sparse_offsets[i], sparse_offsets[i+1]) of sparse query i               */
+    const uint32_t *sparse_offsets;     /*   [n_sparse + 1] */
+    const uint32_t *bm25_terms;         /* CSR over the n_bm25 queries whose arm has a BM25 half, in query order: hashed terms */
+    const uint32_t *bm25_offsets;       /*   [n_bm25 + 1] */
+    float sparse_early_terminate_threshold; /* one per call, as cos_sparse_search_batch takes it */
+    uint32_t sparse_reranking_factor;   /* 0 = no raw-value rerank */
+    uint32_t top_k;
+    float fusion_constant_k;            /* dtos.rs:10-12, default 60 */
+} cos_hybrid_request;
+
+/* n_dense, n_sparse and n_bm25 are what arm[] implies; the arrays of a half without queries may be NULL.  Host outputs:
+ * out_ids / out_scores [B][top_k], out_counts [B]. */
+int32_t cos_hybrid_search_mixed(cos_hybrid *h, cos_index *ix, cos_sparse *sp, cos_bm25 *bm, const cos_hybrid_request *rq,
+                                uint32_t *out_ids, float *out_scores, uint32_t *out_counts);
+
+/* cos_sparse_search_batch with the results left in DEVICE memory (d_out_ids / d_out_scores [B][top_k], d_out_counts [B]) and the
+ * copies and kernels enqueued on `stream` (NULL = the default stream, where cos_sparse_search_batch launches) without
+ * synchronising it: the sparse half of a hybrid batch runs beside the other halves and feeds the fusion without a round trip.
+ * The query CSR is host memory (find_node, the quantization and the early-termination rule use host tables); it is resolved into
+ * pinned staging the handle owns, so the caller's arrays are free as soon as the call returns.  One batch is in flight per handle:
+ * a call waits for the handle's previous batch (an event) before it overwrites the staging or the workspace, and holds the
+ * handle's lock while the host tables are read.  Same limits and statuses as cos_sparse_search_batch; cos_sparse_last_stats
+ * afterwards waits for the batch and reports it. */
+int32_t cos_sparse_search_batch_device(cos_sparse *s, const uint32_t *q_dims, const float *q_vals, const uint32_t *q_offsets, uint32_t B,
+                                       uint32_t top_k, float early_terminate_threshold, uint32_t reranking_factor,
+                                       uint32_t *d_out_ids, float *d_out_scores, uint32_t *d_out_counts, void *stream);
+
 /* ---- multi-GPU helper ----------------------------------------------------------------------- */
 /* S-way merge of per-shard top-k lists gathered by the caller's RCCL all-gather
  * (SURVEY.md §8e): in [S][B][k] -> out [B][k], total_cmp desc, larger id first on ties.
