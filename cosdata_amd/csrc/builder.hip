@@ -627,7 +627,8 @@ extern "C" int32_t cos_index_delete(cos_index *ix, const uint32_t *ids, uint32_t
     VisTab vtab;
     std::vector<u32> h_ids((size_t)L1 * KEEP), h_nodes((size_t)L1 * KEEP), h_counts(L1), h_dn(L1), h_ust(L1);
     std::vector<std::vector<u32>> node_vec(L1); // slow path only: node -> vector row, fetched once per level
-    // (the locality order stays a permutation of the level's nodes and the level table's operand holds code rows: both still valid)
+    // (the locality order stays a permutation of the level's nodes and the level table's operand holds code rows: both still valid —
+    // tests/test_gpu_mutation_coherence.py searches a warm handle with both after every delete, against a handle that never had them)
     ix->adj_mag_valid = false;
     for (auto &l : ix->lv) { l.host_valid = false; l.nbr_ids.clear(); }
 
