@@ -1,4 +1,4 @@
-// Shared between kernels_flat.hip (host flow, tile kernel) and kernels_scan.hip (query-resident quaternary scan kernel).
+// Shared between kernels_flat.hip (host flow, tile kernel) and kernels_scan.hip (query-resident scan kernels).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -16,16 +16,21 @@ struct FusedOut {
     u64 *app;         // [B][cap]
     u32 *app_cnt;     // [B]
     u32 cap;
-    const uint8_t *qdigits; // ENG_Q2: [B][kdims] pre-expanded query digits (expand_q2_digits_kernel)
+    const uint8_t *qdigits; // bit-plane codes (binary, quaternary, octal): [B][kdims] pre-expanded query digits (expand_digits_kernel)
 };
 
 
-// query-resident quaternary scan (kernels_scan.hip)
+// query-resident scan of bit-plane codes (kernels_scan.hip): eng = ENG_Q1 (binary), ENG_Q2 (quaternary) or ENG_Q3 (octal); kdims = the
+// dims multiplied, a multiple of 64 (a 16-byte chunk of a row holds 128, 64 or 32 of them)
 bool flat_scan_supported(u32 kdims);
+// the same per storage: octal codes of 16 digit chunks (993..1024 dims) stay on the tile kernel — their i8 kernel holds 256 AccVGPRs of
+// query fragments and six raw dwords per staged chunk, spills, and measured slower than the tile kernel
+bool flat_scan_supported(int eng, u32 kdims);
 // queries' planes -> permuted digit bytes [B][kdims] (the layout the scan kernel multiplies)
-// (fp4: the operands as e2m1 nibbles for the scaled MFMA — flat_scan_q2_fp4 — instead of i8 digits; the buffer is half as long)
-hipError_t launch_flat_scan_expand_queries(const uint8_t *qcodes, u64 row_stride, u32 B, u32 kdims, uint8_t *digits, hipStream_t st, bool fp4);
-hipError_t launch_flat_scan(u32 kdims, u32 n_cus, hipStream_t st, const uint8_t *qdig, const float *qmags, u32 B, const uint8_t *codes,
+// (fp4, binary and quaternary: the operands as e2m1 nibbles for the scaled MFMA — flat_scan_q2_fp4 — instead of i8 digits; the buffer is
+// half as long.  Octal digits 5 and 7 have no e2m1 code: i8 only)
+hipError_t launch_flat_scan_expand_queries(int eng, const uint8_t *qcodes, u64 row_stride, u32 B, u32 kdims, uint8_t *digits, hipStream_t st, bool fp4);
+hipError_t launch_flat_scan(int eng, u32 kdims, u32 n_cus, hipStream_t st, const uint8_t *qdig, const float *qmags, u32 B, const uint8_t *codes,
                             const float *mags, u64 row_stride, u32 n0, u32 nc, u32 metric, const FusedOut &fo, bool fp4);
 
 // the same for u8 codes (flat_scan_u8_areg): qcodes = the queries' code rows [B][kdims], qsums / csums = code sums; rows must be exactly kdims bytes

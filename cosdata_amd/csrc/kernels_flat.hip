@@ -334,6 +334,9 @@ __global__ __launch_bounds__(64) void flat_rescore(const float *__restrict__ Q, 
 //   quaternary : the two bit planes are expanded to the digit (plane0 bit + 2 * plane1 bit), i.e. exactly the
 //                value dot_product_quaternary multiplies (dot_product.rs:35-57), 4 digits per u32 via
 //                (nibble * 0x00204081) & 0x01010101
+//   binary     : the digit is the bit of the row's one plane, 128 dims per 16-byte chunk (dot_product_binary, dot_product.rs:21-33)
+//   octal      : three planes of 32 dims per 16-byte chunk [plane0 | plane1 | plane2 | 0]; digit = p0 + 2 p1 + 4 p2 on the planes as
+//                stored (dot_product_octal, dot_product.rs:64-90; chunk_dot<ENG_Q3> has the quirk).  Accumulators stay below 49 * dim
 // A/B fragments are read K-contiguous (16 B per lane, k-block = lane >> 5) for both operands, so the result is
 // the plain sum over k whatever the hardware's internal k order is; C/D layout as in flat_gemm_f32.
 // Workgroup = 8 waves, tile 256 queries x 128 candidates, K step 64; rows padded to 80 B in LDS (conflict-free
@@ -351,14 +354,37 @@ template <int ENG>
 __device__ __forceinline__ uint4 load16_raw(const uint8_t *__restrict__ row, u32 k0 /*multiple of 16*/, bool valid) {
     if (!valid) return make_uint4(0, 0, 0, 0);
     if constexpr (ENG == ENG_U8) return *(const uint4 *)(row + k0);
+    else if constexpr (ENG == ENG_Q1) return *(const uint4 *)(row + (u64)(k0 >> 7) * 16); // 16 B per 128 dims: the one plane
+    else if constexpr (ENG == ENG_Q3) return *(const uint4 *)(row + (u64)(k0 >> 5) * 16); // 16 B per 32 dims: [plane0 4 B | plane1 4 B | plane2 4 B | 0]
     else return *(const uint4 *)(row + (u64)(k0 >> 6) * 16); // 16 B per 64 dims: [plane0 8 B | plane1 8 B]
 }
+// dims that one 16-byte chunk of a code row covers
+template <int ENG>
+constexpr u32 chunk_dims() { return ENG == ENG_U8 ? 16u : ENG == ENG_Q1 ? 128u : ENG == ENG_Q3 ? 32u : 64u; }
 template <int ENG>
 __device__ __forceinline__ uint4 unpack16(uint4 raw, u32 k0, bool valid) {
     uint4 o = make_uint4(0, 0, 0, 0);
     if constexpr (ENG == ENG_U8) {
         o = raw;
         o.x ^= 0x80808080u; o.y ^= 0x80808080u; o.z ^= 0x80808080u; o.w ^= 0x80808080u; // padding (0) becomes -128 too: see epilogue
+    } else if constexpr (ENG == ENG_Q1) { // binary: the digit is the bit (dot_product_binary, dot_product.rs:21-33)
+        if (valid) {
+            const u32 sh = k0 & 127, wd = sh >> 5;
+            const u32 b0 = ((wd == 0 ? raw.x : wd == 1 ? raw.y : wd == 2 ? raw.z : raw.w) >> (sh & 31)) & 0xFFFFu;
+            o.x = spread4(b0 & 15u);
+            o.y = spread4((b0 >> 4) & 15u);
+            o.z = spread4((b0 >> 8) & 15u);
+            o.w = spread4((b0 >> 12) & 15u);
+        }
+    } else if constexpr (ENG == ENG_Q3) { // octal: p0 + 2 p1 + 4 p2 on the planes as stored (dot_product_octal, dot_product.rs:64-90; chunk_dot<ENG_Q3>)
+        if (valid) {
+            const u32 sh = k0 & 31;
+            const u32 b0 = (raw.x >> sh) & 0xFFFFu, b1 = (raw.y >> sh) & 0xFFFFu, b2 = (raw.z >> sh) & 0xFFFFu;
+            o.x = spread4(b0 & 15u) + 2u * spread4(b1 & 15u) + 4u * spread4(b2 & 15u);
+            o.y = spread4((b0 >> 4) & 15u) + 2u * spread4((b1 >> 4) & 15u) + 4u * spread4((b2 >> 4) & 15u);
+            o.z = spread4((b0 >> 8) & 15u) + 2u * spread4((b1 >> 8) & 15u) + 4u * spread4((b2 >> 8) & 15u);
+            o.w = spread4((b0 >> 12) & 15u) + 2u * spread4((b1 >> 12) & 15u) + 4u * spread4((b2 >> 12) & 15u);
+        }
     } else {
         if (valid) {
             const u32 sh = k0 & 63;
@@ -377,15 +403,16 @@ __device__ __forceinline__ uint4 stage16(const uint8_t *__restrict__ row, u32 k0
     return unpack16<ENG>(load16_raw<ENG>(row, k0, valid), k0, valid);
 }
 
-// queries' quaternary planes -> the i8 digits the GEMM multiplies, once per batch ([B][kdims] bytes): the scan kernel then
-// stages the query operand with plain 16 B copies instead of re-expanding it for every one of the N / 128 candidate tiles
-__global__ void expand_q2_digits_kernel(const uint8_t *__restrict__ qcodes, u64 row_stride, u32 B, u32 kdims, uint8_t *__restrict__ digits) {
+// queries' bit planes (binary, quaternary, octal) -> the i8 digits the GEMM multiplies, once per batch ([B][kdims] bytes): the scan kernel
+// then stages the query operand with plain 16 B copies instead of re-expanding it for every one of the N / 128 candidate tiles
+template <int ENG>
+__global__ void expand_digits_kernel(const uint8_t *__restrict__ qcodes, u64 row_stride, u32 B, u32 kdims, uint8_t *__restrict__ digits) {
     const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     const u32 pieces = kdims / 16;
     if (t >= (u64)B * pieces) return;
     const u32 q = (u32)(t / pieces), k0 = (u32)(t % pieces) * 16;
-    const u32 code_k = (u32)(row_stride / 16) * 64;
-    *(uint4 *)(digits + (u64)q * kdims + k0) = stage16<ENG_Q2>(qcodes + (u64)q * row_stride, k0, k0 < code_k);
+    const u32 code_k = (u32)(row_stride / 16) * chunk_dims<ENG>();
+    *(uint4 *)(digits + (u64)q * kdims + k0) = stage16<ENG>(qcodes + (u64)q * row_stride, k0, k0 < code_k);
 }
 
 template <int ENG, bool FUSED, int PF>
@@ -406,7 +433,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         for (int j = 0; j < 2; j++)
 #pragma unroll
             for (int r = 0; r < 16; r++) acc[i][j][r] = 0;
-    const u32 code_k = ENG == ENG_U8 ? (u32)row_stride : (u32)(row_stride / 16) * 64; // dims covered by stored bytes
+    const u32 code_k = ENG == ENG_U8 ? (u32)row_stride : (u32)(row_stride / 16) * chunk_dims<ENG>(); // dims covered by stored bytes
     // Register ring of PF k panels: the 16 B pieces of panels k+1 .. k+PF are in flight (global -> VGPR) while panel k is
     // unpacked into LDS and multiplied.  With only 2 workgroups per CU the un-prefetched loop exposed the full HBM latency on
     // every panel (0.21 of the MFMA peak); the ring hides it behind PF panels of MFMA work per workgroup.
@@ -420,7 +447,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 #pragma unroll
         for (int h = 0; h < 2; h++) {
             const u32 qr = row0 + ar[h];
-            if constexpr (FUSED && ENG == ENG_Q2)
+            if constexpr (FUSED && ENG != ENG_U8)
                 ra[s][h] = qr < B ? *(const uint4 *)(fo.qdigits + (u64)qr * kdims + k0 + akq[h]) : make_uint4(0, 0, 0, 0);
             else
                 ra[s][h] = load16_raw<ENG>(qcodes + (u64)(qr < B ? qr : 0) * row_stride, k0 + akq[h], qr < B && k0 + akq[h] < code_k);
@@ -437,7 +464,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             if (k0 >= kdims) break; // uniform
 #pragma unroll
             for (int h = 0; h < 2; h++) {
-                if constexpr (FUSED && ENG == ENG_Q2)
+                if constexpr (FUSED && ENG != ENG_U8)
                     *(uint4 *)(As + ar[h] * CLD + akq[h]) = ra[s][h];
                 else
                     *(uint4 *)(As + ar[h] * CLD + akq[h]) = unpack16<ENG>(ra[s][h], k0 + akq[h], row0 + ar[h] < B && k0 + akq[h] < code_k);
@@ -467,7 +494,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             const u32 row = row0 + idx;
             const u64 k = row < B ? fo.thr[row] : ~0ull;
             thr_key[idx] = k;
-            thr_lo[idx] = k == 0ull ? -1.0f : simkey_inv((u32)(k >> 32)) * (1.0f - 4e-6f); // scores of u8 / quaternary codes are >= 0
+            thr_lo[idx] = k == 0ull ? -1.0f : simkey_inv((u32)(k >> 32)) * (1.0f - 4e-6f); // scores of u8 / bit-plane codes are >= 0
             rq[idx] = row < B ? __builtin_amdgcn_rcpf(qmags[row]) : 0.0f;
         }
         __syncthreads();
@@ -729,7 +756,9 @@ void cos_flat_ws_release(cos_index *ix) { // cos_index_destroy, and every upload
 }
 
 // ------------------------------------------------------------------------------------------------
-// cos_flat_search_batch: exhaustive search over the index's quantized codes (i8 MFMA) + exact rerank of the best 5k
+// cos_flat_search_batch: exhaustive search over the index's quantized codes (i8 MFMA) + exact rerank of the best 5k.
+// u8 and the three bit-plane storages (binary, quaternary, octal): integer dots, exact in any order.  f16 / f32 codes are refused: their
+// reference dots are order-dependent f32 chains that an MFMA cannot reproduce, so the candidate set could not be exact.
 // ------------------------------------------------------------------------------------------------
 extern "C" int32_t cos_flat_search_batch(cos_index *ix, const float *queries, uint32_t B, uint32_t top_k, uint32_t *out_ids, float *out_scores,
                                          uint32_t *out_counts, cos_flat_stats *stats) {
@@ -739,11 +768,15 @@ extern "C" int32_t cos_flat_search_batch(cos_index *ix, const float *queries, ui
     // survivors per query: the smallest pool that holds the 5 * top_k rerank candidates (64 for top_k <= 12, as ever).  Every buffer
     // below is sized and indexed by this call's P, not by the widest call the handle has served.
     const u32 P = flat_pool_width(5 * top_k), R = P / SEL;
-    if (ix->eng != ENG_U8 && ix->eng != ENG_Q2) return cos_fail(COS_ERR_UNIMPLEMENTED, "flat search over codes implements u8 and quaternary storage");
+    const bool planes = ix->eng == ENG_Q1 || ix->eng == ENG_Q2 || ix->eng == ENG_Q3; // bit-plane storage: the operands are expanded to digits
+    if (ix->eng != ENG_U8 && !planes)
+        return cos_fail(COS_ERR_UNIMPLEMENTED, "flat search over codes implements u8, binary, quaternary and octal storage");
     int32_t rc = cos_set_device(ix);
     if (rc) return rc;
     const u32 dim = ix->p.dim, n = ix->n;
-    const u32 kdims = ix->eng == ENG_U8 ? (u32)((ix->row_stride + 63) / 64 * 64) : (u32)(ix->row_stride / 16) * 64;
+    // dims the GEMM multiplies, a multiple of 64: a 16-byte chunk holds 128 binary, 64 quaternary or 32 octal dims
+    const u32 chunk_k = ix->eng == ENG_Q1 ? 128u : ix->eng == ENG_Q3 ? 32u : 64u;
+    const u32 kdims = ix->eng == ENG_U8 ? (u32)((ix->row_stride + 63) / 64 * 64) : ((u32)(ix->row_stride / 16) * chunk_k + 63) / 64 * 64;
     // Scan schedule.  The first candidates (SEED of them) go through the unfused path — score matrix + segmented selection —
     // and seed every query's threshold; from then on chunks grow 8x (128 K, 1 M, 4 M ...) and the fused GEMM appends only what
     // beats the threshold: a chunk 8x the size of everything seen before lets ~64 * 8 entries per query through, an eighth of
@@ -754,9 +787,10 @@ extern "C" int32_t cos_flat_search_batch(cos_index *ix, const float *queries, ui
     // eighth of the capacity again (flat_scan.h flat_growth / flat_app_cap).
     const bool allow_fused = tune_or(TUNE_FLAT_UNFUSED, 0) == 0;
     const int pf = (int)tune_or(TUNE_FLAT_PF, 1); // k panels prefetched into registers (1..3); results do not depend on it
-    // fused chunks of quaternary codes run on the query-resident kernel when K has an instantiation (tuning knob flat_tile_kernel = 1: never)
-    const bool use_areg = ix->eng == ENG_Q2 && flat_scan_supported(kdims) && tune_or(TUNE_FLAT_TILE_KERNEL, 0) == 0;
-    const bool use_fp4 = use_areg && tune_or(TUNE_FLAT_FP4, 1) != 0; // e2m1 digits on the scaled MFMA (kernels_scan.hip flat_scan_q2_fp4); 0 = i8 digits
+    // fused chunks of bit-plane codes run on the query-resident kernel when K has an instantiation (tuning knob flat_tile_kernel = 1: never)
+    const bool use_areg = planes && flat_scan_supported(ix->eng, kdims) && tune_or(TUNE_FLAT_TILE_KERNEL, 0) == 0;
+    // e2m1 digits on the scaled MFMA (kernels_scan.hip flat_scan_q2_fp4); 0 = i8 digits.  Octal digits (0..7) have no e2m1 form: i8 always
+    const bool use_fp4 = use_areg && ix->eng != ENG_Q3 && tune_or(TUNE_FLAT_FP4, 1) != 0;
     // fused chunks of u8 codes too (round 6: flat_scan_u8_areg), when a row is exactly a supported number of 64-byte chunks
     const bool use_u8q = ix->eng == ENG_U8 && ix->row_stride == (u64)kdims && flat_scan_supported(kdims) && tune_or(TUNE_FLAT_TILE_KERNEL, 0) == 0; // (1024 dims: 32 query rows per wave instead of 64)
     int n_cus = 0;
@@ -819,11 +853,14 @@ extern "C" int32_t cos_flat_search_batch(cos_index *ix, const float *queries, ui
                 }
                 e = hipGetLastError();
             }
-            if (e == hipSuccess && ix->eng == ENG_Q2) {
+            if (e == hipSuccess && planes) {
                 const u64 pieces = (u64)B * (kdims / 16);
-                hipLaunchKernelGGL(expand_q2_digits_kernel, dim3((u32)((pieces + 255) / 256)), dim3(256), 0, st, d_qc, ix->row_stride, B, kdims, d_qd);
+                const dim3 eg((u32)((pieces + 255) / 256));
+                if (ix->eng == ENG_Q2) hipLaunchKernelGGL(expand_digits_kernel<ENG_Q2>, eg, dim3(256), 0, st, d_qc, ix->row_stride, B, kdims, d_qd);
+                else if (ix->eng == ENG_Q1) hipLaunchKernelGGL(expand_digits_kernel<ENG_Q1>, eg, dim3(256), 0, st, d_qc, ix->row_stride, B, kdims, d_qd);
+                else hipLaunchKernelGGL(expand_digits_kernel<ENG_Q3>, eg, dim3(256), 0, st, d_qc, ix->row_stride, B, kdims, d_qd);
                 e = hipGetLastError();
-                if (e == hipSuccess && use_areg) e = launch_flat_scan_expand_queries(d_qc, ix->row_stride, B, kdims, d_qdp, st, use_fp4);
+                if (e == hipSuccess && use_areg) e = launch_flat_scan_expand_queries(ix->eng, d_qc, ix->row_stride, B, kdims, d_qdp, st, use_fp4);
             }
             // zero-norm screening (cosine): the reference aborts a search on the first zero denominator it meets; an
             // exhaustive scan meets every vector, so any zero |q| or zero |v| is a CalculationError for the call.
@@ -871,15 +908,19 @@ extern "C" int32_t cos_flat_search_batch(cos_index *ix, const float *queries, ui
 #define FLAT_LAUNCH(E, F, P) hipLaunchKernelGGL((flat_codes_gemm_i8<E, F, P>), grid, dim3(512), 0, st, FLAT_ARGS)
 #define FLAT_LAUNCH_PF(E, F) do { if (pf == 2) FLAT_LAUNCH(E, F, 2); else if (pf == 3) FLAT_LAUNCH(E, F, 3); else FLAT_LAUNCH(E, F, 1); } while (0)
             if (use_fused && use_areg) {
-                e = launch_flat_scan(kdims, (u32)n_cus, st, d_qdp, d_qm, B, ix->d_codes, ix->d_mags, ix->row_stride, n0, nc, ix->p.metric, fo, use_fp4);
+                e = launch_flat_scan(ix->eng, kdims, (u32)n_cus, st, d_qdp, d_qm, B, ix->d_codes, ix->d_mags, ix->row_stride, n0, nc, ix->p.metric, fo, use_fp4);
                 if (e != hipSuccess) break;
             } else if (use_fused && use_u8q) {
                 e = launch_flat_scan_u8(kdims, (u32)n_cus, st, d_qc, d_qs, d_qm, B, ix->d_codes, d_cs, ix->d_mags, ix->row_stride, n0, nc, ix->p.metric, fo);
                 if (e != hipSuccess) break;
             } else if (ix->eng == ENG_U8) {
                 if (use_fused) FLAT_LAUNCH_PF(ENG_U8, true); else FLAT_LAUNCH_PF(ENG_U8, false);
-            } else {
+            } else if (ix->eng == ENG_Q2) {
                 if (use_fused) FLAT_LAUNCH_PF(ENG_Q2, true); else FLAT_LAUNCH_PF(ENG_Q2, false);
+            } else if (ix->eng == ENG_Q1) {
+                if (use_fused) FLAT_LAUNCH_PF(ENG_Q1, true); else FLAT_LAUNCH_PF(ENG_Q1, false);
+            } else {
+                if (use_fused) FLAT_LAUNCH_PF(ENG_Q3, true); else FLAT_LAUNCH_PF(ENG_Q3, false);
             }
 #undef FLAT_LAUNCH_PF
 #undef FLAT_LAUNCH
@@ -1011,7 +1052,7 @@ hipError_t launch_level_table(int eng, const uint8_t *qcodes, const float *qmags
     hipError_t e = hipSuccess;
     if (level_table_gemm_queue(eng, row_stride)) {
         if (q2 && first) { // the queries' planes -> the permuted i8 digit rows the kernel keeps resident
-            e = launch_flat_scan_expand_queries(qcodes, row_stride, B, kdims, qdig, st, false);
+            e = launch_flat_scan_expand_queries(ENG_Q2, qcodes, row_stride, B, kdims, qdig, st, false);
             if (e != hipSuccess) return e;
         }
         // (one workgroup per CU; on half the CUs — so that the previous launch's walk keeps the other half — the GEMM takes 1.31 instead

@@ -1,4 +1,4 @@
-// Query-resident scan of quaternary codes: its own translation unit because it is compiled with
+// Query-resident scans of bit-plane (binary, quaternary, octal) and u8 codes: their own translation unit because it is compiled with
 // -mllvm -amdgpu-mfma-vgpr-form=1 (MFMA accumulators in VGPRs, query fragments usable straight from AccVGPRs; see areg_mfma).
 #include <hip/hip_runtime.h>
 
@@ -50,14 +50,88 @@ __device__ __forceinline__ uint4 q2_piece_perm(uint4 raw, int pp) {
     return make_uint4(q2_dword_perm(raw, pp, 0), q2_dword_perm(raw, pp, 1), q2_dword_perm(raw, pp, 2), q2_dword_perm(raw, pp, 3));
 }
 
+
+// ------------------------------------------------------------------------------------------------
+// The three bit-plane storages on ONE kernel family.  The kernels below multiply chunks of 64 digits; what differs between binary,
+// quaternary and octal codes is only where the planes of such a chunk sit in a stored row and how they become digits:
+//   quaternary  one 16-byte chunk of the row [plane0 8 B | plane1 8 B]; digit = p0 + 2 p1 (q2_dword_perm / q2_nibble_dword above)
+//   binary      half a 16-byte chunk (the row's one plane, 128 dims per chunk): a quaternary chunk whose plane 1 is absent; digit = the bit
+//   octal       TWO 16-byte chunks [plane0 4 B | plane1 4 B | plane2 4 B | 0] of 32 dims each; digit = p0 + 2 p1 + 4 p2 on the planes as
+//               stored (chunk_dot<ENG_Q3>, dot_engines.h).  A row with an odd number of chunks ends in half a digit chunk: zeros.
+// ScanRow<ENG>::Raw is what a lane keeps in registers between the global load and the expansion (4, 2 or 6 dwords), digit_dword /
+// nibble_dword produce dword jj of 16-byte piece pp of the chunk's i8 / e2m1 operand — the SAME dim permutation inside a chunk for every
+// storage and for both operands of the product, so the sum does not see it.  e2m1 holds 0, 0.5, 1, 1.5 (and 2, 3, 4, 6): binary and
+// quaternary digits fit as d / 2, octal 5 and 7 do not — octal runs the i8 form only.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ u32 q2_nibble_dword(uint4 raw, int pp, int jj);
+template <int ENG>
+struct ScanRow;
+template <>
+struct ScanRow<ENG_Q2> {
+    typedef uint4 Raw;
+    static __device__ __forceinline__ Raw zero() { return make_uint4(0, 0, 0, 0); }
+    static __device__ __forceinline__ bool in_row(u32 j, u64 row_stride) { return (u64)j * 16 < row_stride; }
+    static __device__ __forceinline__ Raw load(const uint8_t *__restrict__ rowp, int j, u64) { return *(const uint4 *)(rowp + (u64)j * 16); }
+    static __device__ __forceinline__ u32 digit_dword(const Raw &raw, int pp, int jj) { return q2_dword_perm(raw, pp, jj); }
+    static __device__ __forceinline__ u32 nibble_dword(const Raw &raw, int pp, int jj) { return q2_nibble_dword(raw, pp, jj); }
+    // the plane words of nibble piece p (32 dims) of chunk j alone, and the Raw that presents them as piece 0 (flat_scan_q2_fp4_w8, ORDER >= 1)
+    static __device__ __forceinline__ void load_half(Raw &dst, const uint8_t *__restrict__ rowp, int j, int p) {
+        dst.x = *(const u32 *)(rowp + (u64)j * 16 + 4 * p);
+        dst.z = *(const u32 *)(rowp + (u64)j * 16 + 8 + 4 * p);
+    }
+    static __device__ __forceinline__ Raw half_as_piece0(const Raw &r) { return make_uint4(r.x, 0u, r.z, 0u); }
+};
+template <>
+struct ScanRow<ENG_Q1> {
+    typedef uint2 Raw; // dims 0..31 | 32..63 of digit chunk j: bytes [8 j, 8 j + 8) of the row
+    static __device__ __forceinline__ Raw zero() { return make_uint2(0, 0); }
+    static __device__ __forceinline__ bool in_row(u32 j, u64 row_stride) { return (u64)j * 8 < row_stride; }
+    static __device__ __forceinline__ Raw load(const uint8_t *__restrict__ rowp, int j, u64) { return *(const uint2 *)(rowp + (u64)j * 8); }
+    static __device__ __forceinline__ u32 digit_dword(const Raw &raw, int pp, int jj) { return ((pp < 2 ? raw.x : raw.y) >> (4 * (pp & 1) + jj)) & 0x01010101u; }
+    static __device__ __forceinline__ u32 nibble_dword(const Raw &raw, int pp, int jj) { return ((pp == 0 ? raw.x : raw.y) >> jj) & 0x11111111u; }
+    static __device__ __forceinline__ void load_half(Raw &dst, const uint8_t *__restrict__ rowp, int j, int p) { dst.x = *(const u32 *)(rowp + (u64)j * 8 + 4 * p); }
+    static __device__ __forceinline__ Raw half_as_piece0(const Raw &r) { return make_uint2(r.x, 0u); }
+};
+template <>
+struct ScanRow<ENG_Q3> {
+    struct Raw { u32 p[2][3]; }; // [half: dims 0..31 | 32..63 of digit chunk j][plane]: row chunks 2 j and 2 j + 1
+    static __device__ __forceinline__ Raw zero() { return Raw{{{0, 0, 0}, {0, 0, 0}}}; }
+    static __device__ __forceinline__ bool in_row(u32 j, u64 row_stride) { return (u64)j * 32 < row_stride; }
+    static __device__ __forceinline__ Raw load(const uint8_t *__restrict__ rowp, int j, u64 row_stride) {
+        const bool two = (u64)j * 32 + 16 < row_stride; // (uniform) an odd chunk count: the last digit chunk has no second half
+        const uint4 a = *(const uint4 *)(rowp + (u64)j * 32), b = *(const uint4 *)(rowp + (u64)j * 32 + (two ? 16 : 0)); // unconditional loads
+        return Raw{{{a.x, a.y, a.z}, {two ? b.x : 0u, two ? b.y : 0u, two ? b.z : 0u}}};
+    }
+    // byte b of dword jj of piece pp is dim 32 * (pp >> 1) + 4 * (pp & 1) + jj + 8 * b, as in q2_dword_perm
+    static __device__ __forceinline__ u32 digit_dword(const Raw &raw, int pp, int jj) {
+        const int h = pp >> 1, sh = 4 * (pp & 1) + jj;
+        const u32 x0 = raw.p[h][0] >> sh;
+        const u32 x1 = sh ? (raw.p[h][1] >> (sh - 1)) : (raw.p[h][1] << 1);
+        const u32 x2 = sh >= 2 ? (raw.p[h][2] >> (sh - 2)) : (raw.p[h][2] << (2 - sh));
+        return (x0 & 0x01010101u) | (x1 & 0x02020202u) | (x2 & 0x04040404u);
+    }
+};
+template <int ENG>
+__device__ __forceinline__ uint4 digit_piece(const typename ScanRow<ENG>::Raw &raw, int pp) {
+    typedef ScanRow<ENG> R;
+    return make_uint4(R::digit_dword(raw, pp, 0), R::digit_dword(raw, pp, 1), R::digit_dword(raw, pp, 2), R::digit_dword(raw, pp, 3));
+}
+template <int ENG>
+__device__ __forceinline__ uint4 nibble_piece(const typename ScanRow<ENG>::Raw &raw, int pp) {
+    typedef ScanRow<ENG> R;
+    return make_uint4(R::nibble_dword(raw, pp, 0), R::nibble_dword(raw, pp, 1), R::nibble_dword(raw, pp, 2), R::nibble_dword(raw, pp, 3));
+}
+
+template <int ENG>
 __global__ void expand_q2_digits_perm_kernel(const uint8_t *__restrict__ qcodes, u64 row_stride, u32 B, u32 kdims, uint8_t *__restrict__ digits) {
+    typedef ScanRow<ENG> R;
     const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     const u32 chunks = kdims / 64;
     if (t >= (u64)B * chunks) return;
     const u32 q = (u32)(t / chunks), j = (u32)(t % chunks);
-    const uint4 raw = (u64)j * 16 < row_stride ? *(const uint4 *)(qcodes + (u64)q * row_stride + (u64)j * 16) : make_uint4(0, 0, 0, 0);
+    const typename R::Raw raw = R::in_row(j, row_stride) ? R::load(qcodes + (u64)q * row_stride, (int)j, row_stride) : R::zero();
 #pragma unroll
-    for (int pp = 0; pp < 4; pp++) *(uint4 *)(digits + (u64)q * kdims + (u64)j * 64 + pp * 16) = q2_piece_perm(raw, pp);
+    for (int pp = 0; pp < 4; pp++) *(uint4 *)(digits + (u64)q * kdims + (u64)j * 64 + pp * 16) = digit_piece<ENG>(raw, pp);
 }
 
 // The MFMA of the query-resident kernel.  What the kernel needs from the register allocator: query fragments resident in
@@ -97,11 +171,12 @@ __device__ __forceinline__ void static_for(F &&f) {
     }
 }
 
-template <int KC>
+template <int KC, int ENG = ENG_Q2>
 __global__ __launch_bounds__(256) void flat_scan_q2_areg(const uint8_t *__restrict__ qdig /*[B][64 KC] permuted digits*/,
                                                          const float *__restrict__ qmags, u32 B, const uint8_t *__restrict__ codes,
                                                          const float *__restrict__ mags, u64 row_stride, u32 n0, u32 n_chunk, u32 metric,
                                                          const FusedOut fo) {
+    typedef ScanRow<ENG> R;
     constexpr int K = KC * 64, KS = KC * 2, LDB = K + 16, ITS = (KC + 3) / 4, PIECES = ITS * 4;
     extern __shared__ __attribute__((aligned(16))) unsigned char areg_lds[]; // [2][64][LDB] | survivors [AREG_STAGE][3] u32 | count
     u32 *stage = (u32 *)(areg_lds + (size_t)2 * 64 * LDB), *stage_cnt = stage + 3 * AREG_STAGE;
@@ -136,15 +211,15 @@ __global__ __launch_bounds__(256) void flat_scan_q2_areg(const uint8_t *__restri
     // set (PAR^1) (tile t+G) is expanded into the other LDS buffer and reloaded with tile t+3G; set PAR (tile t+2G) is in
     // flight.  Loads are unconditional (addresses clamped to the last row of the chunk: a duplicated row is never appended,
     // its columns fail the `col < n_chunk` test), so they stay in flight across the MFMAs.
-    uint4 raw[2][ITS];
-    auto load_raw = [&](u32 tile, uint4 *dst, int it) __attribute__((always_inline)) {
+    typename R::Raw raw[2][ITS];
+    auto load_raw = [&](u32 tile, typename R::Raw *dst, int it) __attribute__((always_inline)) {
         const int j = w + 4 * it;
         const u32 c = tile * 64 + lane, cc = c < n_chunk ? c : n_chunk - 1;
-        dst[it] = *(const uint4 *)(codes + (u64)(n0 + cc) * row_stride + (u64)(KC % 4 == 0 || j < KC ? j : 0) * 16);
+        dst[it] = R::load(codes + (u64)(n0 + cc) * row_stride, KC % 4 == 0 || j < KC ? j : 0, row_stride);
     };
-    auto store_piece = [&](int buf, const uint4 *src, int it, int pp) __attribute__((always_inline)) {
+    auto store_piece = [&](int buf, const typename R::Raw *src, int it, int pp) __attribute__((always_inline)) {
         const int j = w + 4 * it;
-        if (KC % 4 == 0 || j < KC) *(uint4 *)(areg_lds + (size_t)buf * 64 * LDB + lane * LDB + j * 64 + pp * 16) = q2_piece_perm(src[it], pp);
+        if (KC % 4 == 0 || j < KC) *(uint4 *)(areg_lds + (size_t)buf * 64 * LDB + lane * LDB + j * 64 + pp * 16) = digit_piece<ENG>(src[it], pp);
     };
     float xm[2][2]; // candidate norms of the tile in accumulator set 0 / 1 (consumed by the deferred epilogue)
     auto load_norms = [&](u32 tile, float *dst) __attribute__((always_inline)) {
@@ -247,20 +322,20 @@ __global__ __launch_bounds__(256) void flat_scan_q2_areg(const uint8_t *__restri
             const bool lane_stores = KC % 4 == 0 || w + 4 * it < KC;
             u32 o[4] = {0, 0, 0, 0};
             areg_mfma<s == 0>(acc[P][0][0], a[0][s], b0);
-            if (expand) { o[0] = q2_dword_perm(raw[P ^ 1][it], pp, 0); asm volatile("" : "+v"(o[0])); } // pinned behind its MFMA
+            if (expand) { o[0] = R::digit_dword(raw[P ^ 1][it], pp, 0); asm volatile("" : "+v"(o[0])); } // pinned behind its MFMA
             if (epi) epi_rows(std::integral_constant<int, (P ^ 1)>{}, s - EPI0, 0);
             __builtin_amdgcn_sched_barrier(0);
             areg_mfma<s == 0>(acc[P][0][1], a[0][s], b1);
-            if (expand) { o[1] = q2_dword_perm(raw[P ^ 1][it], pp, 1); asm volatile("" : "+v"(o[1])); } // pinned behind its MFMA
+            if (expand) { o[1] = R::digit_dword(raw[P ^ 1][it], pp, 1); asm volatile("" : "+v"(o[1])); } // pinned behind its MFMA
             if (epi) epi_rows(std::integral_constant<int, (P ^ 1)>{}, s - EPI0, 2);
             __builtin_amdgcn_sched_barrier(0);
             areg_mfma<s == 0>(acc[P][1][0], a[1][s], b0);
-            if (expand) { o[2] = q2_dword_perm(raw[P ^ 1][it], pp, 2); asm volatile("" : "+v"(o[2])); } // pinned behind its MFMA
+            if (expand) { o[2] = R::digit_dword(raw[P ^ 1][it], pp, 2); asm volatile("" : "+v"(o[2])); } // pinned behind its MFMA
             if (epi) epi_rows(std::integral_constant<int, (P ^ 1)>{}, s - EPI0, 4);
             __builtin_amdgcn_sched_barrier(0);
             areg_mfma<s == 0>(acc[P][1][1], a[1][s], b1);
             if (expand) {
-                o[3] = q2_dword_perm(raw[P ^ 1][it], pp, 3);
+                o[3] = R::digit_dword(raw[P ^ 1][it], pp, 3);
                 asm volatile("" : "+v"(o[3]));
                 if (lane_stores)
                     *(uint4 *)(areg_lds + (size_t)(P ^ 1) * 64 * LDB + lane * LDB + (w + 4 * it) * 64 + pp * 16) = make_uint4(o[0], o[1], o[2], o[3]);
@@ -325,14 +400,16 @@ __device__ __forceinline__ uint4 q2_nibble_piece(uint4 raw, int pp) {
     return make_uint4(q2_nibble_dword(raw, pp, 0), q2_nibble_dword(raw, pp, 1), q2_nibble_dword(raw, pp, 2), q2_nibble_dword(raw, pp, 3));
 }
 
+template <int ENG>
 __global__ void expand_q2_nibbles_kernel(const uint8_t *__restrict__ qcodes, u64 row_stride, u32 B, u32 kdims, uint8_t *__restrict__ nib /*[B][kdims / 2]*/) {
+    typedef ScanRow<ENG> R;
     const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     const u32 chunks = kdims / 64;
     if (t >= (u64)B * chunks) return;
     const u32 q = (u32)(t / chunks), j = (u32)(t % chunks);
-    const uint4 raw = (u64)j * 16 < row_stride ? *(const uint4 *)(qcodes + (u64)q * row_stride + (u64)j * 16) : make_uint4(0, 0, 0, 0);
+    const typename R::Raw raw = R::in_row(j, row_stride) ? R::load(qcodes + (u64)q * row_stride, (int)j, row_stride) : R::zero();
 #pragma unroll
-    for (int pp = 0; pp < 2; pp++) *(uint4 *)(nib + (u64)q * (kdims / 2) + (u64)j * 32 + pp * 16) = q2_nibble_piece(raw, pp);
+    for (int pp = 0; pp < 2; pp++) *(uint4 *)(nib + (u64)q * (kdims / 2) + (u64)j * 32 + pp * 16) = nibble_piece<ENG>(raw, pp);
 }
 
 template <bool FIRST>
@@ -343,11 +420,12 @@ __device__ __forceinline__ void fp4_mfma(f32x16 &acc, const i32x4 &afrag, const 
     acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, FIRST ? z : acc, 4, 4, 0, 0x7F7F7F7F, 0, 0x7F7F7F7F);
 }
 
-template <int KC>
+template <int KC, int ENG = ENG_Q2>
 __global__ __launch_bounds__(256) void flat_scan_q2_fp4(const uint8_t *__restrict__ qnib /*[B][32 KC] nibble bytes*/,
                                                         const float *__restrict__ qmags, u32 B, const uint8_t *__restrict__ codes,
                                                         const float *__restrict__ mags, u64 row_stride, u32 n0, u32 n_chunk, u32 metric,
                                                         const FusedOut fo) {
+    typedef ScanRow<ENG> R;
     constexpr int KB = KC * 32, KS = KC, LDB = KB + 16, ITS = (KC + 3) / 4, PIECES = ITS * 2; // KB = operand bytes per row, one k step per chunk
     extern __shared__ __attribute__((aligned(16))) unsigned char areg_lds[]; // [2][64][LDB] | survivors [AREG_STAGE][3] u32 | count
     u32 *stage = (u32 *)(areg_lds + (size_t)2 * 64 * LDB), *stage_cnt = stage + 3 * AREG_STAGE;
@@ -378,15 +456,15 @@ __global__ __launch_bounds__(256) void flat_scan_q2_fp4(const uint8_t *__restric
             const float v = metric == 0u ? lo * qm : lo;
             T[i][r] = row < B ? v : __builtin_inff();
         }
-    uint4 raw[2][ITS];
-    auto load_raw = [&](u32 tile, uint4 *dst, int it) __attribute__((always_inline)) {
+    typename R::Raw raw[2][ITS];
+    auto load_raw = [&](u32 tile, typename R::Raw *dst, int it) __attribute__((always_inline)) {
         const int j = w + 4 * it;
         const u32 c = tile * 64 + lane, cc = c < n_chunk ? c : n_chunk - 1;
-        dst[it] = *(const uint4 *)(codes + (u64)(n0 + cc) * row_stride + (u64)(KC % 4 == 0 || j < KC ? j : 0) * 16);
+        dst[it] = R::load(codes + (u64)(n0 + cc) * row_stride, KC % 4 == 0 || j < KC ? j : 0, row_stride);
     };
-    auto store_piece = [&](int buf, const uint4 *src, int it, int pp) __attribute__((always_inline)) {
+    auto store_piece = [&](int buf, const typename R::Raw *src, int it, int pp) __attribute__((always_inline)) {
         const int j = w + 4 * it;
-        if (KC % 4 == 0 || j < KC) *(uint4 *)(areg_lds + (size_t)buf * 64 * LDB + lane * LDB + j * 32 + pp * 16) = q2_nibble_piece(src[it], pp);
+        if (KC % 4 == 0 || j < KC) *(uint4 *)(areg_lds + (size_t)buf * 64 * LDB + lane * LDB + j * 32 + pp * 16) = nibble_piece<ENG>(src[it], pp);
     };
     float xm[2][2]; // candidate norms of the tile in accumulator set 0 / 1 (consumed by the deferred epilogue)
     auto load_norms = [&](u32 tile, float *dst) __attribute__((always_inline)) {
@@ -482,20 +560,20 @@ __global__ __launch_bounds__(256) void flat_scan_q2_fp4(const uint8_t *__restric
             const bool lane_stores = KC % 4 == 0 || w + 4 * it < KC;
             u32 o[4] = {0, 0, 0, 0};
             fp4_mfma<s == 0>(acc[P][0][0], a[0][s], b0);
-            if (expand) { o[0] = q2_nibble_dword(raw[P ^ 1][it], pp, 0); asm volatile("" : "+v"(o[0])); } // pinned behind its MFMA
+            if (expand) { o[0] = R::nibble_dword(raw[P ^ 1][it], pp, 0); asm volatile("" : "+v"(o[0])); } // pinned behind its MFMA
             if (epi) epi_rows(std::integral_constant<int, (P ^ 1)>{}, s - EPI0, 0);
             __builtin_amdgcn_sched_barrier(0);
             fp4_mfma<s == 0>(acc[P][0][1], a[0][s], b1);
-            if (expand) { o[1] = q2_nibble_dword(raw[P ^ 1][it], pp, 1); asm volatile("" : "+v"(o[1])); }
+            if (expand) { o[1] = R::nibble_dword(raw[P ^ 1][it], pp, 1); asm volatile("" : "+v"(o[1])); }
             if (epi) epi_rows(std::integral_constant<int, (P ^ 1)>{}, s - EPI0, 2);
             __builtin_amdgcn_sched_barrier(0);
             fp4_mfma<s == 0>(acc[P][1][0], a[1][s], b0);
-            if (expand) { o[2] = q2_nibble_dword(raw[P ^ 1][it], pp, 2); asm volatile("" : "+v"(o[2])); }
+            if (expand) { o[2] = R::nibble_dword(raw[P ^ 1][it], pp, 2); asm volatile("" : "+v"(o[2])); }
             if (epi) epi_rows(std::integral_constant<int, (P ^ 1)>{}, s - EPI0, 4);
             __builtin_amdgcn_sched_barrier(0);
             fp4_mfma<s == 0>(acc[P][1][1], a[1][s], b1);
             if (expand) {
-                o[3] = q2_nibble_dword(raw[P ^ 1][it], pp, 3);
+                o[3] = R::nibble_dword(raw[P ^ 1][it], pp, 3);
                 asm volatile("" : "+v"(o[3]));
                 if (lane_stores)
                     *(uint4 *)(areg_lds + (size_t)(P ^ 1) * 64 * LDB + lane * LDB + (w + 4 * it) * 32 + pp * 16) = make_uint4(o[0], o[1], o[2], o[3]);
@@ -548,7 +626,7 @@ __global__ __launch_bounds__(256) void flat_scan_q2_fp4(const uint8_t *__restric
 // epilogue of a tile runs in line, right after its last k step, while the SIMD's other wave multiplies.  Same estimate, same survivors,
 // same staging and exact test as above: the results are the tile kernel's bit for bit.
 // ------------------------------------------------------------------------------------------------
-template <int KC, int ORDER>
+template <int KC, int ORDER, int ENG = ENG_Q2>
 __global__ __launch_bounds__(512) void flat_scan_q2_fp4_w8(const uint8_t *__restrict__ qnib /*[B][32 KC] nibble bytes*/, const float *__restrict__ qmags, u32 B,
                                                            const uint8_t *__restrict__ codes, const float *__restrict__ mags, u64 row_stride, u32 n0,
                                                            u32 n_chunk, u32 metric, const FusedOut fo) {
@@ -561,6 +639,7 @@ __global__ __launch_bounds__(512) void flat_scan_q2_fp4_w8(const uint8_t *__rest
     //      same accumulator costs ~43 cycles), the second row block's chain sunk below the first one's epilogue;
     //   3  + tiles of 128 columns (two sub-tiles per barrier: a wave multiplies column blocks cb and cb + 2): half the barriers, so
     //      half the tile tails in which a SIMD's first-finished wave is parked and its other wave runs alone.
+    typedef ScanRow<ENG> R;
     static_assert(ORDER == 0 || KC == 12, "the even deal is written for 12 chunks");
     constexpr int KB = KC * 32, KS = KC, LDB = KB + 16, ITS = (KC + 7) / 8, PIECES = ORDER >= 1 ? 3 : ITS * 2;
     constexpr int SUB = ORDER >= 3 ? 2 : 1, TW = 64 * SUB, NSET = SUB == 2 ? 1 : 2, AHEAD = NSET + 1; // raw register sets; tiles ahead of a reload
@@ -594,29 +673,28 @@ __global__ __launch_bounds__(512) void flat_scan_q2_fp4_w8(const uint8_t *__rest
             T[i][r] = row < B ? v : __builtin_inff();
         }
     // staging registers of one tile column (lane + 64 u): slot 0 = chunk w; slot 1 = ORDER 0: chunk w + 8 (waves 0..3 at KC 12), ORDER >= 1:
-    // the two plane words (.x plane 0, .z plane 1) of piece w & 1 of chunk 8 + (w >> 1)
+    // the plane words (quaternary: .x plane 0, .z plane 1) of piece w & 1 of chunk 8 + (w >> 1)
     const int xw = __builtin_amdgcn_readfirstlane(w);
     const int xj = 8 + (xw >> 1), xp = xw & 1;
-    uint4 raw[NSET][SUB][ITS];
-    auto load_raw = [&](u32 tile, uint4 *dst, int u, int it) __attribute__((always_inline)) {
+    typename R::Raw raw[NSET][SUB][ITS];
+    auto load_raw = [&](u32 tile, typename R::Raw *dst, int u, int it) __attribute__((always_inline)) {
         const u32 c = tile * TW + 64 * u + lane, cc = c < n_chunk ? c : n_chunk - 1;
         const uint8_t *rowp = codes + (u64)(n0 + cc) * row_stride;
         if (ORDER >= 1 && it == 1) {
-            dst[1].x = *(const u32 *)(rowp + (u64)xj * 16 + 4 * xp);
-            dst[1].z = *(const u32 *)(rowp + (u64)xj * 16 + 8 + 4 * xp);
+            R::load_half(dst[1], rowp, xj, xp);
             return;
         }
         const int j = w + 8 * it;
-        dst[it] = *(const uint4 *)(rowp + (u64)(KC % 8 == 0 || j < KC ? j : 0) * 16);
+        dst[it] = R::load(rowp, KC % 8 == 0 || j < KC ? j : 0, row_stride);
     };
-    auto store_piece = [&](int buf, const uint4 *src, int u, int it, int pp) __attribute__((always_inline)) {
+    auto store_piece = [&](int buf, const typename R::Raw *src, int u, int it, int pp) __attribute__((always_inline)) {
         unsigned char *rowl = areg_lds + (size_t)buf * TW * LDB + (size_t)(64 * u + lane) * LDB;
         if (ORDER >= 1 && it == 1) { // the one extra piece (pp ignored: the registers hold piece xp's words as piece 0)
-            *(uint4 *)(rowl + xj * 32 + xp * 16) = q2_nibble_piece(make_uint4(src[1].x, 0u, src[1].z, 0u), 0);
+            *(uint4 *)(rowl + xj * 32 + xp * 16) = nibble_piece<ENG>(R::half_as_piece0(src[1]), 0);
             return;
         }
         const int j = w + 8 * it;
-        if (KC % 8 == 0 || j < KC) *(uint4 *)(rowl + j * 32 + pp * 16) = q2_nibble_piece(src[it], pp);
+        if (KC % 8 == 0 || j < KC) *(uint4 *)(rowl + j * 32 + pp * 16) = nibble_piece<ENG>(src[it], pp);
     };
 #pragma unroll
     for (int u = 0; u < SUB; u++)
@@ -661,21 +739,21 @@ __global__ __launch_bounds__(512) void flat_scan_q2_fp4_w8(const uint8_t *__rest
                 if (s + 2 < KS) bf[(s + 2) % 3] = *(const i32x4 *)(bt + 32 * (s + 2));
                 const i32x4 b = bf[s % 3];
                 if constexpr (ORDER >= 2) { // pinned: MFMA row block 0 | half a piece | MFMA row block 1 | the other half, its store, the reload
-                    const uint4 src = it == 1 ? make_uint4(raw[RS][u][1].x, 0u, raw[RS][u][1].z, 0u) : raw[RS][u][it];
+                    const typename R::Raw src = it == 1 ? R::half_as_piece0(raw[RS][u][1]) : raw[RS][u][it];
                     u32 o[4] = {0, 0, 0, 0};
                     __builtin_amdgcn_sched_barrier(0);
                     fp4_mfma<s == 0>(acc[0], a[0][s], b);
                     __builtin_amdgcn_sched_barrier(0);
                     if (expand) {
-                        o[0] = q2_nibble_dword(src, pp, 0);
-                        o[1] = q2_nibble_dword(src, pp, 1);
+                        o[0] = R::nibble_dword(src, pp, 0);
+                        o[1] = R::nibble_dword(src, pp, 1);
                     }
                     __builtin_amdgcn_sched_barrier(0);
                     fp4_mfma<s == 0>(acc[1], a[1][s], b);
                     __builtin_amdgcn_sched_barrier(0);
                     if (expand) {
-                        o[2] = q2_nibble_dword(src, pp, 2);
-                        o[3] = q2_nibble_dword(src, pp, 3);
+                        o[2] = R::nibble_dword(src, pp, 2);
+                        o[3] = R::nibble_dword(src, pp, 3);
                         const int j = it == 1 ? xj : w, ppx = it == 1 ? xp : pp;
                         *(uint4 *)(areg_lds + (size_t)(P ^ 1) * TW * LDB + (size_t)(64 * u + lane) * LDB + j * 32 + ppx * 16) = make_uint4(o[0], o[1], o[2], o[3]);
                         if (last_of_slot) load_raw(tt + AHEAD * G, raw[RS][u], u, it);
@@ -1060,16 +1138,17 @@ bool flat_scan_supported(u32 kdims) {
     const u32 kc = kdims / 64;
     return kdims % 64 == 0 && (kc == 2 || kc == 4 || kc == 6 || kc == 8 || kc == 12 || kc == 16);
 }
-template <int KC>
+bool flat_scan_supported(int eng, u32 kdims) { return flat_scan_supported(kdims) && !(eng == ENG_Q3 && kdims == 1024); }
+template <int KC, int ENG>
 static hipError_t launch_areg_kc(dim3 grid, hipStream_t st, const uint8_t *qdig, const float *qmags, u32 B, const uint8_t *codes, const float *mags,
                                  u64 row_stride, u32 n0, u32 nc, u32 metric, const FusedOut &fo) {
     const size_t lds = (size_t)2 * 64 * (KC * 64 + 16) + (size_t)AREG_STAGE * 12 + 16;
-    hipError_t e = hipFuncSetAttribute((const void *)flat_scan_q2_areg<KC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute((const void *)flat_scan_q2_areg<KC, ENG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((flat_scan_q2_areg<KC>), grid, dim3(256), lds, st, qdig, qmags, B, codes, mags, row_stride, n0, nc, metric, fo);
+    hipLaunchKernelGGL((flat_scan_q2_areg<KC, ENG>), grid, dim3(256), lds, st, qdig, qmags, B, codes, mags, row_stride, n0, nc, metric, fo);
     return hipGetLastError();
 }
-template <int KC>
+template <int KC, int ENG>
 static hipError_t launch_fp4_kc(dim3 grid, hipStream_t st, const uint8_t *qnib, const float *qmags, u32 B, const uint8_t *codes, const float *mags,
                                 u64 row_stride, u32 n0, u32 nc, u32 metric, const FusedOut &fo) {
     const size_t lds = (size_t)2 * 64 * (KC * 32 + 16) + (size_t)AREG_STAGE * 12 + 16;
@@ -1078,10 +1157,10 @@ static hipError_t launch_fp4_kc(dim3 grid, hipStream_t st, const uint8_t *qnib, 
         auto go = [&](auto Oc) -> hipError_t {
             constexpr int ORDER = decltype(Oc)::value, TW = ORDER >= 3 ? 128 : 64;
             const size_t lds8 = (size_t)2 * TW * (KC * 32 + 16) + (size_t)AREG_STAGE * 12 + 16;
-            hipError_t e8 = hipFuncSetAttribute((const void *)flat_scan_q2_fp4_w8<KC, ORDER>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds8);
+            hipError_t e8 = hipFuncSetAttribute((const void *)flat_scan_q2_fp4_w8<KC, ORDER, ENG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds8);
             if (e8 != hipSuccess) return e8;
             const dim3 g8(std::min(grid.x, (nc + TW - 1) / TW), grid.y);
-            hipLaunchKernelGGL((flat_scan_q2_fp4_w8<KC, ORDER>), g8, dim3(512), lds8, st, qnib, qmags, B, codes, mags, row_stride, n0, nc, metric, fo);
+            hipLaunchKernelGGL((flat_scan_q2_fp4_w8<KC, ORDER, ENG>), g8, dim3(512), lds8, st, qnib, qmags, B, codes, mags, row_stride, n0, nc, metric, fo);
             return hipGetLastError();
         };
         if (w8 == 1) return go(std::integral_constant<int, 0>{});
@@ -1089,31 +1168,45 @@ static hipError_t launch_fp4_kc(dim3 grid, hipStream_t st, const uint8_t *qnib, 
         if (w8 == 3) return go(std::integral_constant<int, 2>{});
         if (w8 >= 4) return go(std::integral_constant<int, 3>{});
     }
-    hipError_t e = hipFuncSetAttribute((const void *)flat_scan_q2_fp4<KC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute((const void *)flat_scan_q2_fp4<KC, ENG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((flat_scan_q2_fp4<KC>), grid, dim3(256), lds, st, qnib, qmags, B, codes, mags, row_stride, n0, nc, metric, fo);
+    hipLaunchKernelGGL((flat_scan_q2_fp4<KC, ENG>), grid, dim3(256), lds, st, qnib, qmags, B, codes, mags, row_stride, n0, nc, metric, fo);
     return hipGetLastError();
 }
-// fp4 = the e2m1 form of the digits on the scaled MFMA (flat_scan_q2_fp4; qdig then holds the nibble rows of
-// launch_flat_scan_expand_queries(..., fp4 = true)), else the i8 digits (flat_scan_q2_areg)
-hipError_t launch_flat_scan(u32 kdims, u32 n_cus, hipStream_t st, const uint8_t *qdig, const float *qmags, u32 B, const uint8_t *codes,
-                              const float *mags, u64 row_stride, u32 n0, u32 nc, u32 metric, const FusedOut &fo, bool fp4) {
-    const u32 n_tiles = (nc + 63) / 64;
-    dim3 grid(std::min(n_tiles, n_cus), (B + 255) / 256);
-    if (fp4) {
-#define FP4_CASE(KC) case KC: return launch_fp4_kc<KC>(grid, st, qdig, qmags, B, codes, mags, row_stride, n0, nc, metric, fo)
-        switch (kdims / 64) {
-            FP4_CASE(2); FP4_CASE(4); FP4_CASE(6); FP4_CASE(8); FP4_CASE(12); FP4_CASE(16);
-            default: return hipErrorInvalidValue;
-        }
+// eng = ENG_Q1 / ENG_Q2 / ENG_Q3 (the row expansion, ScanRow).  fp4 (binary, quaternary) = the e2m1 form of the digits on the scaled MFMA
+// (flat_scan_q2_fp4; qdig then holds the nibble rows of launch_flat_scan_expand_queries(..., fp4 = true)), else the i8 digits (flat_scan_q2_areg)
+template <int ENG>
+static hipError_t launch_flat_scan_eng(u32 kdims, dim3 grid, hipStream_t st, const uint8_t *qdig, const float *qmags, u32 B, const uint8_t *codes,
+                                       const float *mags, u64 row_stride, u32 n0, u32 nc, u32 metric, const FusedOut &fo, bool fp4) {
+    if constexpr (ENG != ENG_Q3) {
+        if (fp4) {
+#define FP4_CASE(KC) case KC: return launch_fp4_kc<KC, ENG>(grid, st, qdig, qmags, B, codes, mags, row_stride, n0, nc, metric, fo)
+            switch (kdims / 64) {
+                FP4_CASE(2); FP4_CASE(4); FP4_CASE(6); FP4_CASE(8); FP4_CASE(12); FP4_CASE(16);
+                default: return hipErrorInvalidValue;
+            }
 #undef FP4_CASE
-    }
-#define AREG_CASE(KC) case KC: return launch_areg_kc<KC>(grid, st, qdig, qmags, B, codes, mags, row_stride, n0, nc, metric, fo)
+        }
+    } else if (fp4)
+        return hipErrorInvalidValue;
+#define AREG_CASE(KC) case KC: return launch_areg_kc<KC, ENG>(grid, st, qdig, qmags, B, codes, mags, row_stride, n0, nc, metric, fo)
     switch (kdims / 64) {
-        AREG_CASE(2); AREG_CASE(4); AREG_CASE(6); AREG_CASE(8); AREG_CASE(12); AREG_CASE(16);
+        AREG_CASE(2); AREG_CASE(4); AREG_CASE(6); AREG_CASE(8); AREG_CASE(12);
+        case 16:
+            if constexpr (ENG != ENG_Q3) return launch_areg_kc<16, ENG>(grid, st, qdig, qmags, B, codes, mags, row_stride, n0, nc, metric, fo);
+            return hipErrorInvalidValue; // flat_scan_supported(ENG_Q3, 1024) is false: the tile kernel runs
         default: return hipErrorInvalidValue;
     }
 #undef AREG_CASE
+}
+hipError_t launch_flat_scan(int eng, u32 kdims, u32 n_cus, hipStream_t st, const uint8_t *qdig, const float *qmags, u32 B, const uint8_t *codes,
+                            const float *mags, u64 row_stride, u32 n0, u32 nc, u32 metric, const FusedOut &fo, bool fp4) {
+    const u32 n_tiles = (nc + 63) / 64;
+    dim3 grid(std::min(n_tiles, n_cus), (B + 255) / 256);
+    if (eng == ENG_Q2) return launch_flat_scan_eng<ENG_Q2>(kdims, grid, st, qdig, qmags, B, codes, mags, row_stride, n0, nc, metric, fo, fp4);
+    if (eng == ENG_Q1) return launch_flat_scan_eng<ENG_Q1>(kdims, grid, st, qdig, qmags, B, codes, mags, row_stride, n0, nc, metric, fo, fp4);
+    if (eng == ENG_Q3) return launch_flat_scan_eng<ENG_Q3>(kdims, grid, st, qdig, qmags, B, codes, mags, row_stride, n0, nc, metric, fo, fp4);
+    return hipErrorInvalidValue;
 }
 
 
@@ -1176,12 +1269,18 @@ hipError_t launch_level_table_areg(int eng, u32 n_cus, hipStream_t st, const uin
 #undef TAB_CASE
 }
 
-hipError_t launch_flat_scan_expand_queries(const uint8_t *qcodes, u64 row_stride, u32 B, u32 kdims, uint8_t *digits, hipStream_t st, bool fp4) {
+hipError_t launch_flat_scan_expand_queries(int eng, const uint8_t *qcodes, u64 row_stride, u32 B, u32 kdims, uint8_t *digits, hipStream_t st, bool fp4) {
+    const dim3 grid((u32)(((u64)B * (kdims / 64) + 255) / 256));
     if (fp4) {
-        hipLaunchKernelGGL(expand_q2_nibbles_kernel, dim3((u32)(((u64)B * (kdims / 64) + 255) / 256)), dim3(256), 0, st, qcodes, row_stride, B, kdims, digits);
+        if (eng == ENG_Q2) hipLaunchKernelGGL(expand_q2_nibbles_kernel<ENG_Q2>, grid, dim3(256), 0, st, qcodes, row_stride, B, kdims, digits);
+        else if (eng == ENG_Q1) hipLaunchKernelGGL(expand_q2_nibbles_kernel<ENG_Q1>, grid, dim3(256), 0, st, qcodes, row_stride, B, kdims, digits);
+        else return hipErrorInvalidValue;
         return hipGetLastError();
     }
-    hipLaunchKernelGGL(expand_q2_digits_perm_kernel, dim3((u32)(((u64)B * (kdims / 64) + 255) / 256)), dim3(256), 0, st, qcodes, row_stride, B, kdims, digits);
+    if (eng == ENG_Q2) hipLaunchKernelGGL(expand_q2_digits_perm_kernel<ENG_Q2>, grid, dim3(256), 0, st, qcodes, row_stride, B, kdims, digits);
+    else if (eng == ENG_Q1) hipLaunchKernelGGL(expand_q2_digits_perm_kernel<ENG_Q1>, grid, dim3(256), 0, st, qcodes, row_stride, B, kdims, digits);
+    else if (eng == ENG_Q3) hipLaunchKernelGGL(expand_q2_digits_perm_kernel<ENG_Q3>, grid, dim3(256), 0, st, qcodes, row_stride, B, kdims, digits);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

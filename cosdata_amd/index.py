@@ -450,7 +450,9 @@ class HNSWIndex:
         return st
 
     def flat_search(self, queries, top_k: int, with_stats: bool = False):
-        """Exhaustive search over the quantized codes (i8 MFMA GEMM) + exact rerank of the best 5 * top_k.
+        """Exhaustive search over the quantized codes (exact-integer MFMA GEMM) + exact rerank of the best 5 * top_k.
+        Storages: UnsignedByte and SubByte of resolution 1, 2, 3 (binary, quaternary, octal); f16 / f32 indexes raise status 4
+        (Unimplemented) and stay usable.  A zero-norm query or stored vector raises status 2 (CalculationError) for the call.
         top_k in [1, 204] (status 4, Unimplemented, above): a query keeps the smallest pool of 64 .. 1024 survivors that holds
         5 * top_k; the append buffer of a wide call (top_k > 12) costs 256 bytes per pool slot and query (include/cosdata_hip.h)."""
         q = self._queries(queries)

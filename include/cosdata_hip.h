@@ -382,11 +382,15 @@ int32_t cos_distance_batch(uint32_t metric, uint32_t storage, uint32_t resolutio
 int32_t cos_bruteforce_topk(cos_index *ix, const float *queries, uint32_t B, uint32_t k, uint32_t *out_ids,
                             float *out_scores);
 
-/* Exhaustive search over the index's QUANTIZED codes (u8 / quaternary) as an exact-integer i8 MFMA GEMM,
- * then the reference's finalisation on the full candidate set: sort by quantized score (desc, larger id
+/* Exhaustive search over the index's QUANTIZED codes as an exact-integer MFMA GEMM, then the reference's finalisation on the full candidate set: sort by quantized score (desc, larger id
  * first), keep 5k, exact f32 rerank (vector_store.rs:404-445), top-k.  The result is what
  * ann_search + finalize_ann_results would return if the walk visited every node: config c3's flat scan and
  * the exhaustive per-shard mode.  Host buffers.
+ * Storages: UnsignedByte and SubByte of resolution 1 (binary), 2 (quaternary) and 3 (octal): their reference dots are integers, exact
+ * in any summation order (dot_product_u8 / _binary / _quaternary / _octal), so the candidate set is the reference's bit for bit.
+ * HalfPrecisionFP and FullPrecisionFP indexes: COS_ERR_UNIMPLEMENTED (their reference dots are order-dependent f32 chains; the handle
+ * stays usable — cos_bruteforce_topk scans the raw rows of any index).  Cosine divides by the norms the quantizer keeps (SubByte: of the
+ * original vector), and a zero norm among the queries or the stored vectors is COS_ERR_CALCULATION for the call.
  * top_k in [1, 204]; above that COS_ERR_UNIMPLEMENTED (the handle stays usable).  A query keeps a pool of P
  * survivors, the smallest of 64, 128, 256, 512, 1024 with 5 * top_k <= P: top_k <= 12 runs the 64-key kernels,
  * 13..25 P = 128, 26..51 P = 256, 52..102 P = 512, 103..204 P = 1024.  The index's workspace grows to the widest call
@@ -398,7 +402,7 @@ int32_t cos_bruteforce_topk(cos_index *ix, const float *queries, uint32_t B, uin
 typedef struct {
     float gemm_ms;          /* summed HIP-event time of the i8 MFMA GEMM launches */
     uint32_t gemm_launches;
-    double int8_ops;        /* 2 * B * n * padded_dim */
+    double int8_ops;        /* 2 * B * n * padded_dim (the dims multiplied: the stored row's dims rounded up to 64) */
     double code_bytes;      /* bytes of codes streamed from HBM (n * row bytes * query-tile rows) */
 } cos_flat_stats;
 int32_t cos_flat_search_batch(cos_index *ix, const float *queries, uint32_t B, uint32_t top_k, uint32_t *out_ids,
