@@ -200,9 +200,12 @@ __device__ __forceinline__ void finalize_one(const IndexDev &ix, const FinalizeA
         for (u32 s = 0; s <= L; s++) {
             // a level list is sorted: entries past its first 5k+1 cannot reach the global top 5k (each is preceded by 5k
             // distinct better non-root nodes — one of the first 5k+1 may be the root, which is filtered), so only
-            // min(count, 5k+1) entries per level take part in the sort
+            // min(count, 5k+1) entries per level take part in the sort.  Not so in a metadata collection: the pseudo nodes are
+            // filtered as well, a list may hold any number of them ahead of its replicas (one per matching filter at cosine 1.0;
+            // under the other metrics every pseudo node scores like the all-zero vector), and the whole list takes part
+            // (launch_finalize sizes FR for it)
             u32 c = fa.walk_counts[(u64)qi * (L + 1) + s];
-            if (c > 5u * fa.top_k + 1u) c = 5u * fa.top_k + 1u;
+            if (ix.mdim == 0u && c > 5u * fa.top_k + 1u) c = 5u * fa.top_k + 1u;
             const u64 b = ((u64)qi * (L + 1) + s) * KEEP_SEARCH;
             // element index off + j  lives in lane (off+j)/FR, register (off+j)%FR
 #pragma unroll
@@ -662,7 +665,8 @@ hipError_t launch_finalize(const IndexDev &ix, const float *queries, u64 q_strid
     if (B == 0) return hipSuccess;
     FinalizeArgs fa{queries, q_stride, q_raw_mags, walk_ids, walk_sims, walk_counts, walk_status, B, top_k,
                     out_ids, out_scores, out_counts, out_status, out_rerank_rows, q_order, nullptr, nullptr};
-    const u32 per_level = std::min<u32>(KEEP_SEARCH, 5u * top_k + 1u);
+    // (metadata collections: whole lists, see finalize_one — 16 levels x 100 entries still fit the widest instance)
+    const u32 per_level = ix.mdim != 0u ? (u32)KEEP_SEARCH : std::min<u32>(KEEP_SEARCH, 5u * top_k + 1u);
     const u32 total = (ix.num_layers + 1) * per_level;
     dim3 grid(B), block(64);
     // small launches: FIN_WAVES waves per query (finalize_one); tuning knob finalize_wide_max_b = the largest such launch (0 = never)

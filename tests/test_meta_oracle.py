@@ -27,29 +27,33 @@ def world():
     return sc, sc.oracle()
 
 
-def test_filtered_results_satisfy_the_filter_and_carry_exact_scores(world):
-    sc, oix = world
+@pytest.fixture(scope="module")
+def world_a():
+    sc = MH.Scenario(n=1200, dim=48, seed=2, **MH.SCHEMAS["A"])
+    return sc, sc.oracle()
+
+
+@pytest.mark.parametrize("which", ["world", "world_a"])
+def test_filtered_results_satisfy_the_filter_and_carry_exact_scores(which, request):
+    sc, oix = request.getfixturevalue(which)
     Q, off, rows, desc = sc.queries(nq=30, seed=5)
     ids, scores, counts = oix.search_filtered_batch(Q, off, rows, 10, threads=4)
     seen = 0
-    for b, (kind, c, s) in enumerate(desc):
+    for b, (kind, *want) in enumerate(desc):
         for j in range(int(counts[b])):
             rid = int(ids[b, j])
-            r, rep = rid // 4, rid % 4
+            r, rep = rid // sc.replicas, rid % sc.replicas
             assert rid < MH.PSEUDO_ROOT                                       # pseudo nodes never come back (common.rs:400-402)
-            ok_color, ok_size = sc.color[r] == c, sc.size[r] == s
-            if kind == "is_color":
-                assert rep == 1 and ok_color
-            elif kind == "is_size":
-                assert rep == 2 and ok_size
-            elif kind == "and":
-                assert rep == 3 and ok_color and ok_size
+            # replica 1 + i carries condition i; it satisfies the query if every field of that condition has the wanted value
+            ok = lambda i: rep == 1 + i and all(sc.values[f][r] == want[f] for f in sc.conditions[i])
+            if kind in sc.kind_cond:                                          # "is_<field>" and "and"
+                assert ok(sc.kind_cond[kind])
             elif kind == "or":
-                assert (rep == 1 and ok_color) or (rep == 2 and ok_size)
+                assert ok(sc.or_conds[0]) or ok(sc.or_conds[1])
             x, q = sc.X[r].astype(np.float64), Q[b].astype(np.float64)
             assert abs(float(scores[b, j]) - x @ q / np.linalg.norm(x) / np.linalg.norm(q)) < 1e-5
             seen += 1
-        if kind in ("is_color", "is_size", "or"):
+        if kind == "or" or (kind in sc.kind_cond and len(sc.conditions[sc.kind_cond[kind]]) == 1):
             assert counts[b] == 10
     assert seen > 150
 
