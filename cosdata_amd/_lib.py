@@ -78,6 +78,15 @@ class CosFlatStats(C.Structure):
     _fields_ = [("gemm_ms", C.c_float), ("gemm_launches", C.c_uint32), ("int8_ops", C.c_double), ("code_bytes", C.c_double)]
 
 
+SCAN_SKIP_DELETED = 1  # COS_SCAN_SKIP_DELETED
+
+
+class CosScanMask(C.Structure):
+    """cos_scan_mask: the row masks of a masked exhaustive scan (host arrays; bit r % 32 of word r / 32 = row r may be returned)"""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("n_masks", C.c_uint32), ("bits", C.c_void_p),
+                ("query_mask", C.c_void_p)]
+
+
 class CosBM25Stats(C.Structure):
     """cos_bm25_index_stats: what a BM25 handle holds (postings count tombstones too)"""
     _fields_ = [("struct_size", C.c_uint32), ("documents_count", C.c_uint32), ("n_terms", C.c_uint32), ("largest_doc_id", C.c_uint32),
@@ -126,7 +135,8 @@ ABI_SYMBOLS = [
     "cos_ann_search_filtered_batch", "cos_index_load_reference_dir", "cos_reference_dir_level_counts", "cos_reference_dir_read_level",
     "cos_search_batch", "cos_search_batch_device", "cos_ann_search_batch", "cos_index_set_coalescing", "cos_index_coalescing_stats", "cos_index_set_ef_search",
     "cos_index_set_visited_mode", "cos_index_set_latency_mode", "cos_index_set_latency_waves", "cos_index_set_walk_order", "cos_index_walk_order_cuts", "cos_index_set_walk_table", "cos_index_walk_table_info", "cos_index_last_walk_split", "cos_index_enable_timing", "cos_index_last_stats", "cos_index_timing_summary", "cos_quantize_batch",
-    "cos_code_bytes", "cos_sample_values_range", "cos_distance_batch", "cos_bruteforce_topk", "cos_flat_search_batch", "cos_bm25_create", "cos_bm25_destroy",
+    "cos_code_bytes", "cos_sample_values_range", "cos_distance_batch", "cos_bruteforce_topk", "cos_flat_search_batch",
+    "cos_flat_search_masked_batch", "cos_bruteforce_topk_masked", "cos_index_deleted_count", "cos_index_download_deleted", "cos_bm25_create", "cos_bm25_destroy",
     "cos_bm25_insert", "cos_bm25_delete", "cos_bm25_stats", "cos_bm25_download",
     "cos_bm25_search_batch", "cos_bm25_search_batch_device", "cos_rrf_fuse_batch", "cos_hybrid_search_batch", "cos_text_process", "cos_text_count_tokens", "cos_bm25_term_frequency", "cos_xxhash32", "cos_stem_english", "cos_sparse_create", "cos_sparse_build_csr", "cos_sparse_create_from_vectors", "cos_sparse_destroy", "cos_sparse_search_batch", "cos_sparse_last_stats", "cos_sparse_layout",
     "cos_sparse_set_max_candidates", "cos_sparse_max_candidates", "cos_sparse_search_batch_device",
@@ -202,6 +212,10 @@ def lib():
         "cos_distance_batch": [u32, u32, u32, u32, vp, vp, u32, vp, vp, u32, vp, vp, u32, vp, vp],
         "cos_bruteforce_topk": [vp, vp, u32, u32, vp, vp],
         "cos_flat_search_batch": [vp, vp, u32, u32, vp, vp, vp, C.POINTER(CosFlatStats)],
+        "cos_flat_search_masked_batch": [vp, vp, u32, u32, C.POINTER(CosScanMask), vp, vp, vp, C.POINTER(CosFlatStats)],
+        "cos_bruteforce_topk_masked": [vp, vp, u32, u32, C.POINTER(CosScanMask), vp, vp, vp],
+        "cos_index_deleted_count": [vp, C.POINTER(u32)],
+        "cos_index_download_deleted": [vp, vp],
         "cos_bm25_create": [i32, vp, vp, u32, vp, vp, u32, C.POINTER(vp)],
         "cos_bm25_destroy": [vp],
         "cos_bm25_insert": [vp, vp, vp, u32, vp, vp],

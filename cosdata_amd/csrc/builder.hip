@@ -427,6 +427,7 @@ extern "C" int32_t cos_index_append(cos_index *ix, const float *raw, uint32_t m,
             new_rows = new_raw + (size_t)n0 * dim;
         }
         HIP_TRY(launch_quantize_rows(ix->eng, new_rows, dim, m, ix->p.dim, ix->p.range_lo, ix->p.range_hi, codes + (size_t)n0 * rs, rs, mags + n0, raw_mags + n0, st));
+        HIP_TRY(cos_deleted_grow(ix, n0, n1, st)); // the deleted set follows the tables: the new rows are live
         HIP_TRY(hipStreamSynchronize(st));
         codes.swap(ix->d_codes);
         mags.swap(ix->d_mags);
@@ -604,6 +605,8 @@ extern "C" int32_t cos_index_delete(cos_index *ix, const uint32_t *ids, uint32_t
     HIP_TRY(hipDeviceSynchronize()); // exclusive: no search in flight
     const u32 Ltop = ix->p.num_layers, L1 = Ltop + 1, metric = ix->p.metric, KEEP = (u32)KEEP_SEARCH, EF = 512;
     hipStream_t st = ix->own_stream;
+    // the deleted set records the intent, whether or not the walks below find the nodes (the masked exhaustive scans read it)
+    HIP_TRY(cos_deleted_mark(ix, ids, m, st));
     LinkArgs la;
     memset(&la, 0, sizeof(la));
     u32 maxM = 0;

@@ -230,7 +230,7 @@ extern "C" int32_t cos_index_upload_vectors(cos_index *ix, const float *raw, uin
     int32_t rc = cos_set_device(ix);
     if (rc) return rc;
     ix->d_raw = nullptr;
-    ix->raw_own.reset(); ix->d_raw_mags.reset(); ix->d_codes.reset(); ix->d_mags.reset();
+    ix->raw_own.reset(); ix->d_raw_mags.reset(); ix->d_codes.reset(); ix->d_mags.reset(); ix->d_deleted.reset();
     ix->have_vectors = false;
     cos_flat_ws_release(ix); // cached sums of the stored codes, scan buffers sized for the old corpus
     ix->have_root = false;
@@ -261,6 +261,7 @@ extern "C" int32_t cos_index_upload_vectors(cos_index *ix, const float *raw, uin
     HIP_TRY(hipMemsetAsync(codes + (size_t)n * ix->row_stride, 0, 2 * ix->row_stride, ix->own_stream));
     HIP_TRY(hipMemsetAsync(mags + n, 0, 8, ix->own_stream));
     HIP_TRY(launch_quantize_rows(ix->eng, d_raw, dim, n, ix->p.dim, ix->p.range_lo, ix->p.range_hi, codes, ix->row_stride, mags, raw_mags, ix->own_stream));
+    HIP_TRY(cos_deleted_reset(ix, n, ix->own_stream)); // new vectors: nothing is deleted
     HIP_TRY(hipStreamSynchronize(ix->own_stream));
     ix->d_raw = d_raw;
     ix->raw_own = std::move(raw_own);

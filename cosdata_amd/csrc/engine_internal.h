@@ -227,6 +227,7 @@ struct cos_index {
     DevArr<float> d_raw_mags;
     DevArr<uint8_t> d_codes;
     DevArr<float> d_mags;
+    DevArr<u32> d_deleted;        // [ceil(n / 32)] the deleted set: bit (r % 32) of word r / 32 = row r was given to cos_index_delete (kernels_flat.hip)
     u64 row_stride = 0;
     u32 nchunks = 0, G = 1;
     std::vector<float> root_raw;
@@ -313,6 +314,10 @@ struct cos_index {
 
 struct FlatWs;
 void cos_flat_ws_release(cos_index *ix);
+// the deleted set (kernels_flat.hip), on `st`: a fresh all-live bitmap for n rows | grown from n0 to n1 rows, the new ones live | ids marked
+hipError_t cos_deleted_reset(cos_index *ix, u32 n, hipStream_t st);
+hipError_t cos_deleted_grow(cos_index *ix, u32 n0, u32 n1, hipStream_t st);
+hipError_t cos_deleted_mark(cos_index *ix, const u32 *ids, u32 m, hipStream_t st);
 void cos_coalesce_release(cos_index *ix);
 cosdev::IndexDev cos_make_index_dev(const cos_index *ix);
 cosdev::IndexDev cos_make_meta_dev(const cos_index *ix);

@@ -11,12 +11,30 @@ namespace cosdev {
 // SEL-th best key and only the rare survivors are appended to app[B][cap] through a per-query counter.  A reciprocal-based
 // estimate (4 VALU ops) screens the elements; the exact IEEE quotient — the value that is ranked — is formed only for those
 // within 4e-6 of the threshold or above it, so results are identical to the unfused path.
+// Row masks of a masked scan (cos_flat_search_masked_batch, cos_bruteforce_topk_masked): query q may only be given rows whose bit is set
+// in mask qmask[q].  The masks are the call's EFFECTIVE ones — the caller's allow-lists AND NOT the handle's deleted set, padding bits
+// cleared — built once per call (launch_scan_mask_build).  Only the MASKED instantiations of the kernels read them; bits == nullptr
+// is the unmasked call, which launches the unmasked instantiations.
+struct ScanMask {
+    const u32 *bits;  // [G][words]: bit (r % 32) of word r / 32 = row r is live
+    const u32 *qmask; // [B] -> mask index
+    u32 words;        // ceil(n / 32)
+};
+// The test sits where a candidate is about to be kept (a pool, the append buffer, the staging area of the query-resident kernels): a
+// pool only ever holds live rows, so a query's threshold is the one of its live rows and the appends per chunk do not grow.
+template <bool MASKED>
+__device__ __forceinline__ bool scan_live(const ScanMask &m, u32 q, u32 row) {
+    if constexpr (!MASKED) return true;
+    else return ((m.bits[(u64)m.qmask[q] * m.words + (row >> 5)] >> (row & 31u)) & 1u) != 0u;
+}
+
 struct FusedOut {
     const u64 *thr;   // [B] SEL-th best (key) so far; 0 = pool not full yet, everything passes
     u64 *app;         // [B][cap]
     u32 *app_cnt;     // [B]
     u32 cap;
     const uint8_t *qdigits; // bit-plane codes (binary, quaternary, octal): [B][kdims] pre-expanded query digits (expand_digits_kernel)
+    ScanMask m;       // masked instantiations only
 };
 
 
@@ -53,9 +71,10 @@ inline u32 flat_pool_width(u32 need) {
         if (need <= P) return P;
     return 0;
 }
-// score chunk [B][nc] -> per-segment top P (part[B][S][P]) -> merged into pool[B][P]; thr[q] = the pool's P-th best
+// score chunk [B][nc] -> per-segment top P (part[B][S][P]) -> merged into pool[B][P]; thr[q] = the pool's P-th best.  m.bits set: rows
+// outside a query's mask are skipped
 hipError_t launch_flat_select_wide(u32 R, const float *d_scores, u64 s_stride, u32 B, u32 n0, u32 nc, u64 *d_part, u32 S, u64 *d_pool, u64 *d_thr,
-                                   hipStream_t st);
+                                   hipStream_t st, const ScanMask &m);
 // fold of the fused scan's append buffer (entries past `cap` were dropped: *d_overflow |= 1), new thresholds, counters cleared
 hipError_t launch_flat_append_wide(u32 R, const u64 *d_app, u32 *d_appcnt, u32 cap, u32 B, u64 *d_pool, u64 *d_thr, u32 *d_overflow, hipStream_t st);
 // exact re-score against the raw rows, sort, top k.  brute = false: the best min(have, ncand_max) of the pool, out_counts set (code scan);

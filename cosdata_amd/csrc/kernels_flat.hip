@@ -38,7 +38,7 @@ constexpr size_t GEMM_SMEM = 2ull * (BM + BN) * LDT * sizeof(float); // double-b
 // of 32 double-buffered in LDS: panel p+1 travels HBM -> registers while panel p is multiplied, then registers -> LDS, one
 // barrier per panel.  A lane's MFMA operand for k-step s of an 8-wide k block is element s of ONE ds_read_b128
 // (k = 4*(lane>>5) + s): the k permutation is the same for both operands, so the sum is unchanged.
-template <bool VEC, bool FUSED>
+template <bool VEC, bool FUSED, bool MASKED = false /* FUSED: a survivor also passes its query's row mask (flat_scan.h ScanMask) */>
 __global__ __launch_bounds__(256) void flat_gemm_f32(const float *__restrict__ Q, u64 q_stride, const float *__restrict__ qmags, u32 B,
                                                      const float *__restrict__ X, u64 x_stride, const float *__restrict__ xmags, u32 n0,
                                                      u32 n_chunk, u32 dim, float *__restrict__ scores /*[B][n_chunk_padded]*/, u64 s_stride,
@@ -166,7 +166,7 @@ __global__ __launch_bounds__(256) void flat_gemm_f32(const float *__restrict__ Q
                     if (row0 + (u32)rl < B && cv && !(est < thr_lo[rl])) {
                         const float sc = x86_div(acc[i][j][r], qm[rl] * xm);
                         const u64 key = pack_key(simkey(sc), n0 + col);
-                        if (key > thr_key[rl]) {
+                        if (key > thr_key[rl] && scan_live<MASKED>(fo.m, row0 + (u32)rl, n0 + col)) {
                             const u32 row = row0 + (u32)rl;
                             const u32 pos = atomicAdd(&fo.app_cnt[row], 1u);
                             if (pos < fo.cap) fo.app[(u64)row * fo.cap + pos] = key;
@@ -195,8 +195,10 @@ __global__ __launch_bounds__(256) void flat_gemm_f32(const float *__restrict__ Q
 //                         (sorted register pool, ballot threshold filter) -> part[B][S][SEL]
 //   flat_select_merge     one wave per query folds the S sorted partial lists into the running pool[B][SEL]
 // keys = (simkey(score), global id): ties go to the larger id, like everywhere else.
-__global__ __launch_bounds__(64) void flat_select_segments(const float *__restrict__ scores, u64 s_stride, u32 B, u32 n0, u32 n_chunk, u32 seg_len,
-                                                           u64 *__restrict__ part /*[B][S][64]*/) {
+// MASKED (flat_select_segments_masked): a row outside the query's mask gives the empty key
+template <bool MASKED>
+__device__ __forceinline__ void select_segments_body(const float *__restrict__ scores, u64 s_stride, u32 B, u32 n0, u32 n_chunk, u32 seg_len,
+                                                     u64 *__restrict__ part /*[B][S][64]*/, const ScanMask &m) {
     const int lane = threadIdx.x;
     const u32 q = blockIdx.x, seg = blockIdx.y, S = gridDim.y;
     if (q >= B) return;
@@ -208,10 +210,18 @@ __global__ __launch_bounds__(64) void flat_select_segments(const float *__restri
     for (u32 c = c0; c < c1; c += 64) {
         const u32 col = c + lane;
         u64 key = 0ull;
-        if (col < c1) key = pack_key(simkey(sr[col]), n0 + col);
+        if (col < c1 && scan_live<MASKED>(m, q, n0 + col)) key = pack_key(simkey(sr[col]), n0 + col);
         pool_fold_lanes<1>(pool, thr, key, lane);
     }
     part[((u64)q * S + seg) * SEL + lane] = pool.e[0];
+}
+__global__ __launch_bounds__(64) void flat_select_segments(const float *__restrict__ scores, u64 s_stride, u32 B, u32 n0, u32 n_chunk, u32 seg_len,
+                                                           u64 *__restrict__ part /*[B][S][64]*/) {
+    select_segments_body<false>(scores, s_stride, B, n0, n_chunk, seg_len, part, ScanMask{nullptr, nullptr, 0u});
+}
+__global__ __launch_bounds__(64) void flat_select_segments_masked(const float *__restrict__ scores, u64 s_stride, u32 B, u32 n0, u32 n_chunk, u32 seg_len,
+                                                                  u64 *__restrict__ part /*[B][S][64]*/, const ScanMask m) {
+    select_segments_body<true>(scores, s_stride, B, n0, n_chunk, seg_len, part, m);
 }
 
 __global__ __launch_bounds__(64) void flat_select_merge(const u64 *__restrict__ part, u32 B, u32 S, u64 *__restrict__ pool_mem /*[B][64]*/,
@@ -260,9 +270,10 @@ static u32 select_segments(u32 B, u32 n_chunk) {
     return S ? S : 1;
 }
 static hipError_t launch_select(const float *d_scores, u64 s_stride, u32 B, u32 n0, u32 nc, u64 *d_part, u32 S, u64 *d_pool, hipStream_t st,
-                                u64 *d_thr = nullptr) {
+                                u64 *d_thr, const ScanMask &m) {
     const u32 seg_len = ((nc + S - 1) / S + 63) / 64 * 64;
-    hipLaunchKernelGGL(flat_select_segments, dim3(B, S), dim3(64), 0, st, d_scores, s_stride, B, n0, nc, seg_len, d_part);
+    if (m.bits) hipLaunchKernelGGL(flat_select_segments_masked, dim3(B, S), dim3(64), 0, st, d_scores, s_stride, B, n0, nc, seg_len, d_part, m);
+    else hipLaunchKernelGGL(flat_select_segments, dim3(B, S), dim3(64), 0, st, d_scores, s_stride, B, n0, nc, seg_len, d_part);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(flat_select_merge, dim3(B), dim3(64), 0, st, (const u64 *)d_part, B, S, d_pool, d_thr);
@@ -274,6 +285,55 @@ __global__ void any_zero_kernel(const float *__restrict__ v, u32 n, u32 *__restr
     bool z = false;
     for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) z |= (v[i] == 0.0f);
     if (__any(z) && (threadIdx.x & 63) == 0) atomicOr(flag, 1u);
+}
+
+// ---- row masks of the masked scans (flat_scan.h ScanMask) ----
+// The call's effective masks: eff[g] = user[g] (all ones without an allow-list) AND NOT deleted (when asked), bits at and past n cleared;
+// uni = the OR of them, the rows that some query of the call can be given (the masked zero-norm screen reads it).  One thread per word.
+__global__ void scan_mask_build_kernel(const u32 *__restrict__ user /*[G][words] or null*/, const u32 *__restrict__ deleted /*[words] or null*/, u32 G,
+                                       u32 words, u32 n, u32 *__restrict__ eff /*[G][words]*/, u32 *__restrict__ uni /*[words]*/) {
+    const u32 w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= words) return;
+    u32 keep = deleted ? ~deleted[w] : ~0u;
+    if (w == words - 1 && (n & 31u)) keep &= (1u << (n & 31u)) - 1u;
+    u32 u = 0;
+    for (u32 g = 0; g < G; g++) {
+        const u32 v = (user ? user[(u64)g * words + w] : ~0u) & keep;
+        eff[(u64)g * words + w] = v;
+        u |= v;
+    }
+    uni[w] = u;
+}
+// any_zero_kernel over the rows of a bitmap
+__global__ void any_zero_masked_kernel(const float *__restrict__ v, u32 n, const u32 *__restrict__ rows, u32 *__restrict__ flag) {
+    bool z = false;
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x)
+        z |= ((rows[i >> 5] >> (i & 31u)) & 1u) != 0u && v[i] == 0.0f;
+    if (__any(z) && (threadIdx.x & 63) == 0) atomicOr(flag, 1u);
+}
+// masked brute force: out_counts[q] = min(k, survivors in the query's pool) — the pool (P >= 2k keys) holds every live row while there are
+// fewer than P of them.  One wave per query.
+__global__ __launch_bounds__(64) void pool_count_kernel(const u64 *__restrict__ pool_mem, u32 P, u32 B, u32 k, u32 *__restrict__ out_counts) {
+    const u32 q = blockIdx.x;
+    if (q >= B) return;
+    u32 have = 0;
+    for (u32 c = threadIdx.x; c < P; c += 64) have += (u32)(pool_mem[(u64)q * P + c] >> 32) != 0u ? 1u : 0u;
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) have += (u32)__shfl_xor((int)have, m, 64);
+    if (threadIdx.x == 0) out_counts[q] = have < k ? have : k;
+}
+
+// ---- the handle's deleted set: one bit per row (cos_index::d_deleted) ----
+__global__ void deleted_mark_kernel(const u32 *__restrict__ ids, u32 m, u32 *__restrict__ bits) {
+    const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < m) atomicOr(&bits[ids[t] >> 5], 1u << (ids[t] & 31u));
+}
+__global__ void popcount_kernel(const u32 *__restrict__ bits, u32 words, u32 *__restrict__ out) {
+    u32 c = 0;
+    for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < words; i += gridDim.x * blockDim.x) c += (u32)__popc(bits[i]);
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) c += (u32)__shfl_xor((int)c, m, 64);
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(out, c);
 }
 
 // one launch instead of four memsets in front of every scan: the survivor pools, the thresholds, the append counters, the overflow flag
@@ -415,7 +475,7 @@ __global__ void expand_digits_kernel(const uint8_t *__restrict__ qcodes, u64 row
     *(uint4 *)(digits + (u64)q * kdims + k0) = stage16<ENG>(qcodes + (u64)q * row_stride, k0, k0 < code_k);
 }
 
-template <int ENG, bool FUSED, int PF>
+template <int ENG, bool FUSED, int PF, bool MASKED = false /* FUSED: as in flat_gemm_f32 */>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void flat_codes_gemm_i8(const uint8_t *__restrict__ qcodes, const float *__restrict__ qmags,
                                                           const u32 *__restrict__ qsums, u32 B, const uint8_t *__restrict__ codes,
                                                           const float *__restrict__ mags, const u32 *__restrict__ csums, u64 row_stride,
@@ -518,7 +578,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                     if (row < B && cv && est >= thr_lo[rl]) {
                         const float sc = metric == 0u ? __fdiv_rn(dotf, __fmul_rn(qmags[row], xm)) : dotf;
                         const u64 key = pack_key(simkey(sc), n0 + col);
-                        if (key > thr_key[rl]) {
+                        if (key > thr_key[rl] && scan_live<MASKED>(fo.m, row, n0 + col)) {
                             const u32 pos = atomicAdd(&fo.app_cnt[row], 1u);
                             if (pos < fo.cap) fo.app[(u64)row * fo.cap + pos] = key;
                         }
@@ -618,12 +678,72 @@ __global__ __launch_bounds__(64) void flat_rerank_top5k(const float *__restrict_
     if (lane == 0) out_counts[q] = nout;
 }
 
-} // namespace
+// ---- a call's cos_scan_mask: checked on the host, then one set of device buffers ----
+struct MaskPlan {
+    bool masked = false;        // false: the unmasked call (mask == NULL, or no allow-list and no flag)
+    bool skip_deleted = false;
+    std::vector<u32> used;      // the caller's masks that some query names, ascending; empty = no allow-list (one all-ones mask)
+    std::vector<u32> qmask;     // [B] -> index into `used`
+};
+// COS_OK or the refusal.  Masks no query names are neither uploaded nor part of the zero-norm screen.
+int32_t scan_mask_plan(const cos_scan_mask *mask, u32 B, MaskPlan &mp) {
+    if (!mask) return COS_OK;
+    if (mask->struct_size != sizeof(cos_scan_mask)) return cos_fail(COS_ERR_INVALID, "cos_scan_mask::struct_size is %u, expected %zu", mask->struct_size, sizeof(cos_scan_mask));
+    if (mask->flags & ~COS_SCAN_SKIP_DELETED) return cos_fail(COS_ERR_INVALID, "unknown cos_scan_mask::flags 0x%x", mask->flags);
+    const u32 G = mask->n_masks;
+    if (G > 0 && !mask->bits) return cos_fail(COS_ERR_INVALID, "cos_scan_mask::bits is NULL with n_masks = %u", G);
+    if (G > 1 && !mask->query_mask) return cos_fail(COS_ERR_INVALID, "cos_scan_mask::query_mask is NULL with n_masks = %u", G);
+    mp.skip_deleted = (mask->flags & COS_SCAN_SKIP_DELETED) != 0;
+    if (G == 0 && !mp.skip_deleted) return COS_OK;
+    mp.qmask.assign(B, 0u);
+    if (G > 0) {
+        std::vector<u32> slot(G, 0xFFFFFFFFu);
+        if (mask->query_mask) {
+            for (u32 b = 0; b < B; b++) {
+                if (mask->query_mask[b] >= G) return cos_fail(COS_ERR_INVALID, "query_mask[%u] = %u with n_masks = %u", b, mask->query_mask[b], G);
+                slot[mask->query_mask[b]] = 0;
+            }
+        } else
+            slot[0] = 0;
+        for (u32 g = 0; g < G; g++)
+            if (slot[g] == 0) { slot[g] = (u32)mp.used.size(); mp.used.push_back(g); }
+        if (mask->query_mask)
+            for (u32 b = 0; b < B; b++) mp.qmask[b] = slot[mask->query_mask[b]];
+    }
+    mp.masked = true;
+    return COS_OK;
+}
+struct MaskBufs { // grow-only, like the other buffers of a scan
+    DevArr<u32> user, eff, uni, qmask;
+};
+// the plan's masks on the device (stream st: the plan and the caller's arrays stay until the caller has drained it): sm for the kernels,
+// *uni = the union of the live sets
+hipError_t scan_mask_upload(const cos_index *ix, const cos_scan_mask *mask, const MaskPlan &mp, u32 B, MaskBufs &mb, hipStream_t st, ScanMask &sm, const u32 **uni) {
+    const u32 n = ix->n, words = (n + 31) / 32, G = mp.used.empty() ? 1u : (u32)mp.used.size();
+    hipError_t e = mb.eff.grow((size_t)G * words);
+    if (e == hipSuccess) e = mb.uni.grow(words);
+    if (e == hipSuccess) e = mb.qmask.grow(B);
+    if (e == hipSuccess && !mp.used.empty()) e = mb.user.grow((size_t)G * words);
+    for (u32 g = 0; g < (u32)mp.used.size() && e == hipSuccess; g++)
+        e = hipMemcpyAsync(mb.user.p + (size_t)g * words, mask->bits + (size_t)mp.used[g] * words, (size_t)words * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(mb.qmask.p, mp.qmask.data(), (size_t)B * 4, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(scan_mask_build_kernel, dim3((words + 255) / 256), dim3(256), 0, st, mp.used.empty() ? (const u32 *)nullptr : (const u32 *)mb.user.p,
+                       mp.skip_deleted ? (const u32 *)ix->d_deleted.p : (const u32 *)nullptr, G, words, n, mb.eff.p, mb.uni.p);
+    e = hipGetLastError();
+    sm =ScanMask{mb.eff.p, mb.qmask.p, words};
+    *uni = mb.uni.p;
+    return e;
+}
 
-extern "C" int32_t cos_bruteforce_topk(cos_index *ix, const float *queries, uint32_t B, uint32_t k, uint32_t *out_ids, float *out_scores) {
+// cos_bruteforce_topk (mask == nullptr, out_counts optional) and cos_bruteforce_topk_masked
+int32_t bruteforce_run(cos_index *ix, const float *queries, uint32_t B, uint32_t k, const cos_scan_mask *mask, uint32_t *out_ids, float *out_scores,
+                       uint32_t *out_counts) {
     if (!ix || !queries || !out_ids || !out_scores || B == 0) return cos_fail(COS_ERR_INVALID, "bad argument");
     if (!ix->have_vectors) return cos_fail(COS_ERR_NOT_READY, "upload vectors first");
     if (k == 0 || k > 512 || k > ix->n) return cos_fail(COS_ERR_INVALID, "k must be in [1, min(512, n)]");
+    MaskPlan mp;
+    if (int32_t mrc = scan_mask_plan(mask, B, mp)) return mrc;
     // survivors per query: the GEMM only generates candidates, so the pool holds at least 2k of them (64 for k <= 32, as ever)
     const u32 P = flat_pool_width(2 * k), R = P / SEL;
     int32_t rc = cos_set_device(ix);
@@ -642,8 +762,9 @@ extern "C" int32_t cos_bruteforce_topk(cos_index *ix, const float *queries, uint
     const u64 s_stride = ((u64)chunk + 63) & ~63ull;
     DevArr<float> d_q, d_qm, d_scores, d_os, d_dummy;
     DevArr<u64> d_pool, d_part, d_thr, d_app;
-    DevArr<u32> d_oi, d_appcnt, d_over;
+    DevArr<u32> d_oi, d_appcnt, d_over, d_oc;
     DevArr<uint8_t> d_codes;
+    MaskBufs mb;
     hipStream_t st = ix->own_stream;
     const u32 S = select_segments(B, chunk);
     HIP_TRY(d_q.alloc((size_t)B * dim));
@@ -659,13 +780,17 @@ extern "C" int32_t cos_bruteforce_topk(cos_index *ix, const float *queries, uint
     HIP_TRY(d_over.alloc(1));
     HIP_TRY(d_oi.alloc((size_t)B * k));
     HIP_TRY(d_os.alloc((size_t)B * k));
+    if (mp.masked) HIP_TRY(d_oc.alloc(B));
     // (from here on a ladder: the stream is drained below on every path before the buffers and `hover` go out of scope)
     hipError_t e = hipMemcpyAsync(d_q, queries, (size_t)B * dim * 4, hipMemcpyHostToDevice, st);
     // |q| in the reference's sequential order (vector_store.rs:414): reuse the F32 quantize kernel's raw_mags output
     if (e == hipSuccess) e = launch_quantize_rows(ENG_F32, d_q, dim, B, dim, 0.f, 0.f, d_codes, ((u64)dim * 4 + 15) & ~15ull, d_dummy, d_qm, st);
     for (const void *f : {(const void *)flat_gemm_f32<true, false>, (const void *)flat_gemm_f32<false, false>, (const void *)flat_gemm_f32<true, true>,
-                          (const void *)flat_gemm_f32<false, true>})
+                          (const void *)flat_gemm_f32<false, true>, (const void *)flat_gemm_f32<true, true, true>, (const void *)flat_gemm_f32<false, true, true>})
         if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GEMM_SMEM);
+    ScanMask sm{nullptr, nullptr, 0u};
+    const u32 *d_uni = nullptr; // (the brute force has no zero-norm screen)
+    if (e == hipSuccess && mp.masked) e = scan_mask_upload(ix, mask, mp, B, mb, st, sm, &d_uni);
     // float4 staging needs 16 B aligned rows: dim % 4 == 0 (hipMalloc'd bases are 256 B aligned; a borrowed raw pointer is checked)
     const bool vec = dim % 4 == 0 && ((uintptr_t)ix->d_raw & 15) == 0;
     for (int attempt = 0; attempt < 2 && e == hipSuccess; attempt++) {
@@ -674,7 +799,7 @@ extern "C" int32_t cos_bruteforce_topk(cos_index *ix, const float *queries, uint
         if (e == hipSuccess) e = hipMemsetAsync(d_thr, 0, (size_t)B * 8, st);
         if (e == hipSuccess) e = hipMemsetAsync(d_appcnt, 0, (size_t)B * 4, st);
         if (e == hipSuccess) e = hipMemsetAsync(d_over, 0, 4, st);
-        const FusedOut fo{d_thr, d_app, d_appcnt, APP_CAP, nullptr};
+        const FusedOut fo{d_thr, d_app, d_appcnt, APP_CAP, nullptr, sm};
         u32 n0 = 0;
         while (n0 < n && e == hipSuccess) {
             const bool use_fused = fused && n0 > 0;
@@ -683,7 +808,9 @@ extern "C" int32_t cos_bruteforce_topk(cos_index *ix, const float *queries, uint
             dim3 grid((nc + BN - 1) / BN, (B + BM - 1) / BM);
 #define GEMM_ARGS d_q, (u64)dim, d_qm, B, ix->d_raw, (u64)dim, ix->d_raw_mags, n0, nc, dim, d_scores, s_stride, fo
             if (use_fused) {
-                if (vec) hipLaunchKernelGGL((flat_gemm_f32<true, true>), grid, dim3(256), GEMM_SMEM, st, GEMM_ARGS);
+                if (mp.masked && vec) hipLaunchKernelGGL((flat_gemm_f32<true, true, true>), grid, dim3(256), GEMM_SMEM, st, GEMM_ARGS);
+                else if (mp.masked) hipLaunchKernelGGL((flat_gemm_f32<false, true, true>), grid, dim3(256), GEMM_SMEM, st, GEMM_ARGS);
+                else if (vec) hipLaunchKernelGGL((flat_gemm_f32<true, true>), grid, dim3(256), GEMM_SMEM, st, GEMM_ARGS);
                 else hipLaunchKernelGGL((flat_gemm_f32<false, true>), grid, dim3(256), GEMM_SMEM, st, GEMM_ARGS);
                 e = hipGetLastError();
                 if (e == hipSuccess && R == 1) {
@@ -695,8 +822,8 @@ extern "C" int32_t cos_bruteforce_topk(cos_index *ix, const float *queries, uint
                 if (vec) hipLaunchKernelGGL((flat_gemm_f32<true, false>), grid, dim3(256), GEMM_SMEM, st, GEMM_ARGS);
                 else hipLaunchKernelGGL((flat_gemm_f32<false, false>), grid, dim3(256), GEMM_SMEM, st, GEMM_ARGS);
                 e = hipGetLastError();
-                if (e == hipSuccess && R == 1) e = launch_select(d_scores, s_stride, B, n0, nc, d_part, select_segments(B, nc), d_pool, st, d_thr);
-                else if (e == hipSuccess) e = launch_flat_select_wide(R, d_scores, s_stride, B, n0, nc, d_part, select_segments(B, nc), d_pool, d_thr, st);
+                if (e == hipSuccess && R == 1) e = launch_select(d_scores, s_stride, B, n0, nc, d_part, select_segments(B, nc), d_pool, st, d_thr, sm);
+                else if (e == hipSuccess) e = launch_flat_select_wide(R, d_scores, s_stride, B, n0, nc, d_part, select_segments(B, nc), d_pool, d_thr, st, sm);
             }
 #undef GEMM_ARGS
             n0 += nc;
@@ -714,9 +841,26 @@ extern "C" int32_t cos_bruteforce_topk(cos_index *ix, const float *queries, uint
         e = launch_flat_rerank_wide(R, true, d_q, (u64)dim, d_qm, B, ix->d_raw, (u64)dim, ix->d_raw_mags, dim, d_pool, P, k, ix->p.id_base, d_oi, d_os, nullptr, st);
     if (e == hipSuccess) e = hipMemcpyAsync(out_ids, d_oi, (size_t)B * k * 4, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipMemcpyAsync(out_scores, d_os, (size_t)B * k * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && mp.masked) { // a query may have fewer live rows than k
+        hipLaunchKernelGGL(pool_count_kernel, dim3(B), dim3(64), 0, st, (const u64 *)d_pool, P, B, k, d_oc.p);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(out_counts, d_oc, (size_t)B * 4, hipMemcpyDeviceToHost, st);
+    }
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     HIP_TRY(e);
+    if (!mp.masked && out_counts) std::fill(out_counts, out_counts + B, k); // k <= n: every list is full
     return COS_OK;
+}
+
+} // namespace
+
+extern "C" int32_t cos_bruteforce_topk(cos_index *ix, const float *queries, uint32_t B, uint32_t k, uint32_t *out_ids, float *out_scores) {
+    return bruteforce_run(ix, queries, B, k, nullptr, out_ids, out_scores, nullptr);
+}
+extern "C" int32_t cos_bruteforce_topk_masked(cos_index *ix, const float *queries, uint32_t B, uint32_t k, const cos_scan_mask *mask, uint32_t *out_ids,
+                                              float *out_scores, uint32_t *out_counts) {
+    if (!out_counts) return cos_fail(COS_ERR_INVALID, "bad argument");
+    return bruteforce_run(ix, queries, B, k, mask, out_ids, out_scores, out_counts);
 }
 
 // Per-index workspace of cos_flat_search_batch: every buffer is grow-only and lives until the index is destroyed (or its
@@ -732,7 +876,10 @@ struct FlatWs {
     u32 cs_n = 0;
     bool zn_valid = false, zn_zero = false; // "a stored vector has a zero norm" for the current upload (cosine's CalculationError screen)
     u32 zn_n = 0;
-    DevArr<u32> out;          // [ids B x k | scores B x k | counts B | zero-norm flag, overflow flag]: ONE copy back per call
+    // a masked call's effective masks.  Its zero-norm answer depends on the masks and is computed per call: the cached flag above stays
+    // the unmasked calls'; the code sums above do not depend on a mask and serve both
+    MaskBufs mask;
+    DevArr<u32> out;         // [ids B x k | scores B x k | counts B | zero-norm flag, overflow flag]: ONE copy back per call
     PinArr<u32> h_out;        // its pinned landing area
     std::vector<hipEvent_t> evs;
     hipError_t event(size_t i, hipEvent_t *out) {
@@ -760,10 +907,13 @@ void cos_flat_ws_release(cos_index *ix) { // cos_index_destroy, and every upload
 // u8 and the three bit-plane storages (binary, quaternary, octal): integer dots, exact in any order.  f16 / f32 codes are refused: their
 // reference dots are order-dependent f32 chains that an MFMA cannot reproduce, so the candidate set could not be exact.
 // ------------------------------------------------------------------------------------------------
-extern "C" int32_t cos_flat_search_batch(cos_index *ix, const float *queries, uint32_t B, uint32_t top_k, uint32_t *out_ids, float *out_scores,
-                                         uint32_t *out_counts, cos_flat_stats *stats) {
+// cos_flat_search_batch (mask == nullptr) and cos_flat_search_masked_batch
+static int32_t flat_search_run(cos_index *ix, const float *queries, uint32_t B, uint32_t top_k, const cos_scan_mask *mask, uint32_t *out_ids,
+                               float *out_scores, uint32_t *out_counts, cos_flat_stats *stats) {
     if (!ix || !queries || !out_ids || !out_scores || !out_counts || B == 0) return cos_fail(COS_ERR_INVALID, "bad argument");
     if (!ix->have_vectors) return cos_fail(COS_ERR_NOT_READY, "upload vectors first");
+    MaskPlan mp;
+    if (int32_t mrc = scan_mask_plan(mask, B, mp)) return mrc;
     if (top_k == 0 || top_k > 204) return cos_fail(COS_ERR_UNIMPLEMENTED, "flat search keeps at most 1024 survivors (5 * top_k): top_k must be in [1, 204]");
     // survivors per query: the smallest pool that holds the 5 * top_k rerank candidates (64 for top_k <= 12, as ever).  Every buffer
     // below is sized and indexed by this call's P, not by the widest call the handle has served.
@@ -810,6 +960,8 @@ extern "C" int32_t cos_flat_search_batch(cos_index *ix, const float *queries, ui
     uint8_t *d_qc = nullptr, *d_qd = nullptr, *d_qdp = nullptr;
     u32 *d_qs = nullptr, *d_cs = nullptr, *d_oi = nullptr, *d_oc = nullptr, *d_zero = nullptr, *d_appcnt = nullptr;
     u64 *d_pool = nullptr, *d_part = nullptr, *d_thr = nullptr, *d_app = nullptr;
+    ScanMask sm{nullptr, nullptr, 0u}; // masked call: the effective masks (W->mask)
+    const u32 *d_uni = nullptr;        // ... and the union of the queries' live sets
     size_t n_ev = 0; // (start, stop) events of the GEMM launches, read after the last one
     float gemm_ms = 0.f;
     u32 launches = 0;
@@ -842,6 +994,7 @@ extern "C" int32_t cos_flat_search_batch(cos_index *ix, const float *queries, ui
             need(W->oi, d_oi, (size_t)B * top_k);
             need(W->os, d_os, (size_t)B * top_k);
             need(W->oc, d_oc, B);
+            if (e == hipSuccess && mp.masked) e = scan_mask_upload(ix, mask, mp, B, W->mask, st, sm, &d_uni);
             if (e == hipSuccess) e = hipMemcpyAsync(d_q, queries, (size_t)B * dim * 4, hipMemcpyHostToDevice, st);
             if (e == hipSuccess) e = launch_quantize_rows(ix->eng, d_q, dim, B, dim, ix->p.range_lo, ix->p.range_hi, d_qc, ix->row_stride, d_qm, d_qrm, st);
             if (e == hipSuccess && ix->eng == ENG_U8) {
@@ -867,7 +1020,13 @@ extern "C" int32_t cos_flat_search_batch(cos_index *ix, const float *queries, ui
             // The stored vectors' answer is computed once per upload (and read back then); the queries' flag stays on the device and comes
             // back with the results: a call with a zero-norm query runs its scan for nothing and then reports the error — until round 6
             // every call stopped here for a device round trip (~50 us of a 1.9 ms call) before its first GEMM.
-            if (e == hipSuccess && ix->p.metric == COS_METRIC_COSINE) {
+            // A masked call screens the rows that are live for at least one of its queries, every time (the answer is the masks'); its flag
+            // travels back with the queries' flag.
+            if (e == hipSuccess && ix->p.metric == COS_METRIC_COSINE && mp.masked) {
+                hipLaunchKernelGGL(any_zero_masked_kernel, dim3(1024), dim3(256), 0, st, (const float *)ix->d_mags, n, d_uni, d_zero);
+                hipLaunchKernelGGL(any_zero_kernel, dim3(64), dim3(256), 0, st, (const float *)d_qm, B, d_zero);
+                e = hipGetLastError();
+            } else if (e == hipSuccess && ix->p.metric == COS_METRIC_COSINE) {
                 if (!W->zn_valid || W->zn_n != n) {
                     u32 hz = 0;
                     hipLaunchKernelGGL(any_zero_kernel, dim3(1024), dim3(256), 0, st, (const float *)ix->d_mags, n, d_zero);
@@ -890,7 +1049,7 @@ extern "C" int32_t cos_flat_search_batch(cos_index *ix, const float *queries, ui
             hipLaunchKernelGGL(flat_reset_kernel, dim3(64), dim3(256), 0, st, d_pool, (u64)B * P, d_thr, d_appcnt, B, d_zero + 1); // (d_zero + 1: overflow flag of the fused path)
             e = hipGetLastError();
         }
-        FusedOut fo{d_thr, d_app, d_appcnt, APP_CAP, d_qd};
+        FusedOut fo{d_thr, d_app, d_appcnt, APP_CAP, d_qd, sm};
         u32 n0 = 0, seen = 0;
         while (n0 < n && e == hipSuccess) {
             const bool use_fused = fused && n0 > 0;
@@ -907,6 +1066,8 @@ extern "C" int32_t cos_flat_search_batch(cos_index *ix, const float *queries, ui
 #define FLAT_ARGS d_qc, d_qm, d_qs, B, ix->d_codes, ix->d_mags, d_cs, ix->row_stride, n0, nc, kdims, ix->p.metric, d_scores, s_stride, fo
 #define FLAT_LAUNCH(E, F, P) hipLaunchKernelGGL((flat_codes_gemm_i8<E, F, P>), grid, dim3(512), 0, st, FLAT_ARGS)
 #define FLAT_LAUNCH_PF(E, F) do { if (pf == 2) FLAT_LAUNCH(E, F, 2); else if (pf == 3) FLAT_LAUNCH(E, F, 3); else FLAT_LAUNCH(E, F, 1); } while (0)
+// fused chunk of a masked call on the tile kernel: the masked instantiation, one k panel in flight (the default; the knob flat_pf steers the unmasked ones)
+#define FLAT_LAUNCH_MASKED(E) hipLaunchKernelGGL((flat_codes_gemm_i8<E, true, 1, true>), grid, dim3(512), 0, st, FLAT_ARGS)
             if (use_fused && use_areg) {
                 e = launch_flat_scan(ix->eng, kdims, (u32)n_cus, st, d_qdp, d_qm, B, ix->d_codes, ix->d_mags, ix->row_stride, n0, nc, ix->p.metric, fo, use_fp4);
                 if (e != hipSuccess) break;
@@ -914,14 +1075,15 @@ extern "C" int32_t cos_flat_search_batch(cos_index *ix, const float *queries, ui
                 e = launch_flat_scan_u8(kdims, (u32)n_cus, st, d_qc, d_qs, d_qm, B, ix->d_codes, d_cs, ix->d_mags, ix->row_stride, n0, nc, ix->p.metric, fo);
                 if (e != hipSuccess) break;
             } else if (ix->eng == ENG_U8) {
-                if (use_fused) FLAT_LAUNCH_PF(ENG_U8, true); else FLAT_LAUNCH_PF(ENG_U8, false);
+                if (use_fused && mp.masked) FLAT_LAUNCH_MASKED(ENG_U8); else if (use_fused) FLAT_LAUNCH_PF(ENG_U8, true); else FLAT_LAUNCH_PF(ENG_U8, false);
             } else if (ix->eng == ENG_Q2) {
-                if (use_fused) FLAT_LAUNCH_PF(ENG_Q2, true); else FLAT_LAUNCH_PF(ENG_Q2, false);
+                if (use_fused && mp.masked) FLAT_LAUNCH_MASKED(ENG_Q2); else if (use_fused) FLAT_LAUNCH_PF(ENG_Q2, true); else FLAT_LAUNCH_PF(ENG_Q2, false);
             } else if (ix->eng == ENG_Q1) {
-                if (use_fused) FLAT_LAUNCH_PF(ENG_Q1, true); else FLAT_LAUNCH_PF(ENG_Q1, false);
+                if (use_fused && mp.masked) FLAT_LAUNCH_MASKED(ENG_Q1); else if (use_fused) FLAT_LAUNCH_PF(ENG_Q1, true); else FLAT_LAUNCH_PF(ENG_Q1, false);
             } else {
-                if (use_fused) FLAT_LAUNCH_PF(ENG_Q3, true); else FLAT_LAUNCH_PF(ENG_Q3, false);
+                if (use_fused && mp.masked) FLAT_LAUNCH_MASKED(ENG_Q3); else if (use_fused) FLAT_LAUNCH_PF(ENG_Q3, true); else FLAT_LAUNCH_PF(ENG_Q3, false);
             }
+#undef FLAT_LAUNCH_MASKED
 #undef FLAT_LAUNCH_PF
 #undef FLAT_LAUNCH
 #undef FLAT_ARGS
@@ -934,9 +1096,9 @@ extern "C" int32_t cos_flat_search_batch(cos_index *ix, const float *queries, ui
                 } else if (use_fused)
                     e = launch_flat_append_wide(R, d_app, d_appcnt, APP_CAP, B, d_pool, d_thr, d_zero + 1, st);
                 else if (R == 1)
-                    e = launch_select(d_scores, s_stride, B, n0, nc, d_part, S, d_pool, st, d_thr);
+                    e = launch_select(d_scores, s_stride, B, n0, nc, d_part, S, d_pool, st, d_thr, sm);
                 else
-                    e = launch_flat_select_wide(R, d_scores, s_stride, B, n0, nc, d_part, S, d_pool, d_thr, st);
+                    e = launch_flat_select_wide(R, d_scores, s_stride, B, n0, nc, d_part, S, d_pool, d_thr, st, sm);
             }
             launches++;
             streamed += (double)nc * (double)ix->row_stride * (double)((B + CM - 1) / CM);
@@ -987,6 +1149,75 @@ extern "C" int32_t cos_flat_search_batch(cos_index *ix, const float *queries, ui
     }
     HIP_TRY(e);
     if (zero) return cos_fail(COS_ERR_CALCULATION, "zero-norm query or stored vector: DistanceError::CalculationError (cosine.rs:228-232)");
+    return COS_OK;
+}
+
+extern "C" int32_t cos_flat_search_batch(cos_index *ix, const float *queries, uint32_t B, uint32_t top_k, uint32_t *out_ids, float *out_scores,
+                                         uint32_t *out_counts, cos_flat_stats *stats) {
+    return flat_search_run(ix, queries, B, top_k, nullptr, out_ids, out_scores, out_counts, stats);
+}
+extern "C" int32_t cos_flat_search_masked_batch(cos_index *ix, const float *queries, uint32_t B, uint32_t top_k, const cos_scan_mask *mask, uint32_t *out_ids,
+                                                float *out_scores, uint32_t *out_counts, cos_flat_stats *stats) {
+    return flat_search_run(ix, queries, B, top_k, mask, out_ids, out_scores, out_counts, stats);
+}
+
+// ---- the deleted set ----
+hipError_t cos_deleted_reset(cos_index *ix, u32 n, hipStream_t st) {
+    const size_t words = ((size_t)n + 31) / 32;
+    hipError_t e = ix->d_deleted.alloc(words);
+    if (e == hipSuccess) e = hipMemsetAsync(ix->d_deleted.p, 0, words * 4, st);
+    return e;
+}
+hipError_t cos_deleted_grow(cos_index *ix, u32 n0, u32 n1, hipStream_t st) {
+    const size_t w0 = ((size_t)n0 + 31) / 32, w1 = ((size_t)n1 + 31) / 32;
+    DevArr<u32> grown;
+    hipError_t e = grown.alloc(w1);
+    if (e == hipSuccess) e = hipMemsetAsync(grown.p, 0, w1 * 4, st);
+    // (bits at and past n0 of the old last word are clear: cos_index_delete refuses ids >= n)
+    if (e == hipSuccess && ix->d_deleted.p) e = hipMemcpyAsync(grown.p, ix->d_deleted.p, w0 * 4, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st); // before the old bitmap is freed
+    if (e == hipSuccess) grown.swap(ix->d_deleted);
+    return e;
+}
+hipError_t cos_deleted_mark(cos_index *ix, const u32 *ids, u32 m, hipStream_t st) {
+    if (m == 0) return hipSuccess;
+    DevArr<u32> d_ids;
+    hipError_t e = d_ids.alloc(m);
+    if (e == hipSuccess && !ix->d_deleted.p) e = cos_deleted_reset(ix, ix->n, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_ids.p, ids, (size_t)m * 4, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(deleted_mark_kernel, dim3((m + 255) / 256), dim3(256), 0, st, (const u32 *)d_ids.p, m, ix->d_deleted.p);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(st); // d_ids goes out of scope
+    return e;
+}
+extern "C" int32_t cos_index_deleted_count(cos_index *ix, uint32_t *out) {
+    if (!ix || !out) return cos_fail(COS_ERR_INVALID, "null argument");
+    if (!ix->have_vectors) return cos_fail(COS_ERR_NOT_READY, "upload vectors first");
+    int32_t rc = cos_set_device(ix);
+    if (rc) return rc;
+    const u32 words = (ix->n + 31) / 32;
+    hipStream_t st = ix->own_stream;
+    DevArr<u32> d_cnt;
+    HIP_TRY(d_cnt.alloc(1));
+    hipError_t e = hipMemsetAsync(d_cnt.p, 0, 4, st);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(popcount_kernel, dim3(std::min<u32>((words + 255) / 256, 1024u)), dim3(256), 0, st, (const u32 *)ix->d_deleted.p, words, d_cnt.p);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_cnt.p, 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    HIP_TRY(e);
+    return COS_OK;
+}
+extern "C" int32_t cos_index_download_deleted(cos_index *ix, uint32_t *bits) {
+    if (!ix || !bits) return cos_fail(COS_ERR_INVALID, "null argument");
+    if (!ix->have_vectors) return cos_fail(COS_ERR_NOT_READY, "upload vectors first");
+    int32_t rc = cos_set_device(ix);
+    if (rc) return rc;
+    hipError_t e = hipMemcpyAsync(bits, ix->d_deleted.p, (size_t)((ix->n + 31) / 32) * 4, hipMemcpyDeviceToHost, ix->own_stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ix->own_stream);
+    HIP_TRY(e);
     return COS_OK;
 }
 

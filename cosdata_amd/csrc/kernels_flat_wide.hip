@@ -20,10 +20,10 @@ using namespace cosdev;
 
 namespace {
 
-template <int R>
-__global__ __launch_bounds__(64) void flat_select_segments_w(const float *__restrict__ scores, u64 s_stride, u32 B, u32 n0, u32 n_chunk, u32 seg_len,
-                                                             u64 *__restrict__ part /*[B][S][64 R]*/) {
-    __shared__ u64 batch[WAVE * R];
+// MASKED (flat_select_segments_w_masked): a row outside the query's mask gives the empty key (flat_scan.h ScanMask)
+template <int R, bool MASKED>
+__device__ __forceinline__ void select_segments_w_body(const float *__restrict__ scores, u64 s_stride, u32 B, u32 n0, u32 n_chunk, u32 seg_len,
+                                                       u64 *__restrict__ part /*[B][S][64 R]*/, const ScanMask &m, u64 *batch /* LDS [64 R] */) {
     const int lane = threadIdx.x;
     const u32 q = blockIdx.x, seg = blockIdx.y, S = gridDim.y;
     if (q >= B) return;
@@ -34,10 +34,22 @@ __global__ __launch_bounds__(64) void flat_select_segments_w(const float *__rest
     const float *sr = scores + (u64)q * s_stride;
     const u32 c0 = seg * seg_len, c1 = (c0 + seg_len < n_chunk) ? c0 + seg_len : n_chunk;
     const u32 count = c1 > c0 ? c1 - c0 : 0u;
-    fold_stream<R>(pool, thr, batch, count, [&](u32 i) { return pack_key(simkey(sr[c0 + i]), n0 + c0 + i); }, lane);
+    fold_stream<R>(pool, thr, batch, count, [&](u32 i) { return scan_live<MASKED>(m, q, n0 + c0 + i) ? pack_key(simkey(sr[c0 + i]), n0 + c0 + i) : 0ull; }, lane);
     u64 *dst = part + ((u64)q * S + seg) * (WAVE * R) + (u32)lane * R;
 #pragma unroll
     for (int r = 0; r < R; r++) dst[r] = pool[r];
+}
+template <int R>
+__global__ __launch_bounds__(64) void flat_select_segments_w(const float *__restrict__ scores, u64 s_stride, u32 B, u32 n0, u32 n_chunk, u32 seg_len,
+                                                             u64 *__restrict__ part /*[B][S][64 R]*/) {
+    __shared__ u64 batch[WAVE * R];
+    select_segments_w_body<R, false>(scores, s_stride, B, n0, n_chunk, seg_len, part, ScanMask{nullptr, nullptr, 0u}, batch);
+}
+template <int R>
+__global__ __launch_bounds__(64) void flat_select_segments_w_masked(const float *__restrict__ scores, u64 s_stride, u32 B, u32 n0, u32 n_chunk, u32 seg_len,
+                                                                    u64 *__restrict__ part /*[B][S][64 R]*/, const ScanMask m) {
+    __shared__ u64 batch[WAVE * R];
+    select_segments_w_body<R, true>(scores, s_stride, B, n0, n_chunk, seg_len, part, m, batch);
 }
 
 template <int R>
@@ -168,9 +180,13 @@ namespace cosdev {
     }
 
 hipError_t launch_flat_select_wide(u32 R, const float *d_scores, u64 s_stride, u32 B, u32 n0, u32 nc, u64 *d_part, u32 S, u64 *d_pool, u64 *d_thr,
-                                   hipStream_t st) {
+                                   hipStream_t st, const ScanMask &m) {
     const u32 seg_len = ((nc + S - 1) / S + 63) / 64 * 64;
-    WIDE_DISPATCH(R, hipLaunchKernelGGL(flat_select_segments_w<RR>, dim3(B, S), dim3(64), 0, st, d_scores, s_stride, B, n0, nc, seg_len, d_part))
+    if (m.bits) {
+        WIDE_DISPATCH(R, hipLaunchKernelGGL(flat_select_segments_w_masked<RR>, dim3(B, S), dim3(64), 0, st, d_scores, s_stride, B, n0, nc, seg_len, d_part, m))
+    } else {
+        WIDE_DISPATCH(R, hipLaunchKernelGGL(flat_select_segments_w<RR>, dim3(B, S), dim3(64), 0, st, d_scores, s_stride, B, n0, nc, seg_len, d_part))
+    }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     WIDE_DISPATCH(R, hipLaunchKernelGGL(flat_select_merge_w<RR>, dim3(B), dim3(64), 0, st, (const u64 *)d_part, B, S, d_pool, d_thr))

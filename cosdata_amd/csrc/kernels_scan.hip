@@ -11,6 +11,13 @@
 #include "tuning.h"
 #include "walk_plan.h"
 
+// The flat scan kernels exist twice: plain, and MASKED (a survivor also passes its query's row mask, flat_scan.h).  They are the longest
+// compile of the library, so the masked half is a translation unit of its own — kernels_scan_masked.hip includes this file with
+// COS_SCAN_MASKED_TU set and gets the masked instantiations and their two launchers, nothing else — and the halves build side by side.
+#ifndef COS_SCAN_MASKED_TU
+#define COS_SCAN_MASKED_TU 0
+#endif
+
 using namespace cosdev;
 
 namespace {
@@ -171,7 +178,7 @@ __device__ __forceinline__ void static_for(F &&f) {
     }
 }
 
-template <int KC, int ENG = ENG_Q2>
+template <int KC, int ENG = ENG_Q2, bool MASKED = false /* survivors pass the query's row mask (flat_scan.h ScanMask) */>
 __global__ __launch_bounds__(256) void flat_scan_q2_areg(const uint8_t *__restrict__ qdig /*[B][64 KC] permuted digits*/,
                                                          const float *__restrict__ qmags, u32 B, const uint8_t *__restrict__ codes,
                                                          const float *__restrict__ mags, u64 row_stride, u32 n0, u32 n_chunk, u32 metric,
@@ -278,7 +285,7 @@ __global__ __launch_bounds__(256) void flat_scan_q2_areg(const uint8_t *__restri
             for (int r = 0; r < 16; r++) {
                 const u32 row = rbase + (r & 3) + 8 * (r >> 2);
                 const float dotf = (float)(u32)acc[P][i][j][r];
-                if (row < B && __builtin_fmaf(dotf, rx, -T[i][r]) >= 0.0f) {
+                if (row < B && __builtin_fmaf(dotf, rx, -T[i][r]) >= 0.0f && scan_live<MASKED>(fo.m, row, n0 + col)) {
                     const u32 sp = atomicAdd(stage_cnt, 1u);
                     if (sp < AREG_STAGE) {
                         stage[3 * sp] = col;
@@ -420,7 +427,7 @@ __device__ __forceinline__ void fp4_mfma(f32x16 &acc, const i32x4 &afrag, const 
     acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, FIRST ? z : acc, 4, 4, 0, 0x7F7F7F7F, 0, 0x7F7F7F7F);
 }
 
-template <int KC, int ENG = ENG_Q2>
+template <int KC, int ENG = ENG_Q2, bool MASKED = false>
 __global__ __launch_bounds__(256) void flat_scan_q2_fp4(const uint8_t *__restrict__ qnib /*[B][32 KC] nibble bytes*/,
                                                         const float *__restrict__ qmags, u32 B, const uint8_t *__restrict__ codes,
                                                         const float *__restrict__ mags, u64 row_stride, u32 n0, u32 n_chunk, u32 metric,
@@ -517,7 +524,7 @@ __global__ __launch_bounds__(256) void flat_scan_q2_fp4(const uint8_t *__restric
             for (int r = 0; r < 16; r++) {
                 const u32 row = rbase + (r & 3) + 8 * (r >> 2);
                 const float q4 = acc[P][i][j][r];
-                if (row < B && __builtin_fmaf(q4, rx, -T[i][r]) >= 0.0f) {
+                if (row < B && __builtin_fmaf(q4, rx, -T[i][r]) >= 0.0f && scan_live<MASKED>(fo.m, row, n0 + col)) {
                     const u32 dot = (u32)(q4 * 4.0f); // exact: q4 is a multiple of 1/4 below 2^22
                     const u32 sp = atomicAdd(stage_cnt, 1u);
                     if (sp < AREG_STAGE) {
@@ -626,7 +633,7 @@ __global__ __launch_bounds__(256) void flat_scan_q2_fp4(const uint8_t *__restric
 // epilogue of a tile runs in line, right after its last k step, while the SIMD's other wave multiplies.  Same estimate, same survivors,
 // same staging and exact test as above: the results are the tile kernel's bit for bit.
 // ------------------------------------------------------------------------------------------------
-template <int KC, int ORDER, int ENG = ENG_Q2>
+template <int KC, int ORDER, int ENG = ENG_Q2, bool MASKED = false>
 __global__ __launch_bounds__(512) void flat_scan_q2_fp4_w8(const uint8_t *__restrict__ qnib /*[B][32 KC] nibble bytes*/, const float *__restrict__ qmags, u32 B,
                                                            const uint8_t *__restrict__ codes, const float *__restrict__ mags, u64 row_stride, u32 n0,
                                                            u32 n_chunk, u32 metric, const FusedOut fo) {
@@ -786,7 +793,7 @@ __global__ __launch_bounds__(512) void flat_scan_q2_fp4_w8(const uint8_t *__rest
                     for (int r = 0; r < 16; r++) {
                         const u32 row = rbase + (r & 3) + 8 * (r >> 2);
                         const float q4 = acc[i][r];
-                        if (row < B && __builtin_fmaf(q4, rx, -T[i][r]) >= 0.0f) {
+                        if (row < B && __builtin_fmaf(q4, rx, -T[i][r]) >= 0.0f && scan_live<MASKED>(fo.m, row, n0 + colx)) {
                             const u32 dot = (u32)(q4 * 4.0f); // exact: q4 is a multiple of 1/4 below 2^22
                             const u32 sp = atomicAdd(stage_cnt, 1u);
                             if (sp < AREG_STAGE) {
@@ -990,7 +997,7 @@ __global__ __launch_bounds__(256) void level_table_areg(const uint8_t *__restric
 // append at the end of the kernel (areg_append: the value that is ranked is dot / (|q| |v|) exactly as the tile kernel forms it, so the
 // results are the tile kernel's bit for bit; tuning knob flat_tile_kernel = 1 keeps that one).
 // ------------------------------------------------------------------------------------------------
-template <int KC, int RB /* row blocks of 32 queries per wave: 2 (K <= 768), 1 (K = 1024: 128 AccVGPRs of fragments) */>
+template <int KC, int RB /* row blocks of 32 queries per wave: 2 (K <= 768), 1 (K = 1024: 128 AccVGPRs of fragments) */, bool MASKED = false>
 __global__ __launch_bounds__(256) void flat_scan_u8_areg(const uint8_t *__restrict__ qcodes /*[B][64 KC]*/, const u32 *__restrict__ qsums,
                                                          const float *__restrict__ qmags, u32 B, const uint8_t *__restrict__ codes,
                                                          const u32 *__restrict__ csums, const float *__restrict__ mags, u64 row_stride, u32 n0,
@@ -1105,7 +1112,7 @@ __global__ __launch_bounds__(256) void flat_scan_u8_areg(const uint8_t *__restri
                     for (int r = 0; r < 16; r++) {
                         const u32 row = rbase + (r & 3) + 8 * (r >> 2);
                         const u32 dot = (u32)(acc[i][j][r] + rqs[i][r] + cs);
-                        if (row < B && __builtin_fmaf((float)dot, rx, -T[i][r]) >= 0.0f) {
+                        if (row < B && __builtin_fmaf((float)dot, rx, -T[i][r]) >= 0.0f && scan_live<MASKED>(fo.m, row, n0 + col)) {
                             const u32 sp = atomicAdd(stage_cnt, 1u);
                             if (sp < AREG_STAGE) {
                                 stage[3 * sp] = col;
@@ -1133,22 +1140,26 @@ __global__ __launch_bounds__(256) void flat_scan_u8_areg(const uint8_t *__restri
 
 namespace cosdev {
 
+#if !COS_SCAN_MASKED_TU
 // KC = k chunks of 64 dims; false when this K has no instantiation (the tile kernel runs instead)
 bool flat_scan_supported(u32 kdims) {
     const u32 kc = kdims / 64;
     return kdims % 64 == 0 && (kc == 2 || kc == 4 || kc == 6 || kc == 8 || kc == 12 || kc == 16);
 }
 bool flat_scan_supported(int eng, u32 kdims) { return flat_scan_supported(kdims) && !(eng == ENG_Q3 && kdims == 1024); }
-template <int KC, int ENG>
+#endif
+// M = COS_SCAN_MASKED_TU: this translation unit's half of the flat scan kernels (masked or not)
+constexpr bool SCAN_M = COS_SCAN_MASKED_TU != 0;
+template <int KC, int ENG, bool M>
 static hipError_t launch_areg_kc(dim3 grid, hipStream_t st, const uint8_t *qdig, const float *qmags, u32 B, const uint8_t *codes, const float *mags,
                                  u64 row_stride, u32 n0, u32 nc, u32 metric, const FusedOut &fo) {
     const size_t lds = (size_t)2 * 64 * (KC * 64 + 16) + (size_t)AREG_STAGE * 12 + 16;
-    hipError_t e = hipFuncSetAttribute((const void *)flat_scan_q2_areg<KC, ENG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute((const void *)flat_scan_q2_areg<KC, ENG, M>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((flat_scan_q2_areg<KC, ENG>), grid, dim3(256), lds, st, qdig, qmags, B, codes, mags, row_stride, n0, nc, metric, fo);
+    hipLaunchKernelGGL((flat_scan_q2_areg<KC, ENG, M>), grid, dim3(256), lds, st, qdig, qmags, B, codes, mags, row_stride, n0, nc, metric, fo);
     return hipGetLastError();
 }
-template <int KC, int ENG>
+template <int KC, int ENG, bool M>
 static hipError_t launch_fp4_kc(dim3 grid, hipStream_t st, const uint8_t *qnib, const float *qmags, u32 B, const uint8_t *codes, const float *mags,
                                 u64 row_stride, u32 n0, u32 nc, u32 metric, const FusedOut &fo) {
     const size_t lds = (size_t)2 * 64 * (KC * 32 + 16) + (size_t)AREG_STAGE * 12 + 16;
@@ -1157,10 +1168,10 @@ static hipError_t launch_fp4_kc(dim3 grid, hipStream_t st, const uint8_t *qnib, 
         auto go = [&](auto Oc) -> hipError_t {
             constexpr int ORDER = decltype(Oc)::value, TW = ORDER >= 3 ? 128 : 64;
             const size_t lds8 = (size_t)2 * TW * (KC * 32 + 16) + (size_t)AREG_STAGE * 12 + 16;
-            hipError_t e8 = hipFuncSetAttribute((const void *)flat_scan_q2_fp4_w8<KC, ORDER, ENG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds8);
+            hipError_t e8 = hipFuncSetAttribute((const void *)flat_scan_q2_fp4_w8<KC, ORDER, ENG, M>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds8);
             if (e8 != hipSuccess) return e8;
             const dim3 g8(std::min(grid.x, (nc + TW - 1) / TW), grid.y);
-            hipLaunchKernelGGL((flat_scan_q2_fp4_w8<KC, ORDER, ENG>), g8, dim3(512), lds8, st, qnib, qmags, B, codes, mags, row_stride, n0, nc, metric, fo);
+            hipLaunchKernelGGL((flat_scan_q2_fp4_w8<KC, ORDER, ENG, M>), g8, dim3(512), lds8, st, qnib, qmags, B, codes, mags, row_stride, n0, nc, metric, fo);
             return hipGetLastError();
         };
         if (w8 == 1) return go(std::integral_constant<int, 0>{});
@@ -1168,19 +1179,20 @@ static hipError_t launch_fp4_kc(dim3 grid, hipStream_t st, const uint8_t *qnib, 
         if (w8 == 3) return go(std::integral_constant<int, 2>{});
         if (w8 >= 4) return go(std::integral_constant<int, 3>{});
     }
-    hipError_t e = hipFuncSetAttribute((const void *)flat_scan_q2_fp4<KC, ENG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute((const void *)flat_scan_q2_fp4<KC, ENG, M>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((flat_scan_q2_fp4<KC, ENG>), grid, dim3(256), lds, st, qnib, qmags, B, codes, mags, row_stride, n0, nc, metric, fo);
+    hipLaunchKernelGGL((flat_scan_q2_fp4<KC, ENG, M>), grid, dim3(256), lds, st, qnib, qmags, B, codes, mags, row_stride, n0, nc, metric, fo);
     return hipGetLastError();
 }
 // eng = ENG_Q1 / ENG_Q2 / ENG_Q3 (the row expansion, ScanRow).  fp4 (binary, quaternary) = the e2m1 form of the digits on the scaled MFMA
 // (flat_scan_q2_fp4; qdig then holds the nibble rows of launch_flat_scan_expand_queries(..., fp4 = true)), else the i8 digits (flat_scan_q2_areg)
-template <int ENG>
+// M: the masked instantiations (fo.m set); an unmasked call launches exactly the kernels it launched before masks existed
+template <int ENG, bool M>
 static hipError_t launch_flat_scan_eng(u32 kdims, dim3 grid, hipStream_t st, const uint8_t *qdig, const float *qmags, u32 B, const uint8_t *codes,
                                        const float *mags, u64 row_stride, u32 n0, u32 nc, u32 metric, const FusedOut &fo, bool fp4) {
     if constexpr (ENG != ENG_Q3) {
         if (fp4) {
-#define FP4_CASE(KC) case KC: return launch_fp4_kc<KC, ENG>(grid, st, qdig, qmags, B, codes, mags, row_stride, n0, nc, metric, fo)
+#define FP4_CASE(KC) case KC: return launch_fp4_kc<KC, ENG, M>(grid, st, qdig, qmags, B, codes, mags, row_stride, n0, nc, metric, fo)
             switch (kdims / 64) {
                 FP4_CASE(2); FP4_CASE(4); FP4_CASE(6); FP4_CASE(8); FP4_CASE(12); FP4_CASE(16);
                 default: return hipErrorInvalidValue;
@@ -1189,48 +1201,67 @@ static hipError_t launch_flat_scan_eng(u32 kdims, dim3 grid, hipStream_t st, con
         }
     } else if (fp4)
         return hipErrorInvalidValue;
-#define AREG_CASE(KC) case KC: return launch_areg_kc<KC, ENG>(grid, st, qdig, qmags, B, codes, mags, row_stride, n0, nc, metric, fo)
+#define AREG_CASE(KC) case KC: return launch_areg_kc<KC, ENG, M>(grid, st, qdig, qmags, B, codes, mags, row_stride, n0, nc, metric, fo)
     switch (kdims / 64) {
         AREG_CASE(2); AREG_CASE(4); AREG_CASE(6); AREG_CASE(8); AREG_CASE(12);
         case 16:
-            if constexpr (ENG != ENG_Q3) return launch_areg_kc<16, ENG>(grid, st, qdig, qmags, B, codes, mags, row_stride, n0, nc, metric, fo);
+            if constexpr (ENG != ENG_Q3) return launch_areg_kc<16, ENG, M>(grid, st, qdig, qmags, B, codes, mags, row_stride, n0, nc, metric, fo);
             return hipErrorInvalidValue; // flat_scan_supported(ENG_Q3, 1024) is false: the tile kernel runs
         default: return hipErrorInvalidValue;
     }
 #undef AREG_CASE
 }
+// fo.m.bits set: the masked instantiations (kernels_scan_masked.hip); an unmasked call launches the kernels it launched before masks existed
+#if COS_SCAN_MASKED_TU
+hipError_t launch_flat_scan_masked(int eng, u32 kdims, u32 n_cus, hipStream_t st, const uint8_t *qdig, const float *qmags, u32 B, const uint8_t *codes,
+                                   const float *mags, u64 row_stride, u32 n0, u32 nc, u32 metric, const FusedOut &fo, bool fp4) {
+#else
+hipError_t launch_flat_scan_masked(int eng, u32 kdims, u32 n_cus, hipStream_t st, const uint8_t *qdig, const float *qmags, u32 B, const uint8_t *codes,
+                                   const float *mags, u64 row_stride, u32 n0, u32 nc, u32 metric, const FusedOut &fo, bool fp4);
 hipError_t launch_flat_scan(int eng, u32 kdims, u32 n_cus, hipStream_t st, const uint8_t *qdig, const float *qmags, u32 B, const uint8_t *codes,
                             const float *mags, u64 row_stride, u32 n0, u32 nc, u32 metric, const FusedOut &fo, bool fp4) {
+    if (fo.m.bits) return launch_flat_scan_masked(eng, kdims, n_cus, st, qdig, qmags, B, codes, mags, row_stride, n0, nc, metric, fo, fp4);
+#endif
     const u32 n_tiles = (nc + 63) / 64;
     dim3 grid(std::min(n_tiles, n_cus), (B + 255) / 256);
-    if (eng == ENG_Q2) return launch_flat_scan_eng<ENG_Q2>(kdims, grid, st, qdig, qmags, B, codes, mags, row_stride, n0, nc, metric, fo, fp4);
-    if (eng == ENG_Q1) return launch_flat_scan_eng<ENG_Q1>(kdims, grid, st, qdig, qmags, B, codes, mags, row_stride, n0, nc, metric, fo, fp4);
-    if (eng == ENG_Q3) return launch_flat_scan_eng<ENG_Q3>(kdims, grid, st, qdig, qmags, B, codes, mags, row_stride, n0, nc, metric, fo, fp4);
+    if (eng == ENG_Q2) return launch_flat_scan_eng<ENG_Q2, SCAN_M>(kdims, grid, st, qdig, qmags, B, codes, mags, row_stride, n0, nc, metric, fo, fp4);
+    if (eng == ENG_Q1) return launch_flat_scan_eng<ENG_Q1, SCAN_M>(kdims, grid, st, qdig, qmags, B, codes, mags, row_stride, n0, nc, metric, fo, fp4);
+    if (eng == ENG_Q3) return launch_flat_scan_eng<ENG_Q3, SCAN_M>(kdims, grid, st, qdig, qmags, B, codes, mags, row_stride, n0, nc, metric, fo, fp4);
     return hipErrorInvalidValue;
 }
 
 
-template <int KC>
+template <int KC, bool M>
 static hipError_t launch_u8_kc(u32 n_cus, hipStream_t st, const uint8_t *qcodes, const u32 *qsums, const float *qmags, u32 B, const uint8_t *codes,
                                const u32 *csums, const float *mags, u64 row_stride, u32 n0, u32 nc, u32 metric, const FusedOut &fo) {
     constexpr int RB = KC > 12 ? 1 : 2;
     const size_t lds = (size_t)2 * 64 * (KC * 64 + 16) + (size_t)AREG_STAGE * 12 + 16;
-    hipError_t e = hipFuncSetAttribute((const void *)flat_scan_u8_areg<KC, RB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute((const void *)flat_scan_u8_areg<KC, RB, M>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     const dim3 grid(std::min((nc + 63) / 64, n_cus), (B + 128 * RB - 1) / (128 * RB));
-    hipLaunchKernelGGL((flat_scan_u8_areg<KC, RB>), grid, dim3(256), lds, st, qcodes, qsums, qmags, B, codes, csums, mags, row_stride, n0, nc, metric, fo);
+    hipLaunchKernelGGL((flat_scan_u8_areg<KC, RB, M>), grid, dim3(256), lds, st, qcodes, qsums, qmags, B, codes, csums, mags, row_stride, n0, nc, metric, fo);
     return hipGetLastError();
 }
 // fused chunk of u8 codes on the query-resident kernel (rows of exactly kdims = 64 KC bytes)
+#if COS_SCAN_MASKED_TU
+hipError_t launch_flat_scan_u8_masked(u32 kdims, u32 n_cus, hipStream_t st, const uint8_t *qcodes, const u32 *qsums, const float *qmags, u32 B, const uint8_t *codes,
+                                      const u32 *csums, const float *mags, u64 row_stride, u32 n0, u32 nc, u32 metric, const FusedOut &fo) {
+#else
+hipError_t launch_flat_scan_u8_masked(u32 kdims, u32 n_cus, hipStream_t st, const uint8_t *qcodes, const u32 *qsums, const float *qmags, u32 B, const uint8_t *codes,
+                                      const u32 *csums, const float *mags, u64 row_stride, u32 n0, u32 nc, u32 metric, const FusedOut &fo);
 hipError_t launch_flat_scan_u8(u32 kdims, u32 n_cus, hipStream_t st, const uint8_t *qcodes, const u32 *qsums, const float *qmags, u32 B, const uint8_t *codes,
                                const u32 *csums, const float *mags, u64 row_stride, u32 n0, u32 nc, u32 metric, const FusedOut &fo) {
-#define U8_CASE(KC) case KC: return launch_u8_kc<KC>(n_cus, st, qcodes, qsums, qmags, B, codes, csums, mags, row_stride, n0, nc, metric, fo)
+    if (fo.m.bits) return launch_flat_scan_u8_masked(kdims, n_cus, st, qcodes, qsums, qmags, B, codes, csums, mags, row_stride, n0, nc, metric, fo);
+#endif
+#define U8_CASE(KC) case KC: return launch_u8_kc<KC, SCAN_M>(n_cus, st, qcodes, qsums, qmags, B, codes, csums, mags, row_stride, n0, nc, metric, fo)
     switch (kdims / 64) {
         U8_CASE(2); U8_CASE(4); U8_CASE(6); U8_CASE(8); U8_CASE(12); U8_CASE(16);
         default: return hipErrorInvalidValue;
     }
 #undef U8_CASE
 }
+
+#if !COS_SCAN_MASKED_TU
 
 // level table as a query-resident GEMM: u8 codes whose rows are a whole number of 64-byte chunks with an instantiation, quaternary
 // codes whose rows (16 B per 64 dims) have one
@@ -1283,5 +1314,6 @@ hipError_t launch_flat_scan_expand_queries(int eng, const uint8_t *qcodes, u64 r
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
+#endif // !COS_SCAN_MASKED_TU
 
 } // namespace cosdev

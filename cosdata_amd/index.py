@@ -472,3 +472,82 @@ class HNSWIndex:
         scores = np.zeros((q.shape[0], k), np.float32)
         check(_lib.lib().cos_bruteforce_topk(self._h, _p(q), q.shape[0], k, _p(ids), _p(scores)))
         return ids, scores
+
+    # ---- exhaustive scans over a subset of the rows ------------------------------------------
+    def _scan_mask(self, masks, query_mask, skip_deleted: bool, B: int):
+        """-> (CosScanMask or None, arrays to keep alive).  `masks`: bool [n] (shared) or [G][n], or uint32 [G][ceil(n / 32)] packed
+        already (pack_row_masks); `query_mask`: [B] indices into it."""
+        if masks is None and query_mask is None and not skip_deleted:
+            return None, ()
+        words = (self.n + 31) // 32
+        bits, qm, G = None, None, 0
+        if masks is not None and np.asarray(masks).dtype == np.uint32:
+            bits = _c(np.atleast_2d(masks), np.uint32)
+            if bits.ndim != 2 or bits.shape[1] != words:
+                raise CosdataError(_lib.ERR_INVALID, f"packed masks must be uint32 [G][{words}], got shape {tuple(bits.shape)}")
+            G = bits.shape[0]
+        elif masks is not None:
+            m = np.atleast_2d(np.asarray(masks, dtype=bool))
+            if m.ndim != 2 or m.shape[1] != self.n:
+                raise CosdataError(_lib.ERR_INVALID, f"masks must be bool [{self.n}] or [G][{self.n}], got shape {tuple(np.shape(masks))}")
+            G = m.shape[0]
+            bits = pack_row_masks(m)
+        if query_mask is not None:
+            qm = _c(np.atleast_1d(query_mask), np.uint32)
+            if qm.shape != (B,):
+                raise CosdataError(_lib.ERR_INVALID, f"query_mask must hold {B} mask indices, got shape {tuple(qm.shape)}")
+        sm = _lib.CosScanMask(C.sizeof(_lib.CosScanMask), _lib.SCAN_SKIP_DELETED if skip_deleted else 0, G,
+                              bits.ctypes.data if bits is not None else None, qm.ctypes.data if qm is not None else None)
+        return sm, (bits, qm)
+
+    def flat_search_masked(self, queries, top_k: int, masks=None, query_mask=None, skip_deleted: bool = False, with_stats: bool = False):
+        """flat_search over a subset of the rows (cos_flat_search_masked_batch): query b may only be given rows r with
+        masks[query_mask[b]][r] set (`masks` bool [n] shared by every query, or [G][n] with `query_mask` [B]) and, with skip_deleted,
+        rows that were not given to delete().  The result is flat_search's on an index holding only those rows, with the original ids;
+        counts[b] = min(top_k, live rows of b).  A zero norm fails the call (status 2) only on a row some query of the call can see."""
+        q = self._queries(queries)
+        B = q.shape[0]
+        sm, keep = self._scan_mask(masks, query_mask, skip_deleted, B)
+        ids = np.full((B, top_k), 0xFFFFFFFF, np.uint32)
+        scores = np.zeros((B, top_k), np.float32)
+        counts = np.zeros(B, np.uint32)
+        st = CosFlatStats()
+        check(_lib.lib().cos_flat_search_masked_batch(self._h, _p(q), B, top_k, C.byref(sm) if sm is not None else None, _p(ids), _p(scores),
+                                                      _p(counts), C.byref(st)))
+        del keep
+        return (ids, scores, counts, st) if with_stats else (ids, scores, counts)
+
+    def bruteforce_topk_masked(self, queries, k: int, masks=None, query_mask=None, skip_deleted: bool = False):
+        """bruteforce_topk over a subset of the rows (cos_bruteforce_topk_masked); masks as in flat_search_masked.  -> ids, scores, counts:
+        k may exceed a query's live rows, counts[b] = min(k, live rows of b) and the entries past it are unspecified."""
+        q = self._queries(queries)
+        B = q.shape[0]
+        sm, keep = self._scan_mask(masks, query_mask, skip_deleted, B)
+        ids = np.zeros((B, k), np.uint32)
+        scores = np.zeros((B, k), np.float32)
+        counts = np.zeros(B, np.uint32)
+        check(_lib.lib().cos_bruteforce_topk_masked(self._h, _p(q), B, k, C.byref(sm) if sm is not None else None, _p(ids), _p(scores), _p(counts)))
+        del keep
+        return ids, scores, counts
+
+    def deleted_count(self) -> int:
+        """rows in the handle's deleted set (every id given to delete() since the vectors were uploaded)"""
+        n = C.c_uint32()
+        check(_lib.lib().cos_index_deleted_count(self._h, C.byref(n)))
+        return n.value
+
+    def deleted_rows(self) -> np.ndarray:
+        """the deleted set as ascending row numbers (id - id_base)"""
+        bits = np.zeros((self.n + 31) // 32, np.uint32)
+        check(_lib.lib().cos_index_download_deleted(self._h, _p(bits)))
+        return np.flatnonzero(np.unpackbits(bits.view(np.uint8), bitorder="little")[:self.n]).astype(np.uint32)
+
+
+def pack_row_masks(masks) -> np.ndarray:
+    """bool [G][n] -> uint32 [G][ceil(n / 32)], the layout of cos_scan_mask::bits: bit (r % 32) of word r / 32 is row r (padding bits 0)"""
+    m = np.atleast_2d(np.asarray(masks, dtype=bool))
+    words = (m.shape[1] + 31) // 32
+    by = np.packbits(m, axis=1, bitorder="little")
+    out = np.zeros((m.shape[0], words * 4), np.uint8)
+    out[:, :by.shape[1]] = by
+    return np.ascontiguousarray(out).view("<u4").astype(np.uint32, copy=False)

@@ -170,7 +170,8 @@ int32_t cos_index_append(cos_index *ix, const float *raw, uint32_t m, uint32_t f
  * holds the node, its neighbours drop their back edges (remove_neighbor_by_id, prob_node.rs:285-306), a neighbour left without any
  * neighbour is linked again from the walk's results re-scored against it (:1305-1357), and the node's own slots are emptied.  The
  * vector's rows stay resident (ids are never reused, collection.rs:451-468); no walk reaches the node again (exhaustive scans —
- * cos_flat_search_batch, cos_bruteforce_topk — still see the row: the host filters deleted ids there, as it owns the id map).
+ * cos_flat_search_batch, cos_bruteforce_topk — still see the row: use their masked forms with COS_SCAN_SKIP_DELETED; the id is recorded in
+ * the handle's deleted set whether or not the walk found the node).
  * Needs the link state like cos_index_append; exclusive like every graph change.  oracle: coso_index_delete. */
 int32_t cos_index_delete(cos_index *ix, const uint32_t *ids, uint32_t m);
 /* The link state of an UPLOADED graph (cos_index_upload_graph_level, cos_index_load_reference_dir), as the reference has it after a reload:
@@ -407,6 +408,39 @@ typedef struct {
 } cos_flat_stats;
 int32_t cos_flat_search_batch(cos_index *ix, const float *queries, uint32_t B, uint32_t top_k, uint32_t *out_ids,
                               float *out_scores, uint32_t *out_counts, cos_flat_stats *stats /* optional */);
+
+/* The two exhaustive scans over a SUBSET of the rows: per-query allow-lists and / or the handle's deleted set.
+ * Query q's live set is mask query_mask[q] AND NOT the deleted rows (COS_SCAN_SKIP_DELETED); its result is exactly what the unmasked
+ * call returns on an index that holds only those rows, with the original ids — the reference's finalisation (sort by quantized score,
+ * keep 5 * top_k, exact rerank, top_k) over the live rows, which dropping ids from an unmasked result cannot give.  The test is applied
+ * inside the scan kernels where a candidate is about to be kept; the masks are read on the host once per call.
+ *   out_counts[q] = min(top_k, live rows of q) (required in both calls); entries past the count are unspecified.  The brute force keeps
+ *   its rule k in [1, min(512, n)]: k may exceed a query's live rows.
+ *   Bits at and past n in a mask's last word are ignored.
+ *   mask == NULL, or n_masks == 0 with flags == 0: the unmasked call — the same kernels, the same bits.
+ *   Zero norms (cosine, code scan): COS_ERR_CALCULATION iff a query has zero norm or a row that is live for at least one query of the
+ *   call has; a zero-norm row no query can see does not fail the call (the unmasked entry point keeps its rule).
+ *   COS_ERR_INVALID: struct_size mismatch, unknown flags, bits == NULL with n_masks > 0, query_mask == NULL with n_masks > 1, a
+ *   query_mask entry >= n_masks.  COS_ERR_UNIMPLEMENTED: f16 / f32 storage and top_k > 204 in the code scan, as in the unmasked call.
+ *   The handle stays usable after every refusal.
+ * The deleted set is a device bitmap on the handle, n / 8 bytes, always kept: cos_index_delete sets the bit of every id it is given
+ * (whether or not its walk found the node; a repeated id is harmless), cos_index_append grows it (new rows are live), every upload
+ * that replaces the vectors clears it. */
+#define COS_SCAN_SKIP_DELETED 1u
+typedef struct cos_scan_mask {
+    uint32_t struct_size;        /* sizeof(cos_scan_mask) */
+    uint32_t flags;              /* COS_SCAN_SKIP_DELETED: rows given to cos_index_delete are not returned */
+    uint32_t n_masks;            /* 0 = no allow-list (every row, minus the deleted ones if flagged) */
+    const uint32_t *bits;        /* HOST [n_masks][ceil(n / 32)]: bit (r % 32) of word r / 32 = ROW r (id - id_base) may be returned */
+    const uint32_t *query_mask;  /* HOST [B] -> mask index; NULL = every query uses mask 0 (then n_masks must be 1) */
+} cos_scan_mask;
+int32_t cos_flat_search_masked_batch(cos_index *ix, const float *queries, uint32_t B, uint32_t top_k, const cos_scan_mask *mask,
+                                     uint32_t *out_ids, float *out_scores, uint32_t *out_counts, cos_flat_stats *stats /* optional */);
+int32_t cos_bruteforce_topk_masked(cos_index *ix, const float *queries, uint32_t B, uint32_t k, const cos_scan_mask *mask,
+                                   uint32_t *out_ids, float *out_scores, uint32_t *out_counts);
+/* rows in the deleted set; the set itself, HOST bits[ceil(n / 32)] in the layout of cos_scan_mask::bits (a set bit = deleted) */
+int32_t cos_index_deleted_count(cos_index *ix, uint32_t *out);
+int32_t cos_index_download_deleted(cos_index *ix, uint32_t *bits);
 
 /* ---- hybrid (config c5) --------------------------------------------------------------------- */
 typedef struct cos_bm25 cos_bm25;
