@@ -76,7 +76,7 @@ struct GraphGuard {
         (void)hipStreamSynchronize(ix->own_stream);
         for (auto &l : ix->lv) l.release();
         ix->link.release();
-        ix->adj_mag_valid = false;
+        ix->invalidate_adj_side();
         ix->have_root = false;
     }
 };
@@ -243,7 +243,7 @@ extern "C" int32_t cos_index_build(cos_index *ix, uint32_t batch_size) {
 
     ix->order_rank_valid = false; // the order key's table follows the graph (engine.hip, ensure_order_rank)
     ix->level_table_valid = false; // and so does the level table's operand (ensure_level_table)
-    ix->adj_mag_valid = false;     // the builder's walks gather mags[]; the adjacency-side norms are written when the graph is committed
+    ix->invalidate_adj_side();     // the builder's walks gather mags[]; the adjacency-side norms are written when the graph is committed
     ix->link.release();
     // ---- root + level draws (same RNG stream as the oracle builders) ----------------------------
     uint64_t rng = ix->p.seed ? ix->p.seed : 0x1234567ull;
@@ -400,7 +400,7 @@ extern "C" int32_t cos_index_append(cos_index *ix, const float *raw, uint32_t m,
     GraphGuard guard{ix};
     ix->order_rank_valid = false;
     ix->level_table_valid = false;
-    ix->adj_mag_valid = false;
+    ix->invalidate_adj_side();
     ix->link.valid = false; // until the append is complete
     cos_flat_ws_release(ix); // cached sums of the stored codes, scan buffers sized for the old corpus
 
@@ -459,6 +459,7 @@ extern "C" int32_t cos_index_append(cos_index *ix, const float *raw, uint32_t m,
         H.host_valid = false;
         H.nbr_ids.clear();
         H.d_adj_mag.reset();
+        H.d_adj_up.reset();
         DevArr<u32> adj_vec, adj_node, node_vec, child;
         DevBuf key, low_idx, low_key;
         HIP_TRY(adj_vec.alloc((size_t)nl1 * M));
@@ -632,7 +633,7 @@ extern "C" int32_t cos_index_delete(cos_index *ix, const uint32_t *ids, uint32_t
     std::vector<std::vector<u32>> node_vec(L1); // slow path only: node -> vector row, fetched once per level
     // (the locality order stays a permutation of the level's nodes and the level table's operand holds code rows: both still valid —
     // tests/test_gpu_mutation_coherence.py searches a warm handle with both after every delete, against a handle that never had them)
-    ix->adj_mag_valid = false;
+    ix->invalidate_adj_side();
     for (auto &l : ix->lv) { l.host_valid = false; l.nbr_ids.clear(); }
 
     for (u32 t = 0; t < m; t++) {

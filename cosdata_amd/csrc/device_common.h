@@ -12,7 +12,9 @@ typedef unsigned long long u64;
 
 constexpr int WAVE = 64;
 constexpr u32 ROW_EMPTY = 0xFFFFFFFFu; // empty neighbour slot in the device adjacency (vec-row space)
-constexpr int KEEP_SEARCH = 100;       // vector_store.rs:1194 (search)
+constexpr u32 ADJ_UP_NONE = 0xFFFFFFFFu; // LevelDev::adj_up: the neighbour has no node one level up (or the slot is empty)
+struct alignas(8) AdjUp { float mag; u32 up; }; // one scanned neighbour slot of LevelDev::adj_up: the neighbour's norm, its node one level up
+constexpr int KEEP_SEARCH = 100;      // vector_store.rs:1194 (search)
 constexpr int KEEP_INDEX = 64;         // vector_store.rs:1194 (indexing)
 constexpr int MAX_LEVELS = 16;
 

@@ -93,6 +93,7 @@ IndexDev cos_make_index_dev(const cos_index *ix) {
         d.lv[l].root_idx = h.n ? h.n - 1 : 0;
         d.lv[l].adj_mag = (ix->adj_mag_valid && cosdev::tune_or(cosdev::TUNE_WALK_ADJ_MAG, 1) != 0) ? h.d_adj_mag : nullptr;
         d.lv[l].mag_stride = std::min(h.M, ix->p.shortlist_size);
+        d.lv[l].adj_up = (d.lv[l].adj_mag != nullptr && l != 0 && ix->adj_up_level == l) ? h.d_adj_up : nullptr;
     }
     return d;
 }
@@ -237,7 +238,7 @@ extern "C" int32_t cos_index_upload_vectors(cos_index *ix, const float *raw, uin
     for (auto &l : ix->lv) l.release(); // a graph refers to vector rows: new vectors invalidate it
     ix->order_rank_valid = false;
     ix->level_table_valid = false;
-    ix->adj_mag_valid = false;
+    ix->invalidate_adj_side();
     ix->link.release();
     reset_meta(ix);                       // ... and so do the pseudo-root component, its node table and the id stride
     const u64 dim = ix->p.dim;
@@ -291,7 +292,7 @@ extern "C" int32_t cos_index_set_root(cos_index *ix, const float *root_raw) {
     // the root is a node of every level: the level-table operand holds a gathered COPY of its code row, norm and code sum, which a
     // second set_root on a live graph would leave stale (the row levels would use the new row) — the next search regathers
     ix->level_table_valid = false;
-    ix->adj_mag_valid = false; // ... and the adjacency-side norms hold the old root's |v| wherever the root is a neighbour
+    ix->invalidate_adj_side(); // ... and the adjacency-side norms hold the old root's |v| wherever the root is a neighbour
     if (ix->link.valid && graph_ready(ix)) ix->link.release(); // the slot similarities of edges to the root were computed with the old root
     return COS_OK;
 }
@@ -333,7 +334,7 @@ static int32_t push_level_to_device(cos_index *ix, u32 level) {
     L.host_valid = true;
     ix->order_rank_valid = false; // the order key's table follows the graph (ensure_order_rank)
     ix->level_table_valid = false;
-    ix->adj_mag_valid = false;
+    ix->invalidate_adj_side();
     ix->link.release();           // an uploaded level carries no slot similarities / lowest caches to continue from
     return COS_OK;
 }
@@ -395,7 +396,7 @@ static int32_t push_level0_to_device(cos_index *ix, const u32 *nbr) {
     L.host_valid = false;
     ix->order_rank_valid = false;
     ix->level_table_valid = false;
-    ix->adj_mag_valid = false;
+    ix->invalidate_adj_side();
     ix->link.release();
     return COS_OK;
 }
@@ -550,7 +551,7 @@ int32_t cos_set_root_code(cos_index *ix, const uint8_t *ref_code, float mag) {
     ix->root_raw.assign(ix->p.dim, 0.0f);
     ix->have_root = true;
     ix->level_table_valid = false;
-    ix->adj_mag_valid = false;
+    ix->invalidate_adj_side();
     return COS_OK;
 }
 
@@ -751,6 +752,9 @@ static u32 walk_table_min_B(const cos_index *ix) {
 // Workgroups of the early part of a gated level-table GEMM (walk_plan.h; tuning knob walk_table_early_wgs).  Measured on the 12.5M x 1024
 // shard, 32 768 queries per step: DESIGN.md §8.1, profiles/r07_table_early_wgs_sweep.jsonl.
 static constexpr long long WALK_TABLE_EARLY_WGS_DEFAULT = 0;
+// The row level under the level table reads table columns for the neighbours that have a node one level up (walk_plan.h,
+// WalkPlan::up_table_level; tuning knob walk_up_table).
+static constexpr long long WALK_UP_TABLE_DEFAULT = 1;
 // the handle as walk_plan (walk_plan.h) sees it: shape, every knob resolved (the tuning registry's overrides included), a launch of B
 // queries at beam width ef that takes part in the walk chain.  Caller holds ix->mu where the handle is shared.
 cosdev::WalkPlanIn cos_walk_plan_in(const cos_index *ix, u32 B, u32 ef) {
@@ -780,6 +784,7 @@ cosdev::WalkPlanIn cos_walk_plan_in(const cos_index *ix, u32 B, u32 ef) {
     in.table_after_sort = cosdev::tune_or(cosdev::TUNE_WALK_TABLE_AFTER_SORT, 1);
     in.table_supported = cosdev::level_table_eng_supported(ix->eng, ix->row_stride);
     in.adj_mag_valid = ix->adj_mag_valid;
+    in.up_table_mode = (u32)std::min<long long>(std::max<long long>(cosdev::tune_or(cosdev::TUNE_WALK_UP_TABLE, WALK_UP_TABLE_DEFAULT), 0), 2);
     in.table_early_wgs = (u32)std::min<long long>(std::max<long long>(cosdev::tune_or(cosdev::TUNE_WALK_TABLE_EARLY_WGS, WALK_TABLE_EARLY_WGS_DEFAULT), 0), 0xFFFFFFFFll);
     in.table_queue = cosdev::level_table_gemm_queue(ix->eng, ix->row_stride);
     in.n_cus = ix->n_cus;
@@ -931,13 +936,55 @@ static int32_t ensure_adj_mags(cos_index *ix) {
     return COS_OK;
 }
 
+// LevelDev::adj_up of the ONE level that can use it: the row level directly under the current level table (level >= 1), on a graph
+// whose norms beside the adjacency are valid (the walk takes both from the same window).  Caller holds ix->mu; called where the
+// table's operand is (a commit; get_workspace's fall-back after a knob changed).  When the table rule moves to another level the old
+// array goes.  Out of memory leaves this graph and rule without — same results — and is remembered, not retried per launch.
+static int32_t ensure_adj_up(cos_index *ix) {
+    const u32 want = (ix->adj_mag_valid && ix->level_table_valid && ix->table_level_min >= 2u && ix->eng == ENG_U8 && ix->G == 64u &&
+                      cosdev::tune_or(cosdev::TUNE_WALK_UP_TABLE, WALK_UP_TABLE_DEFAULT) != 0)
+                         ? ix->table_level_min - 1u
+                         : 0u;
+    if (want != 0u && (ix->adj_up_level == want || ix->adj_up_oom_level == want)) return COS_OK; // filled for this graph and rule, or known not to fit
+    bool any = false;
+    for (u32 l = 0; l <= ix->p.num_layers; l++) any = any || ix->lv[l].d_adj_up;
+    if (any) {
+        HIP_TRY(hipDeviceSynchronize()); // (the rule moved under running searches: a launch in flight may still read the array that goes)
+        for (u32 l = 0; l <= ix->p.num_layers; l++) ix->lv[l].d_adj_up.reset();
+    }
+    ix->adj_up_level = 0;
+    if (want == 0u) return COS_OK;
+    ix->adj_up_oom_level = 0;
+    HIP_TRY(hipDeviceSynchronize()); // a build or an upload on another stream may still be writing the adjacency
+    LevelHost &H = ix->lv[want];
+    const LevelHost &U = ix->lv[want + 1];
+    const u32 slots = std::min(H.M, ix->p.shortlist_size);
+    if (!H.d_adj_node || !U.d_child || H.n == 0 || U.n == 0) return COS_OK;
+    DevArr<u32> up; // node of level `want` -> node of the level above
+    hipError_t e = H.d_adj_up.alloc((size_t)H.n * slots);
+    if (e == hipSuccess) e = up.alloc(H.n);
+    if (e == hipErrorOutOfMemory) {
+        (void)hipGetLastError();
+        H.d_adj_up.reset();
+        ix->adj_up_oom_level = want;
+        return COS_OK;
+    }
+    HIP_TRY(e);
+    HIP_TRY(cosdev::launch_fill_adj_up(H.d_adj_vec, H.d_adj_node, ix->d_mags, U.d_child, U.n, up, H.d_adj_up, H.n, H.M, slots, ix->own_stream));
+    HIP_TRY(hipStreamSynchronize(ix->own_stream));
+    ix->adj_up_level = want;
+    return COS_OK;
+}
+
 int32_t cos_prepare_walk_plans(cos_index *ix) {
     std::lock_guard<std::mutex> g(ix->mu);
     if (int32_t rc = ensure_adj_mags(ix)) return rc;
     if (ix->walk_order_min_B)
         if (int32_t rc = ensure_order_rank(ix)) return rc;
-    if (walk_table_min_B(ix))
+    if (walk_table_min_B(ix)) {
         if (int32_t rc = ensure_level_table(ix)) return rc;
+        if (int32_t rc = ensure_adj_up(ix)) return rc;
+    }
     return COS_OK;
 }
 
@@ -1031,6 +1078,8 @@ static int32_t get_workspace(cos_index *ix, void *key, hipStream_t st, u32 B, u3
     }
     if (want.prepare_table) {
         if (int32_t rc = ensure_level_table(ix)) return rc;
+        if (int32_t rc = ensure_adj_up(ix)) return rc; // (nothing to do unless the table rule, the knob or the norms changed since the commit)
+        have.adj_up_level = ix->adj_up_level;
         const size_t need = (size_t)w->capB * ix->table_stride;
         if (need > w->tab.cap) {
             // every workspace (one per caller stream, up to five per leased host pipe) holds the table of its own launch in flight:
@@ -1097,6 +1146,8 @@ static int32_t run_search(cos_index *ix, Workspace *w, const SearchLaunch &L, co
     dev.visited_mode = L.visited_mode;
     for (u32 l = 0; l <= dev.num_layers; l++)
         if (!((plan.use_adj_mag >> l) & 1u)) dev.lv[l].adj_mag = nullptr;
+    for (u32 l = 0; l <= dev.num_layers; l++)
+        if (plan.up_table_level != l || l == 0u || dev.lv[l].adj_mag == nullptr) dev.lv[l].adj_up = nullptr;
     WalkArgs wa;
     memset(&wa, 0, sizeof(wa));
     if (dev.visited_mode == COS_VISITED_EXACT) {
@@ -1107,6 +1158,10 @@ static int32_t run_search(cos_index *ix, Workspace *w, const SearchLaunch &L, co
     if (timed) HIP_TRY(hipEventRecord(ev[0], st));
     HIP_TRY(launch_quantize_rows(ix->eng, d_queries, ix->p.dim, B, ix->p.dim, ix->p.range_lo, ix->p.range_hi, w->q_codes, ix->row_stride,
                                  w->q_mags, w->q_raw_mags, st, plan.use_table && ix->eng == ENG_U8 ? w->qsums.p : nullptr));
+    // WalkArgs::out_stats2 cleared (the latency kernels do not write it) HERE, in front of the table GEMM's gate: after the GEMM this fill
+    // was a 0.24 ms launch of its own between the end of the GEMM and the start of the upper range, on the chain that decides the step.
+    // Stream order still puts it behind this workspace's previous launch.
+    HIP_TRY(hipMemsetAsync(w->stats2, 0, (size_t)B * 32, st));
     // Level table: on the caller's stream, i.e. BEFORE the walk takes its place in the walk chain — the GEMM of this launch runs next
     // to the previous launch's walk.  (Round 5 also issued it inside the chain, right in front of its own walk, where it shares the
     // chip with nobody: 7.07-7.12 against 6.69 ms per step — the overlap hides 0.4 ms.  profiles/r05_table_gemm_in_chain_probe_not_kept.jsonl)
@@ -1145,7 +1200,6 @@ static int32_t run_search(cos_index *ix, Workspace *w, const SearchLaunch &L, co
     wa.out_status = w->walk_status;
     wa.out_stats = w->stats;
     wa.out_stats2 = w->stats2;
-    HIP_TRY(hipMemsetAsync(w->stats2, 0, (size_t)B * 32, st)); // the latency kernels do not write it
     if (plan.use_table) {
         wa.tab = w->tab;
         wa.tab_mags = L.tmags;

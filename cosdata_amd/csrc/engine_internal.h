@@ -29,6 +29,8 @@ hipError_t launch_index_pair_distances(int eng, const uint8_t *codes, const floa
 hipError_t launch_grow_rows(const u32 *src, u32 *dst, u32 old_n, u32 new_n, u32 M, u32 remap_from, u32 remap_to, u32 fill, hipStream_t st);
 hipError_t launch_grow_bytes(const uint8_t *src, uint8_t *dst, u32 old_n, u32 new_n, hipStream_t st);
 hipError_t launch_fill_adj_mag(const u32 *adj_vec, const float *mags, float *adj_mag, u32 n, u32 M, u32 slots, hipStream_t st);
+hipError_t launch_fill_adj_up(const u32 *adj_vec, const u32 *adj_node, const float *mags, const u32 *child_up, u32 n_up, u32 *up, AdjUp *adj_up, u32 n, u32 M, u32 slots,
+                              hipStream_t st);
 hipError_t launch_link_round(const LinkArgs &a, u32 maxM, const u32 *pend, const u32 *pcount, u32 *next, u32 *next_count, u32 *evq, u32 *evq_count,
                              u32 count_ub, u32 round, hipStream_t st);
 hipError_t launch_quantize_rows(int eng, const float *x, u64 x_stride, u32 n, u32 dim, float lo, float hi, uint8_t *codes,
@@ -96,12 +98,13 @@ struct LevelHost {
     DevArr<u32> d_adj_vec, d_adj_node, d_node_vec, d_child;
     DevArr<u32> d_node_id, d_node_meta; // pseudo-root component only (metadata-filtered search)
     DevArr<float> d_adj_mag; // [n][min(M, shortlist)] norms of the scanned neighbour slots (LevelDev::adj_mag), valid while cos_index::adj_mag_valid
+    DevArr<cosdev::AdjUp> d_adj_up; // same shape: the neighbours' norms and nodes one level up (LevelDev::adj_up); only level cos_index::adj_up_level has it
     u32 n = 0, M = 0;
     u32 root_idx = 0;        // pseudo-root component: node index of the pseudo root (base graph: the root is the last node)
     bool host_valid = false; // node_ids/nbr_ids mirror the device arrays
     void release() { // the level's device arrays and host mirrors (M stays)
         d_adj_vec.reset(); d_adj_node.reset(); d_node_vec.reset(); d_child.reset();
-        d_node_id.reset(); d_node_meta.reset(); d_adj_mag.reset();
+        d_node_id.reset(); d_node_meta.reset(); d_adj_mag.reset(); d_adj_up.reset();
         n = 0;
         node_ids.clear();
         nbr_ids.clear();
@@ -290,6 +293,11 @@ struct cos_index {
     u32 walk_table_max_cols = COS_WALK_TABLE_AUTO, walk_table_min_B = COS_WALK_TABLE_DEFAULT_MIN_B;
     size_t table_bytes_total = 0;    // tables held by this handle's workspaces (budget: get_workspace)
     bool adj_mag_valid = false;      // LevelHost::d_adj_mag follows the graph, the norms and the root (ensure_adj_mags)
+    // LevelHost::d_adj_up: the level that holds a filled one (0 = none; always table_level_min - 1 of the table rule it was filled
+    // for), and the level an allocation ran out of memory for (0 = none): that graph and rule go without, it is not tried again
+    // until either changes.  Both fall with adj_mag_valid (invalidate_adj_side) — the array follows the graph exactly like the norms.
+    u32 adj_up_level = 0, adj_up_oom_level = 0;
+    void invalidate_adj_side() { adj_mag_valid = false; adj_up_level = 0; adj_up_oom_level = 0; }
     LinkState link;                  // cos_index_build -> cos_index_append (builder.hip); dropped with the graph
     bool level_table_valid = false;  // the arrays below follow the graph and walk_table_max_cols
     u32 table_level_min = 0, table_cols = 0;

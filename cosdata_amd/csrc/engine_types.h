@@ -22,6 +22,18 @@ struct LevelDev {
     // gathers mags[] as before.  Same values, same bits.
     const float *adj_mag;
     u32 mag_stride;
+    // The node index ONE LEVEL UP of every scanned neighbour slot, same shape and index as adj_mag: adj_up[node * mag_stride + slot].up =
+    // the node of level l + 1 whose child link is the neighbour in that slot, ADJ_UP_NONE where the neighbour has no node there or the
+    // slot is empty.  Only the row level directly under the level table has it (WalkPlan::up_table_level): a winner with a node one
+    // level up already has its integer dot in the table (WalkArgs::tab, column tab_col0[l + 1] + up), so the walk reads that
+    // column — one line — instead of the neighbour's code row.  Same integer, same bits.  nullptr everywhere else.  Filled after
+    // adj_mag (engine.hip ensure_adj_up) and invalidated with it.
+    // Every entry carries the slot's norm too (.mag = adj_mag's value, same bits), and the walk of that level reads THIS array instead
+    // of adj_mag, one 8-byte load per slot: a plain u32 array beside adj_mag is one more pointer alive through the level's rounds, which
+    // cost two VGPRs in every u8 instantiation of walk_kernel and put walk_kernel<ENG_U8, 1, 1, true, false, 8> (71 of its 72 VGPRs
+    // used) 12 bytes into scratch; through one pointer every instantiation keeps the register count it had.  Same lines fetched either
+    // way (8 bytes per slot); the price is 4 more bytes per slot of ONE small level in HBM (12.5M x 1024 shard: 100 MB instead of 50).
+    const AdjUp *adj_up;
     // pseudo-root component (metadata-filtered search): nodes are replicas, not vectors
     const u32 *node_id;   // [n] internal (replica) id of a node; nullptr on the base graph (id = vector row * id_stride)
     const u32 *node_meta; // [n] row of the node's metadata dimensions in IndexDev::mbits

@@ -470,6 +470,29 @@ __global__ void fill_adj_mag_kernel(const u32 *__restrict__ adj_vec, const float
     }
 }
 
+// LevelDev::adj_up (engine_types.h) of level l, in two steps.  First the inverse of level l + 1's child links: up[child[j]] = j for
+// every node j of level l + 1 (the root like any other), `up` holding one entry per node of level l, preset to ADJ_UP_NONE ...
+__global__ void scatter_up_kernel(const u32 *__restrict__ child_up, u32 n_up, u32 *__restrict__ up, u32 n) {
+    for (u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x; j < n_up; j += (u64)gridDim.x * blockDim.x) {
+        const u32 c = child_up[j];
+        if (c < n) up[c] = (u32)j;
+    }
+}
+// ... then, per scanned slot, the entry of the neighbour's node (adj_node: node indices of level l, l >= 1)
+// with the neighbour's norm beside it (the value fill_adj_mag_kernel writes)
+__global__ void fill_adj_up_kernel(const u32 *__restrict__ adj_vec, const u32 *__restrict__ adj_node, const float *__restrict__ mags, const u32 *__restrict__ up, u32 n,
+                                   AdjUp *__restrict__ adj_up, u64 total, u32 M, u32 slots) {
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (u64)gridDim.x * blockDim.x) {
+        const u64 node = i / slots;
+        const u32 slot = (u32)(i - node * slots);
+        const u32 row = adj_vec[node * M + slot], v = adj_node[node * M + slot];
+        AdjUp e;
+        e.mag = row == NONE ? 1.0f : mags[row];
+        e.up = v < n ? up[v] : ADJ_UP_NONE;
+        adj_up[i] = e;
+    }
+}
+
 } // namespace
 
 namespace cosdev {
@@ -521,6 +544,18 @@ hipError_t launch_fill_adj_mag(const u32 *adj_vec, const float *mags, float *adj
     if (total == 0) return hipSuccess;
     const u32 blocks = (u32)std::min<u64>((total + 255) / 256, 1u << 20);
     hipLaunchKernelGGL(fill_adj_mag_kernel, dim3(blocks), dim3(256), 0, st, adj_vec, mags, adj_mag, total, M, slots);
+    return hipGetLastError();
+}
+
+// `up`: [n] scratch (overwritten); child_up: the child links of the n_up nodes of the level above
+hipError_t launch_fill_adj_up(const u32 *adj_vec, const u32 *adj_node, const float *mags, const u32 *child_up, u32 n_up, u32 *up, AdjUp *adj_up, u32 n, u32 M, u32 slots,
+                              hipStream_t st) {
+    const u64 total = (u64)n * slots;
+    if (total == 0 || n_up == 0) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(up, 0xFF, (size_t)n * sizeof(u32), st); // = ADJ_UP_NONE
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(scatter_up_kernel, dim3((u32)std::min<u64>(((u64)n_up + 255) / 256, 1u << 20)), dim3(256), 0, st, child_up, n_up, up, n);
+    hipLaunchKernelGGL(fill_adj_up_kernel, dim3((u32)std::min<u64>((total + 255) / 256, 1u << 20)), dim3(256), 0, st, adj_vec, adj_node, mags, up, n, adj_up, total, M, slots);
     return hipGetLastError();
 }
 

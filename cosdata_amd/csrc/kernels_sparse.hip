@@ -1164,6 +1164,14 @@ extern "C" int32_t cos_sparse_search_batch(cos_sparse *s, const uint32_t *q_dims
     HIP_TRY(hipMemcpy(out_ids, s->w_oi.p, (size_t)B * top_k * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(out_scores, s->w_os.p, (size_t)B * top_k * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(out_counts, s->w_oc.p, (size_t)B * 4, hipMemcpyDeviceToHost));
+    // The finish kernels write a query's first `count` entries only: what lies behind them in the result buffers is whatever the
+    // device memory held.  The caller gets defined values there (no id, score 0), so that two calls on the same state return the
+    // same arrays byte for byte, not only the same answers.
+    for (u32 q = 0; q < B; q++)
+        for (u32 i = std::min(out_counts[q], top_k); i < top_k; i++) {
+            out_ids[(size_t)q * top_k + i] = 0xFFFFFFFFu;
+            out_scores[(size_t)q * top_k + i] = 0.0f;
+        }
     return sparse_wait_previous(s); // (complete already: settles kernel_ms)
 }
 

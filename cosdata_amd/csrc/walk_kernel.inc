@@ -1,5 +1,7 @@
 // walk_kernel.inc — the HNSW walk kernel (ann_search / traverse_find_nearest, vector_store.rs:256-402, 1112-1204), textually included
 // by kernels_walk.hip; the rules it shares with the other walk kernels are in walk_common.h.
+// The row level directly under the level table reads table columns for the neighbours that have a node one level up (LevelDev::adj_up,
+// `UPT` below): u8 codes only — quaternary codes walk that level as they did, every winner from its code row.
 constexpr int PB = 4; // code rows in flight per lane group before the dots are consumed
 constexpr int LA = 4; // lookahead window: adjacency rows prefetched per round
 // G = 64 path: code rows in flight per wave = template parameter PB64.  An expansion discovers ~7 new neighbours on average:
@@ -178,14 +180,28 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH >= 3 ? (R
         // (3-4 evaluations per pop on average), so this collapses chains of dependent HBM round trips.
         // The rounds of a level, compiled TWICE: for a table level (no row is ever fetched: the evaluation blocks are not in its
         // instruction stream) and for a row level (no table gather) — `tab_level` is uniform for the level, the branch is taken once.
-        auto level_rounds = [&](auto tabc, auto cosc, auto amagc) __attribute__((always_inline)) {
+        // ... and a row level a THIRD time where it is the level directly under the table and has LevelDev::adj_up (UPT): u8 codes on the
+        // one-row-per-pass path, every CH, both filters, both metrics.  Quaternary codes keep the AMAG variant.  The variant is taken once
+        // per level, so every other level runs the instruction stream it ran before.
+        auto level_rounds = [&](auto tabc, auto cosc, auto amagc, auto upc) __attribute__((always_inline)) {
         constexpr bool TAB = decltype(tabc)::value;
         constexpr bool COSINE = decltype(cosc)::value;       // table levels of a cosine index: the metric tests fold away
         constexpr bool AMAG = decltype(amagc)::value && G64 && !FLOAT_ENG; // row levels, one-row-per-pass path: norms beside the adjacency
+        constexpr bool UPT = decltype(upc)::value && AMAG && !TAB && ENG == ENG_U8; // ... and table columns for the neighbours with a node one level up
         const u32 metric_t = COSINE ? 0u : metric;
+        // The level under the table stages FOUR values per slot (row, node, norm, node one level up) for a window of LA - 1 entries in the
+        // LDS the other row levels use for three values of LA entries: 4 x 3 = 3 x 4 arrays of 64 words.  A fourth array of LA entries
+        // is 1 KB more per wave, and LDS is what caps the resident waves of the flagship's lower range (6.5 KB per wave at M0 256, ef 112:
+        // 24 waves per CU; 7.5 KB: 21) — on all its levels, for the sake of one.  A shorter window changes when adjacency rows are
+        // fetched, never what is popped (tests/test_commit_equivalence.py runs the model at windows of 1, 4 and 8).
+        constexpr int LAW = UPT ? LA - 1 : LA;
+        u32 *const w_vec = sm.win_vec, *const w_node = UPT ? sm.win_vec + LAW * 64 : sm.win_node, *const w_up = sm.win_vec + 3 * LAW * 64;
+        float *const w_mag = UPT ? (float *)(sm.win_vec + 2 * LAW * 64) : sm.win_mag;
+        // the level under the table: this query's table columns of the level ABOVE (level + 1 = tab_level_min <= L)
+        const float *tabu = UPT ? wa.tab + (u64)qi * wa.tab_stride + wa.tab_col0[UPT ? level + 1 : 0] : nullptr;
         while (npool > 0 && npop < wa.ef) {
             n_rounds++;
-            u32 kwin = npool < (u32)LA ? npool : (u32)LA;
+            u32 kwin = npool < (u32)LAW ? npool : (u32)LAW;
             if (kwin > wa.ef - npop) kwin = wa.ef - npop;
             // the window lives in LDS so the consume loop below is a runtime loop (small code, no extra VGPRs)
             // All loads of the window are issued before the first value is looked at, and none is predicated: a pool position past
@@ -204,20 +220,27 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH >= 3 ? (R
                 auto fetch_stage = [&](auto bothc) {
                     constexpr bool BOTH = decltype(bothc)::value;
                     float wm_[LA];
-                    static_for<0, LA>([&](auto ic) {
+                    u32 wu_[LA];
+                    static_for<0, LAW>([&](auto ic) {
                         constexpr int i = decltype(ic)::value;
                         const u32 nd = pool.template peek_node<i>();
                         const u64 off = ((u64)nd << log2M) + slot_l;
                         wv_[i] = lv.adj_vec[off];
                         if constexpr (BOTH) wn_[i] = lv.adj_node[off];
-                        if constexpr (!TAB && AMAG) wm_[i] = lv.adj_mag[(u64)nd * lv.mag_stride + slot_l]; // (slot_l < slots = mag_stride)
+                        if constexpr (!TAB && AMAG && !UPT) wm_[i] = lv.adj_mag[(u64)nd * lv.mag_stride + slot_l]; // (slot_l < slots = mag_stride)
+                        if constexpr (UPT) { // norm and node one level up in ONE 8-byte load through ONE pointer (LevelDev::adj_up says why)
+                            const uint2 mu = ((const uint2 *)lv.adj_up)[(u64)nd * lv.mag_stride + slot_l];
+                            wm_[i] = __uint_as_float(mu.x);
+                            wu_[i] = mu.y;
+                        }
                     });
                     if constexpr (!TAB) {
-                        static_for<0, LA>([&](auto ic) {
+                        static_for<0, LAW>([&](auto ic) {
                             constexpr int i = decltype(ic)::value;
-                            sm.win_vec[i * 64 + lane] = wv_[i];
-                            sm.win_node[i * 64 + lane] = BOTH ? wn_[i] : wv_[i];
-                            if constexpr (AMAG) sm.win_mag[i * 64 + lane] = wm_[i];
+                            w_vec[i * 64 + lane] = wv_[i];
+                            w_node[i * 64 + lane] = BOTH ? wn_[i] : wv_[i];
+                            if constexpr (AMAG) w_mag[i * 64 + lane] = wm_[i];
+                            if constexpr (UPT) w_up[i * 64 + lane] = wu_[i];
                         });
                     }
                 };
@@ -225,7 +248,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH >= 3 ? (R
                 else fetch_stage(std::false_type{});
             }
             u32 stop = 0; // wave-uniform: the window went stale or the level failed
-            auto consume = [&](u32 wi, u32 nb_vec, u32 nb_node, float nb_mag) __attribute__((always_inline)) {
+            auto consume = [&](u32 wi, u32 nb_vec, u32 nb_node, float nb_mag, u32 nb_up) __attribute__((always_inline)) {
                 // the window entry being consumed IS the pool's head (that is what "still provably the next pop" means): the
                 // popped list takes it from lane 0's register — until round 4 the window's keys made a detour through LDS
                 if constexpr (R == 1) { // ef <= 64: the popped list is one entry per lane, lane npop takes the head by v_writelane
@@ -384,6 +407,32 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH >= 3 ? (R
                     if constexpr (AMAG) magw = nb_mag;
                     else if (win) magw = ix.mags[nb_vec];
                     u64 m = wmask;
+                    if constexpr (UPT) {
+                        // The level under the table: a winner that has a node one level up (nb_up) was dotted with this query by the
+                        // table GEMM — tabu[nb_up] is the integer dot `as f32` the row block below would compute (both are exact) — so
+                        // it costs one 4-byte gather instead of a code row; its norm is in the lane already.  These winners (tmask) are
+                        // committed BEFORE the row winners (rmask), not in slot order.  That cannot change a result:
+                        //   * keys are unique (the node index is the low word), so pool and winners have one descending order;
+                        //   * the entries that can still be popped afterwards are the top `limit` of pool + winners whatever the order
+                        //     of insertion (insert_serial refuses exactly the keys with `limit` larger ones before them, and an entry
+                        //     pushed past position limit - 1 by a later insert is one the other order would have refused or pushed too);
+                        //   * window_ok falls iff SOME winner is inserted with fewer than `ahead` entries above it at that moment; the
+                        //     LARGEST winner has only pool entries above it whenever it goes in (every other winner is below it), and no
+                        //     winner can have fewer entries above it than the largest has pool entries above it — so the flag falls iff
+                        //     fewer than `ahead` POOL entries beat the largest winner, in any order (commit_merge relies on the same).
+                        // tests/test_walk_up_table_model.py checks the three on the pool model of tests/test_commit_equivalence.py.
+                        const u64 tmask = wmask & ballot64(nb_up != ADJ_UP_NONE);
+                        if (tmask) {
+                            float dotv = 0.0f;
+                            if (__builtin_amdgcn_inverse_ballot_w64(tmask)) dotv = tabu[nb_up];
+                            bool badl;
+                            const float sim = cosine_or_dot<ENG == ENG_U8>(metric, dotv, qmag, magw, badl);
+                            if (tmask & ballot64(badl)) failed = 1;
+                            else commit(tmask, metric_key(metric, sim), nb_node);
+                            n_tab += (u64)__popcll(tmask);
+                            m = wmask & ~tmask;
+                        }
+                    }
                     while (m && !failed) {
                         u32 lsel = 0;  // landing lane of winner p of this block <- 4 * (the lane that owns the winner): a ds_bpermute address
                         u32 tot = 0;   // landing lanes: the winner's integer dot
@@ -515,32 +564,39 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH >= 3 ? (R
             if constexpr (TAB) {
                 static_for<0, LA>([&](auto ic) __attribute__((always_inline)) {
                     constexpr int i = decltype(ic)::value;
-                    if ((u32)i < kwin && !stop) consume((u32)i, wv_[i], wn_[i], 1.0f);
+                    if ((u32)i < kwin && !stop) consume((u32)i, wv_[i], wn_[i], 1.0f, ADJ_UP_NONE);
                 });
             } else {
                 for (u32 wi = 0; wi < kwin && !stop; wi++)
-                    consume(wi, sm.win_vec[wi * 64 + lane], sm.win_node[wi * 64 + lane], AMAG ? sm.win_mag[wi * 64 + lane] : 1.0f);
+                    consume(wi, w_vec[wi * 64 + lane], w_node[wi * 64 + lane], AMAG ? w_mag[wi * 64 + lane] : 1.0f, UPT ? w_up[wi * 64 + lane] : ADJ_UP_NONE);
             }
             if (failed) break;
         }
         };
         if (tab_level) {
-            if (metric == 0u) level_rounds(std::true_type{}, std::true_type{}, std::false_type{});
-            else level_rounds(std::true_type{}, std::false_type{}, std::false_type{});
+            if (metric == 0u) level_rounds(std::true_type{}, std::true_type{}, std::false_type{}, std::false_type{});
+            else level_rounds(std::true_type{}, std::false_type{}, std::false_type{}, std::false_type{});
         } else {
             bool done = false;
             if constexpr (G64 && !FLOAT_ENG) {
                 if (lv.adj_mag != nullptr) { // (uniform for the level: the branch is taken once)
-                    level_rounds(std::false_type{}, std::false_type{}, std::true_type{});
+                    bool up = false;
+                    if constexpr (ENG == ENG_U8) {
+                        if (lv.adj_up != nullptr && wa.tab != nullptr && (u32)level + 1u == wa.tab_level_min) { // the level under the table
+                            level_rounds(std::false_type{}, std::false_type{}, std::true_type{}, std::true_type{});
+                            up = true;
+                        }
+                    }
+                    if (!up) level_rounds(std::false_type{}, std::false_type{}, std::true_type{}, std::false_type{});
                     done = true;
                 }
             }
-            if (!done) level_rounds(std::false_type{}, std::false_type{}, std::false_type{});
+            if (!done) level_rounds(std::false_type{}, std::false_type{}, std::false_type{}, std::false_type{});
         }
         n_exp += npop;
         adj_bytes += (u64)npop * slots * 4; // what an expansion reads: the scanned slots of the row (min(M, shortlist_size))
         n_evals += lev_evals;
-        if (tab_level) n_tab += lev_evals;
+        if (tab_level) n_tab += lev_evals; // (the level under the table has added its table winners itself)
         if (exact) {
             // undo: zero exactly the words this level set (whole words belong to this query), leaving the bitset all-zero
             // for the next level / launch.  One wave owns the filter and its vector-memory operations reach L2 in issue

@@ -65,6 +65,8 @@ struct WalkPlanIn {
     uint32_t table_early_wgs;       // tuning knob walk_table_early_wgs, resolved (0 = one launch)
     bool table_queue;               // the table comes from the query-resident GEMM, whose work items can be shared by two launches
     uint32_t n_cus;                 // compute units of the device (0 = 256): sizes the GEMM's work items
+    // the row level under the table reads table columns for neighbours with a node one level up (WalkPlan::up_table_level)
+    uint32_t up_table_mode;         // tuning knob walk_up_table, resolved: 0 never | 1 by the rule below | 2 at every ef and launch size
 };
 
 // What preparation left, for the second step: no table operand for this graph and rule, no room for a workspace's table (out of
@@ -74,6 +76,7 @@ struct WalkHave {
     bool table_buffer;                    // the workspace's table holds B rows
     uint32_t n_order_keys, order_level0;  // key levels of the locality order and the first (highest) of them
     bool order_buffers;                   // the workspace's order buffers hold B queries
+    uint32_t adj_up_level;                // the level whose LevelDev::adj_up is filled for this graph and table rule (0 = none)
 };
 
 struct WalkPlan {
@@ -88,6 +91,11 @@ struct WalkPlan {
     bool side_stream;          // the walk runs on the workspace's low-priority stream
     bool prepare_order, prepare_table; // what the above needs: order buffers + ranks, table operand + buffer
     uint32_t table_level_min, table_cols, cut_after_level; // of this launch (0 without a table / unsplit): cos_index_last_walk_split
+    // The row level directly under the table (0 = none): its walk reads tab[q][tab_col0[l + 1] + adj_up] — one line — instead of the
+    // code row — eight lines at 1024 dims — for every winner that has a node one level up (LevelDev::adj_up; a quarter of them where a
+    // level holds a quarter of the nodes of the level below).  The GEMM computed that integer dot anyway.  Settled only (the table's
+    // lowest level is known after preparation), throughput kernel, u8 codes on the one-row-per-pass path (G = 64).
+    uint32_t up_table_level;
 };
 
 // Work items of the query-resident level-table GEMM: a row group of 256 queries x a stripe of table_gemm_stripe_tiles() column tiles of
@@ -208,6 +216,15 @@ inline WalkPlan walk_plan(const WalkPlanIn &in, const WalkHave *have = nullptr) 
             if (in.adj_mag_mode == 2 || (in.ef <= 2u * in.M[l] && in.B >= ADJ_MAG_USE_MIN_B)) p.use_adj_mag |= 1u << l;
     // (a root replaced on a live graph; small launches keep their gathers until a big one pays for the refill)
     p.refill_adj_mag = !in.adj_mag_valid && in.B >= ADJ_MAG_REFILL_MIN_B;
+    // The level under the table takes its winners' norms from the window (adj_mag) and their columns from the same window (adj_up):
+    // it follows adj_mag's rule — the extra window array costs what adj_mag's costs and pays under the same conditions.  Mode 2 drops
+    // the launch-size condition of that rule for this one level (tests: a few hundred queries), not its need for valid norms.
+    if (have && p.use_table && p.kernel == WalkKernel::Throughput && in.up_table_mode != 0 && in.eng == WALK_PLAN_ENG_U8 && in.G == 64u &&
+        in.mdim == 0u && have->table_level_min >= 2u && have->adj_up_level == have->table_level_min - 1u) {
+        const uint32_t l = have->table_level_min - 1u;
+        if (in.up_table_mode == 2 && in.adj_mag_valid && in.adj_mag_mode != 0) p.use_adj_mag |= 1u << l;
+        if ((p.use_adj_mag >> l) & 1u) p.up_table_level = l;
+    }
     p.side_stream = in.side_min_B && in.B >= in.side_min_B;
     p.prepare_order = p.ordered;
     p.prepare_table = p.use_table;
