@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "engine_types.h"
+#include "flat_plan.h"
 
 namespace cosdev {
 
@@ -58,19 +59,12 @@ hipError_t launch_flat_scan_u8(u32 kdims, u32 n_cus, hipStream_t st, const uint8
 // Survivor pools wider than 64 keys (kernels_flat_wide.hip): P = 64 * R keys per query, R = 2, 4, 8, 16, kept sorted (descending) as
 // pool[B][P].  The scan kernels are the same at every width: they read thr[q] (the P-th best key, 0 while the pool is not full) and
 // append to app[B][cap].  R = 1 stays on the kernels of kernels_flat.hip.
-constexpr u32 FLAT_SEED = 16384;  // candidates that go through the score matrix first and seed every query's threshold (every width)
-// Fused schedule of a pool of P keys: a chunk `growth` times the size of everything seen lets ~growth * P keys per query through (a key
-// passes with probability P / seen while the threshold stands), and the append buffer holds eight times that:
-//   P = 64        growth 8, cap 64 P = 4096 keys (32 KB per query)
-//   P = 128..1024 growth 4, cap 32 P        keys (256 P bytes per query: 32 KB .. 256 KB)
-__host__ __device__ constexpr u32 flat_growth(u32 P) { return P == 64 ? 8u : 4u; }
-__host__ __device__ constexpr u32 flat_app_cap(u32 P) { return P == 64 ? 4096u : 32u * P; }
-// smallest pool width (64, 128, ..., 1024) that holds `need` keys; 0 when none does
-inline u32 flat_pool_width(u32 need) {
-    for (u32 P = 64; P <= 1024; P *= 2)
-        if (need <= P) return P;
-    return 0;
-}
+// FLAT_SEED, the fused schedule of a pool of P keys (flat_growth, flat_app_cap) and the pool widths (flat_pool_width) are host numbers:
+// flat_plan.h, with the rest of what a scan decides between its launches
+using flat_plan::FLAT_SEED;
+using flat_plan::flat_app_cap;
+using flat_plan::flat_growth;
+using flat_plan::flat_pool_width;
 // score chunk [B][nc] -> per-segment top P (part[B][S][P]) -> merged into pool[B][P]; thr[q] = the pool's P-th best.  m.bits set: rows
 // outside a query's mask are skipped
 hipError_t launch_flat_select_wide(u32 R, const float *d_scores, u64 s_stride, u32 B, u32 n0, u32 nc, u64 *d_part, u32 S, u64 *d_pool, u64 *d_thr,

@@ -261,14 +261,7 @@ __global__ __launch_bounds__(64) void flat_select_append(const u64 *__restrict__
     if (lane == 0) { thr_out[q] = thr; app_cnt[q] = 0; }
 }
 
-// segments per query: enough waves to fill 256 CUs x 8, at least 4096 candidates per segment
-static u32 select_segments(u32 B, u32 n_chunk) {
-    u32 S = (4096 + B - 1) / B;
-    const u32 max_s = (n_chunk + 4095) / 4096;
-    if (S > max_s) S = max_s;
-    if (S > 64) S = 64;
-    return S ? S : 1;
-}
+// S = segments per query (flat_plan.h select_segments)
 static hipError_t launch_select(const float *d_scores, u64 s_stride, u32 B, u32 n0, u32 nc, u64 *d_part, u32 S, u64 *d_pool, hipStream_t st,
                                 u64 *d_thr, const ScanMask &m) {
     const u32 seg_len = ((nc + S - 1) / S + 63) / 64 * 64;
@@ -736,46 +729,154 @@ hipError_t scan_mask_upload(const cos_index *ix, const cos_scan_mask *mask, cons
     return e;
 }
 
+// ---- what the two scans share: the numbers are flat_plan.h's, the launches are here ----
+namespace fp = flat_plan;
+static_assert(fp::OK == COS_OK && fp::INVALID == COS_ERR_INVALID && fp::UNIMPLEMENTED == COS_ERR_UNIMPLEMENTED, "flat_plan.h restates cos_status");
+static_assert(fp::U8 == ENG_U8 && fp::Q2 == ENG_Q2 && fp::Q1 == ENG_Q1 && fp::Q3 == ENG_Q3, "flat_plan.h restates the engines");
+static_assert(BN == 128 && CN == 128, "flat_plan.h unfused_chunk: whole tiles of 128 candidates");
+static_assert(SEL == 64, "flat_plan.h flat_pool_width: the narrowest pool");
+
+// the device buffers that the chunks of an attempt go through, sized by the caller from its plan
+struct ScanBufs {
+    float *scores;    // [B][s_stride]: the score matrix of an unfused chunk
+    u64 s_stride;
+    u64 *part;        // [B][S][P]: its selection's partial lists
+    u64 *pool, *thr;  // [B][P] survivors, [B] their P-th best
+    u64 *app;         // [B][app_cap]: what a fused chunk lets through, appcnt[B] of them
+    u32 *appcnt, *overflow; // *overflow |= 1 by a fold that found a counter above app_cap
+    ScanMask sm;
+    FusedOut fused_out(const fp::Scan &plan, const uint8_t *qdigits) const { return FusedOut{thr, app, appcnt, plan.app_cap(), qdigits, sm}; }
+};
+
+// a scored chunk into the pools: a fused chunk's append buffer, or the selection over an unfused chunk's score matrix; 64-key pools on the
+// kernels above, wider ones on kernels_flat_wide.hip
+hipError_t fold_chunk(const fp::Scan &plan, const fp::Chunk &c, const ScanBufs &b, hipStream_t st) {
+    const u32 B = plan.B, R = plan.P / SEL;
+    if (c.fused && R == 1) {
+        hipLaunchKernelGGL(flat_select_append, dim3(B), dim3(64), 0, st, (const u64 *)b.app, b.appcnt, plan.app_cap(), B, b.pool, b.thr, b.overflow);
+        return hipGetLastError();
+    }
+    if (c.fused) return launch_flat_append_wide(R, b.app, b.appcnt, plan.app_cap(), B, b.pool, b.thr, b.overflow, st);
+    const u32 S = fp::select_segments(B, c.nc);
+    if (R == 1) return launch_select(b.scores, b.s_stride, B, c.n0, c.nc, b.part, S, b.pool, st, b.thr, b.sm);
+    return launch_flat_select_wide(R, b.scores, b.s_stride, B, c.n0, c.nc, b.part, S, b.pool, b.thr, st, b.sm);
+}
+
+// the chunks of one attempt, in order: score(chunk) enqueues the kernel that scores it, then the chunk is folded.  The first failed HIP
+// call ends it: nothing further is started on the stream
+template <class Score>
+hipError_t run_chunks(const fp::Scan &plan, int attempt, const ScanBufs &b, hipStream_t st, Score &&score) {
+    fp::Schedule sched = plan.schedule(attempt);
+    fp::Chunk c;
+    hipError_t e = hipSuccess;
+    while (e == hipSuccess && sched.next(c)) {
+        e = score(c);
+        if (e == hipSuccess) e = fold_chunk(plan, c, b, st);
+    }
+    return e;
+}
+
+// flat_gemm_f32<VEC, FUSED, MASKED>.  An unfused chunk has no masked form: its selection applies the mask
+using GemmF32Kernel = decltype(&flat_gemm_f32<true, false>);
+GemmF32Kernel gemm_f32_kernel(bool vec, bool fused, bool masked) {
+    if (!fused) return vec ? flat_gemm_f32<true, false> : flat_gemm_f32<false, false>;
+    if (!masked) return vec ? flat_gemm_f32<true, true> : flat_gemm_f32<false, true>;
+    return vec ? flat_gemm_f32<true, true, true> : flat_gemm_f32<false, true, true>;
+}
+// every instantiation above may use GEMM_SMEM bytes of dynamic LDS
+hipError_t gemm_f32_allow_lds() {
+    hipError_t e = hipSuccess;
+    for (int vec = 0; vec < 2; vec++)
+        for (int fused = 0; fused < 2; fused++)
+            for (int masked = 0; masked <= fused && e == hipSuccess; masked++)
+                e = hipFuncSetAttribute((const void *)gemm_f32_kernel(vec, fused, masked), hipFuncAttributeMaxDynamicSharedMemorySize, (int)GEMM_SMEM);
+    return e;
+}
+// scores of rows [n0, n0 + nc) of X against the B queries
+hipError_t launch_gemm_f32(bool vec, bool fused, bool masked, const float *Q, const float *qmags, u32 B, const float *X, const float *xmags, u32 n0, u32 nc,
+                           u32 dim, float *scores, u64 s_stride, const FusedOut &fo, hipStream_t st) {
+    const dim3 grid((nc + BN - 1) / BN, (B + BM - 1) / BM);
+    hipLaunchKernelGGL(gemm_f32_kernel(vec, fused, masked), grid, dim3(256), GEMM_SMEM, st, Q, (u64)dim, qmags, B, X, (u64)dim, xmags, n0, nc, dim, scores, s_stride, fo);
+    return hipGetLastError();
+}
+
+// the queries' bit planes -> the digit bytes [B][kdims] the tile kernel multiplies; eng = ENG_Q2, ENG_Q1 or ENG_Q3
+hipError_t launch_expand_digits(int eng, const uint8_t *qcodes, u64 row_stride, u32 B, u32 kdims, uint8_t *digits, hipStream_t st) {
+    const u64 pieces = (u64)B * (kdims / 16);
+    const dim3 grid((u32)((pieces + 255) / 256));
+    if (eng == ENG_Q2) hipLaunchKernelGGL(expand_digits_kernel<ENG_Q2>, grid, dim3(256), 0, st, qcodes, row_stride, B, kdims, digits);
+    else if (eng == ENG_Q1) hipLaunchKernelGGL(expand_digits_kernel<ENG_Q1>, grid, dim3(256), 0, st, qcodes, row_stride, B, kdims, digits);
+    else hipLaunchKernelGGL(expand_digits_kernel<ENG_Q3>, grid, dim3(256), 0, st, qcodes, row_stride, B, kdims, digits);
+    return hipGetLastError();
+}
+
+// flat_codes_gemm_i8<ENG, FUSED, PF, MASKED>: pf = k panels prefetched into registers (1..3; results do not depend on it).  A fused chunk
+// of a masked call keeps one panel in flight whatever pf says; an unfused chunk has no masked form
+using CodesGemmKernel = decltype(&flat_codes_gemm_i8<ENG_U8, false, 1>);
+template <int ENG>
+CodesGemmKernel codes_gemm_kernel_of(bool fused, int pf, bool masked) {
+    if (fused && masked) return flat_codes_gemm_i8<ENG, true, 1, true>;
+    if (fused && pf == 2) return flat_codes_gemm_i8<ENG, true, 2>;
+    if (fused && pf == 3) return flat_codes_gemm_i8<ENG, true, 3>;
+    if (fused) return flat_codes_gemm_i8<ENG, true, 1>;
+    if (pf == 2) return flat_codes_gemm_i8<ENG, false, 2>;
+    if (pf == 3) return flat_codes_gemm_i8<ENG, false, 3>;
+    return flat_codes_gemm_i8<ENG, false, 1>;
+}
+// the operands of the tile kernel that stay the same from chunk to chunk
+struct CodesGemm {
+    const uint8_t *qcodes; const float *qmags; const u32 *qsums; u32 B;             // the queries
+    const uint8_t *codes; const float *mags; const u32 *csums; u64 row_stride;      // the rows
+    u32 kdims, metric;
+    float *scores; u64 s_stride;                                                    // unfused: [B][s_stride]
+    FusedOut fo;
+};
+// rows [n0, n0 + nc) of the codes; eng = ENG_U8, ENG_Q2, ENG_Q1 or ENG_Q3
+hipError_t launch_codes_gemm(int eng, bool fused, int pf, bool masked, const CodesGemm &g, u32 n0, u32 nc, hipStream_t st) {
+    const CodesGemmKernel kernel = eng == ENG_U8   ? codes_gemm_kernel_of<ENG_U8>(fused, pf, masked)
+                                   : eng == ENG_Q2 ? codes_gemm_kernel_of<ENG_Q2>(fused, pf, masked)
+                                   : eng == ENG_Q1 ? codes_gemm_kernel_of<ENG_Q1>(fused, pf, masked)
+                                                   : codes_gemm_kernel_of<ENG_Q3>(fused, pf, masked);
+    const dim3 grid((nc + CN - 1) / CN, (g.B + CM - 1) / CM);
+    hipLaunchKernelGGL(kernel, grid, dim3(512), 0, st, g.qcodes, g.qmags, g.qsums, g.B, g.codes, g.mags, g.csums, g.row_stride, n0, nc, g.kdims, g.metric, g.scores,
+                       g.s_stride, g.fo);
+    return hipGetLastError();
+}
+
 // cos_bruteforce_topk (mask == nullptr, out_counts optional) and cos_bruteforce_topk_masked
 int32_t bruteforce_run(cos_index *ix, const float *queries, uint32_t B, uint32_t k, const cos_scan_mask *mask, uint32_t *out_ids, float *out_scores,
                        uint32_t *out_counts) {
     if (!ix || !queries || !out_ids || !out_scores || B == 0) return cos_fail(COS_ERR_INVALID, "bad argument");
     if (!ix->have_vectors) return cos_fail(COS_ERR_NOT_READY, "upload vectors first");
-    if (k == 0 || k > 512 || k > ix->n) return cos_fail(COS_ERR_INVALID, "k must be in [1, min(512, n)]");
+    if (int32_t krc = fp::check_brute_k(k, ix->n)) return cos_fail(krc, "k must be in [1, min(512, n)]");
     MaskPlan mp;
     if (int32_t mrc = scan_mask_plan(mask, B, mp)) return mrc;
-    // survivors per query: the GEMM only generates candidates, so the pool holds at least 2k of them (64 for k <= 32, as ever)
-    const u32 P = flat_pool_width(2 * k), R = P / SEL;
     int32_t rc = cos_set_device(ix);
     if (rc) return rc;
     const u32 dim = ix->p.dim, n = ix->n;
-    // candidates per pass: the [B][chunk] score buffer stays <= 1 GiB
-    u32 chunk = (u32)std::min<u64>(1u << 18, ((1ull << 30) / B / 4) / BN * BN);
-    chunk = std::min(n, std::max<u32>(chunk, BN));
-    // Same schedule as cos_flat_search_batch: the first SEED candidates go through the score matrix + segmented selection and
-    // seed every query's threshold; later chunks grow 8x and the GEMM epilogue appends only what beats the threshold.  An
-    // append-buffer overflow repeats the call on the unfused path (tuning knob flat_unfused = 1 forces it).  Wider pools grow 4x into
-    // an append buffer of 32 P keys (flat_scan.h flat_growth / flat_app_cap).
-    constexpr u32 SEED = FLAT_SEED;
-    const u32 APP_CAP = flat_app_cap(P), growth = flat_growth(P);
-    const bool allow_fused = tune_or(TUNE_FLAT_UNFUSED, 0) == 0 && n > SEED;
-    const u64 s_stride = ((u64)chunk + 63) & ~63ull;
+    // Same schedule as cos_flat_search_batch (flat_plan.h): the seed chunk goes through the score matrix + segmented selection and
+    // seeds every query's threshold; later chunks grow and the GEMM epilogue appends only what beats the threshold.  An
+    // append-buffer overflow repeats the call on the unfused path (tuning knob flat_unfused = 1 forces it).
+    // Survivors per query: the GEMM only generates candidates, so the pool holds at least 2k of them (64 for k <= 32, as ever).
+    const fp::Scan plan = fp::brute_scan(n, B, k, tune_or(TUNE_FLAT_UNFUSED, 0) != 0);
+    const u32 P = plan.P, R = P / SEL;
+    // the score matrix and the selection's lists serve the unfused chunks of both attempts
+    const u64 s_stride = fp::score_stride(plan.unfused);
     DevArr<float> d_q, d_qm, d_scores, d_os, d_dummy;
     DevArr<u64> d_pool, d_part, d_thr, d_app;
     DevArr<u32> d_oi, d_appcnt, d_over, d_oc;
     DevArr<uint8_t> d_codes;
     MaskBufs mb;
     hipStream_t st = ix->own_stream;
-    const u32 S = select_segments(B, chunk);
     HIP_TRY(d_q.alloc((size_t)B * dim));
-    HIP_TRY(d_part.alloc((size_t)B * S * P));
+    HIP_TRY(d_part.alloc((size_t)B * fp::select_segments(B, plan.unfused) * P));
     HIP_TRY(d_qm.alloc(B));
     HIP_TRY(d_dummy.alloc(B));
     HIP_TRY(d_codes.alloc((size_t)B * (((size_t)dim * 4 + 15) & ~(size_t)15)));
     HIP_TRY(d_scores.alloc((size_t)B * s_stride));
     HIP_TRY(d_pool.alloc((size_t)B * P));
     HIP_TRY(d_thr.alloc(B));
-    if (allow_fused) HIP_TRY(d_app.alloc((size_t)B * APP_CAP));
+    if (plan.allow_fused) HIP_TRY(d_app.alloc((size_t)B * plan.app_cap()));
     HIP_TRY(d_appcnt.alloc(B));
     HIP_TRY(d_over.alloc(1));
     HIP_TRY(d_oi.alloc((size_t)B * k));
@@ -785,53 +886,27 @@ int32_t bruteforce_run(cos_index *ix, const float *queries, uint32_t B, uint32_t
     hipError_t e = hipMemcpyAsync(d_q, queries, (size_t)B * dim * 4, hipMemcpyHostToDevice, st);
     // |q| in the reference's sequential order (vector_store.rs:414): reuse the F32 quantize kernel's raw_mags output
     if (e == hipSuccess) e = launch_quantize_rows(ENG_F32, d_q, dim, B, dim, 0.f, 0.f, d_codes, ((u64)dim * 4 + 15) & ~15ull, d_dummy, d_qm, st);
-    for (const void *f : {(const void *)flat_gemm_f32<true, false>, (const void *)flat_gemm_f32<false, false>, (const void *)flat_gemm_f32<true, true>,
-                          (const void *)flat_gemm_f32<false, true>, (const void *)flat_gemm_f32<true, true, true>, (const void *)flat_gemm_f32<false, true, true>})
-        if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GEMM_SMEM);
+    if (e == hipSuccess) e = gemm_f32_allow_lds();
     ScanMask sm{nullptr, nullptr, 0u};
     const u32 *d_uni = nullptr; // (the brute force has no zero-norm screen)
     if (e == hipSuccess && mp.masked) e = scan_mask_upload(ix, mask, mp, B, mb, st, sm, &d_uni);
     // float4 staging needs 16 B aligned rows: dim % 4 == 0 (hipMalloc'd bases are 256 B aligned; a borrowed raw pointer is checked)
     const bool vec = dim % 4 == 0 && ((uintptr_t)ix->d_raw & 15) == 0;
     for (int attempt = 0; attempt < 2 && e == hipSuccess; attempt++) {
-        const bool fused = allow_fused && attempt == 0;
         if (e == hipSuccess) e = hipMemsetAsync(d_pool, 0, (size_t)B * P * 8, st);
         if (e == hipSuccess) e = hipMemsetAsync(d_thr, 0, (size_t)B * 8, st);
         if (e == hipSuccess) e = hipMemsetAsync(d_appcnt, 0, (size_t)B * 4, st);
         if (e == hipSuccess) e = hipMemsetAsync(d_over, 0, 4, st);
-        const FusedOut fo{d_thr, d_app, d_appcnt, APP_CAP, nullptr, sm};
-        u32 n0 = 0;
-        while (n0 < n && e == hipSuccess) {
-            const bool use_fused = fused && n0 > 0;
-            u32 nc = use_fused ? (u32)std::min<u64>((u64)n0 * growth, 1ull << 22) : (fused ? std::min(SEED, chunk) : chunk);
-            nc = std::min(nc, n - n0);
-            dim3 grid((nc + BN - 1) / BN, (B + BM - 1) / BM);
-#define GEMM_ARGS d_q, (u64)dim, d_qm, B, ix->d_raw, (u64)dim, ix->d_raw_mags, n0, nc, dim, d_scores, s_stride, fo
-            if (use_fused) {
-                if (mp.masked && vec) hipLaunchKernelGGL((flat_gemm_f32<true, true, true>), grid, dim3(256), GEMM_SMEM, st, GEMM_ARGS);
-                else if (mp.masked) hipLaunchKernelGGL((flat_gemm_f32<false, true, true>), grid, dim3(256), GEMM_SMEM, st, GEMM_ARGS);
-                else if (vec) hipLaunchKernelGGL((flat_gemm_f32<true, true>), grid, dim3(256), GEMM_SMEM, st, GEMM_ARGS);
-                else hipLaunchKernelGGL((flat_gemm_f32<false, true>), grid, dim3(256), GEMM_SMEM, st, GEMM_ARGS);
-                e = hipGetLastError();
-                if (e == hipSuccess && R == 1) {
-                    hipLaunchKernelGGL(flat_select_append, dim3(B), dim3(64), 0, st, (const u64 *)d_app, d_appcnt, APP_CAP, B, d_pool, d_thr, d_over);
-                    e = hipGetLastError();
-                } else if (e == hipSuccess)
-                    e = launch_flat_append_wide(R, d_app, d_appcnt, APP_CAP, B, d_pool, d_thr, d_over, st);
-            } else {
-                if (vec) hipLaunchKernelGGL((flat_gemm_f32<true, false>), grid, dim3(256), GEMM_SMEM, st, GEMM_ARGS);
-                else hipLaunchKernelGGL((flat_gemm_f32<false, false>), grid, dim3(256), GEMM_SMEM, st, GEMM_ARGS);
-                e = hipGetLastError();
-                if (e == hipSuccess && R == 1) e = launch_select(d_scores, s_stride, B, n0, nc, d_part, select_segments(B, nc), d_pool, st, d_thr, sm);
-                else if (e == hipSuccess) e = launch_flat_select_wide(R, d_scores, s_stride, B, n0, nc, d_part, select_segments(B, nc), d_pool, d_thr, st, sm);
-            }
-#undef GEMM_ARGS
-            n0 += nc;
-        }
+        const ScanBufs bufs{d_scores, s_stride, d_part, d_pool, d_thr, d_app, d_appcnt, d_over, sm};
+        const FusedOut fo = bufs.fused_out(plan, nullptr);
+        if (e == hipSuccess)
+            e = run_chunks(plan, attempt, bufs, st, [&](const fp::Chunk &c) {
+                return launch_gemm_f32(vec, c.fused, mp.masked, d_q, d_qm, B, ix->d_raw, ix->d_raw_mags, c.n0, c.nc, dim, d_scores, s_stride, fo, st);
+            });
         u32 hover = 0;
         if (e == hipSuccess) e = hipMemcpyAsync(&hover, d_over, 4, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess || !fused || hover == 0) break; // done; otherwise the append buffer overflowed: repeat unfused
+        if (e != hipSuccess || !plan.fused(attempt) || hover == 0) break; // done; otherwise the append buffer overflowed: repeat unfused
     }
     if (e == hipSuccess && R == 1) {
         hipLaunchKernelGGL(flat_rescore, dim3(B), dim3(64), (((size_t)dim * 4 + 15) & ~(size_t)15), st, d_q, (u64)dim, d_qm, B, ix->d_raw, (u64)dim,
@@ -914,41 +989,31 @@ static int32_t flat_search_run(cos_index *ix, const float *queries, uint32_t B, 
     if (!ix->have_vectors) return cos_fail(COS_ERR_NOT_READY, "upload vectors first");
     MaskPlan mp;
     if (int32_t mrc = scan_mask_plan(mask, B, mp)) return mrc;
-    if (top_k == 0 || top_k > 204) return cos_fail(COS_ERR_UNIMPLEMENTED, "flat search keeps at most 1024 survivors (5 * top_k): top_k must be in [1, 204]");
-    // survivors per query: the smallest pool that holds the 5 * top_k rerank candidates (64 for top_k <= 12, as ever).  Every buffer
-    // below is sized and indexed by this call's P, not by the widest call the handle has served.
-    const u32 P = flat_pool_width(5 * top_k), R = P / SEL;
-    const bool planes = ix->eng == ENG_Q1 || ix->eng == ENG_Q2 || ix->eng == ENG_Q3; // bit-plane storage: the operands are expanded to digits
+    if (int32_t krc = fp::check_code_top_k(top_k)) return cos_fail(krc, "flat search keeps at most 1024 survivors (5 * top_k): top_k must be in [1, 204]");
+    const bool planes = fp::bit_planes(ix->eng); // bit-plane storage: the operands are expanded to digits
     if (ix->eng != ENG_U8 && !planes)
         return cos_fail(COS_ERR_UNIMPLEMENTED, "flat search over codes implements u8, binary, quaternary and octal storage");
     int32_t rc = cos_set_device(ix);
     if (rc) return rc;
     const u32 dim = ix->p.dim, n = ix->n;
-    // dims the GEMM multiplies, a multiple of 64: a 16-byte chunk holds 128 binary, 64 quaternary or 32 octal dims
-    const u32 chunk_k = ix->eng == ENG_Q1 ? 128u : ix->eng == ENG_Q3 ? 32u : 64u;
-    const u32 kdims = ix->eng == ENG_U8 ? (u32)((ix->row_stride + 63) / 64 * 64) : ((u32)(ix->row_stride / 16) * chunk_k + 63) / 64 * 64;
-    // Scan schedule.  The first candidates (SEED of them) go through the unfused path — score matrix + segmented selection —
-    // and seed every query's threshold; from then on chunks grow 8x (128 K, 1 M, 4 M ...) and the fused GEMM appends only what
-    // beats the threshold: a chunk 8x the size of everything seen before lets ~64 * 8 entries per query through, an eighth of
-    // the append capacity.  An adversarially ordered corpus can still overflow it; that is detected on the device and the
-    // call is repeated on the unfused path, so the result never depends on the shortcut.  Tuning knob flat_unfused = 1 forces that path.
-    // Wider pools (P = 128 .. 1024) keep the seed — 16 candidates per pool slot at P = 1024: the pool is full and its threshold is the
-    // best 1/16 before the first fused chunk — and grow 4x into an append buffer of 32 P keys: ~4 P entries per query pass a chunk, an
-    // eighth of the capacity again (flat_scan.h flat_growth / flat_app_cap).
-    const bool allow_fused = tune_or(TUNE_FLAT_UNFUSED, 0) == 0;
-    const int pf = (int)tune_or(TUNE_FLAT_PF, 1); // k panels prefetched into registers (1..3); results do not depend on it
-    // fused chunks of bit-plane codes run on the query-resident kernel when K has an instantiation (tuning knob flat_tile_kernel = 1: never)
-    const bool use_areg = planes && flat_scan_supported(ix->eng, kdims) && tune_or(TUNE_FLAT_TILE_KERNEL, 0) == 0;
-    // e2m1 digits on the scaled MFMA (kernels_scan.hip flat_scan_q2_fp4); 0 = i8 digits.  Octal digits (0..7) have no e2m1 form: i8 always
-    const bool use_fp4 = use_areg && ix->eng != ENG_Q3 && tune_or(TUNE_FLAT_FP4, 1) != 0;
-    // fused chunks of u8 codes too (round 6: flat_scan_u8_areg), when a row is exactly a supported number of 64-byte chunks
-    const bool use_u8q = ix->eng == ENG_U8 && ix->row_stride == (u64)kdims && flat_scan_supported(kdims) && tune_or(TUNE_FLAT_TILE_KERNEL, 0) == 0; // (1024 dims: 32 query rows per wave instead of 64)
+    const u32 kdims = fp::code_kdims(ix->eng, ix->row_stride);
+    // Fused chunks run on a query-resident kernel where the storage and K have an instantiation (kernels_scan.hip: flat_scan_q2_* for
+    // bit-plane codes, with e2m1 digits on the scaled MFMA by default; flat_scan_u8_areg for u8 rows of whole 64-byte chunks — 1024 dims:
+    // 32 query rows per wave instead of 64), on the tile kernel otherwise, and always with tuning knob flat_tile_kernel = 1.
+    const fp::ScanKernel kernel = fp::fused_kernel(ix->eng, kdims, ix->row_stride, tune_or(TUNE_FLAT_TILE_KERNEL, 0) != 0, flat_scan_supported(ix->eng, kdims),
+                                                   flat_scan_supported(kdims));
+    const bool use_areg = kernel == fp::ScanKernel::RESIDENT_PLANES, use_fp4 = fp::scan_fp4(kernel, ix->eng, tune_or(TUNE_FLAT_FP4, 1) != 0);
+    // Scan schedule (flat_plan.h).  The first candidates go through the unfused path — score matrix + segmented selection — and seed
+    // every query's threshold; from then on chunks grow and the fused kernel appends only what beats the threshold.  An adversarially
+    // ordered corpus can still overflow the append buffer; that is detected on the device and the call is repeated on the unfused path,
+    // so the result never depends on the shortcut.  Tuning knob flat_unfused = 1 forces that path.
+    // Survivors per query: the smallest pool that holds the 5 * top_k rerank candidates (64 for top_k <= 12, as ever).  Every buffer
+    // below is sized and indexed by this call's P, not by the widest call the handle has served.
+    const fp::Scan plan = fp::code_scan(n, B, top_k, tune_or(TUNE_FLAT_UNFUSED, 0) != 0, kernel);
+    const u32 P = plan.P, R = P / SEL;
+    const int pf = (int)tune_or(TUNE_FLAT_PF, 1); // the tile kernel's k panels in flight
     int n_cus = 0;
     if (hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, ix->p.device) != hipSuccess || n_cus <= 0) n_cus = 256;
-    constexpr u32 SEED = FLAT_SEED;
-    const u32 APP_CAP = flat_app_cap(P), growth = flat_growth(P);
-    u32 chunk = (u32)std::min<u64>(1u << 20, ((1ull << 31) / B / 4) / CN * CN); // unfused: the [B][chunk] score buffer stays <= 2 GiB
-    chunk = std::min(n, std::max<u32>(chunk, CN));
     hipStream_t st = ix->own_stream;
     {
         std::lock_guard<std::mutex> g(ix->mu);
@@ -972,10 +1037,9 @@ static int32_t flat_search_run(cos_index *ix, const float *queries, uint32_t B, 
         if (e == hipSuccess) { e = buf.grow(count); ptr = buf; }
     };
     for (int attempt = 0; attempt < 2 && e == hipSuccess; attempt++) {
-        const bool fused = allow_fused && attempt == 0 && n > SEED;
-        const u32 first = fused ? SEED : chunk;                              // size of the (unfused) first chunk
-        const u64 s_stride = ((u64)std::min(first, n) + 63) & ~63ull;
-        const u32 S = select_segments(B, std::min(first, n));
+        // the score matrix and the selection's lists: as wide as this attempt's first chunk, its widest unfused one
+        const u64 s_stride = fp::score_stride(plan.first(attempt));
+        const u32 S = fp::select_segments(B, plan.first(attempt));
         if (attempt == 0) {
             need(W->q, d_q, (size_t)B * dim);
             need(W->zero, d_zero, 2);
@@ -989,7 +1053,7 @@ static int32_t flat_search_run(cos_index *ix, const float *queries, uint32_t B, 
             need(W->cs, d_cs, (size_t)n + 1);
             need(W->pool, d_pool, (size_t)B * P);
             need(W->thr, d_thr, B);
-            need(W->app, d_app, (size_t)B * APP_CAP);
+            need(W->app, d_app, (size_t)B * plan.app_cap());
             need(W->appcnt, d_appcnt, B);
             need(W->oi, d_oi, (size_t)B * top_k);
             need(W->os, d_os, (size_t)B * top_k);
@@ -1007,12 +1071,7 @@ static int32_t flat_search_run(cos_index *ix, const float *queries, uint32_t B, 
                 e = hipGetLastError();
             }
             if (e == hipSuccess && planes) {
-                const u64 pieces = (u64)B * (kdims / 16);
-                const dim3 eg((u32)((pieces + 255) / 256));
-                if (ix->eng == ENG_Q2) hipLaunchKernelGGL(expand_digits_kernel<ENG_Q2>, eg, dim3(256), 0, st, d_qc, ix->row_stride, B, kdims, d_qd);
-                else if (ix->eng == ENG_Q1) hipLaunchKernelGGL(expand_digits_kernel<ENG_Q1>, eg, dim3(256), 0, st, d_qc, ix->row_stride, B, kdims, d_qd);
-                else hipLaunchKernelGGL(expand_digits_kernel<ENG_Q3>, eg, dim3(256), 0, st, d_qc, ix->row_stride, B, kdims, d_qd);
-                e = hipGetLastError();
+                e = launch_expand_digits(ix->eng, d_qc, ix->row_stride, B, kdims, d_qd, st);
                 if (e == hipSuccess && use_areg) e = launch_flat_scan_expand_queries(ix->eng, d_qc, ix->row_stride, B, kdims, d_qdp, st, use_fp4);
             }
             // zero-norm screening (cosine): the reference aborts a search on the first zero denominator it meets; an
@@ -1049,61 +1108,28 @@ static int32_t flat_search_run(cos_index *ix, const float *queries, uint32_t B, 
             hipLaunchKernelGGL(flat_reset_kernel, dim3(64), dim3(256), 0, st, d_pool, (u64)B * P, d_thr, d_appcnt, B, d_zero + 1); // (d_zero + 1: overflow flag of the fused path)
             e = hipGetLastError();
         }
-        FusedOut fo{d_thr, d_app, d_appcnt, APP_CAP, d_qd, sm};
-        u32 n0 = 0, seen = 0;
-        while (n0 < n && e == hipSuccess) {
-            const bool use_fused = fused && n0 > 0;
-            // chunk cap: the tile kernel's grid (and its event granularity) like 4 M; the query-resident kernel is persistent and
-            // pays ~35 us of prologue per launch, so it takes everything that is left once the 8x rule allows it
-            u32 nc = use_fused ? (u32)std::min<u64>((u64)seen * growth, use_areg || use_u8q ? (1ull << 31) : (1ull << 22)) : first;
-            nc = std::min(nc, n - n0);
-            dim3 grid((nc + CN - 1) / CN, (B + CM - 1) / CM);
-            hipEvent_t ev0 = nullptr, ev1 = nullptr;
-            e = W->event(n_ev, &ev0);
-            if (e == hipSuccess) e = W->event(n_ev + 1, &ev1);
-            if (e == hipSuccess) { n_ev += 2; e = hipEventRecord(ev0, st); }
-            if (e != hipSuccess) break;
-#define FLAT_ARGS d_qc, d_qm, d_qs, B, ix->d_codes, ix->d_mags, d_cs, ix->row_stride, n0, nc, kdims, ix->p.metric, d_scores, s_stride, fo
-#define FLAT_LAUNCH(E, F, P) hipLaunchKernelGGL((flat_codes_gemm_i8<E, F, P>), grid, dim3(512), 0, st, FLAT_ARGS)
-#define FLAT_LAUNCH_PF(E, F) do { if (pf == 2) FLAT_LAUNCH(E, F, 2); else if (pf == 3) FLAT_LAUNCH(E, F, 3); else FLAT_LAUNCH(E, F, 1); } while (0)
-// fused chunk of a masked call on the tile kernel: the masked instantiation, one k panel in flight (the default; the knob flat_pf steers the unmasked ones)
-#define FLAT_LAUNCH_MASKED(E) hipLaunchKernelGGL((flat_codes_gemm_i8<E, true, 1, true>), grid, dim3(512), 0, st, FLAT_ARGS)
-            if (use_fused && use_areg) {
-                e = launch_flat_scan(ix->eng, kdims, (u32)n_cus, st, d_qdp, d_qm, B, ix->d_codes, ix->d_mags, ix->row_stride, n0, nc, ix->p.metric, fo, use_fp4);
-                if (e != hipSuccess) break;
-            } else if (use_fused && use_u8q) {
-                e = launch_flat_scan_u8(kdims, (u32)n_cus, st, d_qc, d_qs, d_qm, B, ix->d_codes, d_cs, ix->d_mags, ix->row_stride, n0, nc, ix->p.metric, fo);
-                if (e != hipSuccess) break;
-            } else if (ix->eng == ENG_U8) {
-                if (use_fused && mp.masked) FLAT_LAUNCH_MASKED(ENG_U8); else if (use_fused) FLAT_LAUNCH_PF(ENG_U8, true); else FLAT_LAUNCH_PF(ENG_U8, false);
-            } else if (ix->eng == ENG_Q2) {
-                if (use_fused && mp.masked) FLAT_LAUNCH_MASKED(ENG_Q2); else if (use_fused) FLAT_LAUNCH_PF(ENG_Q2, true); else FLAT_LAUNCH_PF(ENG_Q2, false);
-            } else if (ix->eng == ENG_Q1) {
-                if (use_fused && mp.masked) FLAT_LAUNCH_MASKED(ENG_Q1); else if (use_fused) FLAT_LAUNCH_PF(ENG_Q1, true); else FLAT_LAUNCH_PF(ENG_Q1, false);
-            } else {
-                if (use_fused && mp.masked) FLAT_LAUNCH_MASKED(ENG_Q3); else if (use_fused) FLAT_LAUNCH_PF(ENG_Q3, true); else FLAT_LAUNCH_PF(ENG_Q3, false);
-            }
-#undef FLAT_LAUNCH_MASKED
-#undef FLAT_LAUNCH_PF
-#undef FLAT_LAUNCH
-#undef FLAT_ARGS
-            e = hipGetLastError();
-            if (e == hipSuccess) e = hipEventRecord(ev1, st);
-            if (e == hipSuccess) {
-                if (use_fused && R == 1) {
-                    hipLaunchKernelGGL(flat_select_append, dim3(B), dim3(64), 0, st, (const u64 *)d_app, d_appcnt, APP_CAP, B, d_pool, d_thr, d_zero + 1);
-                    e = hipGetLastError();
-                } else if (use_fused)
-                    e = launch_flat_append_wide(R, d_app, d_appcnt, APP_CAP, B, d_pool, d_thr, d_zero + 1, st);
-                else if (R == 1)
-                    e = launch_select(d_scores, s_stride, B, n0, nc, d_part, S, d_pool, st, d_thr, sm);
+        if (e == hipSuccess) {
+            const ScanBufs bufs{d_scores, s_stride, d_part, d_pool, d_thr, d_app, d_appcnt, d_zero + 1, sm};
+            const FusedOut fo = bufs.fused_out(plan, d_qd);
+            const CodesGemm tile{d_qc, d_qm, d_qs, B, ix->d_codes, ix->d_mags, d_cs, ix->row_stride, kdims, ix->p.metric, d_scores, s_stride, fo};
+            // a chunk's scoring kernel stands between a (start, stop) pair of events, read after the last chunk
+            e = run_chunks(plan, attempt, bufs, st, [&](const fp::Chunk &c) {
+                hipEvent_t ev0 = nullptr, ev1 = nullptr;
+                hipError_t ce = W->event(n_ev, &ev0);
+                if (ce == hipSuccess) ce = W->event(n_ev + 1, &ev1);
+                if (ce == hipSuccess) { n_ev += 2; ce = hipEventRecord(ev0, st); }
+                if (ce != hipSuccess) return ce;
+                if (c.fused && kernel == fp::ScanKernel::RESIDENT_PLANES)
+                    ce = launch_flat_scan(ix->eng, kdims, (u32)n_cus, st, d_qdp, d_qm, B, ix->d_codes, ix->d_mags, ix->row_stride, c.n0, c.nc, ix->p.metric, fo, use_fp4);
+                else if (c.fused && kernel == fp::ScanKernel::RESIDENT_U8)
+                    ce = launch_flat_scan_u8(kdims, (u32)n_cus, st, d_qc, d_qs, d_qm, B, ix->d_codes, d_cs, ix->d_mags, ix->row_stride, c.n0, c.nc, ix->p.metric, fo);
                 else
-                    e = launch_flat_select_wide(R, d_scores, s_stride, B, n0, nc, d_part, S, d_pool, d_thr, st, sm);
-            }
-            launches++;
-            streamed += (double)nc * (double)ix->row_stride * (double)((B + CM - 1) / CM);
-            n0 += nc;
-            seen += nc;
+                    ce = launch_codes_gemm(ix->eng, c.fused, pf, mp.masked, tile, c.n0, c.nc, st);
+                if (ce != hipSuccess) return ce;
+                launches++;
+                streamed += (double)c.nc * (double)ix->row_stride * (double)((B + CM - 1) / CM);
+                return hipEventRecord(ev1, st);
+            });
         }
         // rerank, then ONE copy back: results, the zero-norm flag of the queries and the overflow flag of the fused path.  (Until round 6: a
         // device round trip for the overflow flag, then the rerank, then three pageable copies.)  An overflow repeats the scan unfused.
@@ -1128,7 +1154,7 @@ static int32_t flat_search_run(cos_index *ix, const float *queries, uint32_t B, 
         zero = ho[2 * nk + B] != 0;
         const u32 hover = ho[2 * nk + B + 1];
         if (zero) break;
-        if (fused && hover != 0) continue; // the append buffer overflowed: repeat unfused
+        if (plan.fused(attempt) && hover != 0) continue; // the append buffer overflowed: repeat unfused
         memcpy(out_ids, ho, nk * 4);
         memcpy(out_scores, ho + nk, nk * 4);
         memcpy(out_counts, ho + 2 * nk, (size_t)B * 4);
@@ -1292,16 +1318,9 @@ hipError_t launch_level_table(int eng, const uint8_t *qcodes, const float *qmags
     }
     if (!first) return hipSuccess; // (the tile kernel has no queue: one launch computes the table)
     const u32 metric = 1u; // the tile kernel's unfused epilogue with the dot-product metric: the converted integer dot, no quotient
-    dim3 grid((ncols + CN - 1) / CN, (B + CM - 1) / CM);
-    FusedOut fo{nullptr, nullptr, nullptr, 0u, nullptr};
-    // two k panels in flight (one and three were measured slower in round 4)
-    if (q2)
-        hipLaunchKernelGGL((flat_codes_gemm_i8<ENG_Q2, false, 2>), grid, dim3(512), 0, st, qcodes, qmags, qsums, B, tcodes, tmags, tcsums, row_stride, 0u,
-                           ncols, kdims, metric, tab, tab_stride, fo);
-    else
-        hipLaunchKernelGGL((flat_codes_gemm_i8<ENG_U8, false, 2>), grid, dim3(512), 0, st, qcodes, qmags, qsums, B, tcodes, tmags, tcsums, row_stride, 0u,
-                           ncols, kdims, metric, tab, tab_stride, fo);
-    return hipGetLastError();
+    const CodesGemm g{qcodes, qmags, qsums, B, tcodes, tmags, tcsums, row_stride, kdims, metric, tab, tab_stride, FusedOut{nullptr, nullptr, nullptr, 0u, nullptr}};
+    // unfused, two k panels in flight (one and three were measured slower in round 4)
+    return launch_codes_gemm(q2 ? ENG_Q2 : ENG_U8, false, 2, false, g, 0u, ncols, st);
 }
 
 } // namespace cosdev

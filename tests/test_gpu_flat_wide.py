@@ -117,6 +117,30 @@ def test_fused_path_matches_oracle_and_does_not_fall_back(storage, res, dim, B, 
     assert got[3].gemm_launches == fused_launches(40000, pool_width(5 * top_k)) == 2
 
 
+@functools.lru_cache(maxsize=1)
+def _rows_once_corpus():
+    return H.clustered_corpus(40000, 128, n_centers=40, sigma=0.2, seed=41)
+
+
+@pytest.mark.parametrize("knobs", [{}, {"flat_tile_kernel": 1}], ids=["default", "tile_kernel"])
+@pytest.mark.parametrize("n,launches", [(16384, 1), (16385, 2), (40000, 2)])
+@pytest.mark.parametrize("storage,res,row_bytes", [(O.STORAGE_U8, 0, 128), (O.STORAGE_SUBBYTE, 2, 32)])
+def test_a_scan_reads_every_row_once(storage, res, row_bytes, n, launches, knobs):
+    """The chunks of a scan that does not overflow cover [0, n) exactly once: the code bytes streamed are n rows for the one block of
+    256 queries (B = 3; a u8 row of 128 dims is 128 bytes, a quaternary one 2 chunks of 16 = 32; the products are exact in a double),
+    and the launches are the schedule's (tests/golden/flat_plan_cases.txt): n = 16384 is the seed chunk alone and not fused, one row
+    more is a fused chunk of one row, 40000 = 16384 + 23616.  Query-resident kernels (128 dims has an instantiation) and the tile kernel."""
+    from cosdata_amd import _lib
+    X = _rows_once_corpus()[:n]
+    Q = mixed_queries(X, 3)
+    ix = device_index(X, storage, res)
+    with _lib.tuning(**knobs):
+        got = ix.flat_search(Q, 10, with_stats=True)
+    assert got[3].code_bytes == float(n * row_bytes * 1)
+    assert got[3].gemm_launches == launches
+    assert same(got, oracle_index(X, storage, res).flat_search_batch(Q, 10, threads=4))
+
+
 @pytest.mark.parametrize("n", [30, 100, 700])
 @pytest.mark.parametrize("top_k", [50, 204])
 def test_fewer_vectors_than_the_pool(n, top_k):
