@@ -149,7 +149,7 @@ struct Workspace {
     DevArr<u32> qsums;          // [capB] code sums of the queries (the table GEMM's recentring term; written by quantize_rows_kernel)
     DevArr<u32> tab_queue;      // [1] next work item of the table GEMM in flight (level_table_areg), zeroed before its first part
     DevArr<uint8_t> qdig;       // [capB][dims] quaternary codes: the queries' i8 digit rows (the table GEMM's resident operand)
-    DevArr<u32> fin_flags;      // [capB + 1] finalize_fast_kernel -> finalize_list_kernel hand-over: count, then the queries (kernels_walk.hip)
+    DevArr<u32> fin_flags;      // [capB + 1] finalize_fast_kernel -> finalize_list_kernel hand-over: count, then the queries (kernels_finalize.hip)
     DevArr<u64> rerank_rows;    // [B]
     VisTab vis; // EXACT mode visited filters
     cosdev::WalkOrder order; // locality order of big launches (cos_index::walk_order_min_B)

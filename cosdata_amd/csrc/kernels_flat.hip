@@ -19,10 +19,9 @@
 #include <type_traits>
 #include <vector>
 
-#include "dot_engines.h"
 #include "engine_internal.h"
+#include "exact_rerank.h"
 #include "flat_scan.h"
-#include "topk_select.h"
 
 using namespace cosdev;
 
@@ -165,7 +164,7 @@ __global__ __launch_bounds__(256) void flat_gemm_f32(const float *__restrict__ Q
                     // NaN-safe: an estimate that is not provably below the bar (incl. 0 * inf of a zero-norm operand) takes the exact path
                     if (row0 + (u32)rl < B && cv && !(est < thr_lo[rl])) {
                         const float sc = x86_div(acc[i][j][r], qm[rl] * xm);
-                        const u64 key = pack_key(simkey(sc), n0 + col);
+                        const u64 key = score_key(sc, n0 + col);
                         if (key > thr_key[rl] && scan_live<MASKED>(fo.m, row0 + (u32)rl, n0 + col)) {
                             const u32 row = row0 + (u32)rl;
                             const u32 pos = atomicAdd(&fo.app_cnt[row], 1u);
@@ -210,7 +209,7 @@ __device__ __forceinline__ void select_segments_body(const float *__restrict__ s
     for (u32 c = c0; c < c1; c += 64) {
         const u32 col = c + lane;
         u64 key = 0ull;
-        if (col < c1 && scan_live<MASKED>(m, q, n0 + col)) key = pack_key(simkey(sr[col]), n0 + col);
+        if (col < c1 && scan_live<MASKED>(m, q, n0 + col)) key = score_key(sr[col], n0 + col);
         pool_fold_lanes<1>(pool, thr, key, lane);
     }
     part[((u64)q * S + seg) * SEL + lane] = pool.e[0];
@@ -365,15 +364,10 @@ __global__ __launch_bounds__(64) void flat_rescore(const float *__restrict__ Q, 
         const bool valid = __shfl((int)(u32)(mine >> 32), src, 64) != 0;
         const u32 row = valid ? sid : 0u;
         const float dp = f32_pair_dot(X + (u64)row * x_stride, qf, dim, lane & 1);
-        const float cs = x86_div(dp, mq * xmags[row]); // dp / (mag_query * mag_raw), vector_store.rs:427
-        const u64 key = valid ? pack_key(simkey(cs), sid) : 0ull;
-        // survivor base + j was computed by lanes 2j and 2j+1 -> hand it to lane base + j
-        const int from = (2 * (lane - base)) & 63;
-        const u32 klo = (u32)__shfl((int)(u32)key, from, 64), khi = (u32)__shfl((int)(u32)(key >> 32), from, 64);
-        if (lane >= base && lane < base + 32) res[0] = ((u64)khi << 32) | klo;
+        pair_keys_to_lanes(exact_key(dp, mq, xmags[row], sid, valid), (u32)base, lane, res[0]);
     }
     bitonic_sort_desc<1>(res, lane);
-    if ((u32)lane < k) {
+    if ((u32)lane < k) { // (as write_topk<1, true>)
         const bool ok = res[0] != 0ull;
         out_ids[(u64)q * k + lane] = ok ? (u32)res[0] + id_base : 0xFFFFFFFFu;
         out_scores[(u64)q * k + lane] = ok ? simkey_inv((u32)(res[0] >> 32)) : 0.0f;
@@ -570,7 +564,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                     const float est = metric == 0u ? dotf * rx * rq[rl] : dotf;
                     if (row < B && cv && est >= thr_lo[rl]) {
                         const float sc = metric == 0u ? __fdiv_rn(dotf, __fmul_rn(qmags[row], xm)) : dotf;
-                        const u64 key = pack_key(simkey(sc), n0 + col);
+                        const u64 key = score_key(sc, n0 + col);
                         if (key > thr_key[rl] && scan_live<MASKED>(fo.m, row, n0 + col)) {
                             const u32 pos = atomicAdd(&fo.app_cnt[row], 1u);
                             if (pos < fo.cap) fo.app[(u64)row * fo.cap + pos] = key;
@@ -656,15 +650,11 @@ __global__ __launch_bounds__(64) void flat_rerank_top5k(const float *__restrict_
         const bool valid = (u32)src < ncand;
         const u32 row = valid ? sid : 0u;
         const float dp = f32_pair_dot(X + (u64)row * x_stride, qf, dim, lane & 1);
-        const float cs = x86_div(dp, mq * xmags[row]);
-        const u64 key = valid ? pack_key(simkey(cs), sid) : 0ull;
-        const int from = (2 * (lane - base)) & 63;
-        const u32 klo = (u32)__shfl((int)(u32)key, from, 64), khi = (u32)__shfl((int)(u32)(key >> 32), from, 64);
-        if (lane >= base && lane < base + 32) res[0] = ((u64)khi << 32) | klo;
+        pair_keys_to_lanes(exact_key(dp, mq, xmags[row], sid, valid), (u32)base, lane, res[0]);
     }
     bitonic_sort_desc<1>(res, lane);
     const u32 nout = ncand < k ? ncand : k;
-    if ((u32)lane < nout) {
+    if ((u32)lane < nout) { // (as write_topk<1, false>)
         out_ids[(u64)q * k + lane] = (u32)res[0] + id_base;
         out_scores[(u64)q * k + lane] = simkey_inv((u32)(res[0] >> 32));
     }
@@ -909,7 +899,7 @@ int32_t bruteforce_run(cos_index *ix, const float *queries, uint32_t B, uint32_t
         if (e != hipSuccess || !plan.fused(attempt) || hover == 0) break; // done; otherwise the append buffer overflowed: repeat unfused
     }
     if (e == hipSuccess && R == 1) {
-        hipLaunchKernelGGL(flat_rescore, dim3(B), dim3(64), (((size_t)dim * 4 + 15) & ~(size_t)15), st, d_q, (u64)dim, d_qm, B, ix->d_raw, (u64)dim,
+        hipLaunchKernelGGL(flat_rescore, dim3(B), dim3(64), staged_query_bytes(dim), st, d_q, (u64)dim, d_qm, B, ix->d_raw, (u64)dim,
                            ix->d_raw_mags, dim, d_pool, k, ix->p.id_base, d_oi, d_os);
         e = hipGetLastError();
     } else if (e == hipSuccess)
@@ -1138,7 +1128,7 @@ static int32_t flat_search_run(cos_index *ix, const float *queries, uint32_t B, 
         if (e == hipSuccess) e = W->h_out.grow(out_words);
         if (e != hipSuccess) break;
         if (R == 1) {
-            hipLaunchKernelGGL(flat_rerank_top5k, dim3(B), dim3(64), (((size_t)dim * 4 + 15) & ~(size_t)15), st, d_q, (u64)dim, d_qrm, B, ix->d_raw, (u64)dim,
+            hipLaunchKernelGGL(flat_rerank_top5k, dim3(B), dim3(64), staged_query_bytes(dim), st, d_q, (u64)dim, d_qrm, B, ix->d_raw, (u64)dim,
                                ix->d_raw_mags, dim, d_pool, 5 * top_k, top_k, ix->p.id_base, d_oi, d_os, d_oc);
         } else {
             e = launch_flat_rerank_wide(R, false, d_q, (u64)dim, d_qrm, B, ix->d_raw, (u64)dim, ix->d_raw_mags, dim, d_pool, 5 * top_k, top_k, ix->p.id_base,

@@ -11,10 +11,9 @@
 // (DESIGN.md §4.9).  This file holds the kernels and their launchers only.
 #include <hip/hip_runtime.h>
 
-#include "dot_engines.h"
 #include "engine_internal.h"
+#include "exact_rerank.h"
 #include "flat_scan.h"
-#include "topk_select.h"
 
 using namespace cosdev;
 
@@ -34,7 +33,7 @@ __device__ __forceinline__ void select_segments_w_body(const float *__restrict__
     const float *sr = scores + (u64)q * s_stride;
     const u32 c0 = seg * seg_len, c1 = (c0 + seg_len < n_chunk) ? c0 + seg_len : n_chunk;
     const u32 count = c1 > c0 ? c1 - c0 : 0u;
-    fold_stream<R>(pool, thr, batch, count, [&](u32 i) { return scan_live<MASKED>(m, q, n0 + c0 + i) ? pack_key(simkey(sr[c0 + i]), n0 + c0 + i) : 0ull; }, lane);
+    fold_stream<R>(pool, thr, batch, count, [&](u32 i) { return scan_live<MASKED>(m, q, n0 + c0 + i) ? score_key(sr[c0 + i], n0 + c0 + i) : 0ull; }, lane);
     u64 *dst = part + ((u64)q * S + seg) * (WAVE * R) + (u32)lane * R;
 #pragma unroll
     for (int r = 0; r < R; r++) dst[r] = pool[r];
@@ -96,8 +95,8 @@ __global__ __launch_bounds__(64) void flat_select_append_w(const u64 *__restrict
     if (lane == 0) { thr_out[q] = thr; app_cnt[q] = 0; }
 }
 
-// Exact re-score of a query's survivors against the raw f32 rows, sort, top k: the arithmetic of flat_rerank_top5k / flat_rescore
-// (f32_pair_dot, x86_div(dp, |q| * |x|), simkey, pack_key), one lane pair per survivor, 128 survivors per pass of the 4 waves.
+// Exact re-score of a query's survivors against the raw f32 rows, sort, top k (the rule of exact_rerank.h), one lane pair per
+// survivor, 128 survivors per pass of the 4 waves.
 //   BRUTE = false (code scan): the best min(have, ncand_max) entries of the pool (sorted by quantized score) are re-scored;
 //                              min(that, k) results and out_counts
 //   BRUTE = true  (brute force): every survivor with a non-zero score key; k results, ~0 / 0.0 where there is none
@@ -109,7 +108,7 @@ __global__ __launch_bounds__(256) void flat_rerank_w(const float *__restrict__ Q
     constexpr u32 P = WAVE * R;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     float *qf = (float *)smem_raw;                                            // [dim], padded to 16 B
-    u64 *keys = (u64 *)(smem_raw + (((size_t)dim * 4 + 15) & ~(size_t)15));   // [P]
+    u64 *keys = (u64 *)(smem_raw + staged_query_bytes(dim));   // [P]
     const int tid = threadIdx.x, lane = tid & 63;
     const u32 q = blockIdx.x;
     if (q >= B) return;
@@ -126,8 +125,7 @@ __global__ __launch_bounds__(256) void flat_rerank_w(const float *__restrict__ Q
             const bool valid = BRUTE ? (u32)(pk >> 32) != 0u : (pk != 0ull && c < lim);
             const u32 sid = (u32)pk, row = valid ? sid : 0u;
             const float dp = f32_pair_dot(X + (u64)row * x_stride, qf, dim, tid & 1);
-            const float cs = x86_div(dp, mq * xmags[row]); // dp / (mag_query * mag_raw), vector_store.rs:427
-            if (valid) key = pack_key(simkey(cs), sid);
+            key = exact_key(dp, mq, xmags[row], sid, valid);
         }
         if ((tid & 1) == 0) keys[c] = key;
     }
@@ -142,26 +140,11 @@ __global__ __launch_bounds__(256) void flat_rerank_w(const float *__restrict__ Q
     }
     bitonic_sort_desc<R>(res, lane);
     if constexpr (BRUTE) {
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            const u32 e = (u32)lane * R + r;
-            if (e < k) {
-                const bool ok = res[r] != 0ull;
-                out_ids[(u64)q * k + e] = ok ? (u32)res[r] + id_base : 0xFFFFFFFFu;
-                out_scores[(u64)q * k + e] = ok ? simkey_inv((u32)(res[r] >> 32)) : 0.0f;
-            }
-        }
+        write_topk<R, true>(res, k, k, q, id_base, out_ids, out_scores, lane);
     } else {
         const u32 ncand = have < lim ? have : lim;
         const u32 nout = ncand < k ? ncand : k;
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            const u32 e = (u32)lane * R + r;
-            if (e < nout) {
-                out_ids[(u64)q * k + e] = (u32)res[r] + id_base;
-                out_scores[(u64)q * k + e] = simkey_inv((u32)(res[r] >> 32));
-            }
-        }
+        write_topk<R, false>(res, nout, k, q, id_base, out_ids, out_scores, lane);
         if (lane == 0) out_counts[q] = nout;
     }
 }
@@ -201,7 +184,7 @@ hipError_t launch_flat_append_wide(u32 R, const u64 *d_app, u32 *d_appcnt, u32 c
 hipError_t launch_flat_rerank_wide(u32 R, bool brute, const float *Q, u64 q_stride, const float *qmags, u32 B, const float *X, u64 x_stride,
                                    const float *xmags, u32 dim, const u64 *d_pool, u32 ncand_max, u32 k, u32 id_base, u32 *out_ids, float *out_scores,
                                    u32 *out_counts, hipStream_t st) {
-    const size_t smem = (((size_t)dim * 4 + 15) & ~(size_t)15) + (size_t)R * 64 * 8;
+    const size_t smem = staged_query_bytes(dim) + (size_t)R * 64 * 8;
 #define RERANK_ARGS Q, q_stride, qmags, B, X, x_stride, xmags, dim, d_pool, ncand_max, k, id_base, out_ids, out_scores, out_counts
     if (brute) {
         WIDE_DISPATCH(R, hipLaunchKernelGGL((flat_rerank_w<RR, true>), dim3(B), dim3(256), smem, st, RERANK_ARGS))

@@ -1,4 +1,4 @@
-"""GPU: small launches finalize with eight waves per query (kernels_walk.hip finalize_one / rerank_wide: wave 0 selects the 5 x top_k
+"""GPU: small launches finalize with eight waves per query (kernels_finalize.hip finalize_one / rerank_wide: wave 0 selects the 5 x top_k
 candidates, every wave dots its share of their raw rows with the eight-lane chains, wave 0 sorts).  The one-wave kernels stay for
 big launches: both must return the same bits as each other and as the oracle (replace_with_exact_distances, vector_store.rs:404-445),
 for lists that fit one register per lane and lists that do not, the screened kernel and the general one."""
