@@ -17,12 +17,14 @@
 #include <map>
 
 #include "engine_internal.h"
+#include "meta_grow_plan.h"
 
 using namespace cosdev;
 
 namespace {
 
 constexpr u32 NONE = 0xFFFFFFFFu;
+constexpr u32 META_PSEUDO_LO = meta_grow_plan::PSEUDO_LO, META_PSEUDO_HI = 0xFFFFFFFDu; // pseudo root ..= u32::MAX - 2 (metadata/mod.rs:217)
 
 inline uint64_t splitmix64(uint64_t &st) {
     uint64_t z = (st += 0x9E3779B97F4A7C15ull);
@@ -229,6 +231,56 @@ int32_t run_batches(cos_index *ix, u32 first, const uint8_t *max_level, std::vec
     return COS_OK;
 }
 
+// ---- the pseudo-root component of a collection with a metadata schema (cos_index_build_meta, cos_index_append_meta below) ----
+inline bool is_pseudo(u32 id) { return id >= META_PSEUDO_LO && id <= META_PSEUDO_HI; }
+
+// a failed build / growth leaves the handle WITHOUT the component (filtered search: NotReady) instead of a half-linked one
+struct MetaGuard {
+    cos_index *ix;
+    bool armed = true;
+    ~MetaGuard() { if (armed) { (void)hipStreamSynchronize(ix->own_stream); cos_meta_free_levels(ix); } }
+};
+
+// Metadata::from (types.rs:112-126) for rows of the node table: the norm of the metadata dimensions (sqrt of the sequential sum of
+// squares) and the ReplicaNodeKind — 0 Base (all dimensions zero: the node lives under the main root, not here), 1 Pseudo, 2 Metadata
+void meta_row_kinds(u32 n_nodes, const u32 *node_ids, const int32_t *mbits, u32 md, std::vector<float> &mmag, std::vector<uint8_t> &kind) {
+    mmag.resize(n_nodes);
+    kind.resize(n_nodes);
+    for (u32 i = 0; i < n_nodes; i++) {
+        float acc = -0.0f;
+        for (u32 j = 0; j < md; j++) { const float x = (float)mbits[(size_t)i * md + j]; acc = acc + x * x; }
+        mmag[i] = sqrtf(acc);
+        kind[i] = mmag[i] == 0.0f ? 0 : (is_pseudo(node_ids[i]) ? 1 : 2);
+    }
+}
+
+int32_t meta_run_batches(cos_index *ix, const u32 *node_ids, const int32_t *mbits, const float *mmag, const uint8_t *max_levels, const std::vector<u32> &ord, u32 Bmax);
+
+// cos_index_append on a collection with a metadata schema: the pseudo nodes' vector moved from row n0 + 1 to row n1 + 1, and every level
+// of the resident pseudo-root component names it in d_node_vec and d_adj_vec (the component keeps no adjacency-side norms:
+// walk_meta_kernel gathers mags[], which moved with the row).  Nothing else of the component changes — node indices, ids, link state —
+// so filtered search answers as before over the old replicas.  A failure drops the component.
+int32_t meta_follow_vector_growth(cos_index *ix, u32 n0, u32 n1) {
+    hipStream_t st = ix->own_stream;
+    MetaGuard guard{ix};
+    GrowValues v;
+    v.remap_from = n0 + 1;
+    v.remap_to = n1 + 1;
+    for (LevelHost &H : ix->meta.lv) {
+        if (H.n == 0) continue;
+        DevArr<u32> adj_vec, node_vec;
+        HIP_TRY(adj_vec.alloc((size_t)H.n * H.M));
+        HIP_TRY(node_vec.alloc(H.n));
+        HIP_TRY(launch_grow_tail(H.d_adj_vec, adj_vec, H.n, H.n, 0, H.M, ROW_EMPTY, v, st));
+        HIP_TRY(launch_grow_tail(H.d_node_vec, node_vec, H.n, H.n, 0, 1, ROW_EMPTY, v, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        adj_vec.swap(H.d_adj_vec);
+        node_vec.swap(H.d_node_vec);
+    }
+    guard.armed = false;
+    return COS_OK;
+}
+
 } // namespace
 
 extern "C" int32_t cos_index_build(cos_index *ix, uint32_t batch_size) {
@@ -299,7 +351,7 @@ extern "C" int32_t cos_index_build(cos_index *ix, uint32_t batch_size) {
     guard.armed = false;
     ix->link.rng = rng;
     ix->link.n_built = n;
-    ix->link.valid = ix->id_stride == 1u; // (collections with a metadata schema reserve ids per embedding: not appendable here)
+    ix->link.valid = true;
     if (int32_t rc2 = cos_prepare_walk_plans(ix)) return rc2; // order ranks + level-table operand of the new graph, outside any search
     return COS_OK; // the id-format host copy is made on demand (cos_index_download_graph_level)
 }
@@ -368,6 +420,7 @@ extern "C" int32_t cos_index_release_link_state(cos_index *ix) {
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(ix->own_stream));
     ix->link.release();
+    ix->meta.link.release(); // the pseudo-root component's (cos_index_build_meta): cos_index_append_meta then answers NotReady
     return COS_OK;
 }
 
@@ -385,8 +438,9 @@ extern "C" int32_t cos_index_append(cos_index *ix, const float *raw, uint32_t m,
     if (!ix->link.valid || ix->link.n_built != ix->n)
         return cos_fail(COS_ERR_NOT_READY, "no link state to continue from: the graph was uploaded (not built by cos_index_build on this handle), its root "
                                            "was replaced, or cos_index_release_link_state freed it");
-    if (ix->id_stride != 1u || ix->meta.mdim != 0u) return cos_fail(COS_ERR_UNIMPLEMENTED, "append on a collection with a metadata schema");
     if ((u64)ix->n + m >= 0xFFFFFFF0ull) return cos_fail(COS_ERR_INVALID, "too many vectors");
+    if (ix->meta.mdim != 0u && (u64)ix->p.id_base + ((u64)ix->n + m) * ix->id_stride >= META_PSEUDO_LO)
+        return cos_fail(COS_ERR_INVALID, "replica ids would run into the reserved id range");
     const bool borrow = (flags & COS_UPLOAD_BORROW_DEVICE) != 0;
     if (borrow != !ix->raw_own) // (an empty owner = the table is the caller's)
         return cos_fail(COS_ERR_INVALID, borrow ? "the index owns its raw rows: append host rows" : "the index borrows its raw rows: append with COS_UPLOAD_BORROW_DEVICE and the whole grown table");
@@ -436,6 +490,10 @@ extern "C" int32_t cos_index_append(cos_index *ix, const float *raw, uint32_t m,
         ix->d_raw = borrow ? raw : ix->raw_own.p;
         ix->n = n1; // (the locals free the old arrays)
     }
+    if (ix->meta.mdim != 0u) { // the resident pseudo-root component names the pseudo nodes' vector row
+        rc = meta_follow_vector_growth(ix, n0, n1);
+        if (rc) return rc;
+    }
 
     // ---- 2. level draws of the new ids: the draws a full build would have given them
     uint64_t rng = ix->link.rng;
@@ -454,7 +512,7 @@ extern "C" int32_t cos_index_append(cos_index *ix, const float *raw, uint32_t m,
         const u32 nl0 = H.n, nl1 = nl0 + add[l], M = H.M;
         cursor[l] = nl0 - 1; // the first new node takes the root's old index
         H.node_ids.pop_back();
-        for (u32 i = 0; i < m; i++) if (max_level[i] >= l) H.node_ids.push_back(n0 + i);
+        for (u32 i = 0; i < m; i++) if (max_level[i] >= l) H.node_ids.push_back((n0 + i) * ix->id_stride); // internal id of vector row n0 + i
         H.node_ids.push_back(COS_ROOT_ID);
         H.host_valid = false;
         H.nbr_ids.clear();
@@ -765,7 +823,7 @@ extern "C" int32_t cos_index_delete(cos_index *ix, const uint32_t *ids, uint32_t
 extern "C" int32_t cos_index_build_meta(cos_index *ix, uint32_t n_nodes, const uint32_t *node_ids, const int32_t *mbits, const uint8_t *max_levels,
                                         uint32_t batch_size) {
     if (!ix || !node_ids || !mbits || !max_levels || n_nodes == 0) return cos_fail(COS_ERR_INVALID, "null/empty node table");
-    constexpr u32 PSEUDO_LO = 0xFFFFFEFEu, PSEUDO_HI = 0xFFFFFFFDu;
+    constexpr u32 PSEUDO_LO = META_PSEUDO_LO;
     u32 vmode;
     { std::lock_guard<std::mutex> g(ix->mu); vmode = ix->p.visited_mode; }
     if (vmode != COS_VISITED_REF) return cos_fail(COS_ERR_UNIMPLEMENTED, "the metadata component is built and searched with the reference's PerformantFixedSet filter only");
@@ -778,20 +836,13 @@ extern "C" int32_t cos_index_build_meta(cos_index *ix, uint32_t n_nodes, const u
     // nodes each whatever its size, and a round costs what its PENDING list costs — 600 k nodes: 27 s at 4096, 16.4 s at 1024 or 256
     const u32 Bmax = std::min<u32>(batch_size ? batch_size : 1024u, LINK_MAX_BATCH);
     hipStream_t st = ix->own_stream;
-    auto is_pseudo = [&](u32 id) { return id >= PSEUDO_LO && id <= PSEUDO_HI; };
     const std::vector<u32> &tab = ix->meta.node_ids;
     if (!std::binary_search(tab.begin(), tab.end(), PSEUDO_LO)) return cos_fail(COS_ERR_INVALID, "the node table has no pseudo root (u32::MAX - 257)");
     for (u32 i = 0; i < n_nodes; i++)
         if (max_levels[i] > Ltop) return cos_fail(COS_ERR_INVALID, "node %u: level %u above num_layers %u", node_ids[i], max_levels[i], Ltop);
-    // Metadata::from (types.rs:112-126): a node whose metadata dimensions are all zero is a Base replica — it lives under the main root
-    std::vector<float> mmag(n_nodes);
-    std::vector<uint8_t> kind(n_nodes);
-    for (u32 i = 0; i < n_nodes; i++) {
-        float acc = -0.0f;
-        for (u32 j = 0; j < md; j++) { const float x = (float)mbits[(size_t)i * md + j]; acc = acc + x * x; }
-        mmag[i] = sqrtf(acc);
-        kind[i] = mmag[i] == 0.0f ? 0 : (is_pseudo(node_ids[i]) ? 1 : 2);
-    }
+    std::vector<float> mmag;
+    std::vector<uint8_t> kind;
+    meta_row_kinds(n_nodes, node_ids, mbits, md, mmag, kind);
     std::vector<u32> ord; // insertion order: pseudo nodes (ascending id, the root excluded), then the Metadata replicas (ascending id)
     for (int pass = 0; pass < 2; pass++)
         for (u32 i = 0; i < n_nodes; i++) {
@@ -799,20 +850,11 @@ extern "C" int32_t cos_index_build_meta(cos_index *ix, uint32_t n_nodes, const u
             if (node_ids[i] == PSEUDO_LO || ps != (pass == 0) || kind[i] == 0) continue;
             ord.push_back(i);
         }
-    const u32 total = (u32)ord.size();
 
-    struct Guard { // a failed build leaves the handle without the component (filtered search: NotReady)
-        cos_index *ix;
-        bool armed = true;
-        ~Guard() { if (armed) { (void)hipStreamSynchronize(ix->own_stream); cos_meta_free_levels(ix); } }
-    } guard{ix};
+    MetaGuard guard{ix}; // a failed build leaves the handle without the component (filtered search: NotReady)
 
-    // ---- level skeletons: the root + every node whose level reaches l, ascending id; every slot empty ------------------------------
-    u32 maxM = 0;
-    std::vector<DevBuf> key(L1), low_idx(L1), low_key(L1), owner(L1), d_kind(L1);
-    std::vector<std::vector<u32>> tab_of(L1); // per level: node index -> row of the node table
-    LinkArgs la;
-    memset(&la, 0, sizeof(la));
+    // ---- level skeletons: the root + every node whose level reaches l, ascending id; every slot empty; the link state beside them ------
+    MetaLinkState &ls = ix->meta.link; // (released with the old levels by cos_index_upload_meta_nodes)
     ix->meta.lv.resize(L1);
     for (u32 l = 0; l <= Ltop; l++) {
         LevelHost &H = ix->meta.lv[l];
@@ -821,7 +863,6 @@ extern "C" int32_t cos_index_build_meta(cos_index *ix, uint32_t n_nodes, const u
         for (u32 i = 0; i < n_nodes; i++)
             if (node_ids[i] == PSEUDO_LO || (kind[i] != 0 && max_levels[i] >= l)) rows.push_back(i);
         const u32 nl = (u32)rows.size(), M = H.M;
-        maxM = std::max(maxM, M);
         H.node_ids.resize(nl);
         std::vector<u32> node_vec(nl), node_meta(nl), child(nl);
         std::vector<uint8_t> kd(nl);
@@ -837,7 +878,6 @@ extern "C" int32_t cos_index_build_meta(cos_index *ix, uint32_t n_nodes, const u
                 child[i] = (u32)(std::lower_bound(D.begin(), D.end(), id) - D.begin());
             }
         }
-        tab_of[l] = std::move(rows);
         auto up = [&](DevArr<u32> &dst, const std::vector<u32> &src) -> hipError_t {
             hipError_t e = dst.alloc(src.size());
             return e == hipSuccess ? hipMemcpy(dst, src.data(), src.size() * 4, hipMemcpyHostToDevice) : e;
@@ -852,29 +892,55 @@ extern "C" int32_t cos_index_build_meta(cos_index *ix, uint32_t n_nodes, const u
         if (l > 0) HIP_TRY(up(H.d_child, child));
         H.n = nl;
         H.host_valid = false;
-        HIP_TRY(key[l].alloc((size_t)nl * M * 4));
-        HIP_TRY(low_idx[l].alloc(nl));
-        HIP_TRY(low_key[l].alloc((size_t)nl * 4));
-        HIP_TRY(owner[l].alloc((size_t)nl * 4));
-        HIP_TRY(d_kind[l].alloc(nl));
-        HIP_TRY(launch_fill_i32(key[l].as<int32_t>(), (u64)nl * M, INT32_MIN, st));
-        HIP_TRY(hipMemsetAsync(low_idx[l].p, 0, nl, st));
-        HIP_TRY(launch_fill_i32(low_key[l].as<int32_t>(), nl, order_key(metric, metric_min(metric)), st));
-        HIP_TRY(hipMemsetAsync(owner[l].p, 0, (size_t)nl * 4, st));
-        HIP_TRY(hipMemcpy(d_kind[l].p, kd.data(), nl, hipMemcpyHostToDevice));
+        HIP_TRY(ls.key[l].alloc((size_t)nl * M * 4));
+        HIP_TRY(ls.low_idx[l].alloc(nl));
+        HIP_TRY(ls.low_key[l].alloc((size_t)nl * 4));
+        HIP_TRY(ls.owner[l].alloc((size_t)nl * 4));
+        HIP_TRY(ls.kind[l].alloc(nl));
+        HIP_TRY(launch_fill_i32(ls.key[l].as<int32_t>(), (u64)nl * M, INT32_MIN, st));
+        HIP_TRY(hipMemsetAsync(ls.low_idx[l].p, 0, nl, st));
+        HIP_TRY(launch_fill_i32(ls.low_key[l].as<int32_t>(), nl, order_key(metric, metric_min(metric)), st));
+        HIP_TRY(hipMemsetAsync(ls.owner[l].p, 0, (size_t)nl * 4, st));
+        HIP_TRY(hipMemcpy(ls.kind[l].p, kd.data(), nl, hipMemcpyHostToDevice));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+
+    rc = meta_run_batches(ix, node_ids, mbits, mmag.data(), max_levels, ord, Bmax);
+    if (rc) return rc;
+    ls.valid = true; // kept for cos_index_append_meta until cos_index_release_link_state
+    guard.armed = false;
+    return COS_OK;
+}
+
+namespace {
+
+// The batch loop of cos_index_build_meta and cos_index_append_meta: the nodes ord[0], ord[1], ... (positions in the caller's node_ids /
+// mbits / mmag / max_levels) are inserted by the schedule CONTINUED at ix->meta.link.inserted — batches of min(Bmax, max(1, inserted / 4))
+// walk the snapshot that precedes them, then the link rounds run on the handle's link state.  The levels already hold every node of
+// `ord` (all slots empty, claim tags zero: a new tag epoch).
+int32_t meta_run_batches(cos_index *ix, const u32 *node_ids, const int32_t *mbits, const float *mmag, const uint8_t *max_levels, const std::vector<u32> &ord, u32 Bmax) {
+    const u32 n = ix->n, Ltop = ix->p.num_layers, L1 = Ltop + 1, metric = ix->p.metric, md = ix->meta.mdim;
+    hipStream_t st = ix->own_stream;
+    MetaLinkState &ls = ix->meta.link;
+    LinkArgs la;
+    memset(&la, 0, sizeof(la));
+    u32 maxM = 0;
+    for (u32 l = 0; l <= Ltop; l++) {
+        LevelHost &H = ix->meta.lv[l];
         LinkLevelDev &D = la.lv[l];
         D.adj_vec = H.d_adj_vec;
         D.adj_node = H.d_adj_node;
         D.node_vec = H.d_node_vec;
-        D.key = key[l].as<int32_t>();
-        D.low_idx = low_idx[l].as<uint8_t>();
-        D.low_key = low_key[l].as<int32_t>();
-        D.owner = owner[l].as<u32>();
-        D.kind = d_kind[l].as<uint8_t>();
-        D.M = M;
+        D.key = ls.key[l].as<int32_t>();
+        D.low_idx = ls.low_idx[l].as<uint8_t>();
+        D.low_key = ls.low_key[l].as<int32_t>();
+        D.owner = ls.owner[l].as<u32>();
+        D.kind = ls.kind[l].as<uint8_t>();
+        D.M = H.M;
+        maxM = std::max(maxM, H.M);
     }
     if (maxM > 256) return cos_fail(COS_ERR_UNIMPLEMENTED, "more than 256 neighbour slots per node");
-    HIP_TRY(hipStreamSynchronize(st));
+    const u32 first = ls.inserted, total = first + (u32)ord.size();
 
     const u32 KEEP = (u32)KEEP_INDEX;
     DevBuf d_rows, d_self, d_foff, d_fdims, d_fmags, d_qc, d_qm, d_out_ids, d_out_nodes, d_out_sims, d_out_counts, d_status, d_me, d_pend[2], d_cnt, d_evq;
@@ -910,13 +976,13 @@ extern "C" int32_t cos_index_build_meta(cos_index *ix, uint32_t n_nodes, const u
 
     IndexDev dev = cos_make_meta_dev(ix);
     dev.visited_mode = COS_VISITED_REF;
-    u32 inserted = 0, round = 0;
+    u32 inserted = first, round = 0;
     u32 *cnt = d_cnt.as<u32>();
     while (inserted < total) {
         const u32 bs = std::min({Bmax, std::max(1u, inserted / 4u), total - inserted});
         u32 np = 0;
         for (u32 b = 0; b < bs; b++) {
-            const u32 t = ord[inserted + b], id = node_ids[t];
+            const u32 t = ord[inserted - first + b], id = node_ids[t];
             h_rows[b] = is_pseudo(id) ? n + 1 : id / ix->id_stride;
             h_self[b] = id;
             h_foff[b] = b;
@@ -965,13 +1031,13 @@ extern "C" int32_t cos_index_build_meta(cos_index *ix, uint32_t n_nodes, const u
         HIP_TRY(hipStreamSynchronize(st));
         for (u32 b = 0; b < bs; b++)
             if (h_status[b] != COS_OK)
-                return cos_fail(h_status[b], "node %u of the metadata component cannot be indexed (status %d)", node_ids[ord[inserted + b]], h_status[b]);
+                return cos_fail(h_status[b], "node %u of the metadata component cannot be indexed (status %d)", node_ids[ord[inserted - first + b]], h_status[b]);
         u32 pending_ub = np, cur = 0;
         while (pending_ub > 0) {
             const u32 chunk = pending_ub > 64 ? 2 : 4;
             for (u32 r = 0; r < chunk; r++) {
                 if (++round > LINK_MAX_ROUND) {
-                    for (u32 l = 0; l <= Ltop; l++) HIP_TRY(hipMemsetAsync(owner[l].p, 0, (size_t)ix->meta.lv[l].n * 4, st));
+                    for (u32 l = 0; l <= Ltop; l++) HIP_TRY(hipMemsetAsync(ls.owner[l].p, 0, (size_t)ix->meta.lv[l].n * 4, st));
                     round = 1;
                 }
                 HIP_TRY(launch_link_round(la, maxM, d_pend[cur].as<u32>(), cnt + cur, d_pend[cur ^ 1].as<u32>(), cnt + (cur ^ 1), d_evq.as<u32>(), cnt + 2,
@@ -985,6 +1051,153 @@ extern "C" int32_t cos_index_build_meta(cos_index *ix, uint32_t n_nodes, const u
         inserted += bs;
     }
     HIP_TRY(hipStreamSynchronize(st));
+    ls.inserted = total;
+    return COS_OK;
+}
+
+} // namespace
+
+// index_embeddings on a LIVE collection with a metadata schema, the component's half (vector_store.rs:484-640; the embeddings themselves:
+// cos_index_append).  The new replicas' ids lie above every resident replica's and below the pseudo range, so on every level — and in the
+// node table — they go between the old replicas and the pseudo nodes: every array grows in front of its tail (grow_tail_kernel), the
+// indices that point into a tail follow it (meta_grow_plan.h), and the schedule of cos_index_build_meta continues at the number of nodes
+// it has inserted.  oracle/cosdata_oracle_hnsw.c: coso_meta_build_rounds over the WHOLE table is the CPU statement when the earlier calls
+// ended on one of its batch boundaries; tests/test_gpu_meta_append.py asserts identical graphs.
+extern "C" int32_t cos_index_append_meta(cos_index *ix, uint32_t n_new, const uint32_t *node_ids, const int32_t *mbits, const uint8_t *max_levels,
+                                         uint32_t batch_size) {
+    if (!ix || !node_ids || !mbits || !max_levels || n_new == 0) return cos_fail(COS_ERR_INVALID, "null/empty node list");
+    const u32 Ltop = ix->p.num_layers, L1 = Ltop + 1, metric = ix->p.metric, md = ix->meta.mdim;
+    MetaLinkState &ls = ix->meta.link;
+    bool resident = md != 0u && ix->have_vectors && ix->meta.lv.size() == L1 && ls.valid;
+    for (u32 l = 0; resident && l <= Ltop; l++) resident = ix->meta.lv[l].n != 0 && ls.key[l].p != nullptr;
+    if (!resident)
+        return cos_fail(COS_ERR_NOT_READY, "no component to continue: cos_index_build_meta has not built one on this handle (an uploaded component has no "
+                                           "link state), or cos_index_release_link_state freed its link state");
+    u32 vmode;
+    { std::lock_guard<std::mutex> g(ix->mu); vmode = ix->p.visited_mode; }
+    if (vmode != COS_VISITED_REF) return cos_fail(COS_ERR_INVALID, "the metadata component is built and searched with the reference's PerformantFixedSet filter only");
+    std::vector<u32> &tab = ix->meta.node_ids;
+    const u32 n_tab = (u32)tab.size(), tab_tail = meta_grow_plan::tail_first(tab.data(), n_tab);
+    if ((u64)n_tab + n_new >= 0xFFFFFFF0ull) return cos_fail(COS_ERR_INVALID, "too many nodes");
+    for (u32 i = 0; i < n_new; i++) {
+        const u32 id = node_ids[i];
+        if (i && id <= node_ids[i - 1]) return cos_fail(COS_ERR_INVALID, "node ids must be strictly ascending");
+        if (is_pseudo(id)) return cos_fail(COS_ERR_INVALID, "node %u lies in the pseudo nodes' id range", id);
+        if (tab_tail > 0 && id <= tab[tab_tail - 1]) return cos_fail(COS_ERR_INVALID, "node %u is not above every resident replica id (%u)", id, tab[tab_tail - 1]);
+        if (id / ix->id_stride >= ix->n) return cos_fail(COS_ERR_INVALID, "replica id %u has no resident vector (cos_index_append first)", id);
+        if (max_levels[i] > Ltop) return cos_fail(COS_ERR_INVALID, "node %u: level %u above num_layers %u", id, max_levels[i], Ltop);
+    }
+    int32_t rc = cos_set_device(ix);
+    if (rc) return rc;
+    const u32 Bmax = std::min<u32>(batch_size ? batch_size : 1024u, LINK_MAX_BATCH);
+    hipStream_t st = ix->own_stream;
+    HIP_TRY(hipDeviceSynchronize()); // exclusive: whatever read the old arrays is done
+
+    std::vector<float> mmag;
+    std::vector<uint8_t> kind;
+    meta_row_kinds(n_new, node_ids, mbits, md, mmag, kind); // (no pseudo id among them: 0 Base or 2 Metadata)
+    std::vector<u32> tails(L1);
+    for (u32 l = 0; l <= Ltop; l++) tails[l] = ix->meta.lv[l].root_idx; // the pseudo root is the first pseudo node of every level
+    const std::vector<meta_grow_plan::LevelPlan> plan = meta_grow_plan::plan_levels(tails, n_new, kind.data(), max_levels);
+
+    // ---- 1. every array grows into a local; nothing of the handle changes before all of them are written ---------------------------
+    struct Grown {
+        DevArr<u32> adj_vec, adj_node, node_vec, node_id, node_meta, child;
+        DevBuf key, low_idx, low_key, owner, kind;
+        std::vector<u32> h_vec, h_id, h_meta; // the new nodes' entries (alive until the copies below have run)
+    };
+    std::vector<Grown> grown(L1);
+    DevArr<int32_t> new_mbits;
+    DevArr<float> new_mmags;
+    const GrowValues as_is;
+    auto put = [&](u32 *dst, const std::vector<u32> &src) { return src.empty() ? hipSuccess : hipMemcpyAsync(dst, src.data(), src.size() * 4, hipMemcpyHostToDevice, st); };
+    for (u32 l = 0; l <= Ltop; l++) {
+        LevelHost &H = ix->meta.lv[l];
+        Grown &G = grown[l];
+        const meta_grow_plan::LevelPlan &P = plan[l];
+        const u32 nl0 = H.n, tf = P.tail_first, add = P.add, nl1 = nl0 + add, M = H.M;
+        GrowValues nodes_here, table_rows, nodes_below; // what a stored index points into: this level | the node table | the level below
+        nodes_here.shift_from = tf; nodes_here.shift_add = add;
+        table_rows.shift_from = tab_tail; table_rows.shift_add = n_new;
+        if (l > 0) { nodes_below.shift_from = plan[l - 1].tail_first; nodes_below.shift_add = plan[l - 1].add; }
+        HIP_TRY(G.adj_vec.alloc((size_t)nl1 * M));
+        HIP_TRY(G.adj_node.alloc((size_t)nl1 * M));
+        HIP_TRY(G.node_vec.alloc(nl1));
+        HIP_TRY(G.node_id.alloc(nl1));
+        HIP_TRY(G.node_meta.alloc(nl1));
+        HIP_TRY(G.key.alloc((size_t)nl1 * M * 4));
+        HIP_TRY(G.low_idx.alloc(nl1));
+        HIP_TRY(G.low_key.alloc((size_t)nl1 * 4));
+        HIP_TRY(G.owner.alloc((size_t)nl1 * 4));
+        HIP_TRY(G.kind.alloc(nl1));
+        HIP_TRY(launch_grow_tail(H.d_adj_vec, G.adj_vec, nl0, tf, add, M, ROW_EMPTY, as_is, st));
+        HIP_TRY(launch_grow_tail(H.d_adj_node, G.adj_node, nl0, tf, add, M, ROW_EMPTY, nodes_here, st));
+        HIP_TRY(launch_grow_tail(H.d_node_vec, G.node_vec, nl0, tf, add, 1, ROW_EMPTY, as_is, st));
+        HIP_TRY(launch_grow_tail(H.d_node_id, G.node_id, nl0, tf, add, 1, ROW_EMPTY, as_is, st));
+        HIP_TRY(launch_grow_tail(H.d_node_meta, G.node_meta, nl0, tf, add, 1, ROW_EMPTY, table_rows, st));
+        HIP_TRY(launch_grow_tail(ls.key[l].as<u32>(), G.key.as<u32>(), nl0, tf, add, M, (u32)INT32_MIN, as_is, st));
+        HIP_TRY(launch_grow_tail(ls.low_key[l].as<u32>(), G.low_key.as<u32>(), nl0, tf, add, 1, (u32)order_key(metric, metric_min(metric)), as_is, st));
+        HIP_TRY(launch_grow_tail_bytes(ls.low_idx[l].as<uint8_t>(), G.low_idx.as<uint8_t>(), nl0, tf, add, 0, st));
+        HIP_TRY(launch_grow_tail_bytes(ls.kind[l].as<uint8_t>(), G.kind.as<uint8_t>(), nl0, tf, add, 2, st)); // every new node is a Metadata replica
+        HIP_TRY(hipMemsetAsync(G.owner.p, 0, (size_t)nl1 * 4, st)); // a new tag epoch (meta_run_batches starts at round 1)
+        for (u32 k = 0; k < add; k++) {
+            const u32 i = P.who[k];
+            G.h_vec.push_back(node_ids[i] / ix->id_stride);
+            G.h_id.push_back(node_ids[i]);
+            G.h_meta.push_back(tab_tail + i); // the call's rows go into the node table in order, in front of its pseudo rows
+        }
+        HIP_TRY(put(G.node_vec + tf, G.h_vec));
+        HIP_TRY(put(G.node_id + tf, G.h_id));
+        HIP_TRY(put(G.node_meta + tf, G.h_meta));
+        if (l > 0) {
+            HIP_TRY(G.child.alloc(nl1));
+            HIP_TRY(launch_grow_tail(H.d_child, G.child, nl0, tf, add, 1, ROW_EMPTY, nodes_below, st));
+            HIP_TRY(put(G.child + tf, P.child));
+        }
+    }
+    HIP_TRY(new_mbits.alloc(((size_t)n_tab + n_new) * md));
+    HIP_TRY(new_mmags.alloc((size_t)n_tab + n_new));
+    HIP_TRY(launch_grow_tail((const u32 *)ix->meta.d_mbits.p, (u32 *)new_mbits.p, n_tab, tab_tail, n_new, md, 0u, as_is, st));
+    HIP_TRY(launch_grow_tail((const u32 *)ix->meta.d_mmags.p, (u32 *)new_mmags.p, n_tab, tab_tail, n_new, 1, 0u, as_is, st));
+    HIP_TRY(hipMemcpyAsync(new_mbits + (size_t)tab_tail * md, mbits, (size_t)n_new * md * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(new_mmags + tab_tail, mmag.data(), (size_t)n_new * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+
+    // ---- 2. commit: the grown arrays move in, the host lists follow ---------------------------------------------------------------
+    MetaGuard guard{ix}; // from here on a failure drops the component, as a failed cos_index_build_meta does
+    for (u32 l = 0; l <= Ltop; l++) {
+        LevelHost &H = ix->meta.lv[l];
+        Grown &G = grown[l];
+        const meta_grow_plan::LevelPlan &P = plan[l];
+        G.adj_vec.swap(H.d_adj_vec);
+        G.adj_node.swap(H.d_adj_node);
+        G.node_vec.swap(H.d_node_vec);
+        G.node_id.swap(H.d_node_id);
+        G.node_meta.swap(H.d_node_meta);
+        if (l > 0) G.child.swap(H.d_child);
+        G.key.swap(ls.key[l]);
+        G.low_idx.swap(ls.low_idx[l]);
+        G.low_key.swap(ls.low_key[l]);
+        G.owner.swap(ls.owner[l]);
+        G.kind.swap(ls.kind[l]);
+        H.node_ids.insert(H.node_ids.begin() + P.tail_first, G.h_id.begin(), G.h_id.end());
+        H.n += P.add;
+        H.root_idx = meta_grow_plan::remap_index(H.root_idx, P.tail_first, P.add);
+        H.host_valid = false;
+        H.nbr_ids.clear();
+    }
+    new_mbits.swap(ix->meta.d_mbits);
+    new_mmags.swap(ix->meta.d_mmags);
+    tab.insert(tab.begin() + tab_tail, node_ids, node_ids + n_new);
+    grown.clear(); // (frees the old arrays)
+    new_mbits.reset();
+    new_mmags.reset();
+
+    // ---- 3. the new Metadata replicas, batch by batch ------------------------------------------------------------------------------
+    std::vector<u32> ord;
+    for (u32 i = 0; i < n_new; i++) if (kind[i] != 0) ord.push_back(i);
+    rc = meta_run_batches(ix, node_ids, mbits, mmag.data(), max_levels, ord, Bmax);
+    if (rc) return rc;
     guard.armed = false;
     return COS_OK;
 }

@@ -192,12 +192,13 @@ IndexDev cos_make_meta_dev(const cos_index *ix) {
 
 void cos_meta_free_levels(cos_index *ix) {
     for (auto &l : ix->meta.lv) l.release();
+    ix->meta.link.release(); // the link state describes these levels
 }
 
 // the whole pseudo-root component: levels, node table, metadata dimensions, and the id stride it imposed on the base graph.
 // After this the handle is a collection without a metadata schema again (cos_index_enable_metadata re-creates row n + 1).
 static void reset_meta(cos_index *ix) {
-    for (auto &l : ix->meta.lv) l.release();
+    cos_meta_free_levels(ix);
     ix->meta.d_mbits.reset();
     ix->meta.d_mmags.reset();
     ix->meta.node_ids.clear();
@@ -1905,7 +1906,7 @@ extern "C" int32_t cos_index_upload_meta_nodes(cos_index *ix, uint32_t n_nodes, 
     }
     ix->meta.d_mbits.reset();
     ix->meta.d_mmags.reset();
-    for (auto &l : ix->meta.lv) l.release();
+    cos_meta_free_levels(ix);
     HIP_TRY(ix->meta.d_mbits.alloc((size_t)n_nodes * md));
     HIP_TRY(ix->meta.d_mmags.alloc(n_nodes));
     HIP_TRY(hipMemcpy(ix->meta.d_mbits, mbits, (size_t)n_nodes * md * 4, hipMemcpyHostToDevice));
@@ -1946,6 +1947,7 @@ extern "C" int32_t cos_index_upload_meta_graph_level(cos_index *ix, uint32_t lev
             adj_vec[(size_t)i * M + j] = node_vec[it - node_ids];
         }
     L.release();
+    ix->meta.link.release(); // an uploaded level has no link state: cos_index_append_meta continues built components only
     auto up = [&](DevArr<u32> &dst, const std::vector<u32> &src) -> hipError_t {
         hipError_t e = dst.alloc(src.size());
         return e == hipSuccess ? hipMemcpy(dst, src.data(), src.size() * 4, hipMemcpyHostToDevice) : e;

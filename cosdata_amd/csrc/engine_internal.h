@@ -28,6 +28,10 @@ hipError_t launch_index_pair_distances(int eng, const uint8_t *codes, const floa
                                        const u32 *d_pair_y, u32 n_pairs, float *d_out, int32_t *d_status, hipStream_t st); // kernels_misc.hip
 hipError_t launch_grow_rows(const u32 *src, u32 *dst, u32 old_n, u32 new_n, u32 M, u32 remap_from, u32 remap_to, u32 fill, hipStream_t st);
 hipError_t launch_grow_bytes(const uint8_t *src, uint8_t *dst, u32 old_n, u32 new_n, hipStream_t st);
+// the pseudo-root component's growth (cos_index_append_meta): rows [tail_first, old_n) move up by `add`, the rows between are `fill`;
+// of the copied values, remap_from becomes remap_to, any other at or above shift_from (the empty slot excepted) gains shift_add
+hipError_t launch_grow_tail(const u32 *src, u32 *dst, u32 old_n, u32 tail_first, u32 add, u32 M, u32 fill, const GrowValues &v, hipStream_t st);
+hipError_t launch_grow_tail_bytes(const uint8_t *src, uint8_t *dst, u32 old_n, u32 tail_first, u32 add, uint8_t fill, hipStream_t st);
 hipError_t launch_fill_adj_mag(const u32 *adj_vec, const float *mags, float *adj_mag, u32 n, u32 M, u32 slots, hipStream_t st);
 hipError_t launch_fill_adj_up(const u32 *adj_vec, const u32 *adj_node, const float *mags, const u32 *child_up, u32 n_up, u32 *up, AdjUp *adj_up, u32 n, u32 M, u32 slots,
                               hipStream_t st);
@@ -190,12 +194,27 @@ struct Workspace {
 
 // The pseudo-root component of a collection with a metadata schema: pseudo nodes + Metadata replicas, a graph of
 // its own next to the base graph.  Node table = level 0 of the component, ascending replica id.
+// What cos_index_build_meta leaves behind so that cos_index_append_meta can CONTINUE it: LinkState's arrays for the component's levels,
+// every node's ReplicaNodeKind (LinkLevelDev::kind) and how many nodes the schedule has inserted.  4 bytes per neighbour slot and 10
+// bytes per node of a level; freed by cos_index_release_link_state and with the levels (an uploaded component has none).
+struct MetaLinkState {
+    DevBuf key[cosdev::MAX_LEVELS], low_idx[cosdev::MAX_LEVELS], low_key[cosdev::MAX_LEVELS], owner[cosdev::MAX_LEVELS], kind[cosdev::MAX_LEVELS];
+    u32 inserted = 0; // nodes inserted so far: pseudo nodes without the pseudo root + Metadata replicas
+    bool valid = false;
+    void release() {
+        for (int l = 0; l < cosdev::MAX_LEVELS; l++) { key[l].reset(); low_idx[l].reset(); low_key[l].reset(); owner[l].reset(); kind[l].reset(); }
+        inserted = 0;
+        valid = false;
+    }
+};
+
 struct MetaGraph {
     u32 mdim = 0;                 // metadata dimensions per node (0 = the index has no metadata schema)
     std::vector<u32> node_ids;    // [n_meta] ascending
     DevArr<int32_t> d_mbits;      // [n_meta][mdim]
     DevArr<float> d_mmags;        // [n_meta]
     std::vector<LevelHost> lv;    // [num_layers + 1]
+    MetaLinkState link;           // cos_index_build_meta -> cos_index_append_meta (builder.hip); dropped with the levels
 };
 
 // Device-side resources of ONE host-API call in flight (cos_search_batch, cos_ann_search_batch, cos_search_filtered_batch):

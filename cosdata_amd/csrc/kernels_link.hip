@@ -459,6 +459,23 @@ __global__ void grow_bytes_kernel(const uint8_t *__restrict__ src, uint8_t *__re
         dst[i] = i + 1 < old_n ? src[i] : (i + 1 == new_n ? src[old_n - 1] : (uint8_t)0);
 }
 
+// cos_index_append_meta (builder.hip): a [n][M] array of the pseudo-root component grows.  Its nodes are in ascending id, so the pseudo
+// nodes are the TAIL [tail_first, old_n) of the array and the new nodes go in front of it: rows below tail_first keep their place, the
+// tail moves up by `add`, the rows between are filled.  A copied value that equals remap_from becomes remap_to (the pseudo nodes' vector
+// row after the vector table grew); any other at or above shift_from gains shift_add (an index into an array whose own tail moved; the
+// empty slot stays).  One thread per slot in destination order: consecutive lanes read and write consecutive words.
+template <typename T>
+__global__ void grow_tail_kernel(const T *__restrict__ src, T *__restrict__ dst, u32 old_n, u32 tail_first, u32 add, u32 M, T fill, u32 shift_from, u32 shift_add,
+                                 u32 remap_from, u32 remap_to) {
+    const u64 total = ((u64)old_n + add) * M, gap0 = (u64)tail_first * M, gap1 = gap0 + (u64)add * M;
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (u64)gridDim.x * blockDim.x) {
+        if (i >= gap0 && i < gap1) { dst[i] = fill; continue; }
+        const T v = src[i < gap0 ? i : i - (gap1 - gap0)];
+        if constexpr (sizeof(T) == 4) dst[i] = v == remap_from ? remap_to : (v >= shift_from && v != NONE ? v + shift_add : v);
+        else dst[i] = v;
+    }
+}
+
 // LevelDev::adj_mag (engine_types.h): the norm of every scanned neighbour slot, next to the adjacency.  slots is a power of two
 // (min of two powers of two) or the shortlist size: plain division.
 __global__ void fill_adj_mag_kernel(const u32 *__restrict__ adj_vec, const float *__restrict__ mags, float *__restrict__ adj_mag, u64 total, u32 M, u32 slots) {
@@ -536,6 +553,21 @@ hipError_t launch_grow_bytes(const uint8_t *src, uint8_t *dst, u32 old_n, u32 ne
     if (new_n == 0 || old_n == 0) return hipErrorInvalidValue;
     const u32 blocks = (u32)std::min<u64>(((u64)new_n + 255) / 256, 1u << 20);
     hipLaunchKernelGGL(grow_bytes_kernel, dim3(blocks), dim3(256), 0, st, src, dst, old_n, new_n);
+    return hipGetLastError();
+}
+
+hipError_t launch_grow_tail(const u32 *src, u32 *dst, u32 old_n, u32 tail_first, u32 add, u32 M, u32 fill, const GrowValues &v, hipStream_t st) {
+    const u64 total = ((u64)old_n + add) * M;
+    if (total == 0 || tail_first > old_n) return hipErrorInvalidValue;
+    const u32 blocks = (u32)std::min<u64>((total + 255) / 256, 1u << 20);
+    hipLaunchKernelGGL(grow_tail_kernel<u32>, dim3(blocks), dim3(256), 0, st, src, dst, old_n, tail_first, add, M, fill, v.shift_from, v.shift_add, v.remap_from, v.remap_to);
+    return hipGetLastError();
+}
+hipError_t launch_grow_tail_bytes(const uint8_t *src, uint8_t *dst, u32 old_n, u32 tail_first, u32 add, uint8_t fill, hipStream_t st) {
+    const u64 total = (u64)old_n + add;
+    if (total == 0 || tail_first > old_n) return hipErrorInvalidValue;
+    const u32 blocks = (u32)std::min<u64>((total + 255) / 256, 1u << 20);
+    hipLaunchKernelGGL(grow_tail_kernel<uint8_t>, dim3(blocks), dim3(256), 0, st, src, dst, old_n, tail_first, add, 1u, fill, NONE, 0u, NONE, NONE);
     return hipGetLastError();
 }
 

@@ -31,7 +31,13 @@ struct LinkArgs {
     int32_t kmin, kmax;  // order keys of MetricResult::min / ::max (types.rs:435-457)
 };
 
-constexpr u32 LINK_MAX_BATCH = 8192;       // batch position must fit the 13-bit field of the claim tag
+// What grow_tail_kernel does to the values it copies (launch_grow_tail): remap_from becomes remap_to, any other at or above shift_from
+// (the empty slot excepted) gains shift_add.  The default copies them as they are.
+struct GrowValues {
+    u32 shift_from = 0xFFFFFFFFu, shift_add = 0, remap_from = 0xFFFFFFFFu, remap_to = 0xFFFFFFFFu;
+};
+
+constexpr u32 LINK_MAX_BATCH = 8192;      // batch position must fit the 13-bit field of the claim tag
 constexpr u32 LINK_MAX_ROUND = (1u << 19) - 1;
 
 } // namespace cosdev

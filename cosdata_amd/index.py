@@ -228,7 +228,8 @@ class HNSWIndex:
 
     def append(self, raw_new, batch_size: int = 0):
         """vector_store::index_embeddings on a LIVE index (cos_index_append): `raw_new` [m][dim] take the ids [n, n + m) and are inserted
-        into the resident graph — the schedule of build() continued, no rebuild.  For an index that owns its raw rows (upload_vectors)."""
+        into the resident graph — the schedule of build() continued, no rebuild.  For an index that owns its raw rows (upload_vectors).
+        With a metadata schema the ids are (n + i) x max_replicas and the replica nodes follow with append_meta()."""
         x = _c(np.atleast_2d(raw_new), np.float32)
         if x.ndim != 2 or x.shape[1] != self.dim or x.shape[0] == 0:
             raise CosdataError(_lib.ERR_INVALID, f"new vectors must be [m][{self.dim}] f32, got shape {tuple(x.shape)}")
@@ -390,6 +391,15 @@ class HNSWIndex:
         ids, mb, ml = _c(node_ids, np.uint32), _c(mbits, np.int32), _c(max_levels, np.uint8)
         assert mb.shape == (ids.size, self.mdim) and ml.size == ids.size
         check(_lib.lib().cos_index_build_meta(self._h, ids.size, _p(ids), _p(mb), _p(ml), batch_size))
+        return self
+
+    def append_meta(self, node_ids, mbits, max_levels, batch_size: int = 0):
+        """the replica nodes of embeddings that append() has made resident join the component build_meta() built (cos_index_append_meta):
+        ascending replica ids above every resident one, their metadata dimensions and drawn levels; the schedule of build_meta() continued"""
+        ids, mb, ml = _c(node_ids, np.uint32), _c(mbits, np.int32), _c(max_levels, np.uint8)
+        if mb.shape != (ids.size, self.mdim) or ml.size != ids.size:
+            raise CosdataError(_lib.ERR_INVALID, f"new nodes must be ids [k], mbits [k][{self.mdim}] and max_levels [k]")
+        check(_lib.lib().cos_index_append_meta(self._h, ids.size, _p(ids), _p(mb), _p(ml), batch_size))
         return self
 
     def download_meta_graph(self):

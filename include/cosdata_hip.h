@@ -163,6 +163,8 @@ int32_t cos_index_build(cos_index *ix, uint32_t batch_size);
  *   raw, flags = COS_UPLOAD_BORROW_DEVICE: DEVICE pointer to the caller's WHOLE grown table [n + m][dim] (rows [0, n) unchanged), borrowed
  *                                          from now on — for an index whose rows were uploaded with the same flag
  * COS_ERR_NOT_READY: no graph, or no link state to continue from (the graph was uploaded, its root replaced, or the state released).
+ * A collection with a metadata schema (cos_index_enable_metadata): the new rows take the ids (n + i) x max_replicas_per_node; their
+ * replica nodes follow with cos_index_append_meta.
  * Exclusive like every graph change (no search in flight); a failed append leaves the handle without a graph. */
 int32_t cos_index_append(cos_index *ix, const float *raw, uint32_t m, uint32_t flags, uint32_t batch_size /* 0 = 4096 */);
 /* vector_store::delete_embedding (vector_store.rs:1206-1400) for the internal ids of `ids`, one after the other in the given order: per id
@@ -180,7 +182,8 @@ int32_t cos_index_delete(cos_index *ix, const uint32_t *ids, uint32_t m);
  * slot, else the first strictly smallest similarity).  Afterwards cos_index_append / cos_index_delete work on the uploaded graph; appends
  * draw their levels from the seed's stream advanced past the resident vectors.  Every storage an index can have. */
 int32_t cos_index_restore_link_state(cos_index *ix);
-/* frees the link state (as large as the adjacency: 4 bytes per neighbour slot); cos_index_append then returns COS_ERR_NOT_READY */
+/* frees the link state (as large as the adjacency: 4 bytes per neighbour slot) of the base graph and of the pseudo-root component;
+ * cos_index_append and cos_index_append_meta then return COS_ERR_NOT_READY */
 int32_t cos_index_release_link_state(cos_index *ix);
 
 /* ---- search --------------------------------------------------------------------------------- */
@@ -341,6 +344,24 @@ int32_t cos_index_upload_meta_graph_level(cos_index *ix, uint32_t level, uint32_
  * metadata dimensions are all zero are Base replicas and stay out of the component.  Replaces the node table and every level. */
 int32_t cos_index_build_meta(cos_index *ix, uint32_t n_nodes, const uint32_t *node_ids, const int32_t *mbits, const uint8_t *max_levels,
                              uint32_t batch_size /* 0 = 1024 */);
+/* index_embeddings on a LIVE collection with a metadata schema (vector_store.rs:484-640, api_service.rs:135-210), in two calls:
+ * cos_index_append adds the embeddings — their Base nodes take the ids (n + i) x max_replicas_per_node and join the base graph as on any
+ * collection, and the resident component follows the vector table's growth (the pseudo nodes' vector moves from row n + 1 to row
+ * n + m + 1), so filtered search keeps answering over the old replicas — then cos_index_append_meta adds their replica nodes to the
+ * component.  node_ids: strictly ascending replica ids of RESIDENT embeddings (id / max_replicas_per_node < n), every one above every
+ * replica id of the node table, none in the pseudo range; mbits [n_new][mdim]; max_levels [n_new] as in cos_index_build_meta.  A row
+ * whose metadata dimensions are all zero is a Base replica: recorded in the node table, inserted nowhere.  The others are inserted by
+ * the schedule of cos_index_build_meta CONTINUED at the number of nodes inserted so far: batches of min(batch_size, max(1, inserted / 4))
+ * walk the snapshot that precedes them from the pseudo root with their own dimensions as the filter, then the link kernels run on the
+ * link state cos_index_build_meta left on the handle.  The component equals one cos_index_build_meta over the whole table when the
+ * earlier calls ended on a batch boundary of that build, and always what the same schedule gives from the resident component.
+ *   COS_ERR_NOT_READY: no component built by cos_index_build_meta on this handle (it was uploaded, or never built), or
+ *                      cos_index_release_link_state freed its link state.
+ *   COS_ERR_INVALID:   one of the rules above is broken, a level is above num_layers, or the visited mode is not COS_VISITED_REF; the
+ *                      handle is unchanged and searchable.
+ * Exclusive like every graph change.  A failure after the arrays have grown drops the component, as a failed cos_index_build_meta does. */
+int32_t cos_index_append_meta(cos_index *ix, uint32_t n_new, const uint32_t *node_ids, const int32_t *mbits, const uint8_t *max_levels,
+                              uint32_t batch_size /* 0 = 1024 */);
 /* the component back on the host: node count of a level; (node_ids ascending [n_l], nbr_ids [n_l][M_l], COS_SLOT_EMPTY = null slot) */
 int32_t cos_index_meta_level_count(cos_index *ix, uint32_t level, uint32_t *out);
 int32_t cos_index_download_meta_graph_level(cos_index *ix, uint32_t level, uint32_t *node_ids, uint32_t *nbr_ids);
