@@ -17,14 +17,14 @@
 #include <map>
 
 #include "engine_internal.h"
-#include "meta_grow_plan.h"
+#include "level_grow_plan.h"
 
 using namespace cosdev;
 
 namespace {
 
 constexpr u32 NONE = 0xFFFFFFFFu;
-constexpr u32 META_PSEUDO_LO = meta_grow_plan::PSEUDO_LO, META_PSEUDO_HI = 0xFFFFFFFDu; // pseudo root ..= u32::MAX - 2 (metadata/mod.rs:217)
+static_assert(level_grow_plan::PSEUDO_LO == PSEUDO_LO && level_grow_plan::NONE == ROW_EMPTY, "level_grow_plan.h restates these");
 
 inline uint64_t splitmix64(uint64_t &st) {
     uint64_t z = (st += 0x9E3779B97F4A7C15ull);
@@ -48,6 +48,44 @@ inline int32_t order_key(u32 metric, float v) {
 }
 
 } // namespace
+
+// ---- LinkLevels (engine_internal.h): the one place a level's link state is allocated, initialised and grown -------------------------
+int32_t LinkLevels::alloc_level(u32 l, u32 nl, u32 M) {
+    HIP_TRY(key[l].alloc((size_t)nl * M * 4));
+    HIP_TRY(low_idx[l].alloc(nl));
+    HIP_TRY(low_key[l].alloc((size_t)nl * 4));
+    HIP_TRY(owner[l].alloc((size_t)nl * 4));
+    kind[l].reset();
+    return COS_OK;
+}
+
+int32_t LinkLevels::init_level(u32 l, u32 nl, u32 M, u32 metric, const uint8_t *kinds, hipStream_t st) {
+    if (int32_t rc = alloc_level(l, nl, M)) return rc;
+    HIP_TRY(launch_fill_i32(key[l].as<int32_t>(), (u64)nl * M, INT32_MIN, st));
+    HIP_TRY(hipMemsetAsync(low_idx[l].p, 0, nl, st));
+    HIP_TRY(launch_fill_i32(low_key[l].as<int32_t>(), nl, order_key(metric, metric_min(metric)), st));
+    HIP_TRY(hipMemsetAsync(owner[l].p, 0, (size_t)nl * 4, st));
+    if (kinds) {
+        HIP_TRY(kind[l].alloc(nl));
+        HIP_TRY(hipMemcpy(kind[l].p, kinds, nl, hipMemcpyHostToDevice));
+    }
+    return COS_OK;
+}
+
+int32_t LinkLevels::grow_level(u32 l, u32 old_n, u32 tail_first, u32 add, u32 M, u32 metric, LinkLevels &out, hipStream_t st) const {
+    const u32 nl = old_n + add;
+    const GrowValues as_is; // keys and caches are similarities, not indices
+    if (int32_t rc = out.alloc_level(l, nl, M)) return rc;
+    HIP_TRY(launch_grow_tail(key[l].as<u32>(), out.key[l].as<u32>(), old_n, tail_first, add, M, (u32)INT32_MIN, as_is, st));
+    HIP_TRY(launch_grow_tail(low_key[l].as<u32>(), out.low_key[l].as<u32>(), old_n, tail_first, add, 1, (u32)order_key(metric, metric_min(metric)), as_is, st));
+    HIP_TRY(launch_grow_tail_bytes(low_idx[l].as<uint8_t>(), out.low_idx[l].as<uint8_t>(), old_n, tail_first, add, 0, st));
+    HIP_TRY(hipMemsetAsync(out.owner[l].p, 0, (size_t)nl * 4, st)); // a new tag epoch (run_link_schedule starts at round 1)
+    if (kind[l].p) {
+        HIP_TRY(out.kind[l].alloc(nl));
+        HIP_TRY(launch_grow_tail_bytes(kind[l].as<uint8_t>(), out.kind[l].as<uint8_t>(), old_n, tail_first, add, 2, st)); // every new node is a Metadata replica
+    }
+    return COS_OK;
+}
 
 namespace {
 
@@ -83,43 +121,78 @@ struct GraphGuard {
     }
 };
 
-// LinkArgs over the handle's level arrays and link state
-void fill_link_levels(cos_index *ix, LinkArgs &la, u32 &maxM) {
+// The batch size of a build or an append: the caller's or the graph's default, within what a claim tag's 13-bit batch position holds.
+// The component's default is 1024 (the base graph's: 4096): every Metadata replica links to the same few pseudo nodes, the rounds of a
+// batch run ~1.4 nodes each whatever its size, and a round costs what its PENDING list costs — 600 k nodes: 27 s at 4096, 16.4 s at
+// 1024 or 256
+constexpr u32 BASE_DEFAULT_BATCH = 4096u, COMPONENT_DEFAULT_BATCH = 1024u;
+inline u32 batch_max(u32 batch_size, u32 graph_default) { return std::min<u32>(batch_size ? batch_size : graph_default, LINK_MAX_BATCH); }
+
+// LinkArgs over a graph's level arrays and link state, base graph and component alike.  Level 0 of the base graph keeps neither a
+// node-index adjacency nor a node -> vector row array (there a node index IS the vector row): adj_node = adj_vec, node_vec = nullptr.
+// `kind` is the component's (nullptr on the base graph).
+void fill_link_levels(const std::vector<LevelHost> &lv, const LinkLevels &ls, LinkArgs &la, u32 &maxM) {
     maxM = 0;
-    for (u32 l = 0; l <= ix->p.num_layers; l++) {
-        LevelHost &H = ix->lv[l];
+    for (u32 l = 0; l < (u32)lv.size(); l++) {
+        const LevelHost &H = lv[l];
         LinkLevelDev &D = la.lv[l];
         D.adj_vec = H.d_adj_vec;
-        D.adj_node = l == 0 ? H.d_adj_vec : H.d_adj_node;
-        D.node_vec = l == 0 ? nullptr : H.d_node_vec;
-        D.key = ix->link.key[l].as<int32_t>();
-        D.low_idx = ix->link.low_idx[l].as<uint8_t>();
-        D.low_key = ix->link.low_key[l].as<int32_t>();
-        D.owner = ix->link.owner[l].as<u32>();
+        D.adj_node = H.d_adj_node.p ? H.d_adj_node.p : H.d_adj_vec.p;
+        D.node_vec = H.d_node_vec;
+        D.key = ls.key[l].as<int32_t>();
+        D.low_idx = ls.low_idx[l].as<uint8_t>();
+        D.low_key = ls.low_key[l].as<int32_t>();
+        D.owner = ls.owner[l].as<u32>();
+        D.kind = ls.kind[l].as<uint8_t>();
         D.M = H.M;
         maxM = std::max(maxM, H.M);
     }
 }
 
-// The batch loop of index_embeddings for the vectors [first, ix->n): batches of min(Bmax, max(1, inserted / 4)) ids run the reference
-// walk against the snapshot that precedes the batch, then the round-synchronous link kernels connect them.  max_level is indexed by
-// vector row - first; cursor[l] = the node index the next inserted vector takes on level l (nodes are in id order, the root last).
-int32_t run_batches(cos_index *ix, u32 first, const uint8_t *max_level, std::vector<u32> &cursor, u32 Bmax) {
-    const u32 n = ix->n, Ltop = ix->p.num_layers, L1 = Ltop + 1, metric = ix->p.metric;
+// ---- the link schedule of both graphs -----------------------------------------------------------------------------------------------
+// What a graph tells the schedule about itself ...
+struct LinkSchedule {
+    const char *graph;          // which graph, for the build_profile line
+    std::vector<LevelHost> &lv; // its levels: they already hold every item of the call (all slots empty, claim tags zero: a new tag epoch)
+    LinkLevels &link;           // ... and their link state
+    u32 first, count;           // items the schedule had inserted before this call (the batch-size rule continues there) | items of this call
+    u32 md;                     // filter columns per item (0: the walk takes no filter)
+    u32 Bmax;
+};
+// ... and what its `item` callback writes for item i of the call, into the batch's staging
+struct BatchSlot {
+    u32 &row, &self_id; // the walk's query: a vector row, and the id pre-inserted in its visited filter (vector_store.rs:807)
+    u32 *me;            // [levels] the item's node index on every level it reaches; preset NONE
+    int32_t *fdims;     // [md] the query's filter columns ...
+    float &fmag;        // ... and their norm
+};
+
+// index_embeddings' batch loop: batches of min(Bmax, max(1, inserted / 4), left) items run the reference walk against the snapshot that
+// precedes the batch, then the round-synchronous link kernels (kernels_link.hip) connect them.
+//   item(i, BatchSlot)        fills the slot of item i, 0 <= i < count
+//   walk(WalkArgs &, stream)  launches the graph's insertion walk for a batch: queries, outputs, ef and keep are set
+//   fail(i, status)           -> cos_fail for item i, whose walk reported `status`
+template <typename Item, typename Walk, typename Fail>
+int32_t run_link_schedule(cos_index *ix, const LinkSchedule &s, Item item, Walk walk, Fail fail) {
+    const u32 L1 = (u32)s.lv.size(), metric = ix->p.metric, md = s.md, Bmax = s.Bmax, total = s.first + s.count;
     hipStream_t st = ix->own_stream;
     LinkArgs la;
     memset(&la, 0, sizeof(la));
     u32 maxM = 0;
-    fill_link_levels(ix, la, maxM);
+    fill_link_levels(s.lv, s.link, la, maxM);
     if (maxM > 256) return cos_fail(COS_ERR_UNIMPLEMENTED, "more than 256 neighbour slots per node");
 
-    // ---- batch workspace (device) + pinned staging -----------------------------------------------------------
+    // ---- batch workspace (device) + pinned staging: a batch's staging is rewritten only after the synchronisation that ends the
+    //      previous batch's round loop, so every upload runs asynchronously
     const u32 KEEP = (u32)KEEP_INDEX;
-    DevBuf d_rows, d_out_ids, d_out_nodes, d_out_sims, d_out_counts, d_status, d_me, d_pend[2], d_cnt, d_evq;
-    PinArr<unsigned char> h_rows, h_me, h_pend, h_status, h_cnt;
+    DevBuf d_rows, d_self, d_foff, d_fdims, d_fmags, d_out_ids, d_out_nodes, d_out_sims, d_out_counts, d_status, d_me, d_pend[2], d_cnt, d_evq;
+    PinArr<u32> h_rows, h_self, h_foff, h_me, h_pend, h_cnt;
+    PinArr<int32_t> h_fdims, h_status;
+    PinArr<float> h_fmags;
     const size_t pend_cap = (size_t)Bmax * L1;              // (level, batch position) entries
     const size_t evq_cap = pend_cap * 2 * KEEP;             // a node queues at most 2 evictions per candidate
     HIP_TRY(d_rows.alloc((size_t)Bmax * 4));
+    HIP_TRY(d_self.alloc((size_t)Bmax * 4));
     HIP_TRY(d_out_ids.alloc((size_t)Bmax * L1 * KEEP * 4));
     HIP_TRY(d_out_nodes.alloc((size_t)Bmax * L1 * KEEP * 4));
     HIP_TRY(d_out_sims.alloc((size_t)Bmax * L1 * KEEP * 4));
@@ -130,12 +203,22 @@ int32_t run_batches(cos_index *ix, u32 first, const uint8_t *max_level, std::vec
     HIP_TRY(d_pend[1].alloc(pend_cap * 4));
     HIP_TRY(d_cnt.alloc(4 * 4));                            // [0], [1]: pending counters (ping-pong); [2]: eviction queue length
     HIP_TRY(d_evq.alloc(evq_cap * 3 * 4));
-    HIP_TRY(h_rows.alloc((size_t)Bmax * 4));
-    HIP_TRY(h_me.alloc((size_t)Bmax * L1 * 4));
-    HIP_TRY(h_pend.alloc(pend_cap * 4));
-    HIP_TRY(h_status.alloc((size_t)Bmax * 4));
-    HIP_TRY(h_cnt.alloc(4 * 4));
-    VisTab vtab; // EXACT build mode: visited filters of the batch walks
+    HIP_TRY(h_rows.alloc(Bmax));
+    HIP_TRY(h_self.alloc(Bmax));
+    HIP_TRY(h_me.alloc((size_t)Bmax * L1));
+    HIP_TRY(h_pend.alloc(pend_cap));
+    HIP_TRY(h_status.alloc(Bmax));
+    HIP_TRY(h_cnt.alloc(4));
+    HIP_TRY(h_fdims.alloc((size_t)Bmax * md));
+    HIP_TRY(h_fmags.alloc(Bmax));
+    if (md) { // one filter per query: its offsets are 0, 1, 2, ... whatever the batch
+        HIP_TRY(d_foff.alloc(((size_t)Bmax + 1) * 4));
+        HIP_TRY(d_fdims.alloc((size_t)Bmax * md * 4));
+        HIP_TRY(d_fmags.alloc((size_t)Bmax * 4));
+        HIP_TRY(h_foff.alloc((size_t)Bmax + 1));
+        for (u32 b = 0; b <= Bmax; b++) h_foff[b] = b;
+        HIP_TRY(hipMemcpyAsync(d_foff.p, h_foff.p, ((size_t)Bmax + 1) * 4, hipMemcpyHostToDevice, st));
+    }
 
     la.L1 = L1;
     la.z_nodes = d_out_nodes.as<u32>();
@@ -146,44 +229,42 @@ int32_t run_batches(cos_index *ix, u32 first, const uint8_t *max_level, std::vec
     la.kmin = order_key(metric, metric_min(metric));
     la.kmax = order_key(metric, metric_max(metric));
 
-    IndexDev dev = cos_make_index_dev(ix);
-    u32 inserted = first, round = 0;
+    u32 inserted = s.first, round = 0;
     u64 n_rounds = 0, n_batches = 0;
     const bool prof = cosdev::tune_or(cosdev::TUNE_BUILD_PROFILE, 0) != 0;
     double t_walk = 0, t_link = 0;
     auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     u32 *cnt = d_cnt.as<u32>();
-    while (inserted < n) {
+    while (inserted < total) {
         const double t0 = now();
         n_batches++;
-        const u32 bs = std::min({Bmax, std::max(1u, inserted / 4u), n - inserted});
-        // batch bookkeeping: rows to walk, node index of every (batch item, level), initial pending list (all levels together)
+        const u32 bs = std::min({Bmax, std::max(1u, inserted / 4u), total - inserted});
+        // batch bookkeeping: the walks' queries, node index of every (batch item, level), initial pending list (all levels together)
         u32 np = 0;
         for (u32 b = 0; b < bs; b++) {
-            const u32 id = inserted + b;
-            h_rows.as<u32>()[b] = id;
-            for (u32 l = 0; l <= Ltop; l++) {
-                u32 m = NONE;
-                if (max_level[id - first] >= l) { m = cursor[l]++; h_pend.as<u32>()[np++] = (l << 16) | b; }
-                h_me.as<u32>()[(size_t)b * L1 + l] = m;
-            }
+            u32 *me = h_me.p + (size_t)b * L1;
+            std::fill(me, me + L1, NONE);
+            item(inserted - s.first + b, BatchSlot{h_rows[b], h_self[b], me, h_fdims.p + (size_t)b * md, h_fmags[b]});
+            for (u32 l = 0; l < L1; l++)
+                if (me[l] != NONE) h_pend[np++] = (l << 16) | b;
         }
         HIP_TRY(hipMemcpyAsync(d_rows.p, h_rows.p, (size_t)bs * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_self.p, h_self.p, (size_t)bs * 4, hipMemcpyHostToDevice, st));
+        if (md) {
+            HIP_TRY(hipMemcpyAsync(d_fdims.p, h_fdims.p, (size_t)bs * md * 4, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(d_fmags.p, h_fmags.p, (size_t)bs * 4, hipMemcpyHostToDevice, st));
+        }
         HIP_TRY(hipMemcpyAsync(d_me.p, h_me.p, (size_t)bs * L1 * 4, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(d_pend[0].p, h_pend.p, (size_t)np * 4, hipMemcpyHostToDevice, st));
-        h_cnt.as<u32>()[0] = np; h_cnt.as<u32>()[1] = 0; h_cnt.as<u32>()[2] = 0; h_cnt.as<u32>()[3] = 0;
+        h_cnt[0] = np; h_cnt[1] = 0; h_cnt[2] = 0; h_cnt[3] = 0;
         HIP_TRY(hipMemcpyAsync(cnt, h_cnt.p, 16, hipMemcpyHostToDevice, st));
-        // 1. the reference walk of every new vector against the snapshot that precedes the batch (one wave each)
+        // 1. the reference walk of every item against the snapshot that precedes the batch (one wave each)
         WalkArgs wa;
         memset(&wa, 0, sizeof(wa));
         wa.qcodes = ix->d_codes;
         wa.qmags = ix->d_mags;
         wa.q_rows = d_rows.as<u32>();
-        wa.self_ids = d_rows.as<u32>(); // the new node's id is pre-inserted in the visited filter (vector_store.rs:807)
-        if (dev.visited_mode == COS_VISITED_EXACT) {
-            const int32_t vrc = vis_tab_prepare(vtab, ix, Bmax, ix->p.ef_construction, st, wa);
-            if (vrc) return vrc;
-        }
+        wa.self_ids = d_self.as<u32>();
         wa.B = bs;
         wa.ef = ix->p.ef_construction;
         wa.keep = KEEP;
@@ -192,14 +273,16 @@ int32_t run_batches(cos_index *ix, u32 first, const uint8_t *max_level, std::vec
         wa.out_nodes = d_out_nodes.as<u32>();
         wa.out_counts = d_out_counts.as<u32>();
         wa.out_status = d_status.as<int32_t>();
-        cosdev::WalkPlanIn pin = cos_walk_plan_in(ix, bs, wa.ef); // the handle's latency knobs; an insertion walk has no table and no order
-        pin.table_min_B = pin.order_min_B = 0;
-        HIP_TRY(launch_walk(ix->eng, dev, wa, cosdev::walk_plan(pin).kernel, st));
+        if (md) {
+            wa.f_dims = d_fdims.as<int32_t>();
+            wa.f_mags = d_fmags.as<float>();
+            wa.f_off = d_foff.as<u32>();
+        }
+        if (int32_t wrc = walk(wa, st)) return wrc;
         HIP_TRY(hipMemcpyAsync(h_status.p, d_status.p, (size_t)bs * 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st)); // a failed walk leaves its lower levels unwritten: never link from it
         for (u32 b = 0; b < bs; b++)
-            if (h_status.as<int32_t>()[b] != COS_OK)
-                return cos_fail(h_status.as<int32_t>()[b], "vector %u cannot be indexed (zero norm -> DistanceError::CalculationError)", inserted + b);
+            if (h_status[b] != COS_OK) return fail(inserted - s.first + b, h_status[b]);
         t_walk += now() - t0;
         const double t1 = now();
         // 2. link rounds (kernels_link.hip).  Rounds are enqueued a few at a time; each reads the true pending count on the
@@ -209,7 +292,7 @@ int32_t run_batches(cos_index *ix, u32 first, const uint8_t *max_level, std::vec
             const u32 chunk = pending_ub > 64 ? 2 : 4;
             for (u32 r = 0; r < chunk; r++) {
                 if (++round > LINK_MAX_ROUND) { // claim tags would wrap: start a new tag epoch
-                    for (u32 l = 0; l <= Ltop; l++) HIP_TRY(hipMemsetAsync(ix->link.owner[l].p, 0, (size_t)ix->lv[l].n * 4, st));
+                    for (u32 l = 0; l < L1; l++) HIP_TRY(hipMemsetAsync(s.link.owner[l].p, 0, (size_t)s.lv[l].n * 4, st));
                     round = 1;
                 }
                 HIP_TRY(launch_link_round(la, maxM, d_pend[cur].as<u32>(), cnt + cur, d_pend[cur ^ 1].as<u32>(), cnt + (cur ^ 1), d_evq.as<u32>(), cnt + 2,
@@ -219,21 +302,45 @@ int32_t run_batches(cos_index *ix, u32 first, const uint8_t *max_level, std::vec
             }
             HIP_TRY(hipMemcpyAsync(h_cnt.p, cnt, 16, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
-            pending_ub = h_cnt.as<u32>()[cur]; // the list the next round would read
+            pending_ub = h_cnt[cur]; // the list the next round would read
         }
         t_link += now() - t1;
         inserted += bs;
     }
     HIP_TRY(hipStreamSynchronize(st));
     if (prof)
-        fprintf(stderr, "[cos_index_build] vectors [%u, %u) batches=%llu link rounds=%llu walk %.2fs link %.2fs\n", first, n, (unsigned long long)n_batches,
-                (unsigned long long)n_rounds, t_walk, t_link);
+        fprintf(stderr, "[cos_index_build] %s: items [%u, %u) batches=%llu link rounds=%llu walk %.2fs link %.2fs\n", s.graph, s.first, total,
+                (unsigned long long)n_batches, (unsigned long long)n_rounds, t_walk, t_link);
     return COS_OK;
 }
 
-// ---- the pseudo-root component of a collection with a metadata schema (cos_index_build_meta, cos_index_append_meta below) ----
-inline bool is_pseudo(u32 id) { return id >= META_PSEUDO_LO && id <= META_PSEUDO_HI; }
+// The base graph's items are the vectors [first, ix->n): max_level is indexed by vector row - first; cursor[l] = the node index the next
+// inserted vector takes on level l (nodes are in id order, the root last).
+int32_t link_vectors(cos_index *ix, u32 first, const uint8_t *max_level, std::vector<u32> &cursor, u32 Bmax) {
+    IndexDev dev = cos_make_index_dev(ix);
+    VisTab vtab; // EXACT build mode: visited filters of the batch walks
+    const LinkSchedule s{"base graph", ix->lv, ix->link.lv, first, ix->n - first, 0u, Bmax};
+    return run_link_schedule(
+        ix, s,
+        [&](u32 i, BatchSlot o) {
+            o.row = o.self_id = first + i;
+            for (u32 l = 0; l <= max_level[i]; l++) o.me[l] = cursor[l]++;
+        },
+        [&](WalkArgs &wa, hipStream_t st) -> int32_t {
+            if (dev.visited_mode == COS_VISITED_EXACT) {
+                const int32_t vrc = vis_tab_prepare(vtab, ix, Bmax, wa.ef, st, wa);
+                if (vrc) return vrc;
+            }
+            cosdev::WalkPlanIn pin = cos_walk_plan_in(ix, wa.B, wa.ef); // the handle's latency knobs; an insertion walk has no table and no order
+            pin.table_min_B = pin.order_min_B = 0;
+            HIP_TRY(launch_walk(ix->eng, dev, wa, cosdev::walk_plan(pin).kernel, st));
+            return COS_OK;
+        },
+        [&](u32 i, int32_t status) { return cos_fail(status, "vector %u cannot be indexed (zero norm -> DistanceError::CalculationError)", first + i); });
+}
 
+
+// ---- the pseudo-root component of a collection with a metadata schema (cos_index_build_meta, cos_index_append_meta below) ----
 // a failed build / growth leaves the handle WITHOUT the component (filtered search: NotReady) instead of a half-linked one
 struct MetaGuard {
     cos_index *ix;
@@ -254,7 +361,36 @@ void meta_row_kinds(u32 n_nodes, const u32 *node_ids, const int32_t *mbits, u32 
     }
 }
 
-int32_t meta_run_batches(cos_index *ix, const u32 *node_ids, const int32_t *mbits, const float *mmag, const uint8_t *max_levels, const std::vector<u32> &ord, u32 Bmax);
+// The component's items are the nodes ord[0], ord[1], ... (positions in the caller's node_ids / mbits / mmag / max_levels), inserted by the
+// schedule CONTINUED at ix->meta.link.inserted.  A node walks from the pseudo root with its OWN metadata dimensions as the query's filter
+// (walk_meta_kernel<.., INDEXING>); its node index on a level is its place in the level's ascending id list.
+int32_t link_component_nodes(cos_index *ix, const u32 *node_ids, const int32_t *mbits, const float *mmag, const uint8_t *max_levels, const std::vector<u32> &ord, u32 Bmax) {
+    const u32 n = ix->n, md = ix->meta.mdim;
+    IndexDev dev = cos_make_meta_dev(ix);
+    dev.visited_mode = COS_VISITED_REF;
+    const LinkSchedule s{"metadata component", ix->meta.lv, ix->meta.link.lv, ix->meta.link.inserted, (u32)ord.size(), md, Bmax};
+    const int32_t rc = run_link_schedule(
+        ix, s,
+        [&](u32 i, BatchSlot o) {
+            const u32 t = ord[i], id = node_ids[t];
+            o.row = is_pseudo(id) ? n + 1 : id / ix->id_stride;
+            o.self_id = id;
+            std::copy(mbits + (size_t)t * md, mbits + (size_t)(t + 1) * md, o.fdims);
+            o.fmag = mmag[t];
+            for (u32 l = 0; l <= max_levels[t]; l++) {
+                const std::vector<u32> &ids = ix->meta.lv[l].node_ids;
+                o.me[l] = (u32)(std::lower_bound(ids.begin(), ids.end(), id) - ids.begin());
+            }
+        },
+        [&](WalkArgs &wa, hipStream_t st) -> int32_t {
+            HIP_TRY(launch_walk_meta_index(ix->eng, dev, wa, st));
+            return COS_OK;
+        },
+        [&](u32 i, int32_t status) { return cos_fail(status, "node %u of the metadata component cannot be indexed (status %d)", node_ids[ord[i]], status); });
+    if (rc) return rc;
+    ix->meta.link.inserted += (u32)ord.size();
+    return COS_OK;
+}
 
 // cos_index_append on a collection with a metadata schema: the pseudo nodes' vector moved from row n0 + 1 to row n1 + 1, and every level
 // of the resident pseudo-root component names it in d_node_vec and d_adj_vec (the component keeps no adjacency-side norms:
@@ -289,7 +425,7 @@ extern "C" int32_t cos_index_build(cos_index *ix, uint32_t batch_size) {
     int32_t rc = cos_set_device(ix);
     if (rc) return rc;
     const u32 n = ix->n, Ltop = ix->p.num_layers, metric = ix->p.metric;
-    const u32 Bmax = std::min<u32>(batch_size ? batch_size : 4096u, LINK_MAX_BATCH);
+    const u32 Bmax = batch_max(batch_size, BASE_DEFAULT_BATCH);
     hipStream_t st = ix->own_stream;
     GraphGuard guard{ix};
 
@@ -333,20 +469,13 @@ extern "C" int32_t cos_index_build(cos_index *ix, uint32_t batch_size) {
             HIP_TRY(hipMemcpy(H.d_child, child.data(), (size_t)nl * 4, hipMemcpyHostToDevice));
         }
         H.n = nl;
-        // link state: slot keys (all empty), cached lowest = (0, MetricResult::min) (prob_node.rs:140), claim tags
-        HIP_TRY(ix->link.key[l].alloc((size_t)nl * M * 4));
-        HIP_TRY(ix->link.low_idx[l].alloc(nl));
-        HIP_TRY(ix->link.low_key[l].alloc((size_t)nl * 4));
-        HIP_TRY(ix->link.owner[l].alloc((size_t)nl * 4));
-        HIP_TRY(launch_fill_i32(ix->link.key[l].as<int32_t>(), (u64)nl * M, INT32_MIN, st));
-        HIP_TRY(hipMemsetAsync(ix->link.low_idx[l].p, 0, nl, st));
-        HIP_TRY(launch_fill_i32(ix->link.low_key[l].as<int32_t>(), nl, order_key(metric, metric_min(metric)), st));
-        HIP_TRY(hipMemsetAsync(ix->link.owner[l].p, 0, (size_t)nl * 4, st));
+        rc = ix->link.lv.init_level(l, nl, M, metric, nullptr, st);
+        if (rc) return rc;
     }
     HIP_TRY(hipStreamSynchronize(st));
 
     std::vector<u32> cursor(Ltop + 1, 0); // first node of each level not yet inserted (nodes are in id order)
-    rc = run_batches(ix, 0, max_level.data(), cursor, Bmax);
+    rc = link_vectors(ix, 0, max_level.data(), cursor, Bmax);
     if (rc) return rc;
     guard.armed = false;
     ix->link.rng = rng;
@@ -386,20 +515,18 @@ extern "C" int32_t cos_index_restore_link_state(cos_index *ix) {
     for (u32 l = 0; l <= Ltop; l++) {
         LevelHost &H = ix->lv[l];
         const u32 nl = H.n, M = H.M;
-        HIP_TRY(ix->link.key[l].alloc((size_t)nl * M * 4));
-        HIP_TRY(ix->link.low_idx[l].alloc(nl));
-        HIP_TRY(ix->link.low_key[l].alloc((size_t)nl * 4));
-        HIP_TRY(ix->link.owner[l].alloc((size_t)nl * 4));
-        HIP_TRY(hipMemsetAsync(ix->link.owner[l].p, 0, (size_t)nl * 4, st));
+        rc = ix->link.lv.alloc_level(l, nl, M);
+        if (rc) return rc;
+        HIP_TRY(hipMemsetAsync(ix->link.lv.owner[l].p, 0, (size_t)nl * 4, st));
         const u32 step = (u32)std::max<u64>(1, CHUNK_PAIRS / M);
         for (u32 n0 = 0; n0 < nl; n0 += step) {
             const u32 cn = std::min(step, nl - n0);
             HIP_TRY(launch_edge_pairs(H.d_adj_vec, l == 0 ? nullptr : H.d_node_vec, n0, cn, M, px.as<u32>(), py.as<u32>(), st));
             HIP_TRY(cosdev::launch_index_pair_distances(ix->eng, ix->d_codes, ix->d_mags, ix->row_stride, ix->nchunks, ix->p.dim, metric, px.as<u32>(), py.as<u32>(),
                                                        (u32)((u64)cn * M), sims.as<float>(), dst.as<int32_t>(), st));
-            HIP_TRY(launch_edge_keys(H.d_adj_vec, sims.as<float>(), dst.as<int32_t>(), n0, cn, M, metric, ix->link.key[l].as<int32_t>(), d_fail.as<int32_t>(), st));
+            HIP_TRY(launch_edge_keys(H.d_adj_vec, sims.as<float>(), dst.as<int32_t>(), n0, cn, M, metric, ix->link.lv.key[l].as<int32_t>(), d_fail.as<int32_t>(), st));
         }
-        HIP_TRY(launch_low_cache(H.d_adj_vec, ix->link.key[l].as<int32_t>(), nl, M, kmin, kmax, ix->link.low_idx[l].as<uint8_t>(), ix->link.low_key[l].as<int32_t>(), st));
+        HIP_TRY(launch_low_cache(H.d_adj_vec, ix->link.lv.key[l].as<int32_t>(), nl, M, kmin, kmax, ix->link.lv.low_idx[l].as<uint8_t>(), ix->link.lv.low_key[l].as<int32_t>(), st));
     }
     int32_t failed = 0;
     HIP_TRY(hipMemcpyAsync(&failed, d_fail.p, 4, hipMemcpyDeviceToHost, st));
@@ -439,7 +566,7 @@ extern "C" int32_t cos_index_append(cos_index *ix, const float *raw, uint32_t m,
         return cos_fail(COS_ERR_NOT_READY, "no link state to continue from: the graph was uploaded (not built by cos_index_build on this handle), its root "
                                            "was replaced, or cos_index_release_link_state freed it");
     if ((u64)ix->n + m >= 0xFFFFFFF0ull) return cos_fail(COS_ERR_INVALID, "too many vectors");
-    if (ix->meta.mdim != 0u && (u64)ix->p.id_base + ((u64)ix->n + m) * ix->id_stride >= META_PSEUDO_LO)
+    if (ix->meta.mdim != 0u && (u64)ix->p.id_base + ((u64)ix->n + m) * ix->id_stride >= PSEUDO_LO)
         return cos_fail(COS_ERR_INVALID, "replica ids would run into the reserved id range");
     const bool borrow = (flags & COS_UPLOAD_BORROW_DEVICE) != 0;
     if (borrow != !ix->raw_own) // (an empty owner = the table is the caller's)
@@ -447,7 +574,7 @@ extern "C" int32_t cos_index_append(cos_index *ix, const float *raw, uint32_t m,
     int32_t rc = cos_set_device(ix);
     if (rc) return rc;
     const u32 n0 = ix->n, n1 = n0 + m, Ltop = ix->p.num_layers, metric = ix->p.metric;
-    const u32 Bmax = std::min<u32>(batch_size ? batch_size : 4096u, LINK_MAX_BATCH);
+    const u32 Bmax = batch_max(batch_size, BASE_DEFAULT_BATCH);
     const u64 dim = ix->p.dim, rs = ix->row_stride;
     hipStream_t st = ix->own_stream;
     HIP_TRY(hipDeviceSynchronize()); // exclusive: whatever read the old arrays is done
@@ -501,69 +628,63 @@ extern "C" int32_t cos_index_append(cos_index *ix, const float *raw, uint32_t m,
     std::vector<uint8_t> max_level(m);
     for (u32 i = 0; i < m; i++) max_level[i] = draw_level(rng, pv, Ltop);
 
-    // ---- 3. every level grows: the new nodes (ascending id) go between the old nodes and the root, every slot empty; references to
-    //         the root (vector row n0 -> n1, node index nl - 1 -> nl' - 1) are rewritten
-    std::vector<u32> cursor(Ltop + 1, 0);
-    std::vector<u32> add(Ltop + 1, 0);
-    for (u32 l = 0; l <= Ltop; l++)
-        for (u32 i = 0; i < m; i++) add[l] += max_level[i] >= l ? 1u : 0u;
+    // ---- 3. every level grows in front of its tail, which on the base graph is ONE node, the root: the new nodes (ascending id) go
+    //         between the old nodes and the root, every slot empty (level_grow_plan.h, grow_tail_kernel — the component's rule with its
+    //         pseudo tail).  What names the root follows it: its vector row n0 -> n1 is a remap; its node index is the SHIFT of every
+    //         index at or above the tail, where the root is the only one — so adj_node and child say what the component's say.
+    std::vector<u32> tails(Ltop + 1), cursor(Ltop + 1);
+    for (u32 l = 0; l <= Ltop; l++) tails[l] = ix->lv[l].n - 1;
+    const std::vector<uint8_t> in_graph(m, 1);
+    const std::vector<level_grow_plan::LevelPlan> plan = level_grow_plan::plan_levels(tails, m, in_graph.data(), max_level.data());
+    GrowValues root_row;
+    root_row.remap_from = n0;
+    root_row.remap_to = n1;
     for (u32 l = 0; l <= Ltop; l++) {
         LevelHost &H = ix->lv[l];
-        const u32 nl0 = H.n, nl1 = nl0 + add[l], M = H.M;
-        cursor[l] = nl0 - 1; // the first new node takes the root's old index
+        const level_grow_plan::LevelPlan &P = plan[l];
+        const u32 nl0 = H.n, tf = P.tail_first, add = P.add, nl1 = nl0 + add, M = H.M;
+        cursor[l] = tf; // the first new node takes the root's old index
         H.node_ids.pop_back();
-        for (u32 i = 0; i < m; i++) if (max_level[i] >= l) H.node_ids.push_back((n0 + i) * ix->id_stride); // internal id of vector row n0 + i
+        for (u32 i : P.who) H.node_ids.push_back((n0 + i) * ix->id_stride); // internal id of vector row n0 + i
         H.node_ids.push_back(COS_ROOT_ID);
         H.host_valid = false;
         H.nbr_ids.clear();
         H.d_adj_mag.reset();
         H.d_adj_up.reset();
         DevArr<u32> adj_vec, adj_node, node_vec, child;
-        DevBuf key, low_idx, low_key;
+        LinkLevels link;
+        std::vector<u32> rows(add); // the new nodes' vector rows (alive until the synchronisation below)
+        for (u32 k = 0; k < add; k++) rows[k] = n0 + P.who[k];
         HIP_TRY(adj_vec.alloc((size_t)nl1 * M));
-        HIP_TRY(launch_grow_rows(H.d_adj_vec, adj_vec, nl0, nl1, M, n0, n1, ROW_EMPTY, st)); // vector rows: the root is row n
+        HIP_TRY(launch_grow_tail(H.d_adj_vec, adj_vec, nl0, tf, add, M, ROW_EMPTY, root_row, st));
         if (l > 0) {
+            GrowValues nodes_here, nodes_below; // what a stored index points into: this level | the level below
+            nodes_here.shift_from = tf; nodes_here.shift_add = add;
+            nodes_below.shift_from = plan[l - 1].tail_first; nodes_below.shift_add = plan[l - 1].add;
             HIP_TRY(adj_node.alloc((size_t)nl1 * M));
-            HIP_TRY(launch_grow_rows(H.d_adj_node, adj_node, nl0, nl1, M, nl0 - 1, nl1 - 1, ROW_EMPTY, st)); // node indices: the root is the last node
-            // node -> vector row and node -> node one level down: old nodes keep theirs, the root's follow it, the new nodes' are known
-            std::vector<u32> nv(add[l] + 1), ch(add[l] + 1);
-            const u32 below0 = ix->lv[l - 1].n - add[l - 1] - 1; // first new node index one level down (level l - 1 has grown already)
-            u32 k = 0, kb = 0;
-            for (u32 i = 0; i < m; i++) {
-                if (max_level[i] >= l) { nv[k] = n0 + i; ch[k] = below0 + kb; k++; }
-                if (max_level[i] >= l - 1) kb++;
-            }
-            nv[k] = n1;                       // the root's vector row
-            ch[k] = ix->lv[l - 1].n - 1;      // ... and its node one level down
             HIP_TRY(node_vec.alloc(nl1));
             HIP_TRY(child.alloc(nl1));
-            HIP_TRY(hipMemcpyAsync(node_vec, H.d_node_vec, (size_t)(nl0 - 1) * 4, hipMemcpyDeviceToDevice, st));
-            HIP_TRY(hipMemcpyAsync(child, H.d_child, (size_t)(nl0 - 1) * 4, hipMemcpyDeviceToDevice, st));
-            HIP_TRY(hipMemcpy(node_vec + (nl0 - 1), nv.data(), nv.size() * 4, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(child + (nl0 - 1), ch.data(), ch.size() * 4, hipMemcpyHostToDevice));
+            HIP_TRY(launch_grow_tail(H.d_adj_node, adj_node, nl0, tf, add, M, ROW_EMPTY, nodes_here, st));
+            HIP_TRY(launch_grow_tail(H.d_node_vec, node_vec, nl0, tf, add, 1, ROW_EMPTY, root_row, st));
+            HIP_TRY(launch_grow_tail(H.d_child, child, nl0, tf, add, 1, ROW_EMPTY, nodes_below, st));
+            if (add) { // node -> vector row and node -> node one level down of the new nodes
+                HIP_TRY(hipMemcpyAsync(node_vec + tf, rows.data(), (size_t)add * 4, hipMemcpyHostToDevice, st));
+                HIP_TRY(hipMemcpyAsync(child + tf, P.child.data(), (size_t)add * 4, hipMemcpyHostToDevice, st));
+            }
         }
-        HIP_TRY(key.alloc((size_t)nl1 * M * 4));
-        HIP_TRY(low_idx.alloc(nl1));
-        HIP_TRY(low_key.alloc((size_t)nl1 * 4));
-        HIP_TRY(launch_grow_rows(ix->link.key[l].as<u32>(), key.as<u32>(), nl0, nl1, M, 0xFFFFFFFFu, 0xFFFFFFFFu, (u32)INT32_MIN, st));
-        HIP_TRY(launch_grow_rows(ix->link.low_key[l].as<u32>(), low_key.as<u32>(), nl0, nl1, 1, 0xFFFFFFFFu, 0xFFFFFFFFu, (u32)order_key(metric, metric_min(metric)), st));
-        HIP_TRY(launch_grow_bytes(ix->link.low_idx[l].as<uint8_t>(), low_idx.as<uint8_t>(), nl0, nl1, st));
-        HIP_TRY(ix->link.owner[l].alloc((size_t)nl1 * 4));
-        HIP_TRY(hipMemsetAsync(ix->link.owner[l].p, 0, (size_t)nl1 * 4, st)); // a new tag epoch (run_batches starts at round 1)
+        rc = ix->link.lv.grow_level(l, nl0, tf, add, M, metric, link, st);
+        if (rc) return rc;
         HIP_TRY(hipStreamSynchronize(st));
         adj_vec.swap(H.d_adj_vec);
         adj_node.swap(H.d_adj_node);
         node_vec.swap(H.d_node_vec);
         child.swap(H.d_child);
-        key.swap(ix->link.key[l]);
-        low_idx.swap(ix->link.low_idx[l]);
-        low_key.swap(ix->link.low_key[l]);
+        ix->link.lv.swap_level(l, link);
         H.n = nl1; // (the locals free the old arrays)
     }
-    // child links INTO a level that grew: level l's root entry was written above; the old nodes' children are old nodes (unchanged)
 
     // ---- 4. the new vectors, batch by batch
-    rc = run_batches(ix, n0, max_level.data(), cursor, Bmax);
+    rc = link_vectors(ix, n0, max_level.data(), cursor, Bmax);
     if (rc) return rc;
     guard.armed = false;
     ix->link.rng = rng;
@@ -597,9 +718,9 @@ struct RowCache { // host copies of the level rows a slow-path delete touches; w
         r.adj.resize(M); r.key.resize(M);
         auto cp = [&](void *dst, const void *src, size_t n) { if (err == hipSuccess) err = hipMemcpy(dst, src, n, hipMemcpyDeviceToHost); };
         cp(r.adj.data(), (level == 0 ? H.d_adj_vec : H.d_adj_node) + (size_t)node * M, (size_t)M * 4);
-        cp(r.key.data(), ix->link.key[level].as<int32_t>() + (size_t)node * M, (size_t)M * 4);
-        cp(&r.low_idx, ix->link.low_idx[level].as<uint8_t>() + node, 1);
-        cp(&r.low_key, ix->link.low_key[level].as<int32_t>() + node, 4);
+        cp(r.key.data(), ix->link.lv.key[level].as<int32_t>() + (size_t)node * M, (size_t)M * 4);
+        cp(&r.low_idx, ix->link.lv.low_idx[level].as<uint8_t>() + node, 1);
+        cp(&r.low_key, ix->link.lv.low_key[level].as<int32_t>() + node, 4);
         return r;
     }
     hipError_t flush(const std::vector<u32> &node_vec /* node -> vector row (level 0: identity) */) {
@@ -616,9 +737,9 @@ struct RowCache { // host copies of the level rows a slow-path delete touches; w
                 cp(H.d_adj_node + (size_t)node * M, r.adj.data(), (size_t)M * 4);
                 cp(H.d_adj_vec + (size_t)node * M, av.data(), (size_t)M * 4);
             }
-            cp(ix->link.key[level].as<int32_t>() + (size_t)node * M, r.key.data(), (size_t)M * 4);
-            cp(ix->link.low_idx[level].as<uint8_t>() + node, &r.low_idx, 1);
-            cp(ix->link.low_key[level].as<int32_t>() + node, &r.low_key, 4);
+            cp(ix->link.lv.key[level].as<int32_t>() + (size_t)node * M, r.key.data(), (size_t)M * 4);
+            cp(ix->link.lv.low_idx[level].as<uint8_t>() + node, &r.low_idx, 1);
+            cp(ix->link.lv.low_key[level].as<int32_t>() + node, &r.low_key, 4);
         }
         return err;
     }
@@ -669,7 +790,7 @@ extern "C" int32_t cos_index_delete(cos_index *ix, const uint32_t *ids, uint32_t
     LinkArgs la;
     memset(&la, 0, sizeof(la));
     u32 maxM = 0;
-    fill_link_levels(ix, la, maxM);
+    fill_link_levels(ix->lv, ix->link.lv, la, maxM);
     la.L1 = L1;
     la.metric = metric;
     const int32_t kmin = order_key(metric, metric_min(metric)), kmax = order_key(metric, metric_max(metric));
@@ -823,7 +944,6 @@ extern "C" int32_t cos_index_delete(cos_index *ix, const uint32_t *ids, uint32_t
 extern "C" int32_t cos_index_build_meta(cos_index *ix, uint32_t n_nodes, const uint32_t *node_ids, const int32_t *mbits, const uint8_t *max_levels,
                                         uint32_t batch_size) {
     if (!ix || !node_ids || !mbits || !max_levels || n_nodes == 0) return cos_fail(COS_ERR_INVALID, "null/empty node table");
-    constexpr u32 PSEUDO_LO = META_PSEUDO_LO;
     u32 vmode;
     { std::lock_guard<std::mutex> g(ix->mu); vmode = ix->p.visited_mode; }
     if (vmode != COS_VISITED_REF) return cos_fail(COS_ERR_UNIMPLEMENTED, "the metadata component is built and searched with the reference's PerformantFixedSet filter only");
@@ -832,9 +952,7 @@ extern "C" int32_t cos_index_build_meta(cos_index *ix, uint32_t n_nodes, const u
     rc = cos_set_device(ix);
     if (rc) return rc;
     const u32 n = ix->n, Ltop = ix->p.num_layers, L1 = Ltop + 1, metric = ix->p.metric, md = ix->meta.mdim;
-    // default batch 1024 (the base graph's: 4096): every Metadata replica links to the same few pseudo nodes, the rounds of a batch run ~1.4
-    // nodes each whatever its size, and a round costs what its PENDING list costs — 600 k nodes: 27 s at 4096, 16.4 s at 1024 or 256
-    const u32 Bmax = std::min<u32>(batch_size ? batch_size : 1024u, LINK_MAX_BATCH);
+    const u32 Bmax = batch_max(batch_size, COMPONENT_DEFAULT_BATCH);
     hipStream_t st = ix->own_stream;
     const std::vector<u32> &tab = ix->meta.node_ids;
     if (!std::binary_search(tab.begin(), tab.end(), PSEUDO_LO)) return cos_fail(COS_ERR_INVALID, "the node table has no pseudo root (u32::MAX - 257)");
@@ -854,8 +972,7 @@ extern "C" int32_t cos_index_build_meta(cos_index *ix, uint32_t n_nodes, const u
     MetaGuard guard{ix}; // a failed build leaves the handle without the component (filtered search: NotReady)
 
     // ---- level skeletons: the root + every node whose level reaches l, ascending id; every slot empty; the link state beside them ------
-    MetaLinkState &ls = ix->meta.link; // (released with the old levels by cos_index_upload_meta_nodes)
-    ix->meta.lv.resize(L1);
+    ix->meta.lv.resize(L1); // (the link state was released with the old levels by cos_index_upload_meta_nodes)
     for (u32 l = 0; l <= Ltop; l++) {
         LevelHost &H = ix->meta.lv[l];
         H.M = l == 0 ? ix->p.level0_neighbors_count : ix->p.neighbors_count;
@@ -892,183 +1009,30 @@ extern "C" int32_t cos_index_build_meta(cos_index *ix, uint32_t n_nodes, const u
         if (l > 0) HIP_TRY(up(H.d_child, child));
         H.n = nl;
         H.host_valid = false;
-        HIP_TRY(ls.key[l].alloc((size_t)nl * M * 4));
-        HIP_TRY(ls.low_idx[l].alloc(nl));
-        HIP_TRY(ls.low_key[l].alloc((size_t)nl * 4));
-        HIP_TRY(ls.owner[l].alloc((size_t)nl * 4));
-        HIP_TRY(ls.kind[l].alloc(nl));
-        HIP_TRY(launch_fill_i32(ls.key[l].as<int32_t>(), (u64)nl * M, INT32_MIN, st));
-        HIP_TRY(hipMemsetAsync(ls.low_idx[l].p, 0, nl, st));
-        HIP_TRY(launch_fill_i32(ls.low_key[l].as<int32_t>(), nl, order_key(metric, metric_min(metric)), st));
-        HIP_TRY(hipMemsetAsync(ls.owner[l].p, 0, (size_t)nl * 4, st));
-        HIP_TRY(hipMemcpy(ls.kind[l].p, kd.data(), nl, hipMemcpyHostToDevice));
+        rc = ix->meta.link.lv.init_level(l, nl, M, metric, kd.data(), st);
+        if (rc) return rc;
     }
     HIP_TRY(hipStreamSynchronize(st));
 
-    rc = meta_run_batches(ix, node_ids, mbits, mmag.data(), max_levels, ord, Bmax);
+    rc = link_component_nodes(ix, node_ids, mbits, mmag.data(), max_levels, ord, Bmax);
     if (rc) return rc;
-    ls.valid = true; // kept for cos_index_append_meta until cos_index_release_link_state
+    ix->meta.link.valid = true; // kept for cos_index_append_meta until cos_index_release_link_state
     guard.armed = false;
     return COS_OK;
 }
 
-namespace {
-
-// The batch loop of cos_index_build_meta and cos_index_append_meta: the nodes ord[0], ord[1], ... (positions in the caller's node_ids /
-// mbits / mmag / max_levels) are inserted by the schedule CONTINUED at ix->meta.link.inserted — batches of min(Bmax, max(1, inserted / 4))
-// walk the snapshot that precedes them, then the link rounds run on the handle's link state.  The levels already hold every node of
-// `ord` (all slots empty, claim tags zero: a new tag epoch).
-int32_t meta_run_batches(cos_index *ix, const u32 *node_ids, const int32_t *mbits, const float *mmag, const uint8_t *max_levels, const std::vector<u32> &ord, u32 Bmax) {
-    const u32 n = ix->n, Ltop = ix->p.num_layers, L1 = Ltop + 1, metric = ix->p.metric, md = ix->meta.mdim;
-    hipStream_t st = ix->own_stream;
-    MetaLinkState &ls = ix->meta.link;
-    LinkArgs la;
-    memset(&la, 0, sizeof(la));
-    u32 maxM = 0;
-    for (u32 l = 0; l <= Ltop; l++) {
-        LevelHost &H = ix->meta.lv[l];
-        LinkLevelDev &D = la.lv[l];
-        D.adj_vec = H.d_adj_vec;
-        D.adj_node = H.d_adj_node;
-        D.node_vec = H.d_node_vec;
-        D.key = ls.key[l].as<int32_t>();
-        D.low_idx = ls.low_idx[l].as<uint8_t>();
-        D.low_key = ls.low_key[l].as<int32_t>();
-        D.owner = ls.owner[l].as<u32>();
-        D.kind = ls.kind[l].as<uint8_t>();
-        D.M = H.M;
-        maxM = std::max(maxM, H.M);
-    }
-    if (maxM > 256) return cos_fail(COS_ERR_UNIMPLEMENTED, "more than 256 neighbour slots per node");
-    const u32 first = ls.inserted, total = first + (u32)ord.size();
-
-    const u32 KEEP = (u32)KEEP_INDEX;
-    DevBuf d_rows, d_self, d_foff, d_fdims, d_fmags, d_qc, d_qm, d_out_ids, d_out_nodes, d_out_sims, d_out_counts, d_status, d_me, d_pend[2], d_cnt, d_evq;
-    const size_t pend_cap = (size_t)Bmax * L1, evq_cap = pend_cap * 2 * KEEP;
-    HIP_TRY(d_rows.alloc((size_t)Bmax * 4));
-    HIP_TRY(d_self.alloc((size_t)Bmax * 4));
-    HIP_TRY(d_foff.alloc(((size_t)Bmax + 1) * 4));
-    HIP_TRY(d_fdims.alloc((size_t)Bmax * md * 4));
-    HIP_TRY(d_fmags.alloc((size_t)Bmax * 4));
-    HIP_TRY(d_out_ids.alloc((size_t)Bmax * L1 * KEEP * 4));
-    HIP_TRY(d_out_nodes.alloc((size_t)Bmax * L1 * KEEP * 4));
-    HIP_TRY(d_out_sims.alloc((size_t)Bmax * L1 * KEEP * 4));
-    HIP_TRY(d_out_counts.alloc((size_t)Bmax * L1 * 4));
-    HIP_TRY(d_status.alloc((size_t)Bmax * 4));
-    HIP_TRY(d_me.alloc((size_t)Bmax * L1 * 4));
-    HIP_TRY(d_pend[0].alloc(pend_cap * 4));
-    HIP_TRY(d_pend[1].alloc(pend_cap * 4));
-    HIP_TRY(d_cnt.alloc(4 * 4));
-    HIP_TRY(d_evq.alloc(evq_cap * 3 * 4));
-    std::vector<u32> h_rows(Bmax), h_self(Bmax), h_foff(Bmax + 1), h_me((size_t)Bmax * L1), h_pend(pend_cap);
-    std::vector<int32_t> h_fdims((size_t)Bmax * md), h_status(Bmax);
-    std::vector<float> h_fmags(Bmax);
-    u32 h_cnt[4];
-
-    la.L1 = L1;
-    la.z_nodes = d_out_nodes.as<u32>();
-    la.z_sims = d_out_sims.as<float>();
-    la.z_counts = d_out_counts.as<u32>();
-    la.me = d_me.as<u32>();
-    la.metric = metric;
-    la.kmin = order_key(metric, metric_min(metric));
-    la.kmax = order_key(metric, metric_max(metric));
-
-    IndexDev dev = cos_make_meta_dev(ix);
-    dev.visited_mode = COS_VISITED_REF;
-    u32 inserted = first, round = 0;
-    u32 *cnt = d_cnt.as<u32>();
-    while (inserted < total) {
-        const u32 bs = std::min({Bmax, std::max(1u, inserted / 4u), total - inserted});
-        u32 np = 0;
-        for (u32 b = 0; b < bs; b++) {
-            const u32 t = ord[inserted - first + b], id = node_ids[t];
-            h_rows[b] = is_pseudo(id) ? n + 1 : id / ix->id_stride;
-            h_self[b] = id;
-            h_foff[b] = b;
-            for (u32 j = 0; j < md; j++) h_fdims[(size_t)b * md + j] = mbits[(size_t)t * md + j];
-            h_fmags[b] = mmag[t];
-            for (u32 l = 0; l <= Ltop; l++) {
-                u32 m = NONE;
-                if (max_levels[t] >= l) {
-                    const std::vector<u32> &ids = ix->meta.lv[l].node_ids;
-                    m = (u32)(std::lower_bound(ids.begin(), ids.end(), id) - ids.begin());
-                    h_pend[np++] = (l << 16) | b;
-                }
-                h_me[(size_t)b * L1 + l] = m;
-            }
-        }
-        h_foff[bs] = bs;
-        HIP_TRY(hipMemcpyAsync(d_rows.p, h_rows.data(), (size_t)bs * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_self.p, h_self.data(), (size_t)bs * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_foff.p, h_foff.data(), ((size_t)bs + 1) * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_fdims.p, h_fdims.data(), (size_t)bs * md * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_fmags.p, h_fmags.data(), (size_t)bs * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_me.p, h_me.data(), (size_t)bs * L1 * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_pend[0].p, h_pend.data(), (size_t)np * 4, hipMemcpyHostToDevice, st));
-        h_cnt[0] = np; h_cnt[1] = 0; h_cnt[2] = 0; h_cnt[3] = 0;
-        HIP_TRY(hipMemcpyAsync(cnt, h_cnt, 16, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipStreamSynchronize(st)); // the staging vectors are pageable and rewritten by the next batch
-        WalkArgs wa;
-        memset(&wa, 0, sizeof(wa));
-        wa.qcodes = ix->d_codes;
-        wa.qmags = ix->d_mags;
-        wa.q_rows = d_rows.as<u32>();
-        wa.self_ids = d_self.as<u32>();
-        wa.B = bs;
-        wa.ef = ix->p.ef_construction;
-        wa.keep = KEEP;
-        wa.out_ids = d_out_ids.as<u32>();
-        wa.out_sims = d_out_sims.as<float>();
-        wa.out_nodes = d_out_nodes.as<u32>();
-        wa.out_counts = d_out_counts.as<u32>();
-        wa.out_status = d_status.as<int32_t>();
-        wa.f_dims = d_fdims.as<int32_t>();
-        wa.f_mags = d_fmags.as<float>();
-        wa.f_off = d_foff.as<u32>();
-        HIP_TRY(launch_walk_meta_index(ix->eng, dev, wa, st));
-        HIP_TRY(hipMemcpyAsync(h_status.data(), d_status.p, (size_t)bs * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        for (u32 b = 0; b < bs; b++)
-            if (h_status[b] != COS_OK)
-                return cos_fail(h_status[b], "node %u of the metadata component cannot be indexed (status %d)", node_ids[ord[inserted - first + b]], h_status[b]);
-        u32 pending_ub = np, cur = 0;
-        while (pending_ub > 0) {
-            const u32 chunk = pending_ub > 64 ? 2 : 4;
-            for (u32 r = 0; r < chunk; r++) {
-                if (++round > LINK_MAX_ROUND) {
-                    for (u32 l = 0; l <= Ltop; l++) HIP_TRY(hipMemsetAsync(ls.owner[l].p, 0, (size_t)ix->meta.lv[l].n * 4, st));
-                    round = 1;
-                }
-                HIP_TRY(launch_link_round(la, maxM, d_pend[cur].as<u32>(), cnt + cur, d_pend[cur ^ 1].as<u32>(), cnt + (cur ^ 1), d_evq.as<u32>(), cnt + 2,
-                                          pending_ub, round, st));
-                cur ^= 1;
-            }
-            HIP_TRY(hipMemcpyAsync(h_cnt, cnt, 16, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            pending_ub = h_cnt[cur];
-        }
-        inserted += bs;
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    ls.inserted = total;
-    return COS_OK;
-}
-
-} // namespace
-
 // index_embeddings on a LIVE collection with a metadata schema, the component's half (vector_store.rs:484-640; the embeddings themselves:
 // cos_index_append).  The new replicas' ids lie above every resident replica's and below the pseudo range, so on every level — and in the
 // node table — they go between the old replicas and the pseudo nodes: every array grows in front of its tail (grow_tail_kernel), the
-// indices that point into a tail follow it (meta_grow_plan.h), and the schedule of cos_index_build_meta continues at the number of nodes
+// indices that point into a tail follow it (level_grow_plan.h), and the schedule of cos_index_build_meta continues at the number of nodes
 // it has inserted.  oracle/cosdata_oracle_hnsw.c: coso_meta_build_rounds over the WHOLE table is the CPU statement when the earlier calls
 // ended on one of its batch boundaries; tests/test_gpu_meta_append.py asserts identical graphs.
 extern "C" int32_t cos_index_append_meta(cos_index *ix, uint32_t n_new, const uint32_t *node_ids, const int32_t *mbits, const uint8_t *max_levels,
                                          uint32_t batch_size) {
     if (!ix || !node_ids || !mbits || !max_levels || n_new == 0) return cos_fail(COS_ERR_INVALID, "null/empty node list");
     const u32 Ltop = ix->p.num_layers, L1 = Ltop + 1, metric = ix->p.metric, md = ix->meta.mdim;
-    MetaLinkState &ls = ix->meta.link;
-    bool resident = md != 0u && ix->have_vectors && ix->meta.lv.size() == L1 && ls.valid;
+    LinkLevels &ls = ix->meta.link.lv;
+    bool resident = md != 0u && ix->have_vectors && ix->meta.lv.size() == L1 && ix->meta.link.valid;
     for (u32 l = 0; resident && l <= Ltop; l++) resident = ix->meta.lv[l].n != 0 && ls.key[l].p != nullptr;
     if (!resident)
         return cos_fail(COS_ERR_NOT_READY, "no component to continue: cos_index_build_meta has not built one on this handle (an uploaded component has no "
@@ -1077,7 +1041,7 @@ extern "C" int32_t cos_index_append_meta(cos_index *ix, uint32_t n_new, const ui
     { std::lock_guard<std::mutex> g(ix->mu); vmode = ix->p.visited_mode; }
     if (vmode != COS_VISITED_REF) return cos_fail(COS_ERR_INVALID, "the metadata component is built and searched with the reference's PerformantFixedSet filter only");
     std::vector<u32> &tab = ix->meta.node_ids;
-    const u32 n_tab = (u32)tab.size(), tab_tail = meta_grow_plan::tail_first(tab.data(), n_tab);
+    const u32 n_tab = (u32)tab.size(), tab_tail = level_grow_plan::tail_first(tab.data(), n_tab);
     if ((u64)n_tab + n_new >= 0xFFFFFFF0ull) return cos_fail(COS_ERR_INVALID, "too many nodes");
     for (u32 i = 0; i < n_new; i++) {
         const u32 id = node_ids[i];
@@ -1089,7 +1053,7 @@ extern "C" int32_t cos_index_append_meta(cos_index *ix, uint32_t n_new, const ui
     }
     int32_t rc = cos_set_device(ix);
     if (rc) return rc;
-    const u32 Bmax = std::min<u32>(batch_size ? batch_size : 1024u, LINK_MAX_BATCH);
+    const u32 Bmax = batch_max(batch_size, COMPONENT_DEFAULT_BATCH);
     hipStream_t st = ix->own_stream;
     HIP_TRY(hipDeviceSynchronize()); // exclusive: whatever read the old arrays is done
 
@@ -1098,15 +1062,15 @@ extern "C" int32_t cos_index_append_meta(cos_index *ix, uint32_t n_new, const ui
     meta_row_kinds(n_new, node_ids, mbits, md, mmag, kind); // (no pseudo id among them: 0 Base or 2 Metadata)
     std::vector<u32> tails(L1);
     for (u32 l = 0; l <= Ltop; l++) tails[l] = ix->meta.lv[l].root_idx; // the pseudo root is the first pseudo node of every level
-    const std::vector<meta_grow_plan::LevelPlan> plan = meta_grow_plan::plan_levels(tails, n_new, kind.data(), max_levels);
+    const std::vector<level_grow_plan::LevelPlan> plan = level_grow_plan::plan_levels(tails, n_new, kind.data(), max_levels);
 
     // ---- 1. every array grows into a local; nothing of the handle changes before all of them are written ---------------------------
     struct Grown {
         DevArr<u32> adj_vec, adj_node, node_vec, node_id, node_meta, child;
-        DevBuf key, low_idx, low_key, owner, kind;
         std::vector<u32> h_vec, h_id, h_meta; // the new nodes' entries (alive until the copies below have run)
     };
     std::vector<Grown> grown(L1);
+    LinkLevels grown_link;
     DevArr<int32_t> new_mbits;
     DevArr<float> new_mmags;
     const GrowValues as_is;
@@ -1114,7 +1078,7 @@ extern "C" int32_t cos_index_append_meta(cos_index *ix, uint32_t n_new, const ui
     for (u32 l = 0; l <= Ltop; l++) {
         LevelHost &H = ix->meta.lv[l];
         Grown &G = grown[l];
-        const meta_grow_plan::LevelPlan &P = plan[l];
+        const level_grow_plan::LevelPlan &P = plan[l];
         const u32 nl0 = H.n, tf = P.tail_first, add = P.add, nl1 = nl0 + add, M = H.M;
         GrowValues nodes_here, table_rows, nodes_below; // what a stored index points into: this level | the node table | the level below
         nodes_here.shift_from = tf; nodes_here.shift_add = add;
@@ -1125,21 +1089,13 @@ extern "C" int32_t cos_index_append_meta(cos_index *ix, uint32_t n_new, const ui
         HIP_TRY(G.node_vec.alloc(nl1));
         HIP_TRY(G.node_id.alloc(nl1));
         HIP_TRY(G.node_meta.alloc(nl1));
-        HIP_TRY(G.key.alloc((size_t)nl1 * M * 4));
-        HIP_TRY(G.low_idx.alloc(nl1));
-        HIP_TRY(G.low_key.alloc((size_t)nl1 * 4));
-        HIP_TRY(G.owner.alloc((size_t)nl1 * 4));
-        HIP_TRY(G.kind.alloc(nl1));
         HIP_TRY(launch_grow_tail(H.d_adj_vec, G.adj_vec, nl0, tf, add, M, ROW_EMPTY, as_is, st));
         HIP_TRY(launch_grow_tail(H.d_adj_node, G.adj_node, nl0, tf, add, M, ROW_EMPTY, nodes_here, st));
         HIP_TRY(launch_grow_tail(H.d_node_vec, G.node_vec, nl0, tf, add, 1, ROW_EMPTY, as_is, st));
         HIP_TRY(launch_grow_tail(H.d_node_id, G.node_id, nl0, tf, add, 1, ROW_EMPTY, as_is, st));
         HIP_TRY(launch_grow_tail(H.d_node_meta, G.node_meta, nl0, tf, add, 1, ROW_EMPTY, table_rows, st));
-        HIP_TRY(launch_grow_tail(ls.key[l].as<u32>(), G.key.as<u32>(), nl0, tf, add, M, (u32)INT32_MIN, as_is, st));
-        HIP_TRY(launch_grow_tail(ls.low_key[l].as<u32>(), G.low_key.as<u32>(), nl0, tf, add, 1, (u32)order_key(metric, metric_min(metric)), as_is, st));
-        HIP_TRY(launch_grow_tail_bytes(ls.low_idx[l].as<uint8_t>(), G.low_idx.as<uint8_t>(), nl0, tf, add, 0, st));
-        HIP_TRY(launch_grow_tail_bytes(ls.kind[l].as<uint8_t>(), G.kind.as<uint8_t>(), nl0, tf, add, 2, st)); // every new node is a Metadata replica
-        HIP_TRY(hipMemsetAsync(G.owner.p, 0, (size_t)nl1 * 4, st)); // a new tag epoch (meta_run_batches starts at round 1)
+        rc = ls.grow_level(l, nl0, tf, add, M, metric, grown_link, st);
+        if (rc) return rc;
         for (u32 k = 0; k < add; k++) {
             const u32 i = P.who[k];
             G.h_vec.push_back(node_ids[i] / ix->id_stride);
@@ -1168,21 +1124,17 @@ extern "C" int32_t cos_index_append_meta(cos_index *ix, uint32_t n_new, const ui
     for (u32 l = 0; l <= Ltop; l++) {
         LevelHost &H = ix->meta.lv[l];
         Grown &G = grown[l];
-        const meta_grow_plan::LevelPlan &P = plan[l];
+        const level_grow_plan::LevelPlan &P = plan[l];
         G.adj_vec.swap(H.d_adj_vec);
         G.adj_node.swap(H.d_adj_node);
         G.node_vec.swap(H.d_node_vec);
         G.node_id.swap(H.d_node_id);
         G.node_meta.swap(H.d_node_meta);
         if (l > 0) G.child.swap(H.d_child);
-        G.key.swap(ls.key[l]);
-        G.low_idx.swap(ls.low_idx[l]);
-        G.low_key.swap(ls.low_key[l]);
-        G.owner.swap(ls.owner[l]);
-        G.kind.swap(ls.kind[l]);
+        ls.swap_level(l, grown_link);
         H.node_ids.insert(H.node_ids.begin() + P.tail_first, G.h_id.begin(), G.h_id.end());
         H.n += P.add;
-        H.root_idx = meta_grow_plan::remap_index(H.root_idx, P.tail_first, P.add);
+        H.root_idx = level_grow_plan::remap_index(H.root_idx, P.tail_first, P.add);
         H.host_valid = false;
         H.nbr_ids.clear();
     }
@@ -1190,13 +1142,14 @@ extern "C" int32_t cos_index_append_meta(cos_index *ix, uint32_t n_new, const ui
     new_mmags.swap(ix->meta.d_mmags);
     tab.insert(tab.begin() + tab_tail, node_ids, node_ids + n_new);
     grown.clear(); // (frees the old arrays)
+    grown_link.release();
     new_mbits.reset();
     new_mmags.reset();
 
     // ---- 3. the new Metadata replicas, batch by batch ------------------------------------------------------------------------------
     std::vector<u32> ord;
     for (u32 i = 0; i < n_new; i++) if (kind[i] != 0) ord.push_back(i);
-    rc = meta_run_batches(ix, node_ids, mbits, mmag.data(), max_levels, ord, Bmax);
+    rc = link_component_nodes(ix, node_ids, mbits, mmag.data(), max_levels, ord, Bmax);
     if (rc) return rc;
     guard.armed = false;
     return COS_OK;

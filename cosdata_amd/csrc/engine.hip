@@ -1853,8 +1853,6 @@ extern "C" int32_t cos_index_timing_summary(cos_index *ix, void *stream, cos_tim
 // ------------------------------------------------------------------------------------------------
 // metadata-filtered search: the pseudo-root component and cos_search_filtered_batch
 // ------------------------------------------------------------------------------------------------
-static constexpr u32 PSEUDO_LO = 0xFFFFFEFEu, PSEUDO_HI = 0xFFFFFFFDu; // u32::MAX - 257 (pseudo_root_id, metadata/mod.rs:217) ..= u32::MAX - 2
-
 extern "C" int32_t cos_index_enable_metadata(cos_index *ix, uint32_t mdim, uint32_t max_replicas_per_node) {
     if (!ix || mdim == 0 || mdim > 64 || max_replicas_per_node == 0) return cos_fail(COS_ERR_INVALID, "metadata dimensions must be in [1, 64] and max_replicas_per_node >= 1");
     if (!ix->have_vectors) return cos_fail(COS_ERR_NOT_READY, "upload vectors before enabling the metadata component");
@@ -1895,7 +1893,7 @@ extern "C" int32_t cos_index_upload_meta_nodes(cos_index *ix, uint32_t n_nodes, 
     const u32 md = ix->meta.mdim;
     for (u32 i = 0; i < n_nodes; i++) {
         if (i && node_ids[i] <= node_ids[i - 1]) return cos_fail(COS_ERR_INVALID, "node ids must be strictly ascending");
-        const bool pseudo = node_ids[i] >= PSEUDO_LO && node_ids[i] <= PSEUDO_HI;
+        const bool pseudo = is_pseudo(node_ids[i]);
         if (!pseudo && node_ids[i] / ix->id_stride >= ix->n) return cos_fail(COS_ERR_INVALID, "replica id %u has no resident vector", node_ids[i]);
     }
     std::vector<float> mags(n_nodes);
@@ -1932,7 +1930,7 @@ extern "C" int32_t cos_index_upload_meta_graph_level(cos_index *ix, uint32_t lev
         auto it = std::lower_bound(tab.begin(), tab.end(), node_ids[i]);
         if (it == tab.end() || *it != node_ids[i]) return cos_fail(COS_ERR_INVALID, "level %u: node %u is not in the node table", level, node_ids[i]);
         node_meta[i] = (u32)(it - tab.begin());
-        const bool pseudo = node_ids[i] >= PSEUDO_LO && node_ids[i] <= PSEUDO_HI;
+        const bool pseudo = is_pseudo(node_ids[i]);
         if (!pseudo && node_ids[i] / ix->id_stride >= n) return cos_fail(COS_ERR_INVALID, "level %u: replica id %u has no resident vector", level, node_ids[i]);
         node_vec[i] = pseudo ? n + 1 : node_ids[i] / ix->id_stride;
         if (node_ids[i] == PSEUDO_LO) root_idx = i;

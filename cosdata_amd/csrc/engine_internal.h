@@ -26,10 +26,9 @@ hipError_t launch_low_cache(const u32 *adj_vec, const int32_t *key, u32 n, u32 M
 hipError_t launch_unlink(const LinkArgs &a, const u32 *dn, u32 *status, hipStream_t st);
 hipError_t launch_index_pair_distances(int eng, const uint8_t *codes, const float *mags, u64 row_stride, u32 nchunks, u32 dim, u32 metric, const u32 *d_pair_x,
                                        const u32 *d_pair_y, u32 n_pairs, float *d_out, int32_t *d_status, hipStream_t st); // kernels_misc.hip
-hipError_t launch_grow_rows(const u32 *src, u32 *dst, u32 old_n, u32 new_n, u32 M, u32 remap_from, u32 remap_to, u32 fill, hipStream_t st);
-hipError_t launch_grow_bytes(const uint8_t *src, uint8_t *dst, u32 old_n, u32 new_n, hipStream_t st);
-// the pseudo-root component's growth (cos_index_append_meta): rows [tail_first, old_n) move up by `add`, the rows between are `fill`;
-// of the copied values, remap_from becomes remap_to, any other at or above shift_from (the empty slot excepted) gains shift_add
+// a level's growth (cos_index_append: the tail is the root; cos_index_append_meta: the pseudo nodes): rows [tail_first, old_n) move up by
+// `add`, the rows between are `fill`; of the copied values, remap_from becomes remap_to, any other at or above shift_from (the empty slot
+// excepted) gains shift_add
 hipError_t launch_grow_tail(const u32 *src, u32 *dst, u32 old_n, u32 tail_first, u32 add, u32 M, u32 fill, const GrowValues &v, hipStream_t st);
 hipError_t launch_grow_tail_bytes(const uint8_t *src, uint8_t *dst, u32 old_n, u32 tail_first, u32 add, uint8_t fill, hipStream_t st);
 hipError_t launch_fill_adj_mag(const u32 *adj_vec, const float *mags, float *adj_mag, u32 n, u32 M, u32 slots, hipStream_t st);
@@ -116,19 +115,36 @@ struct LevelHost {
     }
 };
 
-// What cos_index_build leaves behind so that cos_index_append can CONTINUE it (builder.hip): the link state of every level — the
-// similarity key of every neighbour slot and every node's cached (lowest index, lowest similarity), prob_node.rs:108, which is
-// history (remove_neighbor_by_id does not refresh it) and cannot be recomputed from the graph —, the RNG stream after the last level
-// draw, and how many vectors the graph holds.  As large as the adjacency itself; cos_index_release_link_state frees it.
+// The link state of a graph's levels, base graph and pseudo-root component alike (builder.hip): the similarity key of every neighbour
+// slot and every node's cached (lowest index, lowest similarity), prob_node.rs:108, which is history (remove_neighbor_by_id does not
+// refresh it) and cannot be recomputed from the graph; the claim tags of the link rounds; and, for the component only, every node's
+// ReplicaNodeKind (LinkLevelDev::kind; empty on the base graph).  4 bytes per neighbour slot and 9 (10) bytes per node of a level.
+struct LinkLevels {
+    DevBuf key[cosdev::MAX_LEVELS], low_idx[cosdev::MAX_LEVELS], low_key[cosdev::MAX_LEVELS], owner[cosdev::MAX_LEVELS], kind[cosdev::MAX_LEVELS];
+    void release() {
+        for (int l = 0; l < cosdev::MAX_LEVELS; l++) { key[l].reset(); low_idx[l].reset(); low_key[l].reset(); owner[l].reset(); kind[l].reset(); }
+    }
+    // level l for nl nodes of M slots, contents undefined (cos_index_restore_link_state computes them); no `kind`
+    int32_t alloc_level(u32 l, u32 nl, u32 M);
+    // ... allocated and filled for a level without edges: every slot empty (INT32_MIN), cached lowest = (0, MetricResult::min)
+    // (prob_node.rs:140), claim tags 0; kinds [nl] (host) = the nodes' kinds, nullptr = none (base graph)
+    int32_t init_level(u32 l, u32 nl, u32 M, u32 metric, const uint8_t *kinds, hipStream_t st);
+    // out's level l = this level of old_n nodes grown in front of its tail: the nodes [tail_first, old_n) move up by `add`, the `add` new ones
+    // between are filled as init_level fills them (kind: 2, a Metadata replica); the claim tags are zeroed for a new tag epoch.  Fresh
+    // buffers: this level is only read.
+    int32_t grow_level(u32 l, u32 old_n, u32 tail_first, u32 add, u32 M, u32 metric, LinkLevels &out, hipStream_t st) const;
+    void swap_level(u32 l, LinkLevels &o) { key[l].swap(o.key[l]); low_idx[l].swap(o.low_idx[l]); low_key[l].swap(o.low_key[l]); owner[l].swap(o.owner[l]); kind[l].swap(o.kind[l]); }
+};
+
+// What cos_index_build leaves behind so that cos_index_append can CONTINUE it (builder.hip): the link state of every level, the RNG
+// stream after the last level draw, and how many vectors the graph holds.  As large as the adjacency itself;
+// cos_index_release_link_state frees it.
 struct LinkState {
-    DevBuf key[cosdev::MAX_LEVELS], low_idx[cosdev::MAX_LEVELS], low_key[cosdev::MAX_LEVELS], owner[cosdev::MAX_LEVELS];
+    LinkLevels lv;
     uint64_t rng = 0;
     u32 n_built = 0;
     bool valid = false;
-    void release() {
-        for (int l = 0; l < cosdev::MAX_LEVELS; l++) { key[l].reset(); low_idx[l].reset(); low_key[l].reset(); owner[l].reset(); }
-        valid = false;
-    }
+    void release() { lv.release(); valid = false; }
 };
 
 // EXACT-mode visited filters of one stream (WalkArgs::vis_bits / vis_log).  The bitset is zeroed once, when it is
@@ -194,27 +210,21 @@ struct Workspace {
 
 // The pseudo-root component of a collection with a metadata schema: pseudo nodes + Metadata replicas, a graph of
 // its own next to the base graph.  Node table = level 0 of the component, ascending replica id.
-// What cos_index_build_meta leaves behind so that cos_index_append_meta can CONTINUE it: LinkState's arrays for the component's levels,
-// every node's ReplicaNodeKind (LinkLevelDev::kind) and how many nodes the schedule has inserted.  4 bytes per neighbour slot and 10
-// bytes per node of a level; freed by cos_index_release_link_state and with the levels (an uploaded component has none).
-struct MetaLinkState {
-    DevBuf key[cosdev::MAX_LEVELS], low_idx[cosdev::MAX_LEVELS], low_key[cosdev::MAX_LEVELS], owner[cosdev::MAX_LEVELS], kind[cosdev::MAX_LEVELS];
-    u32 inserted = 0; // nodes inserted so far: pseudo nodes without the pseudo root + Metadata replicas
-    bool valid = false;
-    void release() {
-        for (int l = 0; l < cosdev::MAX_LEVELS; l++) { key[l].reset(); low_idx[l].reset(); low_key[l].reset(); owner[l].reset(); kind[l].reset(); }
-        inserted = 0;
-        valid = false;
-    }
-};
-
 struct MetaGraph {
     u32 mdim = 0;                 // metadata dimensions per node (0 = the index has no metadata schema)
     std::vector<u32> node_ids;    // [n_meta] ascending
     DevArr<int32_t> d_mbits;      // [n_meta][mdim]
     DevArr<float> d_mmags;        // [n_meta]
     std::vector<LevelHost> lv;    // [num_layers + 1]
-    MetaLinkState link;           // cos_index_build_meta -> cos_index_append_meta (builder.hip); dropped with the levels
+    // What cos_index_build_meta leaves behind so that cos_index_append_meta can CONTINUE it (builder.hip): the link state of the component's
+    // levels and how many nodes the schedule has inserted.  Freed by cos_index_release_link_state and with the levels (an uploaded
+    // component has none).
+    struct Link {
+        LinkLevels lv;
+        u32 inserted = 0; // nodes inserted so far: pseudo nodes without the pseudo root + Metadata replicas
+        bool valid = false;
+        void release() { lv.release(); inserted = 0; valid = false; }
+    } link;
 };
 
 // Device-side resources of ONE host-API call in flight (cos_search_batch, cos_ann_search_batch, cos_search_filtered_batch):

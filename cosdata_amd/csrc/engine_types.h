@@ -136,4 +136,9 @@ struct WalkArgs {
 constexpr u32 WALK_FAST_MAX_EF = 1024u;
 constexpr u32 WALK_GENERAL_MAX_EF = 16384u;
 
+// The reserved ids of a metadata collection's pseudo nodes: the pseudo root u32::MAX - 257 (pseudo_root_id, metadata/mod.rs:217)
+// ..= u32::MAX - 2 (types.rs:229).  level_grow_plan.h, which includes nothing of the library, keeps the lower bound under its own name.
+constexpr u32 PSEUDO_LO = 0xFFFFFEFEu, PSEUDO_HI = 0xFFFFFFFDu;
+__host__ __device__ constexpr bool is_pseudo(u32 id) { return id >= PSEUDO_LO && id <= PSEUDO_HI; }
+
 } // namespace cosdev

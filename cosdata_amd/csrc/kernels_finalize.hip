@@ -136,7 +136,7 @@ __device__ __forceinline__ void finalize_one(const IndexDev &ix, const FinalizeA
                     const u32 id = fa.walk_ids[b + j];
                     const float sv = fa.walk_sims[b + j];
                     // root filtered (common.rs:397); so are the pseudo nodes of a metadata collection (common.rs:400-402)
-                    const bool drop = id == COS_ROOT_ID || (ix.mdim != 0u && id >= 0xFFFFFEFEu && id <= 0xFFFFFFFDu);
+                    const bool drop = id == COS_ROOT_ID || (ix.mdim != 0u && id >= PSEUDO_LO && id <= PSEUDO_HI);
                     k[r] = drop ? 0ull : pack_key(metric_key(metric, sv), id);
                 }
             }
@@ -333,7 +333,7 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(NWV ==
         for (int u = 0; u < 4; u++) {
             const u32 id = idv[u];
             // root filtered (common.rs:397); so are the pseudo nodes of a metadata collection (common.rs:400-402)
-            const bool drop = id == COS_ROOT_ID || (ix.mdim != 0u && id >= 0xFFFFFEFEu && id <= 0xFFFFFFFDu);
+            const bool drop = id == COS_ROOT_ID || (ix.mdim != 0u && id >= PSEUDO_LO && id <= PSEUDO_HI);
             const u64 key = pack_key(metric_key(metric, smv[u]), id);
             const u64 keep = ballot64((u32)lane < cc[u] && !drop && key >= T);
             const u32 nk = (u32)__popcll(keep);

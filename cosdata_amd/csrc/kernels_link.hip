@@ -440,30 +440,12 @@ __global__ void low_cache_kernel(const u32 *__restrict__ adj_vec, const int32_t 
     }
 }
 
-// cos_index_append (builder.hip): a level's [n][M] array grows.  Rows [0, old_n - 1) keep their place, the LAST old row (the root) becomes
-// the last new row, the rows between (the new nodes) are filled; a value equal to remap_from (a reference to the root) becomes remap_to.
-__global__ void grow_rows_kernel(const u32 *__restrict__ src, u32 *__restrict__ dst, u32 old_n, u32 new_n, u32 M, u32 remap_from, u32 remap_to, u32 fill) {
-    const u64 total = (u64)new_n * M;
-    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (u64)gridDim.x * blockDim.x) {
-        const u64 row = i / M;
-        const u32 col = (u32)(i - row * M);
-        u32 v = fill;
-        if (row + 1 < old_n) v = src[row * M + col];
-        else if (row + 1 == new_n) v = src[(u64)(old_n - 1) * M + col];
-        else { dst[i] = fill; continue; }
-        dst[i] = v == remap_from ? remap_to : v;
-    }
-}
-__global__ void grow_bytes_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, u32 old_n, u32 new_n) {
-    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < new_n; i += (u64)gridDim.x * blockDim.x)
-        dst[i] = i + 1 < old_n ? src[i] : (i + 1 == new_n ? src[old_n - 1] : (uint8_t)0);
-}
-
-// cos_index_append_meta (builder.hip): a [n][M] array of the pseudo-root component grows.  Its nodes are in ascending id, so the pseudo
-// nodes are the TAIL [tail_first, old_n) of the array and the new nodes go in front of it: rows below tail_first keep their place, the
-// tail moves up by `add`, the rows between are filled.  A copied value that equals remap_from becomes remap_to (the pseudo nodes' vector
-// row after the vector table grew); any other at or above shift_from gains shift_add (an index into an array whose own tail moved; the
-// empty slot stays).  One thread per slot in destination order: consecutive lanes read and write consecutive words.
+// cos_index_append, cos_index_append_meta (builder.hip): a level's [n][M] array grows.  Its nodes are in ascending id and what an append
+// adds lies below the level's TAIL [tail_first, old_n) — the root (one node) on the base graph, the pseudo nodes on the pseudo-root
+// component — so the new nodes go in front of it: rows below tail_first keep their place, the tail moves up by `add`, the rows between
+// are filled.  A copied value that equals remap_from becomes remap_to (the vector row of the root / of the pseudo nodes after the vector
+// table grew); any other at or above shift_from gains shift_add (an index into an array whose own tail moved; the empty slot stays).
+// One thread per slot in destination order: consecutive lanes read and write consecutive words.
 template <typename T>
 __global__ void grow_tail_kernel(const T *__restrict__ src, T *__restrict__ dst, u32 old_n, u32 tail_first, u32 add, u32 M, T fill, u32 shift_from, u32 shift_add,
                                  u32 remap_from, u32 remap_to) {
@@ -542,20 +524,6 @@ hipError_t launch_unlink(const LinkArgs &a, const u32 *dn, u32 *status, hipStrea
     hipLaunchKernelGGL(unlink_kernel, dim3(a.L1), dim3(64), 0, st, a, dn, status);
     return hipGetLastError();
 }
-hipError_t launch_grow_rows(const u32 *src, u32 *dst, u32 old_n, u32 new_n, u32 M, u32 remap_from, u32 remap_to, u32 fill, hipStream_t st) {
-    const u64 total = (u64)new_n * M;
-    if (total == 0 || old_n == 0) return hipErrorInvalidValue;
-    const u32 blocks = (u32)std::min<u64>((total + 255) / 256, 1u << 20);
-    hipLaunchKernelGGL(grow_rows_kernel, dim3(blocks), dim3(256), 0, st, src, dst, old_n, new_n, M, remap_from, remap_to, fill);
-    return hipGetLastError();
-}
-hipError_t launch_grow_bytes(const uint8_t *src, uint8_t *dst, u32 old_n, u32 new_n, hipStream_t st) {
-    if (new_n == 0 || old_n == 0) return hipErrorInvalidValue;
-    const u32 blocks = (u32)std::min<u64>(((u64)new_n + 255) / 256, 1u << 20);
-    hipLaunchKernelGGL(grow_bytes_kernel, dim3(blocks), dim3(256), 0, st, src, dst, old_n, new_n);
-    return hipGetLastError();
-}
-
 hipError_t launch_grow_tail(const u32 *src, u32 *dst, u32 old_n, u32 tail_first, u32 add, u32 M, u32 fill, const GrowValues &v, hipStream_t st) {
     const u64 total = ((u64)old_n + add) * M;
     if (total == 0 || tail_first > old_n) return hipErrorInvalidValue;

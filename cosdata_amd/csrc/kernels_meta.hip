@@ -22,7 +22,6 @@ using namespace cosdev;
 
 namespace {
 
-constexpr u32 PSEUDO_LO = 0xFFFFFEFEu, PSEUDO_HI = 0xFFFFFFFDu; // u32::MAX - 257 ..= u32::MAX - 2 (types.rs:229)
 constexpr int PBM = 4;                                          // code rows in flight per lane group
 enum : int { KIND_BASE = 0, KIND_PSEUDO = 1, KIND_METADATA = 2 };
 

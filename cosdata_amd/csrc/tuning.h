@@ -38,7 +38,7 @@ enum TuneKey : int {
     TUNE_WALK_LAT4_E,         // entries consumed per round by the four-wave latency kernel
     TUNE_FINALIZE_FAST,       // 0 = the general finalize kernel alone
     TUNE_SHARDSET_FORCE_RCCL, // 1 = a world of one still goes through the RCCL exchange (tests)
-    TUNE_BUILD_PROFILE,       // 1 = cos_index_build prints its phase times to stderr
+    TUNE_BUILD_PROFILE,       // 1 = every build / append prints its link schedule's phase times to stderr (base graph and component)
     TUNE_WALK_MERGE_MIN,      // table levels: winners from which an expansion takes the ranked merge (0 = never; default 4 up to ef 64, 3 above)
     TUNE_WALK_ADJ_MAG,        // 0 = row levels gather the winners' norms from mags[] instead of reading them beside the adjacency (LevelDev::adj_mag); 2 = beside the adjacency at every ef and launch size (default 1: up to ef = 2 x the level's neighbour count, launches of 4096 queries or more)
     TUNE_WALK_TABLE_RULE_C,   // the automatic level-table rule's constant: a level takes part while it holds <= c x ef_search x neighbors_count nodes (default 10 up to ef = 1.5 x neighbors_count, 8 up to 2 x, 6 above)

@@ -1,6 +1,7 @@
-// Stand-alone check of cosdata_amd/csrc/meta_grow_plan.h (driven by tests/test_meta_grow_plan.py, built with -fsanitize=address,undefined):
-// where the new nodes of an append go on every level of the pseudo-root component, their child links, and the renumbering of an old index.
-// The expected values are the hand-written lines of tests/golden/meta_grow_plan_cases.txt (argv[1]), never taken from the header.
+// Stand-alone check of cosdata_amd/csrc/level_grow_plan.h (driven by tests/test_level_grow_plan.py, built with -fsanitize=address,undefined):
+// where the new nodes of an append go on every level of the base graph (tail: the root) and of the pseudo-root component (tail: the pseudo
+// nodes), their child links, and the renumbering of an old index.
+// The expected values are the hand-written lines of tests/golden/level_grow_plan_cases.txt (argv[1]), never taken from the header.
 #include <cstdint>
 #include <cstdio>
 #include <fstream>
@@ -8,9 +9,9 @@
 #include <string>
 #include <vector>
 
-#include "meta_grow_plan.h"
+#include "level_grow_plan.h"
 
-namespace mg = meta_grow_plan;
+namespace mg = level_grow_plan;
 
 static int failures = 0;
 static int line_no = 0;
@@ -75,7 +76,7 @@ static bool plan_case(std::istringstream &in) {
 
 int main(int argc, char **argv) {
     if (argc != 2) {
-        std::printf("usage: meta_grow_plan_check tests/golden/meta_grow_plan_cases.txt\n");
+        std::printf("usage: level_grow_plan_check tests/golden/level_grow_plan_cases.txt\n");
         return 2;
     }
     std::ifstream file(argv[1]);
@@ -113,7 +114,7 @@ int main(int argc, char **argv) {
             failures++;
         }
     }
-    EXPECT(plans >= 5 && remaps >= 7 && tails >= 5); // a truncated file is no pass
+    EXPECT(plans >= 9 && remaps >= 9 && tails >= 5); // a truncated file is no pass
     EXPECT(mg::PSEUDO_LO == 0xFFFFFFFFu - 257u && mg::NONE == 0xFFFFFFFFu);
     if (failures) {
         std::printf("%d failures\n", failures);

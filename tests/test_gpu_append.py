@@ -79,6 +79,36 @@ def test_append_on_a_batch_boundary_equals_the_full_build():
     _same_graph(part.download_graph(), full.download_graph())
 
 
+def test_append_grows_levels_that_hold_only_the_root():
+    """a level grows in front of a tail of ONE node, the root (grow_tail_kernel, level_grow_plan.h): levels that hold nothing but the
+    root, a level that gains nothing while the level below gains, appends of 1 and 3 vectors, and a new vector that reaches a root-only
+    level.  The seed is chosen so that the oracle's graph shows those shapes; the test asserts that it does."""
+    dim, n0, adds, batch = 32, 40, (1, 3, 60), 8
+    X = H.clustered_corpus(n0 + sum(adds), dim, n_centers=4, seed=17)
+    p = O.HNSWParams(dim=dim, storage=O.STORAGE_U8, num_layers=5, ef_construction=32, ef_search=32, seed=5,
+                     level0_neighbors_count=16, neighbors_count=8)
+    oix = O.OracleIndex(p).set_vectors(X[:n0])
+    oix.build_rounds(batch)
+    dix = _device(X[:n0], p).build(batch)
+    before = [len(ids) for ids, _ in oix.export_graph()]
+    assert 1 in before, before                                   # at least one level holds exactly one node, the root
+    _same_graph(dix.download_graph(), oix.export_graph())
+    at = n0
+    for k, a in enumerate(adds):
+        oix.append(X[at:at + a], batch)
+        dix.append(X[at:at + a], batch)
+        at += a
+        after = [len(ids) for ids, _ in oix.export_graph()]
+        if k == 0:
+            assert any(x == y for x, y in zip(before, after)), (before, after)   # the first append leaves a level's node count unchanged
+        _same_graph(dix.download_graph(), oix.export_graph())
+    assert any(x == 1 and y > 1 for x, y in zip(before, after)), (before, after)  # a root-only level gained a node
+    Q = H.queries_from(X, 64, noise=0.05, seed=3)
+    ids, sc, cnt = dix.batch_search(Q, 10)
+    oids, osc, ocnt = oix.search_batch(Q, 10, threads=4)[:3]
+    assert np.array_equal(cnt, ocnt) and np.array_equal(ids, oids) and np.array_equal(sc.view(np.uint32), osc.view(np.uint32))
+
+
 def test_append_device_rows_and_refusals():
     import torch
     import cosdata_amd as ca

@@ -185,3 +185,26 @@ def test_filtered_search_on_two_shards_of_a_metadata_collection():
     assert owners == {False, True}                               # both shards contribute to merged answers
     with pytest.raises(ca.CosdataError):                         # a base that is not a whole number of embeddings is refused
         Bs.device(ob, id_base=base_b + 1)
+
+
+def test_failed_component_build_leaves_no_component():
+    """a replica whose vector has zero norm aborts its insertion walk with CalculationError (cosine.rs:228-232), as on the base graph
+    (tests/test_gpu_builder.py::test_failed_build_leaves_no_graph): the handle must come out of the failed cos_index_build_meta without
+    the component (filtered search -> NotReady), not half-linked, and a build on repaired vectors succeeds"""
+    import cosdata_amd as ca
+    sc = MH.Scenario(n=400, dim=32, seed=31)
+    good = sc.X.copy()
+    sc.X[250] = -1.0                                              # quantizes to all-zero bytes -> |v| = 0
+    dix = sc.device_index()
+    sc.X = good                                                   # (the queries below come from the repaired rows)
+    with pytest.raises(ca.CosdataError) as ei:
+        dix.build_meta(sc.node_ids, sc.mbits, sc.max_levels, 16)
+    assert ei.value.status == ca._lib.ERR_CALCULATION
+    Q, off, rows, _ = sc.queries(nq=4, seed=1)
+    with pytest.raises(ca.CosdataError) as ei:
+        dix.search_filtered(Q, off, rows.astype(np.int8), 5)
+    assert ei.value.status == ca._lib.ERR_NOT_READY
+    dix.upload_vectors(good).enable_metadata(sc.mdim, sc.replicas)
+    dix.build_meta(sc.node_ids, sc.mbits, sc.max_levels, 16)
+    _, _, counts = dix.search_filtered(Q, off, rows.astype(np.int8), 5)
+    assert (counts > 0).any()                                     # the component answers again
