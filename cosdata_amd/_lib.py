@@ -142,7 +142,9 @@ ABI_SYMBOLS = [
     "cos_sparse_set_max_candidates", "cos_sparse_max_candidates", "cos_sparse_search_batch_device",
     "cos_hybrid_create", "cos_hybrid_destroy", "cos_hybrid_search_mixed",
     "cos_sparse_insert", "cos_sparse_delete", "cos_sparse_stats", "cos_sparse_download", "cos_merge_topk_device", "cos_merge_topk_packed_device", "cos_hbm_probe",
+    "cos_merge_lists_device", "cos_merge_lists_packed_device",
     "cos_shardset_unique_id", "cos_shardset_create", "cos_shardset_destroy", "cos_shardset_search_batch", "cos_shardset_exchange_device",
+    "cos_shardset_search_filtered_batch", "cos_shardset_flat_search_batch", "cos_shardset_bruteforce_topk",
     "cos_tuning_set", "cos_tuning_clear", "cos_tuning_get",
 ]
 
@@ -252,6 +254,11 @@ def lib():
         "cos_shardset_destroy": [vp],
         "cos_shardset_search_batch": [vp, vp, u32, u32, vp, vp, vp],
         "cos_shardset_exchange_device": [vp, vp, u32, u32, vp, vp, vp, vp, vp],
+        "cos_merge_lists_device": [vp, vp, vp, u32, u32, u32, vp, vp, vp, i32, vp],
+        "cos_merge_lists_packed_device": [vp, u32, u32, u32, vp, vp, vp, i32, vp],
+        "cos_shardset_search_filtered_batch": [vp, vp, u32, vp, vp, u32, vp, vp, vp],
+        "cos_shardset_flat_search_batch": [vp, vp, u32, u32, vp, vp, vp, vp],
+        "cos_shardset_bruteforce_topk": [vp, vp, u32, u32, vp, vp, vp, vp],
         "cos_tuning_set": [C.c_char_p, C.c_int64],
         "cos_tuning_clear": [C.c_char_p],
         "cos_tuning_get": [C.c_char_p, C.POINTER(C.c_int64), C.POINTER(i32)],

@@ -1983,8 +1983,11 @@ static bool meta_ready(const cos_index *ix) {
 }
 
 // quantize -> filtered walk (pseudo-root component) -> [finalize]; host buffers.  per-level lists when out_lvl_* are given.
+// With d_record (device memory on the index's device, B * (2 top_k + 1) words; top_k > 0) the shard set's form: the finalize writes
+// [ids B*top_k | scores B*top_k | counts B] there instead of the workspace's staging and only the statuses come back.
 static int32_t search_filtered_host(cos_index *ix, const float *queries, u32 B, const u32 *f_off, const int8_t *f_dims, u32 top_k, u32 *out_ids,
-                                    float *out_scores, u32 *out_counts, int32_t *out_status, u32 *lvl_ids, float *lvl_sims, u32 *lvl_counts) {
+                                    float *out_scores, u32 *out_counts, int32_t *out_status, u32 *lvl_ids, float *lvl_sims, u32 *lvl_counts,
+                                    u32 *d_record = nullptr) {
     if (!ix || !queries || !f_off || !f_dims || B == 0) return cos_fail(COS_ERR_INVALID, "bad argument");
     if (!meta_ready(ix)) return cos_fail(COS_ERR_NOT_READY, "the metadata component needs its node table and every graph level before a filtered search");
     u32 ef, vmode;
@@ -2049,6 +2052,10 @@ static int32_t search_filtered_host(cos_index *ix, const float *queries, u32 B, 
         HIP_TRY(hipMemcpyAsync(lvl_sims, w->walk_sims, (size_t)B * L1 * KEEP_SEARCH * 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(lvl_counts, w->walk_counts, (size_t)B * L1 * 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(status.data(), w->walk_status, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+    } else if (d_record) {
+        HIP_TRY(launch_finalize(dev, w->d_queries, ix->p.dim, w->q_raw_mags, w->walk_ids, w->walk_sims, w->walk_counts, w->walk_status, B, top_k, d_record,
+                                reinterpret_cast<float *>(d_record + (size_t)B * top_k), d_record + 2 * (size_t)B * top_k, w->d_out_status, w->rerank_rows, st));
+        HIP_TRY(hipMemcpyAsync(status.data(), w->d_out_status, (size_t)B * 4, hipMemcpyDeviceToHost, st));
     } else {
         HIP_TRY(launch_finalize(dev, w->d_queries, ix->p.dim, w->q_raw_mags, w->walk_ids, w->walk_sims, w->walk_counts, w->walk_status, B, top_k, w->d_out_ids,
                                 w->d_out_scores, w->d_out_counts, w->d_out_status, w->rerank_rows, st));
@@ -2069,6 +2076,14 @@ extern "C" int32_t cos_search_filtered_batch(cos_index *ix, const float *queries
     if (!out_ids || !out_scores || !out_counts || top_k == 0 || top_k > 1024) return cos_fail(COS_ERR_INVALID, "bad argument");
     return search_filtered_host(ix, queries, B, filter_offsets, filter_dims, top_k, out_ids, out_scores, out_counts, out_status, nullptr, nullptr, nullptr);
 }
+
+namespace cosdev {
+// cos_search_filtered_batch for one shard of a shard set (shardset.hip): the packed record stays in d_record on the index's device
+int32_t search_filtered_record(cos_index *ix, const float *queries, u32 B, const u32 *filter_offsets, const int8_t *filter_dims, u32 top_k, u32 *d_record) {
+    if (!d_record || top_k == 0 || top_k > 1024) return cos_fail(COS_ERR_INVALID, "bad argument");
+    return search_filtered_host(ix, queries, B, filter_offsets, filter_dims, top_k, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, d_record);
+}
+} // namespace cosdev
 
 extern "C" int32_t cos_ann_search_filtered_batch(cos_index *ix, const float *queries, uint32_t B, const uint32_t *filter_offsets, const int8_t *filter_dims,
                                                  uint32_t *out_ids, float *out_sims, uint32_t *out_counts, int32_t *out_status) {

@@ -351,6 +351,14 @@ struct cos_index {
 
 struct FlatWs;
 void cos_flat_ws_release(cos_index *ix);
+namespace cosdev {
+// The single-index searches as one shard of a shard set runs them (shardset.hip): the operator's own kernels, refusals and zero-norm rule;
+// the packed record [ids B*k | scores B*k | counts B] is left in d_record (device memory on the index's device, B * (2k + 1) words) and is
+// complete when the call returns.  kernels_flat.hip (the first two), engine.hip.
+int32_t flat_search_record(cos_index *ix, const float *queries, u32 B, u32 top_k, const cos_scan_mask *mask, u32 *d_record);
+int32_t bruteforce_record(cos_index *ix, const float *queries, u32 B, u32 k, const cos_scan_mask *mask, u32 *d_record);
+int32_t search_filtered_record(cos_index *ix, const float *queries, u32 B, const u32 *filter_offsets, const int8_t *filter_dims, u32 top_k, u32 *d_record);
+} // namespace cosdev
 // the deleted set (kernels_flat.hip), on `st`: a fresh all-live bitmap for n rows | grown from n0 to n1 rows, the new ones live | ids marked
 hipError_t cos_deleted_reset(cos_index *ix, u32 n, hipStream_t st);
 hipError_t cos_deleted_grow(cos_index *ix, u32 n0, u32 n1, hipStream_t st);

@@ -833,10 +833,12 @@ hipError_t launch_codes_gemm(int eng, bool fused, int pf, bool masked, const Cod
     return hipGetLastError();
 }
 
-// cos_bruteforce_topk (mask == nullptr, out_counts optional) and cos_bruteforce_topk_masked
+// cos_bruteforce_topk (mask == nullptr, out_counts optional) and cos_bruteforce_topk_masked; with d_record (device memory on the index's
+// device, B * (2k + 1) words) the shard set's form: the same launches, the rerank writes [ids B*k | scores B*k | counts B] there instead of
+// the call's own buffers, nothing is copied out (out_* unused) and the record is complete when the call returns
 int32_t bruteforce_run(cos_index *ix, const float *queries, uint32_t B, uint32_t k, const cos_scan_mask *mask, uint32_t *out_ids, float *out_scores,
-                       uint32_t *out_counts) {
-    if (!ix || !queries || !out_ids || !out_scores || B == 0) return cos_fail(COS_ERR_INVALID, "bad argument");
+                       uint32_t *out_counts, u32 *d_record = nullptr) {
+    if (!ix || !queries || ((!out_ids || !out_scores) && !d_record) || B == 0) return cos_fail(COS_ERR_INVALID, "bad argument");
     if (!ix->have_vectors) return cos_fail(COS_ERR_NOT_READY, "upload vectors first");
     if (int32_t krc = fp::check_brute_k(k, ix->n)) return cos_fail(krc, "k must be in [1, min(512, n)]");
     MaskPlan mp;
@@ -869,9 +871,13 @@ int32_t bruteforce_run(cos_index *ix, const float *queries, uint32_t B, uint32_t
     if (plan.allow_fused) HIP_TRY(d_app.alloc((size_t)B * plan.app_cap()));
     HIP_TRY(d_appcnt.alloc(B));
     HIP_TRY(d_over.alloc(1));
-    HIP_TRY(d_oi.alloc((size_t)B * k));
-    HIP_TRY(d_os.alloc((size_t)B * k));
-    if (mp.masked) HIP_TRY(d_oc.alloc(B));
+    if (!d_record) {
+        HIP_TRY(d_oi.alloc((size_t)B * k));
+        HIP_TRY(d_os.alloc((size_t)B * k));
+        if (mp.masked) HIP_TRY(d_oc.alloc(B));
+    }
+    u32 *const r_oi = d_record ? d_record : d_oi.p, *const r_oc = d_record ? d_record + 2 * (size_t)B * k : d_oc.p;
+    float *const r_os = d_record ? reinterpret_cast<float *>(d_record + (size_t)B * k) : d_os.p;
     // (from here on a ladder: the stream is drained below on every path before the buffers and `hover` go out of scope)
     hipError_t e = hipMemcpyAsync(d_q, queries, (size_t)B * dim * 4, hipMemcpyHostToDevice, st);
     // |q| in the reference's sequential order (vector_store.rs:414): reuse the F32 quantize kernel's raw_mags output
@@ -900,20 +906,21 @@ int32_t bruteforce_run(cos_index *ix, const float *queries, uint32_t B, uint32_t
     }
     if (e == hipSuccess && R == 1) {
         hipLaunchKernelGGL(flat_rescore, dim3(B), dim3(64), staged_query_bytes(dim), st, d_q, (u64)dim, d_qm, B, ix->d_raw, (u64)dim,
-                           ix->d_raw_mags, dim, d_pool, k, ix->p.id_base, d_oi, d_os);
+                           ix->d_raw_mags, dim, d_pool, k, ix->p.id_base, r_oi, r_os);
         e = hipGetLastError();
     } else if (e == hipSuccess)
-        e = launch_flat_rerank_wide(R, true, d_q, (u64)dim, d_qm, B, ix->d_raw, (u64)dim, ix->d_raw_mags, dim, d_pool, P, k, ix->p.id_base, d_oi, d_os, nullptr, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(out_ids, d_oi, (size_t)B * k * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(out_scores, d_os, (size_t)B * k * 4, hipMemcpyDeviceToHost, st);
+        e = launch_flat_rerank_wide(R, true, d_q, (u64)dim, d_qm, B, ix->d_raw, (u64)dim, ix->d_raw_mags, dim, d_pool, P, k, ix->p.id_base, r_oi, r_os, nullptr, st);
+    if (e == hipSuccess && !d_record) e = hipMemcpyAsync(out_ids, r_oi, (size_t)B * k * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && !d_record) e = hipMemcpyAsync(out_scores, r_os, (size_t)B * k * 4, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && mp.masked) { // a query may have fewer live rows than k
-        hipLaunchKernelGGL(pool_count_kernel, dim3(B), dim3(64), 0, st, (const u64 *)d_pool, P, B, k, d_oc.p);
+        hipLaunchKernelGGL(pool_count_kernel, dim3(B), dim3(64), 0, st, (const u64 *)d_pool, P, B, k, r_oc);
         e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(out_counts, d_oc, (size_t)B * 4, hipMemcpyDeviceToHost, st);
-    }
+        if (e == hipSuccess && !d_record) e = hipMemcpyAsync(out_counts, r_oc, (size_t)B * 4, hipMemcpyDeviceToHost, st);
+    } else if (e == hipSuccess && d_record)
+        e = launch_fill_i32(reinterpret_cast<int32_t *>(r_oc), B, (int32_t)k, st); // k <= n: every list is full
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     HIP_TRY(e);
-    if (!mp.masked && out_counts) std::fill(out_counts, out_counts + B, k); // k <= n: every list is full
+    if (!mp.masked && out_counts && !d_record) std::fill(out_counts, out_counts + B, k); // k <= n: every list is full
     return COS_OK;
 }
 
@@ -972,10 +979,12 @@ void cos_flat_ws_release(cos_index *ix) { // cos_index_destroy, and every upload
 // u8 and the three bit-plane storages (binary, quaternary, octal): integer dots, exact in any order.  f16 / f32 codes are refused: their
 // reference dots are order-dependent f32 chains that an MFMA cannot reproduce, so the candidate set could not be exact.
 // ------------------------------------------------------------------------------------------------
-// cos_flat_search_batch (mask == nullptr) and cos_flat_search_masked_batch
+// cos_flat_search_batch (mask == nullptr) and cos_flat_search_masked_batch; with d_record (device memory on the index's device,
+// B * (2 top_k + 1) words) the shard set's form: the same launches and read-backs, and the first 2 B top_k + B words of the packed output
+// [ids | scores | counts] go to d_record by a device copy instead of to out_* (unused); the record is complete when the call returns
 static int32_t flat_search_run(cos_index *ix, const float *queries, uint32_t B, uint32_t top_k, const cos_scan_mask *mask, uint32_t *out_ids,
-                               float *out_scores, uint32_t *out_counts, cos_flat_stats *stats) {
-    if (!ix || !queries || !out_ids || !out_scores || !out_counts || B == 0) return cos_fail(COS_ERR_INVALID, "bad argument");
+                               float *out_scores, uint32_t *out_counts, cos_flat_stats *stats, u32 *d_record = nullptr) {
+    if (!ix || !queries || ((!out_ids || !out_scores || !out_counts) && !d_record) || B == 0) return cos_fail(COS_ERR_INVALID, "bad argument");
     if (!ix->have_vectors) return cos_fail(COS_ERR_NOT_READY, "upload vectors first");
     MaskPlan mp;
     if (int32_t mrc = scan_mask_plan(mask, B, mp)) return mrc;
@@ -1145,6 +1154,11 @@ static int32_t flat_search_run(cos_index *ix, const float *queries, uint32_t B, 
         const u32 hover = ho[2 * nk + B + 1];
         if (zero) break;
         if (plan.fused(attempt) && hover != 0) continue; // the append buffer overflowed: repeat unfused
+        if (d_record) {
+            e = hipMemcpyAsync(d_record, W->out.p, (2 * nk + B) * 4, hipMemcpyDeviceToDevice, st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            break;
+        }
         memcpy(out_ids, ho, nk * 4);
         memcpy(out_scores, ho + nk, nk * 4);
         memcpy(out_counts, ho + 2 * nk, (size_t)B * 4);
@@ -1176,6 +1190,19 @@ extern "C" int32_t cos_flat_search_masked_batch(cos_index *ix, const float *quer
                                                 float *out_scores, uint32_t *out_counts, cos_flat_stats *stats) {
     return flat_search_run(ix, queries, B, top_k, mask, out_ids, out_scores, out_counts, stats);
 }
+
+namespace cosdev {
+// The per-shard forms of a shard set (shardset.hip): the single-index operator with its refusals and its zero-norm rule, the packed record
+// [ids B*k | scores B*k | counts B] left in d_record on the index's device.
+int32_t flat_search_record(cos_index *ix, const float *queries, u32 B, u32 top_k, const cos_scan_mask *mask, u32 *d_record) {
+    if (!d_record) return cos_fail(COS_ERR_INVALID, "bad argument");
+    return flat_search_run(ix, queries, B, top_k, mask, nullptr, nullptr, nullptr, nullptr, d_record);
+}
+int32_t bruteforce_record(cos_index *ix, const float *queries, u32 B, u32 k, const cos_scan_mask *mask, u32 *d_record) {
+    if (!d_record) return cos_fail(COS_ERR_INVALID, "bad argument");
+    return bruteforce_run(ix, queries, B, k, mask, nullptr, nullptr, nullptr, d_record);
+}
+} // namespace cosdev
 
 // ---- the deleted set ----
 hipError_t cos_deleted_reset(cos_index *ix, u32 n, hipStream_t st) {

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "engine_internal.h"
+#include "merge_plan.h"
 #include "topk_select.h"
 
 using namespace cosdev;
@@ -52,23 +53,80 @@ __global__ __launch_bounds__(64) void merge_topk_kernel(const u32 *__restrict__ 
     if (lane == 0) out_counts[q] = n;
 }
 
+// The same rule for 1025 .. 8192 keys (merge_plan.h): one workgroup per query, the keys in N = 2048, 4096 or 8192 words of LDS
+// (dynamic: N * 8 bytes + the count), sorted by the workgroup's bitonic network.  Unsorted input is accepted because everything is sorted.
+template <u32 N>
+__global__ __launch_bounds__(merge_plan::LDS_THREADS) void merge_lists_lds_kernel(const u32 *__restrict__ ids, const float *__restrict__ scores,
+                                                                                  const u32 *__restrict__ counts, u64 stride_rows, u64 stride_counts,
+                                                                                  u32 S, u32 B, u32 k, u32 *__restrict__ out_ids,
+                                                                                  float *__restrict__ out_scores, u32 *__restrict__ out_counts) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    u64 *keys = (u64 *)smem_raw;
+    u32 *s_total = (u32 *)(keys + N);
+    const u32 q = blockIdx.x;
+    if (q >= B) return;
+    const u32 live = S * k; // <= N (the launch checks it)
+    if (threadIdx.x == 0) *s_total = 0u;
+    for (u32 e = threadIdx.x; e < N; e += blockDim.x) {
+        u64 key = 0ull;
+        if (e < live) {
+            const u32 s = e / k, j = e % k;
+            if (j < counts[(u64)s * stride_counts + q]) {
+                const u64 off = (u64)s * stride_rows + (u64)q * k + j;
+                key = pack_key(simkey(scores[off]), ids[off]);
+            }
+        }
+        keys[e] = key;
+    }
+    u32 part = 0;
+    for (u32 s = threadIdx.x; s < S; s += blockDim.x) part += counts[(u64)s * stride_counts + q];
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) part += (u32)__shfl_xor((int)part, m, 64);
+    __syncthreads(); // s_total is zero
+    if ((threadIdx.x & 63) == 0 && part) atomicAdd(s_total, part);
+    lds_bitonic_sort_desc<N>(keys); // (begins and ends with a barrier)
+    const u32 total = *s_total, n = total < k ? total : k;
+    for (u32 e = threadIdx.x; e < n; e += blockDim.x) {
+        const u64 key = keys[e];
+        out_ids[(u64)q * k + e] = (u32)key;
+        out_scores[(u64)q * k + e] = simkey_inv((u32)(key >> 32));
+    }
+    if (threadIdx.x == 0) out_counts[q] = n;
+}
+
+static_assert(merge_plan::OK == COS_OK && merge_plan::INVALID == COS_ERR_INVALID && merge_plan::UNIMPLEMENTED == COS_ERR_UNIMPLEMENTED, "merge_plan.h restates these");
+
+// max_keys: merge_plan::WAVE_MAX_KEYS (cos_merge_topk_*) or merge_plan::LDS_MAX_KEYS (cos_merge_lists_*)
 int32_t merge_topk_launch(const uint32_t *d_ids, const float *d_scores, const uint32_t *d_counts, u64 stride_rows, u64 stride_counts,
                           uint32_t S, uint32_t B, uint32_t k, uint32_t *d_out_ids, float *d_out_scores, uint32_t *d_out_counts,
-                          int32_t device, void *stream) {
+                          int32_t device, void *stream, uint32_t max_keys) {
     if (!d_ids || !d_scores || !d_counts || !d_out_ids || !d_out_scores || !d_out_counts || S == 0 || B == 0 || k == 0)
         return cos_fail(COS_ERR_INVALID, "bad argument");
+    const merge_plan::Plan plan = merge_plan::plan(S, k, max_keys);
+    if (plan.kind == merge_plan::Kind::REFUSED)
+        return cos_fail(plan.status, "S*k > %u not supported by the merge kernel", max_keys);
     HIP_TRY(hipSetDevice(device));
-    const u32 total = S * k;
     hipStream_t st = (hipStream_t)stream;
     dim3 grid(B), block(64);
 #define LAUNCH(R) hipLaunchKernelGGL(merge_topk_kernel<R>, grid, block, 0, st, d_ids, d_scores, d_counts, stride_rows, stride_counts, S, B, k, d_out_ids, d_out_scores, d_out_counts)
-    if (total <= 64) LAUNCH(1);
-    else if (total <= 128) LAUNCH(2);
-    else if (total <= 256) LAUNCH(4);
-    else if (total <= 512) LAUNCH(8);
-    else if (total <= 1024) LAUNCH(16);
-    else return cos_fail(COS_ERR_UNIMPLEMENTED, "S*k > 1024 not supported by the merge kernel");
+#define LAUNCH_LDS(N)                                                                                                                                   \
+    do {                                                                                                                                                \
+        const size_t smem = (size_t)(N) * 8 + 16;                                                                                                       \
+        HIP_TRY(hipFuncSetAttribute((const void *)merge_lists_lds_kernel<N>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));                   \
+        hipLaunchKernelGGL(merge_lists_lds_kernel<N>, grid, dim3(merge_plan::LDS_THREADS), smem, st, d_ids, d_scores, d_counts, stride_rows, stride_counts, \
+                           S, B, k, d_out_ids, d_out_scores, d_out_counts);                                                                             \
+    } while (0)
+    if (plan.kind == merge_plan::Kind::WAVE) {
+        if (plan.width == 1) LAUNCH(1);
+        else if (plan.width == 2) LAUNCH(2);
+        else if (plan.width == 4) LAUNCH(4);
+        else if (plan.width == 8) LAUNCH(8);
+        else LAUNCH(16);
+    } else if (plan.width == 2048) LAUNCH_LDS(2048);
+    else if (plan.width == 4096) LAUNCH_LDS(4096);
+    else LAUNCH_LDS(8192);
 #undef LAUNCH
+#undef LAUNCH_LDS
     HIP_TRY(hipGetLastError());
     return COS_OK;
 }
@@ -78,7 +136,7 @@ int32_t merge_topk_launch(const uint32_t *d_ids, const float *d_scores, const ui
 extern "C" int32_t cos_merge_topk_device(const uint32_t *d_ids, const float *d_scores, const uint32_t *d_counts, uint32_t S, uint32_t B,
                                          uint32_t k, uint32_t *d_out_ids, float *d_out_scores, uint32_t *d_out_counts, int32_t device,
                                          void *stream) {
-    return merge_topk_launch(d_ids, d_scores, d_counts, (u64)B * k, B, S, B, k, d_out_ids, d_out_scores, d_out_counts, device, stream);
+    return merge_topk_launch(d_ids, d_scores, d_counts, (u64)B * k, B, S, B, k, d_out_ids, d_out_scores, d_out_counts, device, stream, merge_plan::WAVE_MAX_KEYS);
 }
 
 extern "C" int32_t cos_merge_topk_packed_device(const uint32_t *d_packed, uint32_t S, uint32_t B, uint32_t k, uint32_t *d_out_ids,
@@ -86,7 +144,22 @@ extern "C" int32_t cos_merge_topk_packed_device(const uint32_t *d_packed, uint32
     if (!d_packed) return cos_fail(COS_ERR_INVALID, "bad argument");
     const u64 rec = (u64)B * (2ull * k + 1ull);
     return merge_topk_launch(d_packed, reinterpret_cast<const float *>(d_packed + (u64)B * k), d_packed + 2ull * B * k, rec, rec, S, B, k,
-                             d_out_ids, d_out_scores, d_out_counts, device, stream);
+                             d_out_ids, d_out_scores, d_out_counts, device, stream, merge_plan::WAVE_MAX_KEYS);
+}
+
+// the same two calls for up to 8192 keys per query: S * k <= 1024 launches what they launch, above it merge_lists_lds_kernel
+extern "C" int32_t cos_merge_lists_device(const uint32_t *d_ids, const float *d_scores, const uint32_t *d_counts, uint32_t S, uint32_t B,
+                                          uint32_t k, uint32_t *d_out_ids, float *d_out_scores, uint32_t *d_out_counts, int32_t device,
+                                          void *stream) {
+    return merge_topk_launch(d_ids, d_scores, d_counts, (u64)B * k, B, S, B, k, d_out_ids, d_out_scores, d_out_counts, device, stream, merge_plan::LDS_MAX_KEYS);
+}
+
+extern "C" int32_t cos_merge_lists_packed_device(const uint32_t *d_packed, uint32_t S, uint32_t B, uint32_t k, uint32_t *d_out_ids,
+                                                 float *d_out_scores, uint32_t *d_out_counts, int32_t device, void *stream) {
+    if (!d_packed) return cos_fail(COS_ERR_INVALID, "bad argument");
+    const u64 rec = (u64)B * (2ull * k + 1ull);
+    return merge_topk_launch(d_packed, reinterpret_cast<const float *>(d_packed + (u64)B * k), d_packed + 2ull * B * k, rec, rec, S, B, k,
+                             d_out_ids, d_out_scores, d_out_counts, device, stream, merge_plan::LDS_MAX_KEYS);
 }
 
 // ================================================================================================

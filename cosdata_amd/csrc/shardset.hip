@@ -4,7 +4,9 @@
 // The caller of the reference's search path is ONE process: IndexOps::batch_search (indexes/mod.rs:260-272).  A cos_shardset
 // gives that process one call that fans a query batch out to S resident shards (cos_index handles, id_base = first id of the
 // shard), runs walk + exact rerank on every shard's GPU, exchanges the packed per-shard records [ids | scores | counts] with
-// ONE all-gather and merges them (merge_topk_kernel): cos_shardset_search_batch.  Two deployments share the code:
+// ONE all-gather and merges them (cos_merge_lists_packed_device, up to 8192 keys per query): cos_shardset_search_batch.  The filtered
+// and the two exhaustive searches have the same shape (cos_shardset_search_filtered_batch, cos_shardset_flat_search_batch,
+// cos_shardset_bruteforce_topk): every shard runs the single-index operator and leaves its record on its device.  Two deployments share the code:
 //   * single process, S devices   (the Rust host):  ranks 0..S-1 are all local; communicators from ncclCommInitAll;
 //     the per-launch collective is S grouped ncclAllGather calls, one per device stream;
 //   * one process per GPU         (bench.py under torchrun): every process owns one local shard and joins a world-size
@@ -22,9 +24,13 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <string>
+#include <thread>
 #include <vector>
 
 #include "engine_internal.h"
+#include "flat_plan.h"
+#include "merge_plan.h"
 
 using namespace cosdev;
 
@@ -213,20 +219,51 @@ static int32_t exchange_local(cos_shardset *ss, size_t words) {
     return COS_OK;
 }
 
+namespace {
+struct DrainAll { // every return path — a later shard's error, a failed grow, a failed exchange — leaves no walk or collective
+    cos_shardset *ss; // of this batch queued on any shard's stream: the next call (or destroy) starts from idle streams
+    ~DrainAll() {
+        for (LocalShard &s : ss->sh) { (void)hipSetDevice(s.device); (void)hipStreamSynchronize(s.stream); }
+        (void)hipSetDevice(ss->sh[0].device);
+    }
+};
+
+// the merge takes at most 8192 keys per query (merge_plan.h)
+int32_t check_merge_width(u32 S, u32 top_k) {
+    const merge_plan::Plan mp = merge_plan::plan(S, top_k, merge_plan::LDS_MAX_KEYS);
+    if (mp.kind == merge_plan::Kind::REFUSED)
+        return cos_fail(mp.status, "%u shards x top_k %u = %llu merged keys per query: at most %u", S, top_k, (unsigned long long)mp.keys, merge_plan::LDS_MAX_KEYS);
+    return COS_OK;
+}
+
+// every shard's record is in its d_packed (events `done` recorded): ONE exchange, the merge on shard 0's device and the copies back, all
+// enqueued on the shards' streams; the caller synchronises shard 0's
+int32_t exchange_merge_copy(cos_shardset *ss, u32 B, u32 top_k, size_t words, uint32_t *out_ids, float *out_scores, uint32_t *out_counts) {
+    int32_t rc = exchange_local(ss, words);
+    if (rc) return rc;
+    LocalShard &root = ss->sh[0];
+    HIP_TRY(hipSetDevice(root.device));
+    HIP_TRY(ss->d_out_ids.grow((size_t)B * top_k));
+    HIP_TRY(ss->d_out_scores.grow((size_t)B * top_k));
+    HIP_TRY(ss->d_out_counts.grow((size_t)B * top_k));
+    rc = cos_merge_lists_packed_device(root.d_gathered, ss->world, B, top_k, ss->d_out_ids, ss->d_out_scores, ss->d_out_counts, root.device, root.stream);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out_ids, ss->d_out_ids, (size_t)B * top_k * 4, hipMemcpyDeviceToHost, root.stream));
+    HIP_TRY(hipMemcpyAsync(out_scores, ss->d_out_scores, (size_t)B * top_k * 4, hipMemcpyDeviceToHost, root.stream));
+    HIP_TRY(hipMemcpyAsync(out_counts, ss->d_out_counts, (size_t)B * 4, hipMemcpyDeviceToHost, root.stream));
+    return COS_OK;
+}
+} // namespace
+
 extern "C" int32_t cos_shardset_search_batch(cos_shardset *ss, const float *queries, uint32_t B, uint32_t top_k, uint32_t *out_ids, float *out_scores,
                                              uint32_t *out_counts) {
     if (!ss || !queries || !out_ids || !out_scores || !out_counts || B == 0 || top_k == 0) return cos_fail(COS_ERR_INVALID, "bad argument");
     if (ss->sh.size() != ss->world) return cos_fail(COS_ERR_INVALID, "cos_shardset_search_batch needs every shard in this process; a process-per-GPU job uses cos_shardset_exchange_device");
+    if (int32_t wrc = check_merge_width(ss->world, top_k)) return wrc;
     std::lock_guard<std::mutex> g(ss->mu);
     const u32 S = ss->world, dim = ss->sh[0].ix->p.dim;
     const size_t words = (size_t)B * (2 * (size_t)top_k + 1);
-    struct DrainAll { // every return path — a later shard's error, a failed grow, a failed exchange — leaves no walk or collective
-        cos_shardset *ss; // of this batch queued on any shard's stream: the next call (or destroy) starts from idle streams
-        ~DrainAll() {
-            for (LocalShard &s : ss->sh) { (void)hipSetDevice(s.device); (void)hipStreamSynchronize(s.stream); }
-            (void)hipSetDevice(ss->sh[0].device);
-        }
-    } drain_all{ss};
+    DrainAll drain_all{ss};
     // 1. every shard: queries up, walk + exact rerank into its packed record (all shards run concurrently on their devices)
     for (LocalShard &s : ss->sh) {
         HIP_TRY(hipSetDevice(s.device));
@@ -241,18 +278,9 @@ extern "C" int32_t cos_shardset_search_batch(cos_shardset *ss, const float *quer
         HIP_TRY(hipEventRecord(s.done, s.stream));
     }
     // 2. ONE exchange step, 3. merge on shard 0's device
-    int32_t rc = exchange_local(ss, words);
+    int32_t rc = exchange_merge_copy(ss, B, top_k, words, out_ids, out_scores, out_counts);
     if (rc) return rc;
     LocalShard &root = ss->sh[0];
-    HIP_TRY(hipSetDevice(root.device));
-    HIP_TRY(ss->d_out_ids.grow((size_t)B * top_k));
-    HIP_TRY(ss->d_out_scores.grow((size_t)B * top_k));
-    HIP_TRY(ss->d_out_counts.grow((size_t)B * top_k));
-    rc = cos_merge_topk_packed_device(root.d_gathered, S, B, top_k, ss->d_out_ids, ss->d_out_scores, ss->d_out_counts, root.device, root.stream);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out_ids, ss->d_out_ids, (size_t)B * top_k * 4, hipMemcpyDeviceToHost, root.stream));
-    HIP_TRY(hipMemcpyAsync(out_scores, ss->d_out_scores, (size_t)B * top_k * 4, hipMemcpyDeviceToHost, root.stream));
-    HIP_TRY(hipMemcpyAsync(out_counts, ss->d_out_counts, (size_t)B * 4, hipMemcpyDeviceToHost, root.stream));
     // per-shard statuses: like the reference's collect::<Result<_>>, one failing query on any shard fails the call
     std::vector<int32_t> status((size_t)B);
     for (LocalShard &s : ss->sh) {
@@ -286,5 +314,115 @@ extern "C" int32_t cos_shardset_exchange_device(cos_shardset *ss, const uint32_t
         if (ss->use_rccl) RCCL_TRY(rccl()->AllGather(d_packed_local, d_gathered, words, ncclUint32, s.comm, st));
         else HIP_TRY(hipMemcpyAsync(d_gathered, d_packed_local, words * 4, hipMemcpyDeviceToDevice, st)); // world of one
     }
-    return cos_merge_topk_packed_device(d_gathered, ss->world, B, top_k, d_out_ids, d_out_scores, d_out_counts, s.device, st);
+    return cos_merge_lists_packed_device(d_gathered, ss->world, B, top_k, d_out_ids, d_out_scores, d_out_counts, s.device, st);
+}
+
+// ---- the filtered and the exhaustive searches on a shard set ---------------------------------------------------------------------------
+namespace {
+enum class ShardOp { FILTERED, FLAT, BRUTE };
+struct ShardOpArgs {
+    ShardOp op;
+    const float *queries;
+    u32 B, top_k;
+    const u32 *f_off = nullptr;                  // FILTERED
+    const int8_t *f_dims = nullptr;
+    const cos_scan_mask *const *masks = nullptr; // FLAT, BRUTE: NULL or [S], every entry NULL or a mask over that shard's own rows
+};
+
+// Every shard's operator (the single-index call's own kernels; each blocks its host thread until the shard's record is complete on the
+// shard's device), one exchange, one merge, one copy back.  Shards on different devices run from one host thread per device, so that the
+// devices work at once; the shards of one device run in turn.
+int32_t shardset_run(cos_shardset *ss, const ShardOpArgs &a, uint32_t *out_ids, float *out_scores, uint32_t *out_counts) {
+    const u32 S = ss->world, B = a.B, top_k = a.top_k;
+    const size_t words = (size_t)B * (2 * (size_t)top_k + 1);
+    std::lock_guard<std::mutex> g(ss->mu);
+    DrainAll drain_all{ss};
+    for (LocalShard &s : ss->sh) {
+        HIP_TRY(hipSetDevice(s.device));
+        HIP_TRY(s.d_packed.grow(words));
+        HIP_TRY(s.d_gathered.grow(words * S));
+    }
+    std::vector<int32_t> rcs(S, COS_OK);
+    std::vector<std::string> errs(S);
+    auto run_shard = [&](u32 i) {
+        LocalShard &s = ss->sh[i];
+        const cos_scan_mask *m = a.masks ? a.masks[i] : nullptr;
+        int32_t rc = a.op == ShardOp::FILTERED ? search_filtered_record(s.ix, a.queries, B, a.f_off, a.f_dims, top_k, s.d_packed)
+                     : a.op == ShardOp::FLAT   ? flat_search_record(s.ix, a.queries, B, top_k, m, s.d_packed)
+                                               : bruteforce_record(s.ix, a.queries, B, top_k, m, s.d_packed);
+        if (rc == COS_OK && (hipSetDevice(s.device) != hipSuccess || hipEventRecord(s.done, s.stream) != hipSuccess))
+            rc = cos_fail(COS_ERR_HIP, "cannot record an event on device %d", s.device);
+        rcs[i] = rc;
+        if (rc) errs[i] = cos_last_error_string(); // (the message belongs to the thread that ran the shard)
+    };
+    // the shards grouped by device, in shard order
+    std::vector<std::vector<u32>> groups;
+    for (u32 i = 0; i < S; i++) {
+        size_t gi = 0;
+        while (gi < groups.size() && ss->sh[groups[gi][0]].device != ss->sh[i].device) gi++;
+        if (gi == groups.size()) groups.emplace_back();
+        groups[gi].push_back(i);
+    }
+    auto run_group = [&](const std::vector<u32> &grp) {
+        for (u32 i : grp) {
+            run_shard(i);
+            if (rcs[i]) break; // a failure ends the call: the device's later shards are not started
+        }
+    };
+    if (groups.size() == 1) run_group(groups[0]);
+    else {
+        std::vector<std::thread> threads;
+        for (size_t gi = 1; gi < groups.size(); gi++) threads.emplace_back(run_group, std::cref(groups[gi]));
+        run_group(groups[0]);
+        for (std::thread &t : threads) t.join();
+    }
+    for (u32 i = 0; i < S; i++) // the first failing shard, in shard order
+        if (rcs[i]) return cos_fail(rcs[i], "shard %u: %s", ss->first_rank + i, errs[i].c_str());
+    int32_t rc = exchange_merge_copy(ss, B, top_k, words, out_ids, out_scores, out_counts);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ss->sh[0].device));
+    HIP_TRY(hipStreamSynchronize(ss->sh[0].stream));
+    return COS_OK;
+}
+
+int32_t shardset_check(cos_shardset *ss, const void *queries, uint32_t B, uint32_t top_k, const void *o0, const void *o1, const void *o2, const char *name) {
+    if (!ss || !queries || !o0 || !o1 || !o2 || B == 0 || top_k == 0) return cos_fail(COS_ERR_INVALID, "bad argument");
+    if (ss->sh.size() != ss->world) return cos_fail(COS_ERR_INVALID, "%s needs every shard in this process", name);
+    return check_merge_width(ss->world, top_k);
+}
+} // namespace
+
+extern "C" int32_t cos_shardset_search_filtered_batch(cos_shardset *ss, const float *queries, uint32_t B, const uint32_t *filter_offsets,
+                                                      const int8_t *filter_dims, uint32_t top_k, uint32_t *out_ids, float *out_scores, uint32_t *out_counts) {
+    if (int32_t rc = shardset_check(ss, queries, B, top_k, out_ids, out_scores, out_counts, "cos_shardset_search_filtered_batch")) return rc;
+    if (!filter_offsets || !filter_dims) return cos_fail(COS_ERR_INVALID, "bad argument");
+    for (u32 i = 0; i < ss->world; i++) { // one schema: the filters are written once for every shard
+        const u32 md = ss->sh[i].ix->meta.mdim;
+        if (md == 0) return cos_fail(COS_ERR_NOT_READY, "shard %u is not a metadata collection", ss->first_rank + i);
+        if (md != ss->sh[0].ix->meta.mdim)
+            return cos_fail(COS_ERR_INVALID, "shard %u has %u metadata dimensions, shard %u has %u", ss->first_rank + i, md, ss->first_rank, ss->sh[0].ix->meta.mdim);
+    }
+    ShardOpArgs a{ShardOp::FILTERED, queries, B, top_k};
+    a.f_off = filter_offsets;
+    a.f_dims = filter_dims;
+    return shardset_run(ss, a, out_ids, out_scores, out_counts);
+}
+
+extern "C" int32_t cos_shardset_flat_search_batch(cos_shardset *ss, const float *queries, uint32_t B, uint32_t top_k, const cos_scan_mask *const *shard_masks,
+                                                  uint32_t *out_ids, float *out_scores, uint32_t *out_counts) {
+    if (int32_t rc = shardset_check(ss, queries, B, top_k, out_ids, out_scores, out_counts, "cos_shardset_flat_search_batch")) return rc;
+    ShardOpArgs a{ShardOp::FLAT, queries, B, top_k};
+    a.masks = shard_masks;
+    return shardset_run(ss, a, out_ids, out_scores, out_counts);
+}
+
+extern "C" int32_t cos_shardset_bruteforce_topk(cos_shardset *ss, const float *queries, uint32_t B, uint32_t k, const cos_scan_mask *const *shard_masks,
+                                                uint32_t *out_ids, float *out_scores, uint32_t *out_counts) {
+    if (int32_t rc = shardset_check(ss, queries, B, k, out_ids, out_scores, out_counts, "cos_shardset_bruteforce_topk")) return rc;
+    for (u32 i = 0; i < ss->world; i++) // every shard must hold k rows: a short list would not be the single-index call's answer
+        if (int32_t krc = flat_plan::check_brute_k(k, ss->sh[i].ix->n))
+            return cos_fail(krc, "shard %u holds %u rows: k must be in [1, min(512, smallest shard)]", ss->first_rank + i, ss->sh[i].ix->n);
+    ShardOpArgs a{ShardOp::BRUTE, queries, B, k};
+    a.masks = shard_masks;
+    return shardset_run(ss, a, out_ids, out_scores, out_counts);
 }

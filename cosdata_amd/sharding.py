@@ -21,6 +21,39 @@ def shard_range(n_total: int, world: int, rank: int):
     return lo, hi
 
 
+def slice_row_masks(bits, bounds):
+    """A packed mask over the GLOBAL rows of a sharded collection -> one packed mask per shard over the shard's OWN rows (what
+    cos_shardset_flat_search_batch / cos_shardset_bruteforce_topk take).  Pure numpy.
+    bits    uint32 [n_masks][>= ceil(N / 32)] (or one row), the layout of cos_scan_mask::bits: bit r % 32 of word r / 32 = global row r
+    bounds  [S + 1] ascending row numbers; shard s holds the global rows [bounds[s], bounds[s + 1]) and N = bounds[S]
+    -> list of S uint32 arrays [n_masks][ceil(n_s / 32)]: bit j of shard s = global bit bounds[s] + j; padding bits are 0, bits of the
+    input at or past N are ignored.  Shard boundaries are generally not multiples of 32, so a shard's words straddle the global ones."""
+    import numpy as np
+    b = np.atleast_2d(np.asarray(bits))
+    if b.dtype != np.uint32 or b.ndim != 2:
+        raise ValueError("bits must be uint32 [n_masks][words]")
+    bounds = [int(x) for x in bounds]
+    if len(bounds) < 2 or bounds[0] < 0 or any(hi < lo for lo, hi in zip(bounds, bounds[1:])):
+        raise ValueError("bounds must be ascending row numbers, at least two of them")
+    if b.shape[1] * 32 < bounds[-1]:
+        raise ValueError(f"the mask holds {b.shape[1] * 32} bits, the bounds end at row {bounds[-1]}")
+    G = b.shape[0]
+    src = np.zeros((G, b.shape[1] + 2), np.uint64)          # two zero words behind the end: the reads below never leave it
+    src[:, :b.shape[1]] = b
+    out = []
+    for lo, hi in zip(bounds, bounds[1:]):
+        n = hi - lo
+        words = (n + 31) // 32
+        w0, sh = lo // 32, lo % 32
+        lo_part = src[:, w0:w0 + words] >> np.uint64(sh)    # shard word j = global bits [lo + 32 j, lo + 32 j + 32)
+        hi_part = (src[:, w0 + 1:w0 + words + 1] << np.uint64(32 - sh)) & np.uint64(0xFFFFFFFF)   # (sh = 0: shifted out entirely)
+        m = ((lo_part | hi_part) & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+        if n % 32:                                          # the bits past the shard's last row belong to the next shard (or to nobody)
+            m[:, -1] &= np.uint32((1 << (n % 32)) - 1)
+        out.append(np.ascontiguousarray(m))
+    return out
+
+
 def allgather_topk(ids: torch.Tensor, scores: torch.Tensor, counts: torch.Tensor, out_ids=None, out_scores=None, out_counts=None):
     """ids/scores [B][k], counts [B] of this shard -> gathered [S][B][k], [S][B][k], [S][B] on every rank.
     Payload per rank: B*k*8 + B*4 bytes (20 KB at B=256, k=10): latency-bound, far below xGMI bandwidth."""
@@ -76,6 +109,22 @@ def merge_topk_packed_device(g_packed, B: int, k: int, out_ids, out_scores, out_
     S = g_packed.shape[0]
     _lib.check(_lib.lib().cos_merge_topk_packed_device(g_packed.data_ptr(), S, B, k, out_ids.data_ptr(), out_scores.data_ptr(),
                                                        out_counts.data_ptr(), device_index, stream))
+
+
+def merge_lists_device(g_ids, g_scores, g_counts, out_ids, out_scores, out_counts, device_index: int, stream: int = 0):
+    """merge_topk_device for up to 8192 keys per query (cos_merge_lists_device): S * k <= 1024 launches the same kernel, above it one
+    workgroup per query sorts the keys in LDS; the rule and the contract are the same."""
+    from . import _lib
+    S, B, k = g_ids.shape
+    _lib.check(_lib.lib().cos_merge_lists_device(g_ids.data_ptr(), g_scores.data_ptr(), g_counts.data_ptr(), S, B, k,
+                                                 out_ids.data_ptr(), out_scores.data_ptr(), out_counts.data_ptr(), device_index, stream))
+
+
+def merge_lists_packed_device(g_packed, B: int, k: int, out_ids, out_scores, out_counts, device_index: int, stream: int = 0):
+    from . import _lib
+    S = g_packed.shape[0]
+    _lib.check(_lib.lib().cos_merge_lists_packed_device(g_packed.data_ptr(), S, B, k, out_ids.data_ptr(), out_scores.data_ptr(),
+                                                        out_counts.data_ptr(), device_index, stream))
 
 
 def global_topk_by_score(ids_global: torch.Tensor, scores: torch.Tensor, k: int) -> torch.Tensor:

@@ -2,7 +2,8 @@
 
 ShardSet          every shard in this process (the reference's single-process host): batch_search() fans a query batch out to
                   the S resident shards and returns the merged global top-k — walk + rerank per shard, ONE all-gather of the
-                  packed records (RCCL), merge kernel; everything below the call is C++/HIP.
+                  packed records (RCCL), merge kernel; everything below the call is C++/HIP.  search_filtered(), flat_search() and
+                  bruteforce_topk() do the same with the index's other search operators (masks over the collection's GLOBAL rows).
 ProcessShardSet   one process per GPU (bench.py under torchrun): the process owns one shard; exchange_device() is the
                   per-launch all-gather + merge on the caller's stream.  torch.distributed is used ONLY to hand rank 0's
                   ncclUniqueId to the other ranks.
@@ -50,6 +51,83 @@ class ShardSet:
         counts = np.zeros(B, np.uint32)
         p = lambda a: a.ctypes.data_as(C.c_void_p)
         check(_lib.lib().cos_shardset_search_batch(self._h, p(q), B, top_k, p(ids), p(scores), p(counts)))
+        return ids, scores, counts
+
+    # ---- the other search operators of an index, on every shard behind one call ----------------------------------------------
+    def _outputs(self, queries, top_k: int):
+        q = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise CosdataError(_lib.ERR_INVALID, f"queries must be [B][{self.dim}] f32, got shape {tuple(q.shape)}")
+        B = q.shape[0]
+        return q, B, np.full((B, top_k), 0xFFFFFFFF, np.uint32), np.zeros((B, top_k), np.float32), np.zeros(B, np.uint32)
+
+    def row_bounds(self):
+        """[S + 1] global row numbers: shard s holds the rows [bounds[s], bounds[s + 1]) of the collection, in shard order"""
+        return np.concatenate([[0], np.cumsum([s.n for s in self.shards])]).astype(np.int64)
+
+    def _shard_masks(self, masks, query_mask, skip_deleted: bool, B: int):
+        """masks over GLOBAL rows (bool [N] or [G][N], or uint32 [G][ceil(N / 32)] packed) -> (cos_scan_mask*[S] or None, keep-alive)"""
+        from .index import pack_row_masks
+        from .sharding import slice_row_masks
+        if masks is None and query_mask is None and not skip_deleted:
+            return None, ()
+        bounds = self.row_bounds()
+        N, S = int(bounds[-1]), len(self.shards)
+        per_shard, qm = [None] * S, None
+        if masks is not None:
+            m = np.asarray(masks)
+            if m.dtype == np.uint32:
+                bits = np.ascontiguousarray(np.atleast_2d(m))
+                if bits.ndim != 2 or bits.shape[1] != (N + 31) // 32:
+                    raise CosdataError(_lib.ERR_INVALID, f"packed masks must be uint32 [G][{(N + 31) // 32}], got shape {tuple(bits.shape)}")
+            else:
+                m = np.atleast_2d(m.astype(bool))
+                if m.ndim != 2 or m.shape[1] != N:
+                    raise CosdataError(_lib.ERR_INVALID, f"masks must be bool [{N}] or [G][{N}] over the collection's rows, got shape {tuple(np.shape(masks))}")
+                bits = pack_row_masks(m)
+            per_shard = slice_row_masks(bits, bounds)
+        if query_mask is not None:
+            qm = np.ascontiguousarray(np.atleast_1d(query_mask), dtype=np.uint32)
+            if qm.shape != (B,):
+                raise CosdataError(_lib.ERR_INVALID, f"query_mask must hold {B} mask indices, got shape {tuple(qm.shape)}")
+        structs = [_lib.CosScanMask(C.sizeof(_lib.CosScanMask), _lib.SCAN_SKIP_DELETED if skip_deleted else 0,
+                                    b.shape[0] if b is not None else 0, b.ctypes.data if b is not None else None,
+                                    qm.ctypes.data if qm is not None else None) for b in per_shard]
+        arr = (C.POINTER(_lib.CosScanMask) * S)(*[C.pointer(s) for s in structs])
+        return arr, (structs, per_shard, qm)
+
+    def search_filtered(self, queries, filter_offsets, filter_dims, top_k: int):
+        """HNSWIndex.search_filtered on every shard (each a metadata collection, id_base = first embedding x max_replicas), merged:
+        (global replica ids [B][k], exact cosine scores, counts)"""
+        q, B, ids, scores, counts = self._outputs(queries, top_k)
+        off = np.ascontiguousarray(filter_offsets, dtype=np.uint32)
+        fd = np.ascontiguousarray(np.atleast_2d(filter_dims), dtype=np.int8)
+        mdim = self.shards[0].mdim
+        if off.shape != (B + 1,) or fd.ndim != 2 or fd.shape[1] != mdim or off[-1] != fd.shape[0]:
+            raise CosdataError(_lib.ERR_INVALID, f"filters must be [F][{mdim}] i8 with {B + 1} offsets ending at F")
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        check(_lib.lib().cos_shardset_search_filtered_batch(self._h, p(q), B, p(off), p(fd), top_k, p(ids), p(scores), p(counts)))
+        return ids, scores, counts
+
+    def flat_search(self, queries, top_k: int, masks=None, query_mask=None, skip_deleted: bool = False):
+        """HNSWIndex.flat_search / flat_search_masked on every shard, merged.  `masks` are over the GLOBAL rows of the collection (row r of
+        shard s is global row row_bounds()[s] + r) and are cut at the shard boundaries here; skip_deleted reads every shard's own deleted
+        set.  The 5 * top_k cut of the rerank is applied per shard."""
+        q, B, ids, scores, counts = self._outputs(queries, top_k)
+        sm, keep = self._shard_masks(masks, query_mask, skip_deleted, B)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        check(_lib.lib().cos_shardset_flat_search_batch(self._h, p(q), B, top_k, sm, p(ids), p(scores), p(counts)))
+        del keep
+        return ids, scores, counts
+
+    def bruteforce_topk(self, queries, k: int, masks=None, query_mask=None, skip_deleted: bool = False):
+        """HNSWIndex.bruteforce_topk / bruteforce_topk_masked on every shard, merged: the exact global top-k of the collection (ids and
+        score bits of one index holding every row).  k in [1, min(512, rows of the smallest shard)]; masks as in flat_search."""
+        q, B, ids, scores, counts = self._outputs(queries, k)
+        sm, keep = self._shard_masks(masks, query_mask, skip_deleted, B)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        check(_lib.lib().cos_shardset_bruteforce_topk(self._h, p(q), B, k, sm, p(ids), p(scores), p(counts)))
+        del keep
         return ids, scores, counts
 
 

@@ -759,6 +759,19 @@ int32_t cos_merge_topk_packed_device(const uint32_t *d_packed, uint32_t S, uint3
                                      uint32_t *d_out_ids, float *d_out_scores, uint32_t *d_out_counts,
                                      int32_t device, void *stream);
 
+/* The same two merges for up to 8192 keys per query (8 shards x brute-force k 512 = 4096, 8 x flat top_k 204 = 1632), under the same
+ * contract word for word: total_cmp score descending (+0.0 ahead of -0.0), larger id first; only the first counts[s][q] entries of a list
+ * are read; the lists may be in any order; out_counts[q] = min(sum of counts, k); output slots past the count are not written.
+ * S * k <= 1024 launches the kernel of cos_merge_topk_device (one wave per query, the keys in registers: the same bits); 1025 .. 8192 runs
+ * one workgroup per query with the keys in 2048, 4096 or 8192 words of LDS; S * k > 8192 is COS_ERR_UNIMPLEMENTED with nothing written.
+ * (cos_merge_topk_device / cos_merge_topk_packed_device keep refusing S * k > 1024.) */
+int32_t cos_merge_lists_device(const uint32_t *d_ids, const float *d_scores, const uint32_t *d_counts, uint32_t S,
+                               uint32_t B, uint32_t k, uint32_t *d_out_ids, float *d_out_scores,
+                               uint32_t *d_out_counts, int32_t device, void *stream);
+int32_t cos_merge_lists_packed_device(const uint32_t *d_packed, uint32_t S, uint32_t B, uint32_t k,
+                                      uint32_t *d_out_ids, float *d_out_scores, uint32_t *d_out_counts,
+                                      int32_t device, void *stream);
+
 /* ---- sharded serving --------------------------------------------------------- */
 /* A shard set = the S id-range shards of one collection (cos_index handles, cos_params.id_base = first id of the shard) plus
  * the exchange step between them: ONE all-gather of the packed per-shard records (RCCL over xGMI) and the S-way merge.
@@ -787,6 +800,35 @@ int32_t cos_shardset_search_batch(cos_shardset *ss, const float *queries, uint32
 int32_t cos_shardset_exchange_device(cos_shardset *ss, const uint32_t *d_packed_local, uint32_t B, uint32_t top_k,
                                      uint32_t *d_gathered, uint32_t *d_out_ids, float *d_out_scores, uint32_t *d_out_counts,
                                      void *stream);
+/* Both calls above merge with cos_merge_lists_packed_device: world_size * top_k <= 8192, otherwise COS_ERR_UNIMPLEMENTED.
+ *
+ * The other search operators of a cos_index on a shard set, in the shape of cos_shardset_search_batch: every shard runs the single-index
+ * operator (its own kernels, refusals and zero-norm rule) and leaves its packed record on its device, ONE exchange, ONE merge on shard 0's
+ * device, one copy back; under the set's lock, every shard in this process.  The first failing shard, in shard order, fails the call with
+ * its status (the message names the shard); S * top_k <= 8192, otherwise COS_ERR_UNIMPLEMENTED.  The exhaustive operators block their host
+ * thread (overflow retry, zero-norm read-back), so shards on different devices run from one host thread per device; shards that share a
+ * device run in turn.  The outputs are those of cos_shardset_search_batch: global ids, out_counts[q] = min(sum of the shards' counts, top_k).
+ *   cos_shardset_search_filtered_batch   cos_search_filtered_batch per shard (filters as there, one set for every shard): every shard is a
+ *       ready metadata collection (COS_ERR_NOT_READY) with the same number of metadata dimensions (COS_ERR_INVALID) and
+ *       id_base = first embedding x max_replicas.
+ *   cos_shardset_flat_search_batch       cos_flat_search_batch / cos_flat_search_masked_batch per shard.  Exhaustive per-shard mode: the
+ *       5 x top_k cut of the finalisation is applied PER SHARD, so the answer is the per-shard operator's answers under the merge rule — not
+ *       the answer of one index over the whole corpus, whose single cut keeps 5 x top_k candidates in all.
+ *   cos_shardset_bruteforce_topk         cos_bruteforce_topk / cos_bruteforce_topk_masked per shard; k in [1, min(512, rows of the smallest
+ *       shard)] (COS_ERR_INVALID).  The exact re-score is per row and every shard keeps a pool of at least 2k, so over the id-range shards
+ *       of a corpus this is the exact global top-k: ids and score bits of cos_bruteforce_topk on one index holding the whole corpus.
+ * shard_masks: NULL, or [S] pointers, entry s NULL (shard s unmasked) or a cos_scan_mask over shard s's OWN rows (bit r = row r of that
+ * shard, not a global id); COS_SCAN_SKIP_DELETED reads shard s's own deleted set.  Cutting a mask over global rows at the shard boundaries
+ * is the host's work (Python: cosdata_amd.sharding.slice_row_masks). */
+int32_t cos_shardset_search_filtered_batch(cos_shardset *ss, const float *queries, uint32_t B, const uint32_t *filter_offsets,
+                                           const int8_t *filter_dims, uint32_t top_k, uint32_t *out_ids, float *out_scores,
+                                           uint32_t *out_counts);
+int32_t cos_shardset_flat_search_batch(cos_shardset *ss, const float *queries, uint32_t B, uint32_t top_k,
+                                       const cos_scan_mask *const *shard_masks, uint32_t *out_ids, float *out_scores,
+                                       uint32_t *out_counts);
+int32_t cos_shardset_bruteforce_topk(cos_shardset *ss, const float *queries, uint32_t B, uint32_t k,
+                                     const cos_scan_mask *const *shard_masks, uint32_t *out_ids, float *out_scores,
+                                     uint32_t *out_counts);
 
 /* ---- tuning knobs (experiments; NOT a reference interface) ------------------------------------------------------------------
  * Launch-policy knobs of the kernels — which of two implementations of one operator runs, launch sizes at which a policy
