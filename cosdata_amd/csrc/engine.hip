@@ -756,6 +756,12 @@ static constexpr long long WALK_TABLE_EARLY_WGS_DEFAULT = 0;
 // The row level under the level table reads table columns for the neighbours that have a node one level up (walk_plan.h,
 // WalkPlan::up_table_level; tuning knob walk_up_table).
 static constexpr long long WALK_UP_TABLE_DEFAULT = 1;
+// The throughput kernel's launches read the nested level table, one GEMM column per vector of the lowest table level (table_nested.h,
+// ensure_nested_table; tuning knob walk_table_nested): 1 = on graphs where that saves TABLE_NESTED_MIN_SAVED_COLS columns or more.
+static constexpr long long WALK_TABLE_NESTED_DEFAULT = 1;
+static u32 walk_table_nested_mode() {
+    return (u32)std::min<long long>(std::max<long long>(cosdev::tune_or(cosdev::TUNE_WALK_TABLE_NESTED, WALK_TABLE_NESTED_DEFAULT), 0), 2);
+}
 // the handle as walk_plan (walk_plan.h) sees it: shape, every knob resolved (the tuning registry's overrides included), a launch of B
 // queries at beam width ef that takes part in the walk chain.  Caller holds ix->mu where the handle is shared.
 cosdev::WalkPlanIn cos_walk_plan_in(const cos_index *ix, u32 B, u32 ef) {
@@ -789,9 +795,10 @@ cosdev::WalkPlanIn cos_walk_plan_in(const cos_index *ix, u32 B, u32 ef) {
     in.table_early_wgs = (u32)std::min<long long>(std::max<long long>(cosdev::tune_or(cosdev::TUNE_WALK_TABLE_EARLY_WGS, WALK_TABLE_EARLY_WGS_DEFAULT), 0), 0xFFFFFFFFll);
     in.table_queue = cosdev::level_table_gemm_queue(ix->eng, ix->row_stride);
     in.n_cus = ix->n_cus;
+    in.table_nested_mode = walk_table_nested_mode();
     return in;
 }
-static int32_t ensure_level_table(cos_index *ix) {
+static int32_t ensure_per_level_table(cos_index *ix) {
     const u32 max_cols = walk_table_max_cols(ix);
     // Which levels pay.  A table column costs one GEMM column per launch (~2.6 ps per query and column at K = 1024), a level walked
     // from rows costs ~0.11 ns per evaluation, and a level's walk evaluates 0.2-0.4 x ef x M rows per query: a level of n nodes pays
@@ -883,6 +890,114 @@ static int32_t ensure_level_table(cos_index *ix) {
     return COS_OK;
 }
 
+// The NESTED operand of the current table levels (table_nested.h): one column per node of the lowest table level, in nested order, kept
+// in table_sets beside the per-level set under a key of its own, and LevelDev::adj_tab of every table level filled for it.  Caller holds
+// ix->mu, right after ensure_per_level_table.  Leaves cos_index::table_nested_idx: the set the throughput kernel's launches use, or -1 —
+// the knob, a storage other than u8, a metadata schema, a graph whose packed words do not fit 32 bits or whose levels are not nested,
+// too few columns saved (knob 1), out of memory: every launch then reads the per-level set exactly as before (same results either way).
+static int32_t ensure_nested_table(cos_index *ix) {
+    const u32 mode = walk_table_nested_mode();
+    ix->table_nested_idx = -1;
+    if (mode == 0 || !ix->level_table_valid || ix->table_level_min == 0 || ix->eng != ENG_U8 || ix->meta.mdim != 0u) return COS_OK;
+    if (ix->G == 0u || ix->nchunks > ix->G) return COS_OK; // rows of more than one chunk pass: walk_kernel's nested rounds do not exist there (walk_plan.h)
+    const u32 lmin = ix->table_level_min, Ltop = ix->p.num_layers;
+    if (mode == 1 && ix->table_cols - ix->lv[lmin].n < cosdev::TABLE_NESTED_MIN_SAVED_COLS) return COS_OK;
+    const u64 nkey = ix->table_built_for_key | cos_index::TABLE_NESTED_KEY;
+    if (ix->table_nested_failed_key == nkey) return COS_OK;
+    auto go_without = [&](hipError_t e) -> int32_t { // like the per-level operand: short of HBM the launch does without, anything else is reported
+        (void)hipDeviceSynchronize();
+        if (e == hipErrorOutOfMemory) {
+            (void)hipGetLastError();
+            return COS_OK;
+        }
+        HIP_TRY(e);
+        return COS_OK;
+    };
+    int idx = -1;
+    for (size_t i = 0; i < ix->table_sets.size(); i++)
+        if (ix->table_sets[i].key == nkey) idx = (int)i;
+    if (idx < 0) {
+        HIP_TRY(hipDeviceSynchronize()); // a build or an upload on another stream may still be writing the levels
+        std::vector<u32> n(Ltop + 1, 0u);
+        std::vector<std::vector<u32>> child(Ltop + 1);
+        for (u32 l = lmin; l <= Ltop; l++) {
+            n[l] = ix->lv[l].n;
+            if (l == lmin) continue;
+            if (!ix->lv[l].d_child) { ix->table_nested_failed_key = nkey; return COS_OK; }
+            child[l].resize(n[l]);
+            HIP_TRY(hipMemcpy(child[l].data(), ix->lv[l].d_child, (size_t)n[l] * 4, hipMemcpyDeviceToHost));
+        }
+        cosdev::NestedTable nt;
+        if (!cosdev::table_nested_columns(lmin, Ltop, n, child, &nt)) { ix->table_nested_failed_key = nkey; return COS_OK; }
+        // the gather's index list: vector row of every column
+        std::vector<u32> rows(nt.cols), node_vec(nt.cols);
+        HIP_TRY(hipMemcpy(node_vec.data(), ix->lv[lmin].d_node_vec, (size_t)nt.cols * 4, hipMemcpyDeviceToHost));
+        for (u32 c = 0; c < nt.cols; c++) rows[c] = node_vec[nt.col_node[c]];
+        cos_index::TableSet t;
+        DevArr<u32> d_rows;
+        auto build = [&]() -> hipError_t {
+            hipError_t e = t.tcodes.alloc((size_t)nt.cols * ix->row_stride);
+            if (e == hipSuccess) e = t.tmags.alloc(nt.cols);
+            if (e == hipSuccess) e = t.tcsums.alloc(nt.cols);
+            if (e == hipSuccess) e = d_rows.alloc(nt.cols);
+            if (e == hipSuccess) e = hipMemcpy(d_rows, rows.data(), (size_t)nt.cols * 4, hipMemcpyHostToDevice);
+            if (e == hipSuccess) e = cosdev::launch_level_table_gather(ix->d_codes, ix->d_mags, ix->row_stride, d_rows, nt.cols, 0u, t.tcodes, t.tmags, nullptr);
+            if (e == hipSuccess) e = cosdev::launch_code_sums(t.tcodes, ix->row_stride, nt.cols, t.tcsums, nullptr);
+            for (u32 l = lmin; l <= Ltop && e == hipSuccess; l++) {
+                e = t.tab_col[l].alloc(n[l]);
+                if (e == hipSuccess) e = hipMemcpy(t.tab_col[l], nt.col[l - lmin].data(), (size_t)n[l] * 4, hipMemcpyHostToDevice);
+                t.node_bits[l] = nt.node_bits[l - lmin];
+            }
+            if (e == hipSuccess) e = hipDeviceSynchronize();
+            return e;
+        };
+        if (const hipError_t e = build(); e != hipSuccess) {
+            ix->table_nested_failed_key = e == hipErrorOutOfMemory ? nkey : 0;
+            return go_without(e);
+        }
+        t.key = nkey;
+        t.level_min = lmin;
+        t.cols = nt.cols;
+        t.stride = ((u64)nt.cols + 31) / 32 * 32;
+        memset(t.col0, 0, sizeof(t.col0));
+        ix->table_sets.push_back(std::move(t));
+        idx = (int)ix->table_sets.size() - 1;
+    }
+    if (ix->adj_tab_key != nkey) { // a new graph or key, or the adjacency changed under a table that stayed (cos_index_delete): refill
+        if (ix->adj_tab_oom_key == nkey) return COS_OK;
+        HIP_TRY(hipDeviceSynchronize()); // (a launch in flight may still read the arrays that go; the adjacency may still be written)
+        ix->adj_tab_key = 0;
+        for (u32 l = 0; l <= ix->p.num_layers; l++) ix->lv[l].d_adj_tab.reset();
+        const cos_index::TableSet &t = ix->table_sets[(size_t)idx];
+        hipError_t e = hipSuccess;
+        for (u32 l = lmin; l <= Ltop && e == hipSuccess; l++) {
+            LevelHost &H = ix->lv[l];
+            if (!H.d_adj_node) e = hipErrorInvalidValue;
+            if (e == hipSuccess) e = H.d_adj_tab.alloc((size_t)H.n * H.M);
+            if (e == hipSuccess) e = cosdev::launch_fill_adj_tab(H.d_adj_node, t.tab_col[l], H.n, H.M, t.node_bits[l], H.d_adj_tab, ix->own_stream);
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(ix->own_stream);
+        if (e != hipSuccess) {
+            for (u32 l = 0; l <= ix->p.num_layers; l++) ix->lv[l].d_adj_tab.reset();
+            if (e == hipErrorOutOfMemory) ix->adj_tab_oom_key = nkey;
+            return go_without(e);
+        }
+        ix->adj_tab_key = nkey;
+    }
+    ix->table_nested_idx = idx;
+    return COS_OK;
+}
+
+static int32_t ensure_level_table(cos_index *ix) {
+    if (!ix->level_table_valid) { // a new graph: its nested set goes with the others
+        ix->table_nested_idx = -1;
+        ix->table_nested_failed_key = 0;
+        ix->adj_tab_key = ix->adj_tab_oom_key = 0;
+    }
+    if (int32_t rc = ensure_per_level_table(ix)) return rc;
+    return ensure_nested_table(ix);
+}
+
 extern "C" int32_t cos_index_set_walk_table(cos_index *ix, uint32_t max_cols, uint32_t min_queries) {
     if (!ix) return cos_fail(COS_ERR_INVALID, "null argument");
     if (max_cols > (1u << 20) && max_cols != COS_WALK_TABLE_AUTO) return cos_fail(COS_ERR_INVALID, "max_cols must be <= 2^20 (or COS_WALK_TABLE_AUTO)");
@@ -902,7 +1017,7 @@ extern "C" int32_t cos_index_walk_table_info(cos_index *ix, uint32_t *out_level_
     if (walk_table_min_B(ix) == 0) return COS_OK;
     if ((rc = ensure_level_table(ix))) return rc;
     *out_level_min = ix->table_level_min;
-    *out_cols = ix->table_cols;
+    *out_cols = ix->table_nested_idx >= 0 ? ix->table_sets[(size_t)ix->table_nested_idx].cols : ix->table_cols; // what the next big launch computes
     return COS_OK;
 }
 
@@ -946,7 +1061,10 @@ static int32_t ensure_adj_up(cos_index *ix) {
                       cosdev::tune_or(cosdev::TUNE_WALK_UP_TABLE, WALK_UP_TABLE_DEFAULT) != 0)
                          ? ix->table_level_min - 1u
                          : 0u;
-    if (want != 0u && (ix->adj_up_level == want || ix->adj_up_oom_level == want)) return COS_OK; // filled for this graph and rule, or known not to fit
+    // With the nested table (ensure_nested_table has settled it) the entries hold the COLUMN of the node one level up, which is what the
+    // throughput kernel — the array's only reader — then indexes the table with; a change of form refills like a change of level.
+    const bool nested = ix->table_nested_idx >= 0;
+    if (want != 0u && ((ix->adj_up_level == want && ix->adj_up_nested == nested) || ix->adj_up_oom_level == want)) return COS_OK; // filled for this graph and rule, or known not to fit
     bool any = false;
     for (u32 l = 0; l <= ix->p.num_layers; l++) any = any || ix->lv[l].d_adj_up;
     if (any) {
@@ -971,9 +1089,11 @@ static int32_t ensure_adj_up(cos_index *ix) {
         return COS_OK;
     }
     HIP_TRY(e);
-    HIP_TRY(cosdev::launch_fill_adj_up(H.d_adj_vec, H.d_adj_node, ix->d_mags, U.d_child, U.n, up, H.d_adj_up, H.n, H.M, slots, ix->own_stream));
+    const u32 *up_col = nested ? ix->table_sets[(size_t)ix->table_nested_idx].tab_col[want + 1].p : nullptr;
+    HIP_TRY(cosdev::launch_fill_adj_up(H.d_adj_vec, H.d_adj_node, ix->d_mags, U.d_child, U.n, up, H.d_adj_up, H.n, H.M, slots, ix->own_stream, up_col));
     HIP_TRY(hipStreamSynchronize(ix->own_stream));
     ix->adj_up_level = want;
+    ix->adj_up_nested = nested;
     return COS_OK;
 }
 
@@ -1017,6 +1137,9 @@ struct SearchLaunch {
     const uint8_t *tcodes = nullptr;
     const float *tmags = nullptr;
     const u32 *tcsums = nullptr;
+    // ... of the nested table (plan.table_nested): LevelDev::adj_tab / tab_col / tab_bits of its levels
+    const u32 *adj_tab[cosdev::MAX_LEVELS] = {}, *tab_col[cosdev::MAX_LEVELS] = {};
+    u32 tab_bits[cosdev::MAX_LEVELS] = {};
     // the order keys (plan.ordered)
     u32 n_keys = 0, key_level[cosdev::MAX_LEVELS], key_n[cosdev::MAX_LEVELS];
     const u32 *order_rank[cosdev::MAX_LEVELS];
@@ -1078,10 +1201,21 @@ static int32_t get_workspace(cos_index *ix, void *key, hipStream_t st, u32 B, u3
         have.order_level0 = have.n_order_keys ? ix->order_levels[0] : 0u;
     }
     if (want.prepare_table) {
+        bool nested = false;
         if (int32_t rc = ensure_level_table(ix)) return rc;
         if (int32_t rc = ensure_adj_up(ix)) return rc; // (nothing to do unless the table rule, the knob or the norms changed since the commit)
         have.adj_up_level = ix->adj_up_level;
-        const size_t need = (size_t)w->capB * ix->table_stride;
+        have.adj_up_nested = ix->adj_up_nested;
+        // the set this launch reads: the nested one where the handle has it and the kernel that walks is the throughput kernel
+        // (settled below by the same rule); its buffer is sized by ITS stride
+        const cos_index::TableSet *nset = ix->table_nested_idx >= 0 ? &ix->table_sets[(size_t)ix->table_nested_idx] : nullptr;
+        have.nested_cols = nset ? nset->cols : 0u;
+        have.table_level_min = ix->level_table_valid ? ix->table_level_min : 0u;
+        have.table_cols = ix->table_cols;
+        have.table_buffer = true;
+        nested = cosdev::walk_plan(in, &have).table_nested;
+        const u64 table_stride = nested ? nset->stride : ix->table_stride;
+        const size_t need = (size_t)w->capB * table_stride;
         if (need > w->tab.cap) {
             // every workspace (one per caller stream, up to five per leased host pipe) holds the table of its own launch in flight:
             // a handle's tables together stay under a budget (tuning knob walk_table_max_bytes, default 48 GiB) — a workspace that would
@@ -1099,12 +1233,22 @@ static int32_t get_workspace(cos_index *ix, void *key, hipStream_t st, u32 B, u3
                     HIP_TRY(e);
             }
         }
-        have.table_level_min = ix->level_table_valid ? ix->table_level_min : 0u;
-        have.table_cols = ix->table_cols;
-        have.table_buffer = w->tab && (size_t)B * ix->table_stride <= w->tab.cap;
+        have.table_buffer = w->tab && (size_t)B * table_stride <= w->tab.cap;
     }
     L->plan = cosdev::walk_plan(in, &have);
-    if (L->plan.use_table) {
+    if (L->plan.use_table && L->plan.table_nested) {
+        const cos_index::TableSet &t = ix->table_sets[(size_t)ix->table_nested_idx];
+        L->tab_stride = t.stride;
+        memcpy(L->tab_col0, t.col0, sizeof(L->tab_col0)); // all zero: a level's columns are a prefix of the table
+        L->tcodes = t.tcodes;
+        L->tmags = t.tmags;
+        L->tcsums = t.tcsums;
+        for (u32 l = t.level_min; l <= ix->p.num_layers; l++) {
+            L->adj_tab[l] = ix->lv[l].d_adj_tab;
+            L->tab_col[l] = t.tab_col[l];
+            L->tab_bits[l] = t.node_bits[l];
+        }
+    } else if (L->plan.use_table) {
         L->tab_stride = ix->table_stride;
         memcpy(L->tab_col0, ix->table_col0, sizeof(L->tab_col0));
         L->tcodes = ix->d_tcodes;
@@ -1149,6 +1293,12 @@ static int32_t run_search(cos_index *ix, Workspace *w, const SearchLaunch &L, co
         if (!((plan.use_adj_mag >> l) & 1u)) dev.lv[l].adj_mag = nullptr;
     for (u32 l = 0; l <= dev.num_layers; l++)
         if (plan.up_table_level != l || l == 0u || dev.lv[l].adj_mag == nullptr) dev.lv[l].adj_up = nullptr;
+    if (plan.use_table && plan.table_nested) // (cos_make_index_dev leaves these null: every other launch reads adj_node)
+        for (u32 l = plan.table_level_min; l <= dev.num_layers; l++) {
+            dev.lv[l].adj_tab = L.adj_tab[l];
+            dev.lv[l].tab_col = L.tab_col[l];
+            dev.lv[l].tab_bits = L.tab_bits[l];
+        }
     WalkArgs wa;
     memset(&wa, 0, sizeof(wa));
     if (dev.visited_mode == COS_VISITED_EXACT) {

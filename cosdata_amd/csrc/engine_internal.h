@@ -17,6 +17,7 @@
 #include "link_types.h"
 #include "dev_mem.h"
 #include "walk_plan.h"
+#include "table_nested.h"
 
 namespace cosdev {
 hipError_t launch_fill_i32(int32_t *p, u64 n, int32_t v, hipStream_t st);
@@ -33,7 +34,8 @@ hipError_t launch_grow_tail(const u32 *src, u32 *dst, u32 old_n, u32 tail_first,
 hipError_t launch_grow_tail_bytes(const uint8_t *src, uint8_t *dst, u32 old_n, u32 tail_first, u32 add, uint8_t fill, hipStream_t st);
 hipError_t launch_fill_adj_mag(const u32 *adj_vec, const float *mags, float *adj_mag, u32 n, u32 M, u32 slots, hipStream_t st);
 hipError_t launch_fill_adj_up(const u32 *adj_vec, const u32 *adj_node, const float *mags, const u32 *child_up, u32 n_up, u32 *up, AdjUp *adj_up, u32 n, u32 M, u32 slots,
-                              hipStream_t st);
+                              hipStream_t st, const u32 *up_col = nullptr);
+hipError_t launch_fill_adj_tab(const u32 *adj_node, const u32 *tab_col, u32 n, u32 M, u32 node_bits, u32 *adj_tab, hipStream_t st);
 hipError_t launch_link_round(const LinkArgs &a, u32 maxM, const u32 *pend, const u32 *pcount, u32 *next, u32 *next_count, u32 *evq, u32 *evq_count,
                              u32 count_ub, u32 round, hipStream_t st);
 hipError_t launch_quantize_rows(int eng, const float *x, u64 x_stride, u32 n, u32 dim, float lo, float hi, uint8_t *codes,
@@ -102,12 +104,13 @@ struct LevelHost {
     DevArr<u32> d_node_id, d_node_meta; // pseudo-root component only (metadata-filtered search)
     DevArr<float> d_adj_mag; // [n][min(M, shortlist)] norms of the scanned neighbour slots (LevelDev::adj_mag), valid while cos_index::adj_mag_valid
     DevArr<cosdev::AdjUp> d_adj_up; // same shape: the neighbours' norms and nodes one level up (LevelDev::adj_up); only level cos_index::adj_up_level has it
+    DevArr<u32> d_adj_tab;   // [n][M] node | nested-table column of every neighbour slot (LevelDev::adj_tab); the table levels of cos_index::adj_tab_key have it
     u32 n = 0, M = 0;
     u32 root_idx = 0;        // pseudo-root component: node index of the pseudo root (base graph: the root is the last node)
     bool host_valid = false; // node_ids/nbr_ids mirror the device arrays
     void release() { // the level's device arrays and host mirrors (M stays)
         d_adj_vec.reset(); d_adj_node.reset(); d_node_vec.reset(); d_child.reset();
-        d_node_id.reset(); d_node_meta.reset(); d_adj_mag.reset(); d_adj_up.reset();
+        d_node_id.reset(); d_node_meta.reset(); d_adj_mag.reset(); d_adj_up.reset(); d_adj_tab.reset();
         n = 0;
         node_ids.clear();
         nbr_ids.clear();
@@ -326,7 +329,11 @@ struct cos_index {
     // for), and the level an allocation ran out of memory for (0 = none): that graph and rule go without, it is not tried again
     // until either changes.  Both fall with adj_mag_valid (invalidate_adj_side) — the array follows the graph exactly like the norms.
     u32 adj_up_level = 0, adj_up_oom_level = 0;
-    void invalidate_adj_side() { adj_mag_valid = false; adj_up_level = 0; adj_up_oom_level = 0; }
+    bool adj_up_nested = false;      // ... and its entries hold columns of the nested table (ensure_adj_up), not node indices
+    // LevelHost::d_adj_tab of the table levels: the key of the nested table set it is filled for (0 = none), and the key an allocation
+    // ran out of memory for (that graph and key walk on the per-level table).  Falls with the other two side arrays.
+    u64 adj_tab_key = 0, adj_tab_oom_key = 0;
+    void invalidate_adj_side() { adj_mag_valid = false; adj_up_level = 0; adj_up_oom_level = 0; adj_tab_key = 0; adj_tab_oom_key = 0; }
     LinkState link;                  // cos_index_build -> cos_index_append (builder.hip); dropped with the graph
     bool level_table_valid = false;  // the arrays below follow the graph and walk_table_max_cols
     u32 table_level_min = 0, table_cols = 0;
@@ -338,8 +345,16 @@ struct cos_index {
     const u32 *d_tcsums = nullptr;   // [table_cols]
     // operands built for other keys of the SAME graph (ef_search changes re-select the table's levels while searches of the previous
     // ef may still be in flight: nothing a launch may be reading is freed before the graph itself is replaced)
-    struct TableSet { u64 key; u32 level_min, cols; u64 stride; u32 col0[cosdev::MAX_LEVELS]; DevArr<uint8_t> tcodes; DevArr<float> tmags; DevArr<u32> tcsums; };
+    // A NESTED set (table_nested.h; key = the per-level set's | TABLE_NESTED_KEY) has one column per node of level_min, col0 all zero, and
+    // per table level the node -> column array and the node bits of LevelDev::adj_tab's words.
+    struct TableSet { u64 key; u32 level_min, cols; u64 stride; u32 col0[cosdev::MAX_LEVELS]; DevArr<uint8_t> tcodes; DevArr<float> tmags; DevArr<u32> tcsums;
+                      DevArr<u32> tab_col[cosdev::MAX_LEVELS]; u32 node_bits[cosdev::MAX_LEVELS] = {}; };
     std::vector<TableSet> table_sets;
+    static constexpr u64 TABLE_NESTED_KEY = 1ull << 62;
+    // the nested set of the current (graph, key) that the throughput kernel's launches use: index into table_sets, -1 = none (knob, rule,
+    // a graph whose words do not fit, out of memory); the key it was last settled for together with the knob's value
+    int table_nested_idx = -1;
+    u64 table_nested_failed_key = 0; // this (graph, key) has no nested set and is not tried again
     u32 walk_side_min_B = 4096; // launches of at least this many queries walk on the workspace's low-priority stream; 0 = never
     // launches of at most this many queries run the latency variant of the walk (kernels_walk_lat.hip) where it applies; 0 = never
     u32 lat_max_B = COS_LATENCY_MODE_DEFAULT_MAX_B;

@@ -22,6 +22,7 @@ struct LevelDev {
     // gathers mags[] as before.  Same values, same bits.
     const float *adj_mag;
     u32 mag_stride;
+    u32 tab_bits; // adj_tab: bits of the node index in a word (bits(n - 1)); sits in what was padding
     // The node index ONE LEVEL UP of every scanned neighbour slot, same shape and index as adj_mag: adj_up[node * mag_stride + slot].up =
     // the node of level l + 1 whose child link is the neighbour in that slot, ADJ_UP_NONE where the neighbour has no node there or the
     // slot is empty.  Only the row level directly under the level table has it (WalkPlan::up_table_level): a winner with a node one
@@ -37,6 +38,14 @@ struct LevelDev {
     // pseudo-root component (metadata-filtered search): nodes are replicas, not vectors
     const u32 *node_id;   // [n] internal (replica) id of a node; nullptr on the base graph (id = vector row * id_stride)
     const u32 *node_meta; // [n] row of the node's metadata dimensions in IndexDev::mbits
+    // Table levels of a launch on the NESTED level table (table_nested.h, WalkPlan::table_nested; walk_kernel only): shaped like adj_node,
+    // adj_tab[node * M + slot] = adj_node's node | its table column << tab_bits, the empty marker kept — a table level's walk loads it
+    // WHERE it loaded adj_node (same two loads per window entry, same bytes) and has the winner's column without a load of its own.
+    // tab_col: [n] node -> column, for the level's start node (one wave-uniform load per level).  A side array like adj_mag and adj_up:
+    // filled where the table's operand is (engine.hip ensure_nested_table), invalidated with them.  nullptr on every other level and launch;
+    // with the nested table adj_up.up of the level under it holds the COLUMN of the node one level up (WalkArgs::tab_col0 is all zero).
+    const u32 *adj_tab;
+    const u32 *tab_col;
 };
 
 struct IndexDev {

@@ -477,6 +477,21 @@ __global__ void scatter_up_kernel(const u32 *__restrict__ child_up, u32 n_up, u3
         if (c < n) up[c] = (u32)j;
     }
 }
+// (nested level table: the node one level up gives way to its table column, up_col[node of level l + 1])
+__global__ void map_up_col_kernel(u32 *__restrict__ up, u32 n, const u32 *__restrict__ up_col, u32 n_up) {
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
+        const u32 j = up[i];
+        if (j < n_up) up[i] = up_col[j];
+    }
+}
+// LevelDev::adj_tab (engine_types.h) of a table level: adj_node's node with its nested-table column above it; the empty marker (any value
+// that is no node of the level) stays what it is
+__global__ void fill_adj_tab_kernel(const u32 *__restrict__ adj_node, const u32 *__restrict__ tab_col, u32 n, u32 node_bits, u32 *__restrict__ adj_tab, u64 total) {
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (u64)gridDim.x * blockDim.x) {
+        const u32 v = adj_node[i];
+        adj_tab[i] = v < n ? (v | (tab_col[v] << node_bits)) : v;
+    }
+}
 // ... then, per scanned slot, the entry of the neighbour's node (adj_node: node indices of level l, l >= 1)
 // with the neighbour's norm beside it (the value fill_adj_mag_kernel writes)
 __global__ void fill_adj_up_kernel(const u32 *__restrict__ adj_vec, const u32 *__restrict__ adj_node, const float *__restrict__ mags, const u32 *__restrict__ up, u32 n,
@@ -547,15 +562,24 @@ hipError_t launch_fill_adj_mag(const u32 *adj_vec, const float *mags, float *adj
     return hipGetLastError();
 }
 
-// `up`: [n] scratch (overwritten); child_up: the child links of the n_up nodes of the level above
+// `up`: [n] scratch (overwritten); child_up: the child links of the n_up nodes of the level above; up_col: nullptr, or the nested level
+// table's column of every node of the level above — the entries then hold that column instead of the node
 hipError_t launch_fill_adj_up(const u32 *adj_vec, const u32 *adj_node, const float *mags, const u32 *child_up, u32 n_up, u32 *up, AdjUp *adj_up, u32 n, u32 M, u32 slots,
-                              hipStream_t st) {
+                              hipStream_t st, const u32 *up_col) {
     const u64 total = (u64)n * slots;
     if (total == 0 || n_up == 0) return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(up, 0xFF, (size_t)n * sizeof(u32), st); // = ADJ_UP_NONE
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(scatter_up_kernel, dim3((u32)std::min<u64>(((u64)n_up + 255) / 256, 1u << 20)), dim3(256), 0, st, child_up, n_up, up, n);
+    if (up_col) hipLaunchKernelGGL(map_up_col_kernel, dim3((u32)std::min<u64>(((u64)n + 255) / 256, 1u << 20)), dim3(256), 0, st, up, n, up_col, n_up);
     hipLaunchKernelGGL(fill_adj_up_kernel, dim3((u32)std::min<u64>((total + 255) / 256, 1u << 20)), dim3(256), 0, st, adj_vec, adj_node, mags, up, n, adj_up, total, M, slots);
+    return hipGetLastError();
+}
+
+hipError_t launch_fill_adj_tab(const u32 *adj_node, const u32 *tab_col, u32 n, u32 M, u32 node_bits, u32 *adj_tab, hipStream_t st) {
+    const u64 total = (u64)n * M;
+    if (total == 0) return hipSuccess;
+    hipLaunchKernelGGL(fill_adj_tab_kernel, dim3((u32)std::min<u64>((total + 255) / 256, 1u << 20)), dim3(256), 0, st, adj_node, tab_col, n, node_bits, adj_tab, total);
     return hipGetLastError();
 }
 

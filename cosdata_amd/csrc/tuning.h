@@ -49,6 +49,7 @@ enum TuneKey : int {
     TUNE_FLAT_FP4_W8,         // the FP4 scan of 768-dim quaternary codes: 0 = one wave per SIMD (flat_scan_q2_fp4), 1..4 = two waves per SIMD, flat_scan_q2_fp4_w8<ORDER = value - 1> (default 4: even deal, alternating accumulators, 128-column tiles)
     TUNE_WALK_TABLE_EARLY_WGS, // workgroups of the EARLY part of a gated level-table GEMM, issued behind the previous chained walk's upper range (walk_plan.h); 0 = one launch behind its order sort (default: WALK_TABLE_EARLY_WGS_DEFAULT, engine.hip)
     TUNE_WALK_UP_TABLE,       // the row level directly under the level table reads table columns for neighbours that have a node one level up (LevelDev::adj_up): 0 = never, 1 = where that level reads its norms beside the adjacency (walk_adj_mag's rule), 2 = at every ef and launch size (tests); default WALK_UP_TABLE_DEFAULT, engine.hip
+    TUNE_WALK_TABLE_NESTED,   // the throughput kernel's level table holds one column per vector of its lowest level, in nested order (table_nested.h), and its table levels read LevelDev::adj_tab: 0 = never, 1 = on graphs where that saves TABLE_NESTED_MIN_SAVED_COLS columns or more, 2 = on every graph (tests); default WALK_TABLE_NESTED_DEFAULT, engine.hip
     TUNE_COUNT
 };
 

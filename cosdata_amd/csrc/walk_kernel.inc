@@ -154,7 +154,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH >= 3 ? (R
             float s0;
             if (tab_level) { // the table holds the integer dot `as f32`: the same product and quotient as single_distance
                 bool bad;
-                s0 = cosine_or_dot(metric, uniform_f32(tabq[entry]), qmag, uniform_f32(tabm[entry]), bad);
+                // (nested table, LevelDev::adj_tab: the start node's column from the level's node -> column array, once per level)
+                u32 ecol = entry;
+                if constexpr (ENG == ENG_U8 && CH == 1 && R <= 4) {
+                    if (lv.adj_tab != nullptr) ecol = uniform_u32(lv.tab_col[entry]);
+                }
+                s0 = cosine_or_dot(metric, uniform_f32(tabq[ecol]), qmag, uniform_f32(tabm[ecol]), bad);
                 if (bad) { status = COS_ERR_CALCULATION; break; }
             } else if (!single_distance(erow, s0)) { status = COS_ERR_CALCULATION; break; }
             if (lane == 0) {
@@ -183,8 +188,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH >= 3 ? (R
         // ... and a row level a THIRD time where it is the level directly under the table and has LevelDev::adj_up (UPT): u8 codes on the
         // one-row-per-pass path, every CH, both filters, both metrics.  Quaternary codes keep the AMAG variant.  The variant is taken once
         // per level, so every other level runs the instruction stream it ran before.
-        auto level_rounds = [&](auto tabc, auto cosc, auto amagc, auto upc) __attribute__((always_inline)) {
+        // ... and a table level a second time where the launch reads the NESTED table (LevelDev::adj_tab, `NEST`): u8 codes only.  The window
+        // loads adj_tab where it loaded adj_node, and an expansion splits the word into node and column; everything after the gather is the
+        // same code.  Taken once per level, like UPT.
+        auto level_rounds = [&](auto tabc, auto cosc, auto amagc, auto upc, auto nestc) __attribute__((always_inline)) {
         constexpr bool TAB = decltype(tabc)::value;
+        constexpr bool NEST = decltype(nestc)::value && TAB && ENG == ENG_U8 && CH == 1 && R <= 4; // nb_node arrives as node | column << tab_bits
+        const u32 nest_bits = NEST ? lv.tab_bits : 0u;
         constexpr bool COSINE = decltype(cosc)::value;       // table levels of a cosine index: the metric tests fold away
         constexpr bool AMAG = decltype(amagc)::value && G64 && !FLOAT_ENG; // row levels, one-row-per-pass path: norms beside the adjacency
         constexpr bool UPT = decltype(upc)::value && AMAG && !TAB && ENG == ENG_U8; // ... and table columns for the neighbours with a node one level up
@@ -226,7 +236,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH >= 3 ? (R
                         const u32 nd = pool.template peek_node<i>();
                         const u64 off = ((u64)nd << log2M) + slot_l;
                         wv_[i] = lv.adj_vec[off];
-                        if constexpr (BOTH) wn_[i] = lv.adj_node[off];
+                        if constexpr (BOTH) wn_[i] = NEST ? lv.adj_tab[off] : lv.adj_node[off];
                         if constexpr (!TAB && AMAG && !UPT) wm_[i] = lv.adj_mag[(u64)nd * lv.mag_stride + slot_l]; // (slot_l < slots = mag_stride)
                         if constexpr (UPT) { // norm and node one level up in ONE 8-byte load through ONE pointer (LevelDev::adj_up says why)
                             const uint2 mu = ((const uint2 *)lv.adj_up)[(u64)nd * lv.mag_stride + slot_l];
@@ -262,6 +272,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH >= 3 ? (R
                 const int limit = (int)wa.ef - (int)npop; // future pops still allowed
                 const int ahead = (int)kwin - 1 - (int)wi; // window entries still waiting at pool positions 0..ahead-1
                 u32 window_ok = 1;
+                // nested table: the word is node | column << nest_bits.  The exact filter needs the node now; the reference filter tests
+                // the vector row, so there the word stays ONE register through the filter: the column leaves it for the two gathers and
+                // dies, then the node replaces it.
+                const u32 nb_word = nb_node;
+                if constexpr (NEST && EXACT) nb_node = nb_word & ((1u << nest_bits) - 1u);
 
                 // neighbour slots in slot order, one per lane (vector_store.rs:1161-1171): nb_vec / nb_node
                 const u64 vmask = ballot64(nb_vec != ROW_EMPTY) & slotmask;
@@ -384,7 +399,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH >= 3 ? (R
                     // quotient — the product and the division of the row levels (cosine.rs:223-235) — and no code row is
                     // fetched or dotted.
                     float simv = 0.0f, magv = 1.0f;
-                    if (win) { simv = tabq[nb_node]; magv = tabm[nb_node]; }
+                    if constexpr (NEST) {
+                        const u32 nb_col = nb_word >> nest_bits;
+                        if (win) { simv = tabq[nb_col]; magv = tabm[nb_col]; }
+                        if constexpr (!EXACT) nb_node = nb_word & ((1u << nest_bits) - 1u);
+                    } else if (win) { simv = tabq[nb_node]; magv = tabm[nb_node]; }
                     bool badl;
                     // u8 codes: both norms are roots of integer sums (>= 1 when not 0): the quotient needs no scaling
                     simv = cosine_or_dot<ENG == ENG_U8>(metric_t, simv, qmag, magv, badl);
@@ -574,8 +593,22 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH >= 3 ? (R
         }
         };
         if (tab_level) {
-            if (metric == 0u) level_rounds(std::true_type{}, std::true_type{}, std::false_type{}, std::false_type{});
-            else level_rounds(std::true_type{}, std::false_type{}, std::false_type{}, std::false_type{});
+            bool nest = false;
+            // Rows of one chunk pass and pools of up to 256 keys only (WalkPlan::table_nested follows): every further copy of the rounds
+            // moves the scalar spills of the kernel around, and in the instantiations of two to four passes that cost a VGPR (96 -> 97 at
+            // CH 2, R 8: a wave per SIMD); so it did at R 8 with the exact filter (84 -> 85).  Rows of fewer than 64 chunks take ONE copy
+            // for both metrics for the same reason (two copies: 72 -> 73 VGPRs at R 4).
+            if constexpr (ENG == ENG_U8 && CH == 1 && R <= 4) {
+                if (lv.adj_tab != nullptr) { // the nested table (uniform for the level: the branch is taken once)
+                    if (G64 && metric == 0u) level_rounds(std::true_type{}, std::integral_constant<bool, G64>{}, std::false_type{}, std::false_type{}, std::true_type{});
+                    else level_rounds(std::true_type{}, std::false_type{}, std::false_type{}, std::false_type{}, std::true_type{});
+                    nest = true;
+                }
+            }
+            if (!nest) {
+                if (metric == 0u) level_rounds(std::true_type{}, std::true_type{}, std::false_type{}, std::false_type{}, std::false_type{});
+                else level_rounds(std::true_type{}, std::false_type{}, std::false_type{}, std::false_type{}, std::false_type{});
+            }
         } else {
             bool done = false;
             if constexpr (G64 && !FLOAT_ENG) {
@@ -583,15 +616,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH >= 3 ? (R
                     bool up = false;
                     if constexpr (ENG == ENG_U8) {
                         if (lv.adj_up != nullptr && wa.tab != nullptr && (u32)level + 1u == wa.tab_level_min) { // the level under the table
-                            level_rounds(std::false_type{}, std::false_type{}, std::true_type{}, std::true_type{});
+                            level_rounds(std::false_type{}, std::false_type{}, std::true_type{}, std::true_type{}, std::false_type{});
                             up = true;
                         }
                     }
-                    if (!up) level_rounds(std::false_type{}, std::false_type{}, std::true_type{}, std::false_type{});
+                    if (!up) level_rounds(std::false_type{}, std::false_type{}, std::true_type{}, std::false_type{}, std::false_type{});
                     done = true;
                 }
             }
-            if (!done) level_rounds(std::false_type{}, std::false_type{}, std::false_type{}, std::false_type{});
+            if (!done) level_rounds(std::false_type{}, std::false_type{}, std::false_type{}, std::false_type{}, std::false_type{});
         }
         n_exp += npop;
         adj_bytes += (u64)npop * slots * 4; // what an expansion reads: the scanned slots of the row (min(M, shortlist_size))

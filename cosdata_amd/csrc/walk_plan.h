@@ -67,6 +67,9 @@ struct WalkPlanIn {
     uint32_t n_cus;                 // compute units of the device (0 = 256): sizes the GEMM's work items
     // the row level under the table reads table columns for neighbours with a node one level up (WalkPlan::up_table_level)
     uint32_t up_table_mode;         // tuning knob walk_up_table, resolved: 0 never | 1 by the rule below | 2 at every ef and launch size
+    // the throughput kernel reads the nested table, one column per vector (WalkPlan::table_nested, table_nested.h)
+    uint32_t table_nested_mode;     // tuning knob walk_table_nested, resolved: 0 never | 1, 2 wherever the handle has the nested operand (the knob's two
+                                    // values differ in which graphs get one: engine.hip ensure_nested_table)
 };
 
 // What preparation left, for the second step: no table operand for this graph and rule, no room for a workspace's table (out of
@@ -77,6 +80,10 @@ struct WalkHave {
     uint32_t n_order_keys, order_level0;  // key levels of the locality order and the first (highest) of them
     bool order_buffers;                   // the workspace's order buffers hold B queries
     uint32_t adj_up_level;                // the level whose LevelDev::adj_up is filled for this graph and table rule (0 = none)
+    // the nested operand of the same table levels, with LevelDev::adj_tab filled for it (0 = none): its columns, and whether
+    // LevelDev::adj_up holds columns of THAT table (a launch on the per-level table cannot read them, and the other way round)
+    uint32_t nested_cols;
+    bool adj_up_nested;
 };
 
 struct WalkPlan {
@@ -96,6 +103,10 @@ struct WalkPlan {
     // level holds a quarter of the nodes of the level below).  The GEMM computed that integer dot anyway.  Settled only (the table's
     // lowest level is known after preparation), throughput kernel, u8 codes on the one-row-per-pass path (G = 64).
     uint32_t up_table_level;
+    // The table is the nested one (table_nested.h): one GEMM column per vector of the lowest table level instead of one per (level, node),
+    // table_cols = that level's nodes; the table levels read LevelDev::adj_tab.  Settled only, like up_table_level: throughput kernel, u8
+    // codes, no metadata schema, and the handle has the operand (WalkHave::nested_cols).  The four-wave kernel keeps the per-level table.
+    bool table_nested;
 };
 
 // Work items of the query-resident level-table GEMM: a row group of 256 queries x a stripe of table_gemm_stripe_tiles() column tiles of
@@ -196,13 +207,19 @@ inline WalkPlan walk_plan(const WalkPlanIn &in, const WalkHave *have = nullptr) 
     if (have && table) {
         p.table_level_min = have->table_level_min;
         p.table_cols = have->table_cols;
+        // (rows of one chunk pass, u8 up to 1024 dims, and ef up to 256: walk_kernel has the nested rounds in those instantiations only — walk_kernel.inc says why)
+        if (p.kernel == WalkKernel::Throughput && in.table_nested_mode != 0 && in.eng == WALK_PLAN_ENG_U8 && in.mdim == 0u && have->nested_cols != 0u &&
+            in.G != 0u && in.nchunks <= in.G && in.ef <= 256u) {
+            p.table_nested = true;
+            p.table_cols = have->nested_cols;
+        }
         // Only a GEMM long enough to outlast the previous walk's upper range blocks its sort (engine_internal.h, chain_last_range_ev): the
         // shard's 65 161 columns x 32 768 queries (3.1 ms alone; gate: 33.3 -> 32.6 ms per step) do, c2's 20 903 (0.85 ms; 6.22 -> 6.29) do not
         // (profiles/r06_inflight_probe.txt)
-        p.table_waits_for_sort = p.chained && (in.table_after_sort == 2 || (in.table_after_sort == 1 && (uint64_t)have->table_cols * in.B >= (1ull << 30)));
+        p.table_waits_for_sort = p.chained && (in.table_after_sort == 2 || (in.table_after_sort == 1 && (uint64_t)p.table_cols * in.B >= (1ull << 30)));
         // ... and only such a GEMM is worth two launches: the early part runs under the previous walk's lower range (header comment)
         if (p.table_waits_for_sort && in.table_queue)
-            p.table_early_wgs = std::min(in.table_early_wgs, table_gemm_items(in.B, have->table_cols, in.n_cus, true));
+            p.table_early_wgs = std::min(in.table_early_wgs, table_gemm_items(in.B, p.table_cols, in.n_cus, true));
     }
     if (have && p.ordered) p.cut_after_level = have->order_level0;
     // Norms beside the adjacency cost two more lines per window entry and save one line per winner: they pay while an expansion still
@@ -220,7 +237,7 @@ inline WalkPlan walk_plan(const WalkPlanIn &in, const WalkHave *have = nullptr) 
     // it follows adj_mag's rule — the extra window array costs what adj_mag's costs and pays under the same conditions.  Mode 2 drops
     // the launch-size condition of that rule for this one level (tests: a few hundred queries), not its need for valid norms.
     if (have && p.use_table && p.kernel == WalkKernel::Throughput && in.up_table_mode != 0 && in.eng == WALK_PLAN_ENG_U8 && in.G == 64u &&
-        in.mdim == 0u && have->table_level_min >= 2u && have->adj_up_level == have->table_level_min - 1u) {
+        in.mdim == 0u && have->table_level_min >= 2u && have->adj_up_level == have->table_level_min - 1u && have->adj_up_nested == p.table_nested) {
         const uint32_t l = have->table_level_min - 1u;
         if (in.up_table_mode == 2 && in.adj_mag_valid && in.adj_mag_mode != 0) p.use_adj_mag |= 1u << l;
         if ((p.use_adj_mag >> l) & 1u) p.up_table_level = l;

@@ -273,7 +273,12 @@ int32_t cos_index_walk_order_cuts(cos_index *ix, uint32_t *out_levels, uint32_t 
  * query; the table costs one GEMM column per node): 1M x 768 at ef 64 / M 32 -> levels >= 3 (20 903 columns); a 12.5M x 1024 shard at ef 128 / M 64 -> levels >= 4 (65 161
  * columns, +45 % QPS over a fixed 8 192).  An explicit max_cols caps the columns of all table levels together; 0 = no table.  The
  * operand follows ef_search (cos_index_set_ef_search rebuilds it on the next big launch).
- * A launch holds queries x columns x 4 bytes of table (32 768 x 20 928: 2.7 GB; 32 768 x 65 184: 8.5 GB); a handle's tables together
+ * The levels are nested (a node of level l + 1 is a node of level l), so the throughput kernel's table has ONE column per vector
+ * of level L_t instead of one per (level, node) where that saves 4 096 columns or more (u8 codes up to 1024 dims, no metadata
+ * schema, node index and column of a neighbour fit one 32-bit word; tuning knob walk_table_nested): the shard's 65 161 columns
+ * become 48 822.  The four-wave kernel keeps the per-level table.  Same integers, same results.
+ * A launch holds queries x columns x 4 bytes of table (32 768 x 20 928: 2.7 GB; 32 768 x 65 184: 8.5 GB — 32 768 x 48 832: 6.4 GB
+ * with one column per vector); a handle's tables together
  * stay under 48 GiB (tuning knob walk_table_max_bytes): a launch whose workspace would exceed that walks without a table.
  * Device memory of the search side in general: every caller stream (cos_search_batch_device) and every host call in flight
  * (cos_search_batch: up to 32 leased pipes, a lone big call uses up to five workspaces) owns a workspace sized for its largest launch
@@ -283,7 +288,8 @@ int32_t cos_index_walk_order_cuts(cos_index *ix, uint32_t *out_levels, uint32_t 
 #define COS_WALK_TABLE_DEFAULT_MAX_COLS 8192u /* kept for callers that want the round-4 mid-round default */
 #define COS_WALK_TABLE_AUTO 0xFFFFFFFFu
 int32_t cos_index_set_walk_table(cos_index *ix, uint32_t max_cols, uint32_t min_queries);
-/* the table the next big launch would use: its lowest level and its columns (0, 0 = none).  Diagnostic: bench.py reports it. */
+/* the table the next big launch would use: its lowest level and its columns (0, 0 = none; the nested table's columns where the
+ * throughput kernel reads that one — a one-client-batch launch on the four-wave kernel then reports more).  Diagnostic: bench.py reports it. */
 int32_t cos_index_walk_table_info(cos_index *ix, uint32_t *out_level_min, uint32_t *out_cols);
 /* The last completed batch on `stream` split by dispatch, for the roofline report: a big launch is up to three
  * pieces of work with three different bounds — the level-table GEMM (MFMA), the level range above the cut (rows that stay in
