@@ -78,6 +78,11 @@ class CosFlatStats(C.Structure):
     _fields_ = [("gemm_ms", C.c_float), ("gemm_launches", C.c_uint32), ("int8_ops", C.c_double), ("code_bytes", C.c_double)]
 
 
+class CosBruteStats(C.Structure):
+    """cos_brute_stats: the handle's last brute force — how many of its queries the margin rule sent down the exact path"""
+    _fields_ = [("struct_size", C.c_uint32), ("queries", C.c_uint32), ("exact_queries", C.c_uint32), ("pool", C.c_uint32)]
+
+
 SCAN_SKIP_DELETED = 1  # COS_SCAN_SKIP_DELETED
 
 
@@ -136,7 +141,7 @@ ABI_SYMBOLS = [
     "cos_search_batch", "cos_search_batch_device", "cos_ann_search_batch", "cos_index_set_coalescing", "cos_index_coalescing_stats", "cos_index_set_ef_search",
     "cos_index_set_visited_mode", "cos_index_set_latency_mode", "cos_index_set_latency_waves", "cos_index_set_walk_order", "cos_index_walk_order_cuts", "cos_index_set_walk_table", "cos_index_walk_table_info", "cos_index_last_walk_split", "cos_index_enable_timing", "cos_index_last_stats", "cos_index_timing_summary", "cos_quantize_batch",
     "cos_code_bytes", "cos_sample_values_range", "cos_distance_batch", "cos_bruteforce_topk", "cos_flat_search_batch",
-    "cos_flat_search_masked_batch", "cos_bruteforce_topk_masked", "cos_index_deleted_count", "cos_index_download_deleted", "cos_bm25_create", "cos_bm25_destroy",
+    "cos_flat_search_masked_batch", "cos_bruteforce_topk_masked", "cos_index_last_brute_stats", "cos_index_deleted_count", "cos_index_download_deleted", "cos_bm25_create", "cos_bm25_destroy",
     "cos_bm25_insert", "cos_bm25_delete", "cos_bm25_stats", "cos_bm25_download",
     "cos_bm25_search_batch", "cos_bm25_search_batch_device", "cos_rrf_fuse_batch", "cos_hybrid_search_batch", "cos_text_process", "cos_text_count_tokens", "cos_bm25_term_frequency", "cos_xxhash32", "cos_stem_english", "cos_sparse_create", "cos_sparse_build_csr", "cos_sparse_create_from_vectors", "cos_sparse_destroy", "cos_sparse_search_batch", "cos_sparse_last_stats", "cos_sparse_layout",
     "cos_sparse_set_max_candidates", "cos_sparse_max_candidates", "cos_sparse_search_batch_device",
@@ -217,6 +222,7 @@ def lib():
         "cos_flat_search_batch": [vp, vp, u32, u32, vp, vp, vp, C.POINTER(CosFlatStats)],
         "cos_flat_search_masked_batch": [vp, vp, u32, u32, C.POINTER(CosScanMask), vp, vp, vp, C.POINTER(CosFlatStats)],
         "cos_bruteforce_topk_masked": [vp, vp, u32, u32, C.POINTER(CosScanMask), vp, vp, vp],
+        "cos_index_last_brute_stats": [vp, C.POINTER(CosBruteStats)],
         "cos_index_deleted_count": [vp, C.POINTER(u32)],
         "cos_index_download_deleted": [vp, vp],
         "cos_bm25_create": [i32, vp, vp, u32, vp, vp, u32, C.POINTER(vp)],
@@ -291,7 +297,7 @@ def check(rc: int):
 
 
 def tuning_set(name: str, value: int):
-    """cos_tuning_set: an experiment knob of the library (cosdata_amd/csrc/tuning.h); never changes a result."""
+    """cos_tuning_set: an experiment knob of the library (cosdata_amd/csrc/tuning.h); never changes a result (flat_brute_exact = 0 apart)."""
     check(lib().cos_tuning_set(name.encode(), int(value)))
 
 

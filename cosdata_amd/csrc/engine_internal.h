@@ -361,6 +361,7 @@ struct cos_index {
     // ... and the smallest of them (one client batch) give every query four waves (kernels_walk_lat4.hip); 0 = never
     u32 lat4_max_B = COS_LATENCY_WAVES_DEFAULT_MAX_B;
     struct FlatWs *flat_ws = nullptr; // cos_flat_search_batch's buffers (kernels_flat.hip), created on first use under `mu`
+    cos_brute_stats brute_last = {(u32)sizeof(cos_brute_stats), 0u, 0u, 0u}; // the last brute force of this handle (cos_index_last_brute_stats)
 };
 
 

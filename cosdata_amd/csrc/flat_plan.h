@@ -1,7 +1,7 @@
 // flat_plan.h — the host-only part of the two exhaustive scans (kernels_flat.hip: cos_flat_search_batch over the quantized codes,
 // cos_bruteforce_topk over the f32 rows): the limits, the survivor pool's width, the chunk schedule of an attempt, the buffer sizes
-// that follow from it and the kernel that scores a fused chunk of the code scan.  Every number a scan decides before or between its
-// launches.  Plain C++17, no HIP header and no handle, so that a stand-alone program can check it (tests/cxx/flat_plan_check.cpp).
+// that follow from it, the kernel that scores a fused chunk of the code scan and the rule that says when the brute force's pool can be
+// trusted (brute_margin_safe).  Every number a scan decides before or between its launches.  Plain C++17, no HIP header and no handle, so that a stand-alone program can check it (tests/cxx/flat_plan_check.cpp).
 #pragma once
 #include <cstdint>
 
@@ -28,10 +28,44 @@ inline uint32_t flat_pool_width(uint32_t need) {
 }
 
 // ---- limits ----
-// brute force: the f32 MFMA GEMM only generates candidates, so the pool holds at least 2k of them; k in [1, min(512, n)]
+// brute force: the f32 MFMA GEMM only generates candidates, so the pool holds at least 2k of them (and is trusted only under the margin
+// rule below); k in [1, min(512, n)]
 constexpr uint32_t BRUTE_MAX_K = 512, BRUTE_POOL_FACTOR = 2;
 inline int32_t check_brute_k(uint32_t k, uint32_t n) { return k == 0 || k > BRUTE_MAX_K || k > n ? INVALID : OK; }
 inline uint32_t brute_pool(uint32_t k) { return flat_pool_width(BRUTE_POOL_FACTOR * k); }
+
+// ---- brute force: when the pool that the GEMM's ranking cut can be trusted ----
+// The pool holds the P best rows by the GEMM's score g; the answer is the k best by the reference-order score e.  With
+// |g - e| <= bound for every row: a row outside a FULL pool has g <= g_P (the pool's P-th score), so e <= g_P + bound, and the k best
+// of the pool have e >= g_k - bound.  When g_P + bound < g_k - bound, k rows of the pool beat every row outside it in the exact order
+// too, and the exact top k lies in the pool: the query is SAFE.  A pool that is not full holds every (live) row and is always safe.
+// Otherwise — more than P - k rows within 2 * bound of the k-th score: copies, scaled copies, boilerplate documents — the pool may
+// have dropped rows of the answer, and the call scores every row of that query in the reference's order instead (kernels_flat.hip,
+// the exact path).  Scores that are not finite are never safe.
+//
+// The bound.  u = 2^-24.  Both scores divide by the SAME f32 denominator D = fl(|q| * |x|) (the norms the handle keeps): their
+// difference is that of the two f32 dots over D, plus one rounding of each quotient.
+//   GEMM dot       one k-ordered chain of dim fused steps (v_mfma_f32_32x32x2_f32): |err| <= dim u S, S = sum |x_i q_i| —
+//                  which holds for dim correctly rounded operations in ANY order
+//   reference dot  eight chains of dim / 8 fused steps, a pairwise tree of 3, a scalar tail of up to 7 unfused multiply-adds: the
+//                  model of tests/odd_dims.py bound_a, |err| <= (dim / 8 + 16) u S
+//   two quotients  |g|, |e| <= ~1: 2 u each with the product |q| * |x| rounded once more — 8 u for both, an absolute term
+// With S <= |x| |q| (Cauchy-Schwarz) and S / D ~ 1: |g - e| <= ((dim + dim / 8 + 32) + 8) u, the extra 16 u being slack for the chain
+// ends.  That figure assumes round-to-nearest at every step and D equal to the true |x| |q|.  Neither is documented: the MFMA's
+// internal rounding of its two-term step is not stated by the ISA guide (a truncating step errs by 2 u, not u), and the handle's
+// norms are sequential f32 sums whose relative error (up to dim u / 2 each) scales S / D.  The bound therefore takes TWICE the figure —
+// a truncating chain, or S / D up to 2 — and the rule twice the bound.  On Gaussian-mixture corpora the k-th and P-th scores are
+// hundreds of bounds apart (tests/test_oracle_near_copies.py), so ordinary data never leaves the MFMA path.
+// constexpr: the kernel that flags the queries calls the same function (a constexpr function is host and device code under hipcc).
+constexpr double brute_margin_bound(uint32_t dim) { return 2.0 * (double)((dim + dim / 8 + 32) + 8) * (1.0 / 16777216.0); }
+constexpr bool brute_margin_safe(float kth, float pth, uint32_t dim, bool pool_full) {
+    if (!pool_full) return true;
+    const double a = (double)kth, b = (double)pth;
+    if (!(a - a == 0.0) || !(b - b == 0.0)) return false; // NaN or inf
+    return a - b > 2.0 * brute_margin_bound(dim);
+}
+// tuning knob flat_brute_exact: which queries take the exact path
+enum BruteExact : int { BRUTE_EXACT_NEVER = 0, BRUTE_EXACT_BY_RULE = 1, BRUTE_EXACT_ALWAYS = 2 };
 // code scan: the pool holds the 5 * top_k candidates of the exact rerank; top_k in [1, 204]
 constexpr uint32_t CODE_MAX_TOP_K = 204, CODE_POOL_FACTOR = 5;
 inline int32_t check_code_top_k(uint32_t top_k) { return top_k == 0 || top_k > CODE_MAX_TOP_K ? UNIMPLEMENTED : OK; }

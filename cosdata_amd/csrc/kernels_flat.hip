@@ -7,8 +7,12 @@
 //   flat_select_*      waves per (query, segment) keep a top-64 (sorted register pool, threshold filter); merged per query
 //   flat_rescore       exact reference-order re-score (dot_product_f32_simd order) of the 64 survivors -> top-k
 // MFMA accumulation order differs from the reference's 8-lane tree in the last ulp, so the GEMM only
-// GENERATES candidates (64 >= 2k with margin); the returned ids/scores come from the reference-order kernel
-// and are bit-identical to the oracle's brute force.
+// GENERATES candidates (a pool of P >= 2k); the returned ids/scores come from the reference-order kernel
+// and are bit-identical to the oracle's brute force.  The pool is trusted only while its P-th GEMM score lies more
+// than twice a derived error bound under its k-th (flat_plan.h brute_margin_safe; brute_margin_kernel flags the rest):
+// a query with more than P - k rows that close to the k-th score (copies, scaled copies of one vector) is answered by the
+// exact path — flat_exact_scores writes the reference-order score of EVERY row where the GEMM wrote its own, the same
+// selection and re-score follow (bruteforce_run, exact_pass).
 // Calls that need more than 64 survivors (k > 32 here, top_k > 12 in the code scan) keep pools of 128 .. 1024 keys: the kernels
 // behind the GEMMs are then those of kernels_flat_wide.hip, the GEMMs and the flow below are the same.
 #include <hip/hip_runtime.h>
@@ -833,11 +837,56 @@ hipError_t launch_codes_gemm(int eng, bool fused, int pf, bool masked, const Cod
     return hipGetLastError();
 }
 
+// ---- brute force: which pools the GEMM's ranking may have cut wrongly, and the scores of the exact path ----
+// flags[q] = 1 and *n_flagged += 1 where flat_plan.h brute_margin_safe says no: the pool (sorted descending, P keys, at every width
+// pool[q][e]) is full and its P-th score is not more than twice the bound under its k-th.  One thread per query.
+__global__ void brute_margin_kernel(const u64 *__restrict__ pool_mem, u32 P, u32 B, u32 k, u32 dim, u32 *__restrict__ flags, u32 *__restrict__ n_flagged) {
+    const u32 q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= B) return;
+    const u64 kth = pool_mem[(u64)q * P + k - 1], pth = pool_mem[(u64)q * P + P - 1];
+    const bool safe = fp::brute_margin_safe(simkey_inv((u32)(kth >> 32)), simkey_inv((u32)(pth >> 32)), dim, (u32)(pth >> 32) != 0u);
+    flags[q] = safe ? 0u : 1u;
+    if (!safe) atomicAdd(n_flagged, 1u);
+}
+// The exact path's scores: scores[q][c] = dot_f32(q, x) / (|q| * |x|) of row n0 + c in the REFERENCE's order — the value exact_key ranks
+// and flat_rescore returns, so the selection over this matrix (the unfused chunk's, ties to the larger id, masks applied there) keeps
+// the exact top P and the re-score that follows reproduces it.  A lane pair per row (f32_pair_dot), 128 rows per pass of the 4 waves,
+// EXACT_ROWS rows per workgroup so that the query is staged once per 8 passes.  Grid (B, ceil(n_chunk / EXACT_ROWS)).
+constexpr u32 EXACT_ROWS = 1024;
+__global__ __launch_bounds__(256) void flat_exact_scores(const float *__restrict__ Q, u64 q_stride, const float *__restrict__ qmags,
+                                                         const float *__restrict__ X, u64 x_stride, const float *__restrict__ xmags, u32 n0,
+                                                         u32 n_chunk, u32 dim, float *__restrict__ scores /*[B][s_stride]*/, u64 s_stride) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    float *qf = (float *)smem_raw;
+    const u32 tid = threadIdx.x, q = blockIdx.x;
+    for (u32 i = tid; i < dim; i += 256) qf[i] = Q[(u64)q * q_stride + i];
+    __syncthreads();
+    const float mq = qmags[q];
+    const u32 c_begin = blockIdx.y * EXACT_ROWS, c_end = c_begin + EXACT_ROWS < n_chunk ? c_begin + EXACT_ROWS : n_chunk;
+    for (u32 c0 = c_begin; c0 < c_end; c0 += 128) { // (workgroup-uniform: both lanes of a pair run every pass)
+        const u32 col = c0 + (tid >> 1);
+        const bool valid = col < n_chunk;
+        const u32 row = n0 + (valid ? col : 0u);
+        const float dp = f32_pair_dot(X + (u64)row * x_stride, qf, dim, (int)(tid & 1));
+        if (valid && (tid & 1) == 0) scores[(u64)q * s_stride + col] = x86_div(dp, __fmul_rn(mq, xmags[row]));
+    }
+}
+hipError_t launch_exact_scores(const float *Q, const float *qmags, u32 B, const float *X, const float *xmags, u32 n0, u32 nc, u32 dim, float *scores,
+                               u64 s_stride, hipStream_t st) {
+    hipLaunchKernelGGL(flat_exact_scores, dim3(B, (nc + EXACT_ROWS - 1) / EXACT_ROWS), dim3(256), staged_query_bytes(dim), st, Q, (u64)dim, qmags, X, (u64)dim,
+                       xmags, n0, nc, dim, scores, s_stride);
+    return hipGetLastError();
+}
+
 // cos_bruteforce_topk (mask == nullptr, out_counts optional) and cos_bruteforce_topk_masked; with d_record (device memory on the index's
 // device, B * (2k + 1) words) the shard set's form: the same launches, the rerank writes [ids B*k | scores B*k | counts B] there instead of
-// the call's own buffers, nothing is copied out (out_* unused) and the record is complete when the call returns
+// the call's own buffers, nothing is copied out (out_* unused) and the record is complete when the call returns.
+// The exact path (flat_plan.h brute_margin_safe; tuning knob flat_brute_exact): a query whose pool the GEMM's ranking may have cut
+// wrongly is answered again by the same call on the sub-batch of such queries with exact_pass set — every chunk unfused, its score
+// matrix written by flat_exact_scores instead of the GEMM, the same selection, masks, re-score and counts — and its rows replace the
+// first answer's.  The flags' count comes back with the overflow flag: a call with nothing flagged makes no further round trip.
 int32_t bruteforce_run(cos_index *ix, const float *queries, uint32_t B, uint32_t k, const cos_scan_mask *mask, uint32_t *out_ids, float *out_scores,
-                       uint32_t *out_counts, u32 *d_record = nullptr) {
+                       uint32_t *out_counts, u32 *d_record = nullptr, bool exact_pass = false) {
     if (!ix || !queries || ((!out_ids || !out_scores) && !d_record) || B == 0) return cos_fail(COS_ERR_INVALID, "bad argument");
     if (!ix->have_vectors) return cos_fail(COS_ERR_NOT_READY, "upload vectors first");
     if (int32_t krc = fp::check_brute_k(k, ix->n)) return cos_fail(krc, "k must be in [1, min(512, n)]");
@@ -850,13 +899,15 @@ int32_t bruteforce_run(cos_index *ix, const float *queries, uint32_t B, uint32_t
     // seeds every query's threshold; later chunks grow and the GEMM epilogue appends only what beats the threshold.  An
     // append-buffer overflow repeats the call on the unfused path (tuning knob flat_unfused = 1 forces it).
     // Survivors per query: the GEMM only generates candidates, so the pool holds at least 2k of them (64 for k <= 32, as ever).
-    const fp::Scan plan = fp::brute_scan(n, B, k, tune_or(TUNE_FLAT_UNFUSED, 0) != 0);
+    const int exact_mode = exact_pass ? (int)fp::BRUTE_EXACT_ALWAYS : (int)tune_or(TUNE_FLAT_BRUTE_EXACT, fp::BRUTE_EXACT_BY_RULE);
+    const bool exact = exact_mode >= fp::BRUTE_EXACT_ALWAYS, by_rule = exact_mode == fp::BRUTE_EXACT_BY_RULE;
+    const fp::Scan plan = fp::brute_scan(n, B, k, exact || tune_or(TUNE_FLAT_UNFUSED, 0) != 0);
     const u32 P = plan.P, R = P / SEL;
     // the score matrix and the selection's lists serve the unfused chunks of both attempts
     const u64 s_stride = fp::score_stride(plan.unfused);
     DevArr<float> d_q, d_qm, d_scores, d_os, d_dummy;
     DevArr<u64> d_pool, d_part, d_thr, d_app;
-    DevArr<u32> d_oi, d_appcnt, d_over, d_oc;
+    DevArr<u32> d_oi, d_appcnt, d_over, d_oc, d_flag;
     DevArr<uint8_t> d_codes;
     MaskBufs mb;
     hipStream_t st = ix->own_stream;
@@ -870,7 +921,8 @@ int32_t bruteforce_run(cos_index *ix, const float *queries, uint32_t B, uint32_t
     HIP_TRY(d_thr.alloc(B));
     if (plan.allow_fused) HIP_TRY(d_app.alloc((size_t)B * plan.app_cap()));
     HIP_TRY(d_appcnt.alloc(B));
-    HIP_TRY(d_over.alloc(1));
+    HIP_TRY(d_over.alloc(2)); // [the fused path's overflow flag, queries the margin rule flagged]
+    if (by_rule) HIP_TRY(d_flag.alloc(B));
     if (!d_record) {
         HIP_TRY(d_oi.alloc((size_t)B * k));
         HIP_TRY(d_os.alloc((size_t)B * k));
@@ -888,21 +940,28 @@ int32_t bruteforce_run(cos_index *ix, const float *queries, uint32_t B, uint32_t
     if (e == hipSuccess && mp.masked) e = scan_mask_upload(ix, mask, mp, B, mb, st, sm, &d_uni);
     // float4 staging needs 16 B aligned rows: dim % 4 == 0 (hipMalloc'd bases are 256 B aligned; a borrowed raw pointer is checked)
     const bool vec = dim % 4 == 0 && ((uintptr_t)ix->d_raw & 15) == 0;
+    u32 n_flagged = 0;
     for (int attempt = 0; attempt < 2 && e == hipSuccess; attempt++) {
         if (e == hipSuccess) e = hipMemsetAsync(d_pool, 0, (size_t)B * P * 8, st);
         if (e == hipSuccess) e = hipMemsetAsync(d_thr, 0, (size_t)B * 8, st);
         if (e == hipSuccess) e = hipMemsetAsync(d_appcnt, 0, (size_t)B * 4, st);
-        if (e == hipSuccess) e = hipMemsetAsync(d_over, 0, 4, st);
+        if (e == hipSuccess) e = hipMemsetAsync(d_over, 0, 8, st);
         const ScanBufs bufs{d_scores, s_stride, d_part, d_pool, d_thr, d_app, d_appcnt, d_over, sm};
         const FusedOut fo = bufs.fused_out(plan, nullptr);
         if (e == hipSuccess)
             e = run_chunks(plan, attempt, bufs, st, [&](const fp::Chunk &c) {
+                if (exact) return launch_exact_scores(d_q, d_qm, B, ix->d_raw, ix->d_raw_mags, c.n0, c.nc, dim, d_scores, s_stride, st);
                 return launch_gemm_f32(vec, c.fused, mp.masked, d_q, d_qm, B, ix->d_raw, ix->d_raw_mags, c.n0, c.nc, dim, d_scores, s_stride, fo, st);
             });
-        u32 hover = 0;
-        if (e == hipSuccess) e = hipMemcpyAsync(&hover, d_over, 4, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && by_rule) { // the pools are final (or about to be repeated): ranks k and P of each
+            hipLaunchKernelGGL(brute_margin_kernel, dim3((B + 255) / 256), dim3(256), 0, st, (const u64 *)d_pool, P, B, k, dim, d_flag.p, d_over.p + 1);
+            e = hipGetLastError();
+        }
+        u32 hover[2] = {0u, 0u};
+        if (e == hipSuccess) e = hipMemcpyAsync(hover, d_over, 8, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess || !plan.fused(attempt) || hover == 0) break; // done; otherwise the append buffer overflowed: repeat unfused
+        n_flagged = hover[1];
+        if (e != hipSuccess || !plan.fused(attempt) || hover[0] == 0) break; // done; otherwise the append buffer overflowed: repeat unfused
     }
     if (e == hipSuccess && R == 1) {
         hipLaunchKernelGGL(flat_rescore, dim3(B), dim3(64), staged_query_bytes(dim), st, d_q, (u64)dim, d_qm, B, ix->d_raw, (u64)dim,
@@ -918,9 +977,57 @@ int32_t bruteforce_run(cos_index *ix, const float *queries, uint32_t B, uint32_t
         if (e == hipSuccess && !d_record) e = hipMemcpyAsync(out_counts, r_oc, (size_t)B * 4, hipMemcpyDeviceToHost, st);
     } else if (e == hipSuccess && d_record)
         e = launch_fill_i32(reinterpret_cast<int32_t *>(r_oc), B, (int32_t)k, st); // k <= n: every list is full
+    std::vector<u32> h_flag;
+    if (e == hipSuccess && n_flagged) {
+        h_flag.resize(B);
+        e = hipMemcpyAsync(h_flag.data(), d_flag.p, (size_t)B * 4, hipMemcpyDeviceToHost, st);
+    }
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     HIP_TRY(e);
     if (!mp.masked && out_counts && !d_record) std::fill(out_counts, out_counts + B, k); // k <= n: every list is full
+    if (!exact_pass) ix->brute_last = cos_brute_stats{(u32)sizeof(cos_brute_stats), B, exact ? B : n_flagged, P};
+    if (n_flagged == 0) return COS_OK;
+    // the flagged queries again, exactly: the big buffers of this pass go first, the sub-batch's answer replaces theirs
+    d_scores.reset(); d_part.reset(); d_app.reset(); d_pool.reset();
+    std::vector<u32> sel;
+    for (u32 b = 0; b < B; b++)
+        if (h_flag[b]) sel.push_back(b);
+    const u32 Bx = (u32)sel.size();
+    std::vector<float> xq((size_t)Bx * dim), xs((size_t)Bx * k);
+    std::vector<u32> xi((size_t)Bx * k), xc(Bx), xqm;
+    for (u32 i = 0; i < Bx; i++) memcpy(xq.data() + (size_t)i * dim, queries + (size_t)sel[i] * dim, (size_t)dim * 4);
+    cos_scan_mask xmask;
+    if (mask) {
+        xmask = *mask;
+        if (mask->query_mask) {
+            for (u32 i = 0; i < Bx; i++) xqm.push_back(mask->query_mask[sel[i]]);
+            xmask.query_mask = xqm.data();
+        }
+    }
+    if (int32_t xrc = bruteforce_run(ix, xq.data(), Bx, k, mask ? &xmask : nullptr, xi.data(), xs.data(), xc.data(), nullptr, true)) return xrc;
+    const size_t nk = (size_t)B * k;
+    std::vector<u32> h_rec;
+    u32 *h_i = out_ids, *h_c = out_counts;
+    float *h_s = out_scores;
+    if (d_record) { // the shard set's form: the record comes down, takes the rows and goes back
+        h_rec.resize(2 * nk + B);
+        e = hipMemcpyAsync(h_rec.data(), d_record, h_rec.size() * 4, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        HIP_TRY(e);
+        h_i = h_rec.data();
+        h_s = reinterpret_cast<float *>(h_rec.data() + nk);
+        h_c = h_rec.data() + 2 * nk;
+    }
+    for (u32 i = 0; i < Bx; i++) {
+        memcpy(h_i + (size_t)sel[i] * k, xi.data() + (size_t)i * k, (size_t)k * 4);
+        memcpy(h_s + (size_t)sel[i] * k, xs.data() + (size_t)i * k, (size_t)k * 4);
+        if (h_c) h_c[sel[i]] = xc[i]; // (an unmasked call's counts are k in both passes)
+    }
+    if (d_record) {
+        e = hipMemcpyAsync(d_record, h_rec.data(), h_rec.size() * 4, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        HIP_TRY(e);
+    }
     return COS_OK;
 }
 
@@ -933,6 +1040,12 @@ extern "C" int32_t cos_bruteforce_topk_masked(cos_index *ix, const float *querie
                                               float *out_scores, uint32_t *out_counts) {
     if (!out_counts) return cos_fail(COS_ERR_INVALID, "bad argument");
     return bruteforce_run(ix, queries, B, k, mask, out_ids, out_scores, out_counts);
+}
+extern "C" int32_t cos_index_last_brute_stats(cos_index *ix, cos_brute_stats *out) {
+    if (!ix || !out) return cos_fail(COS_ERR_INVALID, "null argument");
+    if (out->struct_size != sizeof(cos_brute_stats)) return cos_fail(COS_ERR_INVALID, "cos_brute_stats::struct_size is %u, expected %zu", out->struct_size, sizeof(cos_brute_stats));
+    *out = ix->brute_last;
+    return COS_OK;
 }
 
 // Per-index workspace of cos_flat_search_batch: every buffer is grow-only and lives until the index is destroyed (or its

@@ -6,7 +6,8 @@
 //     compare two implementations of one operator call them;
 //   * the ONLY environment variable the library reads is COS_TUNING="name=value,name=value", parsed once on first use, so that a
 //     script can still steer an unmodified process (rocprofv3 runs);
-//   * a knob nobody set reports TUNE_UNSET and the call site applies its measured default.  None of them changes a result.
+//   * a knob nobody set reports TUNE_UNSET and the call site applies its measured default.  None of them changes a result — but for
+//     flat_brute_exact = 0, which switches a correctness rule off to time what it costs.
 #pragma once
 #include <cstdint>
 
@@ -50,6 +51,7 @@ enum TuneKey : int {
     TUNE_WALK_TABLE_EARLY_WGS, // workgroups of the EARLY part of a gated level-table GEMM, issued behind the previous chained walk's upper range (walk_plan.h); 0 = one launch behind its order sort (default: WALK_TABLE_EARLY_WGS_DEFAULT, engine.hip)
     TUNE_WALK_UP_TABLE,       // the row level directly under the level table reads table columns for neighbours that have a node one level up (LevelDev::adj_up): 0 = never, 1 = where that level reads its norms beside the adjacency (walk_adj_mag's rule), 2 = at every ef and launch size (tests); default WALK_UP_TABLE_DEFAULT, engine.hip
     TUNE_WALK_TABLE_NESTED,   // the throughput kernel's level table holds one column per vector of its lowest level, in nested order (table_nested.h), and its table levels read LevelDev::adj_tab: 0 = never, 1 = on graphs where that saves TABLE_NESTED_MIN_SAVED_COLS columns or more, 2 = on every graph (tests); default WALK_TABLE_NESTED_DEFAULT, engine.hip
+    TUNE_FLAT_BRUTE_EXACT,    // which queries of a brute force are scored again in the reference's order (flat_plan.h brute_margin_safe): 0 = none — the ranking of the f32 MFMA alone cuts the pool, which on corpora with near-copies of one row CAN return a wrong list (kept for A/B timing; the one knob that can change a result), 1 = those the margin rule flags (default), 2 = every query
     TUNE_COUNT
 };
 

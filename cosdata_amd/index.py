@@ -483,6 +483,13 @@ class HNSWIndex:
         check(_lib.lib().cos_bruteforce_topk(self._h, _p(q), q.shape[0], k, _p(ids), _p(scores)))
         return ids, scores
 
+    def last_brute_stats(self):
+        """cos_index_last_brute_stats: the last bruteforce_topk / bruteforce_topk_masked of this handle -> CosBruteStats (queries,
+        exact_queries: those whose pool failed the margin rule and were scored in the reference's order, pool)."""
+        st = _lib.CosBruteStats(struct_size=C.sizeof(_lib.CosBruteStats))
+        check(_lib.lib().cos_index_last_brute_stats(self._h, C.byref(st)))
+        return st
+
     # ---- exhaustive scans over a subset of the rows ------------------------------------------
     def _scan_mask(self, masks, query_mask, skip_deleted: bool, B: int):
         """-> (CosScanMask or None, arrays to keep alive).  `masks`: bool [n] (shared) or [G][n], or uint32 [G][ceil(n / 32)] packed

@@ -404,11 +404,26 @@ int32_t cos_distance_batch(uint32_t metric, uint32_t storage, uint32_t resolutio
  * MFMA f32 GEMM for candidate generation + reference-order re-score of the survivors.
  * k in [1, min(512, n)], anything else is COS_ERR_INVALID.  A query keeps a pool of P survivors, the smallest of
  * 64, 128, 256, 512, 1024 with 2k <= P (the GEMM's summation order differs from the reference's in the last ulp:
- * it only generates candidates).  Device memory of a call beyond the score chunk, per query: 8 P bytes of pool,
+ * it only generates candidates).  The pool is trusted only where its P-th GEMM score lies more than twice a derived
+ * error bound under its k-th (cosdata_amd/csrc/flat_plan.h brute_margin_safe); a query that fails the rule — more than
+ * P - k rows within the scores' error of the k-th: copies and scaled copies of one vector — has every row scored in the
+ * reference's order instead, n * dim fused multiply-adds on the vector units for that query, so the answer is the
+ * reference's bit for bit on such corpora too.  cos_index_last_brute_stats says how many queries that was.
+ * Device memory of a call beyond the score chunk, per query: 8 P bytes of pool,
  * up to 512 P bytes of per-segment partial pools (fewer for batches above 64 queries) and, above 16384 vectors, the
  * append buffer of the threshold-filtered scan: 32 KB at P = 64, 256 P bytes (32 KB .. 256 KB) at P >= 128. */
 int32_t cos_bruteforce_topk(cos_index *ix, const float *queries, uint32_t B, uint32_t k, uint32_t *out_ids,
                             float *out_scores);
+/* The last cos_bruteforce_topk / cos_bruteforce_topk_masked on this handle (a shard set's brute force counts as one per shard):
+ * all zero before the first.  out->struct_size must be sizeof(cos_brute_stats) on entry, anything else is COS_ERR_INVALID. */
+typedef struct cos_brute_stats {
+    uint32_t struct_size;   /* in: sizeof(cos_brute_stats) */
+    uint32_t queries;       /* B of the call */
+    uint32_t exact_queries; /* queries answered by the exact path: those the margin rule flagged (every one with tuning knob
+                             * flat_brute_exact = 2, none with 0) */
+    uint32_t pool;          /* P */
+} cos_brute_stats;
+int32_t cos_index_last_brute_stats(cos_index *ix, cos_brute_stats *out);
 
 /* Exhaustive search over the index's QUANTIZED codes as an exact-integer MFMA GEMM, then the reference's finalisation on the full candidate set: sort by quantized score (desc, larger id
  * first), keep 5k, exact f32 rerank (vector_store.rs:404-445), top-k.  The result is what

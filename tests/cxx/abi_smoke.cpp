@@ -24,6 +24,10 @@ int main() {
     if (cos_shardset_create(nullptr, 0, 0, 0, nullptr, &ss) != COS_ERR_INVALID || ss != nullptr) { printf("FAIL shardset null list\n"); return 1; }
     if (cos_shardset_search_batch(nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr) != COS_ERR_INVALID) { printf("FAIL shardset search args\n"); return 1; }
     if (cos_shardset_destroy(nullptr) != COS_OK) { printf("FAIL shardset destroy(null)\n"); return 1; }
+    {
+        cos_brute_stats bs = {sizeof(cos_brute_stats), 0, 0, 0};
+        if (cos_index_last_brute_stats(nullptr, &bs) != COS_ERR_INVALID) { printf("FAIL brute stats null handle\n"); return 1; }
+    }
     // host-side entry points (no GPU needed): text -> BM25 terms with the built-in English stemmer, sparse index construction
     {
         char st[32];

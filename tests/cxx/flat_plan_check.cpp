@@ -181,6 +181,34 @@ int main(int argc, char **argv) {
         fp::Chunk c0{0, 0, false};
         EXPECT(!es.next(c0));
     }
+    // ---- the brute force's margin rule: safe = the pool is not full, or the P-th GEMM score lies more than 2 * bound under the k-th ----
+    {
+        const double u = 1.0 / 16777216.0;
+        // the bound, restated by hand: 2 * ((dim + dim / 8 + 32) + 8) * 2^-24 (tests/near_copies.py margin_bound states the same)
+        EXPECT(fp::brute_margin_bound(64) == 2.0 * 112 * u && fp::brute_margin_bound(65) == 2.0 * 113 * u && fp::brute_margin_bound(96) == 2.0 * 148 * u);
+        EXPECT(fp::brute_margin_bound(97) == 2.0 * 149 * u && fp::brute_margin_bound(100) == 2.0 * 152 * u && fp::brute_margin_bound(768) == 2.0 * 904 * u);
+        EXPECT(fp::brute_margin_bound(1) == 2.0 * 41 * u);
+        const float b96 = (float)fp::brute_margin_bound(96); // 296 * 2^-24: exact in f32
+        EXPECT(!fp::brute_margin_safe(0.75f, 0.75f, 96, true));                              // equal scores
+        EXPECT(!fp::brute_margin_safe(0.75f, 0.75f - 2.0f * b96, 96, true));                 // a gap of exactly 2 * bound is not "more than"
+        EXPECT(fp::brute_margin_safe(0.75f, 0.75f - 2.0f * b96 - 0x1p-24f, 96, true));       // one ulp (of 0.5 .. 1) more is
+        EXPECT(!fp::brute_margin_safe(0.5f, 0.75f, 96, true));                               // (a P-th score above the k-th: never)
+        EXPECT(fp::brute_margin_safe(-0.25f, -0.5f, 96, true));                              // negative scores: the same subtraction
+        EXPECT(!fp::brute_margin_safe(-0.25f, -0.25f - b96, 96, true));
+        EXPECT(fp::brute_margin_safe(1e-3f, -1e-3f, 96, true) && !fp::brute_margin_safe(1e-5f, -1e-5f, 96, true)); // across zero
+        EXPECT(fp::brute_margin_safe(0.75f, 0.75f, 96, false));                              // a pool that is not full holds every row
+        EXPECT(fp::brute_margin_safe(__builtin_nanf(""), 0.0f, 96, false));
+        const float nan = __builtin_nanf(""), inf = __builtin_inff();
+        EXPECT(!fp::brute_margin_safe(nan, 0.0f, 96, true) && !fp::brute_margin_safe(1.0f, nan, 96, true) && !fp::brute_margin_safe(-nan, -nan, 96, true));
+        EXPECT(!fp::brute_margin_safe(inf, 0.0f, 96, true) && !fp::brute_margin_safe(1.0f, -inf, 96, true) && !fp::brute_margin_safe(inf, -inf, 96, true));
+        // the same two scores are safe at a short dim and not at a long one
+        EXPECT(fp::brute_margin_safe(0.5f, 0.5f - 1e-4f, 64, true) && !fp::brute_margin_safe(0.5f, 0.5f - 1e-4f, 1024, true));
+        // k = P / 2 exactly: the pool's width does not enter the rule beyond "full" — the caller reads ranks k and P of a pool of
+        // brute_pool(k) keys, and at k = 32, 64, ..., 512 that pool is exactly 2k wide
+        for (uint32_t k = 32; k <= 512; k *= 2) EXPECT(fp::brute_pool(k) == 2 * k && fp::brute_pool(k + 1) == (k == 512 ? 0u : 4 * k));
+        static_assert(fp::brute_margin_safe(1.0f, 0.0f, 4096, true) && !fp::brute_margin_safe(1.0f, 1.0f, 1, true), "the rule is a constant expression");
+        EXPECT(fp::BRUTE_EXACT_NEVER == 0 && fp::BRUTE_EXACT_BY_RULE == 1 && fp::BRUTE_EXACT_ALWAYS == 2);
+    }
     if (failures) {
         std::printf("%d failures\n", failures);
         return 1;

@@ -40,6 +40,19 @@ def test_params_struct_layout_matches_header(tmp_path):
     assert C.sizeof(CosSearchStats) == sz_stats
 
 
+def test_brute_stats_struct_layout_matches_header(tmp_path):
+    from cosdata_amd._lib import CosBruteStats
+    src = tmp_path / "bs.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "cosdata_hip.h"\n'
+                   'int main(){printf("%zu %zu %zu %zu\\n", sizeof(cos_brute_stats), offsetof(cos_brute_stats, queries), '
+                   'offsetof(cos_brute_stats, exact_queries), offsetof(cos_brute_stats, pool));return 0;}\n')
+    exe = tmp_path / "bs"
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    sz, off_q, off_e, off_p = map(int, subprocess.check_output([str(exe)]).split())
+    assert C.sizeof(CosBruteStats) == sz == 16
+    assert (CosBruteStats.queries.offset, CosBruteStats.exact_queries.offset, CosBruteStats.pool.offset) == (off_q, off_e, off_p) == (4, 8, 12)
+
+
 def test_cxx_host_links_and_error_contract(tmp_path):
     exe = tmp_path / "abi_smoke"
     so_dir = os.path.join(ROOT, "cosdata_amd")

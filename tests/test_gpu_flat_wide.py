@@ -280,10 +280,10 @@ def _brute(shape):
 @pytest.mark.parametrize("shape", list(BRUTE_SHAPES))
 def test_bruteforce_wide_matches_oracle(shape, k):
     """both edges of the 128, 256, 512 and 1024 pools (2k = 66 / 128 | 130 / 256 | 258 / 512 | 514 / 1024).  Continuous random data:
-    the 2k-candidate margin is an argument about last-ulp differences between the MFMA's summation order and the reference's — a
-    candidate's GEMM score can move by a few ulps, so only entries within a few ulps of the k-th exact score can change sides, and a
-    pool of 2k keeps k more than needed.  It is not an argument about exact duplicates: more than k copies of one row could fill the
-    margin, so duplicated corpora belong to the code scan's tie test, not here."""
+    a candidate's GEMM score differs from its reference-order score by a few ulps, so only entries within a few ulps of the k-th exact
+    score can change sides, and here the k-th and the P-th score lie thousands of error bounds apart: the pool of P >= 2k holds the
+    answer and the margin rule (flat_plan.h brute_margin_safe) flags no query.  Corpora where that is NOT so — more than P - k copies
+    or scaled copies of one row — take the library's exact path and are the subject of test_gpu_brute_near_copies.py."""
     Q, ix, (oids, osc) = _brute(shape)
     ids, sc = ix.bruteforce_topk(Q, k)
     assert np.array_equal(ids, oids[:, :k])
