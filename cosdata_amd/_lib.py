@@ -60,6 +60,11 @@ class CosWalkSplit(C.Structure):
     ]
 
 
+class CosPairStats(C.Structure):
+    """cos_pair_stats: the pair walk of the last batch of a stream (all zero when it did not walk in pairs)"""
+    _fields_ = [("struct_size", C.c_uint32), ("cache_entries", C.c_uint32), ("cache_hits", C.c_uint64), ("row_evals", C.c_uint64)]
+
+
 class CosTimingSummary(C.Structure):
     _fields_ = [("launches", C.c_uint32), ("prep_ms_sum", C.c_float), ("walk_ms_sum", C.c_float), ("finalize_ms_sum", C.c_float),
                 ("walk_ms_min", C.c_float), ("walk_ms_max", C.c_float)]
@@ -139,7 +144,7 @@ ABI_SYMBOLS = [
     "cos_index_download_graph_level", "cos_index_download_codes", "cos_index_download_root", "cos_index_build", "cos_index_append", "cos_index_delete", "cos_index_restore_link_state", "cos_index_release_link_state", "cos_index_enable_metadata", "cos_index_upload_meta_nodes", "cos_index_upload_meta_graph_level", "cos_index_build_meta", "cos_index_append_meta", "cos_index_meta_level_count", "cos_index_download_meta_graph_level", "cos_search_filtered_batch",
     "cos_ann_search_filtered_batch", "cos_index_load_reference_dir", "cos_reference_dir_level_counts", "cos_reference_dir_read_level",
     "cos_search_batch", "cos_search_batch_device", "cos_ann_search_batch", "cos_index_set_coalescing", "cos_index_coalescing_stats", "cos_index_set_ef_search",
-    "cos_index_set_visited_mode", "cos_index_set_latency_mode", "cos_index_set_latency_waves", "cos_index_set_walk_order", "cos_index_walk_order_cuts", "cos_index_set_walk_table", "cos_index_walk_table_info", "cos_index_last_walk_split", "cos_index_enable_timing", "cos_index_last_stats", "cos_index_timing_summary", "cos_quantize_batch",
+    "cos_index_set_visited_mode", "cos_index_set_latency_mode", "cos_index_set_latency_waves", "cos_index_set_walk_order", "cos_index_walk_order_cuts", "cos_index_set_walk_table", "cos_index_walk_table_info", "cos_index_last_walk_split", "cos_index_last_pair_stats", "cos_index_enable_timing", "cos_index_last_stats", "cos_index_timing_summary", "cos_quantize_batch",
     "cos_code_bytes", "cos_sample_values_range", "cos_distance_batch", "cos_bruteforce_topk", "cos_flat_search_batch",
     "cos_flat_search_masked_batch", "cos_bruteforce_topk_masked", "cos_index_last_brute_stats", "cos_index_deleted_count", "cos_index_download_deleted", "cos_bm25_create", "cos_bm25_destroy",
     "cos_bm25_insert", "cos_bm25_delete", "cos_bm25_stats", "cos_bm25_download",
@@ -214,6 +219,7 @@ def lib():
         "cos_index_set_walk_table": [vp, u32, u32],
         "cos_index_walk_table_info": [vp, C.POINTER(u32), C.POINTER(u32)],
         "cos_index_last_walk_split": [vp, vp, C.POINTER(CosWalkSplit)],
+        "cos_index_last_pair_stats": [vp, vp, C.POINTER(CosPairStats)],
         "cos_index_timing_summary": [vp, vp, C.POINTER(CosTimingSummary)],
         "cos_quantize_batch": [u32, u32, u32, f32, f32, vp, u32, vp, vp],
         "cos_sample_values_range": [vp, u32, u32, f32, C.POINTER(f32), C.POINTER(f32)],

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "engine_internal.h"
+#include "walk_pair_plan.h"
 
 using namespace cosdev;
 
@@ -759,6 +760,9 @@ static constexpr long long WALK_UP_TABLE_DEFAULT = 1;
 // The throughput kernel's launches read the nested level table, one GEMM column per vector of the lowest table level (table_nested.h,
 // ensure_nested_table; tuning knob walk_table_nested): 1 = on graphs where that saves TABLE_NESTED_MIN_SAVED_COLS columns or more.
 static constexpr long long WALK_TABLE_NESTED_DEFAULT = 1;
+// The last range of an ordered launch walks two sorted neighbours per workgroup (kernels_walk_pair.hip, walk_pair_plan.h; tuning knobs
+// walk_pair, walk_pair_cache).  Defaults: DESIGN.md §0.4.
+static constexpr long long WALK_PAIR_DEFAULT = 1, WALK_PAIR_CACHE_DEFAULT = 512;
 static u32 walk_table_nested_mode() {
     return (u32)std::min<long long>(std::max<long long>(cosdev::tune_or(cosdev::TUNE_WALK_TABLE_NESTED, WALK_TABLE_NESTED_DEFAULT), 0), 2);
 }
@@ -1140,6 +1144,7 @@ struct SearchLaunch {
     // ... of the nested table (plan.table_nested): LevelDev::adj_tab / tab_col / tab_bits of its levels
     const u32 *adj_tab[cosdev::MAX_LEVELS] = {}, *tab_col[cosdev::MAX_LEVELS] = {};
     u32 tab_bits[cosdev::MAX_LEVELS] = {};
+    u32 pair_cache = 0; // walk_pair_plan: cache entries per query, 0 = walk_kernel walks the last range too
     // the order keys (plan.ordered)
     u32 n_keys = 0, key_level[cosdev::MAX_LEVELS], key_n[cosdev::MAX_LEVELS];
     const u32 *order_rank[cosdev::MAX_LEVELS];
@@ -1168,6 +1173,7 @@ static int32_t get_workspace(cos_index *ix, void *key, hipStream_t st, u32 B, u3
         HIP_TRY(w->walk_status.alloc(cap));
         HIP_TRY(w->stats.alloc((size_t)cap * 4));
         HIP_TRY(w->stats2.alloc((size_t)cap * 4));
+        HIP_TRY(w->pair_stats.alloc((size_t)cap * 2));
         HIP_TRY(w->qsums.alloc(cap));
         HIP_TRY(w->tab_queue.alloc(16));
         if (ix->eng == ENG_Q2) HIP_TRY(w->qdig.alloc((size_t)cap * (ix->row_stride / 16) * 64)); // the table GEMM's digit rows of the queries
@@ -1261,6 +1267,14 @@ static int32_t get_workspace(cos_index *ix, void *key, hipStream_t st, u32 B, u3
             L->key_n[L->n_keys] = ix->order_rank_n[l];
             L->order_rank[L->n_keys++] = ix->d_order_rank[l];
         }
+    if (L->plan.ordered && L->n_keys) {
+        cosdev::WalkPairIn pi{};
+        pi.mode = (u32)std::min<long long>(std::max<long long>(cosdev::tune_or(cosdev::TUNE_WALK_PAIR, WALK_PAIR_DEFAULT), 0), 2);
+        pi.cache_entries = (u32)std::min<long long>(std::max<long long>(cosdev::tune_or(cosdev::TUNE_WALK_PAIR_CACHE, WALK_PAIR_CACHE_DEFAULT), 0), 0xFFFFFFFFll);
+        pi.last_first = L->key_level[L->n_keys - 1] - 1u; // (a key level is >= 1)
+        pi.n_vectors = ix->n;
+        L->pair_cache = cosdev::walk_pair_plan(in, L->plan, pi);
+    }
     if (host_api && (size_t)top_k * w->capB > (size_t)w->cap_topk * w->capB) {
         w->cap_topk = 0;
         HIP_TRY(w->d_out_ids.alloc((size_t)w->capB * top_k));
@@ -1313,6 +1327,7 @@ static int32_t run_search(cos_index *ix, Workspace *w, const SearchLaunch &L, co
     // was a 0.24 ms launch of its own between the end of the GEMM and the start of the upper range, on the chain that decides the step.
     // Stream order still puts it behind this workspace's previous launch.
     HIP_TRY(hipMemsetAsync(w->stats2, 0, (size_t)B * 32, st));
+    if (L.pair_cache) HIP_TRY(hipMemsetAsync(w->pair_stats, 0, (size_t)B * 16, st)); // (a wave that returns early writes nothing)
     // Level table: on the caller's stream, i.e. BEFORE the walk takes its place in the walk chain — the GEMM of this launch runs next
     // to the previous launch's walk.  (Round 5 also issued it inside the chain, right in front of its own walk, where it shares the
     // chip with nobody: 7.07-7.12 against 6.69 ms per step — the overlap hides 0.4 ms.  profiles/r05_table_gemm_in_chain_probe_not_kept.jsonl)
@@ -1396,11 +1411,13 @@ static int32_t run_search(cos_index *ix, Workspace *w, const SearchLaunch &L, co
             wa.key_n = last ? 0u : L.key_n[i];
             wa.order_rank = last ? nullptr : L.order_rank[i];
             if (last && chained) HIP_TRY(hipEventRecord(w->last_range, s));
-            HIP_TRY(launch_walk(ix->eng, dev, wa, plan.kernel, s));
+            if (last && L.pair_cache) HIP_TRY(cosdev::launch_walk_pair(dev, wa, L.pair_cache, w->pair_stats, s));
+            else HIP_TRY(launch_walk(ix->eng, dev, wa, plan.kernel, s));
             if (last) break;
             if (chained && i == 0) HIP_TRY(hipEventRecord(w->upper_done, s));
             if (timed && i == 0) HIP_TRY(hipEventRecord(ev[6], s));
-            HIP_TRY(cosdev::launch_walk_order(w->order, B, L.key_n[i], ix->num_xcd, s));
+            // (the pair kernel's workgroups take two neighbours of the sorted order: the order in front of the last range is dealt in twos)
+            HIP_TRY(cosdev::launch_walk_order(w->order, B, L.key_n[i], ix->num_xcd, s, i + 1 == n_keys && L.pair_cache ? 2u : 1u));
             if (timed && i == 0) HIP_TRY(hipEventRecord(ev[7], s));
             wa.q_order = w->order.q_order;
             first = L.key_level[i] - 1;
@@ -1435,6 +1452,7 @@ static int32_t run_search(cos_index *ix, Workspace *w, const SearchLaunch &L, co
     w->lastB = B;
     w->timed = timed;
     w->last_plan = plan;
+    w->last_pair_cache = L.pair_cache;
     { std::lock_guard<std::mutex> g(ix->mu); ix->last_ws = w; }
     return COS_OK;
 }
@@ -1971,6 +1989,27 @@ extern "C" int32_t cos_index_last_walk_split(cos_index *ix, void *stream, cos_wa
     out->upper_evals = st[0] - s2[0];
     out->upper_expansions = st[1] - s2[1];
     out->upper_adj_bytes = st[2] - s2[2];
+    return COS_OK;
+}
+
+extern "C" int32_t cos_index_last_pair_stats(cos_index *ix, void *stream, cos_pair_stats *out) {
+    if (!ix || !out) return cos_fail(COS_ERR_INVALID, "null argument");
+    if (out->struct_size != sizeof(cos_pair_stats)) return cos_fail(COS_ERR_INVALID, "cos_pair_stats.struct_size mismatch");
+    memset(out, 0, sizeof(*out));
+    out->struct_size = sizeof(cos_pair_stats);
+    int32_t rc = cos_set_device(ix);
+    if (rc) return rc;
+    Workspace *w = find_workspace(ix, stream, true);
+    if (!w || w->lastB == 0) return cos_fail(COS_ERR_NOT_READY, "no batch has run on this stream");
+    if (w->last_pair_cache == 0u) return COS_OK;
+    HIP_TRY(hipDeviceSynchronize());
+    std::vector<u64> st((size_t)w->lastB * 2);
+    HIP_TRY(hipMemcpy(st.data(), w->pair_stats, st.size() * 8, hipMemcpyDeviceToHost));
+    out->cache_entries = w->last_pair_cache;
+    for (u32 b = 0; b < w->lastB; b++) {
+        out->cache_hits += st[(size_t)b * 2];
+        out->row_evals += st[(size_t)b * 2 + 1];
+    }
     return COS_OK;
 }
 

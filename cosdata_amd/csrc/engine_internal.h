@@ -59,7 +59,9 @@ struct WalkOrder {
     DevBuf tmp;                 // radix sort scratch
 };
 hipError_t walk_order_reserve(WalkOrder &o, u32 B); // synchronous (re)allocation
-hipError_t launch_walk_order(WalkOrder &o, u32 B, u32 key_max, u32 num_xcd, hipStream_t st);
+hipError_t launch_walk_order(WalkOrder &o, u32 B, u32 key_max, u32 num_xcd, hipStream_t st, u32 unit = 1u); // unit: queries per workgroup of the range below
+// the last range of an ordered launch, two sorted neighbours per workgroup (kernels_walk_pair.hip; walk_pair_plan.h decides)
+hipError_t launch_walk_pair(const IndexDev &ix, const WalkArgs &wa, u32 cache_entries, u64 *out_pair, hipStream_t st);
 // level table of the walk (kernels_flat.hip; WalkArgs::tab)
 hipError_t launch_level_table_gather(const uint8_t *codes, const float *mags, u64 row_stride, const u32 *node_vec, u32 n, u32 col0,
                                      uint8_t *tcodes, float *tmags, hipStream_t st);
@@ -168,6 +170,8 @@ struct Workspace {
     DevArr<int32_t> walk_status;
     DevArr<u64> stats;          // [B][4]
     DevArr<u64> stats2;         // [B][4] WalkArgs::out_stats2
+    DevArr<u64> pair_stats;     // [B][2] WalkPairArgs::out_pair (cos_index_last_pair_stats); last_pair_cache: the cache entries of the last launch, 0 = it did not walk in pairs
+    u32 last_pair_cache = 0;
     DevArr<float> tab;          // level table of this workspace's big launches [capB][tab_stride] (WalkArgs::tab), grown on demand
     DevArr<u32> qsums;          // [capB] code sums of the queries (the table GEMM's recentring term; written by quantize_rows_kernel)
     DevArr<u32> tab_queue;      // [1] next work item of the table GEMM in flight (level_table_areg), zeroed before its first part

@@ -139,6 +139,16 @@ struct WalkArgs {
     u32 *order_iota;       // [B] order_iota[b] = b (the values the sort carries), written with the key
 };
 
+// What walk_pair_kernel (kernels_walk_pair.hip) takes beside WalkArgs: the last range of an ordered launch walked by workgroups of two
+// waves, neighbours in the order (q_order[2b], q_order[2b + 1]), that share one small LDS cache of integer dots per query.
+struct WalkPairArgs {
+    u32 wave_bytes; // LDS of one wave: walk_kernel's layout, then its dot cache
+    u32 cache_off;  // ... where the cache starts in it (a multiple of 8)
+    u32 cache_bits; // log2 of the cache's 8-byte entries
+    u32 reserved;
+    u64 *out_pair;  // optional [B][2], by query: winners served by the cache, winners served by a fetched code row
+};
+
 // Parameter domains of the walk kernels.  walk_kernel (register pools of up to 64 x 16 keys, one lane per scanned slot) and the latency
 // kernels hold ef <= WALK_FAST_MAX_EF and <= 64 scanned slots per node; everything else the reference accepts (hnsw/types.rs:10-17,
 // config.toml:32) goes to walk_general_kernel (kernels_walk_general.hip), whose candidates live in ef x 8 bytes of one workgroup's LDS.

@@ -15,13 +15,22 @@
 namespace cosdev {
 
 // num_xcd: the device's XCD count (hipDeviceAttributeNumberOfXccs, read at cos_index_create; MI355X: 8 XCDs x 32 CUs)
-__global__ void deal_to_xcds_kernel(const u32 *__restrict__ sorted, u32 B, u32 num_xcd, u32 *__restrict__ q_order) {
+// unit: queries per workgroup of the launch that reads q_order — 1 (walk_kernel), or 2 (walk_pair_kernel: workgroup b walks q_order[2b]
+// and q_order[2b + 1], which must be neighbours in the sorted order).  The U = B / unit whole units are dealt; what is left of an odd
+// launch goes to the workgroup behind them.
+__global__ void deal_to_xcds_kernel(const u32 *__restrict__ sorted, u32 B, u32 num_xcd, u32 unit, u32 *__restrict__ q_order) {
     const u32 b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    // XCD x receives workgroups x, x + num_xcd, ...: B / num_xcd of them, one more for x < B % num_xcd.  Its run of the sorted order
+    const u32 U = B / unit;
+    if (b > U) return;
+    if (b == U) { // (unit 1: nothing is left)
+        for (u32 i = U * unit; i < B; i++) q_order[i] = sorted[i];
+        return;
+    }
+    // XCD x receives workgroups x, x + num_xcd, ...: U / num_xcd of them, one more for x < U % num_xcd.  Its run of the sorted order
     // starts after the runs of the XCDs before it.
-    const u32 q = B / num_xcd, r = B % num_xcd, x = b % num_xcd, j = b / num_xcd;
-    q_order[b] = sorted[x * q + (x < r ? x : r) + j];
+    const u32 q = U / num_xcd, r = U % num_xcd, x = b % num_xcd, j = b / num_xcd;
+    const u32 src = x * q + (x < r ? x : r) + j;
+    for (u32 k = 0; k < unit; k++) q_order[b * unit + k] = sorted[src * unit + k];
 }
 
 hipError_t walk_order_reserve(WalkOrder &o, u32 B) {
@@ -39,8 +48,8 @@ hipError_t walk_order_reserve(WalkOrder &o, u32 B) {
 }
 
 // order_key[0..B) / iota[0..B) (both written by the upper-level phase; keys <= key_max) -> q_order[0..B), all on `st`
-hipError_t launch_walk_order(WalkOrder &o, u32 B, u32 key_max, u32 num_xcd, hipStream_t st) {
-    if (B > o.cap) return hipErrorInvalidValue;
+hipError_t launch_walk_order(WalkOrder &o, u32 B, u32 key_max, u32 num_xcd, hipStream_t st, u32 unit) {
+    if (B > o.cap || unit == 0u) return hipErrorInvalidValue;
     int end_bit = 1;
     while (end_bit < 32 && (key_max >> end_bit)) end_bit++; // radix passes over the bits the keys have
     size_t bytes = 0;
@@ -50,7 +59,7 @@ hipError_t launch_walk_order(WalkOrder &o, u32 B, u32 key_max, u32 num_xcd, hipS
     bytes = o.tmp.cap;
     e = hipcub::DeviceRadixSort::SortPairs(o.tmp.p, bytes, o.order_key.p, o.keys_sorted.p, o.iota.p, o.vals_sorted.p, (int)B, 0, end_bit, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(deal_to_xcds_kernel, dim3((B + 255) / 256), dim3(256), 0, st, o.vals_sorted.p, B, num_xcd ? num_xcd : 1u, o.q_order.p);
+    hipLaunchKernelGGL(deal_to_xcds_kernel, dim3((B / unit + 1u + 255u) / 256u), dim3(256), 0, st, o.vals_sorted.p, B, num_xcd ? num_xcd : 1u, unit, o.q_order.p);
     return hipGetLastError();
 }
 

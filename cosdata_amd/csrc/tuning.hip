@@ -17,6 +17,7 @@ const char *const NAMES[TUNE_COUNT] = {
     "walk_lat_la", "walk_lat4_e", "finalize_fast", "shardset_force_rccl", "build_profile",
     "walk_merge_min", "walk_adj_mag", "walk_table_rule_c", "walk_table_after_sort", "walk_upper_lds_pad", "walk_r2", "finalize_wide_max_b", "flat_fp4_w8",
     "walk_table_early_wgs", "walk_up_table", "walk_table_nested", "flat_brute_exact",
+    "walk_pair", "walk_pair_cache",
 };
 std::atomic<long long> g_values[TUNE_COUNT];
 std::once_flag g_once;

@@ -2,6 +2,22 @@
 // by kernels_walk.hip; the rules it shares with the other walk kernels are in walk_common.h.
 // The row level directly under the level table reads table columns for the neighbours that have a node one level up (LevelDev::adj_up,
 // `UPT` below): u8 codes only — quaternary codes walk that level as they did, every winner from its code row.
+//
+// kernels_walk_pair.hip includes this text a second time with WALK_PAIR defined: the same walk as walk_pair_kernel, a workgroup of TWO
+// waves that walk two neighbours of the sorted order (the last range of an ordered launch).  Each wave walks its own query exactly as
+// below — own pool, filter, popped list, window; what `PAIR` adds is a small LDS cache of integer dots per query that the PARTNER
+// fills: every code row a wave fetches is dotted with both queries, and a winner whose row the partner has already fetched costs one
+// LDS read instead of the row.  Everything of it sits under `if constexpr (PAIR)`: walk_kernel's instantiations compile to what they were.
+#ifdef WALK_PAIR
+#define WALK_KERNEL_NAME walk_pair_kernel
+#define WALK_PAIR_PARAM , const WalkPairArgs pa
+constexpr bool PAIR = true;
+#else
+#define WALK_KERNEL_NAME walk_kernel
+#define WALK_PAIR_PARAM
+constexpr bool PAIR = false;
+#endif
+constexpr u32 PAIR_HASH = 0x9E3779B1u; // the cache's slot of vector row r: the top WalkPairArgs::cache_bits bits of r * PAIR_HASH
 constexpr int PB = 4; // code rows in flight per lane group before the dots are consumed
 constexpr int LA = 4; // lookahead window: adjacency rows prefetched per round
 // G = 64 path: code rows in flight per wave = template parameter PB64.  An expansion discovers ~7 new neighbours on average:
@@ -27,18 +43,27 @@ struct WalkSmem {
 };
 
 template <int ENG, int CH, int R, bool G64, bool EXACT, int PB64 = 4>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH >= 3 ? (R <= 4 ? (CH == 3 ? 4 : 3) : (CH == 3 ? 3 : 2)) : (R == 1 ? ((ENG == ENG_U8 && CH == 1 && G64 && !EXACT) ? 7 : 6) : (R <= 4 ? 5 : 4)), 8))) void walk_kernel(const IndexDev ix, const WalkArgs wa) {
+// (a pair wave's LDS — 10.5 KB with a 512-entry cache — caps the resident waves at 14 per CU: its registers are not what decides, 4 waves per SIMD are asked for)
+__global__ __launch_bounds__(PAIR ? 128 : 64) __attribute__((amdgpu_waves_per_eu(PAIR ? 4 : CH >= 3 ? (R <= 4 ? (CH == 3 ? 4 : 3) : (CH == 3 ? 3 : 2)) : (R == 1 ? ((ENG == ENG_U8 && CH == 1 && G64 && !EXACT) ? 7 : 6) : (R <= 4 ? 5 : 4)), 8))) void WALK_KERNEL_NAME(const IndexDev ix, const WalkArgs wa WALK_PAIR_PARAM) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const int lane = threadIdx.x;
-    if (blockIdx.x >= wa.B) return;
-    const u32 qi = wa.q_order ? wa.q_order[blockIdx.x] : blockIdx.x; // split walk: locality order (engine_types.h)
+#ifndef WALK_PAIR
+    constexpr WalkPairArgs pa{}; // (never read: every use is under `if constexpr (PAIR)`)
+#endif
+    const int lane = PAIR ? (int)(threadIdx.x & 63u) : (int)threadIdx.x;
+    u32 wv = 0; // pair: the wave of the workgroup (wave-uniform, in an SGPR)
+    if constexpr (PAIR) wv = uniform_u32(threadIdx.x >> 6);
+    const u32 slot = PAIR ? blockIdx.x * 2u + wv : blockIdx.x; // position in the launch's order: a pair's waves take two neighbours
+    if (slot >= wa.B) return;
+    const u32 qi = wa.q_order ? wa.q_order[slot] : slot; // split walk: locality order (engine_types.h)
     const bool resume = wa.phase != 0u && wa.level_first < ix.num_layers; // a level range below the top: entry node from the range above
     if (resume && wa.out_status[qi] != COS_OK) return;                   // failed in the levels above: nothing below is read
+                                                                         // (pair: no barrier anywhere, the partner walks alone)
 
     const u32 Mmax = wa.smem_mmax; // the widest row among the levels of THIS launch (launch_walk_r)
     WalkSmem sm;
     {
         unsigned char *p = smem_raw;
+        if constexpr (PAIR) p += wv * pa.wave_bytes; // every wave of a pair has walk_kernel's layout to itself, its dot cache behind it
         sm.vis = (u32 *)p;      p += (size_t)Mmax * 8;
         sm.res = (u64 *)p;      p += (size_t)wa.ef * 8;
         sm.wl_vec = (u32 *)p;   p += 64 * 4;
@@ -99,6 +124,36 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH >= 3 ? (R
     for (int c = 0; c < CH; c++) {
         const u32 chunk = (u32)lane + (u32)c * 64u;
         loff64[c] = (chunk < ix.nchunks ? chunk : 0u) * 16u;
+    }
+
+    // Pair: the partner's query chunk beside qreg, and the two dot caches — 8-byte entries (vector row << 32 | integer dot), read and
+    // written whole, so a tag never pairs with another row's dot.  A wave fills ITS cache with the empty tag before its first probe
+    // (LDS arrives uninitialised); an insert of the partner's that the fill wipes is only a lost hit.  Entries never go stale: queries
+    // and rows are fixed for the launch and a dot does not depend on the level.
+    uint4 qreg2[CH];
+    u32 partner = 0; // wave-uniform: the neighbour in the order exists (odd B: the last wave has none)
+    u64 *cache_mine = nullptr, *cache_partner = nullptr;
+    u32 cache_shift = 0;
+    u64 n_hits = 0, n_rows = 0; // winners served by the cache / by a fetched code row
+    if constexpr (PAIR) {
+        static_assert(!PAIR || (!FLOAT_ENG && G64 && !EXACT), "the pair walk exists on the one-row-per-pass path with the reference filter");
+        cache_mine = (u64 *)(smem_raw + wv * pa.wave_bytes + pa.cache_off);
+        cache_partner = (u64 *)(smem_raw + (wv ^ 1u) * pa.wave_bytes + pa.cache_off);
+        cache_shift = 32u - pa.cache_bits;
+        for (u32 i = (u32)lane; i < (1u << pa.cache_bits); i += 64u)
+            __hip_atomic_store(&cache_mine[i], (u64)ROW_EMPTY << 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        partner = (slot ^ 1u) < wa.B ? 1u : 0u;
+#pragma unroll
+        for (int c = 0; c < CH; c++) qreg2[c] = make_uint4(0, 0, 0, 0);
+        if (partner) {
+            const u32 qi2 = wa.q_order ? wa.q_order[slot ^ 1u] : (slot ^ 1u);
+            const uint8_t *qcode2 = wa.qcodes + (u64)(wa.q_rows ? wa.q_rows[qi2] : qi2) * ix.row_stride;
+#pragma unroll
+            for (int c = 0; c < CH; c++) {
+                const u32 chunk = (u32)lig + (u32)c * (u32)G;
+                if (chunk < ix.nchunks) qreg2[c] = *(const uint4 *)(qcode2 + (u64)chunk * 16);
+            }
+        }
     }
 
     u64 n_evals = 0, n_exp = 0, adj_bytes = 0, n_rounds = 0, n_tab = 0;
@@ -452,9 +507,33 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH >= 3 ? (R
                             m = wmask & ~tmask;
                         }
                     }
+                    if constexpr (PAIR) {
+                        // Pair: every winner left reads ITS cache at its row's slot.  A hit is the integer dot the partner computed from
+                        // the same row and this query's chunk — `(float)` of it is the value the row block below would form — so the hits
+                        // (hmask) are committed like tmask above, before the row winners: table winners, cache hits, rows.  The three
+                        // points of the comment above hold for any split of an expansion's winners into groups committed one after the
+                        // other (tests/test_walk_pair_model.py).
+                        if (m && !failed) {
+                            u64 ent = 0;
+                            if (__builtin_amdgcn_inverse_ballot_w64(m))
+                                ent = __hip_atomic_load(&cache_mine[(nb_vec * PAIR_HASH) >> cache_shift], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                            const u64 hmask = m & ballot64((u32)(ent >> 32) == nb_vec);
+                            if (hmask) {
+                                const float dotv = (float)(u32)ent;
+                                bool badl;
+                                const float sim = cosine_or_dot<ENG == ENG_U8>(metric, dotv, qmag, magw, badl);
+                                if (hmask & ballot64(badl)) failed = 1;
+                                else commit(hmask, metric_key(metric, sim), nb_node);
+                                n_hits += (u64)__popcll(hmask);
+                                m &= ~hmask;
+                            }
+                        }
+                        if (!failed) n_rows += (u64)__popcll(m);
+                    }
                     while (m && !failed) {
                         u32 lsel = 0;  // landing lane of winner p of this block <- 4 * (the lane that owns the winner): a ds_bpermute address
                         u32 tot = 0;   // landing lanes: the winner's integer dot
+                        u32 tot2 = 0;  // pair: the PARTNER's integer dot with the same row
                         u64 leadmask = 0; // first lane of the landing group of every winner of this block
                         // A block of up to NP winners, row p landing in lanes p*(64/NP)...: the rows are fetched together, dotted,
                         // and the NP partial-sum vectors reduced at once.  The dots of rows a short block does not have are
@@ -491,6 +570,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH >= 3 ? (R
                                 }
                             });
                             tot = wave_reduce_rows<NP>(acc);
+                            if constexpr (PAIR) {
+                                if (partner) { // the rows are in registers: the partner's dots cost the v_dot4 and one more reduce (the range is bound by the fabric)
+                                    u32 acc2[NP];
+                                    static_for<0, NP>([&](auto pc) {
+                                        constexpr int p = decltype(pc)::value;
+                                        acc2[p] = 0;
+                                        if (p < cnt) {
+                                            asm volatile("");
+#pragma unroll
+                                            for (int c = 0; c < CH; c++) acc2[p] = chunk_dot<ENG>(qreg2[c], buf[p][c], acc2[p]);
+                                        }
+                                    });
+                                    tot2 = wave_reduce_rows<NP>(acc2);
+                                }
+                            }
                             constexpr u64 firsts = NP == 8 ? 0x0101010101010101ull : 0x0001000100010001ull;
                             leadmask = cnt == NP ? firsts : firsts & ((1ull << (cnt * LS)) - 1ull);
                         };
@@ -503,6 +597,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH >= 3 ? (R
                         // |v| and node index of the block's winners move to the landing lanes (two ds_bpermute)
                         const float magv = __uint_as_float((u32)__builtin_amdgcn_ds_bpermute((int)lsel, (int)__float_as_uint(magw)));
                         const u32 nodev = (u32)__builtin_amdgcn_ds_bpermute((int)lsel, (int)nb_node);
+                        if constexpr (PAIR) {
+                            if (partner) { // the row's id comes to the landing lane too, and (row, partner's dot) goes into the partner's cache
+                                const u32 rowv = (u32)__builtin_amdgcn_ds_bpermute((int)lsel, (int)nb_vec);
+                                if (__builtin_amdgcn_inverse_ballot_w64(leadmask))
+                                    __hip_atomic_store(&cache_partner[(rowv * PAIR_HASH) >> cache_shift], ((u64)rowv << 32) | (u64)tot2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                            }
+                        }
                         const float dotv = (float)tot; // integer dot `as f32` (RNE)
                         // one vector epilogue for the whole block
                         bool badl;
@@ -707,6 +808,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH >= 3 ? (R
                 wa.out_stats2[(u64)qi * 4 + 2] = adj_bytes;
             }
             wa.out_stats2[(u64)qi * 4 + 3] = n_tab + (resume ? wa.out_stats2[(u64)qi * 4 + 3] : 0ull);
+        }
+        if constexpr (PAIR) {
+            if (pa.out_pair) {
+                pa.out_pair[(u64)qi * 2 + 0] = n_hits;
+                pa.out_pair[(u64)qi * 2 + 1] = n_rows;
+            }
         }
     }
 }

@@ -23,7 +23,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import CosdataError, CosFlatStats, CosParams, CosSearchStats, CosTimingSummary, CosWalkSplit, check
+from ._lib import CosdataError, CosFlatStats, CosPairStats, CosParams, CosSearchStats, CosTimingSummary, CosWalkSplit, check
 
 ROOT_ID, QUERY_ID, SLOT_EMPTY = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD
 VISITED_REF, VISITED_EXACT = 0, 1
@@ -328,6 +328,14 @@ class HNSWIndex:
         st = CosWalkSplit()
         st.struct_size = C.sizeof(CosWalkSplit)
         check(_lib.lib().cos_index_last_walk_split(self._h, C.c_void_p(stream), C.byref(st)))
+        return st
+
+    def last_pair_stats(self, stream: int = 0) -> CosPairStats:
+        """The pair walk of the last batch on `stream` (tuning knob walk_pair): cache hits, code rows fetched, cache entries per query;
+        all zero when the launch did not walk in pairs."""
+        st = CosPairStats()
+        st.struct_size = C.sizeof(CosPairStats)
+        check(_lib.lib().cos_index_last_pair_stats(self._h, C.c_void_p(stream), C.byref(st)))
         return st
 
     def batch_search(self, queries, top_k: int, return_status: bool = False):

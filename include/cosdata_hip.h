@@ -310,6 +310,16 @@ typedef struct {
     uint64_t lower_evals, lower_expansions, lower_adj_bytes; /* levels below the cut (or the whole walk) */
 } cos_walk_split;
 int32_t cos_index_last_walk_split(cos_index *ix, void *stream, cos_walk_split *out);
+/* The pair walk of the last completed batch on `stream` (tuning knob walk_pair: the levels below the cut of a big launch walked two
+ * sorted neighbours per workgroup, which share their integer dots through LDS): how many of that range's evaluations found their dot
+ * in the cache, how many fetched a code row, and the cache entries per query.  All three are 0 when the launch did not walk in pairs.
+ * Hits depend on how the two waves of a workgroup interleave: they may differ from run to run, results never do. */
+typedef struct {
+    uint32_t struct_size;       /* in: sizeof(cos_pair_stats) */
+    uint32_t cache_entries;
+    uint64_t cache_hits, row_evals;
+} cos_pair_stats;
+int32_t cos_index_last_pair_stats(cos_index *ix, void *stream, cos_pair_stats *out);
 /* counters + kernel times of the last completed batch on `stream` (NULL = the host API's stream).  A lone big cos_search_batch call
  * runs as up to four chunk launches (each with its own workspace): with stream == NULL the figures then describe the LAST chunk only
  * (about a quarter of the call's queries; cos_walk_split.queries says how many) — whether a call is chunked depends on what else is

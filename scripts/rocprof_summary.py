@@ -5,7 +5,7 @@ import sys
 
 
 def short(name):
-    for key in ("walk_lat4_kernel", "walk_lat_kernel", "walk_meta_kernel", "walk_spec_kernel", "walk_kernel", "finalize_kernel", "quantize_rows_kernel", "scatter_rows_kernel",
+    for key in ("walk_lat4_kernel", "walk_lat_kernel", "walk_meta_kernel", "walk_spec_kernel", "walk_pair_kernel", "walk_kernel", "finalize_kernel", "quantize_rows_kernel", "scatter_rows_kernel",
                 "merge_topk_kernel", "deal_to_xcds_kernel", "level_table_areg", "flat_", "bm25_", "rrf_kernel", "sparse_tile_kernel", "sparse_finish_kernel", "link_kernel", "claim_kernel", "evict_kernel"):
         if key in name:
             i = name.index(key)
@@ -74,7 +74,8 @@ def main(path):
     parts = {}
     prev = {}
     for name, grid, dur, lane in seq:
-        if ("walk_kernel" in name or "walk_spec_kernel" in name) and grid >= 4096:
+        # (walk_pair_kernel: two queries per workgroup, so half the grid of the launch it belongs to)
+        if (("walk_kernel" in name or "walk_spec_kernel" in name) and grid >= 4096) or ("walk_pair_kernel" in name and grid >= 2048):
             after_deal = "deal_to_xcds" in prev.get(lane, "")
             part = "lower levels, after deal_to_xcds (locality order)" if after_deal else "upper levels (arrival order) or unsplit walk"
             parts.setdefault((short(name), grid, part), []).append(dur)
@@ -103,16 +104,19 @@ def main(path):
         ocol = next((c for c in ("dispatch_id", "start", "id") if c in ccols), None)
         if ocol and any("after deal_to_xcds" in k[2] for k in parts):
             rows = cur.execute(f"select kernel_name, grid_size/workgroup_size, counter_name, value, {ocol} from counters_collection "
-                               f"where (kernel_name like '%walk_kernel%' or kernel_name like '%walk_spec_kernel%') and grid_size/workgroup_size >= 4096 order by {ocol}").fetchall()
+                               f"where (kernel_name like '%walk_kernel%' or kernel_name like '%walk_spec_kernel%' or kernel_name like '%walk_pair_kernel%') "
+                               f"and grid_size/workgroup_size >= 4096 order by {ocol}").fetchall()
             seen, acc = {}, {}
             for name, grid, cn, val, oid in rows:
                 # (above ef 64 the two level ranges are different instantiations — four / eight row buffers —: the alternation is over the
                 # walk kernel's big dispatches whatever their template arguments)
-                key = (short(name).split("<")[0] + "<...> big dispatches", grid, cn)
-                idx = seen.setdefault(key, {})
+                # ... and whichever kernel walks the lower range (walk_pair_kernel where the plan pairs): the position is counted over all
+                # of them, the row is kept per kernel family, so a trace that holds both kinds of lower range does not mix them
+                idx = seen.setdefault((grid * 2 if "walk_pair_kernel" in name else grid, cn), {})  # (one sequence per launch size in QUERIES)
                 if oid not in idx:
                     idx[oid] = len(idx)
                 part = "upper range (even dispatches)" if idx[oid] % 2 == 0 else "lower range (odd dispatches)"
+                key = (short(name).split("<")[0] + "<...> big dispatches", grid, cn)
                 a = acc.setdefault(key + (part,), [0, 0.0])
                 a[0] += 1
                 a[1] += val
