@@ -42,26 +42,28 @@ def four_masks():
     return np.stack([keep_mask(k) for k in KEEPS] + [np.ones(N, bool)])
 
 
-def oracle_index(X, storage, metric=O.METRIC_COSINE):
+def oracle_index(X, storage, metric=O.METRIC_COSINE, values_range=(-1.0, 1.0)):
     kind, res = STORAGES[storage]
-    return O.OracleIndex(O.HNSWParams(dim=X.shape[1], metric=metric, storage=kind, resolution=res, num_layers=3)).set_vectors(X)
+    p = O.HNSWParams(dim=X.shape[1], metric=metric, storage=kind, resolution=res, num_layers=3, range_lo=values_range[0], range_hi=values_range[1])
+    return O.OracleIndex(p).set_vectors(X)
 
 
-def subset_flat(X, Q, storage, live, top_k, metric=O.METRIC_COSINE, key=None):
+def subset_flat(X, Q, storage, live, top_k, metric=O.METRIC_COSINE, key=None, values_range=(-1.0, 1.0)):
     """the oracle's flat search over the rows X[live], ids mapped back -> (ids [B][top_k], scores, counts); counts = min(top_k, live rows),
-    checked, so that a bad corpus cannot pass for a device bug.  `key` names (X, Q, live) for the cache; None = not cached."""
+    checked, so that a bad corpus cannot pass for a device bug.  `key` names (X, Q, live) for the cache; None = not cached.
+    `values_range`: the u8 quantizer's (lo, hi); the default is the index's default."""
     def make():
         rows = np.flatnonzero(live).astype(np.uint32)
         B = Q.shape[0]
         if rows.size == 0:
             return np.full((B, top_k), 0xFFFFFFFF, np.uint32), np.zeros((B, top_k), np.float32), np.zeros(B, np.uint32)
-        ids, sc, cnt = oracle_index(np.ascontiguousarray(X[rows]), storage, metric).flat_search_batch(Q, top_k, threads=8)   # raises unless COSO_OK
+        ids, sc, cnt = oracle_index(np.ascontiguousarray(X[rows]), storage, metric, values_range).flat_search_batch(Q, top_k, threads=8)   # raises unless COSO_OK
         assert (cnt == min(top_k, rows.size)).all()
         out = np.full_like(ids, 0xFFFFFFFF)
         for b in range(B):
             out[b, :cnt[b]] = rows[ids[b, :cnt[b]]]
         return out, sc, cnt
-    return make() if key is None else _memo(("flat", key, storage, top_k, metric), make)
+    return make() if key is None else _memo(("flat", key, storage, top_k, metric, tuple(values_range)), make)
 
 
 def subset_brute(X, Q, live, k, key=None):

@@ -202,6 +202,57 @@ def test_auto_quantization_sampler_matches_oracle():
         assert ca.sample_values_range(x, 5.0) == O.sample_values_range(x, 5.0)
 
 
+def _sampler_edge_inputs():
+    """(name, sample [rows][dim], margin, expected range or None) that Gaussian draws never give.  The expectations state the rule
+    (strict comparisons, `<=` on the tail share, -1 / 1 when no threshold holds); None = only the oracle says"""
+    F = np.float32
+    T = [F(t) for t in (0.025, 0.05, 0.1, 0.2, 0.3, 0.4, 0.5)]
+    up = T[1:] + [F(1.0)]
+    cases = []
+    for i, t in enumerate(T):                                    # 11 of 1000 values (1.1 %) on, just above and just below a threshold
+        for what, v, want in (("on", t, t), ("above", np.nextafter(t, F(1)), up[i]), ("below", np.nextafter(t, F(0)), t)):
+            x = np.zeros(1000, F)
+            x[::97][:11] = v
+            cases.append((f"{what} {t}", x.reshape(10, 100), 1.0, (-0.025, float(want))))
+            cases.append((f"{what} -{t}", -x.reshape(10, 100), 1.0, (-float(want), 0.025)))
+    x = np.zeros(1000, F)
+    x[:10], x[500:510] = 0.7, -0.7                               # a tail share of exactly clamp_margin_percent: 10 of 1000, `<=` holds
+    cases.append(("share on the margin", x.reshape(4, 250), 1.0, (-0.025, 0.025)))
+    x = np.zeros(1000, F)
+    x[:11], x[500:510] = 0.7, -0.7                               # ... and one value more above
+    cases.append(("share above the margin", x.reshape(4, 250), 1.0, (-0.025, 1.0)))
+    x = np.zeros(1000, F)
+    x[:20], x[20:40], x[40:60] = np.nan, np.inf, -np.inf         # NaN is neither above nor below; the infinities are both tails' members
+    cases.append(("NaN and infinities", x.reshape(10, 100), 1.0, (-1.0, 1.0)))
+    cases.append(("NaN alone", np.full((3, 7), np.nan, F), 1.0, (-0.025, 0.025)))
+    r = np.random.default_rng(8)
+    x = np.abs(r.standard_normal((200, 64))).astype(F) * F(0.15)
+    x[::3] *= F(-0.1)                                            # skewed: a long positive tail, a short negative one
+    cases.append(("skewed", x, 1.0, None))
+    cases.append(("skewed, margin 5", x, 5.0, None))
+    for total in (1, 255, 257, 2048 * 256 + 3):                  # one lane; a ragged last wave; a second wave; a grid-stride tail of three
+        k = total // 100 + 1                                     # the tail's share exceeds 1 % by the LAST elements alone
+        x = np.zeros(total, F)
+        x[total - k:] = 0.06
+        cases.append((f"{total} values", x.reshape(1, total), 1.0, (-0.025, 0.1)))
+        cases.append((f"{total} values, last one zero", np.concatenate([x[:-1], [F(0)]]).reshape(total, 1), 1.0, (-0.025, 0.025)))
+    return cases
+
+
+def test_auto_quantization_sampler_edge_inputs_match_oracle():
+    """values on the thresholds and their f32 neighbours, a tail share that lands on the margin, NaN and +-inf, a sample with
+    lo != -hi, and element counts around a wave and past the grid (the last elements decide)"""
+    import cosdata_amd as ca
+    asym = 0
+    for name, x, margin, want in _sampler_edge_inputs():
+        o = O.sample_values_range(x, margin)
+        if want is not None:
+            assert o == tuple(float(np.float32(w)) for w in want), (name, o, want)
+        assert ca.sample_values_range(x, margin) == o, (name, o)
+        asym += o[0] != -o[1]
+    assert asym > 20
+
+
 ALL_STORAGES = [("u8", O.STORAGE_U8, 0), ("bin", O.STORAGE_SUBBYTE, 1), ("q2", O.STORAGE_SUBBYTE, 2), ("oct", O.STORAGE_SUBBYTE, 3),
                 ("f16", O.STORAGE_F16, 0), ("f32", O.STORAGE_F32, 0)]
 

@@ -26,16 +26,24 @@ BASE = dict(walk_up_table=2, walk_adj_mag=2)
 
 
 @functools.lru_cache(maxsize=None)
-def _graph(dim, m0, m):
+def _corpus(dim):
+    X = H.clustered_corpus(N, dim, n_centers=24, seed=1300 + dim)
+    X.setflags(write=False)
+    return X
+
+
+@functools.lru_cache(maxsize=None)
+def _graph(dim, m0, m, values_range=(-1.0, 1.0)):
     """corpus, oracle index over a graph the device builder made, and the device index the tests search (same graph, uploaded)"""
     import cosdata_amd as ca
     from cosdata_amd import _lib
-    X = H.clustered_corpus(N, dim, n_centers=24, seed=1300 + dim)
-    X.setflags(write=False)
+    X = _corpus(dim)
+    lo, hi = values_range
     hp = ca.HNSWHyperParams(num_layers=LAYERS, ef_construction=64, ef_search=112, level_0_neighbors_count=m0, neighbors_count=m)
-    bix = ca.HNSWIndex(dim, hp, ca.DistanceMetric.Cosine, ca.StorageType.UnsignedByte(), seed=5)
+    bix = ca.HNSWIndex(dim, hp, ca.DistanceMetric.Cosine, ca.StorageType.UnsignedByte(), (lo, hi), seed=5)
     bix.upload_vectors(X).build(512)
-    op = O.HNSWParams(dim=dim, num_layers=LAYERS, ef_construction=64, ef_search=112, level0_neighbors_count=m0, neighbors_count=m, seed=5)
+    op = O.HNSWParams(dim=dim, num_layers=LAYERS, ef_construction=64, ef_search=112, level0_neighbors_count=m0, neighbors_count=m, seed=5,
+                      range_lo=lo, range_hi=hi)
     oix = O.OracleIndex(op).set_vectors(X).import_graph(bix.download_graph(), bix.download_root())
     del bix
     with _lib.tuning(walk_split_levels=1 << CUT):
@@ -52,9 +60,7 @@ def _pin(dix):
     assert dix.walk_table_info()[0] == TAB_MIN and dix.walk_order_cuts() == [CUT]
 
 
-@functools.lru_cache(maxsize=None)
-def _queries(dim, m0, m):
-    X, oix, _ = _graph(dim, m0, m)
+def _make_queries(X, dim, m0, range_lo):
     rng = np.random.default_rng(dim + m0)
     noise = lambda k: 0.05 * rng.standard_normal((k, dim)).astype(np.float32)
     base = X[rng.integers(0, N, 60)] + noise(60)
@@ -65,10 +71,15 @@ def _queries(dim, m0, m):
     cluster[0::2], cluster[1::2] = X[rows] + noise(60), X[mates] + noise(60)
     other = X[rng.integers(0, N, 61)] + noise(61)
     Q = np.ascontiguousarray(np.concatenate([same, cluster, other]).astype(np.float32))
-    Q[150] = oix.params.range_lo                                          # the all-zero code: |q| = 0, CalculationError at the top level
+    Q[150] = range_lo                                                     # the all-zero code: |q| = 0, CalculationError at the top level
     assert Q.shape[0] == 301
     Q.setflags(write=False)
     return Q
+
+
+@functools.lru_cache(maxsize=None)
+def _queries(dim, m0, m, values_range=(-1.0, 1.0)):
+    return _make_queries(_corpus(dim), dim, m0, values_range[0])
 
 
 def _run(dix, Q, pair, cache=512, top_k=10, taken=True):
