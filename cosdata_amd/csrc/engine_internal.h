@@ -94,6 +94,23 @@ int32_t sparse_device(const cos_sparse *s);
 void sparse_limits(const cos_sparse *s, u32 *max_candidates, bool *have_raw, u32 *batch_bound);
 int32_t sparse_search_locked(cos_sparse *s, const uint32_t *q_dims, const float *q_vals, const uint32_t *q_offsets, u32 B, u32 top_k,
                              float early_terminate_threshold, u32 reranking_factor, u32 *d_out_ids, float *d_out_scores, u32 *d_out_counts, hipStream_t st);
+// The BM25 handle as a shard set sees it (kernels_hybrid.hip defines it; shardset.hip holds the lock of every attached handle, in shard
+// order, from the term lookup to the call's synchronisation).  Everything but bm25_mutex / bm25_device is for a caller that holds the locks.
+std::mutex &bm25_mutex(cos_bm25 *b);
+int32_t bm25_device(const cos_bm25 *b);
+long long bm25_largest_id(const cos_bm25 *b); // the largest document id the handle has ever held, -1 = none
+hipStream_t bm25_stream(cos_bm25 *b);         // the handle's scoring stream (after bm25_set_score)
+const u64 *bm25_buckets(const cos_bm25 *b);   // [B][512] bucket keys of the last scoring
+int32_t bm25_dense_stream(cos_bm25 *b, hipStream_t *out); // the stream cos_hybrid_search_batch walks on (highest priority; created on first use)
+// One query batch over the S handles of a collection (handle s: local ids, global id = doc_bases[s] + local): every term is resolved in
+// every handle's term table, its idf is the collection's, every handle's table goes into its own pinned staging and its scoring kernel
+// onto its own stream, into its own bucket array, keyed by global ids.
+int32_t bm25_set_score(cos_bm25 *const *hs, const u32 *doc_bases, u32 S, const uint32_t *q_terms, const uint32_t *q_offsets, u32 B);
+// gathered [S][B][512] bucket keys -> their element-wise maximum -> the lists of bm25_topk_kernel, [B][top_k] / [B], on `st`
+int32_t bm25_fold_topk(const u64 *d_gathered, u32 S, u32 B, u32 top_k, u32 *d_out_ids, float *d_out_scores, u32 *d_out_counts, hipStream_t st);
+// rrf_kernel over two resident list sets of stride k3 = 3 * top_k, on `st`
+int32_t rrf_fuse_device(const u32 *d_first_ids, const u32 *d_first_counts, const u32 *d_second_ids, const u32 *d_second_counts, u32 k3, u32 B,
+                        float fusion_constant_k, u32 top_k, u32 *d_out_ids, float *d_out_scores, u32 *d_out_counts, hipStream_t st);
 } // namespace cosdev
 
 // ------------------------------------------------------------------------------------------------

@@ -101,10 +101,16 @@ struct Bm25Cursor { // block-uniform
     bool valid;
 };
 
-template <bool TOMBS>
+// BASED: the handle is one shard of a collection and holds its documents under LOCAL ids (a shard set's text half, shardset.hip): the
+// bucket index and the key's id are formed from the GLOBAL id doc_base + local where a tile is flushed; nothing else differs.  A single
+// handle runs the BASED = false instantiations, whose last argument is empty: the code they were before shard sets had a text half.
+template <bool BASED> struct DocBase { u32 v; };
+template <> struct DocBase<false> {};
+template <bool TOMBS, bool BASED = false>
 __global__ __launch_bounds__(256) void bm25_score_kernel(const u32 *__restrict__ docs, const float *__restrict__ tfs,
                                                          const QueryTerms *__restrict__ qts, u32 n_docs, const u32 *__restrict__ tile_dir,
-                                                         u64 *__restrict__ buckets /*[B][512]*/, const u32 *__restrict__ order, u32 splits) {
+                                                         u64 *__restrict__ buckets /*[B][512]*/, const u32 *__restrict__ order, u32 splits,
+                                                         DocBase<BASED> doc_base) {
     __shared__ float acc[TILE]; // UNTOUCHED (a NaN pattern no score can take) until a term reaches the document
     __shared__ u64 lb[BUCKETS];
     // 1-D grid, heaviest queries first: block id -> (rank in the host's descending-postings order, split).  Query sizes are
@@ -167,7 +173,8 @@ __global__ __launch_bounds__(256) void bm25_score_kernel(const u32 *__restrict__
             for (u32 slot = threadIdx.x; slot < TILE; slot += blockDim.x) {
                 const float v = acc[slot];
                 if (__float_as_uint(v) != UNTOUCHED) {
-                    const u32 doc = d0 + slot;
+                    u32 doc = d0 + slot;
+                    if constexpr (BASED) doc += doc_base.v;
                     const u64 key = pack_key(simkey(v), ~doc); // larger score, then smaller doc id
                     atomicMax((unsigned long long *)&lb[doc % BUCKETS], (unsigned long long)key);
                     acc[slot] = __uint_as_float(UNTOUCHED);
@@ -204,17 +211,14 @@ __global__ __launch_bounds__(256) void bm25_score_kernel(const u32 *__restrict__
     }
 }
 
-// one wave per query: 512 buckets -> sort by (score desc, larger id first) -> top k
-__global__ __launch_bounds__(64) void bm25_topk_kernel(const u64 *__restrict__ buckets, u32 B, u32 top_k, u32 *__restrict__ out_ids,
-                                                       float *__restrict__ out_scores, u32 *__restrict__ out_counts) {
-    const int lane = threadIdx.x;
-    const u32 q = blockIdx.x;
-    if (q >= B) return;
-    u64 k[8];
+// What bm25_topk_kernel and bm25_fold_topk_kernel share, from a wave's 512 bucket keys on (lane l holds buckets 8l .. 8l + 7 as the
+// scoring kernel left them, (score, ~doc id), 0 = empty): back to (score, doc id), count, sort by (score desc, larger id first), top k
+__device__ __forceinline__ void bm25_buckets_topk(u64 (&k)[8], int lane, u32 q, u32 top_k, u32 *__restrict__ out_ids, float *__restrict__ out_scores,
+                                                  u32 *__restrict__ out_counts) {
     u32 cnt = 0;
 #pragma unroll
     for (int r = 0; r < 8; r++) {
-        const u64 v = buckets[(u64)q * BUCKETS + (u32)lane * 8 + r];
+        const u64 v = k[r];
         k[r] = v ? pack_key((u32)(v >> 32), ~(u32)v) : 0ull; // back to (score, doc id)
         cnt += v != 0ull;
     }
@@ -231,6 +235,43 @@ __global__ __launch_bounds__(64) void bm25_topk_kernel(const u64 *__restrict__ b
         }
     }
     if (lane == 0) out_counts[q] = n;
+}
+
+// one wave per query: 512 buckets -> sort by (score desc, larger id first) -> top k
+__global__ __launch_bounds__(64) void bm25_topk_kernel(const u64 *__restrict__ buckets, u32 B, u32 top_k, u32 *__restrict__ out_ids,
+                                                       float *__restrict__ out_scores, u32 *__restrict__ out_counts) {
+    const int lane = threadIdx.x;
+    const u32 q = blockIdx.x;
+    if (q >= B) return;
+    u64 k[8];
+#pragma unroll
+    for (int r = 0; r < 8; r++) k[r] = buckets[(u64)q * BUCKETS + (u32)lane * 8 + r];
+    bm25_buckets_topk(k, lane, q, top_k, out_ids, out_scores, out_counts);
+}
+
+// The collection's buckets from its S shards' (shardset.hip): one wave per query; gathered[s][q][512] are the keys shard s's scoring
+// kernel left, over GLOBAL ids, and the key is an order-independent maximum, so the collection's array is their element-wise u64
+// maximum.  Lane l reads buckets 8l .. 8l + 7 of every shard's row — 64 contiguous bytes per lane, 4 KB per row and wave, as four
+// 16-byte loads — and the rest is bm25_topk_kernel's.  The lists go where the caller points: the host's staging, or where rrf_kernel
+// reads its second list set.
+__global__ __launch_bounds__(64) void bm25_fold_topk_kernel(const u64 *__restrict__ gathered, u32 S, u32 B, u32 top_k, u32 *__restrict__ out_ids,
+                                                            float *__restrict__ out_scores, u32 *__restrict__ out_counts) {
+    const int lane = threadIdx.x;
+    const u32 q = blockIdx.x;
+    if (q >= B) return;
+    u64 k[8];
+#pragma unroll
+    for (int r = 0; r < 8; r++) k[r] = 0ull;
+    for (u32 s = 0; s < S; s++) {
+        const ulonglong2 *row = reinterpret_cast<const ulonglong2 *>(gathered + ((u64)s * B + q) * BUCKETS + (u32)lane * 8);
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const ulonglong2 v = row[r];
+            k[2 * r] = k[2 * r] > v.x ? k[2 * r] : (u64)v.x;
+            k[2 * r + 1] = k[2 * r + 1] > v.y ? k[2 * r + 1] : (u64)v.y;
+        }
+    }
+    bm25_buckets_topk(k, lane, q, top_k, out_ids, out_scores, out_counts);
 }
 
 // RRF: one wave per query.  score(id) = [last occurrence in the FIRST list: 1/(rank+k+eps)] then += each occurrence in the SECOND list.
@@ -416,6 +457,35 @@ extern "C" int32_t cos_bm25_destroy(cos_bm25 *b) {
 
 // host side of a batch: sort each query's terms by hash, look the posting lists up, idf via libm log1pf
 // (sparse_ann_query.rs:298-302) -> QueryTerms in pinned memory
+//
+// Two pieces, shared by a single handle and by the shards of a collection (bm25_set_score): a query term resolved against ONE handle's
+// term table, and a handle's QueryTerms filled from resolved terms and an idf.  The idf is a statistic of the COLLECTION: a single handle
+// is its own collection, a shard takes the sums over every shard.
+struct Bm25Term { // one query term in one handle: its posting list, its row of the tile directory, the list's length (tombstones included)
+    u64 begin, end;
+    u32 dir, len;
+};
+static bool bm25_resolve_term(const cos_bm25 *b, u32 h, Bm25Term &r) {
+    auto it = std::lower_bound(b->term_hashes.begin(), b->term_hashes.end(), h);
+    if (it == b->term_hashes.end() || *it != h) return false; // no node / no term: skipped (:165-167)
+    const size_t ti = (size_t)(it - b->term_hashes.begin());
+    r.begin = b->offsets[ti];
+    r.end = b->offsets[ti + 1];
+    r.dir = b->dir_row[ti];
+    r.len = (u32)(b->offsets[ti + 1] - b->offsets[ti]);
+    return true;
+}
+// get_idf(documents_count, documents.len()) with the reference's u32 wrap, on the host libm
+static float bm25_idf(u32 documents_count, u32 len) { return log1pf(((float)(u32)(documents_count - len) + 0.5f) / ((float)len + 0.5f)); }
+static void bm25_push_term(QueryTerms &qt, const Bm25Term &r, float idf) { // the caller has checked qt.n < MAX_QTERMS
+    qt.begin[qt.n] = r.begin;
+    qt.end[qt.n] = r.end;
+    qt.idf[qt.n] = idf;
+    qt.dir[qt.n] = r.dir;
+    qt.n++;
+}
+static void bm25_launch_order(cos_bm25 *b, u32 B);
+
 static int32_t bm25_prepare(cos_bm25 *b, const uint32_t *q_terms, const uint32_t *q_offsets, u32 B) {
     QueryTerms *h_qt = b->h_qt.as<QueryTerms>();
     for (u32 q = 0; q < B; q++) {
@@ -424,18 +494,18 @@ static int32_t bm25_prepare(cos_bm25 *b, const uint32_t *q_terms, const uint32_t
         QueryTerms &qt = h_qt[q];
         qt.n = 0;
         for (u32 h : t) {
-            auto it = std::lower_bound(b->term_hashes.begin(), b->term_hashes.end(), h);
-            if (it == b->term_hashes.end() || *it != h) continue; // no node / no term: skipped (:165-167)
+            Bm25Term r;
+            if (!bm25_resolve_term(b, h, r)) continue;
             if (qt.n == MAX_QTERMS) return cos_fail(COS_ERR_UNIMPLEMENTED, "more than %u matching terms in query %u", MAX_QTERMS, q);
-            const size_t ti = (size_t)(it - b->term_hashes.begin());
-            const u32 len = (u32)(b->offsets[ti + 1] - b->offsets[ti]);
-            qt.begin[qt.n] = b->offsets[ti];
-            qt.end[qt.n] = b->offsets[ti + 1];
-            qt.idf[qt.n] = log1pf(((float)(u32)(b->documents_count - len) + 0.5f) / ((float)len + 0.5f));
-            qt.dir[qt.n] = b->dir_row[ti];
-            qt.n++;
+            bm25_push_term(qt, r, bm25_idf(b->documents_count, r.len));
         }
     }
+    bm25_launch_order(b, B);
+    return COS_OK;
+}
+
+static void bm25_launch_order(cos_bm25 *b, u32 B) {
+    QueryTerms *h_qt = b->h_qt.as<QueryTerms>();
     // launch order: heaviest query (most postings) first; ties by index
     std::vector<std::pair<u64, u32>> w(B);
     for (u32 q = 0; q < B; q++) {
@@ -446,7 +516,6 @@ static int32_t bm25_prepare(cos_bm25 *b, const uint32_t *q_terms, const uint32_t
     std::sort(w.begin(), w.end());
     u32 *order = (u32 *)(h_qt + b->capB);
     for (u32 q = 0; q < B; q++) order[q] = w[q].second;
-    return COS_OK;
 }
 
 static int32_t bm25_workspace(cos_bm25 *b, u32 B, u32 top_k) {
@@ -467,8 +536,9 @@ static int32_t bm25_workspace(cos_bm25 *b, u32 B, u32 top_k) {
     return COS_OK;
 }
 
-// scoring + bucket top-k enqueued on `st`; outputs are device pointers
-static int32_t bm25_launch(cos_bm25 *b, u32 B, u32 top_k, u32 *d_out_ids, float *d_out_scores, u32 *d_out_counts, hipStream_t st) {
+// scoring into the handle's bucket array, enqueued on `st`.  BASED: as one shard of a collection, keyed by doc_base + local id
+template <bool BASED>
+static int32_t bm25_launch_score(cos_bm25 *b, u32 B, hipStream_t st, u32 doc_base) {
     const QueryTerms *d_qt = b->d_qt.as<QueryTerms>(), *h_qt = b->h_qt.as<QueryTerms>();
     HIP_TRY(hipMemcpyAsync(b->d_qt, h_qt, (size_t)B * sizeof(QueryTerms), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(b->d_qt.as<QueryTerms>() + b->capB, h_qt + b->capB, (size_t)B * 4, hipMemcpyHostToDevice, st));
@@ -481,13 +551,23 @@ static int32_t bm25_launch(cos_bm25 *b, u32 B, u32 top_k, u32 *d_out_ids, float 
     const u32 n_tiles = (span + TILE - 1) / TILE;
     const u32 splits = std::max(1u, std::min(n_tiles, std::max(1u, target_blocks / B)));
     // an index that holds no tombstone (never the target of a delete that found something) keeps the kernel without the tombstone test
+    const u32 *d_order = (const u32 *)(d_qt + b->capB);
+    DocBase<BASED> base;
+    if constexpr (BASED) base.v = doc_base;
     if (b->n_tombstones)
-        hipLaunchKernelGGL(bm25_score_kernel<true>, dim3(B * splits), dim3(256), 0, st, b->d_docs, b->d_tfs, d_qt, span, b->d_tile_dir, b->d_buckets,
-                           (const u32 *)(d_qt + b->capB), splits);
+        hipLaunchKernelGGL((bm25_score_kernel<true, BASED>), dim3(B * splits), dim3(256), 0, st, b->d_docs, b->d_tfs, d_qt, span, b->d_tile_dir, b->d_buckets,
+                           d_order, splits, base);
     else
-        hipLaunchKernelGGL(bm25_score_kernel<false>, dim3(B * splits), dim3(256), 0, st, b->d_docs, b->d_tfs, d_qt, span, b->d_tile_dir, b->d_buckets,
-                           (const u32 *)(d_qt + b->capB), splits);
+        hipLaunchKernelGGL((bm25_score_kernel<false, BASED>), dim3(B * splits), dim3(256), 0, st, b->d_docs, b->d_tfs, d_qt, span, b->d_tile_dir, b->d_buckets,
+                           d_order, splits, base);
     HIP_TRY(hipGetLastError());
+    return COS_OK;
+}
+
+// scoring + bucket top-k enqueued on `st`; outputs are device pointers
+static int32_t bm25_launch(cos_bm25 *b, u32 B, u32 top_k, u32 *d_out_ids, float *d_out_scores, u32 *d_out_counts, hipStream_t st) {
+    int32_t rc = bm25_launch_score<false>(b, B, st, 0u);
+    if (rc) return rc;
     hipLaunchKernelGGL(bm25_topk_kernel, dim3(B), dim3(64), 0, st, b->d_buckets, B, top_k, d_out_ids, d_out_scores, d_out_counts);
     HIP_TRY(hipGetLastError());
     return COS_OK;
@@ -586,11 +666,9 @@ extern "C" int32_t cos_hybrid_search_batch(cos_index *ix, cos_bm25 *b, const flo
     std::lock_guard<std::mutex> g(b->mu);
     int32_t rc = bm25_workspace(b, B, k3);
     if (rc) return rc;
-    if (!b->stream_dense) {
-        int prio_low = 0, prio_high = 0;
-        HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_low, &prio_high));
-        HIP_TRY(hipStreamCreateWithPriority(&b->stream_dense, hipStreamNonBlocking, prio_high));
-    }
+    hipStream_t sd = nullptr;
+    rc = bm25_dense_stream(b, &sd);
+    if (rc) return rc;
     if (!b->ev_sparse) HIP_TRY(hipEventCreateWithFlags(&b->ev_sparse, hipEventDisableTiming));
     HIP_TRY(hipStreamSynchronize(b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream_dense));
@@ -610,7 +688,6 @@ extern "C" int32_t cos_hybrid_search_batch(cos_index *ix, cos_bm25 *b, const flo
     // leaves free.  Until round 6 the sparse half was enqueued first: its workgroups held every CU until they drained and the dense
     // half's first dispatch (the query copy) waited for them — the two halves ran one after the other (c5: 2.55 ms per batch,
     // profiles/r06_final_kernel_trace_c5_rocprofv3.txt: a 256-workgroup copy of 0.52 ms beside a 0.57 ms bm25_score_kernel).
-    hipStream_t sd = b->stream_dense;
     HIP_TRY(hipMemcpyAsync(b->d_hq, queries, (size_t)B * dim * 4, hipMemcpyHostToDevice, sd));
     rc = cos_search_batch_device(ix, b->d_hq, B, k3, b->d_did, b->d_dsc, b->d_dcnt, d_dst, sd);
     if (rc) return rc;
@@ -622,15 +699,8 @@ extern "C" int32_t cos_hybrid_search_batch(cos_index *ix, cos_bm25 *b, const flo
     HIP_TRY(hipEventRecord(b->ev_sparse, b->stream));
     // fusion once both lists are there
     HIP_TRY(hipStreamWaitEvent(sd, b->ev_sparse, 0));
-    const size_t smem = (size_t)maxn * 4;
-#define LAUNCH(R) hipLaunchKernelGGL(rrf_kernel<R>, dim3(B), dim3(64), smem, sd, b->d_did, b->d_dcnt, k3, b->d_ids, b->d_cnt, k3, B, fusion_constant_k, top_k, d_fid, d_fsc, d_fcnt)
-    if (maxn <= 64) LAUNCH(1);
-    else if (maxn <= 128) LAUNCH(2);
-    else if (maxn <= 256) LAUNCH(4);
-    else if (maxn <= 512) LAUNCH(8);
-    else LAUNCH(16);
-#undef LAUNCH
-    HIP_TRY(hipGetLastError());
+    rc = rrf_fuse_device(b->d_did, b->d_dcnt, b->d_ids, b->d_cnt, k3, B, fusion_constant_k, top_k, d_fid, d_fsc, d_fcnt, sd);
+    if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(b->h_ret, b->d_ret, ret_words * 4, hipMemcpyDeviceToHost, sd)); // (until round 6: four pageable copies)
     HIP_TRY(hipStreamSynchronize(sd));
     const u32 *hr = b->h_ret;
@@ -642,6 +712,98 @@ extern "C" int32_t cos_hybrid_search_batch(cos_index *ix, cos_bm25 *b, const flo
         if (status[q] != COS_OK) return cos_fail(status[q], "dense half: query %u failed with status %d (zero-norm vector -> DistanceError::CalculationError)", q, status[q]);
     return COS_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// The BM25 handle as one shard of a collection (shardset.hip: cos_shardset_bm25_search_batch, cos_shardset_hybrid_search_batch).
+// Handle s holds the documents of shard s under local ids.  What makes the sharded answer the whole index's, bit for bit:
+//   * idf: N = the sum of the shards' documents_count, len = the sum of the term's list lengths (tombstones included), through the
+//     expression a single handle uses (bm25_idf);
+//   * a document lives in one shard, and a term without a list there adds nothing to it: with the collection's idf the shard's kernel
+//     adds the same products in the same (term-hash) order as the whole index's;
+//   * the bucket key (score, ~GLOBAL id) is an order-independent maximum, so the collection's buckets are the element-wise maximum of
+//     the shards' (bm25_fold_topk_kernel).
+// ------------------------------------------------------------------------------------------------
+namespace cosdev {
+std::mutex &bm25_mutex(cos_bm25 *b) { return b->mu; }
+int32_t bm25_device(const cos_bm25 *b) { return b->device; }
+long long bm25_largest_id(const cos_bm25 *b) { return b->max_id_ever; }
+hipStream_t bm25_stream(cos_bm25 *b) { return b->stream; }
+const u64 *bm25_buckets(const cos_bm25 *b) { return b->d_buckets; }
+
+int32_t bm25_dense_stream(cos_bm25 *b, hipStream_t *out) {
+    if (!b->stream_dense) {
+        int prio_low = 0, prio_high = 0;
+        HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_low, &prio_high));
+        HIP_TRY(hipStreamCreateWithPriority(&b->stream_dense, hipStreamNonBlocking, prio_high));
+    }
+    *out = b->stream_dense;
+    return COS_OK;
+}
+
+int32_t bm25_set_score(cos_bm25 *const *hs, const u32 *doc_bases, u32 S, const uint32_t *q_terms, const uint32_t *q_offsets, u32 B) {
+    u32 N = 0; // TFIDFIndexRoot::total_documents_count of the collection (u32 arithmetic, like a handle's own count)
+    for (u32 s = 0; s < S; s++) {
+        cos_bm25 *b = hs[s];
+        HIP_TRY(hipSetDevice(b->device));
+        int32_t rc = bm25_workspace(b, B, 1);
+        if (rc) return rc;
+        HIP_TRY(hipStreamSynchronize(b->stream)); // the pinned term table of the previous batch must have been consumed
+        N += b->documents_count;
+    }
+    std::vector<Bm25Term> res(S);
+    std::vector<char> has(S);
+    for (u32 q = 0; q < B; q++) {
+        std::vector<u32> t(q_terms + q_offsets[q], q_terms + q_offsets[q + 1]);
+        std::sort(t.begin(), t.end());
+        for (u32 s = 0; s < S; s++) hs[s]->h_qt.as<QueryTerms>()[q].n = 0;
+        u32 matched = 0; // terms with a list in ANY shard: what the whole index's table would hold of this query
+        for (u32 h : t) {
+            u64 len = 0;
+            bool any = false;
+            for (u32 s = 0; s < S; s++) {
+                has[s] = bm25_resolve_term(hs[s], h, res[s]);
+                if (has[s]) { any = true; len += res[s].len; }
+            }
+            if (!any) continue;
+            if (matched == MAX_QTERMS) return cos_fail(COS_ERR_UNIMPLEMENTED, "more than %u matching terms in query %u", MAX_QTERMS, q);
+            matched++;
+            const float idf = bm25_idf(N, (u32)len);
+            for (u32 s = 0; s < S; s++)
+                if (has[s]) bm25_push_term(hs[s]->h_qt.as<QueryTerms>()[q], res[s], idf);
+        }
+    }
+    for (u32 s = 0; s < S; s++) {
+        cos_bm25 *b = hs[s];
+        bm25_launch_order(b, B);
+        HIP_TRY(hipSetDevice(b->device));
+        int32_t rc = bm25_launch_score<true>(b, B, b->stream, doc_bases[s]);
+        if (rc) return rc;
+    }
+    return COS_OK;
+}
+
+int32_t bm25_fold_topk(const u64 *d_gathered, u32 S, u32 B, u32 top_k, u32 *d_out_ids, float *d_out_scores, u32 *d_out_counts, hipStream_t st) {
+    hipLaunchKernelGGL(bm25_fold_topk_kernel, dim3(B), dim3(64), 0, st, d_gathered, S, B, top_k, d_out_ids, d_out_scores, d_out_counts);
+    HIP_TRY(hipGetLastError());
+    return COS_OK;
+}
+
+int32_t rrf_fuse_device(const u32 *d_first_ids, const u32 *d_first_counts, const u32 *d_second_ids, const u32 *d_second_counts, u32 k3, u32 B,
+                        float fusion_constant_k, u32 top_k, u32 *d_out_ids, float *d_out_scores, u32 *d_out_counts, hipStream_t st) {
+    const u32 maxn = 2 * k3;
+    if (maxn > 1024) return cos_fail(COS_ERR_UNIMPLEMENTED, "top_k above 170: RRF lists longer than 1024 entries");
+    const size_t smem = (size_t)maxn * 4;
+#define LAUNCH(R) hipLaunchKernelGGL(rrf_kernel<R>, dim3(B), dim3(64), smem, st, d_first_ids, d_first_counts, k3, d_second_ids, d_second_counts, k3, B, fusion_constant_k, top_k, d_out_ids, d_out_scores, d_out_counts)
+    if (maxn <= 64) LAUNCH(1);
+    else if (maxn <= 128) LAUNCH(2);
+    else if (maxn <= 256) LAUNCH(4);
+    else if (maxn <= 512) LAUNCH(8);
+    else LAUNCH(16);
+#undef LAUNCH
+    HIP_TRY(hipGetLastError());
+    return COS_OK;
+}
+} // namespace cosdev
 
 
 // ------------------------------------------------------------------------------------------------

@@ -85,11 +85,13 @@ struct LocalShard {
     int device = 0;
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;
+    hipEvent_t done_text = nullptr; // the shard's BM25 buckets are complete (recorded on the attached handle's stream)
     ncclComm_t comm = nullptr;
     // per-shard device buffers, grown on demand
     DevArr<float> d_queries;
     DevArr<u32> d_packed;   // this shard's record [ids B*k | scores B*k | counts B]
     DevArr<u32> d_gathered; // [world][words]
+    DevArr<u32> d_gathered_text; // [world][B * 1024]: every shard's B x 512 bucket keys (u64)
     DevArr<int32_t> d_status;
     LocalShard() = default;
     LocalShard(const LocalShard &) = delete;
@@ -97,8 +99,9 @@ struct LocalShard {
         (void)hipSetDevice(device);
         if (stream) (void)hipStreamSynchronize(stream);
         if (comm) (void)rccl()->CommDestroy(comm);
-        d_queries.reset(); d_packed.reset(); d_gathered.reset(); d_status.reset();
+        d_queries.reset(); d_packed.reset(); d_gathered.reset(); d_gathered_text.reset(); d_status.reset();
         if (done) (void)hipEventDestroy(done);
+        if (done_text) (void)hipEventDestroy(done_text);
         if (stream) (void)hipStreamDestroy(stream);
     }
 };
@@ -113,6 +116,13 @@ struct cos_shardset {
     // merge output on shard 0's device
     DevArr<u32> d_out_ids, d_out_counts;
     DevArr<float> d_out_scores;
+    // the text half (cos_shardset_attach_bm25): handle s holds shard s's documents under local ids, global id = bm_base[s] + local
+    std::vector<cos_bm25 *> bm;
+    std::vector<u32> bm_base;
+    // on shard 0's device: the collection's BM25 lists [B][k] after the fold; the fused lists of a hybrid call [ids | scores | counts]
+    DevArr<u32> d_text_ids, d_text_counts, d_ret;
+    DevArr<float> d_text_scores;
+    PinArr<u32> h_ret;
 };
 
 extern "C" int32_t cos_shardset_unique_id(uint8_t *out) {
@@ -134,6 +144,7 @@ extern "C" int32_t cos_shardset_destroy(cos_shardset *ss) {
     ss->sh.clear();
     if (any) (void)hipSetDevice(dev0);
     ss->d_out_ids.reset(); ss->d_out_counts.reset(); ss->d_out_scores.reset();
+    ss->d_text_ids.reset(); ss->d_text_counts.reset(); ss->d_text_scores.reset(); ss->d_ret.reset(); ss->h_ret.reset();
     delete ss;
     return COS_OK;
 }
@@ -163,7 +174,8 @@ extern "C" int32_t cos_shardset_create(cos_index *const *shards, uint32_t n_loca
     auto fail = [&](int32_t rc) { cos_shardset_destroy(ss); return rc; };
     for (LocalShard &s : ss->sh) {
         if (hipSetDevice(s.device) != hipSuccess || hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) != hipSuccess ||
-            hipEventCreateWithFlags(&s.done, hipEventDisableTiming) != hipSuccess)
+            hipEventCreateWithFlags(&s.done, hipEventDisableTiming) != hipSuccess ||
+            hipEventCreateWithFlags(&s.done_text, hipEventDisableTiming) != hipSuccess)
             return fail(cos_fail(COS_ERR_HIP, "cannot create stream/event on device %d", s.device));
     }
     // RCCL communicators: needed whenever records cross a device boundary
@@ -192,14 +204,24 @@ extern "C" int32_t cos_shardset_create(cos_index *const *shards, uint32_t n_loca
     return COS_OK;
 }
 
-// gathered[world][words] on every local shard's device <- every shard's packed record; enqueued on the shards' streams
-static int32_t exchange_local(cos_shardset *ss, size_t words) {
+// What one exchange moves: a record is `words` words per shard — the packed lists B (2k + 1) of the dense operators, or the B x 512 bucket
+// keys of the text half, which leave straight from the attached handle's bucket array.
+enum class Record { LISTS, BUCKETS };
+static const u32 *record_src(cos_shardset *ss, u32 i, Record rec) {
+    return rec == Record::LISTS ? ss->sh[i].d_packed.p : reinterpret_cast<const u32 *>(cosdev::bm25_buckets(ss->bm[i]));
+}
+static u32 *record_dst(LocalShard &s, Record rec) { return rec == Record::LISTS ? s.d_gathered.p : s.d_gathered_text.p; }
+
+// gathered[world][words] on every local shard's device <- every shard's record; enqueued on the shards' streams, each of which is
+// already behind its own shard's record (it produced it, or waits for the event of the stream that did)
+static int32_t exchange_local(cos_shardset *ss, size_t words, Record rec = Record::LISTS) {
     const u32 S = (u32)ss->sh.size();
     if (ss->use_rccl) {
         RcclApi *r = rccl();
         RCCL_TRY(r->GroupStart());
-        for (LocalShard &s : ss->sh) {
-            ncclResult_t rr = r->AllGather(s.d_packed, s.d_gathered, words, ncclUint32, s.comm, s.stream);
+        for (u32 i = 0; i < S; i++) {
+            LocalShard &s = ss->sh[i];
+            ncclResult_t rr = r->AllGather(record_src(ss, i, rec), record_dst(s, rec), words, ncclUint32, s.comm, s.stream);
             if (rr != ncclSuccess) { (void)r->GroupEnd(); return cos_fail(COS_ERR_HIP, "ncclAllGather: %s", r->GetErrorString(rr)); }
         }
         RCCL_TRY(r->GroupEnd());
@@ -210,11 +232,12 @@ static int32_t exchange_local(cos_shardset *ss, size_t words) {
     HIP_TRY(hipSetDevice(root.device));
     for (u32 s = 0; s < S; s++) {
         LocalShard &src = ss->sh[s];
-        if (s) HIP_TRY(hipStreamWaitEvent(root.stream, src.done, 0));
+        if (s) HIP_TRY(hipStreamWaitEvent(root.stream, rec == Record::LISTS ? src.done : src.done_text, 0));
+        u32 *dst = record_dst(root, rec) + (size_t)s * words;
         if (src.device == root.device)
-            HIP_TRY(hipMemcpyAsync(root.d_gathered + (size_t)s * words, src.d_packed, words * 4, hipMemcpyDeviceToDevice, root.stream));
+            HIP_TRY(hipMemcpyAsync(dst, record_src(ss, s, rec), words * 4, hipMemcpyDeviceToDevice, root.stream));
         else // a mixed set (e.g. 3 shards on 2 GPUs): explicit peer copy, valid with or without peer access between the two devices
-            HIP_TRY(hipMemcpyPeerAsync(root.d_gathered + (size_t)s * words, root.device, src.d_packed, src.device, words * 4, root.stream));
+            HIP_TRY(hipMemcpyPeerAsync(dst, root.device, record_src(ss, s, rec), src.device, words * 4, root.stream));
     }
     return COS_OK;
 }
@@ -222,7 +245,9 @@ static int32_t exchange_local(cos_shardset *ss, size_t words) {
 namespace {
 struct DrainAll { // every return path — a later shard's error, a failed grow, a failed exchange — leaves no walk or collective
     cos_shardset *ss; // of this batch queued on any shard's stream: the next call (or destroy) starts from idle streams
+    std::vector<std::pair<int, hipStream_t>> text; // ... nor on a stream of an attached BM25 handle that the call has used
     ~DrainAll() {
+        for (auto &t : text) { (void)hipSetDevice(t.first); (void)hipStreamSynchronize(t.second); }
         for (LocalShard &s : ss->sh) { (void)hipSetDevice(s.device); (void)hipStreamSynchronize(s.stream); }
         (void)hipSetDevice(ss->sh[0].device);
     }
@@ -238,7 +263,7 @@ int32_t check_merge_width(u32 S, u32 top_k) {
 
 // every shard's record is in its d_packed (events `done` recorded): ONE exchange, the merge on shard 0's device and the copies back, all
 // enqueued on the shards' streams; the caller synchronises shard 0's
-int32_t exchange_merge_copy(cos_shardset *ss, u32 B, u32 top_k, size_t words, uint32_t *out_ids, float *out_scores, uint32_t *out_counts) {
+int32_t exchange_merge(cos_shardset *ss, u32 B, u32 top_k, size_t words) { // ... up to the merged lists in d_out_* on shard 0's device
     int32_t rc = exchange_local(ss, words);
     if (rc) return rc;
     LocalShard &root = ss->sh[0];
@@ -246,42 +271,47 @@ int32_t exchange_merge_copy(cos_shardset *ss, u32 B, u32 top_k, size_t words, ui
     HIP_TRY(ss->d_out_ids.grow((size_t)B * top_k));
     HIP_TRY(ss->d_out_scores.grow((size_t)B * top_k));
     HIP_TRY(ss->d_out_counts.grow((size_t)B * top_k));
-    rc = cos_merge_lists_packed_device(root.d_gathered, ss->world, B, top_k, ss->d_out_ids, ss->d_out_scores, ss->d_out_counts, root.device, root.stream);
+    return cos_merge_lists_packed_device(root.d_gathered, ss->world, B, top_k, ss->d_out_ids, ss->d_out_scores, ss->d_out_counts, root.device, root.stream);
+}
+int32_t exchange_merge_copy(cos_shardset *ss, u32 B, u32 top_k, size_t words, uint32_t *out_ids, float *out_scores, uint32_t *out_counts) {
+    int32_t rc = exchange_merge(ss, B, top_k, words);
     if (rc) return rc;
+    LocalShard &root = ss->sh[0];
     HIP_TRY(hipMemcpyAsync(out_ids, ss->d_out_ids, (size_t)B * top_k * 4, hipMemcpyDeviceToHost, root.stream));
     HIP_TRY(hipMemcpyAsync(out_scores, ss->d_out_scores, (size_t)B * top_k * 4, hipMemcpyDeviceToHost, root.stream));
     HIP_TRY(hipMemcpyAsync(out_counts, ss->d_out_counts, (size_t)B * 4, hipMemcpyDeviceToHost, root.stream));
     return COS_OK;
 }
-} // namespace
-
-extern "C" int32_t cos_shardset_search_batch(cos_shardset *ss, const float *queries, uint32_t B, uint32_t top_k, uint32_t *out_ids, float *out_scores,
-                                             uint32_t *out_counts) {
-    if (!ss || !queries || !out_ids || !out_scores || !out_counts || B == 0 || top_k == 0) return cos_fail(COS_ERR_INVALID, "bad argument");
-    if (ss->sh.size() != ss->world) return cos_fail(COS_ERR_INVALID, "cos_shardset_search_batch needs every shard in this process; a process-per-GPU job uses cos_shardset_exchange_device");
-    if (int32_t wrc = check_merge_width(ss->world, top_k)) return wrc;
-    std::lock_guard<std::mutex> g(ss->mu);
+// every shard: queries up, walk + exact rerank into its packed record (all shards run concurrently on their devices).  The walk runs on
+// the shard's stream, or — the dense half of a hybrid call — on the stream the attached BM25 handle keeps for it (the one
+// cos_hybrid_search_batch walks on), which the shard's stream then waits for.
+int32_t enqueue_walks(cos_shardset *ss, const float *queries, u32 B, u32 top_k, size_t words, DrainAll *hybrid) {
     const u32 S = ss->world, dim = ss->sh[0].ix->p.dim;
-    const size_t words = (size_t)B * (2 * (size_t)top_k + 1);
-    DrainAll drain_all{ss};
-    // 1. every shard: queries up, walk + exact rerank into its packed record (all shards run concurrently on their devices)
-    for (LocalShard &s : ss->sh) {
+    for (u32 i = 0; i < S; i++) {
+        LocalShard &s = ss->sh[i];
         HIP_TRY(hipSetDevice(s.device));
         HIP_TRY(s.d_queries.grow((size_t)B * dim));
         HIP_TRY(s.d_packed.grow(words));
         HIP_TRY(s.d_gathered.grow(words * S));
         HIP_TRY(s.d_status.grow((size_t)B));
-        HIP_TRY(hipMemcpyAsync(s.d_queries, queries, (size_t)B * dim * 4, hipMemcpyHostToDevice, s.stream));
+        hipStream_t st = s.stream;
+        if (hybrid) {
+            if (int32_t rc = cosdev::bm25_dense_stream(ss->bm[i], &st)) return rc;
+            hybrid->text.emplace_back(s.device, st);
+        }
+        HIP_TRY(hipMemcpyAsync(s.d_queries, queries, (size_t)B * dim * 4, hipMemcpyHostToDevice, st));
         int32_t rc = cos_search_batch_device(s.ix, s.d_queries, B, top_k, s.d_packed, reinterpret_cast<float *>(s.d_packed + (size_t)B * top_k),
-                                             s.d_packed + 2 * (size_t)B * top_k, s.d_status, s.stream);
+                                             s.d_packed + 2 * (size_t)B * top_k, s.d_status, st);
         if (rc) return rc;
-        HIP_TRY(hipEventRecord(s.done, s.stream));
+        HIP_TRY(hipEventRecord(s.done, st));
+        if (st != s.stream) HIP_TRY(hipStreamWaitEvent(s.stream, s.done, 0));
     }
-    // 2. ONE exchange step, 3. merge on shard 0's device
-    int32_t rc = exchange_merge_copy(ss, B, top_k, words, out_ids, out_scores, out_counts);
-    if (rc) return rc;
+    return COS_OK;
+}
+
+// per-shard statuses of the walks: like the reference's collect::<Result<_>>, one failing query on any shard fails the call
+int32_t check_walk_statuses(cos_shardset *ss, u32 B) {
     LocalShard &root = ss->sh[0];
-    // per-shard statuses: like the reference's collect::<Result<_>>, one failing query on any shard fails the call
     std::vector<int32_t> status((size_t)B);
     for (LocalShard &s : ss->sh) {
         HIP_TRY(hipSetDevice(s.device));
@@ -298,6 +328,24 @@ extern "C" int32_t cos_shardset_search_batch(cos_shardset *ss, const float *quer
     HIP_TRY(hipSetDevice(root.device));
     HIP_TRY(hipStreamSynchronize(root.stream));
     return COS_OK;
+}
+} // namespace
+
+extern "C" int32_t cos_shardset_search_batch(cos_shardset *ss, const float *queries, uint32_t B, uint32_t top_k, uint32_t *out_ids, float *out_scores,
+                                             uint32_t *out_counts) {
+    if (!ss || !queries || !out_ids || !out_scores || !out_counts || B == 0 || top_k == 0) return cos_fail(COS_ERR_INVALID, "bad argument");
+    if (ss->sh.size() != ss->world) return cos_fail(COS_ERR_INVALID, "cos_shardset_search_batch needs every shard in this process; a process-per-GPU job uses cos_shardset_exchange_device");
+    if (int32_t wrc = check_merge_width(ss->world, top_k)) return wrc;
+    std::lock_guard<std::mutex> g(ss->mu);
+    const size_t words = (size_t)B * (2 * (size_t)top_k + 1);
+    DrainAll drain_all{ss};
+    // 1. every shard's walk
+    int32_t rc = enqueue_walks(ss, queries, B, top_k, words, nullptr);
+    if (rc) return rc;
+    // 2. ONE exchange step, 3. merge on shard 0's device
+    rc = exchange_merge_copy(ss, B, top_k, words, out_ids, out_scores, out_counts);
+    if (rc) return rc;
+    return check_walk_statuses(ss, B);
 }
 
 extern "C" int32_t cos_shardset_exchange_device(cos_shardset *ss, const uint32_t *d_packed_local, uint32_t B, uint32_t top_k, uint32_t *d_gathered,
@@ -425,4 +473,158 @@ extern "C" int32_t cos_shardset_bruteforce_topk(cos_shardset *ss, const float *q
     ShardOpArgs a{ShardOp::BRUTE, queries, B, k};
     a.masks = shard_masks;
     return shardset_run(ss, a, out_ids, out_scores, out_counts);
+}
+
+// ---- the text half of the collection on a shard set: BM25 and dense + BM25 hybrid search ------------------------------------------------
+// (the scheme and why it is the whole index's answer bit for bit: kernels_hybrid.hip, "The BM25 handle as one shard of a collection")
+namespace {
+constexpr size_t BUCKET_WORDS = 1024; // 512 u64 bucket keys per query
+
+// the locks of every attached handle, in shard order, until the call has synchronised
+struct TextLocks {
+    std::vector<std::unique_lock<std::mutex>> held;
+    explicit TextLocks(cos_shardset *ss) {
+        for (cos_bm25 *b : ss->bm) held.emplace_back(cosdev::bm25_mutex(b));
+    }
+};
+
+// global ids stay below 2^32 - 1 and inside their shard's range (inserts move the largest id, so every search asks again); locks held
+int32_t check_text_ids(const std::vector<cos_bm25 *> &bm, const std::vector<u32> &base, u32 first_rank) {
+    for (size_t s = 0; s < bm.size(); s++) {
+        const long long largest = cosdev::bm25_largest_id(bm[s]);
+        const u64 top = (u64)base[s] + (u64)(largest < 0 ? 0 : largest);
+        if (top >= 0xFFFFFFFFull)
+            return cos_fail(COS_ERR_INVALID, "BM25 shard %u: doc_base %u + largest id %lld does not fit below 2^32 - 1", first_rank + (u32)s, base[s], largest);
+        if (s + 1 < bm.size() && largest >= 0 && top >= base[s + 1])
+            return cos_fail(COS_ERR_INVALID, "BM25 shard %u: doc_base %u + largest id %lld reaches into the next shard (doc_base %u)", first_rank + (u32)s, base[s],
+                            largest, base[s + 1]);
+    }
+    return COS_OK;
+}
+
+int32_t text_check(cos_shardset *ss, const void *q_terms, const void *q_offsets, u32 B, u32 top_k, const void *o0, const void *o1, const void *o2, const char *name) {
+    if (!ss || !q_terms || !q_offsets || !o0 || !o1 || !o2 || B == 0 || top_k == 0) return cos_fail(COS_ERR_INVALID, "bad argument");
+    if (ss->sh.size() != ss->world) return cos_fail(COS_ERR_UNIMPLEMENTED, "%s needs every shard in this process", name);
+    return COS_OK;
+}
+
+// every shard scores into its handle's buckets on the handle's stream; ONE exchange of the S bucket arrays; the fold on shard 0's device
+// leaves the collection's lists in d_text_* ([B][top_k], [B]); everything enqueued, nothing synchronised
+int32_t text_lists(cos_shardset *ss, DrainAll &drain, const uint32_t *q_terms, const uint32_t *q_offsets, u32 B, u32 top_k) {
+    const u32 S = ss->world;
+    const size_t words = (size_t)B * BUCKET_WORDS;
+    LocalShard &root = ss->sh[0];
+    for (LocalShard &s : ss->sh) { // (only the all-gather writes every shard's buffer; the copies fill shard 0's)
+        if (!ss->use_rccl && &s != &root) continue;
+        HIP_TRY(hipSetDevice(s.device));
+        HIP_TRY(s.d_gathered_text.grow(words * S));
+    }
+    HIP_TRY(hipSetDevice(root.device));
+    HIP_TRY(ss->d_text_ids.grow((size_t)B * top_k));
+    HIP_TRY(ss->d_text_scores.grow((size_t)B * top_k));
+    HIP_TRY(ss->d_text_counts.grow((size_t)B));
+    int32_t rc = cosdev::bm25_set_score(ss->bm.data(), ss->bm_base.data(), S, q_terms, q_offsets, B);
+    for (u32 i = 0; i < S; i++) // (whatever the call has launched before a failure is drained too)
+        if (hipStream_t st = cosdev::bm25_stream(ss->bm[i])) drain.text.emplace_back(ss->sh[i].device, st);
+    if (rc) return rc;
+    for (u32 i = 0; i < S; i++) {
+        LocalShard &s = ss->sh[i];
+        HIP_TRY(hipSetDevice(s.device));
+        HIP_TRY(hipEventRecord(s.done_text, cosdev::bm25_stream(ss->bm[i])));
+        HIP_TRY(hipStreamWaitEvent(s.stream, s.done_text, 0));
+    }
+    rc = exchange_local(ss, words, Record::BUCKETS);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(root.device));
+    return cosdev::bm25_fold_topk(reinterpret_cast<const u64 *>(root.d_gathered_text.p), S, B, top_k, ss->d_text_ids, ss->d_text_scores, ss->d_text_counts, root.stream);
+}
+} // namespace
+
+extern "C" int32_t cos_shardset_attach_bm25(cos_shardset *ss, cos_bm25 *const *shards, uint32_t n_shards, const uint32_t *doc_bases) {
+    if (!ss) return cos_fail(COS_ERR_INVALID, "bad argument");
+    if (ss->sh.size() != ss->world) return cos_fail(COS_ERR_UNIMPLEMENTED, "cos_shardset_attach_bm25 needs every shard in this process");
+    std::lock_guard<std::mutex> g(ss->mu);
+    if (!shards) { // detach
+        ss->bm.clear();
+        ss->bm_base.clear();
+        return COS_OK;
+    }
+    if (n_shards != ss->world) return cos_fail(COS_ERR_INVALID, "%u BM25 handles for a set of %u shards", n_shards, ss->world);
+    std::vector<cos_bm25 *> bm(shards, shards + n_shards);
+    std::vector<u32> base(n_shards);
+    for (u32 s = 0; s < n_shards; s++) {
+        if (!bm[s]) return cos_fail(COS_ERR_INVALID, "BM25 shard %u is null", s);
+        for (u32 t = 0; t < s; t++)
+            if (bm[t] == bm[s]) return cos_fail(COS_ERR_INVALID, "BM25 shards %u and %u are the same handle", t, s);
+        if (cosdev::bm25_device(bm[s]) != ss->sh[s].device)
+            return cos_fail(COS_ERR_INVALID, "BM25 shard %u lives on device %d, its dense shard on device %d", s, cosdev::bm25_device(bm[s]), ss->sh[s].device);
+        base[s] = doc_bases ? doc_bases[s] : ss->sh[s].ix->p.id_base;
+        if (s && base[s] <= base[s - 1]) return cos_fail(COS_ERR_INVALID, "doc_bases must strictly increase (shard %u: %u after %u)", s, base[s], base[s - 1]);
+    }
+    {
+        std::vector<std::unique_lock<std::mutex>> held;
+        for (cos_bm25 *b : bm) held.emplace_back(cosdev::bm25_mutex(b));
+        if (int32_t rc = check_text_ids(bm, base, ss->first_rank)) return rc;
+    }
+    ss->bm.swap(bm);
+    ss->bm_base.swap(base);
+    return COS_OK;
+}
+
+extern "C" int32_t cos_shardset_bm25_search_batch(cos_shardset *ss, const uint32_t *q_terms, const uint32_t *q_offsets, uint32_t B, uint32_t top_k,
+                                                  uint32_t *out_ids, float *out_scores, uint32_t *out_counts) {
+    if (int32_t rc = text_check(ss, q_terms, q_offsets, B, top_k, out_ids, out_scores, out_counts, "cos_shardset_bm25_search_batch")) return rc;
+    std::lock_guard<std::mutex> g(ss->mu);
+    if (ss->bm.empty()) return cos_fail(COS_ERR_NOT_READY, "no BM25 shards attached (cos_shardset_attach_bm25)");
+    TextLocks locks(ss);
+    if (int32_t rc = check_text_ids(ss->bm, ss->bm_base, ss->first_rank)) return rc;
+    DrainAll drain_all{ss};
+    int32_t rc = text_lists(ss, drain_all, q_terms, q_offsets, B, top_k);
+    if (rc) return rc;
+    LocalShard &root = ss->sh[0];
+    HIP_TRY(hipMemcpyAsync(out_ids, ss->d_text_ids, (size_t)B * top_k * 4, hipMemcpyDeviceToHost, root.stream));
+    HIP_TRY(hipMemcpyAsync(out_scores, ss->d_text_scores, (size_t)B * top_k * 4, hipMemcpyDeviceToHost, root.stream));
+    HIP_TRY(hipMemcpyAsync(out_counts, ss->d_text_counts, (size_t)B * 4, hipMemcpyDeviceToHost, root.stream));
+    HIP_TRY(hipStreamSynchronize(root.stream));
+    return COS_OK;
+}
+
+extern "C" int32_t cos_shardset_hybrid_search_batch(cos_shardset *ss, const float *queries, const uint32_t *q_terms, const uint32_t *q_offsets, uint32_t B,
+                                                    uint32_t top_k, float fusion_constant_k, uint32_t *out_ids, float *out_scores, uint32_t *out_counts) {
+    if (int32_t rc = text_check(ss, q_terms, q_offsets, B, top_k, out_ids, out_scores, out_counts, "cos_shardset_hybrid_search_batch")) return rc;
+    if (!queries) return cos_fail(COS_ERR_INVALID, "bad argument");
+    if (top_k > 170) return cos_fail(COS_ERR_UNIMPLEMENTED, "top_k above 170: RRF lists longer than 1024 entries");
+    const u32 k3 = 3 * top_k; // repo::hybrid_search asks both halves for top_k * 3
+    if (int32_t wrc = check_merge_width(ss->world, k3)) return wrc;
+    std::lock_guard<std::mutex> g(ss->mu);
+    if (ss->bm.empty()) return cos_fail(COS_ERR_NOT_READY, "no BM25 shards attached (cos_shardset_attach_bm25)");
+    TextLocks locks(ss);
+    if (int32_t rc = check_text_ids(ss->bm, ss->bm_base, ss->first_rank)) return rc;
+    LocalShard &root = ss->sh[0];
+    const size_t words = (size_t)B * (2 * (size_t)k3 + 1), nk = (size_t)B * top_k, ret_words = 2 * nk + B;
+    HIP_TRY(hipSetDevice(root.device));
+    HIP_TRY(ss->d_ret.grow(ret_words));
+    HIP_TRY(ss->h_ret.grow(ret_words));
+    DrainAll drain_all{ss};
+    // 1. the dense half FIRST on every device (cos_hybrid_search_batch: the walk is a chain of dependent rounds, the scoring kernel fills
+    //    whatever it leaves free), 2. the text half beside it, its host side prepared while the devices already walk
+    int32_t rc = enqueue_walks(ss, queries, B, k3, words, &drain_all);
+    if (rc) return rc;
+    rc = text_lists(ss, drain_all, q_terms, q_offsets, B, k3);
+    if (rc) return rc;
+    // 3. the dense exchange and merge; both merged list sets are now on shard 0's device: RRF there, ONE copy back
+    rc = exchange_merge(ss, B, k3, words);
+    if (rc) return rc;
+    u32 *d_fid = ss->d_ret, *d_fcnt = ss->d_ret + 2 * nk;
+    float *d_fsc = reinterpret_cast<float *>(ss->d_ret + nk);
+    rc = cosdev::rrf_fuse_device(ss->d_out_ids, ss->d_out_counts, ss->d_text_ids, ss->d_text_counts, k3, B, fusion_constant_k, top_k, d_fid, d_fsc, d_fcnt, root.stream);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(ss->h_ret, ss->d_ret, ret_words * 4, hipMemcpyDeviceToHost, root.stream));
+    rc = check_walk_statuses(ss, B); // (synchronises every shard's stream, shard 0's last)
+    if (rc) return rc;
+    const u32 *hr = ss->h_ret;
+    memcpy(out_ids, hr, nk * 4);
+    memcpy(out_scores, hr + nk, nk * 4);
+    memcpy(out_counts, hr + 2 * nk, (size_t)B * 4);
+    return COS_OK;
 }

@@ -28,11 +28,13 @@ class ShardSet:
         self._h = C.c_void_p()
         check(_lib.lib().cos_shardset_create(arr, len(self.shards), 0, len(self.shards), None, C.byref(self._h)))
         self.dim = self.shards[0].dim
+        self.bm25_shards = []                           # the attached BM25 handles (attach_bm25), kept alive while attached
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             _lib.lib().cos_shardset_destroy(self._h)
             self._h = C.c_void_p()
+        self.bm25_shards = []
 
     def __del__(self):
         try:
@@ -128,6 +130,56 @@ class ShardSet:
         p = lambda a: a.ctypes.data_as(C.c_void_p)
         check(_lib.lib().cos_shardset_bruteforce_topk(self._h, p(q), B, k, sm, p(ids), p(scores), p(counts)))
         del keep
+        return ids, scores, counts
+
+    # ---- the text half of the collection: BM25 and dense + BM25 hybrid search ---------------------------------------------------
+    def attach_bm25(self, indexes, doc_bases=None):
+        """indexes[s] (BM25Index) holds the documents of shard s under LOCAL ids; a document's global id is doc_bases[s] + local id
+        (None: the dense shards' id_base).  The handles stay the caller's — inserts and deletes go to the owning shard's handle with
+        local ids — and must outlive the attachment; attaching again replaces them, attach_bm25(None) detaches."""
+        if indexes is None:
+            check(_lib.lib().cos_shardset_attach_bm25(self._h, None, 0, None))
+            self.bm25_shards = []
+            return self
+        indexes = list(indexes)
+        arr = (C.c_void_p * max(len(indexes), 1))(*[b._h for b in indexes])
+        bases = None if doc_bases is None else np.ascontiguousarray(doc_bases, dtype=np.uint32)
+        if bases is not None and bases.shape != (len(indexes),):
+            raise CosdataError(_lib.ERR_INVALID, f"doc_bases must hold {len(indexes)} bases, got shape {tuple(bases.shape)}")
+        check(_lib.lib().cos_shardset_attach_bm25(self._h, arr, len(indexes), None if bases is None else bases.ctypes.data_as(C.c_void_p)))
+        self.bm25_shards = indexes                      # (kept alive while attached)
+        return self
+
+    @staticmethod
+    def _terms(q_terms, q_offsets):
+        qt = np.ascontiguousarray(q_terms, dtype=np.uint32).ravel()
+        qo = np.ascontiguousarray(q_offsets, dtype=np.uint32).ravel()
+        if qo.size < 1 or int(qo[-1]) != qt.size:
+            raise CosdataError(_lib.ERR_INVALID, "q_offsets must have B + 1 entries and end at len(q_terms)")
+        if qt.size == 0:
+            qt = np.zeros(1, np.uint32)                 # (a non-null pointer for a batch of empty queries)
+        return qt, qo
+
+    def bm25_search(self, q_terms, q_offsets, top_k: int):
+        """BM25Index.search_batch over the attached shards: global ids [B][k], score bits and counts [B] of ONE index holding the whole
+        collection's postings (the idf is the collection's, the 512 buckets are folded over the shards)"""
+        qt, qo = self._terms(q_terms, q_offsets)
+        B = qo.size - 1
+        ids = np.full((B, top_k), 0xFFFFFFFF, np.uint32)
+        scores = np.zeros((B, top_k), np.float32)
+        counts = np.zeros(B, np.uint32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        check(_lib.lib().cos_shardset_bm25_search_batch(self._h, p(qt), p(qo), B, top_k, p(ids), p(scores), p(counts)))
+        return ids, scores, counts
+
+    def hybrid_search(self, queries, q_terms, q_offsets, top_k: int, fusion_constant_k: float = 60.0):
+        """hybrid_search_batch on the set: batch_search and bm25_search for 3 * top_k each, fused by RRF on shard 0's device"""
+        q, B, ids, scores, counts = self._outputs(queries, top_k)
+        qt, qo = self._terms(q_terms, q_offsets)
+        if qo.size != B + 1:
+            raise CosdataError(_lib.ERR_INVALID, f"{B} dense queries but {qo.size - 1} term lists")
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        check(_lib.lib().cos_shardset_hybrid_search_batch(self._h, p(q), p(qt), p(qo), B, top_k, fusion_constant_k, p(ids), p(scores), p(counts)))
         return ids, scores, counts
 
 

@@ -861,6 +861,30 @@ int32_t cos_shardset_bruteforce_topk(cos_shardset *ss, const float *queries, uin
                                      const cos_scan_mask *const *shard_masks, uint32_t *out_ids, float *out_scores,
                                      uint32_t *out_counts);
 
+/* The text half of the collection on a shard set.  cos_bm25 handle s holds the documents of shard s under LOCAL ids
+ * 0 .. n_s - 1; the global id of a document is doc_bases[s] + local id (doc_bases == NULL: the dense shards' id_base).  The handles stay
+ * owned by the caller, who inserts into and deletes from the owning shard's handle with local ids; attaching again replaces them;
+ * shards == NULL detaches.  n_shards must equal the set's shard count, handle s must live on dense shard s's device, the bases must
+ * strictly increase and doc_bases[s] + (largest id handle s has ever held) must stay below 2^32 - 1 and below doc_bases[s + 1] (a global
+ * id names one document), else COS_ERR_INVALID (the id rules are checked again by every search: inserts move the largest id).  A set that
+ * does not hold every shard in this process: COS_ERR_UNIMPLEMENTED. */
+int32_t cos_shardset_attach_bm25(cos_shardset *ss, cos_bm25 *const *shards, uint32_t n_shards, const uint32_t *doc_bases);
+/* cos_bm25_search_batch over the attached shards: ids (global), score bits and counts of ONE cos_bm25 handle created from the whole
+ * collection's postings.  Per query term the idf comes from the collection — documents_count and list length summed over the shards,
+ * tombstones included — looked up in every shard's term table per call; every shard scores its own documents with it into its 512
+ * buckets per query, keyed by the GLOBAL id; ONE exchange brings the S bucket arrays to shard 0's device, one kernel takes their
+ * element-wise maximum, sorts and cuts.  More than 64 of a query's terms with a list in ANY shard: COS_ERR_UNIMPLEMENTED, as the single
+ * handle refuses 64 matching terms.  Nothing attached: COS_ERR_NOT_READY.  Locks: the set's, then every handle's in shard order, held
+ * from the term lookup to the call's synchronisation — an update of a shard handle happens before or after a search, never inside. */
+int32_t cos_shardset_bm25_search_batch(cos_shardset *ss, const uint32_t *q_terms, const uint32_t *q_offsets, uint32_t B,
+                                       uint32_t top_k, uint32_t *out_ids, float *out_scores, uint32_t *out_counts);
+/* cos_hybrid_search_batch on the set: cos_shardset_search_batch for 3 * top_k and the call above for 3 * top_k, both merged lists left on
+ * shard 0's device, RRF there, one copy back.  On every device the dense half is enqueued first.  top_k > 170 or S * 3 * top_k > 8192:
+ * COS_ERR_UNIMPLEMENTED.  A failing dense query fails the call with the first failing shard's status. */
+int32_t cos_shardset_hybrid_search_batch(cos_shardset *ss, const float *queries, const uint32_t *q_terms, const uint32_t *q_offsets,
+                                         uint32_t B, uint32_t top_k, float fusion_constant_k,
+                                         uint32_t *out_ids, float *out_scores, uint32_t *out_counts);
+
 /* ---- tuning knobs (experiments; NOT a reference interface) ------------------------------------------------------------------
  * Launch-policy knobs of the kernels — which of two implementations of one operator runs, launch sizes at which a policy
  * switches, prefetch depths.  None changes a result; the parity tests use them to compare implementations, the profiling
