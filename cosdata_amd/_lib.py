@@ -156,6 +156,7 @@ ABI_SYMBOLS = [
     "cos_shardset_unique_id", "cos_shardset_create", "cos_shardset_destroy", "cos_shardset_search_batch", "cos_shardset_exchange_device",
     "cos_shardset_search_filtered_batch", "cos_shardset_flat_search_batch", "cos_shardset_bruteforce_topk",
     "cos_shardset_attach_bm25", "cos_shardset_bm25_search_batch", "cos_shardset_hybrid_search_batch",
+    "cos_shardset_attach_sparse", "cos_shardset_sparse_search_batch", "cos_shardset_hybrid_search_mixed",
     "cos_tuning_set", "cos_tuning_clear", "cos_tuning_get",
 ]
 
@@ -275,6 +276,9 @@ def lib():
         "cos_shardset_attach_bm25": [vp, vp, u32, vp],
         "cos_shardset_bm25_search_batch": [vp, vp, vp, u32, u32, vp, vp, vp],
         "cos_shardset_hybrid_search_batch": [vp, vp, vp, vp, u32, u32, f32, vp, vp, vp],
+        "cos_shardset_attach_sparse": [vp, vp, u32, vp],
+        "cos_shardset_sparse_search_batch": [vp, vp, vp, vp, u32, u32, f32, u32, vp, vp, vp],
+        "cos_shardset_hybrid_search_mixed": [vp, C.POINTER(CosHybridRequest), vp, vp, vp],
         "cos_tuning_set": [C.c_char_p, C.c_int64],
         "cos_tuning_clear": [C.c_char_p],
         "cos_tuning_get": [C.c_char_p, C.POINTER(C.c_int64), C.POINTER(i32)],

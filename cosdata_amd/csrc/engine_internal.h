@@ -19,6 +19,10 @@
 #include "walk_plan.h"
 #include "table_nested.h"
 
+namespace hybrid_plan {
+struct Slot; // hybrid_plan.h
+}
+
 namespace cosdev {
 hipError_t launch_fill_i32(int32_t *p, u64 n, int32_t v, hipStream_t st);
 hipError_t launch_edge_pairs(const u32 *adj_vec, const u32 *node_vec, u32 node0, u32 cn, u32 M, u32 *px, u32 *py, hipStream_t st);
@@ -94,6 +98,17 @@ int32_t sparse_device(const cos_sparse *s);
 void sparse_limits(const cos_sparse *s, u32 *max_candidates, bool *have_raw, u32 *batch_bound);
 int32_t sparse_search_locked(cos_sparse *s, const uint32_t *q_dims, const float *q_vals, const uint32_t *q_offsets, u32 B, u32 top_k,
                              float early_terminate_threshold, u32 reranking_factor, u32 *d_out_ids, float *d_out_scores, u32 *d_out_counts, hipStream_t st);
+// The learned-sparse handle as one shard of a collection (shardset.hip holds the lock of every attached handle, in shard order, from the
+// limit checks to the call's synchronisation).  sparse_shape and sparse_record_locked are for a caller that holds sparse_mutex.
+void sparse_shape(const cos_sparse *s, u32 *bits, float *upper, u32 *n);
+// resolve + scan + the record form of the finish kernel on `st`: the handle's best top_k * max(reranking_factor, 1) candidates per query
+// under global ids id_base + local id, laid out as sparse_fold_plan::layout says, into d_record (8-byte aligned).  sparse_admit's rules;
+// one batch in flight per handle.
+int32_t sparse_record_locked(cos_sparse *s, const uint32_t *q_dims, const float *q_vals, const uint32_t *q_offsets, u32 B, u32 top_k,
+                             float early_terminate_threshold, u32 reranking_factor, u32 id_base, u32 *d_record, hipStream_t st);
+// gathered [S][record words] -> the collection's lists [B][top_k] / [B] (sparse_fold_rerank_kernel<N>, N from sparse_fold_plan::plan), on `st`
+int32_t sparse_fold_rerank(const u32 *d_gathered, u32 S, u32 B, u32 top_k, u32 reranking_factor, u32 *d_out_ids, float *d_out_scores, u32 *d_out_counts,
+                           hipStream_t st);
 // The BM25 handle as a shard set sees it (kernels_hybrid.hip defines it; shardset.hip holds the lock of every attached handle, in shard
 // order, from the term lookup to the call's synchronisation).  Everything but bm25_mutex / bm25_device is for a caller that holds the locks.
 std::mutex &bm25_mutex(cos_bm25 *b);
@@ -111,6 +126,11 @@ int32_t bm25_fold_topk(const u64 *d_gathered, u32 S, u32 B, u32 top_k, u32 *d_ou
 // rrf_kernel over two resident list sets of stride k3 = 3 * top_k, on `st`
 int32_t rrf_fuse_device(const u32 *d_first_ids, const u32 *d_first_counts, const u32 *d_second_ids, const u32 *d_second_counts, u32 k3, u32 B,
                         float fusion_constant_k, u32 top_k, u32 *d_out_ids, float *d_out_scores, u32 *d_out_counts, hipStream_t st);
+// rrf_mixed_kernel over the three resident list sets of a mixed hybrid batch (stride k3; a set without queries is NULL), d_slots[B] the
+// request's query_mapping (hybrid_plan.h), on `st`
+int32_t rrf_mixed_device(const u32 *d_dense_ids, const u32 *d_dense_counts, const u32 *d_sparse_ids, const u32 *d_sparse_counts, const u32 *d_bm25_ids,
+                         const u32 *d_bm25_counts, const hybrid_plan::Slot *d_slots, u32 k3, u32 B, float fusion_constant_k, u32 top_k, u32 *d_out_ids,
+                         float *d_out_scores, u32 *d_out_counts, hipStream_t st);
 } // namespace cosdev
 
 // ------------------------------------------------------------------------------------------------

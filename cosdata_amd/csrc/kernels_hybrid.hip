@@ -803,6 +803,25 @@ int32_t rrf_fuse_device(const u32 *d_first_ids, const u32 *d_first_counts, const
     HIP_TRY(hipGetLastError());
     return COS_OK;
 }
+
+int32_t rrf_mixed_device(const u32 *d_dense_ids, const u32 *d_dense_counts, const u32 *d_sparse_ids, const u32 *d_sparse_counts, const u32 *d_bm25_ids,
+                         const u32 *d_bm25_counts, const hybrid_plan::Slot *d_slots, u32 k3, u32 B, float fusion_constant_k, u32 top_k, u32 *d_out_ids,
+                         float *d_out_scores, u32 *d_out_counts, hipStream_t st) {
+    const RrfListSets sets{d_dense_ids, d_dense_counts, d_sparse_ids, d_sparse_counts, d_bm25_ids, d_bm25_counts};
+    const size_t smem = (size_t)2 * k3 * 4;
+#define LAUNCH(R) hipLaunchKernelGGL(rrf_mixed_kernel<R>, dim3(B), dim3(64), smem, st, sets, d_slots, k3, B, fusion_constant_k, top_k, d_out_ids, d_out_scores, d_out_counts)
+    switch (hybrid_plan::rrf_keys_per_lane(2 * k3)) {
+    case 0: return cos_fail(COS_ERR_UNIMPLEMENTED, "top_k above 170: RRF lists longer than 1024 entries");
+    case 1: LAUNCH(1); break;
+    case 2: LAUNCH(2); break;
+    case 4: LAUNCH(4); break;
+    case 8: LAUNCH(8); break;
+    default: LAUNCH(16); break;
+    }
+#undef LAUNCH
+    HIP_TRY(hipGetLastError());
+    return COS_OK;
+}
 } // namespace cosdev
 
 
@@ -977,20 +996,10 @@ extern "C" int32_t cos_hybrid_search_mixed(cos_hybrid *h, cos_index *ix, cos_spa
     hipStream_t sf = h->st_dense;
     if (n.n_sparse) HYB_TRY(hipStreamWaitEvent(sf, h->ev_sparse, 0));
     if (n.n_bm25) HYB_TRY(hipStreamWaitEvent(sf, h->ev_bm25, 0));
-    const RrfListSets sets{n.n_dense ? h->d_did.p : nullptr, n.n_dense ? h->d_dcnt.p : nullptr, n.n_sparse ? h->d_sid.p : nullptr, n.n_sparse ? h->d_scnt.p : nullptr,
-                           n.n_bm25 ? h->d_bid.p : nullptr, n.n_bm25 ? h->d_bcnt.p : nullptr};
     const hp::Slot *d_slots = (const hp::Slot *)(h->d_in.p + q_bytes);
-    const size_t smem = (size_t)2 * k3 * 4;
-#define LAUNCH(R) hipLaunchKernelGGL(rrf_mixed_kernel<R>, dim3(B), dim3(64), smem, sf, sets, d_slots, k3, B, rq->fusion_constant_k, top_k, d_fid, d_fsc, d_fcnt)
-    switch (hp::rrf_keys_per_lane(2 * k3)) {
-    case 1: LAUNCH(1); break;
-    case 2: LAUNCH(2); break;
-    case 4: LAUNCH(4); break;
-    case 8: LAUNCH(8); break;
-    default: LAUNCH(16); break; // (2 * k3 <= 1024: checked above)
-    }
-#undef LAUNCH
-    HYB_TRY(hipGetLastError());
+    rc = rrf_mixed_device(n.n_dense ? h->d_did.p : nullptr, n.n_dense ? h->d_dcnt.p : nullptr, n.n_sparse ? h->d_sid.p : nullptr, n.n_sparse ? h->d_scnt.p : nullptr,
+                          n.n_bm25 ? h->d_bid.p : nullptr, n.n_bm25 ? h->d_bcnt.p : nullptr, d_slots, k3, B, rq->fusion_constant_k, top_k, d_fid, d_fsc, d_fcnt, sf);
+    if (rc) return fail(rc); // (2 * k3 <= 1024: checked above)
     HYB_TRY(hipMemcpyAsync(h->h_ret, h->d_ret, ret_words * 4, hipMemcpyDeviceToHost, sf));
     HYB_TRY(hipStreamSynchronize(sf));
 #undef HYB_TRY

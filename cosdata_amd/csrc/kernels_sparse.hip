@@ -19,6 +19,7 @@
 
 #include "engine_internal.h"
 #include "postings_update.h"
+#include "sparse_fold_plan.h"
 #include "topk_select.h"
 
 using namespace cosdev;
@@ -649,19 +650,26 @@ __device__ __forceinline__ u64 raw_rerank_key(const SparseDev &ix, u32 v, const 
     return pack_key(simkey(dp), v);
 }
 
+// What sparse_finish_kernel and sparse_record_kernel share: the best 64 keys of a query's S segment pools, lane l the l-th, and how many
+// of them are candidates (select_nth + truncate(k * reranking_factor))
+__device__ __forceinline__ u64 narrow_merge_cut(const u64 *__restrict__ part, u32 S, u32 q, u32 k_with_reranking, int lane, u32 &ncand) {
+    Pool<1> pool;
+    pool.clear();
+    u64 thr = 0ull;
+    for (u32 sgm = 0; sgm < S; sgm++) pool_fold_lanes<1>(pool, thr, part[((u64)q * S + sgm) * SEL + lane], lane);
+    const u32 have = (u32)__popcll(__ballot(pool.e[0] != 0ull));
+    ncand = have < k_with_reranking ? have : k_with_reranking;
+    return pool.e[0];
+}
+
 // one wave per query: merge the segment pools, optional raw-value rerank, write the top k
 __global__ __launch_bounds__(64) void sparse_finish_kernel(const SparseDev ix, const u64 *__restrict__ part, u32 S, const u32 *__restrict__ q_dims,
                                                            const float *__restrict__ q_vals, const u32 *__restrict__ q_off, u32 top_k, u32 k_with_reranking,
                                                            int rerank, u32 *__restrict__ out_ids, float *__restrict__ out_scores, u32 *__restrict__ out_counts) {
     const int lane = threadIdx.x;
     const u32 q = blockIdx.x;
-    Pool<1> pool;
-    pool.clear();
-    u64 thr = 0ull;
-    for (u32 sgm = 0; sgm < S; sgm++) pool_fold_lanes<1>(pool, thr, part[((u64)q * S + sgm) * SEL + lane], lane);
-    const u32 have = (u32)__popcll(__ballot(pool.e[0] != 0ull));
-    const u32 ncand = have < k_with_reranking ? have : k_with_reranking; // select_nth + truncate(k * reranking_factor)
-    const u64 mine = pool.e[0];
+    u32 ncand;
+    const u64 mine = narrow_merge_cut(part, S, q, k_with_reranking, lane, ncand);
     if (!rerank) {
         const u32 nout = ncand < top_k ? ncand : top_k;
         if ((u32)lane < nout) {
@@ -684,6 +692,28 @@ __global__ __launch_bounds__(64) void sparse_finish_kernel(const SparseDev ix, c
     if (lane == 0) out_counts[q] = nout;
 }
 
+// What sparse_wide_finish_kernel<R> and sparse_wide_record_kernel<R> share: best[64 R] <- the best keys of the query's S sorted segments,
+// descending; returns the number of candidates among them.  Ends behind a barrier.
+template <u32 N>
+__device__ __forceinline__ u32 wide_merge_cut(u64 *best, u32 *s_ncand, const u64 *__restrict__ seg, u32 S, u32 k_with_reranking) {
+    for (u32 i = threadIdx.x; i < N; i += blockDim.x) best[i] = seg[i];
+    __syncthreads();
+    for (u32 sgm = 1; sgm < S; sgm++) {
+        const u64 *other = seg + (u64)sgm * N;
+        if (other[0] <= best[N - 1]) continue; // block-uniform: the segment's best key does not make the cut (an empty segment never does)
+        __syncthreads();                       // everybody has read best[N - 1]
+        fold_reversed<N>(best, other);
+        lds_bitonic_merge_desc<N>(best, 1, 0);
+    }
+    // select_nth + truncate(k * reranking_factor): the filled entries come first
+    if (threadIdx.x == 0) *s_ncand = k_with_reranking < N ? k_with_reranking : N;
+    __syncthreads();
+    for (u32 i = threadIdx.x; i < k_with_reranking && i < N; i += blockDim.x)
+        if (best[i] == 0ull && (i == 0u || best[i - 1] != 0ull)) *s_ncand = i;
+    __syncthreads();
+    return *s_ncand;
+}
+
 // The wide finish, one block of 256 threads per query: the S sorted segments of 64 * R keys are folded into the best 64 * R one
 // after the other (fold_reversed + lds_bitonic_merge_desc of topk_select.h: log2(64 R) rounds in 8 KB of LDS at R = 16), cut to k * reranking_factor,
 // re-scored four candidates per thread at R = 16 and sorted again in LDS.  Same arithmetic and order as sparse_finish_kernel.
@@ -696,23 +726,7 @@ __global__ __launch_bounds__(256) void sparse_wide_finish_kernel(const SparseDev
     __shared__ u64 best[N];
     __shared__ u32 s_ncand;
     const u32 q = blockIdx.x;
-    const u64 *seg = part + (u64)q * S * N;
-    for (u32 i = threadIdx.x; i < N; i += blockDim.x) best[i] = seg[i];
-    __syncthreads();
-    for (u32 sgm = 1; sgm < S; sgm++) {
-        const u64 *other = seg + (u64)sgm * N;
-        if (other[0] <= best[N - 1]) continue; // block-uniform: the segment's best key does not make the cut (an empty segment never does)
-        __syncthreads();                       // everybody has read best[N - 1]
-        fold_reversed<N>(best, other);
-        lds_bitonic_merge_desc<N>(best, 1, 0);
-    }
-    // select_nth + truncate(k * reranking_factor): the filled entries come first
-    if (threadIdx.x == 0) s_ncand = k_with_reranking < N ? k_with_reranking : N;
-    __syncthreads();
-    for (u32 i = threadIdx.x; i < k_with_reranking && i < N; i += blockDim.x)
-        if (best[i] == 0ull && (i == 0u || best[i - 1] != 0ull)) s_ncand = i;
-    __syncthreads();
-    const u32 ncand = s_ncand, nout = ncand < top_k ? ncand : top_k;
+    const u32 ncand = wide_merge_cut<N>(best, &s_ncand, part + (u64)q * S * N, S, k_with_reranking), nout = ncand < top_k ? ncand : top_k;
     if (!rerank) {
         for (u32 i = threadIdx.x; i < nout; i += blockDim.x) {
             const u64 mine = best[i];
@@ -733,6 +747,120 @@ __global__ __launch_bounds__(256) void sparse_wide_finish_kernel(const SparseDev
     for (u32 i = threadIdx.x; i < nout; i += blockDim.x) {
         out_ids[(u64)q * top_k + i] = (u32)best[i];
         out_scores[(u64)q * top_k + i] = simkey_inv((u32)(best[i] >> 32));
+    }
+    if (threadIdx.x == 0) out_counts[q] = nout;
+}
+
+// ---- the handle as one shard of a collection (cos_shardset_sparse_search_batch) -------------------------------------
+// A vector's quantized similarity depends on the query and its own postings only, and global id = id_base + local id with increasing
+// bases keeps "larger id first": the collection's best C = k * max(reranking_factor, 1) lie inside the union of every shard's best C.
+// The record form of the two finish kernels stops behind the cut at C and leaves, per query, a RECORD of fixed stride W = 64 * R slots
+// (sparse_fold_plan.h: Layout):
+//   rec_keys  [B][W] u64  pack_key(similarity + 1, id_base + local id), descending; 0 in the slots behind the query's count
+//   rec_counts[B]    u32  candidates of the query in this shard, min(touched vectors, C)
+//   rec_raw   [B][W] u32  simkey(raw-value dot product) of the candidate in the same slot — the score half of raw_rerank_key — when
+//                         the call reranks (not written, not part of the record, otherwise)
+// No sort by raw score and no cut to top_k here: which candidates are re-ranked at all is the collection's decision
+// (sparse_fold_rerank_kernel).
+struct SparseRecord {
+    u64 *keys;
+    u32 *counts, *raw;
+    u32 id_base;
+};
+
+__global__ __launch_bounds__(64) void sparse_record_kernel(const SparseDev ix, const u64 *__restrict__ part, u32 S, const u32 *__restrict__ q_dims,
+                                                           const float *__restrict__ q_vals, const u32 *__restrict__ q_off, u32 k_with_reranking, int rerank,
+                                                           const SparseRecord rec) {
+    const int lane = threadIdx.x;
+    const u32 q = blockIdx.x;
+    u32 ncand;
+    const u64 mine = narrow_merge_cut(part, S, q, k_with_reranking, lane, ncand);
+    const bool cand = (u32)lane < ncand;
+    rec.keys[(u64)q * SEL + lane] = cand ? pack_key((u32)(mine >> 32), rec.id_base + (u32)mine) : 0ull;
+    if (rerank) rec.raw[(u64)q * SEL + lane] = cand ? (u32)(raw_rerank_key(ix, (u32)mine, q_dims, q_vals, q_off, q) >> 32) : 0u;
+    if (lane == 0) rec.counts[q] = ncand;
+}
+
+template <int R>
+__global__ __launch_bounds__(256) void sparse_wide_record_kernel(const SparseDev ix, const u64 *__restrict__ part, u32 S, const u32 *__restrict__ q_dims,
+                                                                 const float *__restrict__ q_vals, const u32 *__restrict__ q_off, u32 k_with_reranking,
+                                                                 int rerank, const SparseRecord rec) {
+    static_assert(R == 2 || R == 4 || R == 8 || R == 16, "wide instantiations");
+    constexpr u32 N = 64u * R;
+    __shared__ u64 best[N];
+    __shared__ u32 s_ncand;
+    const u32 q = blockIdx.x;
+    const u32 ncand = wide_merge_cut<N>(best, &s_ncand, part + (u64)q * S * N, S, k_with_reranking);
+    for (u32 c = threadIdx.x; c < N; c += blockDim.x) {
+        const u64 mine = best[c];
+        const bool cand = c < ncand;
+        rec.keys[(u64)q * N + c] = cand ? pack_key((u32)(mine >> 32), rec.id_base + (u32)mine) : 0ull;
+        if (rerank) rec.raw[(u64)q * N + c] = cand ? (u32)(raw_rerank_key(ix, (u32)mine, q_dims, q_vals, q_off, q) >> 32) : 0u;
+    }
+    if (threadIdx.x == 0) rec.counts[q] = ncand;
+}
+
+// any W <= min(N, 1024) keys at the front of buf, W a power of two >= 64 known at run time (block-uniform) -> sorted
+template <u32 N, u32 W = sparse_fold_plan::MIN_STRIDE>
+__device__ __forceinline__ void lds_sort_front_desc(u64 *buf, u32 w) {
+    if (w == W) lds_bitonic_sort_desc<W>(buf);
+    else if constexpr (2 * W <= N && 2 * W <= sparse_fold_plan::MAX_CANDIDATES) lds_sort_front_desc<N, 2 * W>(buf, w);
+}
+
+// The collection's answer from the S gathered records of a query; one workgroup of 256 threads per query, N >= S * W keys in LDS
+// (sparse_fold_plan.h decides N).  gathered = [S][shard_words] words, every record laid out as above (counts_off / raw_off in words).
+//   1. the S * W quantized keys sorted descending: the first C = k_with_reranking of them are the collection's candidates — the order
+//      of the u64 keys (similarity, then the larger global id) is the single handle's;
+//   2. without a rerank that is the answer;
+//   3. with one, the C-th key is the cut: every thread reads its gathered slots again and a slot whose key makes the cut appends
+//      pack_key(its raw score, its global id) to a compact list at the front of the same LDS (keys are unique: at most C pass), which is
+//      sorted and cut to top_k.
+// The count is min(min(candidates of all shards, C), top_k) from the records' counts, never from a key being non-zero: the raw key of a
+// NaN dot product with id 0 is 0 (sparse_finish_kernel counts by ncand too).
+template <u32 N>
+__global__ __launch_bounds__(256) void sparse_fold_rerank_kernel(const u32 *__restrict__ gathered, u32 S, u64 shard_words, u64 counts_off, u64 raw_off, u32 W,
+                                                                 u32 top_k, u32 k_with_reranking, int rerank, u32 *__restrict__ out_ids,
+                                                                 float *__restrict__ out_scores, u32 *__restrict__ out_counts) {
+    static_assert(N >= sparse_fold_plan::MIN_KEYS && N <= sparse_fold_plan::MAX_KEYS && (N & (N - 1)) == 0, "fold widths");
+    __shared__ u64 buf[N]; // nothing else: 64 KB at N = 8192
+    const u32 q = blockIdx.x, SW = S * W; // SW <= N (the host's plan)
+    const u32 wshift = 31u - (u32)__clz((int)W);
+    auto slot_key = [&](u32 i) { return reinterpret_cast<const u64 *>(gathered + (u64)(i >> wshift) * shard_words)[(u64)q * W + (i & (W - 1u))]; };
+    for (u32 i = threadIdx.x; i < N; i += blockDim.x) buf[i] = i < SW ? slot_key(i) : 0ull;
+    u32 total = 0; // block-uniform, at most S * W
+    for (u32 s = 0; s < S; s++) total += gathered[(u64)s * shard_words + counts_off + q];
+    lds_bitonic_sort_desc<N>(buf);
+    const u32 ncand = total < k_with_reranking ? total : k_with_reranking, nout = ncand < top_k ? ncand : top_k;
+    if (!rerank) {
+        for (u32 i = threadIdx.x; i < nout; i += blockDim.x) {
+            const u64 mine = buf[i];
+            out_ids[(u64)q * top_k + i] = (u32)mine;
+            out_scores[(u64)q * top_k + i] = (float)((u32)(mine >> 32) - 1u); // `similarity as f32`
+        }
+        if (threadIdx.x == 0) out_counts[q] = nout;
+        return;
+    }
+    // fewer than C candidates in the whole collection: every one of them passes (a filled slot's key is at least 1 << 32)
+    const u64 cut = total >= k_with_reranking ? buf[k_with_reranking - 1u] : 1ull;
+    // The sorted keys are dead once the cut is read: the compact list takes buf[0 .. W) and, with two shards or more (W < N), the last
+    // key's words count its entries.  One shard's record is the collection's cut already: slot i is entry i, and W may equal N.
+    u32 *fill = reinterpret_cast<u32 *>(&buf[N - 1]);
+    __syncthreads(); // everybody has read the cut
+    for (u32 i = threadIdx.x; i < W; i += blockDim.x) buf[i] = 0ull;
+    if (threadIdx.x == 0 && S > 1) *fill = 0u;
+    __syncthreads();
+    for (u32 i = threadIdx.x; i < SW; i += blockDim.x) {
+        const u64 key = slot_key(i);
+        if (key >= cut) {
+            const u32 at = S > 1 ? atomicAdd(fill, 1u) : i;
+            const u32 raw = (gathered + (u64)(i >> wshift) * shard_words + raw_off)[(u64)q * W + (i & (W - 1u))];
+            if (at < W) buf[at] = pack_key(raw, (u32)key); // (at < C <= W always: the guard keeps a malformed record inside the list)
+        }
+    }
+    lds_sort_front_desc<N>(buf, W);
+    for (u32 i = threadIdx.x; i < nout; i += blockDim.x) {
+        out_ids[(u64)q * top_k + i] = (u32)buf[i];
+        out_scores[(u64)q * top_k + i] = simkey_inv((u32)(buf[i] >> 32));
     }
     if (threadIdx.x == 0) out_counts[q] = nout;
 }
@@ -779,14 +907,15 @@ struct cos_sparse {
 template <int R>
 static hipError_t sparse_launch_wide(const cos_sparse *s, const SparseDev &dev, u32 B, u32 splits, const STerm *terms, const u32 *qt_off, const u32 *order,
                                      u64 *part, const u32 *qd, const float *qv, const u32 *qo, u32 top_k, u32 kwr, int rerank, u32 *oi, float *os, u32 *oc,
-                                     hipStream_t st) {
+                                     hipStream_t st, const SparseRecord *rec) {
     if (s->packed)
         hipLaunchKernelGGL(sparse_wide_packed_kernel<R>, dim3(B * splits), dim3(256), 0, st, s->d_pk.p, terms, qt_off, s->n, s->d_tile_dir.p, order, splits, part);
     else
         hipLaunchKernelGGL(sparse_tile_kernel<R>, dim3(B * splits), dim3(256), 0, st, s->d_ids.p, s->d_keys.p, terms, qt_off, s->n, s->d_tile_dir.p, order, splits, part);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(sparse_wide_finish_kernel<R>, dim3(B), dim3(256), 0, st, dev, part, splits, qd, qv, qo, top_k, kwr, rerank, oi, os, oc);
+    if (rec) hipLaunchKernelGGL(sparse_wide_record_kernel<R>, dim3(B), dim3(256), 0, st, dev, part, splits, qd, qv, qo, kwr, rerank, *rec);
+    else hipLaunchKernelGGL(sparse_wide_finish_kernel<R>, dim3(B), dim3(256), 0, st, dev, part, splits, qd, qv, qo, top_k, kwr, rerank, oi, os, oc);
     return hipGetLastError();
 }
 
@@ -1078,8 +1207,9 @@ static int32_t sparse_resolve(cos_sparse *s, const uint32_t *q_dims, const float
 }
 
 // Launch: one copy of the staging image, then scan + finish, all on `st`; results to device pointers.  The two events bracket the
-// kernels on the stream they run on.  Nothing here synchronises.
-static int32_t sparse_launch(cos_sparse *s, const SparseBatch &sb, u32 *d_oi, float *d_os, u32 *d_oc, hipStream_t st) {
+// kernels on the stream they run on.  Nothing here synchronises.  With `rec` the record form of the finish kernel runs behind the same
+// scan and the three result pointers are not used.
+static int32_t sparse_launch(cos_sparse *s, const SparseBatch &sb, u32 *d_oi, float *d_os, u32 *d_oc, hipStream_t st, const SparseRecord *rec = nullptr) {
     const u32 B = sb.B, R = sb.R, splits = sb.splits, Q = 1u << s->bits;
     const SparseImage im(B, sb.nq);
     HIP_TRY(s->w_in.grow(im.bytes));
@@ -1094,7 +1224,7 @@ static int32_t sparse_launch(cos_sparse *s, const SparseBatch &sb, u32 *d_oi, fl
     HIP_TRY(hipEventRecord(s->ev0, st));
     if (R > 1) {
         auto wide = R == 2 ? sparse_launch_wide<2> : R == 4 ? sparse_launch_wide<4> : R == 8 ? sparse_launch_wide<8> : sparse_launch_wide<16>;
-        HIP_TRY(wide(s, dev, B, splits, d_terms, d_qt_off, d_order, d_part, d_qd, d_qv, d_qo, sb.top_k, sb.kwr, sb.rerank, d_oi, d_os, d_oc, st));
+        HIP_TRY(wide(s, dev, B, splits, d_terms, d_qt_off, d_order, d_part, d_qd, d_qv, d_qo, sb.top_k, sb.kwr, sb.rerank, d_oi, d_os, d_oc, st, rec));
     } else {
         // eight postings per lane and step; sixteen measured the same (0.447 against 0.453 ms) and was dropped
         if (s->packed)
@@ -1103,7 +1233,8 @@ static int32_t sparse_launch(cos_sparse *s, const SparseBatch &sb, u32 *d_oi, fl
             hipLaunchKernelGGL(sparse_tile_kernel<1>, dim3(B * splits), dim3(256), 0, st, s->d_ids.p, s->d_keys.p, d_terms, d_qt_off, s->n, s->d_tile_dir.p, d_order, splits,
                                d_part);
         HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(sparse_finish_kernel, dim3(B), dim3(64), 0, st, dev, d_part, splits, d_qd, d_qv, d_qo, sb.top_k, sb.kwr, sb.rerank, d_oi, d_os, d_oc);
+        if (rec) hipLaunchKernelGGL(sparse_record_kernel, dim3(B), dim3(64), 0, st, dev, d_part, splits, d_qd, d_qv, d_qo, sb.kwr, sb.rerank, *rec);
+        else hipLaunchKernelGGL(sparse_finish_kernel, dim3(B), dim3(64), 0, st, dev, d_part, splits, d_qd, d_qv, d_qo, sb.top_k, sb.kwr, sb.rerank, d_oi, d_os, d_oc);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipEventRecord(s->ev1, st));
@@ -1134,6 +1265,53 @@ void sparse_limits(const cos_sparse *s, u32 *max_candidates, bool *have_raw, u32
 int32_t sparse_search_locked(cos_sparse *s, const uint32_t *q_dims, const float *q_vals, const uint32_t *q_offsets, u32 B, u32 top_k,
                              float early_terminate_threshold, u32 reranking_factor, u32 *d_out_ids, float *d_out_scores, u32 *d_out_counts, hipStream_t st) {
     return sparse_search_on_stream(s, q_dims, q_vals, q_offsets, B, top_k, early_terminate_threshold, reranking_factor, d_out_ids, d_out_scores, d_out_counts, st);
+}
+
+void sparse_shape(const cos_sparse *s, u32 *bits, float *upper, u32 *n) {
+    *bits = s->bits;
+    *upper = s->upper;
+    *n = s->n;
+}
+
+static_assert(sparse_fold_plan::OK == COS_OK && sparse_fold_plan::INVALID == COS_ERR_INVALID && sparse_fold_plan::UNIMPLEMENTED == COS_ERR_UNIMPLEMENTED,
+              "sparse_fold_plan.h restates cos_status");
+static_assert(sparse_fold_plan::MIN_STRIDE == SEL && sparse_fold_plan::MAX_CANDIDATES == SEL_MAX, "sparse_fold_plan.h restates the pool widths");
+
+int32_t sparse_record_locked(cos_sparse *s, const uint32_t *q_dims, const float *q_vals, const uint32_t *q_offsets, u32 B, u32 top_k,
+                             float early_terminate_threshold, u32 reranking_factor, u32 id_base, u32 *d_record, hipStream_t st) {
+    HIP_TRY(hipSetDevice(s->device));
+    int32_t rc = sparse_wait_previous(s);
+    if (rc) return rc;
+    SparseBatch sb;
+    rc = sparse_resolve(s, q_dims, q_vals, q_offsets, B, top_k, early_terminate_threshold, reranking_factor, sb); // (sparse_admit's rules first)
+    if (rc) return rc;
+    const sparse_fold_plan::Layout lay = sparse_fold_plan::layout(B, sb.kwr, sb.rerank != 0);
+    if (lay.stride != SEL * sb.R) return cos_fail(COS_ERR_INVALID, "record stride %u against a pool of %u keys", lay.stride, SEL * sb.R);
+    const SparseRecord rec{reinterpret_cast<u64 *>(d_record), d_record + lay.counts, d_record + lay.raw, id_base};
+    return sparse_launch(s, sb, nullptr, nullptr, nullptr, st, &rec);
+}
+
+int32_t sparse_fold_rerank(const u32 *d_gathered, u32 S, u32 B, u32 top_k, u32 reranking_factor, u32 *d_out_ids, float *d_out_scores, u32 *d_out_counts,
+                           hipStream_t st) {
+    const bool rerank = reranking_factor != 0;
+    const u64 C = (u64)top_k * (rerank ? reranking_factor : 1u);
+    const sparse_fold_plan::Plan fp = sparse_fold_plan::plan(S, C);
+    if (fp.status) return cos_fail(fp.status, "%u shards x %llu candidates: the fold holds at most %u keys per query", S, (unsigned long long)C, sparse_fold_plan::MAX_KEYS);
+    const sparse_fold_plan::Layout lay = sparse_fold_plan::layout(B, C, rerank);
+#define LAUNCH(N)                                                                                                                                          \
+    hipLaunchKernelGGL(sparse_fold_rerank_kernel<N>, dim3(B), dim3(sparse_fold_plan::THREADS), 0, st, d_gathered, S, (u64)lay.words, (u64)lay.counts, (u64)lay.raw, \
+                       lay.stride, top_k, (u32)C, rerank ? 1 : 0, d_out_ids, d_out_scores, d_out_counts)
+    switch (fp.N) {
+    case 256: LAUNCH(256); break;
+    case 512: LAUNCH(512); break;
+    case 1024: LAUNCH(1024); break;
+    case 2048: LAUNCH(2048); break;
+    case 4096: LAUNCH(4096); break;
+    default: LAUNCH(8192); break; // (the plan refuses above)
+    }
+#undef LAUNCH
+    HIP_TRY(hipGetLastError());
+    return COS_OK;
 }
 } // namespace cosdev
 

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -30,7 +31,9 @@
 
 #include "engine_internal.h"
 #include "flat_plan.h"
+#include "hybrid_plan.h"
 #include "merge_plan.h"
+#include "sparse_fold_plan.h"
 
 using namespace cosdev;
 
@@ -86,22 +89,29 @@ struct LocalShard {
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;
     hipEvent_t done_text = nullptr; // the shard's BM25 buckets are complete (recorded on the attached handle's stream)
+    hipStream_t stream_sp = nullptr; // the attached learned-sparse handle's scan and record run here, beside the walk
+    hipEvent_t done_sp = nullptr;    // ... and this says that the record is complete
     ncclComm_t comm = nullptr;
     // per-shard device buffers, grown on demand
     DevArr<float> d_queries;
     DevArr<u32> d_packed;   // this shard's record [ids B*k | scores B*k | counts B]
     DevArr<u32> d_gathered; // [world][words]
     DevArr<u32> d_gathered_text; // [world][B * 1024]: every shard's B x 512 bucket keys (u64)
+    DevArr<u32> d_record_sp;   // this shard's learned-sparse candidate record (sparse_fold_plan::Layout)
+    DevArr<u32> d_gathered_sp; // [world][record words]
     DevArr<int32_t> d_status;
     LocalShard() = default;
     LocalShard(const LocalShard &) = delete;
     ~LocalShard() { // on the shard's device, its stream drained before anything is released
         (void)hipSetDevice(device);
+        if (stream_sp) (void)hipStreamSynchronize(stream_sp);
         if (stream) (void)hipStreamSynchronize(stream);
         if (comm) (void)rccl()->CommDestroy(comm);
-        d_queries.reset(); d_packed.reset(); d_gathered.reset(); d_gathered_text.reset(); d_status.reset();
+        d_queries.reset(); d_packed.reset(); d_gathered.reset(); d_gathered_text.reset(); d_record_sp.reset(); d_gathered_sp.reset(); d_status.reset();
         if (done) (void)hipEventDestroy(done);
         if (done_text) (void)hipEventDestroy(done_text);
+        if (done_sp) (void)hipEventDestroy(done_sp);
+        if (stream_sp) (void)hipStreamDestroy(stream_sp);
         if (stream) (void)hipStreamDestroy(stream);
     }
 };
@@ -123,6 +133,14 @@ struct cos_shardset {
     DevArr<u32> d_text_ids, d_text_counts, d_ret;
     DevArr<float> d_text_scores;
     PinArr<u32> h_ret;
+    // the learned-sparse half (cos_shardset_attach_sparse): handle s holds shard s's vectors under local ids, global id = sp_base[s] + local
+    std::vector<cos_sparse *> sp;
+    std::vector<u32> sp_base;
+    // on shard 0's device: the collection's learned-sparse lists [B][k] after the fold; a mixed hybrid request's query_mapping
+    DevArr<u32> d_sp_ids, d_sp_counts;
+    DevArr<float> d_sp_scores;
+    DevArr<hybrid_plan::Slot> d_slots;
+    PinArr<hybrid_plan::Slot> h_slots;
 };
 
 extern "C" int32_t cos_shardset_unique_id(uint8_t *out) {
@@ -145,6 +163,7 @@ extern "C" int32_t cos_shardset_destroy(cos_shardset *ss) {
     if (any) (void)hipSetDevice(dev0);
     ss->d_out_ids.reset(); ss->d_out_counts.reset(); ss->d_out_scores.reset();
     ss->d_text_ids.reset(); ss->d_text_counts.reset(); ss->d_text_scores.reset(); ss->d_ret.reset(); ss->h_ret.reset();
+    ss->d_sp_ids.reset(); ss->d_sp_counts.reset(); ss->d_sp_scores.reset(); ss->d_slots.reset(); ss->h_slots.reset();
     delete ss;
     return COS_OK;
 }
@@ -175,7 +194,9 @@ extern "C" int32_t cos_shardset_create(cos_index *const *shards, uint32_t n_loca
     for (LocalShard &s : ss->sh) {
         if (hipSetDevice(s.device) != hipSuccess || hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) != hipSuccess ||
             hipEventCreateWithFlags(&s.done, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&s.done_text, hipEventDisableTiming) != hipSuccess)
+            hipEventCreateWithFlags(&s.done_text, hipEventDisableTiming) != hipSuccess ||
+            hipStreamCreateWithFlags(&s.stream_sp, hipStreamNonBlocking) != hipSuccess ||
+            hipEventCreateWithFlags(&s.done_sp, hipEventDisableTiming) != hipSuccess)
             return fail(cos_fail(COS_ERR_HIP, "cannot create stream/event on device %d", s.device));
     }
     // RCCL communicators: needed whenever records cross a device boundary
@@ -205,12 +226,17 @@ extern "C" int32_t cos_shardset_create(cos_index *const *shards, uint32_t n_loca
 }
 
 // What one exchange moves: a record is `words` words per shard — the packed lists B (2k + 1) of the dense operators, or the B x 512 bucket
-// keys of the text half, which leave straight from the attached handle's bucket array.
-enum class Record { LISTS, BUCKETS };
+// keys of the text half, which leave straight from the attached handle's bucket array, or the candidate record of the learned-sparse half.
+enum class Record { LISTS, BUCKETS, CANDIDATES };
 static const u32 *record_src(cos_shardset *ss, u32 i, Record rec) {
-    return rec == Record::LISTS ? ss->sh[i].d_packed.p : reinterpret_cast<const u32 *>(cosdev::bm25_buckets(ss->bm[i]));
+    return rec == Record::LISTS        ? ss->sh[i].d_packed.p
+           : rec == Record::CANDIDATES ? ss->sh[i].d_record_sp.p
+                                       : reinterpret_cast<const u32 *>(cosdev::bm25_buckets(ss->bm[i]));
 }
-static u32 *record_dst(LocalShard &s, Record rec) { return rec == Record::LISTS ? s.d_gathered.p : s.d_gathered_text.p; }
+static u32 *record_dst(LocalShard &s, Record rec) {
+    return rec == Record::LISTS ? s.d_gathered.p : rec == Record::CANDIDATES ? s.d_gathered_sp.p : s.d_gathered_text.p;
+}
+static hipEvent_t record_event(LocalShard &s, Record rec) { return rec == Record::LISTS ? s.done : rec == Record::CANDIDATES ? s.done_sp : s.done_text; }
 
 // gathered[world][words] on every local shard's device <- every shard's record; enqueued on the shards' streams, each of which is
 // already behind its own shard's record (it produced it, or waits for the event of the stream that did)
@@ -232,7 +258,7 @@ static int32_t exchange_local(cos_shardset *ss, size_t words, Record rec = Recor
     HIP_TRY(hipSetDevice(root.device));
     for (u32 s = 0; s < S; s++) {
         LocalShard &src = ss->sh[s];
-        if (s) HIP_TRY(hipStreamWaitEvent(root.stream, rec == Record::LISTS ? src.done : src.done_text, 0));
+        if (s) HIP_TRY(hipStreamWaitEvent(root.stream, record_event(src, rec), 0));
         u32 *dst = record_dst(root, rec) + (size_t)s * words;
         if (src.device == root.device)
             HIP_TRY(hipMemcpyAsync(dst, record_src(ss, s, rec), words * 4, hipMemcpyDeviceToDevice, root.stream));
@@ -248,7 +274,11 @@ struct DrainAll { // every return path — a later shard's error, a failed grow,
     std::vector<std::pair<int, hipStream_t>> text; // ... nor on a stream of an attached BM25 handle that the call has used
     ~DrainAll() {
         for (auto &t : text) { (void)hipSetDevice(t.first); (void)hipStreamSynchronize(t.second); }
-        for (LocalShard &s : ss->sh) { (void)hipSetDevice(s.device); (void)hipStreamSynchronize(s.stream); }
+        for (LocalShard &s : ss->sh) { // (the learned-sparse records first: the shards' streams wait for them)
+            (void)hipSetDevice(s.device);
+            (void)hipStreamSynchronize(s.stream_sp);
+            (void)hipStreamSynchronize(s.stream);
+        }
         (void)hipSetDevice(ss->sh[0].device);
     }
 };
@@ -626,5 +656,231 @@ extern "C" int32_t cos_shardset_hybrid_search_batch(cos_shardset *ss, const floa
     memcpy(out_ids, hr, nk * 4);
     memcpy(out_scores, hr + nk, nk * 4);
     memcpy(out_counts, hr + 2 * nk, (size_t)B * 4);
+    return COS_OK;
+}
+
+// ---- the learned-sparse half of the collection on a shard set, and the mixed hybrid call ------------------------------------------------
+// (the scheme and why it is the whole index's answer bit for bit: kernels_sparse.hip, "The handle as one shard of a collection")
+namespace {
+// the locks of every attached learned-sparse handle, in shard order, until the call has synchronised (taken before any BM25 handle's)
+struct SparseLocks {
+    std::vector<std::unique_lock<std::mutex>> held;
+    explicit SparseLocks(const std::vector<cos_sparse *> &sp) {
+        for (cos_sparse *s : sp) held.emplace_back(cosdev::sparse_mutex(s));
+    }
+};
+
+// a global id names one vector, and every shard quantizes alike (inserts move n, so every search asks again); locks held
+int32_t check_sparse_ids(const std::vector<cos_sparse *> &sp, const std::vector<u32> &base, u32 first_rank) {
+    u32 bits0 = 0;
+    float upper0 = 0.0f;
+    for (size_t s = 0; s < sp.size(); s++) {
+        u32 bits = 0, n = 0;
+        float upper = 0.0f;
+        cosdev::sparse_shape(sp[s], &bits, &upper, &n);
+        const u64 end = (u64)base[s] + n; // one past the shard's largest global id
+        if (end >= 0xFFFFFFFFull)
+            return cos_fail(COS_ERR_INVALID, "sparse shard %u: vec_base %u + %u vectors does not fit below 2^32 - 1", first_rank + (u32)s, base[s], n);
+        if (s + 1 < sp.size() && end > base[s + 1])
+            return cos_fail(COS_ERR_INVALID, "sparse shard %u: vec_base %u + %u vectors reaches into the next shard (vec_base %u)", first_rank + (u32)s, base[s], n,
+                            base[s + 1]);
+        if (s == 0) { bits0 = bits; upper0 = upper; }
+        else if (bits != bits0 || memcmp(&upper, &upper0, 4) != 0)
+            return cos_fail(COS_ERR_INVALID, "sparse shard %u: quantization_bits %u / values_upper_bound %g, shard %u has %u / %g", first_rank + (u32)s, bits, upper,
+                            first_rank, bits0, upper0);
+    }
+    return COS_OK;
+}
+
+// what refuses a learned-sparse batch of B queries for top_k before anything is enqueued, in the order the single handle checks; locks held
+int32_t check_sparse_limits(cos_shardset *ss, const uint32_t *q_offsets, u32 B, u32 top_k, u32 reranking_factor) {
+    const u32 S = ss->world;
+    const u64 C = (u64)top_k * (reranking_factor ? reranking_factor : 1u);
+    u32 narrowest = 0xFFFFFFFFu;
+    bool all_raw = true;
+    for (cos_sparse *s : ss->sp) {
+        u32 max_cand = 0, bound = 0;
+        bool raw = false;
+        cosdev::sparse_limits(s, &max_cand, &raw, &bound);
+        if (B >= bound) return cos_fail(COS_ERR_INVALID, "batch of %u queries", B);
+        narrowest = std::min(narrowest, max_cand);
+        all_raw &= raw;
+    }
+    if (!hybrid_plan::offsets_ascend(q_offsets, B)) return cos_fail(COS_ERR_INVALID, "query offsets decrease");
+    if (reranking_factor && !all_raw) return cos_fail(COS_ERR_NOT_READY, "raw-value rerank needs the raw sparse vectors on every shard");
+    if (C > narrowest) return cos_fail(COS_ERR_UNIMPLEMENTED, "top_k x reranking_factor must be <= %u (the narrowest shard's cos_sparse_set_max_candidates)", narrowest);
+    const sparse_fold_plan::Plan fp = sparse_fold_plan::plan(S, C);
+    if (fp.status)
+        return cos_fail(fp.status, "%u shards x %u candidate slots = %llu gathered keys per query: at most %u", S, sparse_fold_plan::record_stride(C),
+                        (unsigned long long)fp.keys, sparse_fold_plan::MAX_KEYS);
+    return COS_OK;
+}
+
+// every shard scans and writes its candidate record on its sparse stream; ONE exchange of the S records; the fold on shard 0's device
+// leaves the collection's lists in d_ids / d_scores [B][top_k], d_counts [B]; everything enqueued, nothing synchronised
+int32_t sparse_lists(cos_shardset *ss, const uint32_t *q_dims, const float *q_vals, const uint32_t *q_offsets, u32 B, u32 top_k, float early_terminate_threshold,
+                     u32 reranking_factor, u32 *d_ids, float *d_scores, u32 *d_counts) {
+    const u32 S = ss->world;
+    const u64 C = (u64)top_k * (reranking_factor ? reranking_factor : 1u);
+    const sparse_fold_plan::Layout lay = sparse_fold_plan::layout(B, C, reranking_factor != 0);
+    LocalShard &root = ss->sh[0];
+    for (LocalShard &s : ss->sh) {
+        HIP_TRY(hipSetDevice(s.device));
+        HIP_TRY(s.d_record_sp.grow(lay.words));
+        if (ss->use_rccl || &s == &root) HIP_TRY(s.d_gathered_sp.grow(lay.words * S)); // (only the all-gather writes every shard's buffer)
+    }
+    for (u32 i = 0; i < S; i++) {
+        LocalShard &s = ss->sh[i];
+        int32_t rc = cosdev::sparse_record_locked(ss->sp[i], q_dims, q_vals, q_offsets, B, top_k, early_terminate_threshold, reranking_factor, ss->sp_base[i],
+                                                  s.d_record_sp, s.stream_sp);
+        if (rc) return rc;
+        HIP_TRY(hipSetDevice(s.device));
+        HIP_TRY(hipEventRecord(s.done_sp, s.stream_sp));
+        HIP_TRY(hipStreamWaitEvent(s.stream, s.done_sp, 0));
+    }
+    int32_t rc = exchange_local(ss, lay.words, Record::CANDIDATES);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(root.device));
+    return cosdev::sparse_fold_rerank(root.d_gathered_sp, S, B, top_k, reranking_factor, d_ids, d_scores, d_counts, root.stream);
+}
+
+// h_ret = [ids B x k | scores B x k | counts B] -> the caller's arrays; entries past a query's count are not written
+void copy_lists_out(const u32 *hr, u32 B, u32 top_k, uint32_t *out_ids, float *out_scores, uint32_t *out_counts) {
+    const size_t nk = (size_t)B * top_k;
+    for (u32 q = 0; q < B; q++) {
+        const u32 c = std::min(hr[2 * nk + q], top_k);
+        memcpy(out_ids + (size_t)q * top_k, hr + (size_t)q * top_k, (size_t)c * 4);
+        memcpy(out_scores + (size_t)q * top_k, hr + nk + (size_t)q * top_k, (size_t)c * 4);
+        out_counts[q] = c;
+    }
+}
+} // namespace
+
+extern "C" int32_t cos_shardset_attach_sparse(cos_shardset *ss, cos_sparse *const *shards, uint32_t n_shards, const uint32_t *vec_bases) {
+    if (!ss) return cos_fail(COS_ERR_INVALID, "bad argument");
+    if (ss->sh.size() != ss->world) return cos_fail(COS_ERR_UNIMPLEMENTED, "cos_shardset_attach_sparse needs every shard in this process");
+    std::lock_guard<std::mutex> g(ss->mu);
+    if (!shards) { // detach
+        ss->sp.clear();
+        ss->sp_base.clear();
+        return COS_OK;
+    }
+    if (n_shards != ss->world) return cos_fail(COS_ERR_INVALID, "%u sparse handles for a set of %u shards", n_shards, ss->world);
+    std::vector<cos_sparse *> sp(shards, shards + n_shards);
+    std::vector<u32> base(n_shards);
+    for (u32 s = 0; s < n_shards; s++) {
+        if (!sp[s]) return cos_fail(COS_ERR_INVALID, "sparse shard %u is null", s);
+        for (u32 t = 0; t < s; t++)
+            if (sp[t] == sp[s]) return cos_fail(COS_ERR_INVALID, "sparse shards %u and %u are the same handle", t, s);
+        if (cosdev::sparse_device(sp[s]) != ss->sh[s].device)
+            return cos_fail(COS_ERR_INVALID, "sparse shard %u lives on device %d, its dense shard on device %d", s, cosdev::sparse_device(sp[s]), ss->sh[s].device);
+        base[s] = vec_bases ? vec_bases[s] : ss->sh[s].ix->p.id_base;
+        if (s && base[s] <= base[s - 1]) return cos_fail(COS_ERR_INVALID, "vec_bases must strictly increase (shard %u: %u after %u)", s, base[s], base[s - 1]);
+    }
+    {
+        SparseLocks locks(sp);
+        if (int32_t rc = check_sparse_ids(sp, base, ss->first_rank)) return rc;
+    }
+    ss->sp.swap(sp);
+    ss->sp_base.swap(base);
+    return COS_OK;
+}
+
+extern "C" int32_t cos_shardset_sparse_search_batch(cos_shardset *ss, const uint32_t *q_dims, const float *q_vals, const uint32_t *q_offsets, uint32_t B,
+                                                    uint32_t top_k, float early_terminate_threshold, uint32_t reranking_factor, uint32_t *out_ids,
+                                                    float *out_scores, uint32_t *out_counts) {
+    if (!ss || !q_dims || !q_vals || !q_offsets || !out_ids || !out_scores || !out_counts || B == 0 || top_k == 0) return cos_fail(COS_ERR_INVALID, "bad argument");
+    if (ss->sh.size() != ss->world) return cos_fail(COS_ERR_UNIMPLEMENTED, "cos_shardset_sparse_search_batch needs every shard in this process");
+    std::lock_guard<std::mutex> g(ss->mu);
+    if (ss->sp.empty()) return cos_fail(COS_ERR_NOT_READY, "no sparse shards attached (cos_shardset_attach_sparse)");
+    SparseLocks locks(ss->sp);
+    if (int32_t rc = check_sparse_ids(ss->sp, ss->sp_base, ss->first_rank)) return rc;
+    if (int32_t rc = check_sparse_limits(ss, q_offsets, B, top_k, reranking_factor)) return rc;
+    LocalShard &root = ss->sh[0];
+    const size_t nk = (size_t)B * top_k, ret_words = 2 * nk + B;
+    HIP_TRY(hipSetDevice(root.device));
+    HIP_TRY(ss->d_ret.grow(ret_words));
+    HIP_TRY(ss->h_ret.grow(ret_words));
+    DrainAll drain_all{ss};
+    int32_t rc = sparse_lists(ss, q_dims, q_vals, q_offsets, B, top_k, early_terminate_threshold, reranking_factor, ss->d_ret, reinterpret_cast<float *>(ss->d_ret + nk),
+                              ss->d_ret + 2 * nk);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(ss->h_ret, ss->d_ret, ret_words * 4, hipMemcpyDeviceToHost, root.stream));
+    HIP_TRY(hipStreamSynchronize(root.stream));
+    copy_lists_out(ss->h_ret, B, top_k, out_ids, out_scores, out_counts);
+    return COS_OK;
+}
+
+extern "C" int32_t cos_shardset_hybrid_search_mixed(cos_shardset *ss, const cos_hybrid_request *rq, uint32_t *out_ids, float *out_scores, uint32_t *out_counts) {
+    namespace hp = hybrid_plan;
+    if (!ss || !rq || !out_ids || !out_scores || !out_counts) return cos_fail(COS_ERR_INVALID, "bad argument");
+    if (rq->struct_size < sizeof(cos_hybrid_request)) return cos_fail(COS_ERR_INVALID, "cos_hybrid_request.struct_size %u, expected %zu", rq->struct_size, sizeof(cos_hybrid_request));
+    const u32 B = rq->B, top_k = rq->top_k, rf = rq->sparse_reranking_factor;
+    int32_t rc = hp::check_request(rq->struct_size, (u32)sizeof(cos_hybrid_request), B, top_k);
+    if (rc == COS_ERR_UNIMPLEMENTED) return cos_fail(rc, "top_k above %u: every half is asked for 3 * top_k, BM25 keeps %u buckets and the fusion holds two such lists", hp::MAX_TOP_K, hp::MAX_LIST);
+    if (rc || !rq->arm) return cos_fail(COS_ERR_INVALID, "bad argument (B %u, top_k %u)", B, top_k);
+    if (ss->sh.size() != ss->world) return cos_fail(COS_ERR_UNIMPLEMENTED, "cos_shardset_hybrid_search_mixed needs every shard in this process");
+    const u32 k3 = hp::LIST_FACTOR * top_k, S = ss->world;
+    std::lock_guard<std::mutex> g(ss->mu);
+    // ---- the request's query_mapping and everything that refuses it: nothing is enqueued before the last check ----
+    LocalShard &root = ss->sh[0];
+    HIP_TRY(hipSetDevice(root.device));
+    HIP_TRY(ss->h_slots.grow(B)); // (no stream of the set is busy: every call drains them)
+    hp::Split n;
+    u32 bad = 0;
+    if (hp::split(rq->arm, B, ss->h_slots, n, &bad)) return cos_fail(COS_ERR_INVALID, "arm %u of query %u", (u32)rq->arm[bad], bad);
+    if ((n.n_dense && !rq->dense_queries) || (n.n_sparse && (!rq->sparse_dims || !rq->sparse_vals || !rq->sparse_offsets)) || (n.n_bm25 && (!rq->bm25_terms || !rq->bm25_offsets)))
+        return cos_fail(COS_ERR_INVALID, "the queries of a half that has some are NULL");
+    if (n.n_bm25 && !hp::offsets_ascend(rq->bm25_offsets, n.n_bm25)) return cos_fail(COS_ERR_INVALID, "BM25 query offsets decrease");
+    if (n.n_dense)
+        if (int32_t wrc = check_merge_width(S, k3)) return wrc;
+    if (n.n_sparse && ss->sp.empty()) return cos_fail(COS_ERR_NOT_READY, "no sparse shards attached (cos_shardset_attach_sparse)");
+    if (n.n_bm25 && ss->bm.empty()) return cos_fail(COS_ERR_NOT_READY, "no BM25 shards attached (cos_shardset_attach_bm25)");
+    // the set's lock -> every sparse handle's -> every BM25 handle's; a half without queries takes none
+    SparseLocks sparse_locks(n.n_sparse ? ss->sp : std::vector<cos_sparse *>());
+    if (n.n_sparse) {
+        if ((rc = check_sparse_ids(ss->sp, ss->sp_base, ss->first_rank))) return rc;
+        if ((rc = check_sparse_limits(ss, rq->sparse_offsets, n.n_sparse, k3, rf))) return rc;
+    }
+    std::vector<std::unique_lock<std::mutex>> text_locks;
+    if (n.n_bm25) {
+        for (cos_bm25 *b : ss->bm) text_locks.emplace_back(cosdev::bm25_mutex(b));
+        if ((rc = check_text_ids(ss->bm, ss->bm_base, ss->first_rank))) return rc;
+    }
+    // ---- buffers on shard 0's device (grow-only) ----
+    const size_t words = (size_t)n.n_dense * (2 * (size_t)k3 + 1), nk = (size_t)B * top_k, ret_words = 2 * nk + B;
+    HIP_TRY(ss->d_slots.grow(B));
+    HIP_TRY(ss->d_ret.grow(ret_words));
+    HIP_TRY(ss->h_ret.grow(ret_words));
+    if (n.n_sparse) {
+        HIP_TRY(ss->d_sp_ids.grow((size_t)n.n_sparse * k3));
+        HIP_TRY(ss->d_sp_scores.grow((size_t)n.n_sparse * k3));
+        HIP_TRY(ss->d_sp_counts.grow((size_t)n.n_sparse));
+    }
+    DrainAll drain_all{ss};
+    // 1. the dense sub-batch FIRST on every device (beside a BM25 half: on the stream the attached handle keeps for the walk, as in
+    //    cos_shardset_hybrid_search_batch), 2. the sparse records, 3. the BM25 buckets, each with its exchange and fold
+    if (n.n_dense && (rc = enqueue_walks(ss, rq->dense_queries, n.n_dense, k3, words, n.n_bm25 ? &drain_all : nullptr))) return rc;
+    if (n.n_sparse && (rc = sparse_lists(ss, rq->sparse_dims, rq->sparse_vals, rq->sparse_offsets, n.n_sparse, k3, rq->sparse_early_terminate_threshold, rf, ss->d_sp_ids,
+                                         ss->d_sp_scores, ss->d_sp_counts)))
+        return rc;
+    if (n.n_bm25 && (rc = text_lists(ss, drain_all, rq->bm25_terms, rq->bm25_offsets, n.n_bm25, k3))) return rc;
+    if (n.n_dense && (rc = exchange_merge(ss, n.n_dense, k3, words))) return rc;
+    // 4. the three list sets are on shard 0's device: the fusion there, ONE copy back
+    HIP_TRY(hipSetDevice(root.device));
+    HIP_TRY(hipMemcpyAsync(ss->d_slots, ss->h_slots, (size_t)B * sizeof(hp::Slot), hipMemcpyHostToDevice, root.stream));
+    u32 *d_fid = ss->d_ret, *d_fcnt = ss->d_ret + 2 * nk;
+    float *d_fsc = reinterpret_cast<float *>(ss->d_ret + nk);
+    rc = cosdev::rrf_mixed_device(n.n_dense ? ss->d_out_ids.p : nullptr, n.n_dense ? ss->d_out_counts.p : nullptr, n.n_sparse ? ss->d_sp_ids.p : nullptr,
+                                  n.n_sparse ? ss->d_sp_counts.p : nullptr, n.n_bm25 ? ss->d_text_ids.p : nullptr, n.n_bm25 ? ss->d_text_counts.p : nullptr, ss->d_slots, k3, B,
+                                  rq->fusion_constant_k, top_k, d_fid, d_fsc, d_fcnt, root.stream);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(ss->h_ret, ss->d_ret, ret_words * 4, hipMemcpyDeviceToHost, root.stream));
+    if (n.n_dense) {
+        if ((rc = check_walk_statuses(ss, n.n_dense))) return rc; // (synchronises every shard's stream, shard 0's last)
+    } else {
+        HIP_TRY(hipStreamSynchronize(root.stream));
+    }
+    copy_lists_out(ss->h_ret, B, top_k, out_ids, out_scores, out_counts);
     return COS_OK;
 }

@@ -179,6 +179,19 @@ def hybrid_search_mixed(ctx: "HybridContext", index, sparse, bm25, arms, dense_q
     bm25_queries = (q_terms, q_offsets) hold the queries of the arms that have such a half, in query order.  A half without queries
     takes None for its queries and may take None for its index.  Every half searches top_k * 3 on its own stream, RRF fuses each
     query's two lists on the device.  -> ids [B][k], scores [B][k], counts [B]; entries past counts[q] keep 0xFFFFFFFF / 0."""
+    dense = (lambda x: index._queries(x)) if index is not None else (lambda x: _c(np.atleast_2d(x), np.float32))
+    rq, keep, B, ids, sc, cnt = mixed_request(arms, dense, dense_queries, sparse_queries, bm25_queries, top_k, fusion_constant_k,
+                                              early_terminate_threshold, reranking_factor)
+    check(_lib.lib().cos_hybrid_search_mixed(ctx._h, index._h if index is not None else None, sparse._h if sparse is not None else None,
+                                             bm25._h if bm25 is not None else None, C.byref(rq), _p(ids), _p(sc), _p(cnt)))
+    del keep
+    return ids, sc, cnt[:B]
+
+
+def mixed_request(arms, dense, dense_queries, sparse_queries, bm25_queries, top_k: int, fusion_constant_k: float,
+                  early_terminate_threshold: float, reranking_factor: int):
+    """the cos_hybrid_request of a mixed hybrid batch and its output arrays (hybrid_search_mixed, ShardSet.hybrid_search_mixed):
+    `dense` shapes the dense queries.  -> (request, arrays it points into, B, ids, scores, counts)"""
     a = _c(arms, np.uint8).ravel()
     B = a.size
     rq = _lib.CosHybridRequest()
@@ -194,7 +207,7 @@ def hybrid_search_mixed(ctx: "HybridContext", index, sparse, bm25, arms, dense_q
         return x.ctypes.data
 
     if dense_queries is not None:
-        q = index._queries(dense_queries) if index is not None else _c(np.atleast_2d(dense_queries), np.float32)
+        q = dense(dense_queries)
         n_dense = int(np.count_nonzero(a != ARM_SPARSE_BM25))
         if known and q.shape[0] != n_dense:
             raise ValueError(f"arms name {n_dense} queries with a dense half, dense_queries holds {q.shape[0]}")
@@ -218,9 +231,7 @@ def hybrid_search_mixed(ctx: "HybridContext", index, sparse, bm25, arms, dense_q
     ids = np.full((B, max(top_k, 1)), 0xFFFFFFFF, np.uint32)
     sc = np.zeros((B, max(top_k, 1)), np.float32)
     cnt = np.zeros(max(B, 1), np.uint32)
-    check(_lib.lib().cos_hybrid_search_mixed(ctx._h, index._h if index is not None else None, sparse._h if sparse is not None else None,
-                                             bm25._h if bm25 is not None else None, C.byref(rq), _p(ids), _p(sc), _p(cnt)))
-    return ids, sc, cnt[:B]
+    return rq, keep, B, ids, sc, cnt
 
 
 class InvertedIndex:

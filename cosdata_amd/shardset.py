@@ -29,12 +29,14 @@ class ShardSet:
         check(_lib.lib().cos_shardset_create(arr, len(self.shards), 0, len(self.shards), None, C.byref(self._h)))
         self.dim = self.shards[0].dim
         self.bm25_shards = []                           # the attached BM25 handles (attach_bm25), kept alive while attached
+        self.sparse_shards = []                         # ... and the learned-sparse ones (attach_sparse)
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             _lib.lib().cos_shardset_destroy(self._h)
             self._h = C.c_void_p()
         self.bm25_shards = []
+        self.sparse_shards = []
 
     def __del__(self):
         try:
@@ -181,6 +183,60 @@ class ShardSet:
         p = lambda a: a.ctypes.data_as(C.c_void_p)
         check(_lib.lib().cos_shardset_hybrid_search_batch(self._h, p(q), p(qt), p(qo), B, top_k, fusion_constant_k, p(ids), p(scores), p(counts)))
         return ids, scores, counts
+
+    # ---- the learned-sparse half of the collection, and the mixed hybrid call ---------------------------------------------------
+    def attach_sparse(self, indexes, vec_bases=None):
+        """indexes[s] (InvertedIndex) holds the vectors of shard s under LOCAL ids; a vector's global id is vec_bases[s] + local id
+        (None: the dense shards' id_base).  Every handle has the same quantization_bits and values_upper_bound.  The handles stay the
+        caller's — inserts and deletes go to the owning shard's handle with local ids — and must outlive the attachment; attaching again
+        replaces them, attach_sparse(None) detaches."""
+        if indexes is None:
+            check(_lib.lib().cos_shardset_attach_sparse(self._h, None, 0, None))
+            self.sparse_shards = []
+            return self
+        indexes = list(indexes)
+        arr = (C.c_void_p * max(len(indexes), 1))(*[b._h for b in indexes])
+        bases = None if vec_bases is None else np.ascontiguousarray(vec_bases, dtype=np.uint32)
+        if bases is not None and bases.shape != (len(indexes),):
+            raise CosdataError(_lib.ERR_INVALID, f"vec_bases must hold {len(indexes)} bases, got shape {tuple(bases.shape)}")
+        check(_lib.lib().cos_shardset_attach_sparse(self._h, arr, len(indexes), None if bases is None else bases.ctypes.data_as(C.c_void_p)))
+        self.sparse_shards = indexes                    # (kept alive while attached)
+        return self
+
+    def sparse_search(self, q_dims, q_vals, q_offsets, top_k: int, early_terminate_threshold: float = 0.0, reranking_factor: int = 0):
+        """InvertedIndex.search_batch over the attached shards: global ids [B][k], score bits and counts [B] of ONE index holding the
+        whole collection (every shard's best top_k * max(reranking_factor, 1) candidates are cut to the collection's, and only those are
+        re-ranked by raw value); entries past counts[q] keep 0xFFFFFFFF / 0"""
+        qd = np.ascontiguousarray(q_dims, dtype=np.uint32).ravel()
+        qv = np.ascontiguousarray(q_vals, dtype=np.float32).ravel()
+        qo = np.ascontiguousarray(q_offsets, dtype=np.uint32).ravel()
+        if qo.size < 1 or qd.size != qv.size or int(qo.max(initial=0)) > qd.size:
+            raise CosdataError(_lib.ERR_INVALID, "q_offsets must have B + 1 entries inside q_dims / q_vals")
+        if qd.size == 0:
+            qd, qv = np.zeros(1, np.uint32), np.zeros(1, np.float32)   # (non-null pointers for a batch of empty queries)
+        B = qo.size - 1
+        ids = np.full((B, max(top_k, 1)), 0xFFFFFFFF, np.uint32)
+        scores = np.zeros((B, max(top_k, 1)), np.float32)
+        counts = np.zeros(max(B, 1), np.uint32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        check(_lib.lib().cos_shardset_sparse_search_batch(self._h, p(qd), p(qv), p(qo), B, top_k, early_terminate_threshold, reranking_factor,
+                                                          p(ids), p(scores), p(counts)))
+        return ids, scores, counts[:B]
+
+    def hybrid_search_mixed(self, arms, dense_queries, sparse_queries, bm25_queries, top_k: int, fusion_constant_k: float = 60.0,
+                            early_terminate_threshold: float = 0.0, reranking_factor: int = 0):
+        """hybrid.hybrid_search_mixed on the set (cos_shardset_hybrid_search_mixed): the same arguments without the context and the three
+        indexes — the dense shards, attach_sparse and attach_bm25 stand for them; a half without queries needs nothing attached"""
+        from .hybrid import mixed_request
+        dense = lambda x: np.ascontiguousarray(np.atleast_2d(x), dtype=np.float32)
+        rq, keep, B, ids, scores, counts = mixed_request(arms, dense, dense_queries, sparse_queries, bm25_queries, top_k, fusion_constant_k,
+                                                         early_terminate_threshold, reranking_factor)
+        if rq.dense_queries and keep[1].shape[1] != self.dim:
+            raise CosdataError(_lib.ERR_INVALID, f"dense queries must be [n][{self.dim}] f32, got shape {tuple(keep[1].shape)}")
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        check(_lib.lib().cos_shardset_hybrid_search_mixed(self._h, C.byref(rq), p(ids), p(scores), p(counts)))
+        del keep
+        return ids, scores, counts[:B]
 
 
 class ProcessShardSet:

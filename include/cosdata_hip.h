@@ -885,6 +885,39 @@ int32_t cos_shardset_hybrid_search_batch(cos_shardset *ss, const float *queries,
                                          uint32_t B, uint32_t top_k, float fusion_constant_k,
                                          uint32_t *out_ids, float *out_scores, uint32_t *out_counts);
 
+/* The learned-sparse half of the collection on a shard set.  cos_sparse handle s holds the vectors of shard s under
+ * LOCAL ids 0 .. n_s - 1; the global id of a vector is vec_bases[s] + local id (vec_bases == NULL: the dense shards' id_base).  The rules
+ * are those of cos_shardset_attach_bm25: the handles stay owned by the caller, who inserts into and deletes from the owning shard's
+ * handle with local ids; attaching again replaces them; shards == NULL detaches; n_shards equals the set's shard count, handle s lives on
+ * dense shard s's device, no handle twice, the bases strictly increase, vec_bases[s] + n_s stays <= vec_bases[s + 1] and below 2^32 - 1,
+ * else COS_ERR_INVALID (checked again by every search: cos_sparse_insert moves n).  One rule more: quantization_bits and
+ * values_upper_bound (its f32 bits) are the same on every handle, else COS_ERR_INVALID — a vector then has the quantized similarity in
+ * its shard that it has in the whole collection.  A set that does not hold every shard in this process: COS_ERR_UNIMPLEMENTED. */
+int32_t cos_shardset_attach_sparse(cos_shardset *ss, cos_sparse *const *shards, uint32_t n_shards, const uint32_t *vec_bases);
+/* cos_sparse_search_batch over the attached shards: ids (global), score bits and counts of ONE cos_sparse handle created from the whole
+ * collection.  With C = top_k * max(reranking_factor, 1): every shard runs its scan and leaves its best C candidates per query —
+ * (quantized similarity, global id) keys and, for a rerank, each candidate's raw-value score — as one record on its device; ONE exchange
+ * brings the S records to shard 0's device; one kernel cuts the S x C keys to the collection's best C by (similarity, larger id first),
+ * re-ranks exactly those by raw score and cuts to top_k.  (A per-shard rerank followed by a merge would re-rank vectors the whole
+ * collection never re-scores.)  Output slots past a query's count are not written.
+ * Refused before anything is enqueued, the set and every handle staying usable: nothing attached -> COS_ERR_NOT_READY; a rerank while
+ * a shard holds no raw vectors -> COS_ERR_NOT_READY; C above any shard's cos_sparse_set_max_candidates -> COS_ERR_UNIMPLEMENTED;
+ * S x (64, 128, .. 1024: C rounded up) above 8192 -> COS_ERR_UNIMPLEMENTED; B at or above cos_sparse_search_batch's bound, decreasing
+ * offsets, a broken id rule -> COS_ERR_INVALID.  Locks: the set's, then every sparse handle's in shard order, held to the call's
+ * synchronisation — an update of a shard handle happens before or after a search, never inside. */
+int32_t cos_shardset_sparse_search_batch(cos_shardset *ss, const uint32_t *q_dims, const float *q_vals, const uint32_t *q_offsets,
+                                         uint32_t B, uint32_t top_k, float early_terminate_threshold, uint32_t reranking_factor,
+                                         uint32_t *out_ids, float *out_scores, uint32_t *out_counts);
+/* cos_hybrid_search_mixed on the set: the request is split as there; the dense sub-batch is cos_shardset_search_batch for 3 * top_k
+ * (enqueued first on every device), the sparse sub-batch the call above for 3 * top_k with C = 3 * top_k * max(reranking_factor, 1), the
+ * BM25 sub-batch cos_shardset_bm25_search_batch for 3 * top_k; the three list sets stay on shard 0's device, the fusion runs there, one
+ * copy back.  Refusals: those of cos_hybrid_search_mixed, the widths of the three calls (S * 3 * top_k <= 8192 for a dense sub-batch),
+ * and COS_ERR_NOT_READY for a half that has queries and nothing attached; a half without queries needs nothing attached.  Locks: the
+ * set's, every sparse handle's in shard order, every BM25 handle's in shard order.  A failing dense query fails the call with the first
+ * failing shard's status; the next call answers. */
+int32_t cos_shardset_hybrid_search_mixed(cos_shardset *ss, const cos_hybrid_request *rq, uint32_t *out_ids, float *out_scores,
+                                         uint32_t *out_counts);
+
 /* ---- tuning knobs (experiments; NOT a reference interface) ------------------------------------------------------------------
  * Launch-policy knobs of the kernels — which of two implementations of one operator runs, launch sizes at which a policy
  * switches, prefetch depths.  None changes a result; the parity tests use them to compare implementations, the profiling
