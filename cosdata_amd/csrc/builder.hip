@@ -116,7 +116,7 @@ struct GraphGuard {
         (void)hipStreamSynchronize(ix->own_stream);
         for (auto &l : ix->lv) l.release();
         ix->link.release();
-        ix->invalidate_adj_side();
+        cos_graph_changed(ix, GraphChange::ADJACENCY);
         ix->have_root = false;
     }
 };
@@ -429,9 +429,7 @@ extern "C" int32_t cos_index_build(cos_index *ix, uint32_t batch_size) {
     hipStream_t st = ix->own_stream;
     GraphGuard guard{ix};
 
-    ix->order_rank_valid = false; // the order key's table follows the graph (engine.hip, ensure_order_rank)
-    ix->level_table_valid = false; // and so does the level table's operand (ensure_level_table)
-    ix->invalidate_adj_side();     // the builder's walks gather mags[]; the adjacency-side norms are written when the graph is committed
+    cos_graph_changed(ix, GraphChange::LEVELS); // (the builder's walks gather mags[]; the adjacency-side norms are written when the graph is committed)
     ix->link.release();
     // ---- root + level draws (same RNG stream as the oracle builders) ----------------------------
     uint64_t rng = ix->p.seed ? ix->p.seed : 0x1234567ull;
@@ -481,7 +479,7 @@ extern "C" int32_t cos_index_build(cos_index *ix, uint32_t batch_size) {
     ix->link.rng = rng;
     ix->link.n_built = n;
     ix->link.valid = true;
-    if (int32_t rc2 = cos_prepare_walk_plans(ix)) return rc2; // order ranks + level-table operand of the new graph, outside any search
+    if (int32_t rc2 = cos_prepare_walk_plans(ix)) return rc2; // the walk's operands of the new graph (walk_operands.hip), outside any search
     return COS_OK; // the id-format host copy is made on demand (cos_index_download_graph_level)
 }
 
@@ -579,9 +577,7 @@ extern "C" int32_t cos_index_append(cos_index *ix, const float *raw, uint32_t m,
     hipStream_t st = ix->own_stream;
     HIP_TRY(hipDeviceSynchronize()); // exclusive: whatever read the old arrays is done
     GraphGuard guard{ix};
-    ix->order_rank_valid = false;
-    ix->level_table_valid = false;
-    ix->invalidate_adj_side();
+    cos_graph_changed(ix, GraphChange::LEVELS);
     ix->link.valid = false; // until the append is complete
     cos_flat_ws_release(ix); // cached sums of the stored codes, scan buffers sized for the old corpus
 
@@ -810,9 +806,7 @@ extern "C" int32_t cos_index_delete(cos_index *ix, const uint32_t *ids, uint32_t
     VisTab vtab;
     std::vector<u32> h_ids((size_t)L1 * KEEP), h_nodes((size_t)L1 * KEEP), h_counts(L1), h_dn(L1), h_ust(L1);
     std::vector<std::vector<u32>> node_vec(L1); // slow path only: node -> vector row, fetched once per level
-    // (the locality order stays a permutation of the level's nodes and the level table's operand holds code rows: both still valid —
-    // tests/test_gpu_mutation_coherence.py searches a warm handle with both after every delete, against a handle that never had them)
-    ix->invalidate_adj_side();
+    cos_graph_changed(ix, GraphChange::ADJACENCY);
     for (auto &l : ix->lv) { l.host_valid = false; l.nbr_ids.clear(); }
 
     for (u32 t = 0; t < m; t++) {

@@ -54,12 +54,6 @@ int32_t cos_set_device(const cos_index *ix) {
     return COS_OK;
 }
 
-static bool graph_ready(const cos_index *ix) {
-    if (!ix->have_vectors || !ix->have_root) return false;
-    for (auto &l : ix->lv) if (l.n == 0) return false;
-    return true;
-}
-
 IndexDev cos_make_index_dev(const cos_index *ix) {
     IndexDev d;
     memset(&d, 0, sizeof(d));
@@ -92,9 +86,9 @@ IndexDev cos_make_index_dev(const cos_index *ix) {
         d.lv[l].n = h.n;
         d.lv[l].M = h.M;
         d.lv[l].root_idx = h.n ? h.n - 1 : 0;
-        d.lv[l].adj_mag = (ix->adj_mag_valid && cosdev::tune_or(cosdev::TUNE_WALK_ADJ_MAG, 1) != 0) ? h.d_adj_mag : nullptr;
+        d.lv[l].adj_mag = (ix->ops.have_adj_mag() && cosdev::tune_or(cosdev::TUNE_WALK_ADJ_MAG, 1) != 0) ? h.d_adj_mag : nullptr;
         d.lv[l].mag_stride = std::min(h.M, ix->p.shortlist_size);
-        d.lv[l].adj_up = (d.lv[l].adj_mag != nullptr && l != 0 && ix->adj_up_level == l) ? h.d_adj_up : nullptr;
+        d.lv[l].adj_up = (d.lv[l].adj_mag != nullptr && l != 0 && ix->ops.adj_up_level() == l) ? h.d_adj_up : nullptr;
     }
     return d;
 }
@@ -238,9 +232,7 @@ extern "C" int32_t cos_index_upload_vectors(cos_index *ix, const float *raw, uin
     cos_flat_ws_release(ix); // cached sums of the stored codes, scan buffers sized for the old corpus
     ix->have_root = false;
     for (auto &l : ix->lv) l.release(); // a graph refers to vector rows: new vectors invalidate it
-    ix->order_rank_valid = false;
-    ix->level_table_valid = false;
-    ix->invalidate_adj_side();
+    cos_graph_changed(ix, GraphChange::LEVELS);
     ix->link.release();
     reset_meta(ix);                       // ... and so do the pseudo-root component, its node table and the id stride
     const u64 dim = ix->p.dim;
@@ -291,11 +283,8 @@ extern "C" int32_t cos_index_set_root(cos_index *ix, const float *root_raw) {
                                  ix->d_codes + (size_t)ix->n * ix->row_stride, ix->row_stride, ix->d_mags + ix->n, d_dummy, ix->own_stream));
     HIP_TRY(hipStreamSynchronize(ix->own_stream));
     ix->have_root = true;
-    // the root is a node of every level: the level-table operand holds a gathered COPY of its code row, norm and code sum, which a
-    // second set_root on a live graph would leave stale (the row levels would use the new row) — the next search regathers
-    ix->level_table_valid = false;
-    ix->invalidate_adj_side(); // ... and the adjacency-side norms hold the old root's |v| wherever the root is a neighbour
-    if (ix->link.valid && graph_ready(ix)) ix->link.release(); // the slot similarities of edges to the root were computed with the old root
+    cos_graph_changed(ix, GraphChange::ROOT);
+    if (ix->link.valid && cos_graph_ready(ix)) ix->link.release(); // the slot similarities of edges to the root were computed with the old root
     return COS_OK;
 }
 
@@ -334,10 +323,8 @@ static int32_t push_level_to_device(cos_index *ix, u32 level) {
     }
     L.n = n;
     L.host_valid = true;
-    ix->order_rank_valid = false; // the order key's table follows the graph (ensure_order_rank)
-    ix->level_table_valid = false;
-    ix->invalidate_adj_side();
-    ix->link.release();           // an uploaded level carries no slot similarities / lowest caches to continue from
+    cos_graph_changed(ix, GraphChange::LEVELS);
+    ix->link.release(); // an uploaded level carries no slot similarities / lowest caches to continue from
     return COS_OK;
 }
 
@@ -396,9 +383,7 @@ static int32_t push_level0_to_device(cos_index *ix, const u32 *nbr) {
     L.nbr_ids.shrink_to_fit();
     L.n = n;
     L.host_valid = false;
-    ix->order_rank_valid = false;
-    ix->level_table_valid = false;
-    ix->invalidate_adj_side();
+    cos_graph_changed(ix, GraphChange::LEVELS);
     ix->link.release();
     return COS_OK;
 }
@@ -444,7 +429,7 @@ extern "C" int32_t cos_index_upload_graph_level(cos_index *ix, uint32_t level, u
     if (rc) { L.release(); return rc; }
     rc = resolve_children(ix, level);
     if (rc == COS_OK) rc = resolve_children(ix, level + 1);
-    if (rc == COS_OK && graph_ready(ix)) rc = cos_prepare_walk_plans(ix); // the last level of a graph: its order / level tables now, not under a search
+    if (rc == COS_OK && cos_graph_ready(ix)) rc = cos_prepare_walk_plans(ix); // the last level of a graph: its order / level tables now, not under a search
     return rc;
 }
 
@@ -552,8 +537,7 @@ int32_t cos_set_root_code(cos_index *ix, const uint8_t *ref_code, float mag) {
     HIP_TRY(hipMemcpy(ix->d_mags + ix->n, &mag, 4, hipMemcpyHostToDevice));
     ix->root_raw.assign(ix->p.dim, 0.0f);
     ix->have_root = true;
-    ix->level_table_valid = false;
-    ix->invalidate_adj_side();
+    cos_graph_changed(ix, GraphChange::ROOT);
     return COS_OK;
 }
 
@@ -582,13 +566,11 @@ extern "C" int32_t cos_index_download_root(const cos_index *ix, float *root_raw)
     return COS_OK;
 }
 
-static int32_t ensure_level_table(cos_index *ix);
-static u32 walk_table_min_B(const cos_index *ix);
 extern "C" int32_t cos_index_set_ef_search(cos_index *ix, uint32_t ef) {
     if (!ix) return cos_fail(COS_ERR_INVALID, "null index");
     if (ef > cosdev::WALK_GENERAL_MAX_EF) return cos_fail(COS_ERR_UNIMPLEMENTED, "ef > %u not supported on the device", cosdev::WALK_GENERAL_MAX_EF);
     std::lock_guard<std::mutex> g(ix->mu); // searches snapshot ef / visited mode under the same lock (get_workspace); the graph state is read under it too
-    const bool live = graph_ready(ix);
+    const bool live = cos_graph_ready(ix);
     if (live)
         if (int32_t rc = cos_set_device(ix)) return rc; // (nothing changed yet)
     ix->p.ef_search = ef;
@@ -596,9 +578,9 @@ extern "C" int32_t cos_index_set_ef_search(cos_index *ix, uint32_t ef) {
     // knob, not inside the next search (where the gather and its device synchronisation ran under ix->mu in front of every
     // concurrent searcher); operands are cached per (graph, rule), so going back and forth costs nothing the second time.
     // Best effort: the table is an accelerator, not a result — a gather that fails (out of memory is already absorbed inside
-    // ensure_level_table) leaves the new ef in force, the next search walks without a table or retries the gather, and the
+    // cos_ensure_level_table) leaves the new ef in force, the next search walks without a table or retries the gather, and the
     // setter reports success: an error here would say "ef unchanged" while it has changed.
-    if (live && walk_table_min_B(ix)) (void)ensure_level_table(ix);
+    if (live && cos_walk_table_min_B(ix)) (void)cos_ensure_level_table(ix);
     return COS_OK;
 }
 extern "C" int32_t cos_index_set_visited_mode(cos_index *ix, uint32_t mode) {
@@ -664,469 +646,9 @@ int32_t vis_tab_prepare(VisTab &vt, const cos_index *ix, u32 B, u32 ef, hipStrea
     return COS_OK;
 }
 
-// the workspace registered under `key` (a caller's stream, or a HostPipe slot), grown to B queries; `st` is the stream the
-// workspace's previous launches ran on (drained before a buffer is replaced)
-// The tables behind the order keys of big launches (WalkArgs::order_rank): every node of a key level -> its position in a
-// depth-first order of that level's graph.  Consecutive positions are graph neighbours or a short backtrack apart, so queries
-// whose best key-level nodes have close positions walk the same region of the levels below — a one-dimensional locality order
-// that needs nothing but the graph (the vectors' geometry is in its edges).
-// Key levels (the walk is cut AFTER each of them): by default ONE, the lowest level whose code rows take at most 64 MB — a
-// quarter of the 256 MB memory-side cache, so the levels walked in arrival order stay cache-resident whatever the order, and the
-// key is as fine as that allows (c2: level 2, 62 500 nodes x 768 B = 48 MB, levels 1 and 0 walked in order; a 12.5M x 1024
-// shard: level 4, 48 829 nodes).  Every further cut costs the tail of one more launch (~0.3 ms per 32768 queries) and measured
-// slower: profiles/archive/r03_locality_probe_split_levels.jsonl (cuts after 1 | 2 | 3 | 4 | 3,1 | 4,1 | 5,1 | 4,2,1 | 5,3,1).
-// COS_WALK_SPLIT=a,b,.. overrides (descending levels; "0" = no split).
-// Built on the host from the adjacency, once per graph: milliseconds for levels this small (<= 2^20 nodes).  Caller holds ix->mu.
-static int32_t ensure_order_rank(cos_index *ix) {
-    if (ix->order_rank_valid) return COS_OK;
-    for (u32 l = 0; l < cosdev::MAX_LEVELS; l++) {
-        ix->d_order_rank[l].reset();
-        ix->order_rank_n[l] = 0;
-    }
-    ix->order_levels.clear();
-    const u32 Ltop = ix->p.num_layers;
-    auto usable = [&](u32 l) { return l >= 1 && l <= Ltop && ix->lv[l].n > 1 && ix->lv[l].n <= (1u << 20) && ix->lv[l].d_adj_node; };
-    std::vector<u32> want;
-    if (const long long mask = cosdev::tune(cosdev::TUNE_WALK_SPLIT_LEVELS); mask != cosdev::TUNE_UNSET) { // experiments: bit l = cut after level l
-        for (u32 l = Ltop; l >= 1; l--)
-            if ((mask >> l) & 1) want.push_back(l);
-    } else {
-        for (u32 l = 1; l <= Ltop; l++)
-            if (usable(l) && (size_t)ix->lv[l].n * ix->row_stride <= ((size_t)64 << 20)) { want.push_back(l); break; }
-    }
-    u32 prev = Ltop + 1;
-    for (u32 l : want) { // descending, distinct, usable; a level that is not is skipped, not an error
-        if (!usable(l) || l >= prev) continue;
-        ix->order_levels.push_back(l);
-        prev = l;
-    }
-    if (!ix->order_levels.empty()) HIP_TRY(hipDeviceSynchronize()); // a build or an upload on another stream may still be writing the adjacency
-    for (u32 kl : ix->order_levels) {
-        const LevelHost &H = ix->lv[kl];
-        const u32 n = H.n, M = H.M;
-        std::vector<u32> adj((size_t)n * M), rank(n, 0u), stack;
-        HIP_TRY(hipMemcpy(adj.data(), H.d_adj_node, adj.size() * 4, hipMemcpyDeviceToHost));
-        std::vector<uint8_t> seen(n, 0);
-        u32 next = 0;
-        auto dfs_from = [&](u32 start) {
-            stack.push_back(start);
-            while (!stack.empty()) {
-                const u32 v = stack.back();
-                stack.pop_back();
-                if (seen[v]) continue;
-                seen[v] = 1;
-                rank[v] = next++;
-                const u32 *row = &adj[(size_t)v * M];
-                for (u32 j = M; j-- > 0;) { // pushed last = visited first: slot order
-                    const u32 u = row[j];
-                    if (u != cosdev::ROW_EMPTY && u < n && !seen[u]) stack.push_back(u);
-                }
-            }
-        };
-        dfs_from(n - 1); // the root (last node of every level): where every walk of the level starts
-        for (u32 v = 0; v < n; v++) if (!seen[v]) dfs_from(v);
-        HIP_TRY(ix->d_order_rank[kl].alloc(n));
-        HIP_TRY(hipMemcpy(ix->d_order_rank[kl], rank.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-        ix->order_rank_n[kl] = n;
-    }
-    ix->order_rank_valid = true;
-    return COS_OK;
-}
-
-// The level table's per-graph operand (WalkArgs::tab, cosdata_hip.h cos_index_set_walk_table): which levels it covers and the code
-// rows, norms and code sums of their nodes, level by level from the top, gathered on the device.  Caller holds ix->mu.
-static void clear_current_table(cos_index *ix) {
-    ix->d_tcodes = nullptr;
-    ix->d_tmags = nullptr;
-    ix->d_tcsums = nullptr;
-    ix->table_cols = 0;
-    ix->table_level_min = 0;
-    ix->table_stride = 0;
-}
-static u32 walk_table_max_cols(const cos_index *ix) { // COS_WALK_TABLE_AUTO = sized from ef_search and neighbors_count (ensure_level_table)
-    const long long env = cosdev::tune_or(cosdev::TUNE_WALK_TABLE_COLS, -1);
-    return env >= 0 ? (u32)std::min<long long>(env, 1ll << 20) : ix->walk_table_max_cols;
-}
-static u32 walk_table_min_B(const cos_index *ix) {
-    const long long env = cosdev::tune_or(cosdev::TUNE_WALK_TABLE_MIN_B, -1);
-    return env >= 0 ? (u32)std::min<long long>(env, 0xFFFFFFFFll) : ix->walk_table_min_B;
-}
-// Workgroups of the early part of a gated level-table GEMM (walk_plan.h; tuning knob walk_table_early_wgs).  Measured on the 12.5M x 1024
-// shard, 32 768 queries per step: DESIGN.md §8.1, profiles/r07_table_early_wgs_sweep.jsonl.
-static constexpr long long WALK_TABLE_EARLY_WGS_DEFAULT = 0;
-// The row level under the level table reads table columns for the neighbours that have a node one level up (walk_plan.h,
-// WalkPlan::up_table_level; tuning knob walk_up_table).
-static constexpr long long WALK_UP_TABLE_DEFAULT = 1;
-// The throughput kernel's launches read the nested level table, one GEMM column per vector of the lowest table level (table_nested.h,
-// ensure_nested_table; tuning knob walk_table_nested): 1 = on graphs where that saves TABLE_NESTED_MIN_SAVED_COLS columns or more.
-static constexpr long long WALK_TABLE_NESTED_DEFAULT = 1;
 // The last range of an ordered launch walks two sorted neighbours per workgroup (kernels_walk_pair.hip, walk_pair_plan.h; tuning knobs
 // walk_pair, walk_pair_cache).  Defaults: DESIGN.md §0.4.
 static constexpr long long WALK_PAIR_DEFAULT = 1, WALK_PAIR_CACHE_DEFAULT = 512;
-static u32 walk_table_nested_mode() {
-    return (u32)std::min<long long>(std::max<long long>(cosdev::tune_or(cosdev::TUNE_WALK_TABLE_NESTED, WALK_TABLE_NESTED_DEFAULT), 0), 2);
-}
-// the handle as walk_plan (walk_plan.h) sees it: shape, every knob resolved (the tuning registry's overrides included), a launch of B
-// queries at beam width ef that takes part in the walk chain.  Caller holds ix->mu where the handle is shared.
-cosdev::WalkPlanIn cos_walk_plan_in(const cos_index *ix, u32 B, u32 ef) {
-    cosdev::WalkPlanIn in{};
-    in.eng = ix->eng;
-    in.storage = ix->p.storage;
-    in.nchunks = ix->nchunks;
-    in.G = ix->G;
-    in.num_layers = ix->p.num_layers;
-    for (u32 l = 0; l <= ix->p.num_layers; l++) in.M[l] = ix->lv[l].M;
-    in.shortlist = ix->p.shortlist_size;
-    in.visited_mode = ix->p.visited_mode;
-    in.mdim = ix->meta.mdim;
-    in.B = B;
-    in.ef = ef;
-    in.chain = true;
-    // tuning knobs walk_lat / walk_lat4 = <n> override the handle's values (experiments: 0 = off, 4294967295 = always)
-    const long long lat = cosdev::tune_or(cosdev::TUNE_WALK_LAT, -1), lat4 = cosdev::tune_or(cosdev::TUNE_WALK_LAT4, -1);
-    in.lat_max_B = lat >= 0 ? (u32)std::min(lat, 0xFFFFFFFFll) : ix->lat_max_B;
-    in.lat4_max_B = lat4 >= 0 ? (u32)std::min(lat4, 0xFFFFFFFFll) : ix->lat4_max_B;
-    in.small_table_tk = cosdev::tune_or(cosdev::TUNE_WALK_SMALL_TABLE_TK, 1) != 0;
-    in.adj_mag_mode = (u32)cosdev::tune_or(cosdev::TUNE_WALK_ADJ_MAG, 1);
-    in.table_min_B = walk_table_min_B(ix);
-    in.order_min_B = ix->walk_order_min_B;
-    in.chain_min_B = ix->chain_min_B;
-    in.side_min_B = ix->walk_side_min_B;
-    in.table_after_sort = cosdev::tune_or(cosdev::TUNE_WALK_TABLE_AFTER_SORT, 1);
-    in.table_supported = cosdev::level_table_eng_supported(ix->eng, ix->row_stride);
-    in.adj_mag_valid = ix->adj_mag_valid;
-    in.up_table_mode = (u32)std::min<long long>(std::max<long long>(cosdev::tune_or(cosdev::TUNE_WALK_UP_TABLE, WALK_UP_TABLE_DEFAULT), 0), 2);
-    in.table_early_wgs = (u32)std::min<long long>(std::max<long long>(cosdev::tune_or(cosdev::TUNE_WALK_TABLE_EARLY_WGS, WALK_TABLE_EARLY_WGS_DEFAULT), 0), 0xFFFFFFFFll);
-    in.table_queue = cosdev::level_table_gemm_queue(ix->eng, ix->row_stride);
-    in.n_cus = ix->n_cus;
-    in.table_nested_mode = walk_table_nested_mode();
-    return in;
-}
-static int32_t ensure_per_level_table(cos_index *ix) {
-    const u32 max_cols = walk_table_max_cols(ix);
-    // Which levels pay.  A table column costs one GEMM column per launch (~2.6 ps per query and column at K = 1024), a level walked
-    // from rows costs ~0.11 ns per evaluation, and a level's walk evaluates 0.2-0.4 x ef x M rows per query: a level of n nodes pays
-    // while n < ~40 x that.  Measured on both ends — 1M x 768 at ef 64, M 32: level 4 (3 917 nodes) pays, level 3 (15 570) does not;
-    // one 12.5M x 1024 shard at ef 128, M 64: level 5 (12 225) +24 % QPS, level 4 (48 870) another +17 %, both far above a fixed
-    // 8 192 columns (profiles/r04_c4_table_cols_probe.jsonl) — the automatic rule is n_level <= c x ef_search x neighbors_count, level
-    // by level from the top; an explicit max_cols caps the columns of all table levels together instead.  Round 4-5: c = 8 up to ef 64
-    // and 6 above: the wider pools of ef > 64 make a walk spend its time ranking and inserting, so a row it does not fetch saves less
-    // (1M x 768, M 32: at ef 64 level 3 = 7.6 x ef x M pays, 7.53 -> 7.13 ms per 32 768 queries; at ef 256 level 2 = 7.7 x ef x M
-    // costs 5.4 ms of GEMM and saves nothing, level 3 = 1.9 x pays; profiles/r04_table_level_rule_probe.jsonl).
-    const bool automatic = max_cols == COS_WALK_TABLE_AUTO;
-    // Round 6 (profiles/r06_rule_probe_*.jsonl): what decides is how many rows an expansion still evaluates, i.e. how far the level's
-    // filter (64 x M bits) is from saturation after ef pops — ef relative to M, not ef alone.  12.5M x 1024 with M 64: level 4 (48 870
-    // nodes) at ef 80 / 96 / 112 (9.5 / 8.0 / 6.8 x ef x M) +25 % / +25 % / +25 % QPS, 14 evaluations per expansion; 1M x 768 with M 32:
-    // level 2 (62 869 nodes) at ef 128 / 256 (15.3 / 7.7 x) -20 % / -15 %, 3-5 evaluations per expansion.  c = 10 up to ef = 1.5 M, 8 up
-    // to 2 M, 6 above (M 32: the old rule — 8 up to ef 64, 6 above — except c = 10 up to ef 48).
-    const u32 efs = ix->p.ef_search, Mup = ix->p.neighbors_count;
-    const u64 c_rule = (u64)cosdev::tune_or(cosdev::TUNE_WALK_TABLE_RULE_C, 2u * efs <= 3u * Mup ? 10 : (efs <= 2u * Mup ? 8 : 6));
-    const u64 per_level = automatic ? std::min<u64>(c_rule * ix->p.ef_search * ix->p.neighbors_count, 1u << 20) : (u64)(1u << 20);
-    const u64 total_cap = automatic ? (u64)(1u << 20) : (u64)max_cols;
-    const u64 key = automatic ? (0x8000000000000000ull | per_level) : (u64)max_cols;
-    if (ix->level_table_valid && ix->table_built_for_key == key) return COS_OK;
-    if (!ix->level_table_valid) { // a new graph: the old graph's operands go (graph changes are exclusive: no search is in flight)
-        HIP_TRY(hipDeviceSynchronize());
-        ix->table_sets.clear();
-    }
-    // (from here on every path leaves a definite state for this (graph, key): a table, or "none" — which is also what an operand
-    // that could not be allocated leaves, see below)
-    ix->level_table_valid = true;
-    ix->table_built_for_key = key;
-    clear_current_table(ix);
-    for (const auto &t : ix->table_sets)
-        if (t.key == key) { // built before for this graph (ef_search went back and forth)
-            ix->table_level_min = t.level_min;
-            ix->table_cols = t.cols;
-            ix->table_stride = t.stride;
-            memcpy(ix->table_col0, t.col0, sizeof(t.col0));
-            ix->d_tcodes = t.tcodes;
-            ix->d_tmags = t.tmags;
-            ix->d_tcsums = t.tcsums;
-            return COS_OK;
-        }
-    if (!cosdev::level_table_eng_supported(ix->eng, ix->row_stride) || max_cols == 0) return COS_OK; // u8 codes; quaternary codes of 128 ... 1024 dims
-    const u32 Ltop = ix->p.num_layers;
-    u32 cols = 0, lmin = 0;
-    for (u32 l = Ltop; l >= 1; l--) { // level 0 (every vector) never takes part
-        if (!ix->lv[l].d_node_vec || ix->lv[l].n == 0 || ix->lv[l].n > per_level || (u64)cols + ix->lv[l].n > total_cap) break;
-        cols += ix->lv[l].n;
-        lmin = l;
-    }
-    if (lmin == 0) return COS_OK;
-    HIP_TRY(hipDeviceSynchronize()); // a build or an upload on another stream may still be writing the levels
-    cos_index::TableSet t;
-    auto build = [&]() -> hipError_t { // (a failure leaves the handle without a table for this key — same results — and `t` frees what it had allocated)
-        hipError_t e = t.tcodes.alloc((size_t)cols * ix->row_stride);
-        if (e == hipSuccess) e = t.tmags.alloc(cols);
-        if (e == hipSuccess) e = t.tcsums.alloc(cols);
-        u32 c0 = 0;
-        for (u32 l = Ltop; l >= lmin && e == hipSuccess; l--) {
-            ix->table_col0[l] = c0;
-            e = cosdev::launch_level_table_gather(ix->d_codes, ix->d_mags, ix->row_stride, ix->lv[l].d_node_vec, ix->lv[l].n, c0, t.tcodes, t.tmags, nullptr);
-            c0 += ix->lv[l].n;
-        }
-        if (e == hipSuccess) e = cosdev::launch_code_sums(t.tcodes, ix->row_stride, cols, t.tcsums, nullptr);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        return e;
-    };
-    if (const hipError_t e = build(); e != hipSuccess) {
-        (void)hipDeviceSynchronize();
-        if (e == hipErrorOutOfMemory) { // the table is an optimisation: short of HBM the walk reads rows (same results)
-            (void)hipGetLastError();
-            return COS_OK;
-        }
-        ix->level_table_valid = false; // anything else is a real failure: reported, and retried by the next search
-        HIP_TRY(e);
-    }
-    ix->d_tcodes = t.tcodes;
-    ix->d_tmags = t.tmags;
-    ix->d_tcsums = t.tcsums;
-    ix->table_cols = cols;
-    ix->table_level_min = lmin;
-    ix->table_stride = ((u64)cols + 31) / 32 * 32;
-    t.key = key;
-    t.level_min = lmin;
-    t.cols = cols;
-    t.stride = ix->table_stride;
-    memcpy(t.col0, ix->table_col0, sizeof(t.col0));
-    ix->table_sets.push_back(std::move(t));
-    return COS_OK;
-}
-
-// The NESTED operand of the current table levels (table_nested.h): one column per node of the lowest table level, in nested order, kept
-// in table_sets beside the per-level set under a key of its own, and LevelDev::adj_tab of every table level filled for it.  Caller holds
-// ix->mu, right after ensure_per_level_table.  Leaves cos_index::table_nested_idx: the set the throughput kernel's launches use, or -1 —
-// the knob, a storage other than u8, a metadata schema, a graph whose packed words do not fit 32 bits or whose levels are not nested,
-// too few columns saved (knob 1), out of memory: every launch then reads the per-level set exactly as before (same results either way).
-static int32_t ensure_nested_table(cos_index *ix) {
-    const u32 mode = walk_table_nested_mode();
-    ix->table_nested_idx = -1;
-    if (mode == 0 || !ix->level_table_valid || ix->table_level_min == 0 || ix->eng != ENG_U8 || ix->meta.mdim != 0u) return COS_OK;
-    if (ix->G == 0u || ix->nchunks > ix->G) return COS_OK; // rows of more than one chunk pass: walk_kernel's nested rounds do not exist there (walk_plan.h)
-    const u32 lmin = ix->table_level_min, Ltop = ix->p.num_layers;
-    if (mode == 1 && ix->table_cols - ix->lv[lmin].n < cosdev::TABLE_NESTED_MIN_SAVED_COLS) return COS_OK;
-    const u64 nkey = ix->table_built_for_key | cos_index::TABLE_NESTED_KEY;
-    if (ix->table_nested_failed_key == nkey) return COS_OK;
-    auto go_without = [&](hipError_t e) -> int32_t { // like the per-level operand: short of HBM the launch does without, anything else is reported
-        (void)hipDeviceSynchronize();
-        if (e == hipErrorOutOfMemory) {
-            (void)hipGetLastError();
-            return COS_OK;
-        }
-        HIP_TRY(e);
-        return COS_OK;
-    };
-    int idx = -1;
-    for (size_t i = 0; i < ix->table_sets.size(); i++)
-        if (ix->table_sets[i].key == nkey) idx = (int)i;
-    if (idx < 0) {
-        HIP_TRY(hipDeviceSynchronize()); // a build or an upload on another stream may still be writing the levels
-        std::vector<u32> n(Ltop + 1, 0u);
-        std::vector<std::vector<u32>> child(Ltop + 1);
-        for (u32 l = lmin; l <= Ltop; l++) {
-            n[l] = ix->lv[l].n;
-            if (l == lmin) continue;
-            if (!ix->lv[l].d_child) { ix->table_nested_failed_key = nkey; return COS_OK; }
-            child[l].resize(n[l]);
-            HIP_TRY(hipMemcpy(child[l].data(), ix->lv[l].d_child, (size_t)n[l] * 4, hipMemcpyDeviceToHost));
-        }
-        cosdev::NestedTable nt;
-        if (!cosdev::table_nested_columns(lmin, Ltop, n, child, &nt)) { ix->table_nested_failed_key = nkey; return COS_OK; }
-        // the gather's index list: vector row of every column
-        std::vector<u32> rows(nt.cols), node_vec(nt.cols);
-        HIP_TRY(hipMemcpy(node_vec.data(), ix->lv[lmin].d_node_vec, (size_t)nt.cols * 4, hipMemcpyDeviceToHost));
-        for (u32 c = 0; c < nt.cols; c++) rows[c] = node_vec[nt.col_node[c]];
-        cos_index::TableSet t;
-        DevArr<u32> d_rows;
-        auto build = [&]() -> hipError_t {
-            hipError_t e = t.tcodes.alloc((size_t)nt.cols * ix->row_stride);
-            if (e == hipSuccess) e = t.tmags.alloc(nt.cols);
-            if (e == hipSuccess) e = t.tcsums.alloc(nt.cols);
-            if (e == hipSuccess) e = d_rows.alloc(nt.cols);
-            if (e == hipSuccess) e = hipMemcpy(d_rows, rows.data(), (size_t)nt.cols * 4, hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = cosdev::launch_level_table_gather(ix->d_codes, ix->d_mags, ix->row_stride, d_rows, nt.cols, 0u, t.tcodes, t.tmags, nullptr);
-            if (e == hipSuccess) e = cosdev::launch_code_sums(t.tcodes, ix->row_stride, nt.cols, t.tcsums, nullptr);
-            for (u32 l = lmin; l <= Ltop && e == hipSuccess; l++) {
-                e = t.tab_col[l].alloc(n[l]);
-                if (e == hipSuccess) e = hipMemcpy(t.tab_col[l], nt.col[l - lmin].data(), (size_t)n[l] * 4, hipMemcpyHostToDevice);
-                t.node_bits[l] = nt.node_bits[l - lmin];
-            }
-            if (e == hipSuccess) e = hipDeviceSynchronize();
-            return e;
-        };
-        if (const hipError_t e = build(); e != hipSuccess) {
-            ix->table_nested_failed_key = e == hipErrorOutOfMemory ? nkey : 0;
-            return go_without(e);
-        }
-        t.key = nkey;
-        t.level_min = lmin;
-        t.cols = nt.cols;
-        t.stride = ((u64)nt.cols + 31) / 32 * 32;
-        memset(t.col0, 0, sizeof(t.col0));
-        ix->table_sets.push_back(std::move(t));
-        idx = (int)ix->table_sets.size() - 1;
-    }
-    if (ix->adj_tab_key != nkey) { // a new graph or key, or the adjacency changed under a table that stayed (cos_index_delete): refill
-        if (ix->adj_tab_oom_key == nkey) return COS_OK;
-        HIP_TRY(hipDeviceSynchronize()); // (a launch in flight may still read the arrays that go; the adjacency may still be written)
-        ix->adj_tab_key = 0;
-        for (u32 l = 0; l <= ix->p.num_layers; l++) ix->lv[l].d_adj_tab.reset();
-        const cos_index::TableSet &t = ix->table_sets[(size_t)idx];
-        hipError_t e = hipSuccess;
-        for (u32 l = lmin; l <= Ltop && e == hipSuccess; l++) {
-            LevelHost &H = ix->lv[l];
-            if (!H.d_adj_node) e = hipErrorInvalidValue;
-            if (e == hipSuccess) e = H.d_adj_tab.alloc((size_t)H.n * H.M);
-            if (e == hipSuccess) e = cosdev::launch_fill_adj_tab(H.d_adj_node, t.tab_col[l], H.n, H.M, t.node_bits[l], H.d_adj_tab, ix->own_stream);
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(ix->own_stream);
-        if (e != hipSuccess) {
-            for (u32 l = 0; l <= ix->p.num_layers; l++) ix->lv[l].d_adj_tab.reset();
-            if (e == hipErrorOutOfMemory) ix->adj_tab_oom_key = nkey;
-            return go_without(e);
-        }
-        ix->adj_tab_key = nkey;
-    }
-    ix->table_nested_idx = idx;
-    return COS_OK;
-}
-
-static int32_t ensure_level_table(cos_index *ix) {
-    if (!ix->level_table_valid) { // a new graph: its nested set goes with the others
-        ix->table_nested_idx = -1;
-        ix->table_nested_failed_key = 0;
-        ix->adj_tab_key = ix->adj_tab_oom_key = 0;
-    }
-    if (int32_t rc = ensure_per_level_table(ix)) return rc;
-    return ensure_nested_table(ix);
-}
-
-extern "C" int32_t cos_index_set_walk_table(cos_index *ix, uint32_t max_cols, uint32_t min_queries) {
-    if (!ix) return cos_fail(COS_ERR_INVALID, "null argument");
-    if (max_cols > (1u << 20) && max_cols != COS_WALK_TABLE_AUTO) return cos_fail(COS_ERR_INVALID, "max_cols must be <= 2^20 (or COS_WALK_TABLE_AUTO)");
-    std::lock_guard<std::mutex> g(ix->mu);
-    ix->walk_table_max_cols = max_cols;
-    ix->walk_table_min_B = min_queries;
-    return COS_OK;
-}
-
-extern "C" int32_t cos_index_walk_table_info(cos_index *ix, uint32_t *out_level_min, uint32_t *out_cols) {
-    if (!ix || !out_level_min || !out_cols) return cos_fail(COS_ERR_INVALID, "null argument");
-    *out_level_min = *out_cols = 0;
-    if (!graph_ready(ix)) return cos_fail(COS_ERR_NOT_READY, "index needs vectors, root and every graph level");
-    int32_t rc = cos_set_device(ix);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> g(ix->mu);
-    if (walk_table_min_B(ix) == 0) return COS_OK;
-    if ((rc = ensure_level_table(ix))) return rc;
-    *out_level_min = ix->table_level_min;
-    *out_cols = ix->table_nested_idx >= 0 ? ix->table_sets[(size_t)ix->table_nested_idx].cols : ix->table_cols; // what the next big launch computes
-    return COS_OK;
-}
-
-// The per-graph tables of big launches (locality order ranks, level-table operand) built when a graph is committed — the end of
-// cos_index_build, the upload of a graph's last level (which is also how cos_index_load_reference_dir commits) — instead of inside the first big search, where
-// the host-side DFS and the device synchronisations ran under ix->mu and held up every concurrent searcher.  The lazy calls in
-// get_workspace stay as a fall-back (knobs changed after the commit).
-// LevelDev::adj_mag of every level: the norm of each scanned neighbour slot next to the adjacency.  Caller holds ix->mu; graph
-// changes are exclusive (no search in flight).  Out of memory leaves the walk on its mags[] gathers (same results).
-static int32_t ensure_adj_mags(cos_index *ix) {
-    if (ix->adj_mag_valid) return COS_OK;
-    if (!graph_ready(ix) || ix->meta.mdim != 0u) return COS_OK; // (collections with a metadata schema keep the gathers: their walks are walk_meta_kernel's)
-    if (cosdev::walk_rows_over_64_slots(cos_walk_plan_in(ix, 0, 0))) return COS_OK; // (walk_general_kernel's indexes: it gathers the norms)
-    HIP_TRY(hipDeviceSynchronize()); // a build or an upload on another stream may still be writing the adjacency
-    for (u32 l = 0; l <= ix->p.num_layers; l++) {
-        ix->lv[l].d_adj_mag.reset();
-    }
-    for (u32 l = 0; l <= ix->p.num_layers; l++) {
-        LevelHost &H = ix->lv[l];
-        const u32 slots = std::min(H.M, ix->p.shortlist_size);
-        const hipError_t e = H.d_adj_mag.alloc((size_t)H.n * slots);
-        if (e == hipErrorOutOfMemory) {
-            (void)hipGetLastError();
-            for (u32 k = 0; k < l; k++) ix->lv[k].d_adj_mag.reset();
-            return COS_OK; // adj_mag_valid stays false: the next graph change tries again
-        }
-        HIP_TRY(e);
-        HIP_TRY(cosdev::launch_fill_adj_mag(H.d_adj_vec, ix->d_mags, H.d_adj_mag, H.n, H.M, slots, ix->own_stream));
-    }
-    HIP_TRY(hipStreamSynchronize(ix->own_stream));
-    ix->adj_mag_valid = true;
-    return COS_OK;
-}
-
-// LevelDev::adj_up of the ONE level that can use it: the row level directly under the current level table (level >= 1), on a graph
-// whose norms beside the adjacency are valid (the walk takes both from the same window).  Caller holds ix->mu; called where the
-// table's operand is (a commit; get_workspace's fall-back after a knob changed).  When the table rule moves to another level the old
-// array goes.  Out of memory leaves this graph and rule without — same results — and is remembered, not retried per launch.
-static int32_t ensure_adj_up(cos_index *ix) {
-    const u32 want = (ix->adj_mag_valid && ix->level_table_valid && ix->table_level_min >= 2u && ix->eng == ENG_U8 && ix->G == 64u &&
-                      cosdev::tune_or(cosdev::TUNE_WALK_UP_TABLE, WALK_UP_TABLE_DEFAULT) != 0)
-                         ? ix->table_level_min - 1u
-                         : 0u;
-    // With the nested table (ensure_nested_table has settled it) the entries hold the COLUMN of the node one level up, which is what the
-    // throughput kernel — the array's only reader — then indexes the table with; a change of form refills like a change of level.
-    const bool nested = ix->table_nested_idx >= 0;
-    if (want != 0u && ((ix->adj_up_level == want && ix->adj_up_nested == nested) || ix->adj_up_oom_level == want)) return COS_OK; // filled for this graph and rule, or known not to fit
-    bool any = false;
-    for (u32 l = 0; l <= ix->p.num_layers; l++) any = any || ix->lv[l].d_adj_up;
-    if (any) {
-        HIP_TRY(hipDeviceSynchronize()); // (the rule moved under running searches: a launch in flight may still read the array that goes)
-        for (u32 l = 0; l <= ix->p.num_layers; l++) ix->lv[l].d_adj_up.reset();
-    }
-    ix->adj_up_level = 0;
-    if (want == 0u) return COS_OK;
-    ix->adj_up_oom_level = 0;
-    HIP_TRY(hipDeviceSynchronize()); // a build or an upload on another stream may still be writing the adjacency
-    LevelHost &H = ix->lv[want];
-    const LevelHost &U = ix->lv[want + 1];
-    const u32 slots = std::min(H.M, ix->p.shortlist_size);
-    if (!H.d_adj_node || !U.d_child || H.n == 0 || U.n == 0) return COS_OK;
-    DevArr<u32> up; // node of level `want` -> node of the level above
-    hipError_t e = H.d_adj_up.alloc((size_t)H.n * slots);
-    if (e == hipSuccess) e = up.alloc(H.n);
-    if (e == hipErrorOutOfMemory) {
-        (void)hipGetLastError();
-        H.d_adj_up.reset();
-        ix->adj_up_oom_level = want;
-        return COS_OK;
-    }
-    HIP_TRY(e);
-    const u32 *up_col = nested ? ix->table_sets[(size_t)ix->table_nested_idx].tab_col[want + 1].p : nullptr;
-    HIP_TRY(cosdev::launch_fill_adj_up(H.d_adj_vec, H.d_adj_node, ix->d_mags, U.d_child, U.n, up, H.d_adj_up, H.n, H.M, slots, ix->own_stream, up_col));
-    HIP_TRY(hipStreamSynchronize(ix->own_stream));
-    ix->adj_up_level = want;
-    ix->adj_up_nested = nested;
-    return COS_OK;
-}
-
-int32_t cos_prepare_walk_plans(cos_index *ix) {
-    std::lock_guard<std::mutex> g(ix->mu);
-    if (int32_t rc = ensure_adj_mags(ix)) return rc;
-    if (ix->walk_order_min_B)
-        if (int32_t rc = ensure_order_rank(ix)) return rc;
-    if (walk_table_min_B(ix)) {
-        if (int32_t rc = ensure_level_table(ix)) return rc;
-        if (int32_t rc = ensure_adj_up(ix)) return rc;
-    }
-    return COS_OK;
-}
-
-extern "C" int32_t cos_index_walk_order_cuts(cos_index *ix, uint32_t *out_levels, uint32_t cap, uint32_t *out_n) {
-    if (!ix || !out_n || (cap && !out_levels)) return cos_fail(COS_ERR_INVALID, "null argument");
-    *out_n = 0;
-    if (!graph_ready(ix)) return cos_fail(COS_ERR_NOT_READY, "index needs vectors, root and every graph level");
-    int32_t rc = cos_set_device(ix);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> g(ix->mu);
-    if ((rc = ensure_order_rank(ix))) return rc;
-    for (u32 l : ix->order_levels) {
-        if (*out_n < cap) out_levels[*out_n] = l;
-        (*out_n)++;
-    }
-    return COS_OK;
-}
 
 // What one dense search launch runs from: its settled plan (walk_plan.h) and everything of the handle the plan refers to, taken in ONE
 // snapshot under one hold of ix->mu (cos_index_set_* may change the knobs from another thread) by get_workspace; run_search reads
@@ -1150,6 +672,8 @@ struct SearchLaunch {
     const u32 *order_rank[cosdev::MAX_LEVELS];
 };
 
+// the workspace registered under `key` (a caller's stream, or a HostPipe slot), grown to B queries; `st` is the stream the
+// workspace's previous launches ran on (drained before a buffer is replaced)
 // `chain` = the launch may take part in the walk chain (big launches of different streams one after the other); the chunks of one
 // pipelined host call co-run instead.
 static int32_t get_workspace(cos_index *ix, void *key, hipStream_t st, u32 B, u32 top_k, bool host_api, Workspace **out, SearchLaunch *L,
@@ -1158,6 +682,7 @@ static int32_t get_workspace(cos_index *ix, void *key, hipStream_t st, u32 B, u3
     std::unique_ptr<Workspace> &slot = ix->ws[key];
     if (!slot) slot.reset(new Workspace());
     Workspace *w = slot.get();
+    const WalkOperands &ops = ix->ops;
     const u32 L1 = ix->p.num_layers + 1;
     if (B > w->capB) {
         u32 cap = std::max(B, 64u);
@@ -1193,34 +718,35 @@ static int32_t get_workspace(cos_index *ix, void *key, hipStream_t st, u32 B, u3
     const cosdev::WalkPlan want = cosdev::walk_plan(in);
     cosdev::WalkHave have{};
     if (want.refill_adj_mag) {
-        if (int32_t rc = ensure_adj_mags(ix)) return rc;
-        in.adj_mag_valid = ix->adj_mag_valid;
+        if (int32_t rc = cos_ensure_adj_mags(ix)) return rc;
+        in.adj_mag_valid = ops.have_adj_mag();
     }
     if (want.prepare_order) {
         if (w->order.cap < w->capB) {
             HIP_TRY(hipStreamSynchronize(st));
             HIP_TRY(cosdev::walk_order_reserve(w->order, w->capB));
         }
-        if (int32_t rc = ensure_order_rank(ix)) return rc;
+        if (int32_t rc = cos_ensure_order_rank(ix)) return rc;
         have.order_buffers = w->order.cap >= B;
-        have.n_order_keys = (u32)ix->order_levels.size();
-        have.order_level0 = have.n_order_keys ? ix->order_levels[0] : 0u;
+        have.n_order_keys = (u32)ops.order_levels.size();
+        have.order_level0 = have.n_order_keys ? ops.order_levels[0] : 0u;
     }
+    const TableSet *pset = nullptr, *nset = nullptr; // the per-level and the nested table set of the current key
     if (want.prepare_table) {
-        bool nested = false;
-        if (int32_t rc = ensure_level_table(ix)) return rc;
-        if (int32_t rc = ensure_adj_up(ix)) return rc; // (nothing to do unless the table rule, the knob or the norms changed since the commit)
-        have.adj_up_level = ix->adj_up_level;
-        have.adj_up_nested = ix->adj_up_nested;
+        if (int32_t rc = cos_ensure_level_table(ix)) return rc;
+        if (int32_t rc = cos_ensure_adj_up(ix)) return rc; // (nothing to do unless the table rule, the knob or the norms changed since the commit)
+        pset = ops.table_set();
+        nset = ops.nested_set();
+        have.adj_up_level = ops.adj_up_level();
+        have.adj_up_nested = ops.adj_up_nested();
+        have.nested_cols = nset ? nset->cols : 0u;
+        have.table_level_min = pset ? pset->level_min : 0u;
+        have.table_cols = pset ? pset->cols : 0u;
+        have.table_buffer = true;
         // the set this launch reads: the nested one where the handle has it and the kernel that walks is the throughput kernel
         // (settled below by the same rule); its buffer is sized by ITS stride
-        const cos_index::TableSet *nset = ix->table_nested_idx >= 0 ? &ix->table_sets[(size_t)ix->table_nested_idx] : nullptr;
-        have.nested_cols = nset ? nset->cols : 0u;
-        have.table_level_min = ix->level_table_valid ? ix->table_level_min : 0u;
-        have.table_cols = ix->table_cols;
-        have.table_buffer = true;
-        nested = cosdev::walk_plan(in, &have).table_nested;
-        const u64 table_stride = nested ? nset->stride : ix->table_stride;
+        const TableSet *t = cosdev::walk_plan(in, &have).table_nested ? nset : pset;
+        const u64 table_stride = t ? t->stride : 0u;
         const size_t need = (size_t)w->capB * table_stride;
         if (need > w->tab.cap) {
             // every workspace (one per caller stream, up to five per leased host pipe) holds the table of its own launch in flight:
@@ -1231,41 +757,32 @@ static int32_t get_workspace(cos_index *ix, void *key, hipStream_t st, u32 B, u3
             ix->table_bytes_total -= w->tab.cap * 4;
             w->tab.reset();
             if (ix->table_bytes_total + need * 4 <= budget) {
-                if (const hipError_t e = w->tab.alloc(need); e == hipSuccess)
-                    ix->table_bytes_total += need * 4;
-                else if (e == hipErrorOutOfMemory) // HBM is short: this workspace walks without a table (same results)
-                    (void)hipGetLastError();
-                else
-                    HIP_TRY(e);
+                bool without; // HBM is short: this workspace walks without a table (same results)
+                if (int32_t rc = cos_or_go_without(w->tab.alloc(need), &without)) return rc;
+                if (!without) ix->table_bytes_total += need * 4;
             }
         }
         have.table_buffer = w->tab && (size_t)B * table_stride <= w->tab.cap;
     }
     L->plan = cosdev::walk_plan(in, &have);
-    if (L->plan.use_table && L->plan.table_nested) {
-        const cos_index::TableSet &t = ix->table_sets[(size_t)ix->table_nested_idx];
+    if (L->plan.use_table) {
+        const TableSet &t = L->plan.table_nested ? *nset : *pset;
         L->tab_stride = t.stride;
-        memcpy(L->tab_col0, t.col0, sizeof(L->tab_col0)); // all zero: a level's columns are a prefix of the table
+        memcpy(L->tab_col0, t.col0, sizeof(L->tab_col0)); // (nested: all zero, a level's columns are a prefix of the table)
         L->tcodes = t.tcodes;
         L->tmags = t.tmags;
         L->tcsums = t.tcsums;
-        for (u32 l = t.level_min; l <= ix->p.num_layers; l++) {
+        for (u32 l = t.level_min; L->plan.table_nested && l <= ix->p.num_layers; l++) {
             L->adj_tab[l] = ix->lv[l].d_adj_tab;
             L->tab_col[l] = t.tab_col[l];
             L->tab_bits[l] = t.node_bits[l];
         }
-    } else if (L->plan.use_table) {
-        L->tab_stride = ix->table_stride;
-        memcpy(L->tab_col0, ix->table_col0, sizeof(L->tab_col0));
-        L->tcodes = ix->d_tcodes;
-        L->tmags = ix->d_tmags;
-        L->tcsums = ix->d_tcsums;
     }
     if (L->plan.ordered)
-        for (u32 l : ix->order_levels) {
+        for (u32 l : ops.order_levels) {
             L->key_level[L->n_keys] = l;
-            L->key_n[L->n_keys] = ix->order_rank_n[l];
-            L->order_rank[L->n_keys++] = ix->d_order_rank[l];
+            L->key_n[L->n_keys] = ix->lv[l].n; // (the ranks are a permutation of the level's nodes)
+            L->order_rank[L->n_keys++] = ops.d_order_rank[l];
         }
     if (L->plan.ordered && L->n_keys) {
         cosdev::WalkPairIn pi{};
@@ -1459,7 +976,7 @@ static int32_t run_search(cos_index *ix, Workspace *w, const SearchLaunch &L, co
 
 static int32_t check_search_args(cos_index *ix, const void *q, u32 B, u32 top_k) {
     if (!ix || !q) return cos_fail(COS_ERR_INVALID, "null argument");
-    if (!graph_ready(ix)) return cos_fail(COS_ERR_NOT_READY, "index needs vectors, root and every graph level before search");
+    if (!cos_graph_ready(ix)) return cos_fail(COS_ERR_NOT_READY, "index needs vectors, root and every graph level before search");
     if (top_k == 0 || top_k > 1024) return cos_fail(COS_ERR_INVALID, "top_k must be in [1, 1024]");
     if (B == 0) return cos_fail(COS_ERR_INVALID, "empty batch");
     return cos_set_device(ix);

@@ -18,6 +18,7 @@
 #include "dev_mem.h"
 #include "walk_plan.h"
 #include "table_nested.h"
+#include "walk_operands.h"
 
 namespace hybrid_plan {
 struct Slot; // hybrid_plan.h
@@ -141,9 +142,9 @@ struct LevelHost {
     std::vector<u32> nbr_ids;  // [n][M] internal ids / COS_SLOT_EMPTY
     DevArr<u32> d_adj_vec, d_adj_node, d_node_vec, d_child;
     DevArr<u32> d_node_id, d_node_meta; // pseudo-root component only (metadata-filtered search)
-    DevArr<float> d_adj_mag; // [n][min(M, shortlist)] norms of the scanned neighbour slots (LevelDev::adj_mag), valid while cos_index::adj_mag_valid
-    DevArr<cosdev::AdjUp> d_adj_up; // same shape: the neighbours' norms and nodes one level up (LevelDev::adj_up); only level cos_index::adj_up_level has it
-    DevArr<u32> d_adj_tab;   // [n][M] node | nested-table column of every neighbour slot (LevelDev::adj_tab); the table levels of cos_index::adj_tab_key have it
+    DevArr<float> d_adj_mag; // [n][min(M, shortlist)] norms of the scanned neighbour slots (LevelDev::adj_mag), valid while WalkOperands::have_adj_mag()
+    DevArr<cosdev::AdjUp> d_adj_up; // same shape: the neighbours' norms and nodes one level up (LevelDev::adj_up); only level WalkOperands::adj_up_level() has it
+    DevArr<u32> d_adj_tab;   // [n][M] node | nested-table column of every neighbour slot (LevelDev::adj_tab); the table levels of WalkOperands::nested_set() have it
     u32 n = 0, M = 0;
     u32 root_idx = 0;        // pseudo-root component: node index of the pseudo root (base graph: the root is the last node)
     bool host_valid = false; // node_ids/nbr_ids mirror the device arrays
@@ -293,6 +294,47 @@ struct HostPipe {
 };
 static constexpr u32 COS_MAX_HOST_PIPES = 32; // concurrent host-API calls served at once; further callers wait for a pipe
 
+// One operand of the level-table GEMM: the code rows, norms and code sums of the table's nodes ([cols][row_stride] / [cols] / [cols]),
+// level by level from the top, the first column of every level, and floats per query row of the table computed from it (cols padded to
+// 32).  A NESTED set (table_nested.h; key = the per-level set's | TABLE_KEY_NESTED) has one column per node of level_min, col0 all
+// zero, and per table level the node -> column array and the node bits of LevelDev::adj_tab's words.
+struct TableSet : cosdev::TableRule { // key, level_min, cols, col0
+    u64 stride = 0;
+    u32 node_bits[cosdev::MAX_LEVELS] = {};
+    DevArr<uint8_t> tcodes;
+    DevArr<float> tmags;
+    DevArr<u32> tcsums, tab_col[cosdev::MAX_LEVELS];
+};
+
+// Everything a dense handle derives from its resident graph for the walk alone (walk_operands.hip builds and drops it, walk_operands.h
+// decides; DESIGN.md §5.1 has the table of what follows what).  Only LevelHost::d_adj_mag / d_adj_up / d_adj_tab live with their level.
+// Guarded by cos_index::mu; only cos_graph_changed invalidates.
+struct WalkOperands {
+    // the order keys' tables: position of every node of a key level in a depth-first order of that level's graph, and the key
+    // levels themselves, descending (empty = the graph has no level the order could use)
+    DevArr<u32> d_order_rank[cosdev::MAX_LEVELS];
+    std::vector<u32> order_levels;
+    // the table sets of the current graph, one per key: ef_search changes re-select the table's levels while searches of the previous
+    // ef may still be in flight, so nothing a launch may be reading is freed before the graph itself is replaced.  table_idx: the
+    // per-level set of the current key; nested_idx: the nested set of the same levels that the throughput kernel's launches use, with
+    // LevelHost::d_adj_tab filled for it (-1 = none: knob, rule, a graph whose words do not fit, out of memory)
+    std::vector<TableSet> table_sets;
+    int table_idx = -1, nested_idx = -1;
+    // key of `table`: table_rule's; of `nested` and `adj_tab`: that | TABLE_KEY_NESTED; of `adj_up`: the level that holds the filled
+    // array (always the table's level_min - 1), | ADJ_UP_NESTED where its entries hold columns of the nested table, not node indices.
+    // `nested` only remembers "went without" (a built nested set is found in table_sets by its key); `table` is settled for a key with
+    // or without a set (table_idx says which)
+    cosdev::OperandState rank{cosdev::FOLLOWS_LEVELS}, table{cosdev::FOLLOWS_ROOT}, nested{cosdev::FOLLOWS_ROOT};
+    cosdev::OperandState adj_mag{cosdev::FOLLOWS_ADJACENCY}, adj_up{cosdev::FOLLOWS_ADJACENCY}, adj_tab{cosdev::FOLLOWS_ADJACENCY};
+    static constexpr u64 ADJ_UP_NESTED = 1ull << 32;
+    const TableSet *table_set() const { return table_idx >= 0 ? &table_sets[(size_t)table_idx] : nullptr; }
+    const TableSet *nested_set() const { return nested_idx >= 0 ? &table_sets[(size_t)nested_idx] : nullptr; }
+    bool have_adj_mag() const { return adj_mag.kind == cosdev::OperandState::BUILT; }
+    u32 adj_up_level() const { return adj_up.kind == cosdev::OperandState::BUILT ? (u32)adj_up.key : 0u; } // 0 = no level has LevelHost::d_adj_up
+    bool adj_up_nested() const { return adj_up_level() != 0u && (adj_up.key & ADJ_UP_NESTED) != 0; }
+    void drop_tables() { table.invalidate(); nested.invalidate(); adj_tab.invalidate(); table_idx = nested_idx = -1; }
+};
+
 struct cos_index {
     cos_params p;
     int eng = -1;
@@ -354,48 +396,13 @@ struct cos_index {
     u32 walk_order_min_B = COS_WALK_ORDER_DEFAULT_MIN_B;
     u32 n_cus = 256; // hipDeviceAttributeMultiprocessorCount of the handle's device (persistent kernels launch one workgroup per CU)
     u32 num_xcd = 8; // hipDeviceAttributeNumberOfXccs of the handle's device (workgroup b of a grid runs on XCD b % num_xcd)
-    // the order keys' tables: position of every node of a key level in a depth-first order of that level's graph, and the key
-    // levels themselves, descending (ensure_order_rank, engine.hip); rebuilt after the graph changes
-    DevArr<u32> d_order_rank[cosdev::MAX_LEVELS];
-    u32 order_rank_n[cosdev::MAX_LEVELS] = {};
-    std::vector<u32> order_levels; // empty = the graph has no level the order could use
-    bool order_rank_valid = false;
     // Level table (WalkArgs::tab): launches of at least walk_table_min_B queries over u8 codes precompute the similarities to every
-    // node of the levels >= table_level_min with one i8 MFMA GEMM; table_level_min = the lowest level such that the levels from it
-    // to the top hold at most walk_table_max_cols nodes together (0 = no table).  Env COS_WALK_TABLE_COLS / COS_WALK_TABLE_MIN_B.
+    // node of the levels >= the table's level_min with one i8 MFMA GEMM; walk_table_max_cols picks the levels (walk_operands.h,
+    // table_rule; 0 = no table).  Env COS_WALK_TABLE_COLS / COS_WALK_TABLE_MIN_B.
     u32 walk_table_max_cols = COS_WALK_TABLE_AUTO, walk_table_min_B = COS_WALK_TABLE_DEFAULT_MIN_B;
     size_t table_bytes_total = 0;    // tables held by this handle's workspaces (budget: get_workspace)
-    bool adj_mag_valid = false;      // LevelHost::d_adj_mag follows the graph, the norms and the root (ensure_adj_mags)
-    // LevelHost::d_adj_up: the level that holds a filled one (0 = none; always table_level_min - 1 of the table rule it was filled
-    // for), and the level an allocation ran out of memory for (0 = none): that graph and rule go without, it is not tried again
-    // until either changes.  Both fall with adj_mag_valid (invalidate_adj_side) — the array follows the graph exactly like the norms.
-    u32 adj_up_level = 0, adj_up_oom_level = 0;
-    bool adj_up_nested = false;      // ... and its entries hold columns of the nested table (ensure_adj_up), not node indices
-    // LevelHost::d_adj_tab of the table levels: the key of the nested table set it is filled for (0 = none), and the key an allocation
-    // ran out of memory for (that graph and key walk on the per-level table).  Falls with the other two side arrays.
-    u64 adj_tab_key = 0, adj_tab_oom_key = 0;
-    void invalidate_adj_side() { adj_mag_valid = false; adj_up_level = 0; adj_up_oom_level = 0; adj_tab_key = 0; adj_tab_oom_key = 0; }
+    WalkOperands ops;                // what the walk derives from the resident graph (walk_operands.hip; cos_graph_changed invalidates)
     LinkState link;                  // cos_index_build -> cos_index_append (builder.hip); dropped with the graph
-    bool level_table_valid = false;  // the arrays below follow the graph and walk_table_max_cols
-    u32 table_level_min = 0, table_cols = 0;
-    u64 table_built_for_key = 0;    // max_cols, or the automatic rule's per-level bound: a change rebuilds the operand
-    u64 table_stride = 0;            // floats per query row (cols padded to 32)
-    u32 table_col0[cosdev::MAX_LEVELS] = {};
-    const uint8_t *d_tcodes = nullptr; // (these three: views into the set of table_sets that is current) [table_cols][row_stride] code rows of the table's nodes, level by level from the top
-    const float *d_tmags = nullptr;  // [table_cols]
-    const u32 *d_tcsums = nullptr;   // [table_cols]
-    // operands built for other keys of the SAME graph (ef_search changes re-select the table's levels while searches of the previous
-    // ef may still be in flight: nothing a launch may be reading is freed before the graph itself is replaced)
-    // A NESTED set (table_nested.h; key = the per-level set's | TABLE_NESTED_KEY) has one column per node of level_min, col0 all zero, and
-    // per table level the node -> column array and the node bits of LevelDev::adj_tab's words.
-    struct TableSet { u64 key; u32 level_min, cols; u64 stride; u32 col0[cosdev::MAX_LEVELS]; DevArr<uint8_t> tcodes; DevArr<float> tmags; DevArr<u32> tcsums;
-                      DevArr<u32> tab_col[cosdev::MAX_LEVELS]; u32 node_bits[cosdev::MAX_LEVELS] = {}; };
-    std::vector<TableSet> table_sets;
-    static constexpr u64 TABLE_NESTED_KEY = 1ull << 62;
-    // the nested set of the current (graph, key) that the throughput kernel's launches use: index into table_sets, -1 = none (knob, rule,
-    // a graph whose words do not fit, out of memory); the key it was last settled for together with the knob's value
-    int table_nested_idx = -1;
-    u64 table_nested_failed_key = 0; // this (graph, key) has no nested set and is not tried again
     u32 walk_side_min_B = 4096; // launches of at least this many queries walk on the workspace's low-priority stream; 0 = never
     // launches of at most this many queries run the latency variant of the walk (kernels_walk_lat.hip) where it applies; 0 = never
     u32 lat_max_B = COS_LATENCY_MODE_DEFAULT_MAX_B;
@@ -424,6 +431,21 @@ void cos_coalesce_release(cos_index *ix);
 cosdev::IndexDev cos_make_index_dev(const cos_index *ix);
 cosdev::IndexDev cos_make_meta_dev(const cos_index *ix);
 int32_t cos_set_device(const cos_index *ix);
-cosdev::WalkPlanIn cos_walk_plan_in(const cos_index *ix, u32 B, u32 ef); // the handle's shape and resolved knobs as walk_plan's inputs (engine.hip)
-int32_t cos_prepare_walk_plans(cos_index *ix); // order ranks + level-table operand of a freshly committed graph (engine.hip)
+// the walk's operands (walk_operands.hip); the caller holds ix->mu, cos_prepare_walk_plans takes it
+inline bool cos_graph_ready(const cos_index *ix) {
+    if (!ix->have_vectors || !ix->have_root) return false;
+    for (auto &l : ix->lv) if (l.n == 0) return false;
+    return true;
+}
+void cos_graph_changed(cos_index *ix, cosdev::GraphChange change); // the ONLY call that invalidates them
+cosdev::WalkPlanIn cos_walk_plan_in(const cos_index *ix, u32 B, u32 ef); // the handle's shape and resolved knobs as walk_plan's inputs
+u32 cos_walk_table_min_B(const cos_index *ix);   // cos_index_set_walk_table's min_queries after its override
+int32_t cos_ensure_adj_mags(cos_index *ix);      // LevelHost::d_adj_mag of every level
+int32_t cos_ensure_order_rank(cos_index *ix);    // order ranks
+int32_t cos_ensure_level_table(cos_index *ix);   // per-level and nested table sets of the current key, LevelHost::d_adj_tab
+int32_t cos_ensure_adj_up(cos_index *ix);        // LevelHost::d_adj_up of the level under the table (after cos_ensure_level_table)
+int32_t cos_prepare_walk_plans(cos_index *ix);   // all of them, for a freshly committed graph
+// An operand that is an optimisation and does not fit the device's memory: *without = true, the error is cleared, COS_OK (the caller goes
+// without: same results); every other error is reported as HIP_TRY reports it
+int32_t cos_or_go_without(hipError_t e, bool *without);
 void cos_meta_free_levels(cos_index *ix); // device arrays + host lists of every level of the pseudo-root component

@@ -18,7 +18,7 @@ struct LevelDev {
     // (mag_stride = min(M, shortlist_size); empty slots hold 1).  An expansion on a row level then gets its winners' norms with the
     // adjacency row it fetches anyway (coalesced, one more line or two per expansion) instead of one 4-byte gather per winner, each
     // of which pulled a whole line from a 50 MB array (12 % of the lower range's HBM traffic at 12.5M x 1024).  Written when a
-    // graph is committed (engine.hip ensure_adj_mags); nullptr while a graph is being built or after the root changed: the walk then
+    // graph is committed (walk_operands.hip cos_ensure_adj_mags); nullptr while a graph is being built or after the root changed: the walk then
     // gathers mags[] as before.  Same values, same bits.
     const float *adj_mag;
     u32 mag_stride;
@@ -28,7 +28,7 @@ struct LevelDev {
     // slot is empty.  Only the row level directly under the level table has it (WalkPlan::up_table_level): a winner with a node one
     // level up already has its integer dot in the table (WalkArgs::tab, column tab_col0[l + 1] + up), so the walk reads that
     // column — one line — instead of the neighbour's code row.  Same integer, same bits.  nullptr everywhere else.  Filled after
-    // adj_mag (engine.hip ensure_adj_up) and invalidated with it.
+    // adj_mag (walk_operands.hip cos_ensure_adj_up) and invalidated with it.
     // Every entry carries the slot's norm too (.mag = adj_mag's value, same bits), and the walk of that level reads THIS array instead
     // of adj_mag, one 8-byte load per slot: a plain u32 array beside adj_mag is one more pointer alive through the level's rounds, which
     // cost two VGPRs in every u8 instantiation of walk_kernel and put walk_kernel<ENG_U8, 1, 1, true, false, 8> (71 of its 72 VGPRs
@@ -42,7 +42,7 @@ struct LevelDev {
     // adj_tab[node * M + slot] = adj_node's node | its table column << tab_bits, the empty marker kept — a table level's walk loads it
     // WHERE it loaded adj_node (same two loads per window entry, same bytes) and has the winner's column without a load of its own.
     // tab_col: [n] node -> column, for the level's start node (one wave-uniform load per level).  A side array like adj_mag and adj_up:
-    // filled where the table's operand is (engine.hip ensure_nested_table), invalidated with them.  nullptr on every other level and launch;
+    // filled where the table's operand is (walk_operands.hip ensure_nested_table), invalidated with them.  nullptr on every other level and launch;
     // with the nested table adj_up.up of the level under it holds the COLUMN of the node one level up (WalkArgs::tab_col0 is all zero).
     const u32 *adj_tab;
     const u32 *tab_col;
@@ -102,7 +102,7 @@ struct WalkArgs {
     u64 *out_stats;      // [B][4]: evals, expansions, adj_bytes, rounds
     u64 *out_stats2;     // optional [B][4] (walk_kernel only): evals, expansions, adj_bytes of the LAST level range of a split walk
                          // (the whole walk when it is not split), evaluations served by the level table
-    // Level table (big search launches over u8 codes; kernels_flat.hip launch_level_table, engine.hip ensure_level_table): for the
+    // Level table (big search launches over u8 codes; kernels_flat.hip launch_level_table, walk_operands.hip cos_ensure_level_table): for the
     // levels >= tab_level_min — few nodes, walked by every query — the dot product of every (query, node) pair is computed before
     // the walk as ONE exact-integer i8 MFMA GEMM, tab[q][tab_col0[level] + node] = dot_product_u8 `as f32` (x86_64.rs:22-66).
     // The walk of those levels reads 4 bytes (+ the node's norm, tab_mags: a few KB that stay in L2) per evaluation instead of

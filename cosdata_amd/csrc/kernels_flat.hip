@@ -1378,7 +1378,7 @@ extern "C" int32_t cos_index_download_deleted(cos_index *ix, uint32_t *bits) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// Level table of the walk (WalkArgs::tab, engine.hip ensure_level_table / run_search): similarity of every query of a big launch to
+// Level table of the walk (WalkArgs::tab, walk_operands.hip cos_ensure_level_table / engine.hip run_search): similarity of every query of a big launch to
 // every node of the graph's small upper levels, as ONE pass of the exact-integer i8 GEMM above with its unfused epilogue —
 // `(u32 dot) as f32` and the IEEE quotient by |q| * |v|, the very operations the walk applies to a row it dots itself
 // (cosine.rs:223-235), so the table holds the bits the walk would have computed.  The walk then reads 4 bytes per evaluation on

@@ -822,7 +822,7 @@ __global__ __launch_bounds__(512) void flat_scan_q2_fp4_w8(const uint8_t *__rest
 }
 
 // ------------------------------------------------------------------------------------------------
-// Level table of the walk (WalkArgs::tab; engine.hip ensure_level_table / run_search) as a query-resident GEMM over u8 codes.
+// Level table of the walk (WalkArgs::tab; walk_operands.hip cos_ensure_level_table / engine.hip run_search) as a query-resident GEMM over u8 codes.
 // Round 4 ran this product on flat_codes_gemm_i8 (the 256 x 128 tile kernel): 0.15-0.18 of the i8 peak, because every tile
 // restages 256 query rows through LDS for 64 k steps' worth of MFMAs, and its epilogue formed the exact quotient dot / (|q| |v|)
 // for each of B x cols outputs (685 M per launch at c2) of which the walk reads 13 %.  Round 5:

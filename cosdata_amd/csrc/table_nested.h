@@ -1,5 +1,5 @@
 // table_nested.h — the nested column order of the throughput walk's level table and the packed adjacency word of its table levels.
-// Plain integer logic: no HIP, no handle (engine.hip ensure_nested_table fills the device arrays from it; tests/cxx/table_nested_check.cpp
+// Plain integer logic: no HIP, no handle (walk_operands.hip ensure_nested_table fills the device arrays from it; tests/cxx/table_nested_check.cpp
 // checks it on a CPU).
 //
 // The levels of an HNSW graph are nested: every node of level l + 1 has a child on level l (LevelDev::child), the same vector.  A table

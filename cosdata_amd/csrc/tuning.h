@@ -48,9 +48,9 @@ enum TuneKey : int {
     TUNE_WALK_R2,             // 0 = ef 65..128 walks with the 256-key pool of ef 129..256 (default 1: a 128-key pool)
     TUNE_FINALIZE_WIDE_MAX_B, // launches of at most this many queries finalize with eight waves per query (default 1024; 0 = never)
     TUNE_FLAT_FP4_W8,         // the FP4 scan of 768-dim quaternary codes: 0 = one wave per SIMD (flat_scan_q2_fp4), 1..4 = two waves per SIMD, flat_scan_q2_fp4_w8<ORDER = value - 1> (default 4: even deal, alternating accumulators, 128-column tiles)
-    TUNE_WALK_TABLE_EARLY_WGS, // workgroups of the EARLY part of a gated level-table GEMM, issued behind the previous chained walk's upper range (walk_plan.h); 0 = one launch behind its order sort (default: WALK_TABLE_EARLY_WGS_DEFAULT, engine.hip)
-    TUNE_WALK_UP_TABLE,       // the row level directly under the level table reads table columns for neighbours that have a node one level up (LevelDev::adj_up): 0 = never, 1 = where that level reads its norms beside the adjacency (walk_adj_mag's rule), 2 = at every ef and launch size (tests); default WALK_UP_TABLE_DEFAULT, engine.hip
-    TUNE_WALK_TABLE_NESTED,   // the throughput kernel's level table holds one column per vector of its lowest level, in nested order (table_nested.h), and its table levels read LevelDev::adj_tab: 0 = never, 1 = on graphs where that saves TABLE_NESTED_MIN_SAVED_COLS columns or more, 2 = on every graph (tests); default WALK_TABLE_NESTED_DEFAULT, engine.hip
+    TUNE_WALK_TABLE_EARLY_WGS, // workgroups of the EARLY part of a gated level-table GEMM, issued behind the previous chained walk's upper range (walk_plan.h); 0 = one launch behind its order sort (default: WALK_TABLE_EARLY_WGS_DEFAULT, walk_operands.hip)
+    TUNE_WALK_UP_TABLE,       // the row level directly under the level table reads table columns for neighbours that have a node one level up (LevelDev::adj_up): 0 = never, 1 = where that level reads its norms beside the adjacency (walk_adj_mag's rule), 2 = at every ef and launch size (tests); default WALK_UP_TABLE_DEFAULT, walk_operands.hip
+    TUNE_WALK_TABLE_NESTED,   // the throughput kernel's level table holds one column per vector of its lowest level, in nested order (table_nested.h), and its table levels read LevelDev::adj_tab: 0 = never, 1 = on graphs where that saves TABLE_NESTED_MIN_SAVED_COLS columns or more, 2 = on every graph (tests); default WALK_TABLE_NESTED_DEFAULT, walk_operands.hip
     TUNE_FLAT_BRUTE_EXACT,    // which queries of a brute force are scored again in the reference's order (flat_plan.h brute_margin_safe): 0 = none — the ranking of the f32 MFMA alone cuts the pool, which on corpora with near-copies of one row CAN return a wrong list (kept for A/B timing; the one knob that can change a result), 1 = those the margin rule flags (default), 2 = every query
     TUNE_WALK_PAIR,           // the last range of an ordered launch is walked two sorted neighbours per workgroup, sharing integer dots through LDS (kernels_walk_pair.hip, walk_pair_plan.h): 0 = never, 1 = launches of WALK_PAIR_MIN_B queries or more inside the pair kernel's domain, 2 = at every launch size (tests); default WALK_PAIR_DEFAULT, engine.hip
     TUNE_WALK_PAIR_CACHE,     // ... entries of a query's dot cache (a power of two, 64..2048; 8 bytes of LDS each; a size whose two waves do not fit 64 KB of LDS leaves the launch to walk_kernel); default WALK_PAIR_CACHE_DEFAULT, engine.hip

@@ -91,7 +91,7 @@ __global__ __launch_bounds__(PAIR ? 128 : 64) __attribute__((amdgpu_waves_per_eu
 
     // ---- engine set-up -------------------------------------------------------------------------
     constexpr bool FLOAT_ENG = ENG == ENG_F32 || ENG == ENG_F16; // ordered f32 chains instead of integer chunk dots
-    constexpr bool TABLE_OK = ENG == ENG_U8 || ENG == ENG_Q2; // level tables exist for u8 and quaternary codes (engine.hip, ensure_level_table)
+    constexpr bool TABLE_OK = ENG == ENG_U8 || ENG == ENG_Q2; // level tables exist for u8 and quaternary codes (walk_operands.hip, cos_ensure_level_table)
     const int G = (ENG == ENG_F32) ? 8 : (ENG == ENG_F16 ? 1 : (int)ix.G); // f32: eight lanes per row, one per accumulator chain
     const int lig = lane & (G - 1);  // lane in group
     const int grp = lane / G;        // group index

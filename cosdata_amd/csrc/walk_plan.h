@@ -2,7 +2,7 @@
 // whether the level-table GEMM runs (and what it waits for), which levels read norms beside the adjacency, which stream and chain the
 // walk joins, and what has to be prepared for all that.  Plain integer logic: no HIP, no handle, no global — every knob arrives resolved
 // in WalkPlanIn, so the rules can be checked on a CPU (tests/cxx/walk_plan_check.cpp against tests/golden/walk_plan_cases.txt).
-// engine.hip plans in get_workspace (cos_walk_plan_in fills the inputs), prepares what the plan wants, settles it against what exists and
+// engine.hip plans in get_workspace (cos_walk_plan_in, walk_operands.hip, fills the inputs), prepares what the plan wants, settles it against what exists and
 // launches from it; builder.hip's walks take their kernel from the same function.
 //
 // The level-table GEMM of a chained big launch (round 7).  The query-resident GEMM (kernels_scan.hip level_table_areg) is a queue of
@@ -60,7 +60,7 @@ struct WalkPlanIn {
     long long table_after_sort;     // tuning knob walk_table_after_sort: 0 never | 1 tables of 2^30 entries or more | 2 always
     // what exists before anything is prepared
     bool table_supported;           // the engine has a level table at all (level_table_eng_supported)
-    bool adj_mag_valid;             // cos_index::adj_mag_valid (engine.hip sets it again after the refill, before it settles the plan)
+    bool adj_mag_valid;             // WalkOperands::have_adj_mag() (engine.hip sets it again after the refill, before it settles the plan)
     // the two-part level-table GEMM (header comment)
     uint32_t table_early_wgs;       // tuning knob walk_table_early_wgs, resolved (0 = one launch)
     bool table_queue;               // the table comes from the query-resident GEMM, whose work items can be shared by two launches
@@ -69,7 +69,7 @@ struct WalkPlanIn {
     uint32_t up_table_mode;         // tuning knob walk_up_table, resolved: 0 never | 1 by the rule below | 2 at every ef and launch size
     // the throughput kernel reads the nested table, one column per vector (WalkPlan::table_nested, table_nested.h)
     uint32_t table_nested_mode;     // tuning knob walk_table_nested, resolved: 0 never | 1, 2 wherever the handle has the nested operand (the knob's two
-                                    // values differ in which graphs get one: engine.hip ensure_nested_table)
+                                    // values differ in which graphs get one: walk_operands.hip ensure_nested_table)
 };
 
 // What preparation left, for the second step: no table operand for this graph and rule, no room for a workspace's table (out of

@@ -6,7 +6,7 @@
 Every object's gfx950 code object is extracted (llvm-objdump --offloading) and disassembled; a function's instruction sequence is
 its disassembly without addresses, encodings and branch targets.  Prints the functions whose sequences differ, with both
 instruction counts and, for kernels, both vgpr_count / private_segment_fixed_size / group_segment_fixed_size of the code object's
-notes, and the functions only one build has; a differing function whose two builds hold the same opcodes the same number of times
+notes, the functions only one build has, and the objects only one build has (a difference unless the object is host-only); a differing function whose two builds hold the same opcodes the same number of times
 (another schedule or register assignment) is marked.  A plain text diff: it looks for no particular instruction.
 Exit status: 0 = identical, 1 = differences, 2 = a kernel's registers, scratch or LDS grew.
 """
@@ -81,9 +81,13 @@ def main():
     objs = lambda d: {f for f in os.listdir(d) if f.endswith(".o")}
     old_objs, new_objs = objs(a.old_dir), objs(a.new_dir)
     status = 0
-    for f in sorted(old_objs ^ new_objs):
-        print(f"{f}: only in {a.old_dir if f in old_objs else a.new_dir}")
-        status = 1
+    for f in sorted(old_objs ^ new_objs):                    # a translation unit that came or went: a difference if it holds device code
+        d = a.old_dir if f in old_objs else a.new_dir
+        with tempfile.TemporaryDirectory() as w:
+            funcs, _ = code_object(a.llvm, os.path.join(d, f), w)
+        print(f"{f}: only in {d}" + (f", {len(funcs)} device functions" if funcs else ", host-only"))
+        if funcs:
+            status = 1
     n_funcs = n_kernels = 0
     for f in sorted(old_objs & new_objs):
         with tempfile.TemporaryDirectory() as wa, tempfile.TemporaryDirectory() as wb:

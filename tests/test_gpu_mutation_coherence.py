@@ -344,12 +344,12 @@ def scenarios():
 @pytest.mark.parametrize("point", range(len(M.FULL_HISTORY) + 1))
 def test_warm_handle_follows_the_full_history(scenarios, point):
     """u8 x 96, append 1 / 700 / 800, delete 1 / 39 / 120, append 300; the whole matrix at every point.  Guards, in cos_index_append
-    (builder.hip:401-405): order_rank_valid, level_table_valid (with it engine.hip ensure_level_table's table_sets.clear() and the
-    workspace's table buffer regrown by get_workspace when table_stride grows), adj_mag_valid, cos_flat_ws_release (kernels_flat.hip
+    (builder.hip): cos_graph_changed(LEVELS) (with it walk_operands.hip cos_ensure_level_table's table_sets.clear() and the
+    workspace's table buffer regrown by get_workspace when the set's stride grows), cos_flat_ws_release (kernels_flat.hip
     cos_flat_ws_release: the stored code sums and zero-norm flags of the old corpus), the levels' host mirrors (builder.hip:458-459);
-    in cos_index_delete (builder.hip:630-632): adj_mag_valid, the host mirrors, and the argued NON-invalidation of the level table and
+    in cos_index_delete (builder.hip): cos_graph_changed(ADJACENCY), the host mirrors, and the argued NON-invalidation of the level table and
     the locality order; in engine.hip: vis_tab_prepare's stride of the grown graph over a bitset that is all-zero between launches,
-    ensure_adj_mags after every graph change, the host pipe's chunk workspaces."""
+    walk_operands.hip cos_ensure_adj_mags after every graph change, the host pipe's chunk workspaces."""
     sc = scenarios("full")
     _check_at("full", point, len(M.FULL_HISTORY), lambda: Timeline(sc, FULL_ITEMS))
 

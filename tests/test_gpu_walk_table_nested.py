@@ -177,6 +177,73 @@ def test_append_and_delete_on_the_resident_graph():
     assert not np.isin(nest[0], dele).any()
 
 
+def _auto_level_min(counts, ef, M, c=None):
+    """the automatic table rule (walk_operands.h, table_rule) over the nodes of levels 0 .. top: level by level from the top while a level
+    holds at most c x ef x M nodes (c = 10 up to ef = 1.5 M, 8 up to 2 M, 6 above, or knob walk_table_rule_c; 2^20 at most, alone and
+    together)"""
+    if c is None:
+        c = 10 if 2 * ef <= 3 * M else 8 if ef <= 2 * M else 6
+    lmin = cols = 0
+    for l in range(len(counts) - 1, 0, -1):
+        if counts[l] > min(c * ef * M, 1 << 20) or cols + counts[l] > 1 << 20:
+            break
+        lmin, cols = l, cols + counts[l]
+    return lmin
+
+
+# 20 000 x 64, ten layers (levels near 5 000 / 1 250 / 313): ef 16 -> 112 -> 16 moves the table from level 2 to level 1 and back; rows of
+# four chunks, so no level wants adj_up under either key.
+# 6 000 x 1024, five layers (levels near 1 500 / 375 / 94), walk_table_rule_c = 1: ef 16 -> 64 -> 16 moves it from level 3 (bound 256) to
+# level 2 (bound 1 024) and back; rows of one pass, so adj_up is filled for level 2, freed and filled for level 1, and filled for level 2
+# again, every time with columns of the nested table.
+@pytest.mark.parametrize("dim,layers,n,efs,rule_c", [(64, 10, N, (16, 112), None), (1024, 5, 6000, (16, 64), 1)])
+def test_the_table_key_changes_and_comes_back(dim, layers, n, efs, rule_c):
+    """ef_search moves the automatic rule to another key and back on one handle: the nested set, adj_tab and adj_up of the level under
+    the table are settled for the second key beside the first key's sets, which are found again afterwards.  Every step reports the
+    rule's level and the columns of the nested set, equals the same handle without nested table and up-table columns, and equals the
+    oracle; the level under the table reads table columns at every step where it can (1024 dims); the third step gives the first
+    step's bits."""
+    import cosdata_amd as ca
+    X, oix = _oracle(dim, O.METRIC_COSINE, layers, n)
+    dix = H.device_index_from_oracle(oix, X)
+    dix.set_latency_mode(0)
+    dix.set_latency_waves(0)
+    dix.set_walk_order(0)
+    dix.set_walk_table(ca.HNSWIndex.WALK_TABLE_AUTO, 1)
+    counts = [dix.level_count(l) for l in range(_top(dix) + 1)]
+    want = {ef: _auto_level_min(counts, ef, 16, rule_c) for ef in efs}
+    assert want[efs[0]] != want[efs[1]] and min(want.values()) >= (2 if dim == 1024 else 1), (counts, want)
+    Q = H.queries_from(X, 300, noise=0.05, seed=21)
+    rule = {} if rule_c is None else dict(walk_table_rule_c=rule_c)
+    on, off = dict(NEST, **UP_ON, **rule), dict(FLAT, **UP_OFF, **rule)
+    steps = []
+    try:
+        for ef in (efs[0], efs[1], efs[0]):
+            dix.set_ef_search(ef)
+            oix.set_ef_search(ef)
+            lmin, n_min, n_all = want[ef], counts[want[ef]], sum(counts[want[ef]:])
+            nest, rc2, walk2, sp2, sps2, info2 = _run(dix, Q, on)
+            flat, rc0, walk0, sp0, sps0, info0 = _run(dix, Q, off)
+            assert info2 == (lmin, n_min) and info0 == (lmin, n_all)
+            for sp, cols in ((sp2, n_min), (sps2, n_min), (sp0, n_all), (sps0, n_all)):
+                assert sp.table_level_min == lmin and sp.table_cols == cols and sp.table_evals > 0
+            if dim == 1024:     # adj_up of level lmin - 1 is there, in the nested table's columns: a stale or missing array reads no column
+                assert int(sp2.table_evals) > int(sp0.table_evals) and int(sps2.table_evals) > int(sps0.table_evals)
+            else:
+                assert int(sp2.table_evals) == int(sp0.table_evals)
+            assert rc2 == rc0 and _same(nest, flat) and _same(walk2, walk0) and np.count_nonzero(nest[3]) == 0
+            _check_against_oracle(oix, nest[:3], Q, 10, np.arange(0, 300, 19))
+            steps.append((nest, walk2))
+        assert _same(steps[2][0], steps[0][0])
+        # ... and the per-level lists, up to their counts (the workspace keeps step two's longer lists behind them)
+        (ids0, sims0, cnt0), (ids2, sims2, cnt2) = steps[0][1], steps[2][1]
+        live = np.arange(ids0.shape[2])[None, None, :] < cnt0[:, :, None]
+        assert np.array_equal(cnt2, cnt0) and np.array_equal(ids2[live], ids0[live])
+        assert np.array_equal(sims2[live].view(np.uint32), sims0[live].view(np.uint32))
+    finally:
+        oix.set_ef_search(112)
+
+
 def test_one_client_batch_keeps_the_per_level_table():
     """a 256-query batch above ef 128 takes the four-wave kernel, whose source knows nothing of the nested table: on a handle whose big
     launches read the nested set it reads the per-level one, and answers as it did"""
