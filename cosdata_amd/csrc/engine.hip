@@ -149,6 +149,9 @@ extern "C" int32_t cos_index_create(const cos_params *p, cos_index **out) {
     ix->row_stride = row_stride;
     ix->nchunks = nchunks;
     ix->G = G;
+    // (binary / octal codes, f16 / f32 rows: the latency kernels take their small launches where they were measured faster — walk_plan.h)
+    ix->lat_max_B = cosdev::walk_latency_default_max_B(eng, false, COS_LATENCY_MODE_DEFAULT_MAX_B);
+    ix->lat4_max_B = cosdev::walk_latency_default_max_B(eng, true, COS_LATENCY_WAVES_DEFAULT_MAX_B);
     ix->lv.resize(p->num_layers + 1);
     for (u32 l = 0; l <= p->num_layers; l++) ix->lv[l].M = l == 0 ? p->level0_neighbors_count : p->neighbors_count;
     if (hipSetDevice(p->device) != hipSuccess || hipStreamCreateWithFlags(&ix->own_stream, hipStreamNonBlocking) != hipSuccess) {
@@ -1459,6 +1462,14 @@ extern "C" int32_t cos_index_last_stats(cos_index *ix, void *stream, cos_search_
     std::vector<u64> rr(w->lastB);
     HIP_TRY(hipMemcpy(rr.data(), w->rerank_rows, rr.size() * 8, hipMemcpyDeviceToHost));
     for (u32 b = 0; b < w->lastB; b++) out->rerank_rows += rr[b];
+    return COS_OK;
+}
+
+extern "C" int32_t cos_index_last_walk_kernel(cos_index *ix, void *stream, uint32_t *out_kernel) {
+    if (!ix || !out_kernel) return cos_fail(COS_ERR_INVALID, "null argument");
+    Workspace *w = find_workspace(ix, stream, true);
+    if (!w || w->lastB == 0) return cos_fail(COS_ERR_NOT_READY, "no batch has run on this stream");
+    *out_kernel = (uint32_t)w->last_plan.kernel;
     return COS_OK;
 }
 

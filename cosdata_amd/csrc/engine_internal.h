@@ -48,6 +48,9 @@ hipError_t launch_quantize_rows(int eng, const float *x, u64 x_stride, u32 n, u3
 hipError_t launch_walk(int eng, const IndexDev &ix, const WalkArgs &wa, WalkKernel kernel, hipStream_t st); // `kernel`: WalkPlan::kernel (walk_plan.h)
 static_assert(WALK_PLAN_MAX_LEVELS == MAX_LEVELS && WALK_PLAN_ENG_U8 == ENG_U8 && WALK_PLAN_ENG_Q2 == ENG_Q2 && WALK_PLAN_FAST_MAX_EF == WALK_FAST_MAX_EF &&
               COS_STORAGE_U8 == 0u && COS_VISITED_REF == 0u, "walk_plan.h restates these");
+static_assert(WALK_PLAN_ENG_F32 == ENG_F32 && WALK_PLAN_ENG_F16 == ENG_F16 && WALK_PLAN_ENG_Q1 == ENG_Q1 && WALK_PLAN_ENG_Q3 == ENG_Q3 &&
+              (int)WalkKernel::General == COS_WALK_KERNEL_GENERAL && (int)WalkKernel::Throughput == COS_WALK_KERNEL_THROUGHPUT &&
+              (int)WalkKernel::Lat1 == COS_WALK_KERNEL_LATENCY && (int)WalkKernel::Lat4 == COS_WALK_KERNEL_LATENCY_WAVES, "walk_plan.h restates these");
 hipError_t launch_walk_meta(int eng, const IndexDev &ix, const WalkArgs &wa, hipStream_t st);
 hipError_t launch_walk_meta_index(int eng, const IndexDev &ix, const WalkArgs &wa, hipStream_t st);
 hipError_t launch_finalize(const IndexDev &ix, const float *queries, u64 q_stride, const float *q_raw_mags, const u32 *walk_ids,

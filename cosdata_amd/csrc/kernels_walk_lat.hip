@@ -18,8 +18,10 @@
 //     chunk; the commit is unrolled over the window (rows and keys stay in registers) and screens an expansion's winners with one
 //     vector compare before the insertion loop.  A lone wave pays ~4 clocks for EVERY instruction, scalar ones included, so the
 //     kernel is written for instruction count (DESIGN.md 4.1 has the step-by-step measurements).
-// Integer engines ENG_U8 / ENG_Q2 with <= 64 chunks per row, ef <= 256, reference visited filter; everything else stays on
-// walk_kernel (launch_walk decides; cos_index_set_latency_mode).
+// Integer engines (u8, binary, quaternary, octal codes) with <= 64 chunks per row; f32 / f16 rows of <= WALK_LAT_FLOAT_MAX_DIM
+// dimensions, whose step 3 is the float blocks of walk_common.h (spec_f32_dots, spec_f16_dots: reference-order chains against the
+// query in LDS) in place of spec_row_dots; ef <= 256, reference visited filter.  Everything else stays on walk_kernel (walk_plan.h
+// decides; cos_index_set_latency_mode).
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -27,6 +29,7 @@
 #include "engine_types.h"
 #include "tuning.h"
 #include "walk_common.h"
+#include "walk_plan.h"
 
 using namespace cosdev;
 
@@ -35,6 +38,7 @@ namespace {
 constexpr int LAL = 4;  // window capacity (adjacency rows prefetched per round); the launch picks la <= LAL.  8 measured slower (see launch_walk_lat)
 constexpr int GL = LAT_ROW_LANES; // lanes per code row (4 rows per wave pass)
 constexpr int PBL = 8;  // passes in flight before the dots are consumed (32 rows)
+constexpr int PBF = 4;  // f32 rows: passes of 8 rows side by side (32 rows, 32 dwords in flight per lane)
 
 template <int ENG, int CH, int R, bool PREFETCH_ADJ>
 __global__ __launch_bounds__(64) void walk_lat_kernel(const IndexDev ix, const WalkArgs wa, const u32 la) {
@@ -43,14 +47,22 @@ __global__ __launch_bounds__(64) void walk_lat_kernel(const IndexDev ix, const W
     const u32 qi = blockIdx.x;
     if (qi >= wa.B) return;
 
+    constexpr bool FLOAT_ENG = ENG == ENG_F32 || ENG == ENG_F16; // ordered f32 chains instead of integer chunk dots
     u64 *s_spec, *s_cl, *s_res;
     u32 *s_vis;
+    float *s_q = nullptr;  // float engines: the query as f32
+    u32 *s_tile = nullptr; // f16: the row tile (spec_f16_dots)
     {
         unsigned char *p = smem_raw;
         s_spec = (u64 *)p;     p += (size_t)LAL * 64 * 8; // per (window entry, slot): similarity key | zero-denominator flag << 32
         s_cl = (u64 *)p;       p += (size_t)LAL * 64 * 8; // compacted candidates: vector row | (entry * 64 + slot) << 32
         s_res = (u64 *)p;      p += (size_t)wa.ef * 8;    // popped (key, node) list
         s_vis = (u32 *)p;      // visited filter words, Mmax * 2
+        if constexpr (FLOAT_ENG) { // (walk_lat_lds_bytes, walk_plan.h)
+            const u32 own = (u32)(LAL * 64 * 8 * 2) + wa.ef * 8u + walk_mmax(ix) * 8u;
+            s_q = (float *)(smem_raw + ((own + 15u) & ~15u));
+            s_tile = (u32 *)((unsigned char *)s_q + lat_float_query_bytes(ENG, ix.dim));
+        }
     }
 
     const u32 qrow = wa.q_rows ? wa.q_rows[qi] : qi;
@@ -65,10 +77,16 @@ __global__ __launch_bounds__(64) void walk_lat_kernel(const IndexDev ix, const W
     const int grp = lane / GL;
     const u64 lt_mask = (1ull << lane) - 1ull;
     uint4 qreg[CH];
+    if constexpr (FLOAT_ENG) {
+        stage_float_query<ENG, 64>(s_q, qcode, ix, lane);
+        __builtin_amdgcn_s_waitcnt(0);
+        __builtin_amdgcn_wave_barrier();
+    } else {
 #pragma unroll
-    for (int c = 0; c < CH; c++) {
-        const u32 chunk = (u32)lig + (u32)c * (u32)GL;
-        qreg[c] = chunk < ix.nchunks ? *(const uint4 *)(qcode + (u64)chunk * 16) : make_uint4(0, 0, 0, 0);
+        for (int c = 0; c < CH; c++) {
+            const u32 chunk = (u32)lig + (u32)c * (u32)GL;
+            qreg[c] = chunk < ix.nchunks ? *(const uint4 *)(qcode + (u64)chunk * 16) : make_uint4(0, 0, 0, 0);
+        }
     }
 
     u64 n_evals = 0, n_exp = 0, adj_bytes = 0, n_rounds = 0;
@@ -76,11 +94,13 @@ __global__ __launch_bounds__(64) void walk_lat_kernel(const IndexDev ix, const W
     u32 entry = ix.lv[L].root_idx;
     u32 warm = 0; // see the L2 warm-up in step 2
 
-    // similarity of ONE row, computed by lane group 0; result in every lane
+    // similarity of ONE row, computed by lane group 0 (float rows: by the wave); result in every lane
     auto single_distance = [&](u32 row, float &sim_out) -> bool {
-        const u32 acc = int_row_dot_group0<ENG, CH>(qreg, ix.codes + (u64)row * ix.row_stride, ix.nchunks, lig, grp, GL);
+        float dotf;
+        if constexpr (FLOAT_ENG) dotf = float_row_dot_wave<ENG>(ix.codes + (u64)row * ix.row_stride, s_q, ix.dim, lane);
+        else dotf = (float)int_row_dot_group0<ENG, CH>(qreg, ix.codes + (u64)row * ix.row_stride, ix.nchunks, lig, grp, GL); // integer dot `as f32` (RNE)
         bool bad;
-        sim_out = cosine_or_dot(metric, (float)acc, qmag, ix.mags[row], bad); // integer dot `as f32` (RNE)
+        sim_out = cosine_or_dot(metric, dotf, qmag, ix.mags[row], bad);
         return !bad;
     };
 
@@ -174,7 +194,9 @@ __global__ __launch_bounds__(64) void walk_lat_kernel(const IndexDev ix, const W
             __builtin_amdgcn_wave_barrier();
 
             // ---- 3. similarities of every candidate: 4 rows per pass, PBL passes in flight, no lane ever masked off ----------
-            spec_row_dots<ENG, CH, GL, PBL>(s_cl, s_spec, T, qreg, ix, qmag, lig, grp);
+            if constexpr (ENG == ENG_F32) spec_f32_dots<PBF>(s_cl, s_spec, T, s_q, ix, qmag, lane);
+            else if constexpr (ENG == ENG_F16) spec_f16_dots<(int)LAT_F16_TILE_ROWS, (int)LAT_F16_TILE_DIMS>(s_cl, s_spec, T, s_q, s_tile, ix, qmag, lane);
+            else spec_row_dots<ENG, CH, GL, PBL>(s_cl, s_spec, T, qreg, ix, qmag, lig, grp);
             if (PREFETCH_ADJ) {
 #pragma unroll
                 for (int i = 0; i < 2 * LAL; i++) warm ^= wv[i];
@@ -257,13 +279,11 @@ __global__ __launch_bounds__(64) void walk_lat_kernel(const IndexDev ix, const W
     }
 }
 
-size_t walk_lat_smem_bytes(const IndexDev &ix, u32 ef) {
-    return (size_t)LAL * 64 * 8 * 2 + (size_t)ef * 8 + (size_t)walk_mmax(ix) * 8 + 16;
-}
+static_assert(LAL == 4, "walk_lat_lds_bytes (walk_plan.h) sizes the window arrays for four entries");
 
 template <int ENG, int CH>
 hipError_t launch_lat_r(const IndexDev &ix, const WalkArgs &wa, u32 la, hipStream_t st) {
-    const size_t smem = walk_lat_smem_bytes(ix, wa.ef);
+    const size_t smem = walk_lat_lds_bytes(ENG, ix.dim, wa.ef, walk_mmax(ix));
     dim3 grid(wa.B), block(64);
     const bool warm = tune_or(TUNE_WALK_LAT_WARM, 1) != 0; // experiments: 0 = off
     if (warm) {
@@ -299,9 +319,16 @@ hipError_t launch_walk_lat(int eng, const IndexDev &ix, const WalkArgs &wa, hipS
     u32 la = la_env ? la_env : 4u;
     if (la > (u32)LAL) la = LAL;
     const u32 ch = (ix.nchunks + GL - 1) / GL;
-    if (eng == ENG_U8) return launch_lat_ch<ENG_U8>(ix, wa, ch, la, st);
-    if (eng == ENG_Q2) return launch_lat_ch<ENG_Q2>(ix, wa, ch, la, st);
-    return hipErrorInvalidValue;
+    switch (eng) {
+    case ENG_U8: return launch_lat_ch<ENG_U8>(ix, wa, ch, la, st);
+    case ENG_Q2: return launch_lat_ch<ENG_Q2>(ix, wa, ch, la, st);
+    case ENG_Q1: return launch_lat_ch<ENG_Q1>(ix, wa, ch, la, st);
+    case ENG_Q3: return launch_lat_ch<ENG_Q3>(ix, wa, ch, la, st);
+    // float rows hold no chunks (one instantiation each); above the width the LDS was sized for a launch is an error, not a fall-back
+    case ENG_F32: return ix.dim <= WALK_LAT_FLOAT_MAX_DIM ? launch_lat_r<ENG_F32, 1>(ix, wa, la, st) : hipErrorInvalidValue;
+    case ENG_F16: return ix.dim <= WALK_LAT_FLOAT_MAX_DIM ? launch_lat_r<ENG_F16, 1>(ix, wa, la, st) : hipErrorInvalidValue;
+    default: return hipErrorInvalidValue;
+    }
 }
 
 } // namespace cosdev

@@ -19,8 +19,9 @@
 //         computes its own position (binary search + a count over the round's winners) and is scattered into the other pool buffer.
 //         The sequential kernels' `rank < limit` test only ever rejects keys that can never be popped, so the plain merge is
 //         equivalent.
-// Four workgroup barriers per round.  Integer engines ENG_U8 / ENG_Q2 with <= 64 chunks per row, ef <= 256, reference visited
-// filter — the launches the one-wave latency kernel takes; launch_walk picks this one up to cos_index_set_latency_waves' size.
+// Four workgroup barriers per round.  The launches the one-wave latency kernel takes — integer codes of <= 64 chunks per row, f32 /
+// f16 rows of <= WALK_LAT_FLOAT_MAX_DIM dimensions (the float blocks of walk_common.h, every wave on its own candidates and, f16,
+// its own row tile), ef <= 256, reference visited filter; walk_plan.h picks this one up to cos_index_set_latency_waves' size.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -28,6 +29,7 @@
 #include "engine_types.h"
 #include "tuning.h"
 #include "walk_common.h"
+#include "walk_plan.h"
 
 using namespace cosdev;
 
@@ -36,6 +38,7 @@ namespace {
 constexpr int NW = 4;   // waves per query
 constexpr int GL4 = LAT_ROW_LANES; // lanes per code row (4 rows per wave pass)
 constexpr int PBL4 = 8; // passes in flight before the dots are consumed (32 rows per wave)
+constexpr int PBF4 = 4; // f32 rows: passes of 8 rows side by side (32 rows per wave)
 constexpr u32 FREE = 0xFFFFFFFFu;
 
 template <int ENG, int CH, int R, int E>
@@ -50,6 +53,9 @@ __global__ __launch_bounds__(256) void walk_lat4_kernel(const IndexDev ix, const
     const u32 Mmax = walk_mmax(ix);
     u64 *s_pool, *s_res, *s_win, *s_cl, *s_spec;
     u32 *s_vis, *s_first, *s_flag, *s_misc;
+    constexpr bool FLOAT_ENG = ENG == ENG_F32 || ENG == ENG_F16; // ordered f32 chains instead of integer chunk dots
+    float *s_q = nullptr;   // float engines: the query as f32
+    u32 *my_tile = nullptr; // f16: this wave's row tile (spec_f16_dots)
     {
         unsigned char *p = smem_raw;
         s_pool = (u64 *)p;  p += (size_t)2 * CAP * 8;           // sorted (descending) pool, double-buffered
@@ -60,7 +66,11 @@ __global__ __launch_bounds__(256) void walk_lat4_kernel(const IndexDev ix, const
         s_first = (u32 *)p; p += (size_t)64 * Mmax * 4;         // per filter bit: smallest rank (entry * 64 + slot) claiming it this round
         s_vis = (u32 *)p;   p += (size_t)2 * Mmax * 4;          // visited filter words
         s_flag = (u32 *)p;  p += (size_t)LA * 4;                // per entry: stale | fail << 1 | winners << 8
-        s_misc = (u32 *)p;                                      // [0] level entry hand-over, [1] status
+        s_misc = (u32 *)p;      p += 16;                        // [0] level entry hand-over, [1] status
+        if constexpr (FLOAT_ENG) { // (walk_lat4_lds_bytes, walk_plan.h)
+            s_q = (float *)(smem_raw + (((u32)(p - smem_raw) + 15u) & ~15u));
+            my_tile = (u32 *)((unsigned char *)s_q + lat_float_query_bytes(ENG, ix.dim)) + (size_t)wave * (lat_f16_tile_bytes(LAT4_F16_TILE_ROWS, LAT4_F16_TILE_DIMS) / 4u);
+        }
     }
     u64 *my_cl = s_cl + (size_t)wave * E * 64, *my_spec = s_spec + (size_t)wave * E * 64;
 
@@ -76,10 +86,14 @@ __global__ __launch_bounds__(256) void walk_lat4_kernel(const IndexDev ix, const
     const int grp = lane / GL4;
     const u64 lt_mask = (1ull << lane) - 1ull;
     uint4 qreg[CH];
+    if constexpr (FLOAT_ENG) {
+        stage_float_query<ENG, 256>(s_q, qcode, ix, tid); // read behind the first level's barrier
+    } else {
 #pragma unroll
-    for (int c = 0; c < CH; c++) {
-        const u32 chunk = (u32)lig + (u32)c * (u32)GL4;
-        qreg[c] = chunk < ix.nchunks ? *(const uint4 *)(qcode + (u64)chunk * 16) : make_uint4(0, 0, 0, 0);
+        for (int c = 0; c < CH; c++) {
+            const u32 chunk = (u32)lig + (u32)c * (u32)GL4;
+            qreg[c] = chunk < ix.nchunks ? *(const uint4 *)(qcode + (u64)chunk * 16) : make_uint4(0, 0, 0, 0);
+        }
     }
 
     for (u32 i = tid; i < 64u * Mmax; i += 256) s_first[i] = FREE;
@@ -88,11 +102,13 @@ __global__ __launch_bounds__(256) void walk_lat4_kernel(const IndexDev ix, const
     int32_t status = COS_OK;
     u32 entry = ix.lv[L].root_idx;
 
-    // similarity of ONE row, computed by lane group 0 of the calling wave; result in every lane of that wave
+    // similarity of ONE row, computed by lane group 0 of the calling wave (float rows: by the wave); result in every lane of that wave
     auto single_distance = [&](u32 row, float &sim_out) -> bool {
-        const u32 acc = int_row_dot_group0<ENG, CH>(qreg, ix.codes + (u64)row * ix.row_stride, ix.nchunks, lig, grp, GL4);
+        float dotf;
+        if constexpr (FLOAT_ENG) dotf = float_row_dot_wave<ENG>(ix.codes + (u64)row * ix.row_stride, s_q, ix.dim, lane);
+        else dotf = (float)int_row_dot_group0<ENG, CH>(qreg, ix.codes + (u64)row * ix.row_stride, ix.nchunks, lig, grp, GL4); // integer dot `as f32` (RNE)
         bool bad;
-        sim_out = cosine_or_dot(metric, (float)acc, qmag, uniform_f32(ix.mags[row]), bad); // integer dot `as f32` (RNE)
+        sim_out = cosine_or_dot(metric, dotf, qmag, uniform_f32(ix.mags[row]), bad);
         return !bad;
     };
 
@@ -190,7 +206,9 @@ __global__ __launch_bounds__(256) void walk_lat4_kernel(const IndexDev ix, const
                 T = 0; // nothing left for the row loop below
             }
             // similarities of this wave's candidates: 4 rows per pass, PBL4 passes in flight, no lane ever masked off
-            spec_row_dots<ENG, CH, GL4, PBL4>(my_cl, my_spec, T, qreg, ix, qmag, lig, grp);
+            if constexpr (ENG == ENG_F32) spec_f32_dots<PBF4>(my_cl, my_spec, T, s_q, ix, qmag, lane);
+            else if constexpr (ENG == ENG_F16) spec_f16_dots<(int)LAT4_F16_TILE_ROWS, (int)LAT4_F16_TILE_DIMS>(my_cl, my_spec, T, s_q, my_tile, ix, qmag, lane);
+            else spec_row_dots<ENG, CH, GL4, PBL4>(my_cl, my_spec, T, qreg, ix, qmag, lig, grp);
             __syncthreads(); // B1: every claim of the round is in s_first (and this wave's similarities are in my_spec)
 
             // ---- B. winners: first occurrence per filter bit in (entry, slot) order; stale / fail flags per entry ----------------------
@@ -350,18 +368,14 @@ __global__ __launch_bounds__(256) void walk_lat4_kernel(const IndexDev ix, const
     }
 }
 
-template <int E>
-size_t walk_lat4_smem_bytes(const IndexDev &ix, u32 ef, u32 cap) {
-    const u32 Mmax = walk_mmax(ix);
-    const size_t la = (size_t)NW * E;
-    return (size_t)2 * cap * 8 + (size_t)ef * 8 + la * 64 * 8 + (size_t)NW * E * 64 * 8 * 2 + (size_t)64 * Mmax * 4 + (size_t)2 * Mmax * 4 + la * 4 + 16;
-}
+static_assert(NW == 4, "walk_lat4_lds_bytes (walk_plan.h) sizes the per-wave arrays for four waves");
 
 template <int ENG, int CH, int E>
 hipError_t launch_lat4_r(const IndexDev &ix, const WalkArgs &wa, hipStream_t st) {
     dim3 grid(wa.B), block(256);
-    if (wa.ef <= 64) hipLaunchKernelGGL((walk_lat4_kernel<ENG, CH, 1, E>), grid, block, walk_lat4_smem_bytes<E>(ix, wa.ef, 64), st, ix, wa);
-    else hipLaunchKernelGGL((walk_lat4_kernel<ENG, CH, 4, E>), grid, block, walk_lat4_smem_bytes<E>(ix, wa.ef, 256), st, ix, wa);
+    const u32 Mmax = walk_mmax(ix);
+    if (wa.ef <= 64) hipLaunchKernelGGL((walk_lat4_kernel<ENG, CH, 1, E>), grid, block, walk_lat4_lds_bytes(ENG, ix.dim, wa.ef, 64, Mmax, E), st, ix, wa);
+    else hipLaunchKernelGGL((walk_lat4_kernel<ENG, CH, 4, E>), grid, block, walk_lat4_lds_bytes(ENG, ix.dim, wa.ef, 256, Mmax, E), st, ix, wa);
     return hipGetLastError();
 }
 
@@ -392,7 +406,15 @@ hipError_t launch_walk_lat4(int eng, const IndexDev &ix, const WalkArgs &wa, hip
         if (eng == ENG_U8) return launch_lat4_ch<ENG_U8, 2>(ix, wa, ch, st);
         if (eng == ENG_Q2) return launch_lat4_ch<ENG_Q2, 2>(ix, wa, ch, st);
     }
-    return hipErrorInvalidValue;
+    // binary / octal codes and float rows: the four-entry window only (the eight-entry one is an experiment on u8 / quaternary codes)
+    switch (eng) {
+    case ENG_Q1: return launch_lat4_ch<ENG_Q1, 1>(ix, wa, ch, st);
+    case ENG_Q3: return launch_lat4_ch<ENG_Q3, 1>(ix, wa, ch, st);
+    // float rows hold no chunks (one instantiation each); above the width the LDS was sized for a launch is an error, not a fall-back
+    case ENG_F32: return ix.dim <= WALK_LAT_FLOAT_MAX_DIM ? launch_lat4_r<ENG_F32, 1, 1>(ix, wa, st) : hipErrorInvalidValue;
+    case ENG_F16: return ix.dim <= WALK_LAT_FLOAT_MAX_DIM ? launch_lat4_r<ENG_F16, 1, 1>(ix, wa, st) : hipErrorInvalidValue;
+    default: return hipErrorInvalidValue;
+    }
 }
 
 } // namespace cosdev

@@ -130,6 +130,177 @@ __device__ __forceinline__ void spec_row_dots(const u64 *cl, u64 *spec, u32 T, c
     }
 }
 
+// ---- float rows in the latency kernels ----------------------------------------------------------------------------------------------
+// f32 and f16 rows are reference-order f32 chains (dot_engines.h: f32_oct_dot, f16_lane_dot), so the lanes of a row cannot reduce in
+// any order like spec_row_dots' integer lanes.  The query lies in LDS as f32, staged once per query by the NT threads that share it:
+// the padded f32 row itself, or the f16 code widened (exact) — what walk_kernel holds in WalkSmem::qf.
+template <int ENG, int NT>
+__device__ __forceinline__ void stage_float_query(float *q_lds, const uint8_t *qcode, const IndexDev &ix, int tid) {
+    if constexpr (ENG == ENG_F16) {
+        for (u32 i = (u32)tid; i < ix.dim; i += NT) q_lds[i] = __half2float(((const __half *)qcode)[i]);
+    } else {
+        for (u32 i = (u32)tid; i < (u32)(ix.row_stride / 4); i += NT) q_lds[i] = ((const float *)qcode)[i];
+    }
+}
+// ONE row (a level's start node) by the calling wave; the dot in every lane
+template <int ENG>
+__device__ __forceinline__ float float_row_dot_wave(const uint8_t *row_ptr, const float *q_lds, u32 dim, int lane) {
+    float d;
+    if constexpr (ENG == ENG_F16) d = f16_lane_dot(row_ptr, q_lds, dim);
+    else d = f32_oct_dot((const float *)row_ptr, q_lds, dim, lane & 7);
+    return __uint_as_float(readlane_u32(__float_as_uint(d), 0));
+}
+
+// f32 rows, NP wave passes at once: eight lanes per row (8 rows per pass), lane c owning chain c of dot_product_f32_simd — element
+// 8s + c at step s — exactly as f32_oct_dot does, but for NP rows per lane group side by side: a batch of U steps is NP * U
+// independent dword loads in flight per lane (32 at NP = 4) against ONE LDS read of the query per step, and the NP chains
+// interleave instead of waiting on each other.  Same chains, same tree ((s0+s1)+(s2+s3))+((s4+s5)+(s6+s7)), same unfused tail
+// (run by all eight lanes of the group on the same values; its first lane parks the key).
+template <int NP>
+__device__ __forceinline__ void spec_f32_block(const u64 *cl, u64 *spec, u32 b0, u32 T, const float *q_lds, const IndexDev &ix, float qmag, int c, int grp) {
+    constexpr int U = 8;
+    const float *rp[NP];
+    float a[NP], pmag[NP];
+    u32 ppos[NP], prow[NP];
+#pragma unroll
+    for (int p = 0; p < NP; p++) { // the candidates' rows first: one LDS round trip for the whole block
+        const u32 my = b0 + (u32)(p * 8 + grp);
+        const bool v = my < T;
+        const u64 e = cl[v ? my : b0]; // a lane group without a candidate re-reads the block's first row (dropped)
+        prow[p] = (u32)e;
+        ppos[p] = v ? (u32)(e >> 32) : 0xFFFFFFFFu;
+    }
+#pragma unroll
+    for (int p = 0; p < NP; p++) {
+        pmag[p] = ix.mags[prow[p]];
+        rp[p] = (const float *)(ix.codes + (u64)prow[p] * ix.row_stride) + c;
+        a[p] = 0.f;
+    }
+    const float *qp = q_lds + c;
+    const u32 steps = ix.dim >> 3;
+    u32 s = 0;
+    for (; s + U <= steps; s += U) {
+        float y[NP][U];
+#pragma unroll
+        for (int p = 0; p < NP; p++)
+#pragma unroll
+            for (int u = 0; u < U; u++) y[p][u] = rp[p][8 * (s + u)];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const float q = qp[8 * (s + u)];
+#pragma unroll
+            for (int p = 0; p < NP; p++) a[p] = __fmaf_rn(q, y[p][u], a[p]);
+        }
+    }
+    for (; s < steps; s++) {
+        const float q = qp[8 * s];
+#pragma unroll
+        for (int p = 0; p < NP; p++) a[p] = __fmaf_rn(q, rp[p][8 * s], a[p]);
+    }
+#pragma unroll
+    for (int p = 0; p < NP; p++) {
+        float t = __fadd_rn(a[p], __shfl_xor(a[p], 1, 64)); // s0+s1 | s2+s3 | s4+s5 | s6+s7
+        t = __fadd_rn(t, __shfl_xor(t, 2, 64));             // (s0+s1)+(s2+s3) | (s4+s5)+(s6+s7)
+        float r = __fadd_rn(t, __shfl_xor(t, 4, 64));       // low half + high half
+        const float *row = rp[p] - c;
+        for (u32 i = steps * 8; i < ix.dim; i++) r = __fadd_rn(r, __fmul_rn(q_lds[i], row[i])); // scalar tail, non-fused
+        bool bad;
+        const float sim = cosine_or_dot(ix.metric, r, qmag, pmag[p], bad);
+        if (c == 0 && ppos[p] != 0xFFFFFFFFu) spec[ppos[p]] = (u64)metric_key(ix.metric, sim) | (bad ? (1ull << 32) : 0ull);
+    }
+}
+// the T compacted candidates cl[] over f32 rows, parked like spec_row_dots': blocks of 8 * PB rows, the last one as narrow as it is
+template <int PB>
+__device__ __forceinline__ void spec_f32_dots(const u64 *cl, u64 *spec, u32 T, const float *q_lds, const IndexDev &ix, float qmag, int lane) {
+    static_assert(PB == 4, "the dispatch below is written for four passes");
+    const int c = lane & 7, grp = lane >> 3;
+    for (u32 b0 = 0; b0 < T; b0 += 8 * PB) {
+        const u32 np = (T - b0 + 7u) / 8u; // wave-uniform
+        if (np >= 4u) spec_f32_block<4>(cl, spec, b0, T, q_lds, ix, qmag, c, grp);
+        else if (np == 3u) spec_f32_block<3>(cl, spec, b0, T, q_lds, ix, qmag, c, grp);
+        else if (np == 2u) spec_f32_block<2>(cl, spec, b0, T, q_lds, ix, qmag, c, grp);
+        else spec_f32_block<1>(cl, spec, b0, T, q_lds, ix, qmag, c, grp);
+    }
+}
+
+// f16 rows: dot_product_f16 is ONE chain of unfused f32(a) * f32(b) per row, folded from -0.0 — the additions of a row belong to one
+// lane, so lane r chains candidate row r and a wave chains up to RT (<= 64) rows at once.  The rows do not come in lane by lane (64
+// uncoalesced streams): the WAVE fetches a tile of TD dimensions of every candidate row with 16-byte loads, TD / 8 lanes side by
+// side on a row and all loads of the tile in flight, and parks it in LDS — tile[row][TD / 2 + 1 words]: the odd row stride puts
+// word j of the 64 rows in 64 different banks — where every lane then runs its row's chain against the query (a broadcast read).
+// The loads of tile t + 1 are issued before the chain over tile t and wait in registers: the register file is the second buffer.
+// A load past the row's last 16 bytes re-reads those instead (no lane masked off; the chain stops at `dim`), rows past the block's
+// last candidate are neither fetched nor parked (their lanes chain whatever the tile holds, dropped).
+template <int RT, int TD>
+__device__ __forceinline__ void spec_f16_dots(const u64 *cl, u64 *spec, u32 T, const float *q_lds, u32 *tile, const IndexDev &ix, float qmag, int lane) {
+    constexpr int RW = TD / 2 + 1;   // row stride of the tile in words (odd)
+    constexpr int LPR = TD / 8;      // lanes side by side on a row: 16 bytes each
+    constexpr int RPL = 64 / LPR;    // rows per load instruction
+    constexpr int NL = RT / RPL;     // load instructions per tile
+    static_assert(RT <= 64 && 64 % RT == 0 && TD % 8 == 0 && 64 % LPR == 0 && RT % RPL == 0 && (RW & 1) == 1, "tile shape");
+    const int lir = lane % LPR, rgrp = lane / LPR;
+    const u32 dim = ix.dim, ntiles = (dim + TD - 1) / TD;
+    const u32 last16 = (u32)ix.row_stride - 16u;
+    const u32 *my_row = tile + (u32)(lane % RT) * RW;
+    for (u32 b0 = 0; b0 < T; b0 += RT) {
+        const u32 nrows = T - b0 < (u32)RT ? T - b0 : (u32)RT; // wave-uniform
+        const bool mine = (u32)lane < nrows;
+        const u64 e_mine = cl[b0 + (mine ? (u32)lane : 0u)];
+        const float pmag = ix.mags[(u32)e_mine];
+        u32 prow[NL];
+#pragma unroll
+        for (int k = 0; k < NL; k++) {
+            const u32 rr = (u32)(k * RPL + rgrp);
+            prow[k] = (u32)cl[b0 + (rr < nrows ? rr : 0u)];
+        }
+        uint4 buf[NL];
+        auto fetch = [&](u32 t) {
+            u32 off = t * (u32)(TD * 2) + (u32)lir * 16u;
+            off = off < last16 ? off : last16;
+#pragma unroll
+            for (int k = 0; k < NL; k++) {
+                if ((u32)(k * RPL) >= nrows) break; // wave-uniform
+                buf[k] = *(const uint4 *)(ix.codes + (u64)prow[k] * ix.row_stride + off);
+            }
+        };
+        fetch(0);
+        float acc = -0.0f; // <f32 as Sum> folds from -0.0
+        for (u32 t = 0; t < ntiles; t++) {
+            __builtin_amdgcn_wave_barrier(); // the chain over tile t - 1 has read it
+#pragma unroll
+            for (int k = 0; k < NL; k++) {
+                if ((u32)(k * RPL) >= nrows) break; // wave-uniform
+                u32 *w = tile + (u32)(k * RPL + rgrp) * RW + (u32)lir * 4u;
+                w[0] = buf[k].x; w[1] = buf[k].y; w[2] = buf[k].z; w[3] = buf[k].w;
+            }
+            if (t + 1u < ntiles) fetch(t + 1u);
+            __builtin_amdgcn_wave_barrier();
+            const float *q = q_lds + t * (u32)TD;
+            const u32 n = dim - t * (u32)TD < (u32)TD ? dim - t * (u32)TD : (u32)TD;
+            u32 j = 0;
+            for (; j + 8 <= n; j += 8) {
+                const float4 q0 = *(const float4 *)(q + j), q1 = *(const float4 *)(q + j + 4);
+                const u32 w0 = my_row[j / 2], w1 = my_row[j / 2 + 1], w2 = my_row[j / 2 + 2], w3 = my_row[j / 2 + 3];
+                acc = __fadd_rn(acc, __fmul_rn(__half2float(__ushort_as_half((unsigned short)(w0 & 0xFFFFu))), q0.x));
+                acc = __fadd_rn(acc, __fmul_rn(__half2float(__ushort_as_half((unsigned short)(w0 >> 16))), q0.y));
+                acc = __fadd_rn(acc, __fmul_rn(__half2float(__ushort_as_half((unsigned short)(w1 & 0xFFFFu))), q0.z));
+                acc = __fadd_rn(acc, __fmul_rn(__half2float(__ushort_as_half((unsigned short)(w1 >> 16))), q0.w));
+                acc = __fadd_rn(acc, __fmul_rn(__half2float(__ushort_as_half((unsigned short)(w2 & 0xFFFFu))), q1.x));
+                acc = __fadd_rn(acc, __fmul_rn(__half2float(__ushort_as_half((unsigned short)(w2 >> 16))), q1.y));
+                acc = __fadd_rn(acc, __fmul_rn(__half2float(__ushort_as_half((unsigned short)(w3 & 0xFFFFu))), q1.z));
+                acc = __fadd_rn(acc, __fmul_rn(__half2float(__ushort_as_half((unsigned short)(w3 >> 16))), q1.w));
+            }
+            for (; j < n; j++) {
+                const u32 w = my_row[j / 2];
+                acc = __fadd_rn(acc, __fmul_rn(__half2float(__ushort_as_half((unsigned short)((j & 1u) ? w >> 16 : w & 0xFFFFu))), q[j]));
+            }
+        }
+        bool bad;
+        const float sim = cosine_or_dot(ix.metric, acc, qmag, pmag, bad);
+        if (mine) spec[(u32)(e_mine >> 32)] = (u64)metric_key(ix.metric, sim) | (bad ? (1ull << 32) : 0ull);
+    }
+}
+
 // ---- level epilogue --------------------------------------------------------------------------------------------------------------
 // the popped (key, node) list, R entries per lane, sorted descending (vector_store.rs:1194-1201)
 template <int R>

@@ -99,6 +99,10 @@ WalkPlanIn cos_walk_plan_in(const cos_index *ix, u32 B, u32 ef) {
     in.chain = true;
     in.lat_max_B = knob_or(TUNE_WALK_LAT, ix->lat_max_B);
     in.lat4_max_B = knob_or(TUNE_WALK_LAT4, ix->lat4_max_B);
+    // binary / octal codes and float rows answer to the same two settings through a predicate of their own (walk_latency_storages_domain)
+    in.dim = ix->p.dim;
+    in.lat_st_max_B = in.lat_max_B;
+    in.lat4_st_max_B = in.lat4_max_B;
     in.small_table_tk = tune_or(TUNE_WALK_SMALL_TABLE_TK, 1) != 0;
     in.adj_mag_mode = (u32)tune_or(TUNE_WALK_ADJ_MAG, 1);
     in.table_min_B = cos_walk_table_min_B(ix);

@@ -26,6 +26,7 @@ namespace cosdev {
 
 constexpr int WALK_PLAN_MAX_LEVELS = 16;                    // = MAX_LEVELS (device_common.h; engine_internal.h asserts these four)
 constexpr int WALK_PLAN_ENG_U8 = 0, WALK_PLAN_ENG_Q2 = 1;   // = ENG_U8, ENG_Q2
+constexpr int WALK_PLAN_ENG_F32 = 2, WALK_PLAN_ENG_F16 = 3, WALK_PLAN_ENG_Q1 = 4, WALK_PLAN_ENG_Q3 = 5; // = ENG_F32, ENG_F16, ENG_Q1, ENG_Q3
 constexpr uint32_t WALK_PLAN_FAST_MAX_EF = 1024u;           // = WALK_FAST_MAX_EF (engine_types.h)
 
 // The norms beside the adjacency (LevelDev::adj_mag), invalidated by a root replaced on a live graph, are refilled by the first launch
@@ -70,6 +71,11 @@ struct WalkPlanIn {
     // the throughput kernel reads the nested table, one column per vector (WalkPlan::table_nested, table_nested.h)
     uint32_t table_nested_mode;     // tuning knob walk_table_nested, resolved: 0 never | 1, 2 wherever the handle has the nested operand (the knob's two
                                     // values differ in which graphs get one: walk_operands.hip ensure_nested_table)
+    // binary / octal codes and f16 / f32 rows in the latency kernels (walk_latency_storages_domain): the row width in dimensions and
+    // the two launch-size limits as they hold for THOSE storages — the handle's lat_max_B / lat4_max_B, whose default per engine is
+    // walk_latency_default_max_B; 0 = never, which is also what a caller that knows nothing of these fields gets
+    uint32_t dim;
+    uint32_t lat_st_max_B, lat4_st_max_B;
 };
 
 // What preparation left, for the second step: no table operand for this graph and rule, no room for a workspace's table (out of
@@ -158,6 +164,67 @@ inline bool walk_latency_domain(const WalkPlanIn &in, uint32_t max_B) {
     return true;
 }
 
+// ---- binary / octal codes and f16 / f32 rows in the latency kernels ----------------------------------------------------------------
+// walk_latency_domain's answer for these four storages is recorded (tests/golden/walk_plan_cases.txt: the throughput kernel), so they
+// are routed by a predicate of their own over limits of their own (WalkPlanIn::lat_st_max_B / lat4_st_max_B).
+//   * binary / octal: the integer block of the latency kernels (spec_row_dots), rows of <= 64 chunks like u8 / quaternary: 8192
+//     binary dimensions, 2048 octal ones;
+//   * f16 / f32: the float blocks (walk_common.h: spec_f32_dots, spec_f16_dots).  The query lies in LDS as f32 beside the pools, the
+//     filter, the claim table and — f16 — the row tiles: rows of at most WALK_LAT_FLOAT_MAX_DIM dimensions (8 KB of query) keep the
+//     four-wave kernel's workgroup under 64 KB at ef 256 (walk_lat4_lds_bytes; tests/cxx/walk_lat_storages_check.cpp).
+constexpr uint32_t WALK_LAT_FLOAT_MAX_DIM = 2048u;
+inline bool walk_latency_storages_domain(const WalkPlanIn &in, uint32_t max_B) {
+    if (max_B == 0 || in.B > max_B) return false;
+    if (in.visited_mode != 0) return false;
+    if (in.ef == 0 || in.ef > 256) return false;
+    if (in.eng == WALK_PLAN_ENG_Q1 || in.eng == WALK_PLAN_ENG_Q3) return in.nchunks != 0 && in.nchunks <= 64u; // rows of <= 4 passes of LAT_ROW_LANES chunks
+    if (in.eng == WALK_PLAN_ENG_F32 || in.eng == WALK_PLAN_ENG_F16) return in.dim != 0 && in.dim <= WALK_LAT_FLOAT_MAX_DIM;
+    return false;
+}
+// A handle's default launch-size limits (cos_index_set_latency_mode / _waves replace them): u8 / quaternary as ever; the four storages
+// above take a latency kernel by default only where it was measured faster than the throughput kernel.
+inline uint32_t walk_latency_default_max_B(int eng, bool four_waves, uint32_t dflt_u8) {
+    if (eng == WALK_PLAN_ENG_U8 || eng == WALK_PLAN_ENG_Q2) return dflt_u8;
+    // 1M x 768, launches of 256 and of 2048 queries at ef 64 and 256 against the throughput kernel (DESIGN.md 4.1.4 has the table): a
+    // kernel is on up to the largest measured launch at which it won at BOTH beam widths by more than the spread of either
+    switch (eng) {
+    case WALK_PLAN_ENG_F16:
+    case WALK_PLAN_ENG_Q3: return four_waves ? 256u : 2048u; // four waves win one client batch, one wave wins both sizes
+    case WALK_PLAN_ENG_F32: return 256u;                     // both win one client batch; at 2048 queries and ef 64 neither does
+    default: return 0u;                                      // binary: the throughput kernel wins at ef 64 — reachable through the setters only
+    }
+}
+
+// The f16 row tile of the latency kernels: `rows` candidate rows x `dims` dimensions of f16, two per word, every row padded by one
+// word — the row stride in words is ODD, so lane r reading word j of row r hits bank (r * stride + j) mod 64 (or mod 32): all
+// different.  One tile per wave.
+constexpr uint32_t LAT_F16_TILE_ROWS = 64u, LAT_F16_TILE_DIMS = 128u;   // one-wave kernel: 16.3 KB
+constexpr uint32_t LAT4_F16_TILE_ROWS = 32u, LAT4_F16_TILE_DIMS = 64u;  // four-wave kernel: 4.1 KB per wave
+constexpr uint32_t lat_f16_row_words(uint32_t dims) { return dims / 2u + 1u; }
+constexpr uint32_t lat_f16_tile_bytes(uint32_t rows, uint32_t dims) { return rows * lat_f16_row_words(dims) * 4u; }
+// the query as f32 (f32 rows: the padded row itself; f16: the code widened), 16-byte padded; 0 for the integer engines
+constexpr uint32_t lat_float_query_bytes(int eng, uint32_t dim) {
+    return eng == WALK_PLAN_ENG_F32 || eng == WALK_PLAN_ENG_F16 ? (dim * 4u + 15u) & ~15u : 0u;
+}
+// what the float engines add behind a latency kernel's own LDS (16-byte aligned there): query, then the f16 tiles of its waves
+inline uint32_t lat_float_lds_bytes(int eng, uint32_t dim, uint32_t waves) {
+    const uint32_t tile = waves == 1u ? lat_f16_tile_bytes(LAT_F16_TILE_ROWS, LAT_F16_TILE_DIMS) : lat_f16_tile_bytes(LAT4_F16_TILE_ROWS, LAT4_F16_TILE_DIMS);
+    return lat_float_query_bytes(eng, dim) + (eng == WALK_PLAN_ENG_F16 ? waves * tile : 0u);
+}
+// dynamic LDS of walk_lat_kernel: parked similarities | compacted candidates (4 window entries x 64 slots each) | popped list |
+// filter | float part
+inline uint32_t walk_lat_lds_bytes(int eng, uint32_t dim, uint32_t ef, uint32_t mmax) {
+    const uint32_t own = 4u * 64u * 8u * 2u + ef * 8u + mmax * 8u;
+    return ((own + 15u) & ~15u) + lat_float_lds_bytes(eng, dim, 1u) + 16u;
+}
+// ... of walk_lat4_kernel (window of 4 * E entries, pool of `cap` keys): pools | popped list | winners | candidates | similarities |
+// claim table | filter | flags | hand-over words | float part
+inline uint32_t walk_lat4_lds_bytes(int eng, uint32_t dim, uint32_t ef, uint32_t cap, uint32_t mmax, uint32_t E) {
+    const uint32_t la = 4u * E;
+    const uint32_t own = 2u * cap * 8u + ef * 8u + la * 64u * 8u * 3u + 64u * mmax * 4u + 2u * mmax * 4u + la * 4u + 16u;
+    return ((own + 15u) & ~15u) + lat_float_lds_bytes(eng, dim, 4u) + 16u;
+}
+
 // Which fast kernel walks an unsplit launch inside their domain (!walk_general_needed).
 // table_available: the launch can have a level table.  With the table (u8 codes) the throughput kernel beats the one-wave latency
 // kernel at every launch size (1M x 768, ms per launch at ef 64 / 256: 256 queries 0.77 / 2.20 against 0.99 / 2.37; 1 024 queries
@@ -168,11 +235,11 @@ inline bool walk_latency_domain(const WalkPlanIn &in, uint32_t max_B) {
 inline WalkKernel walk_fast_kernel(const WalkPlanIn &in, bool table_available) {
     if (in.no_self_seed) return WalkKernel::Throughput; // the unseeded filter exists in the throughput kernel only
     // the four-wave kernel's s_first is sized 64 * Mmax words: keep the workgroup's LDS small
-    const bool lat4 = walk_latency_domain(in, in.lat4_max_B) && std::max(in.M[0], in.M[in.num_layers]) <= 64u;
+    const bool lat4 = (walk_latency_domain(in, in.lat4_max_B) || walk_latency_storages_domain(in, in.lat4_st_max_B)) && std::max(in.M[0], in.M[in.num_layers]) <= 64u;
     if (table_available && in.small_table_tk && in.eng == WALK_PLAN_ENG_U8)
         return in.ef > 128u && lat4 ? WalkKernel::Lat4 : WalkKernel::Throughput; // (round 6: the 128-key pool + ranked merge moved the crossover from ef 64 to 128)
     if (lat4) return WalkKernel::Lat4;
-    if (walk_latency_domain(in, in.lat_max_B)) return WalkKernel::Lat1;
+    if (walk_latency_domain(in, in.lat_max_B) || walk_latency_storages_domain(in, in.lat_st_max_B)) return WalkKernel::Lat1;
     return WalkKernel::Throughput;
 }
 

@@ -330,6 +330,14 @@ class HNSWIndex:
         check(_lib.lib().cos_index_last_walk_split(self._h, C.c_void_p(stream), C.byref(st)))
         return st
 
+    WALK_KERNELS = ("general", "throughput", "latency", "latency_waves")  # COS_WALK_KERNEL_* (include/cosdata_hip.h)
+
+    def last_walk_kernel(self, stream: int = 0) -> str:
+        """The kernel that walked the last batch on `stream`: one of WALK_KERNELS."""
+        k = C.c_uint32()
+        check(_lib.lib().cos_index_last_walk_kernel(self._h, C.c_void_p(stream), C.byref(k)))
+        return self.WALK_KERNELS[k.value]
+
     def last_pair_stats(self, stream: int = 0) -> CosPairStats:
         """The pair walk of the last batch on `stream` (tuning knob walk_pair): cache hits, code rows fetched, cache entries per query;
         all zero when the launch did not walk in pairs."""

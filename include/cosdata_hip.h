@@ -245,6 +245,18 @@ int32_t cos_index_set_latency_mode(cos_index *ix, uint32_t max_queries);
  * per batch at ef 256); up to ef 64 the throughput kernel with the table is faster (0.77 vs 0.82 ms). */
 #define COS_LATENCY_WAVES_DEFAULT_MAX_B 512u
 int32_t cos_index_set_latency_waves(cos_index *ix, uint32_t max_queries);
+/* Both latency kernels also walk binary and octal codes (rows of at most 64 chunks: 8192 / 2048 dimensions) and f16 / f32 rows of
+ * at most 2048 dimensions (reference-order f32 chains against the query in LDS; f16 rows come in as LDS tiles that the wave loads
+ * together).  Same results bit for bit.  For these four storages the DEFAULTS of the two settings follow what was measured against
+ * the throughput kernel on 1M x 768: f16 and octal 2048 / 256 (latency mode / four waves), f32 256 / 256, binary
+ * 0 / 0 (never: the throughput kernel wins at ef 64); a value set through the two calls above applies to them as it does to u8 /
+ * quaternary codes.  Wider rows keep the kernel they had. */
+/* Which kernel walked the last completed batch on `stream` (the launch plan's choice, which is what was launched). */
+#define COS_WALK_KERNEL_GENERAL 0u       /* walk_general_kernel: rows of more than 64 slots, ef above 1024, code rows of more than 64 chunks */
+#define COS_WALK_KERNEL_THROUGHPUT 1u    /* walk_kernel */
+#define COS_WALK_KERNEL_LATENCY 2u       /* walk_lat_kernel: one wave per query (cos_index_set_latency_mode) */
+#define COS_WALK_KERNEL_LATENCY_WAVES 3u /* walk_lat4_kernel: four waves per query (cos_index_set_latency_waves) */
+int32_t cos_index_last_walk_kernel(cos_index *ix, void *stream, uint32_t *out_kernel);
 /* Locality order of big launches — at least min_queries queries (default COS_WALK_ORDER_DEFAULT_MIN_B; 0 = never).  Not a reference
  * interface: the reference answers each query on its own rayon task (indexes/mod.rs:260-272) and has no launch whose order could
  * matter; on the device the order decides which rows a query finds in cache.  Such a launch walks in two steps of the same kernel:
