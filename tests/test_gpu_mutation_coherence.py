@@ -191,6 +191,8 @@ def _plan_checker(ix, p, counts):
         else:
             assert (lmin, cols) == (0, 0)                       # no level table for this storage: every plan with one is refused
             want = False
+            if visited == 0 and ef <= 256 and B <= LAT:         # f16 / f32 rows, binary / octal codes: the latency kernels under _features_on's limits
+                assert ix.last_walk_kernel() == ("latency_waves" if B <= LAT4 else "latency"), (B, ef)
         if want:
             assert lmin >= 1 and cols == sum(counts[lmin:]) and [ix.level_count(l) for l in range(len(counts))] == counts, (lmin, cols, counts)
         assert (sp.table_level_min, sp.table_cols) == ((lmin, cols) if want else (0, 0)), (B, ef, visited)
@@ -333,7 +335,10 @@ def scenarios():
         if name not in made:
             made[name] = {"full": lambda: M.make(), "short": lambda: M.make(M.SHORT_HISTORY),
                           "q2": lambda: M.make(M.SHORT_HISTORY, dim=128, storage=O.STORAGE_SUBBYTE, resolution=2),
-                          "f16": lambda: M.make(M.SHORT_HISTORY, storage=O.STORAGE_F16)}[name]()
+                          "f16": lambda: M.make(M.SHORT_HISTORY, storage=O.STORAGE_F16),
+                          "f32": lambda: M.make(M.SHORT_HISTORY, storage=O.STORAGE_F32),
+                          "q1": lambda: M.make(M.SHORT_HISTORY, dim=128, storage=O.STORAGE_SUBBYTE, resolution=1),
+                          "q3": lambda: M.make(M.SHORT_HISTORY, storage=O.STORAGE_SUBBYTE, resolution=3)}[name]()
         return made[name]
     yield get
     for tl in _timelines.values():
@@ -399,14 +404,16 @@ def _small_timeline(case, sc):
 
 
 @pytest.mark.parametrize("point", range(len(M.SHORT_HISTORY) + 1))
-@pytest.mark.parametrize("case", ["q2", "f16", "uploaded", "borrowed"])
+@pytest.mark.parametrize("case", ["q2", "f16", "f32", "q1", "q3", "uploaded", "borrowed"])
 def test_warm_handle_follows_the_short_history(scenarios, case, point):
     """append 700, delete 40, append 300 with matrix items 1, 2 (1024 and 4096 queries) and 5.
     q2: quaternary codes x 128 — the level table exists from 128 dims and the workspace's digit rows (engine.hip get_workspace, qdig)
     belong to it; f16: no table — the row path and the refused table plans, the locality order alone (builder.hip:401);
+    f32 x 96, q1 (binary codes) x 128, q3 (octal codes) x 96: like f16, and with it the storages whose 1- / 4-query launches take the
+    four-wave latency kernel and whose 16-query launch the one-wave kernel across every graph change (_plan_checker asserts both);
     uploaded: a graph that came by upload, searched, then cos_index_restore_link_state (builder.hip:359-360) and the history;
     borrowed: the caller's grown table (builder.hip:421-422, 435) — the rerank and the brute force read it."""
-    sc = scenarios(case if case in ("q2", "f16") else "short")
+    sc = scenarios(case if case in ("q2", "f16", "f32", "q1", "q3") else "short")
     _check_at(case, point, len(M.SHORT_HISTORY), lambda: _small_timeline(case, sc))
 
 

@@ -80,12 +80,17 @@ def test_every_big_step_moves_the_answers(full):
     assert (counts[7][0] + 31) // 32 > (counts[3][0] + 31) // 32 > (counts[0][0] + 31) // 32
 
 
-@pytest.mark.parametrize("name,kw", [("short", {}), ("q2", dict(dim=128, storage=O.STORAGE_SUBBYTE, resolution=2)), ("f16", dict(storage=O.STORAGE_F16))])
+@pytest.mark.parametrize("name,kw", [("short", {}), ("q2", dict(dim=128, storage=O.STORAGE_SUBBYTE, resolution=2)), ("f16", dict(storage=O.STORAGE_F16)),
+                                     ("f32", dict(storage=O.STORAGE_F32)), ("q1", dict(dim=128, storage=O.STORAGE_SUBBYTE, resolution=1)),
+                                     ("q3", dict(storage=O.STORAGE_SUBBYTE, resolution=3))])
 def test_the_short_history_moves_the_answers_too(name, kw):
     """append 700, delete 40, append 300.  Measured shares (Q[:512] / Qv):
         u8 x 96      1.000 / 1.000   0.115 / 0.250   0.953 / 0.950
         q2 x 128     0.771 / 0.775   0.133 / 0.400   0.871 / 0.875
         f16 x 96     0.869 / 0.850   0.127 / 1.000   0.533 / 0.550
+        f32 x 96     0.869 / 0.850   0.127 / 1.000   0.533 / 0.550
+        q1 x 128     0.959 / 0.950   0.340 / 0.950   0.736 / 0.825
+        q3 x 96      0.953 / 0.875   0.402 / 0.825   0.730 / 0.625
     floors = half of the smallest measured value of a column: 0.38 for the first append, 0.12 of Qv for the delete, 0.26 for the last append"""
     sc = M.make(M.SHORT_HISTORY, **kw)
     assert sc.n_at == [3000, 3700, 3700, 4000] and np.bincount(sc.victim_levels).tolist() == [20, 12, 6, 2]
