@@ -412,12 +412,14 @@ struct cos_index {
     // ... and the smallest of them (one client batch) give every query four waves (kernels_walk_lat4.hip); 0 = never
     u32 lat4_max_B = COS_LATENCY_WAVES_DEFAULT_MAX_B;
     struct FlatWs *flat_ws = nullptr; // cos_flat_search_batch's buffers (kernels_flat.hip), created on first use under `mu`
+    struct FlatF16Ws *flat_f16_ws = nullptr; // cos_flat_search_f16_batch's (kernels_flat_f16.hip), likewise; released with flat_ws
     cos_brute_stats brute_last = {(u32)sizeof(cos_brute_stats), 0u, 0u, 0u}; // the last brute force of this handle (cos_index_last_brute_stats)
 };
 
 
 struct FlatWs;
-void cos_flat_ws_release(cos_index *ix);
+void cos_flat_ws_release(cos_index *ix);     // both exhaustive scans' workspaces
+void cos_flat_f16_ws_release(cos_index *ix); // (kernels_flat_f16.hip; cos_flat_ws_release calls it)
 namespace cosdev {
 // The single-index searches as one shard of a shard set runs them (shardset.hip): the operator's own kernels, refusals and zero-norm rule;
 // the packed record [ids B*k | scores B*k | counts B] is left in d_record (device memory on the index's device, B * (2k + 1) words) and is

@@ -71,6 +71,41 @@ constexpr uint32_t CODE_MAX_TOP_K = 204, CODE_POOL_FACTOR = 5;
 inline int32_t check_code_top_k(uint32_t top_k) { return top_k == 0 || top_k > CODE_MAX_TOP_K ? UNIMPLEMENTED : OK; }
 inline uint32_t code_pool(uint32_t top_k) { return flat_pool_width(CODE_POOL_FACTOR * top_k); }
 
+// ---- f16 scan (kernels_flat_f16.hip, cos_flat_search_f16_batch): the code scan's finalisation over HalfPrecisionFP rows ----
+// The N = 5 * top_k rerank candidates are the best rows by the reference's f16 dot, an order-dependent f32 chain; the f16 MFMA only
+// generates candidates, so the pool holds P >= 2 N of them and is trusted only under the margin rule below.  top_k in [1, 102]
+// (P <= 1024).
+constexpr uint32_t F16_MAX_TOP_K = 102, F16_POOL_FACTOR = 2;
+inline int32_t check_f16_top_k(uint32_t top_k) { return top_k == 0 ? INVALID : top_k > F16_MAX_TOP_K ? UNIMPLEMENTED : OK; }
+inline uint32_t f16_pool(uint32_t top_k) { return flat_pool_width(F16_POOL_FACTOR * CODE_POOL_FACTOR * top_k); }
+// cos_flat_f16_opts::exact_mode: which queries take the exact path
+enum F16Exact : uint32_t { F16_EXACT_NEVER = 0, F16_EXACT_BY_RULE = 1, F16_EXACT_ALWAYS = 2 };
+// When the pool that the MFMA's ranking cut can be trusted: the argument of brute_margin_safe with N in the place of k — with
+// |g - e| <= bound for every row (g the MFMA's score, e the reference-order one), a FULL pool whose N-th score lies more than
+// 2 * bound above its P-th holds N rows that beat every row outside it in the exact order too, strictly: no outside row can even tie
+// into the cut.  A pool that is not full holds every row.
+//
+// The bound.  u = 2^-24.  The operands are the SAME f16 values on both sides and the product of two f16 values is exact in f32
+// (11-bit significands, exponents far inside f32's), so the two dots differ only in how they add dim exact products; both scores then
+// divide by the SAME f32 denominator D = fl(|q| * |x|) (the norms the handle keeps: of the original f32 vectors, scalar.rs:41).
+//   MFMA dot       v_mfma_f32_32x32x16_f16 (x8 for a k tail of at most 8), f32 accumulation: dim exact products added in an order
+//                  the ISA guide does not state — for dim correctly rounded additions in ANY order |err| <= dim u S, S = sum |x_i q_i|
+//   reference dot  dot_product_f16 (dot_product.rs:13-19; oracle coso_dot_f16, dot_engines.h f16_lane_dot): ONE sequential chain from
+//                  -0.0, acc = acc + f32(a_i) * f32(b_i), no SIMD, no fused step: dim additions of exact products, |err| <= dim u S
+//   two quotients  one rounding each, u |score| <= u S / D each
+// |g - e| <= (2 dim + 2) u S / D.  S <= |x^| |q^| (Cauchy-Schwarz, x^ the f16 row) and |x^_i| <= (1 + 2^-11) |x_i| in f16's normal
+// range, so S / D <= ~1.001 — given round-to-nearest at every step and D equal to the true |x| |q|.  Neither is documented or exact:
+// the MFMA's internal additions may truncate (2 u a step, not u), the handle's norms are sequential f32 sums (relative error up to
+// dim u / 2 each) and f16 subnormals round with an absolute error.  The bound therefore takes TWICE the figure, as brute_margin_bound
+// does, and the rule twice the bound: 1024 dims give a bound of 2.4e-4 and ask for a gap of 4.9e-4 between the N-th and the P-th score.
+constexpr double f16_margin_bound(uint32_t dim) { return 2.0 * (double)(2 * (uint64_t)dim + 2) * (1.0 / 16777216.0); }
+constexpr bool f16_margin_safe(float nth, float pth, uint32_t dim, bool pool_full) {
+    if (!pool_full) return true;
+    const double a = (double)nth, b = (double)pth;
+    if (!(a - a == 0.0) || !(b - b == 0.0)) return false; // NaN or inf
+    return a - b > 2.0 * f16_margin_bound(dim);
+}
+
 // ---- which kernel scores a fused chunk of the code scan ----
 enum class ScanKernel {
     RESIDENT_PLANES, // query-resident scan of bit-plane codes (kernels_scan.hip flat_scan_q2_*)
@@ -168,6 +203,11 @@ inline Scan brute_scan(uint32_t n, uint32_t B, uint32_t k, bool knob_unfused) {
 // code scan: the score matrix is sized per attempt by its first chunk
 inline Scan code_scan(uint32_t n, uint32_t B, uint32_t top_k, bool knob_unfused, ScanKernel kernel) {
     return Scan{n, B, code_pool(top_k), FLAT_SEED, code_unfused_chunk(B, n), fused_cap(kernel), !knob_unfused && n > FLAT_SEED};
+}
+// f16 scan: the code scan's schedule at this call's P; the scan kernel is query-resident (persistent), so a fused chunk takes what the
+// growth rule allows.  `unfused`: an exact pass (every chunk's score matrix comes from the reference-order kernel)
+inline Scan f16_scan(uint32_t n, uint32_t B, uint32_t top_k, bool unfused) {
+    return Scan{n, B, f16_pool(top_k), FLAT_SEED, code_unfused_chunk(B, n), RESIDENT_CHUNK_CAP, !unfused && n > FLAT_SEED};
 }
 
 } // namespace flat_plan

@@ -77,6 +77,42 @@ hipError_t launch_flat_rerank_wide(u32 R, bool brute, const float *Q, u64 q_stri
                                    const float *xmags, u32 dim, const u64 *d_pool, u32 ncand_max, u32 k, u32 id_base, u32 *out_ids, float *out_scores,
                                    u32 *out_counts, hipStream_t st);
 
+// ---- what the exhaustive scans share between their launches (kernels_flat.hip defines the functions; kernels_flat_f16.hip uses them too) ----
+// the device buffers that the chunks of an attempt go through, sized by the caller from its plan
+struct ScanBufs {
+    float *scores;    // [B][s_stride]: the score matrix of an unfused chunk
+    u64 s_stride;
+    u64 *part;        // [B][S][P]: its selection's partial lists
+    u64 *pool, *thr;  // [B][P] survivors, [B] their P-th best
+    u64 *app;         // [B][app_cap]: what a fused chunk lets through, appcnt[B] of them
+    u32 *appcnt, *overflow; // *overflow |= 1 by a fold that found a counter above app_cap
+    ScanMask sm;
+    FusedOut fused_out(const flat_plan::Scan &plan, const uint8_t *qdigits) const { return FusedOut{thr, app, appcnt, plan.app_cap(), qdigits, sm}; }
+};
+// a scored chunk into the pools: a fused chunk's append buffer, or the selection over an unfused chunk's score matrix, at every pool width
+hipError_t fold_chunk(const flat_plan::Scan &plan, const flat_plan::Chunk &c, const ScanBufs &b, hipStream_t st);
+// the chunks of one attempt, in order: score(chunk) enqueues the kernel that scores it, then the chunk is folded.  The first failed HIP
+// call ends it: nothing further is started on the stream
+template <class Score>
+hipError_t run_chunks(const flat_plan::Scan &plan, int attempt, const ScanBufs &b, hipStream_t st, Score &&score) {
+    flat_plan::Schedule sched = plan.schedule(attempt);
+    flat_plan::Chunk c;
+    hipError_t e = hipSuccess;
+    while (e == hipSuccess && sched.next(c)) {
+        e = score(c);
+        if (e == hipSuccess) e = fold_chunk(plan, c, b, st);
+    }
+    return e;
+}
+// one launch in front of an attempt: the survivor pools, the thresholds and the append counters cleared, *overflow = 0
+hipError_t launch_flat_reset(u64 *pool, u64 n_pool, u64 *thr, u32 *appcnt, u32 B, u32 *overflow, hipStream_t st);
+// *flag |= 1 when one of n floats is zero (cosine's zero-norm screen, without copying the norms to the host)
+hipError_t launch_any_zero(const float *v, u32 n, u32 *flag, hipStream_t st);
+// the code scans' last step at every pool width (R = P / 64): exact rerank of the best min(have, ncand_max) keys of pool[B][P] (sorted by
+// quantized score) against the raw rows -> top k, out_counts
+hipError_t launch_flat_rerank(u32 R, const float *Q, const float *qraw_mags, u32 B, const float *X, const float *xmags, u32 dim, const u64 *d_pool,
+                              u32 ncand_max, u32 k, u32 id_base, u32 *out_ids, float *out_scores, u32 *out_counts, hipStream_t st);
+
 // the walk's level table as a query-resident GEMM (kernels_scan.hip): tab[q][c] = (f32) exact integer dot; u8 or quaternary codes.
 // Its workgroups claim work items from *queue (zeroed before the first launch over it); wgs = workgroups of this launch, 0 = full width
 bool level_table_areg_supported(int eng, u64 row_stride);

@@ -730,20 +730,10 @@ static_assert(fp::U8 == ENG_U8 && fp::Q2 == ENG_Q2 && fp::Q1 == ENG_Q1 && fp::Q3
 static_assert(BN == 128 && CN == 128, "flat_plan.h unfused_chunk: whole tiles of 128 candidates");
 static_assert(SEL == 64, "flat_plan.h flat_pool_width: the narrowest pool");
 
-// the device buffers that the chunks of an attempt go through, sized by the caller from its plan
-struct ScanBufs {
-    float *scores;    // [B][s_stride]: the score matrix of an unfused chunk
-    u64 s_stride;
-    u64 *part;        // [B][S][P]: its selection's partial lists
-    u64 *pool, *thr;  // [B][P] survivors, [B] their P-th best
-    u64 *app;         // [B][app_cap]: what a fused chunk lets through, appcnt[B] of them
-    u32 *appcnt, *overflow; // *overflow |= 1 by a fold that found a counter above app_cap
-    ScanMask sm;
-    FusedOut fused_out(const fp::Scan &plan, const uint8_t *qdigits) const { return FusedOut{thr, app, appcnt, plan.app_cap(), qdigits, sm}; }
-};
+} // namespace
 
-// a scored chunk into the pools: a fused chunk's append buffer, or the selection over an unfused chunk's score matrix; 64-key pools on the
-// kernels above, wider ones on kernels_flat_wide.hip
+namespace cosdev {
+// a scored chunk into the pools (flat_scan.h): 64-key pools on the kernels above, wider ones on kernels_flat_wide.hip
 hipError_t fold_chunk(const fp::Scan &plan, const fp::Chunk &c, const ScanBufs &b, hipStream_t st) {
     const u32 B = plan.B, R = plan.P / SEL;
     if (c.fused && R == 1) {
@@ -755,20 +745,24 @@ hipError_t fold_chunk(const fp::Scan &plan, const fp::Chunk &c, const ScanBufs &
     if (R == 1) return launch_select(b.scores, b.s_stride, B, c.n0, c.nc, b.part, S, b.pool, st, b.thr, b.sm);
     return launch_flat_select_wide(R, b.scores, b.s_stride, B, c.n0, c.nc, b.part, S, b.pool, b.thr, st, b.sm);
 }
-
-// the chunks of one attempt, in order: score(chunk) enqueues the kernel that scores it, then the chunk is folded.  The first failed HIP
-// call ends it: nothing further is started on the stream
-template <class Score>
-hipError_t run_chunks(const fp::Scan &plan, int attempt, const ScanBufs &b, hipStream_t st, Score &&score) {
-    fp::Schedule sched = plan.schedule(attempt);
-    fp::Chunk c;
-    hipError_t e = hipSuccess;
-    while (e == hipSuccess && sched.next(c)) {
-        e = score(c);
-        if (e == hipSuccess) e = fold_chunk(plan, c, b, st);
-    }
-    return e;
+hipError_t launch_flat_reset(u64 *pool, u64 n_pool, u64 *thr, u32 *appcnt, u32 B, u32 *overflow, hipStream_t st) {
+    hipLaunchKernelGGL(flat_reset_kernel, dim3(64), dim3(256), 0, st, pool, n_pool, thr, appcnt, B, overflow);
+    return hipGetLastError();
 }
+hipError_t launch_any_zero(const float *v, u32 n, u32 *flag, hipStream_t st) {
+    hipLaunchKernelGGL(any_zero_kernel, dim3(n > 16384u ? 1024u : 64u), dim3(256), 0, st, v, n, flag);
+    return hipGetLastError();
+}
+hipError_t launch_flat_rerank(u32 R, const float *Q, const float *qraw_mags, u32 B, const float *X, const float *xmags, u32 dim, const u64 *d_pool,
+                              u32 ncand_max, u32 k, u32 id_base, u32 *out_ids, float *out_scores, u32 *out_counts, hipStream_t st) {
+    if (R != 1) return launch_flat_rerank_wide(R, false, Q, (u64)dim, qraw_mags, B, X, (u64)dim, xmags, dim, d_pool, ncand_max, k, id_base, out_ids, out_scores, out_counts, st);
+    hipLaunchKernelGGL(flat_rerank_top5k, dim3(B), dim3(64), staged_query_bytes(dim), st, Q, (u64)dim, qraw_mags, B, X, (u64)dim, xmags, dim, d_pool, ncand_max, k,
+                       id_base, out_ids, out_scores, out_counts);
+    return hipGetLastError();
+}
+} // namespace cosdev
+
+namespace {
 
 // flat_gemm_f32<VEC, FUSED, MASKED>.  An unfused chunk has no masked form: its selection applies the mask
 using GemmF32Kernel = decltype(&flat_gemm_f32<true, false>);
@@ -1085,12 +1079,14 @@ struct FlatWs {
 void cos_flat_ws_release(cos_index *ix) { // cos_index_destroy, and every upload that replaces the stored vectors
     delete ix->flat_ws;
     ix->flat_ws = nullptr;
+    cos_flat_f16_ws_release(ix);
 }
 
 // ------------------------------------------------------------------------------------------------
 // cos_flat_search_batch: exhaustive search over the index's quantized codes (i8 MFMA) + exact rerank of the best 5k.
 // u8 and the three bit-plane storages (binary, quaternary, octal): integer dots, exact in any order.  f16 / f32 codes are refused: their
-// reference dots are order-dependent f32 chains that an MFMA cannot reproduce, so the candidate set could not be exact.
+// reference dots are order-dependent f32 chains that an MFMA cannot reproduce, so the candidate set could not be exact.  (f16 rows have a
+// call of their own with a margin rule and an exact path: kernels_flat_f16.hip, cos_flat_search_f16_batch.)
 // ------------------------------------------------------------------------------------------------
 // cos_flat_search_batch (mask == nullptr) and cos_flat_search_masked_batch; with d_record (device memory on the index's device,
 // B * (2 top_k + 1) words) the shard set's form: the same launches and read-backs, and the first 2 B top_k + B words of the packed output
@@ -1249,14 +1245,8 @@ static int32_t flat_search_run(cos_index *ix, const float *queries, uint32_t B, 
         if (e == hipSuccess) e = W->out.grow(out_words);
         if (e == hipSuccess) e = W->h_out.grow(out_words);
         if (e != hipSuccess) break;
-        if (R == 1) {
-            hipLaunchKernelGGL(flat_rerank_top5k, dim3(B), dim3(64), staged_query_bytes(dim), st, d_q, (u64)dim, d_qrm, B, ix->d_raw, (u64)dim,
-                               ix->d_raw_mags, dim, d_pool, 5 * top_k, top_k, ix->p.id_base, d_oi, d_os, d_oc);
-        } else {
-            e = launch_flat_rerank_wide(R, false, d_q, (u64)dim, d_qrm, B, ix->d_raw, (u64)dim, ix->d_raw_mags, dim, d_pool, 5 * top_k, top_k, ix->p.id_base,
-                                        d_oi, d_os, d_oc, st);
-            if (e != hipSuccess) break;
-        }
+        e = launch_flat_rerank(R, d_q, d_qrm, B, ix->d_raw, ix->d_raw_mags, dim, d_pool, 5 * top_k, top_k, ix->p.id_base, d_oi, d_os, d_oc, st);
+        if (e != hipSuccess) break;
         hipLaunchKernelGGL(flat_pack_out_kernel, dim3((u32)((std::max<size_t>(nk, B) + 255) / 256)), dim3(256), 0, st, d_oi, d_os, d_oc, d_zero, B, top_k, W->out.p);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(W->h_out, W->out.p, out_words * 4, hipMemcpyDeviceToHost, st);

@@ -490,6 +490,23 @@ class HNSWIndex:
         check(_lib.lib().cos_flat_search_batch(self._h, _p(q), B, top_k, _p(ids), _p(scores), _p(counts), C.byref(st)))
         return (ids, scores, counts, st) if with_stats else (ids, scores, counts)
 
+    def flat_search_f16(self, queries, top_k: int, exact_mode: int = 1, with_stats: bool = False):
+        """flat_search's answer over a HalfPrecisionFP index with the cosine metric (cos_flat_search_f16_batch): an f16 MFMA GEMM
+        generates a pool of at least 2 * 5 * top_k candidates per query, the pool is scored again in the reference's order and its
+        best 5 * top_k are reranked exactly.  exact_mode: 1 (default) scores every row in the reference's order for the queries whose
+        pool fails the margin rule (near-copies around the cut), 2 for every query, 0 never (the one mode that may differ from the
+        reference, on such corpora).  top_k in [1, 102] (status 4 above); other storages raise status 1, the dot-product metric
+        status 4, a zero-norm query or stored vector status 2.  -> ids, scores, counts (+ CosFlatF16Stats)."""
+        q = self._queries(queries)
+        B = q.shape[0]
+        ids = np.full((B, top_k), 0xFFFFFFFF, np.uint32)
+        scores = np.zeros((B, top_k), np.float32)
+        counts = np.zeros(B, np.uint32)
+        opts = _lib.CosFlatF16Opts(struct_size=C.sizeof(_lib.CosFlatF16Opts), exact_mode=exact_mode)
+        st = _lib.CosFlatF16Stats(struct_size=C.sizeof(_lib.CosFlatF16Stats))
+        check(_lib.lib().cos_flat_search_f16_batch(self._h, _p(q), B, top_k, C.byref(opts), _p(ids), _p(scores), _p(counts), C.byref(st)))
+        return (ids, scores, counts, st) if with_stats else (ids, scores, counts)
+
     def bruteforce_topk(self, queries, k: int):
         """Exact cosine top-k over the raw vectors (f32 MFMA GEMM for candidates + reference-order re-score): the recall ground truth.
         k in [1, min(512, n)] (status 3, Invalid, outside); a query keeps the smallest pool of 64 .. 1024 survivors that holds 2k."""

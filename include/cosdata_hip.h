@@ -454,7 +454,7 @@ int32_t cos_index_last_brute_stats(cos_index *ix, cos_brute_stats *out);
  * Storages: UnsignedByte and SubByte of resolution 1 (binary), 2 (quaternary) and 3 (octal): their reference dots are integers, exact
  * in any summation order (dot_product_u8 / _binary / _quaternary / _octal), so the candidate set is the reference's bit for bit.
  * HalfPrecisionFP and FullPrecisionFP indexes: COS_ERR_UNIMPLEMENTED (their reference dots are order-dependent f32 chains; the handle
- * stays usable — cos_bruteforce_topk scans the raw rows of any index).  Cosine divides by the norms the quantizer keeps (SubByte: of the
+ * stays usable — cos_bruteforce_topk scans the raw rows of any index, cos_flat_search_f16_batch below serves HalfPrecisionFP rows).  Cosine divides by the norms the quantizer keeps (SubByte: of the
  * original vector), and a zero norm among the queries or the stored vectors is COS_ERR_CALCULATION for the call.
  * top_k in [1, 204]; above that COS_ERR_UNIMPLEMENTED (the handle stays usable).  A query keeps a pool of P
  * survivors, the smallest of 64, 128, 256, 512, 1024 with 5 * top_k <= P: top_k <= 12 runs the 64-key kernels,
@@ -472,6 +472,38 @@ typedef struct {
 } cos_flat_stats;
 int32_t cos_flat_search_batch(cos_index *ix, const float *queries, uint32_t B, uint32_t top_k, uint32_t *out_ids,
                               float *out_scores, uint32_t *out_counts, cos_flat_stats *stats /* optional */);
+
+/* cos_flat_search_batch's finalisation over a HalfPrecisionFP index (cosine): the ids, score bits and counts the reference's exhaustive
+ * mode gives — every row scored by dot_product_f16 (a sequential f32 chain) / (|q| * |x|), sorted (desc, larger id first), the best
+ * N = 5 * top_k reranked exactly in f32, top_k.  An f16 MFMA GEMM (f32 accumulation; the products of f16 values are exact, only the
+ * summation order differs from the reference's) generates a pool of P candidates per query, the smallest of 64 .. 1024 with 2 N <= P;
+ * the pool's rows are scored again in the reference's order and the best N of them go to the rerank.  The pool is trusted only where
+ * its P-th MFMA score lies more than twice a derived error bound under its N-th (cosdata_amd/csrc/flat_plan.h f16_margin_safe); a
+ * query that fails the rule — copies or scaled copies of one row around the cut — has EVERY row scored in the reference's order on
+ * the vector units instead (n * dim dependent additions for that query).  exact_mode 0 never takes that path (the one mode whose
+ * answer may differ from the reference's, on corpora with near-copies), 1 by the rule (default), 2 for every query.
+ * Host buffers; out_counts[q] = min(top_k, n).  Refusals, each checked before anything is enqueued, the handle stays usable:
+ *   COS_ERR_STORAGE_MISMATCH  any storage but COS_STORAGE_F16
+ *   COS_ERR_UNIMPLEMENTED     the dot-product metric (its error bound is not relative to 1), top_k > 102 (P would pass 1024)
+ *   COS_ERR_INVALID           top_k == 0, exact_mode > 2, a struct_size that is not the struct's size
+ *   COS_ERR_CALCULATION       a zero norm among the queries or the stored rows, for the call, as in cos_flat_search_batch
+ * Out of scope: row masks and the deleted set, the shard set, FullPrecisionFP storage (cos_bruteforce_topk scans f32 rows) and
+ * top_k above 102.  The workspace lives on the handle beside cos_flat_search_batch's, sized by each call's own P (8 P bytes of pool
+ * twice, the partial pools and the append buffer as there), and goes with it. */
+typedef struct cos_flat_f16_opts {
+    uint32_t struct_size; /* in: sizeof(cos_flat_f16_opts) */
+    uint32_t exact_mode;  /* 0 never, 1 by the margin rule (default), 2 every query */
+} cos_flat_f16_opts;
+typedef struct cos_flat_f16_stats {
+    uint32_t struct_size;   /* in: sizeof(cos_flat_f16_stats) */
+    uint32_t queries;       /* B of the call */
+    uint32_t exact_queries; /* queries answered by the exact path */
+    uint32_t pool;          /* P */
+    float gemm_ms;          /* summed HIP-event time of the first pass's scoring launches (the MFMA scan; exact_mode 2: the exact kernel) */
+    uint32_t gemm_launches;
+} cos_flat_f16_stats;
+int32_t cos_flat_search_f16_batch(cos_index *ix, const float *queries, uint32_t B, uint32_t top_k, const cos_flat_f16_opts *opts /* NULL = defaults */,
+                                  uint32_t *out_ids, float *out_scores, uint32_t *out_counts, cos_flat_f16_stats *stats /* optional */);
 
 /* The two exhaustive scans over a SUBSET of the rows: per-query allow-lists and / or the handle's deleted set.
  * Query q's live set is mask query_mask[q] AND NOT the deleted rows (COS_SCAN_SKIP_DELETED); its result is exactly what the unmasked
