@@ -106,6 +106,24 @@ constexpr bool f16_margin_safe(float nth, float pth, uint32_t dim, bool pool_ful
     return a - b > 2.0 * f16_margin_bound(dim);
 }
 
+// ---- masked f16 scan (kernels_flat_f16_masked.hip, cos_flat_search_f16_masked_batch): the same answer over each query's live rows ----
+// The scan streams row tiles of F16_TILE_ROWS rows for query blocks of F16_QUERY_BLOCK queries; a block walks the list of the tiles
+// that hold a row live for one of its queries.
+constexpr uint32_t F16_TILE_ROWS = 64, F16_QUERY_BLOCK = 128;
+constexpr uint32_t f16_tiles(uint32_t n) { return (n + F16_TILE_ROWS - 1) / F16_TILE_ROWS; }
+constexpr uint32_t f16_query_blocks(uint32_t B) { return (B + F16_QUERY_BLOCK - 1) / F16_QUERY_BLOCK; }
+// workspace of the tile lists: per query block room for every tile (a block whose masks are all ones), and its length
+constexpr uint64_t f16_tile_list_bytes(uint32_t n, uint32_t B) { return (uint64_t)f16_query_blocks(B) * ((uint64_t)f16_tiles(n) + 1) * 4; }
+// pool slots a query with `live` rows fills: its pool of P keys, or every live row where there are fewer — the rerank's N is clamped
+// the same way
+constexpr uint32_t f16_masked_pool(uint32_t P, uint32_t live) { return live < P ? live : P; }
+// A query with at most P live rows needs no margin test: no row was cut, its whole live set is in the pool and is re-scored in the
+// reference's order.  The plan says so from the live count — it is not left to an empty P-th key.
+constexpr bool f16_margin_skipped(uint32_t live, uint32_t P) { return live <= P; }
+constexpr bool f16_masked_margin_safe(float nth, float pth, uint32_t dim, uint32_t live, uint32_t P) {
+    return f16_margin_skipped(live, P) || f16_margin_safe(nth, pth, dim, true);
+}
+
 // ---- which kernel scores a fused chunk of the code scan ----
 enum class ScanKernel {
     RESIDENT_PLANES, // query-resident scan of bit-plane codes (kernels_scan.hip flat_scan_q2_*)

@@ -2,8 +2,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <vector>
+
 #include "engine_types.h"
 #include "flat_plan.h"
+
+struct cos_scan_mask; // include/cosdata_hip.h
 
 namespace cosdev {
 
@@ -29,8 +33,18 @@ __device__ __forceinline__ bool scan_live(const ScanMask &m, u32 q, u32 row) {
     else return ((m.bits[(u64)m.qmask[q] * m.words + (row >> 5)] >> (row & 31u)) & 1u) != 0u;
 }
 
+// a call's cos_scan_mask, checked on the host (kernels_flat.hip): what the masked calls upload
+struct MaskPlan {
+    bool masked = false;        // false: the unmasked call (mask == NULL, or no allow-list and no flag)
+    bool skip_deleted = false;
+    std::vector<u32> used;      // the caller's masks that some query names, ascending; empty = no allow-list (one all-ones mask)
+    std::vector<u32> qmask;     // [B] -> index into `used`
+};
+// COS_OK or the refusal.  Masks no query names are neither uploaded nor part of the zero-norm screen.
+int32_t scan_mask_plan(const cos_scan_mask *mask, u32 B, MaskPlan &mp);
+
 struct FusedOut {
-    const u64 *thr;   // [B] SEL-th best (key) so far; 0 = pool not full yet, everything passes
+    const u64 *thr;  // [B] SEL-th best (key) so far; 0 = pool not full yet, everything passes
     u64 *app;         // [B][cap]
     u32 *app_cnt;     // [B]
     u32 cap;

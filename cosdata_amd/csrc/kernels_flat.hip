@@ -665,15 +665,10 @@ __global__ __launch_bounds__(64) void flat_rerank_top5k(const float *__restrict_
     if (lane == 0) out_counts[q] = nout;
 }
 
-// ---- a call's cos_scan_mask: checked on the host, then one set of device buffers ----
-struct MaskPlan {
-    bool masked = false;        // false: the unmasked call (mask == NULL, or no allow-list and no flag)
-    bool skip_deleted = false;
-    std::vector<u32> used;      // the caller's masks that some query names, ascending; empty = no allow-list (one all-ones mask)
-    std::vector<u32> qmask;     // [B] -> index into `used`
-};
-// COS_OK or the refusal.  Masks no query names are neither uploaded nor part of the zero-norm screen.
-int32_t scan_mask_plan(const cos_scan_mask *mask, u32 B, MaskPlan &mp) {
+} // namespace
+
+// ---- a call's cos_scan_mask: checked on the host (MaskPlan, flat_scan.h), then one set of device buffers ----
+int32_t cosdev::scan_mask_plan(const cos_scan_mask *mask, u32 B, MaskPlan &mp) {
     if (!mask) return COS_OK;
     if (mask->struct_size != sizeof(cos_scan_mask)) return cos_fail(COS_ERR_INVALID, "cos_scan_mask::struct_size is %u, expected %zu", mask->struct_size, sizeof(cos_scan_mask));
     if (mask->flags & ~COS_SCAN_SKIP_DELETED) return cos_fail(COS_ERR_INVALID, "unknown cos_scan_mask::flags 0x%x", mask->flags);
@@ -700,6 +695,9 @@ int32_t scan_mask_plan(const cos_scan_mask *mask, u32 B, MaskPlan &mp) {
     mp.masked = true;
     return COS_OK;
 }
+
+namespace {
+
 struct MaskBufs { // grow-only, like the other buffers of a scan
     DevArr<u32> user, eff, uni, qmask;
 };
@@ -1100,7 +1098,8 @@ static int32_t flat_search_run(cos_index *ix, const float *queries, uint32_t B, 
     if (int32_t krc = fp::check_code_top_k(top_k)) return cos_fail(krc, "flat search keeps at most 1024 survivors (5 * top_k): top_k must be in [1, 204]");
     const bool planes = fp::bit_planes(ix->eng); // bit-plane storage: the operands are expanded to digits
     if (ix->eng != ENG_U8 && !planes)
-        return cos_fail(COS_ERR_UNIMPLEMENTED, "flat search over codes implements u8, binary, quaternary and octal storage");
+        return cos_fail(COS_ERR_UNIMPLEMENTED, "flat search over codes implements u8, binary, quaternary and octal storage "
+                                               "(HalfPrecisionFP rows: cos_flat_search_f16_batch, cos_flat_search_f16_masked_batch)");
     int32_t rc = cos_set_device(ix);
     if (rc) return rc;
     const u32 dim = ix->p.dim, n = ix->n;

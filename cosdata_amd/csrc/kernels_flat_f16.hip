@@ -16,7 +16,9 @@
 // whatever the instruction's internal order.  Rows are padded to 16 bytes (row_stride = (2 dim + 15) & ~15): a piece past dim is never
 // loaded, the piece that holds dim is masked, so the k tail is zero in LDS and in the fragments; a tail of at most 8 dims runs on
 // v_mfma_f32_32x32x8_f16 instead of a half-empty x16 step.
-// Masks, the deleted set, the shard set, f32 storage, the dot-product metric and top_k > 102 are not served (include/cosdata_hip.h).
+// Masks and the deleted set: kernels_flat_f16_masked.hip (cos_flat_search_f16_masked_batch), a scan kernel of its own over the live
+// tiles; flat_f16.h holds what the two share.  The shard set, f32 storage, the dot-product metric and top_k > 102 are not served
+// (include/cosdata_hip.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -26,51 +28,13 @@
 
 #include "engine_internal.h"
 #include "exact_rerank.h"
+#include "flat_f16.h"
 #include "flat_scan.h"
 
 using namespace cosdev;
 namespace fp = flat_plan;
 
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int F_ROWS = 64, F_PAN = 256;                 // stored rows per tile, dims per k panel
-constexpr int F_LDP = F_PAN * 2 + 16;                   // bytes per row of a panel in LDS: 528 = 132 dwords, conflict-free ds_read_b128
-constexpr int F_NP = F_ROWS * (F_PAN / 8) / 256;        // 16-byte pieces per thread and panel: 8
-constexpr size_t F16_SCAN_LDS = (size_t)2 * F_ROWS * F_LDP; // 67 584 B
-constexpr int F_MAX_NPAN = 4;                           // resident fragments: up to 1024 dims
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F &&f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-
-// the first `keep` halves of a piece survive, the rest become +0.0 (keep >= 2 * words: unchanged)
-__device__ __forceinline__ u32 keep_word(u32 w, int keep) { return keep >= 2 ? w : keep == 1 ? (w & 0xFFFFu) : 0u; }
-__device__ __forceinline__ i32x4 keep_halves(i32x4 v, int keep) {
-    v[0] = (int)keep_word((u32)v[0], keep);
-    v[1] = (int)keep_word((u32)v[1], keep - 2);
-    v[2] = (int)keep_word((u32)v[2], keep - 4);
-    v[3] = (int)keep_word((u32)v[3], keep - 6);
-    return v;
-}
-
-// (accumulators in VGPRs, fragments used straight from AccVGPRs: the translation unit is compiled with -mllvm -amdgpu-mfma-vgpr-form=1,
-// kernels_scan.hip areg_mfma has the story)
-__device__ __forceinline__ void mfma16(f32x16 &acc, const i32x4 &a, const i32x4 &b) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), acc, 0, 0, 0);
-}
-__device__ __forceinline__ void mfma8(f32x16 &acc, const i32x2 &a, const i32x2 &b) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x8f16(__builtin_bit_cast(f16x4, a), __builtin_bit_cast(f16x4, b), acc, 0, 0, 0);
-}
 
 // scores of rows [n0, n0 + n_chunk) against the B queries.  Grid (workgroups that stride over the row tiles, ceil(B / 128)).
 //   FUSED   the epilogue screens acc / |x| against the query's threshold * |q| and appends the survivors' keys (flat_gemm_f32's rule:
@@ -267,12 +231,6 @@ hipError_t launch_f16_scan(bool fused, u32 n_cus, hipStream_t st, const uint8_t 
 #undef F16_SCAN_ARGS
 }
 
-// the query's f16 code widened into LDS (exact): what f16_lane_dot multiplies the stored halves with
-__device__ __forceinline__ void stage_f16_query(float *qf, const uint8_t *__restrict__ qrow, u32 dim) {
-    for (u32 i = threadIdx.x; i < dim; i += blockDim.x) qf[i] = __half2float(((const __half *)qrow)[i]);
-    __syncthreads();
-}
-
 // flags[q] = 1 and *n_flagged += 1 where flat_plan.h f16_margin_safe says no: the pool (sorted descending, P keys) is full and its P-th
 // score is not more than twice the bound under its N-th.  One thread per query.
 __global__ void f16_margin_kernel(const u64 *__restrict__ pool_mem, u32 P, u32 B, u32 N, u32 dim, u32 *__restrict__ flags, u32 *__restrict__ n_flagged) {
@@ -307,7 +265,8 @@ __global__ __launch_bounds__(256) void f16_rescore(const uint8_t *__restrict__ q
     lds_bitonic_sort_desc<P>(keys);
     for (u32 c = threadIdx.x; c < P; c += 256) sorted[(u64)q * P + c] = keys[c];
 }
-hipError_t launch_f16_rescore(u32 P, const uint8_t *qh, u64 row_stride, const float *qmags, u32 B, const uint8_t *codes, const float *mags, u32 dim,
+} // namespace
+hipError_t cosdev::launch_f16_rescore(u32 P, const uint8_t *qh, u64 row_stride, const float *qmags, u32 B, const uint8_t *codes, const float *mags, u32 dim,
                               const u64 *pool, u64 *sorted, hipStream_t st) {
     const size_t smem = staged_query_bytes(dim) + (size_t)P * 8;
 #define F16_RESCORE(PP) case PP: hipLaunchKernelGGL(f16_rescore<PP>, dim3(B), dim3(256), smem, st, qh, row_stride, qmags, codes, mags, dim, pool, sorted); break
@@ -318,6 +277,7 @@ hipError_t launch_f16_rescore(u32 P, const uint8_t *qh, u64 row_stride, const fl
 #undef F16_RESCORE
     return hipGetLastError();
 }
+namespace {
 
 // The exact path's scores: scores[q][c] = the reference-order score of row n0 + c, the value f16_rescore ranks, so the selection over
 // this matrix keeps the exact top P.  One workgroup per (query, range of F16_EXACT_ROWS rows), one lane per row.
@@ -340,30 +300,11 @@ __global__ __launch_bounds__(256) void f16_exact_scores(const uint8_t *__restric
 
 } // namespace
 
-// Per-index workspace of cos_flat_search_f16_batch, beside FlatWs: grow-only, sized and indexed by each call's own P, released with it
-struct FlatF16Ws {
-    std::mutex mu; // the scan runs on the index's own stream: one call at a time
-    DevArr<float> q, qm, qrm, os, scores;
-    DevArr<uint8_t> qc;
-    DevArr<u32> flags /*[zero-norm, overflow, queries flagged]*/, appcnt, oi, oc, qflag;
-    DevArr<u64> pool, sorted, thr, app, part;
-    bool zn_valid = false, zn_zero = false; // "a stored vector has a zero norm" for the current rows
-    u32 zn_n = 0;
-    std::vector<hipEvent_t> evs;
-    hipError_t event(size_t i, hipEvent_t *out) {
-        while (evs.size() <= i) {
-            hipEvent_t ev = nullptr;
-            hipError_t e = hipEventCreate(&ev);
-            if (e != hipSuccess) return e;
-            evs.push_back(ev);
-        }
-        *out = evs[i];
-        return hipSuccess;
-    }
-    ~FlatF16Ws() {
-        for (hipEvent_t ev : evs) (void)hipEventDestroy(ev);
-    }
-};
+FlatF16Ws *cos_flat_f16_ws(cos_index *ix) {
+    std::lock_guard<std::mutex> g(ix->mu);
+    if (!ix->flat_f16_ws) ix->flat_f16_ws = new FlatF16Ws();
+    return ix->flat_f16_ws;
+}
 void cos_flat_f16_ws_release(cos_index *ix) {
     delete ix->flat_f16_ws;
     ix->flat_f16_ws = nullptr;
@@ -513,18 +454,18 @@ extern "C" int32_t cos_flat_search_f16_batch(cos_index *ix, const float *queries
     if (!ix || !queries || !out_ids || !out_scores || !out_counts || B == 0) return cos_fail(COS_ERR_INVALID, "bad argument");
     if (!ix->have_vectors) return cos_fail(COS_ERR_NOT_READY, "upload vectors first");
     if (opts && opts->struct_size != sizeof(cos_flat_f16_opts)) return cos_fail(COS_ERR_INVALID, "cos_flat_f16_opts::struct_size is %u, expected %zu", opts->struct_size, sizeof(cos_flat_f16_opts));
-    if (stats && stats->struct_size != sizeof(cos_flat_f16_stats)) return cos_fail(COS_ERR_INVALID, "cos_flat_f16_stats::struct_size is %u, expected %zu", stats->struct_size, sizeof(cos_flat_f16_stats));
+    if (stats && stats->struct_size != sizeof(cos_flat_f16_stats) && stats->struct_size != COS_FLAT_F16_STATS_SIZE_V1)
+        return cos_fail(COS_ERR_INVALID, "cos_flat_f16_stats::struct_size is %u, expected %zu (or %u)", stats->struct_size, sizeof(cos_flat_f16_stats), COS_FLAT_F16_STATS_SIZE_V1);
     const u32 mode = opts ? opts->exact_mode : (u32)fp::F16_EXACT_BY_RULE;
     if (mode > fp::F16_EXACT_ALWAYS) return cos_fail(COS_ERR_INVALID, "cos_flat_f16_opts::exact_mode is %u: 0, 1 or 2", mode);
     if (ix->eng != ENG_F16) return cos_fail(COS_ERR_STORAGE_MISMATCH, "cos_flat_search_f16_batch scans HalfPrecisionFP rows (cos_flat_search_batch: u8 and bit-plane codes)");
     if (ix->p.metric != COS_METRIC_COSINE) return cos_fail(COS_ERR_UNIMPLEMENTED, "cos_flat_search_f16_batch implements the cosine metric");
     if (int32_t krc = fp::check_f16_top_k(top_k)) return cos_fail(krc, "the f16 scan keeps at most 1024 survivors (2 * 5 * top_k): top_k must be in [1, 102]");
     if (int32_t rc = cos_set_device(ix)) return rc;
-    {
-        std::lock_guard<std::mutex> g(ix->mu);
-        if (!ix->flat_f16_ws) ix->flat_f16_ws = new FlatF16Ws();
-    }
-    FlatF16Ws *W = ix->flat_f16_ws;
+    FlatF16Ws *W = cos_flat_f16_ws(ix);
     std::lock_guard<std::mutex> wg(W->mu);
-    return f16_run(ix, W, queries, B, top_k, mode, false, out_ids, out_scores, out_counts, stats);
+    const int32_t rc = f16_run(ix, W, queries, B, top_k, mode, false, out_ids, out_scores, out_counts, stats);
+    if (rc == COS_OK && stats && stats->struct_size == sizeof(cos_flat_f16_stats)) // every tile, for every block of queries
+        stats->tiles_scanned = stats->tiles_total = fp::f16_tiles(ix->n) * fp::f16_query_blocks(B);
+    return rc;
 }

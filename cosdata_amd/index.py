@@ -567,6 +567,25 @@ class HNSWIndex:
         del keep
         return (ids, scores, counts, st) if with_stats else (ids, scores, counts)
 
+    def flat_search_f16_masked(self, queries, top_k: int, masks=None, query_mask=None, skip_deleted: bool = False, exact_mode: int = 1,
+                               with_stats: bool = False):
+        """flat_search_f16 over a subset of the rows (cos_flat_search_f16_masked_batch); masks as in flat_search_masked.  The result is
+        flat_search_f16's on an index holding only each query's live rows, with the original ids; counts[b] = min(top_k, live rows of
+        b), 0 for a query without one.  The scan skips the 64-row tiles without a live row, and the margin rule of exact_mode 1 sees
+        live rows only.  No mask at all is flat_search_f16.  -> ids, scores, counts (+ CosFlatF16Stats with tiles_scanned / tiles_total)."""
+        q = self._queries(queries)
+        B = q.shape[0]
+        sm, keep = self._scan_mask(masks, query_mask, skip_deleted, B)
+        ids = np.full((B, top_k), 0xFFFFFFFF, np.uint32)
+        scores = np.zeros((B, top_k), np.float32)
+        counts = np.zeros(B, np.uint32)
+        opts = _lib.CosFlatF16Opts(struct_size=C.sizeof(_lib.CosFlatF16Opts), exact_mode=exact_mode)
+        st = _lib.CosFlatF16Stats(struct_size=C.sizeof(_lib.CosFlatF16Stats))
+        check(_lib.lib().cos_flat_search_f16_masked_batch(self._h, _p(q), B, top_k, C.byref(sm) if sm is not None else None, C.byref(opts),
+                                                          _p(ids), _p(scores), _p(counts), C.byref(st)))
+        del keep
+        return (ids, scores, counts, st) if with_stats else (ids, scores, counts)
+
     def bruteforce_topk_masked(self, queries, k: int, masks=None, query_mask=None, skip_deleted: bool = False):
         """bruteforce_topk over a subset of the rows (cos_bruteforce_topk_masked); masks as in flat_search_masked.  -> ids, scores, counts:
         k may exceed a query's live rows, counts[b] = min(k, live rows of b) and the entries past it are unspecified."""

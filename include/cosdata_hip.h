@@ -487,9 +487,12 @@ int32_t cos_flat_search_batch(cos_index *ix, const float *queries, uint32_t B, u
  *   COS_ERR_UNIMPLEMENTED     the dot-product metric (its error bound is not relative to 1), top_k > 102 (P would pass 1024)
  *   COS_ERR_INVALID           top_k == 0, exact_mode > 2, a struct_size that is not the struct's size
  *   COS_ERR_CALCULATION       a zero norm among the queries or the stored rows, for the call, as in cos_flat_search_batch
- * Out of scope: row masks and the deleted set, the shard set, FullPrecisionFP storage (cos_bruteforce_topk scans f32 rows) and
- * top_k above 102.  The workspace lives on the handle beside cos_flat_search_batch's, sized by each call's own P (8 P bytes of pool
- * twice, the partial pools and the append buffer as there), and goes with it. */
+ * Row masks and the deleted set: cos_flat_search_f16_masked_batch below.  Out of scope: the shard set, FullPrecisionFP storage
+ * (cos_bruteforce_topk scans f32 rows) and top_k above 102.  The workspace lives on the handle beside cos_flat_search_batch's, sized
+ * by each call's own P (8 P bytes of pool twice, the partial pools and the append buffer as there), and goes with it.
+ * cos_flat_f16_stats is versioned by struct_size: the 24 bytes up to gemm_launches (COS_FLAT_F16_STATS_SIZE_V1) or the whole struct;
+ * the tile counters are written only into the whole struct. */
+#define COS_FLAT_F16_STATS_SIZE_V1 24u
 typedef struct cos_flat_f16_opts {
     uint32_t struct_size; /* in: sizeof(cos_flat_f16_opts) */
     uint32_t exact_mode;  /* 0 never, 1 by the margin rule (default), 2 every query */
@@ -501,9 +504,27 @@ typedef struct cos_flat_f16_stats {
     uint32_t pool;          /* P */
     float gemm_ms;          /* summed HIP-event time of the first pass's scoring launches (the MFMA scan; exact_mode 2: the exact kernel) */
     uint32_t gemm_launches;
+    uint32_t tiles_scanned; /* (64-row tile, block of 128 queries) pairs the scan may visit: the masked call's live tiles ... */
+    uint32_t tiles_total;   /* ... of ceil(n / 64) * ceil(B / 128); the unmasked call scans them all */
 } cos_flat_f16_stats;
 int32_t cos_flat_search_f16_batch(cos_index *ix, const float *queries, uint32_t B, uint32_t top_k, const cos_flat_f16_opts *opts /* NULL = defaults */,
                                   uint32_t *out_ids, float *out_scores, uint32_t *out_counts, cos_flat_f16_stats *stats /* optional */);
+/* cos_flat_search_f16_batch over a SUBSET of the rows: `mask` is the cos_scan_mask of the masked scans below with its rules (host bit
+ * arrays, query_mask, COS_SCAN_SKIP_DELETED, bits at and past n ignored, the same COS_ERR_INVALID cases).  Query q's answer is exactly
+ * what cos_flat_search_f16_batch returns on an index that holds only q's live rows, with the original ids: every live row scored by
+ * dot_product_f16 / (|q| * |x|), sorted, the best 5 * top_k live rows reranked exactly, top_k; out_counts[q] = min(top_k, live rows of
+ * q), 0 for a query without one.  mask == NULL, or n_masks == 0 with no flag, IS the unmasked call.  The scan streams only the 64-row
+ * tiles that hold a row live for one of a query block's 128 queries (a list built on the device once per call), tests the row where a
+ * candidate is about to be kept, and the exact path visits live rows only; the margin rule is evaluated on pools of live rows, so
+ * near-copies among the dead rows send no query down the exact path, and a query with at most P live rows is not tested at all.
+ * Refusals: the unmasked call's and the mask's; COS_ERR_CALCULATION iff a query has a zero norm or a row that is live for at least one
+ * query of the call has.  Out of scope: the shard set, the dot-product metric, FullPrecisionFP storage, top_k above 102 and masks
+ * that are already on the device.  Workspace on the handle beside the unmasked call's: the masks in use twice (uploaded, effective),
+ * n / 8 bytes of their union, one bit per mask and tile, and 4 * ceil(n / 64) bytes of tile list per block of 128 queries. */
+struct cos_scan_mask; /* defined with the masked scans below */
+int32_t cos_flat_search_f16_masked_batch(cos_index *ix, const float *queries, uint32_t B, uint32_t top_k, const struct cos_scan_mask *mask,
+                                         const cos_flat_f16_opts *opts /* NULL = defaults */, uint32_t *out_ids, float *out_scores,
+                                         uint32_t *out_counts, cos_flat_f16_stats *stats /* optional */);
 
 /* The two exhaustive scans over a SUBSET of the rows: per-query allow-lists and / or the handle's deleted set.
  * Query q's live set is mask query_mask[q] AND NOT the deleted rows (COS_SCAN_SKIP_DELETED); its result is exactly what the unmasked

@@ -6,18 +6,23 @@
 One process.  Per width (768, 1024): a Gaussian-mixture corpus of --n rows in an f16 index, 256 queries, top_k 10; a warm-up call, then
 --reps timed calls of each path on the same handle, alternating; the median wall time of a call, the scan kernel's own time
 (cos_flat_f16_stats::gemm_ms, HIP events), and that kernel's share of the f16 MFMA peak (2 B n dim flops) and of the HBM roof (the f16
-rows, streamed once per 128 queries).  One JSON line."""
+rows, streamed once per 128 queries).  Then the masked call (cos_flat_search_f16_masked_batch) on the same handle: an all-ones mask beside
+the unmasked call, 50 / 10 / 1 % live as random rows and as one contiguous id range (tiles_scanned / tiles_total, the scan kernel's
+time), and exact_mode 2 at 1 % live against all live.  --masked 0 leaves that section out.  One JSON line."""
 import argparse, json, os, sys, time
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--n", type=int, default=1000000)
 ap.add_argument("--reps", type=int, default=10)
+ap.add_argument("--masked", type=int, default=1)
+ap.add_argument("--dims", type=int, nargs="+", default=[768, 1024])
 ap.add_argument("--peak-tflops", type=float, default=2516.0, help="dense f16 MFMA peak of the device")
 ap.add_argument("--hbm-gbs", type=float, default=8000.0, help="HBM roof of the device")
 args = ap.parse_args()
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import cosdata_amd as ca
+from cosdata_amd.index import pack_row_masks
 
 B, TOP_K = 256, 10
 
@@ -34,8 +39,37 @@ def clustered(n, d, n_centers=64, sigma=0.15, seed=3):
     return x
 
 
+def masked_cases(ix, Q, n):
+    """median wall / scan-kernel ms of the masked call per mask; the unmasked call is timed between the cases, as everywhere here"""
+    rng, out = np.random.default_rng(4), {}
+    def timed(mask, mode=1, Q=Q):
+        call = (lambda: ix.flat_search_f16(Q, TOP_K, exact_mode=mode, with_stats=True)) if mask is None else \
+               (lambda: ix.flat_search_f16_masked(Q, TOP_K, mask, exact_mode=mode, with_stats=True))
+        call()
+        ms, gemm = [], []
+        for _ in range(args.reps):
+            t = time.perf_counter()
+            st = call()[3]
+            ms.append((time.perf_counter() - t) * 1e3)
+            gemm.append(st.gemm_ms)
+        return {"ms": float(np.median(ms)), "min_max_ms": [float(np.min(ms)), float(np.max(ms))], "scan_kernel_ms": float(np.median(gemm)),
+                "tiles": [int(st.tiles_scanned), int(st.tiles_total)], "exact_queries": int(st.exact_queries)}
+    out["unmasked"] = timed(None)
+    out["all_live"] = timed(pack_row_masks(np.ones(n, bool)))
+    for pct in (50, 10, 1):
+        out[f"random_{pct}"] = timed(pack_row_masks(rng.random(n) < pct / 100.0))
+        rows = np.zeros(n, bool)
+        rows[n // 3: n // 3 + n * pct // 100] = True
+        out[f"range_{pct}"] = timed(pack_row_masks(rows))
+    out["unmasked_again"] = timed(None)
+    # the exact path (n * dim dependent additions per query and live row): eight queries, every row live against the 1 % range
+    out["exact_all_live"] = timed(pack_row_masks(np.ones(n, bool)), 2, Q[:8])
+    out["exact_range_1"] = timed(pack_row_masks(rows), 2, Q[:8])
+    return out
+
+
 cases = {}
-for d in (768, 1024):
+for d in args.dims:
     X = clustered(args.n, d)
     rng = np.random.default_rng(8)
     Q = (X[rng.integers(0, args.n, B)] + np.float32(0.05) * rng.standard_normal((B, d), dtype=np.float32)).astype(np.float32)
@@ -62,5 +96,7 @@ for d in (768, 1024):
         "mfma_peak_share": 2.0 * B * args.n * d / (g * 1e-3) / (args.peak_tflops * 1e12),
         "hbm_roof_share": args.n * row_bytes * ((B + 127) // 128) / (g * 1e-3) / (args.hbm_gbs * 1e9),
     }
+    if args.masked:
+        cases[f"{args.n}x{d} B{B} top_k{TOP_K}"]["masked"] = masked_cases(ix, Q, args.n)
     del ix, X
 print(json.dumps({"reps": args.reps, "cases": cases}))
