@@ -1573,11 +1573,28 @@ extern "C" int32_t cos_index_timing_summary(cos_index *ix, void *stream, cos_tim
 extern "C" int32_t cos_index_enable_metadata(cos_index *ix, uint32_t mdim, uint32_t max_replicas_per_node) {
     if (!ix || mdim == 0 || mdim > 64 || max_replicas_per_node == 0) return cos_fail(COS_ERR_INVALID, "metadata dimensions must be in [1, 64] and max_replicas_per_node >= 1");
     if (!ix->have_vectors) return cos_fail(COS_ERR_NOT_READY, "upload vectors before enabling the metadata component");
-    // (walk_meta_kernel keeps walk_kernel's domain: register pools, one lane per scanned slot)
-    if (ix->p.ef_construction > cosdev::WALK_FAST_MAX_EF || std::min(ix->p.neighbors_count, ix->p.shortlist_size) > 64u ||
-        std::min(ix->p.level0_neighbors_count, ix->p.shortlist_size) > 64u ||
-        (ix->nchunks != 0u && (ix->nchunks + ix->G - 1u) / ix->G > (ix->eng == ENG_U8 ? 2u : 1u)))
-        return cos_fail(COS_ERR_UNIMPLEMENTED, "metadata collections: ef_construction <= %u, at most 64 scanned neighbour slots per node, u8 rows of at most 2048 / SubByte rows of at most 64 x 16 bytes", cosdev::WALK_FAST_MAX_EF);
+    // (both metadata walks keep their candidates in register pools; rows of any width and up to 256 scanned slots per node walk with
+    // walk_meta_general_kernel: kernels_meta_general.hip)
+    if (ix->p.ef_construction > cosdev::WALK_FAST_MAX_EF)
+        return cos_fail(COS_ERR_UNIMPLEMENTED, "metadata collections: ef_construction <= %u", cosdev::WALK_FAST_MAX_EF);
+    int32_t rc = cos_set_device(ix);
+    if (rc) return rc;
+    {   // the widest walk this handle can ask for (ef_search and ef_construction go up to WALK_FAST_MAX_EF) must fit one workgroup's LDS:
+        // refused here, not as a launch failure at search time
+        IndexDev d;
+        memset(&d, 0, sizeof(d));
+        d.num_layers = ix->p.num_layers;
+        d.lv[0].M = ix->p.level0_neighbors_count;
+        d.lv[d.num_layers].M = d.num_layers ? ix->p.neighbors_count : ix->p.level0_neighbors_count;
+        d.dim = ix->p.dim;
+        d.row_stride = ix->row_stride;
+        const size_t need = cosdev::walk_meta_general_smem_bytes(d, cosdev::WALK_FAST_MAX_EF, ix->eng);
+        int lds = 0;
+        HIP_TRY(hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, ix->p.device));
+        if (need > (size_t)lds)
+            return cos_fail(COS_ERR_UNIMPLEMENTED, "metadata collections: the walk of a %u-dimensional row needs %zu bytes of LDS at ef %u (visited filter, popped list, level list, pass window, query row), a workgroup of this device has %d",
+                            ix->p.dim, need, cosdev::WALK_FAST_MAX_EF, lds);
+    }
     if ((u64)ix->n * max_replicas_per_node >= PSEUDO_LO) return cos_fail(COS_ERR_INVALID, "replica ids would run into the reserved id range");
     // a SHARD of a metadata collection (round 6): the shard's embeddings are rows [0, n) here and embeddings [e0, e0 + n) of the
     // collection, so its replica ids are id_base + row x max_replicas + i with id_base = e0 x max_replicas — a multiple of max_replicas
@@ -1586,8 +1603,6 @@ extern "C" int32_t cos_index_enable_metadata(cos_index *ix, uint32_t mdim, uint3
     if ((u64)ix->p.id_base + (u64)ix->n * max_replicas_per_node >= PSEUDO_LO) return cos_fail(COS_ERR_INVALID, "replica ids would run into the reserved id range");
     for (auto &l : ix->lv)
         if (l.n) return cos_fail(COS_ERR_INVALID, "enable the metadata component before uploading / building the base graph: it changes the id of every vector (row x max_replicas)");
-    int32_t rc = cos_set_device(ix);
-    if (rc) return rc;
     ix->id_stride = max_replicas_per_node;
     ix->meta.mdim = mdim;
     ix->meta.lv.resize(ix->p.num_layers + 1);

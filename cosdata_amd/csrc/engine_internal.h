@@ -53,6 +53,11 @@ static_assert(WALK_PLAN_ENG_F32 == ENG_F32 && WALK_PLAN_ENG_F16 == ENG_F16 && WA
               (int)WalkKernel::Lat1 == COS_WALK_KERNEL_LATENCY && (int)WalkKernel::Lat4 == COS_WALK_KERNEL_LATENCY_WAVES, "walk_plan.h restates these");
 hipError_t launch_walk_meta(int eng, const IndexDev &ix, const WalkArgs &wa, hipStream_t st);
 hipError_t launch_walk_meta_index(int eng, const IndexDev &ix, const WalkArgs &wa, hipStream_t st);
+// walk_meta_general_kernel (kernels_meta_general.hip): the launches walk_meta_kernel cannot hold — launch_walk_meta[_index] send them
+// there.  Its dynamic LDS for a beam of ef (cos_index_enable_metadata holds it against the device's limit; the launcher allocates it).
+bool walk_meta_general_needed(int eng, const IndexDev &ix);
+size_t walk_meta_general_smem_bytes(const IndexDev &ix, u32 ef, int eng);
+hipError_t launch_walk_meta_general(int eng, bool indexing, const IndexDev &ix, const WalkArgs &wa, hipStream_t st);
 hipError_t launch_finalize(const IndexDev &ix, const float *queries, u64 q_stride, const float *q_raw_mags, const u32 *walk_ids,
                            const float *walk_sims, const u32 *walk_counts, const int32_t *walk_status, u32 B, u32 top_k,
                            u32 *out_ids, float *out_scores, u32 *out_counts, int32_t *out_status, u64 *out_rerank_rows,

@@ -12,33 +12,21 @@
 // without its lookahead window and scalar-row fast path: this path is about parity (HBM-bound gather like the plain walk; the
 // filter arithmetic is a few dozen integer compares per neighbour).  oracle/cosdata_oracle_hnsw.c (ann_search_filtered) is the
 // CPU statement; tests/test_gpu_meta.py asserts identical per-level lists and final results.
+// Its domain: the query row in CH <= 2 registers per lane (u8 up to 2048 dimensions, SubByte up to 64 chunks) and at most 64 scanned
+// slots.  Everything else — and every launch under the knob meta_walk_general — goes to walk_meta_general_kernel
+// (kernels_meta_general.hip); what the two state once (node kinds, the kind dispatch, the merge into the level list) is meta_walk.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
-#include "walk_common.h"
+#include "meta_walk.h"
+#include "tuning.h"
 
 using namespace cosdev;
 
 namespace {
 
 constexpr int PBM = 4;                                          // code rows in flight per lane group
-enum : int { KIND_BASE = 0, KIND_PSEUDO = 1, KIND_METADATA = 2 };
-
-// dot_product_f32 in the order of dot_product_f32_simd (x86_64.rs:418-444) by ONE lane: 8 FMA chains over chunks of 8,
-// ((s0+s1)+(s2+s3)) + ((s4+s5)+(s6+s7)), non-fused scalar tail.  a: query metadata dims (LDS), b: node mbits (global).
-__device__ __forceinline__ float mdims_dot_ref(const float *__restrict__ a, const int32_t *__restrict__ b, u32 n) {
-    float s[8];
-#pragma unroll
-    for (int i = 0; i < 8; i++) s[i] = 0.0f;
-    const u32 chunks = n >> 3;
-    for (u32 c = 0; c < chunks; c++)
-#pragma unroll
-        for (int i = 0; i < 8; i++) s[i] = __fmaf_rn(a[c * 8 + i], (float)b[c * 8 + i], s[i]);
-    float r = __fadd_rn(__fadd_rn(__fadd_rn(s[0], s[1]), __fadd_rn(s[2], s[3])), __fadd_rn(__fadd_rn(s[4], s[5]), __fadd_rn(s[6], s[7])));
-    for (u32 i = chunks * 8; i < n; i++) r = __fadd_rn(r, __fmul_rn(a[i], (float)b[i]));
-    return r;
-}
 
 struct MetaSmem {
     u32 *vis;     // PerformantFixedSet replica of the level (shared by the level's filter walks)
@@ -128,40 +116,6 @@ __global__ __launch_bounds__(64) void walk_meta_kernel(const IndexDev ix, const 
         return !bad;
     };
 
-    // CosineSimilarity::calculate's dispatch for (stored node, query with the filter in sm.fq / sm.fqi):
-    // returns 0 = the similarity is `sim`, 1 = the vector cosine decides, < 0 = -status.  Executed per LANE (its own node).
-    // (k = the node's metadata row, ymag = its norm: loaded by the caller, TOGETHER with the node's id and vector row — until round 6
-    // they were loaded here, one dependent trip to memory after the other: seven per expansion)
-    auto meta_decide = [&](u32 k, float ymag, u32 nid, float fmag, int xkind, float &sim) -> int {
-        if (metric != 0u) return 1; // the other metrics never look at node kinds
-        const int ykind = ymag == 0.0f ? KIND_BASE : ((nid >= PSEUDO_LO && nid <= PSEUDO_HI) ? KIND_PSEUDO : KIND_METADATA);
-        const int32_t *yb = ix.mbits + (u64)k * md;
-        if (ykind == KIND_PSEUDO && xkind == KIND_METADATA) { // a metadata query strongly matches / mismatches a pseudo node
-            bool eq = true;
-            for (u32 j = 0; j < md; j++) eq &= yb[j] == sm.fqi[j];
-            sim = eq ? 1.0f : -1.0f;
-            return 0;
-        }
-        if (ykind == KIND_PSEUDO && xkind == KIND_PSEUDO) { // two pseudo nodes (index time only): cosine_similarity_mdims (cosine.rs:243-262)
-            const float dp = mdims_dot_ref(sm.fq, yb, md);
-            const float den = __fmul_rn(fmag, ymag);
-            if (den == 0.0f) return -COS_ERR_CALCULATION;
-            sim = __fdiv_rn(dp, den);
-            return 0;
-        }
-        if (ykind == KIND_BASE && xkind == KIND_BASE) return 1;
-        if (ykind == KIND_METADATA && xkind == KIND_METADATA) {
-            const float dp = mdims_dot_ref(sm.fq, yb, md);
-            const float den = __fmul_rn(fmag, ymag);
-            if (den == 0.0f) return -COS_ERR_CALCULATION;
-            if (__fdiv_rn(dp, den) > 0.99f) return 1;
-            sim = -1.0f;
-            return 0;
-        }
-        if (ykind == KIND_BASE && xkind == KIND_METADATA) { sim = 0.0f; return 0; }
-        return -COS_ERR_UNIMPLEMENTED; // the reference's unreachable!() arms (a Base-kind query under the pseudo root, ...)
-    };
-
     for (int level = (int)L; level >= 0 && status == COS_OK; level--) {
         const LevelDev lv = ix.lv[level];
         const u32 M = lv.M;
@@ -173,17 +127,9 @@ __global__ __launch_bounds__(64) void walk_meta_kernel(const IndexDev ix, const 
         u32 nacc = 0; // merged candidates so far (sm.acc)
 
         for (u32 f = f0; f < f1 && status == COS_OK; f++) {
-            // this filter's dimensions -> LDS
-            for (u32 j = lane; j < md; j += 64) {
-                const int32_t v = wa.f_dims[(u64)f * md + j];
-                sm.fqi[j] = v;
-                sm.fq[j] = (float)v;
-            }
-            __builtin_amdgcn_s_waitcnt(0);
-            __builtin_amdgcn_wave_barrier();
+            meta_stage_filter(wa, f, md, sm.fqi, sm.fq, lane); // this filter's dimensions -> LDS
             const float fmag = wa.f_mags[f];
-            // a query has no id (types.rs:227-236); a node being indexed has one: VectorData::replica_node_kind (types.rs:219-241)
-            const int xkind = fmag == 0.0f ? KIND_BASE : (self_pseudo ? KIND_PSEUDO : KIND_METADATA);
+            const int xkind = meta_query_kind(fmag, self_pseudo);
 
             Pool<R> pool;
             pool.clear();
@@ -193,7 +139,7 @@ __global__ __launch_bounds__(64) void walk_meta_kernel(const IndexDev ix, const 
                 const float eymag = ix.mmags[ek];
                 float s0 = 0.0f;
                 int dec = 0;
-                if (lane == 0) dec = meta_decide(ek, eymag, eid, fmag, xkind, s0);
+                if (lane == 0) dec = meta_decide(ix, sm.fq, sm.fqi, ek, eymag, eid, fmag, xkind, s0);
                 dec = (int)readlane_u32((u32)dec, 0);
                 s0 = __uint_as_float(readlane_u32(__float_as_uint(s0), 0));
                 if (dec < 0) { status = -dec; break; }
@@ -265,7 +211,7 @@ __global__ __launch_bounds__(64) void walk_meta_kernel(const IndexDev ix, const 
                 // node-kind dispatch per winner
                 float csim = 0.0f;
                 int dec = 0;
-                if (win) dec = meta_decide(nk, nymag, nid, fmag, xkind, csim);
+                if (win) dec = meta_decide(ix, sm.fq, sm.fqi, nk, nymag, nid, fmag, xkind, csim);
                 const u64 errm = __ballot(win && dec < 0);
                 if (errm) { status = -(int)readlane_u32((u32)dec, __ffsll((long long)errm) - 1); failed = true; break; }
                 // winners whose similarity is already known
@@ -344,76 +290,21 @@ __global__ __launch_bounds__(64) void walk_meta_kernel(const IndexDev ix, const 
             if (failed || status != COS_OK) break;
             // this walk's result: popped list sorted descending, first 100; entries with cosine exactly -1.0 are dropped;
             // merged into the level's candidate list (sorted descending, first 100 kept)
-            u64 rk[R];
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                const u32 e = (u32)lane * R + r;
-                rk[r] = e < npop ? sm.res[e] : 0ull;
-            }
-            bitonic_sort_desc<R>(rk, lane);
-            const u32 keepn = npop < keep_n ? npop : keep_n;
-            const u32 minus1 = metric_key(metric, -1.0f);
-            u64 mk[4]; // 256 >= 100 (so far) + 100 (this walk)
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const u32 e = (u32)lane * 4 + r;
-                mk[r] = e < nacc ? sm.acc[e] : 0ull;
-            }
-            __builtin_amdgcn_wave_barrier();
-            // the walk's survivors, compacted (they stay in descending order) into the staging list, then appended behind the
-            // nacc entries already there and sorted together
-            bool okf[R];
-            u32 mine = 0;
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                const u32 e = (u32)lane * R + r;
-                okf[r] = e < keepn && (INDEXING || !(metric == 0u && (u32)(rk[r] >> 32) == minus1));
-                mine += okf[r] ? 1u : 0u;
-            }
-            u32 incl = mine;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const u32 t = (u32)__shfl_up((int)incl, d, 64);
-                if (lane >= d) incl += t;
-            }
-            const u32 nsurv = readlane_u32(incl, 63); // <= 100
-            u32 pos = incl - mine;
-#pragma unroll
-            for (int r = 0; r < R; r++)
-                if (okf[r]) sm.res[pos++] = rk[r]; // the popped list is dead: its LDS doubles as the staging list (>= 128 entries)
-            __builtin_amdgcn_s_waitcnt(0);
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const u32 e = (u32)lane * 4 + r;
-                if (e >= nacc && e < nacc + nsurv) mk[r] = sm.res[e - nacc];
-            }
-            bitonic_sort_desc<4>(mk, lane);
-            nacc = nacc + nsurv < keep_n ? nacc + nsurv : keep_n;
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const u32 e = (u32)lane * 4 + r;
-                if (e < nacc) sm.acc[e] = mk[r];
-            }
-            __builtin_amdgcn_s_waitcnt(0);
-            __builtin_amdgcn_wave_barrier();
+            nacc = meta_merge_walk<R, INDEXING>(sm.res, sm.acc, npop, nacc, keep_n, metric, lane);
         }
         if (status != COS_OK) break;
 
         if (nacc == 0) { // no candidate survived: the entry node with its strongest match over the filters
             u64 best = 0ull;
             for (u32 f = f0; f < f1 && status == COS_OK; f++) {
-                for (u32 j = lane; j < md; j += 64) { const int32_t v = wa.f_dims[(u64)f * md + j]; sm.fqi[j] = v; sm.fq[j] = (float)v; }
-                __builtin_amdgcn_s_waitcnt(0);
-                __builtin_amdgcn_wave_barrier();
+                meta_stage_filter(wa, f, md, sm.fqi, sm.fq, lane);
                 const float fmag = wa.f_mags[f];
                 const int xkind = fmag == 0.0f ? KIND_BASE : KIND_METADATA; // (vector_store.rs:329-367: the fallback builds the query without an id)
                 const u32 eid = lv.node_id[entry], ek = lv.node_meta[entry];
                 const float eymag = ix.mmags[ek];
                 float s0 = 0.0f;
                 int dec = 0;
-                if (lane == 0) dec = meta_decide(ek, eymag, eid, fmag, xkind, s0);
+                if (lane == 0) dec = meta_decide(ix, sm.fq, sm.fqi, ek, eymag, eid, fmag, xkind, s0);
                 dec = (int)readlane_u32((u32)dec, 0);
                 s0 = __uint_as_float(readlane_u32(__float_as_uint(s0), 0));
                 if (dec < 0) { status = -dec; break; }
@@ -429,14 +320,7 @@ __global__ __launch_bounds__(64) void walk_meta_kernel(const IndexDev ix, const 
             __builtin_amdgcn_s_waitcnt(0);
             __builtin_amdgcn_wave_barrier();
         }
-        const u64 obase = ((u64)qi * (L + 1) + out_slot) * wa.keep;
-        for (u32 e = lane; e < nacc; e += 64) {
-            const u64 kv = sm.acc[e];
-            wa.out_ids[obase + e] = lv.node_id[(u32)kv];
-            wa.out_sims[obase + e] = metric_key_inv(metric, (u32)(kv >> 32));
-            if (INDEXING && wa.out_nodes) wa.out_nodes[obase + e] = (u32)kv;
-        }
-        if (lane == 0) wa.out_counts[(u64)qi * (L + 1) + out_slot] = nacc;
+        meta_write_level<INDEXING>(sm.acc, nacc, ix, lv, wa, qi, out_slot, lane);
         if (level > 0) entry = lv.child[(u32)sm.acc[0]];
         __builtin_amdgcn_wave_barrier();
     }
@@ -472,6 +356,9 @@ static hipError_t launch_meta_r(const IndexDev &ix, const WalkArgs &wa, hipStrea
 template <bool INDEXING>
 static hipError_t launch_walk_meta_t(int eng, const IndexDev &ix, const WalkArgs &wa, hipStream_t st) {
     if (wa.B == 0) return hipSuccess;
+    // rows of more chunk passes than this kernel's registers hold, more than 64 scanned slots on a level — or the knob that holds the
+    // general kernel to the oracle on what both serve (tuning.h: meta_walk_general)
+    if (walk_meta_general_needed(eng, ix) || tune_or(TUNE_META_WALK_GENERAL, 0) == 1) return launch_walk_meta_general(eng, INDEXING, ix, wa, st);
     const u32 ch = (eng == ENG_F32 || eng == ENG_F16) ? 1 : (ix.nchunks + ix.G - 1) / ix.G;
     switch (eng) {
     case ENG_U8: return ch == 1 ? launch_meta_r<ENG_U8, 1, INDEXING>(ix, wa, st) : (ch == 2 ? launch_meta_r<ENG_U8, 2, INDEXING>(ix, wa, st) : hipErrorInvalidValue);

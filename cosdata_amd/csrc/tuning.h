@@ -54,6 +54,7 @@ enum TuneKey : int {
     TUNE_FLAT_BRUTE_EXACT,    // which queries of a brute force are scored again in the reference's order (flat_plan.h brute_margin_safe): 0 = none — the ranking of the f32 MFMA alone cuts the pool, which on corpora with near-copies of one row CAN return a wrong list (kept for A/B timing; the one knob that can change a result), 1 = those the margin rule flags (default), 2 = every query
     TUNE_WALK_PAIR,           // the last range of an ordered launch is walked two sorted neighbours per workgroup, sharing integer dots through LDS (kernels_walk_pair.hip, walk_pair_plan.h): 0 = never, 1 = launches of WALK_PAIR_MIN_B queries or more inside the pair kernel's domain, 2 = at every launch size (tests); default WALK_PAIR_DEFAULT, engine.hip
     TUNE_WALK_PAIR_CACHE,     // ... entries of a query's dot cache (a power of two, 64..2048; 8 bytes of LDS each; a size whose two waves do not fit 64 KB of LDS leaves the launch to walk_kernel); default WALK_PAIR_CACHE_DEFAULT, engine.hip
+    TUNE_META_WALK_GENERAL,   // 1 = every walk of a metadata collection (filtered search, the component's builder) takes walk_meta_general_kernel (kernels_meta_general.hip), not only those walk_meta_kernel cannot hold (tests, scripts/bench_meta_general.py); default 0
     TUNE_COUNT
 };
 

@@ -356,7 +356,11 @@ int32_t cos_index_timing_summary(cos_index *ix, void *stream, cos_timing_summary
  * encoding (metadata/schema.rs, query_filtering.rs) stays on the host; the device takes the numeric form.
  * Ids: an embedding reserves max_replicas_per_node consecutive internal ids (collection.rs:445-468): vector row r has base id
  * r * max_replicas_per_node (also in the BASE graph from now on), replica i = base + i; pseudo root = u32::MAX - 257, pseudo
- * nodes follow it.  Returned ids are replica ids; scores are the exact cosine against the embedding's raw vector. */
+ * nodes follow it.  Returned ids are replica ids; scores are the exact cosine against the embedding's raw vector.
+ * Limits (COS_ERR_UNIMPLEMENTED): ef_construction <= 1024 (ef_search: refused by the filtered calls), and a metadata walk that fits
+ * one workgroup's LDS at ef 1024 — visited filter of the widest level, popped list, level list, pass window and the query row (the
+ * code row; f16 / f32: dim x 4 bytes) against the device's limit, 160 KB on gfx950; the message states both.  Rows of any other width
+ * and up to 256 scanned neighbour slots per node are served (walk_meta_general_kernel where walk_meta_kernel cannot hold them). */
 int32_t cos_index_enable_metadata(cos_index *ix, uint32_t mdim /* <= 64 */, uint32_t max_replicas_per_node);
 /* node table of the pseudo-root component: ascending replica ids (pseudo root and pseudo nodes last), mbits [n_nodes][mdim] */
 int32_t cos_index_upload_meta_nodes(cos_index *ix, uint32_t n_nodes, const uint32_t *node_ids, const int32_t *mbits);
