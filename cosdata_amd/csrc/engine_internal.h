@@ -419,6 +419,11 @@ struct cos_index {
     struct FlatWs *flat_ws = nullptr; // cos_flat_search_batch's buffers (kernels_flat.hip), created on first use under `mu`
     struct FlatF16Ws *flat_f16_ws = nullptr; // cos_flat_search_f16_batch's (kernels_flat_f16.hip), likewise; released with flat_ws
     cos_brute_stats brute_last = {(u32)sizeof(cos_brute_stats), 0u, 0u, 0u}; // the last brute force of this handle (cos_index_last_brute_stats)
+    // cos_bruteforce_topk_dot's margin rule (kernels_brute_dot.hip): the bits of the largest of d_raw_mags[0 .. n), on the device, valid
+    // for brute_xmax_n rows; cos_flat_ws_release — every upload, cos_index_append — invalidates it like the code scan's zn_valid
+    DevArr<u32> brute_xmax;
+    bool brute_xmax_valid = false;
+    u32 brute_xmax_n = 0;
 };
 
 

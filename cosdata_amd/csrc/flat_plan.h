@@ -64,6 +64,24 @@ constexpr bool brute_margin_safe(float kth, float pth, uint32_t dim, bool pool_f
     if (!(a - a == 0.0) || !(b - b == 0.0)) return false; // NaN or inf
     return a - b > 2.0 * brute_margin_bound(dim);
 }
+// The same argument for the INNER PRODUCT (kernels_brute_dot.hip, cos_bruteforce_topk_dot), where no score is divided by a norm and
+// the bound is absolute.  g = the MFMA's dot of a row x with the query q, e = the reference-order dot of the same f32 operands:
+//   |g - e| <= (dim + dim / 8 + 16) u S,  S = sum |q_i x_i|   (the two chains above; no quotient follows)
+// and S <= |q| |x| (Cauchy-Schwarz), so with c = brute_margin_bound(dim) — the cosine figure, its 8 u of quotient terms kept as slack,
+// doubled as there for a truncating MFMA step and for the handle's norms, which are sequential f32 sums (relative error up to
+// dim u / 2) and stand in for the true |q| and |x| — every row obeys |g - e| <= c |q| |x| <= c |q| Xmax, Xmax the largest stored row
+// norm.  A row outside a FULL pool has e <= g_P + c |q| Xmax, the k best of the pool have e >= g_k - c |q| Xmax: the pool is trusted iff
+//   g_k - g_P > 2 c |q| Xmax
+// strictly, so no outside row can even tie into the cut.  The maximum over ALL rows is a valid, looser Xmax for a masked call.  A NaN
+// or an infinity in either score or in the product (a NaN norm, an overflowing |q| Xmax) is never safe; a pool that is not full holds
+// every live row.  (Products that underflow add at most dim * 2^-149 to either dot: far below one u of any score that can be ranked
+// apart from another.)
+constexpr bool brute_dot_margin_safe(float kth, float pth, uint32_t dim, float qnorm, float xmax, bool pool_full) {
+    if (!pool_full) return true;
+    const double a = (double)kth, b = (double)pth, need = 2.0 * brute_margin_bound(dim) * (double)qnorm * (double)xmax;
+    if (!(a - a == 0.0) || !(b - b == 0.0) || !(need - need == 0.0)) return false; // NaN or inf
+    return a - b > need;
+}
 // tuning knob flat_brute_exact: which queries take the exact path
 enum BruteExact : int { BRUTE_EXACT_NEVER = 0, BRUTE_EXACT_BY_RULE = 1, BRUTE_EXACT_ALWAYS = 2 };
 // code scan: the pool holds the 5 * top_k candidates of the exact rerank; top_k in [1, 204]

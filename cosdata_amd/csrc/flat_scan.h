@@ -4,10 +4,12 @@
 
 #include <vector>
 
+#include "dev_mem.h"
 #include "engine_types.h"
 #include "flat_plan.h"
 
 struct cos_scan_mask; // include/cosdata_hip.h
+struct cos_index;     // engine_internal.h
 
 namespace cosdev {
 
@@ -42,6 +44,14 @@ struct MaskPlan {
 };
 // COS_OK or the refusal.  Masks no query names are neither uploaded nor part of the zero-norm screen.
 int32_t scan_mask_plan(const cos_scan_mask *mask, u32 B, MaskPlan &mp);
+struct MaskBufs { // grow-only, like the other buffers of a scan
+    DevArr<u32> user, eff, uni, qmask;
+};
+// the plan's masks on the device (stream st: the plan and the caller's arrays stay until the caller has drained it): sm for the kernels,
+// *uni = the union of the live sets
+hipError_t scan_mask_upload(const cos_index *ix, const cos_scan_mask *mask, const MaskPlan &mp, u32 B, MaskBufs &mb, hipStream_t st, ScanMask &sm, const u32 **uni);
+// masked brute force: out_counts[q] = min(k, survivors in the query's pool of P keys)
+hipError_t launch_pool_count(const u64 *pool, u32 P, u32 B, u32 k, u32 *out_counts, hipStream_t st);
 
 struct FusedOut {
     const u64 *thr;  // [B] SEL-th best (key) so far; 0 = pool not full yet, everything passes

@@ -696,14 +696,8 @@ int32_t cosdev::scan_mask_plan(const cos_scan_mask *mask, u32 B, MaskPlan &mp) {
     return COS_OK;
 }
 
-namespace {
-
-struct MaskBufs { // grow-only, like the other buffers of a scan
-    DevArr<u32> user, eff, uni, qmask;
-};
-// the plan's masks on the device (stream st: the plan and the caller's arrays stay until the caller has drained it): sm for the kernels,
-// *uni = the union of the live sets
-hipError_t scan_mask_upload(const cos_index *ix, const cos_scan_mask *mask, const MaskPlan &mp, u32 B, MaskBufs &mb, hipStream_t st, ScanMask &sm, const u32 **uni) {
+// the plan's masks on the device (MaskBufs and the contract: flat_scan.h; kernels_brute_dot.hip uploads its masks through it too)
+hipError_t cosdev::scan_mask_upload(const cos_index *ix, const cos_scan_mask *mask, const MaskPlan &mp, u32 B, MaskBufs &mb, hipStream_t st, ScanMask &sm, const u32 **uni) {
     const u32 n = ix->n, words = (n + 31) / 32, G = mp.used.empty() ? 1u : (u32)mp.used.size();
     hipError_t e = mb.eff.grow((size_t)G * words);
     if (e == hipSuccess) e = mb.uni.grow(words);
@@ -720,6 +714,8 @@ hipError_t scan_mask_upload(const cos_index *ix, const cos_scan_mask *mask, cons
     *uni = mb.uni.p;
     return e;
 }
+
+namespace {
 
 // ---- what the two scans share: the numbers are flat_plan.h's, the launches are here ----
 namespace fp = flat_plan;
@@ -745,6 +741,10 @@ hipError_t fold_chunk(const fp::Scan &plan, const fp::Chunk &c, const ScanBufs &
 }
 hipError_t launch_flat_reset(u64 *pool, u64 n_pool, u64 *thr, u32 *appcnt, u32 B, u32 *overflow, hipStream_t st) {
     hipLaunchKernelGGL(flat_reset_kernel, dim3(64), dim3(256), 0, st, pool, n_pool, thr, appcnt, B, overflow);
+    return hipGetLastError();
+}
+hipError_t launch_pool_count(const u64 *pool, u32 P, u32 B, u32 k, u32 *out_counts, hipStream_t st) {
+    hipLaunchKernelGGL(pool_count_kernel, dim3(B), dim3(64), 0, st, pool, P, B, k, out_counts);
     return hipGetLastError();
 }
 hipError_t launch_any_zero(const float *v, u32 n, u32 *flag, hipStream_t st) {
@@ -1077,6 +1077,7 @@ struct FlatWs {
 void cos_flat_ws_release(cos_index *ix) { // cos_index_destroy, and every upload that replaces the stored vectors
     delete ix->flat_ws;
     ix->flat_ws = nullptr;
+    ix->brute_xmax_valid = false; // the largest row norm (kernels_brute_dot.hip): the rows are about to change
     cos_flat_f16_ws_release(ix);
 }
 

@@ -599,6 +599,21 @@ class HNSWIndex:
         del keep
         return ids, scores, counts
 
+    def bruteforce_topk_dot(self, queries, k: int, masks=None, query_mask=None, skip_deleted: bool = False):
+        """Exact top-k by INNER PRODUCT over the raw vectors (cos_bruteforce_topk_dot), whatever the index's own metric and storage: the
+        k live rows with the largest dot(q, x), score descending, the larger id first on ties; scores are the reference-order f32 dot.
+        masks as in flat_search_masked (none at all: every row).  -> ids, scores, counts: counts[b] = min(k, live rows of b), the
+        entries past it are unspecified.  No zero-norm error: a zero row scores 0."""
+        q = self._queries(queries)
+        B = q.shape[0]
+        sm, keep = self._scan_mask(masks, query_mask, skip_deleted, B)
+        ids = np.zeros((B, k), np.uint32)
+        scores = np.zeros((B, k), np.float32)
+        counts = np.zeros(B, np.uint32)
+        check(_lib.lib().cos_bruteforce_topk_dot(self._h, _p(q), B, k, C.byref(sm) if sm is not None else None, _p(ids), _p(scores), _p(counts)))
+        del keep
+        return ids, scores, counts
+
     def deleted_count(self) -> int:
         """rows in the handle's deleted set (every id given to delete() since the vectors were uploaded)"""
         n = C.c_uint32()

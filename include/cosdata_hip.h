@@ -559,6 +559,23 @@ int32_t cos_flat_search_masked_batch(cos_index *ix, const float *queries, uint32
                                      uint32_t *out_ids, float *out_scores, uint32_t *out_counts, cos_flat_stats *stats /* optional */);
 int32_t cos_bruteforce_topk_masked(cos_index *ix, const float *queries, uint32_t B, uint32_t k, const cos_scan_mask *mask,
                                    uint32_t *out_ids, float *out_scores, uint32_t *out_counts);
+/* Exact brute-force top-k by INNER PRODUCT on the resident raw vectors: query q's answer is the k live rows with the largest
+ * dot(q, x), score descending, the larger id first on ties; out_scores is the f32 dot in the reference's order (the numerator of
+ * cos_bruteforce_topk's cosine: eight chains, a pairwise tree, a scalar tail), out_ids are original ids.  The index's own metric and
+ * storage play no part: like cos_bruteforce_topk it scans the raw rows of any handle that has vectors, and it is the exact answer a
+ * COS_METRIC_DOT collection has on the device (recall ground truth, maximum-inner-product search over a subset of the rows).
+ * k in [1, min(512, n)], anything else is COS_ERR_INVALID; pools as in cos_bruteforce_topk (the smallest of 64 .. 1024 with 2k <= P),
+ * candidates from an f32 MFMA GEMM without norms, and the pool is trusted only where its k-th GEMM score lies more than
+ * 2 c |q| Xmax above its P-th (cosdata_amd/csrc/flat_plan.h brute_dot_margin_safe: c the relative error bound of the two dots, Xmax
+ * the largest stored row norm, cached per upload); a query that fails the rule has every row scored in the reference's order instead.
+ * Tuning knob flat_brute_exact steers that as in cos_bruteforce_topk, and cos_index_last_brute_stats reports the call.
+ * mask: NULL = every row, or the cos_scan_mask above with all its rules (COS_SCAN_SKIP_DELETED, bits at and past n ignored, the same
+ * COS_ERR_INVALID cases); out_counts[q] = min(k, live rows of q), entries past the count are unspecified.  out_counts may be NULL iff
+ * mask is NULL (COS_ERR_INVALID otherwise).  There is no zero-norm error: a zero row scores 0, a zero query returns ties.
+ * Out of scope: the shard set, k above 512, masks that are already on the device; the f16 and code scans keep their refusals for the
+ * dot-product metric.  The handle stays usable after every refusal. */
+int32_t cos_bruteforce_topk_dot(cos_index *ix, const float *queries, uint32_t B, uint32_t k, const cos_scan_mask *mask /* NULL = every row */,
+                                uint32_t *out_ids, float *out_scores, uint32_t *out_counts /* may be NULL iff mask == NULL */);
 /* rows in the deleted set; the set itself, HOST bits[ceil(n / 32)] in the layout of cos_scan_mask::bits (a set bit = deleted) */
 int32_t cos_index_deleted_count(cos_index *ix, uint32_t *out);
 int32_t cos_index_download_deleted(cos_index *ix, uint32_t *bits);
