@@ -1,6 +1,7 @@
-// flat_f16.h — what the two f16 scans share: kernels_flat_f16.hip (cos_flat_search_f16_batch, every row) and
-// kernels_flat_f16_masked.hip (cos_flat_search_f16_masked_batch, each query's live rows).  The tile geometry, the fragment helpers of
-// the two scan kernels, the handle's workspace and the re-score launch; each scan kernel and its host flow stay in their own file.
+// flat_f16.h — what the f16 scans share: kernels_flat_f16.hip (cos_flat_search_f16_batch, every row), kernels_flat_f16_masked.hip
+// (cos_flat_search_f16_masked_batch, each query's live rows) and kernels_flat_f16_dot.hip (cos_flat_search_f16_dot_batch, the
+// dot-product metric, masked or not).  The tile geometry, the fragment helpers of the scan kernels, the handle's workspace, the
+// re-score launch and the masked calls' prepare step; each scan kernel and its host flow stay in their own file.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -61,6 +62,16 @@ struct FlatF16MaskBufs {
     DevArr<u32> eff, uni, live;                  // [G][words] effective words, [words] their OR, [G] live rows
     DevArr<u64> tile_bits;                       // [G][ceil(tiles / 64)]: bit t = tile t holds a live row of mask g
     DevArr<u32> lists, list_len;                 // [blocks][tiles] the live tiles of a query block, ascending; [blocks] how many
+    std::vector<u32> h_blk_off, h_blk_masks;     // what blk_off / blk_masks are uploaded from: alive until the stream has read them
+};
+// the same buffers as a call's kernels take them (f16_mask_prepare below fills it)
+struct F16MaskDev {
+    ScanMask sm;                 // the effective words and [B] -> mask
+    const u32 *uni, *live;       // [words] the OR of the effective words, [G] live rows
+    const u64 *tile_bits;        // [G][tb_stride]
+    u32 tb_stride;
+    const u32 *lists, *list_len; // [blocks][tiles], [blocks]
+    u32 tiles, blocks;
 };
 
 }  // namespace cosdev
@@ -75,6 +86,9 @@ struct FlatF16Ws {
     cosdev::FlatF16MaskBufs mask;           // the masked call's; empty until one is made
     bool zn_valid = false, zn_zero = false; // "a stored vector has a zero norm" for the current rows (the unmasked call's screen)
     u32 zn_n = 0;
+    DevArr<u32> xmax; // the dot-metric call's: bits of the largest norm of the stored f16 rows, rounded up (kernels_flat_f16_dot.hip);
+    bool xmax_valid = false; // cached like zn_*: the workspace goes with every upload and append
+    u32 xmax_n = 0;
     std::vector<hipEvent_t> evs;
     hipError_t event(size_t i, hipEvent_t *out) {
         while (evs.size() <= i) {
@@ -92,3 +106,7 @@ struct FlatF16Ws {
 };
 // the handle's workspace, created on first use (kernels_flat_f16.hip)
 FlatF16Ws *cos_flat_f16_ws(cos_index *ix);
+// a masked call's prepare step (kernels_flat_f16_masked.hip): `used` / `qmask` of the call's MaskPlan -> effective words, live counts,
+// tile bits and each query block's list of live tiles, all enqueued on st
+hipError_t f16_mask_prepare(cos_index *ix, FlatF16Ws *W, const cos_scan_mask *mask, const std::vector<u32> &used, bool skip_deleted,
+                            const std::vector<u32> &qmask, u32 B, hipStream_t st, cosdev::F16MaskDev &out);

@@ -142,6 +142,33 @@ constexpr bool f16_masked_margin_safe(float nth, float pth, uint32_t dim, uint32
     return f16_margin_skipped(live, P) || f16_margin_safe(nth, pth, dim, true);
 }
 
+// ---- f16 scan by INNER PRODUCT (kernels_flat_f16_dot.hip, cos_flat_search_f16_dot_batch) ----
+// f16_margin_safe's argument where no score is divided by a norm, so the bound is absolute (as brute_dot_margin_safe's).  g = the f16
+// MFMA's dot of a stored row x^ with the query's code q^, e = dot_product_f16 of the same f16 values.  The products are exact in f32 and
+// both dots add the same dim of them, each with at most dim roundings in some order:
+//   |g - S*| <= dim u S,  |e - S*| <= dim u S   (S* the exact sum, S = sum |x^_i q^_i|, u = 2^-24)
+// so |g - e| <= 2 dim u S, and S <= |q^| |x^| <= |q^| X^max (Cauchy-Schwarz; X^max the largest norm of the stored f16 rows).  As
+// f16_margin_bound does — the MFMA's internal additions may truncate (2 u a step), and neither is documented — the bound takes TWICE
+// the figure:
+//   bound(q) = 4 dim u |q^| X^max
+// and a FULL pool is trusted iff g_N - g_P > 2 bound(q), strictly, with both scores and the bound finite; a pool that is not full holds
+// every live row.  |q^| and X^max are f32 norms of the f16 VALUES (not the handle's norms of the original vectors), each rounded UP by
+// (1 + dim u) over its f32 sum of squares (relative error at most dim u / 2 after the root), so neither is an underestimate.  The
+// maximum over ALL rows is a valid, looser X^max for a masked call.  (Products of f16 subnormals are still exact in f32: 2^-48 at the
+// smallest.)
+constexpr double f16_dot_margin_bound(uint32_t dim, float qnorm, float xmax) {
+    return 4.0 * (double)dim * (1.0 / 16777216.0) * (double)qnorm * (double)xmax;
+}
+constexpr bool f16_dot_margin_safe(float nth, float pth, uint32_t dim, float qnorm, float xmax, bool pool_full) {
+    if (!pool_full) return true;
+    const double a = (double)nth, b = (double)pth, need = 2.0 * f16_dot_margin_bound(dim, qnorm, xmax);
+    if (!(a - a == 0.0) || !(b - b == 0.0) || !(need - need == 0.0)) return false; // NaN or inf
+    return a - b > need;
+}
+constexpr bool f16_dot_masked_margin_safe(float nth, float pth, uint32_t dim, float qnorm, float xmax, uint32_t live, uint32_t P) {
+    return f16_margin_skipped(live, P) || f16_dot_margin_safe(nth, pth, dim, qnorm, xmax, true);
+}
+
 // ---- which kernel scores a fused chunk of the code scan ----
 enum class ScanKernel {
     RESIDENT_PLANES, // query-resident scan of bit-plane codes (kernels_scan.hip flat_scan_q2_*)

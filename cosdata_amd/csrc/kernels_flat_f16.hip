@@ -17,8 +17,8 @@
 // loaded, the piece that holds dim is masked, so the k tail is zero in LDS and in the fragments; a tail of at most 8 dims runs on
 // v_mfma_f32_32x32x8_f16 instead of a half-empty x16 step.
 // Masks and the deleted set: kernels_flat_f16_masked.hip (cos_flat_search_f16_masked_batch), a scan kernel of its own over the live
-// tiles; flat_f16.h holds what the two share.  The shard set, f32 storage, the dot-product metric and top_k > 102 are not served
-// (include/cosdata_hip.h).
+// tiles; the dot-product metric: kernels_flat_f16_dot.hip (cos_flat_search_f16_dot_batch); flat_f16.h holds what the three share.
+// The shard set, f32 storage and top_k > 102 are not served (include/cosdata_hip.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -459,7 +459,7 @@ extern "C" int32_t cos_flat_search_f16_batch(cos_index *ix, const float *queries
     const u32 mode = opts ? opts->exact_mode : (u32)fp::F16_EXACT_BY_RULE;
     if (mode > fp::F16_EXACT_ALWAYS) return cos_fail(COS_ERR_INVALID, "cos_flat_f16_opts::exact_mode is %u: 0, 1 or 2", mode);
     if (ix->eng != ENG_F16) return cos_fail(COS_ERR_STORAGE_MISMATCH, "cos_flat_search_f16_batch scans HalfPrecisionFP rows (cos_flat_search_batch: u8 and bit-plane codes)");
-    if (ix->p.metric != COS_METRIC_COSINE) return cos_fail(COS_ERR_UNIMPLEMENTED, "cos_flat_search_f16_batch implements the cosine metric");
+    if (ix->p.metric != COS_METRIC_COSINE) return cos_fail(COS_ERR_UNIMPLEMENTED, "cos_flat_search_f16_batch implements the cosine metric (dot product: cos_flat_search_f16_dot_batch)");
     if (int32_t krc = fp::check_f16_top_k(top_k)) return cos_fail(krc, "the f16 scan keeps at most 1024 survivors (2 * 5 * top_k): top_k must be in [1, 102]");
     if (int32_t rc = cos_set_device(ix)) return rc;
     FlatF16Ws *W = cos_flat_f16_ws(ix);

@@ -19,7 +19,8 @@
 // Pools hold live rows only, so f16_rescore and the rerank run unchanged and the counts are min(top_k, live rows).
 // An append overflow repeats the call unfused, as there; a mask whose live rows all lie behind the seed chunk (no threshold when the
 // first fused chunk meets them) takes that road when a query has more live rows in one chunk than the append buffer holds.
-// Out of scope: the shard set, the dot-product metric, FullPrecisionFP storage, top_k > 102 and masks that are already on the device.
+// Out of scope: the shard set, FullPrecisionFP storage, top_k > 102 and masks that are already on the device.  The dot-product metric
+// is kernels_flat_f16_dot.hip's, which shares this file's prepare step (f16_mask_prepare).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -400,6 +401,60 @@ __global__ __launch_bounds__(256) void f16m_exact_scores(const uint8_t *__restri
     }
 }
 
+} // namespace
+
+// The masks of a call on the device, for both masked f16 scans (this file's, kernels_flat_f16_dot.hip's): the masks of each query block
+// (host), the uploads and f16m_prepare, enqueued on st.  The host arrays that the uploads read live in the workspace until the next call.
+hipError_t f16_mask_prepare(cos_index *ix, FlatF16Ws *W, const cos_scan_mask *mask, const std::vector<u32> &used, bool skip_deleted,
+                            const std::vector<u32> &qmask, u32 B, hipStream_t st, cosdev::F16MaskDev &out) {
+    const u32 n = ix->n, words = (n + 31) / 32, G = used.empty() ? 1u : (u32)used.size(), tiles = fp::f16_tiles(n), blocks = fp::f16_query_blocks(B);
+    const u32 tb_stride = (tiles + 63) / 64;
+    FlatF16MaskBufs &M = W->mask;
+    std::vector<u32> &blk_off = M.h_blk_off, &blk_masks = M.h_blk_masks;
+    blk_off.assign(blocks + 1, 0u);
+    blk_masks.clear();
+    for (u32 b = 0; b < blocks; b++) {
+        std::vector<u32> ms(qmask.begin() + (size_t)b * QB, qmask.begin() + std::min<size_t>((size_t)(b + 1) * QB, B));
+        std::sort(ms.begin(), ms.end());
+        ms.erase(std::unique(ms.begin(), ms.end()), ms.end());
+        blk_masks.insert(blk_masks.end(), ms.begin(), ms.end());
+        blk_off[b + 1] = (u32)blk_masks.size();
+    }
+    u32 *d_user = nullptr, *d_qmask = nullptr, *d_blk_off = nullptr, *d_blk_masks = nullptr, *d_eff = nullptr, *d_uni = nullptr, *d_live = nullptr,
+        *d_lists = nullptr, *d_list_len = nullptr;
+    u64 *d_tile_bits = nullptr;
+    hipError_t e = hipSuccess;
+    auto need = [&e](auto &buf, auto *&ptr, size_t count) {
+        if (e == hipSuccess) { e = buf.grow(count); ptr = buf; }
+    };
+    if (!used.empty()) need(M.user, d_user, (size_t)G * words);
+    need(M.qmask, d_qmask, B);
+    need(M.blk_off, d_blk_off, blocks + 1);
+    need(M.blk_masks, d_blk_masks, blk_masks.size());
+    need(M.eff, d_eff, (size_t)G * words);
+    need(M.uni, d_uni, words);
+    need(M.live, d_live, G);
+    need(M.tile_bits, d_tile_bits, (size_t)G * tb_stride);
+    need(M.lists, d_lists, (size_t)(fp::f16_tile_list_bytes(n, B) / 4) - blocks);
+    need(M.list_len, d_list_len, blocks);
+    if (e == hipSuccess) e = hipMemsetAsync(d_live, 0, (size_t)G * 4, st);
+    for (u32 g = 0; g < (u32)used.size() && e == hipSuccess; g++)
+        e = hipMemcpyAsync(d_user + (size_t)g * words, mask->bits + (size_t)used[g] * words, (size_t)words * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_qmask, qmask.data(), (size_t)B * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_blk_off, blk_off.data(), (size_t)(blocks + 1) * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_blk_masks, blk_masks.data(), blk_masks.size() * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(f16m_prepare, dim3(blocks + (tiles + 255) / 256), dim3(256), 0, st, (const u32 *)d_user,
+                           skip_deleted ? (const u32 *)ix->d_deleted.p : (const u32 *)nullptr, G, words, n, tiles, blocks, (const u32 *)d_blk_off,
+                           (const u32 *)d_blk_masks, d_eff, d_uni, d_live, d_tile_bits, tb_stride, d_lists, d_list_len);
+        e = hipGetLastError();
+    }
+    out = cosdev::F16MaskDev{ScanMask{d_eff, d_qmask, words}, d_uni, d_live, d_tile_bits, tb_stride, d_lists, d_list_len, tiles, blocks};
+    return e;
+}
+
+namespace {
+
 // One pass over B queries under W->mu, f16_run's (kernels_flat_f16.hip) with the masks: `used` = the caller's masks in use (empty: one
 // all-ones mask), qmask[B] -> index into them.  exact_pass: the flagged queries of an exact_mode 1 call again.
 int32_t f16m_run(cos_index *ix, FlatF16Ws *W, const float *queries, u32 B, u32 top_k, u32 mode, bool exact_pass, const cos_scan_mask *mask,
@@ -409,26 +464,13 @@ int32_t f16m_run(cos_index *ix, FlatF16Ws *W, const float *queries, u32 B, u32 t
     const bool exact = exact_pass || mode == fp::F16_EXACT_ALWAYS, by_rule = !exact && mode == fp::F16_EXACT_BY_RULE;
     const fp::Scan plan = fp::f16_scan(n, B, top_k, exact);
     const u32 P = plan.P, R = P / 64;
-    const u32 words = (n + 31) / 32, G = used.empty() ? 1u : (u32)used.size(), tiles = fp::f16_tiles(n), blocks = fp::f16_query_blocks(B);
-    const u32 tb_stride = (tiles + 63) / 64;
+    const u32 tiles = fp::f16_tiles(n), blocks = fp::f16_query_blocks(B), tb_stride = (tiles + 63) / 64;
     const u64 row_stride = ix->row_stride;
     hipStream_t st = ix->own_stream;
-    // the masks of each query block, for the tile lists
-    std::vector<u32> blk_off(blocks + 1, 0u), blk_masks;
-    for (u32 b = 0; b < blocks; b++) {
-        std::vector<u32> ms(qmask.begin() + (size_t)b * QB, qmask.begin() + std::min<size_t>((size_t)(b + 1) * QB, B));
-        std::sort(ms.begin(), ms.end());
-        ms.erase(std::unique(ms.begin(), ms.end()), ms.end());
-        blk_masks.insert(blk_masks.end(), ms.begin(), ms.end());
-        blk_off[b + 1] = (u32)blk_masks.size();
-    }
     float *d_q = nullptr, *d_qm = nullptr, *d_qrm = nullptr, *d_scores = nullptr, *d_os = nullptr;
     uint8_t *d_qc = nullptr;
     u32 *d_flags = nullptr, *d_appcnt = nullptr, *d_oi = nullptr, *d_oc = nullptr, *d_qflag = nullptr;
     u64 *d_pool = nullptr, *d_sorted = nullptr, *d_thr = nullptr, *d_app = nullptr, *d_part = nullptr;
-    u32 *d_user = nullptr, *d_qmask = nullptr, *d_blk_off = nullptr, *d_blk_masks = nullptr, *d_eff = nullptr, *d_uni = nullptr, *d_live = nullptr,
-        *d_lists = nullptr, *d_list_len = nullptr;
-    u64 *d_tile_bits = nullptr;
     hipError_t e = hipSuccess;
     auto need = [&e](auto &buf, auto *&ptr, size_t count) { // the workspace's buffer grown to `count` elements
         if (e == hipSuccess) { e = buf.grow(count); ptr = buf; }
@@ -447,30 +489,11 @@ int32_t f16m_run(cos_index *ix, FlatF16Ws *W, const float *queries, u32 B, u32 t
     need(W->oi, d_oi, (size_t)B * top_k);
     need(W->os, d_os, (size_t)B * top_k);
     need(W->oc, d_oc, B);
-    FlatF16MaskBufs &M = W->mask;
-    if (!used.empty()) need(M.user, d_user, (size_t)G * words);
-    need(M.qmask, d_qmask, B);
-    need(M.blk_off, d_blk_off, blocks + 1);
-    need(M.blk_masks, d_blk_masks, blk_masks.size());
-    need(M.eff, d_eff, (size_t)G * words);
-    need(M.uni, d_uni, words);
-    need(M.live, d_live, G);
-    need(M.tile_bits, d_tile_bits, (size_t)G * tb_stride);
-    need(M.lists, d_lists, (size_t)(fp::f16_tile_list_bytes(n, B) / 4) - blocks);
-    need(M.list_len, d_list_len, blocks);
     if (e == hipSuccess) e = hipMemsetAsync(d_flags, 0, 12, st);
-    if (e == hipSuccess) e = hipMemsetAsync(d_live, 0, (size_t)G * 4, st);
-    for (u32 g = 0; g < (u32)used.size() && e == hipSuccess; g++)
-        e = hipMemcpyAsync(d_user + (size_t)g * words, mask->bits + (size_t)used[g] * words, (size_t)words * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_qmask, qmask.data(), (size_t)B * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_blk_off, blk_off.data(), (size_t)(blocks + 1) * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_blk_masks, blk_masks.data(), blk_masks.size() * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(f16m_prepare, dim3(blocks + (tiles + 255) / 256), dim3(256), 0, st, (const u32 *)d_user,
-                           skip_deleted ? (const u32 *)ix->d_deleted.p : (const u32 *)nullptr, G, words, n, tiles, blocks, (const u32 *)d_blk_off,
-                           (const u32 *)d_blk_masks, d_eff, d_uni, d_live, d_tile_bits, tb_stride, d_lists, d_list_len);
-        e = hipGetLastError();
-    }
+    F16MaskDev md{};
+    if (e == hipSuccess) e = f16_mask_prepare(ix, W, mask, used, skip_deleted, qmask, B, st, md);
+    const u32 *d_uni = md.uni, *d_live = md.live, *d_lists = md.lists, *d_list_len = md.list_len, *d_qmask = md.sm.qmask;
+    const u64 *d_tile_bits = md.tile_bits;
     if (e == hipSuccess) e = hipMemcpyAsync(d_q, queries, (size_t)B * dim * 4, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = launch_quantize_rows(ENG_F16, d_q, dim, B, dim, ix->p.range_lo, ix->p.range_hi, d_qc, row_stride, d_qm, d_qrm, st);
     // zero norms, the masked code scan's rule: the rows that are live for at least one query of the call, and the queries; every call
@@ -479,7 +502,7 @@ int32_t f16m_run(cos_index *ix, FlatF16Ws *W, const float *queries, u32 B, u32 t
         e = hipGetLastError();
         if (e == hipSuccess) e = launch_any_zero(d_qm, B, d_flags, st);
     }
-    const ScanMask sm{d_eff, d_qmask, words};
+    const ScanMask sm = md.sm;
     u32 hflags[3] = {0u, 0u, 0u};
     std::vector<u32> h_len(blocks, 0u);
     bool zero = false;
@@ -591,7 +614,7 @@ extern "C" int32_t cos_flat_search_f16_masked_batch(cos_index *ix, const float *
     const u32 mode = opts ? opts->exact_mode : (u32)fp::F16_EXACT_BY_RULE;
     if (mode > fp::F16_EXACT_ALWAYS) return cos_fail(COS_ERR_INVALID, "cos_flat_f16_opts::exact_mode is %u: 0, 1 or 2", mode);
     if (ix->eng != ENG_F16) return cos_fail(COS_ERR_STORAGE_MISMATCH, "cos_flat_search_f16_masked_batch scans HalfPrecisionFP rows (cos_flat_search_masked_batch: u8 and bit-plane codes)");
-    if (ix->p.metric != COS_METRIC_COSINE) return cos_fail(COS_ERR_UNIMPLEMENTED, "cos_flat_search_f16_masked_batch implements the cosine metric");
+    if (ix->p.metric != COS_METRIC_COSINE) return cos_fail(COS_ERR_UNIMPLEMENTED, "cos_flat_search_f16_masked_batch implements the cosine metric (dot product: cos_flat_search_f16_dot_batch)");
     if (int32_t krc = fp::check_f16_top_k(top_k)) return cos_fail(krc, "the f16 scan keeps at most 1024 survivors (2 * 5 * top_k): top_k must be in [1, 102]");
     MaskPlan mp;
     if (int32_t mrc = scan_mask_plan(mask, B, mp)) return mrc;

@@ -488,7 +488,7 @@ int32_t cos_flat_search_batch(cos_index *ix, const float *queries, uint32_t B, u
  * answer may differ from the reference's, on corpora with near-copies), 1 by the rule (default), 2 for every query.
  * Host buffers; out_counts[q] = min(top_k, n).  Refusals, each checked before anything is enqueued, the handle stays usable:
  *   COS_ERR_STORAGE_MISMATCH  any storage but COS_STORAGE_F16
- *   COS_ERR_UNIMPLEMENTED     the dot-product metric (its error bound is not relative to 1), top_k > 102 (P would pass 1024)
+ *   COS_ERR_UNIMPLEMENTED     the dot-product metric (its error bound is not relative to 1: cos_flat_search_f16_dot_batch below), top_k > 102 (P would pass 1024)
  *   COS_ERR_INVALID           top_k == 0, exact_mode > 2, a struct_size that is not the struct's size
  *   COS_ERR_CALCULATION       a zero norm among the queries or the stored rows, for the call, as in cos_flat_search_batch
  * Row masks and the deleted set: cos_flat_search_f16_masked_batch below.  Out of scope: the shard set, FullPrecisionFP storage
@@ -522,13 +522,34 @@ int32_t cos_flat_search_f16_batch(cos_index *ix, const float *queries, uint32_t 
  * candidate is about to be kept, and the exact path visits live rows only; the margin rule is evaluated on pools of live rows, so
  * near-copies among the dead rows send no query down the exact path, and a query with at most P live rows is not tested at all.
  * Refusals: the unmasked call's and the mask's; COS_ERR_CALCULATION iff a query has a zero norm or a row that is live for at least one
- * query of the call has.  Out of scope: the shard set, the dot-product metric, FullPrecisionFP storage, top_k above 102 and masks
- * that are already on the device.  Workspace on the handle beside the unmasked call's: the masks in use twice (uploaded, effective),
+ * query of the call has.  Out of scope: the shard set, the dot-product metric (cos_flat_search_f16_dot_batch below takes the
+ * same mask), FullPrecisionFP storage, top_k above 102 and masks that are already on the device.  Workspace on the handle beside the unmasked call's: the masks in use twice (uploaded, effective),
  * n / 8 bytes of their union, one bit per mask and tile, and 4 * ceil(n / 64) bytes of tile list per block of 128 queries. */
 struct cos_scan_mask; /* defined with the masked scans below */
 int32_t cos_flat_search_f16_masked_batch(cos_index *ix, const float *queries, uint32_t B, uint32_t top_k, const struct cos_scan_mask *mask,
                                          const cos_flat_f16_opts *opts /* NULL = defaults */, uint32_t *out_ids, float *out_scores,
                                          uint32_t *out_counts, cos_flat_f16_stats *stats /* optional */);
+/* The exhaustive f16 scan of a HalfPrecisionFP index with the DOT-PRODUCT metric, masked or not: query q's answer is what
+ * cos_flat_search_f16_batch would give if its first-pass score were the dot metric's — every live row scored by dot_product_f16 (one
+ * sequential f32 chain from -0.0 over the f16 codes, no quotient), sorted (desc, larger id first), the best N = 5 * top_k reranked
+ * exactly in f32 (cosine whatever the metric, as in the reference), top_k.  Ids, score bits and counts are those of the reference's
+ * exhaustive mode over a dot-metric f16 collection; with a mask, those of that mode over each query's live rows, with the original ids.
+ * mask: NULL (or n_masks == 0 with no flag) = every row, else the cos_scan_mask below with all its rules (COS_SCAN_SKIP_DELETED, bits
+ * at and past n ignored, the same COS_ERR_INVALID cases); out_counts[q] = min(top_k, live rows of q).  Pools, exact_mode and the stats
+ * as in the cosine calls (tiles_scanned / tiles_total as in the masked one).  An f16 MFMA GEMM in raw dot units generates the pool of
+ * P candidates; the margin is absolute: a full pool is trusted only where its N-th MFMA dot lies more than 2 * 4 dim 2^-24 |q^| X^max
+ * above its P-th (cosdata_amd/csrc/flat_plan.h f16_dot_margin_safe: |q^| the norm of the query's f16 code, X^max the largest norm of
+ * the stored f16 rows — of ALL rows also in a masked call, a valid bound and only looser), and a masked query with at most P live rows
+ * is not tested.  Refusals, each checked before anything is enqueued, the handle stays usable:
+ *   COS_ERR_STORAGE_MISMATCH  any storage but COS_STORAGE_F16
+ *   COS_ERR_UNIMPLEMENTED     any metric but COS_METRIC_DOT (cosine: the two calls above), top_k > 102
+ *   COS_ERR_INVALID           top_k == 0, exact_mode > 2, a struct_size that is not the struct's size, the mask's cases
+ * There is no zero-norm error in the first pass: the dot metric has none.  Workspace: the cosine calls', shared on the handle, plus
+ * four bytes for X^max, computed once per upload.  Out of scope: the shard set, FullPrecisionFP storage (cos_bruteforce_topk_dot scans
+ * f32 rows), top_k above 102 and masks that are already on the device. */
+int32_t cos_flat_search_f16_dot_batch(cos_index *ix, const float *queries, uint32_t B, uint32_t top_k,
+                                      const struct cos_scan_mask *mask /* NULL = every row */, const cos_flat_f16_opts *opts /* NULL = defaults */,
+                                      uint32_t *out_ids, float *out_scores, uint32_t *out_counts, cos_flat_f16_stats *stats /* optional */);
 
 /* The two exhaustive scans over a SUBSET of the rows: per-query allow-lists and / or the handle's deleted set.
  * Query q's live set is mask query_mask[q] AND NOT the deleted rows (COS_SCAN_SKIP_DELETED); its result is exactly what the unmasked
