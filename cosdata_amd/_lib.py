@@ -157,7 +157,7 @@ ABI_SYMBOLS = [
     "cos_ann_search_filtered_batch", "cos_index_load_reference_dir", "cos_reference_dir_level_counts", "cos_reference_dir_read_level",
     "cos_search_batch", "cos_search_batch_device", "cos_ann_search_batch", "cos_index_set_coalescing", "cos_index_coalescing_stats", "cos_index_set_ef_search",
     "cos_index_set_visited_mode", "cos_index_set_latency_mode", "cos_index_set_latency_waves", "cos_index_set_walk_order", "cos_index_walk_order_cuts", "cos_index_set_walk_table", "cos_index_walk_table_info", "cos_index_last_walk_split", "cos_index_last_walk_kernel", "cos_index_last_pair_stats", "cos_index_enable_timing", "cos_index_last_stats", "cos_index_timing_summary", "cos_quantize_batch",
-    "cos_code_bytes", "cos_sample_values_range", "cos_distance_batch", "cos_bruteforce_topk", "cos_flat_search_batch", "cos_flat_search_f16_batch", "cos_flat_search_f16_masked_batch", "cos_flat_search_f16_dot_batch",
+    "cos_code_bytes", "cos_sample_values_range", "cos_distance_batch", "cos_bruteforce_topk", "cos_flat_search_batch", "cos_flat_search_f16_batch", "cos_flat_search_f16_masked_batch", "cos_flat_search_f16_dot_batch", "cos_flat_search_f32_batch",
     "cos_flat_search_masked_batch", "cos_bruteforce_topk_masked", "cos_bruteforce_topk_dot", "cos_index_last_brute_stats", "cos_index_deleted_count", "cos_index_download_deleted", "cos_bm25_create", "cos_bm25_destroy",
     "cos_bm25_insert", "cos_bm25_delete", "cos_bm25_stats", "cos_bm25_download",
     "cos_bm25_search_batch", "cos_bm25_search_batch_device", "cos_rrf_fuse_batch", "cos_hybrid_search_batch", "cos_text_process", "cos_text_count_tokens", "cos_bm25_term_frequency", "cos_xxhash32", "cos_stem_english", "cos_sparse_create", "cos_sparse_build_csr", "cos_sparse_create_from_vectors", "cos_sparse_destroy", "cos_sparse_search_batch", "cos_sparse_last_stats", "cos_sparse_layout",
@@ -245,6 +245,7 @@ def lib():
         "cos_flat_search_f16_batch": [vp, vp, u32, u32, C.POINTER(CosFlatF16Opts), vp, vp, vp, C.POINTER(CosFlatF16Stats)],
         "cos_flat_search_f16_masked_batch": [vp, vp, u32, u32, C.POINTER(CosScanMask), C.POINTER(CosFlatF16Opts), vp, vp, vp, C.POINTER(CosFlatF16Stats)],
         "cos_flat_search_f16_dot_batch": [vp, vp, u32, u32, C.POINTER(CosScanMask), C.POINTER(CosFlatF16Opts), vp, vp, vp, C.POINTER(CosFlatF16Stats)],
+        "cos_flat_search_f32_batch": [vp, vp, u32, u32, C.POINTER(CosScanMask), C.POINTER(CosFlatF16Opts), vp, vp, vp, C.POINTER(CosFlatF16Stats)],
         "cos_bruteforce_topk_masked": [vp, vp, u32, u32, C.POINTER(CosScanMask), vp, vp, vp],
         "cos_bruteforce_topk_dot": [vp, vp, u32, u32, C.POINTER(CosScanMask), vp, vp, vp],
         "cos_index_last_brute_stats": [vp, C.POINTER(CosBruteStats)],

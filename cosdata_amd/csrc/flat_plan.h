@@ -169,6 +169,34 @@ constexpr bool f16_dot_masked_margin_safe(float nth, float pth, uint32_t dim, fl
     return f16_margin_skipped(live, P) || f16_dot_margin_safe(nth, pth, dim, qnorm, xmax, true);
 }
 
+// ---- f32 scan (kernels_flat_f32.hip, cos_flat_search_f32_batch): the same finalisation over FullPrecisionFP rows, masked or not ----
+// f16_margin_safe's argument with the f32 arm's two dots.  g = the f32 MFMA's score of a stored row x with the query q, e = the
+// reference's (dot_product_f32_simd over the same f32 values); both divide by the SAME f32 denominator D = fl(|q| * |x|), the
+// quantizer's norms.  Unlike the f16 scans' products, a product of two f32 values is not exact, so this is brute_margin_bound's case —
+// two f32 sums of dim rounded products — and the derivation is the one written there.  u = 2^-24, S = sum |x_i q_i|:
+//   MFMA dot       v_mfma_f32_32x32x2_f32, dim fused steps chained through the accumulator in the kernel's k order (k = 8 s + i and
+//                  8 s + 4 + i in the i-th instruction of step s): for dim correctly rounded operations in ANY order |err| <= dim u S
+//   reference dot  eight chains of dim / 8 fused steps, a pairwise tree of 3, an unfused scalar tail of up to 7 multiply-adds
+//                  (dot_engines.h f32_oct_dot): |err| <= (dim / 8 + 16) u S
+//   two quotients  |g|, |e| <= ~1: one rounding each over the once-rounded product |q| * |x|, 8 u for both with slack
+// With S <= |x| |q| (Cauchy-Schwarz) and S / D ~ 1: |g - e| <= ((dim + dim / 8 + 32) + 8) u.  As there, neither the MFMA's internal
+// rounding nor the exactness of D is documented — a truncating step errs by 2 u, and the norms are sequential f32 sums (relative
+// error up to dim u / 2 each) that scale S / D — so the bound takes TWICE the figure, and the rule twice the bound: 512 dims give a
+// bound of 7.3e-5 and ask for a gap of 1.5e-4 between the N-th and the P-th score, 1024 dims 1.4e-4 and 2.8e-4.  A FULL pool whose
+// N-th score lies more than that above its P-th holds N rows that beat every row outside it in the exact order too, strictly; a pool
+// that is not full holds every (live) row; scores that are not finite are never safe.
+constexpr double f32_margin_bound(uint32_t dim) { return 2.0 * (double)(((uint64_t)dim + dim / 8 + 32) + 8) * (1.0 / 16777216.0); }
+constexpr bool f32_margin_safe(float nth, float pth, uint32_t dim, bool pool_full) {
+    if (!pool_full) return true;
+    const double a = (double)nth, b = (double)pth;
+    if (!(a - a == 0.0) || !(b - b == 0.0)) return false; // NaN or inf
+    return a - b > 2.0 * f32_margin_bound(dim);
+}
+// a masked query with at most P live rows is not tested (f16_margin_skipped)
+constexpr bool f32_masked_margin_safe(float nth, float pth, uint32_t dim, uint32_t live, uint32_t P) {
+    return f16_margin_skipped(live, P) || f32_margin_safe(nth, pth, dim, true);
+}
+
 // ---- which kernel scores a fused chunk of the code scan ----
 enum class ScanKernel {
     RESIDENT_PLANES, // query-resident scan of bit-plane codes (kernels_scan.hip flat_scan_q2_*)

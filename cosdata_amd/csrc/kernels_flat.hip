@@ -1100,7 +1100,8 @@ static int32_t flat_search_run(cos_index *ix, const float *queries, uint32_t B, 
     const bool planes = fp::bit_planes(ix->eng); // bit-plane storage: the operands are expanded to digits
     if (ix->eng != ENG_U8 && !planes)
         return cos_fail(COS_ERR_UNIMPLEMENTED, "flat search over codes implements u8, binary, quaternary and octal storage "
-                                               "(HalfPrecisionFP rows: cos_flat_search_f16_batch, cos_flat_search_f16_masked_batch)");
+                                               "(HalfPrecisionFP rows: cos_flat_search_f16_batch, cos_flat_search_f16_masked_batch; FullPrecisionFP rows: "
+                                               "cos_flat_search_f32_batch)");
     int32_t rc = cos_set_device(ix);
     if (rc) return rc;
     const u32 dim = ix->p.dim, n = ix->n;

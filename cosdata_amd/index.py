@@ -606,6 +606,26 @@ class HNSWIndex:
         del keep
         return (ids, scores, counts, st) if with_stats else (ids, scores, counts)
 
+    def flat_search_f32(self, queries, top_k: int, masks=None, query_mask=None, skip_deleted: bool = False, exact_mode: int = 1,
+                        with_stats: bool = False):
+        """The exhaustive scan of a FullPrecisionFP index (cos_flat_search_f32_batch): flat_search_f16's answer with the f32 arm of the
+        first-pass score, the reference-order f32 dot of the stored rows over the quantizer's norms; the best 5 * top_k rows are
+        reranked exactly as there.  masks as in flat_search_masked (none at all: every row); counts[b] = min(top_k, live rows of b).
+        exact_mode as in flat_search_f16.  top_k in [1, 102] (status 4 above); other storages raise status 1.
+        -> ids, scores, counts (+ CosFlatF16Stats)."""
+        q = self._queries(queries)
+        B = q.shape[0]
+        sm, keep = self._scan_mask(masks, query_mask, skip_deleted, B)
+        ids = np.full((B, top_k), 0xFFFFFFFF, np.uint32)
+        scores = np.zeros((B, top_k), np.float32)
+        counts = np.zeros(B, np.uint32)
+        opts = _lib.CosFlatF16Opts(struct_size=C.sizeof(_lib.CosFlatF16Opts), exact_mode=exact_mode)
+        st = _lib.CosFlatF16Stats(struct_size=C.sizeof(_lib.CosFlatF16Stats))
+        check(_lib.lib().cos_flat_search_f32_batch(self._h, _p(q), B, top_k, C.byref(sm) if sm is not None else None, C.byref(opts),
+                                                   _p(ids), _p(scores), _p(counts), C.byref(st)))
+        del keep
+        return (ids, scores, counts, st) if with_stats else (ids, scores, counts)
+
     def bruteforce_topk_masked(self, queries, k: int, masks=None, query_mask=None, skip_deleted: bool = False):
         """bruteforce_topk over a subset of the rows (cos_bruteforce_topk_masked); masks as in flat_search_masked.  -> ids, scores, counts:
         k may exceed a query's live rows, counts[b] = min(k, live rows of b) and the entries past it are unspecified."""

@@ -458,7 +458,7 @@ int32_t cos_index_last_brute_stats(cos_index *ix, cos_brute_stats *out);
  * Storages: UnsignedByte and SubByte of resolution 1 (binary), 2 (quaternary) and 3 (octal): their reference dots are integers, exact
  * in any summation order (dot_product_u8 / _binary / _quaternary / _octal), so the candidate set is the reference's bit for bit.
  * HalfPrecisionFP and FullPrecisionFP indexes: COS_ERR_UNIMPLEMENTED (their reference dots are order-dependent f32 chains; the handle
- * stays usable — cos_bruteforce_topk scans the raw rows of any index, cos_flat_search_f16_batch below serves HalfPrecisionFP rows).  Cosine divides by the norms the quantizer keeps (SubByte: of the
+ * stays usable — cos_flat_search_f16_batch below serves HalfPrecisionFP rows, cos_flat_search_f32_batch FullPrecisionFP rows).  Cosine divides by the norms the quantizer keeps (SubByte: of the
  * original vector), and a zero norm among the queries or the stored vectors is COS_ERR_CALCULATION for the call.
  * top_k in [1, 204]; above that COS_ERR_UNIMPLEMENTED (the handle stays usable).  A query keeps a pool of P
  * survivors, the smallest of 64, 128, 256, 512, 1024 with 5 * top_k <= P: top_k <= 12 runs the 64-key kernels,
@@ -550,6 +550,28 @@ int32_t cos_flat_search_f16_masked_batch(cos_index *ix, const float *queries, ui
 int32_t cos_flat_search_f16_dot_batch(cos_index *ix, const float *queries, uint32_t B, uint32_t top_k,
                                       const struct cos_scan_mask *mask /* NULL = every row */, const cos_flat_f16_opts *opts /* NULL = defaults */,
                                       uint32_t *out_ids, float *out_scores, uint32_t *out_counts, cos_flat_f16_stats *stats /* optional */);
+/* The exhaustive scan of a FullPrecisionFP index (cosine), masked or not: cos_flat_search_f16_batch's answer with the f32 arm of the
+ * first-pass score — every live row scored by the reference-order f32 dot of the stored f32 codes (dot_product_f32_simd: eight chains,
+ * a pairwise tree, an unfused tail) / (|q| * |x|) with the norms the quantizer keeps, sorted (desc, larger id first), the best
+ * N = 5 * top_k reranked exactly, top_k.  Ids, score bits and counts are those of the reference's exhaustive mode over an f32
+ * collection; with a mask, those of that mode over each query's live rows, with the original ids.  cos_bruteforce_topk answers a
+ * different question: it has no 5 * top_k cut and ranks by the rerank's cosine over the raw rows.
+ * mask: NULL (or n_masks == 0 with no flag) = every row, else the cos_scan_mask below with all its rules (COS_SCAN_SKIP_DELETED, bits
+ * at and past n ignored, the same COS_ERR_INVALID cases); out_counts[q] = min(top_k, live rows of q).  Pools, exact_mode, the opts and
+ * the stats are the f16 calls' (tiles_scanned / tiles_total as in the masked one).  An f32 MFMA GEMM generates the pool of P
+ * candidates, the smallest of 64 .. 1024 with 2 N <= P; a full pool is trusted only where its N-th MFMA score lies more than twice a
+ * derived error bound above its P-th (cosdata_amd/csrc/flat_plan.h f32_margin_safe: two f32 sums of dim rounded products), a masked
+ * query with at most P live rows is not tested, and a query that fails the rule has every live row scored in the reference's order.
+ * Refusals, each checked before anything is enqueued, the handle stays usable:
+ *   COS_ERR_STORAGE_MISMATCH  any storage but COS_STORAGE_F32
+ *   COS_ERR_UNIMPLEMENTED     top_k > 102 (cos_index_create refuses f32 rows with the dot-product metric)
+ *   COS_ERR_INVALID           top_k == 0, exact_mode > 2, a struct_size that is not the struct's size, the mask's cases
+ *   COS_ERR_CALCULATION       a zero norm among the queries, or among the rows that are live for at least one query of the call
+ * Workspace: the f16 calls' struct on the handle (an f32 handle has no other use for it), sized by each call's own P, released with
+ * the code scan's.  Out of scope: the shard set, top_k above 102 and masks that are already on the device. */
+int32_t cos_flat_search_f32_batch(cos_index *ix, const float *queries, uint32_t B, uint32_t top_k,
+                                  const struct cos_scan_mask *mask /* NULL = every row */, const cos_flat_f16_opts *opts /* NULL = defaults */,
+                                  uint32_t *out_ids, float *out_scores, uint32_t *out_counts, cos_flat_f16_stats *stats /* optional */);
 
 /* The two exhaustive scans over a SUBSET of the rows: per-query allow-lists and / or the handle's deleted set.
  * Query q's live set is mask query_mask[q] AND NOT the deleted rows (COS_SCAN_SKIP_DELETED); its result is exactly what the unmasked
