@@ -123,6 +123,12 @@ class CosSparseIndexStats(C.Structure):
                 ("postings", C.c_uint64), ("removed", C.c_uint64), ("raw_pairs", C.c_uint64), ("device_bytes", C.c_uint64)]
 
 
+class CosSparseBruteStats(C.Structure):
+    """cos_sparse_brute_stats: the last cos_sparse_bruteforce_topk on a learned-sparse handle"""
+    _fields_ = [("struct_size", C.c_uint32), ("queries", C.c_uint32), ("slow_queries", C.c_uint32), ("pool", C.c_uint32),
+                ("blocks", C.c_uint32), ("kernel_ms", C.c_float), ("raw_bytes", C.c_uint64)]
+
+
 class CosHybridRequest(C.Structure):
     """cos_hybrid_request: one mixed hybrid batch (every query names its arm; the three query sets are in query order)"""
     _fields_ = [("struct_size", C.c_uint32), ("B", C.c_uint32), ("arm", C.c_void_p), ("dense_queries", C.c_void_p),
@@ -162,6 +168,7 @@ ABI_SYMBOLS = [
     "cos_bm25_insert", "cos_bm25_delete", "cos_bm25_stats", "cos_bm25_download",
     "cos_bm25_search_batch", "cos_bm25_search_batch_device", "cos_rrf_fuse_batch", "cos_hybrid_search_batch", "cos_text_process", "cos_text_count_tokens", "cos_bm25_term_frequency", "cos_xxhash32", "cos_stem_english", "cos_sparse_create", "cos_sparse_build_csr", "cos_sparse_create_from_vectors", "cos_sparse_destroy", "cos_sparse_search_batch", "cos_sparse_last_stats", "cos_sparse_layout",
     "cos_sparse_set_max_candidates", "cos_sparse_max_candidates", "cos_sparse_search_batch_device",
+    "cos_sparse_bruteforce_topk", "cos_sparse_last_brute_stats",
     "cos_hybrid_create", "cos_hybrid_destroy", "cos_hybrid_search_mixed",
     "cos_sparse_insert", "cos_sparse_delete", "cos_sparse_stats", "cos_sparse_download", "cos_merge_topk_device", "cos_merge_topk_packed_device", "cos_hbm_probe",
     "cos_merge_lists_device", "cos_merge_lists_packed_device",
@@ -271,6 +278,8 @@ def lib():
         "cos_hybrid_destroy": [vp],
         "cos_hybrid_search_mixed": [vp, vp, vp, vp, C.POINTER(CosHybridRequest), vp, vp, vp],
         "cos_sparse_last_stats": [vp, vp],
+        "cos_sparse_bruteforce_topk": [vp, vp, vp, vp, u32, u32, vp, vp, vp],
+        "cos_sparse_last_brute_stats": [vp, C.POINTER(CosSparseBruteStats)],
         "cos_sparse_layout": [vp, C.POINTER(u32)],
         "cos_sparse_set_max_candidates": [vp, u32],
         "cos_sparse_max_candidates": [vp, C.POINTER(u32)],

@@ -19,6 +19,7 @@
 
 #include "engine_internal.h"
 #include "postings_update.h"
+#include "sparse_brute.h"
 #include "sparse_fold_plan.h"
 #include "topk_select.h"
 
@@ -897,6 +898,13 @@ struct cos_sparse {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool stats_pending = false; // last.kernel_ms is still to be read from the events
     cos_sparse_search_stats last{};
+    // cos_sparse_bruteforce_topk: the record of the ids given to cos_sparse_delete (a delete removes postings and leaves the raw rows,
+    // so nothing else on the handle says which rows are live), what cos_sparse_create found out about the raw CSR, the scan's workspace
+    std::vector<u32> h_dead; // bit v % 32 of word v / 32; grown to (n + 31) / 32 words by the scan
+    DevArr<u32> d_dead;
+    bool dead_dirty = true;  // d_dead is behind h_dead (or n has grown)
+    bool raw_offsets_ok = false, raw_rows_ascend = false;
+    SparseBruteWs brute;
     ~cos_sparse() {
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
@@ -1017,6 +1025,14 @@ extern "C" int32_t cos_sparse_create(int32_t device, uint32_t quantization_bits,
         if (e == hipSuccess) e = up(s->d_raw_vals, raw_vals, (size_t)rnnz);
         s->have_raw = true;
         s->raw_nnz = rnnz;
+        // what the exact scan relies on and the rerank never needed: offsets that bound every row, dimensions that strictly ascend
+        s->raw_offsets_ok = true;
+        s->raw_rows_ascend = true;
+        for (u32 v = 0; v < n_vectors; v++) {
+            if (row_offsets[v] > row_offsets[v + 1]) { s->raw_offsets_ok = false; break; }
+            for (u64 p = row_offsets[v] + 1; p < row_offsets[v + 1]; p++)
+                if (raw_dims[p] <= raw_dims[p - 1]) s->raw_rows_ascend = false;
+        }
     }
     if (e == hipSuccess) e = hipEventCreate(&s->ev0);
     if (e == hipSuccess) e = hipEventCreate(&s->ev1);
@@ -1386,6 +1402,41 @@ extern "C" int32_t cos_sparse_last_stats(cos_sparse *s, cos_sparse_search_stats 
     return COS_OK;
 }
 
+// The exact answer over the raw rows (kernels_sparse_brute.hip).  The handle's part: the limits, the lock, and the dead-id bitmap brought
+// up to date on the device; a failing call leaves the handle usable.
+extern "C" int32_t cos_sparse_bruteforce_topk(cos_sparse *s, const uint32_t *q_dims, const float *q_vals, const uint32_t *q_offsets, uint32_t B, uint32_t k,
+                                              uint32_t *out_ids, float *out_scores, uint32_t *out_counts) {
+    if (!s || !q_dims || !q_vals || !q_offsets || !out_ids || !out_scores || !out_counts || B == 0 || k == 0) return cos_fail(COS_ERR_INVALID, "bad argument");
+    std::lock_guard<std::mutex> guard(s->mu);
+    if (!s->have_raw) return cos_fail(COS_ERR_NOT_READY, "the exact scan needs the raw sparse vectors (cos_sparse_create row_offsets / raw_dims / raw_vals)");
+    if (k > SPARSE_BRUTE_MAX_K) return cos_fail(COS_ERR_UNIMPLEMENTED, "k must be <= %u (the widest pool)", SPARSE_BRUTE_MAX_K);
+    if (!s->raw_offsets_ok) return cos_fail(COS_ERR_INVALID, "the raw row offsets given to cos_sparse_create decrease: the rows cannot be scanned");
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t words = ((size_t)s->n + 31) / 32;
+    if (s->dead_dirty || s->d_dead.cap < words) {
+        HIP_TRY(hipStreamSynchronize(0)); // nothing of an earlier scan reads the bitmap any more
+        s->h_dead.resize(words, 0u);
+        HIP_TRY(s->d_dead.grow(words));
+        HIP_TRY(hipMemcpy(s->d_dead, s->h_dead.data(), words * 4, hipMemcpyHostToDevice));
+        s->dead_dirty = false;
+    }
+    const SparseBruteIndex ix{s->d_row_off, s->d_raw_dims, s->d_raw_vals, s->d_dead, s->n, s->raw_nnz, s->raw_rows_ascend};
+    return sparse_brute_topk(s->brute, ix, q_dims, q_vals, q_offsets, B, k, out_ids, out_scores, out_counts);
+}
+
+extern "C" int32_t cos_sparse_last_brute_stats(cos_sparse *s, cos_sparse_brute_stats *out) {
+    if (!s || !out || out->struct_size != sizeof(cos_sparse_brute_stats))
+        return cos_fail(COS_ERR_INVALID, "bad argument (struct_size must be sizeof(cos_sparse_brute_stats))");
+    std::lock_guard<std::mutex> guard(s->mu);
+    out->queries = s->brute.queries;
+    out->slow_queries = s->brute.slow_queries;
+    out->pool = s->brute.pool;
+    out->blocks = s->brute.blocks;
+    out->kernel_ms = s->brute.kernel_ms;
+    out->raw_bytes = s->brute.raw_bytes;
+    return COS_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Updates of the resident postings: cos_sparse_insert / cos_sparse_delete / cos_sparse_stats / cos_sparse_download.
 //   InvertedIndex::insert / InvertedIndexRoot::insert / InvertedIndexNode::insert    indexes/inverted/mod.rs:72-89, models/inverted_index.rs:273-289, :176-201
@@ -1695,6 +1746,7 @@ extern "C" int32_t cos_sparse_insert(cos_sparse *s, uint32_t m, const uint64_t *
     if (s->have_raw) {
         s->d_row_off = std::move(d_row_off); s->d_raw_dims = std::move(d_raw_dims); s->d_raw_vals = std::move(d_raw_vals);
         s->raw_nnz += np;
+        s->dead_dirty = true; // (more ids: more words)
     }
     s->h_dims.swap(new_dims);
     s->h_key_off.swap(new_ko);
@@ -1721,6 +1773,14 @@ extern "C" int32_t cos_sparse_delete(cos_sparse *s, const uint32_t *ids, const u
     if (nd > 0x7FFFFFFFull) return cos_fail(COS_ERR_UNIMPLEMENTED, "more than 2^31 - 1 pairs in one delete");
     std::lock_guard<std::mutex> g(s->mu);
     const u32 Q = 1u << s->bits, T = s->T;
+    // every id of a call that succeeds is dead to cos_sparse_bruteforce_topk, whatever its pairs removed: called in front of every
+    // successful return below, never by a failing call (the handle stays as it was)
+    auto mark_dead = [&]() {
+        s->h_dead.resize(((size_t)s->n + 31) / 32, 0u);
+        for (u32 i = 0; i < m; i++)
+            if (ids[i] < s->n) s->h_dead[ids[i] >> 5] |= 1u << (ids[i] & 31u);
+        s->dead_dirty = true;
+    };
     // (id, dimension, value) -> the key list on the host's tables; no node, no list for the key: left alone (inverted_index.rs:205-222)
     std::vector<u32> pair_ik, pair_len, pair_slot; // (id, key) interleaved; pair_slot = t * Q + key for the host's counts
     std::vector<u64> pair_begin;
@@ -1741,7 +1801,7 @@ extern "C" int32_t cos_sparse_delete(cos_sparse *s, const uint32_t *ids, const u
         }
     }
     const u32 np = (u32)pair_len.size();
-    if (!np) return COS_OK;
+    if (!np) { mark_dead(); return COS_OK; }
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipStreamSynchronize(0));
     const u64 nnz0 = s->h_key_off[(size_t)(T - 1) * (Q + 1) + Q];
@@ -1767,7 +1827,7 @@ extern "C" int32_t cos_sparse_delete(cos_sparse *s, const uint32_t *ids, const u
     u64 removed = 0;
     for (u32 i = 0; i < np; i++)
         if (found[i]) { dec[pair_slot[i]]++; removed++; }
-    if (!removed) return COS_OK; // nothing found: nothing swapped
+    if (!removed) { mark_dead(); return COS_OK; } // nothing found: nothing swapped
     std::vector<u64> new_ko((size_t)T * (Q + 1));
     {
         u64 run = 0;
@@ -1811,6 +1871,7 @@ extern "C" int32_t cos_sparse_delete(cos_sparse *s, const uint32_t *ids, const u
     s->h_dir.swap(new_dir);
     s->dir_rows = rows1;
     s->removed += removed; // (h_mult stays: an upper bound is all the COUNTED proof needs)
+    mark_dead();
     if (out_removed) *out_removed = removed;
     return COS_OK;
 }
@@ -1833,6 +1894,8 @@ extern "C" int32_t cos_sparse_stats(cos_sparse *s, cos_sparse_index_stats *out) 
     u64 bytes = (u64)s->d_ids.cap * 4 + s->d_keys.cap + (u64)s->d_pk.cap * 4 + (u64)std::max<size_t>(s->d_tile_dir.cap, 1) * 4; // postings + directory
     bytes += (u64)s->d_row_off.cap * 8 + (u64)s->d_raw_dims.cap * 4 + (u64)s->d_raw_vals.cap * 4;                                 // raw vectors
     for (const DevBuf *w : {&s->w_in, &s->w_part, &s->w_oi, &s->w_os, &s->w_oc}) bytes += w->cap; // search workspace
+    for (const DevBuf *w : {&s->brute.w_in, &s->brute.w_part, &s->brute.w_oi, &s->brute.w_os, &s->brute.w_oc}) bytes += w->cap; // the exact scan's
+    bytes += (u64)s->d_dead.cap * 4;
     out->device_bytes = bytes;
     return COS_OK;
 }

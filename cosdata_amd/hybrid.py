@@ -284,6 +284,24 @@ class InvertedIndex:
                                                  _p(ids), _p(scores), _p(counts)))
         return ids, scores, counts
 
+    def bruteforce_topk(self, q_dims, q_vals, q_offsets, k: int):
+        """cos_sparse_bruteforce_topk: the exact top k over the raw rows (the handle must keep them), scored and ordered as a rerank
+        scores and orders; ids [B][k], scores [B][k], counts [B] = min(k, live vectors sharing a dimension with the query)"""
+        qd, qv, qo = _c(q_dims, np.uint32), _c(q_vals, np.float32), _c(q_offsets, np.uint32)
+        B = qo.size - 1
+        ids = np.full((B, k), 0xFFFFFFFF, np.uint32)
+        scores = np.zeros((B, k), np.float32)
+        counts = np.zeros(B, np.uint32)
+        check(_lib.lib().cos_sparse_bruteforce_topk(self._h, _p(qd), _p(qv), _p(qo), B, k, _p(ids), _p(scores), _p(counts)))
+        return ids, scores, counts
+
+    def last_brute_stats(self) -> dict:
+        """cos_sparse_last_brute_stats as a dict: queries, slow_queries, pool, blocks, kernel_ms, raw_bytes"""
+        st = _lib.CosSparseBruteStats()
+        st.struct_size = C.sizeof(_lib.CosSparseBruteStats)
+        check(_lib.lib().cos_sparse_last_brute_stats(self._h, C.byref(st)))
+        return {name: getattr(st, name) for name, _ in st._fields_ if name != "struct_size"}
+
 
 def _sparse_search_batch_device(self, q_dims, q_vals, q_offsets, top_k: int, out_ids_ptr: int, out_scores_ptr: int, out_counts_ptr: int,
                                 early_terminate_threshold: float = 0.0, reranking_factor: int = 0, stream: int = 0):

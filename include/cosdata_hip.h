@@ -768,6 +768,37 @@ typedef struct cos_sparse_stats {
     uint64_t posting_bytes;
 } cos_sparse_search_stats; /* (the plain name cos_sparse_stats is the function further down: in C say `struct cos_sparse_stats`) */
 int32_t cos_sparse_last_stats(cos_sparse *s, cos_sparse_search_stats *out);
+
+/* The exact answer cos_sparse_search_batch approximates: the top k of every query over the RAW rows of a handle created with raw
+ * vectors, no posting list and no quantization involved.  Queries as in cos_sparse_search_batch; out_ids / out_scores [B][k],
+ * out_counts [B].
+ * Score of vector v: the raw-value rerank's — dp = 0.0f, then over the query's pairs IN THE ORDER GIVEN, where the row holds the
+ * dimension, dp = dp + row_val * q_val with one f32 multiply and one f32 add.  Bit for bit what a rerank returns for v.
+ * Candidates: the vectors that share at least one dimension with the query (one that shares none is no candidate, as it is none for
+ * the index) and whose id was never given to a successful cos_sparse_delete — every id of such a call is dead here, whatever its
+ * pairs removed.  Order: score descending by f32::total_cmp, larger id first: cos_sparse_search_batch's order with a rerank.
+ * out_counts[q] = min(k, candidates); slots behind it hold id 0xFFFFFFFF and score 0.
+ * No raw vectors on the handle -> COS_ERR_NOT_READY; k > 1024 -> COS_ERR_UNIMPLEMENTED; B > 65535, decreasing offsets or a handle
+ * whose raw row offsets decrease -> COS_ERR_INVALID; the handle stays usable after each.
+ * A query whose dimensions strictly ascend and that has at most 128 pairs is scanned by the streaming kernel; any other (unsorted,
+ * a repeated dimension, more pairs, dimension 0xFFFFFFFF), and every query on a handle whose raw rows do not strictly ascend, by a
+ * slower kernel with the same answer.  cos_sparse_last_brute_stats says how many those were.
+ * Takes the handle's lock; launches on the default stream and returns with the results on the host.  Workspace (grow-only): at most
+ * 64 MB of partial results + the results + one bit per vector. */
+int32_t cos_sparse_bruteforce_topk(cos_sparse *s, const uint32_t *q_dims, const float *q_vals, const uint32_t *q_offsets, uint32_t B,
+                                   uint32_t k, uint32_t *out_ids, float *out_scores, uint32_t *out_counts);
+/* The last cos_sparse_bruteforce_topk on this handle; all zero before the first.  (A call of its own: cos_sparse_search_stats carries
+ * no size and its callers allocate it, so it cannot grow.)  out->struct_size must be sizeof(cos_sparse_brute_stats) on entry. */
+typedef struct cos_sparse_brute_stats {
+    uint32_t struct_size;  /* in: sizeof(cos_sparse_brute_stats) */
+    uint32_t queries;      /* B of the call */
+    uint32_t slow_queries; /* queries the streaming kernel could not take */
+    uint32_t pool;         /* keys kept per query and workgroup: 64, 128, 256, 512 or 1024 */
+    uint32_t blocks;       /* workgroups of the two scan kernels */
+    float kernel_ms;       /* HIP-event time of the call's kernels */
+    uint64_t raw_bytes;    /* bytes of the raw CSR: what one pass over the rows reads */
+} cos_sparse_brute_stats;
+int32_t cos_sparse_last_brute_stats(cos_sparse *s, cos_sparse_brute_stats *out);
 /* Device layout of the handle's postings: 0 = a u32 id + a u8 key per posting (5 B), 1 = one packed u32 per posting
  * (key << 24 | id + 1; what cos_sparse_create builds whenever the collection holds fewer than 2^24 - 16384 vectors: measured in
  * round 5 at 0.453 ms against 0.540 ms per 256-query batch; tuning knob sparse_layout = 0 keeps the 5-byte layout).  Same results
@@ -807,6 +838,8 @@ int32_t cos_sparse_insert(cos_sparse *s, uint32_t m, const uint64_t *row_offsets
  * are ever reranked).  The reference marks a tombstone that every reader skips and nothing else of a list enters a score; here the
  * posting is removed (stream compaction into new arrays), which no search can tell apart — so a call streams the index once:
  * pass the ids of a transaction together.  A call that finds nothing swaps nothing.
+ * The handle also records every id < n of a call that succeeds (one bit per vector, on the host): cos_sparse_bruteforce_topk, which
+ * reads the raw rows and not the postings, never returns them.
  * Peak device memory during the call: old + new posting arrays + 1 B per 4 postings (claim flags and their prefix sums) + 21 B
  * per pair + the two tile directories. */
 int32_t cos_sparse_delete(cos_sparse *s, const uint32_t *ids, const uint64_t *row_offsets, uint32_t m, const uint32_t *raw_dims,
